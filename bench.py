@@ -12,10 +12,21 @@ bucket is all-reduced over RCCL once per step (gnn_rul_benchmarking_amd/dp.py).
 
 `--gpus N` from a bare shell (no WORLD_SIZE in the environment) re-launches itself under torch.distributed.run with N
 processes on 127.0.0.1.  The step loop is timed `--reps` times (each repetition = EXACTLY `--steps` steps between barriers +
-synchronize, max over ranks) and the MEDIAN repetition is reported.  For N > 1 the weak-scaling run (fixed per-GPU batch) is the
-headline and a strong-scaling run (the same global batch as N = 1, split over the ranks) is reported beside it.
+synchronize, max over ranks) and the MEDIAN repetition is reported; `--reps` is 1 by default (the run times exactly `--steps`
+steps) and 5 with `--full`.  For N > 1 the weak-scaling run (fixed per-GPU batch) is the headline.  A window of a few
+milliseconds reads high: the first ~100 steps of a process run up to 10 % slower (20 steps after 5 warm-up steps: 0.37-0.41 ms;
+1000 steps: 0.343 ms, the median of five repetitions of 1000 steps within 1 %).
 
-Rank 0 prints ONE JSON line.  Besides the driver contract it carries
+A plain run sets up, warms up, times the steps, writes `--dump-outputs` if given, and prints the line.  Everything else the
+benchmark measures is behind `--full`: the roofline legs, the CPU baseline, the other shapes, the other four families, the RMSE
+legs, and for N > 1 the strong-scaling run (the same global batch as N = 1, split over the ranks) and the `data_parallel` block.
+The `--no-*` options switch single legs of a `--full` run off.
+
+`--dump-outputs DIR` writes what the timed path computed in its last step as DIR/<name>.npy (float32, float64 for integer
+counters): `loss` (what `update` returned), `pred` (that step's predictions) and `state.<key>` (the model's parameters and
+BatchNorm buffers after the step).  The inputs are seeded, so two builds run with the same arguments can be compared file by file.
+
+Rank 0 prints ONE JSON line.  Besides the driver contract a `--full` run carries
   roofline       dominant kernel of the step (picked live by HIP-event timing of each phase kernel).  `achieved` / `frac` are on
                  SURVEY section 8(d)'s ALGORITHMIC bytes (4 N P + 4 = 1684 B per sample at 14x30: the window in, one float out);
                  `frac_traffic` is the same launch priced on the bytes the phase really moves (its inter-phase tensors included);
@@ -56,7 +67,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=30)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--reps", type=int, default=5, help="repetitions of the timed step loop; the median is reported")
+    ap.add_argument("--reps", type=int, default=None,
+                    help="repetitions of the timed step loop; the median is reported (default 1, with --full 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (roofline, CPU baseline, other shapes, families, RMSE; for N > 1 the "
+                         "strong-scaling run and the data_parallel block); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the loss, predictions and model state of the last timed step as DIR/<name>.npy")
     ap.add_argument("--batch", type=int, default=65536, help="per-GPU batch (weak scaling) = global batch of the strong-scaling run")
     ap.add_argument("--sync-bn", action="store_true",
                     help="data parallel with synchronised BatchNorm: the N-GPU step is the 1-GPU function of the global batch "
@@ -65,7 +82,8 @@ def parse():
                     help="with --sync-bn: the BatchNorm reductions through the process group (RCCL: a host callback per collective) or as "
                          "device-side one-shot all-reduces over IPC-mapped mailboxes (csrc/peer_comm.hip; one node)")
     ap.add_argument("--scaling", choices=["weak", "strong", "both"], default="both",
-                    help="N > 1: weak = fixed per-GPU batch (headline), strong = fixed global batch split over the ranks")
+                    help="N > 1: weak = fixed per-GPU batch (headline), strong = fixed global batch split over the ranks; "
+                         "both = weak, and with --full the strong-scaling run beside it")
     ap.add_argument("--patch-size", type=int, default=30, help="window length (BASELINE.json: 30)")
     ap.add_argument("--dropout", type=float, default=0.2)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -84,7 +102,30 @@ def parse():
     ap.add_argument("--family", default="ST_GCN", choices=["ST_GCN", "ASTGCNN", "FC_STGNN", "STMSGCN", "HAGCN", "STGNN", "RGCNU", "STNet", "SAGCN", "STAGNN"],
                     help="ST_GCN (default) is the headline benchmark; the others run the same contract on the SURVEY section 8d "
                          "configuration of that model family")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.reps is None:
+        args.reps = 5 if args.full else 1
+    if not args.full:
+        args.no_roofline = args.no_cpu_baseline = args.no_families = args.no_rmse = args.no_other_shapes = True
+    if args.dump_outputs and args.family != "ST_GCN":
+        ap.error("--dump-outputs is implemented for the ST_GCN headline only")
+    return args
+
+
+def dump_outputs(path, algo, loss):
+    """--dump-outputs: the loss ``update`` returned in the last timed step, that step's predictions and the model state it left,
+    as float32 .npy files (float64 for integer counters); an array over 4M elements is written as a fixed, seeded sample of 4M."""
+    import numpy as np
+    arrays = {"loss": torch.as_tensor(loss).reshape(1), "pred": algo.model._pred_buf}
+    arrays.update(("state." + k, v) for k, v in algo.model.state_dict().items())
+    os.makedirs(path, exist_ok=True)
+    cap = 1 << 22
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy()
+        a = a.astype(np.float32 if a.dtype.kind == "f" and a.dtype != np.float64 else np.float64)
+        if a.size > cap:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def finish(line, use_dist, dist):
@@ -275,8 +316,10 @@ def main():
     els, final_loss, Xs, ys = run(B if weak else max(1, B // world))
     per_rank = B if weak else max(1, B // world)
     el = statistics.median(els)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, algo, final_loss)      # (before any other leg steps the model; state_dict() checks the guard)
     strong = None
-    if world > 1 and args.scaling == "both":
+    if world > 1 and args.scaling == "both" and args.full:
         sb = max(1, B // world)
         sels, _, _, _ = run(sb)
         sel = statistics.median(sels)
@@ -286,7 +329,7 @@ def main():
     # a step the f16 range guard rejected would have been DROPPED (loss kept on the device): never silently
     algo.check_guard()
     dp_diag = None
-    if use_dist:
+    if use_dist and args.full:
         dp_diag = data_parallel_diagnostics(algo, Xs, ys, args, dist, dev, world, el / args.steps * 1e3)
     from gnn_rul_benchmarking_amd import _lib as _L
     on_mx = algo.model._last_chain == _L.STEP_MX

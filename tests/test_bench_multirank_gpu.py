@@ -27,7 +27,7 @@ def test_bench_two_ranks_prints_one_contract_line(extra):
     env = dict(os.environ, RULGNN_BENCH_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-           "--batch", "4096", "--reps", "2", "--no-roofline", "--no-cpu-baseline", "--no-families", "--no-rmse"] + extra
+           "--batch", "4096", "--reps", "2", "--full", "--no-roofline", "--no-cpu-baseline", "--no-families", "--no-rmse"] + extra
     res = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.startswith("{")]

@@ -1,10 +1,11 @@
 #!/bin/bash
 # usage (GPU box, repo root): tools/profile_forward.sh <tag>   -- the fused eval forward kernels alone, batch 65536 and 1M:
 # rocprofv3 kernel stats, then FETCH_SIZE / WRITE_SIZE in separate passes (HBM traffic per launch), then the SQ counter passes
+out=${PROFILE_OUT:-profile_out}      # where the profiles land (relative to the repo root, git-ignored)
 tag=${1:-r03}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for B in 65536 1048576; do
-  d=gpurun_out/$tag/fwd_$B
+  d=$out/$tag/fwd_$B
   mkdir -p $d
   rocprofv3 --kernel-trace --stats -d $d/stats -o s --output-format csv -- python tools/run_forward_once.py $B > /dev/null 2>&1
   rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $d/fetch -o f --output-format csv -- python tools/run_forward_once.py $B > /dev/null 2>&1
