@@ -49,6 +49,19 @@ static int check_ptrs(std::initializer_list<const void*> ps) {
     return RULGNN_OK;
 }
 
+// The optimizer block of a family's fused step (rulgnn_<family>_fwdbwd_f32): a step count or a device step state, the step's own
+// parameter buffer, then the Adam pointers.
+static int check_adam(const rulgnn_adam_args* opt, const float* params) {
+    if ((opt->step < 1 && !opt->step_state) || opt->params != params) return RULGNN_EINVAL;
+    return check_ptrs({opt->params, opt->exp_avg, opt->exp_avg_sq});
+}
+
+// Plain Adam over the flat floats [first, first + n) behind a family's step kernels.
+static int adam_tail(const rulgnn_adam_args* opt, const float* grads, int64_t first, int64_t n, hipStream_t st) {
+    return adam_step(opt->params + first, grads + first, opt->exp_avg + first, opt->exp_avg_sq + first, n, opt->step, opt->lr, opt->beta1,
+                     opt->beta2, opt->eps, opt->weight_decay, 1.0f, st, opt->step_state);
+}
+
 // Path selection.  The fused row-mapped kernels cover num_patch <= 64 as long as one wavefront's input tile
 // fits its LDS staging area (and, for training, num_layers <= 3 / <= 2); everything else valid goes to the
 // tiled path, which has no such limits.
@@ -391,16 +404,11 @@ int rulgnn_stmsgcn_fwdbwd_f32(const rulgnn_stmsgcn_shape* shape, const rulgnn_st
     int rc = check_stmsgcn(shape, args, true, true);
     if (rc != RULGNN_OK) return rc;
     if (args->dpred) return RULGNN_EINVAL;                 // the fused call is the MSE step
-    if (opt) {
-        if ((opt->step < 1 && !opt->step_state) || opt->params != args->params) return RULGNN_EINVAL;
-        rc = check_ptrs({opt->params, opt->exp_avg, opt->exp_avg_sq});
-        if (rc != RULGNN_OK) return rc;
-    }
+    if (opt && (rc = check_adam(opt, args->params)) != RULGNN_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     rc = stmsgcn_run(shape, args, 3, st);
     if (rc != RULGNN_OK || !opt) return rc;
-    return adam_step(opt->params, args->grads, opt->exp_avg, opt->exp_avg_sq, stmsgcn_param_count(shape), opt->step, opt->lr,
-                     opt->beta1, opt->beta2, opt->eps, opt->weight_decay, 1.0f, st, opt->step_state);
+    return adam_tail(opt, args->grads, 0, stmsgcn_param_count(shape), st);
 }
 
 
@@ -450,12 +458,8 @@ int rulgnn_astgcnn_fwdbwd_f32(const rulgnn_astgcnn_shape* shape, const rulgnn_as
     int rc = check_astgcnn(shape, args, true, true);
     if (rc != RULGNN_OK) return rc;
     if (args->dpred) return RULGNN_EINVAL;
-    if (opt) {
-        if ((opt->step < 1 && !opt->step_state) || opt->params != args->params) return RULGNN_EINVAL;
-        rc = check_ptrs({opt->params, opt->exp_avg, opt->exp_avg_sq});
-        if (rc != RULGNN_OK) return rc;
-        if (opt->bn_stats && (!args->bn_batch || (reinterpret_cast<uintptr_t>(opt->bn_stats) & 3))) return RULGNN_EINVAL;
-    }
+    if (opt && (rc = check_adam(opt, args->params)) != RULGNN_OK) return rc;
+    if (opt && opt->bn_stats && (!args->bn_batch || (reinterpret_cast<uintptr_t>(opt->bn_stats) & 3))) return RULGNN_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
     // (plain batch statistics: the running-statistics update rides in the step's finalize kernel)
     const bool tail_bn = opt && opt->bn_stats && args->training && args->bn_moment_weight == 0.f;
@@ -468,8 +472,7 @@ int rulgnn_astgcnn_fwdbwd_f32(const rulgnn_astgcnn_shape* shape, const rulgnn_as
     rc = astgcnn_run(shape, args, 3, st, nullptr, tail_bn ? opt->bn_stats : nullptr, tail_bn ? opt->bn_momentum : 0.f, try_fuse ? &fuse : nullptr);
     if (rc != RULGNN_OK || !opt) return rc;
     if (!(try_fuse && fuse.gbase))
-        rc = adam_step(opt->params, args->grads, opt->exp_avg, opt->exp_avg_sq, astgcnn_param_count(shape), opt->step, opt->lr,
-                       opt->beta1, opt->beta2, opt->eps, opt->weight_decay, 1.0f, st, opt->step_state);
+        rc = adam_tail(opt, args->grads, 0, astgcnn_param_count(shape), st);
     if (rc != RULGNN_OK || !opt->bn_stats || tail_bn) return rc;
     return astgcnn_bn_running_update(shape, opt->bn_stats, args->bn_batch, shape->batch * (int64_t)shape->time_length,
                                      opt->bn_momentum, args->bn_moment_weight > 0.f ? 1 : 0, st);
@@ -556,12 +559,8 @@ int rulgnn_fcstgnn_fwdbwd_f32(const rulgnn_fcstgnn_shape* shape, const rulgnn_fc
     int rc = check_fcstgnn(shape, args, true, true);
     if (rc != RULGNN_OK) return rc;
     if (args->dpred) return RULGNN_EINVAL;
-    if (opt) {
-        if ((opt->step < 1 && !opt->step_state) || opt->params != args->params) return RULGNN_EINVAL;
-        rc = check_ptrs({opt->params, opt->exp_avg, opt->exp_avg_sq});
-        if (rc != RULGNN_OK) return rc;
-        if (opt->bn_stats && (!args->bn_batch || (reinterpret_cast<uintptr_t>(opt->bn_stats) & 3))) return RULGNN_EINVAL;
-    }
+    if (opt && (rc = check_adam(opt, args->params)) != RULGNN_OK) return rc;
+    if (opt && opt->bn_stats && (!args->bn_batch || (reinterpret_cast<uintptr_t>(opt->bn_stats) & 3))) return RULGNN_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const bool tail_bn = opt && opt->bn_stats && args->training && args->bn_moment_weight == 0.f;
     // (host-side step count: the step's last kernel applies the optimizer itself -- adam_device.hpp; a device step state keeps the launch)
@@ -574,8 +573,7 @@ int rulgnn_fcstgnn_fwdbwd_f32(const rulgnn_fcstgnn_shape* shape, const rulgnn_fc
     rc = fcstgnn_run(shape, args, 3, st, nullptr, tail_bn ? opt->bn_stats : nullptr, tail_bn ? opt->bn_momentum : 0.f, fused_adam ? &fuse : nullptr);
     if (rc != RULGNN_OK || !opt) return rc;
     if (!fused_adam)
-        rc = adam_step(opt->params, args->grads, opt->exp_avg, opt->exp_avg_sq, fcstgnn_param_count(shape), opt->step, opt->lr,
-                       opt->beta1, opt->beta2, opt->eps, opt->weight_decay, 1.0f, st, opt->step_state);
+        rc = adam_tail(opt, args->grads, 0, fcstgnn_param_count(shape), st);
     if (rc != RULGNN_OK || !opt->bn_stats || tail_bn) return rc;
     return fcstgnn_bn_running_update(shape, opt->bn_stats, args->bn_batch, opt->bn_momentum, args->bn_moment_weight > 0.f ? 1 : 0, st);
 }
@@ -667,17 +665,12 @@ int rulgnn_stconv_fwdbwd_f32(const rulgnn_stconv_shape* shape, const rulgnn_astg
     int rc = check_stconv(shape, args, true, true);
     if (rc != RULGNN_OK) return rc;
     if (args->dpred) return RULGNN_EINVAL;
-    if (opt) {
-        if ((opt->step < 1 && !opt->step_state) || opt->params != args->params) return RULGNN_EINVAL;
-        rc = check_ptrs({opt->params, opt->exp_avg, opt->exp_avg_sq});
-        if (rc != RULGNN_OK) return rc;
-        if (opt->bn_stats && (!args->bn_batch || (reinterpret_cast<uintptr_t>(opt->bn_stats) & 3))) return RULGNN_EINVAL;
-    }
+    if (opt && (rc = check_adam(opt, args->params)) != RULGNN_OK) return rc;
+    if (opt && opt->bn_stats && (!args->bn_batch || (reinterpret_cast<uintptr_t>(opt->bn_stats) & 3))) return RULGNN_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
     rc = stconv_run(shape, args, 3, st);
     if (rc != RULGNN_OK || !opt) return rc;
-    rc = adam_step(opt->params, args->grads, opt->exp_avg, opt->exp_avg_sq, stconv_param_count(shape), opt->step, opt->lr, opt->beta1,
-                   opt->beta2, opt->eps, opt->weight_decay, 1.0f, st, opt->step_state);
+    rc = adam_tail(opt, args->grads, 0, stconv_param_count(shape), st);
     if (rc != RULGNN_OK || !opt->bn_stats) return rc;
     return stconv_bn_running_update(shape, opt->bn_stats, args->bn_batch, shape->batch * (int64_t)shape->time_length, opt->bn_momentum,
                                     args->bn_moment_weight > 0.f ? 1 : 0, st);
@@ -760,16 +753,11 @@ int rulgnn_stgnn_fwdbwd_f32(const rulgnn_stgnn_shape* shape, const rulgnn_stmsgc
     int rc = check_stgnn(shape, args, true, true);
     if (rc != RULGNN_OK) return rc;
     if (args->dpred) return RULGNN_EINVAL;
-    if (opt) {
-        if ((opt->step < 1 && !opt->step_state) || opt->params != args->params) return RULGNN_EINVAL;
-        rc = check_ptrs({opt->params, opt->exp_avg, opt->exp_avg_sq});
-        if (rc != RULGNN_OK) return rc;
-    }
+    if (opt && (rc = check_adam(opt, args->params)) != RULGNN_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     rc = stgnn_run(shape, args, 3, st);
     if (rc != RULGNN_OK || !opt) return rc;
-    return adam_step(opt->params, args->grads, opt->exp_avg, opt->exp_avg_sq, stgnn_param_count(shape), opt->step, opt->lr, opt->beta1,
-                     opt->beta2, opt->eps, opt->weight_decay, 1.0f, st, opt->step_state);
+    return adam_tail(opt, args->grads, 0, stgnn_param_count(shape), st);
 }
 
 // ---- STNet ----------------------------------------------------------------------------------------------------------------------
@@ -809,17 +797,12 @@ int rulgnn_stnet_fwdbwd_f32(const rulgnn_stnet_shape* shape, const rulgnn_stnet_
     int rc = check_stnet(shape, args, true);
     if (rc != RULGNN_OK) return rc;
     if (args->dpred || (!args->y && shape->batch > 0)) return RULGNN_EINVAL;
-    if (opt) {
-        if ((opt->step < 1 && !opt->step_state) || opt->params != args->params) return RULGNN_EINVAL;
-        rc = check_ptrs({opt->params, opt->exp_avg, opt->exp_avg_sq});
-        if (rc != RULGNN_OK) return rc;
-    }
+    if (opt && (rc = check_adam(opt, args->params)) != RULGNN_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     rc = stnet_run(shape, args, 3, st);
     if (rc != RULGNN_OK || !opt) return rc;
     // cnn.{weight, bias} (the first 3 entries) have no gradient in the reference (`grad is None`): torch's Adam leaves them untouched
-    return adam_step(opt->params + 3, args->grads + 3, opt->exp_avg + 3, opt->exp_avg_sq + 3, stnet_param_count(shape) - 3, opt->step,
-                     opt->lr, opt->beta1, opt->beta2, opt->eps, opt->weight_decay, 1.0f, st, opt->step_state);
+    return adam_tail(opt, args->grads, 3, stnet_param_count(shape) - 3, st);
 }
 
 // ---- SAGCN ----------------------------------------------------------------------------------------------------------------------
@@ -860,16 +843,11 @@ int rulgnn_sagcn_fwdbwd_f32(const rulgnn_sagcn_shape* shape, const rulgnn_sagcn_
     int rc = check_sagcn(shape, args, true);
     if (rc != RULGNN_OK) return rc;
     if (args->dpred || (!args->y && shape->batch > 0)) return RULGNN_EINVAL;
-    if (opt) {
-        if ((opt->step < 1 && !opt->step_state) || opt->params != args->params) return RULGNN_EINVAL;
-        rc = check_ptrs({opt->params, opt->exp_avg, opt->exp_avg_sq});
-        if (rc != RULGNN_OK) return rc;
-    }
+    if (opt && (rc = check_adam(opt, args->params)) != RULGNN_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     rc = sagcn_run(shape, args, 3, st);
     if (rc != RULGNN_OK || !opt) return rc;
-    return adam_step(opt->params, args->grads, opt->exp_avg, opt->exp_avg_sq, sagcn_param_count(shape), opt->step, opt->lr, opt->beta1,
-                     opt->beta2, opt->eps, opt->weight_decay, 1.0f, st, opt->step_state);
+    return adam_tail(opt, args->grads, 0, sagcn_param_count(shape), st);
 }
 
 int rulgnn_sgemm_mode(int32_t mode) {
@@ -918,16 +896,11 @@ int rulgnn_stagnn_fwdbwd_f32(const rulgnn_stagnn_shape* shape, const rulgnn_stag
     int rc = check_stagnn(shape, args, true);
     if (rc != RULGNN_OK) return rc;
     if (args->dpred || (!args->y && shape->batch > 0)) return RULGNN_EINVAL;
-    if (opt) {
-        if ((opt->step < 1 && !opt->step_state) || opt->params != args->params) return RULGNN_EINVAL;
-        rc = check_ptrs({opt->params, opt->exp_avg, opt->exp_avg_sq});
-        if (rc != RULGNN_OK) return rc;
-    }
+    if (opt && (rc = check_adam(opt, args->params)) != RULGNN_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     rc = stagnn_run(shape, args, 3, st);
     if (rc != RULGNN_OK || !opt) return rc;
-    return adam_step(opt->params, args->grads, opt->exp_avg, opt->exp_avg_sq, stagnn_param_count(shape), opt->step, opt->lr, opt->beta1,
-                     opt->beta2, opt->eps, opt->weight_decay, 1.0f, st, opt->step_state);
+    return adam_tail(opt, args->grads, 0, stagnn_param_count(shape), st);
 }
 
 // ---- plain GEMM -------------------------------------------------------------------------------------------------------------------
@@ -1049,18 +1022,13 @@ int rulgnn_rgcnu_fwdbwd_f32(const rulgnn_rgcnu_shape* shape, const rulgnn_rgcnu_
     int rc = check_rgcnu(shape, args, true, true);
     if (rc != RULGNN_OK) return rc;
     if (args->dpred || (!args->y && shape->batch > 0)) return RULGNN_EINVAL;
-    if (opt) {
-        if ((opt->step < 1 && !opt->step_state) || opt->params != args->params) return RULGNN_EINVAL;
-        rc = check_ptrs({opt->params, opt->exp_avg, opt->exp_avg_sq});
-        if (rc != RULGNN_OK) return rc;
-    }
+    if (opt && (rc = check_adam(opt, args->params)) != RULGNN_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     rc = rgcnu_run(shape, args, 3, st);
     if (rc != RULGNN_OK || !opt) return rc;
     // the second head (fc2, the last E*L + 1 entries) has no gradient in the reference (`grad is None`): torch's Adam leaves it untouched
     const int64_t live = rgcnu_param_count(shape) - ((int64_t)shape->encoder_hidden_dim * shape->time_length + 1);
-    return adam_step(opt->params, args->grads, opt->exp_avg, opt->exp_avg_sq, live, opt->step, opt->lr, opt->beta1,
-                     opt->beta2, opt->eps, opt->weight_decay, 1.0f, st, opt->step_state);
+    return adam_tail(opt, args->grads, 0, live, st);
 }
 
 size_t rulgnn_gru_workspace_bytes(const rulgnn_gru_shape* shape) { return gru_workspace_bytes(shape); }

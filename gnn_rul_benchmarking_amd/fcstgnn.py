@@ -80,24 +80,6 @@ BN_NAMES = ("nonlin_map.conv_block1.1", "nonlin_map.conv_block2.1", "nonlin_map2
             "MPNN2.MPNN.bn1")
 
 
-class _TrainFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, model, x2d, *params):
-        model._step += 1
-        ctx.step = model._step
-        pred = model._run_forward(x2d, True, model._step)
-        model._after_train_forward()
-        ctx.model, ctx.x2d = model, x2d
-        return pred.clone().view(-1, 1)
-
-    @staticmethod
-    def backward(ctx, dpred):
-        model = ctx.model
-        grads = model._run_backward(ctx.x2d, dpred.contiguous().view(-1).float(), ctx.step)
-        out = [grads[off:off + n].view(shape).clone() for (off, n, shape) in model._slices]
-        return (None, None, *out)
-
-
 class FC_STGNN_RUL(FlatModule):
     def __init__(self, patch_size, num_patch, encoder_time_out, encoder_hidden_dim, encoder_out_dim, encoder_conv_kernel,
                  hidden_dim, num_sequential, num_node, num_windows):
@@ -121,7 +103,7 @@ class FC_STGNN_RUL(FlatModule):
 
         # flat layout = named_parameters() order (the order include/rulgnn.h documents)
         self._bn_ch = [dict(self.named_buffers())[n + ".running_mean"].numel() for n in BN_NAMES]
-        self._bn = self._bn_batch = self._pred_buf = self._ws = None
+        self._bn = self._bn_batch = None
         self.side_stream = PL.SideStream()
         self._step = 0
         self._seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
@@ -159,11 +141,12 @@ class FC_STGNN_RUL(FlatModule):
         self._bn, self._nbt = bn, nbt
         self._bn_batch = torch.zeros(total, dtype=torch.float32, device=dev)
 
-    def _reset_caches(self):
-        super()._reset_caches()
-        self._pred_buf = self._ws = None
-
     # ---- C-ABI calls -----------------------------------------------------------------------------------
+    c_family, Args = "fcstgnn", _lib.FcstgnnArgs
+    not_covered = ("FC_STGNN kernels do not cover this configuration (encoder_time_out must be the second conv's output length, "
+                   "num_windows the windows of the two blocks; num_node <= 20, hidden_dim <= 32, encoder_out_dim <= 64, "
+                   "encoder_hidden_dim <= 16, encoder_conv_kernel <= 4)")
+
     def _shape(self, batch):
         c = self.cfg
         return _lib.FcstgnnShape(batch, c["patch_size"], c["num_patch"], c["encoder_time_out"], c["encoder_hidden_dim"],
@@ -171,11 +154,7 @@ class FC_STGNN_RUL(FlatModule):
                                  c["num_windows"])
 
     def _check_input(self, x):
-        if not x.is_cuda:
-            raise RuntimeError("FC_STGNN_RUL runs on the HIP kernels only: input must be a CUDA (ROCm) tensor; "
-                               "there is no CPU fallback")
-        if x.device != self._flat.device:
-            raise RuntimeError(f"input on {x.device} but model on {self._flat.device}")
+        self._require_device(x)
         c = self.cfg
         if x.dim() != 3 or x.size(1) != c["num_node"] or x.size(2) != c["num_patch"] * c["patch_size"]:
             raise RuntimeError(f"shape '[{x.size(0)}, {c['num_node']}, {c['num_patch']}, {c['patch_size']}]' is invalid for input "
@@ -183,32 +162,14 @@ class FC_STGNN_RUL(FlatModule):
         return x.reshape(x.size(0), -1).contiguous().float()
 
     def _args(self, shp, x2d, training, step, y=None, dpred=None, global_batch=None, sample_offset=0, moments_to_bucket=False):
-        B = x2d.size(0)
-        ent = self._workspace_entry(B, lambda: _lib.load().rulgnn_fcstgnn_workspace_bytes(C.byref(shp)),
-                                    "FC_STGNN kernels do not cover this configuration (encoder_time_out must be the second conv's "
-                                    "output length, num_windows the windows of the two blocks; num_node <= 20, hidden_dim <= 32, "
-                                    "encoder_out_dim <= 64, encoder_hidden_dim <= 16, encoder_conv_kernel <= 4)",
-                                    make=lambda dev: (torch.empty(B, dtype=torch.float32, device=dev),))
-        self._ws, self._pred_buf = ent
-        a = _lib.FcstgnnArgs()
-        a.x = x2d.data_ptr()
-        a.y = y.data_ptr() if y is not None else None
-        a.dpred = dpred.data_ptr() if dpred is not None else None
-        a.params = self._flat.data_ptr()
-        a.grads = self._grad_flat.data_ptr()
-        a.pred = self._pred_buf.data_ptr()
-        a.loss = self._grad_flat.data_ptr() + 4 * self._count
+        a = super()._args(shp, x2d, y, dpred, global_batch)
         a.bn_stats = self._bn.data_ptr()
-        gb = B if global_batch is None else int(global_batch)
         if moments_to_bucket:
             a.bn_batch = self._grad_flat.data_ptr() + 4 * (self._count + 1)
-            a.bn_moment_weight = B / float(gb)
+            a.bn_moment_weight = x2d.size(0) / float(a.global_batch)
         else:
             a.bn_batch = self._bn_batch.data_ptr()
             a.bn_moment_weight = 0.0
-        a.workspace = self._ws.data_ptr()
-        a.workspace_bytes = self._ws.numel()
-        a.global_batch = gb
         a.sample_offset = int(sample_offset)
         a.dropout_p = float(self.dropout_p)
         a.seed = self._seed
@@ -220,18 +181,6 @@ class FC_STGNN_RUL(FlatModule):
             raise RuntimeError(f"compute_dtype must be 'f32' or 'bf16', not {self.compute_dtype!r}")
         a.compute_dtype = _lib.DTYPE_BF16 if self.compute_dtype == "bf16" else _lib.DTYPE_F32
         return a
-
-    def _run_forward(self, x2d, training, step=0):
-        shp = self._shape(x2d.size(0))
-        a = self._args(shp, x2d, training, step)
-        _lib.check(_lib.load().rulgnn_fcstgnn_forward_f32(C.byref(shp), C.byref(a), _stream()), "rulgnn_fcstgnn_forward_f32")
-        return self._pred_buf
-
-    def _run_backward(self, x2d, dpred, step):
-        shp = self._shape(x2d.size(0))
-        a = self._args(shp, x2d, True, step, dpred=dpred)
-        _lib.check(_lib.load().rulgnn_fcstgnn_backward_f32(C.byref(shp), C.byref(a), _stream()), "rulgnn_fcstgnn_backward_f32")
-        return self._grad_flat
 
     def _after_train_forward(self, batch=None, from_bucket_moments=False, from_bucket_stats=False):
         """BatchNorm side effects of a training forward.  ``batch``: the (global) batch the statistics were taken over;
@@ -248,21 +197,15 @@ class FC_STGNN_RUL(FlatModule):
     def fused_mse_step(self, x, y, optimizer=None, global_batch=None, sample_offset=0, update_running_stats=True,
                        moments_to_bucket=False):
         """train forward + MSE + backward (+ Adam and the running statistics with ``optimizer``) in one C call."""
-        x2d = self._check_input(x)
-        yv = y.reshape(-1).contiguous().float()
-        if yv.numel() != x2d.size(0):
-            raise RuntimeError("target size mismatch")
+        x2d, yv = self._step_inputs(x, y)
         self._step += 1
-        shp = self._shape(x2d.size(0))
-        a = self._args(shp, x2d, True, self._step, y=yv, global_batch=global_batch, sample_offset=sample_offset,
-                       moments_to_bucket=moments_to_bucket)
-        o = self._adam_args(optimizer, bn=self._bn)
-        _lib.check(_lib.load().rulgnn_fcstgnn_fwdbwd_f32(C.byref(shp), C.byref(a), o, _stream()), "rulgnn_fcstgnn_fwdbwd_f32")
+        out = self._fused_step(x2d, yv, optimizer, global_batch, True, self._step, bn=self._bn, sample_offset=sample_offset,
+                               moments_to_bucket=moments_to_bucket)
         if optimizer is not None:
             self._nbt_pending += 1
         elif update_running_stats:
             self._after_train_forward(x2d.size(0))
-        return self._pred_buf, self._grad_flat[self._count]
+        return out
 
     def sync_bn_schedule(self):
         """float64 counts of the all-reduces one synchronised-BatchNorm step issues, in order (dp.py: a rank with an empty shard joins
@@ -275,15 +218,12 @@ class FC_STGNN_RUL(FlatModule):
         inside the workspace and must SUM it over the ranks in place, in stream order.  Fills ``self.bucket`` such that a SUM over the
         ranks is the global-batch gradient / loss (the BatchNorm scale / shift gradients are global sums on every rank and enter
         multiplied by ``bn_param_grad_scale``), and ``self._bn_batch`` with the global (mean, biased variance)."""
-        x2d = self._check_input(x)
-        yv = y.reshape(-1).contiguous().float()
-        if yv.numel() != x2d.size(0):
-            raise RuntimeError("target size mismatch")
+        x2d, yv = self._step_inputs(x, y)
         self._step += 1
         shp = self._shape(x2d.size(0))
+        self._tape.mark(x2d.size(0))
         a = self._args(shp, x2d, True, self._step, y=yv, global_batch=global_batch, sample_offset=sample_offset)
-        ws = self._ws
-        cb, user, failure = _lib.allreduce_callback(allreduce, ws)
+        cb, user, failure = _lib.allreduce_callback(allreduce, self._ws)
         rc = _lib.load().rulgnn_fcstgnn_fwdbwd_syncbn_f32(C.byref(shp), C.byref(a), float(bn_param_grad_scale), cb, user, _stream())
         if failure:
             raise failure[0]
@@ -297,11 +237,9 @@ class FC_STGNN_RUL(FlatModule):
             if self.training:
                 raise RuntimeError("training forward needs a non-empty batch")
             return torch.empty(0, 1, dtype=torch.float32, device=x2d.device)
-        if self.training:
-            if torch.is_grad_enabled():
-                return _TrainFunction.apply(self, x2d, *[p for _, p in self._named_live()])
-            self._step += 1
-            pred = self._run_forward(x2d, True, self._step)
-            self._after_train_forward()
-            return pred.clone().view(-1, 1)
-        return self._run_forward(x2d, False).clone().view(-1, 1)
+        if not self.training:
+            return self._predict(x2d, False, 0, autograd=False)[0]
+        self._step += 1
+        pred = self._predict(x2d, True, self._step, autograd=torch.is_grad_enabled())[0]
+        self._after_train_forward()
+        return pred

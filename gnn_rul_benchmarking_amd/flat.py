@@ -1,5 +1,5 @@
-"""Base class of the model modules: flat fp32 parameter storage, the data-parallel bucket, workspace caches and the Adam
-argument block every family's C-ABI call takes.
+"""Base class of the model modules: flat fp32 parameter storage, the data-parallel bucket, workspace caches and the C-ABI call path
+every flat-parameter family shares (argument struct, ``forward`` / ``backward`` / ``fwdbwd`` calls, Adam argument block, autograd).
 
 A model module keeps the reference's ``nn.Module`` tree (same construction order => same RNG consumption => same initial
 weights, same ``state_dict`` keys; the sub-modules only hold parameters) and runs on ONE flat device buffer:
@@ -11,7 +11,10 @@ weights, same ``state_dict`` keys; the sub-modules only hold parameters) and run
 
 ``nn.Module._apply`` (``.to()``, ``.float()``...) converts tensors one by one: ``_apply`` below rebuilds the views when that
 happened and leaves everything in place when it was a no-op (the per-epoch ``model.to(device)`` of the trainers; captured
-hipGraphs and the optimizer state point into the buffers)."""
+hipGraphs and the optimizer state point into the buffers).
+
+A family describes its C entries as data (``c_family``, ``Args``, ``not_covered``...) and keeps what is its own: ``_shape``, the shape
+check of ``_check_input``, the family fields of ``_args``, its BatchNorm hooks and the ``forward`` the reference pins."""
 from __future__ import annotations
 
 import ctypes as C
@@ -27,10 +30,41 @@ def current_stream():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+class _FlatFunction(torch.autograd.Function):
+    """``model(x)`` with autograd through the family's ``forward`` / ``backward`` C entries.  ``state`` (training flag, dropout step)
+    goes to both calls; the outputs are ``_run_forward``'s, the prediction first.  The backward reads the activations the forward left
+    in the workspace of its batch size, which every later forward of that size overwrites: ``model._tape`` makes that an error."""
+
+    @staticmethod
+    def forward(ctx, model, x, state, *params):
+        outs = model._run_forward(x, *state)
+        ctx.model, ctx.x, ctx.state, ctx.token = model, x, state, model._tape.tokens[x.size(0)]
+        return tuple(o.clone() for o in outs)
+
+    @staticmethod
+    def backward(ctx, *douts):
+        model, B = ctx.model, ctx.x.size(0)
+        model._tape.check(B, ctx.token, model._bufs, type(model).__name__)
+        grads = model._run_backward(ctx.x, douts, *ctx.state)
+        if model.consumes_tape:
+            model._tape.consume(B, ctx.token)
+        k = model.gradless_params
+        return (None,) * (3 + k) + tuple(grads[off:off + n].view(shape).clone() for off, n, shape in model._slices[k:])
+
+
 class FlatModule(nn.Module):
     bucket_tail = 1            # floats behind the gradient in ``_grad_flat``: the loss (+ what a family appends)
     flat_order = None          # parameter names in flat-layout order; None = ``named_parameters()`` order
     workspace_slots = 2        # batch sizes whose workspaces are kept (training batch + evaluation batch)
+    output_buffers = 1         # [B] fp32 outputs cached with each workspace: the prediction (+ RGCNU's std head)
+
+    # ---- the family's C entries: rulgnn_<c_family>_{<workspace_query>, forward_f32, backward_f32, fwdbwd_f32} ---------------
+    c_family = None            # entry prefix ("sagcn", ...)
+    Args = None                # their argument struct (_lib.SagcnArgs, ...)
+    workspace_query = "workspace_bytes"
+    not_covered = None         # RuntimeError text when the workspace query returns 0
+    consumes_tape = False      # the backward reworks the forward's activations in place: one backward per forward
+    gradless_params = 0        # leading parameters of the layout that never receive a gradient (autograd returns None)
 
     # ---- construction ----------------------------------------------------------------------------------
     def _init_flat(self, layout=None, count=None):
@@ -55,6 +89,7 @@ class FlatModule(nn.Module):
             self._count = off
         self._flat = self._grad_flat = None
         self._bufs, self._pin_bufs, self._step_state = {}, False, None
+        self._tape = PL.ForwardTape()
         self._reflatten()
 
     def _named(self):
@@ -88,6 +123,8 @@ class FlatModule(nn.Module):
 
     def _reset_caches(self):
         self._bufs, self._step_state = {}, None
+        self._ws = self._pred_buf = None
+        self._out_bufs = ()
 
     def _reflatten(self):
         self._flush_nbt()
@@ -132,7 +169,7 @@ class FlatModule(nn.Module):
 
     # ---- C-ABI plumbing --------------------------------------------------------------------------------
     def _workspace_entry(self, key, nbytes, unsupported: str, make=None):
-        """The cached ``(workspace bytes, prediction buffer, ...)`` of batch size ``key``; allocates (and evicts the oldest entry
+        """The cached ``(workspace bytes, output buffers...)`` of batch size ``key``; allocates (and evicts the oldest entry
         beyond ``workspace_slots`` unless ``_pin_bufs``) on a miss.  ``nbytes`` is a callable: the family's
         ``rulgnn_*_workspace_bytes`` (0 = configuration not covered -> RuntimeError(unsupported))."""
         ent = self._bufs.get(key)
@@ -143,8 +180,8 @@ class FlatModule(nn.Module):
             if len(self._bufs) >= self.workspace_slots and not self._pin_bufs:
                 self._bufs.pop(next(iter(self._bufs)))
             dev = self._flat.device
-            ent = (torch.empty(n, dtype=torch.uint8, device=dev),) + (make(dev) if make is not None else
-                                                                       (torch.empty(max(int(key), 1), dtype=torch.float32, device=dev),))
+            ent = (torch.empty(n, dtype=torch.uint8, device=dev),) + (make(dev) if make is not None else tuple(     # [B] views, never null
+                torch.empty(max(int(key), 1), dtype=torch.float32, device=dev)[:int(key)] for _ in range(self.output_buffers)))
             self._bufs[key] = ent
         return ent
 
@@ -160,3 +197,84 @@ class FlatModule(nn.Module):
                                      optimizer._steps, float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
                                      float(g["weight_decay"]), 0.1,
                                      self._step_state.data_ptr() if self._step_state is not None else None))
+
+    def _require_device(self, x):
+        """The input guard of every family: the model runs on its HIP kernels, on the device of its parameters."""
+        if not x.is_cuda:
+            raise RuntimeError(f"{type(self).__name__} runs on the HIP path only: input must be a CUDA (ROCm) tensor; "
+                               "there is no CPU fallback")
+        if x.device != self._flat.device:
+            raise RuntimeError(f"input on {x.device} but model on {self._flat.device}")
+
+    def _step_inputs(self, x, y):
+        """``(x, flat fp32 target)`` of a training step: ``_check_input(x)`` and one target per sample."""
+        x = self._check_input(x)
+        yv = y.reshape(-1).contiguous().float()
+        if yv.numel() != x.size(0):
+            raise RuntimeError("target size mismatch")
+        return x, yv
+
+    def _args(self, shp, x, y=None, dpred=None, global_batch=None):
+        """``Args`` of one call at ``x``'s batch size with the fields every family shares; a family's override sets its own on top.  The
+        batch's cached workspace and output buffers become ``_ws`` / ``_out_bufs`` (``_pred_buf`` = the prediction's)."""
+        B = x.size(0)
+        ent = self._workspace_entry(B, lambda: getattr(_lib.load(), f"rulgnn_{self.c_family}_{self.workspace_query}")(C.byref(shp)),
+                                    self.not_covered)
+        # (plain instance attributes, written past nn.Module.__setattr__: its checks cost a microsecond apiece on every step)
+        vars(self).update(_ws=ent[0], _out_bufs=ent[1:], _pred_buf=ent[1])
+        a = self.Args()
+        a.x = x.data_ptr()
+        a.y = y.data_ptr() if y is not None else None
+        a.dpred = dpred.data_ptr() if dpred is not None else None
+        a.params, a.grads = self._flat.data_ptr(), self._grad_flat.data_ptr()
+        a.pred = self._pred_buf.data_ptr()
+        a.loss = self._grad_flat.data_ptr() + 4 * self._count
+        a.workspace, a.workspace_bytes = self._ws.data_ptr(), self._ws.numel()
+        a.global_batch = B if global_batch is None else int(global_batch)
+        return a
+
+    def _call(self, kind, shp, a, *more):
+        """``rulgnn_<c_family>_<kind>_f32(shape, args, *more, stream)``; a non-zero code raises."""
+        name = f"rulgnn_{self.c_family}_{kind}_f32"
+        _lib.check(getattr(_lib.load(), name)(C.byref(shp), C.byref(a), *more, current_stream()), name)
+
+    def _run_forward(self, x, *state):
+        """One ``forward`` call; returns the output buffers' ``[B, 1]`` views (the prediction first), valid until the next call."""
+        B = x.size(0)
+        shp = self._shape(B)
+        self._tape.mark(B)
+        a = self._args(shp, x, *state)
+        self._call("forward", shp, a)
+        return tuple(t.view(-1, 1) for t in self._out_bufs)
+
+    def _run_backward(self, x, douts, *state, **fields):
+        """One ``backward`` call of the last forward at ``x``'s batch size with the outputs' incoming gradients ``douts``; fills
+        ``_grad_flat``."""
+        shp = self._shape(x.size(0))
+        dpred = douts[0].reshape(-1).contiguous().float()
+        a = self._args(shp, x, *state, dpred=dpred, **fields)
+        self._call("backward", shp, a)
+        return self._grad_flat
+
+    def _fused_step(self, x, yv, optimizer, global_batch, *state, bn=None, **fields):
+        """One ``fwdbwd`` call (forward + MSE + backward, + Adam with ``optimizer``) on checked inputs (``_step_inputs``)."""
+        shp = self._shape(x.size(0))
+        self._tape.mark(x.size(0))
+        a = self._args(shp, x, *state, y=yv, global_batch=global_batch, **fields)
+        self._call("fwdbwd", shp, a, self._adam_args(optimizer, bn=bn))
+        return self._pred_buf, self._grad_flat[self._count]
+
+    def fused_mse_step(self, x, y, optimizer=None, global_batch=None):
+        """forward + MSE + backward (+ Adam when ``optimizer`` is a FusedAdam over this model) in one C call; fills ``self.bucket`` =
+        [grad | loss]; returns (pred [B], loss 0-d tensor) on the device, no host sync."""
+        return self._fused_step(*self._step_inputs(x, y), optimizer, global_batch)
+
+    def _needs_grad(self):
+        return torch.is_grad_enabled() and any(p.requires_grad for p in self._named())
+
+    def _predict(self, x, *state, autograd):
+        """``_run_forward``'s outputs as new tensors; through the autograd Function (parameter gradients from the backward entry) when
+        ``autograd``."""
+        if autograd:
+            return _FlatFunction.apply(self, x, state, *self._named())
+        return tuple(o.clone() for o in self._run_forward(x, *state))

@@ -13,13 +13,11 @@ cannot be reproduced by any other implementation).  There is no CPU path: a non-
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 import torch.nn as nn
 
-from . import _lib, params as PL
-from .flat import FlatModule, current_stream as _stream
+from . import _lib
+from .flat import FlatModule
 
 SCL_DROPOUT = 0.5          # models/RGCNU/Model.py:31
 
@@ -71,28 +69,6 @@ PARAM_ORDER = ["adj.trainable_theta1.weight", "adj.trainable_theta1.bias", "adj.
                "fusion.fc1.weight", "fusion.fc1.bias", "fusion.fc2.weight", "fusion.fc2.bias"]
 
 
-class _Function(torch.autograd.Function):
-    """model(x, train=True) through rulgnn_rgcnu_forward_f32 / rulgnn_rgcnu_backward_f32 (flat parameters).  The second head is
-    returned detached: its only consumer in the reference is a commented-out loss (algorithms.py:288)."""
-
-    @staticmethod
-    def forward(ctx, model, x, training, *params):
-        pred, std = model._forward(x, training)
-        ctx.model, ctx.x, ctx.step, ctx.training = model, x, model._step, bool(training)
-        ctx.tape = model._tape.tokens[x.size(0)]
-        ctx.mark_non_differentiable(std)
-        return pred.clone().view(-1, 1), std.clone().view(-1, 1)
-
-    @staticmethod
-    def backward(ctx, dpred, _dstd):
-        model = ctx.model
-        model._tape.check(ctx.x.size(0), ctx.tape, model._bufs, "RGCNU_model")
-        grads = model._backward(ctx.x, dpred.reshape(-1).contiguous().float(), ctx.step, ctx.training)
-        model._tape.consume(ctx.x.size(0), ctx.tape)
-        outs = [grads[off:off + n].view(shape).clone() for off, n, shape in model._slices]
-        return (None, None, None, *outs)
-
-
 class RGCNU_model(FlatModule):
     dropout_by_sample_offset = True          # dp.py: pass the shard's first global sample index to fused_mse_step
     # graph (b, l) meets the adjacency of sample (b * T + l) % bs: the eval forward depends on WHICH samples share a batch, so a test
@@ -112,79 +88,45 @@ class RGCNU_model(FlatModule):
         self._step = 0
         if [n for n, _ in self.named_parameters()] != PARAM_ORDER:
             raise RuntimeError("parameter order differs from the flat layout of include/rulgnn.h")
-        self._tape = PL.ForwardTape()
         self._init_flat()
         # fusion.fc2 (the `std` head) is not in the loss: its gradient is None in the reference and torch's Adam never touches it
         self.num_optimized = self._layout["fusion.fc2.weight"][0]
 
     flat_order = PARAM_ORDER
     workspace_slots = 4
+    output_buffers = 2         # prediction, std head
+    consumes_tape = True       # the backward reworks the gate tape in place: one backward per forward
 
     # ---- C-ABI calls -----------------------------------------------------------------------------------
+    c_family, Args = "rgcnu", _lib.RgcnuArgs
+    not_covered = ("RGCNU HIP kernels do not cover this configuration (num_nodes <= 32, time_length <= 64, hidden widths <= 64, odd "
+                   "kernel_size <= 7)")
+
     def _shape(self, batch):
         return _lib.RgcnuShape(batch, self.num_nodes, self.time_length, self.hidden_dim, self.encoder_hidden_dim, self.kernel_size, self.alpha)
 
     def _check_input(self, x):
         if x.dim() != 3 or x.size(1) != self.num_nodes or x.size(2) != self.time_length:
             raise RuntimeError(f"RGCNU_model expects [bs, {self.num_nodes}, {self.time_length}], got {tuple(x.shape)}")
-        if not x.is_cuda:
-            raise RuntimeError("RGCNU_model runs on the HIP path only: input must be a CUDA (ROCm) tensor; there is no CPU fallback")
-        if x.device != self._flat.device:
-            raise RuntimeError(f"input on {x.device} but model on {self._flat.device}")
+        self._require_device(x)
         return x.contiguous().float()
 
     def _args(self, shp, x, training, step, y=None, dpred=None, global_batch=None, sample_offset=0):
-        B = x.size(0)
-        ent = self._workspace_entry(B, lambda: _lib.load().rulgnn_rgcnu_workspace_bytes(C.byref(shp)),
-                                    "RGCNU HIP kernels do not cover this configuration (num_nodes <= 32, time_length <= 64, hidden widths "
-                                    "<= 64, odd kernel_size <= 7)",
-                                    make=lambda dev: tuple(torch.empty(max(B, 1), dtype=torch.float32, device=dev) for _ in range(2)))
-        ws, pred, std = ent
-        a = _lib.RgcnuArgs()
-        a.x = x.data_ptr()
-        a.y = y.data_ptr() if y is not None else None
-        a.dpred = dpred.data_ptr() if dpred is not None else None
-        a.params, a.grads = self._flat.data_ptr(), self._grad_flat.data_ptr()
-        a.pred, a.std_pred = pred.data_ptr(), std.data_ptr()
-        a.loss = self._grad_flat.data_ptr() + 4 * self._count
-        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-        a.global_batch = B if global_batch is None else int(global_batch)
+        """``training`` and ``step`` of a backward must be the forward's: the dropout mask of rg_scl_bwd is applied only then."""
+        a = super()._args(shp, x, y, dpred, global_batch)
+        a.std_pred = self._out_bufs[1].data_ptr()
         a.sample_offset = int(sample_offset)
         a.dropout_p = float(self.scl.dropout.p)
         a.seed, a.step = self._seed, int(step)
         a.training = 1 if training else 0
-        return a, pred, std
-
-    def _forward(self, x, training):
-        if training:
-            self._step += 1
-        shp = self._shape(x.size(0))
-        self._tape.mark(x.size(0))
-        a, pred, std = self._args(shp, x, training, self._step)
-        _lib.check(_lib.load().rulgnn_rgcnu_forward_f32(C.byref(shp), C.byref(a), _stream()), "rulgnn_rgcnu_forward_f32")
-        return pred[:x.size(0)], std[:x.size(0)]
-
-    def _backward(self, x, dpred, step, training=True):
-        """``training`` must be the flag of the forward this backward belongs to: the dropout mask of rg_scl_bwd is applied only then."""
-        shp = self._shape(x.size(0))
-        a, _, _ = self._args(shp, x, training, step, dpred=dpred)
-        _lib.check(_lib.load().rulgnn_rgcnu_backward_f32(C.byref(shp), C.byref(a), _stream()), "rulgnn_rgcnu_backward_f32")
-        return self._grad_flat
+        return a
 
     def fused_mse_step(self, x, y, optimizer=None, global_batch=None, sample_offset=0):
         """forward (train mode) + MSE of the first head + backward (+ Adam when ``optimizer`` is a FusedAdam over this model) in one C
         call; fills ``self.bucket`` = [grad | loss]; returns (pred [B], loss 0-d tensor) on the device, no host sync."""
-        x = self._check_input(x)
-        yv = y.reshape(-1).contiguous().float()
-        if yv.numel() != x.size(0):
-            raise RuntimeError("target size mismatch")
+        x, yv = self._step_inputs(x, y)
         self._step += 1
-        shp = self._shape(x.size(0))
-        self._tape.mark(x.size(0))
-        a, pred, _ = self._args(shp, x, True, self._step, y=yv, global_batch=global_batch, sample_offset=sample_offset)
-        o = self._adam_args(optimizer)
-        _lib.check(_lib.load().rulgnn_rgcnu_fwdbwd_f32(C.byref(shp), C.byref(a), o, _stream()), "rulgnn_rgcnu_fwdbwd_f32")
-        return pred[:x.size(0)], self._grad_flat[self._count]
+        return self._fused_step(x, yv, optimizer, global_batch, True, self._step, sample_offset=sample_offset)
 
     # ---- nn.Module surface -----------------------------------------------------------------------------
     def forward(self, X, train=False):
@@ -192,9 +134,8 @@ class RGCNU_model(FlatModule):
         x = self._check_input(X)
         if x.size(0) == 0:
             raise RuntimeError("RGCNU_model: empty batch")
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self._named()):
-            pred, std = _Function.apply(self, x, self.training, *self._named())
-        else:
-            p, s = self._forward(x, self.training)
-            pred, std = p.clone().view(-1, 1), s.clone().view(-1, 1)
-        return (pred, std) if train else pred
+        if self.training:
+            self._step += 1
+        # the second head is returned detached: its only consumer in the reference is a commented-out loss (algorithms.py:288)
+        pred, std = self._predict(x, self.training, self._step, autograd=self._needs_grad())
+        return (pred, std.detach()) if train else pred

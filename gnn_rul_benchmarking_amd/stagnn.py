@@ -18,8 +18,8 @@ import torch
 import torch.nn as nn
 from torch.nn.utils import weight_norm
 
-from . import _lib, params as PL
-from .flat import FlatModule, current_stream as _stream
+from . import _lib
+from .flat import FlatModule
 
 
 class GCNLayer(nn.Module):
@@ -95,25 +95,6 @@ def live_parameter_names(num_heads):
 _BN_LAYERS = ("tcn1.conv_block1.2", "tcn1.conv_block2.2", "tcn2.conv_block1.2", "tcn2.conv_block2.2")
 
 
-class _TrainFunction(torch.autograd.Function):
-    """model(x) in train mode through rulgnn_stagnn_forward_f32 / rulgnn_stagnn_backward_f32."""
-
-    @staticmethod
-    def forward(ctx, model, x, *params):
-        pred = model._run_forward(x, training=True)
-        model._nbt_pending += 1
-        ctx.model, ctx.x = model, x
-        ctx.tape = model._tape.tokens[x.size(0)]
-        return pred.clone().view(-1, 1)
-
-    @staticmethod
-    def backward(ctx, dpred):
-        model = ctx.model
-        model._tape.check(ctx.x.size(0), ctx.tape, model._bufs, "STAGNN_model")
-        grads = model._run_backward(ctx.x, dpred.reshape(-1).contiguous().float())
-        return (None, None, *[grads[off:off + n].view(shape).clone() for off, n, shape in model._slices])
-
-
 class STAGNN_model(FlatModule):
     def __init__(self, num_nodes, time_length, hidden_dim, output_dim, num_heads, threshold):
         super().__init__()
@@ -137,7 +118,6 @@ class STAGNN_model(FlatModule):
         self.flat_order = live_parameter_names(self.num_heads)
         self._bn_channels = (h, h, self.output_dim, self.output_dim)
         self._bn = self._nbt = None
-        self._tape = PL.ForwardTape()
         self._track_batchnorm_counters()
         self._init_flat()
 
@@ -159,50 +139,25 @@ class STAGNN_model(FlatModule):
         self._bn, self._nbt = bn, nbt
 
     # ---- C-ABI calls -----------------------------------------------------------------------------------
+    c_family, Args = "stagnn", _lib.StagnnArgs
+    not_covered = ("STAGNN HIP kernels do not cover this configuration (num_nodes <= 32, time_length <= 128, 3 <= hidden_dim <= 64, "
+                   "output_dim <= 16, num_heads <= 4, num_nodes != hidden_dim != output_dim)")
+
     def _shape(self, batch):
         return _lib.StagnnShape(batch, self.num_nodes, self.time_length, self.hidden_dim, self.output_dim, self.num_heads, float(self.threshold))
 
     def _check_input(self, x):
-        if not x.is_cuda:
-            raise RuntimeError("STAGNN_model runs on the HIP path only: input must be a CUDA (ROCm) tensor; there is no CPU fallback")
-        if x.device != self._flat.device:
-            raise RuntimeError(f"input on {x.device} but model on {self._flat.device}")
+        self._require_device(x)
         if x.dim() != 3 or x.size(1) != self.num_nodes or x.size(2) != self.time_length:
             raise RuntimeError(f"expected input [bs, {self.num_nodes}, {self.time_length}], got {list(x.shape)}")
         return x.contiguous().float()
 
     def _args(self, shp, x, training, y=None, dpred=None, global_batch=None, update_running_stats=True):
-        B = x.size(0)
-        ent = self._workspace_entry(B, lambda: _lib.load().rulgnn_stagnn_workspace_bytes(C.byref(shp)),
-                                    "STAGNN HIP kernels do not cover this configuration (num_nodes <= 32, time_length <= 128, 3 <= hidden_dim "
-                                    "<= 64, output_dim <= 16, num_heads <= 4, num_nodes != hidden_dim != output_dim)")
-        ws, pred = ent
-        a = _lib.StagnnArgs()
-        a.x = x.data_ptr()
-        a.y = y.data_ptr() if y is not None else None
-        a.dpred = dpred.data_ptr() if dpred is not None else None
-        a.params, a.grads = self._flat.data_ptr(), self._grad_flat.data_ptr()
-        a.pred = pred.data_ptr()
-        a.loss = self._grad_flat.data_ptr() + 4 * self._count
+        a = super()._args(shp, x, y, dpred, global_batch)
         a.bn_state = self._bn.data_ptr()
-        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-        a.global_batch = B if global_batch is None else int(global_batch)
         a.training = 1 if training else 0
-        a.update_running_stats = 1 if (training and update_running_stats) else 0
-        return a, pred
-
-    def _run_forward(self, x, training):
-        shp = self._shape(x.size(0))
-        self._tape.mark(x.size(0))
-        a, pred = self._args(shp, x, training)
-        _lib.check(_lib.load().rulgnn_stagnn_forward_f32(C.byref(shp), C.byref(a), _stream()), "rulgnn_stagnn_forward_f32")
-        return pred[:x.size(0)]
-
-    def _run_backward(self, x, dpred):
-        shp = self._shape(x.size(0))
-        a, _ = self._args(shp, x, True, dpred=dpred, update_running_stats=False)
-        _lib.check(_lib.load().rulgnn_stagnn_backward_f32(C.byref(shp), C.byref(a), _stream()), "rulgnn_stagnn_backward_f32")
-        return self._grad_flat
+        a.update_running_stats = 1 if (training and update_running_stats and dpred is None) else 0      # (never in a backward)
+        return a
 
     def tap(self, batch, which):
         """Workspace taps of the last forward at this batch size (parity tests)."""
@@ -216,28 +171,19 @@ class STAGNN_model(FlatModule):
     def fused_mse_step(self, x, y, optimizer=None, global_batch=None, update_running_stats=True):
         """train-mode forward + MSE + backward (+ Adam when ``optimizer`` is a FusedAdam over this model) in one C call; fills
         ``self.bucket`` = [grad | loss]; returns (pred [B], loss 0-d tensor) on the device, no host sync."""
-        x = self._check_input(x)
-        yv = y.reshape(-1).contiguous().float()
-        if yv.numel() != x.size(0):
-            raise RuntimeError("target size mismatch")
-        shp = self._shape(x.size(0))
-        self._tape.mark(x.size(0))
-        a, pred = self._args(shp, x, True, y=yv, global_batch=global_batch, update_running_stats=update_running_stats)
-        o = self._adam_args(optimizer)
-        _lib.check(_lib.load().rulgnn_stagnn_fwdbwd_f32(C.byref(shp), C.byref(a), o, _stream()), "rulgnn_stagnn_fwdbwd_f32")
+        x, yv = self._step_inputs(x, y)
+        out = self._fused_step(x, yv, optimizer, global_batch, True, update_running_stats=update_running_stats)
         if update_running_stats:
             self._nbt_pending += 1
-        return pred[:x.size(0)], self._grad_flat[self._count]
+        return out
 
     # ---- nn.Module surface -----------------------------------------------------------------------------
     def forward(self, x):
         x = self._check_input(x)
         if x.size(0) == 0:
             raise RuntimeError("STAGNN_model: empty batch")
-        if self.training:
-            if torch.is_grad_enabled() and any(p.requires_grad for p in self._named()):
-                return _TrainFunction.apply(self, x, *self._named())
-            pred = self._run_forward(x, training=True)
-            self._nbt_pending += 1
-            return pred.clone().view(-1, 1)
-        return self._run_forward(x, training=False).clone().view(-1, 1)
+        if not self.training:
+            return self._predict(x, False, autograd=False)[0]
+        pred = self._predict(x, True, autograd=self._needs_grad())[0]
+        self._nbt_pending += 1
+        return pred

@@ -17,7 +17,7 @@ import ctypes as C
 import torch
 import torch.nn as nn
 
-from . import _lib, params as PL
+from . import _lib
 from .flat import FlatModule, current_stream as _stream
 from .stgcn import MPNN_mk, TemporalConvNet
 
@@ -38,22 +38,6 @@ class CNNLayer(nn.Module):
         self.bn = nn.BatchNorm1d(out_channels)
 
 
-class _TrainFunction(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, model, x2d, *params):
-        pred = model._run_forward(x2d, training=True)
-        model._after_train_forward(x2d.size(0))
-        ctx.model, ctx.x2d = model, x2d
-        return pred.clone().view(-1, 1)
-
-    @staticmethod
-    def backward(ctx, dpred):
-        model = ctx.model
-        grads = model._run_backward(ctx.x2d, dpred.contiguous().view(-1).float())
-        out = [grads[off:off + n].view(shape).clone() for (off, n, shape) in model._slices]
-        return (None, None, *out)
-
-
 class ST_Conv_model(FlatModule):
     def __init__(self, num_nodes, time_length, kernel_size):
         super().__init__()
@@ -71,7 +55,7 @@ class ST_Conv_model(FlatModule):
         self.theta4 = nn.Parameter(torch.randn(1))
         self.fc = nn.Linear(num_nodes * time_length, 1)
 
-        self._bn = self._bn_batch = self._pred_buf = self._ws = None
+        self._bn = self._bn_batch = None
         self._track_batchnorm_counters()
         self._init_flat()
 
@@ -102,63 +86,30 @@ class ST_Conv_model(FlatModule):
         self._bn, self._nbt = bn, nbt
         self._bn_batch = torch.zeros(6 * N, dtype=torch.float32, device=dev)
 
-    def _reset_caches(self):
-        super()._reset_caches()
-        self._pred_buf = self._ws = None
-
     # ---- C-ABI calls -----------------------------------------------------------------------------------
+    c_family, Args = "stconv", _lib.AstgcnnArgs
+    not_covered = "ST_Conv kernels do not cover this configuration (kernel_size 6, num_nodes <= 25, time_length <= 64)"
+
     def _shape(self, batch):
         return _lib.StconvShape(batch, self.num_nodes, self.time_length, self.kernel_size)
 
     def _check_input(self, x):
-        if not x.is_cuda:
-            raise RuntimeError("ST_Conv_model runs on the HIP kernels only: input must be a CUDA (ROCm) tensor; "
-                               "there is no CPU fallback")
-        if x.device != self._flat.device:
-            raise RuntimeError(f"input on {x.device} but model on {self._flat.device}")
+        self._require_device(x)
         if x.dim() != 3 or x.size(1) != self.num_nodes or x.size(2) != self.time_length:
             raise RuntimeError(f"expected input [bs, {self.num_nodes}, {self.time_length}], got {list(x.shape)}")
         return x.reshape(x.size(0), -1).contiguous().float()
 
     def _args(self, shp, x2d, training, y=None, dpred=None, global_batch=None, moments_to_bucket=False):
-        B = x2d.size(0)
-        ent = self._workspace_entry(B, lambda: _lib.load().rulgnn_stconv_workspace_bytes(C.byref(shp)),
-                                    "ST_Conv kernels do not cover this configuration (kernel_size 6, num_nodes <= 25, time_length <= 64)",
-                                    make=lambda dev: (torch.empty(B, dtype=torch.float32, device=dev),))
-        self._ws, self._pred_buf = ent
-        a = _lib.AstgcnnArgs()
-        a.x = x2d.data_ptr()
-        a.y = y.data_ptr() if y is not None else None
-        a.dpred = dpred.data_ptr() if dpred is not None else None
-        a.params = self._flat.data_ptr()
-        a.grads = self._grad_flat.data_ptr()
-        a.pred = self._pred_buf.data_ptr()
-        a.loss = self._grad_flat.data_ptr() + 4 * self._count
+        a = super()._args(shp, x2d, y, dpred, global_batch)
         a.bn_stats = self._bn.data_ptr()
-        gb = B if global_batch is None else int(global_batch)
         if moments_to_bucket:
             a.bn_batch = self._grad_flat.data_ptr() + 4 * (self._count + 1)
-            a.bn_moment_weight = B / float(gb)
+            a.bn_moment_weight = x2d.size(0) / float(a.global_batch)
         else:
             a.bn_batch = self._bn_batch.data_ptr()
             a.bn_moment_weight = 0.0
-        a.workspace = self._ws.data_ptr()
-        a.workspace_bytes = self._ws.numel()
-        a.global_batch = gb
         a.training = 1 if training else 0
         return a
-
-    def _run_forward(self, x2d, training):
-        shp = self._shape(x2d.size(0))
-        a = self._args(shp, x2d, training)
-        _lib.check(_lib.load().rulgnn_stconv_forward_f32(C.byref(shp), C.byref(a), _stream()), "rulgnn_stconv_forward_f32")
-        return self._pred_buf
-
-    def _run_backward(self, x2d, dpred):
-        shp = self._shape(x2d.size(0))
-        a = self._args(shp, x2d, True, dpred=dpred)
-        _lib.check(_lib.load().rulgnn_stconv_backward_f32(C.byref(shp), C.byref(a), _stream()), "rulgnn_stconv_backward_f32")
-        return self._grad_flat
 
     def _after_train_forward(self, batch, from_bucket_moments=False):
         src = self._grad_flat.data_ptr() + 4 * (self._count + 1) if from_bucket_moments else self._bn_batch.data_ptr()
@@ -171,19 +122,13 @@ class ST_Conv_model(FlatModule):
     def fused_mse_step(self, x, y, optimizer=None, global_batch=None, sample_offset=0, update_running_stats=True,
                        moments_to_bucket=False):
         """train forward + MSE + backward (+ Adam and the running statistics with ``optimizer``) in one C call."""
-        x2d = self._check_input(x)
-        yv = y.reshape(-1).contiguous().float()
-        if yv.numel() != x2d.size(0):
-            raise RuntimeError("target size mismatch")
-        shp = self._shape(x2d.size(0))
-        a = self._args(shp, x2d, True, y=yv, global_batch=global_batch, moments_to_bucket=moments_to_bucket)
-        o = self._adam_args(optimizer, bn=self._bn)
-        _lib.check(_lib.load().rulgnn_stconv_fwdbwd_f32(C.byref(shp), C.byref(a), o, _stream()), "rulgnn_stconv_fwdbwd_f32")
+        x2d, yv = self._step_inputs(x, y)
+        out = self._fused_step(x2d, yv, optimizer, global_batch, True, bn=self._bn, moments_to_bucket=moments_to_bucket)
         if optimizer is not None:
             self._nbt_pending += 1
         elif update_running_stats:
             self._after_train_forward(x2d.size(0))
-        return self._pred_buf, self._grad_flat[self._count]
+        return out
 
     # ---- nn.Module surface -----------------------------------------------------------------------------
     def forward(self, x):
@@ -192,10 +137,8 @@ class ST_Conv_model(FlatModule):
             if self.training:
                 raise RuntimeError("training forward needs a non-empty batch")
             return torch.empty(0, 1, dtype=torch.float32, device=x2d.device)
-        if self.training:
-            if torch.is_grad_enabled():
-                return _TrainFunction.apply(self, x2d, *[p for _, p in self._named_live()])
-            pred = self._run_forward(x2d, training=True)
-            self._after_train_forward(x2d.size(0))
-            return pred.clone().view(-1, 1)
-        return self._run_forward(x2d, training=False).clone().view(-1, 1)
+        if not self.training:
+            return self._predict(x2d, False, autograd=False)[0]
+        pred = self._predict(x2d, True, autograd=torch.is_grad_enabled())[0]
+        self._after_train_forward(x2d.size(0))
+        return pred

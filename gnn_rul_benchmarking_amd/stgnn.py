@@ -19,7 +19,7 @@ import ctypes as C
 import torch
 import torch.nn as nn
 
-from . import _lib, params as PL
+from . import _lib
 from .flat import FlatModule, current_stream as _stream
 
 
@@ -120,23 +120,6 @@ class ChebNet(nn.Module):
         nn.init.xavier_uniform_(self.filters)
 
 
-class _Function(torch.autograd.Function):
-    """model(x) through the C entries rulgnn_stgnn_forward_f32 / rulgnn_stgnn_backward_f32 (flat parameters)."""
-
-    @staticmethod
-    def forward(ctx, model, x, *params):
-        pred = model._forward(x).clone()
-        ctx.model, ctx.x = model, x
-        return pred.view(-1, 1)
-
-    @staticmethod
-    def backward(ctx, dout):
-        model = ctx.model
-        grads = model._backward(ctx.x, dout.reshape(-1).contiguous().float())
-        outs = [grads[off:off + n].view(shape).clone() for off, n, shape in model._slices]
-        return (None, None, *outs)
-
-
 def param_layout(patch_size, num_patch, num_nodes, hidden_dim, K):
     """name -> (offset, shape) in the flat buffer the kernels read (include/rulgnn.h), in state_dict order."""
     H = hidden_dim
@@ -169,59 +152,18 @@ class STGNN_model(FlatModule):
     workspace_slots = 4
 
     # ---- C-ABI calls -----------------------------------------------------------------------------------
+    c_family, Args = "stgnn", _lib.StmsgcnArgs
+    workspace_query = "step_workspace_bytes"
+    not_covered = "STGNN HIP kernels do not cover this configuration (num_nodes <= 32, patch_size <= 128, K <= 4, top_k <= num_nodes)"
+
     def _shape(self, batch):
         return _lib.StgnnShape(batch, self.num_nodes, self.num_patch, self.patch_size, self.hidden_dim, self.chebnet.K, self.top_k)
 
     def _check_input(self, x):
         if x.dim() != 3 or x.size(1) != self.num_nodes or x.size(2) != self.num_patch * self.patch_size:
             raise RuntimeError(f"STGNN_model expects [bs, {self.num_nodes}, {self.num_patch * self.patch_size}], got {tuple(x.shape)}")
-        if not x.is_cuda:
-            raise RuntimeError("STGNN_model runs on the HIP path only: input must be a CUDA (ROCm) tensor; there is no CPU fallback")
-        if x.device != self._flat.device:
-            raise RuntimeError(f"input on {x.device} but model on {self._flat.device}")
+        self._require_device(x)
         return x.contiguous().float()
-
-    def _args(self, shp, x, y=None, dpred=None, global_batch=None):
-        B = x.size(0)
-        ent = self._workspace_entry(B, lambda: _lib.load().rulgnn_stgnn_step_workspace_bytes(C.byref(shp)),
-                                    "STGNN HIP kernels do not cover this configuration (num_nodes <= 32, patch_size <= 128, K <= 4, "
-                                    "top_k <= num_nodes)")
-        ws, pred = ent
-        a = _lib.StmsgcnArgs()
-        a.x = x.data_ptr()
-        a.y = y.data_ptr() if y is not None else None
-        a.dpred = dpred.data_ptr() if dpred is not None else None
-        a.params, a.grads = self._flat.data_ptr(), self._grad_flat.data_ptr()
-        a.pred = pred.data_ptr()
-        a.loss = self._grad_flat.data_ptr() + 4 * self._count
-        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-        a.global_batch = B if global_batch is None else int(global_batch)
-        return a, pred
-
-    def _forward(self, x):
-        shp = self._shape(x.size(0))
-        a, pred = self._args(shp, x)
-        _lib.check(_lib.load().rulgnn_stgnn_forward_f32(C.byref(shp), C.byref(a), _stream()), "rulgnn_stgnn_forward_f32")
-        return pred[:x.size(0)]
-
-    def _backward(self, x, dpred):
-        shp = self._shape(x.size(0))
-        a, _ = self._args(shp, x, dpred=dpred)
-        _lib.check(_lib.load().rulgnn_stgnn_backward_f32(C.byref(shp), C.byref(a), _stream()), "rulgnn_stgnn_backward_f32")
-        return self._grad_flat
-
-    def fused_mse_step(self, x, y, optimizer=None, global_batch=None):
-        """forward + MSE + backward (+ Adam when ``optimizer`` is a FusedAdam over this model) in one C call; fills
-        ``self.bucket`` = [grad | loss]; returns (pred [B], loss 0-d tensor) on the device, no host sync."""
-        x = self._check_input(x)
-        yv = y.reshape(-1).contiguous().float()
-        if yv.numel() != x.size(0):
-            raise RuntimeError("target size mismatch")
-        shp = self._shape(x.size(0))
-        a, pred = self._args(shp, x, y=yv, global_batch=global_batch)
-        o = self._adam_args(optimizer)
-        _lib.check(_lib.load().rulgnn_stgnn_fwdbwd_f32(C.byref(shp), C.byref(a), o, _stream()), "rulgnn_stgnn_fwdbwd_f32")
-        return pred[:x.size(0)], self._grad_flat[self._count]
 
     def adjacency(self, x):
         """[bs, num_patch, N, N]: compute_adjacency_matrix of the reference (Model.py:8-25), for inspection / tests."""
@@ -243,6 +185,4 @@ class STGNN_model(FlatModule):
                                "any value and is ambiguous")
         if return_adjacency:
             self.last_adjacency = self.adjacency(x)
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self._named()):
-            return _Function.apply(self, x, *self._named())
-        return self._forward(x).clone().view(-1, 1)
+        return self._predict(x, autograd=self._needs_grad())[0]

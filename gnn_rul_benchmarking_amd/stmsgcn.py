@@ -16,7 +16,7 @@ import ctypes as C
 import torch
 import torch.nn as nn
 
-from . import _lib, params as PL
+from . import _lib
 from .flat import FlatModule, current_stream as _stream
 
 
@@ -63,24 +63,6 @@ def param_layout(num_patch, gcn_dims, gru_hidden_dim):
     return out, off
 
 
-class _Function(torch.autograd.Function):
-    """model(X) with autograd: forward = rulgnn_stmsgcn_forward_f32, backward = rulgnn_stmsgcn_backward_f32 with the
-    incoming d(loss)/d(pred)."""
-
-    @staticmethod
-    def forward(ctx, model, x2d, *params):
-        pred = model._forward(x2d)
-        ctx.model, ctx.x2d = model, x2d
-        return pred.clone().view(-1, 1)
-
-    @staticmethod
-    def backward(ctx, dpred):
-        model = ctx.model
-        grads = model._backward(ctx.x2d, dpred.contiguous().view(-1).float())
-        out = [grads[off:off + n].view(shape).clone() for (off, n, shape) in model._slices]
-        return (None, None, *out)
-
-
 class STMSGCN_model(FlatModule):
     def __init__(self, num_patch, patch_size, interval, band_width, gcn_dims, gru_hidden_dim):
         super().__init__()
@@ -95,17 +77,15 @@ class STMSGCN_model(FlatModule):
         self.gcn_layers = nn.ModuleList([GCNLayer(dims[i], dims[i + 1]) for i in range(len(dims) - 1)])
         self.gru_layer = GRULayer(sum(dims), self.gru_hidden_dim, 1)
         self.fc = nn.Linear(self.gru_hidden_dim * self.num_patch, 1)
-
-        self._loss = self._pred_buf = self._ws = None
         self._init_flat(*param_layout(self.num_patch, dims[1:], self.gru_hidden_dim))
 
     workspace_slots = 4
 
-    def _reset_caches(self):
-        super()._reset_caches()
-        self._pred_buf = self._ws = None
-
     # ---- C-ABI calls -----------------------------------------------------------------------------------
+    c_family, Args = "stmsgcn", _lib.StmsgcnArgs
+    not_covered = ("STMSGCN kernels do not cover this configuration (nodes <= 32, patch_size <= 512, GCN widths <= 64 with sum <= 128, "
+                   "gru_hidden_dim <= 16, num_patch <= 4096)")
+
     def _shape(self, batch):
         s = _lib.StmsgcnShape()
         s.batch, s.num_patch, s.patch_size = batch, self.num_patch, self.patch_size
@@ -119,47 +99,11 @@ class STMSGCN_model(FlatModule):
         return s
 
     def _check_input(self, x):
-        if not x.is_cuda:
-            raise RuntimeError("STMSGCN_model runs on the HIP kernels only: input must be a CUDA (ROCm) tensor; "
-                               "there is no CPU fallback")
-        if x.device != self._flat.device:
-            raise RuntimeError(f"input on {x.device} but model on {self._flat.device}")
+        self._require_device(x)
         bs = x.size(0)
         if x.numel() != bs * self.num_patch * self.patch_size:
             raise RuntimeError(f"shape '[{bs}, {self.num_patch}, {self.patch_size}]' is invalid for input of size {x.numel()}")
         return x.reshape(bs, self.num_patch * self.patch_size).contiguous().float()
-
-    def _args(self, shp, x2d, y=None, dpred=None, global_batch=None):
-        B = x2d.size(0)
-        ent = self._workspace_entry(B, lambda: _lib.load().rulgnn_stmsgcn_workspace_bytes(C.byref(shp)),
-                                    "STMSGCN kernels do not cover this configuration (nodes <= 32, patch_size <= 512, "
-                                    "GCN widths <= 64 with sum <= 128, gru_hidden_dim <= 16, num_patch <= 4096)",
-                                    make=lambda dev: (torch.empty(B, dtype=torch.float32, device=dev),))
-        self._ws, self._pred_buf = ent
-        a = _lib.StmsgcnArgs()
-        a.x = x2d.data_ptr()
-        a.y = y.data_ptr() if y is not None else None
-        a.dpred = dpred.data_ptr() if dpred is not None else None
-        a.params = self._flat.data_ptr()
-        a.grads = self._grad_flat.data_ptr()
-        a.pred = self._pred_buf.data_ptr()
-        a.loss = self._grad_flat.data_ptr() + 4 * self._count
-        a.workspace = self._ws.data_ptr()
-        a.workspace_bytes = self._ws.numel()
-        a.global_batch = B if global_batch is None else int(global_batch)
-        return a
-
-    def _forward(self, x2d):
-        shp = self._shape(x2d.size(0))
-        a = self._args(shp, x2d)
-        _lib.check(_lib.load().rulgnn_stmsgcn_forward_f32(C.byref(shp), C.byref(a), _stream()), "rulgnn_stmsgcn_forward_f32")
-        return self._pred_buf
-
-    def _backward(self, x2d, dpred):
-        shp = self._shape(x2d.size(0))
-        a = self._args(shp, x2d, dpred=dpred)
-        _lib.check(_lib.load().rulgnn_stmsgcn_backward_f32(C.byref(shp), C.byref(a), _stream()), "rulgnn_stmsgcn_backward_f32")
-        return self._grad_flat
 
     def features(self, x):
         """[bs*num_patch, nodes, sum(dims)]: the concatenated GCN features the reference hands to its GRU
@@ -172,24 +116,9 @@ class STMSGCN_model(FlatModule):
                                                            _stream()), "rulgnn_stmsgcn_features_f32")
         return out
 
-    def fused_mse_step(self, x, y, optimizer=None, global_batch=None):
-        """forward + MSE + backward (+ Adam when ``optimizer`` is a FusedAdam over this model) in one C call; fills
-        ``self.bucket`` = [grad | loss]; returns (pred [B], loss 0-d tensor) on the device, no host sync."""
-        x2d = self._check_input(x)
-        yv = y.reshape(-1).contiguous().float()
-        if yv.numel() != x2d.size(0):
-            raise RuntimeError("target size mismatch")
-        shp = self._shape(x2d.size(0))
-        a = self._args(shp, x2d, y=yv, global_batch=global_batch)
-        o = self._adam_args(optimizer)
-        _lib.check(_lib.load().rulgnn_stmsgcn_fwdbwd_f32(C.byref(shp), C.byref(a), o, _stream()), "rulgnn_stmsgcn_fwdbwd_f32")
-        return self._pred_buf, self._grad_flat[self._count]
-
     # ---- nn.Module surface -----------------------------------------------------------------------------
     def forward(self, x):
         x2d = self._check_input(x)
         if x2d.size(0) == 0:
             return torch.empty(0, 1, dtype=torch.float32, device=x2d.device)
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self._named()):
-            return _Function.apply(self, x2d, *self._named())
-        return self._forward(x2d).clone().view(-1, 1)
+        return self._predict(x2d, autograd=self._needs_grad())[0]

@@ -11,13 +11,11 @@ receives a gradient, exactly as in the reference.  There is no CPU path: a non-C
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 import torch.nn as nn
 
-from . import _lib, params as PL
-from .flat import FlatModule, current_stream as _stream
+from . import _lib
+from .flat import FlatModule
 
 
 class ChebNet(nn.Module):
@@ -28,34 +26,6 @@ class ChebNet(nn.Module):
         self.in_channels, self.out_channels, self.K = in_channels, out_channels, K
         self.filters = nn.Parameter(torch.Tensor(K, in_channels, out_channels))
         nn.init.xavier_uniform_(self.filters)
-
-
-class _Function(torch.autograd.Function):
-    """model(x, train=True) through rulgnn_stnet_forward_f32 / rulgnn_stnet_backward_f32.  The reconstruction loss is returned as a
-    0-d tensor whose incoming gradient must be 1 (it is a term of the reference's loss): the backward entry folds it in."""
-
-    @staticmethod
-    def forward(ctx, model, x, *params):
-        pred, recon = model._forward(x)
-        ctx.model, ctx.x = model, x
-        ctx.tape = model._tape.tokens[x.size(0)]
-        ctx.set_materialize_grads(False)
-        return pred.clone().view(-1, 1), recon.clone()
-
-    @staticmethod
-    def backward(ctx, dpred, drecon):
-        # The reconstruction term enters with whatever weight the objective gave it (the reference: 1, algorithms.py:458; a loss on the
-        # prediction alone: none) -- handed to the kernels as a device scalar, no host round trip.  A backward of the forward's own
-        # workspace: run once per forward (the reconstruction gradients are scaled in place).
-        model = ctx.model
-        model._tape.check(ctx.x.size(0), ctx.tape, model._bufs, "STNet_model")
-        B = ctx.x.size(0)
-        dp = dpred.reshape(-1).contiguous().float() if dpred is not None else torch.zeros(B, dtype=torch.float32, device=ctx.x.device)
-        w = drecon.reshape(1).contiguous().float() if drecon is not None else torch.zeros(1, dtype=torch.float32, device=ctx.x.device)
-        grads = model._backward(ctx.x, dp, recon_weight=w)
-        model._tape.consume(ctx.x.size(0), ctx.tape)
-        outs = [grads[off:off + n].view(shape).clone() if i >= 2 else None for i, (off, n, shape) in enumerate(model._slices)]
-        return (None, None, *outs)
 
 
 class STNet_model(FlatModule):
@@ -76,11 +46,13 @@ class STNet_model(FlatModule):
                                      nn.Linear(A, dims[-1] * self.num_nodes))
         self.lstm = nn.LSTM(input_size=A, hidden_size=self.lstm_hidden_dim, batch_first=True)
         self.linear = nn.Linear(self.lstm_hidden_dim * self.num_patch, 1)
-        self._tape = PL.ForwardTape()
         self._init_flat()
         self.optimized_range = (3, self._count)  # cnn.weight [2] + cnn.bias [1] come first and have no gradient
 
     bucket_tail = 2            # [gradient | loss | reconstruction]
+    gradless_params = 2        # cnn.weight, cnn.bias
+    # the reconstruction gradients are scaled in place by the backward: one backward per forward
+    consumes_tape = True
 
     @property
     def bucket(self):
@@ -88,6 +60,10 @@ class STNet_model(FlatModule):
         return self._grad_flat[:self._count + 1]
 
     # ---- C-ABI calls -----------------------------------------------------------------------------------
+    c_family, Args = "stnet", _lib.StnetArgs
+    not_covered = ("STNet HIP kernels do not cover this configuration (num_nodes = nperseg / 2 + 1, input_dim = 1 + patch_size / nperseg, "
+                   "even nperseg <= 64, <= 4 ChebNets)")
+
     def _shape(self, batch):
         s = _lib.StnetShape()
         s.batch, s.num_patch, s.patch_size, s.num_nodes, s.nperseg, s.input_dim = batch, self.num_patch, self.patch_size, self.num_nodes, self.nperseg, self.input_dim
@@ -98,10 +74,7 @@ class STNet_model(FlatModule):
         return s
 
     def _check_input(self, x):
-        if not x.is_cuda:
-            raise RuntimeError("STNet_model runs on the HIP path only: input must be a CUDA (ROCm) tensor; there is no CPU fallback")
-        if x.device != self._flat.device:
-            raise RuntimeError(f"input on {x.device} but model on {self._flat.device}")
+        self._require_device(x)
         bs = x.size(0)
         if x.numel() != bs * self.num_patch * self.patch_size:
             raise RuntimeError(f"shape '[{bs}, {self.num_patch}, {self.patch_size}]' is invalid for input of size {x.numel()}")
@@ -109,60 +82,27 @@ class STNet_model(FlatModule):
             raise RuntimeError("STNet HIP kernels cover up to 4 ChebNet layers")
         return x.reshape(bs, self.num_patch * self.patch_size).contiguous().float()
 
-    def _args(self, shp, x, y=None, dpred=None, global_batch=None):
-        B = x.size(0)
-        ent = self._workspace_entry(B, lambda: _lib.load().rulgnn_stnet_workspace_bytes(C.byref(shp)),
-                                    "STNet HIP kernels do not cover this configuration (num_nodes = nperseg / 2 + 1, input_dim = 1 + "
-                                    "patch_size / nperseg, even nperseg <= 64, <= 4 ChebNets)")
-        ws, pred = ent
-        a = _lib.StnetArgs()
-        a.x = x.data_ptr()
-        a.y = y.data_ptr() if y is not None else None
-        a.dpred = dpred.data_ptr() if dpred is not None else None
-        a.params, a.grads = self._flat.data_ptr(), self._grad_flat.data_ptr()
-        a.pred = pred.data_ptr()
-        a.loss = self._grad_flat.data_ptr() + 4 * self._count
+    def _args(self, shp, x, y=None, dpred=None, global_batch=None, recon_weight=None):
+        a = super()._args(shp, x, y, dpred, global_batch)
         a.recon = self._grad_flat.data_ptr() + 4 * (self._count + 1)
-        a.workspace, a.workspace_bytes = ws.data_ptr(), ws.numel()
-        a.global_batch = B if global_batch is None else int(global_batch)
-        return a, pred
-
-    def _forward(self, x):
-        shp = self._shape(x.size(0))
-        self._tape.mark(x.size(0))
-        a, pred = self._args(shp, x)
-        _lib.check(_lib.load().rulgnn_stnet_forward_f32(C.byref(shp), C.byref(a), _stream()), "rulgnn_stnet_forward_f32")
-        return pred[:x.size(0)], self._grad_flat[self._count + 1]
-
-    def _backward(self, x, dpred, recon_weight=None):
-        shp = self._shape(x.size(0))
-        a, _ = self._args(shp, x, dpred=dpred)
         a.recon_weight = recon_weight.data_ptr() if recon_weight is not None else None
-        _lib.check(_lib.load().rulgnn_stnet_backward_f32(C.byref(shp), C.byref(a), _stream()), "rulgnn_stnet_backward_f32")
-        return self._grad_flat
+        return a
 
-    def fused_mse_step(self, x, y, optimizer=None, global_batch=None):
-        """forward + MSE + reconstruction loss + backward (+ Adam when ``optimizer`` is a FusedAdam over this model) in one C call;
-        fills ``self.bucket`` = [grad | loss]; returns (pred [B], loss 0-d tensor) on the device, no host sync."""
-        x = self._check_input(x)
-        yv = y.reshape(-1).contiguous().float()
-        if yv.numel() != x.size(0):
-            raise RuntimeError("target size mismatch")
-        shp = self._shape(x.size(0))
-        self._tape.mark(x.size(0))
-        a, pred = self._args(shp, x, y=yv, global_batch=global_batch)
-        o = self._adam_args(optimizer)
-        _lib.check(_lib.load().rulgnn_stnet_fwdbwd_f32(C.byref(shp), C.byref(a), o, _stream()), "rulgnn_stnet_fwdbwd_f32")
-        return pred[:x.size(0)], self._grad_flat[self._count]
+    def _run_forward(self, x):
+        """(prediction, reconstruction loss): the reconstruction term is a 0-d tensor whose incoming gradient must be 1 (it is a term of
+        the reference's loss)."""
+        return super()._run_forward(x) + (self._grad_flat[self._count + 1],)
+
+    def _run_backward(self, x, douts):
+        # The reconstruction term enters with whatever weight the objective gave it (the reference: 1, algorithms.py:458; a loss on the
+        # prediction alone: 0) -- handed to the kernels as a device scalar, no host round trip.
+        w = douts[1].reshape(1).contiguous().float()
+        return super()._run_backward(x, douts, recon_weight=w)
 
     # ---- nn.Module surface -----------------------------------------------------------------------------
     def forward(self, x, train=False):
         x2 = self._check_input(x)
         if x2.size(0) == 0:
             raise RuntimeError("STNet_model: empty batch")
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self._named()):
-            pred, recon = _Function.apply(self, x2, *self._named())
-        else:
-            p, r = self._forward(x2)
-            pred, recon = p.clone().view(-1, 1), r.clone()
+        pred, recon = self._predict(x2, autograd=self._needs_grad())
         return (pred, recon) if train else pred

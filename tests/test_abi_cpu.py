@@ -4,6 +4,9 @@ import ctypes as C
 import os
 import re
 
+import pytest
+import torch
+
 from gnn_rul_benchmarking_amd import _lib, build, params as PL
 
 from conftest import ROOT
@@ -80,3 +83,57 @@ def test_single_hip_runtime_even_when_library_is_loaded_before_torch():
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr
     assert out.stdout.strip().splitlines()[-1] == "1", out.stdout
+
+
+# (family, dataset, dataset id, C entry prefix, argument struct): the fwdbwd entries whose rulgnn_adam_args validation is pinned below
+_FWDBWD_FAMILIES = [("STGNN", "CMAPSS", "FD004", "stgnn", _lib.StmsgcnArgs), ("STNet", "PHM2012", "Condition_1", "stnet", _lib.StnetArgs),
+                    ("SAGCN", "PHM2012", "Condition_2", "sagcn", _lib.SagcnArgs), ("RGCNU", "CMAPSS", "FD004", "rgcnu", _lib.RgcnuArgs),
+                    ("STAGNN", "CMAPSS", "FD001", "stagnn", _lib.StagnnArgs), ("ST_Conv", "CMAPSS", "FD004", "stconv", _lib.AstgcnnArgs),
+                    ("STMSGCN", "XJTU_SY", "Condition_1", "stmsgcn", _lib.StmsgcnArgs),
+                    ("FC_STGNN", "CMAPSS", "FD004", "fcstgnn", _lib.FcstgnnArgs), ("ASTGCNN", "NCMAPSS", None, "astgcnn", _lib.AstgcnnArgs)]
+_BN_OPT_FAMILIES = ("ST_Conv", "FC_STGNN", "ASTGCNN")          # their entries also check opt->bn_stats
+
+
+@pytest.mark.skipif(torch.cuda.is_available(),
+                    reason="placeholder device pointers: a case that got through would launch kernels on them")
+@pytest.mark.parametrize("family,ds,did,prefix,Args", _FWDBWD_FAMILIES)
+def test_fwdbwd_rejects_bad_adam_arguments_before_any_launch(family, ds, did, prefix, Args):
+    """Every rulgnn_<family>_fwdbwd_f32 validates its rulgnn_adam_args the same way, in the same order, before any launch: the step
+    (or a device step state) and ``opt->params == args->params`` first, then null / misaligned optimizer pointers (EINVAL / EALIGN),
+    then -- BatchNorm families -- ``opt->bn_stats``.  Every other argument is a valid placeholder, so the codes come from that check."""
+    from gnn_rul_benchmarking_amd.algorithms import get_algorithm_class
+    from gnn_rul_benchmarking_amd.hparams import get_hparams_class
+    h = get_hparams_class(ds)(did)
+    model = get_algorithm_class(family)(h.alg_hparams[family], h.train_params[family], "cpu").model
+    lib = _lib.load()
+    entry = getattr(lib, f"rulgnn_{prefix}_fwdbwd_f32")
+    B, base = 4, 1 << 20
+    shp = model._shape(B)
+    a = Args()
+    for i, (name, ctype) in enumerate(a._fields_):
+        if ctype is C.c_void_p and name not in ("dpred", "recon_weight", "step_state", "aux_stream"):
+            setattr(a, name, base + 256 * i)
+    a.workspace_bytes, a.global_batch = 1 << 40, B
+    if hasattr(a, "training"):
+        a.training = 1
+
+    def code(**opt):
+        o = _lib.AdamArgs(a.params, base + 65536, base + 131072, None, 1, 1e-3, 0.9, 0.999, 1e-8, 0.0, 0.1, None)
+        for k, v in opt.items():
+            setattr(o, k, v)
+        return entry(C.byref(shp), C.byref(a), C.byref(o), None)
+
+    EINVAL, EALIGN = _lib.EINVAL, _lib.EALIGN
+    assert code(step=0) == EINVAL                                        # no step and no device step state
+    assert code(params=a.params + 4) == EINVAL                           # an optimizer over other parameters
+    assert code(params=None) == EINVAL
+    assert code(exp_avg=None) == EINVAL
+    assert code(exp_avg_sq=None) == EINVAL
+    assert code(exp_avg=base + 65538) == EALIGN
+    assert code(exp_avg_sq=base + 131074) == EALIGN
+    assert code(step=0, step_state=base + 196608, exp_avg=base + 65538) == EALIGN     # a device step state stands in for the step
+    assert code(step=0, exp_avg=base + 65538) == EINVAL                  # the step check fires before the pointer checks
+    assert code(params=a.params + 4, exp_avg=None) == EINVAL
+    if family in _BN_OPT_FAMILIES:
+        assert code(bn_stats=base + 196610) == EINVAL                    # misaligned running statistics
+        assert code(bn_stats=base + 196610, exp_avg=base + 65538) == EALIGN

@@ -100,3 +100,50 @@ def test_adam_block_and_side_stream_defaults():
     assert s.pointer(torch.device("cpu"), training=False) is None
     s.enabled = False
     assert s.pointer(torch.device("cpu"), training=True) is None
+
+
+class _AutogradToy(FlatModule):
+    """y = lin(x) through the shared autograd Function; the "workspace" of a batch size holds the forward's input, which the backward
+    reads -- the same hazard the HIP families have."""
+
+    def __init__(self, consumes_tape=False, gradless_params=0):
+        super().__init__()
+        self.lin = nn.Linear(3, 1)
+        self.consumes_tape, self.gradless_params = consumes_tape, gradless_params
+        self._init_flat()
+
+    def _run_forward(self, x):
+        self._tape.mark(x.size(0))
+        self._bufs[x.size(0)] = (x.clone(),)
+        return (x @ self.lin.weight.detach().t() + self.lin.bias.detach(),)
+
+    def _run_backward(self, x, douts):
+        saved, d = self._bufs[x.size(0)][0], douts[0].reshape(-1, 1)
+        self._grad_flat[:3] = (d * saved).sum(0)
+        self._grad_flat[3] = d.sum()
+        return self._grad_flat
+
+
+def test_shared_autograd_function_raises_on_overwritten_activations_and_returns_per_parameter_gradients():
+    torch.manual_seed(0)
+    m, x = _AutogradToy(), torch.rand(4, 3)
+    p1 = m._predict(x, autograd=True)[0]
+    with torch.no_grad():
+        m._predict(x * 0.5, autograd=False)                   # a second forward of the same batch size before the backward
+    with pytest.raises(RuntimeError, match="overwritten"):
+        p1.sum().backward()
+    p2 = m._predict(x, autograd=True)[0]
+    m._predict(torch.rand(5, 3), autograd=False)              # another batch size has its own workspace
+    p2.sum().backward()
+    assert torch.allclose(m.lin.weight.grad, x.sum(0, keepdim=True)) and float(m.lin.bias.grad) == 4.0
+    assert m.lin.weight.grad.data_ptr() != m._grad_flat.data_ptr()                      # clones, not views of the bucket
+
+
+def test_shared_autograd_function_consumes_the_tape_and_skips_gradless_parameters():
+    x = torch.rand(4, 3)
+    m = _AutogradToy(consumes_tape=True, gradless_params=1)
+    loss = m._predict(x, autograd=True)[0].sum()
+    loss.backward(retain_graph=True)
+    assert m.lin.weight.grad is None and float(m.lin.bias.grad) == 4.0
+    with pytest.raises(RuntimeError, match="ran twice"):
+        loss.backward()

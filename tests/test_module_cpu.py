@@ -118,7 +118,7 @@ def test_noop_to_keeps_the_flat_buffers_and_a_real_move_notifies_listeners(famil
 
 def test_forward_tape_tokens():
     """params.ForwardTape: the token of a batch size changes with every forward that writes its workspace; a stale token or an evicted
-    workspace raises (the four flat-parameter models of round 2 use it in their autograd Functions)."""
+    workspace raises (the autograd Function every flat-parameter model shares, flat._FlatFunction, checks it)."""
     from gnn_rul_benchmarking_amd.params import ForwardTape
     tape, bufs = ForwardTape(), {8: object(), 4: object()}
     t8 = tape.mark(8)
