@@ -79,8 +79,6 @@ class ASTGCNN_model(FlatModule):
         self.chebnet = ChebNet(self.encoder_out_dim, self.output_dim, self.K)
         self.fc = nn.Linear(self.output_dim, 1)
 
-        self._bn_names = [f"tcn.conv_block{b}.2.running_{k}" for b in (1, 2) for k in ("mean", "var")]
-        self._bn = self._bn_batch = None
         # (off by default: with the step's five parameter-gradient products as one launch pair behind the backward chain, one stream is
         # faster -- 0.119 vs 0.122 ms per step at N-CMAPSS batch 512; ``enabled = True`` runs the pair beside the TCN backward instead)
         self.side_stream = PL.SideStream()
@@ -90,24 +88,7 @@ class ASTGCNN_model(FlatModule):
 
     # ---- flat storage ----------------------------------------------------------------------------------
     workspace_slots = 4
-
-    def _bucket_floats(self):
-        return self._count + 1 + 4 * self.num_nodes                   # [gradient | loss | BatchNorm batch moments]
-
-    def _reflatten_buffers(self, dev):
-        N = self.num_nodes
-        bufs = dict(self.named_buffers())
-        bn = torch.empty(4 * N, dtype=torch.float32, device=dev)
-        nbt = torch.zeros(2, dtype=torch.int64, device=dev)
-        for i, name in enumerate(self._bn_names):
-            bn[i * N:(i + 1) * N].copy_(bufs[name].detach().float())
-            self._set_buffer(name, bn[i * N:(i + 1) * N])
-        for b in (1, 2):
-            cname = f"tcn.conv_block{b}.2.num_batches_tracked"
-            nbt[b - 1].copy_(bufs[cname])
-            self._set_buffer(cname, nbt[b - 1])
-        self._bn, self._nbt = bn, nbt
-        self._bn_batch = torch.zeros(4 * N, dtype=torch.float32, device=dev)
+    bn_modules = ("tcn.conv_block1.2", "tcn.conv_block2.2")
 
     # ---- C-ABI calls -----------------------------------------------------------------------------------
     c_family, Args = "astgcnn", _lib.AstgcnnArgs
@@ -127,13 +108,7 @@ class ASTGCNN_model(FlatModule):
 
     def _args(self, shp, x2d, training, y=None, dpred=None, global_batch=None, moments_to_bucket=False):
         a = super()._args(shp, x2d, y, dpred, global_batch)
-        a.bn_stats = self._bn.data_ptr()
-        if moments_to_bucket:
-            a.bn_batch = self._grad_flat.data_ptr() + 4 * (self._count + 1)
-            a.bn_moment_weight = x2d.size(0) / float(a.global_batch)
-        else:
-            a.bn_batch = self._bn_batch.data_ptr()
-            a.bn_moment_weight = 0.0
+        self._bn_args(a, x2d.size(0), moments_to_bucket)
         a.training = 1 if training else 0
         a.aux_stream = self.side_stream.pointer(self._flat.device, training)
         return a
@@ -141,8 +116,7 @@ class ASTGCNN_model(FlatModule):
     def _after_train_forward(self, batch, from_bucket_moments=False, from_bucket_stats=False):
         """BatchNorm side effects of a training forward (running stats, num_batches_tracked).  ``from_bucket_moments``: the bucket
         tail holds the all-reduced (E[z], E[z^2]) (local BatchNorm); ``from_bucket_stats``: the global (mean, var) (synchronised)."""
-        in_bucket = from_bucket_moments or from_bucket_stats
-        src = self._grad_flat.data_ptr() + 4 * (self._count + 1) if in_bucket else self._bn_batch.data_ptr()
+        src = self._bn_source(from_bucket_moments or from_bucket_stats)
         shp = self._shape(batch)
         _lib.check(_lib.load().rulgnn_astgcnn_bn_running_update_f32(C.byref(shp), self._bn.data_ptr(), src,
                                                                     batch * self.time_length, 0.1,
@@ -154,13 +128,7 @@ class ASTGCNN_model(FlatModule):
                        moments_to_bucket=False):
         """train forward + MSE + backward (+ Adam and the running-statistics update when ``optimizer`` is a FusedAdam over
         this model) in one C call; fills ``self.bucket``; returns (pred [B], loss 0-d tensor) on the device."""
-        x2d, yv = self._step_inputs(x, y)
-        out = self._fused_step(x2d, yv, optimizer, global_batch, True, bn=self._bn, moments_to_bucket=moments_to_bucket)
-        if optimizer is not None:
-            self._nbt_pending += 1
-        elif update_running_stats:
-            self._after_train_forward(x2d.size(0))
-        return out
+        return self._bn_fused_mse_step(x, y, optimizer, global_batch, update_running_stats, moments_to_bucket)
 
     def sync_bn_schedule(self):
         """float64 counts of the all-reduces one synchronised-BatchNorm step issues, in order (dp.py: a rank with an empty shard joins
@@ -168,31 +136,9 @@ class ASTGCNN_model(FlatModule):
         return [50] * 4
 
     def fused_mse_step_syncbn(self, x, y, global_batch, sample_offset, bn_param_grad_scale, allreduce):
-        """``fused_mse_step`` on this rank's shard with every BatchNorm normalising by the GLOBAL batch's statistics (dp.py,
-        ``DataParallel(sync_bn=True)``; rulgnn_astgcnn_fwdbwd_syncbn_f32).  ``allreduce(view)`` is called 4 times with a float64 view of 50 reduction cells
-        inside the workspace and must SUM it over the ranks in place, in stream order.  Fills ``self.bucket`` such that a SUM over the
-        ranks is the global-batch gradient / loss (the BatchNorm scale / shift gradients are global sums on every rank and enter
-        multiplied by ``bn_param_grad_scale``), and ``self._bn_batch`` with the global (mean, biased variance)."""
-        x2d, yv = self._step_inputs(x, y)
-        shp = self._shape(x2d.size(0))
-        self._tape.mark(x2d.size(0))
-        a = self._args(shp, x2d, True, y=yv, global_batch=global_batch)
-        cb, user, failure = _lib.allreduce_callback(allreduce, self._ws)
-        rc = _lib.load().rulgnn_astgcnn_fwdbwd_syncbn_f32(C.byref(shp), C.byref(a), float(bn_param_grad_scale), cb, user, _stream())
-        if failure:
-            raise failure[0]
-        _lib.check(rc, "rulgnn_astgcnn_fwdbwd_syncbn_f32")
-        return self._pred_buf, self._grad_flat[self._count]
+        """See ``FlatModule._syncbn_step`` (rulgnn_astgcnn_fwdbwd_syncbn_f32)."""
+        return self._syncbn_step("rulgnn_astgcnn_fwdbwd_syncbn_f32", x, y, global_batch, bn_param_grad_scale, allreduce)
 
     # ---- nn.Module surface -----------------------------------------------------------------------------
     def forward(self, X):
-        x2d = self._check_input(X)
-        if x2d.size(0) == 0:
-            if self.training:
-                raise RuntimeError("training forward needs a non-empty batch")
-            return torch.empty(0, 1, dtype=torch.float32, device=x2d.device)
-        if not self.training:
-            return self._predict(x2d, False, autograd=False)[0]
-        pred = self._predict(x2d, True, autograd=torch.is_grad_enabled())[0]
-        self._after_train_forward(x2d.size(0))
-        return pred
+        return self._bn_forward(X)

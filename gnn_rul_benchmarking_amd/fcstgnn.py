@@ -101,9 +101,6 @@ class FC_STGNN_RUL(FlatModule):
             ('fc3', nn.Linear(2 * hidden_dim, hidden_dim)), ('relu3', nn.ReLU(inplace=True)),
             ('fc4', nn.Linear(hidden_dim, 1))]))
 
-        # flat layout = named_parameters() order (the order include/rulgnn.h documents)
-        self._bn_ch = [dict(self.named_buffers())[n + ".running_mean"].numel() for n in BN_NAMES]
-        self._bn = self._bn_batch = None
         self.side_stream = PL.SideStream()
         self._step = 0
         self._seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
@@ -113,33 +110,14 @@ class FC_STGNN_RUL(FlatModule):
         # optimizer -- BASELINE.json's "FC_STGNN ... bf16" variant, reported separately (rulgnn.h: rulgnn_fcstgnn_args.compute_dtype)
         self.compute_dtype = "f32"
         self._track_batchnorm_counters()
-        self._init_flat()
+        self._init_flat()                   # flat layout = named_parameters() order (the order include/rulgnn.h documents)
         lib_count = _lib.load().rulgnn_fcstgnn_param_count(C.byref(self._shape(1)))
         if lib_count >= 0 and lib_count != self._count:
             raise RuntimeError(f"flat parameter layout mismatch: module {self._count} vs kernels {lib_count}")
 
     # ---- flat storage ----------------------------------------------------------------------------------
     workspace_slots = 4
-
-    def _bucket_floats(self):
-        return self._count + 1 + 2 * sum(self._bn_ch)                 # [gradient | loss | BatchNorm batch moments]
-
-    def _reflatten_buffers(self, dev):
-        bufs = dict(self.named_buffers())
-        total = 2 * sum(self._bn_ch)
-        bn = torch.empty(total, dtype=torch.float32, device=dev)
-        nbt = torch.zeros(len(BN_NAMES), dtype=torch.int64, device=dev)
-        o = 0
-        for i, (name, c) in enumerate(zip(BN_NAMES, self._bn_ch)):
-            bn[o:o + c].copy_(bufs[name + ".running_mean"].detach().float())
-            bn[o + c:o + 2 * c].copy_(bufs[name + ".running_var"].detach().float())
-            self._set_buffer(name + ".running_mean", bn[o:o + c])
-            self._set_buffer(name + ".running_var", bn[o + c:o + 2 * c])
-            nbt[i].copy_(bufs[name + ".num_batches_tracked"])
-            self._set_buffer(name + ".num_batches_tracked", nbt[i])
-            o += 2 * c
-        self._bn, self._nbt = bn, nbt
-        self._bn_batch = torch.zeros(total, dtype=torch.float32, device=dev)
+    bn_modules = BN_NAMES
 
     # ---- C-ABI calls -----------------------------------------------------------------------------------
     c_family, Args = "fcstgnn", _lib.FcstgnnArgs
@@ -163,13 +141,7 @@ class FC_STGNN_RUL(FlatModule):
 
     def _args(self, shp, x2d, training, step, y=None, dpred=None, global_batch=None, sample_offset=0, moments_to_bucket=False):
         a = super()._args(shp, x2d, y, dpred, global_batch)
-        a.bn_stats = self._bn.data_ptr()
-        if moments_to_bucket:
-            a.bn_batch = self._grad_flat.data_ptr() + 4 * (self._count + 1)
-            a.bn_moment_weight = x2d.size(0) / float(a.global_batch)
-        else:
-            a.bn_batch = self._bn_batch.data_ptr()
-            a.bn_moment_weight = 0.0
+        self._bn_args(a, x2d.size(0), moments_to_bucket)
         a.sample_offset = int(sample_offset)
         a.dropout_p = float(self.dropout_p)
         a.seed = self._seed
@@ -182,30 +154,29 @@ class FC_STGNN_RUL(FlatModule):
         a.compute_dtype = _lib.DTYPE_BF16 if self.compute_dtype == "bf16" else _lib.DTYPE_F32
         return a
 
-    def _after_train_forward(self, batch=None, from_bucket_moments=False, from_bucket_stats=False):
-        """BatchNorm side effects of a training forward.  ``batch``: the (global) batch the statistics were taken over;
-        only needed when it differs from the last forward's (data parallel).  ``from_bucket_moments``: the bucket tail holds
-        the all-reduced (E[z], E[z^2]) (local BatchNorm); ``from_bucket_stats``: it holds the global (mean, var) (synchronised)."""
-        in_bucket = from_bucket_moments or from_bucket_stats
-        src = self._grad_flat.data_ptr() + 4 * (self._count + 1) if in_bucket else self._bn_batch.data_ptr()
-        shp = self._shape(int(batch) if batch is not None else self._pred_buf.numel())
+    def _after_train_forward(self, batch, from_bucket_moments=False, from_bucket_stats=False):
+        """BatchNorm side effects of a training forward.  ``batch``: the (global) batch the statistics were taken over.
+        ``from_bucket_moments``: the bucket tail holds the all-reduced (E[z], E[z^2]) (local BatchNorm); ``from_bucket_stats``: it
+        holds the global (mean, var) (synchronised)."""
+        src = self._bn_source(from_bucket_moments or from_bucket_stats)
+        shp = self._shape(int(batch))
         _lib.check(_lib.load().rulgnn_fcstgnn_bn_running_update_f32(C.byref(shp), self._bn.data_ptr(), src, 0.1,
                                                                     1 if from_bucket_moments else 0, _stream()),
                    "rulgnn_fcstgnn_bn_running_update_f32")
         self._nbt_pending += 1
 
+    def _forward_state(self, training):
+        """(training, dropout step): a training forward draws the next step."""
+        if not training:
+            return False, 0
+        self._step += 1
+        return True, self._step
+
     def fused_mse_step(self, x, y, optimizer=None, global_batch=None, sample_offset=0, update_running_stats=True,
                        moments_to_bucket=False):
         """train forward + MSE + backward (+ Adam and the running statistics with ``optimizer``) in one C call."""
-        x2d, yv = self._step_inputs(x, y)
-        self._step += 1
-        out = self._fused_step(x2d, yv, optimizer, global_batch, True, self._step, bn=self._bn, sample_offset=sample_offset,
-                               moments_to_bucket=moments_to_bucket)
-        if optimizer is not None:
-            self._nbt_pending += 1
-        elif update_running_stats:
-            self._after_train_forward(x2d.size(0))
-        return out
+        return self._bn_fused_mse_step(x, y, optimizer, global_batch, update_running_stats, moments_to_bucket,
+                                       sample_offset=sample_offset)
 
     def sync_bn_schedule(self):
         """float64 counts of the all-reduces one synchronised-BatchNorm step issues, in order (dp.py: a rank with an empty shard joins
@@ -213,33 +184,10 @@ class FC_STGNN_RUL(FlatModule):
         return [128] * 14
 
     def fused_mse_step_syncbn(self, x, y, global_batch, sample_offset, bn_param_grad_scale, allreduce):
-        """``fused_mse_step`` on this rank's shard with every BatchNorm normalising by the GLOBAL batch's statistics (dp.py,
-        ``DataParallel(sync_bn=True)``; rulgnn_fcstgnn_fwdbwd_syncbn_f32).  ``allreduce(view)`` is called 14 times with a float64 view of 128 reduction cells
-        inside the workspace and must SUM it over the ranks in place, in stream order.  Fills ``self.bucket`` such that a SUM over the
-        ranks is the global-batch gradient / loss (the BatchNorm scale / shift gradients are global sums on every rank and enter
-        multiplied by ``bn_param_grad_scale``), and ``self._bn_batch`` with the global (mean, biased variance)."""
-        x2d, yv = self._step_inputs(x, y)
-        self._step += 1
-        shp = self._shape(x2d.size(0))
-        self._tape.mark(x2d.size(0))
-        a = self._args(shp, x2d, True, self._step, y=yv, global_batch=global_batch, sample_offset=sample_offset)
-        cb, user, failure = _lib.allreduce_callback(allreduce, self._ws)
-        rc = _lib.load().rulgnn_fcstgnn_fwdbwd_syncbn_f32(C.byref(shp), C.byref(a), float(bn_param_grad_scale), cb, user, _stream())
-        if failure:
-            raise failure[0]
-        _lib.check(rc, "rulgnn_fcstgnn_fwdbwd_syncbn_f32")
-        return self._pred_buf, self._grad_flat[self._count]
+        """See ``FlatModule._syncbn_step`` (rulgnn_fcstgnn_fwdbwd_syncbn_f32)."""
+        return self._syncbn_step("rulgnn_fcstgnn_fwdbwd_syncbn_f32", x, y, global_batch, bn_param_grad_scale, allreduce,
+                                 sample_offset=sample_offset)
 
     # ---- nn.Module surface -----------------------------------------------------------------------------
     def forward(self, X):
-        x2d = self._check_input(X)
-        if x2d.size(0) == 0:
-            if self.training:
-                raise RuntimeError("training forward needs a non-empty batch")
-            return torch.empty(0, 1, dtype=torch.float32, device=x2d.device)
-        if not self.training:
-            return self._predict(x2d, False, 0, autograd=False)[0]
-        self._step += 1
-        pred = self._predict(x2d, True, self._step, autograd=torch.is_grad_enabled())[0]
-        self._after_train_forward()
-        return pred
+        return self._bn_forward(X)

@@ -7,14 +7,15 @@ weights, same ``state_dict`` keys; the sub-modules only hold parameters) and run
   * ``_flat``       every parameter, in the order of the family's flat layout (include/rulgnn.h); the ``nn.Parameter``s are views
   * ``_grad_flat``  ``[gradient | loss | family extras]`` -- what the kernels write and one all-reduce carries (``bucket``)
   * ``_bufs``       per-batch-size workspaces (activations kept from forward to backward), a small LRU
-  * BatchNorm statistics / counters of the families that have them live in ``_bn`` / ``_nbt`` (``_reflatten_buffers`` hook)
+  * ``_bn`` / ``_nbt``  the BatchNorm statistics / counters of the families that have them (``bn_modules``), the modules' buffers are views
 
 ``nn.Module._apply`` (``.to()``, ``.float()``...) converts tensors one by one: ``_apply`` below rebuilds the views when that
 happened and leaves everything in place when it was a no-op (the per-epoch ``model.to(device)`` of the trainers; captured
 hipGraphs and the optimizer state point into the buffers).
 
 A family describes its C entries as data (``c_family``, ``Args``, ``not_covered``...) and keeps what is its own: ``_shape``, the shape
-check of ``_check_input``, the family fields of ``_args``, its BatchNorm hooks and the ``forward`` the reference pins."""
+check of ``_check_input``, the family fields of ``_args``, its BatchNorm running-statistics entry and the ``forward`` the reference
+pins."""
 from __future__ import annotations
 
 import ctypes as C
@@ -99,10 +100,15 @@ class FlatModule(nn.Module):
     def _named_live(self):
         return list(zip(self._layout, self._named()))
 
-    # ---- BatchNorm counters ----------------------------------------------------------------------------
-    # num_batches_tracked of the families with BatchNorm: a fused step only counts (``_nbt_pending``); the int64 device tensor ``_nbt``
-    # (the modules' buffers are views of it) is brought up to date when somebody looks (state_dict, a move)
-    _nbt, _nbt_pending = None, 0
+    # ---- BatchNorm state --------------------------------------------------------------------------------
+    # A family with BatchNorm names its modules in ``bn_modules``.  ``_bn`` holds every module's running_mean then running_var, module
+    # after module: the fp32 buffer the kernels read.  ``_bn_batch`` has the same layout for the batch statistics of the latest training
+    # forward, and the bucket carries one more such block behind the loss (data parallel: the batch moments, all-reduced with the
+    # gradient).  num_batches_tracked: a fused step only counts (``_nbt_pending``); the int64 device tensor ``_nbt`` (one per module) is
+    # brought up to date when somebody looks (state_dict, a move).  The modules' buffers are views of ``_bn`` / ``_nbt``.
+    bn_modules = ()
+    _bn = _bn_batch = _nbt = None
+    _nbt_pending = 0
 
     def _track_batchnorm_counters(self):
         """Call in ``__init__`` before ``_init_flat``."""
@@ -114,12 +120,47 @@ class FlatModule(nn.Module):
             self._nbt += self._nbt_pending
             self._nbt_pending = 0
 
+    def _reflatten_buffers(self, dev):
+        """Move the statistics / counters of ``bn_modules`` into ``_bn`` / ``_nbt`` and allocate a zeroed ``_bn_batch``.  A family with
+        another layout overrides this."""
+        if not self.bn_modules:
+            return
+        bufs = dict(self.named_buffers())
+        stats = [f"{m}.{leaf}" for m in self.bn_modules for leaf in ("running_mean", "running_var")]
+        bn = torch.empty(sum(bufs[name].numel() for name in stats), dtype=torch.float32, device=dev)
+        off = 0
+        for name in stats:
+            n = bufs[name].numel()
+            bn[off:off + n].copy_(bufs[name].detach().float())
+            self._set_buffer(name, bn[off:off + n])
+            off += n
+        nbt = torch.zeros(len(self.bn_modules), dtype=torch.int64, device=dev)
+        for i, m in enumerate(self.bn_modules):
+            nbt[i].copy_(bufs[m + ".num_batches_tracked"])
+            self._set_buffer(m + ".num_batches_tracked", nbt[i])
+        self._bn, self._nbt = bn, nbt
+        self._bn_batch = torch.zeros_like(bn)
+
+    def _bn_args(self, a, batch, moments_to_bucket=False):
+        """The BatchNorm fields of ``a`` for a call at ``batch``: the running statistics (where the struct has them) and where a training
+        forward leaves its batch statistics -- ``_bn_batch``, or with ``moments_to_bucket`` (data parallel) the bucket's block, as the
+        moments (E[z], E[z^2]) weighted batch / global_batch, which the all-reduce sums to the global batch's."""
+        if hasattr(self.Args, "bn_stats"):
+            a.bn_stats = self._bn.data_ptr()
+        if moments_to_bucket:
+            a.bn_batch = self._bn_source(True)
+            a.bn_moment_weight = batch / float(a.global_batch)
+        else:
+            a.bn_batch = self._bn_batch.data_ptr()
+            a.bn_moment_weight = 0.0
+
+    def _bn_source(self, in_bucket):
+        """The batch statistics a running-statistics update reads: the bucket's block behind the loss, or ``_bn_batch``."""
+        return self._grad_flat.data_ptr() + 4 * (self._count + self.bucket_tail) if in_bucket else self._bn_batch.data_ptr()
+
     # ---- flat storage ----------------------------------------------------------------------------------
     def _bucket_floats(self) -> int:
-        return self._count + self.bucket_tail
-
-    def _reflatten_buffers(self, dev):
-        """Hook: move the family's BatchNorm statistics / counters into their flat buffers (``_bn``, ``_nbt``)."""
+        return self._count + self.bucket_tail + (self._bn.numel() if self.bn_modules else 0)
 
     def _reset_caches(self):
         self._bufs, self._step_state = {}, None
@@ -268,6 +309,56 @@ class FlatModule(nn.Module):
         """forward + MSE + backward (+ Adam when ``optimizer`` is a FusedAdam over this model) in one C call; fills ``self.bucket`` =
         [grad | loss]; returns (pred [B], loss 0-d tensor) on the device, no host sync."""
         return self._fused_step(*self._step_inputs(x, y), optimizer, global_batch)
+
+    def _forward_state(self, training):
+        """``state`` of one forward of the shared BatchNorm-family paths below (what ``_args`` takes after ``x``): the training flag.  A
+        family that draws dropout per step overrides this and advances its step here."""
+        return (training,)
+
+    def _bn_fused_mse_step(self, x, y, optimizer, global_batch, update_running_stats, moments_to_bucket, **fields):
+        """``fused_mse_step`` of a BatchNorm family.  With ``optimizer`` the C call also updates the running statistics; without, they are
+        updated here unless ``update_running_stats`` is False (data parallel: after the all-reduce, from the bucket)."""
+        x, yv = self._step_inputs(x, y)
+        out = self._fused_step(x, yv, optimizer, global_batch, *self._forward_state(True), bn=self._bn,
+                               moments_to_bucket=moments_to_bucket, **fields)
+        if optimizer is not None:
+            self._nbt_pending += 1
+        elif update_running_stats:
+            self._after_train_forward(x.size(0))
+        return out
+
+    def _syncbn_step(self, entry, x, y, global_batch, bn_param_grad_scale, allreduce, *more, **fields):
+        """``fused_mse_step_syncbn`` (dp.py, ``DataParallel(sync_bn=True)``): the step on this rank's shard with every BatchNorm
+        normalising by the GLOBAL batch's statistics, one ``entry(shape, args, bn_param_grad_scale, callback, user, *more, stream)`` call.
+        It calls ``allreduce(view)`` once per ``sync_bn_schedule()`` count with a float64 view of that many reduction cells inside the
+        workspace, which must SUM it over the ranks in place, in stream order.  Fills ``self.bucket`` such that a SUM over the ranks is
+        the global-batch gradient / loss (the BatchNorm scale / shift gradients are global sums on every rank and enter multiplied by
+        ``bn_param_grad_scale``), and ``self._bn_batch`` with the global (mean, biased variance)."""
+        x, yv = self._step_inputs(x, y)
+        state = self._forward_state(True)
+        shp = self._shape(x.size(0))
+        self._tape.mark(x.size(0))
+        a = self._args(shp, x, *state, y=yv, global_batch=global_batch, **fields)
+        cb, user, failure = _lib.allreduce_callback(allreduce, self._ws)
+        rc = getattr(_lib.load(), entry)(C.byref(shp), C.byref(a), float(bn_param_grad_scale), cb, user, *more, current_stream())
+        if failure:
+            raise failure[0]
+        _lib.check(rc, entry)
+        return self._pred_buf, self._grad_flat[self._count]
+
+    def _bn_forward(self, x):
+        """``forward`` of a BatchNorm family: the prediction [B, 1]; in training through autograd when grad mode is on, and the running
+        statistics advance.  An empty batch gives an empty prediction in eval and raises in training, as BatchNorm does."""
+        x = self._check_input(x)
+        if x.size(0) == 0:
+            if self.training:
+                raise RuntimeError("training forward needs a non-empty batch")
+            return torch.empty(0, 1, dtype=torch.float32, device=x.device)
+        if not self.training:
+            return self._predict(x, *self._forward_state(False), autograd=False)[0]
+        pred = self._predict(x, *self._forward_state(True), autograd=torch.is_grad_enabled())[0]
+        self._after_train_forward(x.size(0))
+        return pred
 
     def _needs_grad(self):
         return torch.is_grad_enabled() and any(p.requires_grad for p in self._named())

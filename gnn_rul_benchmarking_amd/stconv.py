@@ -55,36 +55,18 @@ class ST_Conv_model(FlatModule):
         self.theta4 = nn.Parameter(torch.randn(1))
         self.fc = nn.Linear(num_nodes * time_length, 1)
 
-        self._bn = self._bn_batch = None
         self._track_batchnorm_counters()
         self._init_flat()
 
     # ---- flat storage ----------------------------------------------------------------------------------
     flat_order = LIVE                                                  # the parameters the forward uses; the rest stay ordinary tensors
     workspace_slots = 4
+    bn_modules = BN_NAMES
 
     def _flush_nbt(self):
         if self._nbt_pending and self._nbt is not None:
             self._nbt += 2 * self._nbt_pending          # every live BatchNorm runs twice per training forward (Model.py:196-206)
             self._nbt_pending = 0
-
-    def _bucket_floats(self):
-        return self._count + 1 + 6 * self.num_nodes                   # [gradient | loss | BatchNorm batch moments]
-
-    def _reflatten_buffers(self, dev):
-        N = self.num_nodes
-        bufs = dict(self.named_buffers())
-        bn = torch.empty(6 * N, dtype=torch.float32, device=dev)
-        nbt = torch.zeros(3, dtype=torch.int64, device=dev)
-        for i, name in enumerate(BN_NAMES):
-            for j, leaf in enumerate(("running_mean", "running_var")):
-                sl = bn[(2 * i + j) * N:(2 * i + j + 1) * N]
-                sl.copy_(bufs[f"{name}.{leaf}"].detach().float())
-                self._set_buffer(f"{name}.{leaf}", sl)
-            nbt[i].copy_(bufs[name + ".num_batches_tracked"])
-            self._set_buffer(name + ".num_batches_tracked", nbt[i])
-        self._bn, self._nbt = bn, nbt
-        self._bn_batch = torch.zeros(6 * N, dtype=torch.float32, device=dev)
 
     # ---- C-ABI calls -----------------------------------------------------------------------------------
     c_family, Args = "stconv", _lib.AstgcnnArgs
@@ -101,18 +83,12 @@ class ST_Conv_model(FlatModule):
 
     def _args(self, shp, x2d, training, y=None, dpred=None, global_batch=None, moments_to_bucket=False):
         a = super()._args(shp, x2d, y, dpred, global_batch)
-        a.bn_stats = self._bn.data_ptr()
-        if moments_to_bucket:
-            a.bn_batch = self._grad_flat.data_ptr() + 4 * (self._count + 1)
-            a.bn_moment_weight = x2d.size(0) / float(a.global_batch)
-        else:
-            a.bn_batch = self._bn_batch.data_ptr()
-            a.bn_moment_weight = 0.0
+        self._bn_args(a, x2d.size(0), moments_to_bucket)
         a.training = 1 if training else 0
         return a
 
     def _after_train_forward(self, batch, from_bucket_moments=False):
-        src = self._grad_flat.data_ptr() + 4 * (self._count + 1) if from_bucket_moments else self._bn_batch.data_ptr()
+        src = self._bn_source(from_bucket_moments)
         shp = self._shape(batch)
         _lib.check(_lib.load().rulgnn_stconv_bn_running_update_f32(C.byref(shp), self._bn.data_ptr(), src, batch * self.time_length,
                                                                    0.1, 1 if from_bucket_moments else 0, _stream()),
@@ -122,23 +98,8 @@ class ST_Conv_model(FlatModule):
     def fused_mse_step(self, x, y, optimizer=None, global_batch=None, sample_offset=0, update_running_stats=True,
                        moments_to_bucket=False):
         """train forward + MSE + backward (+ Adam and the running statistics with ``optimizer``) in one C call."""
-        x2d, yv = self._step_inputs(x, y)
-        out = self._fused_step(x2d, yv, optimizer, global_batch, True, bn=self._bn, moments_to_bucket=moments_to_bucket)
-        if optimizer is not None:
-            self._nbt_pending += 1
-        elif update_running_stats:
-            self._after_train_forward(x2d.size(0))
-        return out
+        return self._bn_fused_mse_step(x, y, optimizer, global_batch, update_running_stats, moments_to_bucket)
 
     # ---- nn.Module surface -----------------------------------------------------------------------------
     def forward(self, x):
-        x2d = self._check_input(x)
-        if x2d.size(0) == 0:
-            if self.training:
-                raise RuntimeError("training forward needs a non-empty batch")
-            return torch.empty(0, 1, dtype=torch.float32, device=x2d.device)
-        if not self.training:
-            return self._predict(x2d, False, autograd=False)[0]
-        pred = self._predict(x2d, True, autograd=torch.is_grad_enabled())[0]
-        self._after_train_forward(x2d.size(0))
-        return pred
+        return self._bn_forward(x)

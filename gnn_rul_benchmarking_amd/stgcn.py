@@ -67,34 +67,6 @@ class SG_TCN(nn.Module):
                 nn.Dropout(dropout)]))
 
 
-# --------------------------------------------------------------------------------------------
-# autograd bridge
-# --------------------------------------------------------------------------------------------
-class _TrainFunction(torch.autograd.Function):
-    """model(X) in train mode: forward = rulgnn_stgcn_train_forward_f32, backward =
-    rulgnn_stgcn_train_backward_f32 with the incoming d(loss)/d(pred)."""
-
-    @staticmethod
-    def forward(ctx, model, x2d, *live):
-        pred = model._train_forward(x2d)
-        ctx.model = model
-        ctx.x2d = x2d
-        ctx.step = model._step
-        return pred.view(-1, 1)
-
-    @staticmethod
-    def backward(ctx, dpred):
-        model = ctx.model
-        B = ctx.x2d.size(0)
-        if model._tape_step.get(B) != ctx.step or B not in model._bufs:
-            raise RuntimeError("ST_GCN_model: another training forward of this batch size ran between this forward and its backward "
-                               "(or its workspace was evicted); the saved activations live in one workspace per batch size, not per "
-                               "call, and were overwritten. Call backward() before the next model(x), or use Algorithm.update.")
-        grads = model._train_backward(ctx.x2d, dpred.contiguous().view(-1).float(), ctx.step)
-        out = [grads[off:off + n].view(shape).clone() for (off, n, shape) in model._live_slices]
-        return (None, None, *out)
-
-
 class ST_GCN_model(FlatModule):
     def __init__(self, num_patch, patch_size, num_layers=2, dropout=0.5, k=1):
         super().__init__()
@@ -107,8 +79,7 @@ class ST_GCN_model(FlatModule):
         # fp32 phases in one launch with device-side grid barriers (same bits as the chain, measured slower: an explicit option)
         self.step_path = _lib.STEP_AUTO
         self._last_chain = _lib.STEP_CHAIN   # what the latest whole step resolved to (guard_tensor / retry_on_fp32_chain)
-        self._clean_ws = None                # the workspace a matrix-core whole step left clean (see _train_args)
-        self._tape_step = {}            # batch size -> step whose activations its workspace holds (autograd-path hazard check)
+        self._clean_ws = None                # the workspace a matrix-core whole step left clean (see _args)
         self.side_stream = PL.SideStream()   # tiled path: parameter-gradient products beside the backward chain (aux_stream)
         self.k = int(k)
         in_features = NUM_STATS
@@ -118,9 +89,11 @@ class ST_GCN_model(FlatModule):
         self.fc1 = nn.Linear(self.num_patch, self.num_patch)
         self.fc2 = nn.Linear(self.num_patch, 1)
 
-        self._bn_layout = PL.bn_buffer_layout(self.num_layers)
-        self._bn = None             # [L][2][2][10] running statistics; _nbt: [2L] num_batches_tracked
-        self._bn_batch = self._loss = self._ws = self._pred_buf = self._fwd_ws = None
+        # _bn: [L][2][2][10] running statistics (params.bn_buffer_layout); _nbt: [2L] num_batches_tracked
+        self.bn_modules = tuple(f"sg_tcn.layers.{l}.1.conv_block{b}.2" for l in range(self.num_layers) for b in (1, 2))
+        self.not_covered = (f"ST_GCN training kernels do not cover num_patch={self.num_patch}, num_layers={self.num_layers} at MPNN order "
+                            f"k={self.k} (num_patch 2..4096, patch_size 2..4096, num_layers 1..8; k = 2, 3 for num_patch <= 64 only)")
+        self._fwd_ws = None
         self._step = 0              # training forwards so far (dropout stream position)
         self._seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
         self._track_batchnorm_counters()
@@ -128,33 +101,13 @@ class ST_GCN_model(FlatModule):
         # _bufs: batch size -> (training workspace, prediction buffer), several sizes stay alive; _pin_bufs (graphs.py): captured
         # hipGraphs hold these pointers, never evict; _step_state: device step state (graphs.py), else the host counters are used
         self._init_flat(PL.live_param_layout(self.num_patch, self.num_layers, self.k), PL.param_count(self.num_patch, self.num_layers, self.k))
-        self._live_slices = self._slices
 
     # ---- flat storage --------------------------------------------------------------------------
     workspace_slots = 4
 
-    def _bucket_floats(self):                                          # [gradient (P) | loss (1) | BatchNorm batch moments (2L*2*10)]
-        return self._count + 1 + PL.bn_buffer_count(self.num_layers)
-
-    def _reflatten_buffers(self, dev):
-        bufs = dict(self.named_buffers())
-        bn = torch.empty(PL.bn_buffer_count(self.num_layers), dtype=torch.float32, device=dev)
-        nbt = torch.zeros(2 * self.num_layers, dtype=torch.int64, device=dev)
-        for i, (name, (off, shape)) in enumerate(self._bn_layout.items()):
-            bn[off:off + NUM_STATS].copy_(bufs[name].detach().float())
-            self._set_buffer(name, bn[off:off + NUM_STATS])
-            if name.endswith("running_mean"):
-                cname = name[:-len("running_mean")] + "num_batches_tracked"
-                nbt[i // 2].copy_(bufs[cname])
-                self._set_buffer(cname, nbt[i // 2])
-        self._bn, self._nbt = bn, nbt
-        self._bn_batch = torch.zeros(PL.bn_buffer_count(self.num_layers), dtype=torch.float32, device=dev)
-        self._loss = torch.zeros(1, dtype=torch.float32, device=dev)
-
     def _reset_caches(self):
         super()._reset_caches()
-        self._pred_buf = self._ws = self._fwd_ws = None
-        self._clean_ws = None
+        self._fwd_ws = self._clean_ws = None
         self._guard_off = {}             # batch size -> byte offset of the workspace's sticky guard counter (-1: none)
         self._guard_seen = {}            # batch size -> count already reported
         self._guard_dp = None            # data parallel: device count of the all-reduced losses that came back NaN (dp.py)
@@ -162,61 +115,42 @@ class ST_GCN_model(FlatModule):
         self._guard_carry = 0            # counts read early (before a workspace eviction), not yet reported
 
     # ---- C-ABI calls ---------------------------------------------------------------------------------
+    c_family, Args = "stgcn_train", _lib.StgcnTrainArgs        # the training entries; the eval forward has its own (forward)
+
     def _shape(self, batch):
         return _lib.StgcnShape(batch, self.num_patch, self.patch_size, self.num_layers, self.k)
 
     def _check_input(self, x):
-        if not x.is_cuda:
-            raise RuntimeError("ST_GCN_model runs on the HIP kernels only: input must be a CUDA (ROCm) tensor; "
-                               "there is no CPU fallback")
-        if x.device != self._flat.device:
-            raise RuntimeError(f"input on {x.device} but model on {self._flat.device}")
+        self._require_device(x)
         bs = x.size(0)
         if x.numel() != bs * self.num_patch * self.patch_size:
             raise RuntimeError(f"shape '[{bs}, {self.num_patch}, {self.patch_size}]' is invalid for input of size {x.numel()}")
         return x.reshape(bs, self.num_patch * self.patch_size).contiguous().float()
 
-    def _workspace(self, shp, batch):
-        fresh = batch not in self._bufs
+    def _workspace_entry(self, key, nbytes, unsupported, make=None):
+        """FlatModule's, plus the guard counter each training workspace carries."""
+        fresh = key not in self._bufs
         if fresh and self._guard_unchecked and len(self._bufs) >= self.workspace_slots and not self._pin_bufs:
             self._guard_carry += self.guard_trips()      # a workspace is about to be evicted: its count must not go with it
             self._guard_unchecked = True
-        ent = self._workspace_entry(batch, lambda: _lib.load().rulgnn_stgcn_train_workspace_bytes(C.byref(shp)),
-                                    f"ST_GCN training kernels do not cover num_patch={self.num_patch}, num_layers={self.num_layers} "
-                                    f"at MPNN order k={self.k} (num_patch 2..4096, patch_size 2..4096, num_layers 1..8; k = 2, 3 for "
-                                    "num_patch <= 64 only)",
-                                    make=lambda dev: (torch.empty(batch, dtype=torch.float32, device=dev),))
-        self._ws, self._pred_buf = ent
+        ent = super()._workspace_entry(key, nbytes, unsupported, make)
         if fresh:            # the sticky count of guard-rejected steps lives in the workspace and is only ever ADDED to by the kernels
-            off = int(_lib.load().rulgnn_stgcn_train_guard_counter_offset(C.byref(shp)))
-            self._guard_off[batch] = off
+            off = int(_lib.load().rulgnn_stgcn_train_guard_counter_offset(C.byref(self._shape(key))))
+            self._guard_off[key] = off
             if off >= 0:
-                self._ws[off:off + 4].zero_()
-            self._guard_seen.pop(batch, None)     # a re-created workspace counts from zero again (the old total stayed)
-        return self._ws
+                ent[0][off:off + 4].zero_()
+            self._guard_seen.pop(key, None)       # a re-created workspace counts from zero again (ADVICE r5: the old total stayed)
+        return ent
+
+    def _args(self, shp, x2d, step, y=None, dpred=None, **fields):
+        return self._train_args(shp, x2d, y, dpred, step, **fields)
 
     def _train_args(self, shp, x2d, y, dpred, step, global_batch=None, sample_offset=0, moments_to_bucket=False, whole_step=False):
-        B = x2d.size(0)
-        ws = self._workspace(shp, B)
-        self._tape_step[B] = int(step)
-        a = _lib.StgcnTrainArgs()
-        a.x = x2d.data_ptr()
-        a.y = y.data_ptr() if y is not None else None
-        a.dpred = dpred.data_ptr() if dpred is not None else None
-        a.params = self._flat.data_ptr()
-        a.grads = self._grad_flat.data_ptr()
-        a.pred = self._pred_buf.data_ptr()
-        a.loss = self._grad_flat.data_ptr() + 4 * self.num_live      # loss lands right behind the gradient
-        gb = B if global_batch is None else int(global_batch)
-        if moments_to_bucket:      # data parallel: w*(E[z], E[z^2]) behind the loss, summed by the all-reduce
-            a.bn_batch = self._grad_flat.data_ptr() + 4 * (self.num_live + 1)
-            a.bn_moment_weight = B / float(gb)
-        else:
-            a.bn_batch = self._bn_batch.data_ptr()
-            a.bn_moment_weight = 0.0
-        a.workspace = ws.data_ptr()
-        a.workspace_bytes = ws.numel()
-        a.global_batch = gb
+        """FlatModule's ``_args`` with ST_GCN's fields (every ST_GCN call builds its struct here; benchlib/roofline.py and the tests call
+        it in this positional order).  ``whole_step``: the call is a whole training step (forward + backward in one entry); it resolves
+        its launch form here."""
+        a = super()._args(shp, x2d, y, dpred, global_batch)
+        self._bn_args(a, x2d.size(0), moments_to_bucket)
         a.sample_offset = int(sample_offset)
         a.dropout_p = self.dropout_p
         a.seed = self._seed
@@ -224,11 +158,18 @@ class ST_GCN_model(FlatModule):
         a.step_state = self._step_state.data_ptr() if self._step_state is not None else None
         # RULGNN_TRAIN_WS_CLEAN: a whole step on the matrix-core chain leaves the reduction cells zero; when the LAST use of this very
         # workspace was such a step, the next one runs without its prepare launch (any other use of the workspace drops the claim)
-        a.flags = _lib.TRAIN_WS_CLEAN if (whole_step and self._clean_ws is ws and self._step_state is None) else 0
+        a.flags = _lib.TRAIN_WS_CLEAN if (whole_step and self._clean_ws is self._ws and self._step_state is None) else 0
         # the tiled path's parameter-gradient products beside its backward chain (include/rulgnn.h: aux_stream; the fused chains ignore it)
         a.aux_stream = self.side_stream.pointer(self._flat.device, True) if (self.num_patch > 64 and self._flat.is_cuda) else None
         self._clean_ws = None
+        if whole_step:
+            self._resolve_chain(shp, x2d)
         return a
+
+    def _forward_state(self, training=True):
+        """(dropout step,) of a training forward: the next one.  (The eval forward has an entry of its own.)"""
+        self._step += 1
+        return (self._step,)
 
     def _whole_step_done(self):
         self._clean_ws = self._ws if self._last_chain == _lib.STEP_MX else None
@@ -315,8 +256,7 @@ class ST_GCN_model(FlatModule):
         """BatchNorm side effects of a training forward (running stats, num_batches_tracked).
         ``from_bucket_moments``: use the all-reduced global-batch moments (E[z], E[z^2]) in the bucket tail;
         ``from_bucket_stats``: the bucket tail holds the global (mean, biased variance) themselves (synchronised BatchNorm)."""
-        in_bucket = from_bucket_moments or from_bucket_stats
-        src = self._grad_flat.data_ptr() + 4 * (self.num_live + 1) if in_bucket else self._bn_batch.data_ptr()
+        src = self._bn_source(from_bucket_moments or from_bucket_stats)
         guard = self.guard_tensor
         if guard is not None:
             _lib.check(_lib.load().rulgnn_bn_running_update_guarded_f32(self._bn.data_ptr(), src, self.num_layers,
@@ -347,27 +287,11 @@ class ST_GCN_model(FlatModule):
         _lib.check(_lib.load().rulgnn_adam_bn_step_f32(
             self.flat_params.data_ptr() + o, self.bucket.data_ptr() + o, m.data_ptr() + o, v.data_ptr() + o, end - start,
             optimizer._steps, float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
-            1.0, self._bn.data_ptr(), self._grad_flat.data_ptr() + 4 * (self.num_live + 1), self.num_layers,
+            1.0, self._bn.data_ptr(), self._bn_source(True), self.num_layers,
             batch * self.num_patch, 0.1, 1 if from_bucket_moments else 0, guard.data_ptr() if guard is not None else None,
             _stream()), "rulgnn_adam_bn_step_f32")
         self._nbt_pending += 1
         return True
-
-    def _train_forward(self, x2d):
-        self._step += 1
-        shp = self._shape(x2d.size(0))
-        a = self._train_args(shp, x2d, None, None, self._step)
-        _lib.check(_lib.load().rulgnn_stgcn_train_forward_f32(C.byref(shp), C.byref(a), _stream()),
-                   "rulgnn_stgcn_train_forward_f32")
-        self._after_train_forward(x2d.size(0))
-        return self._pred_buf.clone()
-
-    def _train_backward(self, x2d, dpred, step):
-        shp = self._shape(x2d.size(0))
-        a = self._train_args(shp, x2d, None, dpred, step)
-        _lib.check(_lib.load().rulgnn_stgcn_train_backward_f32(C.byref(shp), C.byref(a), _stream()),
-                   "rulgnn_stgcn_train_backward_f32")
-        return self._grad_flat
 
     def fused_mse_step(self, x, y, global_batch=None, sample_offset=0, update_running_stats=True,
                        moments_to_bucket=False, grad_ready=None):
@@ -379,14 +303,11 @@ class ST_GCN_model(FlatModule):
         ``bucket[offset:offset + count]`` has become final in stream order (rulgnn_stgcn_train_fwdbwd_ready_f32: the head and the
         theta blocks of the tiled path, num_patch > 64, whose bucket is megabytes); the callee starts that region's all-reduce on
         another stream.  What is not reported is final when the call's work has drained."""
-        x2d = self._check_input(x)
-        yv = y.reshape(-1).contiguous().float()
-        if yv.numel() != x2d.size(0):
-            raise RuntimeError("target size mismatch")
-        self._step += 1
+        x2d, yv = self._step_inputs(x, y)
         shp = self._shape(x2d.size(0))
-        a = self._train_args(shp, x2d, yv, None, self._step, global_batch, sample_offset, moments_to_bucket, whole_step=True)
-        self._resolve_chain(shp, x2d)
+        self._tape.mark(x2d.size(0))
+        a = self._args(shp, x2d, *self._forward_state(), y=yv, global_batch=global_batch, sample_offset=sample_offset,
+                       moments_to_bucket=moments_to_bucket, whole_step=True)
         if grad_ready is not None:
             failure = []
 
@@ -403,12 +324,11 @@ class ST_GCN_model(FlatModule):
                 raise failure[0]
             _lib.check(rc, "rulgnn_stgcn_train_fwdbwd_ready_f32")
         else:
-            _lib.check(_lib.load().rulgnn_stgcn_train_step_path_f32(C.byref(shp), C.byref(a), None, int(self.step_path), _stream()),
-                       "rulgnn_stgcn_train_step_path_f32")
+            self._call("step_path", shp, a, None, int(self.step_path))
             self._whole_step_done()
         if update_running_stats:
             self._after_train_forward(x2d.size(0))
-        return self._pred_buf, self._grad_flat[self.num_live]
+        return self._pred_buf, self._grad_flat[self._count]
 
     @property
     def reports_ready_gradients(self):
@@ -435,48 +355,24 @@ class ST_GCN_model(FlatModule):
         return [20] * (self.SYNC_BN_PAIRS_PER_LAYER * self.num_layers)
 
     def fused_mse_step_syncbn(self, x, y, global_batch, sample_offset, bn_param_grad_scale, allreduce):
-        """``fused_mse_step`` on this rank's shard with every BatchNorm normalising by the GLOBAL batch's statistics (dp.py,
-        ``DataParallel(sync_bn=True)``).  ``allreduce(view)`` is called 4 L times with a float64 view of 20 reduction cells inside
-        the workspace and must SUM it over the ranks in place, in stream order.  Fills ``self.bucket`` = [grad | loss | ...] such
-        that a SUM over the ranks is the global-batch gradient / loss (the BatchNorm scale / shift gradients are global sums on every
-        rank and enter multiplied by ``bn_param_grad_scale``: 1 on one rank, 0 elsewhere), and ``self._bn_batch`` with the global
-        (mean, var)."""
-        x2d = self._check_input(x)
-        yv = y.reshape(-1).contiguous().float()
-        if yv.numel() != x2d.size(0):
-            raise RuntimeError("target size mismatch")
-        self._step += 1
-        shp = self._shape(x2d.size(0))
-        a = self._train_args(shp, x2d, yv, None, self._step, global_batch, sample_offset, False, whole_step=True)
-        self._resolve_chain(shp, x2d)
-        ws = self._ws
-        cb, user, failure = _lib.allreduce_callback(allreduce, ws)
+        """See ``FlatModule._syncbn_step`` (4 L all-reduces of 20 cells; ``bn_param_grad_scale`` is 1 on one rank, 0 elsewhere)."""
         # the launch form is the model's (step_path): after a guard trip retry_on_fp32_chain() must really land on the fp32 phases
-        rc = _lib.load().rulgnn_stgcn_train_fwdbwd_syncbn_path_f32(C.byref(shp), C.byref(a), float(bn_param_grad_scale), cb, user,
-                                                                   int(self.step_path), _stream())
-        if failure:
-            raise failure[0]
-        _lib.check(rc, "rulgnn_stgcn_train_fwdbwd_syncbn_path_f32")
+        out = self._syncbn_step("rulgnn_stgcn_train_fwdbwd_syncbn_path_f32", x, y, global_batch, bn_param_grad_scale, allreduce,
+                                int(self.step_path), sample_offset=sample_offset, whole_step=True)
         self._whole_step_done()
-        return self._pred_buf, self._grad_flat[self.num_live]
+        return out
 
     def fused_train_step(self, x, y, optimizer):
         """The whole ``ST_GCN.update`` body in ONE C call (single GPU): forward, MSE, backward, and -- inside the
         kernel that finalises the gradient -- Adam and the BatchNorm running statistics."""
-        x2d = self._check_input(x)
-        yv = y.reshape(-1).contiguous().float()
-        if yv.numel() != x2d.size(0):
-            raise RuntimeError("target size mismatch")
-        self._step += 1
+        x2d, yv = self._step_inputs(x, y)
         shp = self._shape(x2d.size(0))
-        a = self._train_args(shp, x2d, yv, None, self._step, whole_step=True)
-        self._resolve_chain(shp, x2d)
-        o = self._adam_args(optimizer, bn=self._bn)
-        _lib.check(_lib.load().rulgnn_stgcn_train_step_path_f32(C.byref(shp), C.byref(a), o, int(self.step_path), _stream()),
-                   "rulgnn_stgcn_train_step_path_f32")
+        self._tape.mark(x2d.size(0))
+        a = self._args(shp, x2d, *self._forward_state(), y=yv, whole_step=True)
+        self._call("step_path", shp, a, self._adam_args(optimizer, bn=self._bn), int(self.step_path))
         self._whole_step_done()
         self._nbt_pending += 1
-        return self._pred_buf, self._grad_flat[self.num_live]
+        return self._pred_buf, self._grad_flat[self._count]
 
     # ---- nn.Module surface -------------------------------------------------------------------------------
     def forward(self, x):
@@ -485,9 +381,9 @@ class ST_GCN_model(FlatModule):
         if self.training:
             if B == 0:
                 raise RuntimeError("training forward needs a non-empty batch")
-            if torch.is_grad_enabled():
-                return _TrainFunction.apply(self, x2d, *[p for _, p in self._named_live()])
-            return self._train_forward(x2d).view(-1, 1)
+            pred = self._predict(x2d, *self._forward_state(), autograd=torch.is_grad_enabled())[0]
+            self._after_train_forward(B)
+            return pred
         out = torch.empty(B, dtype=torch.float32, device=x2d.device)
         shp = self._shape(B)
         nbytes = _lib.load().rulgnn_stgcn_forward_workspace_bytes(C.byref(shp))       # 0 on the fused path

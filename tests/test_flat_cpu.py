@@ -4,13 +4,14 @@ import pytest
 import torch
 import torch.nn as nn
 
-from gnn_rul_benchmarking_amd import params as PL
+from gnn_rul_benchmarking_amd import _lib, params as PL
 from gnn_rul_benchmarking_amd.flat import FlatModule
 
 
 class _Toy(FlatModule):
     bucket_tail = 3
     workspace_slots = 2
+    bn_modules = ("bn",)
 
     def __init__(self, order=None):
         super().__init__()
@@ -19,19 +20,8 @@ class _Toy(FlatModule):
         self.bn = nn.BatchNorm1d(2)
         if order is not None:
             self.flat_order = order
-        self._bn = None
         self._track_batchnorm_counters()
         self._init_flat()
-
-    def _reflatten_buffers(self, dev):
-        bufs = dict(self.named_buffers())
-        self._bn = torch.empty(4, dtype=torch.float32, device=dev)
-        self._nbt = torch.zeros(1, dtype=torch.int64, device=dev)
-        for i, leaf in enumerate(("running_mean", "running_var")):
-            self._bn[2 * i:2 * i + 2].copy_(bufs[f"bn.{leaf}"])
-            self._set_buffer(f"bn.{leaf}", self._bn[2 * i:2 * i + 2])
-        self._nbt[0].copy_(bufs["bn.num_batches_tracked"])
-        self._set_buffer("bn.num_batches_tracked", self._nbt[0])
 
 
 def test_parameters_are_views_of_one_flat_buffer_in_layout_order():
@@ -40,7 +30,7 @@ def test_parameters_are_views_of_one_flat_buffer_in_layout_order():
     torch.manual_seed(0)
     m = _Toy()
     assert m.num_live == 6 + 2 + 2 + 1 + 2 + 2 and m.flat_params.numel() == m.num_live     # a.w a.b b.w b.b bn.weight bn.bias
-    assert m.bucket.numel() == m.num_live + 3
+    assert m.bucket.numel() == m.num_live + 3 + 4                                          # [gradient | tail | BatchNorm moments]
     off = 0
     for (name, p), (o, n, shape) in zip(m._named_live(), m._slices):
         assert o == off and tuple(p.shape) == shape
@@ -74,6 +64,53 @@ def test_batchnorm_counter_is_flushed_when_somebody_looks():
     m = _Toy()
     m._nbt_pending = 5
     assert int(m.state_dict()["bn.num_batches_tracked"]) == 5 and m._nbt_pending == 0
+
+
+def test_batchnorm_state_round_trips_through_the_flat_buffers():
+    """running_mean then running_var of every BatchNorm module, module after module, in ``_bn``; one counter per module in ``_nbt``;
+    the modules' buffers are views, so state_dict / load_state_dict and a rebuild go through the flat buffers."""
+    m = _Toy()
+    assert m._bn.numel() == m._bn_batch.numel() == 4 and not bool(m._bn_batch.any()) and m._nbt.numel() == 1
+    sd = m.state_dict()
+    sd["bn.running_mean"], sd["bn.running_var"], sd["bn.num_batches_tracked"] = (torch.tensor([1.0, 2.0]), torch.tensor([3.0, 4.0]),
+                                                                                torch.tensor(7))
+    m.load_state_dict(sd)
+    assert m._bn.tolist() == [1.0, 2.0, 3.0, 4.0] and m._nbt.tolist() == [7]
+    m._nbt_pending = 2
+    m.double()                                                                             # rebuilds the flat buffers from the modules'
+    assert m._bn.tolist() == [1.0, 2.0, 3.0, 4.0] and m._nbt.tolist() == [9] and m._nbt_pending == 0
+    assert m.bn.running_var.data_ptr() == m._bn.data_ptr() + 4 * 2 and m.bn.num_batches_tracked.data_ptr() == m._nbt.data_ptr()
+    back = m.state_dict()
+    assert back["bn.running_mean"].tolist() == [1.0, 2.0] and back["bn.running_var"].tolist() == [3.0, 4.0]
+    assert int(back["bn.num_batches_tracked"]) == 9
+
+
+def test_batchnorm_fields_of_the_argument_struct():
+    m = _Toy()
+    m.Args = _lib.AstgcnnArgs
+    a = m.Args()
+    a.global_batch = 8
+    m._bn_args(a, 2)
+    assert (a.bn_stats, a.bn_batch, a.bn_moment_weight) == (m._bn.data_ptr(), m._bn_batch.data_ptr(), 0.0)
+    m._bn_args(a, 2, moments_to_bucket=True)                                               # behind [gradient | tail], weight B / global
+    assert a.bn_batch == m.bucket.data_ptr() + 4 * (m.num_live + 3) == m._bn_source(True) and a.bn_moment_weight == 0.25
+    assert m._bn_source(False) == m._bn_batch.data_ptr()
+    m.Args = _lib.StgcnTrainArgs                                                           # no bn_stats field: left out
+    a = m.Args()
+    a.global_batch = 2
+    m._bn_args(a, 2, moments_to_bucket=True)
+    assert not hasattr(a, "bn_stats") and a.bn_moment_weight == 1.0
+
+
+def test_stgcn_batchnorm_modules_give_the_kernel_layout():
+    from gnn_rul_benchmarking_amd.stgcn import ST_GCN_model
+    for L in (1, 2, 3):
+        m = ST_GCN_model(14, 30, num_layers=L)
+        bufs = dict(m.named_buffers())
+        for name, (off, shape) in PL.bn_buffer_layout(L).items():
+            assert bufs[name].data_ptr() == m._bn.data_ptr() + 4 * off and tuple(bufs[name].shape) == shape
+        assert m._bn.numel() == PL.bn_buffer_count(L) and m._nbt.numel() == 2 * L
+        assert m.bucket.numel() == m.num_live + 1 + PL.bn_buffer_count(L)
 
 
 def test_workspace_cache_evicts_the_oldest_size_unless_pinned():

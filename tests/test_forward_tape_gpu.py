@@ -24,6 +24,22 @@ def _stgnn():
     return build, x, y
 
 
+def _stgcn():
+    from gnn_rul_benchmarking_amd import _lib
+    from gnn_rul_benchmarking_amd.stgcn import ST_GCN_model
+    torch.manual_seed(1)
+    x, y = torch.rand(16, 14, 30, device=DEV), torch.rand(16, 1, device=DEV)
+    sd = {k: v.clone() for k, v in ST_GCN_model(14, 30, dropout=0.2).state_dict().items()}
+
+    def build():
+        m = ST_GCN_model(14, 30, dropout=0.2)
+        m.load_state_dict(sd)
+        m._seed = 5                                  # one dropout stream for both models
+        m.step_path = _lib.STEP_CHAIN                # the fused step on the fp32 phases, the arithmetic of the forward / backward entries
+        return m.to(DEV)
+    return build, x, y
+
+
 def _golden(module, case, build_args=lambda T, z, rest: rest, **kw):
     """(model factory, x, y) of a family's golden case, built by that family's own GPU-test helpers."""
     T = __import__(module)
@@ -39,6 +55,7 @@ def _sd(z):
 
 # family -> (inputs, gradient tolerance of the family's own autograd-vs-fused test; None: bit-exact)
 FAMILIES = {
+    "ST_GCN": (_stgcn, (5e-4, 1e-6)),
     "STGNN": (_stgnn, (1e-4, 1e-7)),
     "STNet": (lambda: _golden("test_stnet_gpu", "stnet_phm_c3like_7x32_bs4"), None),
     "SAGCN": (lambda: _golden("test_sagcn_gpu", "sagcn_phm_c2like_9x20_bs4"), None),
