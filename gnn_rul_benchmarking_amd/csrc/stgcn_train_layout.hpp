@@ -91,45 +91,68 @@ __device__ __forceinline__ double cell_sum(const double* cells, int L, int i) {
 // COHERENT (the persistent small-batch launch, stgcn_train_mx.hip): the cells were completed by OTHER workgroups of this same launch
 // (agent-scope atomics, then a counter) -- read them with agent-scope atomic loads (L1-bypassing `sc1` loads: atomics on both sides).
 constexpr int BN_TABLE_ROWS = 7;        // mean, istd, gamma, beta, gamma istd, mean(dy), mean(dy xhat)
+// In two steps, so that a phase kernel can issue the loads at its entry, ahead of its parameter gathers and its first tile (the vector
+// memory counter retires in issue order: a wait for loads issued last is a wait for everything in front of them), and do the arithmetic
+// only where the table is needed.  The replicas land in sixteen registers before the first add: summed as they are loaded, the compiler
+// issues a few, waits for the first, issues the next few -- two round trips instead of one.
+struct BnPairRaw {
+    double t[CELL_REPLICAS];   // lane < 2 F: the replicas of cell `lane` of the pair
+    double cnt;                // lane < F: the values per channel behind the cells
+    float g, b;                // lane < F, forward pair: gamma, beta of channel `lane`
+};
 template <bool COHERENT = false>
-__device__ __forceinline__ void bn_pair_to_lds(const double* cells, const float* prm, float* bnc, int L, int N, bool fwd, int b, int lane) {
+__device__ __forceinline__ void bn_pair_load(BnPairRaw& p, const double* cells, const float* prm, int L, int N, bool fwd, int b, int lane) {
     const int CS = cell_stride(L);
     const int base = (fwd ? cell_fwd(L) : cell_bwd(L)) + b * 2 * F;
+    if (lane < 2 * F) {
+#pragma unroll
+        for (int r = 0; r < CELL_REPLICAS; ++r) {
+            if constexpr (COHERENT) p.t[r] = __hip_atomic_load(&cells[r * CS + base + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else p.t[r] = cells[r * CS + base + lane];
+        }
+    }
+    if (lane < F) {
+        p.cnt = step_scratch(const_cast<double*>(cells), L)->bn_count;
+        if (fwd) {
+            const int LS = layer_stride(N);
+            p.g = prm[(b / 2) * LS + off_bn_g(N, b % 2) + lane];
+            p.b = prm[(b / 2) * LS + off_bn_b(N, b % 2) + lane];
+        }
+    }
+}
+__device__ __forceinline__ void bn_pair_finish(const BnPairRaw& p, float* bnc, bool fwd, int b, int lane) {
     double v = 0.0;
     if (lane < 2 * F) {
-        if constexpr (COHERENT) {
-            double t[CELL_REPLICAS];
 #pragma unroll
-            for (int r = 0; r < CELL_REPLICAS; ++r) t[r] = __hip_atomic_load(&cells[r * CS + base + lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-            for (int r = 0; r < CELL_REPLICAS; ++r) v += t[r];
-        } else {
-#pragma unroll
-        for (int r = 0; r < CELL_REPLICAS; ++r) v += cells[r * CS + base + lane];
-        }
+        for (int r = 0; r < CELL_REPLICAS; ++r) v += p.t[r];        // the fixed order of cell_sum()
     }
     const double s1 = v, s2 = __shfl(v, (lane + F) & 63, 64);
     if (lane < F) {
         const int c = lane;
-        const double cnt = step_scratch(const_cast<double*>(cells), L)->bn_count;
+        const double cnt = p.cnt;
         float* o = bnc + b * BN_TABLE_ROWS * F;
         if (fwd) {
             const double mean = s1 / cnt;
             double var = s2 / cnt - mean * mean;
             var = var < 0.0 ? 0.0 : var;
             const double istd = 1.0 / sqrt(var + (double)BN_EPS);
-            const int LS = layer_stride(N);
-            const double g = prm[(b / 2) * LS + off_bn_g(N, b % 2) + c];
+            const double g = p.g;
             o[0 * F + c] = (float)mean;
             o[1 * F + c] = (float)istd;
             o[2 * F + c] = (float)g;
-            o[3 * F + c] = prm[(b / 2) * LS + off_bn_b(N, b % 2) + c];
+            o[3 * F + c] = p.b;
             o[4 * F + c] = (float)(g * istd);
         } else {
             o[5 * F + c] = (float)(s1 / cnt);
             o[6 * F + c] = (float)(s2 / cnt);
         }
     }
+}
+template <bool COHERENT = false>
+__device__ __forceinline__ void bn_pair_to_lds(const double* cells, const float* prm, float* bnc, int L, int N, bool fwd, int b, int lane) {
+    BnPairRaw p;
+    bn_pair_load<COHERENT>(p, cells, prm, L, N, fwd, b, lane);
+    bn_pair_finish(p, bnc, fwd, b, lane);
 }
 
 }  // namespace rulgnn

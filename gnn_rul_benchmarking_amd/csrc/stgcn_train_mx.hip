@@ -59,12 +59,24 @@ namespace rulgnn {
 // step's counter) right in front of the cell reads, i.e. behind its first tile's requests and the BatchNorm-independent half of the
 // prologue, and reads the cells with agent-scope atomic loads.  Everything else a phase reads was written by the wavefront itself (tile
 // t belongs to the same wavefront in every phase of a launch) or by an earlier launch.
+// (-DMXP_TRACE: workgroup 0, wavefront 0 stamps the marks below -- in the persistent launch and in the phase kernels alike -- and prints
+// them when the launch ends: 100 MHz ticks since the previous mark)
 #ifdef MXP_TRACE
 __device__ unsigned mxp_ts[128];
 __device__ int mxp_n;
 __device__ unsigned mxp_id[128];
-#define MXP_MARKI(ID) do { if (PERSIST && blockIdx.x == 0 && threadIdx.x == 0 && mxp_n < 128) { mxp_id[mxp_n] = ID; mxp_ts[mxp_n++] = (unsigned)wall_clock64(); } } while (0)
+#define MXP_MARKI(ID) do { if (blockIdx.x == 0 && threadIdx.x == 0 && mxp_n < 128) { mxp_id[mxp_n] = ID; mxp_ts[mxp_n++] = (unsigned)wall_clock64(); } } while (0)
 #define MXP_MARK() MXP_MARKI(0)
+__device__ __forceinline__ void mxp_dump() {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        for (int i = 0; i < mxp_n; ++i) {
+            if (mxp_id[i] >= 100) printf("\nphase %u:", mxp_id[i]);
+            else printf(" [%u] +%u", mxp_id[i], mxp_ts[i] - mxp_ts[i - 1]);
+        }
+        printf("\n");
+        mxp_n = 0;
+    }
+}
 #else
 #define MXP_MARK() do {} while (0)
 #define MXP_MARKI(ID) do {} while (0)
@@ -131,11 +143,23 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
         else if constexpr (GRAD_IN) dma(a.dx + t * XF, off_DX, 4 * XF);
     };
     auto req_XP = [&](int64_t t) { if constexpr (BWD_PREV) dma(a.qrec[LY] + t * XF, off_XP, 4 * XF); };
-    if (tile < a.ntiles) { req_XA(tile); req_SB(tile); req_DX(tile); req_XP(tile); }
 
-    // ---- prologue.  First everything that does not depend on a BatchNorm (parameter loads, theta / transposed-convolution / identity
-    // operands); then the BatchNorm constants from the reduction cells (one pair per wavefront, stgcn_train_layout.hpp); then the operands
-    // that fold a BatchNorm in ----------------------------------------------------------------------------------------------------
+    // ---- prologue.  The loads go out in three bursts, in the order their consumers need them -- the vector memory counter retires in
+    // issue order, so a wait for one burst is a wait for every burst in front of it: (1) the reduction cells, the BatchNorm count and
+    // gamma / beta of this wavefront's pair (one pair per wavefront, stgcn_train_layout.hpp); (2) the parameter gathers of the operands
+    // (theta, the convolutions, the transposed forms, TOP's head) and the dropout keys; (3) the first tile.  The BatchNorm table then waits
+    // for burst 1 alone; the operands that fold a BatchNorm in are built behind it --------------------------------------------------------
+    // the reduction pairs this phase's BatchNorm constants come from, one per wavefront: the forward pairs of the layers it runs
+    // (F_{2l+1}: 2l; F_{2l}, l >= 1: 2l-2, 2l-1; TOP, G_{2l+1}: 2l, 2l+1; G_{2l}: 2l) and the backward pair of BatchNorm IDX (G)
+    constexpr int FW0 = WITH_PREV ? 2 * LY - 2 : 2 * LY;                           // first forward pair
+    constexpr int NFW = (KIND == PH_F && BLK == 1) || (KIND == PH_G && BLK == 0) ? 1 : 2;
+    static_assert(NFW + (KIND == PH_G ? 1 : 0) <= MXT_WAVES, "one reduction pair per wavefront");
+    const bool bn_fwd = wave < NFW, bn_mine = bn_fwd || (KIND == PH_G && wave == NFW);
+    const int bn_b = bn_fwd ? FW0 + wave : IDX;
+    BnPairRaw bnraw;
+    // (PERSIST: the cells are complete only once the step's counter says so -- loaded behind the wait below)
+    if (!PERSIST && bn_mine) bn_pair_load<false>(bnraw, a.cells, a.prm, L, N, bn_fwd, bn_b, lane);
+    __builtin_amdgcn_sched_barrier(0);
     for (int i = lane; i < MXT_ZERO_FLOATS; i += 64) smem[off_zero + i] = 0.f;
     if (lane < 2) sh_tile[64 + 65 * lane] = u32x2{0u, 0u};
     // which convolutions of the main layer / the previous layer this phase runs, and how
@@ -159,12 +183,35 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
         const unsigned p01 = w[0] | (w[1] << 16), p23 = w[2] | (w[3] << 16);
         ident = u32x4{p01, p23, p01, p23};
     }
+    // head (TOP), row mapping: lane (sample row, t) holds row t and column t of fc1
+    float fc1w[16], fc1wT[16];
+    float fc1b = 0.f, fc2w = 0.f, fc2b = 0.f;
+    if constexpr (KIND == PH_TOP) {
+        const int colc = col < N ? col : 0;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const int kc2 = k < N ? k : 0;
+            const float v = a.prm[off_fc1_w(N, L) + colc * N + kc2], vt = a.prm[off_fc1_w(N, L) + kc2 * N + colc];
+            fc1w[k] = (col < N && k < N) ? v : 0.f;
+            fc1wT[k] = (col < N && k < N) ? vt : 0.f;
+        }
+        const float b1 = a.prm[off_fc1_b(N, L) + colc], w2 = a.prm[off_fc2_w(N, L) + colc];
+        fc1b = col < N ? b1 : 0.f;
+        fc2w = col < N ? w2 : 0.f;
+        fc2b = a.prm[off_fc2_b(N, L)];
+    }
+    uint32_t dkey[L];
+#pragma unroll
+    for (int l = 0; l < L; ++l) dkey[l] = step_scratch(a.cells, L)->drop_key[l];
+    const bool use_drop = a.dropout_p > 0.f;
+    uint32_t mask_next = 0u;                    // G_{2l+1}: the dropout mask of the tile in hand, read one tile ahead
+    constexpr bool MASK_IN = KIND == PH_G && BLK == 1;
+    if constexpr (MASK_IN) {
+        if (use_drop && tile < a.ntiles) mask_next = a.mrec[LY][tile * 64 + lane];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    if (tile < a.ntiles) { req_XA(tile); req_SB(tile); req_DX(tile); req_XP(tile); }
     {
-        // the reduction pairs this phase's BatchNorm constants come from, one per wavefront: the forward pairs of the layers it runs
-        // (F_{2l+1}: 2l; F_{2l}, l >= 1: 2l-2, 2l-1; TOP, G_{2l+1}: 2l, 2l+1; G_{2l}: 2l) and the backward pair of BatchNorm IDX (G)
-        constexpr int FW0 = WITH_PREV ? 2 * LY - 2 : 2 * LY;                       // first forward pair
-        constexpr int NFW = (KIND == PH_F && BLK == 1) || (KIND == PH_G && BLK == 0) ? 1 : 2;
-        static_assert(NFW + (KIND == PH_G ? 1 : 0) <= MXT_WAVES, "one reduction pair per wavefront");
         MXP_MARKI(2);                                                              // independent prologue done
         if constexpr (PERSIST) {
             if (threadIdx.x == 0) {
@@ -181,8 +228,10 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
         }
         constexpr bool COH = PERSIST;
         MXP_MARKI(3);                                                              // barrier passed
-        if (wave < NFW) bn_pair_to_lds<COH>(a.cells, a.prm, bnc, L, N, true, FW0 + wave, lane);
-        if (KIND == PH_G && wave == NFW) bn_pair_to_lds<COH>(a.cells, a.prm, bnc, L, N, false, IDX, lane);
+        if (bn_mine) {
+            if constexpr (PERSIST) bn_pair_load<COH>(bnraw, a.cells, a.prm, L, N, bn_fwd, bn_b, lane);
+            bn_pair_finish(bnraw, bnc, bn_fwd, bn_b, lane);
+        }
         if constexpr (KIND == PH_G) {
             wT = conv_bwd_pack(wT_raw);
             if constexpr (BLK == 0 && LY >= 1) thN = theta_pack(thN_raw);
@@ -204,23 +253,6 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
             bk1[r] = c >= 0 ? q[5 * F + c] * a.gscale : 0.f;      // carried x S like the gradients
             bk2[r] = c >= 0 ? q[6 * F + c] * a.gscale : 0.f;
         }
-    }
-    // head (TOP), row mapping: lane (sample row, t) holds row t and column t of fc1
-    float fc1w[16], fc1wT[16];
-    float fc1b = 0.f, fc2w = 0.f, fc2b = 0.f;
-    if constexpr (KIND == PH_TOP) {
-        const int colc = col < N ? col : 0;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            const int kc2 = k < N ? k : 0;
-            const float v = a.prm[off_fc1_w(N, L) + colc * N + kc2], vt = a.prm[off_fc1_w(N, L) + kc2 * N + colc];
-            fc1w[k] = (col < N && k < N) ? v : 0.f;
-            fc1wT[k] = (col < N && k < N) ? vt : 0.f;
-        }
-        const float b1 = a.prm[off_fc1_b(N, L) + colc], w2 = a.prm[off_fc2_w(N, L) + colc];
-        fc1b = col < N ? b1 : 0.f;
-        fc2w = col < N ? w2 : 0.f;
-        fc2b = a.prm[off_fc2_b(N, L)];
     }
 
     // ---- per-lane addressing ---------------------------------------------------------------------------------------------------
@@ -263,13 +295,9 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
     int sh_bk_lo = sh_bk + 65;
     asm volatile("" : "+v"(sh_rd1_lo), "+v"(sh_rd2_lo), "+v"(sh_bk_lo));
     const unsigned t_bias = g == 3 ? 0x3C00u << 16 : 0u;
-    uint32_t dkey[L];
-#pragma unroll
-    for (int l = 0; l < L; ++l) dkey[l] = step_scratch(a.cells, L)->drop_key[l];
     uint32_t dro[3];
 #pragma unroll
     for (int r = 0; r < 3; ++r) dro[r] = (uint32_t)((chan[r] >= 0 ? chan[r] : 0) * N + col);
-    const bool use_drop = a.dropout_p > 0.f;
 
     // ---- persistent accumulators ---------------------------------------------------------------------------------------------------
     float s_a[3] = {0.f, 0.f, 0.f}, s_b[3] = {0.f, 0.f, 0.f};      // BatchNorm reduction pair of this lane's channels
@@ -390,12 +418,7 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
     int pend_ns = 0;
     float pend_v[4][3], pend_q[4][3];
     float pend_top0 = 0.f, pend_top1 = 0.f, pend_pred = 0.f;
-    uint32_t pend_m = 0u;                       // dropout mask bits of the tile (F_{2l}, TOP: written; G_{2l+1}: this tile's, read one tile ahead)
-    uint32_t mask_next = 0u;
-    constexpr bool MASK_IN = KIND == PH_G && BLK == 1;
-    if constexpr (MASK_IN) {
-        if (use_drop && tile < a.ntiles) mask_next = a.mrec[LY][tile * 64 + lane];
-    }
+    uint32_t pend_m = 0u;                       // dropout mask bits of the tile (F_{2l}, TOP: written)
 #pragma unroll
     for (int s = 0; s < 4; ++s)
 #pragma unroll
@@ -413,6 +436,7 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
         const int64_t nt = tile + tstride;
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_wave_barrier();
+        if (!pend) MXP_MARKI(13);                                                  // the first tile in hand
         // ---- what the previous tile leaves: stored HERE, behind the wait that also counts stores ------------------------------------
         if (pend) {
             if constexpr (WITH_PREV) {
@@ -923,64 +947,63 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
     }
 
     MXP_MARKI(9);                                                                  // atomics issued
-    // ---- the workgroup's row of partial gradients: the wavefronts add their accumulators into an LDS image of the phase's contiguous
-    // parameter range in a fixed order, then the image leaves in coalesced stores -------------------------------------------------------------
+    // ---- the workgroup's row of partial gradients: every wavefront writes its accumulators into its own LDS image of the phase's contiguous
+    // parameter range (one round, one barrier), then the row store adds the four images in a fixed order, (w0 + w2) + (w1 + w3) -- the rows,
+    // and with them finalize, stay deterministic -- and the row leaves in coalesced stores ---------------------------------------------------
     const float us = a.inv_gscale;
     const int NN = N * N;
     int rbase = 0, rlen = 0;
-    // (two images -- the second over the wavefronts' regions, dead by now: wavefronts 0 | 1 store, then 2 | 3 add: two rounds, fixed order)
+    // (image 0 in the workgroup's region, images 1 .. 3 over the wavefronts' regions -- dead by now, 4 x wave_floats >= 3 x MXT_RED_FLOATS)
     float* const red2 = smem_all + SH_BNC + MXT_RED_FLOATS + 2 * MXT_WAVES * (2 * F + 2);
-    for (int w = 0; w < 2; ++w) {
-        if ((wave >> 1) == w) {
-            float* const img = (wave & 1) ? red2 : red;
-            auto put = [&](int idx, float v) { img[idx] = (w == 0) ? v : img[idx] + v; };
-            if constexpr (KIND == PH_TOP) {
-                // [fc1.w | fc1.b | fc2.w | fc2.b]; fc1.w in the fp32 MFMA's D layout: row j = 4 g + r, column k = col
+    {
+        float* const img = wave == 0 ? red : red2 + (wave - 1) * MXT_RED_FLOATS;
+        auto put = [&](int idx, float v) { img[idx] = v; };
+        if constexpr (KIND == PH_TOP) {
+            // [fc1.w | fc1.b | fc2.w | fc2.b]; fc1.w in the fp32 MFMA's D layout: row j = 4 g + r, column k = col
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int j = 4 * g + r;
+                if (j < N && col_ok) put(j * N + col, acc_th[r]);
+            }
+            float vb = acc_b, vw = acc_w2, v2 = acc_b2;
+            vb += __shfl_xor(vb, 16, 64); vb += __shfl_xor(vb, 32, 64);
+            vw += __shfl_xor(vw, 16, 64); vw += __shfl_xor(vw, 32, 64);
+            v2 += __shfl_xor(v2, 16, 64); v2 += __shfl_xor(v2, 32, 64);
+            if (g == 0 && col_ok) { put(NN + col, vb); put(NN + N + col, vw); }
+            if (lane == 0) put(NN + 2 * N, v2);
+        }
+        if constexpr (KIND == PH_G) {
+            const int ci = slot_chan(col);
+            const int cbase = BLK == 0 ? NN + N : 0;                  // G_{2l}: [theta.w | theta.b | conv_block1.w]; G_{2l+1}: [conv_block2.w]
+            const float ws = BLK == 1 ? 0.25f : 1.f;                  // conv_block2's data operand was V = 4 o0
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                const int co = chan[r];
+                if (co >= 0 && ci >= 0) {
+                    put(cbase + (co * F + ci) * 2 + 1, acc_w0[r] * ws);
+                    put(cbase + (co * F + ci) * 2 + 0, acc_w1[r] * ws);
+                }
+            }
+            if constexpr (BLK == 0) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int j = 4 * g + r;
                     if (j < N && col_ok) put(j * N + col, acc_th[r]);
                 }
-                float vb = acc_b, vw = acc_w2, v2 = acc_b2;
+                float vb = acc_b;
                 vb += __shfl_xor(vb, 16, 64); vb += __shfl_xor(vb, 32, 64);
-                vw += __shfl_xor(vw, 16, 64); vw += __shfl_xor(vw, 32, 64);
-                v2 += __shfl_xor(v2, 16, 64); v2 += __shfl_xor(v2, 32, 64);
-                if (g == 0 && col_ok) { put(NN + col, vb); put(NN + N + col, vw); }
-                if (lane == 0) put(NN + 2 * N, v2);
-            }
-            if constexpr (KIND == PH_G) {
-                const int ci = slot_chan(col);
-                const int cbase = BLK == 0 ? NN + N : 0;                  // G_{2l}: [theta.w | theta.b | conv_block1.w]; G_{2l+1}: [conv_block2.w]
-                const float ws = BLK == 1 ? 0.25f : 1.f;                  // conv_block2's data operand was V = 4 o0
-#pragma unroll
-                for (int r = 0; r < 3; ++r) {
-                    const int co = chan[r];
-                    if (co >= 0 && ci >= 0) {
-                        put(cbase + (co * F + ci) * 2 + 1, acc_w0[r] * ws);
-                        put(cbase + (co * F + ci) * 2 + 0, acc_w1[r] * ws);
-                    }
-                }
-                if constexpr (BLK == 0) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int j = 4 * g + r;
-                        if (j < N && col_ok) put(j * N + col, acc_th[r]);
-                    }
-                    float vb = acc_b;
-                    vb += __shfl_xor(vb, 16, 64); vb += __shfl_xor(vb, 32, 64);
-                    if (g == 0 && col_ok) put(NN + col, vb);
-                }
+                if (g == 0 && col_ok) put(NN + col, vb);
             }
         }
-        __syncthreads();
     }
+    __syncthreads();
     MXP_MARKI(10);                                                                 // gradient image complete
     if constexpr (KIND == PH_TOP) { rbase = off_fc1_w(N, L); rlen = NN + 2 * N + 1; }
     else if constexpr (BLK == 0) { rbase = LY * LS + off_theta_w(N); rlen = NN + N + CONVW; }
     else { rbase = LY * LS + off_conv_w(N, 1); rlen = CONVW; }
     float* row = a.gpart + (size_t)blockIdx.x * a.pcount + rbase;
     for (int i = threadIdx.x; i < rlen; i += 64 * MXT_WAVES) {
-        const float v = (red[i] + red2[i]) * us;
+        const float v = ((red[i] + red2[MXT_RED_FLOATS + i]) + (red2[i] + red2[2 * MXT_RED_FLOATS + i])) * us;
         row[i] = v;
         bad |= !finite_f(v);
     }
@@ -991,6 +1014,9 @@ template <int L, int KIND, int IDX, int NFIX>
 __global__ __launch_bounds__(64 * MXT_WAVES, MX_WAVES_PER_SIMD) void stgcn_train_mx_kernel(MxTrainK a) {
     extern __shared__ __attribute__((aligned(16))) float smem_all[];
     mxt_phase_body<L, KIND, IDX, NFIX, false>(a, smem_all, 0u);
+#ifdef MXP_TRACE
+    mxp_dump();
+#endif
 }
 
 // =====================================================================================================================
@@ -1040,14 +1066,7 @@ __global__ __launch_bounds__(64 * MXT_WAVES, MX_WAVES_PER_SIMD) void stgcn_train
     mxt_persist_phase<L, PH_TOP, 0, NFIX>(a, smem_all, n);
     MxtPersistChain<L, NFIX, 2 * L - 1>::backward(a, smem_all, n);
 #ifdef MXP_TRACE
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        for (int i = 0; i < mxp_n; ++i) {
-            if (mxp_id[i] >= 100) printf("\nphase %u:", mxp_id[i]);
-            else printf(" [%u] +%u", mxp_id[i], mxp_ts[i] - mxp_ts[i - 1]);
-        }
-        printf("\n");
-        mxp_n = 0;
-    }
+    mxp_dump();
 #endif
 }
 
