@@ -10,10 +10,13 @@
 // A layer forward on the matrix cores costs ~10 MFMAs per sample, so here every phase re-derives what it needs from the layer INPUT:
 //
 //     F_0 (stgcn_forward_mx.hip)  windows -> X_0, adjacency (55 floats), sum z1, sum z1^2 of BatchNorm 0
-//     F_{2l+1}                    X_l, A -> layer l up to conv_block2 -> sums of BatchNorm 2l+1                     nothing written
-//     F_{2l}, l >= 1              X_{l-1}, A -> layer l-1 in full -> X_l (written) -> layer l up to conv_block1 -> sums of BatchNorm 2l
-//     TOP                         X_{L-1}, A -> layer L-1, head, loss, head backward -> d X_L as (value, arg-max channel), sums of BN 2L-1
-//     G_{2l+1}                    X_l, A, d X_{l+1} -> layer l again, BatchNorm 2l+1 / conv_block2 backward -> d(x0 + H) (written)
+//     F_{2l+1}                    l = 0: X_0, A; l >= 1: H_l -> layer l up to conv_block2 -> sums of BatchNorm 2l+1  nothing written
+//     F_{2l}, l >= 1              X_{l-1}, A -> layer l-1 in full -> X_l (written) -> layer l up to conv_block1, H_l (written) -> sums
+//                                 of BatchNorm 2l
+//     TOP                         X_{L-1}, A (L >= 2: H_{L-1} instead of A) -> layer L-1, head, loss, head backward -> d X_L as (value,
+//                                 arg-max channel), sums of BN 2L-1
+//     G_{2l+1}                    X_l, A (l >= 1: H_l), d X_{l+1} -> layer l again, BatchNorm 2l+1 / conv_block2 backward -> d(x0 + H)
+//                                 (written)
 //     G_{2l}                      X_l, A, d(x0 + H) -> BatchNorm 2l / conv_block1 / theta backward; l >= 1: d X_l (written) and, with
 //                                 layer l-1 recomputed from X_{l-1}, the sums of BatchNorm 2l-1
 //
@@ -98,11 +101,16 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
     constexpr bool GRAD_IN = KIND == PH_G && (BLK == 1 || LY >= 1);     // a gradient tensor enters: d X_{l+1}
     constexpr bool GRAD_TOP = GRAD_IN && LY == L - 1;                   // ... in TOP's (value, arg-max) form
     constexpr bool NEED_SB = KIND == PH_G && BLK == 0;
+    // the H_l record, l >= 1 (MxTrainK::hrec): F_{2l} writes H of layer LY; F_{2l+1} and G_{2l+1} need nothing else of X_l and A, and
+    // start from it.  (No H_0 record: F_1 writing it cost more than G_1 gained -- profiles/r08_h_record.md)
+    constexpr bool H_OUT = KIND == PH_F && WITH_PREV;
+    constexpr bool H_IN = (KIND == PH_F || KIND == PH_G) && BLK == 1 && LY >= 1;
+    constexpr bool H_TOP = KIND == PH_TOP && LY >= 1;                  // TOP: X_l for the residual, H_l in place of the adjacency
     static_assert(!(KIND == PH_F && IDX == 0), "F_0 is stgcn_train_f0_mx_kernel");
 
     // ---- LDS carve (floats) ------------------------------------------------------------------------------------------------
     const int XF = 40 * N;                                   // one [10][4 N] tile
-    constexpr int AF = 220;                                  // the adjacency tile
+    constexpr int AF = H_IN ? 0 : 220;                       // the adjacency tile
     // workgroup: [BatchNorm table | gradient row image | pair partials]; then one region per wavefront (the wavefronts only meet in the
     // prologue and the epilogue)
     constexpr int SH_BNC = (NBN * MXT_BNC * F + 3) & ~3;
@@ -112,12 +120,13 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
     const int off_zero = 0;
     const int off_scr = off_zero + MXT_ZERO_FLOATS;
     const int off_sh = off_scr + MXT_SCRATCH_FLOATS;
-    const int off_X = off_sh + MXT_SHIFT_FLOATS;
+    const int off_X = off_sh + MXT_SHIFT_FLOATS;             // X_LIN, or H_LY (H_IN)
     const int off_A = off_X + XF;
-    const int off_SB = off_A + AF;                           // G_{2l}
+    const int off_SB = off_A + (H_TOP ? XF : AF);                           // G_{2l}
     const int off_DX = off_SB + (NEED_SB ? XF : 0);          // gradient in (full tile or TOP's two rows)
     const int off_XP = off_DX + (GRAD_IN ? XF : 0);          // G_{2l}, l >= 1: the gated x-hat of BatchNorm 2l-1
-    const int wave_floats = off_XP + (BWD_PREV ? XF : 0);
+    const int off_HS = off_XP + (BWD_PREV ? XF : 0);         // H_OUT: the H record's staging tile
+    const int wave_floats = off_HS + (H_OUT ? XF : 0);
     float* const smem = smem_all + SH_BNC + MXT_RED_FLOATS + 2 * MXT_WAVES * (2 * F + 2) + wave * wave_floats;
     u32x2* const sh_tile = reinterpret_cast<u32x2*>(smem + off_sh);
 
@@ -130,12 +139,21 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
             if (bytes == 160 * NFIX) { dma_tile_fixed<160 * NFIX>(src, smem + off, lane); return; }
             if (bytes == 32 * NFIX) { dma_tile_fixed<32 * NFIX>(src, smem + off, lane); return; }
         }
-        if (bytes == 4 * AF) { dma_tile_fixed<4 * AF>(src, smem + off, lane); return; }
+        if constexpr (AF != 0) {
+            if (bytes == 4 * AF) { dma_tile_fixed<4 * AF>(src, smem + off, lane); return; }
+        }
         dma_tile(src, smem + off, bytes, lane);
     };
     auto req_XA = [&](int64_t t) {
-        dma(a.xrec[LIN] + t * XF, off_X, 4 * XF);
-        dma(a.arec + t * AF, off_A, 4 * AF);
+        if constexpr (H_IN) {
+            dma(a.hrec[LY] + t * XF, off_X, 4 * XF);
+        } else if constexpr (H_TOP) {
+            dma(a.xrec[LIN] + t * XF, off_X, 4 * XF);
+            dma(a.hrec[LY] + t * XF, off_A, 4 * XF);
+        } else {
+            dma(a.xrec[LIN] + t * XF, off_X, 4 * XF);
+            dma(a.arec + t * AF, off_A, 4 * AF);
+        }
     };
     auto req_SB = [&](int64_t t) { if constexpr (NEED_SB) dma(a.sb + t * XF, off_SB, 4 * XF); };
     auto req_DX = [&](int64_t t) {
@@ -167,7 +185,7 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
     constexpr int M1_LY = (KIND == PH_F && BLK == 0) ? 0 : ((KIND == PH_F) ? 1 : ((KIND == PH_G && BLK == 0) ? 0 : 2));   // conv_block2
     MXP_MARKI(1);
     LayerRaw rc, rp;
-    layer_raw(rc, a.prm, LY, N, g, col, M0_LY, M1_LY);
+    layer_raw(rc, a.prm, LY, N, g, col, M0_LY, M1_LY, !(H_IN || H_TOP));
     if constexpr (WITH_PREV) layer_raw(rp, a.prm, LY - 1, N, g, col, 2, 2);
     ConvOp wT = ConvOp{u32x4{0u, 0u, 0u, 0u}, u32x4{0u, 0u, 0u, 0u}};
     ThetaOp thN = ThetaOp{u32x4{0u, 0u, 0u, 0u}, u32x4{0u, 0u, 0u, 0u}};
@@ -289,6 +307,21 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
                     if (xoff[r] >= 0) dst[xoff[r] + s * N] = v[s][r];
             }
     };
+    // The H record leaves through LDS: the tile is assembled in the wavefront's staging words and stored as 16-byte pieces of the
+    // contiguous [10][4 N] record -- three dwordx4 stores of whole cache lines instead of twelve dword stores of 4 N-byte row pieces.
+    // All four samples go out: beyond the batch the record is never read (H_IN zeroes those samples).
+    auto st_tile_staged = [&](float* dst, const float (&v)[4][3]) {
+        float* const stg = smem + off_HS;
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+            for (int r = 0; r < 3; ++r)
+                if (xoff[r] >= 0) stg[xoff[r] + s * N] = v[s][r];
+        __builtin_amdgcn_wave_barrier();
+        const int nq = XF / 4;
+        for (int i = lane; i < nq; i += 64) reinterpret_cast<float4*>(dst)[i] = reinterpret_cast<const float4*>(stg)[i];
+        __builtin_amdgcn_wave_barrier();
+    };
     const int sh_rd1 = col >= 1 ? lane - 1 : 64, sh_rd2 = col >= 2 ? lane - 2 : 64;     // forward taps: column t - d
     int sh_rd1_lo = sh_rd1 + 65, sh_rd2_lo = sh_rd2 + 65;
     const int sh_bk = col + (BLK == 0 ? 1 : 2) < 16 ? lane + (BLK == 0 ? 1 : 2) : 64;   // transposed convolution of this phase: column t + d
@@ -366,16 +399,26 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
         }
     };
     // One layer in full (both BatchNorms known): X <- dropout(relu(BN(z2)) + o0) + X.  `sbase[s]`: dropout counter of (sample s, channel 0, patch 0).
+    // (`h_in`: H of the layer from its record -- no T, Hp)
     auto layer_full = [&](float (&X)[4][3], const u32x4 (&adjB)[4], const LayerK& k, uint32_t key, const uint32_t (&sbase)[4],
-                          float (*xh1_out)[4][3], float (*y2_out)[4][3], float (*q_out)[4][3], uint32_t* mbits_out) {
-        f32x4 T[4], Hp[4], z[4];
+                          float (*xh1_out)[4][3], float (*y2_out)[4][3], float (*q_out)[4][3], uint32_t* mbits_out,
+                          const float (*h_in)[4][3] = nullptr) {
+        f32x4 z[4];
         float H[4][3], V[4][3];
-        Op2 xo[4];
         Pk pk[4];
         Shifted ps[4];
-        stage_T(X, adjB, T, xo);
-        stage_Hp(T, k.th, Hp);
-        leaky_of(Hp, H);
+        if (h_in) {
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+#pragma unroll
+                for (int r = 0; r < 3; ++r) H[s][r] = (*h_in)[s][r];
+        } else {
+            f32x4 T[4], Hp[4];
+            Op2 xo[4];
+            stage_T(X, adjB, T, xo);
+            stage_Hp(T, k.th, Hp);
+            leaky_of(Hp, H);
+        }
         stage_conv(H, 1.0f, k.w[0], sh_rd1, sh_rd1_lo, z, pk, ps);
 #pragma unroll
         for (int s = 0; s < 4; ++s) {
@@ -416,13 +459,13 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
     bool pend = false;
     int64_t pend_tile = 0;
     int pend_ns = 0;
-    float pend_v[4][3], pend_q[4][3];
+    float pend_v[4][3], pend_q[4][3], pend_h[4][3];
     float pend_top0 = 0.f, pend_top1 = 0.f, pend_pred = 0.f;
     uint32_t pend_m = 0u;                       // dropout mask bits of the tile (F_{2l}, TOP: written)
 #pragma unroll
     for (int s = 0; s < 4; ++s)
 #pragma unroll
-        for (int r = 0; r < 3; ++r) pend_v[s][r] = pend_q[s][r] = 0.f;
+        for (int r = 0; r < 3; ++r) pend_v[s][r] = pend_q[s][r] = pend_h[s][r] = 0.f;
 
     MXP_MARKI(5);                                                                  // constants ready
     for (; tile < a.ntiles; tile += tstride) {
@@ -444,6 +487,7 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
                 st_tile(a.qrec[LY] + pend_tile * XF, pend_q, pend_ns);
                 if (use_drop) a.mrec[LY - 1][pend_tile * 64 + lane] = pend_m;
             }
+            if constexpr (H_OUT) st_tile_staged(a.hrec[LY] + pend_tile * XF, pend_h);
             if constexpr (KIND == PH_G && BLK == 1) st_tile(a.sb + pend_tile * XF, pend_v, pend_ns);
             if constexpr (BWD_PREV) st_tile(a.dx + pend_tile * XF, pend_v, pend_ns);
             if constexpr (KIND == PH_TOP) {
@@ -457,10 +501,21 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
             }
         }
         // ---- inputs ------------------------------------------------------------------------------------------------------------------
-        float X[4][3];
+        float X[4][3];                          // X_LIN; H_IN: H_LY
+        float HT[4][3];                         // H_TOP: H_LY
         u32x4 adjB[4];
         ld_tile(off_X, X);
-        {
+        if constexpr (H_TOP) ld_tile(off_A, HT);
+        if constexpr (H_IN || H_TOP) {
+            if (ns < 4) {                       // the record holds whatever an earlier step left beyond the batch
+#pragma unroll
+                for (int s = 0; s < 4; ++s)
+                    if (s >= ns) {
+                        X[s][0] = X[s][1] = X[s][2] = 0.f;
+                        if constexpr (H_TOP) HT[s][0] = HT[s][1] = HT[s][2] = 0.f;
+                    }
+            }
+        } else {
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 // F_0 left every entry as its (hi | lo << 16) f16 pair: the operand is four byte permutes, no split (slot 3 of every
@@ -494,14 +549,28 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
 #pragma unroll
                     for (int r = 0; r < 3; ++r) pend_v[s][r] = X[s][r];
             }
-            f32x4 T[4], Hp[4], z[4];
+            f32x4 z[4];
             float H[4][3];
-            Op2 xo[4];
             Pk pk[4];
             Shifted ps[4];
-            stage_T(X, adjB, T, xo);
-            stage_Hp(T, kc.th, Hp);
-            leaky_of(Hp, H);
+            if constexpr (H_IN) {
+#pragma unroll
+                for (int s = 0; s < 4; ++s)
+#pragma unroll
+                    for (int r = 0; r < 3; ++r) H[s][r] = X[s][r];
+            } else {
+                f32x4 T[4], Hp[4];
+                Op2 xo[4];
+                stage_T(X, adjB, T, xo);
+                stage_Hp(T, kc.th, Hp);
+                leaky_of(Hp, H);
+            }
+            if constexpr (H_OUT) {
+#pragma unroll
+                for (int s = 0; s < 4; ++s)
+#pragma unroll
+                    for (int r = 0; r < 3; ++r) pend_h[s][r] = H[s][r];
+            }
             if constexpr (BLK == 0) {
                 stage_conv(H, 0.f, kc.w[0], sh_rd1, sh_rd1_lo, z, pk, ps);          // raw z1
             } else {
@@ -527,7 +596,7 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
                     }
                 }
             }
-            if constexpr (WITH_PREV) { pend = true; pend_tile = tile; pend_ns = ns; }
+            if constexpr (H_OUT) { pend = true; pend_tile = tile; pend_ns = ns; }
             return;
         }
 
@@ -537,7 +606,8 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
             // (this row's label, requested before the last layer's forward: read where it is used -- `if (rowok) ... a.y[s0 + g]`, a load
             // under a condition -- it was a memory round trip per tile in the middle of the kernel)
             const float ylab = a.y[s0 + (g < ns ? g : ns - 1)];
-            layer_full(X, adjB, kc, dkey[LY], sbase, &xh1, &y2, nullptr, &pend_m);
+            if constexpr (H_TOP) layer_full(X, adjB, kc, dkey[LY], sbase, &xh1, &y2, nullptr, &pend_m, &HT);
+            else layer_full(X, adjB, kc, dkey[LY], sbase, &xh1, &y2, nullptr, &pend_m);
             // max over the ten channels with its arg-max: per lane over its (up to three) channels, then across the four lane groups
             float pm[4], pa[4];
 #pragma unroll
@@ -672,24 +742,32 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
                 u32x4 ad[NS];
 #pragma unroll
                 for (int e = 0; e < NS; ++e) {
-                    ad[e] = adjB[HS + e];
+                    if constexpr (!H_IN) ad[e] = adjB[HS + e];
 #pragma unroll
                     for (int r = 0; r < 3; ++r) Xh[e][r] = X[HS + e][r];
                 }
-                // layer LY forward again, as far as this phase needs it
-                f32x4 T[NS], Hp[NS], z[NS], AXd[NS];
+                // layer LY forward again, as far as this phase needs it (H_IN: from H on)
+                f32x4 Hp[NS], z[NS], AXd[NS];
                 float H[NS][3];
-                Op2 xo[NS];
-                stage_T(Xh, ad, T, xo);
-                if constexpr (BLK == 0) {
+                if constexpr (H_IN) {
 #pragma unroll
-                    for (int e = 0; e < NS; ++e) {
-                        AXd[e] = mfma16z(ad[e], xo[e].h);                                    // (A X) in the D layout: rows c, columns k
-                        AXd[e] = mfma16(ad[e], xo[e].l, AXd[e]);
+                    for (int e = 0; e < NS; ++e)
+#pragma unroll
+                        for (int r = 0; r < 3; ++r) H[e][r] = Xh[e][r];
+                } else {
+                    f32x4 T[NS];
+                    Op2 xo[NS];
+                    stage_T(Xh, ad, T, xo);
+                    if constexpr (BLK == 0) {
+#pragma unroll
+                        for (int e = 0; e < NS; ++e) {
+                            AXd[e] = mfma16z(ad[e], xo[e].h);                                // (A X) in the D layout: rows c, columns k
+                            AXd[e] = mfma16(ad[e], xo[e].l, AXd[e]);
+                        }
                     }
+                    stage_Hp(T, kc.th, Hp);
+                    leaky_of(Hp, H);
                 }
-                stage_Hp(T, kc.th, Hp);
-                leaky_of(Hp, H);
                 Pk hk[NS];
                 Shifted hks[NS];
                 stage_conv(H, 1.0f, kc.w[0], sh_rd1, sh_rd1_lo, z, hk, hks);                  // x-hat of BatchNorm 2l
@@ -880,6 +958,7 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
             st_tile(a.qrec[LY] + pend_tile * XF, pend_q, pend_ns);
             if (use_drop) a.mrec[LY - 1][pend_tile * 64 + lane] = pend_m;
         }
+        if constexpr (H_OUT) st_tile_staged(a.hrec[LY] + pend_tile * XF, pend_h);
         if constexpr (KIND == PH_G && BLK == 1) st_tile(a.sb + pend_tile * XF, pend_v, pend_ns);
         if constexpr (BWD_PREV) st_tile(a.dx + pend_tile * XF, pend_v, pend_ns);
         if constexpr (KIND == PH_TOP) {
@@ -1076,9 +1155,12 @@ __global__ __launch_bounds__(64 * MXT_WAVES, MX_WAVES_PER_SIMD) void stgcn_train
 static size_t mxt_lds_bytes(int L, int kind, int idx, int N) {
     const int blk = kind == PH_TOP ? 1 : idx % 2, ly = kind == PH_TOP ? L - 1 : idx / 2;
     const bool need_sb = kind == PH_G && blk == 0, grad_in = kind == PH_G && (blk == 1 || ly >= 1), bwd_prev = kind == PH_G && blk == 0 && ly >= 1;
+    const bool h_in = (kind == PH_F || kind == PH_G) && blk == 1 && ly >= 1;     // H_IN of mxt_phase_body: no adjacency tile
+    const bool h_top = kind == PH_TOP && ly >= 1;                                  // H_TOP: an H tile in its place
+    const bool h_out = kind == PH_F && blk == 0 && ly >= 1;       // H_OUT: the staging tile
     const int XF = 40 * N;
-    const size_t wave = (size_t)MXT_ZERO_FLOATS + MXT_SCRATCH_FLOATS + MXT_SHIFT_FLOATS + XF + 220 + (need_sb ? XF : 0) + (grad_in ? XF : 0) +
-                        (bwd_prev ? XF : 0);
+    const size_t wave = (size_t)MXT_ZERO_FLOATS + MXT_SCRATCH_FLOATS + MXT_SHIFT_FLOATS + XF + (h_in ? 0 : h_top ? XF : 220) + (need_sb ? XF : 0) + (grad_in ? XF : 0) +
+                        (bwd_prev ? XF : 0) + (h_out ? XF : 0);
     const size_t shared = (size_t)((2 * L * MXT_BNC * F + 3) & ~3) + MXT_RED_FLOATS + 2 * MXT_WAVES * (2 * F + 2);
     return (shared + MXT_WAVES * wave) * sizeof(float);
 }
@@ -1146,7 +1228,7 @@ float stgcn_train_mx_grad_scale(int64_t global_batch) {
 static MxTrainK mxt_kernel_args(const MxTrainArgs& m) {
     MxTrainK k;
     k.prm = m.prm; k.y = m.y; k.pred = m.pred; k.cells = m.cells; k.gpart = m.gpart;
-    for (int l = 0; l < MX_MAX_LAYERS; ++l) { k.xrec[l] = m.xrec[l]; k.qrec[l] = m.qrec[l]; k.mrec[l] = m.mrec[l]; }
+    for (int l = 0; l < MX_MAX_LAYERS; ++l) { k.xrec[l] = m.xrec[l]; k.qrec[l] = m.qrec[l]; k.hrec[l] = m.hrec[l]; k.mrec[l] = m.mrec[l]; }
     k.arec = m.arec; k.sb = m.sb; k.dx = m.dx; k.dtop = m.dtop;
     k.B = m.B; k.ntiles = (m.B + 3) / 4; k.global_batch = m.global_batch; k.sample_offset = m.sample_offset;
     k.N = m.N; k.pcount = m.pcount;

@@ -139,9 +139,11 @@ struct LayerRaw {
     ThetaRaw th;
     ConvRaw w[2];
 };
-__device__ __forceinline__ void layer_raw(LayerRaw& k, const float* prm, int l, int N, int g, int col, int mode0, int mode1) {
+// (`theta` false: the phase starts from a saved H and needs no theta^T -- no gathers, a zero operand)
+__device__ __forceinline__ void layer_raw(LayerRaw& k, const float* prm, int l, int N, int g, int col, int mode0, int mode1, bool theta = true) {
     const float* lp = prm + l * layer_stride(N);
-    k.th = theta_t_raw(lp, N, g, col);
+    if (theta) k.th = theta_t_raw(lp, N, g, col);
+    else k.th = ThetaRaw{{0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
     for (int blk = 0; blk < 2; ++blk) {
         if ((blk == 0 ? mode0 : mode1) != 0) k.w[blk] = conv_fwd_raw(lp + off_conv_w(N, blk), g, col);
@@ -178,6 +180,8 @@ struct MxTrainK {
     float* gpart;
     float* xrec[MX_MAX_LAYERS];   // X_l tiles: [ntiles][10][4 N]
     float* qrec[MX_MAX_LAYERS];   // l >= 1: x-hat of BatchNorm 2l-1 where the gradient passes (ReLU gate and dropout), else +inf
+    float* hrec[MX_MAX_LAYERS];   // l >= 1: H_l = leaky(theta(A X_l)): [ntiles][10][4 N], written by F_{2l}, read by F_{2l+1} and
+                                  // G_{2l+1} instead of X_l and the adjacency, by TOP (l = L - 1) instead of the adjacency
     uint32_t* mrec[MX_MAX_LAYERS];   // dropout masks of layer l, one word per lane and tile (bit 3 s + r = keep of sample s, register r):
                                      // hashed once, by the phase that first applies them (F_{2l+2} / TOP), read by G_{2l+1}
     float* arec;                  // adjacency tiles: [ntiles][4][55]
