@@ -62,17 +62,20 @@ static int adam_tail(const rulgnn_adam_args* opt, const float* grads, int64_t fi
                      opt->beta2, opt->eps, opt->weight_decay, 1.0f, st, opt->step_state);
 }
 
-// Path selection.  The fused row-mapped kernels cover num_patch <= 64 as long as one wavefront's input tile
-// fits its LDS staging area (and, for training, num_layers <= 3 / <= 2); everything else valid goes to the
-// tiled path, which has no such limits.
+// Path selection.  The fused row-mapped kernels cover num_patch <= 64 as long as one wavefront's input tile fits its LDS staging area,
+// every launch form a call may reach fits the 160 KB of LDS a workgroup can have (stgcn_host.hpp: the *_lds_bytes functions the
+// launchers size their launches with) and, for training, num_layers <= 3 / <= 2; everything else valid goes to the tiled path, which has
+// no such limits.  Deciding it here, before anything is launched, is what makes a refusal (RULGNN_EUNSUPPORTED) leave every buffer as
+// it was.
 static bool tiled_eval(const rulgnn_stgcn_shape* shape) {
     TileGeom g;
-    return tile_geometry(shape, &g) != RULGNN_OK;
+    return tile_geometry(shape, &g) != RULGNN_OK || stgcn_forward_exact_lds_bytes(shape) > MAX_LDS_BYTES;
 }
 static bool tiled(const rulgnn_stgcn_shape* shape) { return stgcn_train_workspace_bytes(shape) == 0; }
 
 // MPNN order k > 1 exists on the fused row-mapped kernels only: a shape they cannot hold (a window beyond a wavefront's LDS staging area,
-// more layers than the phase chain is instantiated for) must NOT fall through to the tiled kernels, which read the order-1 layout.
+// weights + tiles beyond the workgroup's LDS, more layers than the phase chain is instantiated for) must NOT fall through to the tiled
+// kernels, which read the order-1 layout: it is refused up front.
 static bool order_needs_tiled(const rulgnn_stgcn_shape* shape, bool train) {
     return shape->mpnn_k != 1 && (train ? tiled(shape) : tiled_eval(shape));
 }

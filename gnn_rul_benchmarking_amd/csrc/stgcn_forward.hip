@@ -58,6 +58,23 @@ __global__ __launch_bounds__(BLOCK) void stgcn_forward_eval_kernel(const float* 
     }
 }
 
+// LDS of the exact kernel (and of the scan below, which runs the same routine): the weights of every layer and order, then one input
+// tile per wavefront
+static size_t exact_lds_bytes(const TileGeom& g, int L, int K) {
+    const int w = g.RW == 16 ? EvalWeightsLds<16>::floats(L, K) : (g.RW == 32 ? EvalWeightsLds<32>::floats(L, K) : EvalWeightsLds<64>::floats(L, K));
+    return sizeof(float) * ((size_t)w + (size_t)WAVES_PER_BLOCK * g.stage_floats);
+}
+
+size_t stgcn_forward_exact_lds_bytes(const rulgnn_stgcn_shape* s) {
+    TileGeom g;
+    return tile_geometry(s, &g) == RULGNN_OK ? exact_lds_bytes(g, s->num_layers, s->mpnn_k) : 0;
+}
+
+size_t stgcn_forward_fixup_lds_bytes(const rulgnn_stgcn_shape* s) {
+    TileGeom g;
+    return tile_geometry(s, &g) == RULGNN_OK ? exact_lds_bytes(g, s->num_layers, 1) : 0;     // behind the order-1 matrix-core kernels
+}
+
 template <int RW, int NFIX, int PFIX, int LFIX>
 static int launch_forward_fix(const TileGeom& g, const rulgnn_stgcn_shape* s, const float* x, const float* prm,
                           const float* bn, float* out, hipStream_t stream) {
@@ -66,8 +83,8 @@ static int launch_forward_fix(const TileGeom& g, const rulgnn_stgcn_shape* s, co
     a.K = s->mpnn_k;
     a.magicP = g.magicP; a.vec4 = g.vec4 && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
     a.stage_floats = g.stage_floats;
-    const size_t lds = sizeof(float) * ((size_t)EvalWeightsLds<RW>::floats(a.L, a.K) + (size_t)WAVES_PER_BLOCK * g.stage_floats);
-    if (lds > 160 * 1024) return RULGNN_EUNSUPPORTED;
+    const size_t lds = stgcn_forward_exact_lds_bytes(s);
+    if (lds == 0 || lds > MAX_LDS_BYTES) return RULGNN_EUNSUPPORTED;     // backstop: the C-ABI gate (tiled_eval) keeps such shapes out
     if (lds > 48 * 1024) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(&stgcn_forward_eval_kernel<RW, NFIX, PFIX, LFIX>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
@@ -141,8 +158,8 @@ static int launch_fixup(const TileGeom& g, const rulgnn_stgcn_shape* s, const fl
     a.K = 1;                                      // (the matrix-core kernels this scan follows are order 1 only)
     a.magicP = g.magicP; a.vec4 = g.vec4 && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
     a.stage_floats = g.stage_floats;
-    const size_t lds = sizeof(float) * ((size_t)EvalWeightsLds<RW>::floats(a.L) + (size_t)WAVES_PER_BLOCK * g.stage_floats);
-    if (lds > 160 * 1024) return RULGNN_EUNSUPPORTED;
+    const size_t lds = stgcn_forward_fixup_lds_bytes(s);
+    if (lds == 0 || lds > MAX_LDS_BYTES) return RULGNN_EUNSUPPORTED;     // backstop: stgcn_forward_eval checks before the wide kernel runs
     if (lds > 48 * 1024 &&
         hipFuncSetAttribute(reinterpret_cast<const void*>(&stgcn_forward_fixup_kernel<RW>), hipFuncAttributeMaxDynamicSharedMemorySize,
                             (int)lds) != hipSuccess)
@@ -174,7 +191,8 @@ int stgcn_forward_eval(const rulgnn_stgcn_shape* s, const float* x, const float*
     if (s->batch == 0) return RULGNN_OK;
     if (path != STGCN_EVAL_EXACT) {
         int mrc = stgcn_forward_eval_mx(s, x, prm, bn, out, stream);
-        if (mrc == RULGNN_EUNSUPPORTED) {                                         // 16 <= num_patch <= 47: the wide kernel + its scan
+        // 16 <= num_patch <= 47: the wide kernel + its scan, only where the scan fits (it would fail AFTER the wide kernel wrote out)
+        if (mrc == RULGNN_EUNSUPPORTED && stgcn_forward_fixup_lds_bytes(s) <= MAX_LDS_BYTES) {
             mrc = stgcn_forward_eval_mxw(s, x, prm, bn, out, stream);
             if (mrc == RULGNN_OK) return stgcn_forward_fixup(s, x, prm, bn, out, stream);
         }

@@ -123,6 +123,14 @@ struct GradReadyHook {
 int stgcn_tiled_train(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args* a, int mode, hipStream_t stream,
                       const GradReadyHook* ready = nullptr);
 size_t stgcn_train_workspace_bytes(const rulgnn_stgcn_shape* s);
+// The LDS bytes a launch form of the fused row-mapped kernels requests at this shape (and MPNN order): the exact eval kernel, the scan
+// behind the wide matrix-core eval kernel (order 1), the largest phase of the fp32 training chain; 0 where the row-mapped geometry does
+// not apply.  The launchers size their launches with these and the C-ABI gates (rulgnn_api.hip) compare them with MAX_LDS_BYTES, so a
+// shape the gates accept cannot fail a launcher's LDS check after an earlier launch of the same call has run.
+constexpr size_t MAX_LDS_BYTES = 160 * 1024;
+size_t stgcn_forward_exact_lds_bytes(const rulgnn_stgcn_shape* s);
+size_t stgcn_forward_fixup_lds_bytes(const rulgnn_stgcn_shape* s);
+size_t stgcn_train_chain_lds_bytes(const rulgnn_stgcn_shape* s);
 int stgcn_train_forward(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args* a, hipStream_t stream);
 int stgcn_train_backward(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args* a, hipStream_t stream);
 int stgcn_train_fwdbwd(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args* a, hipStream_t stream);

@@ -1155,10 +1155,14 @@ static void ws_layout(const rulgnn_stgcn_shape* s, const TileGeom& g, WsLayout* 
     w->total = o;
 }
 
+// 0: the phase chain does not hold this shape (the caller's tiled path, or a refusal for MPNN order k > 1).  Every shape it holds fits
+// the LDS of every fp32 phase, so that each form of the step -- the fp32 chain, the matrix-core chains and the fp32 chain a guard retry
+// sends a matrix-core shape to -- runs once the gate has let it through.
 size_t stgcn_train_workspace_bytes(const rulgnn_stgcn_shape* s) {
     TileGeom g;
     if (train_geometry(s, &g) != RULGNN_OK) return 0;
     if (s->num_layers > 3 || (g.RW != 16 && s->num_layers > 2)) return 0;
+    if (stgcn_train_chain_lds_bytes(s) > MAX_LDS_BYTES) return 0;
     WsLayout w;
     ws_layout(s, g, &w);
     return w.total;
@@ -1180,14 +1184,38 @@ static size_t train_lds_bytes(int RW, int L, int wave_area, int kord = 1) {
     return fl * sizeof(float);
 }
 
+// The order a phase kernel is specialised on (launch_phase): the theta phases F_{2l} / G_{2l} carry MPNN order k, every other phase 1.
+static int phase_kord(int kind, int idx, int K) { return K > 1 && (kind == PH_F || kind == PH_G) && idx % 2 == 0 ? K : 1; }
+
+// The LDS bytes one fp32 phase kernel requests (launch_phase_n sizes its launch with this).
+static size_t phase_lds_bytes(int RW, int L, int kind, int idx, const TileGeom& g, int kord) {
+    return train_lds_bytes(RW, L, wave_area_for(kind, idx, g), kord);
+}
+
+// The most LDS any phase of the fp32 chain requests at this shape and order; 0 where the row-mapped geometry does not apply.
+size_t stgcn_train_chain_lds_bytes(const rulgnn_stgcn_shape* s) {
+    TileGeom g;
+    if (train_geometry(s, &g) != RULGNN_OK) return 0;
+    const int L = s->num_layers, K = s->mpnn_k;
+    size_t lds = phase_lds_bytes(g.RW, L, PH_TOP, 0, g, 1);
+    const int kinds[2] = {PH_F, PH_G};
+    for (int i = 0; i < 2 * L; ++i) {
+        for (const int kind : kinds) {
+            const size_t b = phase_lds_bytes(g.RW, L, kind, i, g, phase_kord(kind, i, K));
+            if (b > lds) lds = b;
+        }
+    }
+    return lds;
+}
+
 template <int RW, int L, int KIND, int IDX, int NFIX, int PFIX = 0, int KORD = 1>
 static int launch_phase_n(const TrainK& k_in, const float* x, const float* prm, const float* gy, const TileGeom& g, int max_grid,
                           hipStream_t stream, int* grid_out) {
     auto kern = stgcn_train_phase_kernel<RW, L, KIND, IDX, NFIX, PFIX, KORD>;
     TrainK k = k_in;
     k.wave_area_floats = wave_area_for(KIND, IDX, g);
-    const size_t lds = train_lds_bytes(RW, L, k.wave_area_floats, KORD);
-    if (lds > 160 * 1024) return RULGNN_EUNSUPPORTED;
+    const size_t lds = phase_lds_bytes(RW, L, KIND, IDX, g, KORD);
+    if (lds > MAX_LDS_BYTES) return RULGNN_EUNSUPPORTED;       // backstop: the C-ABI gate (stgcn_train_workspace_bytes) keeps such shapes out
     if (lds > 48 * 1024) {
         if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
             hipSuccess)
@@ -1811,8 +1839,7 @@ int stgcn_train_mx_kind(const rulgnn_stgcn_shape* s, const float* x) {
 // does not apply (the tiled path).
 int64_t stgcn_train_guard_counter_offset(const rulgnn_stgcn_shape* s) {
     TileGeom g;
-    if (train_geometry(s, &g) != RULGNN_OK) return -1;
-    if (s->num_layers > 3 || (g.RW != 16 && s->num_layers > 2)) return -1;
+    if (stgcn_train_workspace_bytes(s) == 0 || train_geometry(s, &g) != RULGNN_OK) return -1;
     WsLayout w;
     ws_layout(s, g, &w);
     return (int64_t)(w.off_cells + sizeof(double) * (size_t)CELL_REPLICAS * cell_stride(s->num_layers) + offsetof(StepScratch, pad) + 3 * sizeof(uint32_t));

@@ -137,3 +137,58 @@ def test_fwdbwd_rejects_bad_adam_arguments_before_any_launch(family, ds, did, pr
     if family in _BN_OPT_FAMILIES:
         assert code(bn_stats=base + 196610) == EINVAL                    # misaligned running statistics
         assert code(bn_stats=base + 196610, exp_avg=base + 65538) == EALIGN
+
+
+# The gates at the edges of the fused row-mapped kernels' LDS budget (tests/test_stgcn_lds_envelope_gpu.py runs these shapes): each
+# pair is the last window one launch form holds and the first it does not.  eval: "fused" (no workspace), "tiled" (a workspace) or
+# "refused" (order k > 1: -2 before any launch); training: "chain" (the phase chains), "tiled" or "refused".
+_LDS_EDGE = [
+    # eval, exact row-mapped kernel, order 1 (an order-1 shape past the edge goes to the tiled path)
+    (33, 207, 2, 1, "fused", "tiled"), (33, 208, 2, 1, "tiled", "tiled"),
+    (40, 171, 2, 1, "fused", "tiled"), (40, 172, 2, 1, "tiled", "tiled"),
+    (47, 146, 2, 1, "fused", "tiled"), (47, 147, 2, 1, "tiled", "tiled"),
+    (48, 143, 2, 1, "fused", "tiled"), (48, 144, 2, 1, "tiled", "tiled"),
+    (64, 107, 2, 1, "fused", "tiled"), (64, 108, 2, 1, "tiled", "tiled"),
+    (17, 219, 8, 1, "fused", "tiled"), (17, 220, 8, 1, "tiled", "tiled"), (32, 115, 8, 1, "fused", "tiled"), (32, 116, 8, 1, "tiled", "tiled"),
+    # the wide matrix-core eval shapes past the edge: not the wide kernel (its scan would not fit) but the tiled path
+    (40, 200, 2, 1, "tiled", "tiled"), (47, 190, 2, 1, "tiled", "tiled"),
+    # training, fp32 phase chain, order 1 (41 x 132 and 40 x 136 qualify for the wide matrix-core chain, but a guard retry would land on
+    # the fp32 chain: the tiled path)
+    (41, 131, 2, 1, "fused", "chain"), (41, 133, 2, 1, "fused", "tiled"), (41, 132, 2, 1, "fused", "tiled"),
+    (40, 135, 2, 1, "fused", "chain"), (40, 136, 2, 1, "fused", "tiled"),
+    (48, 111, 2, 1, "fused", "chain"), (48, 112, 2, 1, "fused", "tiled"), (64, 83, 2, 1, "fused", "chain"), (64, 84, 2, 1, "fused", "tiled"),
+    # order 2, 3: refused up front
+    (17, 255, 2, 2, "fused", "chain"), (17, 256, 2, 2, "refused", "chain"),
+    (40, 115, 2, 2, "fused", "chain"), (40, 116, 2, 2, "refused", "chain"), (40, 135, 2, 2, "refused", "chain"), (40, 136, 2, 2, "refused", "refused"),
+    (64, 71, 2, 2, "fused", "chain"), (64, 72, 2, 2, "refused", "chain"), (64, 83, 2, 2, "refused", "chain"), (64, 84, 2, 2, "refused", "refused"),
+    (17, 198, 2, 3, "fused", "chain"), (17, 199, 2, 3, "fused", "refused"), (17, 239, 2, 3, "fused", "refused"), (17, 240, 2, 3, "refused", "refused"),
+    (17, 203, 1, 3, "fused", "chain"), (17, 204, 1, 3, "fused", "refused"),
+    (40, 63, 2, 3, "fused", "chain"), (40, 64, 2, 3, "refused", "chain"), (40, 83, 2, 3, "refused", "chain"), (40, 84, 2, 3, "refused", "refused"),
+    (64, 39, 2, 3, "fused", "chain"), (64, 40, 2, 3, "refused", "chain"), (64, 51, 2, 3, "refused", "chain"), (64, 52, 2, 3, "refused", "refused"),
+    # every benchmarked shape stays where it was
+    (14, 30, 2, 1, "fused", "chain"), (14, 50, 2, 1, "fused", "chain"), (40, 64, 2, 1, "fused", "chain"),
+    (160, 16, 2, 1, "tiled", "tiled"), (1024, 32, 2, 1, "tiled", "tiled"),
+]
+
+
+@pytest.mark.parametrize("N,P,L,k,ev,tr", _LDS_EDGE)
+def test_stgcn_gates_at_the_lds_edge(N, P, L, k, ev, tr):
+    """Host-only: the workspace queries, the null-pointer forward call and rulgnn_stgcn_train_step_resolve agree on which path a shape
+    takes -- and so which calls must run and which are refused before anything is launched."""
+    lib = _lib.load()
+    shp = _lib.StgcnShape(7, N, P, L, k)
+    x = C.c_void_p(1 << 20)                     # 16-byte aligned placeholder: resolve only looks at its alignment
+    fwd_ws = lib.rulgnn_stgcn_forward_workspace_bytes(C.byref(shp))
+    fwd_rc = lib.rulgnn_stgcn_forward_f32(C.byref(shp), None, None, None, None, None, 0, None)
+    assert (fwd_ws > 0, fwd_rc) == {"fused": (False, _lib.EINVAL), "tiled": (True, _lib.EINVAL), "refused": (False, _lib.EUNSUPPORTED)}[ev]
+    train_ws = lib.rulgnn_stgcn_train_workspace_bytes(C.byref(shp))
+    guard = lib.rulgnn_stgcn_train_guard_counter_offset(C.byref(shp))
+    auto = lib.rulgnn_stgcn_train_step_resolve(C.byref(shp), x, _lib.STEP_AUTO)
+    chain = lib.rulgnn_stgcn_train_step_resolve(C.byref(shp), x, _lib.STEP_CHAIN)
+    if tr == "chain":
+        assert train_ws > 0 and guard >= 0 and chain == _lib.STEP_CHAIN
+        # the matrix-core chains where they apply: num_patch <= 47 and num_patch x patch_size a multiple of 4
+        assert auto == (_lib.STEP_MX if N <= 47 and k == 1 and (N * P) % 4 == 0 else _lib.STEP_CHAIN)
+    else:
+        assert (train_ws > 0) == (tr == "tiled")
+        assert guard == -1 and auto == chain == _lib.EUNSUPPORTED
