@@ -28,8 +28,8 @@
 //     d o0 = W2^T-conv(d z2), d H = W1^T-conv(d z1)    A operand [ci][tap, co], data = [d z | d z of column t + d]         3 MFMAs
 //     d X  = A . (d Hp . theta) = ((A d Hp)^T)^T-chain: U = d Hp^T x Adj (2 MFMAs), d X = U x theta (2 MFMAs)
 //     d theta[j][k] = sum_c d Hp[c][j] (A X)[c][k]      contraction over channel slots = the packed D registers themselves
-//     d W[co][ci, tap] = sum_t d z[co][t] h[ci][t - d tap]: contraction over COLUMNS -- both operands transposed by one MFMA
-//                                                      against an identity operand ({hi | lo} halves of K: exact to 22 bits)
+//     d W[co][ci, tap] = sum_t d z[co][t] h[ci][t - d tap]: contraction over COLUMNS -- both operands, already packed (hi | lo)
+//                                                      pairs, transposed through a per-wavefront LDS image and ds_read_b64_tr_b16
 // Weight-gradient accumulators live in MFMA accumulator registers across the persistent tile loop; every wavefront writes one row of
 // partial gradients, summed in a fixed order by stgcn_train_finalize_kernel (shared with the fp32 chain, as are prepare and the cells).
 //
@@ -120,7 +120,8 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
     const int off_zero = 0;
     const int off_scr = off_zero + MXT_ZERO_FLOATS;
     const int off_sh = off_scr + MXT_SCRATCH_FLOATS;
-    const int off_X = off_sh + MXT_SHIFT_FLOATS;             // X_LIN, or H_LY (H_IN)
+    const int off_wg = off_sh + MXT_SHIFT_FLOATS;            // G: the transposing image of the weight gradient's operands
+    const int off_X = off_wg + (KIND == PH_G ? MXT_WG_FLOATS : 0);          // X_LIN, or H_LY (H_IN)
     const int off_A = off_X + XF;
     const int off_SB = off_A + (H_TOP ? XF : AF);                           // G_{2l}
     const int off_DX = off_SB + (NEED_SB ? XF : 0);          // gradient in (full tile or TOP's two rows)
@@ -129,6 +130,7 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
     const int wave_floats = off_HS + (H_OUT ? XF : 0);
     float* const smem = smem_all + SH_BNC + MXT_RED_FLOATS + 2 * MXT_WAVES * (2 * F + 2) + wave * wave_floats;
     u32x2* const sh_tile = reinterpret_cast<u32x2*>(smem + off_sh);
+    u32x2* const wg_img = reinterpret_cast<u32x2*>(smem + off_wg);
 
     int64_t tile = (int64_t)blockIdx.x * MXT_WAVES + wave;
     const int64_t tstride = (int64_t)gridDim.x * MXT_WAVES;
@@ -180,6 +182,9 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
     __builtin_amdgcn_sched_barrier(0);
     for (int i = lane; i < MXT_ZERO_FLOATS; i += 64) smem[off_zero + i] = 0.f;
     if (lane < 2) sh_tile[64 + 65 * lane] = u32x2{0u, 0u};
+    if constexpr (KIND == PH_G) {
+        if (lane < 2) wg_img[WG_H_HI + WG_ZERO + (WG_H_LO - WG_H_HI) * lane] = u32x2{0u, 0u};      // the causal zeros of the shifted read
+    }
     // which convolutions of the main layer / the previous layer this phase runs, and how
     constexpr int M0_LY = (KIND == PH_F && BLK == 0) ? 1 : 2;                          // conv_block1 of layer LY
     constexpr int M1_LY = (KIND == PH_F && BLK == 0) ? 0 : ((KIND == PH_F) ? 1 : ((KIND == PH_G && BLK == 0) ? 0 : 2));   // conv_block2
@@ -189,17 +194,11 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
     if constexpr (WITH_PREV) layer_raw(rp, a.prm, LY - 1, N, g, col, 2, 2);
     ConvOp wT = ConvOp{u32x4{0u, 0u, 0u, 0u}, u32x4{0u, 0u, 0u, 0u}};
     ThetaOp thN = ThetaOp{u32x4{0u, 0u, 0u, 0u}, u32x4{0u, 0u, 0u, 0u}};
-    u32x4 ident = u32x4{0u, 0u, 0u, 0u};
     ConvRaw wT_raw = ConvRaw{{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};          // (converted behind the BatchNorm cells' loads: one round trip)
     ThetaRaw thN_raw = ThetaRaw{{0.f, 0.f, 0.f, 0.f}};
     if constexpr (KIND == PH_G) {
         wT_raw = conv_bwd_raw(a.prm + LY * LS + off_conv_w(N, BLK), g, col);
         if constexpr (BLK == 0 && LY >= 1) thN_raw = theta_n_raw(a.prm + LY * LS, N, g, col);
-        unsigned w[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) w[r] = (4 * g + r == col) ? 0x3C00u : 0u;      // f16 1.0
-        const unsigned p01 = w[0] | (w[1] << 16), p23 = w[2] | (w[3] << 16);
-        ident = u32x4{p01, p23, p01, p23};
     }
     // head (TOP), row mapping: lane (sample row, t) holds row t and column t of fc1
     float fc1w[16], fc1wT[16];
@@ -327,6 +326,13 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
     const int sh_bk = col + (BLK == 0 ? 1 : 2) < 16 ? lane + (BLK == 0 ? 1 : 2) : 64;   // transposed convolution of this phase: column t + d
     int sh_bk_lo = sh_bk + 65;
     asm volatile("" : "+v"(sh_rd1_lo), "+v"(sh_rd2_lo), "+v"(sh_bk_lo));
+    // weight-gradient image (wg_chunk): this lane writes the pairs of its column t = col, slots 4 g .. 4 g + 3; the transposed read hands
+    // lane (g', slot) the columns 4 g' .. 4 g' + 3, for which lane 4 q + p of the group addresses row 4 g' + q, slots 4 p .. 4 p + 3; the
+    // tap at t - d reads d rows higher, rows above the first from the zero chunk
+    const int wg_wr = wg_chunk(col, g);
+    const int wg_row = 4 * g + (col >> 2), wg_rows = wg_row - (BLK == 0 ? 1 : 2);
+    const int wg_rd = wg_chunk(wg_row, col & 3);
+    const int wg_rds = wg_rows >= 0 ? wg_chunk(wg_rows, col & 3) : WG_ZERO;
     const unsigned t_bias = g == 3 ? 0x3C00u << 16 : 0u;
     uint32_t dro[3];
 #pragma unroll
@@ -785,14 +791,16 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
                 Pk dk[NS];                              // packed d z (BLK 1) -- later the packed d Hp (BLK 0)
                 float dz[NS][3], gsum[NS][3], V[NS][3];
                 if constexpr (BLK == 1) {
-                    // ---- G_{2l+1}: BatchNorm 2l+1 backward, conv_block2 gradient, d(x0 + H) ---------------------------------------------------
+                    // ---- G_{2l+1}: conv_block2 again (BatchNorm 2l+1 backward, conv_block2 gradient, d(x0 + H)) ------------------------------
 #pragma unroll
                     for (int e = 0; e < NS; ++e)
 #pragma unroll
                         for (int r = 0; r < 3; ++r) V[e][r] = relu2(fmaf(2.f, H[e][r], relu2(y1[e][r])));
                     stage_conv(V, 1.0f, kc.w[1], sh_rd2, sh_rd2_lo, z, hk, hks);              // x-hat of BatchNorm 2l+1; hk, hks <- V
-#pragma unroll
-                    for (int e = 0; e < NS; ++e) {
+                }
+                // BatchNorm IDX backward of one sample: d z (and, G_{2l+1}, the gradient that bypasses the convolution)
+                auto bn_backward = [&](int e) {
+                    if constexpr (BLK == 1) {
                         keep_until_here(z[e][3]);
 #pragma unroll
                         for (int r = 0; r < 3; ++r) {
@@ -806,32 +814,40 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
                             const float v = bA[r] * (fmaf(-xh, bk2[r], dy) - bk1[r]);
                             dz[e][r] = (HS + e < ns) ? v * colm : 0.f;
                         }
-                    }
-                } else {
-                    // ---- G_{2l}: BatchNorm 2l backward, conv_block1 + theta gradients, d X_l -------------------------------------------------
-#pragma unroll
-                    for (int e = 0; e < NS; ++e)
+                    } else {
 #pragma unroll
                         for (int r = 0; r < 3; ++r) {
                             const float dy = y1[e][r] > 0.f ? SB[HS + e][r] : 0.f;
                             const float v = bA[r] * (fmaf(-xh0[e][r], bk2[r], dy) - bk1[r]);
                             dz[e][r] = (HS + e < ns) ? v * colm : 0.f;
                         }
-                }
+                    }
+                };
                 // d(input of the convolution) = W^T-conv(d z); weight gradient from the transposed tiles: acc += dzT x [hT | hsT]
-                // (contraction over the columns t = 4 g + r of the transposed tiles)
+                // (contraction over the columns t = 4 g + r of the transposed tiles).  The transposition is an LDS round trip: both tiles
+                // are already packed (hi | lo) pairs, written as they are and read back with the transposing read, the tap at t - d as the
+                // same image read d rows higher -- no matrix instruction, no split.  One image serves the samples back to back (LDS
+                // operations of a wavefront execute in order).  Nothing waits for LDS with nothing to do: a sample's H / V tile makes its
+                // round trip under the sample's own BatchNorm backward, its d z tile (shift tile and image) under the next sample's
+                // BatchNorm backward or the d I products.
                 f32x4 dI[NS];
                 {
                     u32x4 bh[NS], bl[NS];
-                    f32x4 dzT[NS], hT[NS];
+                    Pk q[NS], u[NS], us[NS];            // d z, the operand and the operand of the tap at t - d, transposed
 #pragma unroll
                     for (int e = 0; e < NS; ++e) {
+                        wg_img[WG_H_HI + wg_wr] = hk[e].hi;
+                        wg_img[WG_H_LO + wg_wr] = hk[e].lo;
+                        u[e] = Pk{lds_read_tr16(wg_img + WG_H_HI + wg_rd), lds_read_tr16(wg_img + WG_H_LO + wg_rd)};
+                        us[e] = Pk{lds_read_tr16(wg_img + WG_H_HI + wg_rds), lds_read_tr16(wg_img + WG_H_LO + wg_rds)};
+                        bn_backward(e);
                         const Pk p = pack3(dz[e][0], dz[e][1], dz[e][2], 0.f);
+                        wg_img[WG_DZ_HI + wg_wr] = p.hi;
+                        wg_img[WG_DZ_LO + wg_wr] = p.lo;
                         const Shifted nx = shift_read(sh_tile, sh_bk, sh_bk_lo, lane, p);
                         bh[e] = cat(p.hi, nx.hi);
                         bl[e] = cat(p.lo, nx.lo);
-                        dzT[e] = mfma16z(cat(p.hi, p.lo), ident);
-                        hT[e] = mfma16z(cat(hk[e].hi, hk[e].lo), ident);
+                        q[e] = Pk{lds_read_tr16(wg_img + WG_DZ_HI + wg_rd), lds_read_tr16(wg_img + WG_DZ_LO + wg_rd)};
                         __builtin_amdgcn_sched_barrier(0);
                     }
 #pragma unroll
@@ -839,25 +855,6 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
                         dI[e] = mfma16z(wT.hi, bh[e]);
                         dI[e] = mfma16(wT.hi, bl[e], dI[e]);
                         dI[e] = mfma16(wT.lo, bh[e], dI[e]);
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                    Pk q[NS], u[NS], us[NS];
-#pragma unroll
-                    for (int e = 0; e < NS; ++e) {
-                        q[e] = pack3(dzT[e][0], dzT[e][1], dzT[e][2], dzT[e][3]);
-                        u[e] = pack3(hT[e][0], hT[e][1], hT[e][2], hT[e][3]);
-                        // The operand of the tap at t - d is the SAME transposed tile shifted by d columns.  In this arrangement lane
-                        // (g, slot) holds columns 4 g .. 4 g + 3 as two packed pairs, so the shift is a move between registers plus the
-                        // last pair of the row above (lane - 16; nothing above row 0 = the causal zeros): no third transposing MFMA, no
-                        // third split.  d = 2 (conv_block2): pairs move whole; d = 1 (conv_block1): halves recombine (two byte permutes).
-                        const unsigned uh = __builtin_amdgcn_ds_bpermute((lane - 16) << 2, (int)u[e].hi.y), ul = __builtin_amdgcn_ds_bpermute((lane - 16) << 2, (int)u[e].lo.y);
-                        const unsigned ah = g == 0 ? 0u : uh, al = g == 0 ? 0u : ul;
-                        if constexpr (BLK == 1) {
-                            us[e] = Pk{u32x2{ah, u[e].hi.x}, u32x2{al, u[e].lo.x}};
-                        } else {
-                            us[e] = Pk{u32x2{__builtin_amdgcn_perm(u[e].hi.x, ah, 0x05040302u), __builtin_amdgcn_perm(u[e].hi.y, u[e].hi.x, 0x05040302u)},
-                                       u32x2{__builtin_amdgcn_perm(u[e].lo.x, al, 0x05040302u), __builtin_amdgcn_perm(u[e].lo.y, u[e].lo.x, 0x05040302u)}};
-                        }
                         acc_w0 = mfma16(cat(q[e].hi, q[e].lo), cat(u[e].hi, u[e].hi), acc_w0);
                         acc_w1 = mfma16(cat(q[e].hi, q[e].lo), cat(us[e].hi, us[e].hi), acc_w1);
                     }
@@ -1152,24 +1149,29 @@ __global__ __launch_bounds__(64 * MXT_WAVES, MX_WAVES_PER_SIMD) void stgcn_train
 // =====================================================================================================================
 // host side
 // =====================================================================================================================
-static size_t mxt_lds_bytes(int L, int kind, int idx, int N) {
+static constexpr size_t mxt_lds_bytes(int L, int kind, int idx, int N) {
     const int blk = kind == PH_TOP ? 1 : idx % 2, ly = kind == PH_TOP ? L - 1 : idx / 2;
     const bool need_sb = kind == PH_G && blk == 0, grad_in = kind == PH_G && (blk == 1 || ly >= 1), bwd_prev = kind == PH_G && blk == 0 && ly >= 1;
     const bool h_in = (kind == PH_F || kind == PH_G) && blk == 1 && ly >= 1;     // H_IN of mxt_phase_body: no adjacency tile
     const bool h_top = kind == PH_TOP && ly >= 1;                                  // H_TOP: an H tile in its place
     const bool h_out = kind == PH_F && blk == 0 && ly >= 1;       // H_OUT: the staging tile
     const int XF = 40 * N;
-    const size_t wave = (size_t)MXT_ZERO_FLOATS + MXT_SCRATCH_FLOATS + MXT_SHIFT_FLOATS + XF + (h_in ? 0 : h_top ? XF : 220) + (need_sb ? XF : 0) + (grad_in ? XF : 0) +
+    const size_t wave = (size_t)MXT_ZERO_FLOATS + MXT_SCRATCH_FLOATS + MXT_SHIFT_FLOATS + (kind == PH_G ? MXT_WG_FLOATS : 0) + XF + (h_in ? 0 : h_top ? XF : 220) + (need_sb ? XF : 0) + (grad_in ? XF : 0) +
                         (bwd_prev ? XF : 0) + (h_out ? XF : 0);
     const size_t shared = (size_t)((2 * L * MXT_BNC * F + 3) & ~3) + MXT_RED_FLOATS + 2 * MXT_WAVES * (2 * F + 2);
     return (shared + MXT_WAVES * wave) * sizeof(float);
 }
+// stgcn_train_mx_shape_ok admits num_patch <= 15 and at most MX_MAX_LAYERS layers: the largest request (G_{2l}, l >= 1: five tiles and the
+// transposing image per wavefront) stays inside what a launch may ask for, so a shape the gate accepts cannot fail a launcher's check.
+constexpr size_t MXT_MAX_LDS_BYTES = 80 * 1024;
+static_assert(mxt_lds_bytes(MX_MAX_LAYERS, PH_G, 2, 15) <= MXT_MAX_LDS_BYTES && mxt_lds_bytes(MX_MAX_LAYERS, PH_G, 3, 15) <= MXT_MAX_LDS_BYTES,
+              "the largest matrix-core phase must fit its LDS limit");
 
 template <int L, int KIND, int IDX, int NFIX>
 static int mxt_launch(const MxTrainK& k, hipStream_t stream, int max_grid, int* grid_out) {
     auto kern = &stgcn_train_mx_kernel<L, KIND, IDX, NFIX>;
     const size_t lds = mxt_lds_bytes(L, KIND, IDX, k.N);
-    if (lds > 80 * 1024) return RULGNN_EUNSUPPORTED;
+    if (lds > MXT_MAX_LDS_BYTES) return RULGNN_EUNSUPPORTED;
     if (lds > 48 * 1024 &&
         hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return RULGNN_EHIP;
@@ -1250,7 +1252,7 @@ static int mxt_persist_launch(const MxTrainK& k, hipStream_t stream, int64_t gri
     for (int i = 1; i < 2 * L; ++i) lds = std::max(lds, mxt_lds_bytes(L, PH_F, i, k.N));
     lds = std::max(lds, mxt_lds_bytes(L, PH_TOP, 0, k.N));
     for (int i = 0; i < 2 * L; ++i) lds = std::max(lds, mxt_lds_bytes(L, PH_G, i, k.N));
-    if (lds > 80 * 1024) return RULGNN_EUNSUPPORTED;
+    if (lds > MXT_MAX_LDS_BYTES) return RULGNN_EUNSUPPORTED;
     if (lds > 48 * 1024 &&
         hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
         return RULGNN_EHIP;

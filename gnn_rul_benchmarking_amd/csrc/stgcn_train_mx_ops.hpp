@@ -13,6 +13,12 @@ namespace {
 constexpr int MXT_ZERO_FLOATS = 192;     // zeroed LDS words padded lanes read instead of a tile (largest use: 3 * 55 + 1)
 constexpr int MXT_SCRATCH_FLOATS = 128;  // head: d pool / arg-max exchange between the row mapping and the D layout
 constexpr int MXT_SHIFT_FLOATS = 264;    // shift tile: [64 lanes + zero slot] x (hi pair | lo pair) = 1040 bytes
+// Backward phases: the transposing image of the conv weight gradient's two operands (d z, and H or V), one per wavefront.  Unit: the
+// 8-byte chunk (t, g) = the f16 of column t, slots 4 g .. 4 g + 3, as one plane (hi or lo) of a Pk holds them.  Four planes of 64 chunks;
+// the H / V planes carry one more chunk of zeros, which the shifted read addresses for the columns in front of the tile.
+constexpr int WG_ZERO = 64;
+constexpr int WG_DZ_HI = 0, WG_DZ_LO = 64, WG_H_HI = 128, WG_H_LO = WG_H_HI + 65;
+constexpr int MXT_WG_FLOATS = (2 * (WG_H_LO + 65) + 3) & ~3;     // 2080 bytes; the tiles behind it stay 16-byte aligned (LDS-DMA)
 constexpr int MXT_WAVES = 4;              // wavefronts per workgroup: they share the BatchNorm table and reduce their sums / gradient rows in LDS
 constexpr int MXT_RED_FLOATS = 448;      // gradient row image of a phase: at most 15 x 15 + 15 + 200 floats
 constexpr int MXT_BNC = BN_TABLE_ROWS;   // per-BatchNorm constants: mean, istd, gamma, beta, gamma istd, mean(dy), mean(dy xhat)
@@ -36,6 +42,17 @@ __device__ __forceinline__ bool finite_f(float v) { return __builtin_fabsf(v) <=
 // shift tile access for both directions: column t - d (forward taps) or t + d (transposed convolution); `rd` = the lane to read or 64
 __device__ __forceinline__ Shifted shift_read(u32x2* tile, int rd, int rd_lo, int lane, const Pk& p) {
     return shift_columns(tile, rd, rd_lo, lane, p.hi, p.lo);
+}
+
+// Where chunk (t, g) of a plane sits.  Writes (ds_write_b64: groups of 16 lanes = the 16 columns of one g, 32 banks of 4 bytes) and the
+// transposed read (groups of 32 lanes = 8 consecutive rows x 4 chunks, 64 banks) are both free of bank conflicts: within 8 rows the
+// chunks of a row are 8 apart, and the upper 8 rows rotate g by one so that columns t and t + 8 of one g land 64 bytes apart.
+__host__ __device__ constexpr int wg_chunk(int t, int g) { return (t & 7) + 8 * ((g + (t >> 3)) & 3) + 32 * (t >> 3); }
+// ds_read_b64_tr_b16: lane i of a 16-lane group receives 16-bit column i of the four 8-byte rows the group's lanes 4 q + p address
+// (row q, columns 4 p .. 4 p + 3), row q in element q.  Every lane must be active and supply an 8-byte aligned address.
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ u32x2 lds_read_tr16(const u32x2* p) {
+    return __builtin_bit_cast(u32x2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)p));
 }
 
 struct ConvOp { u32x4 hi, lo; };
