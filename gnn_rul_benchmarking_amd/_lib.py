@@ -242,6 +242,8 @@ _SIGNATURES = {
     "rulgnn_stgcn_train_fwdbwd_ready_f32": (C.c_int, [C.POINTER(StgcnShape), C.POINTER(StgcnTrainArgs), GRAD_READY_FN, C.c_void_p, C.c_void_p]),
     "rulgnn_stgcn_train_fwdbwd_syncbn_f32": (C.c_int, [C.POINTER(StgcnShape), C.POINTER(StgcnTrainArgs), C.c_float, ALLREDUCE_F64_FN,
                                                         C.c_void_p, C.c_void_p]),
+    "rulgnn_stgcn_train_fwdbwd_syncbn_ready_f32": (C.c_int, [C.POINTER(StgcnShape), C.POINTER(StgcnTrainArgs), C.c_float, ALLREDUCE_F64_FN,
+                                                              C.c_void_p, GRAD_READY_FN, C.c_void_p, C.c_void_p]),
     "rulgnn_stgcn_train_step_f32": (C.c_int, [C.POINTER(StgcnShape), C.POINTER(StgcnTrainArgs), C.POINTER(AdamArgs),
                                                C.c_void_p]),
     "rulgnn_stgcn_train_step_path_f32": (C.c_int, [C.POINTER(StgcnShape), C.POINTER(StgcnTrainArgs), C.POINTER(AdamArgs), C.c_int32,

@@ -192,7 +192,25 @@ int rulgnn_stgcn_train_fwdbwd_syncbn_f32(const rulgnn_stgcn_shape* shape, const 
     const int rc = check_train(shape, args, true);
     if (rc != RULGNN_OK) return rc;
     if (!(bn_param_grad_scale >= 0.f && bn_param_grad_scale <= 1.f) || !allreduce || args->bn_moment_weight != 0.f) return RULGNN_EINVAL;
-    if (tiled(shape)) return RULGNN_EUNSUPPORTED;          // the tiled path keeps local statistics
+    if (tiled(shape)) {
+        const SyncHook sync = {bn_param_grad_scale, allreduce, user};
+        return stgcn_tiled_train(shape, args, 2, static_cast<hipStream_t>(stream), nullptr, &sync);
+    }
+    return stgcn_train_fwdbwd_syncbn(shape, args, bn_param_grad_scale, allreduce, user, static_cast<hipStream_t>(stream), RULGNN_STEP_CHAIN);
+}
+
+int rulgnn_stgcn_train_fwdbwd_syncbn_ready_f32(const rulgnn_stgcn_shape* shape, const rulgnn_stgcn_train_args* args,
+                                               float bn_param_grad_scale, rulgnn_allreduce_f64_fn allreduce, void* user,
+                                               rulgnn_grad_ready_fn ready, void* ready_user, void* stream) {
+    const int rc = check_train(shape, args, true);
+    if (rc != RULGNN_OK) return rc;
+    if (!(bn_param_grad_scale >= 0.f && bn_param_grad_scale <= 1.f) || !allreduce || !ready || args->bn_moment_weight != 0.f) return RULGNN_EINVAL;
+    if (tiled(shape)) {
+        const SyncHook sync = {bn_param_grad_scale, allreduce, user};
+        const GradReadyHook hook = {ready, ready_user};
+        return stgcn_tiled_train(shape, args, 2, static_cast<hipStream_t>(stream), &hook, &sync);
+    }
+    // (buckets of a few KB: nothing to overlap, no region is reported -- as rulgnn_stgcn_train_fwdbwd_ready_f32 on these shapes)
     return stgcn_train_fwdbwd_syncbn(shape, args, bn_param_grad_scale, allreduce, user, static_cast<hipStream_t>(stream), RULGNN_STEP_CHAIN);
 }
 
@@ -203,7 +221,10 @@ int rulgnn_stgcn_train_fwdbwd_syncbn_path_f32(const rulgnn_stgcn_shape* shape, c
     if (rc != RULGNN_OK) return rc;
     if (!(bn_param_grad_scale >= 0.f && bn_param_grad_scale <= 1.f) || !allreduce || args->bn_moment_weight != 0.f) return RULGNN_EINVAL;
     if (path != RULGNN_STEP_AUTO && path != RULGNN_STEP_CHAIN && path != RULGNN_STEP_MX) return RULGNN_EINVAL;
-    if (tiled(shape)) return RULGNN_EUNSUPPORTED;
+    if (tiled(shape)) {                                    // (one launch form there: `path` is ignored, as by rulgnn_stgcn_train_step_path_f32)
+        const SyncHook sync = {bn_param_grad_scale, allreduce, user};
+        return stgcn_tiled_train(shape, args, 2, static_cast<hipStream_t>(stream), nullptr, &sync);
+    }
     return stgcn_train_fwdbwd_syncbn(shape, args, bn_param_grad_scale, allreduce, user, static_cast<hipStream_t>(stream), path);
 }
 

@@ -120,8 +120,17 @@ struct GradReadyHook {
     rulgnn_grad_ready_fn fn;
     void* user;
 };
+// Synchronised BatchNorm hook of the ST_GCN steps (include/rulgnn.h: rulgnn_stgcn_train_fwdbwd_syncbn_f32): after every launch that
+// completes a reduction pair its replicas are collapsed into replica 0 (the others zeroed, so that the consumers' replica sum is
+// unchanged) and the caller's all-reduce runs on those 2 F contiguous doubles.
+struct SyncHook {
+    float bn_param_grad_scale;
+    rulgnn_allreduce_f64_fn fn;
+    void* user;
+};
+// (`sync` != nullptr: whole steps only, mode 2)
 int stgcn_tiled_train(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args* a, int mode, hipStream_t stream,
-                      const GradReadyHook* ready = nullptr);
+                      const GradReadyHook* ready = nullptr, const SyncHook* sync = nullptr);
 size_t stgcn_train_workspace_bytes(const rulgnn_stgcn_shape* s);
 // The LDS bytes a launch form of the fused row-mapped kernels requests at this shape (and MPNN order): the exact eval kernel, the scan
 // behind the wide matrix-core eval kernel (order 1), the largest phase of the fp32 training chain; 0 where the row-mapped geometry does

@@ -634,6 +634,23 @@ __device__ __forceinline__ void t_pair_reduce(const float (&sa)[F], const float 
     }
 }
 
+// Synchronised BatchNorm: the T_REP replicas of one reduction pair (2 F contiguous doubles at `off` of every replica, the
+// replicas `stride` doubles apart: tc_sf(L) for a forward pair, tc_sb(L) for a backward one) summed into replica 0 in tc_sum()'s order,
+// the other replicas' entries zeroed -- every consumer's tc_sum() then returns what it returned before, and after the caller's
+// all-reduce on replica 0's 2 F doubles the GLOBAL sum.  One workgroup: 20 threads with 16 dependent loads each (see
+// profiles/r10_syncbn_tiled.md for what the 4 L launches cost).
+__global__ __launch_bounds__(64) void t_cells_collapse_kernel(double* __restrict__ cells, int off, int stride) {
+    const int i = threadIdx.x;
+    if (i >= 2 * F) return;
+    double v = 0.0;
+#pragma unroll
+    for (int r = 0; r < T_REP; ++r) {
+        v += cells[r * stride + off + i];
+        if (r) cells[r * stride + off + i] = 0.0;
+    }
+    cells[off + i] = v;
+}
+
 // The kernels with a reduction behind them (BatchNorm sums, convolution weight-gradient partials) are PERSISTENT: at most T_PGRID
 // workgroups (four per CU, what the weight-gradient kernels' LDS tiles allow), each walking chunks of 256 positions with its sums in
 // registers, so that the BatchNorm constants (a chain of fp64 divisions and a square root over 16 cell replicas) and the block
@@ -1141,6 +1158,7 @@ struct TFin {
     int64_t global_batch;
     double cnt;
     float moment_weight;
+    float cell_grad_scale;    // 1; under synchronised BatchNorm the caller's factor: the cells then hold GLOBAL sums on every rank
     int write_loss, write_grads;
 };
 constexpr int TFIN_SUB = (CONVW + 31) / 32;     // workgroups per (layer, conv block): 32 weights each
@@ -1182,8 +1200,8 @@ __global__ __launch_bounds__(1024) void t_finalize_kernel(TFin f) {
     if (threadIdx.x < F) {
         const int c = threadIdx.x;
         if (f.write_grads) {
-            f.grads[l * LS + off_bn_g(N, blk) + c] = (float)tc_sum(f.cells_bwd, tc_sb(L), (bnidx * 2 + 1) * F + c);
-            f.grads[l * LS + off_bn_b(N, blk) + c] = (float)tc_sum(f.cells_bwd, tc_sb(L), (bnidx * 2 + 0) * F + c);
+            f.grads[l * LS + off_bn_g(N, blk) + c] = (float)(tc_sum(f.cells_bwd, tc_sb(L), (bnidx * 2 + 1) * F + c) * (double)f.cell_grad_scale);
+            f.grads[l * LS + off_bn_b(N, blk) + c] = (float)(tc_sum(f.cells_bwd, tc_sb(L), (bnidx * 2 + 0) * F + c) * (double)f.cell_grad_scale);
         }
         const double mean = tc_sum(f.cells_fwd, tc_sf(L), (bnidx * 2 + 0) * F + c) / f.cnt;
         const double ex2 = tc_sum(f.cells_fwd, tc_sf(L), (bnidx * 2 + 1) * F + c) / f.cnt;
@@ -1295,10 +1313,11 @@ size_t stgcn_tiled_train_workspace_bytes(const rulgnn_stgcn_shape* s) {
 
 
 int stgcn_tiled_train(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args* ar, int mode /* 0 fwd, 1 bwd, 2 both */,
-                      hipStream_t stream, const GradReadyHook* ready) {
+                      hipStream_t stream, const GradReadyHook* ready, const SyncHook* sync) {
     TWs w;
     tws_layout(s, &w);
     if (ar->workspace_bytes < w.total) return RULGNN_EWORKSPACE;
+    if (sync && mode != 2) return RULGNN_EINVAL;
     const int N = s->num_patch, L = s->num_layers, LS = layer_stride(N);
     const int64_t B = s->batch, BN_ = B * N;
     char* ws = static_cast<char*>(ar->workspace);
@@ -1334,6 +1353,9 @@ int stgcn_tiled_train(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args
     // ... nor at batch-100-sized row counts: there every launch sits at its latency floor and the fork / join events cost more than the
     // overlap returns (XJTU-SY batch 100: 0.38 -> 0.40 ms with it, batch 1024: 1.24 -> 1.22 ms).
     // (every parameter-gradient product as one launch pair at the end of the chain where the wiring is small: no side stream then)
+    // Under synchronised BatchNorm (`sync`) both stay as they are without it: none of the parameter-gradient products reads a reduction
+    // cell, and the cell callbacks are ordered on `stream`, which the side stream only forks from and joins -- so a synchronised step
+    // launches the plain step's kernels plus the 4 L collapses.  With `ready` they are off, as in the plain step.
     const bool pg_batch = !ready && t_pgrad_batched(N, L);
     SplitKJob pjobs[3 + 2 * 8];
     int npj = 0;
@@ -1371,8 +1393,17 @@ int stgcn_tiled_train(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args
     t.drop_key = 0;
     t.key_dev = nullptr;
     const StepState* sstate = static_cast<const StepState*>(ar->step_state);
-    t.cnt = (double)B * (double)N;
+    t.cnt = (double)(sync ? ar->global_batch : B) * (double)N;         // synchronised BatchNorm: the cells hold the GLOBAL batch's sums
     t.cells_fwd = cells; t.cells_bwd = cells + T_REP * tc_sf(L);
+    // synchronised BatchNorm: reduction pair `bn_index` (forward or backward) is complete behind the launch just enqueued -- collapse its
+    // replicas and hand replica 0's 2 F doubles to the caller's all-reduce, in `stream` order, before the next launch reads the pair
+    auto sync_pair = [&](double* base, int stride, int bn_index) -> int {
+        if (!sync) return RULGNN_OK;
+        (void)hipGetLastError();
+        hipLaunchKernelGGL(t_cells_collapse_kernel, dim3(1), dim3(64), 0, stream, base, bn_index * 2 * F, stride);
+        if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
+        return sync->fn(sync->user, base + bn_index * 2 * F, 2 * F, stream) == 0 ? RULGNN_OK : RULGNN_ECALLBACK;
+    };
     const int has_dpred = ar->dpred ? 1 : (ar->y ? 0 : 2);
     const float* gy = ar->dpred ? ar->dpred : ar->y;
     int rc = RULGNN_OK;
@@ -1412,7 +1443,11 @@ int stgcn_tiled_train(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args
                        l == 0 && agg0 ? (int)B : n_pos, am_th(l), n_th, pb_fwd ? planes : nullptr, pb_fwd);
             if (rc != RULGNN_OK) return rc;
             T_LAUNCH_P(t_conv1_train_kernel, BN_, Hpl, pl, TP(w.off_z1, l), 2 * l, t);
+            rc = sync_pair(t.cells_fwd, tc_sf(L), 2 * l);
+            if (rc != RULGNN_OK) return rc;
             T_LAUNCH_P(t_conv2_train_kernel, BN_, TP(w.off_z1, l), Hpl, pl, TP(w.off_o0, l), TP(w.off_z2, l), 2 * l + 1, t);
+            rc = sync_pair(t.cells_fwd, tc_sf(L), 2 * l + 1);
+            if (rc != RULGNN_OK) return rc;
             // (+ the next layer's A.X, or the channel max-pool behind the last layer)
             T_LAUNCH(t_tail_train_kernel, BN_, TP(w.off_z2, l), TP(w.off_o0, l), TP(w.off_X, l), pl, TP(w.off_X, l + 1), 2 * l + 1, t,
                      (const float*)A, l + 1 < L ? TP(w.off_AX, l + 1) : (float*)nullptr, l + 1 < L ? (float*)nullptr : pooled,
@@ -1465,8 +1500,12 @@ int stgcn_tiled_train(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args
             t.key_dev = sstate ? &sstate->drop_key[l] : nullptr;
             T_LAUNCH_P(t_tail_bwd_kernel, BN_, dpool, TP(w.off_X, l + 1), dX, TP(w.off_z2, l), TP(w.off_o0, l), pl, gsum, 2 * l + 1,
                      l == L - 1 ? 1 : 0, t);
+            rc = sync_pair(t.cells_bwd, tc_sb(L), 2 * l + 1);
+            if (rc != RULGNN_OK) return rc;
             T_LAUNCH_P(t_conv2_bwd_kernel, BN_, gsum, TP(w.off_z2, l), TP(w.off_o0, l), TP(w.off_z1, l), pl, gsum0,
                      gpart + (size_t)(2 * l + 1) * w.grid * CONVW, 2 * l + 1, t);
+            rc = sync_pair(t.cells_bwd, tc_sb(L), 2 * l);
+            if (rc != RULGNN_OK) return rc;
             float* dHp = TP(w.off_dH, l);
             T_LAUNCH_P(t_conv1_bwd_kernel, BN_, gsum0, TP(w.off_z1, l), TP(w.off_H, l), pl, dHp,
                      gpart + (size_t)(2 * l) * w.grid * CONVW, 2 * l, t, am_dh(l));
@@ -1516,6 +1555,7 @@ int stgcn_tiled_train(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args
     f.grads = ar->grads; f.loss = ar->loss; f.bn_batch = ar->bn_batch;
     f.grid = w.grid; f.N = N; f.L = L; f.global_batch = ar->global_batch; f.cnt = t.cnt;
     f.moment_weight = ar->bn_moment_weight;
+    f.cell_grad_scale = sync ? sync->bn_param_grad_scale : 1.0f;
     f.write_loss = (has_dpred == 0) && ar->loss && mode != 0;
     f.write_grads = mode != 0;          // forward only: just the batch statistics for the running-stat update
     (void)hipGetLastError();

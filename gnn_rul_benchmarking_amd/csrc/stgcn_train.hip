@@ -1269,12 +1269,8 @@ enum TrainMode { TM_FORWARD = 0, TM_BACKWARD = 1, TM_FWDBWD = 2 };
 
 // Synchronised BatchNorm ("per-BN all-reduce of [sum x, sum x^2, count] in forward and the matching [sum dy, sum dy xhat]
 // in backward"): after every phase that completes a reduction pair its 16 replicas are collapsed into replica 0 (the others
-// zeroed, so that the consumers' replica sum is unchanged) and the caller's all-reduce runs on those 2 F contiguous doubles.
-struct SyncHook {
-    float bn_param_grad_scale;
-    rulgnn_allreduce_f64_fn fn;
-    void* user;
-};
+// zeroed, so that the consumers' replica sum is unchanged) and the caller's all-reduce runs on those 2 F contiguous doubles
+// (SyncHook: stgcn_host.hpp, shared with the tiled path).
 
 __global__ void stgcn_cells_collapse_kernel(double* cells, int off, int n, int stride) {
     const int i = threadIdx.x;

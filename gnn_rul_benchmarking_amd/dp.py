@@ -13,10 +13,12 @@ all-reduce, over a single flat fp32 bucket:
 * BatchNorm: normalisation uses each rank's LOCAL batch statistics (the torch DDP default); the
   running statistics are updated from the all-reduced global-batch moments, so replicas stay
   bit-identical without a separate buffer broadcast.
-* ``DataParallel(sync_bn=True)`` (ST_GCN, num_patch <= 64): SYNCHRONISED BatchNorm -- SURVEY.md section 8e's "per-BN
-  all-reduce of [sum x, sum x^2, count] in forward and the matching [sum dy, sum dy*xhat] in backward".  The step then
-  computes exactly the single-GPU function of the concatenated batch (tests/test_dp_cpu.py, tests/test_syncbn_gpu.py),
-  at the price of 4 L more latency-bound all-reduces of 20 doubles between the phase kernels (8 at L = 2).
+* ``DataParallel(sync_bn=True)`` (ST_GCN on every path, FC_STGNN, ASTGCNN): SYNCHRONISED BatchNorm -- SURVEY.md section 8e's
+  "per-BN all-reduce of [sum x, sum x^2, count] in forward and the matching [sum dy, sum dy*xhat] in backward".  The step then
+  computes exactly the single-GPU function of the concatenated batch (tests/test_dp_cpu.py, tests/test_syncbn_gpu.py,
+  tests/test_syncbn_tiled_gpu.py), at the price of 4 L more latency-bound all-reduces of 20 doubles between the kernels
+  (8 at L = 2).  On ST_GCN's tiled path (num_patch > 64: a bucket of megabytes) the bucket still leaves in gradient-ready
+  regions beside the backward (``_sync_bn_overlapped_step``).
 
 For C-MAPSS shapes the bucket is 6.4 KB: the collective is latency-bound, so
 it is issued once, on the compute stream, directly on the kernels' output buffer (no copy)."""
@@ -234,20 +236,95 @@ class DataParallel:
             compute.wait_event(fin)
         self.last_overlap_regions = sorted(done)      # (tests / diagnostics)
 
+    def _sync_bn_overlapped_step(self, model, X_shard, y_shard, global_batch, sample_offset, reduce_cells):
+        """The synchronised-BatchNorm step of a model that also reports final gradient regions (ST_GCN's tiled path), with both: the
+        cell all-reduces run in compute-stream order between the kernels, each reported bucket region leaves on the communication
+        stream behind an event recorded on the compute stream (as in ``_overlapped_step``), and the complement -- with the bucket
+        tail (loss, weighted global statistics), written before it is sent -- goes out when the step has been enqueued.
+
+        Every rank issues the SAME interleaved sequence, ``model.sync_collective_schedule()`` (a function of the shape alone) followed
+        by the complement; a rank with an empty shard replays exactly it, zeros for the cells and slices of a zero bucket for the
+        regions.  What the kernels issued is compared with the schedule when everything has been joined; returns the mismatch message
+        (or None) for the caller to raise behind its own checks.
+
+        With ``bn_collective="group"`` the cell reductions and the bucket slices share one process group, so the backend may serialise
+        them (a slice in flight can hold up the next 20-double reduction): a correctness-neutral limit on how much overlaps.  Nobody
+        has measured it on two devices.  With ``"peer"`` the cell reductions never enter Python, so only the regions are checked."""
+        bucket = model.bucket
+        on_gpu = bucket.is_cuda
+        schedule = [tuple(item) for item in model.sync_collective_schedule()]
+        if on_gpu:
+            compute = torch.cuda.current_stream()
+            if getattr(self, "_comm_stream", None) is None or self._comm_stream.device != bucket.device:
+                self._comm_stream = torch.cuda.Stream(device=bucket.device)
+            comm = self._comm_stream
+        issued, done = [], []
+
+        def cells(view):
+            issued.append(("cells", int(view.numel())))
+            reduce_cells(view)
+
+        def launch(offset, count, record=True):
+            if record:
+                issued.append(("region", int(offset), int(count)))
+            if on_gpu:
+                ev = torch.cuda.Event()
+                ev.record(compute)
+                comm.wait_event(ev)
+                with torch.cuda.stream(comm):
+                    dist.all_reduce(bucket[offset:offset + count], op=dist.ReduceOp.SUM, group=self.group)
+            else:
+                dist.all_reduce(bucket[offset:offset + count], op=dist.ReduceOp.SUM, group=self.group)
+            done.append((offset, offset + count))
+
+        b = X_shard.size(0)
+        if b == 0:
+            bucket.zero_()
+            for item in schedule:
+                if item[0] == "cells":
+                    reduce_cells(torch.zeros(item[1], dtype=torch.float64, device=bucket.device))
+                else:
+                    launch(item[1], item[2], record=False)
+            self._empty_shard_bookkeeping(model, global_batch)
+            mismatch = None
+        else:
+            in_python = self.peer is None
+            model.fused_mse_step_syncbn(X_shard, y_shard, global_batch, sample_offset, 1.0 if self.rank == 0 else 0.0,
+                                        cells if in_python else self.peer, grad_ready=launch)
+            tail = bucket[model.num_live + 1:model.num_live + 1 + model._bn_batch.numel()]
+            torch.mul(model._bn_batch.reshape(-1), float(b) / float(global_batch), out=tail)
+            want = schedule if in_python else [item for item in schedule if item[0] == "region"]
+            mismatch = None if issued == want else f"the step's collectives {issued} differ from the model's schedule {want}"
+        for lo, hi in self._complement(done, bucket.numel()):
+            launch(lo, hi - lo, record=False)
+        if on_gpu:
+            fin = torch.cuda.Event()
+            fin.record(comm)
+            compute.wait_event(fin)
+        self.last_overlap_regions = sorted(done)      # (tests / diagnostics)
+        return mismatch
+
     def _sync_bn_step(self, model, optimizer, X_shard, y_shard, global_batch, sample_offset):
-        """Synchronised-BatchNorm step: the model's phase chain calls back for every BatchNorm reduction pair; an empty shard
-        joins the same collectives with zeros."""
+        """Synchronised-BatchNorm step: the model's kernel chain calls back for every BatchNorm reduction pair; an empty shard
+        joins the same collectives with zeros.  Where the model reports final gradient regions and the bucket is large
+        (ST_GCN's tiled path) the bucket leaves in those regions beside the backward: ``_sync_bn_overlapped_step``."""
         b = X_shard.size(0)
         if not hasattr(model, "fused_mse_step_syncbn"):
             raise RuntimeError(f"{type(model).__name__} has no synchronised-BatchNorm step (ST_GCN, FC_STGNN and ASTGCNN do); "
                                "use sync_bn=False")
         schedule = model.sync_bn_schedule()
+        # decided from what every rank shares (the model and its bucket), never from this rank's shard
+        overlap = getattr(model, "reports_ready_gradients", False) and hasattr(model, "sync_collective_schedule") and \
+            model.bucket.numel() * 4 >= self.OVERLAP_MIN_BYTES
         # rank 0 must hold data whenever the batch is not empty (shard_bounds()): it alone contributes the BatchNorm scale / shift
         # gradients.  A violation is raised AFTER this rank has joined every collective of the step with zeros -- raising here would
         # leave the other ranks waiting in theirs forever.
         violated = b == 0 and self.rank == 0 and global_batch > 0
         reduce_cells = self.peer if self.peer is not None else (lambda cells: dist.all_reduce(cells, op=dist.ReduceOp.SUM, group=self.group))
-        if b == 0:
+        mismatch = None
+        if overlap:
+            mismatch = self._sync_bn_overlapped_step(model, X_shard, y_shard, global_batch, sample_offset, reduce_cells)
+        elif b == 0:
             for n in schedule:
                 zero = torch.zeros(n, dtype=torch.float64, device=model.bucket.device)
                 reduce_cells(zero)
@@ -261,9 +338,12 @@ class DataParallel:
             # ranks, which also hands them to a rank whose shard was empty -- one bucket all-reduce as in the local-BN step
             tail = model.bucket[model.num_live + 1:model.num_live + 1 + model._bn_batch.numel()]
             torch.mul(model._bn_batch.reshape(-1), float(b) / float(global_batch), out=tail)
-        self.all_reduce_bucket(model.bucket)
+        if not overlap:
+            self.all_reduce_bucket(model.bucket)
         if violated:
             raise RuntimeError("synchronised BatchNorm expects shard_bounds() sharding: rank 0 holds data whenever the batch is not empty")
+        if mismatch:
+            raise RuntimeError(mismatch)
         self._optimizer_and_stats(model, optimizer, global_batch, from_bucket_stats=True)
         self._note_guard(model, model.bucket[model.num_live])
         return model.bucket[model.num_live]

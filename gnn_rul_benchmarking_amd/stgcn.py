@@ -354,11 +354,54 @@ class ST_GCN_model(FlatModule):
         """float64 counts of the all-reduces one synchronised-BatchNorm step issues, in order (dp.py)."""
         return [20] * (self.SYNC_BN_PAIRS_PER_LAYER * self.num_layers)
 
-    def fused_mse_step_syncbn(self, x, y, global_batch, sample_offset, bn_param_grad_scale, allreduce):
-        """See ``FlatModule._syncbn_step`` (4 L all-reduces of 20 cells; ``bn_param_grad_scale`` is 1 on one rank, 0 elsewhere)."""
-        # the launch form is the model's (step_path): after a guard trip retry_on_fp32_chain() must really land on the fp32 phases
-        out = self._syncbn_step("rulgnn_stgcn_train_fwdbwd_syncbn_path_f32", x, y, global_batch, bn_param_grad_scale, allreduce,
-                                int(self.step_path), sample_offset=sample_offset, whole_step=True)
+    def sync_collective_schedule(self):
+        """The collectives of one ``fused_mse_step_syncbn(..., grad_ready=...)`` in the order the step issues them, as data:
+        ``("cells", count)`` for an all-reduce of ``count`` float64 reduction cells, ``("region", offset, count)`` for a reported bucket
+        region (include/rulgnn.h, rulgnn_stgcn_train_fwdbwd_syncbn_ready_f32).  A function of the shape alone, built from
+        ``sync_bn_schedule()`` and ``ready_regions()``: the 2 L forward pairs, the head region, then per layer from the top its two
+        backward pairs and (every layer but the first) its theta region.  Where no region is reported it is the cell schedule.  dp.py
+        lets a rank with an empty shard replay exactly this sequence."""
+        cells = [("cells", int(n)) for n in self.sync_bn_schedule()]
+        regions = [("region", int(o), int(c)) for o, c in self.ready_regions()]
+        if not regions:
+            return cells
+        L = self.num_layers
+        out = cells[:2 * L] + regions[:1]
+        for i in range(L):                         # layer L - 1 - i
+            out += cells[2 * L + 2 * i:2 * L + 2 * i + 2]
+            out += regions[1 + i:2 + i] if i < L - 1 else []
+        return out
+
+    def fused_mse_step_syncbn(self, x, y, global_batch, sample_offset, bn_param_grad_scale, allreduce, grad_ready=None):
+        """See ``FlatModule._syncbn_step`` (4 L all-reduces of 20 cells; ``bn_param_grad_scale`` is 1 on one rank, 0 elsewhere).
+
+        ``grad_ready(offset, count)``: as in ``fused_mse_step`` -- the step also reports final bucket regions while the backward is being
+        enqueued (rulgnn_stgcn_train_fwdbwd_syncbn_ready_f32; both callbacks interleave as ``sync_collective_schedule()`` says)."""
+        if grad_ready is None:
+            # the launch form is the model's (step_path): after a guard trip retry_on_fp32_chain() must really land on the fp32 phases
+            out = self._syncbn_step("rulgnn_stgcn_train_fwdbwd_syncbn_path_f32", x, y, global_batch, bn_param_grad_scale, allreduce,
+                                    int(self.step_path), sample_offset=sample_offset, whole_step=True)
+            self._whole_step_done()
+            return out
+        failure = []
+
+        def hook(_user, _grads, offset, count, _stream):
+            try:
+                grad_ready(int(offset), int(count))
+                return 0
+            except BaseException as e:          # never let an exception cross the C frame
+                failure.append(e)
+                return 1
+        cb = _lib.GRAD_READY_FN(hook)
+        try:
+            out = self._syncbn_step("rulgnn_stgcn_train_fwdbwd_syncbn_ready_f32", x, y, global_batch, bn_param_grad_scale, allreduce,
+                                    cb, None, sample_offset=sample_offset, whole_step=True)
+        except RuntimeError:
+            if failure:                         # (the entry returned RULGNN_ECALLBACK because of it)
+                raise failure[0] from None
+            raise
+        if self._last_chain == _lib.STEP_MX:    # shapes of the phase chains: this entry always runs the fp32 phases
+            self._last_chain = _lib.STEP_CHAIN
         self._whole_step_done()
         return out
 

@@ -178,13 +178,16 @@ int rulgnn_stgcn_train_fwdbwd_f32(const rulgnn_stgcn_shape *shape, const rulgnn_
  * args->grads multiplied by `bn_param_grad_scale` (in [0, 1]): pass 1 on exactly one rank and 0 on the others (or
  * 1/world_size everywhere when no shard is empty), so that a SUM of args->grads over the ranks is the gradient of the
  * global-batch loss for every parameter.  A rank with an empty shard makes no call; it must still take part in the 4L
- * all-reduces (with zeros).  num_patch <= 64 only (RULGNN_EUNSUPPORTED otherwise). */
+ * all-reduces (with zeros).
+ * Shapes of the tiled path (num_patch > 64, and what the LDS gates or num_layers > 3 send there) run the same contract: the pairs are
+ * forward pair 2l behind the first convolution of layer l and 2l + 1 behind the second, l = 0 .. L-1; then, top layer first, backward
+ * pair 2l + 1 and backward pair 2l of layer l = L-1 .. 0.  The loss and the fc2.bias gradient stay this rank's own sums. */
 typedef int (*rulgnn_allreduce_f64_fn)(void *user, double *device_buf, int32_t count, void *stream);
 int rulgnn_stgcn_train_fwdbwd_syncbn_f32(const rulgnn_stgcn_shape *shape, const rulgnn_stgcn_train_args *args,
                                          float bn_param_grad_scale, rulgnn_allreduce_f64_fn allreduce, void *user,
                                          void *stream);
 /* The same with the launch form chosen by the caller (RULGNN_STEP_AUTO / _CHAIN / _MX below; the entry above is RULGNN_STEP_CHAIN).
- * On the matrix-core chain the f16 range guard applies: see RULGNN_STEP_MX. */
+ * On the matrix-core chain the f16 range guard applies: see RULGNN_STEP_MX.  The tiled path has one launch form and ignores `path`. */
 int rulgnn_stgcn_train_fwdbwd_syncbn_path_f32(const rulgnn_stgcn_shape *shape, const rulgnn_stgcn_train_args *args,
                                               float bn_param_grad_scale, rulgnn_allreduce_f64_fn allreduce, void *user,
                                               int32_t path, void *stream);
@@ -202,6 +205,22 @@ int rulgnn_stgcn_train_fwdbwd_syncbn_path_f32(const rulgnn_stgcn_shape *shape, c
 typedef int (*rulgnn_grad_ready_fn)(void *user, float *grads, int64_t offset, int64_t count, void *stream);
 int rulgnn_stgcn_train_fwdbwd_ready_f32(const rulgnn_stgcn_shape *shape, const rulgnn_stgcn_train_args *args,
                                         rulgnn_grad_ready_fn ready, void *user, void *stream);
+
+/* Both at once: the synchronised-BatchNorm step (rulgnn_stgcn_train_fwdbwd_syncbn_f32: same arguments, same `allreduce` contract) that
+ * also reports final gradient regions as rulgnn_stgcn_train_fwdbwd_ready_f32 does (same regions, same order, same stream contract for
+ * `ready(ready_user, ...)`), so that a data-parallel step on the tiled path keeps the overlap of its bucket all-reduce when it
+ * switches synchronised BatchNorm on.  Both callbacks are made from the launching thread; their interleaved order for one step is a
+ * function of (num_patch, num_layers) alone.  On the tiled path, with L = num_layers:
+ *     allreduce x 2L    forward pairs 0 .. 2L-1
+ *     ready             the head region (fc1 | fc2.weight), right behind the fc1 / fc2 gradient products
+ *     for l = L-1 .. 0: allreduce (backward pair 2l + 1), allreduce (backward pair 2l),
+ *                       then, for l > 0, ready (theta weight | bias of layer l) behind that layer's products
+ * i.e. 4L cell callbacks of 20 doubles and L region callbacks.  On shapes that run the phase chains `ready` is never called and the
+ * step is the RULGNN_STEP_CHAIN synchronised step (4L cell callbacks).  `ready` == NULL is RULGNN_EINVAL (as every argument error, in
+ * front of any launch); RULGNN_ECALLBACK when either callback returns non-zero. */
+int rulgnn_stgcn_train_fwdbwd_syncbn_ready_f32(const rulgnn_stgcn_shape *shape, const rulgnn_stgcn_train_args *args,
+                                               float bn_param_grad_scale, rulgnn_allreduce_f64_fn allreduce, void *user,
+                                               rulgnn_grad_ready_fn ready, void *ready_user, void *stream);
 
 /* Single-GPU fast path: rulgnn_stgcn_train_fwdbwd_f32 with the optimizer folded into its last kernel --
  * the whole body of ST_GCN.update (algorithms/algorithms.py:482-489) in one call: the kernel that
