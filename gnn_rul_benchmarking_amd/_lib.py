@@ -144,6 +144,18 @@ class RgcnuArgs(C.Structure):
                 ("seed", C.c_uint64), ("step", C.c_uint64), ("training", C.c_int32)]
 
 
+class GrucmShape(C.Structure):
+    _fields_ = [("batch", C.c_int64), ("num_nodes", C.c_int32), ("time_length", C.c_int32), ("gru_hidden_dim", C.c_int32)]
+
+
+class GrucmArgs(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("dpred", C.c_void_p), ("params", C.c_void_p), ("grads", C.c_void_p),
+                ("pred", C.c_void_p), ("loss", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("global_batch", C.c_int64), ("sample_offset", C.c_int64), ("dropout_p", C.c_float * 3), ("seed", C.c_uint64),
+                ("step", C.c_uint64), ("training", C.c_int32), ("gru_path", C.c_int32)]
+
+
+GRUCM_GRU_AUTO, GRUCM_GRU_STEP_LOOP, GRUCM_GRU_PERSISTENT = 0, 1, 2      # include/rulgnn.h RULGNN_GRUCM_GRU_*
 DTYPE_F32, DTYPE_BF16 = 0, 1      # include/rulgnn.h RULGNN_DTYPE_*
 GEMM_F32, GEMM_BF16X3, GEMM_BF16X3_ONLY = 0, 1, 2      # include/rulgnn.h RULGNN_GEMM_*
 HAGCN_TOPK_SLOTS = 16
@@ -283,6 +295,14 @@ _SIGNATURES = {
     "rulgnn_gru_workspace_bytes": (C.c_size_t, [C.POINTER(GruShape)]),
     "rulgnn_gru_forward_f32": (C.c_int, [C.POINTER(GruShape), C.POINTER(GruArgs), C.c_void_p]),
     "rulgnn_gru_backward_f32": (C.c_int, [C.POINTER(GruShape), C.POINTER(GruArgs), C.c_void_p]),
+    "rulgnn_gru_persistent_workspace_bytes": (C.c_size_t, [C.POINTER(GruShape)]),
+    "rulgnn_gru_persistent_forward_f32": (C.c_int, [C.POINTER(GruShape), C.POINTER(GruArgs), C.c_void_p]),
+    "rulgnn_gru_persistent_backward_f32": (C.c_int, [C.POINTER(GruShape), C.POINTER(GruArgs), C.c_void_p]),
+    "rulgnn_grucm_param_count": (C.c_int64, [C.POINTER(GrucmShape)]),
+    "rulgnn_grucm_workspace_bytes": (C.c_size_t, [C.POINTER(GrucmShape)]),
+    "rulgnn_grucm_forward_f32": (C.c_int, [C.POINTER(GrucmShape), C.POINTER(GrucmArgs), C.c_void_p]),
+    "rulgnn_grucm_backward_f32": (C.c_int, [C.POINTER(GrucmShape), C.POINTER(GrucmArgs), C.c_void_p]),
+    "rulgnn_grucm_fwdbwd_f32": (C.c_int, [C.POINTER(GrucmShape), C.POINTER(GrucmArgs), C.POINTER(AdamArgs), C.c_void_p]),
     "rulgnn_rul_metrics_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "rulgnn_rul_metrics_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rulgnn_rul_metric_sums_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -332,7 +352,7 @@ _SIGNATURES = {
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
 # index -> ctypes mirror, in the order of the RULGNN_STRUCT_* constants of include/rulgnn.h (rulgnn_struct_size)
-STRUCTS = (StgcnShape, StgcnTrainArgs, AdamArgs, StmsgcnShape, StmsgcnArgs, AstgcnnShape, AstgcnnArgs, FcstgnnShape, FcstgnnArgs, RgcnuShape, RgcnuArgs, StnetShape, StnetArgs, SagcnShape, SagcnArgs, StagnnShape, StagnnArgs, HagcnShape, HagcnArgs, BilstmShape, BilstmArgs, StconvShape, StgnnShape, GruShape, GruArgs)
+STRUCTS = (StgcnShape, StgcnTrainArgs, AdamArgs, StmsgcnShape, StmsgcnArgs, AstgcnnShape, AstgcnnArgs, FcstgnnShape, FcstgnnArgs, RgcnuShape, RgcnuArgs, StnetShape, StnetArgs, SagcnShape, SagcnArgs, StagnnShape, StagnnArgs, HagcnShape, HagcnArgs, BilstmShape, BilstmArgs, StconvShape, StgnnShape, GruShape, GruArgs, GrucmShape, GrucmArgs)
 
 _lib = None
 

@@ -2,8 +2,8 @@
 algorithms/algorithms.py:29-48 does it (lookup by name in this module's globals,
 ``NotImplementedError("Algorithm not found: ...")`` otherwise).
 
-The ST_GCN (reference algorithms/algorithms.py:465-490), STMSGCN (:546-571), ASTGCNN (:139-163), FC_STGNN (:51-76), HAGCN (:222-248)
-and ST_Conv (:195-220) wrappers are implemented:
+The ST_GCN (reference algorithms/algorithms.py:465-490), STMSGCN (:546-571), ASTGCNN (:139-163), FC_STGNN (:51-76), HAGCN (:222-248),
+ST_Conv (:195-220) and GRU_CM (:355-380) wrappers are implemented:
 the hot paths this package accelerates.  The classes keep the reference contract -- constructor
 ``(configs, hparams, device)``, attributes ``model`` / ``optimizer`` / ``hparams`` / ``mse``,
 ``update(X, y, epoch) -> {'loss': float}`` -- so the reference's trainer can drive it unchanged."""
@@ -18,6 +18,7 @@ from . import _lib
 from .optim import FusedAdam
 from .astgcnn import ASTGCNN_model
 from .fcstgnn import FC_STGNN_RUL
+from .grucm import GRU_CM_model
 from .hagcn import HAGCN_model, deferred_weight_gradients
 from .rgcnu import RGCNU_model
 from .stconv import ST_Conv_model
@@ -280,4 +281,12 @@ class STAGNN(_FusedAlgorithm):
     needs_train_mode = "BatchNorm batch statistics"
 
 
-_NOT_ALGORITHMS = {"Algorithm", "FusedAdam", "RGCNU_model", "STNet_model", "SAGCN_model", "STAGNN_model", "ST_GCN_model", "STMSGCN_model", "ASTGCNN_model", "FC_STGNN_RUL", "HAGCN_model", "ST_Conv_model", "STGNN_model", "get_algorithm_class", "torch", "nn", "annotations", "math", "_lib", "deferred_weight_gradients"}
+class GRU_CM(_FusedAlgorithm):
+    """GRU_CM training wrapper (reference algorithms.py:355-380; graph stage and head of csrc/grucm.hip, the persistent GRU of
+    csrc/gru_seq.hip).  No BatchNorm: samples are independent and data parallelism is the plain ``[gradient | loss]`` bucket."""
+    model_class = GRU_CM_model
+    supports_graphs = False
+    needs_train_mode = "dropout"
+
+
+_NOT_ALGORITHMS = {"Algorithm", "GRU_CM_model", "FusedAdam", "RGCNU_model", "STNet_model", "SAGCN_model", "STAGNN_model", "ST_GCN_model", "STMSGCN_model", "ASTGCNN_model", "FC_STGNN_RUL", "HAGCN_model", "ST_Conv_model", "STGNN_model", "get_algorithm_class", "torch", "nn", "annotations", "math", "_lib", "deferred_weight_gradients"}

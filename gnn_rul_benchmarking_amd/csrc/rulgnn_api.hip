@@ -262,6 +262,8 @@ size_t rulgnn_struct_size(int32_t which) {
     case RULGNN_STRUCT_STGNN_SHAPE: return sizeof(rulgnn_stgnn_shape);
     case RULGNN_STRUCT_GRU_SHAPE: return sizeof(rulgnn_gru_shape);
     case RULGNN_STRUCT_GRU_ARGS: return sizeof(rulgnn_gru_args);
+    case RULGNN_STRUCT_GRUCM_SHAPE: return sizeof(rulgnn_grucm_shape);
+    case RULGNN_STRUCT_GRUCM_ARGS: return sizeof(rulgnn_grucm_args);
     default: return 0;
     }
 }
@@ -1078,6 +1080,85 @@ int rulgnn_gru_backward_f32(const rulgnn_gru_shape* shape, const rulgnn_gru_args
         if (rc != RULGNN_OK) return rc;
     }
     return gru_backward(shape, args, static_cast<hipStream_t>(stream));
+}
+
+size_t rulgnn_gru_persistent_workspace_bytes(const rulgnn_gru_shape* shape) { return gru_persistent_workspace_bytes(shape); }
+
+int rulgnn_gru_persistent_forward_f32(const rulgnn_gru_shape* shape, const rulgnn_gru_args* args, void* stream) {
+    if (!shape || !args) return RULGNN_EINVAL;
+    int rc = check_ptrs({args->w_ih, args->w_hh, args->b_ih, args->b_hh, args->workspace});
+    if (rc != RULGNN_OK) return rc;
+    if (shape->num_seq > 0) {
+        rc = check_ptrs({args->x, args->out});
+        if (rc != RULGNN_OK) return rc;
+    }
+    return gru_persistent_forward(shape, args, static_cast<hipStream_t>(stream));
+}
+
+int rulgnn_gru_persistent_backward_f32(const rulgnn_gru_shape* shape, const rulgnn_gru_args* args, void* stream) {
+    if (!shape || !args) return RULGNN_EINVAL;
+    int rc = check_ptrs({args->w_ih, args->w_hh, args->b_ih, args->b_hh, args->workspace, args->dw_ih, args->dw_hh, args->db_ih,
+                         args->db_hh});
+    if (rc != RULGNN_OK) return rc;
+    if (shape->num_seq > 0) {
+        rc = check_ptrs({args->x, args->dout});
+        if (rc != RULGNN_OK) return rc;
+    }
+    if (args->dx && (reinterpret_cast<uintptr_t>(args->dx) & 3)) return RULGNN_EALIGN;
+    return gru_persistent_backward(shape, args, static_cast<hipStream_t>(stream));
+}
+
+// ---- GRU_CM ---------------------------------------------------------------------------------------------------------------------
+int64_t rulgnn_grucm_param_count(const rulgnn_grucm_shape* shape) { return grucm_param_count(shape); }
+size_t rulgnn_grucm_workspace_bytes(const rulgnn_grucm_shape* shape) { return grucm_workspace_bytes(shape); }
+
+static int check_grucm(const rulgnn_grucm_shape* shape, const rulgnn_grucm_args* a, bool bwd) {
+    if (!shape || !a) return RULGNN_EINVAL;
+    if (grucm_param_count(shape) < 0 || grucm_workspace_bytes(shape) == 0)
+        return shape->batch >= 0 && shape->num_nodes >= 2 && shape->time_length >= 1 && shape->gru_hidden_dim >= 1 ? RULGNN_EUNSUPPORTED
+                                                                                                                 : RULGNN_EINVAL;
+    if (a->global_batch < shape->batch || a->sample_offset < 0) return RULGNN_EINVAL;
+    for (int site = 0; site < 3; ++site)
+        if (!(a->dropout_p[site] >= 0.f && a->dropout_p[site] < 1.f)) return RULGNN_EINVAL;
+    if (a->gru_path != RULGNN_GRUCM_GRU_AUTO && a->gru_path != RULGNN_GRUCM_GRU_STEP_LOOP && a->gru_path != RULGNN_GRUCM_GRU_PERSISTENT)
+        return RULGNN_EINVAL;
+    int rc = check_ptrs({a->params, a->workspace});
+    if (rc != RULGNN_OK) return rc;
+    if (shape->batch > 0) {
+        rc = check_ptrs({a->x, a->pred});
+        if (rc != RULGNN_OK) return rc;
+    }
+    for (const void* p : {(const void*)a->y, (const void*)a->dpred, (const void*)a->loss})
+        if (p && (reinterpret_cast<uintptr_t>(p) & 3)) return RULGNN_EALIGN;
+    if (bwd) {
+        rc = check_ptrs({a->grads});
+        if (rc != RULGNN_OK) return rc;
+        if (!a->dpred && !a->y && shape->batch > 0) return RULGNN_EINVAL;
+    }
+    return RULGNN_OK;
+}
+
+int rulgnn_grucm_forward_f32(const rulgnn_grucm_shape* shape, const rulgnn_grucm_args* args, void* stream) {
+    const int rc = check_grucm(shape, args, false);
+    if (rc != RULGNN_OK) return rc;
+    return grucm_run(shape, args, 1, static_cast<hipStream_t>(stream));
+}
+
+int rulgnn_grucm_backward_f32(const rulgnn_grucm_shape* shape, const rulgnn_grucm_args* args, void* stream) {
+    const int rc = check_grucm(shape, args, true);
+    if (rc != RULGNN_OK) return rc;
+    return grucm_run(shape, args, 2, static_cast<hipStream_t>(stream));
+}
+
+int rulgnn_grucm_fwdbwd_f32(const rulgnn_grucm_shape* shape, const rulgnn_grucm_args* args, const rulgnn_adam_args* opt, void* stream) {
+    int rc = check_grucm(shape, args, true);
+    if (rc != RULGNN_OK) return rc;
+    if (args->dpred || (!args->y && shape->batch > 0)) return RULGNN_EINVAL;
+    if (opt && (rc = check_adam(opt, args->params)) != RULGNN_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    rc = grucm_run(shape, args, 3, st);
+    if (rc != RULGNN_OK || !opt) return rc;
+    return adam_tail(opt, args->grads, 0, grucm_param_count(shape), st);
 }
 
 size_t rulgnn_rul_metrics_workspace_bytes(int64_t n) { return rul_metrics_workspace_bytes(n); }

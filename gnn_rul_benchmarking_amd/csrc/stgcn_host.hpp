@@ -237,6 +237,13 @@ int stgnn_run(const rulgnn_stgnn_shape* s, const rulgnn_stmsgcn_args* a, int mod
 size_t gru_workspace_bytes(const rulgnn_gru_shape* s);
 int gru_forward(const rulgnn_gru_shape* s, const rulgnn_gru_args* a, hipStream_t st);
 int gru_backward(const rulgnn_gru_shape* s, const rulgnn_gru_args* a, hipStream_t st);
+// the same layer as one launch over all steps (gru_seq.hip); 0 / RULGNN_EUNSUPPORTED outside hidden_dim == 64, input_dim <= 64, seq_len <= 1024
+size_t gru_persistent_workspace_bytes(const rulgnn_gru_shape* s);
+int gru_persistent_forward(const rulgnn_gru_shape* s, const rulgnn_gru_args* a, hipStream_t st);
+int gru_persistent_backward(const rulgnn_gru_shape* s, const rulgnn_gru_args* a, hipStream_t st);
+int64_t grucm_param_count(const rulgnn_grucm_shape* s);
+size_t grucm_workspace_bytes(const rulgnn_grucm_shape* s);
+int grucm_run(const rulgnn_grucm_shape* s, const rulgnn_grucm_args* a, int mode, hipStream_t st);
 size_t rul_metrics_workspace_bytes(int64_t n);
 int rul_metrics(const float* pred, const float* real, int64_t n, float max_rul, double* out, void* workspace, size_t workspace_bytes,
                 hipStream_t st, int raw = 0);

@@ -1,7 +1,7 @@
 """Hyper-parameter tables, looked up by dataset name then dataset id, like the reference's
 configs/hparams.py:3-7 (``get_hparams_class(name)(dataset_id)`` -> object with ``train_params`` and
 ``alg_hparams`` dicts keyed by ``--GNN_method``; unknown dataset -> NotImplementedError, unknown id ->
-ValueError).  Only the ST_GCN, STMSGCN, ASTGCNN, FC_STGNN, HAGCN, ST_Conv, STGNN, RGCNU, STNet, SAGCN and STAGNN rows are restated (the methods this package
+ValueError).  Only the ST_GCN, STMSGCN, ASTGCNN, FC_STGNN, HAGCN, ST_Conv, STGNN, RGCNU, GRU_CM, STNet, SAGCN and STAGNN rows are restated (the methods this package
 implements).
 
 PHM2012 / XJTU_SY rows are the reference's (configs/hparams.py:223,238,... and :334,349,...; STMSGCN
@@ -82,6 +82,9 @@ class _Table:
                                           'output_dim': 10, 'num_heads': 3, 'threshold': 0}
             self.train_params['FC_STGNN'] = dict(_FC_STGNN_TRAIN)
             self.alg_hparams['FC_STGNN'] = dict(_FC_STGNN_ROWS[dataset_id])
+            # configs/hparams.py:26,46,64,87,104,127,144,167 (C-MAPSS FD001-4) and :190,210 (N-CMAPSS): one row everywhere
+            self.train_params['GRU_CM'] = dict(_ASTGCNN_TRAIN)
+            self.alg_hparams['GRU_CM'] = {'num_nodes': self._astgcnn_nodes, 'time_length': 50, 'gru_hidden_dim': 64}
         if dataset_id in self._stnet_rows:
             self.train_params['STNet'] = {'num_epochs': 81, 'batch_size': 100, 'weight_decay': 1e-2, 'learning_rate': 1e-2}
             num_patch, patch_size, num_nodes, nperseg, input_dim = self._stnet_rows[dataset_id]

@@ -330,6 +330,8 @@ size_t rulgnn_stgcn_train_args_size(void);
 #define RULGNN_STRUCT_STGNN_SHAPE 22
 #define RULGNN_STRUCT_GRU_SHAPE 23
 #define RULGNN_STRUCT_GRU_ARGS 24
+#define RULGNN_STRUCT_GRUCM_SHAPE 25
+#define RULGNN_STRUCT_GRUCM_ARGS 26
 size_t rulgnn_struct_size(int32_t which);
 
 /* Profiling aid: the training step is a chain of 4*num_layers+1 phase kernels:
@@ -1089,6 +1091,71 @@ typedef struct rulgnn_gru_args {
 size_t rulgnn_gru_workspace_bytes(const rulgnn_gru_shape *shape);           /* 0: invalid / unsupported */
 int rulgnn_gru_forward_f32(const rulgnn_gru_shape *shape, const rulgnn_gru_args *args, void *stream);
 int rulgnn_gru_backward_f32(const rulgnn_gru_shape *shape, const rulgnn_gru_args *args, void *stream);
+
+/* The same layer for a few hundred medium-length sequences (GRU_CM: 100 .. 4096 sequences of 50 steps, hidden 64), on the same shape and
+ * argument structs: ONE launch walks all steps -- a workgroup owns a tile of 16 sequences, W_hh stays in registers, h_{t-1} W_hh^T (and,
+ * backward, d gh_t W_hh) runs on the fp32 matrix cores, no cross-workgroup synchronisation (csrc/gru_seq.hip); the input projection is one
+ * GEMM in front, the four weight-gradient products one batched split-K pair behind.  fp32-class results (the summation order differs from
+ * rulgnn_gru_*, which stay what they were).  Covers hidden_dim == 64, input_dim <= 64, seq_len <= 1024: the workspace query returns 0
+ * beyond, and forward / backward RULGNN_EUNSUPPORTED before any launch.  The workspace (its own layout and size) carries the tape. */
+size_t rulgnn_gru_persistent_workspace_bytes(const rulgnn_gru_shape *shape);
+int rulgnn_gru_persistent_forward_f32(const rulgnn_gru_shape *shape, const rulgnn_gru_args *args, void *stream);
+int rulgnn_gru_persistent_backward_f32(const rulgnn_gru_shape *shape, const rulgnn_gru_args *args, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * GRU_CM path (reference models/GRU_CM/Model.py:6-82, algorithms/algorithms.py:355-380; wired to C-MAPSS FD001-4 and N-CMAPSS,
+ * configs/hparams.py:46,87,127,167,210).
+ *
+ * x [batch, num_nodes, time_length], h = num_nodes / 2, H = gru_hidden_dim.  Per (sample, time step) a graph of the sensors:
+ * Linear(1, h), Dropout -> edge MLP over ALL ordered node pairs (j = i included) summed per node, S_i = sum_j relu(W_e [x_i ; x_j] + b_e)
+ * -> node MLP relu(W_n [x_i ; S_i] + b_n), Dropout -> max over the nodes -> nn.GRU(h, H) over the time steps, Dropout -> Linear(H L, 1).
+ * The pair tensors of the reference are never formed (W_e [x_i ; x_j] = P_i + Q_j); the backward recomputes the ReLU signs and the
+ * arg max (first index on ties) from x and the parameters; every parameter gradient is reduced in a fixed order.
+ *
+ * Flat parameter buffer in the reference's state_dict order:
+ *   input_linear.{weight[h][1], bias[h]} | gnn.edge_mlp.0.{weight[h][2h], bias[h]} | gnn.node_mlp.0.{weight[h][2h], bias[h]} |
+ *   gru.{weight_ih_l0[3H][h], weight_hh_l0[3H][H], bias_ih_l0[3H], bias_hh_l0[3H]} | output_linear.{weight[H L], bias[1]}
+ * Dropout: the counter hash of the other families, key = f(seed, step, site), site 0 / 1 / 2 = the three nn.Dropout in model order;
+ * counters (((b + sample_offset) L + t) N + i) h + c (sites 0, 1) and ((b + sample_offset) L + t) H + c (site 2), mod 2^32.
+ * Limits: 2 <= num_nodes <= 32, time_length <= 1024, gru_hidden_dim <= 1024, H L <= 65536 (RULGNN_EUNSUPPORTED beyond: the workspace
+ * query returns 0).  The recurrence runs on rulgnn_gru_persistent_* where that covers the shape (H == 64) and on rulgnn_gru_* elsewhere;
+ * the workspace holds the larger of the two needs.
+ */
+#define RULGNN_GRUCM_GRU_AUTO 0          /* persistent recurrence where it applies, else the step loop */
+#define RULGNN_GRUCM_GRU_STEP_LOOP 1     /* debugging / measurement: the step-loop recurrence (rulgnn_gru_*) */
+#define RULGNN_GRUCM_GRU_PERSISTENT 2    /* the persistent recurrence; RULGNN_EUNSUPPORTED where it does not apply */
+
+typedef struct rulgnn_grucm_shape {
+    int64_t batch;
+    int32_t num_nodes, time_length, gru_hidden_dim;
+} rulgnn_grucm_shape;
+
+typedef struct rulgnn_grucm_args {
+    const float *x;           /* [batch, num_nodes * time_length] */
+    const float *y;           /* [batch] targets, or NULL */
+    const float *dpred;       /* [batch] d loss / d pred (autograd backward); NULL = MSE against y */
+    const float *params;
+    float *grads;             /* same layout as params */
+    float *pred;              /* [batch] */
+    float *loss;              /* [1] sum over the shard of (pred - y)^2 / global_batch; may be NULL */
+    void *workspace;
+    size_t workspace_bytes;
+    int64_t global_batch;
+    int64_t sample_offset;    /* index of this shard's first sample in the global batch (dropout stream) */
+    float dropout_p[3];       /* the three nn.Dropout rates (0.2 in the reference); applied when training != 0 */
+    uint64_t seed, step;      /* dropout stream: mask = f(seed, step, site, element index) */
+    int32_t training;
+    int32_t gru_path;         /* RULGNN_GRUCM_GRU_*; a backward takes its forward's value */
+} rulgnn_grucm_args;
+
+int64_t rulgnn_grucm_param_count(const rulgnn_grucm_shape *shape);         /* < 0: invalid / unsupported */
+size_t rulgnn_grucm_workspace_bytes(const rulgnn_grucm_shape *shape);      /* 0: invalid / unsupported */
+/* model(x): GRU_CM_model.forward (Model.py:59-82). */
+int rulgnn_grucm_forward_f32(const rulgnn_grucm_shape *shape, const rulgnn_grucm_args *args, void *stream);
+/* loss.backward() (algorithms.py:378) after a forward with the same args / workspace. */
+int rulgnn_grucm_backward_f32(const rulgnn_grucm_shape *shape, const rulgnn_grucm_args *args, void *stream);
+/* GRU_CM.update body (algorithms.py:371-380); with `opt` also Adam on the flat parameter buffer. */
+int rulgnn_grucm_fwdbwd_f32(const rulgnn_grucm_shape *shape, const rulgnn_grucm_args *args, const rulgnn_adam_args *opt, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * RUL test metrics on the device.

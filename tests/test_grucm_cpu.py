@@ -1,0 +1,176 @@
+"""CPU-side checks of the GRU_CM family: registry, module attributes, parameter layout, hparams rows (against the reference's, recorded
+by tests/golden/make_golden_grucm.py) and the host-only parts of its C entries (no kernels are launched here)."""
+import ctypes as C
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from gnn_rul_benchmarking_amd import _lib
+
+from conftest import GOLDEN
+
+import grucm_oracle as O
+
+
+def _algo(ds="CMAPSS", did="FD004"):
+    from gnn_rul_benchmarking_amd.algorithms import get_algorithm_class
+    from gnn_rul_benchmarking_amd.hparams import get_hparams_class
+    h = get_hparams_class(ds)(did)
+    return get_algorithm_class("GRU_CM")(h.alg_hparams["GRU_CM"], h.train_params["GRU_CM"], "cpu"), h
+
+
+def test_registry_serves_the_algorithm_and_refuses_the_model():
+    from gnn_rul_benchmarking_amd import algorithms as A
+    assert A.get_algorithm_class("GRU_CM") is A.GRU_CM
+    with pytest.raises(NotImplementedError, match="Algorithm not found: GRU_CM_model"):
+        A.get_algorithm_class("GRU_CM_model")
+    assert A.GRU_CM.needs_train_mode == "dropout" and A.GRU_CM.supports_graphs is False
+
+
+def test_algorithm_attributes_and_state_dict_keys():
+    from gnn_rul_benchmarking_amd.grucm import GRU_CM_model
+    from gnn_rul_benchmarking_amd.optim import FusedAdam
+    algo, h = _algo()
+    assert isinstance(algo.model, GRU_CM_model) and isinstance(algo.optimizer, FusedAdam)
+    assert algo.hparams == h.train_params["GRU_CM"] and isinstance(algo.mse, torch.nn.MSELoss)
+    assert list(algo.model.state_dict().keys()) == O.param_names()
+    assert algo.model.c_family == "grucm" and algo.model.dropout_by_sample_offset is True
+    assert [algo.model.dropout1.p, algo.model.dropout2.p, algo.model.dropout3.p] == [0.2, 0.2, 0.2]
+    assert GRU_CM_model(50, 14).gru_hidden_dim == 128                      # the reference's constructor default
+
+
+@pytest.mark.parametrize("name", ["grucm_cmapss_14x50_bs8", "grucm_ncmapss_20x50_bs5", "grucm_odd_9x21_bs6"])
+def test_a_seed_gives_the_reference_initial_weights(name):
+    from gnn_rul_benchmarking_amd.grucm import GRU_CM_model
+    z = np.load(os.path.join(GOLDEN, name + ".npz"))
+    cfg = {k[4:]: int(z[k]) for k in z.files if k.startswith("cfg:")}
+    torch.manual_seed(int(z["seed"]))
+    m = GRU_CM_model(**cfg)
+    sd = m.state_dict()
+    assert list(sd.keys()) == [k[3:] for k in z.files if k.startswith("sd:")] == O.param_names()
+    for k, v in sd.items():
+        assert v.shape == z["sd:" + k].shape and np.array_equal(v.numpy(), z["sd:" + k]), k
+    assert np.array_equal(m.flat_params.numpy(), O.flatten({k: z["sd:" + k] for k in O.param_names()}))
+
+
+def test_param_layout_counts():
+    from gnn_rul_benchmarking_amd.grucm import GRU_CM_model, param_layout
+    lib = _lib.load()
+    for (N, L, H), count in (((14, 50, 64), 17441), ((20, 50, 64), 18233)):
+        layout, n = param_layout(N, L, H)
+        assert n == count and list(layout) == O.param_names()
+        assert GRU_CM_model(L, N, H).num_live == count
+        assert lib.rulgnn_grucm_param_count(C.byref(_lib.GrucmShape(8, N, L, H))) == count
+
+
+def test_hparams_rows_equal_the_reference():
+    from gnn_rul_benchmarking_amd.hparams import get_hparams_class
+    rows = json.loads(str(np.load(os.path.join(GOLDEN, "grucm_hparams_rows.npz"))["rows_json"]))
+    assert sorted(rows) == ["CMAPSS/FD001", "CMAPSS/FD002", "CMAPSS/FD003", "CMAPSS/FD004", "NCMAPSS/None"]
+    for key, ref in rows.items():
+        ds, did = key.split("/")
+        h = get_hparams_class(ds)(None if did == "None" else did)
+        assert h.train_params["GRU_CM"] == ref["train_params"] and h.alg_hparams["GRU_CM"] == ref["alg_hparams"], key
+
+
+def test_workspace_queries_decide_the_supported_range():
+    lib = _lib.load()
+    ws = lambda *s: lib.rulgnn_grucm_workspace_bytes(C.byref(_lib.GrucmShape(*s)))      # noqa: E731
+    assert ws(100, 14, 50, 64) > 0 and ws(100, 20, 50, 64) > 0 and ws(7, 9, 21, 64) > 0 and ws(7, 2, 1, 8) > 0 and ws(7, 32, 50, 64) > 0
+    assert ws(100, 33, 50, 64) == 0 and ws(100, 1, 50, 64) == 0 and ws(100, 14, 2000, 64) == 0 and ws(100, 14, 50, 2048) == 0
+    assert ws(-1, 14, 50, 64) == 0 and lib.rulgnn_grucm_workspace_bytes(None) == 0
+    # the step-loop recurrence serves what the persistent one does not, and the query holds the larger need
+    g = lambda *s: lib.rulgnn_gru_workspace_bytes(C.byref(_lib.GruShape(*s)))           # noqa: E731
+    gp = lambda *s: lib.rulgnn_gru_persistent_workspace_bytes(C.byref(_lib.GruShape(*s)))   # noqa: E731
+    assert ws(100, 14, 50, 32) > g(100, 50, 7, 32) > 0 and gp(100, 50, 7, 32) == 0
+    assert ws(100, 14, 50, 64) > max(g(100, 50, 7, 64), gp(100, 50, 7, 64))
+    assert gp(100, 50, 7, 64) > 0 and gp(256, 50, 10, 64) > 0 and gp(1, 1, 7, 64) > 0 and gp(0, 50, 7, 64) > 0
+    assert gp(100, 50, 7, 128) == 0 and gp(100, 50, 65, 64) == 0 and gp(100, 2000, 7, 64) == 0 and gp(100, 0, 7, 64) == 0
+    assert lib.rulgnn_gru_persistent_workspace_bytes(None) == 0
+
+
+def _args(B=4, base=1 << 20):
+    a = _lib.GrucmArgs()
+    for i, (name, ctype) in enumerate(a._fields_):
+        if ctype is C.c_void_p and name != "dpred":
+            setattr(a, name, base + 256 * i)
+    a.workspace_bytes, a.global_batch, a.training = 1 << 40, B, 1
+    return a
+
+
+def test_null_pointer_empty_batch_and_range_codes():
+    lib = _lib.load()
+    shp, beyond, empty = _lib.GrucmShape(4, 14, 50, 64), _lib.GrucmShape(4, 40, 50, 64), _lib.GrucmShape(0, 14, 50, 64)
+    a = _lib.GrucmArgs()
+    a.global_batch = 4
+    for entry in (lib.rulgnn_grucm_forward_f32, lib.rulgnn_grucm_backward_f32):
+        assert entry(None, C.byref(a), None) == _lib.EINVAL and entry(C.byref(shp), None, None) == _lib.EINVAL
+        assert entry(C.byref(shp), C.byref(a), None) == _lib.EINVAL                     # null pointers
+        assert entry(C.byref(beyond), C.byref(_args()), None) == _lib.EUNSUPPORTED      # before any launch
+        assert entry(C.byref(_lib.GrucmShape(4, 14, 0, 64)), C.byref(_args()), None) == _lib.EINVAL
+    assert lib.rulgnn_grucm_fwdbwd_f32(C.byref(beyond), C.byref(_args()), None, None) == _lib.EUNSUPPORTED
+    bad = _args()
+    bad.dropout_p[1] = 1.0
+    assert lib.rulgnn_grucm_forward_f32(C.byref(shp), C.byref(bad), None) == _lib.EINVAL
+    bad = _args()
+    bad.gru_path = 7
+    assert lib.rulgnn_grucm_forward_f32(C.byref(shp), C.byref(bad), None) == _lib.EINVAL
+    bad = _args()
+    bad.pred += 2
+    assert lib.rulgnn_grucm_forward_f32(C.byref(shp), C.byref(bad), None) == _lib.EALIGN
+    small = _args()
+    small.workspace_bytes = 16
+    assert lib.rulgnn_grucm_forward_f32(C.byref(shp), C.byref(small), None) == _lib.EWORKSPACE
+    # an empty batch needs neither x nor pred (a null workspace is still an argument error)
+    e = _lib.GrucmArgs()
+    assert lib.rulgnn_grucm_forward_f32(C.byref(empty), C.byref(e), None) == _lib.EINVAL
+    g = _lib.GruArgs()
+    for entry in (lib.rulgnn_gru_persistent_forward_f32, lib.rulgnn_gru_persistent_backward_f32):
+        assert entry(None, C.byref(g), None) == _lib.EINVAL
+        assert entry(C.byref(_lib.GruShape(4, 50, 7, 64)), C.byref(g), None) == _lib.EINVAL
+    full = _lib.GruArgs(*([1 << 20] * 13), 1 << 40)
+    assert lib.rulgnn_gru_persistent_forward_f32(C.byref(_lib.GruShape(4, 50, 7, 32)), C.byref(full), None) == _lib.EUNSUPPORTED
+    assert lib.rulgnn_gru_persistent_backward_f32(C.byref(_lib.GruShape(4, 50, 7, 32)), C.byref(full), None) == _lib.EUNSUPPORTED
+
+
+@pytest.mark.skipif(torch.cuda.is_available(),
+                    reason="placeholder device pointers: a case that got through would launch kernels on them")
+@pytest.mark.parametrize("ds,did", [("CMAPSS", "FD004"), ("NCMAPSS", None)])
+def test_fwdbwd_rejects_bad_adam_arguments_before_any_launch(ds, did):
+    """rulgnn_grucm_fwdbwd_f32 validates its rulgnn_adam_args like every other family (tests/test_abi_cpu.py), in the same order, before
+    any launch: the step (or a device step state) and ``opt->params == args->params`` first, then null / misaligned optimizer pointers."""
+    algo, _ = _algo(ds, did)
+    lib = _lib.load()
+    entry = lib.rulgnn_grucm_fwdbwd_f32
+    B, base = 4, 1 << 20
+    shp = algo.model._shape(B)
+    a = _args(B, base)
+
+    def code(**opt):
+        o = _lib.AdamArgs(a.params, base + 65536, base + 131072, None, 1, 1e-3, 0.9, 0.999, 1e-8, 0.0, 0.1, None)
+        for k, v in opt.items():
+            setattr(o, k, v)
+        return entry(C.byref(shp), C.byref(a), C.byref(o), None)
+
+    EINVAL, EALIGN = _lib.EINVAL, _lib.EALIGN
+    assert code(step=0) == EINVAL                                        # no step and no device step state
+    assert code(params=a.params + 4) == EINVAL                           # an optimizer over other parameters
+    assert code(params=None) == EINVAL
+    assert code(exp_avg=None) == EINVAL
+    assert code(exp_avg_sq=None) == EINVAL
+    assert code(exp_avg=base + 65538) == EALIGN
+    assert code(exp_avg_sq=base + 131074) == EALIGN
+    assert code(step=0, step_state=base + 196608, exp_avg=base + 65538) == EALIGN     # a device step state stands in for the step
+    assert code(step=0, exp_avg=base + 65538) == EINVAL                  # the step check fires before the pointer checks
+    assert code(params=a.params + 4, exp_avg=None) == EINVAL
+
+
+def test_cpu_tensor_raises_hip_path_only():
+    algo, _ = _algo()
+    with pytest.raises(RuntimeError, match="HIP path only"):
+        algo.model(torch.zeros(2, 14, 50))
+    with pytest.raises(RuntimeError, match=r"expects \[bs, 14, 50\]"):
+        algo.model(torch.zeros(2, 50, 14))
