@@ -2314,9 +2314,7 @@ int fcstgnn_run(const rulgnn_fcstgnn_shape* s, const rulgnn_fcstgnn_args* a, int
             } else {
             for (int b = 0; b < 2; ++b) {
                 const size_t lds_b = sizeof(float) * (3 * g.Q * (g.D2 + 1) + 3 * g.Q * (g.Q + 1));
-                if (lds_b > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(fc_graph_bwd_kernel),
-                                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_b) != hipSuccess)
-                    return RULGNN_EHIP;
+                if (const int rcl = allow_dynamic_lds(fc_graph_bwd_kernel, lds_b); rcl != RULGNN_OK) return rcl;
             hipLaunchKernelGGL(fc_graph_bwd_kernel, dim3((unsigned)(g.G[b] < 8192 ? g.G[b] : 8192)), dim3(FC_GRAPH_BWD_THREADS), sizeof(float) * (3 * g.Q * (g.D2 + 1) + 3 * g.Q * (g.Q + 1)), st, g, b, prm,
                                (const Cells*)cells, (const float*)P_(w.F), (const float*)P_(w.Mm[b]), (const float*)P_(w.P[b]),
                                P_(w.dAX[b]), P_(w.dMb[b]));

@@ -512,12 +512,7 @@ __global__ void hg_fill_one_kernel(float* p) { p[0] = 1.f; }
 
 template <typename K>
 int hg_grid(K kernel, int64_t items, size_t lds) {
-    int dev = 0, cus = 256, per_cu = 0;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-    }
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, HB, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+    auto [cus, per_cu] = residency(kernel, HB, lds);
     int64_t want = (int64_t)cus * per_cu;
     if (want > items) want = items;
     return want < 1 ? 1 : (int)want;
@@ -548,9 +543,7 @@ int hagcn_graph_forward(const rulgnn_hagcn_shape* s, const rulgnn_hagcn_args* a,
     if (a->workspace_bytes < (size_t)g.total_floats * sizeof(float)) return RULGNN_EWORKSPACE;
     float* ws = static_cast<float*>(a->workspace);
     (void)hipGetLastError();
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(hg_forward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)HG_FWD_LDS) != hipSuccess)
-        return RULGNN_EHIP;
+    HG_RC(allow_dynamic_lds(hg_forward_kernel, HG_FWD_LDS));
     hipLaunchKernelGGL(hg_forward_kernel, dim3(hg_grid(hg_forward_kernel, g.G, HG_FWD_LDS)), dim3(HB), HG_FWD_LDS, st, g, a->nodes,
                        a->params, ws, a->feats, a->topk, a->forced_topk);
     hipLaunchKernelGGL(hg_kl_kernel, dim3(1), dim3(1024), 0, st, (const float*)(ws + g.t_kl), g.G * NLV, 1.0f / (float)g.G, a->kl);
@@ -563,9 +556,7 @@ int hagcn_graph_backward(const rulgnn_hagcn_shape* s, const rulgnn_hagcn_args* a
     if (a->workspace_bytes < (size_t)g.total_floats * sizeof(float)) return RULGNN_EWORKSPACE;
     float* ws = static_cast<float*>(a->workspace);
     (void)hipGetLastError();
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(hg_backward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)HG_BWD_LDS) != hipSuccess)
-        return RULGNN_EHIP;
+    HG_RC(allow_dynamic_lds(hg_backward_kernel, HG_BWD_LDS));
     hipLaunchKernelGGL(hg_backward_kernel, dim3(hg_grid(hg_backward_kernel, g.G, HG_BWD_LDS)), dim3(HB), HG_BWD_LDS, st, g, a->params, ws,
                        a->dfeats, a->dkl, a->dnodes);
     float* one = ws + g.t_one;

@@ -1124,24 +1124,18 @@ int rgcnu_run(const rulgnn_rgcnu_shape* s, const rulgnn_rgcnu_args* a, int mode,
         hipLaunchKernelGGL(rg_adj_kernel, dim3(blocks), dim3(RB), 0, st, g, a->x, prm, ws);
         if (scl_mx) {
             const size_t lm = rg_scl_mx_lds(scl_nt, false);
-            auto go = [&](auto kernel) {
-                static bool raised = false;                          // once per instantiation and process
-                if (lm > 48 * 1024 && !raised) {
-                    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lm);
-                    raised = true;
-                }
+            auto go = [&](auto kernel) -> int {
+                RG_RC(allow_dynamic_lds(kernel, lm));
                 hipLaunchKernelGGL(kernel, dim3((unsigned)gblocks), dim3(64 * RG_MXW), lm, st, g, a->x, prm, ws, key, thr, scale, a->sample_offset);
+                return RULGNN_OK;
             };
-            if (scl_nt == 1) go(rg_scl_mx_kernel<1>); else go(rg_scl_mx_kernel<2>);
+            RG_RC(scl_nt == 1 ? go(rg_scl_mx_kernel<1>) : go(rg_scl_mx_kernel<2>));
         } else
         hipLaunchKernelGGL(rg_scl_kernel, dim3((unsigned)gblocks), dim3(RB), lds_scl, st, g, a->x, prm, ws, key, thr, scale, a->sample_offset);
         if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
         RG_RC(bilstm_forward(&ls, &la, st, 1));
         const size_t lds = rg_fusion_lds(g, false);
-        if (lds > 160 * 1024) return RULGNN_EUNSUPPORTED;
-        if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(rg_fusion_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   (int)lds) != hipSuccess)
-            return RULGNN_EHIP;
+        RG_RC(allow_dynamic_lds(rg_fusion_kernel, lds));
         if (rg_fusion_mx_ok(g))
             hipLaunchKernelGGL(rg_fusion_mx_kernel, dim3(blocks), dim3(RB), 0, st, g, a->x, a->y, prm, ws, a->pred, a->std_pred, inv_gb);
         else
@@ -1152,10 +1146,7 @@ int rgcnu_run(const rulgnn_rgcnu_shape* s, const rulgnn_rgcnu_args* a, int mode,
     if (mode & 2) {
         if (!a->grads) return RULGNN_EINVAL;
         const size_t lds = rg_fusion_lds(g, true);
-        if (lds > 160 * 1024) return RULGNN_EUNSUPPORTED;
-        if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(rg_fusion_bwd_kernel),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return RULGNN_EHIP;
+        RG_RC(allow_dynamic_lds(rg_fusion_bwd_kernel, lds));
         if (rg_fusion_mx_ok(g))
             hipLaunchKernelGGL(rg_fusion_bwd_mx_kernel, dim3(blocks), dim3(RB), 0, st, g, a->x, a->dpred, prm, ws);
         else
@@ -1166,20 +1157,15 @@ int rgcnu_run(const rulgnn_rgcnu_shape* s, const rulgnn_rgcnu_args* a, int mode,
         la.dw_ih[0] = a->grads + g.o_wih; la.dw_hh[0] = a->grads + g.o_whh; la.db_ih[0] = a->grads + g.o_bih; la.db_hh[0] = a->grads + g.o_bhh;
         la.dw_ih[1] = la.dw_ih[0]; la.dw_hh[1] = la.dw_hh[0]; la.db_ih[1] = la.db_ih[0]; la.db_hh[1] = la.db_hh[0];
         RG_RC(bilstm_backward(&ls, &la, st, 1));
-        if (lds_sclb > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(rg_scl_bwd_kernel),
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_sclb) != hipSuccess)
-            return RULGNN_EHIP;
+        RG_RC(allow_dynamic_lds(rg_scl_bwd_kernel, lds_sclb));
         if (scl_mx) {
             const size_t lm = rg_scl_mx_lds(scl_nt, true);
-            auto go = [&](auto kernel) {
-                static bool raised = false;                          // once per instantiation and process
-                if (lm > 48 * 1024 && !raised) {
-                    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lm);
-                    raised = true;
-                }
+            auto go = [&](auto kernel) -> int {
+                RG_RC(allow_dynamic_lds(kernel, lm));
                 hipLaunchKernelGGL(kernel, dim3((unsigned)gblocks), dim3(64 * RG_MXW), lm, st, g, a->x, prm, ws, key, thr, scale, a->sample_offset);
+                return RULGNN_OK;
             };
-            if (scl_nt == 1) go(rg_scl_bwd_mx_kernel<1>); else go(rg_scl_bwd_mx_kernel<2>);
+            RG_RC(scl_nt == 1 ? go(rg_scl_bwd_mx_kernel<1>) : go(rg_scl_bwd_mx_kernel<2>));
         } else
         hipLaunchKernelGGL(rg_scl_bwd_kernel, dim3((unsigned)gblocks), dim3(RB), lds_sclb, st, g, a->x, prm, ws, key, thr, scale, a->sample_offset);
         hipLaunchKernelGGL(rg_adj_bwd_kernel, dim3(blocks), dim3(RB), 0, st, g, a->x, prm, ws);

@@ -678,11 +678,7 @@ int sagcn_run(const rulgnn_sagcn_shape* s, const rulgnn_sagcn_args* a, int mode,
         hipLaunchKernelGGL(sg_patch_features_kernel<GB>, dim3((unsigned)(g.R < 16384 ? g.R : 16384)), dim3(GB), lds1, st, g, a->x, ws + g.w_raw);
         if (P % 16 == 0 && P <= 128) {
             const size_t lm = sg_graph_mx_lds(P);
-            static bool raised = false;
-            if (lm > 48 * 1024 && !raised) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sg_graph_mx_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                raised = true;
-            }
+            SG_RC(allow_dynamic_lds(sg_graph_mx_kernel, lm));
             hipLaunchKernelGGL(sg_graph_mx_kernel, dim3((unsigned)(g.B < 4096 ? g.B : 4096)), dim3(GB), lm, st, g, (const float*)(ws + g.w_raw),
                            ws + g.w_feat, ws + g.w_ax);
         } else

@@ -1,5 +1,6 @@
 // SGEMM on the gfx950 matrix cores, shared by every family (interface: sgemm_mfma.hpp).  ONE translation unit: the kernels used
 // to live in the header and were instantiated in every unit that included it (most of the library size and build time).
+#include "launch.hpp"
 #include "sgemm_mfma.hpp"
 #include "reduce_device.hpp"
 
@@ -1058,92 +1059,55 @@ static inline bool sgemm_big_ok(const GemmArgs& g, int slices) {
     return g.kchunk % 4 == 0;
 }
 
-// the matrix-core GEMM of a (possibly split-K) problem: the 128x128 kernel where it pays, the 64x64 one otherwise
-static inline void sgemm_launch_tiles(const GemmArgs& g, int slices, hipStream_t st) {
+// the matrix-core GEMM of a (possibly split-K) problem: the 128x128 kernel where it pays, the 64x64 one otherwise.  RULGNN_EHIP when
+// the runtime refuses a kernel its LDS; the caller reads the launch's own error afterwards.
+static inline int sgemm_launch_tiles(const GemmArgs& g, int slices, hipStream_t st) {
+    auto go = [&](auto kernel, dim3 grid, int threads, size_t lds) -> int {
+        if (const int rc = allow_dynamic_lds(kernel, lds); rc != RULGNN_OK) return rc;
+        hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, st, g);
+        return RULGNN_OK;
+    };
     if (sgemm_big_ok(g, slices)) {
         const dim3 grid((g.N + 127) / 128, (g.M + 127) / 128, slices);
         const bool ak = g.sAk == 1, bk = g.sBk == 1;
         if (sgemm_big_mode() >= 1) {                                 // (1: bf16 x 3, f16 x 2 where the caller passes scales; 2: bf16 x 3 only)
-            constexpr size_t lx = (size_t)2 * 6 * 128 * 48;
-            auto gox = [&](auto kernel) {
-                static bool raised = false;                          // once per instantiation and process
-                if (!raised) {
-                    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lx);
-                    raised = true;
-                }
-                hipLaunchKernelGGL(kernel, grid, dim3(256), lx, st, g);
-            };
+            const bool f16 = g.amax_a && g.amax_b && sgemm_big_mode() == 1;
             if (sgemm_wide_ok(g, slices)) {
                 const dim3 wgrid((g.N + 255) / 256, (g.M + 255) / 256, slices);
-                constexpr size_t lw = (size_t)2 * 6 * 256 * 48;
-                auto gow = [&](auto kernel) {
-                    static bool raised = false;
-                    if (!raised) {
-                        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lw);
-                        raised = true;
-                    }
-                    hipLaunchKernelGGL(kernel, wgrid, dim3(512), lw, st, g);
-                };
-                if (g.amax_a && g.amax_b && sgemm_big_mode() == 1) {
+                if (f16) {
                     constexpr size_t lh = (size_t)2 * 4 * 256 * 48;
-                    auto goh = [&](auto kernel) {
-                        static bool raised = false;
-                        if (!raised) {
-                            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lh);
-                            raised = true;
-                        }
-                        hipLaunchKernelGGL(kernel, wgrid, dim3(512), lh, st, g);
-                    };
-                    if (ak && bk) goh(sgemm_f16x2v_kernel<true, true>);
-                    else if (ak) goh(sgemm_f16x2v_kernel<true, false>);
-                    else if (bk) goh(sgemm_f16x2v_kernel<false, true>);
-                    else goh(sgemm_f16x2v_kernel<false, false>);
-                    return;
+                    if (ak && bk) return go(sgemm_f16x2v_kernel<true, true>, wgrid, 512, lh);
+                    if (ak) return go(sgemm_f16x2v_kernel<true, false>, wgrid, 512, lh);
+                    if (bk) return go(sgemm_f16x2v_kernel<false, true>, wgrid, 512, lh);
+                    return go(sgemm_f16x2v_kernel<false, false>, wgrid, 512, lh);
                 }
-                if (ak && bk) gow(sgemm_bf16x3v_kernel<true, true>);
-                else if (ak) gow(sgemm_bf16x3v_kernel<true, false>);
-                else if (bk) gow(sgemm_bf16x3v_kernel<false, true>);
-                else gow(sgemm_bf16x3v_kernel<false, false>);
-                return;
+                constexpr size_t lw = (size_t)2 * 6 * 256 * 48;
+                if (ak && bk) return go(sgemm_bf16x3v_kernel<true, true>, wgrid, 512, lw);
+                if (ak) return go(sgemm_bf16x3v_kernel<true, false>, wgrid, 512, lw);
+                if (bk) return go(sgemm_bf16x3v_kernel<false, true>, wgrid, 512, lw);
+                return go(sgemm_bf16x3v_kernel<false, false>, wgrid, 512, lw);
             }
-            if (g.amax_a && g.amax_b && sgemm_big_mode() == 1) {
+            if (f16) {
                 constexpr size_t l2 = (size_t)2 * 4 * 128 * 48;
-                auto goh = [&](auto kernel) {
-                    static bool raised = false;
-                    if (!raised) {
-                        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)l2);
-                        raised = true;
-                    }
-                    hipLaunchKernelGGL(kernel, grid, dim3(256), l2, st, g);
-                };
-                if (ak && bk) goh(sgemm_f16x2_kernel<true, true>);
-                else if (ak) goh(sgemm_f16x2_kernel<true, false>);
-                else if (bk) goh(sgemm_f16x2_kernel<false, true>);
-                else goh(sgemm_f16x2_kernel<false, false>);
-                return;
+                if (ak && bk) return go(sgemm_f16x2_kernel<true, true>, grid, 256, l2);
+                if (ak) return go(sgemm_f16x2_kernel<true, false>, grid, 256, l2);
+                if (bk) return go(sgemm_f16x2_kernel<false, true>, grid, 256, l2);
+                return go(sgemm_f16x2_kernel<false, false>, grid, 256, l2);
             }
-            if (ak && bk) gox(sgemm_bf16x3_kernel<true, true>);
-            else if (ak) gox(sgemm_bf16x3_kernel<true, false>);
-            else if (bk) gox(sgemm_bf16x3_kernel<false, true>);
-            else gox(sgemm_bf16x3_kernel<false, false>);
-            return;
+            constexpr size_t lx = (size_t)2 * 6 * 128 * 48;
+            if (ak && bk) return go(sgemm_bf16x3_kernel<true, true>, grid, 256, lx);
+            if (ak) return go(sgemm_bf16x3_kernel<true, false>, grid, 256, lx);
+            if (bk) return go(sgemm_bf16x3_kernel<false, true>, grid, 256, lx);
+            return go(sgemm_bf16x3_kernel<false, false>, grid, 256, lx);
         }
         constexpr size_t lds = (size_t)4 * SGEMM_BIG_KT * (128 + 16) * sizeof(float);
-        auto go = [&](auto kernel) {
-            static bool raised = false;                              // once per instantiation and process
-            if (lds > 48 * 1024 && !raised) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-                raised = true;
-            }
-            hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, g);
-        };
-        if (ak && bk) go(sgemm_mfma128_kernel<true, true, SGEMM_BIG_KT>);
-        else if (ak) go(sgemm_mfma128_kernel<true, false, SGEMM_BIG_KT>);
-        else if (bk) go(sgemm_mfma128_kernel<false, true, SGEMM_BIG_KT>);
-        else go(sgemm_mfma128_kernel<false, false, SGEMM_BIG_KT>);
-        return;
+        if (ak && bk) return go(sgemm_mfma128_kernel<true, true, SGEMM_BIG_KT>, grid, 256, lds);
+        if (ak) return go(sgemm_mfma128_kernel<true, false, SGEMM_BIG_KT>, grid, 256, lds);
+        if (bk) return go(sgemm_mfma128_kernel<false, true, SGEMM_BIG_KT>, grid, 256, lds);
+        return go(sgemm_mfma128_kernel<false, false, SGEMM_BIG_KT>, grid, 256, lds);
     }
     hipLaunchKernelGGL(sgemm_mfma_kernel, dim3((g.N + 63) / 64, (g.M + 63) / 64, slices), dim3(256), 0, st, g);
+    return RULGNN_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1309,7 +1273,7 @@ int sgemm(const float* A, int64_t sAm, int64_t sAk, const float* B, int64_t sBn,
     }
     GemmArgs g{A, sAm, sAk, B, sBn, sBk, C, ldc, M, N, K, accumulate ? 1 : 0, K > 0 ? (K + 15) & ~15 : 16, amax_a, amax_b, amax_na, amax_nb};
     (void)hipGetLastError();
-    sgemm_launch_tiles(g, 1, st);
+    if (const int rc = sgemm_launch_tiles(g, 1, st); rc != RULGNN_OK) return rc;
     return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
 }
 
@@ -1742,7 +1706,7 @@ int sgemm_splitk(const float* A, int64_t sAm, int64_t sAk, const float* B, int64
     const int used = (K + kchunk - 1) / kchunk;
     GemmArgs g{A, sAm, sAk, B, sBn, sBk, partial, N, M, N, K, 0, kchunk, amax_a, amax_b, amax_na, amax_nb};
     (void)hipGetLastError();
-    sgemm_launch_tiles(g, used, st);
+    if (const int rc = sgemm_launch_tiles(g, used, st); rc != RULGNN_OK) return rc;
     if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
     return sgemm_reduce_slices(partial, C, ldc, M, N, used, accumulate, st);
 }

@@ -18,6 +18,7 @@
 //      that the four column tiles of a row panel run on one XCD (they share the panel's A planes in that XCD's L2).
 //
 // Shapes: M a multiple of 160 or 128, N of 256, every k slice of 32; anything else stays on sgemm_f16x2v_kernel (sgemm.hip).
+#include "launch.hpp"
 #include "sgemm_mfma.hpp"
 
 namespace rulgnn {
@@ -373,17 +374,13 @@ int sgemm_planes(const float* A, int64_t sAm, int64_t sAk, const float* B, int64
     const int mb = pl_pick_mb(M);
     PlaneGemmArgs g{Ahi, Alo, Bhi, Blo, scales, scales + 64, C, ldc, M, N, K, K / slices, M / (32 * mb), N / 256, slices, accumulate ? 1 : 0};
     const int grid = g.tiles_m * g.tiles_n * slices;
-    auto go = [&](auto kernel, size_t lds) {
-        static bool raised = false;                              // once per instantiation and process
-        if (!raised) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            raised = true;
-        }
+    auto go = [&](auto kernel, size_t lds) -> int {
+        if (const int allowed = allow_dynamic_lds(kernel, lds); allowed != RULGNN_OK) return allowed;
         hipLaunchKernelGGL(kernel, dim3(grid), dim3(512), lds, st, g);
+        return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
     };
-    if (mb == 5) go(sgemm_planes_kernel<5>, (size_t)3 * (2 * 160 * 64 + 2 * 256 * 64));
-    else go(sgemm_planes_kernel<4>, (size_t)3 * (2 * 128 * 64 + 2 * 256 * 64));
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    if (mb == 5) return go(sgemm_planes_kernel<5>, (size_t)3 * (2 * 160 * 64 + 2 * 256 * 64));
+    return go(sgemm_planes_kernel<4>, (size_t)3 * (2 * 128 * 64 + 2 * 256 * 64));
 }
 
 }  // namespace rulgnn

@@ -1477,14 +1477,6 @@ inline int tg_head_groups(const TgGeom& g, bool bwd) {
     return G;
 }
 
-template <typename K>
-inline int tg_allow_lds(K kernel, size_t lds) {
-    if (lds > 160 * 1024) return RULGNN_EUNSUPPORTED;
-    if (lds > 48 * 1024 && hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return RULGNN_EHIP;
-    return RULGNN_OK;
-}
-
 }  // namespace
 
 int64_t stagnn_param_count(const rulgnn_stagnn_shape* s) {
@@ -1544,7 +1536,7 @@ int stagnn_run(const rulgnn_stagnn_shape* s, const rulgnn_stagnn_args* a, int mo
     if (mode & 1) {
         const int G = tg_head_groups(g, false);
         const size_t lg = tg_lds_graph_fwd(g, G);
-        TG_RC(tg_allow_lds(tg_graph_fwd_kernel, lg));
+        TG_RC(allow_dynamic_lds(tg_graph_fwd_kernel, lg));
         hipLaunchKernelGGL(tg_graph_fwd_kernel, grid, dim3(TB * G), lg, st, g, G, a->x, prm, ws);
         TG_LAUNCH_OK();
         for (int l = 0; l < 2; ++l) {
@@ -1552,17 +1544,17 @@ int stagnn_run(const rulgnn_stagnn_shape* s, const rulgnn_stagnn_args* a, int mo
             const size_t l1 = sizeof(float) * ((size_t)Ci * TP + (size_t)Co * TP + 2 * (size_t)Co * Ci);
             const size_t l2 = sizeof(float) * ((size_t)Ci * TP + 2 * (size_t)Co * TP + 2 * Co + (size_t)Co * Ci + 2 * (size_t)Co * Co);
             const size_t l3 = sizeof(float) * ((size_t)Co * TP + (size_t)Hd * T + T + 2 * Co + TB + (size_t)Hd * Co);
-            TG_RC(tg_allow_lds(tg_conv1_fwd_kernel, l1));
-            TG_RC(tg_allow_lds(tg_mid_fwd_kernel, l2));
-            TG_RC(tg_allow_lds(tg_end_fwd_kernel, l3));
+            TG_RC(allow_dynamic_lds(tg_conv1_fwd_kernel, l1));
+            TG_RC(allow_dynamic_lds(tg_mid_fwd_kernel, l2));
+            TG_RC(allow_dynamic_lds(tg_end_fwd_kernel, l3));
             if (tg_conv1_mx_ok(g, l)) {
                 const size_t l1m = tg_conv1_fwd_mx_lds(g, l);
-                TG_RC(tg_allow_lds(tg_conv1_fwd_mx_kernel, l1m));
+                TG_RC(allow_dynamic_lds(tg_conv1_fwd_mx_kernel, l1m));
                 hipLaunchKernelGGL(tg_conv1_fwd_mx_kernel, grid, blk, l1m, st, g, l, stage_in[l], prm, ws);
             } else
             hipLaunchKernelGGL(tg_conv1_fwd_kernel, grid, blk, l1, st, g, l, stage_in[l], prm, ws);
             if (tg_mid_mx_ok(g, l)) {
-                TG_RC(tg_allow_lds(tg_mid_fwd_mx_kernel, TM_FWD_LDS));
+                TG_RC(allow_dynamic_lds(tg_mid_fwd_mx_kernel, TM_FWD_LDS));
                 hipLaunchKernelGGL(tg_mid_fwd_mx_kernel, grid, blk, TM_FWD_LDS, st, g, l, stage_in[l], prm, (const float*)a->bn_state, ws, training);
             } else
             hipLaunchKernelGGL(tg_mid_fwd_kernel, grid, blk, l2, st, g, l, stage_in[l], prm, (const float*)a->bn_state, ws, training);
@@ -1583,19 +1575,19 @@ int stagnn_run(const rulgnn_stagnn_shape* s, const rulgnn_stagnn_args* a, int mo
             const size_t l3 = sizeof(float) * (2 * (size_t)Co * TP + 3 * (size_t)Hd * T + T + 2 * Co + Hd + (size_t)Hd * Co);
             const size_t l2 = sizeof(float) * ((size_t)Ci * TP + 3 * (size_t)Co * TP + 6 * Co + (size_t)Co * Ci + 2 * (size_t)Co * Co);
             const size_t l1 = sizeof(float) * ((size_t)Ci * TP + (size_t)Co * TP + 4 * Co + 2 * (size_t)Co * Ci);
-            TG_RC(tg_allow_lds(tg_mid_bwd_kernel, l2));
-            TG_RC(tg_allow_lds(tg_end_bwd_kernel, l3));
-            TG_RC(tg_allow_lds(tg_conv1_bwd_kernel, l1));
+            TG_RC(allow_dynamic_lds(tg_mid_bwd_kernel, l2));
+            TG_RC(allow_dynamic_lds(tg_end_bwd_kernel, l3));
+            TG_RC(allow_dynamic_lds(tg_conv1_bwd_kernel, l1));
             // (the gradient w.r.t. a stage's input is written over w_dxin[l], which the next kernel down the chain reads)
             hipLaunchKernelGGL(tg_end_bwd_kernel, grid, blk, l3, st, g, l, prm, (const float*)a->bn_state, ws, dpred, (const float*)(ws + g.w_dxin[1]));
             if (tg_mid_mx_ok(g, l)) {
-                TG_RC(tg_allow_lds(tg_mid_bwd_mx_kernel, TM_BWD_LDS));
+                TG_RC(allow_dynamic_lds(tg_mid_bwd_mx_kernel, TM_BWD_LDS));
                 hipLaunchKernelGGL(tg_mid_bwd_mx_kernel, grid, blk, TM_BWD_LDS, st, g, l, stage_in[l], prm, (const float*)a->bn_state, ws);
             } else
             hipLaunchKernelGGL(tg_mid_bwd_kernel, grid, blk, l2, st, g, l, stage_in[l], prm, (const float*)a->bn_state, ws);
             if (tg_conv1_mx_ok(g, l)) {
                 const size_t l1m = tg_conv1_bwd_mx_lds(g, l);
-                TG_RC(tg_allow_lds(tg_conv1_bwd_mx_kernel, l1m));
+                TG_RC(allow_dynamic_lds(tg_conv1_bwd_mx_kernel, l1m));
                 hipLaunchKernelGGL(tg_conv1_bwd_mx_kernel, grid, blk, l1m, st, g, l, stage_in[l], prm, (const float*)a->bn_state, ws, ws + g.w_dxin[l]);
             } else
             hipLaunchKernelGGL(tg_conv1_bwd_kernel, grid, blk, l1, st, g, l, stage_in[l], prm, (const float*)a->bn_state, ws, ws + g.w_dxin[l]);
@@ -1603,7 +1595,7 @@ int stagnn_run(const rulgnn_stagnn_shape* s, const rulgnn_stagnn_args* a, int mo
         }
         const int G = tg_head_groups(g, true);
         const size_t lg = tg_lds_graph_bwd(g, G);
-        TG_RC(tg_allow_lds(tg_graph_bwd_kernel, lg));
+        TG_RC(allow_dynamic_lds(tg_graph_bwd_kernel, lg));
         hipLaunchKernelGGL(tg_graph_bwd_kernel, grid, dim3(TB * G), lg, st, g, G, prm, ws);
         TG_LAUNCH_OK();
         TG_RC(rows_sum(ws + g.w_gpart, g.nblk, g.pcount, g.pcount, a->grads, st));

@@ -453,12 +453,7 @@ void sc_ws_layout(const ScGeom& g, ScWs* w) {
 
 template <typename K>
 int sc_rows(K kernel, int64_t items, int cap) {
-    int dev = 0, cus = 256, per_cu = 0;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-    }
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, AB, 0) != hipSuccess || per_cu < 1) per_cu = 1;
+    auto [cus, per_cu] = residency(kernel, AB, 0);
     int64_t want = (int64_t)cus * per_cu;
     if (want > items) want = items;
     if (want > cap) want = cap;

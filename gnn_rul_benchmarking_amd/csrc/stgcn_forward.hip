@@ -84,12 +84,9 @@ static int launch_forward_fix(const TileGeom& g, const rulgnn_stgcn_shape* s, co
     a.magicP = g.magicP; a.vec4 = g.vec4 && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
     a.stage_floats = g.stage_floats;
     const size_t lds = stgcn_forward_exact_lds_bytes(s);
-    if (lds == 0 || lds > MAX_LDS_BYTES) return RULGNN_EUNSUPPORTED;     // backstop: the C-ABI gate (tiled_eval) keeps such shapes out
-    if (lds > 48 * 1024) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&stgcn_forward_eval_kernel<RW, NFIX, PFIX, LFIX>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return RULGNN_EHIP;
-    }
+    if (lds == 0) return RULGNN_EUNSUPPORTED;
+    // (above MAX_LDS_BYTES: a backstop, the C-ABI gate (tiled_eval) keeps such shapes out)
+    if (const int rc = allow_dynamic_lds(&stgcn_forward_eval_kernel<RW, NFIX, PFIX, LFIX>, lds); rc != RULGNN_OK) return rc;
     const int grid = persistent_grid(stgcn_forward_eval_kernel<RW, NFIX, PFIX, LFIX>, g.ntiles, lds, 4);
     (void)hipGetLastError();   // drop any stale error of the caller's earlier HIP calls
     hipLaunchKernelGGL((stgcn_forward_eval_kernel<RW, NFIX, PFIX, LFIX>), dim3(grid), dim3(BLOCK), lds, stream, x, prm, bn, out, a);
@@ -159,11 +156,9 @@ static int launch_fixup(const TileGeom& g, const rulgnn_stgcn_shape* s, const fl
     a.magicP = g.magicP; a.vec4 = g.vec4 && ((reinterpret_cast<uintptr_t>(x) & 15) == 0);
     a.stage_floats = g.stage_floats;
     const size_t lds = stgcn_forward_fixup_lds_bytes(s);
-    if (lds == 0 || lds > MAX_LDS_BYTES) return RULGNN_EUNSUPPORTED;     // backstop: stgcn_forward_eval checks before the wide kernel runs
-    if (lds > 48 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(&stgcn_forward_fixup_kernel<RW>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess)
-        return RULGNN_EHIP;
+    if (lds == 0) return RULGNN_EUNSUPPORTED;
+    // (above MAX_LDS_BYTES: a backstop, stgcn_forward_eval checks before the wide kernel runs)
+    if (const int rc = allow_dynamic_lds(&stgcn_forward_fixup_kernel<RW>, lds); rc != RULGNN_OK) return rc;
     int64_t grid = (s->batch + BLOCK - 1) / BLOCK;
     if (grid > 1024) grid = 1024;
     (void)hipGetLastError();

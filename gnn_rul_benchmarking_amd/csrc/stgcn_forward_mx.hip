@@ -1172,17 +1172,9 @@ static int mx_launch(const rulgnn_stgcn_shape* s, const float* x, const float* p
     a.buf_floats = mx_buf_floats(s);
     a.taps = taps;
     const size_t lds = (size_t)a.buf_floats * sizeof(float) + MX_CONV_BYTES;
-    if (lds > 64 * 1024) return RULGNN_EUNSUPPORTED;
     auto kern = &stgcn_forward_mx_kernel<L, NFIX, PFIX, TAPS>;
-    if (lds > 48 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return RULGNN_EHIP;
-    int dev = 0, cus = 256, per_cu = 0;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-    }
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+    if (const int rc = allow_dynamic_lds(kern, lds, 64 * 1024); rc != RULGNN_OK) return rc;
+    auto [cus, per_cu] = residency(kern, 64, lds);
     // Wavefronts per CU: as many as fit, in whole multiples of the four SIMDs (an uneven spread costs more than the extra
     // wavefront brings: at 1M samples 8 per CU 806 us, 9: 981, 10: 912, 11: 850 -- round 2's kernel).  Three per SIMD at 14x30.
     if (per_cu > MX_BLOCKS_PER_CU) per_cu = MX_BLOCKS_PER_CU;
@@ -1241,17 +1233,9 @@ static int train_f0_mx_launch(const rulgnn_stgcn_shape* s, const float* x, const
     MxF0Out o;
     o.cacheX = cacheX; o.cacheA = cacheA; o.H0 = H0; o.Z1 = Z1; o.cells = cells_bn0; o.cell_stride = cell_stride_doubles; o.replicas = replicas;
     const size_t lds = MXF0_WAVES * ((size_t)a.buf_floats * sizeof(float) + MX_CONV_BYTES) + sizeof(double) * MXF0_WAVES * 2 * F;
-    if (lds > 80 * 1024) return RULGNN_EUNSUPPORTED;
     auto launch = [&](auto kern) -> int {
-        if (lds > 48 * 1024 &&
-            hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return RULGNN_EHIP;
-        int dev = 0, cus = 256, per_cu = 0;
-        if (hipGetDevice(&dev) == hipSuccess) {
-            int v = 0;
-            if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-        }
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64 * MXF0_WAVES, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+        if (const int rc = allow_dynamic_lds(kern, lds, 80 * 1024); rc != RULGNN_OK) return rc;
+        auto [cus, per_cu] = residency(kern, 64 * MXF0_WAVES, lds);
         if (per_cu > MX_WAVES_PER_SIMD) per_cu = MX_WAVES_PER_SIMD;         // a workgroup is one wavefront per SIMD
         int64_t grid = (int64_t)cus * per_cu;
         const int64_t want = (a.ntiles + MXF0_WAVES - 1) / MXF0_WAVES;
@@ -1283,16 +1267,9 @@ static int mxw_launch(const rulgnn_stgcn_shape* s, const float* x, const float* 
     a.buf_floats = (s->num_patch * s->patch_size + 3) & ~3;
     a.taps = nullptr;
     const size_t lds = (size_t)G::theta_bytes(L) + (size_t)MXW_WAVES * ((size_t)a.buf_floats * 4 + G::region_bytes);
-    if (lds > 160 * 1024) return RULGNN_EUNSUPPORTED;
     auto kern = &stgcn_forward_mxw_kernel<L, NT, NFIX, PFIX>;
-    if (lds > 48 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return RULGNN_EHIP;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-    }
+    if (const int rc = allow_dynamic_lds(kern, lds); rc != RULGNN_OK) return rc;
+    const int cus = device_cu_count();
     int64_t grid = (s->batch + MXW_WAVES - 1) / MXW_WAVES;
     if (grid > cus) grid = cus;
     (void)hipGetLastError();

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/rulgnn.h"
+#include "launch.hpp"
 #include "stgcn_device.hpp"
 
 namespace rulgnn {
@@ -80,15 +81,9 @@ __host__ __device__ inline uint32_t dropout_layer_key(uint64_t seed, uint64_t st
 // (measured on the fused forward at 1M samples: x4 -> -10 %; it hurts the short training phases).
 template <typename K>
 inline int persistent_grid(K kernel, int64_t ntiles, size_t lds_bytes, int oversub = 1) {
-    int dev = 0, cus = 256, per_cu = 0;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-    }
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, BLOCK, lds_bytes) != hipSuccess || per_cu < 1)
-        per_cu = 1;
+    const Residency r = residency(kernel, BLOCK, lds_bytes);
     int64_t want = (ntiles + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
-    int64_t cap = (int64_t)cus * per_cu;
+    int64_t cap = (int64_t)r.cus * r.per_cu;
     if (oversub > 1 && want >= cap * oversub * 2) cap *= oversub;    // only when every wavefront still gets >= 8 tiles
     if (want > cap) want = cap;
     if (want < 1) want = 1;
@@ -134,9 +129,8 @@ int stgcn_tiled_train(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args
 size_t stgcn_train_workspace_bytes(const rulgnn_stgcn_shape* s);
 // The LDS bytes a launch form of the fused row-mapped kernels requests at this shape (and MPNN order): the exact eval kernel, the scan
 // behind the wide matrix-core eval kernel (order 1), the largest phase of the fp32 training chain; 0 where the row-mapped geometry does
-// not apply.  The launchers size their launches with these and the C-ABI gates (rulgnn_api.hip) compare them with MAX_LDS_BYTES, so a
+// not apply.  The launchers size their launches with these and the C-ABI gates (rulgnn_api.hip) compare them with MAX_LDS_BYTES (launch.hpp), so a
 // shape the gates accept cannot fail a launcher's LDS check after an earlier launch of the same call has run.
-constexpr size_t MAX_LDS_BYTES = 160 * 1024;
 size_t stgcn_forward_exact_lds_bytes(const rulgnn_stgcn_shape* s);
 size_t stgcn_forward_fixup_lds_bytes(const rulgnn_stgcn_shape* s);
 size_t stgcn_train_chain_lds_bytes(const rulgnn_stgcn_shape* s);

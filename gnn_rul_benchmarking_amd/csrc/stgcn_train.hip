@@ -1115,14 +1115,7 @@ struct WsLayout {
     int max_grid;
 };
 
-static int max_resident_blocks() {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-    }
-    return cus * 8;
-}
+static int max_resident_blocks() { return device_cu_count() * 8; }
 
 // training geometry: RW 16 for num_patch <= 16, else one sample per wavefront (RW 64)
 static int train_geometry(const rulgnn_stgcn_shape* s, TileGeom* g) {
@@ -1215,12 +1208,8 @@ static int launch_phase_n(const TrainK& k_in, const float* x, const float* prm, 
     TrainK k = k_in;
     k.wave_area_floats = wave_area_for(KIND, IDX, g);
     const size_t lds = phase_lds_bytes(RW, L, KIND, IDX, g, KORD);
-    if (lds > MAX_LDS_BYTES) return RULGNN_EUNSUPPORTED;       // backstop: the C-ABI gate (stgcn_train_workspace_bytes) keeps such shapes out
-    if (lds > 48 * 1024) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
-            hipSuccess)
-            return RULGNN_EHIP;
-    }
+    // (above MAX_LDS_BYTES: a backstop, the C-ABI gate (stgcn_train_workspace_bytes) keeps such shapes out)
+    if (const int rc = allow_dynamic_lds(kern, lds); rc != RULGNN_OK) return rc;
     int grid = persistent_grid(kern, k.ntiles, lds);
     if (grid > max_grid) grid = max_grid;
     if (grid_out) *grid_out = grid;
@@ -1495,17 +1484,13 @@ static int launch_coop(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_arg
     wa = wa > c.wa_top ? wa : c.wa_top;
     size_t lds = train_lds_bytes(RW, L, wa);
     if (lds < sizeof(float) * FIN_SLICES * FIN_COLS) lds = sizeof(float) * FIN_SLICES * FIN_COLS;
-    if (lds > 160 * 1024) return RULGNN_EUNSUPPORTED;
     const int64_t grid = (k.ntiles + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
     if (grid > w.max_grid) return RULGNN_EUNSUPPORTED;
-    if (lds > 48 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return RULGNN_EHIP;
-    int dev = 0, cus = 0, per_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return RULGNN_EHIP;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, BLOCK, lds) != hipSuccess || per_cu < 1) return RULGNN_EUNSUPPORTED;
+    if (const int rc = allow_dynamic_lds(kern, lds); rc != RULGNN_OK) return rc;
+    Residency res;
+    if (const int rc = residency(reinterpret_cast<const void*>(kern), BLOCK, lds, &res, /*strict=*/true); rc != RULGNN_OK) return rc;
     // every workgroup must be resident for the grid barriers; one workgroup per CU keeps them evenly spread as well
-    if (grid > (int64_t)cus) return RULGNN_EUNSUPPORTED;
+    if (grid > (int64_t)res.cus) return RULGNN_EUNSUPPORTED;
     const bool fused_adam = opt != nullptr;
     void* adam_state = fused_adam ? opt->step_state : nullptr;
     if (adam_state && a->step_state && adam_state != a->step_state) return RULGNN_EINVAL;

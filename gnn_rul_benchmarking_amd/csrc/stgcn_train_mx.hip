@@ -1171,16 +1171,8 @@ template <int L, int KIND, int IDX, int NFIX>
 static int mxt_launch(const MxTrainK& k, hipStream_t stream, int max_grid, int* grid_out) {
     auto kern = &stgcn_train_mx_kernel<L, KIND, IDX, NFIX>;
     const size_t lds = mxt_lds_bytes(L, KIND, IDX, k.N);
-    if (lds > MXT_MAX_LDS_BYTES) return RULGNN_EUNSUPPORTED;
-    if (lds > 48 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return RULGNN_EHIP;
-    int dev = 0, cus = 256, per_cu = 0;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-    }
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64 * MXT_WAVES, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+    if (const int rc = allow_dynamic_lds(kern, lds, MXT_MAX_LDS_BYTES); rc != RULGNN_OK) return rc;
+    auto [cus, per_cu] = residency(kern, 64 * MXT_WAVES, lds);
     if (per_cu > MX_WAVES_PER_SIMD) per_cu = MX_WAVES_PER_SIMD;           // a workgroup is one wavefront per SIMD
     if (const char* e = getenv("RULGNN_MXT_BLOCKS_PER_CU")) { const int v = atoi(e); if (v > 0) per_cu = v; }   // tuning aid
     int64_t grid = (int64_t)cus * per_cu;
@@ -1252,21 +1244,14 @@ static int mxt_persist_launch(const MxTrainK& k, hipStream_t stream, int64_t gri
     for (int i = 1; i < 2 * L; ++i) lds = std::max(lds, mxt_lds_bytes(L, PH_F, i, k.N));
     lds = std::max(lds, mxt_lds_bytes(L, PH_TOP, 0, k.N));
     for (int i = 0; i < 2 * L; ++i) lds = std::max(lds, mxt_lds_bytes(L, PH_G, i, k.N));
-    if (lds > MXT_MAX_LDS_BYTES) return RULGNN_EUNSUPPORTED;
-    if (lds > 48 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return RULGNN_EHIP;
+    if (const int rc = allow_dynamic_lds(kern, lds, MXT_MAX_LDS_BYTES); rc != RULGNN_OK) return rc;
     (void)hipGetLastError();
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * MXT_WAVES), lds, stream, k);
     return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
 }
 int stgcn_train_mx_persistent_grid(int64_t batch, int num_layers, int max_grid) {
     if (num_layers != 2 || batch <= 0) return 0;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-    }
+    const int cus = device_cu_count();
     const int64_t grid = ((batch + 3) / 4 + MXT_WAVES - 1) / MXT_WAVES;
     // one workgroup per CU: co-resident whatever else runs.  (Measured with a 512-workgroup grid at the headline batch: 0.44 ms against
     // 0.345 for the launches, 0.23 against 0.14 at 16 384 -- one register allocation for eight bodies spills in the tile loops.)

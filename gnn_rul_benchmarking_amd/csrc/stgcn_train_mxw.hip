@@ -1275,16 +1275,8 @@ static size_t mxtw_lds_bytes(int L, int kind, int idx, int N, int NT) {
 template <typename K>
 static int mxtw_grid(K kern, size_t lds, int64_t B, int max_grid, int* grid_out) {
     constexpr int cap = MX_WAVES_PER_SIMD;
-    if (lds > 160 * 1024) return RULGNN_EUNSUPPORTED;
-    if (lds > 48 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-        return RULGNN_EHIP;
-    int dev = 0, cus = 256, per_cu = 0;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-    }
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64 * MXT_WAVES, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+    if (const int rc = allow_dynamic_lds(kern, lds); rc != RULGNN_OK) return rc;
+    auto [cus, per_cu] = residency(kern, 64 * MXT_WAVES, lds);
     if (per_cu > cap) per_cu = cap;
     int64_t grid = (int64_t)cus * per_cu;
     const int64_t want = (B + MXT_WAVES - 1) / MXT_WAVES;

@@ -1600,12 +1600,7 @@ static void msg_ws_layout(const MsgGeom& g, MsgWs* w) {
 
 template <typename K>
 static int resident_grid(K kernel, int64_t items, size_t lds, int cap_rows) {
-    int dev = 0, cus = 256, per_cu = 0;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-    }
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, MB, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+    auto [cus, per_cu] = residency(kernel, MB, lds);
     int64_t want = (int64_t)cus * per_cu;
     if (want > items) want = items;
     if (want > cap_rows) want = cap_rows;
@@ -1616,10 +1611,7 @@ static int resident_grid(K kernel, int64_t items, size_t lds, int cap_rows) {
 template <int TW>
 static int launch_features_tw(const MsgGeom& g, const float* x, const float* prm, float* cat, float* gi, hipStream_t st) {
     const size_t lds = features_lds_bytes(g);
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(msg_features_kernel<TW>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess)
-        return RULGNN_EHIP;
+    if (const int rc = allow_dynamic_lds(msg_features_kernel<TW>, lds); rc != RULGNN_OK) return rc;
     const int grid = resident_grid(msg_features_kernel<TW>, g.G, lds, 1 << 20);
     hipLaunchKernelGGL(msg_features_kernel<TW>, dim3(grid), dim3(MB), lds, st, g, x, prm, cat, gi);
     return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
@@ -1628,15 +1620,8 @@ static int launch_features(const MsgGeom& g, const float* x, const float* prm, f
     size_t lds = 0;
     if (mx_features_ok(g, &lds)) {                  // graphs of >= 12 nodes: one wavefront per graph on the fp32 matrix cores
         auto go = [&](auto kern) -> int {
-            if (lds > 48 * 1024 &&
-                hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-                return RULGNN_EHIP;
-            int dev = 0, cus = 256, per_cu = 0;
-            if (hipGetDevice(&dev) == hipSuccess) {
-                int v = 0;
-                if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-            }
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64 * MXW, lds) != hipSuccess || per_cu < 1) per_cu = 1;
+            if (const int rc = allow_dynamic_lds(kern, lds); rc != RULGNN_OK) return rc;
+            auto [cus, per_cu] = residency(kern, 64 * MXW, lds);
             int64_t grid = (int64_t)cus * per_cu;
             const int64_t need = (g.G + MXW - 1) / MXW;
             if (grid > need) grid = need;
@@ -1652,10 +1637,7 @@ template <int TW>
 static int launch_gcn_backward(const MsgGeom& g, int rows_max, const float* cat, const float* dcat, const float* prm, float* gpart,
                                hipStream_t st, int* rows_out) {
     const size_t lds = gcn_backward_lds_bytes(g);
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(msg_gcn_backward_kernel<TW>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess)
-        return RULGNN_EHIP;
+    if (const int rc = allow_dynamic_lds(msg_gcn_backward_kernel<TW>, lds); rc != RULGNN_OK) return rc;
     const int rows = resident_grid(msg_gcn_backward_kernel<TW>, g.G, lds, rows_max);
     hipLaunchKernelGGL(msg_gcn_backward_kernel<TW>, dim3(rows), dim3(MB), lds, st, g, cat, dcat, prm, gpart);
     *rows_out = rows;
@@ -1766,15 +1748,8 @@ int stmsgcn_run(const rulgnn_stmsgcn_shape* s, const rulgnn_stmsgcn_args* a, int
         int rcb;
         if (mx_backward_ok(g, &lds_mx)) {                  // graphs of >= 12 nodes: one wavefront per graph on the fp32 matrix cores
             auto launch_mx = [&](auto kern) -> int {
-                if (lds_mx > 48 * 1024 &&
-                    hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_mx) != hipSuccess)
-                    return RULGNN_EHIP;
-                int dev = 0, cus = 256, per_cu = 0;
-                if (hipGetDevice(&dev) == hipSuccess) {
-                    int v = 0;
-                    if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-                }
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 64 * MXW, lds_mx) != hipSuccess || per_cu < 1) per_cu = 1;
+                if (const int rc = allow_dynamic_lds(kern, lds_mx); rc != RULGNN_OK) return rc;
+                auto [cus, per_cu] = residency(kern, 64 * MXW, lds_mx);
                 int64_t grid = (int64_t)cus * per_cu;
                 const int64_t need = (g.G + MXW - 1) / MXW;
                 if (grid > need) grid = need;
