@@ -15,7 +15,7 @@
 #include "aux_stream.hpp"
 #include "reduce_device.hpp"
 #include "sgemm_mfma.hpp"
-#include "stgcn_host.hpp"
+#include "families_host.hpp"
 #include "tcn_nodes.hpp"
 
 namespace rulgnn {
@@ -755,33 +755,32 @@ static void ast_pgrad_dims(const AstGeom& g, SplitKJob* j) {
 }
 
 void ast_ws_layout(const AstGeom& g, AstWs* w) {
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t BNT = (size_t)g.B * g.N * g.T * sizeof(float);
-    size_t o = 0;
-    w->cells = o; o = al(o + sizeof(Cells) * CELL_REP);
-    w->one = o; o = al(o + 256);
-    w->z1 = o; o = al(o + BNT);
-    w->out0 = o; o = al(o + BNT);
-    w->z2 = o; o = al(o + BNT);
-    w->zpre = o; o = al(o + BNT);
-    w->out1 = o; o = al(o + BNT);
-    w->tcat = o; o = al(o + BNT * g.K);
-    w->px = o; o = al(o + BNT);
-    w->adj = o; o = al(o + (size_t)g.B * g.N * g.N * sizeof(float));
-    w->dist = o; o = al(o + (size_t)g.B * g.N * g.N * sizeof(float));
-    w->scat = o; o = al(o + (size_t)g.B * g.KE * sizeof(float));
-    w->pooled = o; o = al(o + (size_t)g.B * g.O * sizeof(float));
-    w->dpred = o; o = al(o + (size_t)g.B * sizeof(float));
-    w->sqerr = o; o = al(o + (size_t)g.B * sizeof(float));
-    w->dmat = o; o = al(o + (size_t)g.B * g.O * sizeof(float));
-    w->dpx = o; o = al(o + BNT);
-    w->ds1 = o; o = al(o + BNT);
-    w->dy2 = o; o = al(o + BNT);
-    w->dy1 = o; o = al(o + BNT);
+    const size_t BNT = (size_t)g.B * g.N * g.T;
+    WsCarver c;
+    w->cells = c.take_bytes(sizeof(Cells) * CELL_REP);
+    w->one = c.take_bytes(256);
+    w->z1 = c.take<float>(BNT);
+    w->out0 = c.take<float>(BNT);
+    w->z2 = c.take<float>(BNT);
+    w->zpre = c.take<float>(BNT);
+    w->out1 = c.take<float>(BNT);
+    w->tcat = c.take<float>(BNT * g.K);
+    w->px = c.take<float>(BNT);
+    w->adj = c.take<float>((size_t)g.B * g.N * g.N);
+    w->dist = c.take<float>((size_t)g.B * g.N * g.N);
+    w->scat = c.take<float>((size_t)g.B * g.KE);
+    w->pooled = c.take<float>((size_t)g.B * g.O);
+    w->dpred = c.take<float>((size_t)g.B);
+    w->sqerr = c.take<float>((size_t)g.B);
+    w->dmat = c.take<float>((size_t)g.B * g.O);
+    w->dpx = c.take<float>(BNT);
+    w->ds1 = c.take<float>(BNT);
+    w->dy2 = c.take<float>(BNT);
+    w->dy1 = c.take<float>(BNT);
     w->rows = 1024;
-    w->thb = o; o = al(o + (size_t)AST_BWD_ROWS * g.E * sizeof(float));
-    w->gp1 = o; o = al(o + (size_t)w->rows * g.N * g.N * KT * sizeof(float));
-    w->gp2 = o; o = al(o + (size_t)w->rows * g.N * g.N * KT * sizeof(float));
+    w->thb = c.take<float>((size_t)AST_BWD_ROWS * g.E);
+    w->gp1 = c.take<float>((size_t)w->rows * g.N * g.N * KT);
+    w->gp2 = c.take<float>((size_t)w->rows * g.N * g.N * KT);
     const int mx = g.KE > g.E ? g.KE : g.E;
     // (... or the five parameter-gradient products of a step at once: ast_pgrad_jobs)
     SplitKJob dims[5];
@@ -790,17 +789,8 @@ void ast_ws_layout(const AstGeom& g, AstWs* w) {
     const size_t bf = sgemm_splitk_batch_floats(dims, 5);
     sf = sf > bf ? sf : bf;
     w->split_floats = sf;
-    w->split = o; o = al(o + sf * sizeof(float));
-    w->total = o;
-}
-
-template <typename K>
-int resident_rows(K kernel, int64_t items, int cap, int block = AB) {
-    auto [cus, per_cu] = residency(kernel, block, 0);
-    int64_t want = (int64_t)cus * per_cu;
-    if (want > items) want = items;
-    if (want > cap) want = cap;
-    return want < 1 ? 1 : (int)want;
+    w->split = c.take<float>(sf);
+    w->total = c.total();
 }
 
 }  // namespace
@@ -818,12 +808,6 @@ size_t astgcnn_workspace_bytes(const rulgnn_astgcnn_shape* s) {
     return w.total;
 }
 
-#define AST_RC(call)                  \
-    do {                              \
-        const int rc_ = (call);       \
-        if (rc_ != RULGNN_OK) return rc_; \
-    } while (0)
-
 // mode bit 0: forward (training != 0: batch statistics), bit 1: backward
 // <SN, SE, SO>: the kernels' instantiation -- the reference's two wirings (N-CMAPSS: 20 nodes, C-MAPSS: 14; 50 steps, 64 outputs) have their
 // shapes as compile-time constants, anything else runs the generic <0, 0, 0>
@@ -833,7 +817,7 @@ static int astgcnn_run_t(const rulgnn_astgcnn_shape* s, const rulgnn_astgcnn_arg
     // threads of the TCN kernels: 20 nodes x 50 steps are 260 / 400 work items per sample -- one round of 448 threads (tcn_nodes.hpp)
     constexpr int TTB = AB;             // (the matrix-core convolution kernels: four wavefronts, a 16-step column tile each)
     AstGeom g;
-    AST_RC(ast_geometry(s, &g));
+    RULGNN_TRY(ast_geometry(s, &g));
     if (sync) {          // both BatchNorm layers normalise by the statistics of the GLOBAL batch (cells all-reduced between the kernels)
         if (mode != 3 || !a->training || a->global_batch < g.B || g.B < 1 || a->bn_moment_weight > 0.f) return RULGNN_EINVAL;
         g.BG = a->global_batch;
@@ -841,9 +825,9 @@ static int astgcnn_run_t(const rulgnn_astgcnn_shape* s, const rulgnn_astgcnn_arg
     AstWs w;
     ast_ws_layout(g, &w);
     if (a->workspace_bytes < w.total) return RULGNN_EWORKSPACE;
-    char* ws = static_cast<char*>(a->workspace);
-    auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-    Cells* cells = reinterpret_cast<Cells*>(ws + w.cells);
+    const Workspace ws(a->workspace);
+    auto F = [&](size_t off) { return ws.at<float>(off); };
+    Cells* cells = ws.at<Cells>(w.cells);
     const float* prm = a->params;
     const int training = a->training ? 1 : 0;
     const int N = g.N, T = g.T, E = g.E, O = g.O, KE = g.KE;
@@ -862,15 +846,15 @@ static int astgcnn_run_t(const rulgnn_astgcnn_shape* s, const rulgnn_astgcnn_arg
     AuxFork fk(st, (mode & 2) ? a->aux_stream : nullptr);
     if (mode & 1) {
         hipLaunchKernelGGL(ast_prepare_kernel, dim3(1), dim3(1024), 0, st, cells, F(w.one));
-        const int rows = resident_rows((tcn_conv_kernel<1, AstGeom, SN, SE, TTB>), g.B, 1 << 20, TTB);
+        const int rows = resident_rows((tcn_conv_kernel<1, AstGeom, SN, SE, TTB>), TTB, 0, g.B, 1 << 20);
         hipLaunchKernelGGL((tcn_conv_kernel<1, AstGeom, SN, SE, TTB>), dim3(rows), dim3(TTB), 0, st, g, a->x, prm, a->bn_stats, training, (const float*)nullptr,
                            F(w.z1), (float*)nullptr, cells);
-        AST_RC(sync_pair(0, 0));
+        RULGNN_TRY(sync_pair(0, 0));
         hipLaunchKernelGGL((tcn_conv_kernel<2, AstGeom, SN, SE, TTB>), dim3(rows), dim3(TTB), 0, st, g, a->x, prm, a->bn_stats, training, (const float*)F(w.z1),
                            F(w.z2), F(w.out0), cells);
-        AST_RC(sync_pair(0, 1));
+        RULGNN_TRY(sync_pair(0, 1));
         // gate, P projection, graph, Chebyshev terms, node sums, the filter product and the head: one launch (ast_front_kernel)
-        hipLaunchKernelGGL((ast_front_kernel<SN, SE, SO>), dim3(resident_rows((ast_front_kernel<SN, SE, SO>), g.B, 1 << 20)), dim3(AB), 0, st, g, a->x, prm, a->bn_stats, training,
+        hipLaunchKernelGGL((ast_front_kernel<SN, SE, SO>), dim3(resident_rows((ast_front_kernel<SN, SE, SO>), AB, 0, g.B, 1 << 20)), dim3(AB), 0, st, g, a->x, prm, a->bn_stats, training,
                            (const Cells*)cells, (const float*)F(w.z2), (const float*)F(w.out0), F(w.zpre), F(w.out1), F(w.tcat), F(w.px), F(w.adj),
                            F(w.dist), F(w.scat), F(w.pooled), a->y, a->pred, F(w.dpred), F(w.sqerr), F(w.dmat), inv_gb);
         if (training && a->bn_batch && !(mode & 2))            // (with a backward in the same call: beside its chain, below)
@@ -889,7 +873,7 @@ static int astgcnn_run_t(const rulgnn_astgcnn_shape* s, const rulgnn_astgcnn_arg
         // (with a forward in the same call ast_prepare_kernel wrote it; batch statistics and the loss sum ride in the finalize kernel)
         if (!(mode & 1)) hipLaunchKernelGGL(ast_fill_one_kernel, dim3(1), dim3(1), 0, st, F(w.one));
         // DT = D Fcat^T, the graph backward, dG = dG_cheb + dPX P and the gate backward (BatchNorm-2 sums): one launch
-        const int bwd_rows = resident_rows((ast_graph_bwd_kernel<SN, SE, SO>), g.B, AST_BWD_ROWS);
+        const int bwd_rows = resident_rows((ast_graph_bwd_kernel<SN, SE, SO>), AB, 0, g.B, AST_BWD_ROWS);
         hipEvent_t bwd_done = fk.stop_event();                       // (the fork point: behind this kernel)
         RULGNN_LAUNCH_EV(bwd_done, (ast_graph_bwd_kernel<SN, SE, SO>), dim3(bwd_rows), dim3(AB), 0, st, g, prm,
                          (const float*)F(w.px), (const float*)F(w.tcat), (const float*)F(w.adj), (const float*)F(w.dist), (const float*)F(w.dmat),
@@ -908,13 +892,13 @@ static int astgcnn_run_t(const rulgnn_astgcnn_shape* s, const rulgnn_astgcnn_arg
         jobs[4].A = F(w.zpre); jobs[4].sAm = 1; jobs[4].sAk = E; jobs[4].B = a->x; jobs[4].sBn = 1; jobs[4].sBk = T; jobs[4].C = gr + g.o_thw; jobs[4].ldc = T;
         if (fk.active()) {
             fk.fork_after(bwd_done);
-            AST_RC(sgemm_splitk_batch(jobs, 5, split, w.split_floats, wst));
+            RULGNN_TRY(sgemm_splitk_batch(jobs, 5, split, w.split_floats, wst));
         }
-        const int rows = resident_rows((tcn_conv_bwd_kernel<2, AstGeom, SN, SE, TTB>), g.B, w.rows, TTB);
-        AST_RC(sync_pair(1, 1));
+        const int rows = resident_rows((tcn_conv_bwd_kernel<2, AstGeom, SN, SE, TTB>), TTB, 0, g.B, w.rows);
+        RULGNN_TRY(sync_pair(1, 1));
         hipLaunchKernelGGL((tcn_conv_bwd_kernel<2, AstGeom, SN, SE, TTB>), dim3(rows), dim3(TTB), 0, st, g, prm, cells, (const float*)F(w.z2), (const float*)F(w.dy2),
                            (const float*)F(w.out0), (const float*)F(w.ds1), (const float*)F(w.z1), F(w.dy1), F(w.gp2));
-        AST_RC(sync_pair(1, 0));
+        RULGNN_TRY(sync_pair(1, 0));
         hipLaunchKernelGGL((tcn_conv_bwd_kernel<1, AstGeom, SN, SE, TTB>), dim3(rows), dim3(TTB), 0, st, g, prm, cells, (const float*)F(w.z1), (const float*)F(w.dy1),
                            a->x, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, F(w.gp1));
         AstFin fin;
@@ -928,7 +912,7 @@ static int astgcnn_run_t(const rulgnn_astgcnn_shape* s, const rulgnn_astgcnn_arg
             // one stream: the products' slice sums, both convolutions' partial weight rows, the gate's bias gradient (the graph backward's
             // partial rows; theta.bias and gate.bias share it) and the finalize body in ONE launch behind the product launch
             ReduceBatch rb;
-            AST_RC(sgemm_splitk_batch_products(jobs, 5, split, w.split_floats, st, &rb));
+            RULGNN_TRY(sgemm_splitk_batch_products(jobs, 5, split, w.split_floats, st, &rb));
             RowsSumJobs jb{};
             jb.part[0] = F(w.gp1); jb.out[0] = gr + g.o_w1; jb.rows[0] = rows; jb.n[0] = N * N * KT; jb.ld[0] = (int64_t)N * N * KT;
             jb.part[1] = F(w.gp2); jb.out[1] = gr + g.o_w2; jb.rows[1] = rows; jb.n[1] = N * N * KT; jb.ld[1] = (int64_t)N * N * KT;
@@ -945,12 +929,12 @@ static int astgcnn_run_t(const rulgnn_astgcnn_shape* s, const rulgnn_astgcnn_arg
         }
         // both convolutions' partial weight rows in one launch (the second used to sit between the two backward kernels)
         // ... and the gate's bias gradient (the graph backward's partial rows; theta.bias and gate.bias share it)
-        AST_RC(rows_sum3(F(w.gp1), gr + g.o_w1, F(w.gp2), gr + g.o_w2, rows, (int64_t)N * N * KT, N * N * KT, F(w.thb), gr + g.o_thb, gr + g.o_gb,
+        RULGNN_TRY(rows_sum3(F(w.gp1), gr + g.o_w1, F(w.gp2), gr + g.o_w2, rows, (int64_t)N * N * KT, N * N * KT, F(w.thb), gr + g.o_thb, gr + g.o_gb,
                          bwd_rows, (int64_t)E, E, st));
         // (the finalize kernel reads the cells and the squared errors only -- nothing the side stream writes: it runs in front of the join,
         // beside the side stream's last product, instead of behind the wake-up of a stream that sat waiting)
         hipLaunchKernelGGL(ast_finalize_kernel, dim3(1), dim3(AB), 0, st, g, fin);
-        AST_RC(fk.join());
+        RULGNN_TRY(fk.join());
     }
     return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
 }
@@ -968,7 +952,7 @@ int astgcnn_run(const rulgnn_astgcnn_shape* s, const rulgnn_astgcnn_args* a, int
 int astgcnn_bn_running_update(const rulgnn_astgcnn_shape* s, float* bn_stats, const float* bn_batch, int64_t count, float momentum,
                               int from_moments, hipStream_t st) {
     AstGeom g;
-    AST_RC(ast_geometry(s, &g));
+    RULGNN_TRY(ast_geometry(s, &g));
     (void)hipGetLastError();
     hipLaunchKernelGGL(ast_bn_running_kernel, dim3(1), dim3(64), 0, st, bn_stats, bn_batch, g.N, (double)count, momentum, from_moments);
     return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;

@@ -15,7 +15,7 @@
 #include "async_mem.hpp"
 #include "aux_stream.hpp"
 #include "sgemm_mfma.hpp"
-#include "stgcn_host.hpp"
+#include "families_host.hpp"
 
 namespace rulgnn {
 
@@ -357,17 +357,11 @@ size_t bilstm_workspace_bytes(const rulgnn_bilstm_shape* s) {
     return (size_t)g.total * sizeof(float);
 }
 
-#define LS_RC(call)                        \
-    do {                                   \
-        const int rc_ = (call);            \
-        if (rc_ != RULGNN_OK) return rc_;  \
-    } while (0)
-
 // ndir = 2: the bidirectional layer of the ABI; ndir = 1: the forward direction alone (nn.LSTM(bidirectional=False), e.g. RGCNU's
 // TDL, models/RGCNU/Model.py:46-53) -- same kernels, half the workgroups, out = h of direction 0
 int bilstm_forward(const rulgnn_bilstm_shape* s, const rulgnn_bilstm_args* a, hipStream_t st, int ndir) {
     LstmGeom g;
-    LS_RC(lstm_geometry(s, &g));
+    RULGNN_TRY(lstm_geometry(s, &g));
     if (a->workspace_bytes < (size_t)g.total * sizeof(float)) return RULGNN_EWORKSPACE;
     float* ws = static_cast<float*>(a->workspace);
     (void)hipGetLastError();
@@ -375,7 +369,7 @@ int bilstm_forward(const rulgnn_bilstm_shape* s, const rulgnn_bilstm_args* a, hi
     // input projections of both directions: gi[dir] = x W_ih[dir]^T   ([rows, I] x [I, 4H])
     if (ndir != 1 && ndir != 2) return RULGNN_EINVAL;
     for (int d = 0; d < ndir; ++d)
-        LS_RC(sgemm(a->x, g.I, 1, a->w_ih[d], g.I, 1, ws + g.o_gi + (int64_t)d * g.rows * g.H4, g.H4, R, g.H4, g.I, false, st));
+        RULGNN_TRY(sgemm(a->x, g.I, 1, a->w_ih[d], g.I, 1, ws + g.o_gi + (int64_t)d * g.rows * g.H4, g.H4, R, g.H4, g.I, false, st));
     const int threads = (g.H4 + 63) & ~63;
     const int d1 = ndir == 2 ? 1 : 0;                 // the one-direction launch never selects direction 1
     auto fwd = [&](auto kernel) {
@@ -394,7 +388,7 @@ int bilstm_forward(const rulgnn_bilstm_shape* s, const rulgnn_bilstm_args* a, hi
 
 int bilstm_backward(const rulgnn_bilstm_shape* s, const rulgnn_bilstm_args* a, hipStream_t st, int ndir) {
     LstmGeom g;
-    LS_RC(lstm_geometry(s, &g));
+    RULGNN_TRY(lstm_geometry(s, &g));
     if (a->workspace_bytes < (size_t)g.total * sizeof(float)) return RULGNN_EWORKSPACE;
     float* ws = static_cast<float*>(a->workspace);
     (void)hipGetLastError();
@@ -416,7 +410,7 @@ int bilstm_backward(const rulgnn_bilstm_shape* s, const rulgnn_bilstm_args* a, h
     // The data gradient first: the layer below waits for nothing else.  dx (+)= dG W_ih
     if (a->dx)
         for (int d = 0; d < ndir; ++d)
-            LS_RC(sgemm(ws + g.o_dgates + (int64_t)d * g.rows * H4, H4, 1, a->w_ih[d], 1, I, a->dx, I, R, I, H4, d == 1, st));
+            RULGNN_TRY(sgemm(ws + g.o_dgates + (int64_t)d * g.rows * H4, H4, 1, a->w_ih[d], 1, I, a->dx, I, R, I, H4, d == 1, st));
     // The parameter gradients feed nothing in this call: on the caller's second stream (args->aux_stream) they run beside what the caller
     // enqueues on `st` next -- in a stack of layers the BPTT of the layer below, a persistent recurrence on 2 * num_seq of the CUs.
     // NOT joined here: the caller joins before it reads them (include/rulgnn.h).
@@ -437,7 +431,7 @@ int bilstm_backward(const rulgnn_bilstm_shape* s, const rulgnn_bilstm_args* a, h
         jobs[nj++] = SplitKJob{one, 0, 0, dg, 1, H4, a->db_ih[d], H4, 1, H4, R};
         jobs[nj++] = SplitKJob{one, 0, 0, dg, 1, H4, a->db_hh[d], H4, 1, H4, R};
     }
-    if (R > 0) LS_RC(sgemm_splitk_batch(jobs, nj, split, (size_t)g.o_split_floats, wst));
+    if (R > 0) RULGNN_TRY(sgemm_splitk_batch(jobs, nj, split, (size_t)g.o_split_floats, wst));
     else
         for (int j = 0; j < nj; ++j)
             if (hipMemsetAsync(jobs[j].C, 0, sizeof(float) * (size_t)jobs[j].M * jobs[j].N, wst) != hipSuccess) return RULGNN_EHIP;

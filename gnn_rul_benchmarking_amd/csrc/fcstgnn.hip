@@ -17,7 +17,7 @@
 #include "async_mem.hpp"
 #include "aux_stream.hpp"
 #include "sgemm_mfma.hpp"
-#include "stgcn_host.hpp"
+#include "families_host.hpp"
 
 namespace rulgnn {
 
@@ -1949,10 +1949,9 @@ struct FcWs {
 };
 
 void fc_ws_layout(const FcGeom& g, FcWs* w) {
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    size_t o = 0;
-    auto take = [&](size_t floats) { const size_t r = o; o = al(o + floats * sizeof(float)); return r; };
-    w->cells = o; o = al(o + sizeof(Cells) * CELL_REP);
+    WsCarver c;
+    auto take = [&](size_t floats) { return c.take<float>(floats); };
+    w->cells = c.take_bytes(sizeof(Cells) * CELL_REP);
     w->one = take(64);
     const size_t M = (size_t)g.M, B = (size_t)g.B;
     w->z1 = take(M * g.H1 * g.L1);
@@ -2008,7 +2007,7 @@ void fc_ws_layout(const FcGeom& g, FcWs* w) {
     }
     w->split_floats = mx;
     w->split = take(mx);
-    w->total = o;
+    w->total = c.total();
 }
 
 // streaming kernels: at most this many workgroups (each ends in one fp64 atomic per channel onto the statistics cells; 4096 workgroups
@@ -2040,17 +2039,11 @@ size_t fcstgnn_workspace_bytes(const rulgnn_fcstgnn_shape* s) {
     return w.total;
 }
 
-#define FC_RC(call)                        \
-    do {                                   \
-        const int rc_ = (call);            \
-        if (rc_ != RULGNN_OK) return rc_;  \
-    } while (0)
-
 // mode bit 0: forward (args->training selects batch / running statistics), bit 1: backward
 int fcstgnn_run(const rulgnn_fcstgnn_shape* s, const rulgnn_fcstgnn_args* a, int mode, hipStream_t st, const FcstgnnSync* sync, float* bn_running_out,
                 float bn_momentum, const AdamFuse* fuse) {
     FcGeom g;
-    FC_RC(fc_geometry(s, &g));
+    RULGNN_TRY(fc_geometry(s, &g));
     if (sync) {
         // every BatchNorm normalises by the statistics of the GLOBAL batch: the cells are all-reduced between the kernel that
         // completes a pair and its first reader, and the element counts are those of the global batch
@@ -2061,9 +2054,9 @@ int fcstgnn_run(const rulgnn_fcstgnn_shape* s, const rulgnn_fcstgnn_args* a, int
     FcWs w;
     fc_ws_layout(g, &w);
     if (a->workspace_bytes < w.total) return RULGNN_EWORKSPACE;
-    char* ws = static_cast<char*>(a->workspace);
-    auto P_ = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-    Cells* cells = reinterpret_cast<Cells*>(ws + w.cells);
+    const Workspace ws(a->workspace);
+    auto P_ = [&](size_t off) { return ws.at<float>(off); };
+    Cells* cells = ws.at<Cells>(w.cells);
     const float* prm = a->params;
     const float* run = a->bn_stats;
     const int training = a->training ? 1 : 0;
@@ -2089,13 +2082,9 @@ int fcstgnn_run(const rulgnn_fcstgnn_shape* s, const rulgnn_fcstgnn_args* a, int
     };
     // positional-encoding dropout (train mode only)
     const float p = training ? a->dropout_p : 0.f;
-    uint32_t thr = 0;
-    if (p > 0.f) {
-        const double t = (double)p * 4294967296.0;
-        const uint64_t ti = (uint64_t)(t + 0.5);
-        thr = ti > 4294967295ull ? 4294967295u : (uint32_t)ti;
-    }
-    const float dscale = p > 0.f ? 1.0f / (1.0f - p) : 1.0f;
+    const DropoutConst drop = dropout_const(p);
+    const uint32_t thr = drop.thr;
+    const float dscale = drop.scale;
     const uint32_t key = dropout_layer_key(a->seed, a->step, 0);
     const uint32_t* key_dev = a->step_state ? static_cast<const StepState*>(a->step_state)->drop_key : nullptr;
     const int64_t row_off = a->sample_offset * g.NP * g.N;
@@ -2109,35 +2098,35 @@ int fcstgnn_run(const rulgnn_fcstgnn_shape* s, const rulgnn_fcstgnn_args* a, int
     };
 
     if (mode & 1) {
-        if (training && a->step_state) FC_RC(step_prepare_dropout(a->step_state, a->seed, 1, st));
+        if (training && a->step_state) RULGNN_TRY(step_prepare_dropout(a->step_state, a->seed, 1, st));
         if (hipMemsetAsync(cells, 0, sizeof(Cells) * CELL_REP, st) != hipSuccess) return RULGNN_EHIP;
         // (the reference's C-MAPSS wiring has its own instantiations: shapes as compile-time constants)
         const bool fd004_conv = g.K == 2 && g.L1 == 3 && g.L2 == 4 && g.H1 == 8 && g.CO == 6;
         const bool fd004_in = fd004_conv && g.N == 14 && g.NP == 25 && g.PS == 2 && g.TL == 50;
         if (fd004_in) hipLaunchKernelGGL(fc_conv1_kernel<true>, dim3(grid_for(g.M * g.H1 * g.L1)), dim3(FB), 0, st, g, a->x, prm, P_(w.z1), cells, training);
         else hipLaunchKernelGGL(fc_conv1_kernel<false>, dim3(grid_for(g.M * g.H1 * g.L1)), dim3(FB), 0, st, g, a->x, prm, P_(w.z1), cells, training);
-        FC_RC(sync_pair(0, 0));
+        RULGNN_TRY(sync_pair(0, 0));
         if (fd004_conv)
             hipLaunchKernelGGL((fc_conv2_kernel<2, 3, 4, 8, 6>), dim3(grid_for(g.M * CL)), dim3(FB), 0, st, g, prm, run, (const float*)P_(w.z1), P_(w.z2),
                                cells, training);
         else
             hipLaunchKernelGGL((fc_conv2_kernel<0, 0, 0, 0, 0>), dim3(grid_for(g.M * CL)), dim3(FB), 0, st, g, prm, run, (const float*)P_(w.z1), P_(w.z2),
                                cells, training);
-        FC_RC(sync_pair(0, 1));
+        RULGNN_TRY(sync_pair(0, 1));
         if (proj_fused) {
             hipLaunchKernelGGL(fc_proj3_kernel, dim3(grid_for(g.M * CL)), dim3(FB), proj_lds, st, g, prm, run, cells, training,
                                (const float*)P_(w.z2), P_(w.a2), P_(w.z3));
         } else {
             hipLaunchKernelGGL(fc_act2_kernel, dim3(grid_for(g.M * CL)), dim3(FB), 0, st, g, prm, run, (const Cells*)cells, training,
                                (const float*)P_(w.z2), P_(w.a2));
-            FC_RC(sgemm(P_(w.a2), CL, 1, prm + g.o_W3, CL, 1, P_(w.z3), D2, Mi, D2, CL, false, st, bf));
+            RULGNN_TRY(sgemm(P_(w.a2), CL, 1, prm + g.o_W3, CL, 1, P_(w.z3), D2, Mi, D2, CL, false, st, bf));
             hipLaunchKernelGGL(fc_bias_stats_kernel, dim3(grid_for(g.M * D2)), dim3(FB), 0, st, P_(w.z3), prm + g.o_b3, g.M, D2, cells, 2, training);
         }
-        FC_RC(sync_pair(0, 2));
+        RULGNN_TRY(sync_pair(0, 2));
         hipLaunchKernelGGL(fc_pe_kernel, dim3(grid_for(g.M * D2)), dim3(FB), 0, st, g, prm, run, cells, training, (const float*)P_(w.z3),
                            P_(w.F), thr, dscale, key, key_dev, row_off);
-        FC_RC(sync_pair(0, 3));
-        FC_RC(sync_pair(0, 5));
+        RULGNN_TRY(sync_pair(0, 3));
+        RULGNN_TRY(sync_pair(0, 5));
         const int64_t Gmax = g.G[0] > g.G[1] ? g.G[0] : g.G[1];
         const bool block_fused = graph_mx && D2 == 2 * HD;
         if (block_fused) {
@@ -2155,14 +2144,14 @@ int fcstgnn_run(const rulgnn_fcstgnn_shape* s, const rulgnn_fcstgnn_args* a, int
             // (compute_dtype = bf16: the four products of a window graph on bf16 matrix instructions, fc_prod)
             if (D2 == 16) { if (bf) go(fc_block_mx_kernel<16, true>); else go(fc_block_mx_kernel<16, false>); }
             else { if (bf) go(fc_block_mx_kernel<32, true>); else go(fc_block_mx_kernel<32, false>); }
-            FC_RC(sync_pair(0, 4));
-            FC_RC(sync_pair(0, 6));
+            RULGNN_TRY(sync_pair(0, 4));
+            RULGNN_TRY(sync_pair(0, 6));
         }
         for (int b = 0; b < 2 && !block_fused; ++b) {
             const int GQ = (int)(g.G[b] * g.Q);
             const unsigned wgs = (unsigned)((g.G[b] + FC_MX_WAVES - 1) / FC_MX_WAVES);
             {
-                FC_RC(sgemm(P_(w.F), D2, 1, prm + g.o_map[b], D2, 1, P_(w.Mm[b]), D2, Mi, D2, D2, false, st, bf));
+                RULGNN_TRY(sgemm(P_(w.F), D2, 1, prm + g.o_map[b], D2, 1, P_(w.Mm[b]), D2, Mi, D2, D2, false, st, bf));
                 if (graph_mx) {
                     auto go = [&](auto kernel) {
                         hipLaunchKernelGGL(kernel, dim3(wgs < 4096 ? wgs : 4096), dim3(64 * FC_MX_WAVES), 0, st, g, b, prm, run, (const Cells*)cells, training,
@@ -2175,23 +2164,23 @@ int fcstgnn_run(const rulgnn_fcstgnn_shape* s, const rulgnn_fcstgnn_args* a, int
                                        sizeof(float) * (2 * g.Q * (g.D2 + 1) + g.Q * (g.Q + 1)), st, g, b, prm, run, (const Cells*)cells, training,
                                        (const float*)P_(w.F), (const float*)P_(w.Mm[b]), P_(w.P[b]), P_(w.AX[b]));
                 }
-                FC_RC(sgemm(P_(w.AX[b]), D2, 1, prm + g.o_th[b], D2, 1, P_(w.z5[b]), HD, GQ, HD, D2, false, st, bf));
+                RULGNN_TRY(sgemm(P_(w.AX[b]), D2, 1, prm + g.o_th[b], D2, 1, P_(w.z5[b]), HD, GQ, HD, D2, false, st, bf));
                 hipLaunchKernelGGL(fc_bias_stats_kernel, dim3(grid_for((int64_t)GQ * HD)), dim3(FB), 0, st, P_(w.z5[b]), prm + g.o_thb[b],
                                    (int64_t)GQ, HD, cells, 4 + 2 * b, training);
             }
-            FC_RC(sync_pair(0, 4 + 2 * b));
+            RULGNN_TRY(sync_pair(0, 4 + 2 * b));
         }
         hipLaunchKernelGGL(fc_pool_kernel, dim3(grid_for(Gmax * g.N * HD), 2), dim3(FB), 0, st, g, prm, run, (const Cells*)cells, training,
                            CPtr2{{P_(w.z5[0]), P_(w.z5[1])}}, P_(w.feat));
         // K = FIN (4032 at FD004) against a [batch x 16] output: split the reduction, or four workgroups walk it alone (250 us)
-        FC_RC(sgemm_splitk(P_(w.feat), FIN, 1, prm + g.o_f1w, FIN, 1, P_(w.h1), D2, Bi, D2, FIN, false, P_(w.split), st));
+        RULGNN_TRY(sgemm_splitk(P_(w.feat), FIN, 1, prm + g.o_f1w, FIN, 1, P_(w.h1), D2, Bi, D2, FIN, false, P_(w.split), st));
         if (mlp_fused) {
             mlp_tail(1, a->y, nullptr);
         } else {
             hipLaunchKernelGGL(fc_bias_relu_kernel, dim3(grid_for(g.B * D2)), dim3(FB), 0, st, P_(w.h1), prm + g.o_f1b, g.B, D2);
-            FC_RC(sgemm(P_(w.h1), D2, 1, prm + g.o_f2w, D2, 1, P_(w.h2), D2, Bi, D2, D2, false, st, bf));
+            RULGNN_TRY(sgemm(P_(w.h1), D2, 1, prm + g.o_f2w, D2, 1, P_(w.h2), D2, Bi, D2, D2, false, st, bf));
             hipLaunchKernelGGL(fc_bias_relu_kernel, dim3(grid_for(g.B * D2)), dim3(FB), 0, st, P_(w.h2), prm + g.o_f2b, g.B, D2);
-            FC_RC(sgemm(P_(w.h2), D2, 1, prm + g.o_f3w, D2, 1, P_(w.h3), HD, Bi, HD, D2, false, st, bf));
+            RULGNN_TRY(sgemm(P_(w.h2), D2, 1, prm + g.o_f3w, D2, 1, P_(w.h3), HD, Bi, HD, D2, false, st, bf));
             hipLaunchKernelGGL(fc_bias_relu_kernel, dim3(grid_for(g.B * HD)), dim3(FB), 0, st, P_(w.h3), prm + g.o_f3b, g.B, HD);
             hipLaunchKernelGGL(fc_head_kernel, dim3((unsigned)((g.B + FB - 1) / FB)), dim3(FB), 0, st, g, prm, (const float*)P_(w.h3), a->y,
                                (const float*)nullptr, a->pred, P_(w.dpred), P_(w.sqerr), P_(w.dh3), inv_gb, 0);
@@ -2218,7 +2207,7 @@ int fcstgnn_run(const rulgnn_fcstgnn_shape* s, const rulgnn_fcstgnn_args* a, int
         fork();
         // (the host enqueues in program order: the MAIN stream's next kernel goes out before the dozen side-stream launches behind this fork
         // -- with the side launches first the main queue sat empty for ~30 us while the host enqueued them; same at every fork below)
-        if (mlp_fused) FC_RC(sgemm(P_(w.dh1), D2, 1, prm + g.o_f1w, 1, FIN, P_(w.dfeat), FIN, Bi, FIN, D2, false, st, bf));
+        if (mlp_fused) RULGNN_TRY(sgemm(P_(w.dh1), D2, 1, prm + g.o_f1w, 1, FIN, P_(w.dfeat), FIN, Bi, FIN, D2, false, st, bf));
         if ((mode & 1) && training && a->bn_batch)
             hipLaunchKernelGGL(fc_side_head_kernel, dim3(1), dim3(64), 0, wst, g, (const Cells*)cells, one, a->bn_batch, a->bn_moment_weight,
                                (bn_running_out && a->bn_moment_weight == 0.f) ? bn_running_out : (float*)nullptr, bn_momentum);
@@ -2241,42 +2230,42 @@ int fcstgnn_run(const rulgnn_fcstgnn_shape* s, const rulgnn_fcstgnn_args* a, int
             k.loss = (!a->dpred && a->loss) ? a->loss : nullptr;
             // (d fc1.weight [2h x FIN] stays on the split-K matrix-core pair: as 64-column workgroups walking the batch in order it took
             // ~90 us at batch 256 -- a chain of 256 dependent-latency iterations -- and the side stream is nearly as long as the main one)
-            FC_RC(sgemm_splitk(P_(w.dh1), 1, D2, P_(w.feat), 1, FIN, gr + g.o_f1w, FIN, D2, FIN, Bi, false, split, wst));
+            RULGNN_TRY(sgemm_splitk(P_(w.dh1), 1, D2, P_(w.feat), 1, FIN, gr + g.o_f1w, FIN, D2, FIN, Bi, false, split, wst));
             k.B = Bi; k.D2 = D2; k.HD = HD; k.FIN = FIN; k.nfw = 0;
             const int small = D2 * D2 + HD * D2 + HD + D2 + D2 + HD + 2;
             hipLaunchKernelGGL(fc_mlp_wgrad_kernel, dim3((unsigned)(k.nfw + (small + 255) / 256)), dim3(256), 0, wst, k);
         } else if (mlp_fused) {
             // d h3, d h2, d h1 are there (formed with the loss in the forward's fused MLP kernel, or here from the incoming gradient):
             // one fork, every parameter gradient of the MLP on the side
-            FC_RC(sgemm_splitk(P_(w.dpred), 0, 1, P_(w.h3), 1, HD, gr + g.o_f4w, HD, 1, HD, Bi, false, split, wst));
-            FC_RC(colsum(P_(w.dpred), g.B, 1, gr + g.o_f4b));
-            FC_RC(sgemm_splitk(P_(w.dh3), 1, HD, P_(w.h2), 1, D2, gr + g.o_f3w, D2, HD, D2, Bi, false, split, wst));
-            FC_RC(colsum(P_(w.dh3), g.B, HD, gr + g.o_f3b));
-            FC_RC(sgemm_splitk(P_(w.dh2), 1, D2, P_(w.h1), 1, D2, gr + g.o_f2w, D2, D2, D2, Bi, false, split, wst));
-            FC_RC(colsum(P_(w.dh2), g.B, D2, gr + g.o_f2b));
-            FC_RC(sgemm_splitk(P_(w.dh1), 1, D2, P_(w.feat), 1, FIN, gr + g.o_f1w, FIN, D2, FIN, Bi, false, split, wst));
-            FC_RC(colsum(P_(w.dh1), g.B, D2, gr + g.o_f1b));
+            RULGNN_TRY(sgemm_splitk(P_(w.dpred), 0, 1, P_(w.h3), 1, HD, gr + g.o_f4w, HD, 1, HD, Bi, false, split, wst));
+            RULGNN_TRY(colsum(P_(w.dpred), g.B, 1, gr + g.o_f4b));
+            RULGNN_TRY(sgemm_splitk(P_(w.dh3), 1, HD, P_(w.h2), 1, D2, gr + g.o_f3w, D2, HD, D2, Bi, false, split, wst));
+            RULGNN_TRY(colsum(P_(w.dh3), g.B, HD, gr + g.o_f3b));
+            RULGNN_TRY(sgemm_splitk(P_(w.dh2), 1, D2, P_(w.h1), 1, D2, gr + g.o_f2w, D2, D2, D2, Bi, false, split, wst));
+            RULGNN_TRY(colsum(P_(w.dh2), g.B, D2, gr + g.o_f2b));
+            RULGNN_TRY(sgemm_splitk(P_(w.dh1), 1, D2, P_(w.feat), 1, FIN, gr + g.o_f1w, FIN, D2, FIN, Bi, false, split, wst));
+            RULGNN_TRY(colsum(P_(w.dh1), g.B, D2, gr + g.o_f1b));
         } else {
         fork();
         if (a->dpred)
             hipLaunchKernelGGL(fc_head_kernel, dim3((unsigned)((g.B + FB - 1) / FB)), dim3(FB), 0, st, g, prm, (const float*)P_(w.h3),
                                (const float*)nullptr, a->dpred, a->pred, P_(w.dpred), P_(w.sqerr), P_(w.dh3), inv_gb, 1);
-        FC_RC(sgemm_splitk(P_(w.dpred), 0, 1, P_(w.h3), 1, HD, gr + g.o_f4w, HD, 1, HD, Bi, false, split, wst));
-        FC_RC(sgemm_splitk(P_(w.dpred), 0, 1, one, 0, 0, gr + g.o_f4b, 1, 1, 1, Bi, false, split, wst));
-        FC_RC(sgemm_splitk(P_(w.dh3), 1, HD, P_(w.h2), 1, D2, gr + g.o_f3w, D2, HD, D2, Bi, false, split, wst));
-        FC_RC(colsum(P_(w.dh3), g.B, HD, gr + g.o_f3b));
-        FC_RC(sgemm(P_(w.dh3), HD, 1, prm + g.o_f3w, 1, D2, P_(w.dh2), D2, Bi, D2, HD, false, st, bf));
+        RULGNN_TRY(sgemm_splitk(P_(w.dpred), 0, 1, P_(w.h3), 1, HD, gr + g.o_f4w, HD, 1, HD, Bi, false, split, wst));
+        RULGNN_TRY(sgemm_splitk(P_(w.dpred), 0, 1, one, 0, 0, gr + g.o_f4b, 1, 1, 1, Bi, false, split, wst));
+        RULGNN_TRY(sgemm_splitk(P_(w.dh3), 1, HD, P_(w.h2), 1, D2, gr + g.o_f3w, D2, HD, D2, Bi, false, split, wst));
+        RULGNN_TRY(colsum(P_(w.dh3), g.B, HD, gr + g.o_f3b));
+        RULGNN_TRY(sgemm(P_(w.dh3), HD, 1, prm + g.o_f3w, 1, D2, P_(w.dh2), D2, Bi, D2, HD, false, st, bf));
         hipLaunchKernelGGL(fc_relu_mask_kernel, dim3(grid_for(g.B * D2)), dim3(FB), 0, st, P_(w.dh2), (const float*)P_(w.h2), g.B * D2);
         fork();
-        FC_RC(sgemm_splitk(P_(w.dh2), 1, D2, P_(w.h1), 1, D2, gr + g.o_f2w, D2, D2, D2, Bi, false, split, wst));
-        FC_RC(colsum(P_(w.dh2), g.B, D2, gr + g.o_f2b));
-        FC_RC(sgemm(P_(w.dh2), D2, 1, prm + g.o_f2w, 1, D2, P_(w.dh1), D2, Bi, D2, D2, false, st, bf));
+        RULGNN_TRY(sgemm_splitk(P_(w.dh2), 1, D2, P_(w.h1), 1, D2, gr + g.o_f2w, D2, D2, D2, Bi, false, split, wst));
+        RULGNN_TRY(colsum(P_(w.dh2), g.B, D2, gr + g.o_f2b));
+        RULGNN_TRY(sgemm(P_(w.dh2), D2, 1, prm + g.o_f2w, 1, D2, P_(w.dh1), D2, Bi, D2, D2, false, st, bf));
         hipLaunchKernelGGL(fc_relu_mask_kernel, dim3(grid_for(g.B * D2)), dim3(FB), 0, st, P_(w.dh1), (const float*)P_(w.h1), g.B * D2);
         fork();
-        FC_RC(sgemm_splitk(P_(w.dh1), 1, D2, P_(w.feat), 1, FIN, gr + g.o_f1w, FIN, D2, FIN, Bi, false, split, wst));
-        FC_RC(colsum(P_(w.dh1), g.B, D2, gr + g.o_f1b));
+        RULGNN_TRY(sgemm_splitk(P_(w.dh1), 1, D2, P_(w.feat), 1, FIN, gr + g.o_f1w, FIN, D2, FIN, Bi, false, split, wst));
+        RULGNN_TRY(colsum(P_(w.dh1), g.B, D2, gr + g.o_f1b));
         }
-        if (!mlp_fused) FC_RC(sgemm(P_(w.dh1), D2, 1, prm + g.o_f1w, 1, FIN, P_(w.dfeat), FIN, Bi, FIN, D2, false, st, bf));
+        if (!mlp_fused) RULGNN_TRY(sgemm(P_(w.dh1), D2, 1, prm + g.o_f1w, 1, FIN, P_(w.dfeat), FIN, Bi, FIN, D2, false, st, bf));
         // ---- graph blocks ----
         // (both window blocks in each launch: blockIdx.y)
         {
@@ -2286,14 +2275,14 @@ int fcstgnn_run(const rulgnn_fcstgnn_shape* s, const rulgnn_fcstgnn_args* a, int
             const Ptr2 dz5p{{P_(w.dz5[0]), P_(w.dz5[1])}};
             hipLaunchKernelGGL(fc_pool_bwd_kernel, dim3(grid_for(Gmax * g.Q * HD), 2), dim3(FB), 0, st, g, prm, cells, z5p,
                                (const float*)P_(w.dfeat), dz5p);
-            FC_RC(sync_pair(1, 4));
-            FC_RC(sync_pair(1, 6));
+            RULGNN_TRY(sync_pair(1, 4));
+            RULGNN_TRY(sync_pair(1, 6));
             hipLaunchKernelGGL(fc_bn_rows_bwd_kernel, dim3(grid_for(Gmax * g.Q * HD), 2), dim3(FB), 0, st, g, 4, prm, (const Cells*)cells, z5p, dz5p,
                                GQ0, GQ1);
             const bool bwd_fused = graph_mx && D2 == 2 * HD;          // d AX = d z5 W_theta inside the graph kernel
             if (!bwd_fused)
                 for (int b = 0; b < 2; ++b)
-                    FC_RC(sgemm(P_(w.dz5[b]), HD, 1, prm + g.o_th[b], 1, D2, P_(w.dAX[b]), D2, (int)(g.G[b] * g.Q), D2, HD, false, st, bf));
+                    RULGNN_TRY(sgemm(P_(w.dz5[b]), HD, 1, prm + g.o_th[b], 1, D2, P_(w.dAX[b]), D2, (int)(g.G[b] * g.Q), D2, HD, false, st, bf));
             // (the per-graph d mapping blocks have their own buffer: the theta gradient, possibly on the other stream, still reads AX[b])
             if (graph_mx) {
                 const unsigned wgs = (unsigned)((Gmax + FC_MX_WAVES - 1) / FC_MX_WAVES);
@@ -2330,15 +2319,15 @@ int fcstgnn_run(const rulgnn_fcstgnn_shape* s, const rulgnn_fcstgnn_args* a, int
         }
         hipLaunchKernelGGL(fc_feat_stats_kernel, dim3(grid_for(g.M * D2)), dim3(FB), 0, st, g, prm, cells, (const float*)P_(w.F),
                            (const float*)P_(w.gX[0]), (const float*)P_(w.gX[1]));
-        FC_RC(sync_pair(1, 3));
-        FC_RC(sync_pair(1, 5));
+        RULGNN_TRY(sync_pair(1, 3));
+        RULGNN_TRY(sync_pair(1, 5));
         // window BatchNorms' backward + both d M W_map products + positional encoding / dropout backward: one launch
         hipLaunchKernelGGL(fc_feat_pe_bwd_kernel, dim3(grid_for(g.M * D2)), dim3(FB), 0, st, g, prm, cells, (const float*)P_(w.F),
                            (const float*)P_(w.gX[0]), (const float*)P_(w.gX[1]), (const float*)P_(w.gM[0]), (const float*)P_(w.gM[1]),
                            (const float*)P_(w.z3), P_(w.dF), thr, dscale, key, key_dev, row_off);
         for (int b = 0; b < 2; ++b)
             wjobs[nwj++] = SplitKColsumJob{P_(w.gM[b]), 1, D2, P_(w.F), 1, D2, gr + g.o_map[b], D2, D2, D2, Mi, gr + g.o_bmap[b]};
-        FC_RC(sync_pair(1, 2));
+        RULGNN_TRY(sync_pair(1, 2));
         hipLaunchKernelGGL(fc_bn_rows_bwd_kernel, dim3(grid_for(g.M * D2)), dim3(FB), 0, st, g, 2, prm, (const Cells*)cells,
                            CPtr2{{P_(w.z3), nullptr}}, Ptr2{{P_(w.dF), nullptr}}, g.M, (int64_t)0);
         fork();
@@ -2347,13 +2336,13 @@ int fcstgnn_run(const rulgnn_fcstgnn_shape* s, const rulgnn_fcstgnn_args* a, int
             hipLaunchKernelGGL(fc_proj3_bwd_kernel, dim3(grid_for(g.M * CL)), dim3(FB), proj_lds, st, g, prm, cells, (const float*)P_(w.z2),
                                (const float*)P_(w.a2), (const float*)P_(w.dF), P_(w.da2));
         } else {
-            FC_RC(sgemm(P_(w.dF), D2, 1, prm + g.o_W3, 1, CL, P_(w.da2), CL, Mi, CL, D2, false, st, bf));
+            RULGNN_TRY(sgemm(P_(w.dF), D2, 1, prm + g.o_W3, 1, CL, P_(w.da2), CL, Mi, CL, D2, false, st, bf));
             hipLaunchKernelGGL(fc_act2_bwd_kernel, dim3(grid_for(g.M * CL)), dim3(FB), 0, st, g, prm, cells, (const float*)P_(w.z2),
                                (const float*)P_(w.a2), P_(w.da2));
         }
         wjobs[nwj++] = SplitKColsumJob{P_(w.dF), 1, D2, P_(w.a2), 1, CL, gr + g.o_W3, CL, D2, CL, Mi, gr + g.o_b3};
-        FC_RC(sgemm_splitk_colsum_batch(wjobs, nwj, one, split, w.split_floats, wst));
-        FC_RC(sync_pair(1, 1));
+        RULGNN_TRY(sgemm_splitk_colsum_batch(wjobs, nwj, one, split, w.split_floats, wst));
+        RULGNN_TRY(sync_pair(1, 1));
         // (BatchNorm 1's and BatchNorm 0's channel-major backward passes ride in the loads of the kernels that consume them)
         // the second convolution's weight gradient needs d z2 (final here) and the forward statistics only: beside the rest of the chain
         const int rows = (int)(g.M < w.rows ? g.M : w.rows);
@@ -2364,7 +2353,7 @@ int fcstgnn_run(const rulgnn_fcstgnn_shape* s, const rulgnn_fcstgnn_args* a, int
         else
             hipLaunchKernelGGL((fc_conv2_dx_kernel<0, 0, 0, 0, 0>), dim3(grid_for(g.M * g.H1 * g.L1)), dim3(FB), 0, st, g, prm, cells,
                                (const float*)P_(w.z1), (const float*)P_(w.da2), P_(w.dy1), (const float*)P_(w.z2));
-        FC_RC(sync_pair(1, 0));
+        RULGNN_TRY(sync_pair(1, 0));
         // both convolutions' weight gradients (the second one's needs d z2 only, but the side stream is the longer one by then)
         if (fd004_conv)
             hipLaunchKernelGGL((fc_conv_wgrad_both_kernel<2, 3, 4, 8, 6>), dim3(rows, 2), dim3(FB), 0, st, g, a->x, prm, (const Cells*)cells,
@@ -2380,11 +2369,11 @@ int fcstgnn_run(const rulgnn_fcstgnn_shape* s, const rulgnn_fcstgnn_args* a, int
         const bool with_adam = fuse && fuse->p && !sync;
         AdamFuse none{};
         none.p = nullptr;
-        if (with_adam) FC_RC(fk.join());
+        if (with_adam) RULGNN_TRY(fk.join());
         hipLaunchKernelGGL(fc_finalize_kernel, dim3(nfin + (with_adam ? (g.nparam + FB - 1) / FB : 0)), dim3(FB), 0, st, g,
                            (const float*)P_(w.gp1), (const float*)P_(w.gp2), rows, (const Cells*)cells, gr, sync ? sync->bn_param_grad_scale : 1.0f,
                            with_adam ? *fuse : none, nfin);
-        FC_RC(fk.join());                                    // the gradient GEMMs are done when the call's work has drained
+        RULGNN_TRY(fk.join());                                    // the gradient GEMMs are done when the call's work has drained
     }
     return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
 }
@@ -2392,7 +2381,7 @@ int fcstgnn_run(const rulgnn_fcstgnn_shape* s, const rulgnn_fcstgnn_args* a, int
 int fcstgnn_bn_running_update(const rulgnn_fcstgnn_shape* s, float* bn_stats, const float* bn_batch, float momentum, int from_moments,
                               hipStream_t st) {
     FcGeom g;
-    FC_RC(fc_geometry(s, &g));
+    RULGNN_TRY(fc_geometry(s, &g));
     (void)hipGetLastError();
     hipLaunchKernelGGL(fc_bn_running_kernel, dim3(1), dim3(64), 0, st, g, bn_stats, bn_batch, momentum, from_moments);
     return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;

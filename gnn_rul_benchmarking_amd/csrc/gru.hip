@@ -12,7 +12,7 @@
 // (recomputes the gates from the saved gi / gh), d h_{t-1} += d gh_t W_hh (GEMM); the weight gradients are four split-K
 // GEMMs over all (sequence, step) rows at the end (fixed reduction order: deterministic).
 #include "sgemm_mfma.hpp"
-#include "stgcn_host.hpp"
+#include "families_host.hpp"
 
 namespace rulgnn {
 
@@ -111,21 +111,20 @@ struct GruWs {
 };
 
 void gru_ws(const GruGeom& g, GruWs* w) {
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    size_t o = 0;
+    WsCarver c;
     const size_t R = (size_t)g.R, S = (size_t)g.S;
-    w->gi = o; o = al(o + R * g.H3 * sizeof(float));           // tape: W_ih x (no bias)
-    w->gh = o; o = al(o + R * g.H3 * sizeof(float));           // tape: W_hh h_{t-1} (no bias), zeros at t = 0
-    w->hprev = o; o = al(o + R * g.H * sizeof(float));         // tape: h_{t-1}
-    w->ghstep = o; o = al(o + S * g.H3 * sizeof(float));
-    w->dgi = o; o = al(o + R * g.H3 * sizeof(float));
-    w->dgh = o; o = al(o + R * g.H3 * sizeof(float));
-    w->dh = o; o = al(o + S * g.H * sizeof(float));
-    w->dgstep = o; o = al(o + S * g.H3 * sizeof(float));
-    w->one = o; o = al(o + R * sizeof(float));
+    w->gi = c.take<float>(R * g.H3);           // tape: W_ih x (no bias)
+    w->gh = c.take<float>(R * g.H3);           // tape: W_hh h_{t-1} (no bias), zeros at t = 0
+    w->hprev = c.take<float>(R * g.H);         // tape: h_{t-1}
+    w->ghstep = c.take<float>(S * g.H3);
+    w->dgi = c.take<float>(R * g.H3);
+    w->dgh = c.take<float>(R * g.H3);
+    w->dh = c.take<float>(S * g.H);
+    w->dgstep = c.take<float>(S * g.H3);
+    w->one = c.take<float>(R);
     const int mx = g.I > g.H ? g.I : g.H;
-    w->split = o; o = al(o + sgemm_splitk_partial_floats(g.H3, mx) * sizeof(float));
-    w->total = o;
+    w->split = c.take<float>(sgemm_splitk_partial_floats(g.H3, mx));
+    w->total = c.total();
 }
 
 inline unsigned blocks(int64_t n) { return (unsigned)((n + 255) / 256); }
@@ -140,25 +139,23 @@ size_t gru_workspace_bytes(const rulgnn_gru_shape* s) {
     return w.total;
 }
 
-#define GRU_RC(x) do { const int rc_ = (x); if (rc_ != RULGNN_OK) return rc_; } while (0)
-
 int gru_forward(const rulgnn_gru_shape* s, const rulgnn_gru_args* a, hipStream_t st) {
     GruGeom g;
-    GRU_RC(gru_geometry(s, &g));
+    RULGNN_TRY(gru_geometry(s, &g));
     GruWs w;
     gru_ws(g, &w);
     if (!a->workspace || a->workspace_bytes < w.total) return RULGNN_EWORKSPACE;
     if (g.S == 0) return RULGNN_OK;
-    char* ws = static_cast<char*>(a->workspace);
-    auto Fp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    const Workspace ws(a->workspace);
+    auto Fp = [&](size_t off) { return ws.at<float>(off); };
     // gi[row][q] = sum_i x[row][i] W_ih[q][i]
-    GRU_RC(sgemm(a->x, g.I, 1, a->w_ih, g.I, 1, Fp(w.gi), g.H3, (int)g.R, g.H3, g.I, false, st));
+    RULGNN_TRY(sgemm(a->x, g.I, 1, a->w_ih, g.I, 1, Fp(w.gi), g.H3, (int)g.R, g.H3, g.I, false, st));
     if (hipMemsetAsync(Fp(w.gh), 0, (size_t)g.R * g.H3 * sizeof(float), st) != hipSuccess) return RULGNN_EHIP;
     (void)hipGetLastError();
     for (int t = 0; t < g.L; ++t) {
         if (t > 0) {
             // gh[s][q] = sum_j h_{t-1}[s][j] W_hh[q][j]; h_{t-1} = out[s, t-1, :] (row stride L*H)
-            GRU_RC(sgemm(a->out + (int64_t)(t - 1) * g.H, (int64_t)g.L * g.H, 1, a->w_hh, g.H, 1, Fp(w.ghstep), g.H3, (int)g.S, g.H3, g.H,
+            RULGNN_TRY(sgemm(a->out + (int64_t)(t - 1) * g.H, (int64_t)g.L * g.H, 1, a->w_hh, g.H, 1, Fp(w.ghstep), g.H3, (int)g.S, g.H3, g.H,
                          false, st));
             hipLaunchKernelGGL(gru_rows_copy_kernel, dim3(blocks(g.S * g.H3)), dim3(256), 0, st, g, t, (const float*)Fp(w.ghstep), Fp(w.gh), 1);
         }
@@ -170,7 +167,7 @@ int gru_forward(const rulgnn_gru_shape* s, const rulgnn_gru_args* a, hipStream_t
 
 int gru_backward(const rulgnn_gru_shape* s, const rulgnn_gru_args* a, hipStream_t st) {
     GruGeom g;
-    GRU_RC(gru_geometry(s, &g));
+    RULGNN_TRY(gru_geometry(s, &g));
     GruWs w;
     gru_ws(g, &w);
     if (!a->workspace || a->workspace_bytes < w.total) return RULGNN_EWORKSPACE;
@@ -180,8 +177,8 @@ int gru_backward(const rulgnn_gru_shape* s, const rulgnn_gru_args* a, hipStream_
             return RULGNN_EHIP;
         return RULGNN_OK;
     }
-    char* ws = static_cast<char*>(a->workspace);
-    auto Fp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    const Workspace ws(a->workspace);
+    auto Fp = [&](size_t off) { return ws.at<float>(off); };
     (void)hipGetLastError();
     for (int t = g.L - 1; t >= 0; --t) {
         hipLaunchKernelGGL(gru_gate_bwd_kernel, dim3(blocks(g.S * g.H)), dim3(256), 0, st, g, t, (const float*)Fp(w.gi), (const float*)Fp(w.gh),
@@ -189,19 +186,19 @@ int gru_backward(const rulgnn_gru_shape* s, const rulgnn_gru_args* a, hipStream_
         if (t > 0) {
             // dh[s][j] += sum_q dgh_t[s][q] W_hh[q][j]
             hipLaunchKernelGGL(gru_rows_copy_kernel, dim3(blocks(g.S * g.H3)), dim3(256), 0, st, g, t, (const float*)Fp(w.dgh), Fp(w.dgstep), 0);
-            GRU_RC(sgemm(Fp(w.dgstep), g.H3, 1, a->w_hh, 1, g.H, Fp(w.dh), g.H, (int)g.S, g.H, g.H3, true, st));
+            RULGNN_TRY(sgemm(Fp(w.dgstep), g.H3, 1, a->w_hh, 1, g.H, Fp(w.dh), g.H, (int)g.S, g.H, g.H3, true, st));
         }
     }
     hipLaunchKernelGGL(gru_fill_kernel, dim3(blocks(g.R)), dim3(256), 0, st, Fp(w.one), g.R, 1.0f);
     if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
     float* split = Fp(w.split);
     // dW_ih[q][i] = sum_row dgi[row][q] x[row][i];  dW_hh[q][j] = sum_row dgh[row][q] hprev[row][j];  biases: column sums
-    GRU_RC(sgemm_splitk(Fp(w.dgi), 1, g.H3, a->x, 1, g.I, a->dw_ih, g.I, g.H3, g.I, (int)g.R, false, split, st));
-    GRU_RC(sgemm_splitk(Fp(w.dgh), 1, g.H3, Fp(w.hprev), 1, g.H, a->dw_hh, g.H, g.H3, g.H, (int)g.R, false, split, st));
-    GRU_RC(sgemm_splitk(Fp(w.dgi), 1, g.H3, Fp(w.one), 0, 1, a->db_ih, 1, g.H3, 1, (int)g.R, false, split, st));
-    GRU_RC(sgemm_splitk(Fp(w.dgh), 1, g.H3, Fp(w.one), 0, 1, a->db_hh, 1, g.H3, 1, (int)g.R, false, split, st));
+    RULGNN_TRY(sgemm_splitk(Fp(w.dgi), 1, g.H3, a->x, 1, g.I, a->dw_ih, g.I, g.H3, g.I, (int)g.R, false, split, st));
+    RULGNN_TRY(sgemm_splitk(Fp(w.dgh), 1, g.H3, Fp(w.hprev), 1, g.H, a->dw_hh, g.H, g.H3, g.H, (int)g.R, false, split, st));
+    RULGNN_TRY(sgemm_splitk(Fp(w.dgi), 1, g.H3, Fp(w.one), 0, 1, a->db_ih, 1, g.H3, 1, (int)g.R, false, split, st));
+    RULGNN_TRY(sgemm_splitk(Fp(w.dgh), 1, g.H3, Fp(w.one), 0, 1, a->db_hh, 1, g.H3, 1, (int)g.R, false, split, st));
     if (a->dx)   // dx[row][i] = sum_q dgi[row][q] W_ih[q][i]
-        GRU_RC(sgemm(Fp(w.dgi), g.H3, 1, a->w_ih, 1, g.I, a->dx, g.I, (int)g.R, g.I, g.H3, false, st));
+        RULGNN_TRY(sgemm(Fp(w.dgi), g.H3, 1, a->w_ih, 1, g.I, a->dx, g.I, (int)g.R, g.I, g.H3, false, st));
     return RULGNN_OK;
 }
 

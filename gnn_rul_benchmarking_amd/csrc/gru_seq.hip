@@ -17,7 +17,7 @@
 // A operand of d h_{t-1} += d gh_t W_hh (again 48 instructions per wavefront and step); the d gi / d gh rows go to memory and the four
 // weight-gradient products over all (sequence, step) rows are one batched split-K pair at the end (fixed reduction order: deterministic).
 #include "sgemm_mfma.hpp"
-#include "stgcn_host.hpp"
+#include "families_host.hpp"
 
 namespace rulgnn {
 
@@ -215,20 +215,19 @@ void gs_jobs(const GsGeom& g, SplitKJob (&jobs)[4]) {             // shapes only
 }
 
 void gs_ws(const GsGeom& g, GsWs* w) {
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    size_t o = 0;
+    WsCarver c;
     const size_t R = (size_t)g.R;
-    w->gi = o; o = al(o + R * GS_H3 * sizeof(float));            // tape: W_ih x (no bias)
-    w->gh = o; o = al(o + R * GS_H3 * sizeof(float));            // tape: W_hh h_{t-1} (no bias)
-    w->hprev = o; o = al(o + R * GS_H * sizeof(float));          // tape: h_{t-1}
-    w->dgi = o; o = al(o + R * GS_H3 * sizeof(float));
-    w->dgh = o; o = al(o + R * GS_H3 * sizeof(float));
-    w->one = o; o = al(o + (R > 0 ? R : 1) * sizeof(float));
+    w->gi = c.take<float>(R * GS_H3);            // tape: W_ih x (no bias)
+    w->gh = c.take<float>(R * GS_H3);            // tape: W_hh h_{t-1} (no bias)
+    w->hprev = c.take<float>(R * GS_H);          // tape: h_{t-1}
+    w->dgi = c.take<float>(R * GS_H3);
+    w->dgh = c.take<float>(R * GS_H3);
+    w->one = c.take<float>(R > 0 ? R : 1);
     SplitKJob jobs[4];
     gs_jobs(g, jobs);
     w->split_floats = g.R > 0 ? sgemm_splitk_batch_floats(jobs, 4) : 1;
-    w->split = o; o = al(o + w->split_floats * sizeof(float));
-    w->total = o;
+    w->split = c.take<float>(w->split_floats);
+    w->total = c.total();
 }
 
 inline unsigned gs_tiles(const GsGeom& g) { return (unsigned)((g.S + GS_TILE - 1) / GS_TILE); }
@@ -243,19 +242,17 @@ size_t gru_persistent_workspace_bytes(const rulgnn_gru_shape* s) {
     return w.total;
 }
 
-#define GS_RC(x) do { const int rc_ = (x); if (rc_ != RULGNN_OK) return rc_; } while (0)
-
 int gru_persistent_forward(const rulgnn_gru_shape* s, const rulgnn_gru_args* a, hipStream_t st) {
     GsGeom g;
-    GS_RC(gs_geometry(s, &g));
+    RULGNN_TRY(gs_geometry(s, &g));
     GsWs w;
     gs_ws(g, &w);
     if (!a->workspace || a->workspace_bytes < w.total) return RULGNN_EWORKSPACE;
     if (g.S == 0) return RULGNN_OK;
-    char* ws = static_cast<char*>(a->workspace);
-    auto Fp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    const Workspace ws(a->workspace);
+    auto Fp = [&](size_t off) { return ws.at<float>(off); };
     // gi[row][q] = sum_i x[row][i] W_ih[q][i]
-    GS_RC(sgemm(a->x, g.I, 1, a->w_ih, g.I, 1, Fp(w.gi), GS_H3, (int)g.R, GS_H3, g.I, false, st));
+    RULGNN_TRY(sgemm(a->x, g.I, 1, a->w_ih, g.I, 1, Fp(w.gi), GS_H3, (int)g.R, GS_H3, g.I, false, st));
     (void)hipGetLastError();
     hipLaunchKernelGGL(gru_seq_fwd_kernel, dim3(gs_tiles(g)), dim3(GS_BLOCK), 0, st, g, (const float*)Fp(w.gi), a->w_hh, a->b_ih, a->b_hh,
                        a->out, Fp(w.gh), Fp(w.hprev));
@@ -264,7 +261,7 @@ int gru_persistent_forward(const rulgnn_gru_shape* s, const rulgnn_gru_args* a, 
 
 int gru_persistent_backward(const rulgnn_gru_shape* s, const rulgnn_gru_args* a, hipStream_t st) {
     GsGeom g;
-    GS_RC(gs_geometry(s, &g));
+    RULGNN_TRY(gs_geometry(s, &g));
     GsWs w;
     gs_ws(g, &w);
     if (!a->workspace || a->workspace_bytes < w.total) return RULGNN_EWORKSPACE;
@@ -274,8 +271,8 @@ int gru_persistent_backward(const rulgnn_gru_shape* s, const rulgnn_gru_args* a,
             return RULGNN_EHIP;
         return RULGNN_OK;
     }
-    char* ws = static_cast<char*>(a->workspace);
-    auto Fp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    const Workspace ws(a->workspace);
+    auto Fp = [&](size_t off) { return ws.at<float>(off); };
     (void)hipGetLastError();
     hipLaunchKernelGGL(gru_seq_bwd_kernel, dim3(gs_tiles(g)), dim3(GS_BLOCK), 0, st, g, (const float*)Fp(w.gi), (const float*)Fp(w.gh),
                        (const float*)Fp(w.hprev), a->w_hh, a->b_ih, a->b_hh, a->dout, Fp(w.dgi), Fp(w.dgh));
@@ -288,9 +285,9 @@ int gru_persistent_backward(const rulgnn_gru_shape* s, const rulgnn_gru_args* a,
     jobs[1].A = Fp(w.dgh); jobs[1].B = Fp(w.hprev); jobs[1].C = a->dw_hh;
     jobs[2].A = Fp(w.dgi); jobs[2].B = Fp(w.one); jobs[2].C = a->db_ih;
     jobs[3].A = Fp(w.dgh); jobs[3].B = Fp(w.one); jobs[3].C = a->db_hh;
-    GS_RC(sgemm_splitk_batch(jobs, 4, Fp(w.split), w.split_floats, st));
+    RULGNN_TRY(sgemm_splitk_batch(jobs, 4, Fp(w.split), w.split_floats, st));
     if (a->dx)   // dx[row][i] = sum_q dgi[row][q] W_ih[q][i]
-        GS_RC(sgemm(Fp(w.dgi), GS_H3, 1, a->w_ih, 1, g.I, a->dx, g.I, (int)g.R, g.I, GS_H3, false, st));
+        RULGNN_TRY(sgemm(Fp(w.dgi), GS_H3, 1, a->w_ih, 1, g.I, a->dx, g.I, (int)g.R, g.I, GS_H3, false, st));
     return RULGNN_OK;
 }
 

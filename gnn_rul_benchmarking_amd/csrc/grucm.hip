@@ -20,7 +20,7 @@
 // Dropout: the counter hash of the other families (stgcn_device.hpp lowbias32, key = dropout_layer_key(seed, step, site));
 // sites 0, 1: counter (((b + sample_offset) L + t) N + i) h + c; site 2: ((b + sample_offset) L + t) H + c; both mod 2^32.
 #include "sgemm_mfma.hpp"
-#include "stgcn_host.hpp"
+#include "families_host.hpp"
 
 namespace rulgnn {
 
@@ -412,30 +412,29 @@ bool gc_use_persistent(const GcGeom& g, int gru_path) {
 }
 
 void gc_ws(const GcGeom& g, GcWs* w) {
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const size_t G = (size_t)g.G, B = (size_t)(g.B > 0 ? g.B : 1);
-    size_t o = 0;
-    w->pooled = o; o = al(o + G * g.h * sizeof(float));
-    w->hs = o; o = al(o + G * g.H * sizeof(float));
-    w->dhs = o; o = al(o + G * g.H * sizeof(float));
-    w->dpooled = o; o = al(o + G * g.h * sizeof(float));
-    w->dpred = o; o = al(o + B * sizeof(float));
-    w->sqerr = o; o = al(o + B * sizeof(float));
+    WsCarver c;
+    w->pooled = c.take<float>(G * g.h);
+    w->hs = c.take<float>(G * g.H);
+    w->dhs = c.take<float>(G * g.H);
+    w->dpooled = c.take<float>(G * g.h);
+    w->dpred = c.take<float>(B);
+    w->sqerr = c.take<float>(B);
     auto blocks = [&](int blk) {
         const int64_t rounds = (g.G + blk / g.RW - 1) / (blk / g.RW);
         return (int)(rounds < 1 ? 1 : (rounds > GC_MAX_BLOCKS ? GC_MAX_BLOCKS : rounds));
     };
     w->fblocks = blocks(GC_FB);
     w->gblocks = blocks(g.BLKB);
-    w->gpart = o; o = al(o + (size_t)w->gblocks * (4 * g.h * g.h + 4 * g.h) * sizeof(float));
+    w->gpart = c.take<float>((size_t)w->gblocks * (4 * g.h * g.h + 4 * g.h));
     w->hslices = (int)((B + GC_SLICE - 1) / GC_SLICE);
-    w->hpart = o; o = al(o + (size_t)w->hslices * ((size_t)g.L * g.H + 1) * sizeof(float));
+    w->hpart = c.take<float>((size_t)w->hslices * ((size_t)g.L * g.H + 1));
     // the larger of the two recurrences' needs: the path is a per-call switch (rulgnn_grucm_args.gru_path)
     rulgnn_gru_shape gs{g.B, g.L, g.h, g.H};
     const size_t loop = gru_workspace_bytes(&gs), pers = gru_persistent_workspace_bytes(&gs);
     w->gru_bytes = loop > pers ? loop : pers;
-    w->gru = o; o = al(o + w->gru_bytes);
-    w->total = o;
+    w->gru = c.take_bytes(w->gru_bytes);
+    w->total = c.total();
 }
 
 template <int HC, int BLK>
@@ -471,13 +470,11 @@ size_t grucm_workspace_bytes(const rulgnn_grucm_shape* s) {
     return w.gru_bytes == 0 ? 0 : w.total;
 }
 
-#define GC_RC(x) do { const int rc_ = (x); if (rc_ != RULGNN_OK) return rc_; } while (0)
-
 // mode bit 0: forward (pred; with y also d pred and the loss terms), bit 1: backward (gradients; d pred from args->dpred or from the
 // forward of this call)
 int grucm_run(const rulgnn_grucm_shape* s, const rulgnn_grucm_args* a, int mode, hipStream_t st) {
     GcGeom g;
-    GC_RC(gc_geometry(s, &g));
+    RULGNN_TRY(gc_geometry(s, &g));
     GcWs w;
     gc_ws(g, &w);
     if (w.gru_bytes == 0) return RULGNN_EUNSUPPORTED;
@@ -490,18 +487,14 @@ int grucm_run(const rulgnn_grucm_shape* s, const rulgnn_grucm_args* a, int mode,
     }
     GcDrop d{};
     for (int site = 0; site < 3; ++site) {
-        const float p = a->training ? a->dropout_p[site] : 0.f;
-        d.thr[site] = 0;
-        if (p > 0.f) {
-            const uint64_t ti = (uint64_t)((double)p * 4294967296.0 + 0.5);
-            d.thr[site] = ti > 4294967295ull ? 4294967295u : (uint32_t)ti;
-        }
-        d.scale[site] = p > 0.f ? 1.0f / (1.0f - p) : 1.0f;
+        const DropoutConst dc = dropout_const(a->training ? a->dropout_p[site] : 0.f);
+        d.thr[site] = dc.thr;
+        d.scale[site] = dc.scale;
         d.key[site] = dropout_layer_key(a->seed, a->step, site);
     }
     d.sample_offset = (uint32_t)a->sample_offset;
-    char* ws = static_cast<char*>(a->workspace);
-    auto Fp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    const Workspace ws(a->workspace);
+    auto Fp = [&](size_t off) { return ws.at<float>(off); };
     const float* prm = a->params;
     const int Q = g.L * g.H;
     const bool persistent = gc_use_persistent(g, a->gru_path);
@@ -509,14 +502,14 @@ int grucm_run(const rulgnn_grucm_shape* s, const rulgnn_grucm_args* a, int mode,
     rulgnn_gru_shape gs{g.B, g.L, g.h, g.H};
     rulgnn_gru_args ga{};
     ga.w_ih = prm + o.wih; ga.w_hh = prm + o.whh; ga.b_ih = prm + o.bih; ga.b_hh = prm + o.bhh;
-    ga.workspace = ws + w.gru; ga.workspace_bytes = w.gru_bytes;
+    ga.workspace = ws.at<void>(w.gru); ga.workspace_bytes = w.gru_bytes;
     ga.x = Fp(w.pooled);
     (void)hipGetLastError();
     if (mode & 1) {
         gc_graph(g, d, w, false, a->x, prm, Fp(w.pooled), nullptr, nullptr, st);
         if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
         ga.out = Fp(w.hs);
-        GC_RC(persistent ? gru_persistent_forward(&gs, &ga, st) : gru_forward(&gs, &ga, st));
+        RULGNN_TRY(persistent ? gru_persistent_forward(&gs, &ga, st) : gru_forward(&gs, &ga, st));
         const float inv_gb = 1.0f / (float)(a->global_batch > 0 ? a->global_batch : g.B);
         hipLaunchKernelGGL(grucm_head_kernel, dim3((unsigned)g.B), dim3(GC_HB), 0, st, g, d, (const float*)Fp(w.hs), prm + o.wout, prm + o.bout,
                            a->y, a->pred, Fp(w.dpred), Fp(w.sqerr), inv_gb);
@@ -528,14 +521,14 @@ int grucm_run(const rulgnn_grucm_shape* s, const rulgnn_grucm_args* a, int mode,
         hipLaunchKernelGGL(grucm_head_bwd_kernel, dim3((unsigned)((Q + 1 + GC_HB - 1) / GC_HB), (unsigned)w.hslices), dim3(GC_HB), 0, st, g, d,
                            (const float*)Fp(w.hs), prm + o.wout, dpred, Fp(w.dhs), w.hslices == 1 ? gr + o.wout : Fp(w.hpart));
         if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
-        if (w.hslices > 1) GC_RC(rows_sum(Fp(w.hpart), w.hslices, Q + 1, Q + 1, gr + o.wout, st));
+        if (w.hslices > 1) RULGNN_TRY(rows_sum(Fp(w.hpart), w.hslices, Q + 1, Q + 1, gr + o.wout, st));
         ga.dout = Fp(w.dhs); ga.dx = Fp(w.dpooled);
         ga.dw_ih = gr + o.wih; ga.dw_hh = gr + o.whh; ga.db_ih = gr + o.bih; ga.db_hh = gr + o.bhh;
-        GC_RC(persistent ? gru_persistent_backward(&gs, &ga, st) : gru_backward(&gs, &ga, st));
+        RULGNN_TRY(persistent ? gru_persistent_backward(&gs, &ga, st) : gru_backward(&gs, &ga, st));
         gc_graph(g, d, w, true, a->x, prm, nullptr, Fp(w.dpooled), Fp(w.gpart), st);
         if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
-        GC_RC(rows_sum(Fp(w.gpart), w.gblocks, o.graph, o.graph, gr, st));
-        if (!a->dpred && a->loss) GC_RC(block_sum((const float*)Fp(w.sqerr), g.B, a->loss, st));
+        RULGNN_TRY(rows_sum(Fp(w.gpart), w.gblocks, o.graph, o.graph, gr, st));
+        if (!a->dpred && a->loss) RULGNN_TRY(block_sum((const float*)Fp(w.sqerr), g.B, a->loss, st));
     }
     return RULGNN_OK;
 }

@@ -11,7 +11,7 @@
 // data gradients per graph and leaves the per-row output gradients of every linear layer in the workspace, from which the
 // weight gradients are reduced over all graphs by split-K MFMA GEMMs (deterministic).
 #include "sgemm_mfma.hpp"
-#include "stgcn_host.hpp"
+#include "families_host.hpp"
 
 namespace rulgnn {
 
@@ -510,14 +510,6 @@ constexpr size_t HG_BWD_LDS = sizeof(float) * (10 * MAXN * TS + MAXF * TS + 3 * 
 
 __global__ void hg_fill_one_kernel(float* p) { p[0] = 1.f; }
 
-template <typename K>
-int hg_grid(K kernel, int64_t items, size_t lds) {
-    auto [cus, per_cu] = residency(kernel, HB, lds);
-    int64_t want = (int64_t)cus * per_cu;
-    if (want > items) want = items;
-    return want < 1 ? 1 : (int)want;
-}
-
 }  // namespace
 
 int64_t hagcn_graph_param_count(const rulgnn_hagcn_shape* s) {
@@ -531,20 +523,14 @@ size_t hagcn_workspace_bytes(const rulgnn_hagcn_shape* s) {
     return (size_t)g.total_floats * sizeof(float);
 }
 
-#define HG_RC(call)                        \
-    do {                                   \
-        const int rc_ = (call);            \
-        if (rc_ != RULGNN_OK) return rc_;  \
-    } while (0)
-
 int hagcn_graph_forward(const rulgnn_hagcn_shape* s, const rulgnn_hagcn_args* a, hipStream_t st) {
     HgGeom g;
-    HG_RC(hg_geometry(s, &g));
+    RULGNN_TRY(hg_geometry(s, &g));
     if (a->workspace_bytes < (size_t)g.total_floats * sizeof(float)) return RULGNN_EWORKSPACE;
     float* ws = static_cast<float*>(a->workspace);
     (void)hipGetLastError();
-    HG_RC(allow_dynamic_lds(hg_forward_kernel, HG_FWD_LDS));
-    hipLaunchKernelGGL(hg_forward_kernel, dim3(hg_grid(hg_forward_kernel, g.G, HG_FWD_LDS)), dim3(HB), HG_FWD_LDS, st, g, a->nodes,
+    RULGNN_TRY(allow_dynamic_lds(hg_forward_kernel, HG_FWD_LDS));
+    hipLaunchKernelGGL(hg_forward_kernel, dim3(resident_rows(hg_forward_kernel, HB, HG_FWD_LDS, g.G, g.G)), dim3(HB), HG_FWD_LDS, st, g, a->nodes,
                        a->params, ws, a->feats, a->topk, a->forced_topk);
     hipLaunchKernelGGL(hg_kl_kernel, dim3(1), dim3(1024), 0, st, (const float*)(ws + g.t_kl), g.G * NLV, 1.0f / (float)g.G, a->kl);
     return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
@@ -552,12 +538,12 @@ int hagcn_graph_forward(const rulgnn_hagcn_shape* s, const rulgnn_hagcn_args* a,
 
 int hagcn_graph_backward(const rulgnn_hagcn_shape* s, const rulgnn_hagcn_args* a, hipStream_t st) {
     HgGeom g;
-    HG_RC(hg_geometry(s, &g));
+    RULGNN_TRY(hg_geometry(s, &g));
     if (a->workspace_bytes < (size_t)g.total_floats * sizeof(float)) return RULGNN_EWORKSPACE;
     float* ws = static_cast<float*>(a->workspace);
     (void)hipGetLastError();
-    HG_RC(allow_dynamic_lds(hg_backward_kernel, HG_BWD_LDS));
-    hipLaunchKernelGGL(hg_backward_kernel, dim3(hg_grid(hg_backward_kernel, g.G, HG_BWD_LDS)), dim3(HB), HG_BWD_LDS, st, g, a->params, ws,
+    RULGNN_TRY(allow_dynamic_lds(hg_backward_kernel, HG_BWD_LDS));
+    hipLaunchKernelGGL(hg_backward_kernel, dim3(resident_rows(hg_backward_kernel, HB, HG_BWD_LDS, g.G, g.G)), dim3(HB), HG_BWD_LDS, st, g, a->params, ws,
                        a->dfeats, a->dkl, a->dnodes);
     float* one = ws + g.t_one;
     float* split = ws + g.t_split;
@@ -567,7 +553,7 @@ int hagcn_graph_backward(const rulgnn_hagcn_shape* s, const rulgnn_hagcn_args* a
         const int nj = hg_pgrad_jobs(g, ws, a->grads, jobs);
         const size_t split_floats = (size_t)(g.total_floats - g.t_split);
         for (int j0 = 0; j0 < nj; j0 += HG_PGRAD_BATCH)
-            HG_RC(sgemm_splitk_batch(jobs + j0, nj - j0 < HG_PGRAD_BATCH ? nj - j0 : HG_PGRAD_BATCH, split, split_floats, st));
+            RULGNN_TRY(sgemm_splitk_batch(jobs + j0, nj - j0 < HG_PGRAD_BATCH ? nj - j0 : HG_PGRAD_BATCH, split, split_floats, st));
     } else if (hipMemsetAsync(a->grads, 0, sizeof(float) * (size_t)g.nparam, st) != hipSuccess) {      // (no graphs: every sum is empty)
         return RULGNN_EHIP;
     }

@@ -5,7 +5,7 @@
 // trainer.py:calc_results_per_run after the predictions were copied to the host batch by batch (trainer.py:148-152).
 // Here the predictions stay where the eval forward wrote them: one pass over (pred, real) accumulates the four sums in
 // fp64, per-block partials are combined in a fixed order (deterministic), 32 bytes travel to the host.
-#include "stgcn_host.hpp"
+#include "families_host.hpp"
 
 namespace rulgnn {
 

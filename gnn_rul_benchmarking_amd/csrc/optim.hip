@@ -2,7 +2,7 @@
 //   adam_step:          torch.optim.Adam as the reference configures it (algorithms/algorithms.py:474-478):
 //                       L2 weight decay folded into the gradient, bias-corrected, no amsgrad.
 //   bn_running_update:  nn.BatchNorm1d running statistics (momentum 0.1, unbiased running variance).
-#include "stgcn_host.hpp"
+#include "families_host.hpp"
 #include "adam_device.hpp"
 
 namespace rulgnn {
@@ -141,8 +141,7 @@ int adam_step(float* p, const float* g, float* m, float* v, int64_t n, int64_t s
               float eps, float wd, float gscale, hipStream_t stream, void* step_state, const float* guard) {
     if (n <= 0) return RULGNN_OK;
     if (step_state) {
-        const int rc = step_prepare_adam(step_state, lr, beta1, beta2, stream);
-        if (rc != RULGNN_OK) return rc;
+        RULGNN_TRY(step_prepare_adam(step_state, lr, beta1, beta2, stream));
         step = 1;                  // placeholder: the kernel takes the corrections from the state
     }
     const double bc1 = 1.0 - pow((double)beta1, (double)step);

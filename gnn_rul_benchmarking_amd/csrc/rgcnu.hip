@@ -18,7 +18,7 @@
 
 #include "sgemm_mfma.hpp"
 #include "stgcn_device.hpp"
-#include "stgcn_host.hpp"
+#include "families_host.hpp"
 
 namespace rulgnn {
 
@@ -1082,27 +1082,18 @@ size_t rgcnu_workspace_bytes(const rulgnn_rgcnu_shape* s) {
     return rg_geometry(s, &g) == RULGNN_OK ? (size_t)g.total * sizeof(float) : 0;
 }
 
-#define RG_RC(call)                        \
-    do {                                   \
-        const int rc_ = (call);            \
-        if (rc_ != RULGNN_OK) return rc_;  \
-    } while (0)
-
 // mode bit 0: forward, bit 1: backward (after a forward with the same args / workspace)
 int rgcnu_run(const rulgnn_rgcnu_shape* s, const rulgnn_rgcnu_args* a, int mode, hipStream_t st) {
     RgGeom g;
-    RG_RC(rg_geometry(s, &g));
+    RULGNN_TRY(rg_geometry(s, &g));
     if (a->workspace_bytes < (size_t)g.total * sizeof(float)) return RULGNN_EWORKSPACE;
     if (g.B == 0) return RULGNN_OK;
     float* ws = static_cast<float*>(a->workspace);
     const float* prm = a->params;
     const float p = a->training ? a->dropout_p : 0.f;
-    uint32_t thr = 0;
-    if (p > 0.f) {
-        const uint64_t ti = (uint64_t)((double)p * 4294967296.0 + 0.5);
-        thr = ti > 4294967295ull ? 4294967295u : (uint32_t)ti;
-    }
-    const float scale = p > 0.f ? 1.0f / (1.0f - p) : 1.0f;
+    const DropoutConst drop = dropout_const(p);
+    const uint32_t thr = drop.thr;
+    const float scale = drop.scale;
     const uint32_t key = dropout_layer_key(a->seed, a->step, 0);
     const float inv_gb = 1.0f / (float)(a->global_batch > 0 ? a->global_batch : g.B);
     rulgnn_bilstm_shape ls{g.L, (int32_t)g.B, g.N, g.E};
@@ -1125,17 +1116,17 @@ int rgcnu_run(const rulgnn_rgcnu_shape* s, const rulgnn_rgcnu_args* a, int mode,
         if (scl_mx) {
             const size_t lm = rg_scl_mx_lds(scl_nt, false);
             auto go = [&](auto kernel) -> int {
-                RG_RC(allow_dynamic_lds(kernel, lm));
+                RULGNN_TRY(allow_dynamic_lds(kernel, lm));
                 hipLaunchKernelGGL(kernel, dim3((unsigned)gblocks), dim3(64 * RG_MXW), lm, st, g, a->x, prm, ws, key, thr, scale, a->sample_offset);
                 return RULGNN_OK;
             };
-            RG_RC(scl_nt == 1 ? go(rg_scl_mx_kernel<1>) : go(rg_scl_mx_kernel<2>));
+            RULGNN_TRY(scl_nt == 1 ? go(rg_scl_mx_kernel<1>) : go(rg_scl_mx_kernel<2>));
         } else
         hipLaunchKernelGGL(rg_scl_kernel, dim3((unsigned)gblocks), dim3(RB), lds_scl, st, g, a->x, prm, ws, key, thr, scale, a->sample_offset);
         if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
-        RG_RC(bilstm_forward(&ls, &la, st, 1));
+        RULGNN_TRY(bilstm_forward(&ls, &la, st, 1));
         const size_t lds = rg_fusion_lds(g, false);
-        RG_RC(allow_dynamic_lds(rg_fusion_kernel, lds));
+        RULGNN_TRY(allow_dynamic_lds(rg_fusion_kernel, lds));
         if (rg_fusion_mx_ok(g))
             hipLaunchKernelGGL(rg_fusion_mx_kernel, dim3(blocks), dim3(RB), 0, st, g, a->x, a->y, prm, ws, a->pred, a->std_pred, inv_gb);
         else
@@ -1146,7 +1137,7 @@ int rgcnu_run(const rulgnn_rgcnu_shape* s, const rulgnn_rgcnu_args* a, int mode,
     if (mode & 2) {
         if (!a->grads) return RULGNN_EINVAL;
         const size_t lds = rg_fusion_lds(g, true);
-        RG_RC(allow_dynamic_lds(rg_fusion_bwd_kernel, lds));
+        RULGNN_TRY(allow_dynamic_lds(rg_fusion_bwd_kernel, lds));
         if (rg_fusion_mx_ok(g))
             hipLaunchKernelGGL(rg_fusion_bwd_mx_kernel, dim3(blocks), dim3(RB), 0, st, g, a->x, a->dpred, prm, ws);
         else
@@ -1156,16 +1147,16 @@ int rgcnu_run(const rulgnn_rgcnu_shape* s, const rulgnn_rgcnu_args* a, int mode,
         la.dx = ws + g.w_dsp;
         la.dw_ih[0] = a->grads + g.o_wih; la.dw_hh[0] = a->grads + g.o_whh; la.db_ih[0] = a->grads + g.o_bih; la.db_hh[0] = a->grads + g.o_bhh;
         la.dw_ih[1] = la.dw_ih[0]; la.dw_hh[1] = la.dw_hh[0]; la.db_ih[1] = la.db_ih[0]; la.db_hh[1] = la.db_hh[0];
-        RG_RC(bilstm_backward(&ls, &la, st, 1));
-        RG_RC(allow_dynamic_lds(rg_scl_bwd_kernel, lds_sclb));
+        RULGNN_TRY(bilstm_backward(&ls, &la, st, 1));
+        RULGNN_TRY(allow_dynamic_lds(rg_scl_bwd_kernel, lds_sclb));
         if (scl_mx) {
             const size_t lm = rg_scl_mx_lds(scl_nt, true);
             auto go = [&](auto kernel) -> int {
-                RG_RC(allow_dynamic_lds(kernel, lm));
+                RULGNN_TRY(allow_dynamic_lds(kernel, lm));
                 hipLaunchKernelGGL(kernel, dim3((unsigned)gblocks), dim3(64 * RG_MXW), lm, st, g, a->x, prm, ws, key, thr, scale, a->sample_offset);
                 return RULGNN_OK;
             };
-            RG_RC(scl_nt == 1 ? go(rg_scl_bwd_mx_kernel<1>) : go(rg_scl_bwd_mx_kernel<2>));
+            RULGNN_TRY(scl_nt == 1 ? go(rg_scl_bwd_mx_kernel<1>) : go(rg_scl_bwd_mx_kernel<2>));
         } else
         hipLaunchKernelGGL(rg_scl_bwd_kernel, dim3((unsigned)gblocks), dim3(RB), lds_sclb, st, g, a->x, prm, ws, key, thr, scale, a->sample_offset);
         hipLaunchKernelGGL(rg_adj_bwd_kernel, dim3(blocks), dim3(RB), 0, st, g, a->x, prm, ws);
@@ -1175,7 +1166,7 @@ int rgcnu_run(const rulgnn_rgcnu_shape* s, const rulgnn_rgcnu_args* a, int mode,
             float* const out[3] = {a->grads, a->grads + g.o_g1w, a->grads + g.o_c1w};
             const int rows[3] = {blocks, gblocks, blocks}, n[3] = {g.nA, g.nS, g.nF};
             const int64_t ld[3] = {g.nA, g.nS, g.nF};
-            RG_RC(rows_sum_three(part, out, rows, ld, n, st));
+            RULGNN_TRY(rows_sum_three(part, out, rows, ld, n, st));
         }
         const int nz = g.E * g.L + 1;                                    // the `std` head is not in the loss (algorithms.py:287-290)
         hipLaunchKernelGGL(rg_zero_kernel, dim3((nz + 255) / 256), dim3(256), 0, st, a->grads + g.o_f2w, nz);

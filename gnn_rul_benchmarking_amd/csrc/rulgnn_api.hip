@@ -2,7 +2,7 @@
 #include <initializer_list>
 
 #include "sgemm_mfma.hpp"
-#include "stgcn_host.hpp"
+#include "families_host.hpp"
 #include "adam_device.hpp"
 #include "stgcn_train_mx.hpp"
 
@@ -49,6 +49,25 @@ static int check_ptrs(std::initializer_list<const void*> ps) {
     return RULGNN_OK;
 }
 
+// An optional pointer: null, or 4-byte aligned.
+static bool opt_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
+
+// The pointer checks the plain families' steps end in, in two halves (a family with tests of its own between them calls the halves):
+// parameters and workspace always, x and pred with a batch; for a backward the gradients and, with a batch, d pred or the targets.
+static int check_fwd_ptrs(const void* params, const void* workspace, const void* x, const void* pred, int64_t batch) {
+    RULGNN_TRY(check_ptrs({params, workspace}));
+    return batch > 0 ? check_ptrs({x, pred}) : RULGNN_OK;
+}
+static int check_bwd_ptrs(const void* grads, const void* y, const void* dpred, int64_t batch) {
+    RULGNN_TRY(check_ptrs({grads}));
+    return !dpred && !y && batch > 0 ? RULGNN_EINVAL : RULGNN_OK;
+}
+static int check_step_ptrs(const void* params, const void* workspace, const void* x, const void* pred, const void* grads, const void* y,
+                           const void* dpred, int64_t batch, bool bwd) {
+    RULGNN_TRY(check_fwd_ptrs(params, workspace, x, pred, batch));
+    return bwd ? check_bwd_ptrs(grads, y, dpred, batch) : RULGNN_OK;
+}
+
 // The optimizer block of a family's fused step (rulgnn_<family>_fwdbwd_f32): a step count or a device step state, the step's own
 // parameter buffer, then the Adam pointers.
 static int check_adam(const rulgnn_adam_args* opt, const float* params) {
@@ -60,6 +79,20 @@ static int check_adam(const rulgnn_adam_args* opt, const float* params) {
 static int adam_tail(const rulgnn_adam_args* opt, const float* grads, int64_t first, int64_t n, hipStream_t st) {
     return adam_step(opt->params + first, grads + first, opt->exp_avg + first, opt->exp_avg_sq + first, n, opt->step, opt->lr, opt->beta1,
                      opt->beta2, opt->eps, opt->weight_decay, 1.0f, st, opt->step_state);
+}
+
+// What follows a family's argument check in its fused MSE step (rulgnn_<family>_fwdbwd_f32): d pred is refused (`missing_y`: so is a
+// batch without targets), the optimizer block checked, `run` (mode 3) enqueued and, with an optimizer, plain Adam over the flat floats
+// [first, first + n).
+extern "C++" template <typename Run>
+static int fused_step_tail(const float* dpred, bool missing_y, const rulgnn_adam_args* opt, const float* params, Run run, const float* grads,
+                           int64_t first, int64_t n, void* stream) {
+    if (dpred || missing_y) return RULGNN_EINVAL;          // the fused call is the MSE step
+    if (opt) RULGNN_TRY(check_adam(opt, params));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int rc = run(st);
+    if (rc != RULGNN_OK || !opt) return rc;
+    return adam_tail(opt, grads, first, n, st);
 }
 
 // Path selection.  The fused row-mapped kernels cover num_patch <= 64 as long as one wavefront's input tile fits its LDS staging area,
@@ -144,7 +177,7 @@ static int check_train(const rulgnn_stgcn_shape* shape, const rulgnn_stgcn_train
         if (!a->dpred) {
             rc = check_ptrs({a->y, a->loss});
             if (rc != RULGNN_OK) return rc;
-        } else if (reinterpret_cast<uintptr_t>(a->dpred) & 3) {
+        } else if (!opt_aligned(a->dpred)) {
             return RULGNN_EALIGN;
         }
     }
@@ -284,11 +317,10 @@ int rulgnn_stgcn_train_step_path_f32(const rulgnn_stgcn_shape* shape, const rulg
         if (tiled(shape)) return stgcn_tiled_train(shape, args, 2, static_cast<hipStream_t>(stream));
         return stgcn_train_step(shape, args, nullptr, static_cast<hipStream_t>(stream), path);
     }
-    if ((opt->step < 1 && !opt->step_state) || args->dpred) return RULGNN_EINVAL;
-    if (opt->params != args->params) return RULGNN_EINVAL;
-    rc = check_ptrs({opt->params, opt->exp_avg, opt->exp_avg_sq});
+    if (args->dpred) return RULGNN_EINVAL;
+    rc = check_adam(opt, args->params);
     if (rc != RULGNN_OK) return rc;
-    if (opt->bn_stats && (reinterpret_cast<uintptr_t>(opt->bn_stats) & 3)) return RULGNN_EALIGN;
+    if (!opt_aligned(opt->bn_stats)) return RULGNN_EALIGN;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (tiled(shape)) {                                    // tiled path: same call, optimizer (+ running statistics) as one more kernel
         rc = stgcn_tiled_train(shape, args, 2, st);
@@ -399,12 +431,12 @@ static int check_stmsgcn(const rulgnn_stmsgcn_shape* shape, const rulgnn_stmsgcn
     if (shape->batch < 1 || a->global_batch < shape->batch) return RULGNN_EINVAL;
     int rc = check_ptrs({a->x, a->params, a->pred, a->workspace});
     if (rc != RULGNN_OK) return rc;
-    if (a->y && (reinterpret_cast<uintptr_t>(a->y) & 3)) return RULGNN_EALIGN;
+    if (!opt_aligned(a->y)) return RULGNN_EALIGN;
     if (backward) {
         rc = check_ptrs({a->grads});
         if (rc != RULGNN_OK) return rc;
         if (a->dpred) {
-            if (reinterpret_cast<uintptr_t>(a->dpred) & 3) return RULGNN_EALIGN;
+            if (!opt_aligned(a->dpred)) return RULGNN_EALIGN;
         } else if (need_target) {
             rc = check_ptrs({a->y, a->loss});
             if (rc != RULGNN_OK) return rc;
@@ -427,14 +459,9 @@ int rulgnn_stmsgcn_backward_f32(const rulgnn_stmsgcn_shape* shape, const rulgnn_
 
 int rulgnn_stmsgcn_fwdbwd_f32(const rulgnn_stmsgcn_shape* shape, const rulgnn_stmsgcn_args* args, const rulgnn_adam_args* opt,
                               void* stream) {
-    int rc = check_stmsgcn(shape, args, true, true);
-    if (rc != RULGNN_OK) return rc;
-    if (args->dpred) return RULGNN_EINVAL;                 // the fused call is the MSE step
-    if (opt && (rc = check_adam(opt, args->params)) != RULGNN_OK) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    rc = stmsgcn_run(shape, args, 3, st);
-    if (rc != RULGNN_OK || !opt) return rc;
-    return adam_tail(opt, args->grads, 0, stmsgcn_param_count(shape), st);
+    RULGNN_TRY(check_stmsgcn(shape, args, true, true));
+    auto run = [&](hipStream_t st) { return stmsgcn_run(shape, args, 3, st); };
+    return fused_step_tail(args->dpred, false, opt, args->params, run, args->grads, 0, stmsgcn_param_count(shape), stream);
 }
 
 
@@ -454,7 +481,7 @@ static int check_astgcnn(const rulgnn_astgcnn_shape* shape, const rulgnn_astgcnn
         if (rc != RULGNN_OK) return rc;
     }
     for (const void* p : {(const void*)a->y, (const void*)a->dpred, (const void*)a->bn_batch, (const void*)a->loss})
-        if (p && (reinterpret_cast<uintptr_t>(p) & 3)) return RULGNN_EALIGN;
+        if (!opt_aligned(p)) return RULGNN_EALIGN;
     if (backward) {
         if (!a->training) return RULGNN_EINVAL;            // the backward is the train-mode (batch-statistics) one
         rc = check_ptrs({a->grads});
@@ -485,7 +512,7 @@ int rulgnn_astgcnn_fwdbwd_f32(const rulgnn_astgcnn_shape* shape, const rulgnn_as
     if (rc != RULGNN_OK) return rc;
     if (args->dpred) return RULGNN_EINVAL;
     if (opt && (rc = check_adam(opt, args->params)) != RULGNN_OK) return rc;
-    if (opt && opt->bn_stats && (!args->bn_batch || (reinterpret_cast<uintptr_t>(opt->bn_stats) & 3))) return RULGNN_EINVAL;
+    if (opt && opt->bn_stats && (!args->bn_batch || !opt_aligned(opt->bn_stats))) return RULGNN_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
     // (plain batch statistics: the running-statistics update rides in the step's finalize kernel)
     const bool tail_bn = opt && opt->bn_stats && args->training && args->bn_moment_weight == 0.f;
@@ -555,7 +582,7 @@ static int check_fcstgnn(const rulgnn_fcstgnn_shape* shape, const rulgnn_fcstgnn
         if (rc != RULGNN_OK) return rc;
     }
     for (const void* p : {(const void*)a->y, (const void*)a->dpred, (const void*)a->bn_batch, (const void*)a->loss})
-        if (p && (reinterpret_cast<uintptr_t>(p) & 3)) return RULGNN_EALIGN;
+        if (!opt_aligned(p)) return RULGNN_EALIGN;
     if (backward) {
         if (!a->training) return RULGNN_EINVAL;
         rc = check_ptrs({a->grads});
@@ -586,7 +613,7 @@ int rulgnn_fcstgnn_fwdbwd_f32(const rulgnn_fcstgnn_shape* shape, const rulgnn_fc
     if (rc != RULGNN_OK) return rc;
     if (args->dpred) return RULGNN_EINVAL;
     if (opt && (rc = check_adam(opt, args->params)) != RULGNN_OK) return rc;
-    if (opt && opt->bn_stats && (!args->bn_batch || (reinterpret_cast<uintptr_t>(opt->bn_stats) & 3))) return RULGNN_EINVAL;
+    if (opt && opt->bn_stats && (!args->bn_batch || !opt_aligned(opt->bn_stats))) return RULGNN_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
     const bool tail_bn = opt && opt->bn_stats && args->training && args->bn_moment_weight == 0.f;
     // (host-side step count: the step's last kernel applies the optimizer itself -- adam_device.hpp; a device step state keeps the launch)
@@ -631,7 +658,7 @@ int rulgnn_hagcn_graph_forward_f32(const rulgnn_hagcn_shape* shape, const rulgnn
     const int rc = check_ptrs({a->nodes, a->params, a->feats, a->kl, a->workspace});
     if (rc != RULGNN_OK) return rc;
     for (const void* p : {(const void*)a->topk, (const void*)a->forced_topk})
-        if (p && (reinterpret_cast<uintptr_t>(p) & 3)) return RULGNN_EALIGN;
+        if (!opt_aligned(p)) return RULGNN_EALIGN;
     return hagcn_graph_forward(shape, a, static_cast<hipStream_t>(stream));
 }
 
@@ -659,7 +686,7 @@ int rulgnn_bilstm_backward_f32(const rulgnn_bilstm_shape* shape, const rulgnn_bi
     const int rc = check_ptrs({a->x, a->w_ih[0], a->w_ih[1], a->w_hh[0], a->w_hh[1], a->dout, a->dw_ih[0], a->dw_ih[1], a->dw_hh[0],
                                a->dw_hh[1], a->db_ih[0], a->db_ih[1], a->db_hh[0], a->db_hh[1], a->workspace});
     if (rc != RULGNN_OK) return rc;
-    if (a->dx && (reinterpret_cast<uintptr_t>(a->dx) & 3)) return RULGNN_EALIGN;
+    if (!opt_aligned(a->dx)) return RULGNN_EALIGN;
     return bilstm_backward(shape, a, static_cast<hipStream_t>(stream));
 }
 
@@ -692,7 +719,7 @@ int rulgnn_stconv_fwdbwd_f32(const rulgnn_stconv_shape* shape, const rulgnn_astg
     if (rc != RULGNN_OK) return rc;
     if (args->dpred) return RULGNN_EINVAL;
     if (opt && (rc = check_adam(opt, args->params)) != RULGNN_OK) return rc;
-    if (opt && opt->bn_stats && (!args->bn_batch || (reinterpret_cast<uintptr_t>(opt->bn_stats) & 3))) return RULGNN_EINVAL;
+    if (opt && opt->bn_stats && (!args->bn_batch || !opt_aligned(opt->bn_stats))) return RULGNN_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
     rc = stconv_run(shape, args, 3, st);
     if (rc != RULGNN_OK || !opt) return rc;
@@ -776,14 +803,9 @@ int rulgnn_stgnn_backward_f32(const rulgnn_stgnn_shape* shape, const rulgnn_stms
 }
 
 int rulgnn_stgnn_fwdbwd_f32(const rulgnn_stgnn_shape* shape, const rulgnn_stmsgcn_args* args, const rulgnn_adam_args* opt, void* stream) {
-    int rc = check_stgnn(shape, args, true, true);
-    if (rc != RULGNN_OK) return rc;
-    if (args->dpred) return RULGNN_EINVAL;
-    if (opt && (rc = check_adam(opt, args->params)) != RULGNN_OK) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    rc = stgnn_run(shape, args, 3, st);
-    if (rc != RULGNN_OK || !opt) return rc;
-    return adam_tail(opt, args->grads, 0, stgnn_param_count(shape), st);
+    RULGNN_TRY(check_stgnn(shape, args, true, true));
+    auto run = [&](hipStream_t st) { return stgnn_run(shape, args, 3, st); };
+    return fused_step_tail(args->dpred, false, opt, args->params, run, args->grads, 0, stgnn_param_count(shape), stream);
 }
 
 // ---- STNet ----------------------------------------------------------------------------------------------------------------------
@@ -793,18 +815,7 @@ size_t rulgnn_stnet_workspace_bytes(const rulgnn_stnet_shape* shape) { return st
 static int check_stnet(const rulgnn_stnet_shape* shape, const rulgnn_stnet_args* a, bool bwd) {
     if (!shape || !a) return RULGNN_EINVAL;
     if (stnet_param_count(shape) < 0) return RULGNN_EUNSUPPORTED;
-    int rc = check_ptrs({a->params, a->workspace});
-    if (rc != RULGNN_OK) return rc;
-    if (shape->batch > 0) {
-        rc = check_ptrs({a->x, a->pred});
-        if (rc != RULGNN_OK) return rc;
-    }
-    if (bwd) {
-        rc = check_ptrs({a->grads});
-        if (rc != RULGNN_OK) return rc;
-        if (!a->dpred && !a->y && shape->batch > 0) return RULGNN_EINVAL;
-    }
-    return RULGNN_OK;
+    return check_step_ptrs(a->params, a->workspace, a->x, a->pred, a->grads, a->y, a->dpred, shape->batch, bwd);
 }
 
 int rulgnn_stnet_forward_f32(const rulgnn_stnet_shape* shape, const rulgnn_stnet_args* args, void* stream) {
@@ -820,15 +831,10 @@ int rulgnn_stnet_backward_f32(const rulgnn_stnet_shape* shape, const rulgnn_stne
 }
 
 int rulgnn_stnet_fwdbwd_f32(const rulgnn_stnet_shape* shape, const rulgnn_stnet_args* args, const rulgnn_adam_args* opt, void* stream) {
-    int rc = check_stnet(shape, args, true);
-    if (rc != RULGNN_OK) return rc;
-    if (args->dpred || (!args->y && shape->batch > 0)) return RULGNN_EINVAL;
-    if (opt && (rc = check_adam(opt, args->params)) != RULGNN_OK) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    rc = stnet_run(shape, args, 3, st);
-    if (rc != RULGNN_OK || !opt) return rc;
+    RULGNN_TRY(check_stnet(shape, args, true));
     // cnn.{weight, bias} (the first 3 entries) have no gradient in the reference (`grad is None`): torch's Adam leaves them untouched
-    return adam_tail(opt, args->grads, 3, stnet_param_count(shape) - 3, st);
+    auto run = [&](hipStream_t st) { return stnet_run(shape, args, 3, st); };
+    return fused_step_tail(args->dpred, !args->y && shape->batch > 0, opt, args->params, run, args->grads, 3, stnet_param_count(shape) - 3, stream);
 }
 
 // ---- SAGCN ----------------------------------------------------------------------------------------------------------------------
@@ -839,18 +845,7 @@ int64_t rulgnn_sagcn_tap_offset(const rulgnn_sagcn_shape* shape, int32_t which) 
 static int check_sagcn(const rulgnn_sagcn_shape* shape, const rulgnn_sagcn_args* a, bool bwd) {
     if (!shape || !a) return RULGNN_EINVAL;
     if (sagcn_param_count(shape) < 0) return RULGNN_EUNSUPPORTED;
-    int rc = check_ptrs({a->params, a->workspace});
-    if (rc != RULGNN_OK) return rc;
-    if (shape->batch > 0) {
-        rc = check_ptrs({a->x, a->pred});
-        if (rc != RULGNN_OK) return rc;
-    }
-    if (bwd) {
-        rc = check_ptrs({a->grads});
-        if (rc != RULGNN_OK) return rc;
-        if (!a->dpred && !a->y && shape->batch > 0) return RULGNN_EINVAL;
-    }
-    return RULGNN_OK;
+    return check_step_ptrs(a->params, a->workspace, a->x, a->pred, a->grads, a->y, a->dpred, shape->batch, bwd);
 }
 
 int rulgnn_sagcn_forward_f32(const rulgnn_sagcn_shape* shape, const rulgnn_sagcn_args* args, void* stream) {
@@ -866,14 +861,9 @@ int rulgnn_sagcn_backward_f32(const rulgnn_sagcn_shape* shape, const rulgnn_sagc
 }
 
 int rulgnn_sagcn_fwdbwd_f32(const rulgnn_sagcn_shape* shape, const rulgnn_sagcn_args* args, const rulgnn_adam_args* opt, void* stream) {
-    int rc = check_sagcn(shape, args, true);
-    if (rc != RULGNN_OK) return rc;
-    if (args->dpred || (!args->y && shape->batch > 0)) return RULGNN_EINVAL;
-    if (opt && (rc = check_adam(opt, args->params)) != RULGNN_OK) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    rc = sagcn_run(shape, args, 3, st);
-    if (rc != RULGNN_OK || !opt) return rc;
-    return adam_tail(opt, args->grads, 0, sagcn_param_count(shape), st);
+    RULGNN_TRY(check_sagcn(shape, args, true));
+    auto run = [&](hipStream_t st) { return sagcn_run(shape, args, 3, st); };
+    return fused_step_tail(args->dpred, !args->y && shape->batch > 0, opt, args->params, run, args->grads, 0, sagcn_param_count(shape), stream);
 }
 
 int rulgnn_sgemm_mode(int32_t mode) {
@@ -891,19 +881,9 @@ int64_t rulgnn_stagnn_tap_offset(const rulgnn_stagnn_shape* shape, int32_t which
 static int check_stagnn(const rulgnn_stagnn_shape* shape, const rulgnn_stagnn_args* a, bool bwd) {
     if (!shape || !a) return RULGNN_EINVAL;
     if (stagnn_param_count(shape) < 0) return RULGNN_EUNSUPPORTED;
-    int rc = check_ptrs({a->params, a->workspace, a->bn_state});
-    if (rc != RULGNN_OK) return rc;
-    if (shape->batch > 0) {
-        rc = check_ptrs({a->x, a->pred});
-        if (rc != RULGNN_OK) return rc;
-    }
-    if (bwd) {
-        rc = check_ptrs({a->grads});
-        if (rc != RULGNN_OK) return rc;
-        if (!a->training) return RULGNN_EINVAL;
-        if (!a->dpred && !a->y && shape->batch > 0) return RULGNN_EINVAL;
-    }
-    return RULGNN_OK;
+    RULGNN_TRY(check_ptrs({a->params, a->workspace, a->bn_state}));         // (bn_state ahead of x and pred)
+    RULGNN_TRY(check_step_ptrs(a->params, a->workspace, a->x, a->pred, a->grads, a->y, a->dpred, shape->batch, bwd));
+    return bwd && !a->training ? RULGNN_EINVAL : RULGNN_OK;                // (the same code as a batch without d pred or targets)
 }
 
 int rulgnn_stagnn_forward_f32(const rulgnn_stagnn_shape* shape, const rulgnn_stagnn_args* args, void* stream) {
@@ -919,14 +899,9 @@ int rulgnn_stagnn_backward_f32(const rulgnn_stagnn_shape* shape, const rulgnn_st
 }
 
 int rulgnn_stagnn_fwdbwd_f32(const rulgnn_stagnn_shape* shape, const rulgnn_stagnn_args* args, const rulgnn_adam_args* opt, void* stream) {
-    int rc = check_stagnn(shape, args, true);
-    if (rc != RULGNN_OK) return rc;
-    if (args->dpred || (!args->y && shape->batch > 0)) return RULGNN_EINVAL;
-    if (opt && (rc = check_adam(opt, args->params)) != RULGNN_OK) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    rc = stagnn_run(shape, args, 3, st);
-    if (rc != RULGNN_OK || !opt) return rc;
-    return adam_tail(opt, args->grads, 0, stagnn_param_count(shape), st);
+    RULGNN_TRY(check_stagnn(shape, args, true));
+    auto run = [&](hipStream_t st) { return stagnn_run(shape, args, 3, st); };
+    return fused_step_tail(args->dpred, !args->y && shape->batch > 0, opt, args->params, run, args->grads, 0, stagnn_param_count(shape), stream);
 }
 
 // ---- plain GEMM -------------------------------------------------------------------------------------------------------------------
@@ -951,7 +926,7 @@ int rulgnn_sgemm_scaled_f32(const float* A, int64_t sAm, int64_t sAk, const floa
     return sgemm(A, sAm, sAk, B, sBn, sBk, C, ldc, M, N, K, accumulate != 0, static_cast<hipStream_t>(stream), 0, amax_a, amax_na, amax_b, amax_nb);
 }
 
-static size_t scaled_plane_bytes(int32_t M, int32_t N, int32_t K) { return (sgemm_planes_ws_bytes(M, N, K) + 255) & ~(size_t)255; }
+static size_t scaled_plane_bytes(int32_t M, int32_t N, int32_t K) { return ws_align(sgemm_planes_ws_bytes(M, N, K)); }
 size_t rulgnn_sgemm_scaled_workspace_bytes(int32_t M, int32_t N, int32_t K, int32_t split_k) {
     if (M <= 0 || N <= 0 || K <= 0) return 0;
     return scaled_plane_bytes(M, N, K) + (split_k ? sgemm_splitk_need_floats(M, N, K) * sizeof(float) : 0);
@@ -1017,19 +992,8 @@ static int check_rgcnu(const rulgnn_rgcnu_shape* shape, const rulgnn_rgcnu_args*
                                                  ? RULGNN_EUNSUPPORTED
                                                  : RULGNN_EINVAL;
     if (!(a->dropout_p >= 0.f && a->dropout_p < 1.f)) return RULGNN_EINVAL;
-    int rc = check_ptrs({a->params, a->workspace});
-    if (rc != RULGNN_OK) return rc;
-    if (shape->batch > 0) {
-        rc = check_ptrs({a->x, a->pred});
-        if (rc != RULGNN_OK) return rc;
-    }
-    if (bwd) {
-        rc = check_ptrs({a->grads});
-        if (rc != RULGNN_OK) return rc;
-        if (!a->dpred && !a->y && shape->batch > 0) return RULGNN_EINVAL;
-    }
     (void)fwd;
-    return RULGNN_OK;
+    return check_step_ptrs(a->params, a->workspace, a->x, a->pred, a->grads, a->y, a->dpred, shape->batch, bwd);
 }
 
 int rulgnn_rgcnu_forward_f32(const rulgnn_rgcnu_shape* shape, const rulgnn_rgcnu_args* args, void* stream) {
@@ -1045,66 +1009,46 @@ int rulgnn_rgcnu_backward_f32(const rulgnn_rgcnu_shape* shape, const rulgnn_rgcn
 }
 
 int rulgnn_rgcnu_fwdbwd_f32(const rulgnn_rgcnu_shape* shape, const rulgnn_rgcnu_args* args, const rulgnn_adam_args* opt, void* stream) {
-    int rc = check_rgcnu(shape, args, true, true);
-    if (rc != RULGNN_OK) return rc;
-    if (args->dpred || (!args->y && shape->batch > 0)) return RULGNN_EINVAL;
-    if (opt && (rc = check_adam(opt, args->params)) != RULGNN_OK) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    rc = rgcnu_run(shape, args, 3, st);
-    if (rc != RULGNN_OK || !opt) return rc;
+    RULGNN_TRY(check_rgcnu(shape, args, true, true));
     // the second head (fc2, the last E*L + 1 entries) has no gradient in the reference (`grad is None`): torch's Adam leaves it untouched
     const int64_t live = rgcnu_param_count(shape) - ((int64_t)shape->encoder_hidden_dim * shape->time_length + 1);
-    return adam_tail(opt, args->grads, 0, live, st);
+    auto run = [&](hipStream_t st) { return rgcnu_run(shape, args, 3, st); };
+    return fused_step_tail(args->dpred, !args->y && shape->batch > 0, opt, args->params, run, args->grads, 0, live, stream);
+}
+
+static int check_gru_fwd(const rulgnn_gru_shape* shape, const rulgnn_gru_args* a) {
+    if (!shape || !a) return RULGNN_EINVAL;
+    RULGNN_TRY(check_ptrs({a->w_ih, a->w_hh, a->b_ih, a->b_hh, a->workspace}));
+    return shape->num_seq > 0 ? check_ptrs({a->x, a->out}) : RULGNN_OK;
+}
+static int check_gru_bwd(const rulgnn_gru_shape* shape, const rulgnn_gru_args* a) {
+    if (!shape || !a) return RULGNN_EINVAL;
+    RULGNN_TRY(check_ptrs({a->w_ih, a->w_hh, a->b_ih, a->b_hh, a->workspace, a->dw_ih, a->dw_hh, a->db_ih, a->db_hh}));
+    return shape->num_seq > 0 ? check_ptrs({a->x, a->dout}) : RULGNN_OK;
 }
 
 size_t rulgnn_gru_workspace_bytes(const rulgnn_gru_shape* shape) { return gru_workspace_bytes(shape); }
 
 int rulgnn_gru_forward_f32(const rulgnn_gru_shape* shape, const rulgnn_gru_args* args, void* stream) {
-    if (!shape || !args) return RULGNN_EINVAL;
-    int rc = check_ptrs({args->w_ih, args->w_hh, args->b_ih, args->b_hh, args->workspace});
-    if (rc != RULGNN_OK) return rc;
-    if (shape->num_seq > 0) {
-        rc = check_ptrs({args->x, args->out});
-        if (rc != RULGNN_OK) return rc;
-    }
+    RULGNN_TRY(check_gru_fwd(shape, args));
     return gru_forward(shape, args, static_cast<hipStream_t>(stream));
 }
 
 int rulgnn_gru_backward_f32(const rulgnn_gru_shape* shape, const rulgnn_gru_args* args, void* stream) {
-    if (!shape || !args) return RULGNN_EINVAL;
-    int rc = check_ptrs({args->w_ih, args->w_hh, args->b_ih, args->b_hh, args->workspace, args->dw_ih, args->dw_hh, args->db_ih,
-                         args->db_hh});
-    if (rc != RULGNN_OK) return rc;
-    if (shape->num_seq > 0) {
-        rc = check_ptrs({args->x, args->dout});
-        if (rc != RULGNN_OK) return rc;
-    }
+    RULGNN_TRY(check_gru_bwd(shape, args));
     return gru_backward(shape, args, static_cast<hipStream_t>(stream));
 }
 
 size_t rulgnn_gru_persistent_workspace_bytes(const rulgnn_gru_shape* shape) { return gru_persistent_workspace_bytes(shape); }
 
 int rulgnn_gru_persistent_forward_f32(const rulgnn_gru_shape* shape, const rulgnn_gru_args* args, void* stream) {
-    if (!shape || !args) return RULGNN_EINVAL;
-    int rc = check_ptrs({args->w_ih, args->w_hh, args->b_ih, args->b_hh, args->workspace});
-    if (rc != RULGNN_OK) return rc;
-    if (shape->num_seq > 0) {
-        rc = check_ptrs({args->x, args->out});
-        if (rc != RULGNN_OK) return rc;
-    }
+    RULGNN_TRY(check_gru_fwd(shape, args));
     return gru_persistent_forward(shape, args, static_cast<hipStream_t>(stream));
 }
 
 int rulgnn_gru_persistent_backward_f32(const rulgnn_gru_shape* shape, const rulgnn_gru_args* args, void* stream) {
-    if (!shape || !args) return RULGNN_EINVAL;
-    int rc = check_ptrs({args->w_ih, args->w_hh, args->b_ih, args->b_hh, args->workspace, args->dw_ih, args->dw_hh, args->db_ih,
-                         args->db_hh});
-    if (rc != RULGNN_OK) return rc;
-    if (shape->num_seq > 0) {
-        rc = check_ptrs({args->x, args->dout});
-        if (rc != RULGNN_OK) return rc;
-    }
-    if (args->dx && (reinterpret_cast<uintptr_t>(args->dx) & 3)) return RULGNN_EALIGN;
+    RULGNN_TRY(check_gru_bwd(shape, args));
+    if (!opt_aligned(args->dx)) return RULGNN_EALIGN;
     return gru_persistent_backward(shape, args, static_cast<hipStream_t>(stream));
 }
 
@@ -1122,20 +1066,10 @@ static int check_grucm(const rulgnn_grucm_shape* shape, const rulgnn_grucm_args*
         if (!(a->dropout_p[site] >= 0.f && a->dropout_p[site] < 1.f)) return RULGNN_EINVAL;
     if (a->gru_path != RULGNN_GRUCM_GRU_AUTO && a->gru_path != RULGNN_GRUCM_GRU_STEP_LOOP && a->gru_path != RULGNN_GRUCM_GRU_PERSISTENT)
         return RULGNN_EINVAL;
-    int rc = check_ptrs({a->params, a->workspace});
-    if (rc != RULGNN_OK) return rc;
-    if (shape->batch > 0) {
-        rc = check_ptrs({a->x, a->pred});
-        if (rc != RULGNN_OK) return rc;
-    }
+    RULGNN_TRY(check_fwd_ptrs(a->params, a->workspace, a->x, a->pred, shape->batch));
     for (const void* p : {(const void*)a->y, (const void*)a->dpred, (const void*)a->loss})
-        if (p && (reinterpret_cast<uintptr_t>(p) & 3)) return RULGNN_EALIGN;
-    if (bwd) {
-        rc = check_ptrs({a->grads});
-        if (rc != RULGNN_OK) return rc;
-        if (!a->dpred && !a->y && shape->batch > 0) return RULGNN_EINVAL;
-    }
-    return RULGNN_OK;
+        if (!opt_aligned(p)) return RULGNN_EALIGN;
+    return bwd ? check_bwd_ptrs(a->grads, a->y, a->dpred, shape->batch) : RULGNN_OK;
 }
 
 int rulgnn_grucm_forward_f32(const rulgnn_grucm_shape* shape, const rulgnn_grucm_args* args, void* stream) {
@@ -1151,14 +1085,9 @@ int rulgnn_grucm_backward_f32(const rulgnn_grucm_shape* shape, const rulgnn_gruc
 }
 
 int rulgnn_grucm_fwdbwd_f32(const rulgnn_grucm_shape* shape, const rulgnn_grucm_args* args, const rulgnn_adam_args* opt, void* stream) {
-    int rc = check_grucm(shape, args, true);
-    if (rc != RULGNN_OK) return rc;
-    if (args->dpred || (!args->y && shape->batch > 0)) return RULGNN_EINVAL;
-    if (opt && (rc = check_adam(opt, args->params)) != RULGNN_OK) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    rc = grucm_run(shape, args, 3, st);
-    if (rc != RULGNN_OK || !opt) return rc;
-    return adam_tail(opt, args->grads, 0, grucm_param_count(shape), st);
+    RULGNN_TRY(check_grucm(shape, args, true));
+    auto run = [&](hipStream_t st) { return grucm_run(shape, args, 3, st); };
+    return fused_step_tail(args->dpred, !args->y && shape->batch > 0, opt, args->params, run, args->grads, 0, grucm_param_count(shape), stream);
 }
 
 size_t rulgnn_rul_metrics_workspace_bytes(int64_t n) { return rul_metrics_workspace_bytes(n); }

@@ -23,7 +23,7 @@
 #include <stdint.h>
 
 #include "sgemm_mfma.hpp"
-#include "stgcn_host.hpp"
+#include "families_host.hpp"
 
 namespace rulgnn {
 
@@ -638,11 +638,6 @@ int64_t sagcn_tap_offset(const rulgnn_sagcn_shape* s, int which) {
     }
 }
 
-#define SG_RC(call)                        \
-    do {                                   \
-        const int rc_ = (call);            \
-        if (rc_ != RULGNN_OK) return rc_;  \
-    } while (0)
 #define SG_LAUNCH_OK()                                           \
     do {                                                         \
         if (hipGetLastError() != hipSuccess) return RULGNN_EHIP; \
@@ -651,7 +646,7 @@ int64_t sagcn_tap_offset(const rulgnn_sagcn_shape* s, int which) {
 // mode bit 0: forward, bit 1: backward (after a forward with the same args / workspace)
 int sagcn_run(const rulgnn_sagcn_shape* s, const rulgnn_sagcn_args* a, int mode, hipStream_t st) {
     SgGeom g;
-    SG_RC(sg_geometry(s, &g));
+    RULGNN_TRY(sg_geometry(s, &g));
     if (a->workspace_bytes < (size_t)g.total * sizeof(float)) return RULGNN_EWORKSPACE;
     if (g.B == 0) return RULGNN_OK;
     float* ws = static_cast<float*>(a->workspace);
@@ -678,7 +673,7 @@ int sagcn_run(const rulgnn_sagcn_shape* s, const rulgnn_sagcn_args* a, int mode,
         hipLaunchKernelGGL(sg_patch_features_kernel<GB>, dim3((unsigned)(g.R < 16384 ? g.R : 16384)), dim3(GB), lds1, st, g, a->x, ws + g.w_raw);
         if (P % 16 == 0 && P <= 128) {
             const size_t lm = sg_graph_mx_lds(P);
-            SG_RC(allow_dynamic_lds(sg_graph_mx_kernel, lm));
+            RULGNN_TRY(allow_dynamic_lds(sg_graph_mx_kernel, lm));
             hipLaunchKernelGGL(sg_graph_mx_kernel, dim3((unsigned)(g.B < 4096 ? g.B : 4096)), dim3(GB), lm, st, g, (const float*)(ws + g.w_raw),
                            ws + g.w_feat, ws + g.w_ax);
         } else
@@ -686,21 +681,21 @@ int sagcn_run(const rulgnn_sagcn_shape* s, const rulgnn_sagcn_args* a, int mode,
                            ws + g.w_feat, ws + g.w_ax);
         SG_LAUNCH_OK();
         // gcn1: [R, 40] x W1^T
-        SG_RC(sgemm(ws + g.w_ax, SG_F, 1, prm + g.o_w1, SG_F, 1, h1, H, R, H, SG_F, false, st));
+        RULGNN_TRY(sgemm(ws + g.w_ax, SG_F, 1, prm + g.o_w1, SG_F, 1, h1, H, R, H, SG_F, false, st));
         hipLaunchKernelGGL(sg_bias_cols_kernel, dim3(sg_grid(RH)), dim3(GB), 0, st, h1, prm + g.o_b1, (int64_t)R, H, 1);
         for (int i = 0; i < 2; ++i) {
             // node axis: U [P, B*H] = Wp [P, P] x h [P, B*H] + bp[p]
-            SG_RC(sgemm(prm + g.o_wp[i], P, 1, hh[i], 1, BH, u[i], BH, P, BH, P, false, st));
+            RULGNN_TRY(sgemm(prm + g.o_wp[i], P, 1, hh[i], 1, BH, u[i], BH, P, BH, P, false, st));
             hipLaunchKernelGGL(sg_bias_rows_kernel, dim3(sg_grid(RH)), dim3(GB), 0, st, u[i], prm + g.o_bp[i], P, (int64_t)BH, 0);
             // feature axis: [R, H] x Wl^T + bl, ReLU
-            SG_RC(sgemm(u[i], H, 1, prm + g.o_wl[i], H, 1, hh[i + 1], H, R, H, H, false, st));
+            RULGNN_TRY(sgemm(u[i], H, 1, prm + g.o_wl[i], H, 1, hh[i + 1], H, R, H, H, false, st));
             hipLaunchKernelGGL(sg_bias_cols_kernel, dim3(sg_grid(RH)), dim3(GB), 0, st, hh[i + 1], prm + g.o_bl[i], (int64_t)R, H, 1);
         }
         SG_LAUNCH_OK();
         // attention: S [Ah, B*H] = tanh(Wt [Ah, P] x h3 + bt[a]) ; logits [P, B*H] = Ws [P, Ah] x S (+ bs[p] in the head kernel)
-        SG_RC(sgemm(prm + g.o_wt, P, 1, hh[2], 1, BH, S, BH, Ah, BH, P, false, st));
+        RULGNN_TRY(sgemm(prm + g.o_wt, P, 1, hh[2], 1, BH, S, BH, Ah, BH, P, false, st));
         hipLaunchKernelGGL(sg_bias_rows_kernel, dim3(sg_grid((int64_t)Ah * BH)), dim3(GB), 0, st, S, prm + g.o_bt, Ah, (int64_t)BH, 2);
-        SG_RC(sgemm(prm + g.o_ws, Ah, 1, S, 1, BH, attn, BH, P, BH, Ah, false, st));
+        RULGNN_TRY(sgemm(prm + g.o_ws, Ah, 1, S, 1, BH, attn, BH, P, BH, Ah, false, st));
         {
             const int64_t waves = g.B * ((H + 63) / 64);
             hipLaunchKernelGGL(sg_attn_head_kernel, dim3((unsigned)(waves < 65536 ? waves : 65536)), dim3(64), 0, st, g, attn, (const float*)hh[2], prm,
@@ -723,39 +718,39 @@ int sagcn_run(const rulgnn_sagcn_shape* s, const rulgnn_sagcn_args* a, int mode,
         // head + softmax: dA = d h3 (direct path), dB = d logits
         hipLaunchKernelGGL(sg_fcw_kernel, dim3(sg_grid((int64_t)P * H)), dim3(GB), 0, st, g, (const float*)attn, (const float*)hh[2], dpred,
                            gr + g.o_wfc);
-        SG_RC(sgemm_splitk(dpred, 0, 1, one, 0, 0, gr + g.o_bfc, 1, 1, 1, (int)g.B, false, split, st));
+        RULGNN_TRY(sgemm_splitk(dpred, 0, 1, one, 0, 0, gr + g.o_bfc, 1, 1, 1, (int)g.B, false, split, st));
         hipLaunchKernelGGL(sg_attn_head_bwd_kernel, dim3(sg_grid(BH)), dim3(GB), 0, st, g, (const float*)attn, (const float*)hh[2], prm, dpred, dA, dB);
         SG_LAUNCH_OK();
-        SG_RC(sgemm_splitk(dB, BH, 1, S, BH, 1, gr + g.o_ws, Ah, P, Ah, BH, false, split, st));
+        RULGNN_TRY(sgemm_splitk(dB, BH, 1, S, BH, 1, gr + g.o_ws, Ah, P, Ah, BH, false, split, st));
         hipLaunchKernelGGL(sg_rowsum_kernel, dim3(P, SG_ROW_SLICES), dim3(GB), 0, st, (const float*)dB, (int64_t)BH, ws + g.w_rowpart);
         hipLaunchKernelGGL(sg_rowsum_finish_kernel, dim3((P + GB - 1) / GB), dim3(GB), 0, st, (const float*)(ws + g.w_rowpart), P, gr + g.o_bs);
         // d S [Ah, B*H] = Ws^T x d logits ; through tanh
-        SG_RC(sgemm(prm + g.o_ws, 1, Ah, dB, 1, BH, ds, BH, Ah, BH, P, false, st));
+        RULGNN_TRY(sgemm(prm + g.o_ws, 1, Ah, dB, 1, BH, ds, BH, Ah, BH, P, false, st));
         hipLaunchKernelGGL(sg_tanh_bwd_kernel, dim3(sg_grid((int64_t)Ah * BH)), dim3(GB), 0, st, ds, (const float*)S, (int64_t)Ah * BH);
-        SG_RC(sgemm_splitk(ds, BH, 1, hh[2], BH, 1, gr + g.o_wt, P, Ah, P, BH, false, split, st));
+        RULGNN_TRY(sgemm_splitk(ds, BH, 1, hh[2], BH, 1, gr + g.o_wt, P, Ah, P, BH, false, split, st));
         hipLaunchKernelGGL(sg_rowsum_kernel, dim3(Ah, SG_ROW_SLICES), dim3(GB), 0, st, (const float*)ds, (int64_t)BH, ws + g.w_rowpart);
         hipLaunchKernelGGL(sg_rowsum_finish_kernel, dim3((Ah + GB - 1) / GB), dim3(GB), 0, st, (const float*)(ws + g.w_rowpart), Ah, gr + g.o_bt);
         // d h3 += Wt^T x d(tanh input)
-        SG_RC(sgemm(prm + g.o_wt, 1, P, ds, 1, BH, dA, BH, P, BH, Ah, true, st));
+        RULGNN_TRY(sgemm(prm + g.o_wt, 1, P, ds, 1, BH, dA, BH, P, BH, Ah, true, st));
         SG_LAUNCH_OK();
         float* d = dA;
         float* other = dB;
         for (int i = 1; i >= 0; --i) {
             hipLaunchKernelGGL(sg_relu_bwd_kernel, dim3(sg_grid(RH)), dim3(GB), 0, st, d, (const float*)hh[i + 1], RH);
-            SG_RC(sgemm_splitk(d, 1, H, u[i], 1, H, gr + g.o_wl[i], H, H, H, R, false, split, st));
-            SG_RC(sgemm_splitk(one, 0, 0, d, 1, H, gr + g.o_bl[i], H, 1, H, R, false, split, st));
+            RULGNN_TRY(sgemm_splitk(d, 1, H, u[i], 1, H, gr + g.o_wl[i], H, H, H, R, false, split, st));
+            RULGNN_TRY(sgemm_splitk(one, 0, 0, d, 1, H, gr + g.o_bl[i], H, 1, H, R, false, split, st));
             // d U [R, H] = d V [R, H] x Wl
-            SG_RC(sgemm(d, H, 1, prm + g.o_wl[i], 1, H, other, H, R, H, H, false, st));
-            SG_RC(sgemm_splitk(other, BH, 1, hh[i], BH, 1, gr + g.o_wp[i], P, P, P, BH, false, split, st));
+            RULGNN_TRY(sgemm(d, H, 1, prm + g.o_wl[i], 1, H, other, H, R, H, H, false, st));
+            RULGNN_TRY(sgemm_splitk(other, BH, 1, hh[i], BH, 1, gr + g.o_wp[i], P, P, P, BH, false, split, st));
             hipLaunchKernelGGL(sg_rowsum_kernel, dim3(P, SG_ROW_SLICES), dim3(GB), 0, st, (const float*)other, (int64_t)BH, ws + g.w_rowpart);
             hipLaunchKernelGGL(sg_rowsum_finish_kernel, dim3((P + GB - 1) / GB), dim3(GB), 0, st, (const float*)(ws + g.w_rowpart), P, gr + g.o_bp[i]);
             // d h_in [P, B*H] = Wp^T x d U
-            SG_RC(sgemm(prm + g.o_wp[i], 1, P, other, 1, BH, d, BH, P, BH, P, false, st));
+            RULGNN_TRY(sgemm(prm + g.o_wp[i], 1, P, other, 1, BH, d, BH, P, BH, P, false, st));
             SG_LAUNCH_OK();
         }
         hipLaunchKernelGGL(sg_relu_bwd_kernel, dim3(sg_grid(RH)), dim3(GB), 0, st, d, (const float*)h1, RH);
-        SG_RC(sgemm_splitk(d, 1, H, ws + g.w_ax, 1, SG_F, gr + g.o_w1, SG_F, H, SG_F, R, false, split, st));
-        SG_RC(sgemm_splitk(one, 0, 0, d, 1, H, gr + g.o_b1, H, 1, H, R, false, split, st));
+        RULGNN_TRY(sgemm_splitk(d, 1, H, ws + g.w_ax, 1, SG_F, gr + g.o_w1, SG_F, H, SG_F, R, false, split, st));
+        RULGNN_TRY(sgemm_splitk(one, 0, 0, d, 1, H, gr + g.o_b1, H, 1, H, R, false, split, st));
         SG_LAUNCH_OK();
     }
     return RULGNN_OK;

@@ -18,7 +18,7 @@
 #include <stdint.h>
 
 #include "sgemm_mfma.hpp"
-#include "stgcn_host.hpp"
+#include "families_host.hpp"
 
 namespace rulgnn {
 
@@ -1508,11 +1508,6 @@ int64_t stagnn_tap_offset(const rulgnn_stagnn_shape* s, int which) {
     }
 }
 
-#define TG_RC(call)                        \
-    do {                                   \
-        const int rc_ = (call);            \
-        if (rc_ != RULGNN_OK) return rc_;  \
-    } while (0)
 #define TG_LAUNCH_OK()                                           \
     do {                                                         \
         if (hipGetLastError() != hipSuccess) return RULGNN_EHIP; \
@@ -1521,7 +1516,7 @@ int64_t stagnn_tap_offset(const rulgnn_stagnn_shape* s, int which) {
 // mode bit 0: forward, bit 1: backward (after a TRAINING forward with the same args / workspace)
 int stagnn_run(const rulgnn_stagnn_shape* s, const rulgnn_stagnn_args* a, int mode, hipStream_t st) {
     TgGeom g;
-    TG_RC(tg_geometry(s, &g));
+    RULGNN_TRY(tg_geometry(s, &g));
     if (a->workspace_bytes < (size_t)g.total * sizeof(float)) return RULGNN_EWORKSPACE;
     if (g.B == 0) return RULGNN_OK;
     float* ws = static_cast<float*>(a->workspace);
@@ -1536,7 +1531,7 @@ int stagnn_run(const rulgnn_stagnn_shape* s, const rulgnn_stagnn_args* a, int mo
     if (mode & 1) {
         const int G = tg_head_groups(g, false);
         const size_t lg = tg_lds_graph_fwd(g, G);
-        TG_RC(allow_dynamic_lds(tg_graph_fwd_kernel, lg));
+        RULGNN_TRY(allow_dynamic_lds(tg_graph_fwd_kernel, lg));
         hipLaunchKernelGGL(tg_graph_fwd_kernel, grid, dim3(TB * G), lg, st, g, G, a->x, prm, ws);
         TG_LAUNCH_OK();
         for (int l = 0; l < 2; ++l) {
@@ -1544,17 +1539,17 @@ int stagnn_run(const rulgnn_stagnn_shape* s, const rulgnn_stagnn_args* a, int mo
             const size_t l1 = sizeof(float) * ((size_t)Ci * TP + (size_t)Co * TP + 2 * (size_t)Co * Ci);
             const size_t l2 = sizeof(float) * ((size_t)Ci * TP + 2 * (size_t)Co * TP + 2 * Co + (size_t)Co * Ci + 2 * (size_t)Co * Co);
             const size_t l3 = sizeof(float) * ((size_t)Co * TP + (size_t)Hd * T + T + 2 * Co + TB + (size_t)Hd * Co);
-            TG_RC(allow_dynamic_lds(tg_conv1_fwd_kernel, l1));
-            TG_RC(allow_dynamic_lds(tg_mid_fwd_kernel, l2));
-            TG_RC(allow_dynamic_lds(tg_end_fwd_kernel, l3));
+            RULGNN_TRY(allow_dynamic_lds(tg_conv1_fwd_kernel, l1));
+            RULGNN_TRY(allow_dynamic_lds(tg_mid_fwd_kernel, l2));
+            RULGNN_TRY(allow_dynamic_lds(tg_end_fwd_kernel, l3));
             if (tg_conv1_mx_ok(g, l)) {
                 const size_t l1m = tg_conv1_fwd_mx_lds(g, l);
-                TG_RC(allow_dynamic_lds(tg_conv1_fwd_mx_kernel, l1m));
+                RULGNN_TRY(allow_dynamic_lds(tg_conv1_fwd_mx_kernel, l1m));
                 hipLaunchKernelGGL(tg_conv1_fwd_mx_kernel, grid, blk, l1m, st, g, l, stage_in[l], prm, ws);
             } else
             hipLaunchKernelGGL(tg_conv1_fwd_kernel, grid, blk, l1, st, g, l, stage_in[l], prm, ws);
             if (tg_mid_mx_ok(g, l)) {
-                TG_RC(allow_dynamic_lds(tg_mid_fwd_mx_kernel, TM_FWD_LDS));
+                RULGNN_TRY(allow_dynamic_lds(tg_mid_fwd_mx_kernel, TM_FWD_LDS));
                 hipLaunchKernelGGL(tg_mid_fwd_mx_kernel, grid, blk, TM_FWD_LDS, st, g, l, stage_in[l], prm, (const float*)a->bn_state, ws, training);
             } else
             hipLaunchKernelGGL(tg_mid_fwd_kernel, grid, blk, l2, st, g, l, stage_in[l], prm, (const float*)a->bn_state, ws, training);
@@ -1575,19 +1570,19 @@ int stagnn_run(const rulgnn_stagnn_shape* s, const rulgnn_stagnn_args* a, int mo
             const size_t l3 = sizeof(float) * (2 * (size_t)Co * TP + 3 * (size_t)Hd * T + T + 2 * Co + Hd + (size_t)Hd * Co);
             const size_t l2 = sizeof(float) * ((size_t)Ci * TP + 3 * (size_t)Co * TP + 6 * Co + (size_t)Co * Ci + 2 * (size_t)Co * Co);
             const size_t l1 = sizeof(float) * ((size_t)Ci * TP + (size_t)Co * TP + 4 * Co + 2 * (size_t)Co * Ci);
-            TG_RC(allow_dynamic_lds(tg_mid_bwd_kernel, l2));
-            TG_RC(allow_dynamic_lds(tg_end_bwd_kernel, l3));
-            TG_RC(allow_dynamic_lds(tg_conv1_bwd_kernel, l1));
+            RULGNN_TRY(allow_dynamic_lds(tg_mid_bwd_kernel, l2));
+            RULGNN_TRY(allow_dynamic_lds(tg_end_bwd_kernel, l3));
+            RULGNN_TRY(allow_dynamic_lds(tg_conv1_bwd_kernel, l1));
             // (the gradient w.r.t. a stage's input is written over w_dxin[l], which the next kernel down the chain reads)
             hipLaunchKernelGGL(tg_end_bwd_kernel, grid, blk, l3, st, g, l, prm, (const float*)a->bn_state, ws, dpred, (const float*)(ws + g.w_dxin[1]));
             if (tg_mid_mx_ok(g, l)) {
-                TG_RC(allow_dynamic_lds(tg_mid_bwd_mx_kernel, TM_BWD_LDS));
+                RULGNN_TRY(allow_dynamic_lds(tg_mid_bwd_mx_kernel, TM_BWD_LDS));
                 hipLaunchKernelGGL(tg_mid_bwd_mx_kernel, grid, blk, TM_BWD_LDS, st, g, l, stage_in[l], prm, (const float*)a->bn_state, ws);
             } else
             hipLaunchKernelGGL(tg_mid_bwd_kernel, grid, blk, l2, st, g, l, stage_in[l], prm, (const float*)a->bn_state, ws);
             if (tg_conv1_mx_ok(g, l)) {
                 const size_t l1m = tg_conv1_bwd_mx_lds(g, l);
-                TG_RC(allow_dynamic_lds(tg_conv1_bwd_mx_kernel, l1m));
+                RULGNN_TRY(allow_dynamic_lds(tg_conv1_bwd_mx_kernel, l1m));
                 hipLaunchKernelGGL(tg_conv1_bwd_mx_kernel, grid, blk, l1m, st, g, l, stage_in[l], prm, (const float*)a->bn_state, ws, ws + g.w_dxin[l]);
             } else
             hipLaunchKernelGGL(tg_conv1_bwd_kernel, grid, blk, l1, st, g, l, stage_in[l], prm, (const float*)a->bn_state, ws, ws + g.w_dxin[l]);
@@ -1595,10 +1590,10 @@ int stagnn_run(const rulgnn_stagnn_shape* s, const rulgnn_stagnn_args* a, int mo
         }
         const int G = tg_head_groups(g, true);
         const size_t lg = tg_lds_graph_bwd(g, G);
-        TG_RC(allow_dynamic_lds(tg_graph_bwd_kernel, lg));
+        RULGNN_TRY(allow_dynamic_lds(tg_graph_bwd_kernel, lg));
         hipLaunchKernelGGL(tg_graph_bwd_kernel, grid, dim3(TB * G), lg, st, g, G, prm, ws);
         TG_LAUNCH_OK();
-        TG_RC(rows_sum(ws + g.w_gpart, g.nblk, g.pcount, g.pcount, a->grads, st));
+        RULGNN_TRY(rows_sum(ws + g.w_gpart, g.nblk, g.pcount, g.pcount, a->grads, st));
     }
     return RULGNN_OK;
 }

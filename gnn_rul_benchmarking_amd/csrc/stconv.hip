@@ -10,7 +10,7 @@
 // The TCN is the block shared with ASTGCNN (tcn_nodes.hpp); the theta projection and the weight gradients with a long
 // reduction are MFMA GEMMs (sgemm_mfma.hpp); the rest is one workgroup per sample with the [nodes x time] tile in LDS.
 #include "sgemm_mfma.hpp"
-#include "stgcn_host.hpp"
+#include "families_host.hpp"
 #include "tcn_nodes.hpp"
 
 namespace rulgnn {
@@ -424,40 +424,27 @@ struct ScWs {
 };
 
 void sc_ws_layout(const ScGeom& g, ScWs* w) {
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t BNT = (size_t)g.B * g.NT * sizeof(float);
-    size_t o = 0;
-    w->cells = o; o = al(o + sizeof(Cells) * CELL_REP);
-    w->c3 = o; o = al(o + sizeof(Cells3) * CELL_REP);
-    w->one = o; o = al(o + 256);
-    for (size_t* p : {&w->ax, &w->gpre, &w->zc, &w->z1, &w->out0, &w->z2, &w->res, &w->ds1, &w->dy2, &w->dyc, &w->dy1}) {
-        *p = o;
-        o = al(o + BNT);
-    }
-    w->dpred = o; o = al(o + (size_t)g.B * sizeof(float));
-    w->sqerr = o; o = al(o + (size_t)g.B * sizeof(float));
+    const size_t BNT = (size_t)g.B * g.NT;
+    WsCarver c;
+    w->cells = c.take_bytes(sizeof(Cells) * CELL_REP);
+    w->c3 = c.take_bytes(sizeof(Cells3) * CELL_REP);
+    w->one = c.take_bytes(256);
+    for (size_t* p : {&w->ax, &w->gpre, &w->zc, &w->z1, &w->out0, &w->z2, &w->res, &w->ds1, &w->dy2, &w->dyc, &w->dy1}) *p = c.take<float>(BNT);
+    w->dpred = c.take<float>((size_t)g.B);
+    w->sqerr = c.take<float>((size_t)g.B);
     w->rows = 1024;
     const size_t nW = (size_t)g.N * g.N * KT;
-    w->gp1 = o; o = al(o + w->rows * nW * sizeof(float));
-    w->gp2 = o; o = al(o + w->rows * nW * sizeof(float));
-    w->gp3 = o; o = al(o + w->rows * (nW + g.N) * sizeof(float));
+    w->gp1 = c.take<float>(w->rows * nW);
+    w->gp2 = c.take<float>(w->rows * nW);
+    w->gp3 = c.take<float>(w->rows * (nW + g.N));
     size_t mx = 1;
     auto need = [&](int M, int Nn, int64_t K) {
         const size_t v = sgemm_splitk_need_floats(M, Nn, (int)K);
         if (v > mx) mx = v;
     };
     need(g.T, g.T, g.B * g.N); need(1, g.T, g.B * g.N); need(1, g.NT, g.B); need(1, 1, g.B);
-    w->split = o; o = al(o + mx * sizeof(float));
-    w->total = o;
-}
-
-template <typename K>
-int sc_rows(K kernel, int64_t items, int cap) {
-    auto [cus, per_cu] = residency(kernel, AB, 0);
-    int64_t want = (int64_t)cus * per_cu;
-    if (want > items) want = items;
-    if (want > cap) want = cap;
-    return want < 1 ? 1 : (int)want;
+    w->split = c.take<float>(mx);
+    w->total = c.total();
 }
 
 }  // namespace
@@ -475,33 +462,27 @@ size_t stconv_workspace_bytes(const rulgnn_stconv_shape* s) {
     return w.total;
 }
 
-#define SC_RC(call)                        \
-    do {                                   \
-        const int rc_ = (call);            \
-        if (rc_ != RULGNN_OK) return rc_;  \
-    } while (0)
-
 // mode bit 0: forward (args->training: batch / running statistics), bit 1: backward.  The args struct is ASTGCNN's.
 int stconv_run(const rulgnn_stconv_shape* s, const rulgnn_astgcnn_args* a, int mode, hipStream_t st) {
     ScGeom g;
-    SC_RC(sc_geometry(s, &g));
+    RULGNN_TRY(sc_geometry(s, &g));
     ScWs w;
     sc_ws_layout(g, &w);
     if (a->workspace_bytes < w.total) return RULGNN_EWORKSPACE;
-    char* ws = static_cast<char*>(a->workspace);
-    auto F = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
-    Cells* cells = reinterpret_cast<Cells*>(ws + w.cells);
-    Cells3* c3 = reinterpret_cast<Cells3*>(ws + w.c3);
+    const Workspace ws(a->workspace);
+    auto F = [&](size_t off) { return ws.at<float>(off); };
+    Cells* cells = ws.at<Cells>(w.cells);
+    Cells3* c3 = ws.at<Cells3>(w.c3);
     const float* prm = a->params;
     const int training = a->training ? 1 : 0;
     const int N = g.N, T = g.T, M = (int)(g.B * N);
     const float inv_gb = 1.0f / (float)(a->global_batch > 0 ? a->global_batch : g.B);
     (void)hipGetLastError();
-    const int rows = sc_rows(sc_cnn_bwd_kernel, g.B, w.rows);
+    const int rows = resident_rows(sc_cnn_bwd_kernel, AB, 0, g.B, w.rows);
     if (mode & 1) {
         if (hipMemsetAsync(cells, 0, w.one - w.cells, st) != hipSuccess) return RULGNN_EHIP;     // both cell blocks
         hipLaunchKernelGGL(sc_graph_kernel, dim3(rows), dim3(AB), 0, st, g, a->x, F(w.ax));
-        SC_RC(sgemm(F(w.ax), T, 1, prm + g.o_gw, T, 1, F(w.gpre), T, M, T, T, false, st));
+        RULGNN_TRY(sgemm(F(w.ax), T, 1, prm + g.o_gw, T, 1, F(w.gpre), T, M, T, T, false, st));
         hipLaunchKernelGGL(sc_cnn_kernel, dim3(rows), dim3(AB), 0, st, g, prm, F(w.gpre), F(w.zc), c3, training);
         hipLaunchKernelGGL((tcn_conv_kernel<1, ScGeom>), dim3(rows), dim3(AB), 0, st, g, a->x, prm, a->bn_stats, training,
                            (const float*)nullptr, F(w.z1), (float*)nullptr, cells);
@@ -522,8 +503,8 @@ int stconv_run(const rulgnn_stconv_shape* s, const rulgnn_astgcnn_args* a, int m
         if (a->dpred && hipMemcpyAsync(F(w.dpred), a->dpred, sizeof(float) * g.B, hipMemcpyDeviceToDevice, st) != hipSuccess)
             return RULGNN_EHIP;
         // fc: d weight = dpred^T res ; d bias = sum dpred
-        SC_RC(sgemm_splitk(F(w.dpred), 0, 1, F(w.res), 1, g.NT, gr + g.o_fcw, g.NT, 1, g.NT, (int)g.B, false, split, st));
-        SC_RC(sgemm_splitk(F(w.dpred), 0, 1, one, 0, 0, gr + g.o_fcb, 1, 1, 1, (int)g.B, false, split, st));
+        RULGNN_TRY(sgemm_splitk(F(w.dpred), 0, 1, F(w.res), 1, g.NT, gr + g.o_fcw, g.NT, 1, g.NT, (int)g.B, false, split, st));
+        RULGNN_TRY(sgemm_splitk(F(w.dpred), 0, 1, one, 0, 0, gr + g.o_fcb, 1, 1, 1, (int)g.B, false, split, st));
         hipLaunchKernelGGL(sc_head_kernel<1>, dim3(rows), dim3(AB), 0, st, g, a->x, prm, a->bn_stats, 1, cells, c3, (const float*)F(w.zc),
                            (const float*)F(w.z2), (const float*)F(w.out0), (const float*)nullptr, (float*)nullptr, (float*)nullptr,
                            F(w.dpred), (float*)nullptr, F(w.ds1), F(w.dy2), F(w.dyc), inv_gb);
@@ -535,17 +516,17 @@ int stconv_run(const rulgnn_stconv_shape* s, const rulgnn_astgcnn_args* a, int m
         hipLaunchKernelGGL(sc_cnn_bwd_kernel, dim3(rows), dim3(AB), 0, st, g, prm, (const Cells3*)c3, (const float*)F(w.zc),
                            (const float*)F(w.dyc), F(w.gpre), F(w.gp3));
         // theta of the MPNN: d weight = dgpre^T (A X) ; d bias = column sums
-        SC_RC(sgemm_splitk(F(w.gpre), 1, T, F(w.ax), 1, T, gr + g.o_gw, T, T, T, M, false, split, st));
-        SC_RC(sgemm_splitk(one, 0, 0, F(w.gpre), 1, T, gr + g.o_gb, T, 1, T, M, false, split, st));
+        RULGNN_TRY(sgemm_splitk(F(w.gpre), 1, T, F(w.ax), 1, T, gr + g.o_gw, T, T, T, M, false, split, st));
+        RULGNN_TRY(sgemm_splitk(one, 0, 0, F(w.gpre), 1, T, gr + g.o_gb, T, 1, T, M, false, split, st));
         {
             const int nW = N * N * KT;
             if (g.o_cb == g.o_cw + nW) {       // the convolution's weight and bias are neighbours in the flat buffer as in the partial rows: one launch for all
-                SC_RC(rows_sum3(F(w.gp1), gr + g.o_w1, F(w.gp2), gr + g.o_w2, rows, nW, nW, F(w.gp3), gr + g.o_cw, nullptr, rows, nW + N, nW + N, st));
+                RULGNN_TRY(rows_sum3(F(w.gp1), gr + g.o_w1, F(w.gp2), gr + g.o_w2, rows, nW, nW, F(w.gp3), gr + g.o_cw, nullptr, rows, nW + N, nW + N, st));
             } else {
-                SC_RC(rows_sum(F(w.gp1), rows, nW, nW, gr + g.o_w1, st));
-                SC_RC(rows_sum(F(w.gp2), rows, nW, nW, gr + g.o_w2, st));
-                SC_RC(rows_sum(F(w.gp3), rows, nW + N, nW, gr + g.o_cw, st));
-                SC_RC(rows_sum(F(w.gp3) + nW, rows, nW + N, N, gr + g.o_cb, st));
+                RULGNN_TRY(rows_sum(F(w.gp1), rows, nW, nW, gr + g.o_w1, st));
+                RULGNN_TRY(rows_sum(F(w.gp2), rows, nW, nW, gr + g.o_w2, st));
+                RULGNN_TRY(rows_sum(F(w.gp3), rows, nW + N, nW, gr + g.o_cw, st));
+                RULGNN_TRY(rows_sum(F(w.gp3) + nW, rows, nW + N, N, gr + g.o_cb, st));
             }
         }
         hipLaunchKernelGGL(sc_finalize_kernel, dim3((N + 4 + AB - 1) / AB), dim3(AB), 0, st, g, (const Cells*)cells, (const Cells3*)c3, gr);
@@ -558,7 +539,7 @@ int stconv_run(const rulgnn_stconv_shape* s, const rulgnn_astgcnn_args* a, int m
 int stconv_bn_running_update(const rulgnn_stconv_shape* s, float* bn_stats, const float* bn_batch, int64_t count, float momentum,
                              int from_moments, hipStream_t st) {
     ScGeom g;
-    SC_RC(sc_geometry(s, &g));
+    RULGNN_TRY(sc_geometry(s, &g));
     (void)hipGetLastError();
     hipLaunchKernelGGL(sc_bn_running_kernel, dim3(1), dim3(128), 0, st, bn_stats, bn_batch, g.N, (double)count, momentum, from_moments);
     return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;

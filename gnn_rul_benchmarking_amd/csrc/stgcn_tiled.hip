@@ -8,6 +8,7 @@
 // holding the ten channels in registers; the causal taps t-1 / t-2 are read from the neighbour's
 // column in memory (coalesced along t).  Reference: models/ST_GCN/Model.py:7-222.
 #include "stgcn_device.hpp"
+#include "families_host.hpp"
 #include "stgcn_host.hpp"
 #include "sgemm_mfma.hpp"
 #include "aux_stream.hpp"
@@ -443,7 +444,6 @@ __global__ __launch_bounds__(256) void t_head_kernel(const float* __restrict__ y
 // ------------------------------------------------------------------------------------------------
 // host: eval forward
 // ------------------------------------------------------------------------------------------------
-static inline size_t al256(size_t v) { return (v + 255) & ~(size_t)255; }
 // split-K scratch of the eval forward: fc1 ([batch x N] . [N x N]: 64 tiles of 128 x 128 at batch 1024 -- through the split-K pair like
 // the training forward; as one launch of the 64 x 64 kernel it was 56 us of the 0.43-ms forward) and, at batch-100-sized row counts, theta
 static inline size_t t_eval_split_floats(int N, int64_t B) {
@@ -457,7 +457,7 @@ static inline size_t t_eval_split_floats(int N, int64_t B) {
 static inline size_t t_plane_bytes(int N, int64_t R, bool with_grad) {
     if (N % 256 != 0 || R < 2048 || R > (1 << 24)) return 0;
     const size_t fwd = sgemm_planes_ws_bytes((int)R, N, N), grad = with_grad ? sgemm_planes_ws_bytes(N, N, (int)R) : 0;
-    return al256(fwd > grad ? fwd : grad);
+    return ws_align(fwd > grad ? fwd : grad);
 }
 
 size_t stgcn_tiled_forward_workspace_bytes(const rulgnn_stgcn_shape* s) {
@@ -467,8 +467,8 @@ size_t stgcn_tiled_forward_workspace_bytes(const rulgnn_stgcn_shape* s) {
     const int64_t R = s->batch * F;
     const size_t sk = t_eval_split_floats(s->num_patch, s->batch);
     // (+ the pre-split operand planes of the theta products, csrc/sgemm_planes.hip)
-    return t_plane_bytes(s->num_patch, R, false) + 4 * al256(T) + al256((size_t)s->batch * F * F * 4) + 2 * al256((size_t)s->batch * s->num_patch * 4) +
-           al256((size_t)s->num_layers * 4 * F * 4) + al256((size_t)(2 + s->num_layers) * T_AMAX_MAX * sizeof(float)) + al256(sk * sizeof(float));
+    return t_plane_bytes(s->num_patch, R, false) + 4 * ws_align(T) + ws_align((size_t)s->batch * F * F * 4) + 2 * ws_align((size_t)s->batch * s->num_patch * 4) +
+           ws_align((size_t)s->num_layers * 4 * F * 4) + ws_align((size_t)(2 + s->num_layers) * T_AMAX_MAX * sizeof(float)) + ws_align(sk * sizeof(float));
 }
 
 // (persistent kernels: at most T_PGRID workgroups)
@@ -499,18 +499,18 @@ int stgcn_tiled_forward_eval(const rulgnn_stgcn_shape* s, const float* x, const 
     const int64_t B = s->batch, BN_ = B * N;
     TArgs a{B, N, s->patch_size, L};
     char* w = static_cast<char*>(workspace);
-    const size_t T = al256((size_t)B * F * N * sizeof(float));
+    const size_t T = ws_align((size_t)B * F * N * sizeof(float));
     float* Xa = reinterpret_cast<float*>(w); w += T;
     float* Xb = reinterpret_cast<float*>(w); w += T;
     float* AX = reinterpret_cast<float*>(w); w += T;
     float* Hpre = reinterpret_cast<float*>(w); w += T;
-    float* A = reinterpret_cast<float*>(w); w += al256((size_t)B * F * F * 4);
-    float* pooled = reinterpret_cast<float*>(w); w += al256((size_t)B * N * 4);
-    float* y1pre = reinterpret_cast<float*>(w); w += al256((size_t)B * N * 4);
-    float* bnf = reinterpret_cast<float*>(w); w += al256((size_t)L * 4 * F * 4);
-    float* amax = reinterpret_cast<float*>(w); w += al256((size_t)(2 + L) * T_AMAX_MAX * sizeof(float));   // A.X of the current layer, theta of every layer, X of the current layer
+    float* A = reinterpret_cast<float*>(w); w += ws_align((size_t)B * F * F * 4);
+    float* pooled = reinterpret_cast<float*>(w); w += ws_align((size_t)B * N * 4);
+    float* y1pre = reinterpret_cast<float*>(w); w += ws_align((size_t)B * N * 4);
+    float* bnf = reinterpret_cast<float*>(w); w += ws_align((size_t)L * 4 * F * 4);
+    float* amax = reinterpret_cast<float*>(w); w += ws_align((size_t)(2 + L) * T_AMAX_MAX * sizeof(float));   // A.X of the current layer, theta of every layer, X of the current layer
     float* amaxX = amax + (size_t)(1 + L) * T_AMAX_MAX;
-    float* split = reinterpret_cast<float*>(w); w += al256(t_eval_split_floats(N, B) * sizeof(float));
+    float* split = reinterpret_cast<float*>(w); w += ws_align(t_eval_split_floats(N, B) * sizeof(float));
     const size_t plane_bytes = t_plane_bytes(N, B * F, false);
     void* planes = plane_bytes ? static_cast<void*>(w) : nullptr;
     const bool few_rows = B * F < 2048;
@@ -1252,33 +1252,33 @@ static int t_pgrad_dims(int N, int L, int Bi, int R, SplitKJob* j) {
 static void tws_layout(const rulgnn_stgcn_shape* s, TWs* w) {
     const int N = s->num_patch, L = s->num_layers;
     const int64_t B = s->batch;
-    w->T = al256((size_t)B * F * N * sizeof(float));
+    w->T = ws_align((size_t)B * F * N * sizeof(float));
     w->grid = t_pgrid(B * N);
-    size_t o = 0;
-    w->off_X = o; o += (size_t)(L + 1) * w->T;
-    w->off_AX = o; o += (size_t)L * w->T;
-    w->off_H = o; o += (size_t)L * w->T;
-    w->off_z1 = o; o += (size_t)L * w->T;
-    w->off_o0 = o; o += (size_t)L * w->T;
-    w->off_z2 = o; o += (size_t)L * w->T;
-    w->off_gsum = o; o += w->T;
-    w->off_gsum0 = o; o += w->T;
-    w->off_dH = o; o += (size_t)L * w->T;          // per layer: the side stream's d theta product of layer l reads it while layer l - 1 runs
-    w->off_dAX = o; o += w->T;
-    w->off_dX = o; o += w->T;
-    const size_t BNb = al256((size_t)B * N * 4);
-    w->off_A = o; o += al256((size_t)B * F * F * 4);
-    w->off_pooled = o; o += BNb;
-    w->off_y1pre = o; o += BNb;
-    w->off_y1 = o; o += BNb;
-    w->off_dy1 = o; o += BNb;
-    w->off_dpool = o; o += BNb;
-    w->off_dpred = o; o += al256((size_t)B * 4);
+    WsCarver c;
+    w->off_X = c.take_bytes((size_t)(L + 1) * w->T);
+    w->off_AX = c.take_bytes((size_t)L * w->T);
+    w->off_H = c.take_bytes((size_t)L * w->T);
+    w->off_z1 = c.take_bytes((size_t)L * w->T);
+    w->off_o0 = c.take_bytes((size_t)L * w->T);
+    w->off_z2 = c.take_bytes((size_t)L * w->T);
+    w->off_gsum = c.take_bytes(w->T);
+    w->off_gsum0 = c.take_bytes(w->T);
+    w->off_dH = c.take_bytes((size_t)L * w->T);          // per layer: the side stream's d theta product of layer l reads it while layer l - 1 runs
+    w->off_dAX = c.take_bytes(w->T);
+    w->off_dX = c.take_bytes(w->T);
+    const size_t BNb = ws_align((size_t)B * N * 4);
+    w->off_A = c.take<float>((size_t)B * F * F);
+    w->off_pooled = c.take_bytes(BNb);
+    w->off_y1pre = c.take_bytes(BNb);
+    w->off_y1 = c.take_bytes(BNb);
+    w->off_dy1 = c.take_bytes(BNb);
+    w->off_dpool = c.take_bytes(BNb);
+    w->off_dpred = c.take<float>((size_t)B);
     w->cells_bytes = sizeof(double) * (size_t)T_REP * (tc_sf(L) + tc_sb(L));
-    w->off_cells = o; o += al256(w->cells_bytes);
-    w->off_gpart = o; o += al256((size_t)2 * L * w->grid * CONVW * 4);
-    w->off_one = o; o += 256;
-    w->off_amax = o; o += al256((size_t)(3 * L + 3) * T_AMAX_MAX * sizeof(float));
+    w->off_cells = c.take_bytes(w->cells_bytes);
+    w->off_gpart = c.take<float>((size_t)2 * L * w->grid * CONVW);
+    w->off_one = c.take_bytes(256);
+    w->off_amax = c.take<float>((size_t)(3 * L + 3) * T_AMAX_MAX);
     // partial products of the split-K weight / bias gradient GEMMs (reductions over batch * 10 or batch rows)
     {
         const int R = (int)(B * F), Bi = (int)B;
@@ -1296,13 +1296,13 @@ static void tws_layout(const rulgnn_stgcn_shape* s, TWs* w) {
             need = bf > need ? bf : need;
         }
         w->split_floats = need;
-        w->off_split = o; o += al256(need * sizeof(float));
-        w->off_split2 = o; o += al256(need * sizeof(float));          // the side stream's own (parameter-gradient products)
+        w->off_split = c.take<float>(need);
+        w->off_split2 = c.take<float>(need);          // the side stream's own (parameter-gradient products)
     }
     w->plane_bytes = t_plane_bytes(N, B * F, false);
-    w->off_planes = o; o += w->plane_bytes;
-    w->off_planes2 = o;                                                  // (the side stream's products stay on the in-loop split: no second area)
-    w->total = o;
+    w->off_planes = c.take_bytes(w->plane_bytes);
+    w->off_planes2 = c.total();                                                  // (the side stream's products stay on the in-loop split: no second area)
+    w->total = c.total();
 }
 
 size_t stgcn_tiled_train_workspace_bytes(const rulgnn_stgcn_shape* s) {
@@ -1320,23 +1320,23 @@ int stgcn_tiled_train(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args
     if (sync && mode != 2) return RULGNN_EINVAL;
     const int N = s->num_patch, L = s->num_layers, LS = layer_stride(N);
     const int64_t B = s->batch, BN_ = B * N;
-    char* ws = static_cast<char*>(ar->workspace);
-    auto TP = [&](size_t off, int l) { return reinterpret_cast<float*>(ws + off + (size_t)l * w.T); };
+    const Workspace ws(ar->workspace);
+    auto TP = [&](size_t off, int l) { return ws.at<float>(off + (size_t)l * w.T); };
     float* gsum = TP(w.off_gsum, 0); float* gsum0 = TP(w.off_gsum0, 0);
     float* dAX = TP(w.off_dAX, 0); float* dX = TP(w.off_dX, 0);
-    float* A = reinterpret_cast<float*>(ws + w.off_A);
-    float* pooled = reinterpret_cast<float*>(ws + w.off_pooled);
-    float* y1pre = reinterpret_cast<float*>(ws + w.off_y1pre);
-    float* y1 = reinterpret_cast<float*>(ws + w.off_y1);
-    float* dy1 = reinterpret_cast<float*>(ws + w.off_dy1);
-    float* dpool = reinterpret_cast<float*>(ws + w.off_dpool);
-    float* dpredb = reinterpret_cast<float*>(ws + w.off_dpred);
-    double* cells = reinterpret_cast<double*>(ws + w.off_cells);
-    float* gpart = reinterpret_cast<float*>(ws + w.off_gpart);
-    float* one = reinterpret_cast<float*>(ws + w.off_one);
-    float* split = reinterpret_cast<float*>(ws + w.off_split);
-    float* split2 = reinterpret_cast<float*>(ws + w.off_split2);
-    void* planes = w.plane_bytes ? static_cast<void*>(ws + w.off_planes) : nullptr;
+    float* A = ws.at<float>(w.off_A);
+    float* pooled = ws.at<float>(w.off_pooled);
+    float* y1pre = ws.at<float>(w.off_y1pre);
+    float* y1 = ws.at<float>(w.off_y1);
+    float* dy1 = ws.at<float>(w.off_dy1);
+    float* dpool = ws.at<float>(w.off_dpool);
+    float* dpredb = ws.at<float>(w.off_dpred);
+    double* cells = ws.at<double>(w.off_cells);
+    float* gpart = ws.at<float>(w.off_gpart);
+    float* one = ws.at<float>(w.off_one);
+    float* split = ws.at<float>(w.off_split);
+    float* split2 = ws.at<float>(w.off_split2);
+    void* planes = w.plane_bytes ? ws.at<void>(w.off_planes) : nullptr;
     void* planes2 = nullptr;
     // Which of the step's products run on pre-split operands (csrc/sgemm_planes.hip), measured at XJTU-SY batch 1024 on one box
     // (tools/time_tiled_step.py): none 1.1945 ms; theta(A.X) 1.1878; + d(A.X) 1.1857 (kept); + d theta 1.2109; + the fc1 products 1.2192.
@@ -1367,7 +1367,7 @@ int stgcn_tiled_train(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args
     hipStream_t wst = fk.side();
     // operand scales of the large GEMMs: partial maxima rows, one float per workgroup of the producing launch.  The scaled form only where
     // the producers' grids fit a row (every reference wiring does: <= 4096 chunks of 256 positions)
-    float* amax = reinterpret_cast<float*>(ws + w.off_amax);
+    float* amax = ws.at<float>(w.off_amax);
     const int n_pos = (int)((BN_ + 255) / 256), n_dh = t_pgrid(BN_), n_th = 256;
     const bool scaled = n_pos <= T_AMAX_MAX;
     const int n_ax0 = (scaled && B <= T_AMAX_MAX) ? (int)B : 0;            // layer 0's row is written per SAMPLE by the Gram kernel (else per chunk)
@@ -1384,12 +1384,9 @@ int stgcn_tiled_train(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args
     TTrain t;
     t.B = B; t.sample_offset = ar->sample_offset; t.global_batch = ar->global_batch; t.N = N; t.P = s->patch_size; t.L = L;
     t.dropout_p = ar->dropout_p;
-    t.drop_scale = ar->dropout_p > 0.f ? 1.0f / (1.0f - ar->dropout_p) : 1.0f;
-    {
-        double thr = (double)ar->dropout_p * 4294967296.0;
-        const uint64_t ti = (uint64_t)((thr < 0 ? 0 : thr) + 0.5);
-        t.drop_thr = ti > 4294967295ull ? 4294967295u : (uint32_t)ti;
-    }
+    const DropoutConst drop = dropout_const(ar->dropout_p);
+    t.drop_scale = drop.scale;
+    t.drop_thr = drop.thr;
     t.drop_key = 0;
     t.key_dev = nullptr;
     const StepState* sstate = static_cast<const StepState*>(ar->step_state);
@@ -1410,8 +1407,7 @@ int stgcn_tiled_train(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args
 
     if (mode == 0 || mode == 2) {
         if (ar->step_state) {
-            rc = step_prepare_dropout(ar->step_state, ar->seed, L, stream);
-            if (rc != RULGNN_OK) return rc;
+            RULGNN_TRY(step_prepare_dropout(ar->step_state, ar->seed, L, stream));
         }
         if (!scaled && hipMemsetAsync(cells, 0, w.cells_bytes, stream) != hipSuccess) return RULGNN_EHIP;
         if (scaled) {
@@ -1443,11 +1439,9 @@ int stgcn_tiled_train(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args
                        l == 0 && agg0 ? (int)B : n_pos, am_th(l), n_th, pb_fwd ? planes : nullptr, pb_fwd);
             if (rc != RULGNN_OK) return rc;
             T_LAUNCH_P(t_conv1_train_kernel, BN_, Hpl, pl, TP(w.off_z1, l), 2 * l, t);
-            rc = sync_pair(t.cells_fwd, tc_sf(L), 2 * l);
-            if (rc != RULGNN_OK) return rc;
+            RULGNN_TRY(sync_pair(t.cells_fwd, tc_sf(L), 2 * l));
             T_LAUNCH_P(t_conv2_train_kernel, BN_, TP(w.off_z1, l), Hpl, pl, TP(w.off_o0, l), TP(w.off_z2, l), 2 * l + 1, t);
-            rc = sync_pair(t.cells_fwd, tc_sf(L), 2 * l + 1);
-            if (rc != RULGNN_OK) return rc;
+            RULGNN_TRY(sync_pair(t.cells_fwd, tc_sf(L), 2 * l + 1));
             // (+ the next layer's A.X, or the channel max-pool behind the last layer)
             T_LAUNCH(t_tail_train_kernel, BN_, TP(w.off_z2, l), TP(w.off_o0, l), TP(w.off_X, l), pl, TP(w.off_X, l + 1), 2 * l + 1, t,
                      (const float*)A, l + 1 < L ? TP(w.off_AX, l + 1) : (float*)nullptr, l + 1 < L ? (float*)nullptr : pooled,
@@ -1482,8 +1476,7 @@ int stgcn_tiled_train(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args
         rc = sgemm_splitk(dy1, 1, N, pooled, 1, N, g + off_fc1_w(N, L), N, N, N, (int)B, false, split2, wst, am_dy1, (int)B,
                           am_dy1 ? am_pool : (float*)nullptr, n_pos, pb_fc ? planes2 : nullptr, pb_fc);
         if (rc != RULGNN_OK) return rc;
-        rc = sgemm_splitk(one, 0, 0, dy1, 1, N, g + off_fc1_b(N, L), N, 1, N, (int)B, false, split2, wst);
-        if (rc != RULGNN_OK) return rc;
+        RULGNN_TRY(sgemm_splitk(one, 0, 0, dy1, 1, N, g + off_fc1_b(N, L), N, 1, N, (int)B, false, split2, wst));
         }
         // data parallel with overlap: the head's gradients (fc1 is N x N: 4 MB at XJTU-SY) are final here, with the whole layer
         // stack still to run -- the caller may start their all-reduce on another stream (include/rulgnn.h: rulgnn_grad_ready_fn)
@@ -1500,12 +1493,10 @@ int stgcn_tiled_train(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args
             t.key_dev = sstate ? &sstate->drop_key[l] : nullptr;
             T_LAUNCH_P(t_tail_bwd_kernel, BN_, dpool, TP(w.off_X, l + 1), dX, TP(w.off_z2, l), TP(w.off_o0, l), pl, gsum, 2 * l + 1,
                      l == L - 1 ? 1 : 0, t);
-            rc = sync_pair(t.cells_bwd, tc_sb(L), 2 * l + 1);
-            if (rc != RULGNN_OK) return rc;
+            RULGNN_TRY(sync_pair(t.cells_bwd, tc_sb(L), 2 * l + 1));
             T_LAUNCH_P(t_conv2_bwd_kernel, BN_, gsum, TP(w.off_z2, l), TP(w.off_o0, l), TP(w.off_z1, l), pl, gsum0,
                      gpart + (size_t)(2 * l + 1) * w.grid * CONVW, 2 * l + 1, t);
-            rc = sync_pair(t.cells_bwd, tc_sb(L), 2 * l);
-            if (rc != RULGNN_OK) return rc;
+            RULGNN_TRY(sync_pair(t.cells_bwd, tc_sb(L), 2 * l));
             float* dHp = TP(w.off_dH, l);
             T_LAUNCH_P(t_conv1_bwd_kernel, BN_, gsum0, TP(w.off_z1, l), TP(w.off_H, l), pl, dHp,
                      gpart + (size_t)(2 * l) * w.grid * CONVW, 2 * l, t, am_dh(l));
@@ -1547,8 +1538,7 @@ int stgcn_tiled_train(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args
         }
     }
     if (npj > 0) {
-        rc = sgemm_splitk_batch(pjobs, npj, split2, w.split_floats, stream);
-        if (rc != RULGNN_OK) return rc;
+        RULGNN_TRY(sgemm_splitk_batch(pjobs, npj, split2, w.split_floats, stream));
     }
     TFin f;
     f.gpart = gpart; f.cells_fwd = t.cells_fwd; f.cells_bwd = t.cells_bwd;

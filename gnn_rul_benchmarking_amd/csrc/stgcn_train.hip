@@ -1119,8 +1119,7 @@ static int max_resident_blocks() { return device_cu_count() * 8; }
 
 // training geometry: RW 16 for num_patch <= 16, else one sample per wavefront (RW 64)
 static int train_geometry(const rulgnn_stgcn_shape* s, TileGeom* g) {
-    const int rc = tile_geometry(s, g);
-    if (rc != RULGNN_OK) return rc;
+    RULGNN_TRY(tile_geometry(s, g));
     if (g->RW != 16) {
         g->RW = 64;
         g->SPW = 1;
@@ -1133,19 +1132,18 @@ static int train_geometry(const rulgnn_stgcn_shape* s, TileGeom* g) {
 
 static void ws_layout(const rulgnn_stgcn_shape* s, const TileGeom& g, WsLayout* w) {
     const int L = s->num_layers, N = s->num_patch;
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    size_t o = 0;
-    w->off_cacheX = o; o = al(o + (size_t)g.ntiles * F * 64 * sizeof(float));
-    w->off_cacheA = o; o = al(o + (size_t)g.ntiles * (g.RW == 16 ? F : 1) * 64 * sizeof(float));
+    WsCarver c;
+    w->off_cacheX = c.take<float>((size_t)g.ntiles * F * 64);
+    w->off_cacheA = c.take<float>((size_t)g.ntiles * (g.RW == 16 ? F : 1) * 64);
     w->cells_bytes = sizeof(double) * (size_t)CELL_REPLICAS * cell_stride(L) + sizeof(StepScratch) + 64;   // + grid-barrier counter
-    w->off_cells = o; o = al(o + w->cells_bytes);
+    w->off_cells = c.take_bytes(w->cells_bytes);
     w->max_grid = 2048;
-    w->off_gpart = o; o = al(o + (size_t)w->max_grid * param_count(N, L, s->mpnn_k) * sizeof(float));
-    const size_t tile_bytes = (size_t)g.ntiles * F * 64 * sizeof(float);
-    w->off_saved = o; o = al(o + (size_t)saved_slots(L) * tile_bytes);
-    w->off_rbuf = o; o = al(o + tile_bytes);
-    w->off_sbuf = o; o = al(o + tile_bytes);
-    w->total = o;
+    w->off_gpart = c.take<float>((size_t)w->max_grid * param_count(N, L, s->mpnn_k));
+    const size_t tile_floats = (size_t)g.ntiles * F * 64;
+    w->off_saved = c.take<float>((size_t)saved_slots(L) * tile_floats);
+    w->off_rbuf = c.take<float>(tile_floats);
+    w->off_sbuf = c.take<float>(tile_floats);
+    w->total = c.total();
 }
 
 // 0: the phase chain does not hold this shape (the caller's tiled path, or a refusal for MPNN order k > 1).  Every shape it holds fits
@@ -1209,7 +1207,7 @@ static int launch_phase_n(const TrainK& k_in, const float* x, const float* prm, 
     k.wave_area_floats = wave_area_for(KIND, IDX, g);
     const size_t lds = phase_lds_bytes(RW, L, KIND, IDX, g, KORD);
     // (above MAX_LDS_BYTES: a backstop, the C-ABI gate (stgcn_train_workspace_bytes) keeps such shapes out)
-    if (const int rc = allow_dynamic_lds(kern, lds); rc != RULGNN_OK) return rc;
+    RULGNN_TRY(allow_dynamic_lds(kern, lds));
     int grid = persistent_grid(kern, k.ntiles, lds);
     if (grid > max_grid) grid = max_grid;
     if (grid_out) *grid_out = grid;
@@ -1286,20 +1284,16 @@ struct PhaseChain {
     static int forward_stats(const TrainK& k, const float* x, const float* prm, const TileGeom& lds, int mg, hipStream_t st,
                              const SyncHook* h) {
         if constexpr (I > 0) {
-            const int rc = PhaseChain<RW, L, I - 1>::forward_stats(k, x, prm, lds, mg, st, h);
-            if (rc != RULGNN_OK) return rc;
+            RULGNN_TRY(PhaseChain<RW, L, I - 1>::forward_stats(k, x, prm, lds, mg, st, h));
         }
-        const int rc = launch_phase<RW, L, PH_F, I>(k, x, prm, nullptr, lds, mg, st, nullptr);
-        if (rc != RULGNN_OK) return rc;
+        RULGNN_TRY(launch_phase<RW, L, PH_F, I>(k, x, prm, nullptr, lds, mg, st, nullptr));
         return sync_pair<L>(k, cell_fwd(L) + I * 2 * F, h, st);          // sum z, sum z^2 of BatchNorm I
     }
     static int backward(const TrainK& k, const float* x, const float* prm, const float* gy, const TileGeom& lds, int mg, hipStream_t st,
                         int* grids, const SyncHook* h) {
-        int rc = launch_phase<RW, L, PH_G, I>(k, x, prm, gy, lds, mg, st, &grids[I]);
-        if (rc != RULGNN_OK) return rc;
+        RULGNN_TRY(launch_phase<RW, L, PH_G, I>(k, x, prm, gy, lds, mg, st, &grids[I]));
         if constexpr (I > 0) {
-            rc = sync_pair<L>(k, cell_bwd(L) + (I - 1) * 2 * F, h, st);  // G_I leaves sum dy, sum dy xhat of BatchNorm I - 1
-            if (rc != RULGNN_OK) return rc;
+            RULGNN_TRY(sync_pair<L>(k, cell_bwd(L) + (I - 1) * 2 * F, h, st));  // G_I leaves sum dy, sum dy xhat of BatchNorm I - 1
             return PhaseChain<RW, L, I - 1>::backward(k, x, prm, gy, lds, mg, st, grids, h);
         }
         return RULGNN_OK;
@@ -1310,22 +1304,21 @@ template <int L>
 static int setup_train(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args* a, int mode, TrainK* kp, WsLayout* wp,
                        TileGeom* ldsp) {
     TileGeom& g = *ldsp;
-    int rc = train_geometry(s, &g);
-    if (rc != RULGNN_OK) return rc;
+    RULGNN_TRY(train_geometry(s, &g));
     if (g.RW != 16 && L > 2) return RULGNN_EUNSUPPORTED;
     WsLayout& w = *wp;
     ws_layout(s, g, &w);
     if (a->workspace_bytes < w.total) return RULGNN_EWORKSPACE;
-    char* ws = static_cast<char*>(a->workspace);
+    const Workspace ws(a->workspace);
     const int N = s->num_patch;
     TrainK& k = *kp;
-    k.cacheX = reinterpret_cast<float*>(ws + w.off_cacheX);
-    k.cacheA = reinterpret_cast<float*>(ws + w.off_cacheA);
-    k.cells = reinterpret_cast<double*>(ws + w.off_cells);
-    k.gpart = reinterpret_cast<float*>(ws + w.off_gpart);
-    k.saved = reinterpret_cast<float*>(ws + w.off_saved);
-    k.rbuf = reinterpret_cast<float*>(ws + w.off_rbuf);
-    k.sbuf = reinterpret_cast<float*>(ws + w.off_sbuf);
+    k.cacheX = ws.at<float>(w.off_cacheX);
+    k.cacheA = ws.at<float>(w.off_cacheA);
+    k.cells = ws.at<double>(w.off_cells);
+    k.gpart = ws.at<float>(w.off_gpart);
+    k.saved = ws.at<float>(w.off_saved);
+    k.rbuf = ws.at<float>(w.off_rbuf);
+    k.sbuf = ws.at<float>(w.off_sbuf);
     k.write_pred = 1;
     k.pred = a->pred;
     k.B = s->batch; k.ntiles = g.ntiles; k.global_batch = a->global_batch; k.sample_offset = a->sample_offset;
@@ -1335,13 +1328,9 @@ static int setup_train(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_arg
     k.do_backward = mode != TM_FORWARD;
     k.has_dpred = a->dpred ? 1 : (a->y ? 0 : 2);
     k.dropout_p = a->dropout_p;
-    k.drop_scale = a->dropout_p > 0.f ? 1.0f / (1.0f - a->dropout_p) : 1.0f;
-    {
-        double thr = (double)a->dropout_p * 4294967296.0;
-        thr = thr < 0 ? 0 : thr;
-        const uint64_t ti = (uint64_t)(thr + 0.5);
-        k.drop_thr = ti > 4294967295ull ? 4294967295u : (uint32_t)ti;
-    }
+    const DropoutConst drop = dropout_const(a->dropout_p);
+    k.drop_scale = drop.scale;
+    k.drop_thr = drop.thr;
     k.K = s->mpnn_k;
     k.pcount = param_count(N, L, k.K);
     k.wave_area_floats = 0;
@@ -1486,9 +1475,9 @@ static int launch_coop(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_arg
     if (lds < sizeof(float) * FIN_SLICES * FIN_COLS) lds = sizeof(float) * FIN_SLICES * FIN_COLS;
     const int64_t grid = (k.ntiles + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
     if (grid > w.max_grid) return RULGNN_EUNSUPPORTED;
-    if (const int rc = allow_dynamic_lds(kern, lds); rc != RULGNN_OK) return rc;
+    RULGNN_TRY(allow_dynamic_lds(kern, lds));
     Residency res;
-    if (const int rc = residency(reinterpret_cast<const void*>(kern), BLOCK, lds, &res, /*strict=*/true); rc != RULGNN_OK) return rc;
+    RULGNN_TRY(residency(reinterpret_cast<const void*>(kern), BLOCK, lds, &res, /*strict=*/true));
     // every workgroup must be resident for the grid barriers; one workgroup per CU keeps them evenly spread as well
     if (grid > (int64_t)res.cus) return RULGNN_EUNSUPPORTED;
     const bool fused_adam = opt != nullptr;
@@ -1625,8 +1614,7 @@ static int run_train_rw(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_ar
                            fused_adam ? opt->lr : 0.f, fused_adam ? opt->beta1 : 0.f, fused_adam ? opt->beta2 : 0.f, bn_count);
         if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
         if (!use_mx) {
-            rc = PhaseChain<RW, L, 2 * L - 1>::forward_stats(k, a->x, a->params, lds, w.max_grid, stream, hook);
-            if (rc != RULGNN_OK) return rc;
+            RULGNN_TRY(PhaseChain<RW, L, 2 * L - 1>::forward_stats(k, a->x, a->params, lds, w.max_grid, stream, hook));
         }
     } else {
         // backward after a separate forward: forward cells are valid, clear the backward ones + loss
@@ -1646,8 +1634,7 @@ static int run_train_rw(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_ar
         if (persist && (use_mxw || hook || stgcn_train_mx_persistent_grid(s->batch, L, w.max_grid) == 0)) return RULGNN_EUNSUPPORTED;
         for (int ph = 0; ph <= (persist ? 0 : 4 * L); ++ph) {
             int grid = 0;
-            rc = mx_phase<L>(s, a, k, m, ph, stream, w.max_grid, &grid, use_mxw, ph == 0 && skip_prepare ? &head : nullptr);
-            if (rc != RULGNN_OK) return rc;
+            RULGNN_TRY(mx_phase<L>(s, a, k, m, ph, stream, w.max_grid, &grid, use_mxw, ph == 0 && skip_prepare ? &head : nullptr));
             // the reduction pair a phase completes (all-reduced here under synchronised BatchNorm; the later phases read the cells):
             // F_i -> forward pair i, TOP -> backward pair 2L-1, G_i -> backward pair i-1
             if (ph < 2 * L) rc = sync_pair<L>(k, cell_fwd(L) + ph * 2 * F, hook, stream);
@@ -1661,20 +1648,17 @@ static int run_train_rw(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_ar
         }
         if (persist) {
             int grid = 0;
-            rc = stgcn_train_mx_persistent(m, stream, w.max_grid, &grid);
-            if (rc != RULGNN_OK) return rc;
+            RULGNN_TRY(stgcn_train_mx_persistent(m, stream, w.max_grid, &grid));
             grid_top = grid;
             for (int i = 0; i < 2 * L; ++i) grids[i] = grid;
         }
     } else {
-    rc = launch_phase<RW, L, PH_TOP, 0>(k, a->x, a->params, gy, lds, w.max_grid, stream, &grid_top);
-    if (rc != RULGNN_OK) return rc;
+    RULGNN_TRY(launch_phase<RW, L, PH_TOP, 0>(k, a->x, a->params, gy, lds, w.max_grid, stream, &grid_top));
     }
     if (mode != TM_FORWARD && !use_mx) {
         rc = sync_pair<L>(k, cell_bwd(L) + (2 * L - 1) * 2 * F, hook, stream);      // TOP leaves the pair of the last BatchNorm
         if (rc != RULGNN_OK) return rc;
-        rc = PhaseChain<RW, L, 2 * L - 1>::backward(k, a->x, a->params, gy, lds, w.max_grid, stream, grids, hook);
-        if (rc != RULGNN_OK) return rc;
+        RULGNN_TRY(PhaseChain<RW, L, 2 * L - 1>::backward(k, a->x, a->params, gy, lds, w.max_grid, stream, grids, hook));
     }
     FinalizeK f{};
     f.gpart = k.gpart; f.cells = k.cells;
@@ -1709,8 +1693,7 @@ static int run_train(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args*
     TrainK k;
     WsLayout w;
     TileGeom lds;
-    const int rc = setup_train<L>(s, a, mode, &k, &w, &lds);
-    if (rc != RULGNN_OK) return rc;
+    RULGNN_TRY(setup_train<L>(s, a, mode, &k, &w, &lds));
     if (lds.RW == 16) return run_train_rw<16, L>(s, a, mode, stream, k, w, lds, opt, hook, path);
     if constexpr (L <= 2) return run_train_rw<64, L>(s, a, mode, stream, k, w, lds, opt, hook, path);
     return RULGNN_EUNSUPPORTED;
@@ -1737,8 +1720,7 @@ static int run_phase(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args*
     TrainK k;
     WsLayout w;
     TileGeom lds;
-    const int rc = setup_train<L>(s, a, TM_FWDBWD, &k, &w, &lds);
-    if (rc != RULGNN_OK) return rc;
+    RULGNN_TRY(setup_train<L>(s, a, TM_FWDBWD, &k, &w, &lds));
     if (phase == -1) {
         // the step's prepare kernel alone: clears the reduction cells (same dropout step) so that a harness timing the phases one by one
         // runs them on valid BatchNorm statistics -- cells that keep accumulating from launch to launch drive the statistics out of range

@@ -12,7 +12,7 @@
 //   projection           out [G*N, H] = terms x filters viewed as [K*f, H]            (sgemm_mfma.hpp)
 //   filter gradient      d filters [K*f, H] = terms^T x d out, split-K, fixed reduction order (deterministic)
 #include "sgemm_mfma.hpp"
-#include "stgcn_host.hpp"
+#include "families_host.hpp"
 
 namespace rulgnn {
 
@@ -138,8 +138,7 @@ size_t stgnn_workspace_bytes(const rulgnn_stgnn_shape* s) {
 
 int stgnn_terms(const rulgnn_stgnn_shape* s, const float* x, float* terms, float* adj, hipStream_t st) {
     GnGeom g;
-    const int rc = gn_geometry(s, &g);
-    if (rc != RULGNN_OK) return rc;
+    RULGNN_TRY(gn_geometry(s, &g));
     if (g.G == 0) return RULGNN_OK;
     const size_t lds = terms_lds_bytes(g);
     if (lds > 64 * 1024) return RULGNN_EUNSUPPORTED;
@@ -150,8 +149,7 @@ int stgnn_terms(const rulgnn_stgnn_shape* s, const float* x, float* terms, float
 
 int stgnn_cheb_forward(const rulgnn_stgnn_shape* s, const float* terms, const float* filters, float* out, hipStream_t st) {
     GnGeom g;
-    const int rc = gn_geometry(s, &g);
-    if (rc != RULGNN_OK) return rc;
+    RULGNN_TRY(gn_geometry(s, &g));
     const int64_t M = g.G * g.N;
     if (M == 0) return RULGNN_OK;
     // out[m][h] = sum_q terms[m][q] * filters[q][h]
@@ -161,8 +159,7 @@ int stgnn_cheb_forward(const rulgnn_stgnn_shape* s, const float* terms, const fl
 int stgnn_cheb_backward(const rulgnn_stgnn_shape* s, const float* terms, const float* dout, float* dfilters, void* workspace,
                         size_t workspace_bytes, hipStream_t st) {
     GnGeom g;
-    const int rc = gn_geometry(s, &g);
-    if (rc != RULGNN_OK) return rc;
+    RULGNN_TRY(gn_geometry(s, &g));
     if (!workspace || workspace_bytes < stgnn_workspace_bytes(s)) return RULGNN_EWORKSPACE;
     const int64_t M = g.G * g.N;
     if (M == 0) return hipMemsetAsync(dfilters, 0, sizeof(float) * g.KF * g.H, st) == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
@@ -252,29 +249,28 @@ struct GnWs {
     size_t gru_bytes;
 };
 void gn_ws(const GnGeom& g, GnWs* w) {
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const size_t R = (size_t)g.G * g.N;
-    size_t o = 0;
-    w->terms = o; o = al(o + R * g.KF * sizeof(float));
-    w->cheb = o; o = al(o + R * g.H * sizeof(float));
-    w->seq = o; o = al(o + R * g.H * sizeof(float));
-    w->hs = o; o = al(o + R * g.H * sizeof(float));
-    w->dhs = o; o = al(o + R * g.H * sizeof(float));
-    w->dseq = o; o = al(o + R * g.H * sizeof(float));
-    w->dcheb = o; o = al(o + R * g.H * sizeof(float));
-    w->dpred = o; o = al(o + (size_t)(g.B > 0 ? g.B : 1) * sizeof(float));
-    w->sqerr = o; o = al(o + (size_t)(g.B > 0 ? g.B : 1) * sizeof(float));
-    w->one = o; o = al(o + 64 * sizeof(float));
+    WsCarver c;
+    w->terms = c.take<float>(R * g.KF);
+    w->cheb = c.take<float>(R * g.H);
+    w->seq = c.take<float>(R * g.H);
+    w->hs = c.take<float>(R * g.H);
+    w->dhs = c.take<float>(R * g.H);
+    w->dseq = c.take<float>(R * g.H);
+    w->dcheb = c.take<float>(R * g.H);
+    w->dpred = c.take<float>((size_t)(g.B > 0 ? g.B : 1));
+    w->sqerr = c.take<float>((size_t)(g.B > 0 ? g.B : 1));
+    w->one = c.take<float>(64);
     rulgnn_gru_shape gs{(int64_t)(g.B * g.N), g.L, g.H, g.H};
     w->gru_bytes = gru_workspace_bytes(&gs);
-    w->gru = o; o = al(o + w->gru_bytes);
+    w->gru = c.take_bytes(w->gru_bytes);
     const int Q = g.N * g.L * g.H;
     size_t sp = sgemm_splitk_partial_floats(g.KF, g.H);
     const size_t s2 = sgemm_splitk_need_floats(1, Q, (int)g.B), s3 = sgemm_splitk_need_floats(1, 1, (int)g.B);
     if (s2 > sp) sp = s2;
     if (s3 > sp) sp = s3;
-    w->split = o; o = al(o + sp * sizeof(float));
-    w->total = o;
+    w->split = c.take<float>(sp);
+    w->total = c.total();
 }
 
 inline unsigned gn_blocks(int64_t n) {
@@ -298,13 +294,11 @@ size_t stgnn_step_workspace_bytes(const rulgnn_stgnn_shape* s) {
     return w.gru_bytes == 0 && g.B > 0 ? 0 : w.total;
 }
 
-#define GN_RC(x) do { const int rc_ = (x); if (rc_ != RULGNN_OK) return rc_; } while (0)
-
 // mode bit 0: forward (pred; with y also d pred and the loss terms), bit 1: backward (gradients; d pred from args->dpred or
 // from the forward of this call)
 int stgnn_run(const rulgnn_stgnn_shape* s, const rulgnn_stmsgcn_args* a, int mode, hipStream_t st) {
     GnGeom g;
-    GN_RC(gn_geometry(s, &g));
+    RULGNN_TRY(gn_geometry(s, &g));
     GnWs w;
     gn_ws(g, &w);
     if (!a->workspace || a->workspace_bytes < w.total) return RULGNN_EWORKSPACE;
@@ -314,25 +308,25 @@ int stgnn_run(const rulgnn_stgnn_shape* s, const rulgnn_stmsgcn_args* a, int mod
         if ((mode & 2) && a->loss && hipMemsetAsync(a->loss, 0, sizeof(float), st) != hipSuccess) return RULGNN_EHIP;
         return RULGNN_OK;
     }
-    char* ws = static_cast<char*>(a->workspace);
-    auto Fp = [&](size_t off) { return reinterpret_cast<float*>(ws + off); };
+    const Workspace ws(a->workspace);
+    auto Fp = [&](size_t off) { return ws.at<float>(off); };
     const float* prm = a->params;
     const int64_t R = g.G * g.N;
     const int Q = g.N * g.L * g.H;
     rulgnn_gru_shape gs{(int64_t)(g.B * g.N), g.L, g.H, g.H};
     rulgnn_gru_args ga{};
     ga.w_ih = prm + o.wih; ga.w_hh = prm + o.whh; ga.b_ih = prm + o.bih; ga.b_hh = prm + o.bhh;
-    ga.workspace = ws + w.gru; ga.workspace_bytes = w.gru_bytes;
+    ga.workspace = ws.at<void>(w.gru); ga.workspace_bytes = w.gru_bytes;
     float* seq = g.L == 1 ? Fp(w.cheb) : Fp(w.seq);          // one patch: the permutation is the identity
     float* dseq = Fp(w.dseq);
     float* dcheb = g.L == 1 ? dseq : Fp(w.dcheb);
     (void)hipGetLastError();
     if (mode & 1) {
-        GN_RC(stgnn_terms(s, a->x, Fp(w.terms), nullptr, st));
-        GN_RC(stgnn_cheb_forward(s, Fp(w.terms), prm + o.filters, Fp(w.cheb), st));
+        RULGNN_TRY(stgnn_terms(s, a->x, Fp(w.terms), nullptr, st));
+        RULGNN_TRY(stgnn_cheb_forward(s, Fp(w.terms), prm + o.filters, Fp(w.cheb), st));
         if (g.L > 1) hipLaunchKernelGGL(stgnn_permute_kernel, dim3(gn_blocks(R * g.H)), dim3(GB), 0, st, g, (const float*)Fp(w.cheb), seq, 1);
         ga.x = seq; ga.out = Fp(w.hs);
-        GN_RC(gru_forward(&gs, &ga, st));
+        RULGNN_TRY(gru_forward(&gs, &ga, st));
         const float inv_gb = 1.0f / (float)(a->global_batch > 0 ? a->global_batch : g.B);
         hipLaunchKernelGGL(stgnn_head_kernel, dim3((unsigned)g.B), dim3(GB), 0, st, g, (const float*)Fp(w.hs), prm + o.fcw, prm + o.fcb, a->y,
                            a->pred, Fp(w.dpred), Fp(w.sqerr), inv_gb);
@@ -344,14 +338,14 @@ int stgnn_run(const rulgnn_stgnn_shape* s, const rulgnn_stmsgcn_args* a, int mod
         float* split = Fp(w.split);
         hipLaunchKernelGGL(stgnn_fill_kernel, dim3(1), dim3(64), 0, st, Fp(w.one), 64, 1.0f);
         // fc: d w[q] = sum_b dpred[b] flat[b][q], d b = sum_b dpred[b], d flat = dpred (x) w
-        GN_RC(sgemm_splitk(dpred, 0, 1, Fp(w.hs), 1, Q, gr + o.fcw, Q, 1, Q, (int)g.B, false, split, st));
-        GN_RC(sgemm_splitk(dpred, 0, 1, Fp(w.one), 0, 0, gr + o.fcb, 1, 1, 1, (int)g.B, false, split, st));
+        RULGNN_TRY(sgemm_splitk(dpred, 0, 1, Fp(w.hs), 1, Q, gr + o.fcw, Q, 1, Q, (int)g.B, false, split, st));
+        RULGNN_TRY(sgemm_splitk(dpred, 0, 1, Fp(w.one), 0, 0, gr + o.fcb, 1, 1, 1, (int)g.B, false, split, st));
         hipLaunchKernelGGL(stgnn_dflat_kernel, dim3(gn_blocks(g.B * Q)), dim3(GB), 0, st, g, dpred, prm + o.fcw, Fp(w.dhs));
         ga.x = seq; ga.dout = Fp(w.dhs); ga.dx = dseq;
         ga.dw_ih = gr + o.wih; ga.dw_hh = gr + o.whh; ga.db_ih = gr + o.bih; ga.db_hh = gr + o.bhh;
-        GN_RC(gru_backward(&gs, &ga, st));
+        RULGNN_TRY(gru_backward(&gs, &ga, st));
         if (g.L > 1) hipLaunchKernelGGL(stgnn_permute_kernel, dim3(gn_blocks(R * g.H)), dim3(GB), 0, st, g, (const float*)dseq, dcheb, 0);
-        GN_RC(stgnn_cheb_backward(s, Fp(w.terms), dcheb, gr + o.filters, split, sgemm_splitk_partial_floats(g.KF, g.H) * sizeof(float), st));
+        RULGNN_TRY(stgnn_cheb_backward(s, Fp(w.terms), dcheb, gr + o.filters, split, sgemm_splitk_partial_floats(g.KF, g.H) * sizeof(float), st));
         if (!a->dpred && a->loss)
             (void)block_sum((const float*)Fp(w.sqerr), (int64_t)g.B, a->loss, st);
         if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;

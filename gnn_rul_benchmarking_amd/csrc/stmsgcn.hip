@@ -18,7 +18,7 @@
 // Everything is fp32; reductions have a fixed order, so results are run-to-run reproducible.
 #include "async_mem.hpp"
 #include "sgemm_mfma.hpp"
-#include "stgcn_host.hpp"
+#include "families_host.hpp"
 
 namespace rulgnn {
 
@@ -1571,48 +1571,37 @@ struct MsgWs {
 };
 
 static void msg_ws_layout(const MsgGeom& g, MsgWs* w) {
-    auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
     const size_t rows = (size_t)g.G * g.n;
-    size_t o = 0;
-    w->cat = o; o = al(o + rows * g.C * sizeof(float));
-    w->gi = o; o = al(o + rows * g.H3 * sizeof(float));
-    w->hseq = o; o = al(o + rows * g.H * sizeof(float));
-    w->dgi = o; o = al(o + rows * g.H3 * sizeof(float));
-    w->dcat = o; o = al(o + rows * g.C * sizeof(float));
-    w->one = o; o = al(o + 64 * sizeof(float));
+    WsCarver c;
+    w->cat = c.take<float>(rows * g.C);
+    w->gi = c.take<float>(rows * g.H3);
+    w->hseq = c.take<float>(rows * g.H);
+    w->dgi = c.take<float>(rows * g.H3);
+    w->dcat = c.take<float>(rows * g.C);
+    w->one = c.take<float>(64);
     {
         const size_t s1 = sgemm_splitk_need_floats(g.H3, g.C, (int)rows), s2 = sgemm_splitk_need_floats(g.H3, 1, (int)rows);
-        w->split = o; o = al(o + (s1 > s2 ? s1 : s2) * sizeof(float));
+        w->split = c.take<float>(s1 > s2 ? s1 : s2);
     }
-    w->pooled = o; o = al(o + (size_t)g.B * g.NP * g.H * sizeof(float));
-    w->dpred = o; o = al(o + (size_t)g.B * sizeof(float));
-    w->sqerr = o; o = al(o + (size_t)g.B * sizeof(float));
-    w->hpart = o; o = al(o + (size_t)g.B * HEAD_MAX_PARTS * sizeof(float));
+    w->pooled = c.take<float>((size_t)g.B * g.NP * g.H);
+    w->dpred = c.take<float>((size_t)g.B);
+    w->sqerr = c.take<float>((size_t)g.B);
+    w->hpart = c.take<float>((size_t)g.B * HEAD_MAX_PARTS);
     w->HG = g.H <= 4 ? 4 : (g.H <= 8 ? 8 : 16);
     w->rows_gcn_max = 1024;
     w->rows_gru = (int)(((size_t)g.B * g.n * w->HG + MB - 1) / MB);
     if (w->rows_gru < 1) w->rows_gru = 1;
-    w->gpart_gcn = o; o = al(o + (size_t)w->rows_gcn_max * g.gcn_params * sizeof(float));
-    w->gpart_gru = o; o = al(o + (size_t)w->rows_gru * (g.H3 * g.H + g.H3) * sizeof(float));
-    w->gpart_gi = o; o = al(o + (size_t)GI_MAX_PARTS * (g.H3 * g.C + g.H3) * sizeof(float));
-    w->total = o;
-}
-
-template <typename K>
-static int resident_grid(K kernel, int64_t items, size_t lds, int cap_rows) {
-    auto [cus, per_cu] = residency(kernel, MB, lds);
-    int64_t want = (int64_t)cus * per_cu;
-    if (want > items) want = items;
-    if (want > cap_rows) want = cap_rows;
-    if (want < 1) want = 1;
-    return (int)want;
+    w->gpart_gcn = c.take<float>((size_t)w->rows_gcn_max * g.gcn_params);
+    w->gpart_gru = c.take<float>((size_t)w->rows_gru * (g.H3 * g.H + g.H3));
+    w->gpart_gi = c.take<float>((size_t)GI_MAX_PARTS * (g.H3 * g.C + g.H3));
+    w->total = c.total();
 }
 
 template <int TW>
 static int launch_features_tw(const MsgGeom& g, const float* x, const float* prm, float* cat, float* gi, hipStream_t st) {
     const size_t lds = features_lds_bytes(g);
-    if (const int rc = allow_dynamic_lds(msg_features_kernel<TW>, lds); rc != RULGNN_OK) return rc;
-    const int grid = resident_grid(msg_features_kernel<TW>, g.G, lds, 1 << 20);
+    RULGNN_TRY(allow_dynamic_lds(msg_features_kernel<TW>, lds));
+    const int grid = resident_rows(msg_features_kernel<TW>, MB, lds, g.G, 1 << 20);
     hipLaunchKernelGGL(msg_features_kernel<TW>, dim3(grid), dim3(MB), lds, st, g, x, prm, cat, gi);
     return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
 }
@@ -1620,11 +1609,9 @@ static int launch_features(const MsgGeom& g, const float* x, const float* prm, f
     size_t lds = 0;
     if (mx_features_ok(g, &lds)) {                  // graphs of >= 12 nodes: one wavefront per graph on the fp32 matrix cores
         auto go = [&](auto kern) -> int {
-            if (const int rc = allow_dynamic_lds(kern, lds); rc != RULGNN_OK) return rc;
-            auto [cus, per_cu] = residency(kern, 64 * MXW, lds);
-            int64_t grid = (int64_t)cus * per_cu;
+            RULGNN_TRY(allow_dynamic_lds(kern, lds));
             const int64_t need = (g.G + MXW - 1) / MXW;
-            if (grid > need) grid = need;
+            const int grid = resident_rows(kern, 64 * MXW, lds, need, need);
             hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * MXW), lds, st, g, x, prm, cat, gi);
             return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
         };
@@ -1637,26 +1624,26 @@ template <int TW>
 static int launch_gcn_backward(const MsgGeom& g, int rows_max, const float* cat, const float* dcat, const float* prm, float* gpart,
                                hipStream_t st, int* rows_out) {
     const size_t lds = gcn_backward_lds_bytes(g);
-    if (const int rc = allow_dynamic_lds(msg_gcn_backward_kernel<TW>, lds); rc != RULGNN_OK) return rc;
-    const int rows = resident_grid(msg_gcn_backward_kernel<TW>, g.G, lds, rows_max);
+    RULGNN_TRY(allow_dynamic_lds(msg_gcn_backward_kernel<TW>, lds));
+    const int rows = resident_rows(msg_gcn_backward_kernel<TW>, MB, lds, g.G, rows_max);
     hipLaunchKernelGGL(msg_gcn_backward_kernel<TW>, dim3(rows), dim3(MB), lds, st, g, cat, dcat, prm, gpart);
     *rows_out = rows;
     return RULGNN_OK;
 }
 
 template <int HG>
-static void launch_gru(const MsgGeom& g, const MsgWs& w, char* ws, const float* prm, bool backward, hipStream_t st) {
+static void launch_gru(const MsgGeom& g, const MsgWs& w, const Workspace& ws, const float* prm, bool backward, hipStream_t st) {
     const int grid = w.rows_gru;
     if (!backward)
-        hipLaunchKernelGGL(msg_gru_forward_kernel<HG>, dim3(grid), dim3(MB), 0, st, g, (const float*)(ws + w.gi), prm,
-                           (float*)(ws + w.hseq));
+        hipLaunchKernelGGL(msg_gru_forward_kernel<HG>, dim3(grid), dim3(MB), 0, st, g, ws.at<float>(w.gi), prm,
+                           ws.at<float>(w.hseq));
     else
-        hipLaunchKernelGGL(msg_gru_backward_kernel<HG>, dim3(grid), dim3(MB), 0, st, g, (const float*)(ws + w.gi),
-                           (const float*)(ws + w.hseq), prm, (const float*)(ws + w.dpred), (float*)(ws + w.dgi),
-                           (float*)(ws + w.gpart_gru));
+        hipLaunchKernelGGL(msg_gru_backward_kernel<HG>, dim3(grid), dim3(MB), 0, st, g, ws.at<float>(w.gi),
+                           ws.at<float>(w.hseq), prm, ws.at<float>(w.dpred), ws.at<float>(w.dgi),
+                           ws.at<float>(w.gpart_gru));
 }
 
-static void dispatch_gru(const MsgGeom& g, const MsgWs& w, char* ws, const float* prm, bool backward, hipStream_t st) {
+static void dispatch_gru(const MsgGeom& g, const MsgWs& w, const Workspace& ws, const float* prm, bool backward, hipStream_t st) {
     if (w.HG == 4) launch_gru<4>(g, w, ws, prm, backward, st);
     else if (w.HG == 8) launch_gru<8>(g, w, ws, prm, backward, st);
     else launch_gru<16>(g, w, ws, prm, backward, st);
@@ -1679,8 +1666,7 @@ size_t stmsgcn_workspace_bytes(const rulgnn_stmsgcn_shape* s) {
 
 int stmsgcn_features(const rulgnn_stmsgcn_shape* s, const float* x, const float* prm, float* features, hipStream_t st) {
     MsgGeom g;
-    const int rc = msg_geometry(s, &g);
-    if (rc != RULGNN_OK) return rc;
+    RULGNN_TRY(msg_geometry(s, &g));
     if (g.B == 0) return RULGNN_OK;
     (void)hipGetLastError();
     return launch_features(g, x, prm, features, nullptr, st);
@@ -1689,33 +1675,31 @@ int stmsgcn_features(const rulgnn_stmsgcn_shape* s, const float* x, const float*
 // mode bit 0: forward, bit 1: backward
 int stmsgcn_run(const rulgnn_stmsgcn_shape* s, const rulgnn_stmsgcn_args* a, int mode, hipStream_t st) {
     MsgGeom g;
-    int rc = msg_geometry(s, &g);
-    if (rc != RULGNN_OK) return rc;
+    RULGNN_TRY(msg_geometry(s, &g));
     MsgWs w;
     msg_ws_layout(g, &w);
     if (a->workspace_bytes < w.total) return RULGNN_EWORKSPACE;
-    char* ws = static_cast<char*>(a->workspace);
+    const Workspace ws(a->workspace);
     (void)hipGetLastError();
     const float inv_gb = 1.0f / (float)(a->global_batch > 0 ? a->global_batch : g.B);
     if (mode & 1) {
-        rc = launch_features(g, a->x, a->params, (float*)(ws + w.cat), (float*)(ws + w.gi), st);
-        if (rc != RULGNN_OK) return rc;
+        RULGNN_TRY(launch_features(g, a->x, a->params, ws.at<float>(w.cat), ws.at<float>(w.gi), st));
         dispatch_gru(g, w, ws, a->params, false, st);
         {
             // enough workgroups to fill the chip: a sample's (patch, unit) pairs in up to HEAD_MAX_PARTS slices
             int parts = 1;
             while (parts < HEAD_MAX_PARTS && g.B * parts < 1024 && g.NP * g.H / (2 * parts) >= MB) parts *= 2;
-            hipLaunchKernelGGL(msg_head_kernel, dim3((unsigned)(g.B * parts)), dim3(MB), 0, st, g, (const float*)(ws + w.hseq), a->params,
-                               a->y, a->pred, (float*)(ws + w.pooled), (float*)(ws + w.dpred), (float*)(ws + w.sqerr), inv_gb, parts,
-                               (float*)(ws + w.hpart));
+            hipLaunchKernelGGL(msg_head_kernel, dim3((unsigned)(g.B * parts)), dim3(MB), 0, st, g, ws.at<float>(w.hseq), a->params,
+                               a->y, a->pred, ws.at<float>(w.pooled), ws.at<float>(w.dpred), ws.at<float>(w.sqerr), inv_gb, parts,
+                               ws.at<float>(w.hpart));
             if (parts > 1)
                 hipLaunchKernelGGL(msg_head_finish_kernel, dim3((unsigned)((g.B + 255) / 256)), dim3(256), 0, st, g, a->params,
-                                   (const float*)(ws + w.hpart), parts, a->y, a->pred, (float*)(ws + w.dpred), (float*)(ws + w.sqerr), inv_gb);
+                                   ws.at<float>(w.hpart), parts, a->y, a->pred, ws.at<float>(w.dpred), ws.at<float>(w.sqerr), inv_gb);
         }
     }
     if (mode & 2) {
         if (a->dpred) {
-            if (hipMemcpyAsync(ws + w.dpred, a->dpred, sizeof(float) * g.B, hipMemcpyDeviceToDevice, st) != hipSuccess)
+            if (hipMemcpyAsync(ws.at<float>(w.dpred), a->dpred, sizeof(float) * g.B, hipMemcpyDeviceToDevice, st) != hipSuccess)
                 return RULGNN_EHIP;
         }
         dispatch_gru(g, w, ws, a->params, true, st);
@@ -1723,24 +1707,21 @@ int stmsgcn_run(const rulgnn_stmsgcn_shape* s, const rulgnn_stmsgcn_args* a, int
         int rows_gi = 0;
         {
             const int64_t R = g.G * g.n;
-            const float* dgi = (const float*)(ws + w.dgi);
+            const float* dgi = ws.at<float>(w.dgi);
             if (g.H3 == 24 && g.C < 128) {                          // the reference's GRU width (hidden 8): one streaming pass
                 int64_t parts = (R + 4 * GI_ROWS - 1) / (4 * GI_ROWS);
                 if (parts > GI_MAX_PARTS) parts = GI_MAX_PARTS;
                 rows_gi = (int)parts;
-                hipLaunchKernelGGL(msg_gi_backward_kernel<24>, dim3((unsigned)parts), dim3(GIB), 0, st, g.C, dgi, (const float*)(ws + w.cat),
-                                   a->params + g.off_wih, (float*)(ws + w.dcat), (float*)(ws + w.gpart_gi), R);
+                hipLaunchKernelGGL(msg_gi_backward_kernel<24>, dim3((unsigned)parts), dim3(GIB), 0, st, g.C, dgi, ws.at<float>(w.cat),
+                                   a->params + g.off_wih, ws.at<float>(w.dcat), ws.at<float>(w.gpart_gi), R);
             } else {
                 const float* wih = a->params + g.off_wih;
-                float* one = (float*)(ws + w.one);
-                float* split = (float*)(ws + w.split);
+                float* one = ws.at<float>(w.one);
+                float* split = ws.at<float>(w.split);
                 hipLaunchKernelGGL(msg_fill_kernel, dim3(1), dim3(64), 0, st, one, 64, 1.0f);
-                rc = sgemm(dgi, g.H3, 1, wih, 1, g.C, (float*)(ws + w.dcat), g.C, (int)R, g.C, g.H3, false, st);
-                if (rc != RULGNN_OK) return rc;
-                rc = sgemm_splitk(dgi, 1, g.H3, (const float*)(ws + w.cat), 1, g.C, a->grads + g.off_wih, g.C, g.H3, g.C, (int)R, false, split, st);
-                if (rc != RULGNN_OK) return rc;
-                rc = sgemm_splitk(dgi, 1, g.H3, one, 0, 0, a->grads + g.off_bih, 1, g.H3, 1, (int)R, false, split, st);
-                if (rc != RULGNN_OK) return rc;
+                RULGNN_TRY(sgemm(dgi, g.H3, 1, wih, 1, g.C, ws.at<float>(w.dcat), g.C, (int)R, g.C, g.H3, false, st));
+                RULGNN_TRY(sgemm_splitk(dgi, 1, g.H3, ws.at<float>(w.cat), 1, g.C, a->grads + g.off_wih, g.C, g.H3, g.C, (int)R, false, split, st));
+                RULGNN_TRY(sgemm_splitk(dgi, 1, g.H3, one, 0, 0, a->grads + g.off_bih, 1, g.H3, 1, (int)R, false, split, st));
             }
         }
         int rows = 0;
@@ -1748,32 +1729,27 @@ int stmsgcn_run(const rulgnn_stmsgcn_shape* s, const rulgnn_stmsgcn_args* a, int
         int rcb;
         if (mx_backward_ok(g, &lds_mx)) {                  // graphs of >= 12 nodes: one wavefront per graph on the fp32 matrix cores
             auto launch_mx = [&](auto kern) -> int {
-                if (const int rc = allow_dynamic_lds(kern, lds_mx); rc != RULGNN_OK) return rc;
-                auto [cus, per_cu] = residency(kern, 64 * MXW, lds_mx);
-                int64_t grid = (int64_t)cus * per_cu;
-                const int64_t need = (g.G + MXW - 1) / MXW;
-                if (grid > need) grid = need;
-                if (grid > w.rows_gcn_max) grid = w.rows_gcn_max;
-                rows = (int)grid;
-                hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * MXW), lds_mx, st, g, (const float*)(ws + w.cat),
-                                   (const float*)(ws + w.dcat), a->params, (float*)(ws + w.gpart_gcn));
+                RULGNN_TRY(allow_dynamic_lds(kern, lds_mx));
+                rows = resident_rows(kern, 64 * MXW, lds_mx, (g.G + MXW - 1) / MXW, w.rows_gcn_max);
+                hipLaunchKernelGGL(kern, dim3((unsigned)rows), dim3(64 * MXW), lds_mx, st, g, ws.at<float>(w.cat),
+                                   ws.at<float>(w.dcat), a->params, ws.at<float>(w.gpart_gcn));
                 return RULGNN_OK;
             };
             const int rl = MsgXJ::matches(g) ? launch_mx(&msg_gcn_backward_mx_kernel<true>) : launch_mx(&msg_gcn_backward_mx_kernel<false>);
             if (rl != RULGNN_OK) return rl;
             rcb = hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
         } else
-        rcb = g.n >= 12 ? launch_gcn_backward<4>(g, w.rows_gcn_max, (const float*)(ws + w.cat), (const float*)(ws + w.dcat), a->params,
-                                                           (float*)(ws + w.gpart_gcn), st, &rows)
-                                  : launch_gcn_backward<1>(g, w.rows_gcn_max, (const float*)(ws + w.cat), (const float*)(ws + w.dcat), a->params,
-                                                           (float*)(ws + w.gpart_gcn), st, &rows);
+        rcb = g.n >= 12 ? launch_gcn_backward<4>(g, w.rows_gcn_max, ws.at<float>(w.cat), ws.at<float>(w.dcat), a->params,
+                                                           ws.at<float>(w.gpart_gcn), st, &rows)
+                                  : launch_gcn_backward<1>(g, w.rows_gcn_max, ws.at<float>(w.cat), ws.at<float>(w.dcat), a->params,
+                                                           ws.at<float>(w.gpart_gcn), st, &rows);
         if (rcb != RULGNN_OK) return rcb;
         const bool mse = a->dpred == nullptr;
         hipLaunchKernelGGL(msg_finalize_kernel, dim3((g.nparam + 3) / 4), dim3(MB), 0, st, g,
-                           (const float*)(ws + w.gpart_gcn), rows, (const float*)(ws + w.gpart_gru), w.rows_gru,
-                           (const float*)(ws + w.gpart_gi), rows_gi, (const float*)(ws + w.dpred), (const float*)(ws + w.pooled), a->grads);
+                           ws.at<float>(w.gpart_gcn), rows, ws.at<float>(w.gpart_gru), w.rows_gru,
+                           ws.at<float>(w.gpart_gi), rows_gi, ws.at<float>(w.dpred), ws.at<float>(w.pooled), a->grads);
         if (mse && a->loss)
-            (void)block_sum((const float*)(ws + w.sqerr), (int64_t)g.B, a->loss, st);
+            (void)block_sum(ws.at<float>(w.sqerr), (int64_t)g.B, a->loss, st);
     }
     return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
 }

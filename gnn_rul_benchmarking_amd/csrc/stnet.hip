@@ -16,7 +16,7 @@
 #include <stdint.h>
 
 #include "sgemm_mfma.hpp"
-#include "stgcn_host.hpp"
+#include "families_host.hpp"
 
 namespace rulgnn {
 
@@ -312,11 +312,6 @@ size_t stnet_workspace_bytes(const rulgnn_stnet_shape* s) {
     return sn_geometry(s, &g) == RULGNN_OK ? (size_t)g.total * sizeof(float) : 0;
 }
 
-#define SN_RC(call)                        \
-    do {                                   \
-        const int rc_ = (call);            \
-        if (rc_ != RULGNN_OK) return rc_;  \
-    } while (0)
 #define SN_LAUNCH_OK()                                        \
     do {                                                      \
         if (hipGetLastError() != hipSuccess) return RULGNN_EHIP; \
@@ -325,7 +320,7 @@ size_t stnet_workspace_bytes(const rulgnn_stnet_shape* s) {
 // mode bit 0: forward, bit 1: backward (after a forward with the same args / workspace)
 int stnet_run(const rulgnn_stnet_shape* s, const rulgnn_stnet_args* a, int mode, hipStream_t st) {
     SnGeom g;
-    SN_RC(sn_geometry(s, &g));
+    RULGNN_TRY(sn_geometry(s, &g));
     if (a->workspace_bytes < (size_t)g.total * sizeof(float)) return RULGNN_EWORKSPACE;
     if (g.B == 0) return RULGNN_OK;
     float* ws = static_cast<float*>(a->workspace);
@@ -379,19 +374,19 @@ int stnet_run(const rulgnn_stnet_shape* s, const rulgnn_stnet_args* a, int mode,
         for (int i = 0; i < nc; ++i) {
             hipLaunchKernelGGL(sn_terms_kernel, dim3(ggrid), dim3(SB), 0, st, g, g.C[i], cur, mask, ws + g.w_terms[i]);
             SN_LAUNCH_OK();
-            SN_RC(sgemm(ws + g.w_terms[i], 3 * g.C[i], 1, fop[i], 1, g.C[i + 1], ws + g.w_out[i], g.C[i + 1], R, g.C[i + 1], 3 * g.C[i],
+            RULGNN_TRY(sgemm(ws + g.w_terms[i], 3 * g.C[i], 1, fop[i], 1, g.C[i + 1], ws + g.w_out[i], g.C[i + 1], R, g.C[i + 1], 3 * g.C[i],
                         false, st));
             cur = ws + g.w_out[i];
         }
         const float* h = cur;                         // Y_o as [BT, D] rows
         for (int i = 0; i < 4; ++i) {
-            SN_RC(gemm_rows(h, ein[i], 1, prm + g.o_enc_w[i], ein[i], 1, ws + g.w_enc[i], eout[i], BT, eout[i], ein[i]));
+            RULGNN_TRY(gemm_rows(h, ein[i], 1, prm + g.o_enc_w[i], ein[i], 1, ws + g.w_enc[i], eout[i], BT, eout[i], ein[i]));
             hipLaunchKernelGGL(sn_bias_act_kernel, dim3(sn_grid((int64_t)BT * eout[i])), dim3(SB), 0, st, ws + g.w_enc[i], prm + g.o_enc_b[i],
                                (int64_t)BT, eout[i], i < 3 ? 1 : 0);
             h = ws + g.w_enc[i];
         }
         for (int i = 0; i < 4; ++i) {
-            SN_RC(sgemm(h, din[i], 1, prm + g.o_dec_w[i], din[i], 1, ws + g.w_dec[i], dout[i], BT, dout[i], din[i], false, st));
+            RULGNN_TRY(sgemm(h, din[i], 1, prm + g.o_dec_w[i], din[i], 1, ws + g.w_dec[i], dout[i], BT, dout[i], din[i], false, st));
             hipLaunchKernelGGL(sn_bias_act_kernel, dim3(sn_grid((int64_t)BT * dout[i])), dim3(SB), 0, st, ws + g.w_dec[i], prm + g.o_dec_b[i],
                                (int64_t)BT, dout[i], i < 3 ? 1 : 0);
             h = ws + g.w_dec[i];
@@ -402,7 +397,7 @@ int stnet_run(const rulgnn_stnet_shape* s, const rulgnn_stnet_args* a, int mode,
                            rscale, ws + g.w_dD1, ws + g.w_dD2, ws + g.w_rsq);
         (void)block_sum((const float*)(ws + g.w_rsq), (int64_t)g.rblocks, ws + g.w_one + 1, st);
         SN_LAUNCH_OK();
-        SN_RC(bilstm_forward(&ls, &la, st, 1));
+        RULGNN_TRY(bilstm_forward(&ls, &la, st, 1));
         hipLaunchKernelGGL(sn_head_kernel, dim3((unsigned)(g.B < 1024 ? g.B : 1024)), dim3(SB), 0, st, g, (const float*)(ws + g.w_hseq), prm, a->y,
                            a->pred, ws, inv_gb);
         if (a->recon) hipLaunchKernelGGL(sn_loss_kernel, dim3(1), dim3(1), 0, st, (const float*)(ws + g.w_one + 1), (const float*)(ws + g.w_one + 3),
@@ -421,15 +416,15 @@ int stnet_run(const rulgnn_stnet_shape* s, const rulgnn_stnet_args* a, int mode,
         hipLaunchKernelGGL(sn_fill_kernel, dim3(1), dim3(64), 0, st, one, 1, 1.0f);
         hipLaunchKernelGGL(sn_fill_kernel, dim3(1), dim3(64), 0, st, gr + g.o_cw, 3, 0.0f);          // the 1x1 convolution has no gradient
         // head
-        SN_RC(sgemm_splitk(dpred, 0, 1, ws + g.w_hseq, 1, E * g.T, gr + g.o_lw, E * g.T, 1, E * g.T, (int)g.B, false, split, st));
-        SN_RC(sgemm_splitk(dpred, 0, 1, one, 0, 0, gr + g.o_lb, 1, 1, 1, (int)g.B, false, split, st));
+        RULGNN_TRY(sgemm_splitk(dpred, 0, 1, ws + g.w_hseq, 1, E * g.T, gr + g.o_lw, E * g.T, 1, E * g.T, (int)g.B, false, split, st));
+        RULGNN_TRY(sgemm_splitk(dpred, 0, 1, one, 0, 0, gr + g.o_lb, 1, 1, 1, (int)g.B, false, split, st));
         hipLaunchKernelGGL(sn_head_bwd_kernel, dim3(sn_grid(g.B * E * g.T)), dim3(SB), 0, st, g, dpred, prm, ws + g.w_dhs);
         SN_LAUNCH_OK();
         la.dout = ws + g.w_dhs;
         la.dx = ws + g.w_dH;
         la.dw_ih[0] = gr + g.o_wih; la.dw_hh[0] = gr + g.o_whh; la.db_ih[0] = gr + g.o_bih; la.db_hh[0] = gr + g.o_bhh;
         la.dw_ih[1] = la.dw_ih[0]; la.dw_hh[1] = la.dw_hh[0]; la.db_ih[1] = la.db_ih[0]; la.db_hh[1] = la.db_hh[0];
-        SN_RC(bilstm_backward(&ls, &la, st, 1));
+        RULGNN_TRY(bilstm_backward(&ls, &la, st, 1));
         // decoder, from d Yp = w_dD1 (the reconstruction scale of a data-parallel shard is the global one: recon is in the loss with weight 1)
         if (a->recon_weight)
             hipLaunchKernelGGL(sn_scale2_kernel, dim3(sn_grid((int64_t)BT * D)), dim3(SB), 0, st, ws + g.w_dD1, ws + g.w_dD2, (int64_t)BT * D,
@@ -440,10 +435,10 @@ int stnet_run(const rulgnn_stnet_shape* s, const rulgnn_stnet_args* a, int mode,
             const float* hin = i > 0 ? ws + g.w_dec[i - 1] : ws + g.w_enc[3];
             if (i < 3) hipLaunchKernelGGL(sn_relu_bwd_kernel, dim3(sn_grid((int64_t)BT * dout[i])), dim3(SB), 0, st, d, (const float*)(ws + g.w_dec[i]),
                                           (int64_t)BT * dout[i]);
-            SN_RC(sgemm_splitk(d, 1, dout[i], hin, 1, din[i], gr + g.o_dec_w[i], din[i], dout[i], din[i], BT, false, split, st));
-            SN_RC(sgemm_splitk(one, 0, 0, d, 1, dout[i], gr + g.o_dec_b[i], dout[i], 1, dout[i], BT, false, split, st));
+            RULGNN_TRY(sgemm_splitk(d, 1, dout[i], hin, 1, din[i], gr + g.o_dec_w[i], din[i], dout[i], din[i], BT, false, split, st));
+            RULGNN_TRY(sgemm_splitk(one, 0, 0, d, 1, dout[i], gr + g.o_dec_b[i], dout[i], 1, dout[i], BT, false, split, st));
             float* dn = dA[i & 1];
-            SN_RC(gemm_rows(d, dout[i], 1, prm + g.o_dec_w[i], 1, din[i], dn, din[i], BT, din[i], dout[i]));
+            RULGNN_TRY(gemm_rows(d, dout[i], 1, prm + g.o_dec_w[i], 1, din[i], dn, din[i], BT, din[i], dout[i]));
             d = dn;
         }
         // d H = decoder path + LSTM path
@@ -454,10 +449,10 @@ int stnet_run(const rulgnn_stnet_shape* s, const rulgnn_stnet_args* a, int mode,
             const float* hin = i > 0 ? ws + g.w_enc[i - 1] : yo;
             if (i < 3) hipLaunchKernelGGL(sn_relu_bwd_kernel, dim3(sn_grid((int64_t)BT * eout[i])), dim3(SB), 0, st, d, (const float*)(ws + g.w_enc[i]),
                                           (int64_t)BT * eout[i]);
-            SN_RC(sgemm_splitk(d, 1, eout[i], hin, 1, ein[i], gr + g.o_enc_w[i], ein[i], eout[i], ein[i], BT, false, split, st));
-            SN_RC(sgemm_splitk(one, 0, 0, d, 1, eout[i], gr + g.o_enc_b[i], eout[i], 1, eout[i], BT, false, split, st));
+            RULGNN_TRY(sgemm_splitk(d, 1, eout[i], hin, 1, ein[i], gr + g.o_enc_w[i], ein[i], eout[i], ein[i], BT, false, split, st));
+            RULGNN_TRY(sgemm_splitk(one, 0, 0, d, 1, eout[i], gr + g.o_enc_b[i], eout[i], 1, eout[i], BT, false, split, st));
             float* dn = i > 0 ? (d == dA[0] ? dA[1] : dA[0]) : ws + g.w_dD1;          // the last one is [BT, D]: d Y_o through the encoder
-            SN_RC(sgemm(d, eout[i], 1, prm + g.o_enc_w[i], 1, ein[i], dn, ein[i], BT, ein[i], eout[i], false, st));
+            RULGNN_TRY(sgemm(d, eout[i], 1, prm + g.o_enc_w[i], 1, ein[i], dn, ein[i], BT, ein[i], eout[i], false, st));
             d = dn;
         }
         // d Y_o = encoder path + the reconstruction term's own gradient
@@ -467,9 +462,9 @@ int stnet_run(const rulgnn_stnet_shape* s, const rulgnn_stnet_args* a, int mode,
         float* dc[2] = {ws + g.w_dc1, ws + g.w_dc2};
         for (int i = nc - 1; i >= 0; --i) {
             const int Ci = g.C[i], Co = g.C[i + 1];
-            SN_RC(sgemm_splitk(ws + g.w_terms[i], 1, 3 * Ci, dcur, 1, Co, gr + g.o_f[i], Co, 3 * Ci, Co, R, false, split, st));
+            RULGNN_TRY(sgemm_splitk(ws + g.w_terms[i], 1, 3 * Ci, dcur, 1, Co, gr + g.o_f[i], Co, 3 * Ci, Co, R, false, split, st));
             if (i == 0) break;                        // the input carries no gradient
-            SN_RC(sgemm(dcur, Co, 1, fop[i], Co, 1, ws + g.w_dterms, 3 * Ci, R, 3 * Ci, Co, false, st));
+            RULGNN_TRY(sgemm(dcur, Co, 1, fop[i], Co, 1, ws + g.w_dterms, 3 * Ci, R, 3 * Ci, Co, false, st));
             float* dn = dc[i & 1];
             hipLaunchKernelGGL(sn_terms_bwd_kernel, dim3(ggrid), dim3(SB), 0, st, g, Ci, (const float*)(ws + g.w_dterms), mask, dn);
             SN_LAUNCH_OK();

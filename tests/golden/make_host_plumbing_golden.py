@@ -1,0 +1,400 @@
+"""Pins the host-only answers of librulgnn.so: every workspace / parameter-count query over a table of shapes, and the code each
+family's C entries return for a fixed list of bad argument sets.  All of it returns before any launch, so it runs without a GPU.
+
+The golden, tests/golden/host_plumbing.json, is written by the library built from the PARENT commit of the change under test, never by
+the code under test:
+
+    RULGNN_LIB=<parent build>/librulgnn.so python tests/golden/make_host_plumbing_golden.py <parent commit hash>
+
+tests/test_host_plumbing_cpu.py imports collect() from this file and replays it against the current build.  Generate where no GPU is
+visible: a size that followed the compute-unit count would then be pinned at the library's fallback of 256, which is also the MI355X's
+count (none does today: the partial-row counts that enter the workspaces are constants).
+"""
+from __future__ import annotations
+
+import ctypes as C
+import json
+import os
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(os.path.dirname(HERE))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from gnn_rul_benchmarking_amd import _lib as L  # noqa: E402
+
+GOLDEN = os.path.join(HERE, "host_plumbing.json")
+BATCHES = (0, 1, 4, 100)            # the empty batch, one sample, a fixture-sized batch, the reference protocol's batch
+BASE = 1 << 20                       # placeholder device pointers: 256 bytes apart, never dereferenced (nothing is launched)
+
+
+# ---- part (a): shapes ---------------------------------------------------------------------------------------------------------------
+# Per family: the shapes of its golden fixtures, then its hparams.py rows (batch left out: every shape runs at each of BATCHES and at
+# the fixture's own batch), then the edges its layout branches on.
+def _msg(num_patch, patch_size, interval, band, dims=(16, 64, 16, 1), hidden=8):
+    def make(batch):
+        s = L.StmsgcnShape()
+        s.batch, s.num_patch, s.patch_size, s.interval, s.band_width = batch, num_patch, patch_size, interval, band
+        s.num_gcn_layers = len(dims) - 1
+        for i, d in enumerate(dims[1:]):
+            s.gcn_dims[i] = d
+        s.gru_hidden = hidden
+        return s
+    return make
+
+
+def _stnet(num_patch, patch_size, nodes, nperseg, input_dim, cheb, lstm=10, ae=50):
+    def make(batch):
+        s = L.StnetShape()
+        s.batch, s.num_patch, s.patch_size, s.num_nodes, s.nperseg, s.input_dim = batch, num_patch, patch_size, nodes, nperseg, input_dim
+        s.num_cheb = len(cheb)
+        for i, c in enumerate(cheb[:4]):
+            s.cheb_layers[i] = c
+        s.lstm_hidden_dim, s.autoencoder_hidden_dim = lstm, ae
+        return s
+    return make
+
+
+def _plain(cls, *fields):
+    return lambda batch: cls(batch, *fields)
+
+
+_FC_ROWS = {"fd001": (25, 2, 27, 8, 32, 2, 8, 6, 14, 2), "fd002": (1, 50, 3, 8, 12, 2, 8, 10, 14, 74), "fd003": (1, 50, 3, 8, 6, 2, 24, 25, 14, 74),
+            "fd004": (2, 25, 4, 8, 6, 2, 8, 10, 14, 36), "ncmapss": (2, 25, 4, 8, 32, 2, 8, 6, 20, 36), "fd003like_6p": (1, 6, 3, 8, 6, 2, 24, 25, 14, 8)}
+
+# family -> (queries, {shape name: (constructor, fixture batches)})
+FAMILIES = {
+    "stmsgcn": (("param_count", "workspace_bytes"), {
+        "phm1_12x16": (_msg(12, 16, 6, 5), (5,)), "phm2_9x20": (_msg(9, 20, 2, 3), (4, 6)), "xjtu1_6x128": (_msg(6, 128, 3, 5), (3,)),
+        "xjtu2_4x256": (_msg(4, 256, 6, 10), (3,)), "dims_7x32": (_msg(7, 32, 2, 3, (8, 24, 5), 6), (4,)),
+        "row_phm_c1": (_msg(160, 16, 6, 5), ()), "row_phm_c2": (_msg(128, 20, 2, 3), ()), "row_xjtu_c1": (_msg(256, 128, 3, 5), ()),
+        "row_xjtu_c2": (_msg(128, 256, 6, 10), ()),
+        # the GRU kernels' unit groups (HG): hidden <= 4, <= 8, above
+        "hidden4": (_msg(9, 20, 2, 3, hidden=4), ()), "hidden3": (_msg(9, 20, 2, 3, hidden=3), ()), "hidden8": (_msg(12, 16, 6, 5, hidden=8), ()),
+        "hidden16": (_msg(9, 20, 2, 3, hidden=16), ()), "hidden12": (_msg(9, 20, 2, 3, hidden=12), ())}),
+    "astgcnn": (("param_count", "workspace_bytes"), {
+        "cmapss_14x50": (_plain(L.AstgcnnShape, 14, 50, 64, 3), (16, 20)), "ncmapss_20x50": (_plain(L.AstgcnnShape, 20, 50, 64, 3), (6,)),
+        "small_5x12": (_plain(L.AstgcnnShape, 5, 12, 8, 3), (9,)), "k2_7x20": (_plain(L.AstgcnnShape, 7, 20, 16, 2), (4,))}),
+    "stconv": (("param_count", "workspace_bytes"), {
+        "cmapss_14x50": (_plain(L.StconvShape, 14, 50, 6), (12, 20)), "ncmapss_20x50": (_plain(L.StconvShape, 20, 50, 6), (5,)),
+        "small_6x11": (_plain(L.StconvShape, 6, 11, 6), (9,))}),
+    "fcstgnn": (("param_count", "bn_count", "workspace_bytes"),
+                {k: (_plain(L.FcstgnnShape, *v), b) for (k, v), b in zip(_FC_ROWS.items(), ((5,), (3,), (), (6, 10), (3,), (2,)))}),
+    "stgnn": (("param_count", "workspace_bytes", "step_workspace_bytes"), {
+        "cmapss_1x50": (_plain(L.StgnnShape, 14, 1, 50, 64, 3, 10), (9, 16)), "ncmapss_5x10": (_plain(L.StgnnShape, 20, 5, 10, 64, 3, 10), (5,)),
+        "small_3x7": (_plain(L.StgnnShape, 6, 3, 7, 12, 2, 4), (6,))}),
+    "stnet": (("param_count", "workspace_bytes"), {
+        "phm_c1like_6x128": (_stnet(6, 128, 9, 16, 9, (40, 24, 12)), (5, 8)), "phm_c3like_7x32": (_stnet(7, 32, 5, 8, 5, (30, 20, 10)), (4,)),
+        "small_3x24": (_stnet(3, 24, 4, 6, 5, (7, 5), 3, 6), (6,)),
+        "row_phm_c1": (_stnet(20, 128, 9, 16, 9, (300, 200, 100)), ()), "row_phm_c3": (_stnet(80, 32, 5, 8, 5, (300, 200, 100)), ()),
+        "row_xjtu_c1": (_stnet(128, 256, 9, 16, 17, (300, 200, 100)), ()), "row_xjtu_c2": (_stnet(32, 1024, 17, 32, 33, (300, 200, 100)), ()),
+        "row_xjtu_c3": (_stnet(64, 512, 17, 32, 17, (300, 200, 100)), ())}),
+    "sagcn": (("param_count", "workspace_bytes"), {
+        "phm_c1like_12x16": (_plain(L.SagcnShape, 12, 16, 24, 20), (5, 8)), "phm_c2like_9x20": (_plain(L.SagcnShape, 9, 20, 40, 12), (4,)),
+        "xjtu_like_4x1024": (_plain(L.SagcnShape, 4, 1024, 16, 10), (3,)), "small_3x7": (_plain(L.SagcnShape, 3, 7, 5, 6), (6,)),
+        "row_phm_c1": (_plain(L.SagcnShape, 160, 16, 100, 100), ()), "row_phm_c2": (_plain(L.SagcnShape, 128, 20, 1000, 200), ()),
+        "row_xjtu_c1": (_plain(L.SagcnShape, 32, 1024, 1000, 100), ()), "row_xjtu_c2": (_plain(L.SagcnShape, 32, 1024, 1000, 200), ())}),
+    "stagnn": (("param_count", "bn_state_count", "workspace_bytes"), {
+        "cmapss_fd001_h64": (_plain(L.StagnnShape, 14, 50, 64, 10, 3, 0.0), (6,)), "cmapss_fd002_h16": (_plain(L.StagnnShape, 14, 50, 16, 10, 3, 0.0), (7, 20)),
+        "ncmapss_h32": (_plain(L.StagnnShape, 20, 50, 32, 10, 3, 0.0), (5,)), "small_5x12": (_plain(L.StagnnShape, 5, 12, 9, 4, 2, 0.001), (9,)),
+        "row_fd003_h32": (_plain(L.StagnnShape, 14, 50, 32, 10, 3, 0.0), ())}),
+    "rgcnu": (("param_count", "workspace_bytes"), {
+        "cmapss_14x50": (_plain(L.RgcnuShape, 14, 50, 32, 32, 3, 1.0), (7, 20)), "ncmapss_20x50": (_plain(L.RgcnuShape, 20, 50, 32, 32, 3, 1.0), (5,)),
+        "small_5x12": (_plain(L.RgcnuShape, 5, 12, 6, 8, 3, 0.7), (9,))}),
+    "grucm": (("param_count", "workspace_bytes"), {
+        "cmapss_14x50": (_plain(L.GrucmShape, 14, 50, 64), (8, 16)), "ncmapss_20x50": (_plain(L.GrucmShape, 20, 50, 64), (5,)),
+        "odd_9x21": (_plain(L.GrucmShape, 9, 21, 64), (6,)),
+        # gru_hidden_dim 64 has the persistent GRU, any other width the step loop only
+        "hidden32": (_plain(L.GrucmShape, 14, 50, 32), ()), "hidden65": (_plain(L.GrucmShape, 14, 50, 65), ()), "hidden8_9x21": (_plain(L.GrucmShape, 9, 21, 8), ())}),
+    "hagcn": (("graph_param_count", "workspace_bytes"), {
+        "n14_e60_h64": (_plain(L.HagcnShape, 14, 60, 64), (6, 5, 7, 24)), "n20_e60_h64": (_plain(L.HagcnShape, 20, 60, 64), (3,)),
+        "n12_e8_h16": (_plain(L.HagcnShape, 12, 8, 16), (4,))}),
+    "gru": (("workspace_bytes", "persistent_workspace_bytes"), {
+        "l50_i64_h64": (_plain(L.GruShape, 50, 64, 64), (14 * 8,)), "l21_i64_h64": (_plain(L.GruShape, 21, 64, 64), (54,)),
+        "l50_i32_h32": (_plain(L.GruShape, 50, 32, 32), ()), "l5_i64_h64": (_plain(L.GruShape, 5, 64, 64), (100,)), "l3_i12_h12": (_plain(L.GruShape, 3, 12, 12), (36,)),
+        "l1025_i64_h64": (_plain(L.GruShape, 1025, 64, 64), ()), "l50_i65_h64": (_plain(L.GruShape, 50, 65, 64), ())}),
+}
+
+# ST_GCN: (num_patch, patch_size) of the fixtures and the hparams rows, then num_patch at the row-width and path edges
+STGCN_NP = ((9, 21), (14, 30), (14, 50), (16, 16), (20, 50), (40, 64), (160, 16), (1024, 32), (2048, 16),
+            (15, 30), (16, 30), (47, 30), (48, 30), (64, 30), (65, 30))
+
+
+def _sizes(lib):
+    out = {}
+    for fam, (queries, shapes) in FAMILIES.items():
+        for name, (make, fixture_batches) in shapes.items():
+            for b in sorted(set(BATCHES + tuple(fixture_batches))):
+                shp = make(b)                    # (one value per query, in the family's order above)
+                out[f"{fam}/{name}/b{b}"] = [int(getattr(lib, f"rulgnn_{fam}_{q}")(C.byref(shp))) for q in queries]
+    for fam, name, make in (("sagcn", "phm_c2like_9x20", FAMILIES["sagcn"][1]["phm_c2like_9x20"][0]),
+                            ("stagnn", "small_5x12", FAMILIES["stagnn"][1]["small_5x12"][0])):
+        out[f"{fam}/{name}/tap_offsets_from_minus1"] = [int(getattr(lib, f"rulgnn_{fam}_tap_offset")(C.byref(make(4)), w)) for w in range(-1, 12)]
+    for N, P in STGCN_NP:
+        for layers in (1, 2, 3):
+            out[f"stgcn/{N}x{P}/L{layers}/param_count"] = int(lib.rulgnn_stgcn_param_count(N, layers))
+            for k in (1, 2, 3):
+                out[f"stgcn/{N}x{P}/L{layers}/k{k}/param_count_order"] = int(lib.rulgnn_stgcn_param_count_order(N, layers, k))
+                for b in BATCHES:
+                    shp = L.StgcnShape(b, N, P, layers, k)
+                    out[f"stgcn/{N}x{P}/L{layers}/k{k}/b{b}"] = [int(getattr(lib, f"rulgnn_stgcn_{q}")(C.byref(shp))) for q in
+                                                                  ("forward_workspace_bytes", "train_workspace_bytes", "train_guard_counter_offset")]
+    for seq, nseq, inp, hid in ((50, 14 * 6, 14, 60), (10, 70, 10, 60), (6, 48, 6, 8), (1, 1, 1, 1)):
+        out[f"bilstm/t{seq}_s{nseq}_i{inp}_h{hid}/workspace_bytes"] = int(lib.rulgnn_bilstm_workspace_bytes(C.byref(L.BilstmShape(seq, nseq, inp, hid))))
+    for M, N, K in ((800, 32, 8192), (512, 32, 8192), (10240, 1024, 1024), (1024, 1024, 10240), (64, 64, 64), (0, 4, 4)):
+        for split in (0, 1):
+            out[f"sgemm_scaled/{M}x{N}x{K}/split{split}/workspace_bytes"] = int(lib.rulgnn_sgemm_scaled_workspace_bytes(M, N, K, split))
+        out[f"sgemm_splitk/{M}x{N}x{K}/workspace_bytes"] = int(lib.rulgnn_sgemm_splitk_workspace_bytes(M, N, K))
+    for n in (1, 100, 10000, 300001):
+        out[f"rul_metrics/n{n}/workspace_bytes"] = int(lib.rulgnn_rul_metrics_workspace_bytes(n))
+    return out
+
+
+# ---- part (b): return codes ---------------------------------------------------------------------------------------------------------
+# Every argument set below carries at least one fault that the C entry (or the top of the family's run function) answers before any
+# launch; test_host_plumbing_cpu.py skips the replay where a GPU is visible all the same, as tests/test_abi_cpu.py does.
+def _fill(a, skip=()):
+    """Every pointer field of an argument struct -> its own aligned placeholder; returns the names set."""
+    names = []
+    for i, (name, ctype) in enumerate(a._fields_):
+        if ctype is C.c_void_p and name not in skip:
+            setattr(a, name, BASE + 256 * (i + 1))
+            names.append(name)
+    return names
+
+
+def _adam(own_params, **over):
+    o = L.AdamArgs(own_params, BASE + 65536, BASE + 131072, None, 1, 1e-3, 0.9, 0.999, 1e-8, 0.0, 0.1, None)
+    for k, v in over.items():
+        setattr(o, k, v)
+    return o
+
+
+# family -> (args struct, a supported shape, an unsupported shape, fields to set on top of the pointers)
+_STEP_FAMILIES = {
+    "stmsgcn": (L.StmsgcnArgs, _msg(9, 20, 2, 3), _msg(9, 20, 2, 3, (16, 128, 16, 1)), {}),
+    "stgnn": (L.StmsgcnArgs, _plain(L.StgnnShape, 6, 3, 7, 12, 2, 4), _plain(L.StgnnShape, 6, 3, 7, 12, 2, 40), {}),
+    "stnet": (L.StnetArgs, _stnet(3, 24, 4, 6, 5, (7, 5), 3, 6), _stnet(3, 24, 4, 7, 5, (7, 5), 3, 6), {}),
+    "sagcn": (L.SagcnArgs, _plain(L.SagcnShape, 3, 7, 5, 6), _plain(L.SagcnShape, 3, 7, 100000, 6), {}),
+    "stagnn": (L.StagnnArgs, _plain(L.StagnnShape, 5, 12, 9, 4, 2, 0.001), _plain(L.StagnnShape, 5, 12, 4, 4, 2, 0.001), {"training": 1}),
+    "rgcnu": (L.RgcnuArgs, _plain(L.RgcnuShape, 5, 12, 6, 8, 3, 0.7), _plain(L.RgcnuShape, 5, 12, 6, 8, 4, 0.7), {"training": 1, "dropout_p": 0.2}),
+    "grucm": (L.GrucmArgs, _plain(L.GrucmShape, 9, 21, 64), _plain(L.GrucmShape, 33, 21, 64), {"training": 1}),
+}
+_OPTIONAL = ("dpred", "recon_weight", "step_state", "aux_stream")
+
+
+def _family_codes(lib, fam, out):
+    Args, good, bad, extra = _STEP_FAMILIES[fam]
+    B = 4
+    ws_need = int(getattr(lib, f"rulgnn_{fam}_{'step_workspace_bytes' if fam == 'stgnn' else 'workspace_bytes'}")(C.byref(good(B))))
+    out[f"{fam}/workspace_need"] = ws_need
+
+    def args(**over):
+        a = Args()
+        ptrs = _fill(a, skip=_OPTIONAL)
+        # (a workspace one byte short is every set's backstop: the size check is the last one before a launch, at the top of the
+        # family's run function, so it changes no code an earlier check returns and keeps every set away from a launch)
+        a.workspace_bytes, a.global_batch = ws_need - 1, B
+        for k, v in extra.items():
+            setattr(a, k, v)
+        for k, v in over.items():
+            setattr(a, k, (getattr(a, k) or 0) + 1 if v == "misalign" else v)
+        return a, ptrs
+
+    for entry in ("forward", "backward", "fwdbwd"):
+        fn = getattr(lib, f"rulgnn_{fam}_{entry}_f32")
+        fused = entry == "fwdbwd"
+
+        def call(shape, a, opt=None, key=None):
+            rc = fn(shape, a, opt, None) if fused else fn(shape, a, None)
+            out[f"{fam}/{entry}/{key}"] = int(rc)
+
+        a0, ptrs = args()
+        shp = good(B)
+        opt0 = _adam(a0.params)
+        call(None, C.byref(a0), C.byref(opt0), "null_shape")
+        call(C.byref(shp), None, C.byref(opt0), "null_args")
+        call(C.byref(shp), C.byref(a0), C.byref(opt0), "short_workspace")
+        call(C.byref(bad(B)), C.byref(a0), C.byref(opt0), "unsupported_shape")
+        call(C.byref(good(-1)), C.byref(a0), C.byref(opt0), "negative_batch")
+        if entry != "forward":       # an empty batch needs no x, pred or y: the next fault in line answers
+            call(C.byref(good(0)), C.byref(args(x=None, pred=None, y=None, grads="misalign")[0]), C.byref(opt0), "empty_batch_without_x_pred_y_and_grads_plus1")
+        for name in ptrs:
+            for fault in (None, "misalign"):
+                a, _ = args(**{name: fault})
+                call(C.byref(shp), C.byref(a), C.byref(_adam(a.params)), f"{name}_{'null' if fault is None else 'plus1'}")
+        a, _ = args(dpred=BASE + 512 * 64)
+        call(C.byref(shp), C.byref(a), C.byref(_adam(a.params)), "dpred_set")
+        a, _ = args(dpred=BASE + 512 * 64 + 1)
+        call(C.byref(shp), C.byref(a), C.byref(_adam(a.params)), "dpred_plus1")
+        a, _ = args(y=None, dpred=BASE + 512 * 64)
+        call(C.byref(shp), C.byref(a), C.byref(_adam(a.params)), "y_null_dpred_set")
+        if "training" in extra:
+            a, _ = args(training=0, grads="misalign")
+            call(C.byref(shp), C.byref(a), C.byref(_adam(a.params)), "eval_mode_and_grads_plus1")
+            a, _ = args(training=0, y=None)
+            call(C.byref(shp), C.byref(a), C.byref(_adam(a.params)), "eval_mode_and_y_null")
+        if fused:
+            for key, over in (("opt_other_params", dict(params=a0.params + 4)), ("opt_step0", dict(step=0)), ("opt_params_null", dict(params=None)),
+                              ("opt_exp_avg_null", dict(exp_avg=None)), ("opt_exp_avg_sq_null", dict(exp_avg_sq=None)),
+                              ("opt_exp_avg_plus1", dict(exp_avg=BASE + 65537)), ("opt_exp_avg_sq_plus1", dict(exp_avg_sq=BASE + 131073)),
+                              ("opt_step0_with_state_and_exp_avg_plus1", dict(step=0, step_state=BASE + 196608, exp_avg=BASE + 65537)),
+                              # two faults: which answers first
+                              ("opt_step0_and_exp_avg_plus1", dict(step=0, exp_avg=BASE + 65537)),
+                              ("opt_other_params_and_exp_avg_null", dict(params=a0.params + 4, exp_avg=None))):
+                call(C.byref(shp), C.byref(a0), C.byref(_adam(a0.params, **over)), key)
+            call(C.byref(shp), C.byref(a0), None, "no_opt")
+            a, _ = args(x="misalign")
+            call(C.byref(shp), C.byref(a), C.byref(_adam(a.params, step=0)), "x_plus1_and_opt_step0")
+            a, _ = args(grads=None, dpred=BASE + 512 * 64)
+            call(C.byref(shp), C.byref(a), C.byref(_adam(a.params)), "grads_null_and_dpred_set")
+            a, _ = args(dpred=BASE + 512 * 64)
+            call(C.byref(shp), C.byref(a), C.byref(_adam(a.params, exp_avg=BASE + 65537)), "dpred_set_and_exp_avg_plus1")
+            a, _ = args(y=None)
+            call(C.byref(shp), C.byref(a), C.byref(_adam(a.params, exp_avg=BASE + 65537)), "y_null_and_exp_avg_plus1")
+        # two faults on every entry
+        a, _ = args(params="misalign", x=None)
+        call(C.byref(shp), C.byref(a), C.byref(_adam(a.params)), "params_plus1_and_x_null")
+        a, _ = args(y="misalign", grads=None)
+        call(C.byref(shp), C.byref(a), C.byref(_adam(a.params)), "y_plus1_and_grads_null")
+        a, _ = args(pred="misalign", workspace=None)
+        call(C.byref(bad(B)), C.byref(a), C.byref(_adam(a.params)), "unsupported_shape_and_workspace_null")
+    if fam == "grucm":
+        fn = lib.rulgnn_grucm_fwdbwd_f32
+        for key, over in (("dropout_p1", dict(dropout_p=(C.c_float * 3)(0.0, 1.0, 0.0))), ("gru_path9", dict(gru_path=9)),
+                          ("sample_offset_negative", dict(sample_offset=-1)), ("global_batch_short", dict(global_batch=1)),
+                          ("gru_path9_and_params_null", dict(gru_path=9, params=None)), ("loss_plus1_and_grads_null", dict(loss="misalign", grads=None))):
+            a, _ = args(**over)
+            out[f"grucm/fwdbwd/{key}"] = int(fn(C.byref(good(B)), C.byref(a), None, None))
+    if fam == "rgcnu":
+        a, _ = args(dropout_p=1.0, params=None)
+        out["rgcnu/fwdbwd/dropout_p1_and_params_null"] = int(lib.rulgnn_rgcnu_fwdbwd_f32(C.byref(good(B)), C.byref(a), None, None))
+
+
+def _gru_codes(lib, out):
+    shp = L.GruShape(12, 5, 64, 64)
+    for entry, query in (("gru_forward", "gru_workspace_bytes"), ("gru_backward", "gru_workspace_bytes"),
+                         ("gru_persistent_forward", "gru_persistent_workspace_bytes"), ("gru_persistent_backward", "gru_persistent_workspace_bytes")):
+        fn = getattr(lib, f"rulgnn_{entry}_f32")
+        need = int(getattr(lib, f"rulgnn_{query}")(C.byref(shp)))
+
+        def args(**over):
+            a = L.GruArgs()
+            ptrs = _fill(a)
+            a.workspace_bytes = need - 1                    # the backstop of _family_codes
+            for k, v in over.items():
+                setattr(a, k, (getattr(a, k) or 0) + 1 if v == "misalign" else v)
+            return a, ptrs
+
+        a0, ptrs = args()
+        out[f"{entry}/null_shape"] = int(fn(None, C.byref(a0), None))
+        out[f"{entry}/null_args"] = int(fn(C.byref(shp), None, None))
+        out[f"{entry}/short_workspace"] = int(fn(C.byref(shp), C.byref(a0), None))
+        out[f"{entry}/unsupported_shape"] = int(fn(C.byref(L.GruShape(12, 5, 64, 2048)), C.byref(a0), None))
+        if entry == "gru_persistent_backward":       # no sequences need no x, out or d out: the next fault in line answers
+            out[f"{entry}/no_sequences_without_x_out_dout_and_dx_plus1"] = int(fn(C.byref(L.GruShape(0, 5, 64, 64)),
+                                                                                 C.byref(args(x=None, out=None, dout=None, dx="misalign")[0]), None))
+        for name in ptrs:
+            for fault in (None, "misalign"):
+                out[f"{entry}/{name}_{'null' if fault is None else 'plus1'}"] = int(fn(C.byref(shp), C.byref(args(**{name: fault})[0]), None))
+        for key, over in (("w_hh_plus1_and_w_ih_null", dict(w_hh="misalign", w_ih=None)), ("x_null_and_workspace_plus1", dict(x=None, workspace="misalign")),
+                          ("dx_plus1_and_dout_null", dict(dx="misalign", dout=None)), ("db_hh_null_and_x_plus1", dict(db_hh=None, x="misalign"))):
+            out[f"{entry}/{key}"] = int(fn(C.byref(shp), C.byref(args(**over)[0]), None))
+
+
+def _stgcn_step_codes(lib, out):
+    """rulgnn_stgcn_train_step_path_f32 on the fused path (14 x 30) and the tiled one (160 x 16).  Its workspace check sits inside the
+    argument check, ahead of the path and optimizer checks, so there is no backstop here: every set is a fault by itself."""
+    fn = lib.rulgnn_stgcn_train_step_path_f32
+    for tag, N, P in (("fused_14x30", 14, 30), ("tiled_160x16", 160, 16)):
+        shp = L.StgcnShape(4, N, P, 2, 1)
+        need = int(lib.rulgnn_stgcn_train_workspace_bytes(C.byref(shp)))
+        out[f"stgcn_step/{tag}/workspace_need"] = need
+
+        def args(**over):
+            a = L.StgcnTrainArgs()
+            ptrs = _fill(a, skip=_OPTIONAL)
+            a.workspace_bytes, a.global_batch, a.dropout_p = need, 4, 0.2
+            for k, v in over.items():
+                setattr(a, k, (getattr(a, k) or 0) + 1 if v == "misalign" else v)
+            return a, ptrs
+
+        def call(key, shape, a, opt, path=L.STEP_AUTO):
+            out[f"stgcn_step/{tag}/{key}"] = int(fn(shape, a, opt, path, None))
+
+        a0, ptrs = args()
+        opt0 = _adam(a0.params)
+        call("null_shape", None, C.byref(a0), C.byref(opt0))
+        call("null_args", C.byref(shp), None, C.byref(opt0))
+        call("unsupported_shape", C.byref(L.StgcnShape(4, 8192, 32, 2, 1)), C.byref(a0), C.byref(opt0))
+        call("order2_beyond_64_patches", C.byref(L.StgcnShape(4, 160, 16, 2, 2)), C.byref(a0), C.byref(opt0))
+        call("empty_batch", C.byref(L.StgcnShape(0, N, P, 2, 1)), C.byref(a0), C.byref(opt0))
+        call("short_workspace", C.byref(shp), C.byref(args(workspace_bytes=need - 1)[0]), C.byref(opt0))
+        call("bad_path", C.byref(shp), C.byref(a0), C.byref(opt0), 9)
+        for name in ptrs:
+            for fault in (None, "misalign"):
+                a, _ = args(**{name: fault})
+                call(f"{name}_{'null' if fault is None else 'plus1'}", C.byref(shp), C.byref(a), C.byref(_adam(a.params)))
+        for key, over in (("dpred_set", dict(dpred=BASE + 512 * 64)), ("dpred_plus1", dict(dpred=BASE + 512 * 64 + 1)),
+                          ("dropout_p1", dict(dropout_p=1.0)), ("global_batch_short", dict(global_batch=1)), ("sample_offset_negative", dict(sample_offset=-1)),
+                          ("bn_moment_weight_negative", dict(bn_moment_weight=-1.0)),
+                          ("y_plus1_and_short_workspace", dict(y="misalign", workspace_bytes=need - 1)),
+                          ("grads_null_and_dpred_set", dict(grads=None, dpred=BASE + 512 * 64))):
+            a, _ = args(**over)
+            call(key, C.byref(shp), C.byref(a), C.byref(_adam(a.params)))
+        for key, over in (("opt_other_params", dict(params=a0.params + 4)), ("opt_step0", dict(step=0)), ("opt_params_null", dict(params=None)),
+                          ("opt_exp_avg_null", dict(exp_avg=None)), ("opt_exp_avg_sq_null", dict(exp_avg_sq=None)),
+                          ("opt_exp_avg_plus1", dict(exp_avg=BASE + 65537)), ("opt_exp_avg_sq_plus1", dict(exp_avg_sq=BASE + 131073)),
+                          ("opt_bn_stats_plus1", dict(bn_stats=BASE + 196609)),
+                          ("opt_step0_with_state_and_exp_avg_plus1", dict(step=0, step_state=BASE + 196608, exp_avg=BASE + 65537)),
+                          ("opt_step0_and_exp_avg_plus1", dict(step=0, exp_avg=BASE + 65537)),
+                          ("opt_other_params_and_exp_avg_null", dict(params=a0.params + 4, exp_avg=None)),
+                          ("opt_bn_stats_plus1_and_exp_avg_sq_null", dict(bn_stats=BASE + 196609, exp_avg_sq=None))):
+            call(key, C.byref(shp), C.byref(a0), C.byref(_adam(a0.params, **over)))
+        call("bad_path_and_opt_step0", C.byref(shp), C.byref(a0), C.byref(_adam(a0.params, step=0)), 9)
+        a, _ = args(dpred=BASE + 512 * 64)
+        call("dpred_set_and_exp_avg_plus1", C.byref(shp), C.byref(a), C.byref(_adam(a.params, exp_avg=BASE + 65537)))
+        a, _ = args(x="misalign")
+        call("x_plus1_and_opt_step0", C.byref(shp), C.byref(a), C.byref(_adam(a.params, step=0)))
+
+
+def _codes(lib):
+    out = {}
+    for fam in _STEP_FAMILIES:
+        _family_codes(lib, fam, out)
+    _gru_codes(lib, out)
+    _stgcn_step_codes(lib, out)
+    beyond = [k for k, v in out.items() if not k.endswith("workspace_need") and v in (L.OK, L.EHIP)]
+    assert not beyond, ("argument sets that got past every check", beyond)
+    return out
+
+
+def pack(flat):
+    """{"a/b/c": v} -> {"a/b": {"c": v}}: one line of the golden per shape or entry."""
+    out = {}
+    for k, v in flat.items():
+        head, _, leaf = k.rpartition("/")
+        out.setdefault(head, {})[leaf] = v
+    return out
+
+
+def unpack(nested):
+    return {f"{head}/{leaf}": v for head, d in nested.items() for leaf, v in d.items()}
+
+
+def collect(lib, codes=True):
+    """{"sizes": {...}, "codes": {...}} of `lib` (a loaded _lib handle); `codes=False` leaves the argument sets out."""
+    return {"sizes": _sizes(lib), "codes": _codes(lib) if codes else {}}
+
+
+if __name__ == "__main__":
+    if len(sys.argv) != 2 or not os.environ.get("RULGNN_LIB"):
+        raise SystemExit("usage: RULGNN_LIB=<library built from the parent commit> make_host_plumbing_golden.py <parent commit hash>")
+    got = collect(L.load())
+    with open(GOLDEN, "w") as f:
+        f.write('{"parent_commit": "%s",\n' % sys.argv[1])
+        for section in ("sizes", "codes"):
+            rows = ",\n".join(f" {json.dumps(k)}: {json.dumps(v, sort_keys=True, separators=(',', ':'))}" for k, v in sorted(pack(got[section]).items()))
+            f.write(f'"{section}": {{\n{rows}\n}}' + (",\n" if section == "sizes" else "}\n"))
+    print("wrote", GOLDEN, len(got["sizes"]), "sizes,", len(got["codes"]), "codes")
