@@ -635,13 +635,8 @@ __device__ __forceinline__ void ast_finalize_body(const AstGeom& g, const AstFin
         ast_bn_batch_body(g, cells, bn_batch, bn_weight, c - 64);
         if (bn_running) {       // nn.BatchNorm1d's running statistics (ast_bn_running_kernel's arithmetic on the values just written)
             const int blk = (c - 64) / g.N, ch = (c - 64) % g.N;
-            const double count = (double)g.BG * g.T;
-            const float mean = bn_batch[(blk * 2 + 0) * g.N + ch], var = bn_batch[(blk * 2 + 1) * g.N + ch];
-            const float unbiased = count > 1.0 ? (float)(var * (count / (count - 1.0))) : var;
-            float* rm = bn_running + (blk * 2 + 0) * g.N + ch;
-            float* rv = bn_running + (blk * 2 + 1) * g.N + ch;
-            *rm = (1.0f - bn_momentum) * *rm + bn_momentum * mean;
-            *rv = (1.0f - bn_momentum) * *rv + bn_momentum * unbiased;
+            bn_running_blend(bn_running + (blk * 2 + 0) * g.N + ch, bn_running + (blk * 2 + 1) * g.N + ch, bn_batch[(blk * 2 + 0) * g.N + ch],
+                             bn_batch[(blk * 2 + 1) * g.N + ch], (double)g.BG * g.T, bn_momentum, 0, 1);
         }
     }
     if (loss) {             // strided partial sums, then a fixed-order tree (block_sum's arithmetic at 256 threads)
@@ -680,33 +675,11 @@ __global__ __launch_bounds__(1024) void ast_tail_kernel(AstGeom g, AstFin f, Row
     else ast_finalize_body(g, f, fred, ad);
 }
 
-// Synchronised BatchNorm: the 16 replicas of one reduction pair (2 MAXN contiguous doubles) collapsed into replica 0, the
-// others zeroed (the readers' replica sum is unchanged): the caller's all-reduce runs on one contiguous buffer.
-__global__ void ast_cells_collapse_kernel(Cells* cells, int bwd, int blk) {
-    for (int i = threadIdx.x; i < 2 * MAXN; i += blockDim.x) {
-        double v = 0.0;
-        for (int r = 0; r < CELL_REP; ++r) {
-            double* p = bwd ? &cells[r].bwd[blk][0][0] : &cells[r].fwd[blk][0][0];
-            v += p[i];
-            if (r) p[i] = 0.0;
-        }
-        (bwd ? &cells[0].bwd[blk][0][0] : &cells[0].fwd[blk][0][0])[i] = v;
-    }
-}
-
 // BatchNorm batch statistics out: (mean, biased var) per block/channel, or weight * (E[z], E[z^2]) for data parallel
 __device__ __forceinline__ void ast_bn_batch_body(const AstGeom& g, const Cells* cells, float* __restrict__ bn_batch, float weight, int e) {
     const int blk = e / g.N, c = e % g.N;
-    const double count = (double)g.BG * g.T;
-    const double m = cell_sum(cells, &Cells::fwd, blk, c, 0) / count, q = cell_sum(cells, &Cells::fwd, blk, c, 1) / count;
-    if (weight > 0.f) {
-        bn_batch[(blk * 2 + 0) * g.N + c] = (float)(weight * m);
-        bn_batch[(blk * 2 + 1) * g.N + c] = (float)(weight * q);
-    } else {
-        double v = q - m * m;
-        bn_batch[(blk * 2 + 0) * g.N + c] = (float)m;
-        bn_batch[(blk * 2 + 1) * g.N + c] = (float)(v < 0.0 ? 0.0 : v);
-    }
+    bn_batch_out(cell_sum(cells, &Cells::fwd, blk, c, 0), cell_sum(cells, &Cells::fwd, blk, c, 1), (double)g.BG * g.T, weight,
+                 bn_batch + (blk * 2 + 0) * g.N + c, bn_batch + (blk * 2 + 1) * g.N + c);
 }
 __global__ void ast_bn_batch_kernel(AstGeom g, const Cells* cells, float* __restrict__ bn_batch, float weight) {
     if ((int)threadIdx.x < 2 * g.N) ast_bn_batch_body(g, cells, bn_batch, weight, threadIdx.x);
@@ -717,20 +690,11 @@ __global__ void ast_bn_running_kernel(float* __restrict__ bn, const float* __res
     const int e = threadIdx.x;
     if (e >= 2 * N) return;
     const int blk = e / N, c = e % N;
-    float mean = batch[(blk * 2 + 0) * N + c], var = batch[(blk * 2 + 1) * N + c];
-    if (from_moments) {
-        var = var - mean * mean;
-        if (var < 0.f) var = 0.f;
-    }
-    const float unbiased = count > 1.0 ? (float)(var * (count / (count - 1.0))) : var;
-    float* rm = bn + (blk * 2 + 0) * N + c;
-    float* rv = bn + (blk * 2 + 1) * N + c;
-    *rm = (1.0f - momentum) * *rm + momentum * mean;
-    *rv = (1.0f - momentum) * *rv + momentum * unbiased;
+    bn_running_blend(bn + (blk * 2 + 0) * N + c, bn + (blk * 2 + 1) * N + c, batch[(blk * 2 + 0) * N + c], batch[(blk * 2 + 1) * N + c], count, momentum,
+                     from_moments, 1);
 }
 
 constexpr int AST_BWD_ROWS = 4096;      // workgroups of the graph backward at most (one partial row of the gate's bias gradient each)
-__global__ void ast_fill_one_kernel(float* p) { p[0] = 1.f; }
 // head of a call with a forward: the reduction cells cleared and the constant 1 of the bias reductions, one launch
 __global__ void ast_prepare_kernel(Cells* cells, float* one) {
     double* p = reinterpret_cast<double*>(cells);
@@ -812,7 +776,7 @@ size_t astgcnn_workspace_bytes(const rulgnn_astgcnn_shape* s) {
 // <SN, SE, SO>: the kernels' instantiation -- the reference's two wirings (N-CMAPSS: 20 nodes, C-MAPSS: 14; 50 steps, 64 outputs) have their
 // shapes as compile-time constants, anything else runs the generic <0, 0, 0>
 template <int SN, int SE, int SO>
-static int astgcnn_run_t(const rulgnn_astgcnn_shape* s, const rulgnn_astgcnn_args* a, int mode, hipStream_t st, const BnSyncHook* sync,
+static int astgcnn_run_t(const rulgnn_astgcnn_shape* s, const rulgnn_astgcnn_args* a, int mode, hipStream_t st, const SyncHook* sync,
                          float* bn_running_out, float bn_momentum, AdamFuse* adam) {
     // threads of the TCN kernels: 20 nodes x 50 steps are 260 / 400 work items per sample -- one round of 448 threads (tcn_nodes.hpp)
     constexpr int TTB = AB;             // (the matrix-core convolution kernels: four wavefronts, a 16-step column tile each)
@@ -834,12 +798,11 @@ static int astgcnn_run_t(const rulgnn_astgcnn_shape* s, const rulgnn_astgcnn_arg
     const int M = (int)(g.B * N);
     const float inv_gb = 1.0f / (float)(a->global_batch > 0 ? a->global_batch : g.B);
     (void)hipGetLastError();
+    // reduction pair `blk` (forward or backward) is complete behind the launch just enqueued: 2 MAXN contiguous doubles of every replica
+    constexpr int PAIR = 2 * MAXN, FWD0 = offsetof(Cells, fwd) / sizeof(double), BWD0 = offsetof(Cells, bwd) / sizeof(double);
+    static_assert(FWD0 == 0 && BWD0 == 2 * PAIR && sizeof(Cells) == sizeof(double) * 4 * PAIR, "Cells: fwd[2] then bwd[2] pairs of doubles");
     auto sync_pair = [&](int bwd, int blk) -> int {
-        if (!sync) return RULGNN_OK;
-        hipLaunchKernelGGL(ast_cells_collapse_kernel, dim3(1), dim3(64), 0, st, cells, bwd, blk);
-        if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
-        double* buf = bwd ? &cells[0].bwd[blk][0][0] : &cells[0].fwd[blk][0][0];
-        return sync->fn(sync->user, buf, 2 * MAXN, st) == 0 ? RULGNN_OK : RULGNN_ECALLBACK;
+        return sync_cells(sync, reinterpret_cast<double*>(cells), (bwd ? BWD0 : FWD0) + blk * PAIR, PAIR, sizeof(Cells) / sizeof(double), st);
     };
     // The parameter-gradient products of the backward feed nothing in this call: with a second stream of the caller (args->aux_stream,
     // aux_stream.hpp) they run beside the TCN backward, forked behind the graph-backward kernel's own completion signal.
@@ -871,7 +834,7 @@ static int astgcnn_run_t(const rulgnn_astgcnn_shape* s, const rulgnn_astgcnn_arg
         // the constant 1 the bias reduction reads: written IN FRONT of the fork (behind it the side stream's product over `one` was
         // ordered against nothing that wrote it -- garbage from a fresh workspace on the first step)
         // (with a forward in the same call ast_prepare_kernel wrote it; batch statistics and the loss sum ride in the finalize kernel)
-        if (!(mode & 1)) hipLaunchKernelGGL(ast_fill_one_kernel, dim3(1), dim3(1), 0, st, F(w.one));
+        if (!(mode & 1)) RULGNN_TRY(fill_f32(F(w.one), 1, 1.f, st));
         // DT = D Fcat^T, the graph backward, dG = dG_cheb + dPX P and the gate backward (BatchNorm-2 sums): one launch
         const int bwd_rows = resident_rows((ast_graph_bwd_kernel<SN, SE, SO>), AB, 0, g.B, AST_BWD_ROWS);
         hipEvent_t bwd_done = fk.stop_event();                       // (the fork point: behind this kernel)
@@ -939,7 +902,7 @@ static int astgcnn_run_t(const rulgnn_astgcnn_shape* s, const rulgnn_astgcnn_arg
     return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
 }
 
-int astgcnn_run(const rulgnn_astgcnn_shape* s, const rulgnn_astgcnn_args* a, int mode, hipStream_t st, const BnSyncHook* sync, float* bn_running_out,
+int astgcnn_run(const rulgnn_astgcnn_shape* s, const rulgnn_astgcnn_args* a, int mode, hipStream_t st, const SyncHook* sync, float* bn_running_out,
                 float bn_momentum, AdamFuse* adam) {
     if (adam) adam->gbase = nullptr;          // (set by the path that applies the update: see stgcn_host.hpp)
     if (s && s->time_length == 50 && s->output_dim == 64) {

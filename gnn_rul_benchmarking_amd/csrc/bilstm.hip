@@ -342,7 +342,6 @@ __global__ __launch_bounds__(4 * HMAX) void lstm_backward_kernel(LstmGeom g, con
     }
 }
 
-__global__ void lstm_fill_one_kernel(float* p) { p[0] = 1.f; }
 // db_ih = db_hh: copy
 __global__ void lstm_copy_kernel(const float* __restrict__ a, float* __restrict__ b, int n) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -406,7 +405,7 @@ int bilstm_backward(const rulgnn_bilstm_shape* s, const rulgnn_bilstm_args* a, h
     else bwd(lstm_backward_kernel<128, true>);
     float* one = ws + g.o_one;
     float* split = ws + g.o_split;
-    hipLaunchKernelGGL(lstm_fill_one_kernel, dim3(1), dim3(1), 0, st, one);
+    RULGNN_TRY(fill_f32(one, 1, 1.f, st));
     // The data gradient first: the layer below waits for nothing else.  dx (+)= dG W_ih
     if (a->dx)
         for (int d = 0; d < ndir; ++d)

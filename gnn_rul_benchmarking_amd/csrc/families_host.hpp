@@ -5,7 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/rulgnn.h"
-#include "stgcn_host.hpp"          // StepState, dropout_layer_key, host_util.hpp
+#include "stgcn_host.hpp"          // StepState, dropout_layer_key, SyncHook (bn_cells.hpp), host_util.hpp
 
 namespace rulgnn {
 
@@ -15,12 +15,11 @@ int stmsgcn_features(const rulgnn_stmsgcn_shape* s, const float* x, const float*
 int stmsgcn_run(const rulgnn_stmsgcn_shape* s, const rulgnn_stmsgcn_args* a, int mode, hipStream_t stream);
 int64_t astgcnn_param_count(const rulgnn_astgcnn_shape* s);
 size_t astgcnn_workspace_bytes(const rulgnn_astgcnn_shape* s);
-struct BnSyncHook;
 struct AdamFuse;          // adam_device.hpp
 // (`bn_running_out` != nullptr, whole training steps with plain batch statistics: the finalize kernel also updates the running statistics;
 // `adam` != nullptr, whole training steps: the constants of the optimizer update (adam_fuse_args) -- on return adam->gbase != nullptr says
 // the step's last kernel applied it, else the caller launches adam_step)
-int astgcnn_run(const rulgnn_astgcnn_shape* s, const rulgnn_astgcnn_args* a, int mode, hipStream_t stream, const BnSyncHook* sync = nullptr,
+int astgcnn_run(const rulgnn_astgcnn_shape* s, const rulgnn_astgcnn_args* a, int mode, hipStream_t stream, const SyncHook* sync = nullptr,
                 float* bn_running_out = nullptr, float bn_momentum = 0.f, AdamFuse* adam = nullptr);
 void adam_fuse_args(AdamFuse* t, float* p, float* m, float* v, const float* gbase, int64_t step, float lr, float beta1, float beta2, float eps,
                     float wd);
@@ -29,19 +28,12 @@ int astgcnn_bn_running_update(const rulgnn_astgcnn_shape* s, float* bn_stats, co
 int64_t fcstgnn_param_count(const rulgnn_fcstgnn_shape* s);
 int64_t fcstgnn_bn_count(const rulgnn_fcstgnn_shape* s);
 size_t fcstgnn_workspace_bytes(const rulgnn_fcstgnn_shape* s);
-// synchronised BatchNorm hook of the FC_STGNN / ASTGCNN steps (include/rulgnn.h: rulgnn_*_fwdbwd_syncbn_f32)
-struct BnSyncHook {
-    rulgnn_allreduce_f64_fn fn;
-    void* user;
-    float bn_param_grad_scale;
-};
-typedef BnSyncHook FcstgnnSync;
 // (`bn_running_out` != nullptr, whole training steps with plain batch statistics: the running-statistics update rides on the side stream
 // behind the batch-statistics kernel instead of closing the step)
 // (`fuse` != nullptr, whole training steps on one rank: the step's last launch -- the finalize kernel, then behind the join with the side
 // stream -- applies torch.optim.Adam to every parameter: adam_device.hpp; no optimizer launch)
 struct AdamFuse;
-int fcstgnn_run(const rulgnn_fcstgnn_shape* s, const rulgnn_fcstgnn_args* a, int mode, hipStream_t stream, const FcstgnnSync* sync = nullptr,
+int fcstgnn_run(const rulgnn_fcstgnn_shape* s, const rulgnn_fcstgnn_args* a, int mode, hipStream_t stream, const SyncHook* sync = nullptr,
                 float* bn_running_out = nullptr, float bn_momentum = 0.f, const AdamFuse* fuse = nullptr);
 int fcstgnn_bn_running_update(const rulgnn_fcstgnn_shape* s, float* bn_stats, const float* bn_batch, float momentum, int from_moments,
                               hipStream_t stream);
@@ -59,6 +51,12 @@ int stconv_bn_running_update(const rulgnn_stconv_shape* s, float* bn_stats, cons
                              int from_moments, hipStream_t stream);
 int adam_step(float* p, const float* g, float* m, float* v, int64_t n, int64_t step, float lr, float beta1, float beta2,
               float eps, float wd, float gscale, hipStream_t stream, void* step_state = nullptr, const float* guard = nullptr);
+// Synchronised BatchNorm, the one step behind every launch that completes a reduction pair (bn_cells.hpp): the CELL_REP replicas of the
+// `n` <= 128 contiguous doubles at cells + off (the replicas `replica_stride` doubles apart) are collapsed into replica 0, then
+// h->fn runs on cells + off.  RULGNN_OK at once when `h` is null; RULGNN_EHIP / RULGNN_ECALLBACK.
+int sync_cells(const SyncHook* h, double* cells, int off, int n, int replica_stride, hipStream_t st);
+// p[0 .. n) = v
+int fill_f32(float* p, int64_t n, float v, hipStream_t st);
 int step_state_set(void* state, uint64_t dropout_step, int64_t adam_step, hipStream_t stream);
 int step_prepare_dropout(void* state, uint64_t seed, int num_layers, hipStream_t stream);   // ++dropout_step, keys
 int step_prepare_adam(void* state, float lr, float beta1, float beta2, hipStream_t stream); // ++adam_step, bias corrections

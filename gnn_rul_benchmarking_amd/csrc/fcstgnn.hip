@@ -117,43 +117,15 @@ struct Cells {
     double bwd[NBN][MAXC][2];       // sum dy, sum dy * xhat
 };
 
-// Every workgroup adds its partial sums with one atomic per channel; thousands of workgroups hitting the same addresses
-// serialise (~10 ns each: 40-50 us per streaming kernel at 4096 workgroups), so the cells exist CELL_REP times, workgroup b
-// adds into replica b % CELL_REP and the readers sum the replicas in a fixed order.
-constexpr int CELL_REP = 16;
-__device__ inline double cell_fwd(const Cells* cells, int id, int c, int j) {
-    double v = 0.0;
-#pragma unroll
-    for (int r = 0; r < CELL_REP; ++r) v += cells[r].fwd[id][c][j];
-    return v;
-}
-__device__ inline double cell_bwd(const Cells* cells, int id, int c, int j) {
-    double v = 0.0;
-#pragma unroll
-    for (int r = 0; r < CELL_REP; ++r) v += cells[r].bwd[id][c][j];
-    return v;
-}
+// one cell over its CELL_REP replicas (bn_cells.hpp)
+constexpr int CELLS_STRIDE = sizeof(Cells) / sizeof(double);
+__device__ inline double cell_fwd(const Cells* cells, int id, int c, int j) { return replica_sum(&cells[0].fwd[id][c][j], CELLS_STRIDE); }
+__device__ inline double cell_bwd(const Cells* cells, int id, int c, int j) { return replica_sum(&cells[0].bwd[id][c][j], CELLS_STRIDE); }
 
-struct BnCoef {
-    float mean, inv, sc, sh;
-};
 __device__ inline BnCoef fbn(const FcGeom& g, const Cells* cells, const float* prm, const float* running, int training, int id, int c) {
-    BnCoef r;
-    float var;
-    if (training) {
-        const double m = cell_fwd(cells, id, c, 0) / g.cnt[id];
-        double v = cell_fwd(cells, id, c, 1) / g.cnt[id] - m * m;
-        if (v < 0.0) v = 0.0;
-        r.mean = (float)m;
-        var = (float)v;
-    } else {
-        r.mean = running[g.bn_off[id] + c];
-        var = running[g.bn_off[id] + g.bn_ch[id] + c];
-    }
-    r.inv = 1.0f / sqrtf(var + BN_EPS);
-    r.sc = prm[g.bn_g[id] + c] * r.inv;
-    r.sh = prm[g.bn_b[id] + c] - r.mean * r.sc;
-    return r;
+    const BnMoments s = training ? bn_moments(cell_fwd(cells, id, c, 0), cell_fwd(cells, id, c, 1), g.cnt[id])
+                                 : BnMoments{running[g.bn_off[id] + c], running[g.bn_off[id] + g.bn_ch[id] + c]};
+    return bn_coef(s, prm[g.bn_g[id] + c], prm[g.bn_b[id] + c], BN_EPS);
 }
 
 // per-workgroup (sum, sumsq) accumulators in LDS doubles, flushed to the cells with one atomic per channel.  Two measures
@@ -1809,21 +1781,6 @@ __global__ __launch_bounds__(FB) void fc_conv_wgrad_both_kernel(FcGeom g, const 
     else fc_conv_wgrad_body<1, SK, SL1, SL2, SH1, SCO>(g, x, prm, cells, z1, dy1, gp1, z1);
 }
 
-// Synchronised BatchNorm: the 16 replicas of ONE reduction pair (forward: sum z, sum z^2; backward: sum dy, sum dy x-hat;
-// 2 MAXC contiguous doubles) are collapsed into replica 0 and the others zeroed -- the readers' replica sum is unchanged -- so that
-// the caller's all-reduce runs on one contiguous buffer.
-__global__ void fc_cells_collapse_kernel(Cells* cells, int bwd, int id) {
-    for (int i = threadIdx.x; i < 2 * MAXC; i += blockDim.x) {
-        double v = 0.0;
-        for (int r = 0; r < CELL_REP; ++r) {
-            double* p = bwd ? &cells[r].bwd[id][0][0] : &cells[r].fwd[id][0][0];
-            v += p[i];
-            if (r) p[i] = 0.0;
-        }
-        (bwd ? &cells[0].bwd[id][0][0] : &cells[0].fwd[id][0][0])[i] = v;
-    }
-}
-
 // conv partial rows -> gradients; BatchNorm gamma / beta gradients from the cells (x bn_scale: under synchronised BatchNorm the
 // cells hold GLOBAL sums on every rank and only one rank may contribute them to the all-reduced gradient)
 // (`fuse.p` != nullptr: the thread that finalises a gradient element applies Adam to that parameter on the spot, and the workgroups from
@@ -1878,17 +1835,8 @@ __global__ __launch_bounds__(FB) void fc_finalize_kernel(FcGeom g, const float* 
 __global__ void fc_bn_batch_kernel(FcGeom g, const Cells* cells, float* __restrict__ bn_batch, float weight) {
     for (int id = 0; id < NBN; ++id)
         for (int c = threadIdx.x; c < g.bn_ch[id]; c += blockDim.x) {
-            const double m = cell_fwd(cells, id, c, 0) / g.cnt[id], q = cell_fwd(cells, id, c, 1) / g.cnt[id];
             float* mean = bn_batch + g.bn_off[id] + c;
-            float* var = mean + g.bn_ch[id];
-            if (weight > 0.f) {
-                *mean = (float)(weight * m);
-                *var = (float)(weight * q);
-            } else {
-                const double v = q - m * m;
-                *mean = (float)m;
-                *var = (float)(v < 0.0 ? 0.0 : v);
-            }
+            bn_batch_out(cell_fwd(cells, id, c, 0), cell_fwd(cells, id, c, 1), g.cnt[id], weight, mean, mean + g.bn_ch[id]);
         }
 }
 
@@ -1896,21 +1844,10 @@ __global__ void fc_bn_batch_kernel(FcGeom g, const Cells* cells, float* __restri
 __global__ void fc_bn_running_kernel(FcGeom g, float* __restrict__ bn, const float* __restrict__ batch, float momentum, int from_moments) {
     for (int id = 0; id < NBN; ++id)
         for (int c = threadIdx.x; c < g.bn_ch[id]; c += blockDim.x) {
-            float mean = batch[g.bn_off[id] + c], var = batch[g.bn_off[id] + g.bn_ch[id] + c];
-            if (from_moments) {
-                var = var - mean * mean;
-                if (var < 0.f) var = 0.f;
-            }
-            const double n = g.cnt[id];
-            const float unbiased = n > 1.0 ? (float)(var * (n / (n - 1.0))) : var;
             float* rm = bn + g.bn_off[id] + c;
-            float* rv = rm + g.bn_ch[id];
-            *rm = (1.0f - momentum) * *rm + momentum * mean;
-            *rv = (1.0f - momentum) * *rv + momentum * unbiased;
+            bn_running_blend(rm, rm + g.bn_ch[id], batch[g.bn_off[id] + c], batch[g.bn_off[id] + g.bn_ch[id] + c], g.cnt[id], momentum, from_moments, 1);
         }
 }
-
-__global__ void fc_fill_one_kernel(float* p) { p[0] = 1.f; }
 
 // the head of the side stream in one launch (it was three): the constant for the bias column sums, the batch statistics for the caller's
 // bucket, and -- when the caller keeps plain (mean, var) there -- the running-statistics update from the same cells
@@ -1919,25 +1856,12 @@ __global__ void fc_side_head_kernel(FcGeom g, const Cells* cells, float* __restr
     if (threadIdx.x == 0) one[0] = 1.f;
     for (int id = 0; id < NBN; ++id)
         for (int c = threadIdx.x; c < g.bn_ch[id]; c += blockDim.x) {
-            const double m = cell_fwd(cells, id, c, 0) / g.cnt[id], q = cell_fwd(cells, id, c, 1) / g.cnt[id];
             float* mean = bn_batch + g.bn_off[id] + c;
             float* var = mean + g.bn_ch[id];
-            if (weight > 0.f) {
-                *mean = (float)(weight * m);
-                *var = (float)(weight * q);
-            } else {
-                const double v = q - m * m;
-                const float mf = (float)m, vf = (float)(v < 0.0 ? 0.0 : v);
-                *mean = mf;
-                *var = vf;
-                if (bn_running) {                                   // (fc_bn_running_kernel's arithmetic on the values just written)
-                    const double n = g.cnt[id];
-                    const float unbiased = n > 1.0 ? (float)(vf * (n / (n - 1.0))) : vf;
-                    float* rm = bn_running + g.bn_off[id] + c;
-                    float* rv = rm + g.bn_ch[id];
-                    *rm = (1.0f - momentum) * *rm + momentum * mf;
-                    *rv = (1.0f - momentum) * *rv + momentum * unbiased;
-                }
+            bn_batch_out(cell_fwd(cells, id, c, 0), cell_fwd(cells, id, c, 1), g.cnt[id], weight, mean, var);
+            if (bn_running && !(weight > 0.f)) {                    // (fc_bn_running_kernel's arithmetic on the values just written)
+                float* rm = bn_running + g.bn_off[id] + c;
+                bn_running_blend(rm, rm + g.bn_ch[id], *mean, *var, g.cnt[id], momentum, 0, 1);
             }
         }
 }
@@ -2040,7 +1964,7 @@ size_t fcstgnn_workspace_bytes(const rulgnn_fcstgnn_shape* s) {
 }
 
 // mode bit 0: forward (args->training selects batch / running statistics), bit 1: backward
-int fcstgnn_run(const rulgnn_fcstgnn_shape* s, const rulgnn_fcstgnn_args* a, int mode, hipStream_t st, const FcstgnnSync* sync, float* bn_running_out,
+int fcstgnn_run(const rulgnn_fcstgnn_shape* s, const rulgnn_fcstgnn_args* a, int mode, hipStream_t st, const SyncHook* sync, float* bn_running_out,
                 float bn_momentum, const AdamFuse* fuse) {
     FcGeom g;
     RULGNN_TRY(fc_geometry(s, &g));
@@ -2089,12 +2013,11 @@ int fcstgnn_run(const rulgnn_fcstgnn_shape* s, const rulgnn_fcstgnn_args* a, int
     const uint32_t* key_dev = a->step_state ? static_cast<const StepState*>(a->step_state)->drop_key : nullptr;
     const int64_t row_off = a->sample_offset * g.NP * g.N;
     (void)hipGetLastError();
+    // reduction pair `id` (forward or backward) is complete behind the launch just enqueued: 2 MAXC contiguous doubles of every replica
+    constexpr int PAIR = 2 * MAXC, FWD0 = offsetof(Cells, fwd) / sizeof(double), BWD0 = offsetof(Cells, bwd) / sizeof(double);
+    static_assert(FWD0 == 0 && BWD0 == NBN * PAIR && CELLS_STRIDE == 2 * NBN * PAIR, "Cells: fwd[NBN] then bwd[NBN] pairs of doubles");
     auto sync_pair = [&](int bwd, int id) -> int {
-        if (!sync) return RULGNN_OK;
-        hipLaunchKernelGGL(fc_cells_collapse_kernel, dim3(1), dim3(128), 0, st, cells, bwd, id);
-        if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
-        double* buf = bwd ? &cells[0].bwd[id][0][0] : &cells[0].fwd[id][0][0];
-        return sync->fn(sync->user, buf, 2 * MAXC, st) == 0 ? RULGNN_OK : RULGNN_ECALLBACK;
+        return sync_cells(sync, reinterpret_cast<double*>(cells), (bwd ? BWD0 : FWD0) + id * PAIR, PAIR, CELLS_STRIDE, st);
     };
 
     if (mode & 1) {
@@ -2212,7 +2135,7 @@ int fcstgnn_run(const rulgnn_fcstgnn_shape* s, const rulgnn_fcstgnn_args* a, int
             hipLaunchKernelGGL(fc_side_head_kernel, dim3(1), dim3(64), 0, wst, g, (const Cells*)cells, one, a->bn_batch, a->bn_moment_weight,
                                (bn_running_out && a->bn_moment_weight == 0.f) ? bn_running_out : (float*)nullptr, bn_momentum);
         else
-            hipLaunchKernelGGL(fc_fill_one_kernel, dim3(1), dim3(1), 0, wst, one);
+            RULGNN_TRY(fill_f32(one, 1, 1.f, wst));
         // (batches of the reference protocol's size: every MLP parameter gradient and the loss sum in one launch, fc_mlp_wgrad_kernel)
         const bool mlp_wgrad_fused = mlp_fused && g.B <= FC_MLPW_MAXB && D2 <= 64;
         if (!a->dpred && a->loss && !mlp_wgrad_fused) (void)block_sum((const float*)P_(w.sqerr), (int64_t)g.B, a->loss, wst);

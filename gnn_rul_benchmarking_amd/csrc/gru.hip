@@ -101,11 +101,6 @@ __global__ __launch_bounds__(256) void gru_rows_copy_kernel(GruGeom g, int t, co
     if (to_rows) dst[row * g.H3 + q] = src[e]; else dst[e] = src[row * g.H3 + q];
 }
 
-__global__ void gru_fill_kernel(float* p, int64_t n, float v) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e < n) p[e] = v;
-}
-
 struct GruWs {
     size_t gi, gh, hprev, ghstep, dgi, dgh, dh, dgstep, one, split, total;
 };
@@ -189,8 +184,7 @@ int gru_backward(const rulgnn_gru_shape* s, const rulgnn_gru_args* a, hipStream_
             RULGNN_TRY(sgemm(Fp(w.dgstep), g.H3, 1, a->w_hh, 1, g.H, Fp(w.dh), g.H, (int)g.S, g.H, g.H3, true, st));
         }
     }
-    hipLaunchKernelGGL(gru_fill_kernel, dim3(blocks(g.R)), dim3(256), 0, st, Fp(w.one), g.R, 1.0f);
-    if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
+    RULGNN_TRY(fill_f32(Fp(w.one), g.R, 1.0f, st));
     float* split = Fp(w.split);
     // dW_ih[q][i] = sum_row dgi[row][q] x[row][i];  dW_hh[q][j] = sum_row dgh[row][q] hprev[row][j];  biases: column sums
     RULGNN_TRY(sgemm_splitk(Fp(w.dgi), 1, g.H3, a->x, 1, g.I, a->dw_ih, g.I, g.H3, g.I, (int)g.R, false, split, st));

@@ -197,11 +197,6 @@ __global__ __launch_bounds__(GS_BLOCK) void gru_seq_bwd_kernel(GsGeom g, const f
     }
 }
 
-__global__ void gru_seq_fill_kernel(float* p, int64_t n, float v) {
-    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (e < n) p[e] = v;
-}
-
 struct GsWs {
     size_t gi, gh, hprev, dgi, dgh, one, split, split_floats, total;
 };
@@ -276,8 +271,7 @@ int gru_persistent_backward(const rulgnn_gru_shape* s, const rulgnn_gru_args* a,
     (void)hipGetLastError();
     hipLaunchKernelGGL(gru_seq_bwd_kernel, dim3(gs_tiles(g)), dim3(GS_BLOCK), 0, st, g, (const float*)Fp(w.gi), (const float*)Fp(w.gh),
                        (const float*)Fp(w.hprev), a->w_hh, a->b_ih, a->b_hh, a->dout, Fp(w.dgi), Fp(w.dgh));
-    hipLaunchKernelGGL(gru_seq_fill_kernel, dim3((unsigned)((g.R + 255) / 256)), dim3(256), 0, st, Fp(w.one), g.R, 1.0f);
-    if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
+    RULGNN_TRY(fill_f32(Fp(w.one), g.R, 1.0f, st));
     // dW_ih[q][i] = sum_row dgi[row][q] x[row][i];  dW_hh[q][j] = sum_row dgh[row][q] hprev[row][j];  biases: column sums
     SplitKJob jobs[4];
     gs_jobs(g, jobs);

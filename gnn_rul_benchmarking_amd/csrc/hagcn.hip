@@ -508,8 +508,6 @@ __global__ __launch_bounds__(HB) void hg_backward_kernel(HgGeom g, const float* 
 
 constexpr size_t HG_BWD_LDS = sizeof(float) * (10 * MAXN * TS + MAXF * TS + 3 * MAXN * AS + 2 * MAXN + HB);
 
-__global__ void hg_fill_one_kernel(float* p) { p[0] = 1.f; }
-
 }  // namespace
 
 int64_t hagcn_graph_param_count(const rulgnn_hagcn_shape* s) {
@@ -547,7 +545,7 @@ int hagcn_graph_backward(const rulgnn_hagcn_shape* s, const rulgnn_hagcn_args* a
                        a->dfeats, a->dkl, a->dnodes);
     float* one = ws + g.t_one;
     float* split = ws + g.t_split;
-    hipLaunchKernelGGL(hg_fill_one_kernel, dim3(1), dim3(1), 0, st, one);
+    RULGNN_TRY(fill_f32(one, 1, 1.f, st));
     if (g.G > 0) {
         SplitKJob jobs[HG_PGRAD_JOBS];
         const int nj = hg_pgrad_jobs(g, ws, a->grads, jobs);

@@ -2,6 +2,8 @@
 //   adam_step:          torch.optim.Adam as the reference configures it (algorithms/algorithms.py:474-478):
 //                       L2 weight decay folded into the gradient, bias-corrected, no amsgrad.
 //   bn_running_update:  nn.BatchNorm1d running statistics (momentum 0.1, unbiased running variance).
+//   sync_cells:         the collapse + all-reduce step of synchronised BatchNorm, for every family (bn_cells.hpp).
+//   fill_f32:           a constant into a few workspace floats (the "one" operand of the bias reductions).
 #include "families_host.hpp"
 #include "adam_device.hpp"
 
@@ -117,6 +119,44 @@ __global__ void step_prepare_adam_kernel(StepState* s, float lr, float beta1, fl
     const double bc2 = 1.0 - pow((double)beta2, (double)step);
     s->lr_over_bc1 = (float)((double)lr / bc1);
     s->inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+}
+
+// One reduction pair (n <= 128 contiguous doubles at `off` of every replica, the replicas `stride` doubles apart) summed into replica 0 in
+// replica_sum()'s order, the other replicas' entries zeroed.  One workgroup, one thread per cell (one wavefront for the 20 / 50 doubles of
+// ST_GCN / ASTGCNN, two for FC_STGNN's 128).
+__global__ __launch_bounds__(128) void cells_collapse_kernel(double* __restrict__ cells, int off, int n, int stride) {
+    const int i = threadIdx.x;
+    if (i >= n) return;
+    double v = 0.0;
+#pragma unroll
+    for (int r = 0; r < CELL_REP; ++r) {
+        v += cells[r * stride + off + i];
+        if (r) cells[r * stride + off + i] = 0.0;
+    }
+    cells[off + i] = v;
+}
+
+// (No clearing of the HIP error in front of the launch: a driver that does not check its every launch learns of an earlier failed one
+// here, as RULGNN_EHIP, instead of handing cells nobody wrote to the caller's all-reduce.)
+int sync_cells(const SyncHook* h, double* cells, int off, int n, int replica_stride, hipStream_t st) {
+    if (!h) return RULGNN_OK;
+    if (n < 1 || n > 128) return RULGNN_EINVAL;
+    hipLaunchKernelGGL(cells_collapse_kernel, dim3(1), dim3(n <= 64 ? 64 : 128), 0, st, cells, off, n, replica_stride);
+    if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
+    return h->fn(h->user, cells + off, n, st) == 0 ? RULGNN_OK : RULGNN_ECALLBACK;
+}
+
+__global__ void fill_f32_kernel(float* __restrict__ p, int64_t n, float v) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) p[i] = v;
+}
+
+int fill_f32(float* p, int64_t n, float v, hipStream_t st) {
+    if (n > 0) {
+        const int block = n < 256 ? 64 : 256;
+        const int64_t grid = (n + block - 1) / block;
+        hipLaunchKernelGGL(fill_f32_kernel, dim3((unsigned)(grid > 1024 ? 1024 : grid)), dim3(block), 0, st, p, n, v);
+    }
+    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
 }
 
 int step_state_set(void* state, uint64_t dropout_step, int64_t adam_step, hipStream_t stream) {

@@ -220,16 +220,27 @@ int rulgnn_stgcn_train_fwdbwd_ready_f32(const rulgnn_stgcn_shape* shape, const r
     return stgcn_train_fwdbwd(shape, args, static_cast<hipStream_t>(stream));     // buckets of a few KB: nothing to overlap
 }
 
+// What every synchronised-BatchNorm entry refuses in its own arguments: a share of the BatchNorm parameter gradients outside [0, 1], no
+// all-reduce, averaged moments (the cells hold the global batch's sums already).  (ASTGCNN and FC_STGNN leave the moment weight to their
+// drivers, which refuse it behind their geometry check.)
+static int check_sync(float bn_param_grad_scale, rulgnn_allreduce_f64_fn allreduce, float bn_moment_weight = 0.f) {
+    if (!(bn_param_grad_scale >= 0.f && bn_param_grad_scale <= 1.f) || !allreduce || bn_moment_weight != 0.f) return RULGNN_EINVAL;
+    return RULGNN_OK;
+}
+
+// the ST_GCN step under `sync` on the launch form the shape takes
+static int stgcn_sync_step(const rulgnn_stgcn_shape* shape, const rulgnn_stgcn_train_args* args, const SyncHook& sync, const GradReadyHook* ready,
+                           int path, void* stream) {
+    if (tiled(shape)) return stgcn_tiled_train(shape, args, 2, static_cast<hipStream_t>(stream), ready, &sync);
+    return stgcn_train_fwdbwd_syncbn(shape, args, &sync, static_cast<hipStream_t>(stream), path);
+}
+
 int rulgnn_stgcn_train_fwdbwd_syncbn_f32(const rulgnn_stgcn_shape* shape, const rulgnn_stgcn_train_args* args,
                                          float bn_param_grad_scale, rulgnn_allreduce_f64_fn allreduce, void* user, void* stream) {
     const int rc = check_train(shape, args, true);
     if (rc != RULGNN_OK) return rc;
-    if (!(bn_param_grad_scale >= 0.f && bn_param_grad_scale <= 1.f) || !allreduce || args->bn_moment_weight != 0.f) return RULGNN_EINVAL;
-    if (tiled(shape)) {
-        const SyncHook sync = {bn_param_grad_scale, allreduce, user};
-        return stgcn_tiled_train(shape, args, 2, static_cast<hipStream_t>(stream), nullptr, &sync);
-    }
-    return stgcn_train_fwdbwd_syncbn(shape, args, bn_param_grad_scale, allreduce, user, static_cast<hipStream_t>(stream), RULGNN_STEP_CHAIN);
+    RULGNN_TRY(check_sync(bn_param_grad_scale, allreduce, args->bn_moment_weight));
+    return stgcn_sync_step(shape, args, {allreduce, user, bn_param_grad_scale}, nullptr, RULGNN_STEP_CHAIN, stream);
 }
 
 int rulgnn_stgcn_train_fwdbwd_syncbn_ready_f32(const rulgnn_stgcn_shape* shape, const rulgnn_stgcn_train_args* args,
@@ -237,14 +248,11 @@ int rulgnn_stgcn_train_fwdbwd_syncbn_ready_f32(const rulgnn_stgcn_shape* shape, 
                                                rulgnn_grad_ready_fn ready, void* ready_user, void* stream) {
     const int rc = check_train(shape, args, true);
     if (rc != RULGNN_OK) return rc;
-    if (!(bn_param_grad_scale >= 0.f && bn_param_grad_scale <= 1.f) || !allreduce || !ready || args->bn_moment_weight != 0.f) return RULGNN_EINVAL;
-    if (tiled(shape)) {
-        const SyncHook sync = {bn_param_grad_scale, allreduce, user};
-        const GradReadyHook hook = {ready, ready_user};
-        return stgcn_tiled_train(shape, args, 2, static_cast<hipStream_t>(stream), &hook, &sync);
-    }
-    // (buckets of a few KB: nothing to overlap, no region is reported -- as rulgnn_stgcn_train_fwdbwd_ready_f32 on these shapes)
-    return stgcn_train_fwdbwd_syncbn(shape, args, bn_param_grad_scale, allreduce, user, static_cast<hipStream_t>(stream), RULGNN_STEP_CHAIN);
+    RULGNN_TRY(check_sync(bn_param_grad_scale, allreduce, args->bn_moment_weight));
+    if (!ready) return RULGNN_EINVAL;
+    // (num_patch <= 64, buckets of a few KB: nothing to overlap, no region is reported -- as rulgnn_stgcn_train_fwdbwd_ready_f32 there)
+    const GradReadyHook hook = {ready, ready_user};
+    return stgcn_sync_step(shape, args, {allreduce, user, bn_param_grad_scale}, &hook, RULGNN_STEP_CHAIN, stream);
 }
 
 int rulgnn_stgcn_train_fwdbwd_syncbn_path_f32(const rulgnn_stgcn_shape* shape, const rulgnn_stgcn_train_args* args,
@@ -252,13 +260,10 @@ int rulgnn_stgcn_train_fwdbwd_syncbn_path_f32(const rulgnn_stgcn_shape* shape, c
                                               void* stream) {
     const int rc = check_train(shape, args, true);
     if (rc != RULGNN_OK) return rc;
-    if (!(bn_param_grad_scale >= 0.f && bn_param_grad_scale <= 1.f) || !allreduce || args->bn_moment_weight != 0.f) return RULGNN_EINVAL;
+    RULGNN_TRY(check_sync(bn_param_grad_scale, allreduce, args->bn_moment_weight));
     if (path != RULGNN_STEP_AUTO && path != RULGNN_STEP_CHAIN && path != RULGNN_STEP_MX) return RULGNN_EINVAL;
-    if (tiled(shape)) {                                    // (one launch form there: `path` is ignored, as by rulgnn_stgcn_train_step_path_f32)
-        const SyncHook sync = {bn_param_grad_scale, allreduce, user};
-        return stgcn_tiled_train(shape, args, 2, static_cast<hipStream_t>(stream), nullptr, &sync);
-    }
-    return stgcn_train_fwdbwd_syncbn(shape, args, bn_param_grad_scale, allreduce, user, static_cast<hipStream_t>(stream), path);
+    // (num_patch > 64 has one launch form: `path` is ignored there, as by rulgnn_stgcn_train_step_path_f32)
+    return stgcn_sync_step(shape, args, {allreduce, user, bn_param_grad_scale}, nullptr, path, stream);
 }
 
 int64_t rulgnn_stgcn_train_guard_counter_offset(const rulgnn_stgcn_shape* shape) {
@@ -535,8 +540,9 @@ int rulgnn_astgcnn_fwdbwd_syncbn_f32(const rulgnn_astgcnn_shape* shape, const ru
                                      rulgnn_allreduce_f64_fn allreduce, void* user, void* stream) {
     const int rc = check_astgcnn(shape, args, true, true);
     if (rc != RULGNN_OK) return rc;
-    if (args->dpred || !allreduce || !(bn_param_grad_scale >= 0.f && bn_param_grad_scale <= 1.f)) return RULGNN_EINVAL;
-    const BnSyncHook hook = {allreduce, user, bn_param_grad_scale};
+    if (args->dpred) return RULGNN_EINVAL;
+    RULGNN_TRY(check_sync(bn_param_grad_scale, allreduce));
+    const SyncHook hook = {allreduce, user, bn_param_grad_scale};
     return astgcnn_run(shape, args, 3, static_cast<hipStream_t>(stream), &hook);
 }
 
@@ -635,8 +641,9 @@ int rulgnn_fcstgnn_fwdbwd_syncbn_f32(const rulgnn_fcstgnn_shape* shape, const ru
                                      rulgnn_allreduce_f64_fn allreduce, void* user, void* stream) {
     const int rc = check_fcstgnn(shape, args, true, true);
     if (rc != RULGNN_OK) return rc;
-    if (args->dpred || !allreduce || !(bn_param_grad_scale >= 0.f && bn_param_grad_scale <= 1.f)) return RULGNN_EINVAL;
-    const BnSyncHook hook = {allreduce, user, bn_param_grad_scale};
+    if (args->dpred) return RULGNN_EINVAL;
+    RULGNN_TRY(check_sync(bn_param_grad_scale, allreduce));
+    const SyncHook hook = {allreduce, user, bn_param_grad_scale};
     return fcstgnn_run(shape, args, 3, static_cast<hipStream_t>(stream), &hook);
 }
 

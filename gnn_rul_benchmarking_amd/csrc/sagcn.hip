@@ -604,11 +604,6 @@ __global__ void sg_fcw_kernel(SgGeom g, const float* __restrict__ attn, const fl
     }
 }
 
-__global__ void sg_fill_kernel(float* p, int n, float v) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) p[i] = v;
-}
-
 inline unsigned sg_grid(int64_t n) {
     int64_t b = (n + GB - 1) / GB;
     return (unsigned)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
@@ -714,7 +709,7 @@ int sagcn_run(const rulgnn_sagcn_shape* s, const rulgnn_sagcn_args* a, int mode,
         float* dA = ws + g.w_dA;
         float* dB = ws + g.w_dB;
         float* ds = ws + g.w_ds;
-        hipLaunchKernelGGL(sg_fill_kernel, dim3(1), dim3(64), 0, st, one, 1, 1.0f);
+        RULGNN_TRY(fill_f32(one, 1, 1.0f, st));
         // head + softmax: dA = d h3 (direct path), dB = d logits
         hipLaunchKernelGGL(sg_fcw_kernel, dim3(sg_grid((int64_t)P * H)), dim3(GB), 0, st, g, (const float*)attn, (const float*)hh[2], dpred,
                            gr + g.o_wfc);

@@ -58,39 +58,15 @@ struct Cells3 {                      // the CNN BatchNorm (slot 2 of the BatchNo
     double th[4];
 };
 
-__device__ inline double cell3_fwd(const Cells3* c3, int c, int j) {
-    double v = 0.0;
-    for (int r = 0; r < CELL_REP; ++r) v += c3[r].fwd[c][j];
-    return v;
-}
-__device__ inline double cell3_bwd(const Cells3* c3, int c, int j) {
-    double v = 0.0;
-    for (int r = 0; r < CELL_REP; ++r) v += c3[r].bwd[c][j];
-    return v;
-}
-__device__ inline double cell3_th(const Cells3* c3, int q) {
-    double v = 0.0;
-    for (int r = 0; r < CELL_REP; ++r) v += c3[r].th[q];
-    return v;
-}
+constexpr int C3_STRIDE = sizeof(Cells3) / sizeof(double);
+__device__ inline double cell3_fwd(const Cells3* c3, int c, int j) { return replica_sum(&c3[0].fwd[c][j], C3_STRIDE); }
+__device__ inline double cell3_bwd(const Cells3* c3, int c, int j) { return replica_sum(&c3[0].bwd[c][j], C3_STRIDE); }
+__device__ inline double cell3_th(const Cells3* c3, int q) { return replica_sum(&c3[0].th[q], C3_STRIDE); }
 __device__ inline BnCoef bnc_coef(const Cells3* c3, const float* bn_running, int training, int c, int N, double count, float gamma,
                                   float beta) {
-    BnCoef r;
-    float var;
-    if (training) {
-        const double m = cell3_fwd(c3, c, 0) / count;
-        double v = cell3_fwd(c3, c, 1) / count - m * m;
-        if (v < 0.0) v = 0.0;
-        r.mean = (float)m;
-        var = (float)v;
-    } else {
-        r.mean = bn_running[(2 * 2 + 0) * N + c];
-        var = bn_running[(2 * 2 + 1) * N + c];
-    }
-    r.inv = 1.0f / sqrtf(var + tcn::BN_EPS);
-    r.sc = gamma * r.inv;
-    r.sh = beta - r.mean * r.sc;
-    return r;
+    const BnMoments s = training ? bn_moments(cell3_fwd(c3, c, 0), cell3_fwd(c3, c, 1), count)
+                                 : BnMoments{bn_running[(2 * 2 + 0) * N + c], bn_running[(2 * 2 + 1) * N + c]};
+    return bn_coef(s, gamma, beta, tcn::BN_EPS);
 }
 
 // Pearson adjacency between the nodes' windows and the aggregate A X   (Model.py:10-28, :47)
@@ -382,17 +358,8 @@ __global__ void sc_bn_batch_kernel(ScGeom g, const Cells* cells, const Cells3* c
     const int e = threadIdx.x;
     if (e >= 3 * g.N) return;
     const int blk = e / g.N, c = e % g.N;
-    const double count = (double)g.BG * g.T;
     const double s = blk < 2 ? cell_sum(cells, &Cells::fwd, blk, c, 0) : cell3_fwd(c3, c, 0), q2 = blk < 2 ? cell_sum(cells, &Cells::fwd, blk, c, 1) : cell3_fwd(c3, c, 1);
-    const double m = s / count, q = q2 / count;
-    if (weight > 0.f) {
-        bn_batch[(blk * 2 + 0) * g.N + c] = (float)(weight * m);
-        bn_batch[(blk * 2 + 1) * g.N + c] = (float)(weight * q);
-    } else {
-        const double v = q - m * m;
-        bn_batch[(blk * 2 + 0) * g.N + c] = (float)m;
-        bn_batch[(blk * 2 + 1) * g.N + c] = (float)(v < 0.0 ? 0.0 : v);
-    }
+    bn_batch_out(s, q2, (double)g.BG * g.T, weight, bn_batch + (blk * 2 + 0) * g.N + c, bn_batch + (blk * 2 + 1) * g.N + c);
 }
 
 // every BatchNorm module runs twice per training forward in the reference (Model.py:196-206): the momentum update twice
@@ -401,22 +368,9 @@ __global__ void sc_bn_running_kernel(float* __restrict__ bn, const float* __rest
     const int e = threadIdx.x;
     if (e >= 3 * N) return;
     const int blk = e / N, c = e % N;
-    float mean = batch[(blk * 2 + 0) * N + c], var = batch[(blk * 2 + 1) * N + c];
-    if (from_moments) {
-        var = var - mean * mean;
-        if (var < 0.f) var = 0.f;
-    }
-    const float unbiased = count > 1.0 ? (float)(var * (count / (count - 1.0))) : var;
-    float rm = bn[(blk * 2 + 0) * N + c], rv = bn[(blk * 2 + 1) * N + c];
-    for (int k = 0; k < 2; ++k) {
-        rm = (1.0f - momentum) * rm + momentum * mean;
-        rv = (1.0f - momentum) * rv + momentum * unbiased;
-    }
-    bn[(blk * 2 + 0) * N + c] = rm;
-    bn[(blk * 2 + 1) * N + c] = rv;
+    bn_running_blend(bn + (blk * 2 + 0) * N + c, bn + (blk * 2 + 1) * N + c, batch[(blk * 2 + 0) * N + c], batch[(blk * 2 + 1) * N + c], count, momentum,
+                     from_moments, 2);
 }
-
-__global__ void sc_fill_one_kernel(float* p) { p[0] = 1.f; }
 
 struct ScWs {
     size_t cells, c3, one, ax, gpre, zc, z1, out0, z2, res, dpred, sqerr, ds1, dy2, dyc, dy1, gp1, gp2, gp3, split, total;
@@ -499,7 +453,7 @@ int stconv_run(const rulgnn_stconv_shape* s, const rulgnn_astgcnn_args* a, int m
         float* gr = a->grads;
         float* split = F(w.split);
         float* one = F(w.one);
-        hipLaunchKernelGGL(sc_fill_one_kernel, dim3(1), dim3(1), 0, st, one);
+        RULGNN_TRY(fill_f32(one, 1, 1.f, st));
         if (a->dpred && hipMemcpyAsync(F(w.dpred), a->dpred, sizeof(float) * g.B, hipMemcpyDeviceToDevice, st) != hipSuccess)
             return RULGNN_EHIP;
         // fc: d weight = dpred^T res ; d bias = sum dpred

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/rulgnn.h"
+#include "bn_cells.hpp"
 #include "host_util.hpp"
 #include "stgcn_device.hpp"
 
@@ -115,15 +116,7 @@ struct GradReadyHook {
     rulgnn_grad_ready_fn fn;
     void* user;
 };
-// Synchronised BatchNorm hook of the ST_GCN steps (include/rulgnn.h: rulgnn_stgcn_train_fwdbwd_syncbn_f32): after every launch that
-// completes a reduction pair its replicas are collapsed into replica 0 (the others zeroed, so that the consumers' replica sum is
-// unchanged) and the caller's all-reduce runs on those 2 F contiguous doubles.
-struct SyncHook {
-    float bn_param_grad_scale;
-    rulgnn_allreduce_f64_fn fn;
-    void* user;
-};
-// (`sync` != nullptr: whole steps only, mode 2)
+// (`sync` != nullptr, synchronised BatchNorm -- SyncHook, bn_cells.hpp: whole steps only, mode 2; the reduction pairs are 2 F doubles)
 int stgcn_tiled_train(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args* a, int mode, hipStream_t stream,
                       const GradReadyHook* ready = nullptr, const SyncHook* sync = nullptr);
 size_t stgcn_train_workspace_bytes(const rulgnn_stgcn_shape* s);
@@ -141,8 +134,8 @@ int stgcn_train_step(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args*
                      hipStream_t stream, int path = RULGNN_STEP_AUTO);     // opt == nullptr: forward + backward only
 int stgcn_train_phase(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args* a, int phase, hipStream_t stream,
                       int path = RULGNN_STEP_AUTO);
-int stgcn_train_fwdbwd_syncbn(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args* a, float bn_param_grad_scale,
-                              rulgnn_allreduce_f64_fn allreduce, void* user, hipStream_t stream, int path = RULGNN_STEP_CHAIN);
+int stgcn_train_fwdbwd_syncbn(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args* a, const SyncHook* hook, hipStream_t stream,
+                              int path = RULGNN_STEP_CHAIN);
 int stgcn_train_mx_kind(const rulgnn_stgcn_shape* s, const float* x);        // 0 fp32 phases, 1 matrix-core chain, 2 wide matrix-core chain
 int64_t stgcn_train_guard_counter_offset(const rulgnn_stgcn_shape* s);
 

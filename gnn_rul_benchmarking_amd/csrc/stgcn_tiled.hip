@@ -634,23 +634,6 @@ __device__ __forceinline__ void t_pair_reduce(const float (&sa)[F], const float 
     }
 }
 
-// Synchronised BatchNorm: the T_REP replicas of one reduction pair (2 F contiguous doubles at `off` of every replica, the
-// replicas `stride` doubles apart: tc_sf(L) for a forward pair, tc_sb(L) for a backward one) summed into replica 0 in tc_sum()'s order,
-// the other replicas' entries zeroed -- every consumer's tc_sum() then returns what it returned before, and after the caller's
-// all-reduce on replica 0's 2 F doubles the GLOBAL sum.  One workgroup: 20 threads with 16 dependent loads each (see
-// profiles/r10_syncbn_tiled.md for what the 4 L launches cost).
-__global__ __launch_bounds__(64) void t_cells_collapse_kernel(double* __restrict__ cells, int off, int stride) {
-    const int i = threadIdx.x;
-    if (i >= 2 * F) return;
-    double v = 0.0;
-#pragma unroll
-    for (int r = 0; r < T_REP; ++r) {
-        v += cells[r * stride + off + i];
-        if (r) cells[r * stride + off + i] = 0.0;
-    }
-    cells[off + i] = v;
-}
-
 // The kernels with a reduction behind them (BatchNorm sums, convolution weight-gradient partials) are PERSISTENT: at most T_PGRID
 // workgroups (four per CU, what the weight-gradient kernels' LDS tiles allow), each walking chunks of 256 positions with its sums in
 // registers, so that the BatchNorm constants (a chain of fp64 divisions and a square root over 16 cell replicas) and the block
@@ -1394,12 +1377,12 @@ int stgcn_tiled_train(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args
     t.cells_fwd = cells; t.cells_bwd = cells + T_REP * tc_sf(L);
     // synchronised BatchNorm: reduction pair `bn_index` (forward or backward) is complete behind the launch just enqueued -- collapse its
     // replicas and hand replica 0's 2 F doubles to the caller's all-reduce, in `stream` order, before the next launch reads the pair
+    // (sync_cells, families_host.hpp: the replicas are `stride` doubles apart -- tc_sf(L) for a forward pair, tc_sb(L) for a backward one --
+    // and summed in tc_sum()'s order, so every consumer's tc_sum() returns what it returned before, and behind the all-reduce the GLOBAL
+    // sum; profiles/r10_syncbn_tiled.md has what the 4 L launches cost)
+    static_assert(T_REP == CELL_REP, "sync_cells collapses CELL_REP replicas");
     auto sync_pair = [&](double* base, int stride, int bn_index) -> int {
-        if (!sync) return RULGNN_OK;
-        (void)hipGetLastError();
-        hipLaunchKernelGGL(t_cells_collapse_kernel, dim3(1), dim3(64), 0, stream, base, bn_index * 2 * F, stride);
-        if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
-        return sync->fn(sync->user, base + bn_index * 2 * F, 2 * F, stream) == 0 ? RULGNN_OK : RULGNN_ECALLBACK;
+        return sync_cells(sync, base, bn_index * 2 * F, 2 * F, stride, stream);
     };
     const int has_dpred = ar->dpred ? 1 : (ar->y ? 0 : 2);
     const float* gy = ar->dpred ? ar->dpred : ar->y;

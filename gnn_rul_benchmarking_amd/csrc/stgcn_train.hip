@@ -27,6 +27,7 @@
 //       LDS transpose ([channel][lane] tile, ds_read_b128 fragments).
 // Accumulators stay in the MFMA accumulator registers across the whole persistent tile loop.
 #include "stgcn_device.hpp"
+#include "families_host.hpp"
 #include "stgcn_host.hpp"
 #include "stgcn_train_layout.hpp"
 #include "stgcn_train_mx.hpp"
@@ -1257,26 +1258,12 @@ enum TrainMode { TM_FORWARD = 0, TM_BACKWARD = 1, TM_FWDBWD = 2 };
 // Synchronised BatchNorm ("per-BN all-reduce of [sum x, sum x^2, count] in forward and the matching [sum dy, sum dy xhat]
 // in backward"): after every phase that completes a reduction pair its 16 replicas are collapsed into replica 0 (the others
 // zeroed, so that the consumers' replica sum is unchanged) and the caller's all-reduce runs on those 2 F contiguous doubles
-// (SyncHook: stgcn_host.hpp, shared with the tiled path).
-
-__global__ void stgcn_cells_collapse_kernel(double* cells, int off, int n, int stride) {
-    const int i = threadIdx.x;
-    if (i >= n) return;
-    double v = 0.0;
-    for (int r = 0; r < CELL_REPLICAS; ++r) {          // same fixed order as cell_sum()
-        v += cells[r * stride + off + i];
-        if (r) cells[r * stride + off + i] = 0.0;
-    }
-    cells[off + i] = v;
-}
+// (sync_cells: families_host.hpp, the step every family shares; cell_sum()'s fixed order is replica_sum()'s).
+static_assert(CELL_REPLICAS == CELL_REP, "sync_cells collapses CELL_REP replicas");
 
 template <int L>
 static int sync_pair(const TrainK& k, int off, const SyncHook* h, hipStream_t st) {
-    if (!h) return RULGNN_OK;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(stgcn_cells_collapse_kernel, dim3(1), dim3(64), 0, st, k.cells, off, 2 * F, cell_stride(L));
-    if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
-    return h->fn(h->user, k.cells + off, 2 * F, st) == 0 ? RULGNN_OK : RULGNN_ECALLBACK;
+    return sync_cells(h, k.cells, off, 2 * F, cell_stride(L), st);
 }
 
 template <int RW, int L, int I>
@@ -1781,10 +1768,8 @@ int stgcn_train_fwdbwd(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_arg
     // (rulgnn_stgcn_train_step_path_f32 with an explicit path is that caller's entry).
     return dispatch_train(s, a, TM_FWDBWD, st, nullptr, nullptr, RULGNN_STEP_CHAIN);
 }
-int stgcn_train_fwdbwd_syncbn(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args* a, float bn_param_grad_scale,
-                              rulgnn_allreduce_f64_fn allreduce, void* user, hipStream_t st, int path) {
-    const SyncHook hook{bn_param_grad_scale, allreduce, user};
-    return dispatch_train(s, a, TM_FWDBWD, st, nullptr, &hook, path);
+int stgcn_train_fwdbwd_syncbn(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args* a, const SyncHook* hook, hipStream_t st, int path) {
+    return dispatch_train(s, a, TM_FWDBWD, st, nullptr, hook, path);
 }
 
 // Which matrix-core chain a whole MSE step of this shape runs on: 0 none (fp32 phases), 1 the 4-sample-tile chain (num_patch <= 15,

@@ -240,10 +240,6 @@ __global__ __launch_bounds__(GB) void stgnn_dflat_kernel(GnGeom g, const float* 
     for (int64_t e = (int64_t)blockIdx.x * GB + threadIdx.x; e < total; e += (int64_t)gridDim.x * GB) dflat[e] = dpred[e / Q] * fcw[e % Q];
 }
 
-__global__ void stgnn_fill_kernel(float* p, int n, float v) {
-    if ((int)threadIdx.x < n) p[threadIdx.x] = v;
-}
-
 struct GnWs {
     size_t terms, cheb, seq, hs, dhs, dseq, dcheb, dpred, sqerr, one, gru, split, total;
     size_t gru_bytes;
@@ -336,7 +332,7 @@ int stgnn_run(const rulgnn_stgnn_shape* s, const rulgnn_stmsgcn_args* a, int mod
         const float* dpred = a->dpred ? a->dpred : Fp(w.dpred);
         float* gr = a->grads;
         float* split = Fp(w.split);
-        hipLaunchKernelGGL(stgnn_fill_kernel, dim3(1), dim3(64), 0, st, Fp(w.one), 64, 1.0f);
+        RULGNN_TRY(fill_f32(Fp(w.one), 64, 1.0f, st));
         // fc: d w[q] = sum_b dpred[b] flat[b][q], d b = sum_b dpred[b], d flat = dpred (x) w
         RULGNN_TRY(sgemm_splitk(dpred, 0, 1, Fp(w.hs), 1, Q, gr + o.fcw, Q, 1, Q, (int)g.B, false, split, st));
         RULGNN_TRY(sgemm_splitk(dpred, 0, 1, Fp(w.one), 0, 0, gr + o.fcb, 1, 1, 1, (int)g.B, false, split, st));

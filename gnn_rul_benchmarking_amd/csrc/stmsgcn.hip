@@ -1561,10 +1561,6 @@ __global__ __launch_bounds__(MB) void msg_finalize_kernel(MsgGeom g, const float
     if (lane == 0) grads[e] = a;
 }
 
-__global__ void msg_fill_kernel(float* p, int n, float v) {
-    if ((int)threadIdx.x < n) p[threadIdx.x] = v;
-}
-
 struct MsgWs {
     size_t cat, gi, hseq, dgi, dcat, one, split, pooled, dpred, sqerr, hpart, gpart_gcn, gpart_gru, gpart_gi, total;
     int rows_gcn_max, rows_gru, HG;
@@ -1718,7 +1714,7 @@ int stmsgcn_run(const rulgnn_stmsgcn_shape* s, const rulgnn_stmsgcn_args* a, int
                 const float* wih = a->params + g.off_wih;
                 float* one = ws.at<float>(w.one);
                 float* split = ws.at<float>(w.split);
-                hipLaunchKernelGGL(msg_fill_kernel, dim3(1), dim3(64), 0, st, one, 64, 1.0f);
+                RULGNN_TRY(fill_f32(one, 64, 1.0f, st));
                 RULGNN_TRY(sgemm(dgi, g.H3, 1, wih, 1, g.C, ws.at<float>(w.dcat), g.C, (int)R, g.C, g.H3, false, st));
                 RULGNN_TRY(sgemm_splitk(dgi, 1, g.H3, ws.at<float>(w.cat), 1, g.C, a->grads + g.off_wih, g.C, g.H3, g.C, (int)R, false, split, st));
                 RULGNN_TRY(sgemm_splitk(dgi, 1, g.H3, one, 0, 0, a->grads + g.off_bih, 1, g.H3, 1, (int)R, false, split, st));

@@ -290,11 +290,6 @@ __global__ void sn_loss_kernel(const float* __restrict__ a, const float* __restr
     if (threadIdx.x == 0 && blockIdx.x == 0) loss[0] = a[0] + b[0];
 }
 
-__global__ void sn_fill_kernel(float* p, int n, float v) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) p[i] = v;
-}
-
 inline unsigned sn_grid(int64_t n) {
     int64_t b = (n + SB - 1) / SB;
     return (unsigned)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
@@ -367,7 +362,7 @@ int stnet_run(const rulgnn_stnet_shape* s, const rulgnn_stnet_args* a, int mode,
     if (mode & 1) {
         const size_t lds = sizeof(float) * ((size_t)g.P + g.nseg + 3 * (size_t)g.nseg + (size_t)g.N * g.f);
         if (lds > 48 * 1024) return RULGNN_EUNSUPPORTED;
-        hipLaunchKernelGGL(sn_fill_kernel, dim3(1), dim3(64), 0, st, ws + g.w_one + 3, 1, 0.0f);
+        RULGNN_TRY(fill_f32(ws + g.w_one + 3, 1, 0.0f, st));
         hipLaunchKernelGGL(sn_stft_kernel, dim3(ggrid), dim3(SB), lds, st, g, a->x, prm, ws);
         SN_LAUNCH_OK();
         const float* cur = ws + g.w_mag;
@@ -413,8 +408,8 @@ int stnet_run(const rulgnn_stnet_shape* s, const rulgnn_stnet_args* a, int mode,
         float* gr = a->grads;
         const float* dpred = a->dpred ? a->dpred : ws + g.w_dpred;
         float* one = ws + g.w_one;
-        hipLaunchKernelGGL(sn_fill_kernel, dim3(1), dim3(64), 0, st, one, 1, 1.0f);
-        hipLaunchKernelGGL(sn_fill_kernel, dim3(1), dim3(64), 0, st, gr + g.o_cw, 3, 0.0f);          // the 1x1 convolution has no gradient
+        RULGNN_TRY(fill_f32(one, 1, 1.0f, st));
+        RULGNN_TRY(fill_f32(gr + g.o_cw, 3, 0.0f, st));          // the 1x1 convolution has no gradient
         // head
         RULGNN_TRY(sgemm_splitk(dpred, 0, 1, ws + g.w_hseq, 1, E * g.T, gr + g.o_lw, E * g.T, 1, E * g.T, (int)g.B, false, split, st));
         RULGNN_TRY(sgemm_splitk(dpred, 0, 1, one, 0, 0, gr + g.o_lb, 1, 1, 1, (int)g.B, false, split, st));

@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "bn_cells.hpp"
+
 namespace rulgnn {
 namespace tcn {
 
@@ -29,39 +31,17 @@ struct Cells {
     double bwd[2][MAXN][2];
 };
 
-// Every workgroup adds its partial sums with one atomic per channel; with one workgroup per sample thousands of them hit
-// the same addresses and serialise (~10 ns each), so the cells exist CELL_REP times: workgroup b adds into replica
-// b % CELL_REP, the readers sum the replicas in a fixed order.
-constexpr int CELL_REP = 16;
+// one cell over its CELL_REP replicas (bn_cells.hpp)
 __device__ inline double cell_sum(const Cells* cells, double (Cells::*field)[2][MAXN][2], int blk, int c, int j) {
-    double v = 0.0;
-#pragma unroll
-    for (int r = 0; r < CELL_REP; ++r) v += (cells[r].*field)[blk][c][j];
-    return v;
+    return replica_sum(&(cells[0].*field)[blk][c][j], sizeof(Cells) / sizeof(double));
 }
 
-// BatchNorm scale/shift of block `blk` for channel c: y = z * sc + sh; xhat = (z - mean) * inv
-struct BnCoef {
-    float mean, inv, sc, sh;
-};
+// BatchNorm scale/shift of block `blk` for channel c
 __device__ inline BnCoef bn_coef(const Cells* cells, const float* bn_running, int training, int blk, int c, int N, double count,
                                  float gamma, float beta) {
-    BnCoef r;
-    float var;
-    if (training) {
-        const double m = cell_sum(cells, &Cells::fwd, blk, c, 0) / count;
-        double v = cell_sum(cells, &Cells::fwd, blk, c, 1) / count - m * m;
-        if (v < 0.0) v = 0.0;
-        r.mean = (float)m;
-        var = (float)v;
-    } else {
-        r.mean = bn_running[(blk * 2 + 0) * N + c];
-        var = bn_running[(blk * 2 + 1) * N + c];
-    }
-    r.inv = 1.0f / sqrtf(var + BN_EPS);
-    r.sc = gamma * r.inv;
-    r.sh = beta - r.mean * r.sc;
-    return r;
+    const BnMoments s = training ? bn_moments(cell_sum(cells, &Cells::fwd, blk, c, 0), cell_sum(cells, &Cells::fwd, blk, c, 1), count)
+                                 : BnMoments{bn_running[(blk * 2 + 0) * N + c], bn_running[(blk * 2 + 1) * N + c]};
+    return rulgnn::bn_coef(s, gamma, beta, BN_EPS);
 }
 
 // ---------------------------------------------------------------------------------------------------
