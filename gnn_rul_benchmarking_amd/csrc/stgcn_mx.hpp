@@ -85,26 +85,31 @@ __device__ __forceinline__ float relu2(float v) { return __builtin_fabsf(v) + v;
 // Inline asm on purpose: the builtin form is counted by the compiler, which then puts s_waitcnt vmcnt(0) in front of EVERY later LDS
 // read (it cannot tell the two buffers apart) -- the prefetch would be waited for at once.  M0 carries the LDS base and is
 // compiler-reserved: saved and restored inside the statement.
+// `NT`: the request of a record's LAST reader in the step -- the line is marked for early replacement in L2 / Infinity Cache.
+template <int OFFSET, bool NT>
+__device__ __forceinline__ void dma_piece(const float* src) {           // 1 KB at the instruction's immediate offset; M0 = the LDS base
+    if constexpr (NT) asm volatile("global_load_lds_dwordx4 %0, off offset:%1 nt" :: "v"(src), "n"(OFFSET) : "memory");
+    else asm volatile("global_load_lds_dwordx4 %0, off offset:%1" :: "v"(src), "n"(OFFSET) : "memory");
+}
+template <bool NT = false>
 __device__ __forceinline__ void dma_tile(const float* __restrict__ g, float* lds_dst, int bytes, int lane) {
     const unsigned base = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds_dst);    // LDS byte address, wave-uniform
     for (int off = 0; off < bytes; off += 1024) {
         if (off + lane * 16 < bytes) {
             const float* src = g + (off >> 2) + lane * 4;
             unsigned keep;
-            asm volatile("s_mov_b32 %0, m0\n\t"
-                         "s_mov_b32 m0, %2\n\t"
-                         "s_nop 0\n\t"
-                         "global_load_lds_dwordx4 %1, off\n\t"
-                         "s_mov_b32 m0, %0"
-                         : "=&s"(keep)
-                         : "v"(src), "s"(base + (unsigned)off)
-                         : "memory");
+            if constexpr (NT)
+                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off nt\n\ts_mov_b32 m0, %0"
+                             : "=&s"(keep) : "v"(src), "s"(base + (unsigned)off) : "memory");
+            else
+                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                             : "=&s"(keep) : "v"(src), "s"(base + (unsigned)off) : "memory");
         }
     }
 }
 // The same copy for a byte count known at compile time: M0 is written once per 4 KB (the instruction's immediate offset advances the
 // global AND the LDS address), so the pieces go out back to back instead of one M0 round trip each.
-template <int BYTES>
+template <int BYTES, bool NT = false>
 __device__ __forceinline__ void dma_tile_fixed(const float* __restrict__ g, float* lds_dst, int lane) {
     static_assert(BYTES % 16 == 0 && BYTES <= 16384, "16-byte pieces, at most four M0 windows");
     const unsigned base = __builtin_amdgcn_readfirstlane((unsigned)(uintptr_t)lds_dst);
@@ -115,24 +120,59 @@ __device__ __forceinline__ void dma_tile_fixed(const float* __restrict__ g, floa
     for (int win = 0; win < BYTES; win += 4096) {
         const float* s4 = src + win / 4;
         asm volatile("s_mov_b32 m0, %0\n\ts_nop 0" :: "s"(base + (unsigned)win) : "memory");
-        if (win + 1024 <= BYTES) asm volatile("global_load_lds_dwordx4 %0, off" :: "v"(s4) : "memory");
-        if (win + 2048 <= BYTES) asm volatile("global_load_lds_dwordx4 %0, off offset:1024" :: "v"(s4) : "memory");
-        if (win + 3072 <= BYTES) asm volatile("global_load_lds_dwordx4 %0, off offset:2048" :: "v"(s4) : "memory");
-        if (win + 4096 <= BYTES) asm volatile("global_load_lds_dwordx4 %0, off offset:3072" :: "v"(s4) : "memory");
+        if (win + 1024 <= BYTES) dma_piece<0, NT>(s4);
+        if (win + 2048 <= BYTES) dma_piece<1024, NT>(s4);
+        if (win + 3072 <= BYTES) dma_piece<2048, NT>(s4);
+        if (win + 4096 <= BYTES) dma_piece<3072, NT>(s4);
         constexpr int full = BYTES / 1024 * 1024;          // the last, partial piece: the lanes below the end
         if (win <= full && full < win + 4096 && full < BYTES) {
             if (lane * 16 < BYTES - full) {
-                if (full - win == 0) asm volatile("global_load_lds_dwordx4 %0, off" :: "v"(s4) : "memory");
-                if (full - win == 1024) asm volatile("global_load_lds_dwordx4 %0, off offset:1024" :: "v"(s4) : "memory");
-                if (full - win == 2048) asm volatile("global_load_lds_dwordx4 %0, off offset:2048" :: "v"(s4) : "memory");
-                if (full - win == 3072) asm volatile("global_load_lds_dwordx4 %0, off offset:3072" :: "v"(s4) : "memory");
+                if (full - win == 0) dma_piece<0, NT>(s4);
+                if (full - win == 1024) dma_piece<1024, NT>(s4);
+                if (full - win == 2048) dma_piece<2048, NT>(s4);
+                if (full - win == 3072) dma_piece<3072, NT>(s4);
             }
         }
     }
     asm volatile("s_mov_b32 m0, %0" :: "s"(keep) : "memory");
 }
 
-
+// ---- record stores ---------------------------------------------------------------------------------------------------
+// A record is written once per step and read by a LATER launch.  The cache policy of its stores decides where the bytes wait for that:
+//   ST_PLAIN  dirty lines in the XCD's write-back L2 -- whatever is still there when the kernel ends is pushed out in front of the next
+//             dependent launch, with the CUs idle;
+//   ST_NT     the same line state, marked for early replacement;
+//   ST_WT     agent-scope write-through (sc1): the bytes go on to memory while the kernel still computes and leave no dirty line.  Only
+//             whole 16-byte pieces of full lines pay: the full tiles written through in place, as dwords of 4 N-byte row pieces, made
+//             F_2 9 us longer (profiles/r15_record_stores.md), hence the staged form of the phase kernels.
+// Vector stores all.  The 16-byte write-through has no builtin: inline asm, with two caveats the compiler does not cover for an
+// instruction inside an asm string.  (1) It is not counted in vmcnt: every caller sits in front of an explicit s_waitcnt vmcnt(0) (the
+// tile loop's, the persistent launch's arrival) or the end of the kernel.  (2) A 16-byte store needs two wait states before a VALU
+// instruction may write its data registers, and the data is dead behind the statement, so the register allocator may hand it to the very
+// next instruction: the string ends with s_nop 1.
+enum StorePolicy { ST_PLAIN = 0, ST_NT = 1, ST_WT = 2 };
+template <int POLICY>
+__device__ __forceinline__ void st_rec16(float* p, const float4& v) {
+    static_assert(POLICY == ST_PLAIN || POLICY == ST_NT || POLICY == ST_WT, "store policy");
+    if constexpr (POLICY == ST_WT) {
+        const f32x4 q = {v.x, v.y, v.z, v.w};
+        asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(p), "v"(q) : "memory");
+    } else if constexpr (POLICY == ST_NT) {
+        const f32x4 q = {v.x, v.y, v.z, v.w};
+        __builtin_nontemporal_store(q, reinterpret_cast<f32x4*>(p));
+    } else {
+        *reinterpret_cast<float4*>(p) = v;
+    }
+}
+template <int POLICY>
+__device__ __forceinline__ void st_rec4(unsigned* p, unsigned v) {
+    static_assert(POLICY == ST_PLAIN || POLICY == ST_NT || POLICY == ST_WT, "store policy");
+    if constexpr (POLICY == ST_WT) __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    else if constexpr (POLICY == ST_NT) __builtin_nontemporal_store(v, p);
+    else *p = v;
+}
+template <int POLICY>
+__device__ __forceinline__ void st_rec4(float* p, float v) { st_rec4<POLICY>(reinterpret_cast<unsigned*>(p), __builtin_bit_cast(unsigned, v)); }
 
 // ---- patch statistics, lean form -------------------------------------------------------------------------------------
 // Same ten statistics as patch_statistics_regs<P, true> (Model.py:7-52) with two of the per-element accumulations removed:

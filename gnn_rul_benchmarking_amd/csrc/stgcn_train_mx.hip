@@ -41,7 +41,9 @@
 // repeats the step on the exact fp32 chain (RULGNN_STEP_CHAIN; stgcn.py does).
 //
 // Memory.  Inputs arrive by LDS-DMA one tile ahead (each record is requested again as soon as its last LDS read has retired), outputs
-// leave one tile late, right behind the s_waitcnt vmcnt(0) that also counts stores (stgcn_forward_mx.hip, round 3).
+// leave one tile late, right behind the s_waitcnt vmcnt(0) that also counts stores (stgcn_forward_mx.hip, round 3).  The records are
+// stored write-through (whole 16-byte pieces out of a staging tile), so a phase ends with no dirty lines in L2 for the next launch to
+// wait behind, and a record's last reader in the step loads it non-temporally (MXT_RECORD_POLICY, MXT_LAST_READER_NT).
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
@@ -126,8 +128,11 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
     const int off_SB = off_A + (H_TOP ? XF : AF);                           // G_{2l}
     const int off_DX = off_SB + (NEED_SB ? XF : 0);          // gradient in (full tile or TOP's two rows)
     const int off_XP = off_DX + (GRAD_IN ? XF : 0);          // G_{2l}, l >= 1: the gated x-hat of BatchNorm 2l-1
-    const int off_HS = off_XP + (BWD_PREV ? XF : 0);         // H_OUT: the H record's staging tile
-    const int wave_floats = off_HS + (H_OUT ? XF : 0);
+    // every full-tile record this phase writes (F_{2l}: X_l, Q_l, H_l; G_{2l+1}: d(x0 + H); G_{2l}, l >= 1: d X_l) leaves through ONE
+    // staging tile per wavefront, one record after the other
+    constexpr bool TILE_OUT = WITH_PREV || (KIND == PH_G && BLK == 1) || BWD_PREV;
+    const int off_HS = off_XP + (BWD_PREV ? XF : 0);         // the staging tile
+    const int wave_floats = off_HS + (TILE_OUT ? XF : 0);
     float* const smem = smem_all + SH_BNC + MXT_RED_FLOATS + 2 * MXT_WAVES * (2 * F + 2) + wave * wave_floats;
     u32x2* const sh_tile = reinterpret_cast<u32x2*>(smem + off_sh);
     u32x2* const wg_img = reinterpret_cast<u32x2*>(smem + off_wg);
@@ -136,33 +141,40 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
     const int64_t tstride = (int64_t)gridDim.x * MXT_WAVES;
 
     // ---- requests --------------------------------------------------------------------------------------------------------
-    auto dma = [&](const float* src, int off, int bytes) {
+    // (`LAST_`: this phase is the record's last reader in the step -- MXT_LAST_READER_NT)
+    auto dma = [&](const float* src, int off, int bytes, auto LAST_) {
+        constexpr bool NT = decltype(LAST_)::value && MXT_LAST_READER_NT;
         if constexpr (NFIX != 0) {
-            if (bytes == 160 * NFIX) { dma_tile_fixed<160 * NFIX>(src, smem + off, lane); return; }
-            if (bytes == 32 * NFIX) { dma_tile_fixed<32 * NFIX>(src, smem + off, lane); return; }
+            if (bytes == 160 * NFIX) { dma_tile_fixed<160 * NFIX, NT>(src, smem + off, lane); return; }
+            if (bytes == 32 * NFIX) { dma_tile_fixed<32 * NFIX, NT>(src, smem + off, lane); return; }
         }
         if constexpr (AF != 0) {
-            if (bytes == 4 * AF) { dma_tile_fixed<4 * AF>(src, smem + off, lane); return; }
+            if (bytes == 4 * AF) { dma_tile_fixed<4 * AF, NT>(src, smem + off, lane); return; }
         }
-        dma_tile(src, smem + off, bytes, lane);
+        dma_tile<NT>(src, smem + off, bytes, lane);
     };
+    constexpr std::true_type LAST{};
+    // H_l dies with G_{2l+1}, X_l with G_{2l}, the adjacency with G_0; the gradient tensors and Q_l have one reader each
+    constexpr std::bool_constant<KIND == PH_G && BLK == 1> LAST_H{};
+    constexpr std::bool_constant<KIND == PH_G && BLK == 0> LAST_X{};
+    constexpr std::bool_constant<KIND == PH_G && IDX == 0> LAST_A{};
     auto req_XA = [&](int64_t t) {
         if constexpr (H_IN) {
-            dma(a.hrec[LY] + t * XF, off_X, 4 * XF);
+            dma(a.hrec[LY] + t * XF, off_X, 4 * XF, LAST_H);
         } else if constexpr (H_TOP) {
-            dma(a.xrec[LIN] + t * XF, off_X, 4 * XF);
-            dma(a.hrec[LY] + t * XF, off_A, 4 * XF);
+            dma(a.xrec[LIN] + t * XF, off_X, 4 * XF, std::false_type{});
+            dma(a.hrec[LY] + t * XF, off_A, 4 * XF, std::false_type{});
         } else {
-            dma(a.xrec[LIN] + t * XF, off_X, 4 * XF);
-            dma(a.arec + t * AF, off_A, 4 * AF);
+            dma(a.xrec[LIN] + t * XF, off_X, 4 * XF, LAST_X);
+            dma(a.arec + t * AF, off_A, 4 * AF, LAST_A);
         }
     };
-    auto req_SB = [&](int64_t t) { if constexpr (NEED_SB) dma(a.sb + t * XF, off_SB, 4 * XF); };
+    auto req_SB = [&](int64_t t) { if constexpr (NEED_SB) dma(a.sb + t * XF, off_SB, 4 * XF, LAST); };
     auto req_DX = [&](int64_t t) {
-        if constexpr (GRAD_TOP) dma(a.dtop + t * (8 * N), off_DX, 32 * N);
-        else if constexpr (GRAD_IN) dma(a.dx + t * XF, off_DX, 4 * XF);
+        if constexpr (GRAD_TOP) dma(a.dtop + t * (8 * N), off_DX, 32 * N, LAST);
+        else if constexpr (GRAD_IN) dma(a.dx + t * XF, off_DX, 4 * XF, LAST);
     };
-    auto req_XP = [&](int64_t t) { if constexpr (BWD_PREV) dma(a.qrec[LY] + t * XF, off_XP, 4 * XF); };
+    auto req_XP = [&](int64_t t) { if constexpr (BWD_PREV) dma(a.qrec[LY] + t * XF, off_XP, 4 * XF, LAST); };
 
     // ---- prologue.  The loads go out in three bursts, in the order their consumers need them -- the vector memory counter retires in
     // issue order, so a wait for one burst is a wait for every burst in front of it: (1) the reduction cells, the BatchNorm count and
@@ -297,19 +309,10 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
 #pragma unroll
             for (int r = 0; r < 3; ++r) v[s][r] = smem[(xoff[r] >= 0 ? base + xoff[r] : off_zero) + s * N];
     };
-    auto st_tile = [&](float* dst, const float (&v)[4][3], int ns) {
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-            if (s < ns) {
-#pragma unroll
-                for (int r = 0; r < 3; ++r)
-                    if (xoff[r] >= 0) dst[xoff[r] + s * N] = v[s][r];
-            }
-    };
-    // The H record leaves through LDS: the tile is assembled in the wavefront's staging words and stored as 16-byte pieces of the
+    // A full-tile record leaves through LDS: the tile is assembled in the wavefront's staging words and stored as 16-byte pieces of the
     // contiguous [10][4 N] record -- three dwordx4 stores of whole cache lines instead of twelve dword stores of 4 N-byte row pieces.
-    // All four samples go out: beyond the batch the record is never read (H_IN zeroes those samples).
-    auto st_tile_staged = [&](float* dst, const float (&v)[4][3]) {
+    // All four samples go out: beyond the batch a record is never used (every reader overwrites the samples >= ns of what it loads).
+    auto st_tile = [&](float* dst, const float (&v)[4][3]) {
         float* const stg = smem + off_HS;
 #pragma unroll
         for (int s = 0; s < 4; ++s)
@@ -318,7 +321,7 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
                 if (xoff[r] >= 0) stg[xoff[r] + s * N] = v[s][r];
         __builtin_amdgcn_wave_barrier();
         const int nq = XF / 4;
-        for (int i = lane; i < nq; i += 64) reinterpret_cast<float4*>(dst)[i] = reinterpret_cast<const float4*>(stg)[i];
+        for (int i = lane; i < nq; i += 64) st_rec16<MXT_RECORD_POLICY>(dst + 4 * i, reinterpret_cast<const float4*>(stg)[i]);
         __builtin_amdgcn_wave_barrier();
     };
     const int sh_rd1 = col >= 1 ? lane - 1 : 64, sh_rd2 = col >= 2 ? lane - 2 : 64;     // forward taps: column t - d
@@ -489,21 +492,21 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
         // ---- what the previous tile leaves: stored HERE, behind the wait that also counts stores ------------------------------------
         if (pend) {
             if constexpr (WITH_PREV) {
-                st_tile(a.xrec[LY] + pend_tile * XF, pend_v, pend_ns);
-                st_tile(a.qrec[LY] + pend_tile * XF, pend_q, pend_ns);
-                if (use_drop) a.mrec[LY - 1][pend_tile * 64 + lane] = pend_m;
+                st_tile(a.xrec[LY] + pend_tile * XF, pend_v);
+                st_tile(a.qrec[LY] + pend_tile * XF, pend_q);
+                if (use_drop) st_rec4<MXT_RECORD_POLICY>(a.mrec[LY - 1] + pend_tile * 64 + lane, pend_m);
             }
-            if constexpr (H_OUT) st_tile_staged(a.hrec[LY] + pend_tile * XF, pend_h);
-            if constexpr (KIND == PH_G && BLK == 1) st_tile(a.sb + pend_tile * XF, pend_v, pend_ns);
-            if constexpr (BWD_PREV) st_tile(a.dx + pend_tile * XF, pend_v, pend_ns);
+            if constexpr (H_OUT) st_tile(a.hrec[LY] + pend_tile * XF, pend_h);
+            if constexpr (KIND == PH_G && BLK == 1) st_tile(a.sb + pend_tile * XF, pend_v);
+            if constexpr (BWD_PREV) st_tile(a.dx + pend_tile * XF, pend_v);
             if constexpr (KIND == PH_TOP) {
                 if (g < pend_ns && col_ok && a.do_backward) {
                     float* p = a.dtop + pend_tile * (8 * N) + g * N + col;
-                    p[0] = pend_top0;
-                    p[pitch] = pend_top1;
+                    st_rec4<MXT_RECORD_POLICY>(p, pend_top0);
+                    st_rec4<MXT_RECORD_POLICY>(p + pitch, pend_top1);
                 }
-                if (g < pend_ns && col == 0) a.pred[pend_tile * 4 + g] = pend_pred;
-                if (use_drop && a.do_backward) a.mrec[LY][pend_tile * 64 + lane] = pend_m;
+                if (g < pend_ns && col == 0) st_rec4<MXT_RECORD_POLICY>(a.pred + pend_tile * 4 + g, pend_pred);
+                if (use_drop && a.do_backward) st_rec4<MXT_RECORD_POLICY>(a.mrec[LY] + pend_tile * 64 + lane, pend_m);
             }
         }
         // ---- inputs ------------------------------------------------------------------------------------------------------------------
@@ -951,21 +954,21 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
     // ---- the last tile's outputs ---------------------------------------------------------------------------------------------------------
     if (pend) {
         if constexpr (WITH_PREV) {
-            st_tile(a.xrec[LY] + pend_tile * XF, pend_v, pend_ns);
-            st_tile(a.qrec[LY] + pend_tile * XF, pend_q, pend_ns);
-            if (use_drop) a.mrec[LY - 1][pend_tile * 64 + lane] = pend_m;
+            st_tile(a.xrec[LY] + pend_tile * XF, pend_v);
+            st_tile(a.qrec[LY] + pend_tile * XF, pend_q);
+            if (use_drop) st_rec4<MXT_RECORD_POLICY>(a.mrec[LY - 1] + pend_tile * 64 + lane, pend_m);
         }
-        if constexpr (H_OUT) st_tile_staged(a.hrec[LY] + pend_tile * XF, pend_h);
-        if constexpr (KIND == PH_G && BLK == 1) st_tile(a.sb + pend_tile * XF, pend_v, pend_ns);
-        if constexpr (BWD_PREV) st_tile(a.dx + pend_tile * XF, pend_v, pend_ns);
+        if constexpr (H_OUT) st_tile(a.hrec[LY] + pend_tile * XF, pend_h);
+        if constexpr (KIND == PH_G && BLK == 1) st_tile(a.sb + pend_tile * XF, pend_v);
+        if constexpr (BWD_PREV) st_tile(a.dx + pend_tile * XF, pend_v);
         if constexpr (KIND == PH_TOP) {
             if (g < pend_ns && col_ok && a.do_backward) {
                 float* p = a.dtop + pend_tile * (8 * N) + g * N + col;
-                p[0] = pend_top0;
-                p[pitch] = pend_top1;
+                st_rec4<MXT_RECORD_POLICY>(p, pend_top0);
+                st_rec4<MXT_RECORD_POLICY>(p + pitch, pend_top1);
             }
-            if (g < pend_ns && col == 0) a.pred[pend_tile * 4 + g] = pend_pred;
-            if (use_drop && a.do_backward) a.mrec[LY][pend_tile * 64 + lane] = pend_m;
+            if (g < pend_ns && col == 0) st_rec4<MXT_RECORD_POLICY>(a.pred + pend_tile * 4 + g, pend_pred);
+            if (use_drop && a.do_backward) st_rec4<MXT_RECORD_POLICY>(a.mrec[LY] + pend_tile * 64 + lane, pend_m);
         }
     }
 
@@ -1080,7 +1083,7 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
     float* row = a.gpart + (size_t)blockIdx.x * a.pcount + rbase;
     for (int i = threadIdx.x; i < rlen; i += 64 * MXT_WAVES) {
         const float v = ((red[i] + red2[MXT_RED_FLOATS + i]) + (red2[i] + red2[2 * MXT_RED_FLOATS + i])) * us;
-        row[i] = v;
+        st_rec4<MXT_RECORD_POLICY>(row + i, v);
         bad |= !finite_f(v);
     }
     if (__any(bad) && lane == 0) atomicOr(&sc->pad[0], 1u);
@@ -1154,10 +1157,11 @@ static constexpr size_t mxt_lds_bytes(int L, int kind, int idx, int N) {
     const bool need_sb = kind == PH_G && blk == 0, grad_in = kind == PH_G && (blk == 1 || ly >= 1), bwd_prev = kind == PH_G && blk == 0 && ly >= 1;
     const bool h_in = (kind == PH_F || kind == PH_G) && blk == 1 && ly >= 1;     // H_IN of mxt_phase_body: no adjacency tile
     const bool h_top = kind == PH_TOP && ly >= 1;                                  // H_TOP: an H tile in its place
-    const bool h_out = kind == PH_F && blk == 0 && ly >= 1;       // H_OUT: the staging tile
+    // the staging tile of the phases that write full-tile records (TILE_OUT of mxt_phase_body)
+    const bool stage = (kind == PH_F && blk == 0 && ly >= 1) || (kind == PH_G && blk == 1) || bwd_prev;
     const int XF = 40 * N;
     const size_t wave = (size_t)MXT_ZERO_FLOATS + MXT_SCRATCH_FLOATS + MXT_SHIFT_FLOATS + (kind == PH_G ? MXT_WG_FLOATS : 0) + XF + (h_in ? 0 : h_top ? XF : 220) + (need_sb ? XF : 0) + (grad_in ? XF : 0) +
-                        (bwd_prev ? XF : 0) + (h_out ? XF : 0);
+                        (bwd_prev ? XF : 0) + (stage ? XF : 0);
     const size_t shared = (size_t)((2 * L * MXT_BNC * F + 3) & ~3) + MXT_RED_FLOATS + 2 * MXT_WAVES * (2 * F + 2);
     return (shared + MXT_WAVES * wave) * sizeof(float);
 }

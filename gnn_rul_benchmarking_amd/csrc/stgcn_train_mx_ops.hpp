@@ -25,6 +25,13 @@ constexpr int MXT_BNC = BN_TABLE_ROWS;   // per-BatchNorm constants: mean, istd,
 
 enum { PH_F = 0, PH_TOP = 1, PH_G = 2 };
 
+// How the records cross the kernel boundaries (StorePolicy, stgcn_mx.hpp; every alternative measured: profiles/r15_record_stores.md).
+// Stores: agent-scope write-through for every record -- the full tiles as whole 16-byte pieces out of the wavefront's staging tile (in
+// place, as dwords, write-through costs F_2 +9 us), the small records (d X_L, predictions, mask words, gradient rows) as dwords.
+// Loads: the phase that reads a record last in the step asks for it non-temporally.
+constexpr int MXT_RECORD_POLICY = ST_WT;
+constexpr bool MXT_LAST_READER_NT = true;
+
 struct Op2 { u32x4 h, l; };              // a D-layout tensor as the ({hi | hi}, {lo | lo}) operand pair against a {hi | lo} partner
 struct Pk { u32x2 hi, lo; };             // its packed halves: slots 4 g .. 4 g + 3 of this lane's column
 
