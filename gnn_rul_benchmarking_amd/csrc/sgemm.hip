@@ -248,19 +248,30 @@ static __global__ __launch_bounds__(256, 2) void sgemm_mfma128_kernel(GemmArgs g
 }
 
 typedef __bf16 gemm_bf16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 gemm_f16x8 __attribute__((ext_vector_type(8)));
 typedef unsigned gemm_u32x4 __attribute__((ext_vector_type(4)));
-// ------------------------------------------------------------------------------------------------
-// The same 128x128 tile on the bf16 matrix cores with fp32-class accuracy ("bf16 x 3").  Every fp32 operand is split EXACTLY into
-// three bf16 parts, x = h + m + l (h = the top 8 significant bits, m = the top 8 of x - h, l = x - h - m: 24 bits in all; the
-// subtractions are exact in fp32), when its tile is written to LDS -- once per element, amortised over the 128 products it takes part
-// in.  a b = ah bh + ah bm + am bh + ah bl + am bm + al bh + (terms below 2^-23 |a b|): six v_mfma_f32_32x32x16_bf16 with fp32
-// accumulation, each bf16 x bf16 product exact.  The error per product is that of ONE fp32 rounding; the rate is a sixth of the bf16
-// matrix peak = 2.6x the fp32 matrix peak (v_mfma_f32_16x16x4_f32 runs at the VALU FMA rate).  bf16 keeps fp32's exponent range, so no
-// scaling is needed (an f16 split would need two parts and three products but underflows on gradient-sized values).
-// LDS: per buffer three bf16 planes per operand, rows of 16 k = 32 bytes padded to 48 (eight consecutive rows x 16-byte reads cover
-// the 32 banks exactly once); a lane's MFMA operand is one ds_read_b128.
-// ------------------------------------------------------------------------------------------------
 typedef float f32x16t __attribute__((ext_vector_type(16)));
+// ------------------------------------------------------------------------------------------------
+// The large tiles on the 16-bit matrix cores with fp32-class accuracy.  Two independent axes, the SPLIT of an fp32 operand into 16-bit
+// planes and the TILE (128 or 256): sgemm_bf16x3_kernel (128) and sgemm_bf16x3v_kernel (256) are ONE body (sgemm_split_body) over a
+// split policy and a tile description; sgemm_f16x2_kernel (128) and sgemm_f16x2v_kernel (256) are the same algorithm in bodies of
+// their own (further down).
+//
+// Split "bf16 x 3" (SplitBf16x3).  Every fp32 operand is split EXACTLY into three bf16 parts, x = h + m + l (h = the top 8 significant
+// bits, m = the top 8 of x - h, l = x - h - m: 24 bits in all; the subtractions are exact in fp32), when its tile is written to LDS
+// -- once per element, amortised over the products it takes part in.  a b = ah bh + ah bm + am bh + ah bl + am bm + al bh + (terms
+// below 2^-23 |a b|): six v_mfma_f32_32x32x16_bf16 with fp32 accumulation, each bf16 x bf16 product exact.  The error per product is
+// that of ONE fp32 rounding; the rate is a sixth of the bf16 matrix peak = 2.6x the fp32 matrix peak (v_mfma_f32_16x16x4_f32 runs at
+// the VALU FMA rate).  bf16 keeps fp32's exponent range, so no scaling is needed.
+//
+// Split "f16 x 2".  TWO f16 planes per operand: a = hi + lo with hi = the top 11 significant bits of a s (exact in f16)
+// and lo = f16(a s - hi); a b = (hi hi + hi lo + lo hi) / (sa sb) + terms below 2^-22 |a b| -- three v_mfma_f32_32x32x16_f16 per fp32
+// product instead of six, the arithmetic of the fused ST_GCN kernels (stgcn_mx.hpp).  f16 has five exponent bits: the caller passes
+// max |A| and max |B| (GemmArgs::amax_*, produced by the kernels that wrote the operands) and each operand is scaled by a power of two
+// so that its largest element lands in [2^11, 2^12); an element more than 2^15 below the largest keeps fewer than 22 bits (its lo part
+// goes subnormal: absolute error 2^-37 of the largest) -- invisible in a product that also contains the large ones, ~4e-5 relative in
+// an output only such elements touch, and the reason this form is opt-in: the generic entry points keep the range-free bf16 split.
+// ------------------------------------------------------------------------------------------------
 
 // one fp32 pair -> one dword (first value in the low half) of each of the three planes
 static __device__ __forceinline__ void split_pair_bf16x3(float a, float b, unsigned& h, unsigned& m, unsigned& l) {
@@ -273,364 +284,6 @@ static __device__ __forceinline__ void split_pair_bf16x3(float a, float b, unsig
     l = __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, lb), __builtin_bit_cast(unsigned, la), 0x07060302u);
 }
 
-// LDS layouts of one operand plane (6 KB reserved each):
-//   operand contiguous along k   : [row][16 k] bf16, rows padded to 48 bytes; a thread's float4 (4 k of one row) is one 8-byte store,
-//                                  a lane's MFMA operand (8 k of its row) one 16-byte read;
-//   operand contiguous along rows: [k pair][128 rows] dwords (k even in the low half); a thread holds 4 rows x 2 k (two float4, k and
-//                                  k + 1) = one 16-byte store, a lane's MFMA operand four 4-byte reads, consecutive lanes consecutive
-//                                  dwords.  (Two-byte stores into the row-major form were 16-way bank conflicts: 56 TFLOP/s.)
-template <bool A_KFAST, bool B_KFAST, bool GUARD>
-static __device__ __forceinline__ void sgemm_bf16x3_body(GemmArgs g) {
-    constexpr int ROWB = 48;                       // bytes per LDS row of the k-contiguous form
-    constexpr int PLANE = 128 * ROWB;              // one bf16 plane of one operand tile
-    constexpr int BUF = 6 * PLANE;                 // A: h, m, l ; B: h, m, l
-    extern __shared__ __attribute__((aligned(16))) unsigned char sgemm_x3_lds[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int m0 = blockIdx.y * 128, n0 = blockIdx.x * 128;
-    const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
-    f32x16t acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    const int kbeg = blockIdx.z * g.kchunk, kend = min(g.K, kbeg + g.kchunk);
-    g.C += (int64_t)blockIdx.z * g.M * g.ldc;
-    f32x4t ra[2], rb[2];
-    // k-contiguous: float4 e of a thread = row (tid + 256 e) >> 2, k = 4 ((tid + 256 e) & 3)
-    // row-contiguous: float4 e of a thread = rows 4 (tid & 31) .. + 3 at k = 2 (tid >> 5) + e
-    auto fetch_one = [&](const float* __restrict__ P, int64_t s_row, int64_t s_k, int rows, int r0, int k0, int e, bool kfast) -> f32x4t {
-        f32x4t v = {0.f, 0.f, 0.f, 0.f};
-        if (!GUARD && k0 + 16 <= kend) {          // interior tile, whole K step (wave-uniform): every 16-byte load is in bounds
-            if (kfast) {
-                const int idx = tid + e * 256;
-                return *reinterpret_cast<const f32x4t*>(P + (int64_t)(r0 + (idx >> 2)) * s_row + k0 + 4 * (idx & 3));
-            }
-            return *reinterpret_cast<const f32x4t*>(P + (int64_t)(k0 + 2 * (tid >> 5) + e) * s_k + r0 + 4 * (tid & 31));
-        }
-        if (kfast) {
-            const int idx = tid + e * 256;
-            const int r = r0 + (idx >> 2), k = k0 + 4 * (idx & 3);
-            if (r < rows) {
-                const float* p = P + (int64_t)r * s_row + k;
-                if (k + 3 < kend) v = *reinterpret_cast<const f32x4t*>(p);
-                else {
-                    if (k < kend) v[0] = p[0];
-                    if (k + 1 < kend) v[1] = p[1];
-                    if (k + 2 < kend) v[2] = p[2];
-                }
-            }
-        } else {
-            const int k = k0 + 2 * (tid >> 5) + e, r = r0 + 4 * (tid & 31);
-            if (k < kend) {
-                const float* p = P + (int64_t)k * s_k + r;
-                if (r + 3 < rows) v = *reinterpret_cast<const f32x4t*>(p);
-                else {
-                    if (r < rows) v[0] = p[0];
-                    if (r + 1 < rows) v[1] = p[1];
-                    if (r + 2 < rows) v[2] = p[2];
-                }
-            }
-        }
-        return v;
-    };
-    auto fetch = [&](int k0) {
-#pragma unroll
-        for (int e = 0; e < 2; ++e) {
-            ra[e] = fetch_one(g.A, g.sAm, g.sAk, g.M, m0, k0, e, A_KFAST);
-            rb[e] = fetch_one(g.B, g.sBn, g.sBk, g.N, n0, k0, e, B_KFAST);
-        }
-    };
-    auto stash_one = [&](unsigned char* base, const f32x4t (&v)[2], bool kfast) {
-        if (kfast) {
-#pragma unroll
-            for (int e = 0; e < 2; ++e) {
-                const int idx = tid + e * 256;
-                const float x0 = v[e][0], x1 = v[e][1], x2 = v[e][2], x3 = v[e][3];
-                unsigned h0, m0_, l0, h1, m1, l1;
-                split_pair_bf16x3(x0, x1, h0, m0_, l0);
-                split_pair_bf16x3(x2, x3, h1, m1, l1);
-                unsigned char* p = base + (idx >> 2) * ROWB + 8 * (idx & 3);
-                *reinterpret_cast<uint2*>(p) = make_uint2(h0, h1);
-                *reinterpret_cast<uint2*>(p + PLANE) = make_uint2(m0_, m1);
-                *reinterpret_cast<uint2*>(p + 2 * PLANE) = make_uint2(l0, l1);
-            }
-        } else {
-            unsigned h[4], m[4], l[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float x0 = v[0][j], x1 = v[1][j];
-                split_pair_bf16x3(x0, x1, h[j], m[j], l[j]);
-            }
-            unsigned char* p = base + ((tid >> 5) * 128 + 4 * (tid & 31)) * 4;
-            *reinterpret_cast<uint4*>(p) = make_uint4(h[0], h[1], h[2], h[3]);
-            *reinterpret_cast<uint4*>(p + PLANE) = make_uint4(m[0], m[1], m[2], m[3]);
-            *reinterpret_cast<uint4*>(p + 2 * PLANE) = make_uint4(l[0], l[1], l[2], l[3]);
-        }
-    };
-    auto stash = [&](int buf) {
-        unsigned char* b = sgemm_x3_lds + buf * BUF;
-        stash_one(b, ra, A_KFAST);
-        stash_one(b + 3 * PLANE, rb, B_KFAST);
-    };
-    // the MFMA operand of this lane: 8 consecutive k (k half lane >> 5) of row `row0 + (lane & 31)` of one plane
-    auto operand = [&](const unsigned char* plane, int row0, bool kfast) -> gemm_bf16x8 {
-        if (kfast) return *reinterpret_cast<const gemm_bf16x8*>(plane + (row0 + (lane & 31)) * ROWB + (lane >> 5) * 16);
-        const unsigned* q = reinterpret_cast<const unsigned*>(plane) + (4 * (lane >> 5)) * 128 + row0 + (lane & 31);
-        const gemm_u32x4 v = {q[0], q[128], q[256], q[384]};
-        return __builtin_bit_cast(gemm_bf16x8, v);
-    };
-    // Software pipeline, two K steps deep: while the matrix cores work on tile k (LDS buffer `buf`), the registers loaded during the
-    // PREVIOUS iteration (tile k + 1: a full iteration of latency cover) are split and written to the other buffer, and the loads of
-    // tile k + 2 are issued.  The split's VALU work is interleaved with the MFMAs by the scheduling hints at the end of the body: an
-    // in-order wavefront hides ~5 other instructions behind each 32-cycle MFMA, or none at all if they sit behind the whole chain.
-    int buf = 0;
-    if (kbeg < kend) {
-        fetch(kbeg);
-        stash(0);
-        fetch(kbeg + 16);                     // tile 1 (past the end the guarded loads return zeros)
-    }
-    __syncthreads();
-    for (int k0 = kbeg; k0 < kend; k0 += 16) {
-        const bool more = k0 + 16 < kend;
-        f32x4t na[2], nb[2];
-#pragma unroll
-        for (int e = 0; e < 2; ++e) { na[e] = ra[e]; nb[e] = rb[e]; }          // tile k + 1, loaded one iteration ago
-        if (k0 + 32 < kend) fetch(k0 + 32);                                      // tile k + 2 into ra / rb
-        const unsigned char* b = sgemm_x3_lds + buf * BUF;
-        gemm_bf16x8 a[2][3], bb[2][3];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int p = 0; p < 3; ++p) {
-                a[i][p] = operand(b + p * PLANE, wm + 32 * i, A_KFAST);
-                bb[i][p] = operand(b + (3 + p) * PLANE, wn + 32 * i, B_KFAST);
-            }
-        // the six product terms, smallest first; consecutive MFMAs go to different accumulators (independent: back-to-back issue)
-        constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
-#pragma unroll
-        for (int t = 0; t < 6; ++t)
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][PA[t]], bb[j][PB[t]], acc[i][j], 0, 0, 0);
-        if (more) {
-            unsigned char* nbuf = sgemm_x3_lds + (buf ^ 1) * BUF;
-            stash_one(nbuf, na, A_KFAST);
-            stash_one(nbuf + 3 * PLANE, nb, B_KFAST);
-        }
-#pragma unroll
-        for (int q = 0; q < 24; ++q) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);      // one MFMA
-            __builtin_amdgcn_sched_group_barrier(0x002, 5, 0);      // five VALU (the split)
-            __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);      // one LDS write
-        }
-        __syncthreads();
-        buf ^= 1;
-    }
-    // D layout of the 32x32 result: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int gm = m0 + wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5), gn = n0 + wn + 32 * j + (lane & 31);
-                if (!GUARD || (gm < g.M && gn < g.N)) {
-                    float* c = g.C + (int64_t)gm * g.ldc + gn;
-                    *c = g.accumulate ? *c + acc[i][j][r] : acc[i][j][r];
-                }
-            }
-}
-
-template <bool A_KFAST, bool B_KFAST>
-static __global__ __launch_bounds__(256, 2) void sgemm_bf16x3_kernel(GemmArgs g) {
-    // interior tiles take the body whose whole K steps load without bounds checks (a third of its non-MFMA instructions were guards)
-    const int kbeg = blockIdx.z * g.kchunk, kend = min(g.K, kbeg + g.kchunk);
-    const bool interior = (int)blockIdx.y * 128 + 128 <= g.M && (int)blockIdx.x * 128 + 128 <= g.N && kend > kbeg;
-    if (interior) sgemm_bf16x3_body<A_KFAST, B_KFAST, false>(g);
-    else sgemm_bf16x3_body<A_KFAST, B_KFAST, true>(g);
-}
-
-// ------------------------------------------------------------------------------------------------
-// The same arithmetic on a 256x256 block tile.  SQ counters of the 128x128 kernel: per K step a wavefront issues 154 VALU + 37
-// scalar + 20 LDS instructions for its 24 MFMAs -- 1044 issue cycles against 768 MFMA cycles, two wavefronts per SIMD: the split is
-// re-done by every tile that loads an element.  Doubling both tile dimensions halves the elements loaded (and split) per MFMA; a
-// thread serves ONE operand (wavefronts 0-3: A, 4-7: B).  First built with 16 wavefronts of 64 x 64 (193 TFLOP/s at 4096^3): that
-// form is bound by LDS READ bandwidth -- 12 KB of operand planes per 24 MFMAs = 512 B per MFMA, 64 B/clk per CU of the LDS's 128 B/clk
-// before bank conflicts (a variant that split every operand once, in a pre-pass, ran no faster).  This one has 8 wavefronts of
-// 64 x 128 (128 accumulator registers): 18 KB per 48 MFMAs = 384 B per MFMA, 203 TFLOP/s.
-// ------------------------------------------------------------------------------------------------
-template <bool A_KFAST, bool B_KFAST, bool GUARD>
-static __device__ __forceinline__ void sgemm_bf16x3v_body(GemmArgs g) {
-    constexpr int T = 256;                         // tile rows / columns
-    constexpr int ROWB = 48;
-    constexpr int PLANE = T * ROWB;                // 12 KB
-    constexpr int BUF = 6 * PLANE;                 // 72 KB
-    extern __shared__ __attribute__((aligned(16))) unsigned char sgemm_x3_lds[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int m0 = blockIdx.y * T, n0 = blockIdx.x * T;
-    const int wm = (wave >> 1) * 64, wn = (wave & 1) * 128;          // 8 wavefronts, each 64 rows x 128 columns
-    f32x16t acc[2][4];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-    const int kbeg = blockIdx.z * g.kchunk, kend = min(g.K, kbeg + g.kchunk);
-    g.C += (int64_t)blockIdx.z * g.M * g.ldc;
-    // this thread's operand
-    const bool mine_b = tid >= 256;
-    const int t = tid & 255;
-    const float* __restrict__ P = mine_b ? g.B : g.A;
-    const int64_t s_row = mine_b ? g.sBn : g.sAm, s_k = mine_b ? g.sBk : g.sAk;
-    const int rows = mine_b ? g.N : g.M, r0 = mine_b ? n0 : m0;
-    const bool kfast = mine_b ? B_KFAST : A_KFAST;                  // wave-uniform
-    f32x4t rr[4];
-    auto fetch = [&](int k0) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            f32x4t v = {0.f, 0.f, 0.f, 0.f};
-            if (kfast) {
-                const int idx = t + e * 256;
-                const int r = r0 + (idx >> 2), k = k0 + 4 * (idx & 3);
-                const float* p = P + (int64_t)r * s_row + k;
-                if (!GUARD && k0 + 16 <= kend) v = *reinterpret_cast<const f32x4t*>(p);
-                else if (r < rows) {
-                    if (k + 3 < kend) v = *reinterpret_cast<const f32x4t*>(p);
-                    else {
-                        if (k < kend) v[0] = p[0];
-                        if (k + 1 < kend) v[1] = p[1];
-                        if (k + 2 < kend) v[2] = p[2];
-                    }
-                }
-            } else {
-                const int k = k0 + 4 * (t >> 6) + e, r = r0 + 4 * (t & 63);
-                const float* p = P + (int64_t)k * s_k + r;
-                if (!GUARD && k0 + 16 <= kend) v = *reinterpret_cast<const f32x4t*>(p);
-                else if (k < kend) {
-                    if (r + 3 < rows) v = *reinterpret_cast<const f32x4t*>(p);
-                    else {
-                        if (r < rows) v[0] = p[0];
-                        if (r + 1 < rows) v[1] = p[1];
-                        if (r + 2 < rows) v[2] = p[2];
-                    }
-                }
-            }
-            rr[e] = v;
-        }
-    };
-    auto stash = [&](unsigned char* bufp, const f32x4t (&v)[4]) {
-        unsigned char* base = bufp + (mine_b ? 3 * PLANE : 0);
-        if (kfast) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int idx = t + e * 256;
-                const float x0 = v[e][0], x1 = v[e][1], x2 = v[e][2], x3 = v[e][3];
-                unsigned h0, m0_, l0, h1, m1, l1;
-                split_pair_bf16x3(x0, x1, h0, m0_, l0);
-                split_pair_bf16x3(x2, x3, h1, m1, l1);
-                unsigned char* p = base + (idx >> 2) * ROWB + 8 * (idx & 3);
-                *reinterpret_cast<uint2*>(p) = make_uint2(h0, h1);
-                *reinterpret_cast<uint2*>(p + PLANE) = make_uint2(m0_, m1);
-                *reinterpret_cast<uint2*>(p + 2 * PLANE) = make_uint2(l0, l1);
-            }
-        } else {
-#pragma unroll
-            for (int pp = 0; pp < 2; ++pp) {                       // two k pairs per thread: (4 kq, 4 kq + 1) and (4 kq + 2, 4 kq + 3)
-                unsigned h[4], m[4], l[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float x0 = v[2 * pp][j], x1 = v[2 * pp + 1][j];
-                    split_pair_bf16x3(x0, x1, h[j], m[j], l[j]);
-                }
-                unsigned char* p = base + ((2 * (t >> 6) + pp) * T + 4 * (t & 63)) * 4;
-                *reinterpret_cast<uint4*>(p) = make_uint4(h[0], h[1], h[2], h[3]);
-                *reinterpret_cast<uint4*>(p + PLANE) = make_uint4(m[0], m[1], m[2], m[3]);
-                *reinterpret_cast<uint4*>(p + 2 * PLANE) = make_uint4(l[0], l[1], l[2], l[3]);
-            }
-        }
-    };
-    auto operand = [&](const unsigned char* plane, int row0, bool kf) -> gemm_bf16x8 {
-        if (kf) return *reinterpret_cast<const gemm_bf16x8*>(plane + (row0 + (lane & 31)) * ROWB + (lane >> 5) * 16);
-        const unsigned* q = reinterpret_cast<const unsigned*>(plane) + (4 * (lane >> 5)) * T + row0 + (lane & 31);
-        const gemm_u32x4 v = {q[0], q[T], q[2 * T], q[3 * T]};
-        return __builtin_bit_cast(gemm_bf16x8, v);
-    };
-    int buf = 0;
-    if (kbeg < kend) {
-        fetch(kbeg);
-        stash(sgemm_x3_lds, rr);
-        fetch(kbeg + 16);
-    }
-    __syncthreads();
-    for (int k0 = kbeg; k0 < kend; k0 += 16) {
-        const bool more = k0 + 16 < kend;
-        f32x4t nn[4] = {rr[0], rr[1], rr[2], rr[3]};                                         // tile k + 1, loaded one iteration ago
-        if (k0 + 32 < kend) fetch(k0 + 32);
-        const unsigned char* b = sgemm_x3_lds + buf * BUF;
-        gemm_bf16x8 a[2][3];
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int p = 0; p < 3; ++p) a[i][p] = operand(b + p * PLANE, wm + 32 * i, A_KFAST);
-        constexpr int PA[6] = {2, 0, 1, 1, 0, 0}, PB[6] = {0, 2, 1, 0, 1, 0};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            gemm_bf16x8 bb[3];
-#pragma unroll
-            for (int p = 0; p < 3; ++p) bb[p] = operand(b + (3 + p) * PLANE, wn + 32 * j, B_KFAST);
-#pragma unroll
-            for (int tt = 0; tt < 6; ++tt)
-#pragma unroll
-                for (int i = 0; i < 2; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i][PA[tt]], bb[PB[tt]], acc[i][j], 0, 0, 0);
-        }
-        if (more) stash(sgemm_x3_lds + (buf ^ 1) * BUF, nn);
-#pragma unroll
-        for (int q = 0; q < 48; ++q) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);
-            __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
-        }
-        __syncthreads();
-        buf ^= 1;
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int gm = m0 + wm + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5), gn = n0 + wn + 32 * j + (lane & 31);
-                if (!GUARD || (gm < g.M && gn < g.N)) {
-                    float* c = g.C + (int64_t)gm * g.ldc + gn;
-                    *c = g.accumulate ? *c + acc[i][j][r] : acc[i][j][r];
-                }
-            }
-}
-
-template <bool A_KFAST, bool B_KFAST>
-static __global__ __launch_bounds__(512) void sgemm_bf16x3v_kernel(GemmArgs g) {
-    const int kbeg = blockIdx.z * g.kchunk, kend = min(g.K, kbeg + g.kchunk);
-    const bool interior = (int)blockIdx.y * 256 + 256 <= g.M && (int)blockIdx.x * 256 + 256 <= g.N && kend > kbeg;
-    if (interior) sgemm_bf16x3v_body<A_KFAST, B_KFAST, false>(g);
-    else sgemm_bf16x3v_body<A_KFAST, B_KFAST, true>(g);
-}
-
-// ------------------------------------------------------------------------------------------------
-// The 256 x 256 kernel on TWO f16 planes per operand: a = hi + lo with hi = the top 11 significant bits of a s (exact in f16) and
-// lo = f16(a s - hi); a b = (hi hi + hi lo + lo hi) / (sa sb) + terms below 2^-22 |a b| -- three v_mfma_f32_32x32x16_f16 per fp32
-// product instead of the six of the bf16 split, the arithmetic of the fused ST_GCN kernels (stgcn_mx.hpp).  f16 has five exponent bits:
-// the caller passes max |A| and max |B| (GemmArgs::amax_*, produced by the kernels that wrote the operands) and each operand is scaled
-// by a power of two so that its largest element lands in [2^11, 2^12); an element more than 2^15 below the largest keeps fewer than 22
-// bits (its lo part goes subnormal: absolute error 2^-37 of the largest) -- invisible in a product that also contains the large ones,
-// ~4e-5 relative in an output only such elements touch, and the reason this form is opt-in: the generic entry points keep the
-// range-free bf16 split.  Same tiles, LDS layout (two planes: 96 KB double-buffered) and pipeline.
-// ------------------------------------------------------------------------------------------------
-typedef _Float16 gemm_f16x8 __attribute__((ext_vector_type(8)));
 static __device__ __forceinline__ float sgemm_f16_scale_of(float amax) {
     const unsigned m = __builtin_bit_cast(unsigned, amax);
     const int e = (int)((m >> 23) & 0xFFu);                          // biased exponent of the largest finite magnitude
@@ -639,7 +292,9 @@ static __device__ __forceinline__ float sgemm_f16_scale_of(float amax) {
     se = se < 1 ? 1 : (se > 254 ? 254 : se);
     return __builtin_bit_cast(float, (unsigned)se << 23);
 }
-// the two operand scales from the producers' partial maxima (256 or 512 threads; a few thousand floats out of L2: ~1 us per workgroup)
+// the two operand scales from the producers' partial maxima (256 or 512 threads; a few thousand floats out of L2: ~1 us per workgroup):
+// max |x| s in [2^11, 2^12) -- sixteen times below the f16 range, and an element down to 2^-25 of the tensor's largest still has a
+// normal hi part
 static __device__ __forceinline__ void sgemm_f16_scales(const GemmArgs& g, float& sa, float& sb) {
     __shared__ float part[2][8];
     float ma = 0.f, mb = 0.f;
@@ -668,6 +323,269 @@ static __device__ __forceinline__ void split_pair_f16x2(float a, float b, unsign
     h = __builtin_bit_cast(unsigned, __builtin_convertvector(hv, h2));
     l = __builtin_bit_cast(unsigned, __builtin_convertvector(lv, h2));
 }
+
+// The split axis.  PLANES per operand (plane 0 = the largest part), the NPROD product terms as plane pairs (PA[t], PB[t]), smallest term
+// first.  LADDER_VALU: the VALU instructions the scheduling ladder of the K loop places behind each MFMA, for the 128 and the 256 tile
+// (tuned: the split's work per MFMA).
+struct SplitBf16x3 {
+    typedef gemm_bf16x8 vec;
+    static constexpr int PLANES = 3, NPROD = 6;
+    static constexpr int PA[NPROD] = {2, 0, 1, 1, 0, 0}, PB[NPROD] = {0, 2, 1, 0, 1, 0};
+    static constexpr int LADDER_VALU[2] = {5, 3};
+    static __device__ __forceinline__ void split_pair(float a, float b, unsigned (&p)[PLANES]) { split_pair_bf16x3(a, b, p[0], p[1], p[2]); }
+    static __device__ __forceinline__ f32x16t mfma(vec a, vec b, f32x16t c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+};
+
+// The tile axis: T x T outputs per workgroup, K step 16, wavefronts in two columns, each owning 64 rows x 32 NJ columns as 2 x NJ MFMA
+// tiles of 32 x 32.
+//   T = 128: 4 wavefronts of 64 x 64 (64 accumulator registers), two workgroups per CU; every thread loads both operands.
+//   T = 256: 8 wavefronts of 64 x 128 (128 accumulator registers).  SQ counters of the 128 tile with the bf16 split: per K step a
+//            wavefront issues 154 VALU + 37 scalar + 20 LDS instructions for its 24 MFMAs -- 1044 issue cycles against 768 MFMA cycles,
+//            two wavefronts per SIMD: the split is re-done by every tile that loads an element.  Doubling both tile dimensions halves
+//            the elements loaded (and split) per MFMA; a thread serves ONE operand (wavefronts 0-3: A, 4-7: B).  First built with 16
+//            wavefronts of 64 x 64 (193 TFLOP/s at 4096^3): that form is bound by LDS READ bandwidth -- 12 KB of operand planes per 24
+//            MFMAs = 512 B per MFMA, 64 B/clk per CU of the LDS's 128 B/clk before bank conflicts (a variant that split every operand
+//            once, in a pre-pass, ran no faster).  With 64 x 128: 18 KB per 48 MFMAs = 384 B per MFMA, 203 TFLOP/s.
+// An operand tile is T x 16 floats = 4 T float4, loaded by 256 threads (t = tid & 255), NV each:
+//   operand contiguous along k   : float4 e of thread t = row (t + 256 e) >> 2, k = 4 ((t + 256 e) & 3)
+//   operand contiguous along rows: float4 e of thread t = rows 4 (t % (T/4)) .. + 3 at k = NV (t / (T/4)) + e
+// LDS layouts of one operand plane (PLANE bytes reserved each):
+//   operand contiguous along k   : [row][16 k] 16-bit, rows of 32 bytes padded to ROWB = 48 (eight consecutive rows x 16-byte reads cover
+//                                  the 32 banks exactly once); a thread's float4 (4 k of one row) is one 8-byte store, a lane's MFMA
+//                                  operand (8 k of its row) one 16-byte read;
+//   operand contiguous along rows: [k pair][T rows] dwords (k even in the low half); a thread holds 4 rows x 2 k (two float4, k and
+//                                  k + 1) per pair = one 16-byte store, a lane's MFMA operand four 4-byte reads, consecutive lanes
+//                                  consecutive dwords.  (Two-byte stores into the row-major form were 16-way bank conflicts: 56 TFLOP/s.)
+template <int T_>
+struct SplitTile {
+    static_assert(T_ == 128 || T_ == 256, "tile");
+    static constexpr int T = T_, ROWB = 48, PLANE = T * ROWB;
+    static constexpr int NV = T / 64;                          // float4 per loading thread and operand
+    static constexpr int NJ = T / 64;                          // 32-column blocks of a wavefront's tile
+    static constexpr int THREADS = 2 * T;
+    static constexpr int OPERANDS = T == 128 ? 2 : 1;          // operands a thread loads, splits and stashes
+    template <class Split> static constexpr int MFMAS = Split::NPROD * 2 * NJ;          // per wavefront and K step
+    template <class Split> static constexpr int LADDER_VALU = Split::LADDER_VALU[T / 256];
+};
+// dynamic LDS of a kernel: two buffers of (A planes, B planes)
+template <int PLANES, int T>
+constexpr size_t lds_bytes() { return (size_t)2 * 2 * PLANES * SplitTile<T>::PLANE; }
+
+// Guarded 16-byte load of elements i .. i + 3 of a contiguous line of n (p: element i); those past n, or all four if the line itself
+// lies outside the operand, read as zero.  `unchecked` (wave-uniform): the caller knows all four are in bounds.
+static __device__ __forceinline__ f32x4t load4_guarded(const float* __restrict__ p, bool line, int i, int n, bool unchecked) {
+    if (unchecked) return *reinterpret_cast<const f32x4t*>(p);
+    f32x4t v = {0.f, 0.f, 0.f, 0.f};
+    if (line) {
+        if (i + 3 < n) v = *reinterpret_cast<const f32x4t*>(p);
+        else {
+            if (i < n) v[0] = p[0];
+            if (i + 1 < n) v[1] = p[1];
+            if (i + 2 < n) v[2] = p[2];
+        }
+    }
+    return v;
+}
+
+// what a thread needs of an operand it serves (kfast: wave-uniform)
+struct SplitOperand {
+    const float* P; int64_t s_row, s_k;
+    int rows, r0;            // the operand's row count, the tile's first row
+    bool kfast;
+    int plane0;              // byte offset of its planes in an LDS buffer
+};
+
+// float4 e of thread t of the K step at k0.  !GUARD: an interior tile, whose whole K steps load without bounds checks (a third of the
+// body's non-MFMA instructions were guards)
+template <int T, bool GUARD>
+static __device__ __forceinline__ f32x4t split_fetch(const SplitOperand& o, int t, int e, int k0, int kend) {
+    const bool whole = !GUARD && k0 + 16 <= kend;
+    if (o.kfast) {
+        const int idx = t + e * 256;
+        const int r = o.r0 + (idx >> 2), k = k0 + 4 * (idx & 3);
+        return load4_guarded(o.P + (int64_t)r * o.s_row + k, r < o.rows, k, kend, whole);
+    }
+    const int k = k0 + SplitTile<T>::NV * (t / (T / 4)) + e, r = o.r0 + 4 * (t % (T / 4));
+    return load4_guarded(o.P + (int64_t)k * o.s_k + r, k < kend, r, o.rows, whole);
+}
+
+// split a thread's NV float4 of one operand and write them to the operand's planes (base: plane 0 in the buffer)
+template <class Split, int T>
+static __device__ __forceinline__ void split_stash(unsigned char* base, const f32x4t (&v)[SplitTile<T>::NV], int t, bool kfast) {
+    constexpr int NV = SplitTile<T>::NV, ROWB = SplitTile<T>::ROWB, PLANE = SplitTile<T>::PLANE, NP = Split::PLANES;
+    if (kfast) {
+#pragma unroll
+        for (int e = 0; e < NV; ++e) {
+            const int idx = t + e * 256;
+            unsigned lo[NP], hi[NP];
+            Split::split_pair(v[e][0], v[e][1], lo);
+            Split::split_pair(v[e][2], v[e][3], hi);
+            unsigned char* p = base + (idx >> 2) * ROWB + 8 * (idx & 3);
+#pragma unroll
+            for (int q = 0; q < NP; ++q) *reinterpret_cast<uint2*>(p + q * PLANE) = make_uint2(lo[q], hi[q]);
+        }
+    } else {
+#pragma unroll
+        for (int pp = 0; pp < NV / 2; ++pp) {                  // the thread's k pairs: (2 pp, 2 pp + 1) of its NV consecutive k
+            unsigned w[4][NP];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) Split::split_pair(v[2 * pp][j], v[2 * pp + 1][j], w[j]);
+            unsigned char* p = base + (((NV / 2) * (t / (T / 4)) + pp) * T + 4 * (t % (T / 4))) * 4;
+#pragma unroll
+            for (int q = 0; q < NP; ++q) *reinterpret_cast<uint4*>(p + q * PLANE) = make_uint4(w[0][q], w[1][q], w[2][q], w[3][q]);
+        }
+    }
+}
+
+// the MFMA operand of this lane: 8 consecutive k (k half lane >> 5) of row `row0 + (lane & 31)` of one plane
+template <class Split, int T>
+static __device__ __forceinline__ typename Split::vec split_operand(const unsigned char* plane, int row0, int lane, bool kfast) {
+    typedef typename Split::vec vec;
+    if (kfast) return *reinterpret_cast<const vec*>(plane + (row0 + (lane & 31)) * SplitTile<T>::ROWB + (lane >> 5) * 16);
+    const unsigned* q = reinterpret_cast<const unsigned*>(plane) + (4 * (lane >> 5)) * T + row0 + (lane & 31);
+    const gemm_u32x4 v = {q[0], q[T], q[2 * T], q[3 * T]};
+    return __builtin_bit_cast(vec, v);
+}
+
+// One K step of a wavefront's products from LDS buffer b: per accumulator the NPROD terms, smallest first (the same order in both nests:
+// the tiles give the same bits).  The nest is tuned per tile.  128: all B operands up front, the term outermost -- consecutive MFMAs go
+// to different accumulators (independent: back-to-back issue).  256: the column block outermost, its B operands read per block.
+template <class Split, int T, bool A_KFAST, bool B_KFAST>
+static __device__ __forceinline__ void split_products(const unsigned char* b, int wm, int wn, int lane, f32x16t (&acc)[2][SplitTile<T>::NJ]) {
+    typedef typename Split::vec vec;
+    constexpr int NP = Split::PLANES, NJ = SplitTile<T>::NJ, PLANE = SplitTile<T>::PLANE;
+    vec a[2][NP];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int p = 0; p < NP; ++p) a[i][p] = split_operand<Split, T>(b + p * PLANE, wm + 32 * i, lane, A_KFAST);
+    if constexpr (T == 128) {
+        vec bb[NJ][NP];
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+#pragma unroll
+            for (int p = 0; p < NP; ++p) bb[j][p] = split_operand<Split, T>(b + (NP + p) * PLANE, wn + 32 * j, lane, B_KFAST);
+#pragma unroll
+        for (int t = 0; t < Split::NPROD; ++t)
+#pragma unroll
+            for (int i = 0; i < 2; ++i)
+#pragma unroll
+                for (int j = 0; j < NJ; ++j) acc[i][j] = Split::mfma(a[i][Split::PA[t]], bb[j][Split::PB[t]], acc[i][j]);
+    } else {
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) {
+            vec bb[NP];
+#pragma unroll
+            for (int p = 0; p < NP; ++p) bb[p] = split_operand<Split, T>(b + (NP + p) * PLANE, wn + 32 * j, lane, B_KFAST);
+#pragma unroll
+            for (int t = 0; t < Split::NPROD; ++t)
+#pragma unroll
+                for (int i = 0; i < 2; ++i) acc[i][j] = Split::mfma(a[i][Split::PA[t]], bb[Split::PB[t]], acc[i][j]);
+        }
+    }
+}
+
+// D layout of a 32x32 result: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5)
+template <int NJ, bool GUARD>
+static __device__ __forceinline__ void split_store(const GemmArgs& g, const f32x16t (&acc)[2][NJ], int m0, int n0, int lane) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int gm = m0 + 32 * i + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5), gn = n0 + 32 * j + (lane & 31);
+                if (!GUARD || (gm < g.M && gn < g.N)) {
+                    float* c = g.C + (int64_t)gm * g.ldc + gn;
+                    *c = g.accumulate ? *c + acc[i][j][r] : acc[i][j][r];
+                }
+            }
+}
+
+template <class Split, int T, bool A_KFAST, bool B_KFAST, bool GUARD>
+static __device__ __forceinline__ void sgemm_split_body(GemmArgs g) {
+    typedef SplitTile<T> Tile;
+    constexpr int NV = Tile::NV, NJ = Tile::NJ, NOP = Tile::OPERANDS;
+    constexpr int BUF = 2 * Split::PLANES * Tile::PLANE;            // A planes, then B planes
+    extern __shared__ __attribute__((aligned(16))) unsigned char sgemm_split_lds[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, t = tid & 255;
+    const int m0 = blockIdx.y * T, n0 = blockIdx.x * T;
+    const int wm = (wave >> 1) * 64, wn = (wave & 1) * 32 * NJ;
+    f32x16t acc[2][NJ];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    const int kbeg = blockIdx.z * g.kchunk, kend = min(g.K, kbeg + g.kchunk);
+    g.C += (int64_t)blockIdx.z * g.M * g.ldc;
+    const SplitOperand opa = {g.A, g.sAm, g.sAk, g.M, m0, A_KFAST, 0};
+    const SplitOperand opb = {g.B, g.sBn, g.sBk, g.N, n0, B_KFAST, Split::PLANES * Tile::PLANE};
+    SplitOperand op[NOP];
+    if constexpr (NOP == 2) { op[0] = opa; op[1] = opb; }
+    else op[0] = tid >= 256 ? opb : opa;
+    f32x4t rr[NOP][NV];
+    auto fetch = [&](int k0) {
+#pragma unroll
+        for (int e = 0; e < NV; ++e)
+#pragma unroll
+            for (int o = 0; o < NOP; ++o) rr[o][e] = split_fetch<T, GUARD>(op[o], t, e, k0, kend);
+    };
+    auto stash = [&](int buf, const f32x4t (&v)[NOP][NV]) {
+#pragma unroll
+        for (int o = 0; o < NOP; ++o) split_stash<Split, T>(sgemm_split_lds + buf * BUF + op[o].plane0, v[o], t, op[o].kfast);
+    };
+    // Software pipeline, two K steps deep: while the matrix cores work on tile k (LDS buffer `buf`), the registers loaded during the
+    // PREVIOUS iteration (tile k + 1: a full iteration of latency cover) are split and written to the other buffer, and the loads of
+    // tile k + 2 are issued.  The split's VALU work is interleaved with the MFMAs by the scheduling hints at the end of the loop body: an
+    // in-order wavefront hides ~5 other instructions behind each 32-cycle MFMA, or none at all if they sit behind the whole chain.
+    int buf = 0;
+    if (kbeg < kend) {
+        fetch(kbeg);
+        stash(0, rr);
+        fetch(kbeg + 16);                     // tile 1 (past the end the guarded loads return zeros)
+    }
+    __syncthreads();
+    for (int k0 = kbeg; k0 < kend; k0 += 16) {
+        const bool more = k0 + 16 < kend;
+        f32x4t nn[NOP][NV];
+#pragma unroll
+        for (int o = 0; o < NOP; ++o)
+#pragma unroll
+            for (int e = 0; e < NV; ++e) nn[o][e] = rr[o][e];                  // tile k + 1, loaded one iteration ago
+        if (k0 + 32 < kend) fetch(k0 + 32);                                    // tile k + 2 into rr
+        split_products<Split, T, A_KFAST, B_KFAST>(sgemm_split_lds + buf * BUF, wm, wn, lane, acc);
+        if (more) stash(buf ^ 1, nn);
+#pragma unroll
+        for (int q = 0; q < Tile::template MFMAS<Split>; ++q) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                                       // one MFMA
+            __builtin_amdgcn_sched_group_barrier(0x002, Tile::template LADDER_VALU<Split>, 0);       // VALU (the split)
+            __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);                                       // one LDS write
+        }
+        __syncthreads();
+        buf ^= 1;
+    }
+    split_store<NJ, GUARD>(g, acc, m0 + wm, n0 + wn, lane);
+}
+
+// interior tiles take the body without bounds checks
+template <class Split, int T, bool A_KFAST, bool B_KFAST>
+static __device__ __forceinline__ void sgemm_split_tile(GemmArgs g) {
+    const int kbeg = blockIdx.z * g.kchunk, kend = min(g.K, kbeg + g.kchunk);
+    const bool interior = (int)blockIdx.y * T + T <= g.M && (int)blockIdx.x * T + T <= g.N && kend > kbeg;
+    if (interior) sgemm_split_body<Split, T, A_KFAST, B_KFAST, false>(g);
+    else sgemm_split_body<Split, T, A_KFAST, B_KFAST, true>(g);
+}
+
+template <bool A_KFAST, bool B_KFAST>
+static __global__ __launch_bounds__(256, 2) void sgemm_bf16x3_kernel(GemmArgs g) { sgemm_split_tile<SplitBf16x3, 128, A_KFAST, B_KFAST>(g); }
+template <bool A_KFAST, bool B_KFAST>
+static __global__ __launch_bounds__(512) void sgemm_bf16x3v_kernel(GemmArgs g) { sgemm_split_tile<SplitBf16x3, 256, A_KFAST, B_KFAST>(g); }
+// ------------------------------------------------------------------------------------------------
+// The two f16 x 2 kernels keep bodies of their own (the shared body was measured 1.2-2.5 % slower on them, cause not found:
+// profiles/r16_sgemm_split_body.md); same tiles, LDS layout (two planes: 96 KB double-buffered at 256) and pipeline as above.
+// ------------------------------------------------------------------------------------------------
 template <bool A_KFAST, bool B_KFAST, bool GUARD>
 static __device__ __forceinline__ void sgemm_f16x2v_body(GemmArgs g) {
     constexpr int T = 256;                         // tile rows / columns
@@ -798,17 +716,12 @@ static __device__ __forceinline__ void sgemm_f16x2v_body(GemmArgs g) {
                 for (int i = 0; i < 2; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[i][PA[tt]], bb[PB[tt]], acc[i][j], 0, 0, 0);
         }
         if (more) stash(sgemm_x3_lds + (buf ^ 1) * BUF, nn);
-#ifndef F16X2_VALU
-#define F16X2_VALU 4
-#endif
-#if F16X2_VALU > 0
 #pragma unroll
         for (int q = 0; q < 24; ++q) {
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            __builtin_amdgcn_sched_group_barrier(0x002, F16X2_VALU, 0);
+            __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
             __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
         }
-#endif
         __syncthreads();
         buf ^= 1;
     }
@@ -840,7 +753,7 @@ static __global__ __launch_bounds__(512) void sgemm_f16x2v_kernel(GemmArgs g) {
 template <bool A_KFAST, bool B_KFAST, bool GUARD>
 static __device__ __forceinline__ void sgemm_f16x2_body(GemmArgs g) {
     constexpr int ROWB = 48;                       // bytes per LDS row of the k-contiguous form
-    constexpr int PLANE = 128 * ROWB;              // one bf16 plane of one operand tile
+    constexpr int PLANE = 128 * ROWB;              // one f16 plane of one operand tile
     constexpr int BUF = 4 * PLANE;                 // A: h, l ; B: h, l
     extern __shared__ __attribute__((aligned(16))) unsigned char sgemm_x3_lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1042,10 +955,7 @@ static inline bool sgemm_wide_ok(const GemmArgs& g, int slices) {
     return (int64_t)((g.M + 255) / 256) * ((g.N + 255) / 256) * slices >= 160;
 }
 
-// process-wide arithmetic of the big-tile GEMM: 1 = bf16 x 3 (default), 0 = fp32 matrix instructions (bit-compatible with the 64x64 kernel)
-// (defined once, in rulgnn_api.hip: this header is included by several translation units)
-int& sgemm_big_mode();
-
+// (sgemm_big_mode(), the process-wide arithmetic of the big-tile GEMM: declared in sgemm_mfma.hpp, defined in rulgnn_api.hip)
 constexpr int SGEMM_BIG_KT = 16;      // k depth of an LDS stage of the 128x128 kernel
 // the 128x128 kernel pays when both output dimensions fill most of a tile and there are enough tiles for the chip
 static inline bool sgemm_big_ok(const GemmArgs& g, int slices) {
@@ -1059,52 +969,35 @@ static inline bool sgemm_big_ok(const GemmArgs& g, int slices) {
     return g.kchunk % 4 == 0;
 }
 
+// f(a, b) with a, b = std::bool_constant of (ak, bk): picks the <A_KFAST, B_KFAST> instance of a kernel from the operands' layouts
+template <class F>
+static inline int sgemm_with_kfast(bool ak, bool bk, F&& f) {
+    if (ak && bk) return f(std::true_type{}, std::true_type{});
+    if (ak) return f(std::true_type{}, std::false_type{});
+    if (bk) return f(std::false_type{}, std::true_type{});
+    return f(std::false_type{}, std::false_type{});
+}
+
 // the matrix-core GEMM of a (possibly split-K) problem: the 128x128 kernel where it pays, the 64x64 one otherwise.  RULGNN_EHIP when
 // the runtime refuses a kernel its LDS; the caller reads the launch's own error afterwards.
 static inline int sgemm_launch_tiles(const GemmArgs& g, int slices, hipStream_t st) {
-    auto go = [&](auto kernel, dim3 grid, int threads, size_t lds) -> int {
+    auto go = [&](auto kernel, int tile, int threads, size_t lds) -> int {
         if (const int rc = allow_dynamic_lds(kernel, lds); rc != RULGNN_OK) return rc;
-        hipLaunchKernelGGL(kernel, grid, dim3(threads), lds, st, g);
+        hipLaunchKernelGGL(kernel, dim3((g.N + tile - 1) / tile, (g.M + tile - 1) / tile, slices), dim3(threads), lds, st, g);
         return RULGNN_OK;
     };
     if (sgemm_big_ok(g, slices)) {
-        const dim3 grid((g.N + 127) / 128, (g.M + 127) / 128, slices);
-        const bool ak = g.sAk == 1, bk = g.sBk == 1;
-        if (sgemm_big_mode() >= 1) {                                 // (1: bf16 x 3, f16 x 2 where the caller passes scales; 2: bf16 x 3 only)
-            const bool f16 = g.amax_a && g.amax_b && sgemm_big_mode() == 1;
-            if (sgemm_wide_ok(g, slices)) {
-                const dim3 wgrid((g.N + 255) / 256, (g.M + 255) / 256, slices);
-                if (f16) {
-                    constexpr size_t lh = (size_t)2 * 4 * 256 * 48;
-                    if (ak && bk) return go(sgemm_f16x2v_kernel<true, true>, wgrid, 512, lh);
-                    if (ak) return go(sgemm_f16x2v_kernel<true, false>, wgrid, 512, lh);
-                    if (bk) return go(sgemm_f16x2v_kernel<false, true>, wgrid, 512, lh);
-                    return go(sgemm_f16x2v_kernel<false, false>, wgrid, 512, lh);
-                }
-                constexpr size_t lw = (size_t)2 * 6 * 256 * 48;
-                if (ak && bk) return go(sgemm_bf16x3v_kernel<true, true>, wgrid, 512, lw);
-                if (ak) return go(sgemm_bf16x3v_kernel<true, false>, wgrid, 512, lw);
-                if (bk) return go(sgemm_bf16x3v_kernel<false, true>, wgrid, 512, lw);
-                return go(sgemm_bf16x3v_kernel<false, false>, wgrid, 512, lw);
-            }
-            if (f16) {
-                constexpr size_t l2 = (size_t)2 * 4 * 128 * 48;
-                if (ak && bk) return go(sgemm_f16x2_kernel<true, true>, grid, 256, l2);
-                if (ak) return go(sgemm_f16x2_kernel<true, false>, grid, 256, l2);
-                if (bk) return go(sgemm_f16x2_kernel<false, true>, grid, 256, l2);
-                return go(sgemm_f16x2_kernel<false, false>, grid, 256, l2);
-            }
-            constexpr size_t lx = (size_t)2 * 6 * 128 * 48;
-            if (ak && bk) return go(sgemm_bf16x3_kernel<true, true>, grid, 256, lx);
-            if (ak) return go(sgemm_bf16x3_kernel<true, false>, grid, 256, lx);
-            if (bk) return go(sgemm_bf16x3_kernel<false, true>, grid, 256, lx);
-            return go(sgemm_bf16x3_kernel<false, false>, grid, 256, lx);
-        }
-        constexpr size_t lds = (size_t)4 * SGEMM_BIG_KT * (128 + 16) * sizeof(float);
-        if (ak && bk) return go(sgemm_mfma128_kernel<true, true, SGEMM_BIG_KT>, grid, 256, lds);
-        if (ak) return go(sgemm_mfma128_kernel<true, false, SGEMM_BIG_KT>, grid, 256, lds);
-        if (bk) return go(sgemm_mfma128_kernel<false, true, SGEMM_BIG_KT>, grid, 256, lds);
-        return go(sgemm_mfma128_kernel<false, false, SGEMM_BIG_KT>, grid, 256, lds);
+        const int mode = sgemm_big_mode();                           // (1: bf16 x 3, f16 x 2 where the caller passes scales; 2: bf16 x 3 only)
+        const bool f16 = g.amax_a && g.amax_b && mode == 1, wide = sgemm_wide_ok(g, slices);
+        return sgemm_with_kfast(g.sAk == 1, g.sBk == 1, [&](auto ak, auto bk) -> int {
+            constexpr bool AK = decltype(ak)::value, BK = decltype(bk)::value;
+            constexpr int T128 = SplitTile<128>::THREADS, T256 = SplitTile<256>::THREADS;
+            if (mode < 1) return go(sgemm_mfma128_kernel<AK, BK, SGEMM_BIG_KT>, 128, 256, (size_t)4 * SGEMM_BIG_KT * (128 + 16) * sizeof(float));
+            if (wide) return f16 ? go(sgemm_f16x2v_kernel<AK, BK>, 256, T256, lds_bytes<2, 256>())
+                                 : go(sgemm_bf16x3v_kernel<AK, BK>, 256, T256, lds_bytes<SplitBf16x3::PLANES, 256>());
+            return f16 ? go(sgemm_f16x2_kernel<AK, BK>, 128, T128, lds_bytes<2, 128>())
+                       : go(sgemm_bf16x3_kernel<AK, BK>, 128, T128, lds_bytes<SplitBf16x3::PLANES, 128>());
+        });
     }
     hipLaunchKernelGGL(sgemm_mfma_kernel, dim3((g.N + 63) / 64, (g.M + 63) / 64, slices), dim3(256), 0, st, g);
     return RULGNN_OK;

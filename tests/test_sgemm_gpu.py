@@ -1,5 +1,7 @@
-"""The fp32 matrix-core GEMM (csrc/sgemm_mfma.hpp: 64x64 and 128x128 tile kernels, generic strides) against numpy fp64 (GPU)."""
+"""The fp32 matrix-core GEMM (csrc/sgemm.hip: the 64x64 tile kernel and the 128 / 256 large-tile kernels, generic strides; interface
+csrc/sgemm_mfma.hpp) against numpy fp64 (GPU)."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -136,7 +138,7 @@ def test_splitk_weight_gradient_matches_numpy(M, N, K, layout, colsum):
     assert np.array_equal(got, got2) and (not colsum or np.array_equal(cs, cs2))
 
 
-def run_scaled(A, B, M, N, K, a_layout, b_layout, nparts=(37, 5)):
+def run_scaled(A, B, M, N, K, a_layout, b_layout, nparts=(37, 5), accumulate=False, C0=None):
     """rulgnn_sgemm_scaled_f32 with the operand scale rows from rulgnn_absmax_partials_f32 (A: logical [M, K], B: logical [N, K])."""
     from gnn_rul_benchmarking_amd import _lib
     lib = _lib.load()
@@ -144,13 +146,13 @@ def run_scaled(A, B, M, N, K, a_layout, b_layout, nparts=(37, 5)):
     Bt = torch.from_numpy(np.ascontiguousarray(B if b_layout == "k" else B.T)).to(DEV)
     sAm, sAk = (K, 1) if a_layout == "k" else (1, M)
     sBn, sBk = (K, 1) if b_layout == "k" else (1, N)
-    Ct = torch.zeros(M, N, device=DEV)
+    Ct = torch.zeros(M, N, device=DEV) if C0 is None else torch.from_numpy(C0.copy()).to(DEV)
     pa, pb = torch.zeros(nparts[0], device=DEV), torch.zeros(nparts[1], device=DEV)
     st = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     _lib.check(lib.rulgnn_absmax_partials_f32(At.data_ptr(), At.numel(), pa.data_ptr(), nparts[0], st), "absmax")
     _lib.check(lib.rulgnn_absmax_partials_f32(Bt.data_ptr(), Bt.numel(), pb.data_ptr(), nparts[1], st), "absmax")
-    _lib.check(lib.rulgnn_sgemm_scaled_f32(At.data_ptr(), sAm, sAk, Bt.data_ptr(), sBn, sBk, Ct.data_ptr(), N, M, N, K, 0, pa.data_ptr(), nparts[0],
-                                           pb.data_ptr(), nparts[1], st), "sgemm_scaled")
+    _lib.check(lib.rulgnn_sgemm_scaled_f32(At.data_ptr(), sAm, sAk, Bt.data_ptr(), sBn, sBk, Ct.data_ptr(), N, M, N, K, 1 if accumulate else 0,
+                                           pa.data_ptr(), nparts[0], pb.data_ptr(), nparts[1], st), "sgemm_scaled")
     return Ct.cpu().numpy(), pa.cpu().numpy(), pb.cpu().numpy()
 
 
@@ -212,6 +214,91 @@ def test_bf16x3_only_mode_ignores_the_operand_scales():
     scaled, _, _ = run_scaled(A, B, M, N, K, "k", "k")
     assert np.array_equal(only, plain)
     assert not np.array_equal(scaled, plain) and np.abs(scaled - plain).max() < 1e-5 * np.abs(plain).max()
+
+
+# ---- the four split-precision large-tile kernels of csrc/sgemm.hip (sgemm_split_body for bf16 x 3, the f16 x 2 bodies) ---------------------
+# The smallest shapes the dispatch rules (sgemm_big_ok / sgemm_wide_ok) send to each tile.  128: 2 x 49 = 98 tiles of 128 (>= 96) and only
+# 25 of 256 (< 160); the second tile row and the last tile column are edge tiles, the rest interior.  256: 3 x 54 = 162 tiles of 256
+# (>= 160); the last tile row and column are edge tiles.  K = 52: K steps of 16, 16, 16 and 4.  M, N, K multiples of 4: every layout passes
+# sgemm_big_ok.  The plain entry runs the three-plane bf16 split (sgemm_bf16x3_kernel / sgemm_bf16x3v_kernel), the scaled entry the
+# two-plane f16 split (sgemm_f16x2_kernel / sgemm_f16x2v_kernel).
+SPLIT_BODY_SHAPES = {128: (200, 6184, 52), 256: (520, 13668, 52)}
+LAYOUTS = [("k", "k"), ("k", "r"), ("r", "k"), ("r", "r")]
+
+
+@functools.lru_cache(maxsize=None)
+def _split_body_case(tile):
+    """Operands and fp64 references of one tile's shape, computed once and shared (read-only) by the tests below."""
+    M, N, K = SPLIT_BODY_SHAPES[tile]
+    rng = np.random.default_rng(M + N + K)
+    A = rng.standard_normal((M, K)).astype(np.float32)
+    B = rng.standard_normal((N, K)).astype(np.float32)
+    C0 = rng.standard_normal((M, N)).astype(np.float32)
+    Ai = rng.integers(-300, 300, (M, K)).astype(np.float32)
+    Bi = rng.integers(-300, 300, (N, K)).astype(np.float32)
+    case = dict(A=A, B=B, C0=C0, ref=A.astype(np.float64) @ B.astype(np.float64).T, Ai=Ai, Bi=Bi,
+                exact=Ai.astype(np.float64) @ Bi.astype(np.float64).T)
+    for v in case.values():
+        v.setflags(write=False)
+    return case
+
+
+@pytest.mark.parametrize("a_layout,b_layout", LAYOUTS)
+@pytest.mark.parametrize("tile", [128, 256])
+def test_split_body_bf16x3_kernels_match_numpy(tile, a_layout, b_layout):
+    M, N, K = SPLIT_BODY_SHAPES[tile]
+    c = _split_body_case(tile)
+    got = run(c["A"], c["B"], M, N, K, a_layout, b_layout)
+    err = np.abs(got - c["ref"]).max()
+    print(f"bf16x3 tile {tile} {a_layout}{b_layout}: max |err| {err:.3e} (max |ref| {np.abs(c['ref']).max():.3e})")
+    assert err < 2e-6 * np.sqrt(K) * np.abs(c["ref"]).max() + 1e-6
+    got = run(c["A"], c["B"], M, N, K, a_layout, b_layout, accumulate=True, C0=c["C0"])
+    assert np.abs(got - (c["ref"] + c["C0"])).max() < 2e-6 * np.sqrt(K) * np.abs(c["ref"]).max() + 1e-5
+
+
+@pytest.mark.parametrize("a_layout,b_layout", LAYOUTS)
+@pytest.mark.parametrize("tile", [128, 256])
+def test_split_body_f16x2_kernels_match_numpy(tile, a_layout, b_layout):
+    """(the bound test_presplit_product_tile_forms_and_short_k applies to the same two-plane f16 arithmetic)"""
+    M, N, K = SPLIT_BODY_SHAPES[tile]
+    c = _split_body_case(tile)
+    got, pa, pb = run_scaled(c["A"], c["B"], M, N, K, a_layout, b_layout)
+    assert pa.max() == np.abs(c["A"]).max() and pb.max() == np.abs(c["B"]).max()
+    err = np.abs(got - c["ref"]).max()
+    print(f"f16x2 tile {tile} {a_layout}{b_layout}: max |err| {err:.3e} (max |ref| {np.abs(c['ref']).max():.3e})")
+    assert err < 2e-6 * np.sqrt(K) * np.abs(c["ref"]).max() + 1e-6
+    got, _, _ = run_scaled(c["A"], c["B"], M, N, K, a_layout, b_layout, accumulate=True, C0=c["C0"])
+    assert np.abs(got - (c["ref"] + c["C0"])).max() < 2e-6 * np.sqrt(K) * np.abs(c["ref"]).max() + 1e-5
+
+
+@pytest.mark.parametrize("a_layout,b_layout", LAYOUTS)
+@pytest.mark.parametrize("tile", [128, 256])
+def test_split_body_integer_operands_come_out_exact(tile, a_layout, b_layout):
+    """|sum| <= 52 * 300^2 = 4.68e6 < 2^24: every partial sum is an exact fp32.  A 9-bit integer has a zero third bf16 part; after the
+    power-of-two operand scale it still has at most 11 significant bits, so its f16 lo part is zero: both splits are exact, in the
+    interior and in the edge tiles alike -- no tolerance."""
+    M, N, K = SPLIT_BODY_SHAPES[tile]
+    c = _split_body_case(tile)
+    assert np.array_equal(run(c["Ai"], c["Bi"], M, N, K, a_layout, b_layout), c["exact"])
+    got, _, _ = run_scaled(c["Ai"], c["Bi"], M, N, K, a_layout, b_layout)
+    assert np.array_equal(got, c["exact"])
+
+
+@pytest.mark.parametrize("layout", ["r", "k"])
+def test_splitk_slices_of_the_128_tile_kernel(layout):
+    """[256 x 256] over K = 6144: sgemm_splitk_slices gives 24 slices of 256 k (one 256 x 256 tile x 24 is below the wide kernel's 160),
+    4 tiles x 24 = 96 workgroups of sgemm_bf16x3_kernel, each slice z > 0 writing its own [M x N] block of the partial buffer, then the
+    fixed-order slice sum."""
+    M, N, K = 256, 256, 6144
+    rng = np.random.default_rng(M + N + K)
+    A = rng.standard_normal((M, K)).astype(np.float32)
+    B = rng.standard_normal((N, K)).astype(np.float32)
+    ref = A.astype(np.float64) @ B.astype(np.float64).T
+    got, _ = run_splitk(A, B, M, N, K, layout, layout, False)
+    assert np.isfinite(got).all()
+    assert np.abs(got - ref).max() < 2e-6 * np.sqrt(K) * max(np.abs(ref).max(), 1.0) + 1e-6
+    got2, _ = run_splitk(A, B, M, N, K, layout, layout, False)
+    assert np.array_equal(got, got2)
 
 
 # ---- the scaled product on PRE-SPLIT operands (csrc/sgemm_planes.hip: split pass + LDS-DMA product kernel; rulgnn_sgemm_scaled_ws_f32) -----
