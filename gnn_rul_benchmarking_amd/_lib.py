@@ -121,6 +121,15 @@ class SagcnArgs(C.Structure):
                 ("global_batch", C.c_int64)]
 
 
+class AgcntfShape(C.Structure):
+    _fields_ = [("batch", C.c_int64), ("num_patch", C.c_int32), ("patch_size", C.c_int32), ("hidden_adj_dim", C.c_int32),
+                ("hidden_gnn_dim", C.c_int32), ("num_heads", C.c_int32)]
+
+
+class AgcntfArgs(C.Structure):
+    _fields_ = list(SagcnArgs._fields_)
+
+
 class StagnnShape(C.Structure):
     _fields_ = [("batch", C.c_int64), ("num_nodes", C.c_int32), ("time_length", C.c_int32), ("hidden_dim", C.c_int32),
                 ("output_dim", C.c_int32), ("num_heads", C.c_int32), ("threshold", C.c_float)]
@@ -298,6 +307,12 @@ _SIGNATURES = {
     "rulgnn_gru_persistent_workspace_bytes": (C.c_size_t, [C.POINTER(GruShape)]),
     "rulgnn_gru_persistent_forward_f32": (C.c_int, [C.POINTER(GruShape), C.POINTER(GruArgs), C.c_void_p]),
     "rulgnn_gru_persistent_backward_f32": (C.c_int, [C.POINTER(GruShape), C.POINTER(GruArgs), C.c_void_p]),
+    "rulgnn_agcntf_param_count": (C.c_int64, [C.POINTER(AgcntfShape)]),
+    "rulgnn_agcntf_workspace_bytes": (C.c_size_t, [C.POINTER(AgcntfShape)]),
+    "rulgnn_agcntf_tap_offset": (C.c_int64, [C.POINTER(AgcntfShape), C.c_int32]),
+    "rulgnn_agcntf_forward_f32": (C.c_int, [C.POINTER(AgcntfShape), C.POINTER(AgcntfArgs), C.c_void_p]),
+    "rulgnn_agcntf_backward_f32": (C.c_int, [C.POINTER(AgcntfShape), C.POINTER(AgcntfArgs), C.c_void_p]),
+    "rulgnn_agcntf_fwdbwd_f32": (C.c_int, [C.POINTER(AgcntfShape), C.POINTER(AgcntfArgs), C.POINTER(AdamArgs), C.c_void_p]),
     "rulgnn_grucm_param_count": (C.c_int64, [C.POINTER(GrucmShape)]),
     "rulgnn_grucm_workspace_bytes": (C.c_size_t, [C.POINTER(GrucmShape)]),
     "rulgnn_grucm_forward_f32": (C.c_int, [C.POINTER(GrucmShape), C.POINTER(GrucmArgs), C.c_void_p]),
@@ -352,7 +367,7 @@ _SIGNATURES = {
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
 # index -> ctypes mirror, in the order of the RULGNN_STRUCT_* constants of include/rulgnn.h (rulgnn_struct_size)
-STRUCTS = (StgcnShape, StgcnTrainArgs, AdamArgs, StmsgcnShape, StmsgcnArgs, AstgcnnShape, AstgcnnArgs, FcstgnnShape, FcstgnnArgs, RgcnuShape, RgcnuArgs, StnetShape, StnetArgs, SagcnShape, SagcnArgs, StagnnShape, StagnnArgs, HagcnShape, HagcnArgs, BilstmShape, BilstmArgs, StconvShape, StgnnShape, GruShape, GruArgs, GrucmShape, GrucmArgs)
+STRUCTS = (StgcnShape, StgcnTrainArgs, AdamArgs, StmsgcnShape, StmsgcnArgs, AstgcnnShape, AstgcnnArgs, FcstgnnShape, FcstgnnArgs, RgcnuShape, RgcnuArgs, StnetShape, StnetArgs, SagcnShape, SagcnArgs, StagnnShape, StagnnArgs, HagcnShape, HagcnArgs, BilstmShape, BilstmArgs, StconvShape, StgnnShape, GruShape, GruArgs, GrucmShape, GrucmArgs, AgcntfShape, AgcntfArgs)
 
 _lib = None
 

@@ -3,7 +3,7 @@ algorithms/algorithms.py:29-48 does it (lookup by name in this module's globals,
 ``NotImplementedError("Algorithm not found: ...")`` otherwise).
 
 The ST_GCN (reference algorithms/algorithms.py:465-490), STMSGCN (:546-571), ASTGCNN (:139-163), FC_STGNN (:51-76), HAGCN (:222-248),
-ST_Conv (:195-220) and GRU_CM (:355-380) wrappers are implemented:
+ST_Conv (:195-220), GRU_CM (:355-380) and AGCN_TF (:574-599) wrappers are implemented:
 the hot paths this package accelerates.  The classes keep the reference contract -- constructor
 ``(configs, hparams, device)``, attributes ``model`` / ``optimizer`` / ``hparams`` / ``mse``,
 ``update(X, y, epoch) -> {'loss': float}`` -- so the reference's trainer can drive it unchanged."""
@@ -27,6 +27,7 @@ from .stgnn import STGNN_model
 from .stmsgcn import STMSGCN_model
 from .stnet import STNet_model
 from .sagcn import SAGCN_model
+from .agcntf import AGCN_TF_model
 from .stagnn import STAGNN_model
 
 
@@ -273,6 +274,14 @@ class SAGCN(_FusedAlgorithm):
     supports_graphs = False
 
 
+class AGCN_TF(_FusedAlgorithm):
+    """AGCN_TF training wrapper (reference algorithms.py:574-599; csrc/agcntf.hip on SAGCN's front end).  No recurrence, no BatchNorm, no
+    dropout: train and eval compute the same function, samples are independent and data parallelism is the plain ``[gradient | loss]``
+    bucket."""
+    model_class = AGCN_TF_model
+    supports_graphs = False
+
+
 class STAGNN(_FusedAlgorithm):
     """STAGNN training wrapper (reference algorithms.py:298-323; csrc/stagnn.hip): batch statistics in the four BatchNorm1d layers,
     running statistics updated inside the step.  Data parallelism: rank-local BatchNorm statistics."""
@@ -289,4 +298,4 @@ class GRU_CM(_FusedAlgorithm):
     needs_train_mode = "dropout"
 
 
-_NOT_ALGORITHMS = {"Algorithm", "GRU_CM_model", "FusedAdam", "RGCNU_model", "STNet_model", "SAGCN_model", "STAGNN_model", "ST_GCN_model", "STMSGCN_model", "ASTGCNN_model", "FC_STGNN_RUL", "HAGCN_model", "ST_Conv_model", "STGNN_model", "get_algorithm_class", "torch", "nn", "annotations", "math", "_lib", "deferred_weight_gradients"}
+_NOT_ALGORITHMS = {"Algorithm", "GRU_CM_model", "FusedAdam", "RGCNU_model", "STNet_model", "SAGCN_model", "AGCN_TF_model", "STAGNN_model", "ST_GCN_model", "STMSGCN_model", "ASTGCNN_model", "FC_STGNN_RUL", "HAGCN_model", "ST_Conv_model", "STGNN_model", "get_algorithm_class", "torch", "nn", "annotations", "math", "_lib", "deferred_weight_gradients"}

@@ -79,6 +79,12 @@ int64_t sagcn_param_count(const rulgnn_sagcn_shape* s);
 size_t sagcn_workspace_bytes(const rulgnn_sagcn_shape* s);
 int64_t sagcn_tap_offset(const rulgnn_sagcn_shape* s, int which);
 int sagcn_run(const rulgnn_sagcn_shape* s, const rulgnn_sagcn_args* a, int mode, hipStream_t st);
+// SAGCN's parameter-free front end alone: x [B][P * n] -> raw [B * P][20] (scratch) -> features [B][P][40] (unit Frobenius norm)
+int sagcn_features(int64_t B, int P, int n, const float* x, float* raw, float* feat, hipStream_t st);
+int64_t agcntf_param_count(const rulgnn_agcntf_shape* s);
+size_t agcntf_workspace_bytes(const rulgnn_agcntf_shape* s);
+int64_t agcntf_tap_offset(const rulgnn_agcntf_shape* s, int which);
+int agcntf_run(const rulgnn_agcntf_shape* s, const rulgnn_agcntf_args* a, int mode, hipStream_t st);
 int64_t stagnn_param_count(const rulgnn_stagnn_shape* s);
 int64_t stagnn_bn_state_count(const rulgnn_stagnn_shape* s);
 size_t stagnn_workspace_bytes(const rulgnn_stagnn_shape* s);

@@ -302,6 +302,8 @@ size_t rulgnn_struct_size(int32_t which) {
     case RULGNN_STRUCT_GRU_ARGS: return sizeof(rulgnn_gru_args);
     case RULGNN_STRUCT_GRUCM_SHAPE: return sizeof(rulgnn_grucm_shape);
     case RULGNN_STRUCT_GRUCM_ARGS: return sizeof(rulgnn_grucm_args);
+    case RULGNN_STRUCT_AGCNTF_SHAPE: return sizeof(rulgnn_agcntf_shape);
+    case RULGNN_STRUCT_AGCNTF_ARGS: return sizeof(rulgnn_agcntf_args);
     default: return 0;
     }
 }
@@ -871,6 +873,35 @@ int rulgnn_sagcn_fwdbwd_f32(const rulgnn_sagcn_shape* shape, const rulgnn_sagcn_
     RULGNN_TRY(check_sagcn(shape, args, true));
     auto run = [&](hipStream_t st) { return sagcn_run(shape, args, 3, st); };
     return fused_step_tail(args->dpred, !args->y && shape->batch > 0, opt, args->params, run, args->grads, 0, sagcn_param_count(shape), stream);
+}
+
+// ---- AGCN_TF --------------------------------------------------------------------------------------------------------------------
+int64_t rulgnn_agcntf_param_count(const rulgnn_agcntf_shape* shape) { return agcntf_param_count(shape); }
+size_t rulgnn_agcntf_workspace_bytes(const rulgnn_agcntf_shape* shape) { return agcntf_workspace_bytes(shape); }
+int64_t rulgnn_agcntf_tap_offset(const rulgnn_agcntf_shape* shape, int32_t which) { return agcntf_tap_offset(shape, which); }
+
+static int check_agcntf(const rulgnn_agcntf_shape* shape, const rulgnn_agcntf_args* a, bool bwd) {
+    if (!shape || !a) return RULGNN_EINVAL;
+    if (agcntf_param_count(shape) < 0) return RULGNN_EUNSUPPORTED;
+    return check_step_ptrs(a->params, a->workspace, a->x, a->pred, a->grads, a->y, a->dpred, shape->batch, bwd);
+}
+
+int rulgnn_agcntf_forward_f32(const rulgnn_agcntf_shape* shape, const rulgnn_agcntf_args* args, void* stream) {
+    const int rc = check_agcntf(shape, args, false);
+    if (rc != RULGNN_OK) return rc;
+    return agcntf_run(shape, args, 1, static_cast<hipStream_t>(stream));
+}
+
+int rulgnn_agcntf_backward_f32(const rulgnn_agcntf_shape* shape, const rulgnn_agcntf_args* args, void* stream) {
+    const int rc = check_agcntf(shape, args, true);
+    if (rc != RULGNN_OK) return rc;
+    return agcntf_run(shape, args, 2, static_cast<hipStream_t>(stream));
+}
+
+int rulgnn_agcntf_fwdbwd_f32(const rulgnn_agcntf_shape* shape, const rulgnn_agcntf_args* args, const rulgnn_adam_args* opt, void* stream) {
+    RULGNN_TRY(check_agcntf(shape, args, true));
+    auto run = [&](hipStream_t st) { return agcntf_run(shape, args, 3, st); };
+    return fused_step_tail(args->dpred, !args->y && shape->batch > 0, opt, args->params, run, args->grads, 0, agcntf_param_count(shape), stream);
 }
 
 int rulgnn_sgemm_mode(int32_t mode) {

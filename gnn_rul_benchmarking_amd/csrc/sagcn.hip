@@ -254,6 +254,56 @@ __global__ __launch_bounds__(TBS) void sg_patch_features_kernel(SgGeom g, const 
     }
 }
 
+// ---- the 40 columns of one sample (Model.py:6-14, 66-69): the 20 statistics, their cumulative form along the patches, the whole
+// [P, 40] block scaled to unit Frobenius norm.  One implementation for every kernel that needs the block (the two graph kernels below and
+// sg_features_kernel, which AGCN_TF's front end runs: csrc/agcntf.hip).  Fl: [P][SG_F + 1] in LDS; red: GB floats.
+// The running sums are a sequential fp64 chain per feature (c / sqrt|c| amplifies their rounding near the zero crossings).  With `cs`
+// ([P][SG_RAW] doubles of LDS scratch) only the additions stay on that chain: the square roots and divisions -- 128 dependent fp64 pairs on
+// 20 threads otherwise -- are taken by all threads afterwards; the values are the same either way.  Ends behind a barrier.
+__device__ __forceinline__ void sg_cum_norm(int P, const float* __restrict__ raw, float* Fl, float* __restrict__ feat, float* red, double* cs) {
+    constexpr int LD = SG_F + 1;
+    const int tid = threadIdx.x;
+    if (tid < SG_RAW) {
+        double c = 0.0;
+        for (int p = 0; p < P; ++p) {
+            const float v = raw[p * SG_RAW + tid];
+            c += (double)v;
+            Fl[p * LD + tid] = v;
+            if (cs) cs[p * SG_RAW + tid] = c;
+            else Fl[p * LD + SG_RAW + tid] = (float)(c / sqrt(fmax(fabs(c), 1e-12)));
+        }
+    }
+    __syncthreads();
+    if (cs) {
+        for (int i = tid; i < P * SG_RAW; i += GB) {
+            const double c = cs[i];
+            Fl[(i / SG_RAW) * LD + SG_RAW + i % SG_RAW] = (float)(c / sqrt(fmax(fabs(c), 1e-12)));
+        }
+        __syncthreads();
+    }
+    float q[1] = {0.f};
+    for (int i = tid; i < P * SG_F; i += GB) { const float v = Fl[(i / SG_F) * LD + i % SG_F]; q[0] = fmaf(v, v, q[0]); }
+    block_sum<1>(q, red);
+    const float inv = 1.0f / sqrtf(q[0]);
+    for (int i = tid; i < P * SG_F; i += GB) {
+        const float v = Fl[(i / SG_F) * LD + i % SG_F] * inv;
+        Fl[(i / SG_F) * LD + i % SG_F] = v;
+        feat[i] = v;
+    }
+    __syncthreads();
+}
+
+// the block alone: features [B][P][40] from the statistics.  dynamic LDS: F[P][41] | red[GB]
+__global__ __launch_bounds__(GB) void sg_features_kernel(int64_t B, int P, const float* __restrict__ raw, float* __restrict__ feat) {
+    extern __shared__ float lds[];
+    float* F = lds;
+    float* red = F + P * (SG_F + 1);
+    for (int64_t b = blockIdx.x; b < B; b += gridDim.x) {
+        __syncthreads();
+        sg_cum_norm(P, raw + b * P * SG_RAW, F, feat + b * P * SG_F, red, nullptr);
+    }
+}
+
 // ---- kernel 2: one workgroup per sample: cumulative columns, unit norm, cosine adjacency, A_hat X (Model.py:6-14, 66-79, 86-91) --
 // dynamic LDS: F[P][41] | nrm[P] | dinv[P] | red[GB]
 __global__ __launch_bounds__(GB) void sg_graph_kernel(SgGeom g, const float* __restrict__ raw, float* __restrict__ feat,
@@ -267,26 +317,7 @@ __global__ __launch_bounds__(GB) void sg_graph_kernel(SgGeom g, const float* __r
     float* red = dinv + P;
     for (int64_t b = blockIdx.x; b < g.B; b += gridDim.x) {
         __syncthreads();
-        if (tid < SG_RAW) {
-            double c = 0.0;                                           // c / sqrt|c| amplifies the running sum's rounding near its zero crossings
-            for (int p = 0; p < P; ++p) {
-                const float v = raw[(b * P + p) * SG_RAW + tid];
-                c += (double)v;
-                F[p * LD + tid] = v;
-                F[p * LD + SG_RAW + tid] = (float)(c / sqrt(fmax(fabs(c), 1e-12)));
-            }
-        }
-        __syncthreads();
-        float q[1] = {0.f};
-        for (int i = tid; i < P * SG_F; i += GB) { const float v = F[(i / SG_F) * LD + i % SG_F]; q[0] = fmaf(v, v, q[0]); }
-        block_sum<1>(q, red);
-        const float inv = 1.0f / sqrtf(q[0]);
-        for (int i = tid; i < P * SG_F; i += GB) {
-            const float v = F[(i / SG_F) * LD + i % SG_F] * inv;
-            F[(i / SG_F) * LD + i % SG_F] = v;
-            feat[b * P * SG_F + i] = v;
-        }
-        __syncthreads();
+        sg_cum_norm(P, raw + b * P * SG_RAW, F, feat + b * P * SG_F, red, nullptr);
         for (int p = tid; p < P; p += GB) {
             float a = 0.f;
             for (int f = 0; f < SG_F; ++f) a = fmaf(F[p * LD + f], F[p * LD + f], a);
@@ -348,34 +379,8 @@ __global__ __launch_bounds__(GB) void sg_graph_mx_kernel(SgGeom g, const float* 
     float* Cm = red + GB;
     for (int64_t b = blockIdx.x; b < g.B; b += gridDim.x) {
         __syncthreads();
-        // the running sums stay a sequential fp64 chain per feature (c / sqrt|c| amplifies their rounding near the zero crossings), but only the
-        // additions: the square roots and divisions -- 128 dependent fp64 pairs on 20 threads before -- are taken by all threads afterwards
-        double* cs = reinterpret_cast<double*>(Cm);                   // [P][SG_RAW], over the (not yet used) C tile; 8-byte aligned: every term above is even
-        if (tid < SG_RAW) {
-            double c = 0.0;
-            for (int p = 0; p < P; ++p) {
-                const float v = raw[(b * P + p) * SG_RAW + tid];
-                c += (double)v;
-                F[p * LD + tid] = v;
-                cs[p * SG_RAW + tid] = c;
-            }
-        }
-        __syncthreads();
-        for (int i = tid; i < P * SG_RAW; i += GB) {
-            const double c = cs[i];
-            F[(i / SG_RAW) * LD + SG_RAW + i % SG_RAW] = (float)(c / sqrt(fmax(fabs(c), 1e-12)));
-        }
-        __syncthreads();
-        float q[1] = {0.f};
-        for (int i = tid; i < P * SG_F; i += GB) { const float v = F[(i / SG_F) * LD + i % SG_F]; q[0] = fmaf(v, v, q[0]); }
-        block_sum<1>(q, red);
-        const float inv = 1.0f / sqrtf(q[0]);
-        for (int i = tid; i < P * SG_F; i += GB) {
-            const float v = F[(i / SG_F) * LD + i % SG_F] * inv;
-            F[(i / SG_F) * LD + i % SG_F] = v;
-            feat[b * P * SG_F + i] = v;
-        }
-        __syncthreads();
+        // (the fp64 running sums [P][SG_RAW] sit over the not yet used C tile; 8-byte aligned: every term above is even)
+        sg_cum_norm(P, raw + b * P * SG_RAW, F, feat + b * P * SG_F, red, reinterpret_cast<double*>(Cm));
         for (int p = tid; p < P; p += GB) {
             float a = 0.f;
             for (int f = 0; f < SG_F; ++f) a = fmaf(F[p * LD + f], F[p * LD + f], a);
@@ -604,6 +609,17 @@ __global__ void sg_fcw_kernel(SgGeom g, const float* __restrict__ attn, const fl
     }
 }
 
+// the 20 statistics of every patch: g.R, g.n, g.nh are read
+inline void sg_launch_patch_features(const SgGeom& g, const float* x, float* raw, hipStream_t st) {
+    if (g.n <= 64) {
+        const size_t lw = sizeof(float) * ((size_t)3 * g.n + g.nh + 7 * 64);
+        hipLaunchKernelGGL(sg_patch_features_kernel<64>, dim3((unsigned)(g.R < 65536 ? g.R : 65536)), dim3(64), lw, st, g, x, raw);
+    } else {
+        const size_t lds1 = sizeof(float) * ((size_t)3 * g.n + g.nh + 7 * GB);
+        hipLaunchKernelGGL(sg_patch_features_kernel<GB>, dim3((unsigned)(g.R < 16384 ? g.R : 16384)), dim3(GB), lds1, st, g, x, raw);
+    }
+}
+
 inline unsigned sg_grid(int64_t n) {
     int64_t b = (n + GB - 1) / GB;
     return (unsigned)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
@@ -631,6 +647,21 @@ int64_t sagcn_tap_offset(const rulgnn_sagcn_shape* s, int which) {
         case 3: return g.w_attn;
         default: return -1;
     }
+}
+
+// x [B][P * n] -> raw [B * P][20] (scratch) -> features [B][P][40]: SAGCN's parameter-free front end for another family's host
+// (1 <= P <= 256, 2 <= n <= 2048: RULGNN_EUNSUPPORTED beyond, before any launch)
+int sagcn_features(int64_t B, int P, int n, const float* x, float* raw, float* feat, hipStream_t st) {
+    if (B < 0 || P < 1 || n < 2) return RULGNN_EINVAL;
+    if (P > SG_MAXP || n > SG_MAXN) return RULGNN_EUNSUPPORTED;
+    if (B == 0) return RULGNN_OK;
+    SgGeom g{};
+    g.B = B; g.P = P; g.n = n; g.nh = n / 2 + 1; g.R = B * P;
+    (void)hipGetLastError();
+    sg_launch_patch_features(g, x, raw, st);
+    hipLaunchKernelGGL(sg_features_kernel, dim3((unsigned)(B < 4096 ? B : 4096)), dim3(GB), sizeof(float) * ((size_t)P * (SG_F + 1) + GB), st, B, P,
+                       (const float*)raw, feat);
+    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
 }
 
 #define SG_LAUNCH_OK()                                           \
@@ -661,11 +692,7 @@ int sagcn_run(const rulgnn_sagcn_shape* s, const rulgnn_sagcn_args* a, int mode,
         const size_t lds1 = sizeof(float) * ((size_t)3 * g.n + g.nh + 7 * GB);
         const size_t lds2 = sizeof(float) * ((size_t)P * (SG_F + 1) + 2 * P + GB);
         if (lds1 > 64 * 1024 || lds2 > 64 * 1024) return RULGNN_EUNSUPPORTED;
-        if (g.n <= 64) {
-            const size_t lw = sizeof(float) * ((size_t)3 * g.n + g.nh + 7 * 64);
-            hipLaunchKernelGGL(sg_patch_features_kernel<64>, dim3((unsigned)(g.R < 65536 ? g.R : 65536)), dim3(64), lw, st, g, a->x, ws + g.w_raw);
-        } else
-        hipLaunchKernelGGL(sg_patch_features_kernel<GB>, dim3((unsigned)(g.R < 16384 ? g.R : 16384)), dim3(GB), lds1, st, g, a->x, ws + g.w_raw);
+        sg_launch_patch_features(g, a->x, ws + g.w_raw, st);
         if (P % 16 == 0 && P <= 128) {
             const size_t lm = sg_graph_mx_lds(P);
             RULGNN_TRY(allow_dynamic_lds(sg_graph_mx_kernel, lm));

@@ -1,7 +1,7 @@
 """Hyper-parameter tables, looked up by dataset name then dataset id, like the reference's
 configs/hparams.py:3-7 (``get_hparams_class(name)(dataset_id)`` -> object with ``train_params`` and
 ``alg_hparams`` dicts keyed by ``--GNN_method``; unknown dataset -> NotImplementedError, unknown id ->
-ValueError).  Only the ST_GCN, STMSGCN, ASTGCNN, FC_STGNN, HAGCN, ST_Conv, STGNN, RGCNU, GRU_CM, STNet, SAGCN and STAGNN rows are restated (the methods this package
+ValueError).  Only the ST_GCN, STMSGCN, ASTGCNN, FC_STGNN, HAGCN, ST_Conv, STGNN, RGCNU, GRU_CM, STNet, SAGCN, AGCN_TF and STAGNN rows are restated (the methods this package
 implements).
 
 PHM2012 / XJTU_SY rows are the reference's (configs/hparams.py:223,238,... and :334,349,...; STMSGCN
@@ -48,6 +48,7 @@ class _Table:
     _stmsgcn_rows: dict = {}          # the reference wires STMSGCN to the bearing datasets only
     _stnet_rows: dict = {}            # ... and STNet (configs/hparams.py:222,236,267,303 and :333,347,382,416)
     _sagcn_rows: dict = {}            # ... and SAGCN (configs/hparams.py:221,235,266,302 and :332,346,381,415)
+    _agcntf_rows: dict = {}           # ... and AGCN_TF (configs/hparams.py:227,243,257,277,293,313 and :338,357,373,392,407,426)
     _astgcnn_nodes = None             # ... and ASTGCNN to the aero-engine datasets only (configs/hparams.py:38,202)
 
     def __init__(self, dataset_id=None, **overrides):
@@ -96,6 +97,11 @@ class _Table:
             num_patch, patch_size, gcn_hidden, attention_hidden = self._sagcn_rows[dataset_id]
             self.alg_hparams['SAGCN'] = {'num_patch': num_patch, 'patch_size': patch_size, 'gcn_hidden_dim': gcn_hidden,
                                          'attention_hidden_dim': attention_hidden}
+        if dataset_id in self._agcntf_rows:
+            self.train_params['AGCN_TF'] = {'num_epochs': 81, 'batch_size': 100, 'weight_decay': 1e-4, 'learning_rate': 1e-4}
+            num_patch, patch_size, hidden_adj, hidden_gnn = self._agcntf_rows[dataset_id]
+            self.alg_hparams['AGCN_TF'] = {'num_patch': num_patch, 'patch_size': patch_size, 'hidden_adj_dim': hidden_adj,
+                                           'hidden_gnn_dim': hidden_gnn}
         if dataset_id in self._stmsgcn_rows:
             self.train_params['STMSGCN'] = dict(_STMSGCN_TRAIN)
             self.alg_hparams['STMSGCN'] = dict(self._stmsgcn_rows[dataset_id], gcn_dims=list(_MSG['gcn_dims']),
@@ -130,6 +136,7 @@ class PHM2012(_Table):
                      'Condition_3': {'num_patch': 160, 'patch_size': 16, 'interval': 6, 'band_width': 5}}
     _stnet_rows = {'Condition_1': (20, 128, 9, 16, 9), 'Condition_2': (20, 128, 9, 16, 9), 'Condition_3': (80, 32, 5, 8, 5)}
     _sagcn_rows = {'Condition_1': (160, 16, 100, 100), 'Condition_2': (128, 20, 1000, 200), 'Condition_3': (128, 20, 1000, 200)}
+    _agcntf_rows = {'Condition_1': (40, 64, 100, 100), 'Condition_2': (40, 64, 100, 100), 'Condition_3': (40, 64, 100, 100)}
 
 
 class XJTU_SY(_Table):
@@ -141,6 +148,7 @@ class XJTU_SY(_Table):
                      'Condition_3': {'num_patch': 256, 'patch_size': 128, 'interval': 3, 'band_width': 5}}
     _stnet_rows = {'Condition_1': (128, 256, 9, 16, 17), 'Condition_2': (32, 1024, 17, 32, 33), 'Condition_3': (64, 512, 17, 32, 17)}
     _sagcn_rows = {'Condition_1': (32, 1024, 1000, 100), 'Condition_2': (32, 1024, 1000, 200), 'Condition_3': (32, 1024, 1000, 200)}
+    _agcntf_rows = {'Condition_1': (128, 256, 100, 100), 'Condition_2': (128, 256, 100, 100), 'Condition_3': (256, 128, 100, 100)}
 
 
 _DATASETS = {'CMAPSS': CMAPSS, 'NCMAPSS': NCMAPSS, 'PHM2012': PHM2012, 'XJTU_SY': XJTU_SY}

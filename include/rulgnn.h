@@ -332,6 +332,8 @@ size_t rulgnn_stgcn_train_args_size(void);
 #define RULGNN_STRUCT_GRU_ARGS 24
 #define RULGNN_STRUCT_GRUCM_SHAPE 25
 #define RULGNN_STRUCT_GRUCM_ARGS 26
+#define RULGNN_STRUCT_AGCNTF_SHAPE 27
+#define RULGNN_STRUCT_AGCNTF_ARGS 28
 size_t rulgnn_struct_size(int32_t which);
 
 /* Profiling aid: the training step is a chain of 4*num_layers+1 phase kernels:
@@ -756,6 +758,53 @@ int rulgnn_sagcn_forward_f32(const rulgnn_sagcn_shape *shape, const rulgnn_sagcn
 int rulgnn_sagcn_backward_f32(const rulgnn_sagcn_shape *shape, const rulgnn_sagcn_args *args, void *stream);
 /* SAGCN.update body (algorithms.py:427-435); with `opt` also Adam on the flat parameter buffer. */
 int rulgnn_sagcn_fwdbwd_f32(const rulgnn_sagcn_shape *shape, const rulgnn_sagcn_args *args, const rulgnn_adam_args *opt, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * AGCN_TF path (reference models/AGCN_TF/Model.py:7-189, algorithms/algorithms.py:574-599; the reference wires it to the bearing
+ * datasets, configs/hparams.py:227,243,257,277,293,313,338,357,373,392,407,426).
+ *
+ * x [batch, num_patch * patch_size] -> X [P, 40]: the SAGCN front end above (same statistics, same tie rule, same kernels) ->
+ * temporal branch over the P patches: A_t = Linear_Ha->P(tanh(Linear_40->Ha(X))), H_t = leaky_relu(Linear_40->Hg(A_t X)); spatial
+ * branch over the 40 features: A_s = Linear_Ha->40(tanh(Linear_P->Ha(X^T))), H_s = leaky_relu(Linear_P->Hg(A_s X^T)) ->
+ * H = [H_s ; H_t] [N = 40 + P, Hg] -> per head softmax(Q K^T / sqrt(Hg)) V with Q, K, V = Linear_Hg->Hg(H), heads side by side ->
+ * Linear(N * heads * Hg -> 1).  AGCN_TF.update: plain MSE.  Neither adjacency is ever formed (A X = U (W2^T X) + 1 (b2^T X)^T), nor
+ * the [N, N] attention probabilities stored.
+ *
+ * Flat parameter buffer in the order of the reference's state_dict, every weight before its bias:
+ *   attention_spa_adj.0.{weight[Ha][P], bias[Ha]} | attention_spa_adj.2.{weight[40][Ha], bias[40]} |
+ *   attention_tem_adj.0.{weight[Ha][40], bias[Ha]} | attention_tem_adj.2.{weight[P][Ha], bias[P]} |
+ *   spatial_gnn.theta.0.{weight[Hg][P], bias[Hg]} | temporal_gnn.theta.0.{weight[Hg][40], bias[Hg]} |
+ *   per head i: self_attention.heads.i.W_q.{weight[Hg][Hg], bias[Hg]}, .W_k.(same), .W_v.(same) | fc.{weight[N * heads * Hg], bias[1]}
+ * Limits: 1 <= num_patch <= 256, 2 <= patch_size <= 2048, 1 <= hidden_adj_dim, hidden_gnn_dim <= 128, 1 <= num_heads <= 4,
+ * batch * N * max(heads * Hg, Ha, 40) < 2^31 (param_count < 0, workspace_bytes == 0, RULGNN_EUNSUPPORTED beyond; no fallback).
+ */
+typedef struct rulgnn_agcntf_shape {
+    int64_t batch;
+    int32_t num_patch, patch_size, hidden_adj_dim, hidden_gnn_dim, num_heads;
+} rulgnn_agcntf_shape;
+
+typedef struct rulgnn_agcntf_args {
+    const float *x;           /* [batch, num_patch * patch_size] */
+    const float *y;           /* [batch] targets, or NULL */
+    const float *dpred;       /* [batch] d loss / d pred (autograd backward); NULL = MSE against y */
+    const float *params;
+    float *grads;
+    float *pred;              /* [batch] */
+    float *loss;              /* [1] this shard's share of MSE(pred, y) over the GLOBAL batch; may be NULL */
+    void *workspace;
+    size_t workspace_bytes;
+    int64_t global_batch;
+} rulgnn_agcntf_args;
+
+int64_t rulgnn_agcntf_param_count(const rulgnn_agcntf_shape *shape);       /* < 0: invalid / unsupported */
+size_t rulgnn_agcntf_workspace_bytes(const rulgnn_agcntf_shape *shape);    /* 0: invalid / unsupported */
+/* workspace taps for the parity tests, float offsets: 0 features [batch][P][40], 1 H [batch][N][Hg] (spatial rows first),
+ * 2 attention output O [batch][N][heads * Hg]; -1 otherwise */
+int64_t rulgnn_agcntf_tap_offset(const rulgnn_agcntf_shape *shape, int32_t which);
+int rulgnn_agcntf_forward_f32(const rulgnn_agcntf_shape *shape, const rulgnn_agcntf_args *args, void *stream);
+int rulgnn_agcntf_backward_f32(const rulgnn_agcntf_shape *shape, const rulgnn_agcntf_args *args, void *stream);
+/* AGCN_TF.update body (algorithms.py:589-597); with `opt` also Adam on the flat parameter buffer. */
+int rulgnn_agcntf_fwdbwd_f32(const rulgnn_agcntf_shape *shape, const rulgnn_agcntf_args *args, const rulgnn_adam_args *opt, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * STAGNN path (reference models/STAGNN/Model.py:8-230, algorithms/algorithms.py:298-323; the reference wires

@@ -1,0 +1,118 @@
+"""AGCN_TF without a GPU: the module's surface, the registry, the hparams rows, the C-ABI's size queries and coverage gate."""
+import ctypes as C
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from gnn_rul_benchmarking_amd import _lib
+
+from conftest import GOLDEN
+
+import agcntf_oracle as O
+
+LIMITS = "num_patch patch_size hidden_adj_dim hidden_gnn_dim num_heads".split()
+
+
+@pytest.mark.parametrize("name", ["agcntf_phm_40x64_bs4", "agcntf_small_5x7_bs6"])
+def test_a_seed_gives_the_reference_state_dict(name):
+    """Keys, their order and the initial values, for one head (20 keys) and two (26)."""
+    from gnn_rul_benchmarking_amd.agcntf import AGCN_TF_model
+    z = np.load(os.path.join(GOLDEN, name + ".npz"))
+    cfg = {k[4:]: int(z[k]) for k in z.files if k.startswith("cfg:")}
+    heads = cfg.get("num_heads", 1)
+    torch.manual_seed(int(z["seed"]))
+    m = AGCN_TF_model(**cfg)
+    sd = m.state_dict()
+    assert list(sd.keys()) == [k[3:] for k in z.files if k.startswith("sd:")] == O.param_names(heads)
+    assert len(sd) == 14 + 6 * heads
+    for k, v in sd.items():
+        assert v.shape == z["sd:" + k].shape and np.array_equal(v.numpy(), z["sd:" + k]), k
+    assert np.array_equal(m.flat_params.numpy(), O.flatten({k: z["sd:" + k] for k in O.param_names(heads)}, heads))
+    assert m.num_heads == heads
+
+
+def test_cpu_input_raises_and_the_tie_rule_is_documented():
+    from gnn_rul_benchmarking_amd import agcntf
+    from gnn_rul_benchmarking_amd.agcntf import AGCN_TF_model
+    assert "stable sort" in agcntf.__doc__ and "median_freq" in agcntf.__doc__
+    m = AGCN_TF_model(5, 7, 6, 7)
+    assert AGCN_TF_model(5, 7, 6, 7).num_heads == 1                        # the reference's constructor default
+    with pytest.raises(RuntimeError, match="HIP path only"):
+        m(torch.zeros(2, 35))
+
+
+def test_hparams_rows_equal_the_reference():
+    from gnn_rul_benchmarking_amd.hparams import get_hparams_class
+    rows = json.loads(str(np.load(os.path.join(GOLDEN, "agcntf_hparams_rows.npz"))["rows_json"]))
+    assert sorted(rows) == [f"{ds}/Condition_{i}" for ds in ("PHM2012", "XJTU_SY") for i in (1, 2, 3)]
+    for key, ref in rows.items():
+        ds, did = key.split("/")
+        h = get_hparams_class(ds)(did)
+        assert h.train_params["AGCN_TF"] == ref["train_params"] and h.alg_hparams["AGCN_TF"] == ref["alg_hparams"], key
+    for h in (get_hparams_class("CMAPSS")("FD001"), get_hparams_class("NCMAPSS")(None)):
+        assert "AGCN_TF" not in h.alg_hparams and "AGCN_TF" not in h.train_params
+
+
+def test_registry_serves_the_algorithm_and_refuses_the_model():
+    from gnn_rul_benchmarking_amd import algorithms as A
+    from gnn_rul_benchmarking_amd.agcntf import AGCN_TF_model
+    from gnn_rul_benchmarking_amd.hparams import get_hparams_class
+    from gnn_rul_benchmarking_amd.optim import FusedAdam
+    assert A.get_algorithm_class("AGCN_TF") is A.AGCN_TF
+    with pytest.raises(NotImplementedError, match="Algorithm not found: AGCN_TF_model"):
+        A.get_algorithm_class("AGCN_TF_model")
+    assert A.AGCN_TF.needs_train_mode is None and A.AGCN_TF.supports_graphs is False
+    h = get_hparams_class("PHM2012")("Condition_1")
+    algo = A.get_algorithm_class("AGCN_TF")(h.alg_hparams["AGCN_TF"], h.train_params["AGCN_TF"], "cpu")
+    assert isinstance(algo.model, AGCN_TF_model) and isinstance(algo.optimizer, FusedAdam)
+    assert algo.hparams == h.train_params["AGCN_TF"] and algo.model.c_family == "agcntf"
+
+
+def test_struct_sizes_are_checked_at_load():
+    lib = _lib.load()
+    assert _lib.AgcntfShape in _lib.STRUCTS and _lib.AgcntfArgs in _lib.STRUCTS
+    assert lib.rulgnn_struct_size(_lib.STRUCTS.index(_lib.AgcntfShape)) == C.sizeof(_lib.AgcntfShape) == 32
+    assert lib.rulgnn_struct_size(_lib.STRUCTS.index(_lib.AgcntfArgs)) == C.sizeof(_lib.AgcntfArgs) == C.sizeof(_lib.SagcnArgs)
+
+
+@pytest.mark.parametrize("P,n,Ha,Hg,heads", [(40, 64, 100, 100, 1), (128, 256, 100, 100, 1), (256, 128, 100, 100, 1), (5, 7, 6, 7, 2),
+                                              (24, 16, 128, 128, 4)])
+def test_param_count_is_the_state_dict(P, n, Ha, Hg, heads):
+    want = sum(int(np.prod(s)) for s in O.param_shapes(P, Ha, Hg, heads).values())
+    assert _lib.load().rulgnn_agcntf_param_count(C.byref(_lib.AgcntfShape(7, P, n, Ha, Hg, heads))) == want
+
+
+def test_coverage_gate_every_limit_plus_and_minus_one():
+    lib = _lib.load()
+    ok = dict(num_patch=40, patch_size=64, hidden_adj_dim=100, hidden_gnn_dim=100, num_heads=1)
+
+    def query(**kw):
+        s = _lib.AgcntfShape(3, *[dict(ok, **kw)[k] for k in LIMITS])
+        pc, ws = lib.rulgnn_agcntf_param_count(C.byref(s)), lib.rulgnn_agcntf_workspace_bytes(C.byref(s))
+        assert (pc < 0) == (ws == 0) and (lib.rulgnn_agcntf_tap_offset(C.byref(s), 1) < 0) == (ws == 0)
+        return ws > 0
+
+    for key, lo, hi in (("num_patch", 1, 256), ("patch_size", 2, 2048), ("hidden_adj_dim", 1, 128), ("hidden_gnn_dim", 1, 128),
+                        ("num_heads", 1, 4)):
+        assert query(**{key: lo}) and query(**{key: hi}), key
+        assert not query(**{key: lo - 1}) and not query(**{key: hi + 1}), key
+    # every limit at once: the LDS each kernel asks for is part of the decision
+    assert query(num_patch=256, patch_size=2048, hidden_adj_dim=128, hidden_gnn_dim=128, num_heads=4)
+    # an unsupported shape is refused by the entries too, before anything is touched
+    s = _lib.AgcntfShape(3, 40, 64, 100, 129, 1)
+    a = _lib.AgcntfArgs()
+    assert lib.rulgnn_agcntf_forward_f32(C.byref(s), C.byref(a), None) == _lib.load().rulgnn_agcntf_fwdbwd_f32(C.byref(s), C.byref(a), None, None)
+    assert lib.rulgnn_agcntf_forward_f32(C.byref(s), C.byref(a), None) != 0
+
+
+def test_workspace_is_monotone_in_the_batch_and_accepts_zero():
+    lib = _lib.load()
+    ws = lambda b, *s: lib.rulgnn_agcntf_workspace_bytes(C.byref(_lib.AgcntfShape(b, *s)))      # noqa: E731
+    for shape in ((40, 64, 100, 100, 1), (256, 128, 100, 100, 1), (5, 7, 6, 7, 2)):
+        sizes = [ws(b, *shape) for b in (0, 1, 2, 3, 100, 101, 257, 1024)]
+        assert sizes[0] > 0 and all(b >= a for a, b in zip(sizes, sizes[1:])) and sizes[-1] > sizes[1]
+        assert lib.rulgnn_agcntf_param_count(C.byref(_lib.AgcntfShape(0, *shape))) > 0
+    assert ws(-1, 40, 64, 100, 100, 1) == 0
