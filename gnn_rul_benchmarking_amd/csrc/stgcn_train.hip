@@ -1513,7 +1513,7 @@ static int run_train_coop(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_
 
 // ---- the matrix-core chain's view of the workspace (stgcn_train_mx.hip): X_0 tiles in cacheX, packed adjacency tiles in cacheA, X_l in
 // the saved slots X(l), TOP's sparse gradient in slot H(0), the dropout masks in O0(l), the gated x-hat of BatchNorm 2l-1 in Z2(l-1),
-// the H_l record (l >= 1) in Z1(l) (a slot the fp32 chain alone uses: every L keeps the workspace size), d(x0 + H) in sbuf, d X_l in rbuf ---------
+// the H_l record (every l; H_0 is F_1's) in Z1(l) (a slot the fp32 chain alone uses: every L keeps the workspace size), d(x0 + H) in sbuf, d X_l in rbuf ---------
 // The wide chain (stgcn_train_mxw.hip, 16 <= num_patch <= 47) keeps per-SAMPLE records in the same slots (a slot is ntiles x 640 floats in
 // either geometry: >= 160 floats per sample, which holds its largest record, 10 x 47 floats, whenever the geometry is one sample per tile).
 template <int L>

@@ -10,17 +10,21 @@
 // A layer forward on the matrix cores costs ~10 MFMAs per sample, so here every phase re-derives what it needs from the layer INPUT:
 //
 //     F_0 (stgcn_forward_mx.hip)  windows -> X_0, adjacency (55 floats), sum z1, sum z1^2 of BatchNorm 0
-//     F_{2l+1}                    l = 0: X_0, A; l >= 1: H_l -> layer l up to conv_block2 -> sums of BatchNorm 2l+1  nothing written
+//     F_{2l+1}                    l = 0: X_0, A -> H_0 (written); l >= 1: H_l -> layer l up to conv_block2 -> sums of BatchNorm 2l+1
 //     F_{2l}, l >= 1              X_{l-1}, A -> layer l-1 in full -> X_l (written) -> layer l up to conv_block1, H_l (written) -> sums
 //                                 of BatchNorm 2l
-//     TOP                         X_{L-1}, A (L >= 2: H_{L-1} instead of A) -> layer L-1, head, loss, head backward -> d X_L as (value,
-//                                 arg-max channel), sums of BN 2L-1
-//     G_{2l+1}                    X_l, A (l >= 1: H_l), d X_{l+1} -> layer l again, BatchNorm 2l+1 / conv_block2 backward -> d(x0 + H)
-//                                 (written)
-//     G_{2l}                      X_l, A, d(x0 + H) -> BatchNorm 2l / conv_block1 / theta backward; l >= 1: d X_l (written) and, with
-//                                 layer l-1 recomputed from X_{l-1}, the sums of BatchNorm 2l-1
+//     TOP                         X_{L-1}, H_{L-1} -> layer L-1 from H on, head, loss, head backward -> d X_L as (value, arg-max
+//                                 channel), sums of BN 2L-1
+//     G_{2l+1}                    H_l, d X_{l+1} -> layer l again from H on, BatchNorm 2l+1 / conv_block2 backward -> d(x0 + H) (written)
+//     G_{2l}                      X_l, A, d(x0 + H); l >= 1 (N = 14): H_l -> BatchNorm 2l / conv_block1 / theta backward (X_l and A for
+//                                 A X and (A d Hp)^T; H_l, read or rebuilt, as the convolution's operand and for the LeakyReLU gate);
+//                                 l >= 1: d X_l (written) and the sums of BatchNorm 2l-1 from the gated x-hat F_{2l} left
+// H_l = leaky(theta(A X_l)) is written once per layer by the first phase of this file that computes it (F_1 for l = 0, F_{2l} above) and
+// read from its record where that pays (rounds 8 and 18; MXT_H_READERS in stgcn_train_mx_ops.hpp: one switch per reader, with what each
+// was measured at -- G_0 and the layer l-1 pass of F_{2l} can read it too and are switched off).
 //
-// Per sample at 14 x 30, L = 2: 13.5 KB instead of 26.0 KB.  Between phases only layer inputs and two gradient tensors cross HBM.
+// Per sample at 14 x 30, L = 2: 13.5 KB instead of 26.0 KB (round 18's H_0 record and G_2's H tile add 0.9 KB: bytes traded for issue
+// slots, the phases' limit).  Between phases only layer inputs, the H records and two gradient tensors cross HBM.
 //
 // Layout.  The "D layout" of stgcn_forward_mx.hip: one 16x16 tile per sample, column = patch t = lane & 15, row = channel slot
 // 4 (lane >> 4) + r; a [10, N] tensor is three registers and four samples are in flight per wavefront.  The backward uses the same
@@ -103,11 +107,15 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
     constexpr bool GRAD_IN = KIND == PH_G && (BLK == 1 || LY >= 1);     // a gradient tensor enters: d X_{l+1}
     constexpr bool GRAD_TOP = GRAD_IN && LY == L - 1;                   // ... in TOP's (value, arg-max) form
     constexpr bool NEED_SB = KIND == PH_G && BLK == 0;
-    // the H_l record, l >= 1 (MxTrainK::hrec): F_{2l} writes H of layer LY; F_{2l+1} and G_{2l+1} need nothing else of X_l and A, and
-    // start from it.  (No H_0 record: F_1 writing it cost more than G_1 gained -- profiles/r08_h_record.md)
-    constexpr bool H_OUT = KIND == PH_F && WITH_PREV;
-    constexpr bool H_IN = (KIND == PH_F || KIND == PH_G) && BLK == 1 && LY >= 1;
-    constexpr bool H_TOP = KIND == PH_TOP && LY >= 1;                  // TOP: X_l for the residual, H_l in place of the adjacency
+    // the H_l record (MxTrainK::hrec): the first phase of this file that computes H of layer LY writes it -- F_{2l}, l >= 1; F_1 for
+    // H_0 (F_0 has it only under its per-sample scale) where a reader of H_0 is switched on.  F_{2l+1} and G_{2l+1} need nothing else
+    // of X_l and A, and start from it.  (The readers beyond round 8's: MXT_H_READERS, stgcn_train_mx_ops.hpp)
+    constexpr bool H_OUT = KIND == PH_F && (WITH_PREV || (IDX == 1 && mxt_h0_record(L)));
+    constexpr bool H_IN = (KIND == PH_F && BLK == 1 && LY >= 1) || (KIND == PH_G && BLK == 1 && (LY >= 1 || MXT_H0_READ_G1));
+    constexpr bool H_TOP = KIND == PH_TOP && (LY >= 1 || MXT_H0_READ_TOP);   // TOP: X_l for the residual, H_l in place of the adjacency
+    constexpr bool H_PREV = WITH_PREV && MXT_H_READ_F_EVEN;            // F_{2l}: the pass over layer l-1 starts from H_{l-1}
+    constexpr bool H_GE = KIND == PH_G && BLK == 0 && mxt_g_even_reads_h(LY, NFIX);   // G_{2l}: H_l beside X_l and the adjacency
+    constexpr bool H_TILE = H_PREV || H_GE;                            // ... in a tile of its own (off_H)
     static_assert(!(KIND == PH_F && IDX == 0), "F_0 is stgcn_train_f0_mx_kernel");
 
     // ---- LDS carve (floats) ------------------------------------------------------------------------------------------------
@@ -130,9 +138,10 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
     const int off_XP = off_DX + (GRAD_IN ? XF : 0);          // G_{2l}, l >= 1: the gated x-hat of BatchNorm 2l-1
     // every full-tile record this phase writes (F_{2l}: X_l, Q_l, H_l; G_{2l+1}: d(x0 + H); G_{2l}, l >= 1: d X_l) leaves through ONE
     // staging tile per wavefront, one record after the other
-    constexpr bool TILE_OUT = WITH_PREV || (KIND == PH_G && BLK == 1) || BWD_PREV;
+    constexpr bool TILE_OUT = WITH_PREV || H_OUT || (KIND == PH_G && BLK == 1) || BWD_PREV;
     const int off_HS = off_XP + (BWD_PREV ? XF : 0);         // the staging tile
-    const int wave_floats = off_HS + (TILE_OUT ? XF : 0);
+    const int off_H = off_HS + (TILE_OUT ? XF : 0);          // H_TILE: H_{l-1} (F_{2l}) / H_l (G_{2l})
+    const int wave_floats = off_H + (H_TILE ? XF : 0);
     float* const smem = smem_all + SH_BNC + MXT_RED_FLOATS + 2 * MXT_WAVES * (2 * F + 2) + wave * wave_floats;
     u32x2* const sh_tile = reinterpret_cast<u32x2*>(smem + off_sh);
     u32x2* const wg_img = reinterpret_cast<u32x2*>(smem + off_wg);
@@ -154,8 +163,9 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
         dma_tile<NT>(src, smem + off, bytes, lane);
     };
     constexpr std::true_type LAST{};
-    // H_l dies with G_{2l+1}, X_l with G_{2l}, the adjacency with G_0; the gradient tensors and Q_l have one reader each
-    constexpr std::bool_constant<KIND == PH_G && BLK == 1> LAST_H{};
+    // H_l dies with G_{2l} where that phase reads it, else with G_{2l+1}; X_l dies with G_{2l}, the adjacency with G_0; the gradient
+    // tensors and Q_l have one reader each
+    constexpr std::bool_constant<KIND == PH_G && (BLK == 0 || !mxt_g_even_reads_h(LY, NFIX))> LAST_H{};
     constexpr std::bool_constant<KIND == PH_G && BLK == 0> LAST_X{};
     constexpr std::bool_constant<KIND == PH_G && IDX == 0> LAST_A{};
     auto req_XA = [&](int64_t t) {
@@ -167,8 +177,13 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
         } else {
             dma(a.xrec[LIN] + t * XF, off_X, 4 * XF, LAST_X);
             dma(a.arec + t * AF, off_A, 4 * AF, LAST_A);
+            if constexpr (H_PREV) dma(a.hrec[LIN] + t * XF, off_H, 4 * XF, std::false_type{});
         }
     };
+    // G_{2l}: each half tile reads its two samples of H_l from the tile when it starts, and the tile is requested again behind the
+    // second half's read -- half a tile later than the other inputs.  (All four samples in registers from the top of the tile, the
+    // request with X_l's: G_2 spills 28 bytes instead of 16 and the step is SLOWER than with the rebuild -- profiles/r18_h_records.md)
+    auto req_H = [&](int64_t t) { if constexpr (H_GE) dma(a.hrec[LY] + t * XF, off_H, 4 * XF, LAST_H); };
     auto req_SB = [&](int64_t t) { if constexpr (NEED_SB) dma(a.sb + t * XF, off_SB, 4 * XF, LAST); };
     auto req_DX = [&](int64_t t) {
         if constexpr (GRAD_TOP) dma(a.dtop + t * (8 * N), off_DX, 32 * N, LAST);
@@ -202,8 +217,8 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
     constexpr int M1_LY = (KIND == PH_F && BLK == 0) ? 0 : ((KIND == PH_F) ? 1 : ((KIND == PH_G && BLK == 0) ? 0 : 2));   // conv_block2
     MXP_MARKI(1);
     LayerRaw rc, rp;
-    layer_raw(rc, a.prm, LY, N, g, col, M0_LY, M1_LY, !(H_IN || H_TOP));
-    if constexpr (WITH_PREV) layer_raw(rp, a.prm, LY - 1, N, g, col, 2, 2);
+    layer_raw(rc, a.prm, LY, N, g, col, M0_LY, M1_LY, !(H_IN || H_TOP || H_GE));
+    if constexpr (WITH_PREV) layer_raw(rp, a.prm, LY - 1, N, g, col, 2, 2, !H_PREV);
     ConvOp wT = ConvOp{u32x4{0u, 0u, 0u, 0u}, u32x4{0u, 0u, 0u, 0u}};
     ThetaOp thN = ThetaOp{u32x4{0u, 0u, 0u, 0u}, u32x4{0u, 0u, 0u, 0u}};
     ConvRaw wT_raw = ConvRaw{{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};          // (converted behind the BatchNorm cells' loads: one round trip)
@@ -239,7 +254,7 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
         if (use_drop && tile < a.ntiles) mask_next = a.mrec[LY][tile * 64 + lane];
     }
     __builtin_amdgcn_sched_barrier(0);
-    if (tile < a.ntiles) { req_XA(tile); req_SB(tile); req_DX(tile); req_XP(tile); }
+    if (tile < a.ntiles) { req_XA(tile); req_H(tile); req_SB(tile); req_DX(tile); req_XP(tile); }
     {
         MXP_MARKI(2);                                                              // independent prologue done
         if constexpr (PERSIST) {
@@ -511,10 +526,18 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
         }
         // ---- inputs ------------------------------------------------------------------------------------------------------------------
         float X[4][3];                          // X_LIN; H_IN: H_LY
-        float HT[4][3];                         // H_TOP: H_LY
+        float HT[4][3];                         // H_TOP: H_LY; H_PREV: H_LIN
         u32x4 adjB[4];
         ld_tile(off_X, X);
         if constexpr (H_TOP) ld_tile(off_A, HT);
+        if constexpr (H_PREV) {
+            ld_tile(off_H, HT);
+            if (ns < 4) {                       // beyond the batch the record holds whatever an earlier step left
+#pragma unroll
+                for (int s = 0; s < 4; ++s)
+                    if (s >= ns) HT[s][0] = HT[s][1] = HT[s][2] = 0.f;
+            }
+        }
         if constexpr (H_IN || H_TOP) {
             if (ns < 4) {                       // the record holds whatever an earlier step left beyond the batch
 #pragma unroll
@@ -552,7 +575,8 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
         if constexpr (KIND == PH_F) {
             // ===== forward statistics phases ==============================================================================================
             if constexpr (WITH_PREV) {
-                layer_full(X, adjB, kp, dkey[LY - 1], sbase, nullptr, nullptr, &pend_q, &pend_m);
+                if constexpr (H_PREV) layer_full(X, adjB, kp, dkey[LY - 1], sbase, nullptr, nullptr, &pend_q, &pend_m, &HT);
+                else layer_full(X, adjB, kp, dkey[LY - 1], sbase, nullptr, nullptr, &pend_q, &pend_m);
 #pragma unroll
                 for (int s = 0; s < 4; ++s)
 #pragma unroll
@@ -763,6 +787,25 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
                     for (int e = 0; e < NS; ++e)
 #pragma unroll
                         for (int r = 0; r < 3; ++r) H[e][r] = Xh[e][r];
+                } else if constexpr (H_GE) {
+                    // H from its record: no T, Hp, LeakyReLU; X_l is split for (A X) alone
+#pragma unroll
+                    for (int e = 0; e < NS; ++e) {
+                        const Split2 p01 = split2(Xh[e][0], Xh[e][1]), p2 = split2(Xh[e][2], 0.f);
+                        AXd[e] = mfma16z(ad[e], u32x4{p01.hi, p2.hi, p01.hi, p2.hi});              // (A X) in the D layout: rows c, columns k
+                        AXd[e] = mfma16(ad[e], u32x4{p01.lo, p2.lo, p01.lo, p2.lo}, AXd[e]);
+#pragma unroll
+                        for (int r = 0; r < 3; ++r) {
+                            const float hv = smem[(xoff[r] >= 0 ? off_H + xoff[r] : off_zero) + (HS + e) * N];
+                            H[e][r] = (HS + e < ns) ? hv : 0.f;          // beyond the batch: whatever an earlier step left
+                        }
+                    }
+                    if constexpr (HS == 2) {
+                        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                        __builtin_amdgcn_wave_barrier();
+                        if (nt < a.ntiles) req_H(nt);
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
                 } else {
                     f32x4 T[NS];
                     Op2 xo[NS];
@@ -889,7 +932,11 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
 #pragma unroll
                         for (int r = 0; r < 3; ++r) {
                             const float gq = dI[e][r] + SB[HS + e][r];
-                            const float v = Hp[e][r] > 0.f ? gq : gq * LEAKY;
+                            // H_GE: the gate from H instead of Hp -- the same branch for every input: H = Hp + c |Hp| with
+                            // c = (1 - a)/(1 + a) in (0, 1) has the sign of Hp, +-0 gives 0 on both sides (not > 0), and a NaN
+                            // compares false on both
+                            const bool hp_pos = H_GE ? H[e][r] > 0.f : Hp[e][r] > 0.f;
+                            const float v = hp_pos ? gq : gq * LEAKY;
                             dHp[r] = (HS + e < ns) ? v * colm : 0.f;
                             acc_b += dHp[r];
                         }
@@ -1155,21 +1202,33 @@ __global__ __launch_bounds__(64 * MXT_WAVES, MX_WAVES_PER_SIMD) void stgcn_train
 static constexpr size_t mxt_lds_bytes(int L, int kind, int idx, int N) {
     const int blk = kind == PH_TOP ? 1 : idx % 2, ly = kind == PH_TOP ? L - 1 : idx / 2;
     const bool need_sb = kind == PH_G && blk == 0, grad_in = kind == PH_G && (blk == 1 || ly >= 1), bwd_prev = kind == PH_G && blk == 0 && ly >= 1;
-    const bool h_in = (kind == PH_F || kind == PH_G) && blk == 1 && ly >= 1;     // H_IN of mxt_phase_body: no adjacency tile
-    const bool h_top = kind == PH_TOP && ly >= 1;                                  // H_TOP: an H tile in its place
+    const bool with_prev = kind == PH_F && blk == 0 && ly >= 1;
+    // H_IN of mxt_phase_body: no adjacency tile
+    const bool h_in = (kind == PH_F && blk == 1 && ly >= 1) || (kind == PH_G && blk == 1 && (ly >= 1 || MXT_H0_READ_G1));
+    const bool h_top = kind == PH_TOP && (ly >= 1 || MXT_H0_READ_TOP);            // H_TOP: an H tile in its place
+    // H_TILE: F_{2l} / G_{2l} with an H tile of their own (mxt_launch_n instantiates NFIX = 14 for N = 14, the generic body otherwise)
+    const bool h_tile = (with_prev && MXT_H_READ_F_EVEN) || (kind == PH_G && blk == 0 && mxt_g_even_reads_h(ly, N == 14 ? 14 : 0));
     // the staging tile of the phases that write full-tile records (TILE_OUT of mxt_phase_body)
-    const bool stage = (kind == PH_F && blk == 0 && ly >= 1) || (kind == PH_G && blk == 1) || bwd_prev;
+    const bool stage = with_prev || (kind == PH_F && idx == 1 && mxt_h0_record(L)) || (kind == PH_G && blk == 1) || bwd_prev;
     const int XF = 40 * N;
     const size_t wave = (size_t)MXT_ZERO_FLOATS + MXT_SCRATCH_FLOATS + MXT_SHIFT_FLOATS + (kind == PH_G ? MXT_WG_FLOATS : 0) + XF + (h_in ? 0 : h_top ? XF : 220) + (need_sb ? XF : 0) + (grad_in ? XF : 0) +
-                        (bwd_prev ? XF : 0) + (stage ? XF : 0);
+                        (bwd_prev ? XF : 0) + (stage ? XF : 0) + (h_tile ? XF : 0);
     const size_t shared = (size_t)((2 * L * MXT_BNC * F + 3) & ~3) + MXT_RED_FLOATS + 2 * MXT_WAVES * (2 * F + 2);
     return (shared + MXT_WAVES * wave) * sizeof(float);
 }
 // stgcn_train_mx_shape_ok admits num_patch <= 15 and at most MX_MAX_LAYERS layers: the largest request (G_{2l}, l >= 1: five tiles and the
-// transposing image per wavefront) stays inside what a launch may ask for, so a shape the gate accepts cannot fail a launcher's check.
+// transposing image per wavefront; six tiles where it reads H_l, which mxt_g_even_reads_h allows at N = 14 only) stays inside what a
+// launch may ask for -- 80 KB, two workgroups per CU -- so a shape the gate accepts cannot fail a launcher's check.
 constexpr size_t MXT_MAX_LDS_BYTES = 80 * 1024;
-static_assert(mxt_lds_bytes(MX_MAX_LAYERS, PH_G, 2, 15) <= MXT_MAX_LDS_BYTES && mxt_lds_bytes(MX_MAX_LAYERS, PH_G, 3, 15) <= MXT_MAX_LDS_BYTES,
-              "the largest matrix-core phase must fit its LDS limit");
+constexpr size_t mxt_lds_bytes_max(int L, int N) {
+    size_t m = mxt_lds_bytes(L, PH_TOP, 0, N);
+    for (int i = 1; i < 2 * L; ++i) m = std::max(m, mxt_lds_bytes(L, PH_F, i, N));
+    for (int i = 0; i < 2 * L; ++i) m = std::max(m, mxt_lds_bytes(L, PH_G, i, N));
+    return m;
+}
+static_assert(mxt_lds_bytes_max(MX_MAX_LAYERS, 15) <= MXT_MAX_LDS_BYTES && mxt_lds_bytes_max(MX_MAX_LAYERS, 14) <= MXT_MAX_LDS_BYTES &&
+                  mxt_lds_bytes_max(1, 15) <= MXT_MAX_LDS_BYTES,
+              "every matrix-core phase must fit its LDS limit");
 
 template <int L, int KIND, int IDX, int NFIX>
 static int mxt_launch(const MxTrainK& k, hipStream_t stream, int max_grid, int* grid_out) {
@@ -1244,10 +1303,7 @@ template <int NFIX>
 static int mxt_persist_launch(const MxTrainK& k, hipStream_t stream, int64_t grid) {
     constexpr int L = 2;
     auto kern = &stgcn_train_mx_persist_kernel<L, NFIX>;
-    size_t lds = 0;
-    for (int i = 1; i < 2 * L; ++i) lds = std::max(lds, mxt_lds_bytes(L, PH_F, i, k.N));
-    lds = std::max(lds, mxt_lds_bytes(L, PH_TOP, 0, k.N));
-    for (int i = 0; i < 2 * L; ++i) lds = std::max(lds, mxt_lds_bytes(L, PH_G, i, k.N));
+    const size_t lds = mxt_lds_bytes_max(L, k.N);
     if (const int rc = allow_dynamic_lds(kern, lds, MXT_MAX_LDS_BYTES); rc != RULGNN_OK) return rc;
     (void)hipGetLastError();
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * MXT_WAVES), lds, stream, k);

@@ -32,6 +32,38 @@ enum { PH_F = 0, PH_TOP = 1, PH_G = 2 };
 constexpr int MXT_RECORD_POLICY = ST_WT;
 constexpr bool MXT_LAST_READER_NT = true;
 
+// Who reads H_l = leaky(theta(A X_l)) from its record (MxTrainK::hrec) instead of rebuilding it from X_l and the adjacency, beyond the
+// round-8 readers F_{2l+1}, TOP and G_{2l+1} of the layers l >= 1.  One switch per reader, each measured on top of the ones before it
+// (profiles/r18_h_records.md, us of the reader's own kernel at batch 65 536; -DMXT_H_READERS=<bits> builds a combination with
+// tools/build_variants.py):
+//   bit 0  G_{2l}, l >= 1 <- H_l    (no new record)                                       G_2 -2.1 (G_3, no longer the last reader, +0.4)
+//   bit 1  G_1 and, at L = 1, TOP <- H_0    } any of these: F_1 WRITES the H_0 record      G_1 -5.8; F_1 +2.9 for the record
+//   bit 2  G_0 <- H_0                       } (mxt_h0_record) -- never F_0, whose H_0 is   G_0 -0.65
+//   bit 3  F_{2l}, l >= 1: its pass over    } computed under the per-sample 2^-k scale     F_2 -2.0
+//          layer l-1 <- H_{l-1}             } and rounds differently in its lo halves
+// (TOP at L = 1 shares G_1's switch and has not been timed: the flagship has two layers.)
+// ON: bits 0 and 1 -- 0.3048 -> 0.2991 ms per step (a later session: 0.3040 -> 0.3015), every run faster than every run of the
+// parent.  OFF: bits 2 and 3.  Their own kernels get shorter as listed, but with
+// either of them the step falls into a slow mode in one run of two or three (all four: 0.3036 / 0.2988 / 0.3036 ms against the
+// parent's 0.3044; under the profiler the sum of the ten kernels 305.5 or 309.3 us, F_3, G_3 and G_2 -- kernels these bits do not
+// touch -- 0.3 to 0.9 us longer in the slow runs), and the opt-in single launch loses 4 us more at batch 100.  Not understood; the
+// bodies stay, they are a few lines on top of bit 0's.
+#ifndef MXT_H_READERS
+#define MXT_H_READERS 3
+#endif
+constexpr bool MXT_H_READ_G_EVEN = (MXT_H_READERS & 1) != 0;
+constexpr bool MXT_H0_READ_G1 = (MXT_H_READERS & 2) != 0;
+constexpr bool MXT_H0_READ_TOP = MXT_H0_READ_G1;
+constexpr bool MXT_H0_READ_G0 = (MXT_H_READERS & 4) != 0;
+constexpr bool MXT_H_READ_F_EVEN = (MXT_H_READERS & 8) != 0;
+// F_1 writes H_0 when somebody in an L-layer step reads it (F_{2l} at l = 1 reads H_0, at l >= 2 a record that exists anyway)
+constexpr bool mxt_h0_record(int L) { return MXT_H0_READ_G1 || MXT_H0_READ_G0 || (L == 1 ? MXT_H0_READ_TOP : MXT_H_READ_F_EVEN); }
+// G_{2l} with the H tile beside X_l, the adjacency, d(x0 + H), d X_{l+1}, Q_l and the staging tile: at l >= 1 that is 82 896 bytes at
+// N = 15, L = 3 -- more than the 80 KB that keep two workgroups on a CU -- so there only the fixed-N (14) instantiations read the record
+// and the generic ones keep the rebuild.  G_0 has three of those tiles and fits at every N.  (`nfix`: the kernel's NFIX; the host passes
+// what mxt_launch_n would instantiate for its N.)
+constexpr bool mxt_g_even_reads_h(int ly, int nfix) { return ly == 0 ? MXT_H0_READ_G0 : (MXT_H_READ_G_EVEN && nfix == 14); }
+
 struct Op2 { u32x4 h, l; };              // a D-layout tensor as the ({hi | hi}, {lo | lo}) operand pair against a {hi | lo} partner
 struct Pk { u32x2 hi, lo; };             // its packed halves: slots 4 g .. 4 g + 3 of this lane's column
 
@@ -204,8 +236,9 @@ struct MxTrainK {
     float* gpart;
     float* xrec[MX_MAX_LAYERS];   // X_l tiles: [ntiles][10][4 N]
     float* qrec[MX_MAX_LAYERS];   // l >= 1: x-hat of BatchNorm 2l-1 where the gradient passes (ReLU gate and dropout), else +inf
-    float* hrec[MX_MAX_LAYERS];   // l >= 1: H_l = leaky(theta(A X_l)): [ntiles][10][4 N], written by F_{2l}, read by F_{2l+1} and
-                                  // G_{2l+1} instead of X_l and the adjacency, by TOP (l = L - 1) instead of the adjacency
+    float* hrec[MX_MAX_LAYERS];   // H_l = leaky(theta(A X_l)): [ntiles][10][4 N], written by F_1 (l = 0) / F_{2l} (l >= 1); read by F_{2l+1}
+                                  // (l >= 1) and G_{2l+1} instead of X_l and the adjacency, by TOP (l = L - 1) instead of the adjacency,
+                                  // by F_{2l+2} and G_{2l} beside them (MXT_H_READERS)
     uint32_t* mrec[MX_MAX_LAYERS];   // dropout masks of layer l, one word per lane and tile (bit 3 s + r = keep of sample s, register r):
                                      // hashed once, by the phase that first applies them (F_{2l+2} / TOP), read by G_{2l+1}
     float* arec;                  // adjacency tiles: [ntiles][4][55]
