@@ -26,6 +26,14 @@ inline int allow_dynamic_lds(void (*kernel)(A...), size_t bytes, size_t cap = MA
     return allow_dynamic_lds(reinterpret_cast<const void*>(kernel), bytes, cap);
 }
 
+// Launch tail: drop any stale error of the caller's earlier HIP calls, launch, report this launch's own error.
+template <typename... P, typename... A>
+inline int launch_checked(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, const A&... args) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
+    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+}
+
 // Compute units of the current device; 256 when the query fails (`ok`, if given, says whether it succeeded).
 inline int device_cu_count(bool* ok = nullptr) {
     int dev = 0, v = 0;

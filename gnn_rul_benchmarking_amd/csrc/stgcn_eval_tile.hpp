@@ -16,6 +16,8 @@ struct EvalWeightsLds {
     float* bnf;     // [L][2][2][F]  folded BatchNorm scale / shift
     float* vecs;    // [L+2][RW]     theta bias per layer (summed over the orders), fc1 bias, fc2 weight
     static __host__ __device__ constexpr int floats(int L, int K = 1) { return (L * K + 1) * RW * wstride<RW>() + L * 4 * F + (L + 2) * RW; }
+    // The kernels' whole block (stgcn_forward.hip): the weights, then from floats(L, K) on one input tile of `stage_floats` per wavefront
+    static __host__ __device__ constexpr int total(int L, int K, int stage_floats) { return floats(L, K) + WAVES_PER_BLOCK * stage_floats; }
     __device__ __forceinline__ void bind(float* base, int L, int K = 1) {
         wlds = base;
         bnf = wlds + (L * K + 1) * RW * wstride<RW>();

@@ -58,21 +58,38 @@ __global__ __launch_bounds__(BLOCK) void stgcn_forward_eval_kernel(const float* 
     }
 }
 
-// LDS of the exact kernel (and of the scan below, which runs the same routine): the weights of every layer and order, then one input
-// tile per wavefront
-static size_t exact_lds_bytes(const TileGeom& g, int L, int K) {
-    const int w = g.RW == 16 ? EvalWeightsLds<16>::floats(L, K) : (g.RW == 32 ? EvalWeightsLds<32>::floats(L, K) : EvalWeightsLds<64>::floats(L, K));
-    return sizeof(float) * ((size_t)w + (size_t)WAVES_PER_BLOCK * g.stage_floats);
+// LDS of the exact kernel (and of the scan below, which runs the same routine): EvalWeightsLds' block at the shape's row width
+static constexpr size_t exact_lds_bytes(int RW, int stage_floats, int L, int K) {
+    const int fl = RW == 16 ? EvalWeightsLds<16>::total(L, K, stage_floats) : (RW == 32 ? EvalWeightsLds<32>::total(L, K, stage_floats) : EvalWeightsLds<64>::total(L, K, stage_floats));
+    return sizeof(float) * (size_t)fl;
 }
+// Pinned (the launches' requests must not move with an edit of the layout): the bytes at the shapes of tests/test_stgcn_lds_envelope_gpu.py (the
+// last window that fits and the first that does not, orders 1 to 3): {RW, layers, order, stage_floats, exact kernel, scan}
+constexpr int EXACT_LDS_PINS[][6] = {
+    {64, 2, 1, 6832, 162880, 162880}, {64, 2, 1, 6932, 164480, 164480}, {64, 2, 1, 6840, 163008, 163008}, {64, 2, 1, 6960, 164928, 164928}, {64, 2, 1, 6864, 163392, 163392}, {64, 2, 1, 6912, 164160, 164160},
+    {64, 2, 1, 7008, 165696, 165696}, {64, 2, 1, 6848, 163136, 163136}, {64, 2, 1, 7040, 166208, 166208}, {32, 8, 1, 7448, 163200, 163200}, {32, 8, 1, 7548, 164800, 164800}, {32, 8, 1, 7360, 161792, 161792},
+    {32, 8, 1, 7552, 164864, 164864}, {16, 8, 1, 9152, 159872, 159872}, {64, 2, 1, 5372, 139520, 139520}, {64, 2, 1, 5456, 140864, 140864}, {64, 2, 1, 5496, 141504, 141504}, {64, 2, 1, 5400, 139968, 139968},
+    {64, 2, 1, 5520, 141888, 141888}, {64, 2, 1, 5328, 138816, 138816}, {64, 2, 1, 5472, 141120, 141120}, {64, 2, 1, 5312, 138560, 138560}, {64, 2, 1, 5504, 141632, 141632}, {32, 2, 2, 8672, 162624, 153408},
+    {32, 2, 2, 8772, 164224, 155008}, {64, 2, 2, 4600, 161984, 127168}, {64, 2, 2, 4720, 163904, 129088}, {64, 2, 2, 5400, 174784, 139968}, {64, 2, 2, 5520, 176704, 141888}, {64, 2, 2, 4544, 161088, 126272},
+    {64, 2, 2, 4736, 164160, 129344}, {64, 2, 2, 5312, 173376, 138560}, {64, 2, 2, 5504, 176448, 141632}, {32, 2, 3, 6732, 140800, 122368}, {32, 2, 3, 6768, 141376, 122944}, {32, 2, 3, 8128, 163136, 144704},
+    {32, 2, 3, 8228, 164736, 146304}, {32, 1, 3, 6904, 129440, 120224}, {32, 1, 3, 7004, 131040, 121824}, {64, 2, 3, 2520, 163520, 93888}, {64, 2, 3, 2640, 165440, 95808}, {64, 2, 3, 3320, 176320, 106688},
+    {64, 2, 3, 3440, 178240, 108608}, {64, 2, 3, 2496, 163136, 93504}, {64, 2, 3, 2688, 166208, 96576}, {64, 2, 3, 3264, 175424, 105792}, {64, 2, 3, 3456, 178496, 108864},
+};
+constexpr bool exact_lds_pins_hold() {
+    for (const auto& p : EXACT_LDS_PINS)
+        if (exact_lds_bytes(p[0], p[3], p[1], p[2]) != (size_t)p[4] || exact_lds_bytes(p[0], p[3], p[1], 1) != (size_t)p[5]) return false;
+    return true;
+}
+static_assert(exact_lds_pins_hold(), "the exact eval kernels request the LDS they always did");
 
 size_t stgcn_forward_exact_lds_bytes(const rulgnn_stgcn_shape* s) {
     TileGeom g;
-    return tile_geometry(s, &g) == RULGNN_OK ? exact_lds_bytes(g, s->num_layers, s->mpnn_k) : 0;
+    return tile_geometry(s, &g) == RULGNN_OK ? exact_lds_bytes(g.RW, g.stage_floats, s->num_layers, s->mpnn_k) : 0;
 }
 
 size_t stgcn_forward_fixup_lds_bytes(const rulgnn_stgcn_shape* s) {
     TileGeom g;
-    return tile_geometry(s, &g) == RULGNN_OK ? exact_lds_bytes(g, s->num_layers, 1) : 0;     // behind the order-1 matrix-core kernels
+    return tile_geometry(s, &g) == RULGNN_OK ? exact_lds_bytes(g.RW, g.stage_floats, s->num_layers, 1) : 0;     // behind the order-1 matrix-core kernels
 }
 
 template <int RW, int NFIX, int PFIX, int LFIX>
@@ -88,9 +105,7 @@ static int launch_forward_fix(const TileGeom& g, const rulgnn_stgcn_shape* s, co
     // (above MAX_LDS_BYTES: a backstop, the C-ABI gate (tiled_eval) keeps such shapes out)
     if (const int rc = allow_dynamic_lds(&stgcn_forward_eval_kernel<RW, NFIX, PFIX, LFIX>, lds); rc != RULGNN_OK) return rc;
     const int grid = persistent_grid(stgcn_forward_eval_kernel<RW, NFIX, PFIX, LFIX>, g.ntiles, lds, 4);
-    (void)hipGetLastError();   // drop any stale error of the caller's earlier HIP calls
-    hipLaunchKernelGGL((stgcn_forward_eval_kernel<RW, NFIX, PFIX, LFIX>), dim3(grid), dim3(BLOCK), lds, stream, x, prm, bn, out, a);
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return launch_checked(stgcn_forward_eval_kernel<RW, NFIX, PFIX, LFIX>, dim3(grid), dim3(BLOCK), lds, stream, x, prm, bn, out, a);
 }
 
 template <int RW>
@@ -161,9 +176,7 @@ static int launch_fixup(const TileGeom& g, const rulgnn_stgcn_shape* s, const fl
     if (const int rc = allow_dynamic_lds(&stgcn_forward_fixup_kernel<RW>, lds); rc != RULGNN_OK) return rc;
     int64_t grid = (s->batch + BLOCK - 1) / BLOCK;
     if (grid > 1024) grid = 1024;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL((stgcn_forward_fixup_kernel<RW>), dim3((unsigned)grid), dim3(BLOCK), lds, stream, x, prm, bn, out, a);
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return launch_checked(stgcn_forward_fixup_kernel<RW>, dim3((unsigned)grid), dim3(BLOCK), lds, stream, x, prm, bn, out, a);
 }
 
 int stgcn_forward_fixup(const rulgnn_stgcn_shape* s, const float* x, const float* prm, const float* bn, float* out, hipStream_t stream) {

@@ -65,6 +65,23 @@ struct MxArgs {
     float* taps;           // debug: raw register dumps of tile 0 (TAPS builds only)
 };
 
+// LDS of the narrow kernels (floats).  A wavefront's part: [window buffer: 4 samples | conversion tile + shift tile].  The eval kernel's
+// safety net stages its tile (and its transpose scratch, PT_FLOATS) in the first region and keeps its weights in the second.  `nwaves`:
+// 1 = the eval kernel, one wavefront per workgroup; MXF0_WAVES = training's F_0, pair partials [nwaves][2 F] doubles in front.
+constexpr int MX_CONV_BYTES = MX_MIN_BUF_BYTES + MX_SHIFT_TILE_BYTES;
+struct MxLds {
+    int waves, cur, sh, wave_floats, total;
+};
+__host__ __device__ constexpr MxLds mx_lds(int buf_floats, int nwaves) {
+    MxLds l{};
+    l.waves = nwaves > 1 ? 2 * nwaves * 2 * F : 0;             // the wavefronts' parts
+    l.cur = buf_floats;                                        // within a part: the conversion region
+    l.sh = MX_MIN_BUF_BYTES / 4;                               // within the conversion region: the shift tile, behind the layout-conversion tile
+    l.wave_floats = l.cur + MX_CONV_BYTES / 4;
+    l.total = l.waves + nwaves * l.wave_floats;
+    return l;
+}
+
 // Development aid (variant builds with -DMX_STAGE_CLOCKS only; tools/mx_stage_clocks.py): s_memtime stamps at the stage boundaries of
 // a tile, consumed at the END of the iteration (an SMEM result needs lgkmcnt(0): consumed in place it would serialise the LDS round
 // trips the stages overlap), summed per wavefront and added to a device array.  The product build compiles every call to nothing.
@@ -223,6 +240,8 @@ __global__ __launch_bounds__(64, MX_WAVES_PER_SIMD) void stgcn_forward_mx_kernel
     const int g = lane >> 4, col = lane & 15;            // D layout: row group / column; row mapping: sample row / patch
     const int tileNP = N * P;                            // floats per sample
 
+    const MxLds ld = mx_lds(a.buf_floats, 1);
+
     int64_t tile = blockIdx.x;
     if (tile >= a.ntiles) return;
 #ifdef MX_STAGE_CLOCKS
@@ -305,7 +324,7 @@ __global__ __launch_bounds__(64, MX_WAVES_PER_SIMD) void stgcn_forward_mx_kernel
     int sh_rd1_lo = sh_rd1 + 65, sh_rd2_lo = sh_rd2 + 65;
     asm volatile("" : "+v"(sh_rd1_lo), "+v"(sh_rd2_lo));
 
-    mx_zero_padding_rows(smem + a.buf_floats, lane);
+    mx_zero_padding_rows(smem + ld.cur, lane);
     bool any_bad = false, pend_mine = false;
     int64_t pend_idx = 0;
     float pend_pred = 0.f;
@@ -317,7 +336,7 @@ __global__ __launch_bounds__(64, MX_WAVES_PER_SIMD) void stgcn_forward_mx_kernel
         StageClk ck;
         ck.template stamp<0>();
         float* const tileA = smem;                       // this tile's windows (LDS-DMA target); free again once the patches are in registers
-        float* const cur = smem + a.buf_floats;          // layout-conversion tile + shift tile (plain arithmetic on the __shared__ base
+        float* const cur = smem + ld.cur;                // layout-conversion tile + shift tile (plain arithmetic on the __shared__ base
                                                          // keeps these LDS, not flat, accesses)
         const int64_t s0 = tile * 4;
         const int ns = (int)((a.B - s0) < 4 ? (a.B - s0) : 4);
@@ -330,7 +349,7 @@ __global__ __launch_bounds__(64, MX_WAVES_PER_SIMD) void stgcn_forward_mx_kernel
         if (pend_mine) out[pend_idx] = pend_pred;
         ck.template stamp<1>();
 
-        u32x2* sh_tile = reinterpret_cast<u32x2*>(cur + MX_MIN_BUF_BYTES / 4);      // behind the layout-conversion tile
+        u32x2* sh_tile = reinterpret_cast<u32x2*>(cur + ld.sh);
 
         const bool valid = (g < ns) && (col < N);
         float X0[F], X[4][3];
@@ -515,7 +534,7 @@ __global__ __launch_bounds__(64, MX_WAVES_PER_SIMD) void stgcn_forward_mx_kernel
         const float* bn_cold = bn;
         asm volatile("" : "+v"(prm_cold), "+v"(bn_cold));
         EvalWeightsLds<16> w;
-        w.bind(smem + a.buf_floats, L);
+        w.bind(smem + ld.cur, L);
         eval_weights_fill<16>(w, prm_cold, bn_cold, N, L, lane, 64);
         __builtin_amdgcn_wave_barrier();
         for (tile = blockIdx.x; tile < a.ntiles; tile += gridDim.x) {
@@ -569,8 +588,9 @@ __global__ __launch_bounds__(64 * MXF0_WAVES, MX_WAVES_PER_SIMD) void stgcn_trai
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int g = lane >> 4, col = lane & 15;
     const int tileNP = N * P;
+    const MxLds ld = mx_lds(a.buf_floats, MXF0_WAVES);
     double* const pairbuf = reinterpret_cast<double*>(smem_all);                       // [MXF0_WAVES][2 F]
-    float* const smem = smem_all + 2 * MXF0_WAVES * 2 * F + wave * (a.buf_floats + (MX_MIN_BUF_BYTES + MX_SHIFT_TILE_BYTES) / 4);
+    float* const smem = smem_all + ld.waves + wave * ld.wave_floats;
 
     int64_t tile = (int64_t)blockIdx.x * MXF0_WAVES + wave;
     const int64_t tstride = (int64_t)gridDim.x * MXF0_WAVES;
@@ -626,16 +646,16 @@ __global__ __launch_bounds__(64 * MXF0_WAVES, MX_WAVES_PER_SIMD) void stgcn_trai
     }
     const int ca_col = slot_chan(col);                    // adjacency: gram[4 b + r] of lane (g, col) = A_b[slot 4 g + r][slot col]
     float sa[3] = {0.f, 0.f, 0.f}, sb[3] = {0.f, 0.f, 0.f};
-    mx_zero_padding_rows(smem + a.buf_floats, lane);
+    mx_zero_padding_rows(smem + ld.cur, lane);
 
     for (int it = 0; tile < a.ntiles; ++it, tile += tstride) {
         float* const tileA = smem;
-        float* const cur = smem + a.buf_floats;
+        float* const cur = smem + ld.cur;
         const int64_t s0 = tile * 4;
         const int ns = (int)((a.B - s0) < 4 ? (a.B - s0) : 4);
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_wave_barrier();
-        u32x2* sh_tile = reinterpret_cast<u32x2*>(cur + MX_MIN_BUF_BYTES / 4);
+        u32x2* sh_tile = reinterpret_cast<u32x2*>(cur + ld.sh);
 
         float X0[F], X[4][3];
         f32x16 gram;
@@ -815,6 +835,9 @@ template <int NT> struct MxwGeom {
     static constexpr int shift_bytes = 2 * (4 * W + 1) * 8;                // hi plane and lo plane: [4 row groups][W] + the zero slot
     static constexpr int region_bytes = ((conv_bytes > shift_bytes ? conv_bytes : shift_bytes) + 15) & ~15;
     static constexpr int theta_bytes(int L) { return L * NT * NT * 64 * 16; }
+    // the whole block (floats): the theta operands, then per wavefront [window buffer | conversion / shift region]
+    static constexpr int wave_floats(int buf_floats) { return buf_floats + region_bytes / 4; }
+    static constexpr int total(int L, int buf_floats) { return theta_bytes(L) / 4 + MXW_WAVES * wave_floats(buf_floats); }
 };
 
 template <int LFIX, int NT, int NFIX, int PFIX>
@@ -829,7 +852,7 @@ __global__ __launch_bounds__(64 * MXW_WAVES, 2) void stgcn_forward_mxw_kernel(co
     const int g = lane >> 4, col = lane & 15;
     const int NP = N * P;
     u32x4* const theta_lds = reinterpret_cast<u32x4*>(smem);
-    float* const win = smem + G::theta_bytes(L) / 4 + wave * (a.buf_floats + G::region_bytes / 4);
+    float* const win = smem + G::theta_bytes(L) / 4 + wave * G::wave_floats(a.buf_floats);
     float* const cur = win + a.buf_floats;
     const int64_t stride = (int64_t)gridDim.x * MXW_WAVES;
     int64_t smp = (int64_t)blockIdx.x * MXW_WAVES + wave;
@@ -1154,10 +1177,13 @@ static bool mx_shape_ok(const rulgnn_stgcn_shape* s, const float* x) {
     return true;
 }
 
-// LDS of a wavefront: [window buffer: 4 samples | conversion tile + shift tile].  The safety net stages its tile (and its transpose
-// scratch, PT_FLOATS) in the first region and keeps its weights in the second.
-constexpr int MX_CONV_BYTES = MX_MIN_BUF_BYTES + MX_SHIFT_TILE_BYTES;
 static_assert(EvalWeightsLds<16>::floats(MX_MAX_LAYERS) * 4 <= MX_CONV_BYTES, "the safety net's weights live in the conversion region");
+// Pinned (the launches' requests must not move with an edit of the layouts): the eval kernel | F_0 at 14 x 30, 14 x 50, 15 x 16, 16 x 16
+// (window buffers of 1680, 2800, 960, 1024 floats); the wide eval kernel at two layers, 16 x 16 and 40 x 64
+static_assert(4 * mx_lds(1680, 1).total == 12880 && 4 * mx_lds(2800, 1).total == 17360 && 4 * mx_lds(960, 1).total == 10000 && 4 * mx_lds(1024, 1).total == 10256);
+static_assert(4 * mx_lds(1680, MXF0_WAVES).total == 52160 && 4 * mx_lds(2800, MXF0_WAVES).total == 70080 && 4 * mx_lds(960, MXF0_WAVES).total == 40640 &&
+              4 * mx_lds(1024, MXF0_WAVES).total == 41664 && 4 * mx_lds(10240, MXF0_WAVES).total == 189120);
+static_assert(4 * MxwGeom<2>::total(2, 256) == 36864 && 4 * MxwGeom<3>::total(2, 2560) == 129024 && 4 * MxwGeom<2>::total(3, 420) == 46208);
 static int mx_buf_floats(const rulgnn_stgcn_shape* s) {
     int bytes = 4 * s->num_patch * s->patch_size * 4;
     if (bytes < PT_FLOATS * 4) bytes = PT_FLOATS * 4;
@@ -1171,7 +1197,7 @@ static int mx_launch(const rulgnn_stgcn_shape* s, const float* x, const float* p
     a.B = s->batch; a.ntiles = (s->batch + 3) / 4; a.N = s->num_patch; a.P = s->patch_size; a.L = s->num_layers;
     a.buf_floats = mx_buf_floats(s);
     a.taps = taps;
-    const size_t lds = (size_t)a.buf_floats * sizeof(float) + MX_CONV_BYTES;
+    const size_t lds = sizeof(float) * (size_t)mx_lds(a.buf_floats, 1).total;
     auto kern = &stgcn_forward_mx_kernel<L, NFIX, PFIX, TAPS>;
     if (const int rc = allow_dynamic_lds(kern, lds, 64 * 1024); rc != RULGNN_OK) return rc;
     auto [cus, per_cu] = residency(kern, 64, lds);
@@ -1182,9 +1208,7 @@ static int mx_launch(const rulgnn_stgcn_shape* s, const float* x, const float* p
     if (const char* e = getenv("RULGNN_MX_BLOCKS_PER_CU")) { const int v = atoi(e); if (v > 0) per_cu = v; }   // tuning aid
     int64_t grid = (int64_t)cus * per_cu;
     if (grid > a.ntiles) grid = a.ntiles;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64), lds, stream, x, prm, bn, out, a);
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return launch_checked(kern, dim3((unsigned)grid), dim3(64), lds, stream, x, prm, bn, out, a);
 }
 
 template <int L, bool TAPS>
@@ -1232,7 +1256,7 @@ static int train_f0_mx_launch(const rulgnn_stgcn_shape* s, const float* x, const
     a.taps = nullptr;
     MxF0Out o;
     o.cacheX = cacheX; o.cacheA = cacheA; o.H0 = H0; o.Z1 = Z1; o.cells = cells_bn0; o.cell_stride = cell_stride_doubles; o.replicas = replicas;
-    const size_t lds = MXF0_WAVES * ((size_t)a.buf_floats * sizeof(float) + MX_CONV_BYTES) + sizeof(double) * MXF0_WAVES * 2 * F;
+    const size_t lds = sizeof(float) * (size_t)mx_lds(a.buf_floats, MXF0_WAVES).total;
     auto launch = [&](auto kern) -> int {
         if (const int rc = allow_dynamic_lds(kern, lds, 80 * 1024); rc != RULGNN_OK) return rc;
         auto [cus, per_cu] = residency(kern, 64 * MXF0_WAVES, lds);
@@ -1240,9 +1264,7 @@ static int train_f0_mx_launch(const rulgnn_stgcn_shape* s, const float* x, const
         int64_t grid = (int64_t)cus * per_cu;
         const int64_t want = (a.ntiles + MXF0_WAVES - 1) / MXF0_WAVES;
         if (grid > want) grid = want;
-        (void)hipGetLastError();
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * MXF0_WAVES), lds, stream, x, prm, a, o, hs);
-        return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+        return launch_checked(kern, dim3((unsigned)grid), dim3(64 * MXF0_WAVES), lds, stream, x, prm, a, o, hs);
     };
     if (s->num_patch == 14 && s->patch_size == 30) return launch(&stgcn_train_f0_mx_kernel<14, 30, PACKED>);
     if (s->num_patch == 14 && s->patch_size == 50) return launch(&stgcn_train_f0_mx_kernel<14, 50, PACKED>);
@@ -1266,15 +1288,13 @@ static int mxw_launch(const rulgnn_stgcn_shape* s, const float* x, const float* 
     a.B = s->batch; a.ntiles = s->batch; a.N = s->num_patch; a.P = s->patch_size; a.L = s->num_layers;
     a.buf_floats = (s->num_patch * s->patch_size + 3) & ~3;
     a.taps = nullptr;
-    const size_t lds = (size_t)G::theta_bytes(L) + (size_t)MXW_WAVES * ((size_t)a.buf_floats * 4 + G::region_bytes);
+    const size_t lds = sizeof(float) * (size_t)G::total(L, a.buf_floats);
     auto kern = &stgcn_forward_mxw_kernel<L, NT, NFIX, PFIX>;
     if (const int rc = allow_dynamic_lds(kern, lds); rc != RULGNN_OK) return rc;
     const int cus = device_cu_count();
     int64_t grid = (s->batch + MXW_WAVES - 1) / MXW_WAVES;
     if (grid > cus) grid = cus;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * MXW_WAVES), lds, stream, x, prm, bn, out, a);
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return launch_checked(kern, dim3((unsigned)grid), dim3(64 * MXW_WAVES), lds, stream, x, prm, bn, out, a);
 }
 
 template <int L>

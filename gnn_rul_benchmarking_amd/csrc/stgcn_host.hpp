@@ -122,8 +122,9 @@ int stgcn_tiled_train(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args
 size_t stgcn_train_workspace_bytes(const rulgnn_stgcn_shape* s);
 // The LDS bytes a launch form of the fused row-mapped kernels requests at this shape (and MPNN order): the exact eval kernel, the scan
 // behind the wide matrix-core eval kernel (order 1), the largest phase of the fp32 training chain; 0 where the row-mapped geometry does
-// not apply.  The launchers size their launches with these and the C-ABI gates (rulgnn_api.hip) compare them with MAX_LDS_BYTES (launch.hpp), so a
-// shape the gates accept cannot fail a launcher's LDS check after an earlier launch of the same call has run.
+// not apply.  Each is the `total` of the layout the kernels carve from and the launchers size their launches with (EvalWeightsLds,
+// train_lds); the C-ABI gates (rulgnn_api.hip) compare them with MAX_LDS_BYTES (launch.hpp), so a shape the gates accept cannot fail a
+// launcher's LDS check after an earlier launch of the same call has run.
 size_t stgcn_forward_exact_lds_bytes(const rulgnn_stgcn_shape* s);
 size_t stgcn_forward_fixup_lds_bytes(const rulgnn_stgcn_shape* s);
 size_t stgcn_train_chain_lds_bytes(const rulgnn_stgcn_shape* s);

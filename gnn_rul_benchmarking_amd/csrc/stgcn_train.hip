@@ -82,7 +82,7 @@ struct TrainK {
     int N, P, Ppad, vec4, stage_floats;
     uint32_t magicP;
     int do_backward;      // TOP: 0 = forward only
-    int wave_area_floats;
+    int wave_area_floats; // TrainLds::wave_floats of the phase (an argument: derived in the kernel, it costs the phases registers)
     int write_pred;
     int has_dpred;        // 1: gy is d(loss)/d(pred); 0: gy is y (MSE); 2: neither (forward only)
     float dropout_p, drop_scale;
@@ -205,6 +205,36 @@ constexpr int phase_min_waves(int RW, int KIND, int IDX) {
     return IDX % 2 == 1 ? PHASE_WAVES_G1 : PHASE_WAVES_G0;
 }
 
+// LDS of a phase (floats), for the body's carve, the launchers and the C-ABI gate alike: the workgroup's part, then one area per wavefront.
+// Only wave_floats (the kernels read it from TrainK::wave_area_floats) and total depend on `stage_floats`.
+struct TrainLds {
+    int w_cur, w_aux, w_tr, vecs, bnc, red, redp, convT, wave_area, wave_floats, total;
+    int red_th, red_k1;     // rows of one [N][N] weight-gradient accumulator in the block reduction; rows of order 1 (orders 2.. behind them)
+};
+__host__ __device__ constexpr TrainLds train_lds(int RW, int L, int kind, int idx, int kord, int stage_floats = 0) {
+    const int nth = RW == 16 ? 0 : (RW / 16) * (RW / 16);      // theta-gradient MFMA tiles (generic path)
+    // three zero-padded [RW][wstride] weight slots: theta of layer LY | theta of layer LY-1 (F_{2l}) or fc1 (TOP) | the transposed matrix the
+    // backward needs (theta^T for G_{2l}, fc1^T for TOP).  Order kord > 1 (F_{2l} / G_{2l} only): kord slots in all -- theta_kk for F_{2l},
+    // theta_kk^T for G_{2l}.
+    const int slot = RW * (RW + 4);
+    const int ncur = kord == 1 ? 1 : (kind == PH_F ? kord : 0), naux = kord == 1 ? 1 : 0, ntr = kord == 1 ? 1 : (kind == PH_G ? kord : 0);
+    TrainLds l{};
+    l.red_th = RW == 16 ? 4 : 4 * nth;
+    l.red_k1 = 15 + 4 * nth;
+    l.w_cur = 2 * cell_stride(L);                              // behind [cell_stride] doubles: the reduction cells, replicas summed
+    l.w_aux = l.w_cur + ncur * slot;
+    l.w_tr = l.w_aux + naux * slot;
+    l.vecs = l.w_tr + ntr * slot;                              // [L+2][RW]  theta bias (summed over the orders), fc1 bias, fc2 weight
+    l.bnc = l.vecs + (L + 2) * RW;                             // [2L][BNC][F] (+pad to 4)
+    l.red = l.bnc + ((2 * L * BNC * F + 3) & ~3);              // [red_k1 + (kord - 1) red_th][64] block reduction of the gradient accumulators
+    l.redp = l.red + (l.red_k1 + (kord - 1) * l.red_th) * 64;  // [4 waves][24] BatchNorm pair / loss partials
+    l.convT = l.redp + WAVES_PER_BLOCK * 24;                   // [F][2F] conv_block1 weights of layer LY as [ci][co][tap] (G_{2l} only)
+    l.wave_area = l.convT + CONVT_FLOATS;                      // per wavefront: staging (F_0) or transpose tile (G; TOP at the generic row width)
+    l.wave_floats = kind == PH_F ? (idx == 0 ? stage_floats : 0) : ((kind == PH_G || RW != 16) ? TT_ROWS * TT_STRIDE : 0);
+    l.total = l.wave_area + WAVES_PER_BLOCK * l.wave_floats;
+    return l;
+}
+
 // NFIX: num_patch known at compile time (14 = C-MAPSS, the headline shape; 0 = read it from the arguments).  With a constant
 // pitch the 10 element addresses of a saved tensor become immediate offsets of one base: ~60 64-bit address computations per
 // tile and the scalar registers that carried them disappear.
@@ -253,27 +283,14 @@ __device__ __forceinline__ void train_phase_body(const float* __restrict__ gx, c
     constexpr bool NEED_A = KIND != PH_TOP && BLK == 0;
     constexpr bool NEED_X = NEED_A || KIND == PH_TOP;
 
-    // ---- LDS carve --------------------------------------------------------------------------------
-    // three zero-padded [RW][TWS] weight slots: theta of layer LY | theta of layer LY-1 (F_{2l}) or fc1 (TOP) |
-    // the transposed matrix the backward needs (theta^T for G_{2l}, fc1^T for TOP)
-    // Order KORD > 1 (F_{2l} / G_{2l} only): KORD slots in all -- theta_kk for F_{2l}, theta_kk^T for G_{2l}.
+    // ---- LDS carve (train_lds) -------------------------------------------------------------------
     constexpr int CS = cell_stride(L);
-    constexpr int NCUR = KORD == 1 ? 1 : (KIND == PH_F ? KORD : 0), NAUX = KORD == 1 ? 1 : 0, NTR = KORD == 1 ? 1 : (KIND == PH_G ? KORD : 0);
+    constexpr TrainLds LD = train_lds(RW, L, KIND, IDX, KORD);
+    constexpr int RED_TH = LD.red_th, RED_K1 = LD.red_k1;
     double* cellsum = reinterpret_cast<double*>(smem);     // [CS] the reduction cells, replicas summed
-    float* w_cur = smem + 2 * CS;
-    float* w_aux = w_cur + NCUR * TRW * TWS;
-    float* w_tr = w_aux + NAUX * TRW * TWS;
-    float* vecs = w_tr + NTR * TRW * TWS;                 // [L+2][RW]        theta bias (summed over the orders), fc1 bias, fc2 weight
-    float* bnc = vecs + (L + 2) * TRW;                    // [NBN][BNC][F] (+pad to 4)
-    constexpr int RED_TH = RW == 16 ? 4 : 4 * NTH;        // rows of one [N][N] weight-gradient accumulator in the block reduction
-    constexpr int RED_K1 = 15 + (RW == 16 ? 0 : 4 * NTH);
-    constexpr int RED_K = RED_K1 + (KORD - 1) * RED_TH;   // orders 2.. behind the rows of order 1
-    float* red = bnc + ((NBN * BNC * F + 3) & ~3);        // [RED_K][64] block reduction of the gradient accumulators
-    float* redp = red + RED_K * 64;                       // [4 waves][24] BatchNorm pair / loss partials
-    float* convT = redp + WAVES_PER_BLOCK * 24;           // [F][2F] conv_block1 weights of layer LY as [ci][co][tap] (G_{2l} only)
-    float* wave_area = convT + CONVT_FLOATS;              // per-wave: staging (F_0) or transpose tile (TOP / G)
-    const int wave_area_floats = a.wave_area_floats;
-    float* mywave = wave_area + wave * wave_area_floats;
+    float *w_cur = smem + LD.w_cur, *w_aux = smem + LD.w_aux, *w_tr = smem + LD.w_tr, *vecs = smem + LD.vecs, *bnc = smem + LD.bnc;
+    float *red = smem + LD.red, *redp = smem + LD.redp, *convT = smem + LD.convT;
+    float* mywave = smem + LD.wave_area + wave * a.wave_area_floats;
 
     // ---- prologue: weights to LDS, BatchNorm constants from the reduction cells ---------------------
     if constexpr (KORD == 1) {
@@ -1160,61 +1177,64 @@ size_t stgcn_train_workspace_bytes(const rulgnn_stgcn_shape* s) {
     return w.total;
 }
 
-static int wave_area_for(int kind, int idx, const TileGeom& g) {
-    if (kind == PH_F) return idx == 0 ? g.stage_floats : 0;
-    if (kind == PH_G) return TT_ROWS * TT_STRIDE;
-    return g.RW == 16 ? 0 : TT_ROWS * TT_STRIDE;          // TOP, generic row width: fc1 gradient through the transpose tile
-}
-
-// (kord: the order a theta phase is specialised on -- 1 for every other phase; mirrors the LDS carve of train_phase_body)
-static size_t train_lds_bytes(int RW, int L, int wave_area, int kord = 1) {
-    const int tws = RW + 4, nth = RW == 16 ? 0 : (RW / 16) * (RW / 16);
-    const int slots = kord == 1 ? 3 : kord, red_th = RW == 16 ? 4 : 4 * nth;
-    const size_t fl = (size_t)2 * cell_stride(L) + (size_t)slots * RW * tws + (size_t)(L + 2) * RW + (size_t)((2 * L * BNC * F + 3) & ~3) +
-                      (size_t)(15 + 4 * nth + (kord - 1) * red_th) * 64 + (size_t)WAVES_PER_BLOCK * 24 + CONVT_FLOATS +
-                      (size_t)WAVES_PER_BLOCK * wave_area;
-    return fl * sizeof(float);
-}
-
 // The order a phase kernel is specialised on (launch_phase): the theta phases F_{2l} / G_{2l} carry MPNN order k, every other phase 1.
-static int phase_kord(int kind, int idx, int K) { return K > 1 && (kind == PH_F || kind == PH_G) && idx % 2 == 0 ? K : 1; }
+static constexpr int phase_kord(int kind, int idx, int K) { return K > 1 && (kind == PH_F || kind == PH_G) && idx % 2 == 0 ? K : 1; }
 
-// The LDS bytes one fp32 phase kernel requests (launch_phase_n sizes its launch with this).
-static size_t phase_lds_bytes(int RW, int L, int kind, int idx, const TileGeom& g, int kord) {
-    return train_lds_bytes(RW, L, wave_area_for(kind, idx, g), kord);
+// The most LDS (floats) any phase of the fp32 chain requests, and what the cooperative launch -- every phase body at order 1 -- requests
+static constexpr int train_chain_lds(int RW, int L, int K, int stage_floats) {
+    int m = train_lds(RW, L, PH_TOP, 0, 1, stage_floats).total;
+    for (int i = 0; i < 2 * L; ++i)
+        for (const int kind : {PH_F, PH_G}) m = std::max(m, train_lds(RW, L, kind, i, phase_kord(kind, i, K), stage_floats).total);
+    return m;
 }
+// Pinned (the launches' requests must not move with an edit of train_lds): the bytes at the shapes of tests/test_stgcn_lds_envelope_gpu.py (the last window
+// that fits and the first that does not, orders 1 to 3) and the C-MAPSS shapes: {RW, layers, order, stage_floats, chain bytes, coop bytes}
+constexpr int TRAIN_LDS_PINS[][6] = {
+    {64, 2, 1, 6832, 186432, 186432}, {64, 2, 1, 6932, 188032, 188032}, {64, 2, 1, 6840, 186560, 186560}, {64, 2, 1, 6960, 188480, 188480}, {64, 2, 1, 6864, 186944, 186944}, {64, 2, 1, 6912, 187712, 187712},
+    {64, 2, 1, 7008, 189248, 189248}, {64, 2, 1, 6848, 186688, 186688}, {64, 2, 1, 7040, 189760, 189760}, {64, 8, 1, 3724, 145440, 145440}, {64, 8, 1, 3776, 146272, 146272}, {64, 8, 1, 3680, 144736, 144736},
+    {16, 8, 1, 9152, 165600, 165600}, {64, 2, 1, 5372, 163072, 163072}, {64, 2, 1, 5456, 164416, 164416}, {64, 2, 1, 5496, 165056, 165056}, {64, 2, 1, 5400, 163520, 163520}, {64, 2, 1, 5520, 165440, 165440},
+    {64, 2, 1, 5328, 162368, 162368}, {64, 2, 1, 5472, 164672, 164672}, {64, 2, 1, 5312, 162112, 162112}, {64, 2, 1, 5504, 165184, 165184}, {64, 2, 2, 4336, 145472, 146496}, {64, 2, 2, 4388, 146304, 147328},
+    {64, 2, 2, 4600, 149696, 150720}, {64, 2, 2, 4720, 151616, 152640}, {64, 2, 2, 5400, 162496, 163520}, {64, 2, 2, 5520, 164416, 165440}, {64, 2, 2, 4544, 148800, 149824}, {64, 2, 2, 4736, 151872, 152896},
+    {64, 2, 2, 5312, 161088, 162112}, {64, 2, 2, 5504, 164160, 165184}, {64, 2, 3, 3368, 163776, 131008}, {64, 2, 3, 3384, 164032, 131264}, {64, 2, 3, 4064, 174912, 142144}, {64, 2, 3, 4116, 175744, 142976},
+    {64, 1, 3, 3452, 163664, 130896}, {64, 1, 3, 3504, 164496, 131728}, {64, 2, 3, 2520, 150208, 117440}, {64, 2, 3, 2640, 152128, 119360}, {64, 2, 3, 3320, 163008, 130240}, {64, 2, 3, 3440, 164928, 132160},
+    {64, 2, 3, 2496, 149824, 117056}, {64, 2, 3, 2688, 152896, 120128}, {64, 2, 3, 3264, 162112, 129344}, {64, 2, 3, 3456, 165184, 132416}, {16, 2, 1, 1680, 44224, 44224}, {16, 2, 1, 2800, 56384, 56384},
+    {16, 3, 1, 1680, 45488, 45488}, {16, 2, 1, 1152, 44224, 44224}, {16, 3, 3, 800, 47536, 45488},
+};
+constexpr bool train_lds_pins_hold() {
+    for (const auto& p : TRAIN_LDS_PINS)
+        if (4 * train_chain_lds(p[0], p[1], p[2], p[3]) != p[4] || 4 * train_chain_lds(p[0], p[1], 1, p[3]) != p[5]) return false;
+    return true;
+}
+static_assert(train_lds_pins_hold(), "the fp32 phases request the LDS they always did");
+// single phases -- 14 x 30, two layers: TOP, F_0, F_1, G_0; 9 x 21, three layers, order 3: F_0, F_2, G_2, G_3; 40 x 135, two layers, order 2: F_0, F_2, G_0
+static_assert(4 * train_lds(16, 2, PH_TOP, 0, 1, 1680).total == 11584 && 4 * train_lds(16, 2, PH_F, 0, 1, 1680).total == 38464 &&
+              4 * train_lds(16, 2, PH_F, 1, 1, 1680).total == 11584 && 4 * train_lds(16, 2, PH_G, 0, 1, 1680).total == 44224 &&
+              4 * train_lds(16, 3, PH_F, 0, 3, 800).total == 27696 && 4 * train_lds(16, 3, PH_F, 2, 3, 800).total == 14896 &&
+              4 * train_lds(16, 3, PH_G, 2, 3, 800).total == 47536 && 4 * train_lds(16, 3, PH_G, 3, 1, 800).total == 45488 &&
+              4 * train_lds(64, 2, PH_F, 0, 2, 5400).total == 162496 && 4 * train_lds(64, 2, PH_F, 2, 2, 5400).total == 76096 &&
+              4 * train_lds(64, 2, PH_G, 0, 2, 5400).total == 108736);
 
 // The most LDS any phase of the fp32 chain requests at this shape and order; 0 where the row-mapped geometry does not apply.
 size_t stgcn_train_chain_lds_bytes(const rulgnn_stgcn_shape* s) {
     TileGeom g;
     if (train_geometry(s, &g) != RULGNN_OK) return 0;
-    const int L = s->num_layers, K = s->mpnn_k;
-    size_t lds = phase_lds_bytes(g.RW, L, PH_TOP, 0, g, 1);
-    const int kinds[2] = {PH_F, PH_G};
-    for (int i = 0; i < 2 * L; ++i) {
-        for (const int kind : kinds) {
-            const size_t b = phase_lds_bytes(g.RW, L, kind, i, g, phase_kord(kind, i, K));
-            if (b > lds) lds = b;
-        }
-    }
-    return lds;
+    return sizeof(float) * (size_t)train_chain_lds(g.RW, s->num_layers, s->mpnn_k, g.stage_floats);
 }
 
 template <int RW, int L, int KIND, int IDX, int NFIX, int PFIX = 0, int KORD = 1>
 static int launch_phase_n(const TrainK& k_in, const float* x, const float* prm, const float* gy, const TileGeom& g, int max_grid,
                           hipStream_t stream, int* grid_out) {
     auto kern = stgcn_train_phase_kernel<RW, L, KIND, IDX, NFIX, PFIX, KORD>;
+    const TrainLds ld = train_lds(RW, L, KIND, IDX, KORD, g.stage_floats);
     TrainK k = k_in;
-    k.wave_area_floats = wave_area_for(KIND, IDX, g);
-    const size_t lds = phase_lds_bytes(RW, L, KIND, IDX, g, KORD);
+    k.wave_area_floats = ld.wave_floats;
+    const size_t lds = sizeof(float) * (size_t)ld.total;
     // (above MAX_LDS_BYTES: a backstop, the C-ABI gate (stgcn_train_workspace_bytes) keeps such shapes out)
     RULGNN_TRY(allow_dynamic_lds(kern, lds));
     int grid = persistent_grid(kern, k.ntiles, lds);
     if (grid > max_grid) grid = max_grid;
     if (grid_out) *grid_out = grid;
-    (void)hipGetLastError();   // drop any stale error of the caller's earlier HIP calls
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(BLOCK), lds, stream, x, prm, gy, k);
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return launch_checked(kern, dim3(grid), dim3(BLOCK), lds, stream, x, prm, gy, k);
 }
 
 template <int RW, int L, int KIND, int IDX>
@@ -1382,7 +1402,7 @@ __device__ __forceinline__ float* coop_smem() {
 
 struct CoopK {
     unsigned* barrier;          // one zeroed 32-bit counter in the workspace
-    int wa_f0, wa_g, wa_top;    // per-wavefront LDS area of F_0 / the G phases / TOP (wave_area_for)
+    int wa_f0, wa_g, wa_top;    // per-wavefront LDS area of F_0 / the G phases / TOP (TrainLds::wave_floats)
     StepState* st;              // optional device step state
     uint64_t seed, step;
     int has_adam;
@@ -1453,12 +1473,10 @@ static int launch_coop(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_arg
                        const WsLayout& w, const TileGeom& g, const rulgnn_adam_args* opt, double bn_count) {
     auto kern = stgcn_train_coop_kernel<RW, L, NFIX, PFIX>;
     CoopK c{};
-    c.wa_f0 = wave_area_for(PH_F, 0, g);
-    c.wa_g = wave_area_for(PH_G, 0, g);
-    c.wa_top = wave_area_for(PH_TOP, 0, g);
-    int wa = c.wa_f0 > c.wa_g ? c.wa_f0 : c.wa_g;
-    wa = wa > c.wa_top ? wa : c.wa_top;
-    size_t lds = train_lds_bytes(RW, L, wa);
+    c.wa_f0 = train_lds(RW, L, PH_F, 0, 1, g.stage_floats).wave_floats;
+    c.wa_g = train_lds(RW, L, PH_G, 0, 1).wave_floats;
+    c.wa_top = train_lds(RW, L, PH_TOP, 0, 1).wave_floats;
+    size_t lds = sizeof(float) * (size_t)train_chain_lds(RW, L, 1, g.stage_floats);
     if (lds < sizeof(float) * FIN_SLICES * FIN_COLS) lds = sizeof(float) * FIN_SLICES * FIN_COLS;
     const int64_t grid = (k.ntiles + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
     if (grid > w.max_grid) return RULGNN_EUNSUPPORTED;
@@ -1496,9 +1514,7 @@ static int launch_coop(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_arg
     f.write_loss = (k.has_dpred == 0) && a->loss;
     const float* gy = a->dpred ? a->dpred : a->y;
     if (hipMemsetAsync(c.barrier, 0, sizeof(unsigned), stream) != hipSuccess) return RULGNN_EHIP;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(BLOCK), lds, stream, a->x, a->params, gy, k, c);
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return launch_checked(kern, dim3((unsigned)grid), dim3(BLOCK), lds, stream, a->x, a->params, gy, k, c);
 }
 
 template <int RW, int L>
@@ -1669,9 +1685,7 @@ static int run_train_rw(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_ar
     f.write_grads = mode != TM_FORWARD;
     f.write_loss = (k.has_dpred == 0) && a->loss;
     const int fgrid = f.write_grads ? (k.pcount + FIN_COLS - 1) / FIN_COLS : 1;
-    (void)hipGetLastError();   // drop any stale error of the caller's earlier HIP calls
-    hipLaunchKernelGGL(stgcn_train_finalize_kernel, dim3(fgrid), dim3(FIN_COLS * FIN_SLICES), 0, stream, f);
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return launch_checked(stgcn_train_finalize_kernel, dim3(fgrid), dim3(FIN_COLS * FIN_SLICES), 0, stream, f);
 }
 
 template <int L>
@@ -1711,10 +1725,8 @@ static int run_phase(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args*
     if (phase == -1) {
         // the step's prepare kernel alone: clears the reduction cells (same dropout step) so that a harness timing the phases one by one
         // runs them on valid BatchNorm statistics -- cells that keep accumulating from launch to launch drive the statistics out of range
-        (void)hipGetLastError();
-        hipLaunchKernelGGL(stgcn_prepare_kernel, dim3(1), dim3(1024), 0, stream, k.cells, 0, cell_stride(L), cell_stride(L), step_scratch(k.cells, L),
-                           (StepState*)nullptr, a->seed, a->step, L, 1, 0, (int64_t)0, 0.f, 0.f, 0.f, (double)s->batch * (double)s->num_patch);
-        return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+        return launch_checked(stgcn_prepare_kernel, dim3(1), dim3(1024), 0, stream, k.cells, 0, cell_stride(L), cell_stride(L), step_scratch(k.cells, L),
+                              (StepState*)nullptr, a->seed, a->step, L, 1, 0, (int64_t)0, 0.f, 0.f, 0.f, (double)s->batch * (double)s->num_patch);
     }
     if (phase < 0 || phase > 4 * L) return RULGNN_EINVAL;
     const float* gy = a->dpred ? a->dpred : a->y;

@@ -90,6 +90,37 @@ __device__ __forceinline__ void mxp_dump() {
 #define MXP_MARK() do {} while (0)
 #define MXP_MARKI(ID) do {} while (0)
 #endif
+// LDS of a phase (floats), for the body's carve and the launchers alike.  Workgroup: [BatchNorm table | gradient row image | pair
+// partials]; then one region per wavefront (the wavefronts only meet in the prologue and the epilogue).
+struct MxtLds {
+    int bnc, red, pairbuf, waves;                                       // the workgroup's part; `waves`: the wavefronts' regions
+    int zero, scr, sh, wg, X, A, SB, DX, XP, HS, H, wave_floats;        // within a region
+    int total;
+};
+__host__ __device__ constexpr MxtLds mxt_lds(int L, int kind, int idx, int nfix, int N) {
+    const MxtTraits t = mxt_traits(L, kind, idx, nfix);
+    const int XF = 40 * N;                                   // one [10][4 N] tile
+    MxtLds l{};
+    l.bnc = 0;                                               // [2L][BN_TABLE_ROWS][F], the rows this phase uses
+    l.red = l.bnc + ((2 * L * MXT_BNC * F + 3) & ~3);        // [MXT_RED_FLOATS]
+    l.pairbuf = l.red + MXT_RED_FLOATS;                      // [MXT_WAVES][2 F + 1] doubles
+    l.waves = l.pairbuf + 2 * MXT_WAVES * (2 * F + 2);
+    l.zero = 0;
+    l.scr = l.zero + MXT_ZERO_FLOATS;
+    l.sh = l.scr + MXT_SCRATCH_FLOATS;
+    l.wg = l.sh + MXT_SHIFT_FLOATS;                          // G: the transposing image of the weight gradient's operands
+    l.X = l.wg + (kind == PH_G ? MXT_WG_FLOATS : 0);         // X_LIN, or H_LY (H_IN)
+    l.A = l.X + XF;                                          // the adjacency tile, or H_LY (H_TOP)
+    l.SB = l.A + (t.H_TOP ? XF : t.AF);                      // G_{2l}
+    l.DX = l.SB + (t.NEED_SB ? XF : 0);                      // gradient in (full tile or TOP's two rows)
+    l.XP = l.DX + (t.GRAD_IN ? XF : 0);                      // G_{2l}, l >= 1: the gated x-hat of BatchNorm 2l-1
+    l.HS = l.XP + (t.BWD_PREV ? XF : 0);                     // the staging tile (TILE_OUT)
+    l.H = l.HS + (t.TILE_OUT ? XF : 0);                      // H_TILE: H_{l-1} (F_{2l}) / H_l (G_{2l})
+    l.wave_floats = l.H + (t.H_TILE ? XF : 0);
+    l.total = l.waves + MXT_WAVES * l.wave_floats;
+    return l;
+}
+
 template <int L, int KIND, int IDX, int NFIX, bool PERSIST>
 __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_all, unsigned target) {
     MXP_MARKI(100 + KIND * 10 + IDX);                                              // phase entry
@@ -99,50 +130,22 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
     const int g = lane >> 4, col = lane & 15;
     constexpr int NBN = 2 * L;
     constexpr int CS = cell_stride(L);
-    constexpr int LY = KIND == PH_TOP ? L - 1 : IDX / 2;
-    constexpr int BLK = KIND == PH_TOP ? 1 : IDX % 2;
-    constexpr bool WITH_PREV = KIND == PH_F && BLK == 0 && LY >= 1;     // F_{2l}: layer l-1 in full first (its input is this phase's input)
-    constexpr bool BWD_PREV = KIND == PH_G && BLK == 0 && LY >= 1;      // G_{2l}: the sums of BatchNorm 2l-1 (its gated x-hat comes from F_{2l})
-    constexpr int LIN = WITH_PREV ? LY - 1 : LY;                        // the layer whose input record is the main input
-    constexpr bool GRAD_IN = KIND == PH_G && (BLK == 1 || LY >= 1);     // a gradient tensor enters: d X_{l+1}
-    constexpr bool GRAD_TOP = GRAD_IN && LY == L - 1;                   // ... in TOP's (value, arg-max) form
-    constexpr bool NEED_SB = KIND == PH_G && BLK == 0;
-    // the H_l record (MxTrainK::hrec): the first phase of this file that computes H of layer LY writes it -- F_{2l}, l >= 1; F_1 for
-    // H_0 (F_0 has it only under its per-sample scale) where a reader of H_0 is switched on.  F_{2l+1} and G_{2l+1} need nothing else
-    // of X_l and A, and start from it.  (The readers beyond round 8's: MXT_H_READERS, stgcn_train_mx_ops.hpp)
-    constexpr bool H_OUT = KIND == PH_F && (WITH_PREV || (IDX == 1 && mxt_h0_record(L)));
-    constexpr bool H_IN = (KIND == PH_F && BLK == 1 && LY >= 1) || (KIND == PH_G && BLK == 1 && (LY >= 1 || MXT_H0_READ_G1));
-    constexpr bool H_TOP = KIND == PH_TOP && (LY >= 1 || MXT_H0_READ_TOP);   // TOP: X_l for the residual, H_l in place of the adjacency
-    constexpr bool H_PREV = WITH_PREV && MXT_H_READ_F_EVEN;            // F_{2l}: the pass over layer l-1 starts from H_{l-1}
-    constexpr bool H_GE = KIND == PH_G && BLK == 0 && mxt_g_even_reads_h(LY, NFIX);   // G_{2l}: H_l beside X_l and the adjacency
-    constexpr bool H_TILE = H_PREV || H_GE;                            // ... in a tile of its own (off_H)
+    constexpr MxtTraits T = mxt_traits(L, KIND, IDX, NFIX);
+    constexpr int LY = T.LY, BLK = T.BLK, LIN = T.LIN, AF = T.AF;
+    constexpr bool WITH_PREV = T.WITH_PREV, BWD_PREV = T.BWD_PREV, GRAD_IN = T.GRAD_IN, GRAD_TOP = T.GRAD_TOP, NEED_SB = T.NEED_SB;
+    constexpr bool H_OUT = T.H_OUT, H_IN = T.H_IN, H_TOP = T.H_TOP, H_PREV = T.H_PREV, H_GE = T.H_GE;
     static_assert(!(KIND == PH_F && IDX == 0), "F_0 is stgcn_train_f0_mx_kernel");
 
-    // ---- LDS carve (floats) ------------------------------------------------------------------------------------------------
+    // ---- LDS carve (mxt_lds) -----------------------------------------------------------------------------------------------
     const int XF = 40 * N;                                   // one [10][4 N] tile
-    constexpr int AF = H_IN ? 0 : 220;                       // the adjacency tile
-    // workgroup: [BatchNorm table | gradient row image | pair partials]; then one region per wavefront (the wavefronts only meet in the
-    // prologue and the epilogue)
-    constexpr int SH_BNC = (NBN * MXT_BNC * F + 3) & ~3;
-    float* const bnc = smem_all;                                                 // [NBN][BN_TABLE_ROWS][F], the rows this phase uses
-    float* const red = smem_all + SH_BNC;                                       // [MXT_RED_FLOATS]
-    double* const pairbuf = reinterpret_cast<double*>(red + MXT_RED_FLOATS);    // [MXT_WAVES][2 F + 1]
-    const int off_zero = 0;
-    const int off_scr = off_zero + MXT_ZERO_FLOATS;
-    const int off_sh = off_scr + MXT_SCRATCH_FLOATS;
-    const int off_wg = off_sh + MXT_SHIFT_FLOATS;            // G: the transposing image of the weight gradient's operands
-    const int off_X = off_wg + (KIND == PH_G ? MXT_WG_FLOATS : 0);          // X_LIN, or H_LY (H_IN)
-    const int off_A = off_X + XF;
-    const int off_SB = off_A + (H_TOP ? XF : AF);                           // G_{2l}
-    const int off_DX = off_SB + (NEED_SB ? XF : 0);          // gradient in (full tile or TOP's two rows)
-    const int off_XP = off_DX + (GRAD_IN ? XF : 0);          // G_{2l}, l >= 1: the gated x-hat of BatchNorm 2l-1
-    // every full-tile record this phase writes (F_{2l}: X_l, Q_l, H_l; G_{2l+1}: d(x0 + H); G_{2l}, l >= 1: d X_l) leaves through ONE
-    // staging tile per wavefront, one record after the other
-    constexpr bool TILE_OUT = WITH_PREV || H_OUT || (KIND == PH_G && BLK == 1) || BWD_PREV;
-    const int off_HS = off_XP + (BWD_PREV ? XF : 0);         // the staging tile
-    const int off_H = off_HS + (TILE_OUT ? XF : 0);          // H_TILE: H_{l-1} (F_{2l}) / H_l (G_{2l})
-    const int wave_floats = off_H + (H_TILE ? XF : 0);
-    float* const smem = smem_all + SH_BNC + MXT_RED_FLOATS + 2 * MXT_WAVES * (2 * F + 2) + wave * wave_floats;
+    constexpr MxtLds LC = mxt_lds(L, KIND, IDX, NFIX, NFIX);      // the workgroup's part and the offsets up to X do not depend on N
+    const MxtLds ld = mxt_lds(L, KIND, IDX, NFIX, N);
+    float* const bnc = smem_all + LC.bnc;
+    float* const red = smem_all + LC.red;
+    double* const pairbuf = reinterpret_cast<double*>(smem_all + LC.pairbuf);
+    const int off_zero = LC.zero, off_scr = LC.scr, off_sh = LC.sh, off_wg = LC.wg, off_X = LC.X;
+    const int off_A = ld.A, off_SB = ld.SB, off_DX = ld.DX, off_XP = ld.XP, off_HS = ld.HS, off_H = ld.H;
+    float* const smem = smem_all + LC.waves + wave * ld.wave_floats;
     u32x2* const sh_tile = reinterpret_cast<u32x2*>(smem + off_sh);
     u32x2* const wg_img = reinterpret_cast<u32x2*>(smem + off_wg);
 
@@ -1080,7 +1083,7 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
     const int NN = N * N;
     int rbase = 0, rlen = 0;
     // (image 0 in the workgroup's region, images 1 .. 3 over the wavefronts' regions -- dead by now, 4 x wave_floats >= 3 x MXT_RED_FLOATS)
-    float* const red2 = smem_all + SH_BNC + MXT_RED_FLOATS + 2 * MXT_WAVES * (2 * F + 2);
+    float* const red2 = smem_all + LC.waves;
     {
         float* const img = wave == 0 ? red : red2 + (wave - 1) * MXT_RED_FLOATS;
         auto put = [&](int idx, float v) { img[idx] = v; };
@@ -1199,41 +1202,38 @@ __global__ __launch_bounds__(64 * MXT_WAVES, MX_WAVES_PER_SIMD) void stgcn_train
 // =====================================================================================================================
 // host side
 // =====================================================================================================================
-static constexpr size_t mxt_lds_bytes(int L, int kind, int idx, int N) {
-    const int blk = kind == PH_TOP ? 1 : idx % 2, ly = kind == PH_TOP ? L - 1 : idx / 2;
-    const bool need_sb = kind == PH_G && blk == 0, grad_in = kind == PH_G && (blk == 1 || ly >= 1), bwd_prev = kind == PH_G && blk == 0 && ly >= 1;
-    const bool with_prev = kind == PH_F && blk == 0 && ly >= 1;
-    // H_IN of mxt_phase_body: no adjacency tile
-    const bool h_in = (kind == PH_F && blk == 1 && ly >= 1) || (kind == PH_G && blk == 1 && (ly >= 1 || MXT_H0_READ_G1));
-    const bool h_top = kind == PH_TOP && (ly >= 1 || MXT_H0_READ_TOP);            // H_TOP: an H tile in its place
-    // H_TILE: F_{2l} / G_{2l} with an H tile of their own (mxt_launch_n instantiates NFIX = 14 for N = 14, the generic body otherwise)
-    const bool h_tile = (with_prev && MXT_H_READ_F_EVEN) || (kind == PH_G && blk == 0 && mxt_g_even_reads_h(ly, N == 14 ? 14 : 0));
-    // the staging tile of the phases that write full-tile records (TILE_OUT of mxt_phase_body)
-    const bool stage = with_prev || (kind == PH_F && idx == 1 && mxt_h0_record(L)) || (kind == PH_G && blk == 1) || bwd_prev;
-    const int XF = 40 * N;
-    const size_t wave = (size_t)MXT_ZERO_FLOATS + MXT_SCRATCH_FLOATS + MXT_SHIFT_FLOATS + (kind == PH_G ? MXT_WG_FLOATS : 0) + XF + (h_in ? 0 : h_top ? XF : 220) + (need_sb ? XF : 0) + (grad_in ? XF : 0) +
-                        (bwd_prev ? XF : 0) + (stage ? XF : 0) + (h_tile ? XF : 0);
-    const size_t shared = (size_t)((2 * L * MXT_BNC * F + 3) & ~3) + MXT_RED_FLOATS + 2 * MXT_WAVES * (2 * F + 2);
-    return (shared + MXT_WAVES * wave) * sizeof(float);
-}
+constexpr int mxt_nfix(int N) { return N == 14 ? 14 : 0; }      // the NFIX mxt_launch_n instantiates
 // stgcn_train_mx_shape_ok admits num_patch <= 15 and at most MX_MAX_LAYERS layers: the largest request (G_{2l}, l >= 1: five tiles and the
 // transposing image per wavefront; six tiles where it reads H_l, which mxt_g_even_reads_h allows at N = 14 only) stays inside what a
 // launch may ask for -- 80 KB, two workgroups per CU -- so a shape the gate accepts cannot fail a launcher's check.
 constexpr size_t MXT_MAX_LDS_BYTES = 80 * 1024;
 constexpr size_t mxt_lds_bytes_max(int L, int N) {
-    size_t m = mxt_lds_bytes(L, PH_TOP, 0, N);
-    for (int i = 1; i < 2 * L; ++i) m = std::max(m, mxt_lds_bytes(L, PH_F, i, N));
-    for (int i = 0; i < 2 * L; ++i) m = std::max(m, mxt_lds_bytes(L, PH_G, i, N));
-    return m;
+    int m = 0;
+    mxt_each_phase(L, [&](int kind, int idx) { m = std::max(m, mxt_lds(L, kind, idx, mxt_nfix(N), N).total); });
+    return sizeof(float) * (size_t)m;
 }
 static_assert(mxt_lds_bytes_max(MX_MAX_LAYERS, 15) <= MXT_MAX_LDS_BYTES && mxt_lds_bytes_max(MX_MAX_LAYERS, 14) <= MXT_MAX_LDS_BYTES &&
                   mxt_lds_bytes_max(1, 15) <= MXT_MAX_LDS_BYTES,
               "every matrix-core phase must fit its LDS limit");
+// Pinned (the launches' requests must not move with an edit of mxt_lds): the bytes of every phase (G_2 at three layers and N = 15: the generic
+// body, without the H tile)
+constexpr bool mxt_bytes_are(int L, int N, std::initializer_list<int> want) {
+    const int* w = want.begin();
+    bool ok = (int)want.size() == 4 * L;
+    mxt_each_phase(L, [&](int kind, int idx) { ok = ok && 4 * mxt_lds(L, kind, idx, mxt_nfix(N), N).total == *w++; });
+    return ok;
+}
+static_assert(mxt_bytes_are(1, 14, {30320, 33840, 42096, 47536}));
+static_assert(mxt_bytes_are(2, 14, {30880, 34400, 34400, 21920, 42656, 48096, 78496, 48096}));
+static_assert(mxt_bytes_are(3, 14, {31440, 34960, 34960, 22480, 34960, 22480, 43216, 48656, 79056, 48656, 79056, 48656}));
+static_assert(mxt_bytes_are(2, 15, {32160, 35680, 35680, 22560, 43936, 50016, 72736, 50016}));
+static_assert(mxt_bytes_are(3, 15, {32720, 36240, 36240, 23120, 36240, 23120, 44496, 50576, 73296, 50576, 73296, 50576}));
+static_assert(mxt_bytes_are(2, 2, {15520, 19040, 19040, 14240, 27296, 25056, 31136, 25056}));
 
 template <int L, int KIND, int IDX, int NFIX>
 static int mxt_launch(const MxTrainK& k, hipStream_t stream, int max_grid, int* grid_out) {
     auto kern = &stgcn_train_mx_kernel<L, KIND, IDX, NFIX>;
-    const size_t lds = mxt_lds_bytes(L, KIND, IDX, k.N);
+    const size_t lds = sizeof(float) * (size_t)mxt_lds(L, KIND, IDX, NFIX, k.N).total;
     if (const int rc = allow_dynamic_lds(kern, lds, MXT_MAX_LDS_BYTES); rc != RULGNN_OK) return rc;
     auto [cus, per_cu] = residency(kern, 64 * MXT_WAVES, lds);
     if (per_cu > MX_WAVES_PER_SIMD) per_cu = MX_WAVES_PER_SIMD;           // a workgroup is one wavefront per SIMD
@@ -1243,31 +1243,20 @@ static int mxt_launch(const MxTrainK& k, hipStream_t stream, int max_grid, int* 
     if (grid > want) grid = want;
     if (grid > max_grid) grid = max_grid;
     if (grid_out) *grid_out = (int)grid;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * MXT_WAVES), lds, stream, k);
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return launch_checked(kern, dim3((unsigned)grid), dim3(64 * MXT_WAVES), lds, stream, k);
 }
 
 template <int L, int KIND, int IDX>
 static int mxt_launch_n(const MxTrainK& k, hipStream_t stream, int max_grid, int* grid_out) {
-    if (k.N == 14) return mxt_launch<L, KIND, IDX, 14>(k, stream, max_grid, grid_out);
+    if (mxt_nfix(k.N) == 14) return mxt_launch<L, KIND, IDX, 14>(k, stream, max_grid, grid_out);
     return mxt_launch<L, KIND, IDX, 0>(k, stream, max_grid, grid_out);
 }
 
-template <int L, int I>
-struct MxtPhase {
-    static int run(int kind, int idx, const MxTrainK& k, hipStream_t st, int mg, int* go) {
-        if (idx == I) {
-            if (kind == PH_F) {
-                if constexpr (I >= 1) return mxt_launch_n<L, PH_F, I>(k, st, mg, go);
-                else return RULGNN_EINVAL;
-            }
-            if (kind == PH_G) return mxt_launch_n<L, PH_G, I>(k, st, mg, go);
-        }
-        if constexpr (I > 0) return MxtPhase<L, I - 1>::run(kind, idx, k, st, mg, go);
-        return RULGNN_EINVAL;
-    }
-};
+template <int L>
+static int mxt_phase(int kind, int idx, const MxTrainK& k, hipStream_t st, int mg, int* go) {
+    if (kind == PH_TOP) return mxt_launch_n<L, PH_TOP, 0>(k, st, mg, go);
+    return mxt_dispatch_phase<2 * L - 1>(kind, idx, [&](auto K, auto I) { return mxt_launch_n<L, decltype(K)::value, decltype(I)::value>(k, st, mg, go); });
+}
 
 bool stgcn_train_mx_shape_ok(const rulgnn_stgcn_shape* s, const float* x) {
     const int N = s->num_patch, P = s->patch_size, L = s->num_layers;
@@ -1282,20 +1271,6 @@ float stgcn_train_mx_grad_scale(int64_t global_batch) {
     return ldexpf(1.0f, e + 3);
 }
 
-static MxTrainK mxt_kernel_args(const MxTrainArgs& m) {
-    MxTrainK k;
-    k.prm = m.prm; k.y = m.y; k.pred = m.pred; k.cells = m.cells; k.gpart = m.gpart;
-    for (int l = 0; l < MX_MAX_LAYERS; ++l) { k.xrec[l] = m.xrec[l]; k.qrec[l] = m.qrec[l]; k.hrec[l] = m.hrec[l]; k.mrec[l] = m.mrec[l]; }
-    k.arec = m.arec; k.sb = m.sb; k.dx = m.dx; k.dtop = m.dtop;
-    k.B = m.B; k.ntiles = (m.B + 3) / 4; k.global_batch = m.global_batch; k.sample_offset = m.sample_offset;
-    k.N = m.N; k.pcount = m.pcount;
-    k.dropout_p = m.dropout_p; k.drop_scale = m.drop_scale; k.drop_thr = m.drop_thr;
-    k.gscale = stgcn_train_mx_grad_scale(m.global_batch);
-    k.inv_gscale = 1.0f / k.gscale;
-    k.do_backward = m.do_backward;
-    return k;
-}
-
 // F_1 .. G_0 of a whole step as one launch (stgcn_train_mx_persist_kernel): two layers, a batch small enough that every workgroup of
 // the phases' common grid (one tile per wavefront) has a CU of its own -- RULGNN_EUNSUPPORTED otherwise, and the caller runs the phases
 // as launches.  *grid_out = the grid: every phase's partial gradient rows (finalize).
@@ -1305,9 +1280,7 @@ static int mxt_persist_launch(const MxTrainK& k, hipStream_t stream, int64_t gri
     auto kern = &stgcn_train_mx_persist_kernel<L, NFIX>;
     const size_t lds = mxt_lds_bytes_max(L, k.N);
     if (const int rc = allow_dynamic_lds(kern, lds, MXT_MAX_LDS_BYTES); rc != RULGNN_OK) return rc;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * MXT_WAVES), lds, stream, k);
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return launch_checked(kern, dim3((unsigned)grid), dim3(64 * MXT_WAVES), lds, stream, k);
 }
 int stgcn_train_mx_persistent_grid(int64_t batch, int num_layers, int max_grid) {
     if (num_layers != 2 || batch <= 0) return 0;
@@ -1320,27 +1293,18 @@ int stgcn_train_mx_persistent_grid(int64_t batch, int num_layers, int max_grid) 
 int stgcn_train_mx_persistent(const MxTrainArgs& m, hipStream_t stream, int max_grid, int* grid_out) {
     const int grid = m.do_backward ? stgcn_train_mx_persistent_grid(m.B, m.L, max_grid) : 0;
     if (grid == 0) return RULGNN_EUNSUPPORTED;
-    const MxTrainK k = mxt_kernel_args(m);
+    const MxTrainK k = mxt_kernel_args(m, 4);
     if (grid_out) *grid_out = grid;
-    return k.N == 14 ? mxt_persist_launch<14>(k, stream, grid) : mxt_persist_launch<0>(k, stream, grid);
+    return mxt_nfix(k.N) == 14 ? mxt_persist_launch<14>(k, stream, grid) : mxt_persist_launch<0>(k, stream, grid);
 }
 
 int stgcn_train_mx_phase(const MxTrainArgs& m, int kind, int idx, hipStream_t stream, int max_grid, int* grid_out) {
-    const MxTrainK k = mxt_kernel_args(m);
+    const MxTrainK k = mxt_kernel_args(m, 4);
     if (m.B == 0) { if (grid_out) *grid_out = 0; return RULGNN_OK; }
-    const int L = m.L;
-    if (kind == PH_TOP) {
-        switch (L) {
-            case 1: return mxt_launch_n<1, PH_TOP, 0>(k, stream, max_grid, grid_out);
-            case 2: return mxt_launch_n<2, PH_TOP, 0>(k, stream, max_grid, grid_out);
-            case 3: return mxt_launch_n<3, PH_TOP, 0>(k, stream, max_grid, grid_out);
-            default: return RULGNN_EUNSUPPORTED;
-        }
-    }
-    switch (L) {
-        case 1: return MxtPhase<1, 1>::run(kind, idx, k, stream, max_grid, grid_out);
-        case 2: return MxtPhase<2, 3>::run(kind, idx, k, stream, max_grid, grid_out);
-        case 3: return MxtPhase<3, 5>::run(kind, idx, k, stream, max_grid, grid_out);
+    switch (m.L) {
+        case 1: return mxt_phase<1>(kind, idx, k, stream, max_grid, grid_out);
+        case 2: return mxt_phase<2>(kind, idx, k, stream, max_grid, grid_out);
+        case 3: return mxt_phase<3>(kind, idx, k, stream, max_grid, grid_out);
         default: return RULGNN_EUNSUPPORTED;
     }
 }

@@ -6,6 +6,7 @@
 
 #include "stgcn_mx.hpp"
 #include "stgcn_train_layout.hpp"
+#include "stgcn_train_mx.hpp"
 
 namespace rulgnn {
 namespace {
@@ -60,9 +61,52 @@ constexpr bool MXT_H_READ_F_EVEN = (MXT_H_READERS & 8) != 0;
 constexpr bool mxt_h0_record(int L) { return MXT_H0_READ_G1 || MXT_H0_READ_G0 || (L == 1 ? MXT_H0_READ_TOP : MXT_H_READ_F_EVEN); }
 // G_{2l} with the H tile beside X_l, the adjacency, d(x0 + H), d X_{l+1}, Q_l and the staging tile: at l >= 1 that is 82 896 bytes at
 // N = 15, L = 3 -- more than the 80 KB that keep two workgroups on a CU -- so there only the fixed-N (14) instantiations read the record
-// and the generic ones keep the rebuild.  G_0 has three of those tiles and fits at every N.  (`nfix`: the kernel's NFIX; the host passes
-// what mxt_launch_n would instantiate for its N.)
+// and the generic ones keep the rebuild.  G_0 has three of those tiles and fits at every N.  (`nfix`: the kernel's NFIX.)
 constexpr bool mxt_g_even_reads_h(int ly, int nfix) { return ly == 0 ? MXT_H0_READ_G0 : (MXT_H_READ_G_EVEN && nfix == 14); }
+
+// What phase (L, kind, idx) of a training chain is, once, for the bodies' `if constexpr`, the LDS layouts and the launchers.  (`nfix`: the
+// kernel's NFIX; the wide chain, which has no H records, passes 0.)
+struct MxtTraits {
+    int LY, BLK, LIN, AF, NTH;
+    bool WITH_PREV, BWD_PREV, GRAD_IN, GRAD_TOP, NEED_SB, H_OUT, H_IN, H_TOP, H_PREV, H_GE, H_TILE, TILE_OUT, LATE;
+};
+__host__ __device__ constexpr MxtTraits mxt_traits(int L, int kind, int idx, int nfix) {
+    MxtTraits t{};
+    t.LY = kind == PH_TOP ? L - 1 : idx / 2;
+    t.BLK = kind == PH_TOP ? 1 : idx % 2;
+    t.WITH_PREV = kind == PH_F && t.BLK == 0 && t.LY >= 1;     // F_{2l}: layer l-1 in full first (its input is this phase's input)
+    t.BWD_PREV = kind == PH_G && t.BLK == 0 && t.LY >= 1;      // G_{2l}: the sums of BatchNorm 2l-1 (its gated x-hat comes from F_{2l})
+    t.LIN = t.WITH_PREV ? t.LY - 1 : t.LY;                     // the layer whose input record is the main input
+    t.GRAD_IN = kind == PH_G && (t.BLK == 1 || t.LY >= 1);     // a gradient tensor enters: d X_{l+1}
+    t.GRAD_TOP = t.GRAD_IN && t.LY == L - 1;                   // ... in TOP's (value, arg-max) form
+    t.NEED_SB = kind == PH_G && t.BLK == 0;
+    // the H_l record (MxTrainK::hrec): the first phase of the narrow chain that computes H of layer LY writes it -- F_{2l}, l >= 1; F_1 for
+    // H_0 (F_0 has it only under its per-sample scale) where a reader of H_0 is switched on.  F_{2l+1} and G_{2l+1} need nothing else
+    // of X_l and A, and start from it.  (The readers beyond round 8's: MXT_H_READERS)
+    t.H_OUT = kind == PH_F && (t.WITH_PREV || (idx == 1 && mxt_h0_record(L)));
+    t.H_IN = (kind == PH_F && t.BLK == 1 && t.LY >= 1) || (kind == PH_G && t.BLK == 1 && (t.LY >= 1 || MXT_H0_READ_G1));
+    t.H_TOP = kind == PH_TOP && (t.LY >= 1 || MXT_H0_READ_TOP);    // TOP: X_l for the residual, H_l in place of the adjacency
+    t.H_PREV = t.WITH_PREV && MXT_H_READ_F_EVEN;                   // F_{2l}: the pass over layer l-1 starts from H_{l-1}
+    t.H_GE = kind == PH_G && t.BLK == 0 && mxt_g_even_reads_h(t.LY, nfix);    // G_{2l}: H_l beside X_l and the adjacency
+    t.H_TILE = t.H_PREV || t.H_GE;                                 // ... in a tile of its own
+    // every full-tile record a phase writes (F_{2l}: X_l, Q_l, H_l; G_{2l+1}: d(x0 + H); G_{2l}, l >= 1: d X_l) leaves through ONE
+    // staging tile per wavefront, one record after the other
+    t.TILE_OUT = t.WITH_PREV || t.H_OUT || (kind == PH_G && t.BLK == 1) || t.BWD_PREV;
+    t.AF = t.H_IN ? 0 : 220;                                   // floats of the narrow chain's adjacency tile
+    // wide chain.  G_{2l} carries the most state (the theta-gradient tiles): its records are read from LDS where they are used instead of
+    // being held in registers across the sample, the next sample's records are requested once the region is free, and d X_l is stored
+    // without the delay
+    t.LATE = kind == PH_G && t.BLK == 0;
+    t.NTH = 1 + (t.WITH_PREV ? 1 : 0) + (t.BWD_PREV ? 1 : 0);  // theta operand tables: theta^T(LY) | theta^T(LY-1) | theta(LY)
+    return t;
+}
+// every phase of the chains' phase kernels, in the order TOP, F_1 .. F_{2L-1}, G_0 .. G_{2L-1}
+template <typename FN>
+constexpr void mxt_each_phase(int L, FN fn) {
+    fn(PH_TOP, 0);
+    for (int i = 1; i < 2 * L; ++i) fn(PH_F, i);
+    for (int i = 0; i < 2 * L; ++i) fn(PH_G, i);
+}
 
 struct Op2 { u32x4 h, l; };              // a D-layout tensor as the ({hi | hi}, {lo | lo}) operand pair against a {hi | lo} partner
 struct Pk { u32x2 hi, lo; };             // its packed halves: slots 4 g .. 4 g + 3 of this lane's column
@@ -252,5 +296,34 @@ struct MxTrainK {
     float gscale, inv_gscale;
     int do_backward;
 };
+
+// The kernels' argument block from the chain's; `samples_per_tile`: 4 (narrow chain) or 1 (wide chain)
+inline MxTrainK mxt_kernel_args(const MxTrainArgs& m, int samples_per_tile) {
+    MxTrainK k;
+    k.prm = m.prm; k.y = m.y; k.pred = m.pred; k.cells = m.cells; k.gpart = m.gpart;
+    for (int l = 0; l < MX_MAX_LAYERS; ++l) { k.xrec[l] = m.xrec[l]; k.qrec[l] = m.qrec[l]; k.hrec[l] = m.hrec[l]; k.mrec[l] = m.mrec[l]; }
+    k.arec = m.arec; k.sb = m.sb; k.dx = m.dx; k.dtop = m.dtop;
+    k.B = m.B; k.ntiles = (m.B + samples_per_tile - 1) / samples_per_tile; k.global_batch = m.global_batch; k.sample_offset = m.sample_offset;
+    k.N = m.N; k.pcount = m.pcount;
+    k.dropout_p = m.dropout_p; k.drop_scale = m.drop_scale; k.drop_thr = m.drop_thr;
+    k.gscale = stgcn_train_mx_grad_scale(m.global_batch);
+    k.inv_gscale = 1.0f / k.gscale;
+    k.do_backward = m.do_backward;
+    return k;
+}
+
+// Phase (kind, idx) -> template arguments: launch(kind, idx as std::integral_constant) for F_1 .. F_I and G_0 .. G_I
+template <int I, typename LAUNCH>
+inline int mxt_dispatch_phase(int kind, int idx, LAUNCH launch) {
+    if (idx == I) {
+        if (kind == PH_F) {
+            if constexpr (I >= 1) return launch(std::integral_constant<int, PH_F>{}, std::integral_constant<int, I>{});
+            else return RULGNN_EINVAL;
+        }
+        if (kind == PH_G) return launch(std::integral_constant<int, PH_G>{}, std::integral_constant<int, I>{});
+    }
+    if constexpr (I > 0) return mxt_dispatch_phase<I - 1>(kind, idx, launch);
+    return RULGNN_EINVAL;
+}
 
 }  // namespace rulgnn

@@ -31,6 +31,62 @@ namespace {
 constexpr int MXW_ASTRIDE = 56;                  // adjacency record: 55 (hi | lo) pairs + 1 pad word (16-byte DMA pieces)
 __host__ __device__ constexpr int mxw_xstride(int N) { return (10 * N + 3) & ~3; }
 __host__ __device__ constexpr int mxw_dstride(int N) { return (2 * N + 3) & ~3; }
+constexpr int MXW_MIN_N = 16;                    // the chain's smallest num_patch: the smallest records and wavefront regions
+
+// LDS of F_0 (floats): [theta operands [NT][NT][64] x 4 | pair partials [MXT_WAVES][2 F] doubles], then per wavefront [window | region]
+struct MxtwF0Lds {
+    int pairbuf, waves, cur, wave_floats, total;      // `cur`, within a wavefront's part: the conversion / shift region behind the window
+};
+__host__ __device__ constexpr MxtwF0Lds mxtw_f0_lds(int NT, int buf_floats) {
+    const int W = 16 * NT, PT = W + 4;
+    const int region = (16 * PT > 2 * (4 * W + 1) * 2 ? 16 * PT : 2 * (4 * W + 1) * 2) + 64;
+    MxtwF0Lds l{};
+    l.pairbuf = NT * NT * 64 * 4;
+    l.waves = l.pairbuf + 2 * MXT_WAVES * 2 * F;
+    l.cur = buf_floats;
+    l.wave_floats = buf_floats + ((region + 3) & ~3);
+    l.total = l.waves + MXT_WAVES * l.wave_floats;
+    return l;
+}
+
+// LDS of a phase (floats): workgroup [theta tables | fc1 tables (TOP) | BatchNorm constants | pair partials | constant operands (G_{2l})],
+// then one region per wavefront; the epilogue's row image lies over the regions (all done by then).
+struct MxtwLds {
+    int fc1N, fc1T, bnc, pairbuf, cops, red;                  // the workgroup's part; `red`: the row image = the wavefronts' regions
+    int FCP, RED_FLOATS, WP, SH_LO;                           // pitches and sizes the body indexes with
+    int zero, scr, sh, X, A, SB, DX, Q, wave_floats;          // within a region
+    int total;
+};
+__host__ __device__ constexpr MxtwLds mxtw_lds(int L, int kind, int idx, int NT, int N) {
+    const MxtTraits t = mxt_traits(L, kind, idx, 0);
+    const int W = 16 * NT, XS = mxw_xstride(N);
+    MxtwLds l{};
+    l.FCP = W + 4;                                            // row pitch of the fc1 tables: 16-byte row reads of 16 lanes fall on distinct banks
+    l.fc1N = t.NTH * NT * NT * 64 * 4;                        // fc1.w[j][k] at j FCP + k: lane j reads its row (y1 = fc1 x pooled)
+    l.fc1T = l.fc1N + W * l.FCP;                              // fc1.w[j][k] at k FCP + j: lane k reads its column (d pooled = fc1^T x d y1)
+    l.bnc = l.fc1N + (kind == PH_TOP ? 2 * W * l.FCP : 0);
+    l.pairbuf = l.bnc + ((2 * L * MXT_BNC * F + 3) & ~3);
+    l.cops = l.pairbuf + 2 * MXT_WAVES * (2 * F + 2);         // G_{2l}: per-lane constant operands kept out of the register file
+    l.red = l.cops + (t.LATE ? 31 * 64 : 0);
+    l.RED_FLOATS = (W * W + W + CONVW + 3) & ~3;
+    // shift tile: [hi | lo][row group][2 zero entries | column 0 .. W): a tap at t - d (d <= 2) of column 0 / 1 reads the zeros in front of its
+    // row, a tap at t + d past the last column the zeros in front of the next row (two more behind the last): every tap is base + constant
+    l.WP = W + 2;
+    l.SH_LO = 4 * l.WP + 2;
+    l.zero = 0;                                               // 64 zero words
+    l.scr = 64;                                               // 4 W floats: pooled | d y1 | d pool | arg-max
+    l.sh = l.scr + 4 * W;
+    l.X = l.sh + (((2 * l.SH_LO * 2) + 3) & ~3);
+    l.A = l.X + XS;
+    l.SB = l.A + MXW_ASTRIDE;
+    l.DX = l.SB + (t.NEED_SB ? XS : 0);
+    l.Q = l.DX + (t.GRAD_IN ? XS : 0);
+    l.wave_floats = l.Q + (t.BWD_PREV ? XS : 0);
+    l.total = l.red + (MXT_WAVES * l.wave_floats > l.RED_FLOATS ? MXT_WAVES * l.wave_floats : l.RED_FLOATS);
+    return l;
+}
+// the smallest the wavefronts' regions of a workgroup get: a phase with the two records every phase reads, at the smallest num_patch
+constexpr int mxtw_min_regions(int NT) { return MXT_WAVES * mxtw_lds(1, PH_F, 1, NT, MXW_MIN_N).wave_floats; }
 }  // namespace
 
 // =====================================================================================================================
@@ -47,10 +103,10 @@ __global__ __launch_bounds__(64 * MXT_WAVES, MX_WAVES_PER_SIMD) void stgcn_train
     const int NP = N * P, XS = mxw_xstride(N);
     constexpr int L = 1;                                                  // (cell layout offsets of the forward pair 0 do not depend on L)
     u32x4* const theta_lds = reinterpret_cast<u32x4*>(smem_all);          // [NT][NT][64]
-    double* const pairbuf = reinterpret_cast<double*>(smem_all + NT * NT * 64 * 4);       // [MXT_WAVES][2 F]
-    constexpr int REGION = (16 * PT > 2 * (4 * W + 1) * 2 ? 16 * PT : 2 * (4 * W + 1) * 2) + 64;
-    float* const win = smem_all + NT * NT * 64 * 4 + 2 * MXT_WAVES * 2 * F + wave * (buf_floats + ((REGION + 3) & ~3));
-    float* const cur = win + buf_floats;
+    const MxtwF0Lds ld = mxtw_f0_lds(NT, buf_floats);
+    double* const pairbuf = reinterpret_cast<double*>(smem_all + ld.pairbuf);             // [MXT_WAVES][2 F]
+    float* const win = smem_all + ld.waves + wave * ld.wave_floats;
+    float* const cur = win + ld.cur;
     const int64_t stride = (int64_t)gridDim.x * MXT_WAVES;
     int64_t smp = (int64_t)blockIdx.x * MXT_WAVES + wave;
     if (smp < a.B) dma_tile(gx + smp * NP, win, NP * 4, lane);
@@ -291,50 +347,23 @@ __global__ __launch_bounds__(64 * MXT_WAVES, MX_WAVES_PER_SIMD) void stgcn_train
     const int g = lane >> 4, col = lane & 15;
     constexpr int NBN = 2 * L;
     constexpr int CS = cell_stride(L);
-    constexpr int LY = KIND == PH_TOP ? L - 1 : IDX / 2;
-    constexpr int BLK = KIND == PH_TOP ? 1 : IDX % 2;
-    constexpr bool WITH_PREV = KIND == PH_F && BLK == 0 && LY >= 1;
-    constexpr bool BWD_PREV = KIND == PH_G && BLK == 0 && LY >= 1;
-    constexpr int LIN = WITH_PREV ? LY - 1 : LY;
-    constexpr bool GRAD_IN = KIND == PH_G && (BLK == 1 || LY >= 1);
-    constexpr bool GRAD_TOP = GRAD_IN && LY == L - 1;
-    constexpr bool NEED_SB = KIND == PH_G && BLK == 0;
-    // G_{2l} carries the most state (the theta-gradient tiles): its records are read from LDS where they are used instead of being held in
-    // registers across the sample, the next sample's records are requested once the region is free, and d X_l is stored without the delay
-    constexpr bool LATE = KIND == PH_G && BLK == 0;
-    constexpr int NTH = 1 + (WITH_PREV ? 1 : 0) + (BWD_PREV ? 1 : 0);          // theta operand tables: theta^T(LY) | theta^T(LY-1) | theta(LY)
+    constexpr MxtTraits T = mxt_traits(L, KIND, IDX, 0);
+    constexpr int LY = T.LY, BLK = T.BLK, LIN = T.LIN, NTH = T.NTH;
+    constexpr bool WITH_PREV = T.WITH_PREV, BWD_PREV = T.BWD_PREV, GRAD_IN = T.GRAD_IN, GRAD_TOP = T.GRAD_TOP, NEED_SB = T.NEED_SB, LATE = T.LATE;
     static_assert(!(KIND == PH_F && IDX == 0), "F_0 is stgcn_train_f0_mxw_kernel");
     const int XS = mxw_xstride(N), DS = mxw_dstride(N);
 
-    // ---- LDS: workgroup [theta tables | fc1 tables (TOP) | BatchNorm constants | row image | pair partials], then one region per wavefront
-    constexpr int SH_BNC = (NBN * MXT_BNC * F + 3) & ~3;
-    constexpr int TH_FLOATS = NTH * NT * NT * 64 * 4;
-    constexpr int FCP = W + 4;                                  // row pitch of the fc1 tables: 16-byte row reads of 16 lanes fall on distinct banks
-    constexpr int FC_FLOATS = KIND == PH_TOP ? 2 * W * FCP : 0;
-    constexpr int RED_FLOATS = (W * W + W + CONVW + 3) & ~3;
+    // ---- LDS carve (mxtw_lds; the workgroup's part and the pitches do not depend on N) ------------------------------------------------
+    constexpr MxtwLds LC = mxtw_lds(L, KIND, IDX, NT, MXW_MIN_N);
+    constexpr int FCP = LC.FCP, RED_FLOATS = LC.RED_FLOATS, WP = LC.WP, SH_LO = LC.SH_LO;
+    const MxtwLds ld = mxtw_lds(L, KIND, IDX, NT, N);
     u32x4* const theta_lds = reinterpret_cast<u32x4*>(smem_all);
-    float* const fc1N = smem_all + TH_FLOATS;                  // fc1.w[j][k] at j FCP + k: lane j reads its row (y1 = fc1 x pooled)
-    float* const fc1T = fc1N + W * FCP;                        // fc1.w[j][k] at k FCP + j: lane k reads its column (d pooled = fc1^T x d y1)
-    constexpr int COPS_FLOATS = LATE ? 31 * 64 : 0;           // G_{2l}: per-lane constant operands kept out of the register file
-    float* const bnc = smem_all + TH_FLOATS + FC_FLOATS;
-    double* const pairbuf = reinterpret_cast<double*>(bnc + SH_BNC);
-    float* const cops = bnc + SH_BNC + 2 * MXT_WAVES * (2 * F + 2);
-    float* const red = cops + COPS_FLOATS;                     // the epilogue's row image lies over the wavefronts' regions (all done by then)
-    // shift tile: [hi | lo][row group][2 zero entries | column 0 .. W): a tap at t - d (d <= 2) of column 0 / 1 reads the zeros in front of its
-    // row, a tap at t + d past the last column the zeros in front of the next row (two more behind the last): every tap is base + constant
-    constexpr int WP = W + 2, SH_LO = 4 * WP + 2;
-    constexpr int SHIFT_FLOATS = ((2 * SH_LO * 2) + 3) & ~3;
-    const int off_zero = 0;                                    // 64 zero words
-    const int off_scr = 64;                                    // 4 W floats: pooled | d y1 | d pool | arg-max
-    const int off_sh = off_scr + 4 * W;
-    const int off_X = off_sh + SHIFT_FLOATS;
-    const int off_A = off_X + XS;
-    const int off_SB = off_A + MXW_ASTRIDE;
-    const int off_DX = off_SB + (NEED_SB ? XS : 0);
-    const int off_Q = off_DX + (GRAD_IN ? XS : 0);
-    const int wave_floats = off_Q + (BWD_PREV ? XS : 0);
-    float* const smem = red + wave * wave_floats;
-    static_assert(RED_FLOATS <= MXT_WAVES * (64 + 4 * W + SHIFT_FLOATS + 160 + MXW_ASTRIDE), "row image fits the wavefronts' regions");
+    float *const fc1N = smem_all + LC.fc1N, *const fc1T = smem_all + LC.fc1T, *const bnc = smem_all + LC.bnc, *const cops = smem_all + LC.cops;
+    double* const pairbuf = reinterpret_cast<double*>(smem_all + LC.pairbuf);
+    float* const red = smem_all + LC.red;
+    const int off_zero = LC.zero, off_scr = LC.scr, off_sh = LC.sh, off_X = LC.X, off_A = ld.A, off_SB = ld.SB, off_DX = ld.DX, off_Q = ld.Q;
+    float* const smem = red + wave * ld.wave_floats;
+    static_assert(RED_FLOATS <= mxtw_min_regions(NT), "row image fits the wavefronts' regions");
     u32x2* const sh_tile = reinterpret_cast<u32x2*>(smem + off_sh);
 
     int64_t smp = (int64_t)blockIdx.x * MXT_WAVES + wave;
@@ -1191,7 +1220,7 @@ __global__ __launch_bounds__(64 * MXT_WAVES, MX_WAVES_PER_SIMD) void stgcn_train
     const float us = a.inv_gscale;
     const int NN = N * N;
     // two images (wavefronts 0 | 1 store, then 2 | 3 add), summed on the way out: two rounds, a fixed order of additions
-    static_assert(2 * RED_FLOATS <= MXT_WAVES * (64 + 4 * W + SHIFT_FLOATS + 160 + MXW_ASTRIDE), "two row images fit the wavefronts' regions");
+    static_assert(2 * RED_FLOATS <= mxtw_min_regions(NT), "two row images fit the wavefronts' regions");
     for (int w = 0; w < 2; ++w) {
         if ((wave >> 1) == w) {
             float* const img = red + (wave & 1) * RED_FLOATS;
@@ -1255,25 +1284,27 @@ __global__ __launch_bounds__(64 * MXT_WAVES, MX_WAVES_PER_SIMD) void stgcn_train
 // =====================================================================================================================
 // host side
 // =====================================================================================================================
-static size_t mxtw_lds_bytes(int L, int kind, int idx, int N, int NT) {
-    const int W = 16 * NT;
-    const int blk = kind == PH_TOP ? 1 : idx % 2, ly = kind == PH_TOP ? L - 1 : idx / 2;
-    const bool with_prev = kind == PH_F && blk == 0 && ly >= 1, bwd_prev = kind == PH_G && blk == 0 && ly >= 1;
-    const bool need_sb = kind == PH_G && blk == 0, grad_in = kind == PH_G && (blk == 1 || ly >= 1);
-    const int nth = 1 + (with_prev ? 1 : 0) + (bwd_prev ? 1 : 0);
-    const int XS = mxw_xstride(N);
-    const bool late = kind == PH_G && blk == 0;
-    const size_t shared = (size_t)nth * NT * NT * 64 * 4 + (kind == PH_TOP ? 2 * W * (W + 4) : 0) + ((2 * L * MXT_BNC * F + 3) & ~3) + 2 * MXT_WAVES * (2 * F + 2) +
-                          (late ? 31 * 64 : 0);
-    const size_t red = (W * W + W + CONVW + 3) & ~3;
-    const size_t wave = 64 + 4 * W + (((2 * (4 * (W + 2) + 2) * 2) + 3) & ~3) + XS + MXW_ASTRIDE + (need_sb ? XS : 0) + (grad_in ? XS : 0) + (bwd_prev ? XS : 0);
-    return (shared + (MXT_WAVES * wave > red ? MXT_WAVES * wave : red)) * sizeof(float);
+// Pinned (the launches' requests must not move with an edit of the layouts): the bytes of every phase (mxt_each_phase's order) and of F_0
+constexpr bool mxtw_bytes_are(int L, int N, std::initializer_list<int> want) {
+    const int* w = want.begin();
+    bool ok = (int)want.size() == 4 * L;
+    mxt_each_phase(L, [&](int kind, int idx) { ok = ok && 4 * mxtw_lds(L, kind, idx, N <= 31 ? 2 : 3, N).total == *w++; });
+    return ok;
 }
+static_assert(mxtw_bytes_are(1, 16, {29936, 20720, 31216, 23280}));
+static_assert(mxtw_bytes_are(2, 16, {30496, 21280, 25376, 21280, 31776, 23840, 40992, 23840}));
+static_assert(mxtw_bytes_are(2, 31, {32928, 23712, 27808, 23712, 36640, 28704, 50720, 28704}));
+static_assert(mxtw_bytes_are(2, 32, {54048, 34080, 43296, 34080, 47136, 39200, 66592, 39200}));
+static_assert(mxtw_bytes_are(2, 40, {55328, 35360, 44576, 35360, 49696, 41760, 71712, 41760}));
+static_assert(mxtw_bytes_are(2, 47, {56480, 36512, 45728, 36512, 52000, 44064, 76320, 44064}));
+static_assert(4 * mxtw_f0_lds(2, 420).total == 21696 && 4 * mxtw_f0_lds(2, 700).total == 26176 && 4 * mxtw_f0_lds(2, 240).total == 18816 &&
+                  4 * mxtw_f0_lds(3, 2560).total == 65152 && 4 * mxtw_f0_lds(2, 256).total == 19072,
+              "F_0 at 14 x 30, 14 x 50, 15 x 16, 40 x 64, 16 x 16");
 
 // Two workgroups per CU: the backward phases hold > 128 registers; a third and fourth workgroup of the forward phases (~110 registers)
 // were measured (F_1 / F_3 at 40 x 64, batch 16384: 23.7 / 23.1 / 23.7 us with 2 / 3 / 4) -- the issue port is the limit, not latency
-template <typename K>
-static int mxtw_grid(K kern, size_t lds, int64_t B, int max_grid, int* grid_out) {
+template <typename K, typename... A>
+static int mxtw_run(K kern, size_t lds, int64_t B, int max_grid, int* grid_out, hipStream_t stream, const A&... args) {
     constexpr int cap = MX_WAVES_PER_SIMD;
     if (const int rc = allow_dynamic_lds(kern, lds); rc != RULGNN_OK) return rc;
     auto [cus, per_cu] = residency(kern, 64 * MXT_WAVES, lds);
@@ -1283,41 +1314,24 @@ static int mxtw_grid(K kern, size_t lds, int64_t B, int max_grid, int* grid_out)
     if (grid > want) grid = want;
     if (grid > max_grid) grid = max_grid;
     if (grid_out) *grid_out = (int)grid;
-    return RULGNN_OK;
+    return launch_checked(kern, dim3((unsigned)grid), dim3(64 * MXT_WAVES), lds, stream, args...);
 }
 
 template <int L, int KIND, int IDX, int NT>
 static int mxtw_launch(const MxTrainK& k, hipStream_t stream, int max_grid, int* grid_out) {
-    const size_t lds = mxtw_lds_bytes(L, KIND, IDX, k.N, NT);
-    auto go = [&](auto kern) -> int {
-        int grid = 0;
-        const int rc = mxtw_grid(kern, lds, k.B, max_grid, &grid);
-        if (rc != RULGNN_OK) return rc;
-        if (grid_out) *grid_out = grid;
-        (void)hipGetLastError();
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * MXT_WAVES), lds, stream, k);
-        return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
-    };
+    const size_t lds = sizeof(float) * (size_t)mxtw_lds(L, KIND, IDX, NT, k.N).total;
+    auto go = [&](auto kern) { return mxtw_run(kern, lds, k.B, max_grid, grid_out, stream, k); };
     if constexpr (NT == 3) {
         if (k.N == 40) return go(&stgcn_train_mxw_kernel<L, KIND, IDX, NT, 40>);          // PHM2012's wiring
     }
     return go(&stgcn_train_mxw_kernel<L, KIND, IDX, NT, 0>);
 }
 
-template <int L, int NT, int I>
-struct MxtwPhase {
-    static int run(int kind, int idx, const MxTrainK& k, hipStream_t st, int mg, int* go) {
-        if (idx == I) {
-            if (kind == PH_F) {
-                if constexpr (I >= 1) return mxtw_launch<L, PH_F, I, NT>(k, st, mg, go);
-                else return RULGNN_EINVAL;
-            }
-            if (kind == PH_G) return mxtw_launch<L, PH_G, I, NT>(k, st, mg, go);
-        }
-        if constexpr (I > 0) return MxtwPhase<L, NT, I - 1>::run(kind, idx, k, st, mg, go);
-        return RULGNN_EINVAL;
-    }
-};
+template <int L, int NT>
+static int mxtw_phase(int kind, int idx, const MxTrainK& k, hipStream_t st, int mg, int* go) {
+    if (kind == PH_TOP) return mxtw_launch<L, PH_TOP, 0, NT>(k, st, mg, go);
+    return mxt_dispatch_phase<2 * L - 1>(kind, idx, [&](auto K, auto I) { return mxtw_launch<L, decltype(K)::value, decltype(I)::value, NT>(k, st, mg, go); });
+}
 
 bool stgcn_train_mxw_shape_ok(const rulgnn_stgcn_shape* s, const float* x) {
     const int N = s->num_patch, P = s->patch_size, L = s->num_layers;
@@ -1327,53 +1341,26 @@ bool stgcn_train_mxw_shape_ok(const rulgnn_stgcn_shape* s, const float* x) {
     return true;
 }
 
-static MxTrainK mxtw_args(const MxTrainArgs& m) {
-    MxTrainK k;
-    k.prm = m.prm; k.y = m.y; k.pred = m.pred; k.cells = m.cells; k.gpart = m.gpart;
-    for (int l = 0; l < MX_MAX_LAYERS; ++l) { k.xrec[l] = m.xrec[l]; k.qrec[l] = m.qrec[l]; k.mrec[l] = m.mrec[l]; }
-    k.arec = m.arec; k.sb = m.sb; k.dx = m.dx; k.dtop = m.dtop;
-    k.B = m.B; k.ntiles = m.B; k.global_batch = m.global_batch; k.sample_offset = m.sample_offset;
-    k.N = m.N; k.pcount = m.pcount;
-    k.dropout_p = m.dropout_p; k.drop_scale = m.drop_scale; k.drop_thr = m.drop_thr;
-    k.gscale = stgcn_train_mx_grad_scale(m.global_batch);
-    k.inv_gscale = 1.0f / k.gscale;
-    k.do_backward = m.do_backward;
-    return k;
-}
-
 int stgcn_train_mxw_f0(const MxTrainArgs& m, const float* x, int P, hipStream_t stream, const HeadScalars* head) {
-    const MxTrainK k = mxtw_args(m);
+    const MxTrainK k = mxt_kernel_args(m, 1);
     HeadScalars hs{};
     if (head) hs = *head;
     if (m.B == 0) return RULGNN_OK;
-    const int NT = m.N <= 31 ? 2 : 3, W = 16 * NT, PT = W + 4;
+    const int NT = m.N <= 31 ? 2 : 3;
     const int buf_floats = (m.N * P + 3) & ~3;
-    const int region = ((16 * PT > 2 * (4 * W + 1) * 2 ? 16 * PT : 2 * (4 * W + 1) * 2) + 64 + 3) & ~3;
-    const size_t lds = ((size_t)NT * NT * 64 * 4 + 2 * MXT_WAVES * 2 * F + (size_t)MXT_WAVES * (buf_floats + region)) * sizeof(float);
-    auto go = [&](auto kern) -> int {
-        int grid = 0;
-        const int rc = mxtw_grid(kern, lds, m.B, 1 << 30, &grid);
-        if (rc != RULGNN_OK) return rc;
-        (void)hipGetLastError();
-        hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * MXT_WAVES), lds, stream, x, k, P, buf_floats, cell_stride(m.L), hs);
-        return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
-    };
+    const size_t lds = sizeof(float) * (size_t)mxtw_f0_lds(NT, buf_floats).total;
+    auto go = [&](auto kern) { return mxtw_run(kern, lds, m.B, 1 << 30, nullptr, stream, x, k, P, buf_floats, cell_stride(m.L), hs); };
     if (m.N == 40 && P == 64) return go(&stgcn_train_f0_mxw_kernel<3, 40, 64>);
     if (NT == 2) return go(&stgcn_train_f0_mxw_kernel<2, 0, 0>);
     return go(&stgcn_train_f0_mxw_kernel<3, 0, 0>);
 }
 
 int stgcn_train_mxw_phase(const MxTrainArgs& m, int kind, int idx, hipStream_t stream, int max_grid, int* grid_out) {
-    const MxTrainK k = mxtw_args(m);
+    const MxTrainK k = mxt_kernel_args(m, 1);
     if (m.B == 0) { if (grid_out) *grid_out = 0; return RULGNN_OK; }
     const int NT = m.N <= 31 ? 2 : 3;
-    if (kind == PH_TOP) {
-        if (m.L == 1) return NT == 2 ? mxtw_launch<1, PH_TOP, 0, 2>(k, stream, max_grid, grid_out) : mxtw_launch<1, PH_TOP, 0, 3>(k, stream, max_grid, grid_out);
-        if (m.L == 2) return NT == 2 ? mxtw_launch<2, PH_TOP, 0, 2>(k, stream, max_grid, grid_out) : mxtw_launch<2, PH_TOP, 0, 3>(k, stream, max_grid, grid_out);
-        return RULGNN_EUNSUPPORTED;
-    }
-    if (m.L == 1) return NT == 2 ? MxtwPhase<1, 2, 1>::run(kind, idx, k, stream, max_grid, grid_out) : MxtwPhase<1, 3, 1>::run(kind, idx, k, stream, max_grid, grid_out);
-    if (m.L == 2) return NT == 2 ? MxtwPhase<2, 2, 3>::run(kind, idx, k, stream, max_grid, grid_out) : MxtwPhase<2, 3, 3>::run(kind, idx, k, stream, max_grid, grid_out);
+    if (m.L == 1) return NT == 2 ? mxtw_phase<1, 2>(kind, idx, k, stream, max_grid, grid_out) : mxtw_phase<1, 3>(kind, idx, k, stream, max_grid, grid_out);
+    if (m.L == 2) return NT == 2 ? mxtw_phase<2, 2>(kind, idx, k, stream, max_grid, grid_out) : mxtw_phase<2, 3>(kind, idx, k, stream, max_grid, grid_out);
     return RULGNN_EUNSUPPORTED;
 }
 

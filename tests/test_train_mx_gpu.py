@@ -53,6 +53,9 @@ def abi_step(x_np, y_np, flat_np, N, P, L, path, dropout=0.0, seed=0, step=1, gl
 CASES = [(14, 30, 32, 2, 0.0), (14, 30, 1, 2, 0.0), (14, 30, 3, 2, 0.0), (14, 30, 5, 2, 0.2), (14, 30, 1027, 2, 0.0), (14, 30, 257, 2, 0.2),
          (14, 50, 130, 2, 0.5), (14, 30, 77, 1, 0.2), (14, 30, 41, 3, 0.2), (14, 30, 8192, 2, 0.2),
          (15, 16, 67, 2, 0.3), (12, 21, 35, 2, 0.2), (2, 6, 18, 2, 0.0), (8, 10, 19, 3, 0.1), (10, 10, 23, 1, 0.0)]
+# three layers at N = 15 on the generic instantiation: the narrow chain's largest LDS request; nine tiles = three workgroups, every
+# wavefront region in use, a ragged last tile
+CASES += [(15, 16, 35, 3, 0.2)]
 # the wide chain (csrc/stgcn_train_mxw.hip): 16 <= num_patch <= 47 in two or three column tiles; PHM2012's 40 x 64 is the reference's wiring
 CASES += [(40, 64, 9, 2, 0.0), (40, 64, 33, 2, 0.2), (40, 64, 1, 2, 0.0), (40, 64, 700, 2, 0.2), (16, 16, 21, 2, 0.2), (17, 28, 19, 2, 0.3),
           (24, 20, 37, 1, 0.2), (31, 12, 11, 2, 0.0), (32, 8, 13, 2, 0.5), (33, 16, 29, 2, 0.2), (47, 4, 15, 1, 0.0), (47, 12, 25, 2, 0.1)]
