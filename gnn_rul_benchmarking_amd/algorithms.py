@@ -3,7 +3,7 @@ algorithms/algorithms.py:29-48 does it (lookup by name in this module's globals,
 ``NotImplementedError("Algorithm not found: ...")`` otherwise).
 
 The ST_GCN (reference algorithms/algorithms.py:465-490), STMSGCN (:546-571), ASTGCNN (:139-163), FC_STGNN (:51-76), HAGCN (:222-248),
-ST_Conv (:195-220), GRU_CM (:355-380) and AGCN_TF (:574-599) wrappers are implemented:
+ST_Conv (:195-220), GRU_CM (:355-380), AGCN_TF (:574-599) and HierCorrPool (:79-104) wrappers are implemented:
 the hot paths this package accelerates.  The classes keep the reference contract -- constructor
 ``(configs, hparams, device)``, attributes ``model`` / ``optimizer`` / ``hparams`` / ``mse``,
 ``update(X, y, epoch) -> {'loss': float}`` -- so the reference's trainer can drive it unchanged."""
@@ -28,6 +28,7 @@ from .stmsgcn import STMSGCN_model
 from .stnet import STNet_model
 from .sagcn import SAGCN_model
 from .agcntf import AGCN_TF_model
+from .hiercorrpool import HierCorrPool_model
 from .stagnn import STAGNN_model
 
 
@@ -282,6 +283,19 @@ class AGCN_TF(_FusedAlgorithm):
     supports_graphs = False
 
 
+class HierCorrPool(_FusedAlgorithm):
+    """HierCorrPool training wrapper (reference algorithms.py:79-104; csrc/hiercorrpool.hip): batch statistics in the encoder's three
+    BatchNorm1d layers, running statistics updated inside the step, dropout behind the first encoder block.  Data parallelism (and with
+    it synchronised BatchNorm) is not built for this family yet."""
+    model_class = HierCorrPool_model
+    supports_graphs = False
+    needs_train_mode = "BatchNorm batch statistics, dropout"
+
+    def attach_data_parallel(self, dp):
+        raise RuntimeError("data parallelism for HierCorrPool is not built yet (its BatchNorm statistics and dropout stream are "
+                           "single-process): run independent replicas")
+
+
 class STAGNN(_FusedAlgorithm):
     """STAGNN training wrapper (reference algorithms.py:298-323; csrc/stagnn.hip): batch statistics in the four BatchNorm1d layers,
     running statistics updated inside the step.  Data parallelism: rank-local BatchNorm statistics."""
@@ -298,4 +312,4 @@ class GRU_CM(_FusedAlgorithm):
     needs_train_mode = "dropout"
 
 
-_NOT_ALGORITHMS = {"Algorithm", "GRU_CM_model", "FusedAdam", "RGCNU_model", "STNet_model", "SAGCN_model", "AGCN_TF_model", "STAGNN_model", "ST_GCN_model", "STMSGCN_model", "ASTGCNN_model", "FC_STGNN_RUL", "HAGCN_model", "ST_Conv_model", "STGNN_model", "get_algorithm_class", "torch", "nn", "annotations", "math", "_lib", "deferred_weight_gradients"}
+_NOT_ALGORITHMS = {"Algorithm", "GRU_CM_model", "FusedAdam", "RGCNU_model", "STNet_model", "SAGCN_model", "AGCN_TF_model", "HierCorrPool_model", "STAGNN_model", "ST_GCN_model", "STMSGCN_model", "ASTGCNN_model", "FC_STGNN_RUL", "HAGCN_model", "ST_Conv_model", "STGNN_model", "get_algorithm_class", "torch", "nn", "annotations", "math", "_lib", "deferred_weight_gradients"}

@@ -106,6 +106,11 @@ int gru_persistent_backward(const rulgnn_gru_shape* s, const rulgnn_gru_args* a,
 int64_t grucm_param_count(const rulgnn_grucm_shape* s);
 size_t grucm_workspace_bytes(const rulgnn_grucm_shape* s);
 int grucm_run(const rulgnn_grucm_shape* s, const rulgnn_grucm_args* a, int mode, hipStream_t st);
+int64_t hiercorrpool_param_count(const rulgnn_hiercorrpool_shape* s);
+int64_t hiercorrpool_bn_state_count(const rulgnn_hiercorrpool_shape* s);
+size_t hiercorrpool_workspace_bytes(const rulgnn_hiercorrpool_shape* s);
+int64_t hiercorrpool_tap_offset(const rulgnn_hiercorrpool_shape* s, int which);
+int hiercorrpool_run(const rulgnn_hiercorrpool_shape* s, const rulgnn_hiercorrpool_args* a, int mode, hipStream_t st);
 size_t rul_metrics_workspace_bytes(int64_t n);
 int rul_metrics(const float* pred, const float* real, int64_t n, float max_rul, double* out, void* workspace, size_t workspace_bytes,
                 hipStream_t st, int raw = 0);

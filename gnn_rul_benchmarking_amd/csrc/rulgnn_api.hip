@@ -304,6 +304,8 @@ size_t rulgnn_struct_size(int32_t which) {
     case RULGNN_STRUCT_GRUCM_ARGS: return sizeof(rulgnn_grucm_args);
     case RULGNN_STRUCT_AGCNTF_SHAPE: return sizeof(rulgnn_agcntf_shape);
     case RULGNN_STRUCT_AGCNTF_ARGS: return sizeof(rulgnn_agcntf_args);
+    case RULGNN_STRUCT_HIERCORRPOOL_SHAPE: return sizeof(rulgnn_hiercorrpool_shape);
+    case RULGNN_STRUCT_HIERCORRPOOL_ARGS: return sizeof(rulgnn_hiercorrpool_args);
     default: return 0;
     }
 }
@@ -1126,6 +1128,44 @@ int rulgnn_grucm_fwdbwd_f32(const rulgnn_grucm_shape* shape, const rulgnn_grucm_
     RULGNN_TRY(check_grucm(shape, args, true));
     auto run = [&](hipStream_t st) { return grucm_run(shape, args, 3, st); };
     return fused_step_tail(args->dpred, !args->y && shape->batch > 0, opt, args->params, run, args->grads, 0, grucm_param_count(shape), stream);
+}
+
+int64_t rulgnn_hiercorrpool_param_count(const rulgnn_hiercorrpool_shape* shape) { return hiercorrpool_param_count(shape); }
+int64_t rulgnn_hiercorrpool_bn_state_count(const rulgnn_hiercorrpool_shape* shape) { return hiercorrpool_bn_state_count(shape); }
+size_t rulgnn_hiercorrpool_workspace_bytes(const rulgnn_hiercorrpool_shape* shape) { return hiercorrpool_workspace_bytes(shape); }
+int64_t rulgnn_hiercorrpool_tap_offset(const rulgnn_hiercorrpool_shape* shape, int32_t which) { return hiercorrpool_tap_offset(shape, which); }
+
+static int check_hiercorrpool(const rulgnn_hiercorrpool_shape* shape, const rulgnn_hiercorrpool_args* a, bool bwd) {
+    if (!shape || !a) return RULGNN_EINVAL;
+    if (hiercorrpool_param_count(shape) < 0)          // (a negative extent is invalid, anything else outside the limits unsupported)
+        return shape->batch >= 0 && shape->patch_size >= 0 && shape->num_patch >= 0 && shape->hidden_dim >= 0 && shape->embedding_dim >= 0 &&
+                       shape->num_nodes >= 0 && shape->encoder_conv_kernel >= 0 && shape->num_nodes_out >= 0
+                   ? RULGNN_EUNSUPPORTED
+                   : RULGNN_EINVAL;
+    if (a->global_batch < shape->batch || a->sample_offset < 0) return RULGNN_EINVAL;
+    if (!(a->dropout_p >= 0.f && a->dropout_p < 1.f)) return RULGNN_EINVAL;
+    RULGNN_TRY(check_ptrs({a->params, a->workspace, a->bn_state}));
+    RULGNN_TRY(check_step_ptrs(a->params, a->workspace, a->x, a->pred, a->grads, a->y, a->dpred, shape->batch, bwd));
+    return bwd && !a->training ? RULGNN_EINVAL : RULGNN_OK;
+}
+
+int rulgnn_hiercorrpool_forward_f32(const rulgnn_hiercorrpool_shape* shape, const rulgnn_hiercorrpool_args* args, void* stream) {
+    const int rc = check_hiercorrpool(shape, args, false);
+    if (rc != RULGNN_OK) return rc;
+    return hiercorrpool_run(shape, args, 1, static_cast<hipStream_t>(stream));
+}
+
+int rulgnn_hiercorrpool_backward_f32(const rulgnn_hiercorrpool_shape* shape, const rulgnn_hiercorrpool_args* args, void* stream) {
+    const int rc = check_hiercorrpool(shape, args, true);
+    if (rc != RULGNN_OK) return rc;
+    return hiercorrpool_run(shape, args, 2, static_cast<hipStream_t>(stream));
+}
+
+int rulgnn_hiercorrpool_fwdbwd_f32(const rulgnn_hiercorrpool_shape* shape, const rulgnn_hiercorrpool_args* args, const rulgnn_adam_args* opt,
+                                   void* stream) {
+    RULGNN_TRY(check_hiercorrpool(shape, args, true));
+    auto run = [&](hipStream_t st) { return hiercorrpool_run(shape, args, 3, st); };
+    return fused_step_tail(args->dpred, !args->y && shape->batch > 0, opt, args->params, run, args->grads, 0, hiercorrpool_param_count(shape), stream);
 }
 
 size_t rulgnn_rul_metrics_workspace_bytes(int64_t n) { return rul_metrics_workspace_bytes(n); }

@@ -1,7 +1,7 @@
 """Hyper-parameter tables, looked up by dataset name then dataset id, like the reference's
 configs/hparams.py:3-7 (``get_hparams_class(name)(dataset_id)`` -> object with ``train_params`` and
 ``alg_hparams`` dicts keyed by ``--GNN_method``; unknown dataset -> NotImplementedError, unknown id ->
-ValueError).  Only the ST_GCN, STMSGCN, ASTGCNN, FC_STGNN, HAGCN, ST_Conv, STGNN, RGCNU, GRU_CM, STNet, SAGCN, AGCN_TF and STAGNN rows are restated (the methods this package
+ValueError).  Only the ST_GCN, STMSGCN, ASTGCNN, FC_STGNN, HAGCN, ST_Conv, STGNN, RGCNU, GRU_CM, STNet, SAGCN, AGCN_TF, STAGNN and HierCorrPool rows are restated (the methods this package
 implements).
 
 PHM2012 / XJTU_SY rows are the reference's (configs/hparams.py:223,238,... and :334,349,...; STMSGCN
@@ -34,6 +34,8 @@ _FC_STGNN_ROWS = {
     None: {'patch_size': 2, 'num_patch': 25, 'encoder_time_out': 4, 'encoder_hidden_dim': 8, 'encoder_out_dim': 32,
            'encoder_conv_kernel': 2, 'hidden_dim': 8, 'num_sequential': 6, 'num_node': 20, 'num_windows': 36},
 }
+# configs/hparams.py:17,35 / 54,72 / 94,112 / 134,152 (C-MAPSS FD001-4) and :182,199 (N-CMAPSS): (patch_size, num_patch, encoder_conv_kernel)
+_HIERCORRPOOL_ROWS = {'FD001': (25, 2, 8), 'FD002': (10, 5, 12), 'FD003': (5, 10, 12), 'FD004': (10, 5, 12), None: (1, 50, 32)}
 
 
 def get_hparams_class(dataset_name):
@@ -86,6 +88,10 @@ class _Table:
             # configs/hparams.py:26,46,64,87,104,127,144,167 (C-MAPSS FD001-4) and :190,210 (N-CMAPSS): one row everywhere
             self.train_params['GRU_CM'] = dict(_ASTGCNN_TRAIN)
             self.alg_hparams['GRU_CM'] = {'num_nodes': self._astgcnn_nodes, 'time_length': 50, 'gru_hidden_dim': 64}
+            self.train_params['HierCorrPool'] = dict(_ASTGCNN_TRAIN)
+            ps, npatch, conv_kernel = _HIERCORRPOOL_ROWS[dataset_id]
+            self.alg_hparams['HierCorrPool'] = {'patch_size': ps, 'num_patch': npatch, 'input_dim': 10, 'hidden_dim': 10, 'embedding_dim': 10,
+                                                'num_nodes': self._astgcnn_nodes, 'encoder_conv_kernel': conv_kernel, 'num_nodes_out': 6}
         if dataset_id in self._stnet_rows:
             self.train_params['STNet'] = {'num_epochs': 81, 'batch_size': 100, 'weight_decay': 1e-2, 'learning_rate': 1e-2}
             num_patch, patch_size, num_nodes, nperseg, input_dim = self._stnet_rows[dataset_id]

@@ -334,6 +334,8 @@ size_t rulgnn_stgcn_train_args_size(void);
 #define RULGNN_STRUCT_GRUCM_ARGS 26
 #define RULGNN_STRUCT_AGCNTF_SHAPE 27
 #define RULGNN_STRUCT_AGCNTF_ARGS 28
+#define RULGNN_STRUCT_HIERCORRPOOL_SHAPE 29
+#define RULGNN_STRUCT_HIERCORRPOOL_ARGS 30
 size_t rulgnn_struct_size(int32_t which);
 
 /* Profiling aid: the training step is a chain of 4*num_layers+1 phase kernels:
@@ -1205,6 +1207,70 @@ int rulgnn_grucm_forward_f32(const rulgnn_grucm_shape *shape, const rulgnn_grucm
 int rulgnn_grucm_backward_f32(const rulgnn_grucm_shape *shape, const rulgnn_grucm_args *args, void *stream);
 /* GRU_CM.update body (algorithms.py:371-380); with `opt` also Adam on the flat parameter buffer. */
 int rulgnn_grucm_fwdbwd_f32(const rulgnn_grucm_shape *shape, const rulgnn_grucm_args *args, const rulgnn_adam_args *opt, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * HierCorrPool path (reference models/HierCorrPool/Model.py:6-52, Model_Base.py:11-145, algorithms/algorithms.py:79-104; wired to
+ * C-MAPSS FD001-4 and N-CMAPSS, configs/hparams.py:17,35,72,112,152,199).
+ *
+ * N = num_nodes, M = num_nodes_out, h = hidden_dim, e = embedding_dim, K = encoder_conv_kernel, P = num_patch, p = patch_size.
+ * x [batch, N, P p] -> encoder input [batch, C0 = N p, P], in[b][n p + j][t] = x[b][n][t p + j] -> three blocks C0 -> C1 = h N ->
+ * C2 = 2 h N -> C3 = 4 h N of Conv1d(k 8, padding 4, no bias; L -> L + 1) -> BatchNorm1d -> ReLU -> MaxPool1d(2, 2, padding 1)
+ * (L + 1 -> (L + 1) / 2 + 1; the first index wins a tie), Dropout behind block 1 -> F [batch, L', C3], read FLAT per sample as node
+ * features X [N, d], X[n][k e + q] = F[(k N + n) e + q], d = K e = L' 4 h -> G = X X^T, A = softmax_row(leaky_relu(G) off the diagonal)
+ * + I -> Z = sigmoid((A X) Wd^T + bd) [N, M], S = softmax over the NODES of ([A | Z] Wm^T + bm) -> X' = S^T X, A' = S^T A S ->
+ * H = leaky_relu((A' X') Wt^T + bt) [M, 3 d] -> leaky_relu(fc_1(leaky_relu(fc_0(H.flat)))).  HierCorrPool.update: plain MSE.
+ * The three BatchNorm1d layers use batch statistics over batch x length when `training` (differentiated through those statistics)
+ * and the running statistics otherwise.
+ *
+ * Flat parameter buffer in the reference's named_parameters() order (19 tensors):
+ *   Time_Preprocessing.conv_block{1,2,3}.{0.weight[Cout][Cin][8], 1.weight[Cout], 1.bias[Cout]} |
+ *   gc1.Message_Passing.theta.0.{weight[3d][d], bias[3d]} | gc1.Graph_Clustering.{dimension_mapping.{weight[M][d], bias[M]},
+ *   matrix.{weight[M][N + M], bias[M]}} | fc_0.{weight[3e][3 d M], bias[3e]} | fc_1.{weight[3e], bias[1]}
+ * The gradient of matrix.bias (constant along the softmax axis) is written as exact zeros.
+ * bn_state: [running_mean | running_var] of conv_block1.1, conv_block2.1, conv_block3.1 (2 * 7 h N floats).
+ * Dropout: the counter hash of the other families, key = dropout_layer_key(seed, step, site 0), dropped where
+ * lowbias32(counter ^ key) < round(p 2^32); the counter of block 1's pooled output [b][c][t] is
+ * ((sample_offset + b) C1 + c) L1 + t, mod 2^32.
+ * Limits: 2 <= N <= 32, 1 <= M <= 16, 2 <= P <= 64, 1 <= p <= 64, d <= 512, C3 <= 1024, L' 4 h == K e (RULGNN_EUNSUPPORTED beyond,
+ * before any launch: the workspace query returns 0).  Deterministic: no floating-point atomics, fixed-order reductions.
+ */
+typedef struct rulgnn_hiercorrpool_shape {
+    int64_t batch;
+    int32_t patch_size, num_patch, hidden_dim, embedding_dim, num_nodes, encoder_conv_kernel, num_nodes_out;
+} rulgnn_hiercorrpool_shape;
+
+typedef struct rulgnn_hiercorrpool_args {
+    const float *x;           /* [batch, num_nodes, num_patch * patch_size] */
+    const float *y;           /* [batch] targets, or NULL */
+    const float *dpred;       /* [batch] d loss / d pred (autograd backward); NULL = MSE against y */
+    const float *params;
+    float *grads;             /* same layout as params */
+    float *pred;              /* [batch] */
+    float *loss;              /* [1] sum over the shard of (pred - y)^2 / global_batch; may be NULL */
+    float *bn_state;          /* running statistics, see above; read in eval mode, updated by a training forward when asked to */
+    void *workspace;
+    size_t workspace_bytes;
+    int64_t global_batch;
+    int64_t sample_offset;    /* index of this shard's first sample in the global batch (dropout stream) */
+    float dropout_p;          /* block 1's nn.Dropout rate (0.35 in the reference); applied when training != 0 */
+    uint64_t seed, step;      /* dropout stream: mask = f(seed, step, element counter); a backward takes its forward's values */
+    int32_t training;              /* != 0: batch statistics and dropout (model.train()) */
+    int32_t update_running_stats;  /* != 0 with training: momentum-0.1 update of bn_state, unbiased variance (BatchNorm1d's defaults) */
+} rulgnn_hiercorrpool_args;
+
+int64_t rulgnn_hiercorrpool_param_count(const rulgnn_hiercorrpool_shape *shape);       /* < 0: invalid / unsupported */
+int64_t rulgnn_hiercorrpool_bn_state_count(const rulgnn_hiercorrpool_shape *shape);    /* < 0: invalid / unsupported */
+size_t rulgnn_hiercorrpool_workspace_bytes(const rulgnn_hiercorrpool_shape *shape);    /* 0: invalid / unsupported */
+/* workspace taps for the parity tests, float offsets: 0 encoder output [batch][L'][C3], 1 pooled_x X' [batch][M][d], 2 pooled_adj A'
+ * [batch][M][M], 3 H [batch][M][3 d]; -1 otherwise */
+int64_t rulgnn_hiercorrpool_tap_offset(const rulgnn_hiercorrpool_shape *shape, int32_t which);
+/* model(x): HierCorrPool_model.forward (Model.py:26-52). */
+int rulgnn_hiercorrpool_forward_f32(const rulgnn_hiercorrpool_shape *shape, const rulgnn_hiercorrpool_args *args, void *stream);
+/* loss.backward() after a TRAINING forward with the same args / workspace (RULGNN_EINVAL when args->training == 0). */
+int rulgnn_hiercorrpool_backward_f32(const rulgnn_hiercorrpool_shape *shape, const rulgnn_hiercorrpool_args *args, void *stream);
+/* HierCorrPool.update body (algorithms.py:95-104); with `opt` also Adam on the flat parameter buffer. */
+int rulgnn_hiercorrpool_fwdbwd_f32(const rulgnn_hiercorrpool_shape *shape, const rulgnn_hiercorrpool_args *args, const rulgnn_adam_args *opt,
+                                   void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * RUL test metrics on the device.
