@@ -142,6 +142,17 @@ class HiercorrpoolArgs(C.Structure):
                 ("seed", C.c_uint64), ("step", C.c_uint64), ("training", C.c_int32), ("update_running_stats", C.c_int32)]
 
 
+class LogoShape(C.Structure):
+    _fields_ = [("batch", C.c_int64), ("patch_size", C.c_int32), ("num_patch", C.c_int32), ("num_nodes", C.c_int32), ("hidden_dim", C.c_int32)]
+
+
+class LogoArgs(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("dpred", C.c_void_p), ("params", C.c_void_p), ("grads", C.c_void_p),
+                ("pred", C.c_void_p), ("loss", C.c_void_p), ("loss_gl", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_size_t), ("global_batch", C.c_int64), ("theta", C.c_float), ("gamma", C.c_float),
+                ("dropout_p", C.c_float), ("seed", C.c_uint64), ("step", C.c_uint64), ("training", C.c_int32)]
+
+
 class StagnnShape(C.Structure):
     _fields_ = [("batch", C.c_int64), ("num_nodes", C.c_int32), ("time_length", C.c_int32), ("hidden_dim", C.c_int32),
                 ("output_dim", C.c_int32), ("num_heads", C.c_int32), ("threshold", C.c_float)]
@@ -332,6 +343,12 @@ _SIGNATURES = {
     "rulgnn_hiercorrpool_forward_f32": (C.c_int, [C.POINTER(HiercorrpoolShape), C.POINTER(HiercorrpoolArgs), C.c_void_p]),
     "rulgnn_hiercorrpool_backward_f32": (C.c_int, [C.POINTER(HiercorrpoolShape), C.POINTER(HiercorrpoolArgs), C.c_void_p]),
     "rulgnn_hiercorrpool_fwdbwd_f32": (C.c_int, [C.POINTER(HiercorrpoolShape), C.POINTER(HiercorrpoolArgs), C.POINTER(AdamArgs), C.c_void_p]),
+    "rulgnn_logo_param_count": (C.c_int64, [C.POINTER(LogoShape)]),
+    "rulgnn_logo_workspace_bytes": (C.c_size_t, [C.POINTER(LogoShape)]),
+    "rulgnn_logo_tap_offset": (C.c_int64, [C.POINTER(LogoShape), C.c_int32]),
+    "rulgnn_logo_forward_f32": (C.c_int, [C.POINTER(LogoShape), C.POINTER(LogoArgs), C.c_void_p]),
+    "rulgnn_logo_backward_f32": (C.c_int, [C.POINTER(LogoShape), C.POINTER(LogoArgs), C.c_void_p]),
+    "rulgnn_logo_fwdbwd_f32": (C.c_int, [C.POINTER(LogoShape), C.POINTER(LogoArgs), C.POINTER(AdamArgs), C.c_void_p]),
     "rulgnn_grucm_param_count": (C.c_int64, [C.POINTER(GrucmShape)]),
     "rulgnn_grucm_workspace_bytes": (C.c_size_t, [C.POINTER(GrucmShape)]),
     "rulgnn_grucm_forward_f32": (C.c_int, [C.POINTER(GrucmShape), C.POINTER(GrucmArgs), C.c_void_p]),
@@ -386,7 +403,7 @@ _SIGNATURES = {
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
 # index -> ctypes mirror, in the order of the RULGNN_STRUCT_* constants of include/rulgnn.h (rulgnn_struct_size)
-STRUCTS = (StgcnShape, StgcnTrainArgs, AdamArgs, StmsgcnShape, StmsgcnArgs, AstgcnnShape, AstgcnnArgs, FcstgnnShape, FcstgnnArgs, RgcnuShape, RgcnuArgs, StnetShape, StnetArgs, SagcnShape, SagcnArgs, StagnnShape, StagnnArgs, HagcnShape, HagcnArgs, BilstmShape, BilstmArgs, StconvShape, StgnnShape, GruShape, GruArgs, GrucmShape, GrucmArgs, AgcntfShape, AgcntfArgs, HiercorrpoolShape, HiercorrpoolArgs)
+STRUCTS = (StgcnShape, StgcnTrainArgs, AdamArgs, StmsgcnShape, StmsgcnArgs, AstgcnnShape, AstgcnnArgs, FcstgnnShape, FcstgnnArgs, RgcnuShape, RgcnuArgs, StnetShape, StnetArgs, SagcnShape, SagcnArgs, StagnnShape, StagnnArgs, HagcnShape, HagcnArgs, BilstmShape, BilstmArgs, StconvShape, StgnnShape, GruShape, GruArgs, GrucmShape, GrucmArgs, AgcntfShape, AgcntfArgs, HiercorrpoolShape, HiercorrpoolArgs, LogoShape, LogoArgs)
 
 _lib = None
 

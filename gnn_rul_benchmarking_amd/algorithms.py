@@ -3,7 +3,7 @@ algorithms/algorithms.py:29-48 does it (lookup by name in this module's globals,
 ``NotImplementedError("Algorithm not found: ...")`` otherwise).
 
 The ST_GCN (reference algorithms/algorithms.py:465-490), STMSGCN (:546-571), ASTGCNN (:139-163), FC_STGNN (:51-76), HAGCN (:222-248),
-ST_Conv (:195-220), GRU_CM (:355-380), AGCN_TF (:574-599) and HierCorrPool (:79-104) wrappers are implemented:
+ST_Conv (:195-220), GRU_CM (:355-380), AGCN_TF (:574-599), HierCorrPool (:79-104) and LOGO (:107-136) wrappers are implemented:
 the hot paths this package accelerates.  The classes keep the reference contract -- constructor
 ``(configs, hparams, device)``, attributes ``model`` / ``optimizer`` / ``hparams`` / ``mse``,
 ``update(X, y, epoch) -> {'loss': float}`` -- so the reference's trainer can drive it unchanged."""
@@ -29,6 +29,7 @@ from .stnet import STNet_model
 from .sagcn import SAGCN_model
 from .agcntf import AGCN_TF_model
 from .hiercorrpool import HierCorrPool_model
+from .logo import LOGO_model
 from .stagnn import STAGNN_model
 
 
@@ -296,6 +297,32 @@ class HierCorrPool(_FusedAlgorithm):
                            "single-process): run independent replicas")
 
 
+class LOGO(_FusedAlgorithm):
+    """LOGO training wrapper (reference algorithms.py:107-136; graph stage of csrc/logo.hip, the three Bi-LSTM layers of csrc/bilstm.hip):
+    ``loss = MSE + theta * L_GL`` with ``theta = hparams['theta']``; the returned ``'loss'`` is that sum.  The reference constructs a
+    ``MultiStepLR`` and never steps it (its ``step()`` is commented out, :135), so the learning rate is constant: no scheduler is built
+    here.  The LSTMs recur along the batch (Model.py:245-251): every sample depends on the whole batch, hence replicas only -- no
+    data-parallel sharding for this model, as for HAGCN."""
+    model_class = LOGO_model
+    supports_graphs = False
+    needs_train_mode = "dropout"
+
+    def __init__(self, configs, hparams, device):
+        super().__init__(configs, hparams, device)
+        self.theta = hparams["theta"]
+
+    def attach_data_parallel(self, dp):
+        raise RuntimeError("LOGO is not sample-shardable (its LSTMs recur along the batch): run independent replicas")
+
+    def _eager_update(self, X, y):
+        _, loss = self.model.fused_mse_step(X, y, self.optimizer, theta=self.theta)
+        return loss
+
+    def _reference_loss(self, X, y):
+        predicted_RUL, loss_GL = self.model(X, GL=True)           # algorithms.py:126-130
+        return self.mse(predicted_RUL, y) + self.theta * loss_GL
+
+
 class STAGNN(_FusedAlgorithm):
     """STAGNN training wrapper (reference algorithms.py:298-323; csrc/stagnn.hip): batch statistics in the four BatchNorm1d layers,
     running statistics updated inside the step.  Data parallelism: rank-local BatchNorm statistics."""
@@ -312,4 +339,4 @@ class GRU_CM(_FusedAlgorithm):
     needs_train_mode = "dropout"
 
 
-_NOT_ALGORITHMS = {"Algorithm", "GRU_CM_model", "FusedAdam", "RGCNU_model", "STNet_model", "SAGCN_model", "AGCN_TF_model", "HierCorrPool_model", "STAGNN_model", "ST_GCN_model", "STMSGCN_model", "ASTGCNN_model", "FC_STGNN_RUL", "HAGCN_model", "ST_Conv_model", "STGNN_model", "get_algorithm_class", "torch", "nn", "annotations", "math", "_lib", "deferred_weight_gradients"}
+_NOT_ALGORITHMS = {"Algorithm", "GRU_CM_model", "FusedAdam", "RGCNU_model", "STNet_model", "SAGCN_model", "AGCN_TF_model", "HierCorrPool_model", "LOGO_model", "STAGNN_model", "ST_GCN_model", "STMSGCN_model", "ASTGCNN_model", "FC_STGNN_RUL", "HAGCN_model", "ST_Conv_model", "STGNN_model", "get_algorithm_class", "torch", "nn", "annotations", "math", "_lib", "deferred_weight_gradients"}

@@ -111,6 +111,10 @@ int64_t hiercorrpool_bn_state_count(const rulgnn_hiercorrpool_shape* s);
 size_t hiercorrpool_workspace_bytes(const rulgnn_hiercorrpool_shape* s);
 int64_t hiercorrpool_tap_offset(const rulgnn_hiercorrpool_shape* s, int which);
 int hiercorrpool_run(const rulgnn_hiercorrpool_shape* s, const rulgnn_hiercorrpool_args* a, int mode, hipStream_t st);
+int64_t logo_param_count(const rulgnn_logo_shape* s);
+size_t logo_workspace_bytes(const rulgnn_logo_shape* s);
+int64_t logo_tap_offset(const rulgnn_logo_shape* s, int which);
+int logo_run(const rulgnn_logo_shape* s, const rulgnn_logo_args* a, int mode, hipStream_t st);
 size_t rul_metrics_workspace_bytes(int64_t n);
 int rul_metrics(const float* pred, const float* real, int64_t n, float max_rul, double* out, void* workspace, size_t workspace_bytes,
                 hipStream_t st, int raw = 0);

@@ -306,6 +306,8 @@ size_t rulgnn_struct_size(int32_t which) {
     case RULGNN_STRUCT_AGCNTF_ARGS: return sizeof(rulgnn_agcntf_args);
     case RULGNN_STRUCT_HIERCORRPOOL_SHAPE: return sizeof(rulgnn_hiercorrpool_shape);
     case RULGNN_STRUCT_HIERCORRPOOL_ARGS: return sizeof(rulgnn_hiercorrpool_args);
+    case RULGNN_STRUCT_LOGO_SHAPE: return sizeof(rulgnn_logo_shape);
+    case RULGNN_STRUCT_LOGO_ARGS: return sizeof(rulgnn_logo_args);
     default: return 0;
     }
 }
@@ -1166,6 +1168,40 @@ int rulgnn_hiercorrpool_fwdbwd_f32(const rulgnn_hiercorrpool_shape* shape, const
     RULGNN_TRY(check_hiercorrpool(shape, args, true));
     auto run = [&](hipStream_t st) { return hiercorrpool_run(shape, args, 3, st); };
     return fused_step_tail(args->dpred, !args->y && shape->batch > 0, opt, args->params, run, args->grads, 0, hiercorrpool_param_count(shape), stream);
+}
+
+int64_t rulgnn_logo_param_count(const rulgnn_logo_shape* shape) { return logo_param_count(shape); }
+size_t rulgnn_logo_workspace_bytes(const rulgnn_logo_shape* shape) { return logo_workspace_bytes(shape); }
+int64_t rulgnn_logo_tap_offset(const rulgnn_logo_shape* shape, int32_t which) { return logo_tap_offset(shape, which); }
+
+static int check_logo(const rulgnn_logo_shape* shape, const rulgnn_logo_args* a, bool bwd) {
+    if (!shape || !a) return RULGNN_EINVAL;
+    if (logo_workspace_bytes(shape) == 0)          // (a negative extent is invalid, anything else outside the limits unsupported)
+        return shape->batch >= 0 && shape->patch_size >= 0 && shape->num_patch >= 0 && shape->num_nodes >= 0 && shape->hidden_dim >= 0
+                   ? RULGNN_EUNSUPPORTED
+                   : RULGNN_EINVAL;
+    if (a->global_batch < shape->batch) return RULGNN_EINVAL;
+    if (!(a->dropout_p >= 0.f && a->dropout_p < 1.f)) return RULGNN_EINVAL;
+    if (!opt_aligned(a->loss) || !opt_aligned(a->loss_gl)) return RULGNN_EALIGN;
+    return check_step_ptrs(a->params, a->workspace, a->x, a->pred, a->grads, a->y, a->dpred, shape->batch, bwd);
+}
+
+int rulgnn_logo_forward_f32(const rulgnn_logo_shape* shape, const rulgnn_logo_args* args, void* stream) {
+    const int rc = check_logo(shape, args, false);
+    if (rc != RULGNN_OK) return rc;
+    return logo_run(shape, args, 1, static_cast<hipStream_t>(stream));
+}
+
+int rulgnn_logo_backward_f32(const rulgnn_logo_shape* shape, const rulgnn_logo_args* args, void* stream) {
+    const int rc = check_logo(shape, args, true);
+    if (rc != RULGNN_OK) return rc;
+    return logo_run(shape, args, 2, static_cast<hipStream_t>(stream));
+}
+
+int rulgnn_logo_fwdbwd_f32(const rulgnn_logo_shape* shape, const rulgnn_logo_args* args, const rulgnn_adam_args* opt, void* stream) {
+    RULGNN_TRY(check_logo(shape, args, true));
+    auto run = [&](hipStream_t st) { return logo_run(shape, args, 3, st); };
+    return fused_step_tail(args->dpred, !args->y && shape->batch > 0, opt, args->params, run, args->grads, 0, logo_param_count(shape), stream);
 }
 
 size_t rulgnn_rul_metrics_workspace_bytes(int64_t n) { return rul_metrics_workspace_bytes(n); }

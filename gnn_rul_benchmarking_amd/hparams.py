@@ -1,7 +1,7 @@
 """Hyper-parameter tables, looked up by dataset name then dataset id, like the reference's
 configs/hparams.py:3-7 (``get_hparams_class(name)(dataset_id)`` -> object with ``train_params`` and
 ``alg_hparams`` dicts keyed by ``--GNN_method``; unknown dataset -> NotImplementedError, unknown id ->
-ValueError).  Only the ST_GCN, STMSGCN, ASTGCNN, FC_STGNN, HAGCN, ST_Conv, STGNN, RGCNU, GRU_CM, STNet, SAGCN, AGCN_TF, STAGNN and HierCorrPool rows are restated (the methods this package
+ValueError).  Only the ST_GCN, STMSGCN, ASTGCNN, FC_STGNN, HAGCN, ST_Conv, STGNN, RGCNU, GRU_CM, STNet, SAGCN, AGCN_TF, STAGNN, HierCorrPool and LOGO rows are restated (the methods this package
 implements).
 
 PHM2012 / XJTU_SY rows are the reference's (configs/hparams.py:223,238,... and :334,349,...; STMSGCN
@@ -36,6 +36,12 @@ _FC_STGNN_ROWS = {
 }
 # configs/hparams.py:17,35 / 54,72 / 94,112 / 134,152 (C-MAPSS FD001-4) and :182,199 (N-CMAPSS): (patch_size, num_patch, encoder_conv_kernel)
 _HIERCORRPOOL_ROWS = {'FD001': (25, 2, 8), 'FD002': (10, 5, 12), 'FD003': (5, 10, 12), 'FD004': (10, 5, 12), None: (1, 50, 32)}
+
+# configs/hparams.py:18,37 / 55,74 / 95,114 / 135,154 (C-MAPSS FD001-4) and :183,201 (N-CMAPSS: batch 50, weight decay 0):
+# (patch_size, num_patch, hidden_dim, theta).  FD003's hidden_dim 32 is beyond the kernels' 6 * hidden_dim <= 128 (logo.py): the row is
+# restated, its model constructs and its forward is refused.
+_LOGO_ROWS = {'FD001': (10, 5, 8, 0.001), 'FD002': (2, 25, 6, 0.01), 'FD003': (10, 5, 32, 0.01), 'FD004': (10, 5, 10, 0.001),
+              None: (5, 10, 10, 0.001)}
 
 
 def get_hparams_class(dataset_name):
@@ -92,6 +98,10 @@ class _Table:
             ps, npatch, conv_kernel = _HIERCORRPOOL_ROWS[dataset_id]
             self.alg_hparams['HierCorrPool'] = {'patch_size': ps, 'num_patch': npatch, 'input_dim': 10, 'hidden_dim': 10, 'embedding_dim': 10,
                                                 'num_nodes': self._astgcnn_nodes, 'encoder_conv_kernel': conv_kernel, 'num_nodes_out': 6}
+            ps, npatch, hidden, theta = _LOGO_ROWS[dataset_id]
+            self.train_params['LOGO'] = {'num_epochs': 81, 'batch_size': 100 if dataset_id is not None else 50,
+                                         'weight_decay': 1e-4 if dataset_id is not None else 0, 'learning_rate': 1e-3, 'theta': theta}
+            self.alg_hparams['LOGO'] = {'patch_size': ps, 'num_patch': npatch, 'num_nodes': self._astgcnn_nodes, 'hidden_dim': hidden}
         if dataset_id in self._stnet_rows:
             self.train_params['STNet'] = {'num_epochs': 81, 'batch_size': 100, 'weight_decay': 1e-2, 'learning_rate': 1e-2}
             num_patch, patch_size, num_nodes, nperseg, input_dim = self._stnet_rows[dataset_id]

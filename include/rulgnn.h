@@ -336,6 +336,8 @@ size_t rulgnn_stgcn_train_args_size(void);
 #define RULGNN_STRUCT_AGCNTF_ARGS 28
 #define RULGNN_STRUCT_HIERCORRPOOL_SHAPE 29
 #define RULGNN_STRUCT_HIERCORRPOOL_ARGS 30
+#define RULGNN_STRUCT_LOGO_SHAPE 31
+#define RULGNN_STRUCT_LOGO_ARGS 32
 size_t rulgnn_struct_size(int32_t which);
 
 /* Profiling aid: the training step is a chain of 4*num_layers+1 phase kernels:
@@ -1271,6 +1273,75 @@ int rulgnn_hiercorrpool_backward_f32(const rulgnn_hiercorrpool_shape *shape, con
 /* HierCorrPool.update body (algorithms.py:95-104); with `opt` also Adam on the flat parameter buffer. */
 int rulgnn_hiercorrpool_fwdbwd_f32(const rulgnn_hiercorrpool_shape *shape, const rulgnn_hiercorrpool_args *args, const rulgnn_adam_args *opt,
                                    void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * LOGO path (reference models/LOGO/Model.py:198-262, algorithms/algorithms.py:107-136; wired to C-MAPSS FD001-4 and N-CMAPSS,
+ * configs/hparams.py:18,37,55,74,95,114,135,154,183,201).
+ *
+ * N = num_nodes, p = patch_size, T = num_patch, h = hidden_dim, graphs g = (b, t), sequences q = t N + n.
+ * x [batch, N, T p] -> Xg = x[b, :, t p : (t + 1) p], E = Xg Wn^T + bn [N, 2p], A_T = softmax_row(leaky_relu(E E^T - 1e8 I)) + I;
+ * A_G = Pearson correlation of the N rows of x[b] (per sample; a constant sensor gives 0 / 0 = NaN, as the reference);
+ * z = sigmoid(W_Z_T A_T + W_Z_G A_G), r = sigmoid(W_R_T A_T + W_R_G A_G), A^ = tanh(W_h_T A_G + W_h r) (Linear on the last axis),
+ * C = softmax_row((1 - z) A_T + z A^ - 1e8 I) + I, Hg = leaky_relu((C E) Theta^T + b) [N, 3p] -> three bidirectional LSTM layers with
+ * summed halves (3p -> 3h -> 6h -> 3h) whose sequences are the q and whose STEPS are the samples b, in train and in eval: every prediction
+ * depends on the whole batch.  Dropout behind layers 2 and 3, leaky_relu behind layer 3 -> per sample the flat [T N 3h] ->
+ * fc1 (16) ReLU fc2 (8) ReLU cls (1).  L_GL = mean(D . C) + gamma sqrt(mean(C^2)) over all batch T N N entries,
+ * D[i][j] = |Xg_i - Xg_j|^2; LOGO.update: loss = MSE + theta L_GL.
+ *
+ * Flat parameter buffer in the reference's named_parameters() order (46 tensors):
+ *   nonlin_map.{weight[2p][p], bias[2p]} | MPNN.theta.0.{weight[3p][2p], bias[3p]} | TD.bi_lstm{1,2,3}.{weight_ih_l0[4H][I],
+ *   weight_hh_l0[4H][H], bias_ih_l0[4H], bias_hh_l0[4H], the same four with _reverse} with (I, H) = (3p, 3h), (3h, 6h), (6h, 3h) |
+ *   graph_attn_blk.{W_Z_T, W_Z_G, W_R_T, W_R_G, W_h_T, W_h}.{weight[N][N], bias[N]} | fc.fc1.{weight[16][T N 3h], bias[16]} |
+ *   fc.fc2.{weight[8][16], bias[8]} | cls.{weight[8], bias[1]}
+ * Dropout: the counter hash of the other families, key = dropout_layer_key(seed, step, site), site 0 behind bi_lstm2 and 1 behind
+ * bi_lstm3, dropped where lowbias32(counter ^ key) < round(p 2^32); the counter of element [q][b][j] of a layer's output of width W is
+ * ((q batch + b) W + j) mod 2^32.
+ * Limits: 2 <= N <= RULGNN_LOGO_MAX_NODES, 1 <= p <= RULGNN_LOGO_MAX_PATCH_SIZE, T >= 1, N T <= RULGNN_LOGO_MAX_SEQUENCES,
+ * 6 h <= RULGNN_LOGO_MAX_LSTM_WIDTH (the persistent LSTM's widest layer), and a sample's whole window plus the graph stage's matrices
+ * within one compute unit's 160 KB of LDS (roughly N T p <= 38 000, which binds before N T does)
+ * (RULGNN_EUNSUPPORTED beyond, before any launch: the workspace query returns 0).  Deterministic: no floating-point atomics,
+ * fixed-order reductions.
+ */
+#define RULGNN_LOGO_MAX_NODES 32
+#define RULGNN_LOGO_MAX_PATCH_SIZE 16
+#define RULGNN_LOGO_MAX_SEQUENCES 65535
+#define RULGNN_LOGO_MAX_LSTM_WIDTH 128
+
+typedef struct rulgnn_logo_shape {
+    int64_t batch;
+    int32_t patch_size, num_patch, num_nodes, hidden_dim;
+} rulgnn_logo_shape;
+
+typedef struct rulgnn_logo_args {
+    const float *x;           /* [batch, num_nodes, num_patch * patch_size] */
+    const float *y;           /* [batch] targets, or NULL */
+    const float *dpred;       /* [batch] d loss / d pred (autograd backward); NULL = MSE against y */
+    const float *params;
+    float *grads;             /* same layout as params */
+    float *pred;              /* [batch] */
+    float *loss;              /* [1] sum over the batch of (pred - y)^2 / global_batch + theta * L_GL; may be NULL */
+    float *loss_gl;           /* [1] L_GL; may be NULL */
+    void *workspace;
+    size_t workspace_bytes;
+    int64_t global_batch;
+    float theta;              /* d loss / d L_GL: hparams['theta'] in a fused step, the incoming gradient of L_GL in an autograd backward */
+    float gamma;              /* weight of sqrt(mean(C^2)) in L_GL (1 in the reference) */
+    float dropout_p;          /* drop2 / drop3 rate (0.2 in the reference); applied when training != 0 */
+    uint64_t seed, step;      /* dropout stream: mask = f(seed, step, element counter); a backward takes its forward's values */
+    int32_t training;         /* != 0: dropout (model.train()) */
+} rulgnn_logo_args;
+
+int64_t rulgnn_logo_param_count(const rulgnn_logo_shape *shape);       /* < 0: invalid / unsupported */
+size_t rulgnn_logo_workspace_bytes(const rulgnn_logo_shape *shape);    /* 0: invalid / unsupported */
+/* workspace taps for the parity tests, float offsets: 0 the graph stage's output Hg [T N][batch][3p], 1 the temporal stack's output
+ * [batch][T N][3h] (the layout fc1 reads), 2 {L_GL, sum(D . C), sum(C^2)}; -1 otherwise */
+int64_t rulgnn_logo_tap_offset(const rulgnn_logo_shape *shape, int32_t which);
+/* model(x, GL=True): LOGO_model.forward (Model.py:222-262). */
+int rulgnn_logo_forward_f32(const rulgnn_logo_shape *shape, const rulgnn_logo_args *args, void *stream);
+/* loss.backward() after a forward with the same args / workspace; theta = d loss / d L_GL. */
+int rulgnn_logo_backward_f32(const rulgnn_logo_shape *shape, const rulgnn_logo_args *args, void *stream);
+/* LOGO.update body (algorithms.py:125-136); with `opt` also Adam on the flat parameter buffer. */
+int rulgnn_logo_fwdbwd_f32(const rulgnn_logo_shape *shape, const rulgnn_logo_args *args, const rulgnn_adam_args *opt, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * RUL test metrics on the device.

@@ -1,0 +1,390 @@
+"""LOGO HIP path vs the reference's golden outputs and vs the fp64 oracle (GPU).
+
+Gates.  Predictions, taps, L_GL and the loss: TOL = 1e-4 relative to the tensor's largest value, the bar of the other families.
+Gradients: element by element through tests/grad_gate.py at rtol 5e-4 and margin 16.  (The gate this family starts from is HAGCN's
+1e-3, tests/test_hagcn_gpu.py:15, since it is the same LSTM stack; on an MI355X the worst ratio of every case at 5e-4 sat below 0.5 --
+0.14 at most -- so the tighter 5e-4 is the gate, the rule this family was given.)  The floor's noise term is the REFERENCE's fp32
+gradient against the fp64 oracle (the fixture's ``refgrad:`` entries; without a fixture an fp32 run of the torch restatement on the
+CPU), never the kernels' output.  Every test prints its worst gate ratio ("LOGO-GATE ...")."""
+import argparse
+import functools
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import adam_reference as R
+import grad_gate as GG
+import logo_oracle as O
+from test_logo_oracle_golden import CASES, CURVE, load_case, rel
+
+pytestmark = pytest.mark.gpu
+GOLD = os.path.join(os.path.dirname(__file__), "golden")
+DEV = "cuda:0"
+TOL, RTOL = 1e-4, 5e-4
+KEYS = O.KEYS
+FD001 = dict(patch_size=10, num_patch=5, num_nodes=14, hidden_dim=8)
+FD004 = dict(patch_size=10, num_patch=5, num_nodes=14, hidden_dim=10)
+
+
+def make_cfg(p, T, N, h):
+    return dict(patch_size=p, num_patch=T, num_nodes=N, hidden_dim=h)
+
+
+def build_model(cfg, sd, dropout=0.0):
+    from gnn_rul_benchmarking_amd.logo import LOGO_model
+    m = LOGO_model(**{k: cfg[k] for k in KEYS})
+    m.load_state_dict({k: torch.from_numpy(np.asarray(v, np.float32)) for k, v in sd.items()}, strict=True)
+    m.dropout_p = dropout
+    return m.to(DEV)
+
+
+def seeded_state(cfg, seed):
+    """The constructor's state dict under ``seed``, moved away from init as the fixtures' maker does (numpy)."""
+    from gnn_rul_benchmarking_amd.logo import LOGO_model
+    torch.manual_seed(seed)
+    g = torch.Generator().manual_seed(seed + 1000)
+    return {k: (v + torch.empty_like(v).uniform_(-0.1, 0.1, generator=g)).numpy().copy()
+            for k, v in LOGO_model(**{k: cfg[k] for k in KEYS}).state_dict().items()}
+
+
+def grads_of(m):
+    flat = m._grad_flat[:m.num_live].detach().cpu().numpy().astype(np.float64)
+    return {name: flat[off:off + int(np.prod(shape))].reshape(shape) for name, (off, shape) in m._layout.items()}
+
+
+def check_grads(what, got, g64, ref32):
+    worst = (0.0, None)
+    for k in O.param_names():
+        if not g64[k].any():              # exactly zero in the oracle (bs = 1: a one-step recurrence has h_prev = 0, so g weight_hh = 0)
+            assert got[k].shape == g64[k].shape and not got[k].any() and not np.asarray(ref32[k]).any(), f"{k} must be exactly zero"
+            continue
+        ratio, where = GG.gate(got[k], g64[k], RTOL, GG.floor_for(ref32[k], g64[k]))
+        print(f"  grad {k}: gate {ratio:.3f} at {where}  rel {rel(got[k], g64[k]):.2e}  max|g| {np.abs(g64[k]).max():.2e}")
+        worst = max(worst, (ratio, k))
+    print(f"LOGO-GATE {what}: worst gradient gate ratio {worst[0]:.3f} ({worst[1]})")
+    assert worst[0] <= 1.0, worst
+
+
+def check_forward(what, m, bs, pred, loss, want, want_loss):
+    errs = {"mpnn": rel(m.tap(bs, "mpnn").cpu().numpy(), want["mpnn"]), "lstm": rel(m.tap(bs, "lstm").cpu().numpy(), want["lstm"]),
+            "gl": abs(float(m.tap(bs, "gl")) - want["gl"]) / abs(want["gl"]),
+            "pred": rel(pred.detach().cpu().numpy().reshape(-1, 1), np.asarray(want["pred"]).reshape(-1, 1))}
+    if loss is not None:
+        errs["loss"] = abs(float(loss) - want_loss) / abs(want_loss)
+    print(f"LOGO-GATE {what}: forward " + " ".join(f"{k}={v:.2e}" for k, v in errs.items()))
+    for k, v in errs.items():
+        assert v < TOL, (k, v)
+
+
+@functools.lru_cache(maxsize=None)
+def fixture_oracle(name):
+    z, cfg, sd = load_case(name)
+    loss, g, fw = O.loss_and_grads(sd, z["x"], z["y"], cfg, float(z["theta"]))
+    return z, cfg, sd, loss, g, fw
+
+
+# ---- 1. the reference's fixtures ----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", CASES)
+def test_fixture_forward_taps_loss_and_gradients(name):
+    z, cfg, sd, loss64, g64, fw = fixture_oracle(name)
+    theta = float(z["theta"])
+    m = build_model(cfg, sd).train()
+    x, y = torch.from_numpy(z["x"]).to(DEV), torch.from_numpy(z["y"]).to(DEV)
+    bs = x.size(0)
+    pred, loss = m.fused_mse_step(x, y, theta=theta)
+    ref = {"mpnn": z["mpnn"], "lstm": z["lstm"], "gl": float(z["loss_gl"]), "pred": z["pred"]}
+    check_forward(name, m, bs, pred, loss, ref, float(z["loss"]))                  # against the reference itself ...
+    check_forward(name + "-oracle", m, bs, pred, loss, fw, loss64)                 # ... and the fp64 oracle
+    check_grads(name, grads_of(m), g64, {k: z["refgrad:" + k] for k in O.param_names()})
+    m.eval()
+    with torch.no_grad():
+        ev, gl = m(x, GL=True)
+    assert ev.shape == (bs, 1) and gl.dim() == 0
+    assert rel(ev.cpu().numpy(), z["pred_eval"]) < TOL and abs(float(gl) - float(z["loss_gl"])) < TOL * float(z["loss_gl"])
+
+
+# ---- 2. full width against the fp64 oracle ------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def seeded_case(cfg_items, bs, seed):
+    """Weights, inputs and targets under ``seed``, advanced -- as the fixtures' maker does -- until at least half of the samples reach the
+    prediction through an open ReLU of fc1 and of fc2 (behind a closed one every gradient but the last bias's is an exact zero)."""
+    cfg = dict(cfg_items)
+    while True:
+        sd = seeded_state(cfg, seed)
+        rng = np.random.default_rng(seed)
+        x = rng.uniform(0, 1, (bs, cfg["num_nodes"], cfg["num_patch"] * cfg["patch_size"])).astype(np.float32)
+        y = rng.uniform(0, 1, bs).astype(np.float32)
+        fw = O.forward(sd, x, cfg)
+        if 2 * int(((fw["pre1"] > 0).any(1) & (fw["pre2"] > 0).any(1)).sum()) >= bs:
+            return cfg, sd, x, y
+        seed += 1
+
+
+def oracle_step_check(what, cfg, sd, x, y, theta):
+    loss64, g64, fw = O.loss_and_grads(sd, x, y, cfg, theta)
+    _, _, g32 = O.torch_grads(sd, x, y, cfg, theta, torch.float32)
+    m = build_model(cfg, sd).train()
+    pred, loss = m.fused_mse_step(torch.from_numpy(x).to(DEV), torch.from_numpy(y).to(DEV), theta=theta)
+    check_forward(what, m, x.shape[0], pred, loss, fw, loss64)
+    check_grads(what, grads_of(m), g64, g32)
+    return m
+
+
+@pytest.mark.parametrize("bs", [3, 1])
+def test_full_width_fd004_step_matches_oracle(bs):
+    """FD004's own widths (hidden_dim 10: LSTMs 30 / 60 / 30 wide) at an odd batch, and ``bs = 1`` (a one-step recurrence)."""
+    cfg, sd, x, y = seeded_case(tuple(FD004.items()), bs, 100 + bs)
+    oracle_step_check(f"fd004-full-bs{bs}", cfg, sd, x, y, 0.001)
+
+
+def test_more_samples_than_backward_workgroups():
+    """bs = 260 > 256 partial rows: some workgroups of the backward accumulate two samples."""
+    cfg, sd, x, y = seeded_case(tuple(make_cfg(2, 2, 3, 1).items()), 260, 9)
+    oracle_step_check("small-bs260", cfg, sd, x, y, 0.01)
+
+
+# ---- 3. dropout ------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", [CASES[0], CASES[1]])
+def test_training_with_dropout_matches_oracle(name):
+    z, cfg, sd = load_case(name)
+    bs, theta = z["x"].shape[0], float(z["theta"])
+    m = build_model(cfg, sd, dropout=0.2).train()
+    keep = O.keep_masks(bs, cfg, m._seed, m._step + 1, 0.2)
+    assert all(0.6 < k.mean() < 0.95 for k in keep)
+    loss64, g64, fw = O.loss_and_grads(sd, z["x"], z["y"], cfg, theta, keep_mask=keep)
+    _, _, g32 = O.torch_grads(sd, z["x"], z["y"], cfg, theta, torch.float32, keep_scale=tuple((k / 0.8).astype(np.float32) for k in keep))
+    x, y = torch.from_numpy(z["x"]).to(DEV), torch.from_numpy(z["y"]).to(DEV)
+    pred, loss = m.fused_mse_step(x, y, theta=theta)
+    assert rel(fw["pred"], z["pred"]) > 10 * TOL                          # the masks matter
+    check_forward(name + "-dropout", m, bs, pred, loss, fw, loss64)
+    check_grads(name + "-dropout", grads_of(m), g64, g32)
+    m.eval()                                                             # eval applies none
+    with torch.no_grad():
+        assert rel(m(x).cpu().numpy(), z["pred_eval"]) < TOL
+
+
+# ---- 4. path equalities ------------------------------------------------------------------------------------------------------------
+def _case(name=CASES[0]):
+    z, cfg, sd = load_case(name)
+    return cfg, sd, torch.from_numpy(z["x"]).to(DEV), torch.from_numpy(z["y"]).to(DEV), float(z["theta"])
+
+
+@pytest.mark.parametrize("name", [CASES[0], CASES[3]])
+def test_same_step_twice_and_forward_then_backward_equal_fwdbwd_bit_for_bit(name):
+    cfg, sd, x, y, theta = _case(name)
+    m = build_model(cfg, sd, dropout=0.2).train()
+    m.fused_mse_step(x, y, theta=theta)
+    fused = m.bucket[:m.num_live + 1].clone()
+    assert torch.isfinite(fused).all() and fused.abs().max() > 0
+    m._step = 0
+    m.fused_mse_step(x, y, theta=theta)
+    assert torch.equal(m.bucket[:m.num_live + 1], fused)                      # twice the same step: the same bits
+    m2 = build_model(cfg, sd, dropout=0.2).train()
+    m2._seed = m._seed
+    x2, yv = m2._step_inputs(x, y)
+    shp = m2._shape(x2.size(0))
+    a = m2._args(shp, x2, True, 1, theta, 1.0, y=yv)
+    m2._call("forward", shp, a)
+    m2._call("backward", shp, a)
+    assert torch.equal(m2.bucket[:m2.num_live + 1], fused)
+
+
+def test_autograd_path_equals_fused_path_and_update_reference_style_equals_update():
+    from gnn_rul_benchmarking_amd.algorithms import get_algorithm_class
+    cfg, sd, x, y, theta = _case()
+    m = build_model(cfg, sd).train()
+    loss = float(m.fused_mse_step(x, y, theta=theta)[1])      # (the returned loss is a view of the bucket: read it before the next step)
+    fused = m._grad_flat[:m.num_live].clone()
+    m2 = build_model(cfg, sd).train()
+    pred, gl = m2(x, GL=True)
+    assert pred.requires_grad and gl.requires_grad and pred.shape == (x.size(0), 1) and gl.dim() == 0
+    total = torch.nn.functional.mse_loss(pred, y) + theta * gl
+    total.backward()
+    auto = torch.cat([t.grad.reshape(-1) for t in m2._named()])
+    assert torch.equal(auto, fused)
+    assert abs(float(total.detach()) - loss) <= 1e-6 * abs(loss)
+    m3 = build_model(cfg, sd).train()                                          # GL=False: the MSE term's gradient alone
+    torch.nn.functional.mse_loss(m3(x), y).backward()
+    m.fused_mse_step(x, y, theta=0.0)
+    assert torch.equal(torch.cat([t.grad.reshape(-1) for t in m3._named()]), m._grad_flat[:m.num_live])
+    algos = []
+    for _ in range(2):
+        algo = get_algorithm_class("LOGO")({k: cfg[k] for k in KEYS}, {"learning_rate": 1e-3, "weight_decay": 1e-4, "theta": theta}, DEV)
+        algo.model.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd.items()})
+        algo.model.dropout_p = 0.0
+        algos.append(algo.to(DEV).train())
+    la = algos[0].update(x, y, 1)["loss"]
+    lb = algos[1].update_reference_style(x, y, 1)["loss"]
+    assert abs(la - lb) <= 1e-6 * abs(la) and abs(la - loss) <= 1e-6 * abs(la)
+    sa, sb = algos[0].state_dict(), algos[1].state_dict()
+    for k in sa:
+        assert rel(sb[k].cpu().numpy(), sa[k].cpu().numpy()) < 1e-6, k       # one Adam step from the same gradient bits
+    assert not torch.equal(sa["model.cls.weight"].cpu(), torch.from_numpy(np.asarray(sd["cls.weight"])))
+
+
+# ---- 5. the batch is the time axis -----------------------------------------------------------------------------------------------------
+def test_batch_coupling_whole_batch_and_its_halves_each_match_the_oracle_and_differ():
+    cfg, sd, x, _ = seeded_case(tuple(FD004.items()), 6, 77)
+    m = build_model(cfg, sd).eval()
+    xt = torch.from_numpy(x).to(DEV)
+    with torch.no_grad():
+        whole, a, b = m(xt).cpu().numpy(), m(xt[:3]).cpu().numpy(), m(xt[3:]).cpu().numpy()
+    assert rel(whole, O.forward(sd, x, cfg)["pred"]) < TOL
+    assert rel(a, O.forward(sd, x[:3], cfg)["pred"]) < TOL and rel(b, O.forward(sd, x[3:], cfg)["pred"]) < TOL
+    d = rel(np.concatenate([a, b]), whole)
+    print(f"LOGO-GATE batch coupling: halves against the whole batch {d:.2e}")
+    assert d > 10 * TOL
+
+
+def test_constant_sensor_makes_every_prediction_of_the_batch_nan_and_the_call_returns():
+    cfg, sd, x, y, theta = _case(CASES[1])
+    x = x.clone()
+    x[2, 5, :] = 0.5
+    assert np.isnan(O.forward(sd, x.cpu().numpy(), cfg)["pred"]).all()
+    m = build_model(cfg, sd).eval()
+    with torch.no_grad():
+        pred = m(x)
+    assert pred.shape == (x.size(0), 1) and torch.isnan(pred).all()
+    m.train()
+    pred, loss = m.fused_mse_step(x, y, theta=theta)                          # rulgnn OK: a NaN is a value, not an error
+    assert torch.isnan(pred).all() and torch.isnan(loss)
+
+
+# ---- 6. training curve -----------------------------------------------------------------------------------------------------------------
+def test_training_curve_matches_reference_algorithm():
+    """Twelve update() steps against the reference's own.  Tolerances: the project's curve tolerances for a BatchNorm-free family
+    (GRU_CM, tests/test_grucm_gpu.py:253-261: the first three losses 1e-4, every loss 2e-3, end state and eval prediction 5e-3)."""
+    from gnn_rul_benchmarking_amd.algorithms import get_algorithm_class
+    z, cfg, sd0 = load_case(CURVE, "sd0:")
+    algo = get_algorithm_class("LOGO")({k: cfg[k] for k in KEYS}, {"learning_rate": float(z["lr"]), "weight_decay": float(z["wd"]),
+                                                                      "theta": float(z["theta"])}, DEV)
+    algo.model.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd0.items()})
+    algo.model.dropout_p = 0.0
+    algo.to(DEV).train()
+    xs, ys = torch.from_numpy(z["xs"]).to(DEV), torch.from_numpy(z["ys"]).to(DEV)
+    assert xs.size(0) == 12
+    losses = np.asarray([algo.update(xs[s], ys[s], 1)["loss"] for s in range(12)])
+    ref = z["losses"]
+    print("LOGO-GATE curve: worst loss ratio", np.abs(losses / ref - 1).max())
+    assert np.max(np.abs(losses[:3] - ref[:3]) / ref[:3]) < 1e-4
+    assert np.max(np.abs(losses - ref) / ref) < 2e-3
+    sd = algo.model.state_dict()
+    assert list(sd) == O.state_keys()
+    for k in sd:
+        assert rel(sd[k].cpu().numpy(), z["sd_end:" + k]) < 5e-3, k
+    algo.eval()
+    with torch.no_grad():
+        assert rel(algo.model(xs[0]).cpu().numpy(), z["eval_pred_end"]) < 5e-3
+
+
+# ---- 7. the optimizer inside the fused step -----------------------------------------------------------------------------------------
+def test_fused_step_applies_adam_to_every_element_exactly_once():
+    """The twin-model procedure of tests/test_fused_adam_families_gpu.py (steps 7-9, bounds from tests/adam_reference.py), dropout on."""
+    from gnn_rul_benchmarking_amd.optim import FusedAdam
+    from test_fused_adam_families_gpu import LR, SEED, STEP0, WD, _bits, _np
+    cfg, sd, x, y, theta = _case(CASES[0])
+
+    def ready():
+        m = build_model(cfg, sd, dropout=0.2).train()
+        m._seed = SEED
+        return m
+    a = ready()
+    p0 = _np(a.flat_params)
+    _, loss_a = a.fused_mse_step(x, y, theta=theta)
+    g_a, loss_a = _np(a.bucket[:a.num_live]), float(loss_a)
+    assert np.isfinite(g_a).all() and np.array_equal(_bits(_np(a.flat_params)), _bits(p0))
+    b = ready()
+    opt = FusedAdam(b, lr=LR, weight_decay=WD)
+    m0, v0 = R.moments_like(g_a, np.random.default_rng(12))
+    s = opt.state_dict()
+    s.update(step=STEP0, exp_avg=torch.from_numpy(m0).to(DEV), exp_avg_sq=torch.from_numpy(v0).to(DEV))
+    opt.load_state_dict(s)
+    worst = dict(p=0.0, m=0.0, v=0.0)
+    for k in (STEP0 + 1, STEP0 + 2, STEP0 + 3):
+        before = tuple(_np(t) for t in (b.flat_params, opt._exp_avg, opt._exp_avg_sq))
+        _, loss_b = b.fused_mse_step(x, y, opt, theta=theta)
+        g = _np(b.bucket[:b.num_live])
+        after = tuple(_np(t) for t in (b.flat_params, opt._exp_avg, opt._exp_avg_sq))
+        if k == STEP0 + 1:
+            assert np.array_equal(_bits(g), _bits(g_a)) and float(loss_b) == loss_a
+        r = R.check(after, before[0], g, before[1], before[2], k, WD, 1.0, what=f"LOGO, step {k}")
+        worst = {q: max(worst[q], r[q]) for q in worst}
+    assert opt._steps == STEP0 + 3
+    print("ADAM-RATIO family LOGO: " + " ".join(f"{q}={worst[q]:.3f}" for q in "pmv"))
+
+
+# ---- 8. coverage ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("cfg", [make_cfg(1, 1, 33, 1), make_cfg(17, 1, 2, 1), make_cfg(1, 1, 2, 22), make_cfg(16, 14, 32, 1),
+                                 make_cfg(10, 5, 14, 32)], ids=["N33", "p17", "6h132", "lds", "FD003"])
+def test_just_outside_each_limit_is_not_covered_and_launches_nothing(cfg):
+    from gnn_rul_benchmarking_amd.logo import LOGO_model
+    m = LOGO_model(**cfg).to(DEV)
+    x = torch.rand(2, cfg["num_nodes"], cfg["num_patch"] * cfg["patch_size"], device=DEV)
+    with pytest.raises(RuntimeError, match="do not cover this configuration"):
+        m(x)
+    with pytest.raises(RuntimeError, match="do not cover this configuration"):
+        m.fused_mse_step(x, torch.zeros(2, device=DEV), theta=0.01)
+    assert not m._bufs and not m.bucket.any()                  # no workspace was made, nothing was written
+
+
+@pytest.mark.parametrize("cfg", [make_cfg(16, 2, 32, 1), make_cfg(3, 2, 5, 21), make_cfg(16, 13, 32, 1)], ids=["N32-p16", "6h126", "N32-p16-T13-lds"])
+def test_just_inside_the_limits_matches_oracle(cfg):
+    """N = 32 and p = 16 together; the widest LSTM stack (6 h = 126 of 128); and the longest window beside N = 32, p = 16 (the LDS
+    backstop's last covered patch count)."""
+    bs = 2
+    cfg_, sd, x, y = seeded_case(tuple(cfg.items()), bs, 7)
+    oracle_step_check("limits-" + "-".join(str(cfg[k]) for k in KEYS), cfg_, sd, x, y, 0.01)
+
+
+# ---- 9. trainer ------------------------------------------------------------------------------------------------------------------------
+def test_trainer_matches_reference_harness_run_on_cmapss(tmp_path, monkeypatch):
+    """--GNN_method LOGO on C-MAPSS FD001 as the reference wires it (configs/hparams.py:18,37; shuffling DataLoader): the reference's
+    own harness, run on the CPU by tests/golden/make_golden_logo.py::case_trainer_cmapss with the two dropouts switched off on the
+    constructed model, vs this package's harness on the GPU with the same switch.  Bars: those of the other families' harness tests
+    (tests/test_trainer_gpu.py:279-285)."""
+    import sys
+    sys.path.insert(0, GOLD)
+    from synth import synthetic_cmapss
+    from gnn_rul_benchmarking_amd import trainer as T
+    z = np.load(os.path.join(GOLD, "logo_trainer_fd001_reference_run.npz"))
+    (xtr, ytr), (xte, yte) = synthetic_cmapss(int(z["seed"]), int(z["n_train"]), int(z["n_test"]))
+    assert abs(xtr.astype(np.float64).sum() - float(z["x_train_checksum"])) < 1e-6
+    d = tmp_path / "data" / "CMAPSS" / "FD001"
+    os.makedirs(d)
+    torch.save({"samples": xtr, "labels": ytr, "max_ruls": 125}, d / "train.pt")
+    torch.save({"samples": xte, "labels": yte, "max_ruls": 125}, d / "test.pt")
+    monkeypatch.chdir(tmp_path)
+    base = T.get_algorithm_class("LOGO")
+
+    class NoDropout(base):
+        def __init__(self, *a, **k):
+            super().__init__(*a, **k)
+            self.model.dropout_p = 0.0
+    monkeypatch.setattr(T, "get_algorithm_class", lambda n: NoDropout)
+    args = argparse.Namespace(save_dir=str(tmp_path / "logs"), experiment_description="exp", run_description="r",
+                              GNN_method="LOGO", data_path=str(tmp_path / "data"), dataset="CMAPSS",
+                              dataset_id="FD001", bearing_id=None, num_runs=1, device=DEV)
+    tr = T.GNN_RUL_trainer(args)
+    tr.train_configs["num_epochs"] = int(z["epochs"])
+    assert tr.train_configs["batch_size"] == int(z["batch_size"]) and tr.train_configs["learning_rate"] == float(z["lr"])
+    assert tr.train_configs["theta"] == float(z["theta"]) and tr.model_configs == FD001
+    per_epoch = []
+    orig = tr.calc_results_per_run
+
+    def spy(run_id):
+        per_epoch.append(T._calc_metrics(tr.pred_labels, tr.true_labels, tr.max_ruls))
+        return orig(run_id)
+    tr.calc_results_per_run = spy
+    tr.train()
+    got, ref = np.asarray(per_epoch, np.float64), z["per_epoch"]
+    print("LOGO harness per-epoch got/ref:\n", got, "\n", ref)
+    assert got.shape == ref.shape == (3, 4)
+    assert np.max(np.abs(got[:, 2:] - ref[:, 2:]) / np.abs(ref[:, 2:])) < 1e-3      # MAE, RMSE (in RUL cycles), relative
+    assert np.max(np.abs(got[:, 3] - ref[:, 3]) / 125.0) < 1e-3                      # RMSE on the normalised scale, absolute
+    sd = tr.algorithm.state_dict()
+    for k in z.files:
+        if k.startswith("final:"):
+            a, b = sd[k[6:]].cpu().numpy().astype(np.float64), z[k].astype(np.float64)
+            assert np.max(np.abs(a - b)) / max(np.max(np.abs(b)), 1e-30) < 3e-3, k
