@@ -218,18 +218,41 @@ class BilstmArgs(C.Structure):
 ALLREDUCE_F64_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p)
 GRAD_READY_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p)
 
+def _step_family(name, Shape, Args, tap_offset=False, bn_state_count=False, bn_count=False, syncbn=False, bn_running_update=None):
+    """The entries every step family has (rulgnn_<name>_{param_count, workspace_bytes, forward_f32, backward_f32, fwdbwd_f32}) and the
+    optional ones; ``bn_running_update`` is "count" where the entry takes the element count, "shape" where the shape holds it."""
+    S, A = C.POINTER(Shape), C.POINTER(Args)
+    sig = {f"rulgnn_{name}_param_count": (C.c_int64, [S]), f"rulgnn_{name}_workspace_bytes": (C.c_size_t, [S]),
+           f"rulgnn_{name}_forward_f32": (C.c_int, [S, A, C.c_void_p]), f"rulgnn_{name}_backward_f32": (C.c_int, [S, A, C.c_void_p]),
+           f"rulgnn_{name}_fwdbwd_f32": (C.c_int, [S, A, C.POINTER(AdamArgs), C.c_void_p])}
+    if tap_offset:
+        sig[f"rulgnn_{name}_tap_offset"] = (C.c_int64, [S, C.c_int32])
+    if bn_state_count:
+        sig[f"rulgnn_{name}_bn_state_count"] = (C.c_int64, [S])
+    if bn_count:
+        sig[f"rulgnn_{name}_bn_count"] = (C.c_int64, [S])
+    if syncbn:
+        sig[f"rulgnn_{name}_fwdbwd_syncbn_f32"] = (C.c_int, [S, A, C.c_float, ALLREDUCE_F64_FN, C.c_void_p, C.c_void_p])
+    if bn_running_update:
+        count = [C.c_int64] if bn_running_update == "count" else []
+        sig[f"rulgnn_{name}_bn_running_update_f32"] = (C.c_int, [S, C.c_void_p, C.c_void_p] + count + [C.c_float, C.c_int32, C.c_void_p])
+    return sig
+
+
+# one line per step family (csrc/families_host.hpp: StepFamily); everything with another shape of call is spelled out below
 _SIGNATURES = {
-    "rulgnn_stnet_param_count": (C.c_int64, [C.POINTER(StnetShape)]),
-    "rulgnn_stnet_workspace_bytes": (C.c_size_t, [C.POINTER(StnetShape)]),
-    "rulgnn_stnet_forward_f32": (C.c_int, [C.POINTER(StnetShape), C.POINTER(StnetArgs), C.c_void_p]),
-    "rulgnn_stnet_backward_f32": (C.c_int, [C.POINTER(StnetShape), C.POINTER(StnetArgs), C.c_void_p]),
-    "rulgnn_stnet_fwdbwd_f32": (C.c_int, [C.POINTER(StnetShape), C.POINTER(StnetArgs), C.POINTER(AdamArgs), C.c_void_p]),
-    "rulgnn_sagcn_param_count": (C.c_int64, [C.POINTER(SagcnShape)]),
-    "rulgnn_sagcn_workspace_bytes": (C.c_size_t, [C.POINTER(SagcnShape)]),
-    "rulgnn_sagcn_tap_offset": (C.c_int64, [C.POINTER(SagcnShape), C.c_int32]),
-    "rulgnn_sagcn_forward_f32": (C.c_int, [C.POINTER(SagcnShape), C.POINTER(SagcnArgs), C.c_void_p]),
-    "rulgnn_sagcn_backward_f32": (C.c_int, [C.POINTER(SagcnShape), C.POINTER(SagcnArgs), C.c_void_p]),
-    "rulgnn_sagcn_fwdbwd_f32": (C.c_int, [C.POINTER(SagcnShape), C.POINTER(SagcnArgs), C.POINTER(AdamArgs), C.c_void_p]),
+    **_step_family("stmsgcn", StmsgcnShape, StmsgcnArgs),
+    **_step_family("astgcnn", AstgcnnShape, AstgcnnArgs, syncbn=True, bn_running_update="count"),
+    **_step_family("fcstgnn", FcstgnnShape, FcstgnnArgs, bn_count=True, syncbn=True, bn_running_update="shape"),
+    **_step_family("stconv", StconvShape, AstgcnnArgs, bn_running_update="count"),
+    **_step_family("stnet", StnetShape, StnetArgs),
+    **_step_family("sagcn", SagcnShape, SagcnArgs, tap_offset=True),
+    **_step_family("agcntf", AgcntfShape, AgcntfArgs, tap_offset=True),
+    **_step_family("stagnn", StagnnShape, StagnnArgs, tap_offset=True, bn_state_count=True),
+    **_step_family("rgcnu", RgcnuShape, RgcnuArgs),
+    **_step_family("grucm", GrucmShape, GrucmArgs),
+    **_step_family("hiercorrpool", HiercorrpoolShape, HiercorrpoolArgs, tap_offset=True, bn_state_count=True),
+    **_step_family("logo", LogoShape, LogoArgs, tap_offset=True),
     "rulgnn_sgemm_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                    C.c_int32, C.c_int32, C.c_void_p]),
     "rulgnn_sgemm_mode": (C.c_int, [C.c_int32]),
@@ -243,18 +266,6 @@ _SIGNATURES = {
     "rulgnn_sgemm_splitk_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
     "rulgnn_sgemm_splitk_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                           C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
-    "rulgnn_stagnn_param_count": (C.c_int64, [C.POINTER(StagnnShape)]),
-    "rulgnn_stagnn_bn_state_count": (C.c_int64, [C.POINTER(StagnnShape)]),
-    "rulgnn_stagnn_workspace_bytes": (C.c_size_t, [C.POINTER(StagnnShape)]),
-    "rulgnn_stagnn_tap_offset": (C.c_int64, [C.POINTER(StagnnShape), C.c_int32]),
-    "rulgnn_stagnn_forward_f32": (C.c_int, [C.POINTER(StagnnShape), C.POINTER(StagnnArgs), C.c_void_p]),
-    "rulgnn_stagnn_backward_f32": (C.c_int, [C.POINTER(StagnnShape), C.POINTER(StagnnArgs), C.c_void_p]),
-    "rulgnn_stagnn_fwdbwd_f32": (C.c_int, [C.POINTER(StagnnShape), C.POINTER(StagnnArgs), C.POINTER(AdamArgs), C.c_void_p]),
-    "rulgnn_rgcnu_param_count": (C.c_int64, [C.POINTER(RgcnuShape)]),
-    "rulgnn_rgcnu_workspace_bytes": (C.c_size_t, [C.POINTER(RgcnuShape)]),
-    "rulgnn_rgcnu_forward_f32": (C.c_int, [C.POINTER(RgcnuShape), C.POINTER(RgcnuArgs), C.c_void_p]),
-    "rulgnn_rgcnu_backward_f32": (C.c_int, [C.POINTER(RgcnuShape), C.POINTER(RgcnuArgs), C.c_void_p]),
-    "rulgnn_rgcnu_fwdbwd_f32": (C.c_int, [C.POINTER(RgcnuShape), C.POINTER(RgcnuArgs), C.POINTER(AdamArgs), C.c_void_p]),
     "rulgnn_peer_mailbox_bytes": (C.c_size_t, []),
     "rulgnn_peer_handle_bytes": (C.c_size_t, []),
     "rulgnn_peer_mailbox_alloc": (C.c_int, [C.POINTER(C.c_void_p), C.c_void_p]),
@@ -330,45 +341,11 @@ _SIGNATURES = {
     "rulgnn_gru_persistent_workspace_bytes": (C.c_size_t, [C.POINTER(GruShape)]),
     "rulgnn_gru_persistent_forward_f32": (C.c_int, [C.POINTER(GruShape), C.POINTER(GruArgs), C.c_void_p]),
     "rulgnn_gru_persistent_backward_f32": (C.c_int, [C.POINTER(GruShape), C.POINTER(GruArgs), C.c_void_p]),
-    "rulgnn_agcntf_param_count": (C.c_int64, [C.POINTER(AgcntfShape)]),
-    "rulgnn_agcntf_workspace_bytes": (C.c_size_t, [C.POINTER(AgcntfShape)]),
-    "rulgnn_agcntf_tap_offset": (C.c_int64, [C.POINTER(AgcntfShape), C.c_int32]),
-    "rulgnn_agcntf_forward_f32": (C.c_int, [C.POINTER(AgcntfShape), C.POINTER(AgcntfArgs), C.c_void_p]),
-    "rulgnn_agcntf_backward_f32": (C.c_int, [C.POINTER(AgcntfShape), C.POINTER(AgcntfArgs), C.c_void_p]),
-    "rulgnn_agcntf_fwdbwd_f32": (C.c_int, [C.POINTER(AgcntfShape), C.POINTER(AgcntfArgs), C.POINTER(AdamArgs), C.c_void_p]),
-    "rulgnn_hiercorrpool_param_count": (C.c_int64, [C.POINTER(HiercorrpoolShape)]),
-    "rulgnn_hiercorrpool_bn_state_count": (C.c_int64, [C.POINTER(HiercorrpoolShape)]),
-    "rulgnn_hiercorrpool_workspace_bytes": (C.c_size_t, [C.POINTER(HiercorrpoolShape)]),
-    "rulgnn_hiercorrpool_tap_offset": (C.c_int64, [C.POINTER(HiercorrpoolShape), C.c_int32]),
-    "rulgnn_hiercorrpool_forward_f32": (C.c_int, [C.POINTER(HiercorrpoolShape), C.POINTER(HiercorrpoolArgs), C.c_void_p]),
-    "rulgnn_hiercorrpool_backward_f32": (C.c_int, [C.POINTER(HiercorrpoolShape), C.POINTER(HiercorrpoolArgs), C.c_void_p]),
-    "rulgnn_hiercorrpool_fwdbwd_f32": (C.c_int, [C.POINTER(HiercorrpoolShape), C.POINTER(HiercorrpoolArgs), C.POINTER(AdamArgs), C.c_void_p]),
-    "rulgnn_logo_param_count": (C.c_int64, [C.POINTER(LogoShape)]),
-    "rulgnn_logo_workspace_bytes": (C.c_size_t, [C.POINTER(LogoShape)]),
-    "rulgnn_logo_tap_offset": (C.c_int64, [C.POINTER(LogoShape), C.c_int32]),
-    "rulgnn_logo_forward_f32": (C.c_int, [C.POINTER(LogoShape), C.POINTER(LogoArgs), C.c_void_p]),
-    "rulgnn_logo_backward_f32": (C.c_int, [C.POINTER(LogoShape), C.POINTER(LogoArgs), C.c_void_p]),
-    "rulgnn_logo_fwdbwd_f32": (C.c_int, [C.POINTER(LogoShape), C.POINTER(LogoArgs), C.POINTER(AdamArgs), C.c_void_p]),
-    "rulgnn_grucm_param_count": (C.c_int64, [C.POINTER(GrucmShape)]),
-    "rulgnn_grucm_workspace_bytes": (C.c_size_t, [C.POINTER(GrucmShape)]),
-    "rulgnn_grucm_forward_f32": (C.c_int, [C.POINTER(GrucmShape), C.POINTER(GrucmArgs), C.c_void_p]),
-    "rulgnn_grucm_backward_f32": (C.c_int, [C.POINTER(GrucmShape), C.POINTER(GrucmArgs), C.c_void_p]),
-    "rulgnn_grucm_fwdbwd_f32": (C.c_int, [C.POINTER(GrucmShape), C.POINTER(GrucmArgs), C.POINTER(AdamArgs), C.c_void_p]),
     "rulgnn_rul_metrics_workspace_bytes": (C.c_size_t, [C.c_int64]),
     "rulgnn_rul_metrics_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rulgnn_rul_metric_sums_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "rulgnn_adam_step_dev_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_float,
                                             C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]),
-    "rulgnn_fcstgnn_param_count": (C.c_int64, [C.POINTER(FcstgnnShape)]),
-    "rulgnn_fcstgnn_bn_count": (C.c_int64, [C.POINTER(FcstgnnShape)]),
-    "rulgnn_fcstgnn_workspace_bytes": (C.c_size_t, [C.POINTER(FcstgnnShape)]),
-    "rulgnn_fcstgnn_forward_f32": (C.c_int, [C.POINTER(FcstgnnShape), C.POINTER(FcstgnnArgs), C.c_void_p]),
-    "rulgnn_fcstgnn_backward_f32": (C.c_int, [C.POINTER(FcstgnnShape), C.POINTER(FcstgnnArgs), C.c_void_p]),
-    "rulgnn_fcstgnn_fwdbwd_f32": (C.c_int, [C.POINTER(FcstgnnShape), C.POINTER(FcstgnnArgs), C.POINTER(AdamArgs), C.c_void_p]),
-    "rulgnn_fcstgnn_fwdbwd_syncbn_f32": (C.c_int, [C.POINTER(FcstgnnShape), C.POINTER(FcstgnnArgs), C.c_float, ALLREDUCE_F64_FN,
-                                                    C.c_void_p, C.c_void_p]),
-    "rulgnn_fcstgnn_bn_running_update_f32": (C.c_int, [C.POINTER(FcstgnnShape), C.c_void_p, C.c_void_p, C.c_float, C.c_int32,
-                                                        C.c_void_p]),
     "rulgnn_hagcn_graph_param_count": (C.c_int64, [C.POINTER(HagcnShape)]),
     "rulgnn_hagcn_workspace_bytes": (C.c_size_t, [C.POINTER(HagcnShape)]),
     "rulgnn_hagcn_graph_forward_f32": (C.c_int, [C.POINTER(HagcnShape), C.POINTER(HagcnArgs), C.c_void_p]),
@@ -376,29 +353,7 @@ _SIGNATURES = {
     "rulgnn_bilstm_workspace_bytes": (C.c_size_t, [C.POINTER(BilstmShape)]),
     "rulgnn_bilstm_forward_f32": (C.c_int, [C.POINTER(BilstmShape), C.POINTER(BilstmArgs), C.c_void_p]),
     "rulgnn_bilstm_backward_f32": (C.c_int, [C.POINTER(BilstmShape), C.POINTER(BilstmArgs), C.c_void_p]),
-    "rulgnn_stconv_param_count": (C.c_int64, [C.POINTER(StconvShape)]),
-    "rulgnn_stconv_workspace_bytes": (C.c_size_t, [C.POINTER(StconvShape)]),
-    "rulgnn_stconv_forward_f32": (C.c_int, [C.POINTER(StconvShape), C.POINTER(AstgcnnArgs), C.c_void_p]),
-    "rulgnn_stconv_backward_f32": (C.c_int, [C.POINTER(StconvShape), C.POINTER(AstgcnnArgs), C.c_void_p]),
-    "rulgnn_stconv_fwdbwd_f32": (C.c_int, [C.POINTER(StconvShape), C.POINTER(AstgcnnArgs), C.POINTER(AdamArgs), C.c_void_p]),
-    "rulgnn_stconv_bn_running_update_f32": (C.c_int, [C.POINTER(StconvShape), C.c_void_p, C.c_void_p, C.c_int64, C.c_float,
-                                                       C.c_int32, C.c_void_p]),
-    "rulgnn_astgcnn_param_count": (C.c_int64, [C.POINTER(AstgcnnShape)]),
-    "rulgnn_astgcnn_workspace_bytes": (C.c_size_t, [C.POINTER(AstgcnnShape)]),
-    "rulgnn_astgcnn_forward_f32": (C.c_int, [C.POINTER(AstgcnnShape), C.POINTER(AstgcnnArgs), C.c_void_p]),
-    "rulgnn_astgcnn_backward_f32": (C.c_int, [C.POINTER(AstgcnnShape), C.POINTER(AstgcnnArgs), C.c_void_p]),
-    "rulgnn_astgcnn_fwdbwd_f32": (C.c_int, [C.POINTER(AstgcnnShape), C.POINTER(AstgcnnArgs), C.POINTER(AdamArgs), C.c_void_p]),
-    "rulgnn_astgcnn_fwdbwd_syncbn_f32": (C.c_int, [C.POINTER(AstgcnnShape), C.POINTER(AstgcnnArgs), C.c_float, ALLREDUCE_F64_FN,
-                                                    C.c_void_p, C.c_void_p]),
-    "rulgnn_astgcnn_bn_running_update_f32": (C.c_int, [C.POINTER(AstgcnnShape), C.c_void_p, C.c_void_p, C.c_int64, C.c_float,
-                                                        C.c_int32, C.c_void_p]),
-    "rulgnn_stmsgcn_param_count": (C.c_int64, [C.POINTER(StmsgcnShape)]),
-    "rulgnn_stmsgcn_workspace_bytes": (C.c_size_t, [C.POINTER(StmsgcnShape)]),
     "rulgnn_stmsgcn_features_f32": (C.c_int, [C.POINTER(StmsgcnShape), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "rulgnn_stmsgcn_forward_f32": (C.c_int, [C.POINTER(StmsgcnShape), C.POINTER(StmsgcnArgs), C.c_void_p]),
-    "rulgnn_stmsgcn_backward_f32": (C.c_int, [C.POINTER(StmsgcnShape), C.POINTER(StmsgcnArgs), C.c_void_p]),
-    "rulgnn_stmsgcn_fwdbwd_f32": (C.c_int, [C.POINTER(StmsgcnShape), C.POINTER(StmsgcnArgs), C.POINTER(AdamArgs),
-                                             C.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -614,17 +614,23 @@ int at_pgrad_jobs(const AtGeom& g, float* ws, float* gr, SplitKJob* jobs) {
 
 }  // namespace
 
-int64_t agcntf_param_count(const rulgnn_agcntf_shape* s) {
+// RULGNN_OK, or the code every entry returns for a refused shape: unsupported for anything at_geometry refuses, a negative batch included.
+int Agcntf::shape_status(const Shape* s) {
+    AtGeom g;
+    return at_geometry(s, &g) == RULGNN_OK ? RULGNN_OK : RULGNN_EUNSUPPORTED;
+}
+
+int64_t Agcntf::param_count(const Shape* s) {
     AtGeom g;
     return at_geometry(s, &g) == RULGNN_OK ? g.pcount : -1;
 }
 
-size_t agcntf_workspace_bytes(const rulgnn_agcntf_shape* s) {
+size_t Agcntf::workspace_bytes(const Shape* s) {
     AtGeom g;
     return at_geometry(s, &g) == RULGNN_OK ? g.total_bytes : 0;
 }
 
-int64_t agcntf_tap_offset(const rulgnn_agcntf_shape* s, int which) {
+int64_t Agcntf::tap_offset(const Shape* s, int which) {
     AtGeom g;
     if (at_geometry(s, &g) != RULGNN_OK) return -1;
     switch (which) {
@@ -635,13 +641,8 @@ int64_t agcntf_tap_offset(const rulgnn_agcntf_shape* s, int which) {
     }
 }
 
-#define AT_LAUNCH_OK()                                           \
-    do {                                                         \
-        if (hipGetLastError() != hipSuccess) return RULGNN_EHIP; \
-    } while (0)
-
 // mode bit 0: forward, bit 1: backward (after a forward with the same args / workspace)
-int agcntf_run(const rulgnn_agcntf_shape* s, const rulgnn_agcntf_args* a, int mode, hipStream_t st) {
+int Agcntf::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
     AtGeom g;
     RULGNN_TRY(at_geometry(s, &g));
     if (a->workspace_bytes < g.total_bytes) return RULGNN_EWORKSPACE;
@@ -660,7 +661,7 @@ int agcntf_run(const rulgnn_agcntf_shape* s, const rulgnn_agcntf_args* a, int mo
         RULGNN_TRY(sagcn_features(g.B, g.P, g.n, a->x, ws + g.w_raw, ws + g.w_feat, st));
         RULGNN_TRY(allow_dynamic_lds(at_graph_kernel<false>, g.lds_graph_fwd));
         hipLaunchKernelGGL(at_graph_kernel<false>, dim3(at_grid(g.B, 8192)), dim3(AT_GB), g.lds_graph_fwd, st, g, prm, gq);
-        AT_LAUNCH_OK();
+        RULGNN_LAUNCH_OK();
         for (int h = 0; h < g.heads; ++h)
             for (int t = 0; t < 3; ++t)
                 RULGNN_TRY(sgemm(ws + g.w_H, Hg, 1, prm + g.o_head + h * g.head_stride + t * (Hg * Hg + Hg), Hg, 1, ws + qkv[t] + h * Hg, HD, BN, Hg,
@@ -669,7 +670,7 @@ int agcntf_run(const rulgnn_agcntf_shape* s, const rulgnn_agcntf_args* a, int mo
         hipLaunchKernelGGL(at_attn_fwd_kernel, dim3(at_grid(g.B * g.heads * g.nqt, 1 << 16)), dim3(AT_GB), g.lds_attn_fwd, st, g, prm, aq);
         hipLaunchKernelGGL(at_head_finish_kernel, dim3(at_grid((g.B + AT_GB - 1) / AT_GB, 4096)), dim3(AT_GB), 0, st, g, (const float*)(ws + g.w_part),
                            prm, a->y, a->pred, ws + g.w_sq, ws + g.w_dpred, 1.0f / (float)gb);
-        AT_LAUNCH_OK();
+        RULGNN_LAUNCH_OK();
         if (a->y && a->loss) RULGNN_TRY(block_sum((const float*)(ws + g.w_sq), g.B, a->loss, st));
     }
     if (mode & 2) {
@@ -683,7 +684,7 @@ int agcntf_run(const rulgnn_agcntf_shape* s, const rulgnn_agcntf_args* a, int mo
         const unsigned grid = at_grid(g.B * g.heads * g.nbt, 1 << 16);
         hipLaunchKernelGGL(at_attn_bwd_kernel<false>, dim3(grid), dim3(AT_GB), g.lds_attn_bwd, st, g, prm, aq);
         hipLaunchKernelGGL(at_attn_bwd_kernel<true>, dim3(grid), dim3(AT_GB), g.lds_attn_bwd, st, g, prm, aq);
-        AT_LAUNCH_OK();
+        RULGNN_LAUNCH_OK();
         // dH [B N, Hg] = sum over heads of dQ Wq + dK Wk + dV Wv
         const int64_t dq[3] = {g.w_dQ, g.w_dK, g.w_dV};
         for (int h = 0; h < g.heads; ++h)
@@ -692,7 +693,7 @@ int agcntf_run(const rulgnn_agcntf_shape* s, const rulgnn_agcntf_args* a, int mo
                                  Hg, h + t > 0, st));
         RULGNN_TRY(allow_dynamic_lds(at_graph_kernel<true>, g.lds_graph_bwd));
         hipLaunchKernelGGL(at_graph_kernel<true>, dim3(at_grid(g.B, 8192)), dim3(AT_GB), g.lds_graph_bwd, st, g, prm, gq);
-        AT_LAUNCH_OK();
+        RULGNN_LAUNCH_OK();
         SplitKJob jobs[12 + 6 * AT_MAXHEADS];
         const int nj = at_pgrad_jobs(g, ws, gr, jobs);
         for (int j0 = 0; j0 < nj; j0 += 10)

@@ -759,12 +759,12 @@ void ast_ws_layout(const AstGeom& g, AstWs* w) {
 
 }  // namespace
 
-int64_t astgcnn_param_count(const rulgnn_astgcnn_shape* s) {
+int64_t Astgcnn::param_count(const Shape* s) {
     AstGeom g;
     return ast_geometry(s, &g) == RULGNN_OK ? g.nparam : -1;
 }
 
-size_t astgcnn_workspace_bytes(const rulgnn_astgcnn_shape* s) {
+size_t Astgcnn::workspace_bytes(const Shape* s) {
     AstGeom g;
     if (ast_geometry(s, &g) != RULGNN_OK) return 0;
     AstWs w;
@@ -902,7 +902,7 @@ static int astgcnn_run_t(const rulgnn_astgcnn_shape* s, const rulgnn_astgcnn_arg
     return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
 }
 
-int astgcnn_run(const rulgnn_astgcnn_shape* s, const rulgnn_astgcnn_args* a, int mode, hipStream_t st, const SyncHook* sync, float* bn_running_out,
+int Astgcnn::run(const Shape* s, const Args* a, int mode, hipStream_t st, const SyncHook* sync, float* bn_running_out,
                 float bn_momentum, AdamFuse* adam) {
     if (adam) adam->gbase = nullptr;          // (set by the path that applies the update: see stgcn_host.hpp)
     if (s && s->time_length == 50 && s->output_dim == 64) {
@@ -912,7 +912,7 @@ int astgcnn_run(const rulgnn_astgcnn_shape* s, const rulgnn_astgcnn_args* a, int
     return astgcnn_run_t<0, 0, 0>(s, a, mode, st, sync, bn_running_out, bn_momentum, adam);
 }
 
-int astgcnn_bn_running_update(const rulgnn_astgcnn_shape* s, float* bn_stats, const float* bn_batch, int64_t count, float momentum,
+int Astgcnn::bn_running_update(const Shape* s, float* bn_stats, const float* bn_batch, int64_t count, float momentum,
                               int from_moments, hipStream_t st) {
     AstGeom g;
     RULGNN_TRY(ast_geometry(s, &g));

@@ -9,34 +9,162 @@
 
 namespace rulgnn {
 
-int64_t stmsgcn_param_count(const rulgnn_stmsgcn_shape* s);
-size_t stmsgcn_workspace_bytes(const rulgnn_stmsgcn_shape* s);
+// ---- step families -------------------------------------------------------------------------------------------------------------------
+// A step family is a model behind rulgnn_<family>_{forward,backward,fwdbwd}_f32: one shape struct, one args struct.  Its description, a
+// struct derived from StepFamily<Shape, Args>, is what rulgnn_api.hip instantiates its entry templates on (step_forward, step_backward,
+// step_fwdbwd); the family's translation unit defines the members declared here:
+//   shape_status(s)      RULGNN_OK, or the code every entry returns for a refused shape: decided there alone, next to the geometry.
+//                        (STMSGCN and the BatchNorm families have none: run() answers with its geometry's code behind the argument check.)
+//   param_count(s), workspace_bytes(s)      the queries: -1 / 0 for a refused shape
+//   run(s, a, mode, stream)                 mode bit 0: forward, bit 1: backward; checks the workspace size before its first launch
+//   check_args(s, a, fwd, bwd)              what the entries refuse before run(): shape_status, then the args' own fields (defined in
+//                                           rulgnn_api.hip on its pointer checks; s and a are not null)
+//   adam_first, adam_frozen_tail(s)         the fused step's Adam updates the flat floats [adam_first, param_count - adam_frozen_tail)
+template <typename S, typename A>
+struct StepFamily {
+    using Shape = S;
+    using Args = A;
+    static constexpr int64_t adam_first = 0;
+    static int64_t adam_frozen_tail(const S*) { return 0; }
+};
+
+struct Stmsgcn : StepFamily<rulgnn_stmsgcn_shape, rulgnn_stmsgcn_args> {
+    static int64_t param_count(const Shape* s);
+    static size_t workspace_bytes(const Shape* s);
+    static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
+    static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
+};
 int stmsgcn_features(const rulgnn_stmsgcn_shape* s, const float* x, const float* prm, float* features, hipStream_t stream);
-int stmsgcn_run(const rulgnn_stmsgcn_shape* s, const rulgnn_stmsgcn_args* a, int mode, hipStream_t stream);
-int64_t astgcnn_param_count(const rulgnn_astgcnn_shape* s);
-size_t astgcnn_workspace_bytes(const rulgnn_astgcnn_shape* s);
+
+// The BatchNorm families (ASTGCNN, FC_STGNN, ST_Conv) share their argument check and fused step (rulgnn_api.hip: check_bn_args,
+// bn_step_fwdbwd).  On top of a step family's members:
+//   run_takes_optimizer      run() has the trailing parameters of a whole training step -- `sync`: synchronised BatchNorm (the
+//                            *_fwdbwd_syncbn_f32 entry); `bn_running_out`, plain batch statistics: the step updates the running statistics
+//                            itself; `adam`: the constants of the optimizer update (adam_fuse_args) -- on return adam->gbase != nullptr says
+//                            the step's last kernel applied it (adam_device.hpp), else the caller launches adam_step
+//   bn_running_update(...)   the running-statistics update as a launch of its own; step_bn_update(...): the same behind a fused step
 struct AdamFuse;          // adam_device.hpp
-// (`bn_running_out` != nullptr, whole training steps with plain batch statistics: the finalize kernel also updates the running statistics;
-// `adam` != nullptr, whole training steps: the constants of the optimizer update (adam_fuse_args) -- on return adam->gbase != nullptr says
-// the step's last kernel applied it, else the caller launches adam_step)
-int astgcnn_run(const rulgnn_astgcnn_shape* s, const rulgnn_astgcnn_args* a, int mode, hipStream_t stream, const SyncHook* sync = nullptr,
-                float* bn_running_out = nullptr, float bn_momentum = 0.f, AdamFuse* adam = nullptr);
 void adam_fuse_args(AdamFuse* t, float* p, float* m, float* v, const float* gbase, int64_t step, float lr, float beta1, float beta2, float eps,
                     float wd);
-int astgcnn_bn_running_update(const rulgnn_astgcnn_shape* s, float* bn_stats, const float* bn_batch, int64_t count, float momentum,
-                              int from_moments, hipStream_t stream);
-int64_t fcstgnn_param_count(const rulgnn_fcstgnn_shape* s);
-int64_t fcstgnn_bn_count(const rulgnn_fcstgnn_shape* s);
-size_t fcstgnn_workspace_bytes(const rulgnn_fcstgnn_shape* s);
-// (`bn_running_out` != nullptr, whole training steps with plain batch statistics: the running-statistics update rides on the side stream
-// behind the batch-statistics kernel instead of closing the step)
-// (`fuse` != nullptr, whole training steps on one rank: the step's last launch -- the finalize kernel, then behind the join with the side
-// stream -- applies torch.optim.Adam to every parameter: adam_device.hpp; no optimizer launch)
-struct AdamFuse;
-int fcstgnn_run(const rulgnn_fcstgnn_shape* s, const rulgnn_fcstgnn_args* a, int mode, hipStream_t stream, const SyncHook* sync = nullptr,
-                float* bn_running_out = nullptr, float bn_momentum = 0.f, const AdamFuse* fuse = nullptr);
-int fcstgnn_bn_running_update(const rulgnn_fcstgnn_shape* s, float* bn_stats, const float* bn_batch, float momentum, int from_moments,
-                              hipStream_t stream);
+struct Astgcnn : StepFamily<rulgnn_astgcnn_shape, rulgnn_astgcnn_args> {
+    static constexpr bool run_takes_optimizer = true;
+    static int64_t param_count(const Shape* s);
+    static size_t workspace_bytes(const Shape* s);
+    static int run(const Shape* s, const Args* a, int mode, hipStream_t st, const SyncHook* sync = nullptr, float* bn_running_out = nullptr,
+                   float bn_momentum = 0.f, AdamFuse* adam = nullptr);
+    static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
+    static int bn_running_update(const Shape* s, float* bn_stats, const float* bn_batch, int64_t count, float momentum, int from_moments,
+                                 hipStream_t st);
+    static int step_bn_update(const Shape* s, float* bn_stats, const float* bn_batch, float momentum, int from_moments, hipStream_t st) {
+        return bn_running_update(s, bn_stats, bn_batch, s->batch * (int64_t)s->time_length, momentum, from_moments, st);
+    }
+};
+// (bn_running_out: the update rides on the side stream behind the batch-statistics kernel; adam: always applied, by the step's last launch)
+struct Fcstgnn : StepFamily<rulgnn_fcstgnn_shape, rulgnn_fcstgnn_args> {
+    static constexpr bool run_takes_optimizer = true;
+    static int64_t param_count(const Shape* s);
+    static int64_t bn_count(const Shape* s);
+    static size_t workspace_bytes(const Shape* s);
+    static int run(const Shape* s, const Args* a, int mode, hipStream_t st, const SyncHook* sync = nullptr, float* bn_running_out = nullptr,
+                   float bn_momentum = 0.f, const AdamFuse* adam = nullptr);
+    static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
+    static int bn_running_update(const Shape* s, float* bn_stats, const float* bn_batch, float momentum, int from_moments, hipStream_t st);
+    static int step_bn_update(const Shape* s, float* bn_stats, const float* bn_batch, float momentum, int from_moments, hipStream_t st) {
+        return bn_running_update(s, bn_stats, bn_batch, momentum, from_moments, st);          // (the element counts are the shape's)
+    }
+};
+// (the args struct is ASTGCNN's)
+struct Stconv : StepFamily<rulgnn_stconv_shape, rulgnn_astgcnn_args> {
+    static constexpr bool run_takes_optimizer = false;
+    static int64_t param_count(const Shape* s);
+    static size_t workspace_bytes(const Shape* s);
+    static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
+    static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
+    static int bn_running_update(const Shape* s, float* bn_stats, const float* bn_batch, int64_t count, float momentum, int from_moments,
+                                 hipStream_t st);
+    static int step_bn_update(const Shape* s, float* bn_stats, const float* bn_batch, float momentum, int from_moments, hipStream_t st) {
+        return bn_running_update(s, bn_stats, bn_batch, s->batch * (int64_t)s->time_length, momentum, from_moments, st);
+    }
+};
+
+// (the args struct is STMSGCN's; workspace_bytes is the step's -- stgnn_workspace_bytes below is that of the terms / cheb entries)
+struct Stgnn : StepFamily<rulgnn_stgnn_shape, rulgnn_stmsgcn_args> {
+    static int shape_status(const Shape* s);
+    static int64_t param_count(const Shape* s);
+    static size_t workspace_bytes(const Shape* s);
+    static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
+    static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
+};
+struct Stnet : StepFamily<rulgnn_stnet_shape, rulgnn_stnet_args> {
+    // cnn.{weight, bias} (the first 3 entries) have no gradient in the reference (`grad is None`): torch's Adam leaves them untouched
+    static constexpr int64_t adam_first = 3;
+    static int shape_status(const Shape* s);
+    static int64_t param_count(const Shape* s);
+    static size_t workspace_bytes(const Shape* s);
+    static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
+    static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
+};
+struct Sagcn : StepFamily<rulgnn_sagcn_shape, rulgnn_sagcn_args> {
+    static int shape_status(const Shape* s);
+    static int64_t param_count(const Shape* s);
+    static size_t workspace_bytes(const Shape* s);
+    static int64_t tap_offset(const Shape* s, int which);
+    static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
+    static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
+};
+// SAGCN's parameter-free front end alone: x [B][P * n] -> raw [B * P][20] (scratch) -> features [B][P][40] (unit Frobenius norm)
+int sagcn_features(int64_t B, int P, int n, const float* x, float* raw, float* feat, hipStream_t st);
+struct Agcntf : StepFamily<rulgnn_agcntf_shape, rulgnn_agcntf_args> {
+    static int shape_status(const Shape* s);
+    static int64_t param_count(const Shape* s);
+    static size_t workspace_bytes(const Shape* s);
+    static int64_t tap_offset(const Shape* s, int which);
+    static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
+    static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
+};
+struct Stagnn : StepFamily<rulgnn_stagnn_shape, rulgnn_stagnn_args> {
+    static int shape_status(const Shape* s);
+    static int64_t param_count(const Shape* s);
+    static int64_t bn_state_count(const Shape* s);
+    static size_t workspace_bytes(const Shape* s);
+    static int64_t tap_offset(const Shape* s, int which);
+    static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
+    static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
+};
+struct Rgcnu : StepFamily<rulgnn_rgcnu_shape, rulgnn_rgcnu_args> {
+    // the second head (fc2, the last E*L + 1 entries) has no gradient in the reference (`grad is None`): torch's Adam leaves it untouched
+    static int64_t adam_frozen_tail(const Shape* s) { return (int64_t)s->encoder_hidden_dim * s->time_length + 1; }
+    static int shape_status(const Shape* s);
+    static int64_t param_count(const Shape* s);
+    static size_t workspace_bytes(const Shape* s);
+    static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
+    static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
+};
+struct Grucm : StepFamily<rulgnn_grucm_shape, rulgnn_grucm_args> {
+    static int shape_status(const Shape* s);
+    static int64_t param_count(const Shape* s);
+    static size_t workspace_bytes(const Shape* s);
+    static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
+    static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
+};
+struct Hiercorrpool : StepFamily<rulgnn_hiercorrpool_shape, rulgnn_hiercorrpool_args> {
+    static int shape_status(const Shape* s);
+    static int64_t param_count(const Shape* s);
+    static int64_t bn_state_count(const Shape* s);
+    static size_t workspace_bytes(const Shape* s);
+    static int64_t tap_offset(const Shape* s, int which);
+    static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
+    static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
+};
+struct Logo : StepFamily<rulgnn_logo_shape, rulgnn_logo_args> {
+    static int shape_status(const Shape* s);
+    static int64_t param_count(const Shape* s);
+    static size_t workspace_bytes(const Shape* s);
+    static int64_t tap_offset(const Shape* s, int which);
+    static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
+    static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
+};
+
 int64_t hagcn_graph_param_count(const rulgnn_hagcn_shape* s);
 size_t hagcn_workspace_bytes(const rulgnn_hagcn_shape* s);
 int hagcn_graph_forward(const rulgnn_hagcn_shape* s, const rulgnn_hagcn_args* a, hipStream_t stream);
@@ -44,11 +172,6 @@ int hagcn_graph_backward(const rulgnn_hagcn_shape* s, const rulgnn_hagcn_args* a
 size_t bilstm_workspace_bytes(const rulgnn_bilstm_shape* s);
 int bilstm_forward(const rulgnn_bilstm_shape* s, const rulgnn_bilstm_args* a, hipStream_t stream, int ndir = 2);
 int bilstm_backward(const rulgnn_bilstm_shape* s, const rulgnn_bilstm_args* a, hipStream_t stream, int ndir = 2);
-int64_t stconv_param_count(const rulgnn_stconv_shape* s);
-size_t stconv_workspace_bytes(const rulgnn_stconv_shape* s);
-int stconv_run(const rulgnn_stconv_shape* s, const rulgnn_astgcnn_args* a, int mode, hipStream_t stream);
-int stconv_bn_running_update(const rulgnn_stconv_shape* s, float* bn_stats, const float* bn_batch, int64_t count, float momentum,
-                             int from_moments, hipStream_t stream);
 int adam_step(float* p, const float* g, float* m, float* v, int64_t n, int64_t step, float lr, float beta1, float beta2,
               float eps, float wd, float gscale, hipStream_t stream, void* step_state = nullptr, const float* guard = nullptr);
 // Synchronised BatchNorm, the one step behind every launch that completes a reduction pair (bn_cells.hpp): the CELL_REP replicas of the
@@ -72,30 +195,6 @@ int stgnn_terms(const rulgnn_stgnn_shape* s, const float* x, float* terms, float
 int stgnn_cheb_forward(const rulgnn_stgnn_shape* s, const float* terms, const float* filters, float* out, hipStream_t st);
 int stgnn_cheb_backward(const rulgnn_stgnn_shape* s, const float* terms, const float* dout, float* dfilters, void* workspace,
                         size_t workspace_bytes, hipStream_t st);
-int64_t stnet_param_count(const rulgnn_stnet_shape* s);
-size_t stnet_workspace_bytes(const rulgnn_stnet_shape* s);
-int stnet_run(const rulgnn_stnet_shape* s, const rulgnn_stnet_args* a, int mode, hipStream_t st);
-int64_t sagcn_param_count(const rulgnn_sagcn_shape* s);
-size_t sagcn_workspace_bytes(const rulgnn_sagcn_shape* s);
-int64_t sagcn_tap_offset(const rulgnn_sagcn_shape* s, int which);
-int sagcn_run(const rulgnn_sagcn_shape* s, const rulgnn_sagcn_args* a, int mode, hipStream_t st);
-// SAGCN's parameter-free front end alone: x [B][P * n] -> raw [B * P][20] (scratch) -> features [B][P][40] (unit Frobenius norm)
-int sagcn_features(int64_t B, int P, int n, const float* x, float* raw, float* feat, hipStream_t st);
-int64_t agcntf_param_count(const rulgnn_agcntf_shape* s);
-size_t agcntf_workspace_bytes(const rulgnn_agcntf_shape* s);
-int64_t agcntf_tap_offset(const rulgnn_agcntf_shape* s, int which);
-int agcntf_run(const rulgnn_agcntf_shape* s, const rulgnn_agcntf_args* a, int mode, hipStream_t st);
-int64_t stagnn_param_count(const rulgnn_stagnn_shape* s);
-int64_t stagnn_bn_state_count(const rulgnn_stagnn_shape* s);
-size_t stagnn_workspace_bytes(const rulgnn_stagnn_shape* s);
-int64_t stagnn_tap_offset(const rulgnn_stagnn_shape* s, int which);
-int stagnn_run(const rulgnn_stagnn_shape* s, const rulgnn_stagnn_args* a, int mode, hipStream_t st);
-int64_t rgcnu_param_count(const rulgnn_rgcnu_shape* s);
-size_t rgcnu_workspace_bytes(const rulgnn_rgcnu_shape* s);
-int rgcnu_run(const rulgnn_rgcnu_shape* s, const rulgnn_rgcnu_args* a, int mode, hipStream_t st);
-int64_t stgnn_param_count(const rulgnn_stgnn_shape* s);
-size_t stgnn_step_workspace_bytes(const rulgnn_stgnn_shape* s);
-int stgnn_run(const rulgnn_stgnn_shape* s, const rulgnn_stmsgcn_args* a, int mode, hipStream_t st);
 size_t gru_workspace_bytes(const rulgnn_gru_shape* s);
 int gru_forward(const rulgnn_gru_shape* s, const rulgnn_gru_args* a, hipStream_t st);
 int gru_backward(const rulgnn_gru_shape* s, const rulgnn_gru_args* a, hipStream_t st);
@@ -103,18 +202,6 @@ int gru_backward(const rulgnn_gru_shape* s, const rulgnn_gru_args* a, hipStream_
 size_t gru_persistent_workspace_bytes(const rulgnn_gru_shape* s);
 int gru_persistent_forward(const rulgnn_gru_shape* s, const rulgnn_gru_args* a, hipStream_t st);
 int gru_persistent_backward(const rulgnn_gru_shape* s, const rulgnn_gru_args* a, hipStream_t st);
-int64_t grucm_param_count(const rulgnn_grucm_shape* s);
-size_t grucm_workspace_bytes(const rulgnn_grucm_shape* s);
-int grucm_run(const rulgnn_grucm_shape* s, const rulgnn_grucm_args* a, int mode, hipStream_t st);
-int64_t hiercorrpool_param_count(const rulgnn_hiercorrpool_shape* s);
-int64_t hiercorrpool_bn_state_count(const rulgnn_hiercorrpool_shape* s);
-size_t hiercorrpool_workspace_bytes(const rulgnn_hiercorrpool_shape* s);
-int64_t hiercorrpool_tap_offset(const rulgnn_hiercorrpool_shape* s, int which);
-int hiercorrpool_run(const rulgnn_hiercorrpool_shape* s, const rulgnn_hiercorrpool_args* a, int mode, hipStream_t st);
-int64_t logo_param_count(const rulgnn_logo_shape* s);
-size_t logo_workspace_bytes(const rulgnn_logo_shape* s);
-int64_t logo_tap_offset(const rulgnn_logo_shape* s, int which);
-int logo_run(const rulgnn_logo_shape* s, const rulgnn_logo_args* a, int mode, hipStream_t st);
 size_t rul_metrics_workspace_bytes(int64_t n);
 int rul_metrics(const float* pred, const float* real, int64_t n, float max_rul, double* out, void* workspace, size_t workspace_bytes,
                 hipStream_t st, int raw = 0);

@@ -1945,17 +1945,17 @@ inline unsigned grid_for(int64_t total) {
 
 }  // namespace
 
-int64_t fcstgnn_param_count(const rulgnn_fcstgnn_shape* s) {
+int64_t Fcstgnn::param_count(const Shape* s) {
     FcGeom g;
     return fc_geometry(s, &g) == RULGNN_OK ? g.nparam : -1;
 }
 
-int64_t fcstgnn_bn_count(const rulgnn_fcstgnn_shape* s) {
+int64_t Fcstgnn::bn_count(const Shape* s) {
     FcGeom g;
     return fc_geometry(s, &g) == RULGNN_OK ? g.bn_total : -1;
 }
 
-size_t fcstgnn_workspace_bytes(const rulgnn_fcstgnn_shape* s) {
+size_t Fcstgnn::workspace_bytes(const Shape* s) {
     FcGeom g;
     if (fc_geometry(s, &g) != RULGNN_OK) return 0;
     FcWs w;
@@ -1964,7 +1964,7 @@ size_t fcstgnn_workspace_bytes(const rulgnn_fcstgnn_shape* s) {
 }
 
 // mode bit 0: forward (args->training selects batch / running statistics), bit 1: backward
-int fcstgnn_run(const rulgnn_fcstgnn_shape* s, const rulgnn_fcstgnn_args* a, int mode, hipStream_t st, const SyncHook* sync, float* bn_running_out,
+int Fcstgnn::run(const Shape* s, const Args* a, int mode, hipStream_t st, const SyncHook* sync, float* bn_running_out,
                 float bn_momentum, const AdamFuse* fuse) {
     FcGeom g;
     RULGNN_TRY(fc_geometry(s, &g));
@@ -2301,7 +2301,7 @@ int fcstgnn_run(const rulgnn_fcstgnn_shape* s, const rulgnn_fcstgnn_args* a, int
     return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
 }
 
-int fcstgnn_bn_running_update(const rulgnn_fcstgnn_shape* s, float* bn_stats, const float* bn_batch, float momentum, int from_moments,
+int Fcstgnn::bn_running_update(const Shape* s, float* bn_stats, const float* bn_batch, float momentum, int from_moments,
                               hipStream_t st) {
     FcGeom g;
     RULGNN_TRY(fc_geometry(s, &g));

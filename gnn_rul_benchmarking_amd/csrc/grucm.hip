@@ -456,13 +456,23 @@ void gc_graph(const GcGeom& g, const GcDrop& d, const GcWs& w, bool bwd, const f
 
 }  // namespace
 
-int64_t grucm_param_count(const rulgnn_grucm_shape* s) {
+// RULGNN_OK, or the code every entry returns for a refused shape: gc_geometry's own, and unsupported where the GRU layer underneath has no
+// workspace for the sequence.
+int Grucm::shape_status(const Shape* s) {
+    GcGeom g;
+    RULGNN_TRY(gc_geometry(s, &g));
+    GcWs w;
+    gc_ws(g, &w);
+    return w.gru_bytes == 0 ? RULGNN_EUNSUPPORTED : RULGNN_OK;
+}
+
+int64_t Grucm::param_count(const Shape* s) {
     GcGeom g;
     if (gc_geometry(s, &g) != RULGNN_OK) return -1;
     return gc_offsets(g.h, g.H, g.L).total;
 }
 
-size_t grucm_workspace_bytes(const rulgnn_grucm_shape* s) {
+size_t Grucm::workspace_bytes(const Shape* s) {
     GcGeom g;
     if (gc_geometry(s, &g) != RULGNN_OK) return 0;
     GcWs w;
@@ -472,7 +482,7 @@ size_t grucm_workspace_bytes(const rulgnn_grucm_shape* s) {
 
 // mode bit 0: forward (pred; with y also d pred and the loss terms), bit 1: backward (gradients; d pred from args->dpred or from the
 // forward of this call)
-int grucm_run(const rulgnn_grucm_shape* s, const rulgnn_grucm_args* a, int mode, hipStream_t st) {
+int Grucm::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
     GcGeom g;
     RULGNN_TRY(gc_geometry(s, &g));
     GcWs w;

@@ -671,11 +671,6 @@ __global__ void hc_head_bwd_kernel(HcGeom g, const float* __restrict__ prm, cons
     if (blockIdx.x == 0 && (int)threadIdx.x < g.M) gr[g.o_bm + threadIdx.x] = 0.f;
 }
 
-#define HC_LAUNCH_OK()                                           \
-    do {                                                         \
-        if (hipGetLastError() != hipSuccess) return RULGNN_EHIP; \
-    } while (0)
-
 HcEpi hc_epi(const HcGeom& g, int l, float* ws, const rulgnn_hiercorrpool_args* a) {
     const HcBlock& k = g.blk[l];
     HcEpi q{};
@@ -698,22 +693,28 @@ HcEpi hc_epi(const HcGeom& g, int l, float* ws, const rulgnn_hiercorrpool_args* 
 
 }  // namespace
 
-int64_t hiercorrpool_param_count(const rulgnn_hiercorrpool_shape* s) {
+// RULGNN_OK, or the code every entry returns for a refused shape: hc_geometry's own.
+int Hiercorrpool::shape_status(const Shape* s) {
+    HcGeom g;
+    return hc_geometry(s, &g);
+}
+
+int64_t Hiercorrpool::param_count(const Shape* s) {
     HcGeom g;
     return hc_geometry(s, &g) == RULGNN_OK ? g.pcount : -1;
 }
 
-int64_t hiercorrpool_bn_state_count(const rulgnn_hiercorrpool_shape* s) {
+int64_t Hiercorrpool::bn_state_count(const Shape* s) {
     HcGeom g;
     return hc_geometry(s, &g) == RULGNN_OK ? g.bncount : -1;
 }
 
-size_t hiercorrpool_workspace_bytes(const rulgnn_hiercorrpool_shape* s) {
+size_t Hiercorrpool::workspace_bytes(const Shape* s) {
     HcGeom g;
     return hc_geometry(s, &g) == RULGNN_OK ? g.total_bytes : 0;
 }
 
-int64_t hiercorrpool_tap_offset(const rulgnn_hiercorrpool_shape* s, int which) {
+int64_t Hiercorrpool::tap_offset(const Shape* s, int which) {
     HcGeom g;
     if (hc_geometry(s, &g) != RULGNN_OK) return -1;
     switch (which) {
@@ -726,7 +727,7 @@ int64_t hiercorrpool_tap_offset(const rulgnn_hiercorrpool_shape* s, int which) {
 }
 
 // mode bit 0: forward, bit 1: backward (after a forward with the same args / workspace)
-int hiercorrpool_run(const rulgnn_hiercorrpool_shape* s, const rulgnn_hiercorrpool_args* a, int mode, hipStream_t st) {
+int Hiercorrpool::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
     HcGeom g;
     RULGNN_TRY(hc_geometry(s, &g));
     if (a->workspace_bytes < g.total_bytes) return RULGNN_EWORKSPACE;
@@ -747,7 +748,7 @@ int hiercorrpool_run(const rulgnn_hiercorrpool_shape* s, const rulgnn_hiercorrpo
             pk.W[l] = prm + k.o_w; pk.Wp[l] = ws + k.w_wp; pk.Wt[l] = l > 0 ? ws + k.w_wt : nullptr; pk.Cin[l] = k.Cin; pk.Cout[l] = k.Cout;
         }
         hipLaunchKernelGGL(hc_pack_weights_kernel<false>, dim3(hc_blocks((int64_t)g.blk[2].Cout * g.blk[2].Cin * HC_TAPS, 4096)), dim3(HC_GB), 0, st, pk);
-        HC_LAUNCH_OK();
+        RULGNN_LAUNCH_OK();
         for (int l = 0; l < 3; ++l) {
             const HcBlock& k = g.blk[l];
             // z [R - 7][Cout] = (overlapping-row view of the padded input) [R - 7][8 Cin] . Wp^T
@@ -762,21 +763,21 @@ int hiercorrpool_run(const rulgnn_hiercorrpool_shape* s, const rulgnn_hiercorrpo
                                (const double*)part, prm + k.o_g, prm + k.o_b, ws + k.w_coef, ws + k.w_bcoef, a->bn_state + k.o_bn,
                                a->training ? 1 : 0, (a->training && a->update_running_stats) ? 1 : 0, (float*)nullptr, (float*)nullptr);
             hipLaunchKernelGGL(hc_epilogue_fwd_kernel, dim3(hc_blocks(B * q.orow * k.Cout)), dim3(HC_GB), 0, st, q);
-            HC_LAUNCH_OK();
+            RULGNN_LAUNCH_OK();
         }
         RULGNN_TRY(allow_dynamic_lds(hcp_graph_fwd, g.lds_fwd));
         hipLaunchKernelGGL(hcp_graph_fwd, dim3(hc_grid(B, 8192)), dim3(HC_GB), g.lds_fwd, st, g, prm, gq);
-        HC_LAUNCH_OK();
+        RULGNN_LAUNCH_OK();
         // H = leaky((A' X') Wt^T + bt); pre0 = H.flat fc_0^T
         RULGNN_TRY(sgemm(ws + g.w_axp, d, 1, prm + g.o_tw, d, 1, ws + g.w_H, d3, BM, d3, d, false, st));
         hipLaunchKernelGGL(hc_bias_leaky_kernel<false>, dim3(hc_blocks((int64_t)BM * d3)), dim3(HC_GB), 0, st, (int64_t)BM, d3, ws + g.w_H, prm + g.o_tb,
                            (const float*)nullptr);
-        HC_LAUNCH_OK();
+        RULGNN_LAUNCH_OK();
         RULGNN_TRY(sgemm_splitk(ws + g.w_H, (int64_t)M * d3, 1, prm + g.o_f0w, (int64_t)M * d3, 1, ws + g.w_pre0, e3, (int)B, e3, M * d3, false,
                                 ws + g.w_split, st));
         hipLaunchKernelGGL(hc_head_kernel, dim3(hc_blocks(B, 4096)), dim3(HC_GB), 0, st, g, prm, ws + g.w_pre0, ws + g.w_pre1, a->y, a->pred, ws + g.w_sq,
                            ws + g.w_dpred, 1.0f / (float)gb);
-        HC_LAUNCH_OK();
+        RULGNN_LAUNCH_OK();
         if (a->y && a->loss) RULGNN_TRY(block_sum((const float*)(ws + g.w_sq), B, a->loss, st));
     }
     if (mode & 2) {
@@ -784,13 +785,13 @@ int hiercorrpool_run(const rulgnn_hiercorrpool_shape* s, const rulgnn_hiercorrpo
         float* gr = a->grads;
         hipLaunchKernelGGL(hc_head_bwd_kernel, dim3(hc_blocks(B, 4096)), dim3(HC_GB), 0, st, g, prm, (const float*)(ws + g.w_pre0), (const float*)(ws + g.w_pre1),
                            dpred, ws + g.w_prod, ws + g.w_dpre0, gr);
-        HC_LAUNCH_OK();
+        RULGNN_LAUNCH_OK();
         // g fc_0.weight [3e][3dM] = dpre0^T H.flat (k = the batch, one fixed-order product); dH = dpre0 fc_0
         RULGNN_TRY(sgemm(ws + g.w_dpre0, 1, e3, ws + g.w_H, 1, (int64_t)M * d3, gr + g.o_f0w, (int64_t)M * d3, e3, M * d3, (int)B, false, st));
         RULGNN_TRY(sgemm(ws + g.w_dpre0, e3, 1, prm + g.o_f0w, 1, (int64_t)M * d3, ws + g.w_dH, (int64_t)M * d3, (int)B, M * d3, e3, false, st));
         hipLaunchKernelGGL(hc_bias_leaky_kernel<true>, dim3(hc_blocks((int64_t)BM * d3)), dim3(HC_GB), 0, st, (int64_t)BM, d3, ws + g.w_dH,
                            (const float*)nullptr, (const float*)(ws + g.w_H));
-        HC_LAUNCH_OK();
+        RULGNN_LAUNCH_OK();
         {   // [g fc_1.weight | g fc_1.bias], g fc_0.bias and g theta.bias: three fixed-order column sums in one launch
             const float* const part[3] = {ws + g.w_prod, ws + g.w_dpre0, ws + g.w_dH};
             float* const out[3] = {gr + g.o_f1w, gr + g.o_f0b, gr + g.o_tb};
@@ -803,7 +804,7 @@ int hiercorrpool_run(const rulgnn_hiercorrpool_shape* s, const rulgnn_hiercorrpo
         RULGNN_TRY(sgemm(ws + g.w_dH, d3, 1, prm + g.o_tw, 1, d, ws + g.w_dq, d, BM, d, d3, false, st));
         RULGNN_TRY(allow_dynamic_lds(hcp_graph_bwd, g.lds_bwd));
         hipLaunchKernelGGL(hcp_graph_bwd, dim3(hc_grid(B, 8192)), dim3(HC_GB), g.lds_bwd, st, g, prm, gq);
-        HC_LAUNCH_OK();
+        RULGNN_LAUNCH_OK();
         // [g Wd | g bd | g Wm] = the samples' contributions in order (contiguous in the parameter layout)
         RULGNN_TRY(rows_sum(ws + g.w_contrib, (int)B, g.CW, g.CW, gr + g.o_wd, st));
         HcPack up{};
@@ -816,7 +817,7 @@ int hiercorrpool_run(const rulgnn_hiercorrpool_shape* s, const rulgnn_hiercorrpo
             hipLaunchKernelGGL(hc_stats_finish_kernel<true>, dim3((k.Cout + 63) / 64), dim3(64), 0, st, k.Cout, slices, (double)(B * k.Lc),
                                (const double*)part, prm + k.o_g, prm + k.o_b, ws + k.w_coef, ws + k.w_bcoef, (float*)nullptr, 1, 0, gr + k.o_g, gr + k.o_b);
             hipLaunchKernelGGL(hc_dz_kernel, dim3(hc_blocks((k.R + 7) * k.Cout)), dim3(HC_GB), 0, st, q, prm + k.o_g);
-            HC_LAUNCH_OK();
+            RULGNN_LAUNCH_OK();
             const float* dz = ws + k.w_dz + (int64_t)7 * k.Cout;           // row r of z's numbering
             // d Wp [Cout][8 Cin] = dz^T . view, k = the R - 7 rows in fixed slices
             RULGNN_TRY(sgemm_splitk(dz, 1, k.Cout, ws + k.w_in, 1, k.Cin, ws + k.w_dwp, (int64_t)HC_TAPS * k.Cin, k.Cout, HC_TAPS * k.Cin, (int)(k.R - 7),
@@ -828,7 +829,7 @@ int hiercorrpool_run(const rulgnn_hiercorrpool_shape* s, const rulgnn_hiercorrpo
             up.W[l] = ws + k.w_dwp; up.Wp[l] = gr + k.o_w; up.Wt[l] = nullptr; up.Cin[l] = k.Cin; up.Cout[l] = k.Cout;
         }
         hipLaunchKernelGGL(hc_pack_weights_kernel<true>, dim3(hc_blocks((int64_t)g.blk[2].Cout * g.blk[2].Cin * HC_TAPS, 4096)), dim3(HC_GB), 0, st, up);
-        HC_LAUNCH_OK();
+        RULGNN_LAUNCH_OK();
     }
     return RULGNN_OK;
 }

@@ -660,24 +660,25 @@ __global__ __launch_bounds__(LG_GB) void lg_loss_kernel(int64_t B, double cnt, f
     }
 }
 
-#define LG_LAUNCH_OK()                                           \
-    do {                                                         \
-        if (hipGetLastError() != hipSuccess) return RULGNN_EHIP; \
-    } while (0)
-
 }  // namespace
 
-int64_t logo_param_count(const rulgnn_logo_shape* s) {
+// RULGNN_OK, or the code every entry returns for a refused shape: lg_geometry's own.
+int Logo::shape_status(const Shape* s) {
+    LgGeom g;
+    return lg_geometry(s, &g);
+}
+
+int64_t Logo::param_count(const Shape* s) {
     LgGeom g;
     return lg_geometry(s, &g) == RULGNN_OK ? g.pcount : -1;
 }
 
-size_t logo_workspace_bytes(const rulgnn_logo_shape* s) {
+size_t Logo::workspace_bytes(const Shape* s) {
     LgGeom g;
     return lg_geometry(s, &g) == RULGNN_OK ? g.total_bytes : 0;
 }
 
-int64_t logo_tap_offset(const rulgnn_logo_shape* s, int which) {
+int64_t Logo::tap_offset(const Shape* s, int which) {
     LgGeom g;
     if (lg_geometry(s, &g) != RULGNN_OK) return -1;
     switch (which) {
@@ -689,7 +690,7 @@ int64_t logo_tap_offset(const rulgnn_logo_shape* s, int which) {
 }
 
 // mode bit 0: forward, bit 1: backward (after a forward with the same args / workspace)
-int logo_run(const rulgnn_logo_shape* s, const rulgnn_logo_args* a, int mode, hipStream_t st) {
+int Logo::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
     LgGeom g;
     RULGNN_TRY(lg_geometry(s, &g));
     if (a->workspace_bytes < g.total_bytes) return RULGNN_EWORKSPACE;
@@ -725,7 +726,7 @@ int logo_run(const rulgnn_logo_shape* s, const rulgnn_logo_args* a, int mode, hi
     if (mode & 1) {
         RULGNN_TRY(allow_dynamic_lds(lg_graph_fwd, g.lds_fwd));
         hipLaunchKernelGGL(lg_graph_fwd, dim3((unsigned)(B > 8192 ? 8192 : B)), dim3(LG_GB), g.lds_fwd, st, g, a->x, prm, ws + g.w_hg, ws + g.w_glpart);
-        LG_LAUNCH_OK();
+        RULGNN_LAUNCH_OK();
         for (int l = 0; l < 3; ++l) {
             rulgnn_bilstm_shape ls;
             rulgnn_bilstm_args la;
@@ -735,21 +736,21 @@ int logo_run(const rulgnn_logo_shape* s, const rulgnn_logo_args* a, int mode, hi
         }
         hipLaunchKernelGGL(lg_close_kernel<false>, dim3(lg_blocks(QB * H1)), dim3(LG_GB), 0, st, B, Q, H1, (const float*)(ws + g.w_o3), (const float*)nullptr,
                            ws + g.w_td, key3, dc.thr, dscale);
-        LG_LAUNCH_OK();
+        RULGNN_LAUNCH_OK();
         // pre1 [B][16] = td [B][Q 3h] fc1^T: a few tiles over k = Q 3h, in fixed slices
         RULGNN_TRY(sgemm_splitk(ws + g.w_td, K1, 1, prm + g.o_f1w, K1, 1, ws + g.w_pre1, LG_F1, (int)B, LG_F1, K1, false, ws + g.w_split, st));
         hipLaunchKernelGGL(lg_head_kernel, dim3(lg_blocks(B, 4096)), dim3(LG_GB), 0, st, g, prm, ws + g.w_pre1, ws + g.w_a2, a->y, a->pred, ws + g.w_sq,
                            ws + g.w_dpred, 1.0f / (float)gb);
         hipLaunchKernelGGL(lg_loss_kernel, dim3(1), dim3(LG_GB), 0, st, B, cnt, a->theta, a->gamma, (const float*)(ws + g.w_glpart),
                            a->y ? (const float*)(ws + g.w_sq) : (const float*)nullptr, ws + g.w_gl, a->loss_gl, a->loss);
-        LG_LAUNCH_OK();
+        RULGNN_LAUNCH_OK();
     }
     if (mode & 2) {
         if (!a->grads) return RULGNN_EINVAL;
         float* gr = a->grads;
         hipLaunchKernelGGL(lg_head_bwd_kernel, dim3(lg_blocks(B, 4096)), dim3(LG_GB), 0, st, g, prm, (const float*)(ws + g.w_pre1), (const float*)(ws + g.w_a2),
                            dpred, ws + g.w_prod, ws + g.w_dpre1);
-        LG_LAUNCH_OK();
+        RULGNN_LAUNCH_OK();
         // [g fc1.bias .. g cls.bias] = the samples' rows in order (contiguous in the parameter layout)
         RULGNN_TRY(rows_sum(ws + g.w_prod, (int)B, LG_HEADROW, LG_HEADROW, gr + g.o_f1b, st));
         // g fc1.weight [16][Q 3h] = dpre1^T td (k = the batch, one fixed-order product); dtd = dpre1 fc1
@@ -757,7 +758,7 @@ int logo_run(const rulgnn_logo_shape* s, const rulgnn_logo_args* a, int mode, hi
         RULGNN_TRY(sgemm(ws + g.w_dpre1, LG_F1, 1, prm + g.o_f1w, 1, K1, ws + g.w_dtd, K1, (int)B, K1, LG_F1, false, st));
         hipLaunchKernelGGL(lg_close_kernel<true>, dim3(lg_blocks(QB * H1)), dim3(LG_GB), 0, st, B, Q, H1, (const float*)(ws + g.w_dtd),
                            (const float*)(ws + g.w_td), ws + g.w_do3, key3, dc.thr, dscale);
-        LG_LAUNCH_OK();
+        RULGNN_LAUNCH_OK();
         for (int l = 2; l >= 0; --l) {
             const LgLstm& k = g.lstm[l];
             rulgnn_bilstm_shape ls;
@@ -771,11 +772,11 @@ int logo_run(const rulgnn_logo_shape* s, const rulgnn_logo_args* a, int mode, hi
             RULGNN_TRY(bilstm_backward(&ls, &la, st, 2));
             if (l == 2 && drop) hipLaunchKernelGGL(lg_drop_kernel, dim3(lg_blocks(QB * H2)), dim3(LG_GB), 0, st, QB * H2, ws + g.w_do2, key2, dc.thr, dscale);
         }
-        LG_LAUNCH_OK();
+        RULGNN_LAUNCH_OK();
         RULGNN_TRY(allow_dynamic_lds(lg_graph_bwd, g.lds_bwd));
         hipLaunchKernelGGL(lg_graph_bwd, dim3((unsigned)g.rows), dim3(LG_GB), g.lds_bwd, st, g, a->x, prm, (const float*)(ws + g.w_dhg),
                            (const float*)(ws + g.w_gl), a->theta, a->gamma, ws + g.w_part);
-        LG_LAUNCH_OK();
+        RULGNN_LAUNCH_OK();
         RULGNN_TRY(rows_sum(ws + g.w_part, g.rows, g.CW, g.nA, gr + g.o_wn, st));
         RULGNN_TRY(rows_sum(ws + g.w_part + g.nA, g.rows, g.CW, g.nB, gr + g.o_fu, st));
     }

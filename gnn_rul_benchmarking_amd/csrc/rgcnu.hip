@@ -1072,18 +1072,24 @@ size_t rg_fusion_lds(const RgGeom& g, bool bwd) {
 
 }  // namespace
 
-int64_t rgcnu_param_count(const rulgnn_rgcnu_shape* s) {
+// RULGNN_OK, or the code every entry returns for a refused shape: rg_geometry's own.
+int Rgcnu::shape_status(const Shape* s) {
+    RgGeom g;
+    return rg_geometry(s, &g);
+}
+
+int64_t Rgcnu::param_count(const Shape* s) {
     RgGeom g;
     return rg_geometry(s, &g) == RULGNN_OK ? g.pcount : -1;
 }
 
-size_t rgcnu_workspace_bytes(const rulgnn_rgcnu_shape* s) {
+size_t Rgcnu::workspace_bytes(const Shape* s) {
     RgGeom g;
     return rg_geometry(s, &g) == RULGNN_OK ? (size_t)g.total * sizeof(float) : 0;
 }
 
 // mode bit 0: forward, bit 1: backward (after a forward with the same args / workspace)
-int rgcnu_run(const rulgnn_rgcnu_shape* s, const rulgnn_rgcnu_args* a, int mode, hipStream_t st) {
+int Rgcnu::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
     RgGeom g;
     RULGNN_TRY(rg_geometry(s, &g));
     if (a->workspace_bytes < (size_t)g.total * sizeof(float)) return RULGNN_EWORKSPACE;

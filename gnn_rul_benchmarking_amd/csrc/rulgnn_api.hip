@@ -54,19 +54,24 @@ static bool opt_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) 
 
 // The pointer checks the plain families' steps end in, in two halves (a family with tests of its own between them calls the halves):
 // parameters and workspace always, x and pred with a batch; for a backward the gradients and, with a batch, d pred or the targets.
-static int check_fwd_ptrs(const void* params, const void* workspace, const void* x, const void* pred, int64_t batch) {
-    RULGNN_TRY(check_ptrs({params, workspace}));
-    return batch > 0 ? check_ptrs({x, pred}) : RULGNN_OK;
+// `a` is any family's args struct: the fields have the same names in all of them.
+extern "C++" {
+template <typename A>
+static int check_fwd_ptrs(const A* a, int64_t batch) {
+    RULGNN_TRY(check_ptrs({a->params, a->workspace}));
+    return batch > 0 ? check_ptrs({a->x, a->pred}) : RULGNN_OK;
 }
-static int check_bwd_ptrs(const void* grads, const void* y, const void* dpred, int64_t batch) {
-    RULGNN_TRY(check_ptrs({grads}));
-    return !dpred && !y && batch > 0 ? RULGNN_EINVAL : RULGNN_OK;
+template <typename A>
+static int check_bwd_ptrs(const A* a, int64_t batch) {
+    RULGNN_TRY(check_ptrs({a->grads}));
+    return !a->dpred && !a->y && batch > 0 ? RULGNN_EINVAL : RULGNN_OK;
 }
-static int check_step_ptrs(const void* params, const void* workspace, const void* x, const void* pred, const void* grads, const void* y,
-                           const void* dpred, int64_t batch, bool bwd) {
-    RULGNN_TRY(check_fwd_ptrs(params, workspace, x, pred, batch));
-    return bwd ? check_bwd_ptrs(grads, y, dpred, batch) : RULGNN_OK;
+template <typename A>
+static int check_step_ptrs(const A* a, int64_t batch, bool bwd) {
+    RULGNN_TRY(check_fwd_ptrs(a, batch));
+    return bwd ? check_bwd_ptrs(a, batch) : RULGNN_OK;
 }
+}  // extern "C++"
 
 // The optimizer block of a family's fused step (rulgnn_<family>_fwdbwd_f32): a step count or a device step state, the step's own
 // parameter buffer, then the Adam pointers.
@@ -81,19 +86,38 @@ static int adam_tail(const rulgnn_adam_args* opt, const float* grads, int64_t fi
                      opt->beta2, opt->eps, opt->weight_decay, 1.0f, st, opt->step_state);
 }
 
-// What follows a family's argument check in its fused MSE step (rulgnn_<family>_fwdbwd_f32): d pred is refused (`missing_y`: so is a
-// batch without targets), the optimizer block checked, `run` (mode 3) enqueued and, with an optimizer, plain Adam over the flat floats
-// [first, first + n).
-extern "C++" template <typename Run>
-static int fused_step_tail(const float* dpred, bool missing_y, const rulgnn_adam_args* opt, const float* params, Run run, const float* grads,
-                           int64_t first, int64_t n, void* stream) {
-    if (dpred || missing_y) return RULGNN_EINVAL;          // the fused call is the MSE step
-    if (opt) RULGNN_TRY(check_adam(opt, params));
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int rc = run(st);
-    if (rc != RULGNN_OK || !opt) return rc;
-    return adam_tail(opt, grads, first, n, st);
+// ---- the entries of a step family (families_host.hpp: StepFamily) -------------------------------------------------------------------
+// Every rulgnn_<family>_{forward,backward,fwdbwd}_f32 is one of these on the family's description F: null structs are refused, then
+// whatever F::check_args refuses (its shape_status first), then F::run is enqueued in mode 1, 2 or 3.
+extern "C++" {
+template <typename F>
+static int step_check(const typename F::Shape* shape, const typename F::Args* args, bool fwd, bool bwd) {
+    if (!shape || !args) return RULGNN_EINVAL;
+    return F::check_args(shape, args, fwd, bwd);
 }
+template <typename F>
+static int step_forward(const typename F::Shape* shape, const typename F::Args* args, void* stream) {
+    RULGNN_TRY(step_check<F>(shape, args, true, false));
+    return F::run(shape, args, 1, static_cast<hipStream_t>(stream));
+}
+template <typename F>
+static int step_backward(const typename F::Shape* shape, const typename F::Args* args, void* stream) {
+    RULGNN_TRY(step_check<F>(shape, args, false, true));
+    return F::run(shape, args, 2, static_cast<hipStream_t>(stream));
+}
+// The fused call is the MSE step: d pred is refused, and so is a batch without targets.  With an optimizer block, plain Adam over the
+// flat floats the family's description leaves live follows the step.
+template <typename F>
+static int step_fwdbwd(const typename F::Shape* shape, const typename F::Args* args, const rulgnn_adam_args* opt, void* stream) {
+    RULGNN_TRY(step_check<F>(shape, args, true, true));
+    if (args->dpred || (!args->y && shape->batch > 0)) return RULGNN_EINVAL;
+    if (opt) RULGNN_TRY(check_adam(opt, args->params));
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int rc = F::run(shape, args, 3, st);
+    if (rc != RULGNN_OK || !opt) return rc;
+    return adam_tail(opt, args->grads, F::adam_first, F::param_count(shape) - F::adam_first - F::adam_frozen_tail(shape), st);
+}
+}  // extern "C++"
 
 // Path selection.  The fused row-mapped kernels cover num_patch <= 64 as long as one wavefront's input tile fits its LDS staging area,
 // every launch form a call may reach fits the 160 KB of LDS a workgroup can have (stgcn_host.hpp: the *_lds_bytes functions the
@@ -424,142 +448,183 @@ int rulgnn_bn_running_update_f32(float* bn_stats, const float* bn_batch, int32_t
 
 
 // ---- STMSGCN ------------------------------------------------------------------------------------------
-int64_t rulgnn_stmsgcn_param_count(const rulgnn_stmsgcn_shape* shape) { return stmsgcn_param_count(shape); }
-
-size_t rulgnn_stmsgcn_workspace_bytes(const rulgnn_stmsgcn_shape* shape) { return stmsgcn_workspace_bytes(shape); }
+int64_t rulgnn_stmsgcn_param_count(const rulgnn_stmsgcn_shape* shape) { return Stmsgcn::param_count(shape); }
+size_t rulgnn_stmsgcn_workspace_bytes(const rulgnn_stmsgcn_shape* shape) { return Stmsgcn::workspace_bytes(shape); }
 
 int rulgnn_stmsgcn_features_f32(const rulgnn_stmsgcn_shape* shape, const float* x, const float* params, float* features,
                                 void* stream) {
     if (!shape) return RULGNN_EINVAL;
-    if (stmsgcn_param_count(shape) >= 0 && shape->batch == 0) return RULGNN_OK;
+    if (Stmsgcn::param_count(shape) >= 0 && shape->batch == 0) return RULGNN_OK;
     const int rc = check_ptrs({x, params, features});
     if (rc != RULGNN_OK) return rc;
     return stmsgcn_features(shape, x, params, features, static_cast<hipStream_t>(stream));
 }
 
-static int check_stmsgcn(const rulgnn_stmsgcn_shape* shape, const rulgnn_stmsgcn_args* a, bool backward, bool need_target) {
-    if (!shape || !a) return RULGNN_EINVAL;
+// (the shape is judged by run(), behind this)
+int Stmsgcn::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
     if (shape->batch < 1 || a->global_batch < shape->batch) return RULGNN_EINVAL;
-    int rc = check_ptrs({a->x, a->params, a->pred, a->workspace});
-    if (rc != RULGNN_OK) return rc;
+    RULGNN_TRY(check_ptrs({a->x, a->params, a->pred, a->workspace}));
     if (!opt_aligned(a->y)) return RULGNN_EALIGN;
-    if (backward) {
-        rc = check_ptrs({a->grads});
-        if (rc != RULGNN_OK) return rc;
-        if (a->dpred) {
-            if (!opt_aligned(a->dpred)) return RULGNN_EALIGN;
-        } else if (need_target) {
-            rc = check_ptrs({a->y, a->loss});
-            if (rc != RULGNN_OK) return rc;
-        }
-    }
-    return RULGNN_OK;
+    if (!bwd) return RULGNN_OK;
+    RULGNN_TRY(check_ptrs({a->grads}));
+    if (a->dpred) return opt_aligned(a->dpred) ? RULGNN_OK : RULGNN_EALIGN;
+    return check_ptrs({a->y, a->loss});
 }
 
 int rulgnn_stmsgcn_forward_f32(const rulgnn_stmsgcn_shape* shape, const rulgnn_stmsgcn_args* args, void* stream) {
-    const int rc = check_stmsgcn(shape, args, false, false);
-    if (rc != RULGNN_OK) return rc;
-    return stmsgcn_run(shape, args, 1, static_cast<hipStream_t>(stream));
+    return step_forward<Stmsgcn>(shape, args, stream);
 }
-
 int rulgnn_stmsgcn_backward_f32(const rulgnn_stmsgcn_shape* shape, const rulgnn_stmsgcn_args* args, void* stream) {
-    const int rc = check_stmsgcn(shape, args, true, true);
-    if (rc != RULGNN_OK) return rc;
-    return stmsgcn_run(shape, args, 2, static_cast<hipStream_t>(stream));
+    return step_backward<Stmsgcn>(shape, args, stream);
+}
+int rulgnn_stmsgcn_fwdbwd_f32(const rulgnn_stmsgcn_shape* shape, const rulgnn_stmsgcn_args* args, const rulgnn_adam_args* opt, void* stream) {
+    return step_fwdbwd<Stmsgcn>(shape, args, opt, stream);
 }
 
-int rulgnn_stmsgcn_fwdbwd_f32(const rulgnn_stmsgcn_shape* shape, const rulgnn_stmsgcn_args* args, const rulgnn_adam_args* opt,
-                              void* stream) {
-    RULGNN_TRY(check_stmsgcn(shape, args, true, true));
-    auto run = [&](hipStream_t st) { return stmsgcn_run(shape, args, 3, st); };
-    return fused_step_tail(args->dpred, false, opt, args->params, run, args->grads, 0, stmsgcn_param_count(shape), stream);
-}
-
-
-// ---- ASTGCNN ------------------------------------------------------------------------------------------
-int64_t rulgnn_astgcnn_param_count(const rulgnn_astgcnn_shape* shape) { return astgcnn_param_count(shape); }
-
-size_t rulgnn_astgcnn_workspace_bytes(const rulgnn_astgcnn_shape* shape) { return astgcnn_workspace_bytes(shape); }
-
-static int check_astgcnn(const rulgnn_astgcnn_shape* shape, const rulgnn_astgcnn_args* a, bool forward, bool backward) {
-    if (!shape || !a) return RULGNN_EINVAL;
-    if (shape->batch < 1 || a->global_batch < shape->batch) return RULGNN_EINVAL;
+// ---- the BatchNorm families: ASTGCNN, FC_STGNN, ST_Conv ---------------------------------------------------------------------------------
+// Their shared argument check (the args structs have these fields under the same names).  The shape is judged by run(), behind it.
+extern "C++" {
+template <typename A>
+static int check_bn_args(int64_t batch, const A* a, bool fwd, bool bwd) {
+    if (batch < 1 || a->global_batch < batch) return RULGNN_EINVAL;          // BatchNorm needs a batch
     if (!(a->bn_moment_weight >= 0.f)) return RULGNN_EINVAL;
-    int rc = check_ptrs({a->x, a->params, a->pred, a->workspace});
-    if (rc != RULGNN_OK) return rc;
-    if (forward && !a->training) {
-        rc = check_ptrs({a->bn_stats});
-        if (rc != RULGNN_OK) return rc;
-    }
+    RULGNN_TRY(check_ptrs({a->x, a->params, a->pred, a->workspace}));
+    if (fwd && !a->training) RULGNN_TRY(check_ptrs({a->bn_stats}));
     for (const void* p : {(const void*)a->y, (const void*)a->dpred, (const void*)a->bn_batch, (const void*)a->loss})
         if (!opt_aligned(p)) return RULGNN_EALIGN;
-    if (backward) {
-        if (!a->training) return RULGNN_EINVAL;            // the backward is the train-mode (batch-statistics) one
-        rc = check_ptrs({a->grads});
-        if (rc != RULGNN_OK) return rc;
-        if (!a->dpred) {
-            rc = check_ptrs({a->y, a->loss});
-            if (rc != RULGNN_OK) return rc;
-        }
-    }
-    return RULGNN_OK;
+    if (!bwd) return RULGNN_OK;
+    if (!a->training) return RULGNN_EINVAL;            // the backward is the train-mode (batch-statistics) one
+    RULGNN_TRY(check_ptrs({a->grads}));
+    return a->dpred ? RULGNN_OK : check_ptrs({a->y, a->loss});
 }
 
-int rulgnn_astgcnn_forward_f32(const rulgnn_astgcnn_shape* shape, const rulgnn_astgcnn_args* args, void* stream) {
-    const int rc = check_astgcnn(shape, args, true, false);
-    if (rc != RULGNN_OK) return rc;
-    return astgcnn_run(shape, args, 1, static_cast<hipStream_t>(stream));
-}
-
-int rulgnn_astgcnn_backward_f32(const rulgnn_astgcnn_shape* shape, const rulgnn_astgcnn_args* args, void* stream) {
-    const int rc = check_astgcnn(shape, args, false, true);
-    if (rc != RULGNN_OK) return rc;
-    return astgcnn_run(shape, args, 2, static_cast<hipStream_t>(stream));
-}
-
-int rulgnn_astgcnn_fwdbwd_f32(const rulgnn_astgcnn_shape* shape, const rulgnn_astgcnn_args* args, const rulgnn_adam_args* opt,
-                              void* stream) {
-    int rc = check_astgcnn(shape, args, true, true);
-    if (rc != RULGNN_OK) return rc;
+// Their fused MSE step.  With an optimizer block, Adam and the running-statistics update follow the step -- inside it where the
+// family's run() takes them (F::run_takes_optimizer), as launches behind it otherwise.
+template <typename F>
+static int bn_step_fwdbwd(const typename F::Shape* shape, const typename F::Args* args, const rulgnn_adam_args* opt, void* stream) {
+    RULGNN_TRY(step_check<F>(shape, args, true, true));
     if (args->dpred) return RULGNN_EINVAL;
-    if (opt && (rc = check_adam(opt, args->params)) != RULGNN_OK) return rc;
+    if (opt) RULGNN_TRY(check_adam(opt, args->params));
     if (opt && opt->bn_stats && (!args->bn_batch || !opt_aligned(opt->bn_stats))) return RULGNN_EINVAL;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    // (plain batch statistics: the running-statistics update rides in the step's finalize kernel)
-    const bool tail_bn = opt && opt->bn_stats && args->training && args->bn_moment_weight == 0.f;
-    // (host-side step count: the step's last kernel may apply the optimizer itself -- adam_device.hpp)
-    AdamFuse fuse{};
-    const bool try_fuse = opt && !opt->step_state;
-    if (try_fuse)
-        adam_fuse_args(&fuse, opt->params, opt->exp_avg, opt->exp_avg_sq, nullptr, opt->step, opt->lr, opt->beta1, opt->beta2, opt->eps,
-                       opt->weight_decay);
-    rc = astgcnn_run(shape, args, 3, st, nullptr, tail_bn ? opt->bn_stats : nullptr, tail_bn ? opt->bn_momentum : 0.f, try_fuse ? &fuse : nullptr);
+    bool bn_in_step = false, adam_in_step = false;
+    int rc;
+    if constexpr (F::run_takes_optimizer) {
+        // (plain batch statistics: the running-statistics update rides in the step)
+        bn_in_step = opt && opt->bn_stats && args->training && args->bn_moment_weight == 0.f;
+        // (host-side step count: the step's last kernel may apply the optimizer itself -- adam_device.hpp; a device step state keeps the
+        // launch.  run() leaves fuse.gbase set where it did.)
+        AdamFuse fuse{};
+        const bool try_fuse = opt && !opt->step_state;
+        if (try_fuse)
+            adam_fuse_args(&fuse, opt->params, opt->exp_avg, opt->exp_avg_sq, args->grads, opt->step, opt->lr, opt->beta1, opt->beta2, opt->eps,
+                           opt->weight_decay);
+        rc = F::run(shape, args, 3, st, nullptr, bn_in_step ? opt->bn_stats : nullptr, bn_in_step ? opt->bn_momentum : 0.f, try_fuse ? &fuse : nullptr);
+        adam_in_step = try_fuse && fuse.gbase;
+    } else {
+        rc = F::run(shape, args, 3, st);
+    }
     if (rc != RULGNN_OK || !opt) return rc;
-    if (!(try_fuse && fuse.gbase))
-        rc = adam_tail(opt, args->grads, 0, astgcnn_param_count(shape), st);
-    if (rc != RULGNN_OK || !opt->bn_stats || tail_bn) return rc;
-    return astgcnn_bn_running_update(shape, opt->bn_stats, args->bn_batch, shape->batch * (int64_t)shape->time_length,
-                                     opt->bn_momentum, args->bn_moment_weight > 0.f ? 1 : 0, st);
+    if (!adam_in_step) rc = adam_tail(opt, args->grads, 0, F::param_count(shape), st);
+    if (rc != RULGNN_OK || !opt->bn_stats || bn_in_step) return rc;
+    return F::step_bn_update(shape, opt->bn_stats, args->bn_batch, opt->bn_momentum, args->bn_moment_weight > 0.f ? 1 : 0, st);
 }
 
-int rulgnn_astgcnn_fwdbwd_syncbn_f32(const rulgnn_astgcnn_shape* shape, const rulgnn_astgcnn_args* args, float bn_param_grad_scale,
-                                     rulgnn_allreduce_f64_fn allreduce, void* user, void* stream) {
-    const int rc = check_astgcnn(shape, args, true, true);
-    if (rc != RULGNN_OK) return rc;
+// The same step under synchronised BatchNorm (rulgnn_<family>_fwdbwd_syncbn_f32).
+template <typename F>
+static int bn_step_syncbn(const typename F::Shape* shape, const typename F::Args* args, float bn_param_grad_scale, rulgnn_allreduce_f64_fn allreduce,
+                          void* user, void* stream) {
+    RULGNN_TRY(step_check<F>(shape, args, true, true));
     if (args->dpred) return RULGNN_EINVAL;
     RULGNN_TRY(check_sync(bn_param_grad_scale, allreduce));
     const SyncHook hook = {allreduce, user, bn_param_grad_scale};
-    return astgcnn_run(shape, args, 3, static_cast<hipStream_t>(stream), &hook);
+    return F::run(shape, args, 3, static_cast<hipStream_t>(stream), &hook);
+}
+}  // extern "C++"
+
+// What the rulgnn_<family>_bn_running_update_f32 entries refuse (FC_STGNN's has no count: its shape holds it).
+static int check_bn_update(const void* shape, const float* bn_stats, const float* bn_batch, int64_t count = 1) {
+    if (!shape || count < 1) return RULGNN_EINVAL;
+    return check_ptrs({bn_stats, bn_batch});
 }
 
+// ---- ASTGCNN ------------------------------------------------------------------------------------------
+int64_t rulgnn_astgcnn_param_count(const rulgnn_astgcnn_shape* shape) { return Astgcnn::param_count(shape); }
+size_t rulgnn_astgcnn_workspace_bytes(const rulgnn_astgcnn_shape* shape) { return Astgcnn::workspace_bytes(shape); }
+
+int Astgcnn::check_args(const Shape* shape, const Args* a, bool fwd, bool bwd) { return check_bn_args(shape->batch, a, fwd, bwd); }
+
+int rulgnn_astgcnn_forward_f32(const rulgnn_astgcnn_shape* shape, const rulgnn_astgcnn_args* args, void* stream) {
+    return step_forward<Astgcnn>(shape, args, stream);
+}
+int rulgnn_astgcnn_backward_f32(const rulgnn_astgcnn_shape* shape, const rulgnn_astgcnn_args* args, void* stream) {
+    return step_backward<Astgcnn>(shape, args, stream);
+}
+int rulgnn_astgcnn_fwdbwd_f32(const rulgnn_astgcnn_shape* shape, const rulgnn_astgcnn_args* args, const rulgnn_adam_args* opt,
+                              void* stream) {
+    return bn_step_fwdbwd<Astgcnn>(shape, args, opt, stream);
+}
+int rulgnn_astgcnn_fwdbwd_syncbn_f32(const rulgnn_astgcnn_shape* shape, const rulgnn_astgcnn_args* args, float bn_param_grad_scale,
+                                     rulgnn_allreduce_f64_fn allreduce, void* user, void* stream) {
+    return bn_step_syncbn<Astgcnn>(shape, args, bn_param_grad_scale, allreduce, user, stream);
+}
 int rulgnn_astgcnn_bn_running_update_f32(const rulgnn_astgcnn_shape* shape, float* bn_stats, const float* bn_batch, int64_t count,
                                          float momentum, int32_t from_moments, void* stream) {
-    if (!shape || count < 1) return RULGNN_EINVAL;
-    const int rc = check_ptrs({bn_stats, bn_batch});
-    if (rc != RULGNN_OK) return rc;
-    return astgcnn_bn_running_update(shape, bn_stats, bn_batch, count, momentum, from_moments, static_cast<hipStream_t>(stream));
+    RULGNN_TRY(check_bn_update(shape, bn_stats, bn_batch, count));
+    return Astgcnn::bn_running_update(shape, bn_stats, bn_batch, count, momentum, from_moments, static_cast<hipStream_t>(stream));
 }
 
+// ---- FC_STGNN -----------------------------------------------------------------------------------------
+int64_t rulgnn_fcstgnn_param_count(const rulgnn_fcstgnn_shape* shape) { return Fcstgnn::param_count(shape); }
+int64_t rulgnn_fcstgnn_bn_count(const rulgnn_fcstgnn_shape* shape) { return Fcstgnn::bn_count(shape); }
+size_t rulgnn_fcstgnn_workspace_bytes(const rulgnn_fcstgnn_shape* shape) { return Fcstgnn::workspace_bytes(shape); }
+
+int Fcstgnn::check_args(const Shape* shape, const Args* a, bool fwd, bool bwd) {
+    if (a->sample_offset < 0 || !(a->dropout_p >= 0.f && a->dropout_p < 1.f)) return RULGNN_EINVAL;
+    return check_bn_args(shape->batch, a, fwd, bwd);
+}
+
+int rulgnn_fcstgnn_forward_f32(const rulgnn_fcstgnn_shape* shape, const rulgnn_fcstgnn_args* args, void* stream) {
+    return step_forward<Fcstgnn>(shape, args, stream);
+}
+int rulgnn_fcstgnn_backward_f32(const rulgnn_fcstgnn_shape* shape, const rulgnn_fcstgnn_args* args, void* stream) {
+    return step_backward<Fcstgnn>(shape, args, stream);
+}
+int rulgnn_fcstgnn_fwdbwd_f32(const rulgnn_fcstgnn_shape* shape, const rulgnn_fcstgnn_args* args, const rulgnn_adam_args* opt,
+                              void* stream) {
+    return bn_step_fwdbwd<Fcstgnn>(shape, args, opt, stream);
+}
+int rulgnn_fcstgnn_fwdbwd_syncbn_f32(const rulgnn_fcstgnn_shape* shape, const rulgnn_fcstgnn_args* args, float bn_param_grad_scale,
+                                     rulgnn_allreduce_f64_fn allreduce, void* user, void* stream) {
+    return bn_step_syncbn<Fcstgnn>(shape, args, bn_param_grad_scale, allreduce, user, stream);
+}
+int rulgnn_fcstgnn_bn_running_update_f32(const rulgnn_fcstgnn_shape* shape, float* bn_stats, const float* bn_batch, float momentum,
+                                         int32_t from_moments, void* stream) {
+    RULGNN_TRY(check_bn_update(shape, bn_stats, bn_batch));
+    return Fcstgnn::bn_running_update(shape, bn_stats, bn_batch, momentum, from_moments, static_cast<hipStream_t>(stream));
+}
+
+// ---- ST_Conv ------------------------------------------------------------------------------------------
+int64_t rulgnn_stconv_param_count(const rulgnn_stconv_shape* shape) { return Stconv::param_count(shape); }
+size_t rulgnn_stconv_workspace_bytes(const rulgnn_stconv_shape* shape) { return Stconv::workspace_bytes(shape); }
+
+int Stconv::check_args(const Shape* shape, const Args* a, bool fwd, bool bwd) { return check_bn_args(shape->batch, a, fwd, bwd); }
+
+int rulgnn_stconv_forward_f32(const rulgnn_stconv_shape* shape, const rulgnn_astgcnn_args* args, void* stream) {
+    return step_forward<Stconv>(shape, args, stream);
+}
+int rulgnn_stconv_backward_f32(const rulgnn_stconv_shape* shape, const rulgnn_astgcnn_args* args, void* stream) {
+    return step_backward<Stconv>(shape, args, stream);
+}
+int rulgnn_stconv_fwdbwd_f32(const rulgnn_stconv_shape* shape, const rulgnn_astgcnn_args* args, const rulgnn_adam_args* opt,
+                             void* stream) {
+    return bn_step_fwdbwd<Stconv>(shape, args, opt, stream);
+}
+int rulgnn_stconv_bn_running_update_f32(const rulgnn_stconv_shape* shape, float* bn_stats, const float* bn_batch, int64_t count,
+                                        float momentum, int32_t from_moments, void* stream) {
+    RULGNN_TRY(check_bn_update(shape, bn_stats, bn_batch, count));
+    return Stconv::bn_running_update(shape, bn_stats, bn_batch, count, momentum, from_moments, static_cast<hipStream_t>(stream));
+}
 
 // ---- device step state (hipGraph-capturable training steps) -----------------------------------------------
 int rulgnn_step_state_set(void* step_state, uint64_t dropout_step, int64_t adam_step, void* stream) {
@@ -575,90 +640,6 @@ int rulgnn_adam_step_dev_f32(float* params, const float* grads, float* exp_avg, 
     if (rc != RULGNN_OK) return rc;
     return adam_step(params, grads, exp_avg, exp_avg_sq, n, 1, lr, beta1, beta2, eps, weight_decay, grad_scale,
                      static_cast<hipStream_t>(stream), step_state);
-}
-
-
-// ---- FC_STGNN -----------------------------------------------------------------------------------------
-int64_t rulgnn_fcstgnn_param_count(const rulgnn_fcstgnn_shape* shape) { return fcstgnn_param_count(shape); }
-int64_t rulgnn_fcstgnn_bn_count(const rulgnn_fcstgnn_shape* shape) { return fcstgnn_bn_count(shape); }
-size_t rulgnn_fcstgnn_workspace_bytes(const rulgnn_fcstgnn_shape* shape) { return fcstgnn_workspace_bytes(shape); }
-
-static int check_fcstgnn(const rulgnn_fcstgnn_shape* shape, const rulgnn_fcstgnn_args* a, bool forward, bool backward) {
-    if (!shape || !a) return RULGNN_EINVAL;
-    if (shape->batch < 1 || a->global_batch < shape->batch || a->sample_offset < 0) return RULGNN_EINVAL;
-    if (!(a->bn_moment_weight >= 0.f) || !(a->dropout_p >= 0.f && a->dropout_p < 1.f)) return RULGNN_EINVAL;
-    int rc = check_ptrs({a->x, a->params, a->pred, a->workspace});
-    if (rc != RULGNN_OK) return rc;
-    if (forward && !a->training) {
-        rc = check_ptrs({a->bn_stats});
-        if (rc != RULGNN_OK) return rc;
-    }
-    for (const void* p : {(const void*)a->y, (const void*)a->dpred, (const void*)a->bn_batch, (const void*)a->loss})
-        if (!opt_aligned(p)) return RULGNN_EALIGN;
-    if (backward) {
-        if (!a->training) return RULGNN_EINVAL;
-        rc = check_ptrs({a->grads});
-        if (rc != RULGNN_OK) return rc;
-        if (!a->dpred) {
-            rc = check_ptrs({a->y, a->loss});
-            if (rc != RULGNN_OK) return rc;
-        }
-    }
-    return RULGNN_OK;
-}
-
-int rulgnn_fcstgnn_forward_f32(const rulgnn_fcstgnn_shape* shape, const rulgnn_fcstgnn_args* args, void* stream) {
-    const int rc = check_fcstgnn(shape, args, true, false);
-    if (rc != RULGNN_OK) return rc;
-    return fcstgnn_run(shape, args, 1, static_cast<hipStream_t>(stream));
-}
-
-int rulgnn_fcstgnn_backward_f32(const rulgnn_fcstgnn_shape* shape, const rulgnn_fcstgnn_args* args, void* stream) {
-    const int rc = check_fcstgnn(shape, args, false, true);
-    if (rc != RULGNN_OK) return rc;
-    return fcstgnn_run(shape, args, 2, static_cast<hipStream_t>(stream));
-}
-
-int rulgnn_fcstgnn_fwdbwd_f32(const rulgnn_fcstgnn_shape* shape, const rulgnn_fcstgnn_args* args, const rulgnn_adam_args* opt,
-                              void* stream) {
-    int rc = check_fcstgnn(shape, args, true, true);
-    if (rc != RULGNN_OK) return rc;
-    if (args->dpred) return RULGNN_EINVAL;
-    if (opt && (rc = check_adam(opt, args->params)) != RULGNN_OK) return rc;
-    if (opt && opt->bn_stats && (!args->bn_batch || !opt_aligned(opt->bn_stats))) return RULGNN_EINVAL;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const bool tail_bn = opt && opt->bn_stats && args->training && args->bn_moment_weight == 0.f;
-    // (host-side step count: the step's last kernel applies the optimizer itself -- adam_device.hpp; a device step state keeps the launch)
-    AdamFuse fuse{};
-    fuse.p = nullptr;
-    const bool fused_adam = opt && !opt->step_state && opt->step >= 1;
-    if (fused_adam)
-        adam_fuse_args(&fuse, opt->params, opt->exp_avg, opt->exp_avg_sq, args->grads, opt->step, opt->lr, opt->beta1, opt->beta2, opt->eps,
-                       opt->weight_decay);
-    rc = fcstgnn_run(shape, args, 3, st, nullptr, tail_bn ? opt->bn_stats : nullptr, tail_bn ? opt->bn_momentum : 0.f, fused_adam ? &fuse : nullptr);
-    if (rc != RULGNN_OK || !opt) return rc;
-    if (!fused_adam)
-        rc = adam_tail(opt, args->grads, 0, fcstgnn_param_count(shape), st);
-    if (rc != RULGNN_OK || !opt->bn_stats || tail_bn) return rc;
-    return fcstgnn_bn_running_update(shape, opt->bn_stats, args->bn_batch, opt->bn_momentum, args->bn_moment_weight > 0.f ? 1 : 0, st);
-}
-
-int rulgnn_fcstgnn_fwdbwd_syncbn_f32(const rulgnn_fcstgnn_shape* shape, const rulgnn_fcstgnn_args* args, float bn_param_grad_scale,
-                                     rulgnn_allreduce_f64_fn allreduce, void* user, void* stream) {
-    const int rc = check_fcstgnn(shape, args, true, true);
-    if (rc != RULGNN_OK) return rc;
-    if (args->dpred) return RULGNN_EINVAL;
-    RULGNN_TRY(check_sync(bn_param_grad_scale, allreduce));
-    const SyncHook hook = {allreduce, user, bn_param_grad_scale};
-    return fcstgnn_run(shape, args, 3, static_cast<hipStream_t>(stream), &hook);
-}
-
-int rulgnn_fcstgnn_bn_running_update_f32(const rulgnn_fcstgnn_shape* shape, float* bn_stats, const float* bn_batch, float momentum,
-                                         int32_t from_moments, void* stream) {
-    if (!shape) return RULGNN_EINVAL;
-    const int rc = check_ptrs({bn_stats, bn_batch});
-    if (rc != RULGNN_OK) return rc;
-    return fcstgnn_bn_running_update(shape, bn_stats, bn_batch, momentum, from_moments, static_cast<hipStream_t>(stream));
 }
 
 
@@ -704,52 +685,6 @@ int rulgnn_bilstm_backward_f32(const rulgnn_bilstm_shape* shape, const rulgnn_bi
 }
 
 
-// ---- ST_Conv ------------------------------------------------------------------------------------------
-int64_t rulgnn_stconv_param_count(const rulgnn_stconv_shape* shape) { return stconv_param_count(shape); }
-size_t rulgnn_stconv_workspace_bytes(const rulgnn_stconv_shape* shape) { return stconv_workspace_bytes(shape); }
-
-static int check_stconv(const rulgnn_stconv_shape* shape, const rulgnn_astgcnn_args* a, bool forward, bool backward) {
-    if (!shape) return RULGNN_EINVAL;
-    rulgnn_astgcnn_shape probe{shape->batch, 1, 1, 1, 1};          // the argument checks do not depend on the model dimensions
-    return check_astgcnn(&probe, a, forward, backward);
-}
-
-int rulgnn_stconv_forward_f32(const rulgnn_stconv_shape* shape, const rulgnn_astgcnn_args* args, void* stream) {
-    const int rc = check_stconv(shape, args, true, false);
-    if (rc != RULGNN_OK) return rc;
-    return stconv_run(shape, args, 1, static_cast<hipStream_t>(stream));
-}
-
-int rulgnn_stconv_backward_f32(const rulgnn_stconv_shape* shape, const rulgnn_astgcnn_args* args, void* stream) {
-    const int rc = check_stconv(shape, args, false, true);
-    if (rc != RULGNN_OK) return rc;
-    return stconv_run(shape, args, 2, static_cast<hipStream_t>(stream));
-}
-
-int rulgnn_stconv_fwdbwd_f32(const rulgnn_stconv_shape* shape, const rulgnn_astgcnn_args* args, const rulgnn_adam_args* opt,
-                             void* stream) {
-    int rc = check_stconv(shape, args, true, true);
-    if (rc != RULGNN_OK) return rc;
-    if (args->dpred) return RULGNN_EINVAL;
-    if (opt && (rc = check_adam(opt, args->params)) != RULGNN_OK) return rc;
-    if (opt && opt->bn_stats && (!args->bn_batch || !opt_aligned(opt->bn_stats))) return RULGNN_EINVAL;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    rc = stconv_run(shape, args, 3, st);
-    if (rc != RULGNN_OK || !opt) return rc;
-    rc = adam_tail(opt, args->grads, 0, stconv_param_count(shape), st);
-    if (rc != RULGNN_OK || !opt->bn_stats) return rc;
-    return stconv_bn_running_update(shape, opt->bn_stats, args->bn_batch, shape->batch * (int64_t)shape->time_length, opt->bn_momentum,
-                                    args->bn_moment_weight > 0.f ? 1 : 0, st);
-}
-
-int rulgnn_stconv_bn_running_update_f32(const rulgnn_stconv_shape* shape, float* bn_stats, const float* bn_batch, int64_t count,
-                                        float momentum, int32_t from_moments, void* stream) {
-    if (!shape || count < 1) return RULGNN_EINVAL;
-    const int rc = check_ptrs({bn_stats, bn_batch});
-    if (rc != RULGNN_OK) return rc;
-    return stconv_bn_running_update(shape, bn_stats, bn_batch, count, momentum, from_moments, static_cast<hipStream_t>(stream));
-}
-
 size_t rulgnn_stgnn_workspace_bytes(const rulgnn_stgnn_shape* shape) { return stgnn_workspace_bytes(shape); }
 
 int rulgnn_stgnn_terms_f32(const rulgnn_stgnn_shape* shape, const float* x, float* terms, float* adj, void* stream) {
@@ -783,129 +718,88 @@ int rulgnn_stgnn_cheb_backward_f32(const rulgnn_stgnn_shape* shape, const float*
     return stgnn_cheb_backward(shape, terms, dout, dfilters, workspace, workspace_bytes, static_cast<hipStream_t>(stream));
 }
 
-int64_t rulgnn_stgnn_param_count(const rulgnn_stgnn_shape* shape) { return stgnn_param_count(shape); }
-size_t rulgnn_stgnn_step_workspace_bytes(const rulgnn_stgnn_shape* shape) { return stgnn_step_workspace_bytes(shape); }
+int64_t rulgnn_stgnn_param_count(const rulgnn_stgnn_shape* shape) { return Stgnn::param_count(shape); }
+size_t rulgnn_stgnn_step_workspace_bytes(const rulgnn_stgnn_shape* shape) { return Stgnn::workspace_bytes(shape); }
 
-static int check_stgnn(const rulgnn_stgnn_shape* shape, const rulgnn_stmsgcn_args* a, bool fwd, bool bwd) {
-    if (!shape || !a) return RULGNN_EINVAL;
-    if (stgnn_param_count(shape) < 0) return stgnn_step_workspace_bytes(shape) == 0 && shape->batch >= 0 ? RULGNN_EUNSUPPORTED : RULGNN_EINVAL;
-    int rc = check_ptrs({a->params, a->workspace});
-    if (rc != RULGNN_OK) return rc;
+int Stgnn::check_args(const Shape* shape, const Args* a, bool fwd, bool bwd) {
+    RULGNN_TRY(shape_status(shape));
+    RULGNN_TRY(check_ptrs({a->params, a->workspace}));
     if (shape->batch > 0) {
-        rc = check_ptrs({a->x});
-        if (rc != RULGNN_OK) return rc;
-        if (fwd && (rc = check_ptrs({a->pred})) != RULGNN_OK) return rc;
+        RULGNN_TRY(check_ptrs({a->x}));
+        if (fwd) RULGNN_TRY(check_ptrs({a->pred}));
     }
-    if (bwd) {
-        if ((rc = check_ptrs({a->grads})) != RULGNN_OK) return rc;
-        if (shape->batch > 0 && !a->dpred && !(fwd && a->y)) return RULGNN_EINVAL;     // needs d pred, or targets with a forward
-    }
-    return RULGNN_OK;
+    if (!bwd) return RULGNN_OK;
+    RULGNN_TRY(check_ptrs({a->grads}));
+    return shape->batch > 0 && !a->dpred && !(fwd && a->y) ? RULGNN_EINVAL : RULGNN_OK;     // needs d pred, or targets with a forward
 }
 
 int rulgnn_stgnn_forward_f32(const rulgnn_stgnn_shape* shape, const rulgnn_stmsgcn_args* args, void* stream) {
-    const int rc = check_stgnn(shape, args, true, false);
-    if (rc != RULGNN_OK) return rc;
-    return stgnn_run(shape, args, 1, static_cast<hipStream_t>(stream));
+    return step_forward<Stgnn>(shape, args, stream);
 }
-
 int rulgnn_stgnn_backward_f32(const rulgnn_stgnn_shape* shape, const rulgnn_stmsgcn_args* args, void* stream) {
-    const int rc = check_stgnn(shape, args, false, true);
-    if (rc != RULGNN_OK) return rc;
-    return stgnn_run(shape, args, 2, static_cast<hipStream_t>(stream));
+    return step_backward<Stgnn>(shape, args, stream);
 }
-
 int rulgnn_stgnn_fwdbwd_f32(const rulgnn_stgnn_shape* shape, const rulgnn_stmsgcn_args* args, const rulgnn_adam_args* opt, void* stream) {
-    RULGNN_TRY(check_stgnn(shape, args, true, true));
-    auto run = [&](hipStream_t st) { return stgnn_run(shape, args, 3, st); };
-    return fused_step_tail(args->dpred, false, opt, args->params, run, args->grads, 0, stgnn_param_count(shape), stream);
+    return step_fwdbwd<Stgnn>(shape, args, opt, stream);
 }
 
-// ---- STNet ----------------------------------------------------------------------------------------------------------------------
-int64_t rulgnn_stnet_param_count(const rulgnn_stnet_shape* shape) { return stnet_param_count(shape); }
-size_t rulgnn_stnet_workspace_bytes(const rulgnn_stnet_shape* shape) { return stnet_workspace_bytes(shape); }
+// ---- STNet ------------------------------------------------------------------------------------------
+int64_t rulgnn_stnet_param_count(const rulgnn_stnet_shape* shape) { return Stnet::param_count(shape); }
+size_t rulgnn_stnet_workspace_bytes(const rulgnn_stnet_shape* shape) { return Stnet::workspace_bytes(shape); }
 
-static int check_stnet(const rulgnn_stnet_shape* shape, const rulgnn_stnet_args* a, bool bwd) {
-    if (!shape || !a) return RULGNN_EINVAL;
-    if (stnet_param_count(shape) < 0) return RULGNN_EUNSUPPORTED;
-    return check_step_ptrs(a->params, a->workspace, a->x, a->pred, a->grads, a->y, a->dpred, shape->batch, bwd);
+int Stnet::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
+    RULGNN_TRY(shape_status(shape));
+    return check_step_ptrs(a, shape->batch, bwd);
 }
 
 int rulgnn_stnet_forward_f32(const rulgnn_stnet_shape* shape, const rulgnn_stnet_args* args, void* stream) {
-    const int rc = check_stnet(shape, args, false);
-    if (rc != RULGNN_OK) return rc;
-    return stnet_run(shape, args, 1, static_cast<hipStream_t>(stream));
+    return step_forward<Stnet>(shape, args, stream);
 }
-
 int rulgnn_stnet_backward_f32(const rulgnn_stnet_shape* shape, const rulgnn_stnet_args* args, void* stream) {
-    const int rc = check_stnet(shape, args, true);
-    if (rc != RULGNN_OK) return rc;
-    return stnet_run(shape, args, 2, static_cast<hipStream_t>(stream));
+    return step_backward<Stnet>(shape, args, stream);
 }
-
 int rulgnn_stnet_fwdbwd_f32(const rulgnn_stnet_shape* shape, const rulgnn_stnet_args* args, const rulgnn_adam_args* opt, void* stream) {
-    RULGNN_TRY(check_stnet(shape, args, true));
-    // cnn.{weight, bias} (the first 3 entries) have no gradient in the reference (`grad is None`): torch's Adam leaves them untouched
-    auto run = [&](hipStream_t st) { return stnet_run(shape, args, 3, st); };
-    return fused_step_tail(args->dpred, !args->y && shape->batch > 0, opt, args->params, run, args->grads, 3, stnet_param_count(shape) - 3, stream);
+    return step_fwdbwd<Stnet>(shape, args, opt, stream);
 }
 
-// ---- SAGCN ----------------------------------------------------------------------------------------------------------------------
-int64_t rulgnn_sagcn_param_count(const rulgnn_sagcn_shape* shape) { return sagcn_param_count(shape); }
-size_t rulgnn_sagcn_workspace_bytes(const rulgnn_sagcn_shape* shape) { return sagcn_workspace_bytes(shape); }
-int64_t rulgnn_sagcn_tap_offset(const rulgnn_sagcn_shape* shape, int32_t which) { return sagcn_tap_offset(shape, which); }
+// ---- SAGCN ------------------------------------------------------------------------------------------
+int64_t rulgnn_sagcn_param_count(const rulgnn_sagcn_shape* shape) { return Sagcn::param_count(shape); }
+size_t rulgnn_sagcn_workspace_bytes(const rulgnn_sagcn_shape* shape) { return Sagcn::workspace_bytes(shape); }
+int64_t rulgnn_sagcn_tap_offset(const rulgnn_sagcn_shape* shape, int32_t which) { return Sagcn::tap_offset(shape, which); }
 
-static int check_sagcn(const rulgnn_sagcn_shape* shape, const rulgnn_sagcn_args* a, bool bwd) {
-    if (!shape || !a) return RULGNN_EINVAL;
-    if (sagcn_param_count(shape) < 0) return RULGNN_EUNSUPPORTED;
-    return check_step_ptrs(a->params, a->workspace, a->x, a->pred, a->grads, a->y, a->dpred, shape->batch, bwd);
+int Sagcn::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
+    RULGNN_TRY(shape_status(shape));
+    return check_step_ptrs(a, shape->batch, bwd);
 }
 
 int rulgnn_sagcn_forward_f32(const rulgnn_sagcn_shape* shape, const rulgnn_sagcn_args* args, void* stream) {
-    const int rc = check_sagcn(shape, args, false);
-    if (rc != RULGNN_OK) return rc;
-    return sagcn_run(shape, args, 1, static_cast<hipStream_t>(stream));
+    return step_forward<Sagcn>(shape, args, stream);
 }
-
 int rulgnn_sagcn_backward_f32(const rulgnn_sagcn_shape* shape, const rulgnn_sagcn_args* args, void* stream) {
-    const int rc = check_sagcn(shape, args, true);
-    if (rc != RULGNN_OK) return rc;
-    return sagcn_run(shape, args, 2, static_cast<hipStream_t>(stream));
+    return step_backward<Sagcn>(shape, args, stream);
 }
-
 int rulgnn_sagcn_fwdbwd_f32(const rulgnn_sagcn_shape* shape, const rulgnn_sagcn_args* args, const rulgnn_adam_args* opt, void* stream) {
-    RULGNN_TRY(check_sagcn(shape, args, true));
-    auto run = [&](hipStream_t st) { return sagcn_run(shape, args, 3, st); };
-    return fused_step_tail(args->dpred, !args->y && shape->batch > 0, opt, args->params, run, args->grads, 0, sagcn_param_count(shape), stream);
+    return step_fwdbwd<Sagcn>(shape, args, opt, stream);
 }
 
-// ---- AGCN_TF --------------------------------------------------------------------------------------------------------------------
-int64_t rulgnn_agcntf_param_count(const rulgnn_agcntf_shape* shape) { return agcntf_param_count(shape); }
-size_t rulgnn_agcntf_workspace_bytes(const rulgnn_agcntf_shape* shape) { return agcntf_workspace_bytes(shape); }
-int64_t rulgnn_agcntf_tap_offset(const rulgnn_agcntf_shape* shape, int32_t which) { return agcntf_tap_offset(shape, which); }
+// ---- AGCN_TF ------------------------------------------------------------------------------------------
+int64_t rulgnn_agcntf_param_count(const rulgnn_agcntf_shape* shape) { return Agcntf::param_count(shape); }
+size_t rulgnn_agcntf_workspace_bytes(const rulgnn_agcntf_shape* shape) { return Agcntf::workspace_bytes(shape); }
+int64_t rulgnn_agcntf_tap_offset(const rulgnn_agcntf_shape* shape, int32_t which) { return Agcntf::tap_offset(shape, which); }
 
-static int check_agcntf(const rulgnn_agcntf_shape* shape, const rulgnn_agcntf_args* a, bool bwd) {
-    if (!shape || !a) return RULGNN_EINVAL;
-    if (agcntf_param_count(shape) < 0) return RULGNN_EUNSUPPORTED;
-    return check_step_ptrs(a->params, a->workspace, a->x, a->pred, a->grads, a->y, a->dpred, shape->batch, bwd);
+int Agcntf::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
+    RULGNN_TRY(shape_status(shape));
+    return check_step_ptrs(a, shape->batch, bwd);
 }
 
 int rulgnn_agcntf_forward_f32(const rulgnn_agcntf_shape* shape, const rulgnn_agcntf_args* args, void* stream) {
-    const int rc = check_agcntf(shape, args, false);
-    if (rc != RULGNN_OK) return rc;
-    return agcntf_run(shape, args, 1, static_cast<hipStream_t>(stream));
+    return step_forward<Agcntf>(shape, args, stream);
 }
-
 int rulgnn_agcntf_backward_f32(const rulgnn_agcntf_shape* shape, const rulgnn_agcntf_args* args, void* stream) {
-    const int rc = check_agcntf(shape, args, true);
-    if (rc != RULGNN_OK) return rc;
-    return agcntf_run(shape, args, 2, static_cast<hipStream_t>(stream));
+    return step_backward<Agcntf>(shape, args, stream);
 }
-
 int rulgnn_agcntf_fwdbwd_f32(const rulgnn_agcntf_shape* shape, const rulgnn_agcntf_args* args, const rulgnn_adam_args* opt, void* stream) {
-    RULGNN_TRY(check_agcntf(shape, args, true));
-    auto run = [&](hipStream_t st) { return agcntf_run(shape, args, 3, st); };
-    return fused_step_tail(args->dpred, !args->y && shape->batch > 0, opt, args->params, run, args->grads, 0, agcntf_param_count(shape), stream);
+    return step_fwdbwd<Agcntf>(shape, args, opt, stream);
 }
 
 int rulgnn_sgemm_mode(int32_t mode) {
@@ -914,36 +808,27 @@ int rulgnn_sgemm_mode(int32_t mode) {
     return prev;
 }
 
-// ---- STAGNN ---------------------------------------------------------------------------------------------------------------------
-int64_t rulgnn_stagnn_param_count(const rulgnn_stagnn_shape* shape) { return stagnn_param_count(shape); }
-int64_t rulgnn_stagnn_bn_state_count(const rulgnn_stagnn_shape* shape) { return stagnn_bn_state_count(shape); }
-size_t rulgnn_stagnn_workspace_bytes(const rulgnn_stagnn_shape* shape) { return stagnn_workspace_bytes(shape); }
-int64_t rulgnn_stagnn_tap_offset(const rulgnn_stagnn_shape* shape, int32_t which) { return stagnn_tap_offset(shape, which); }
+// ---- STAGNN ------------------------------------------------------------------------------------------
+int64_t rulgnn_stagnn_param_count(const rulgnn_stagnn_shape* shape) { return Stagnn::param_count(shape); }
+int64_t rulgnn_stagnn_bn_state_count(const rulgnn_stagnn_shape* shape) { return Stagnn::bn_state_count(shape); }
+size_t rulgnn_stagnn_workspace_bytes(const rulgnn_stagnn_shape* shape) { return Stagnn::workspace_bytes(shape); }
+int64_t rulgnn_stagnn_tap_offset(const rulgnn_stagnn_shape* shape, int32_t which) { return Stagnn::tap_offset(shape, which); }
 
-static int check_stagnn(const rulgnn_stagnn_shape* shape, const rulgnn_stagnn_args* a, bool bwd) {
-    if (!shape || !a) return RULGNN_EINVAL;
-    if (stagnn_param_count(shape) < 0) return RULGNN_EUNSUPPORTED;
+int Stagnn::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
+    RULGNN_TRY(shape_status(shape));
     RULGNN_TRY(check_ptrs({a->params, a->workspace, a->bn_state}));         // (bn_state ahead of x and pred)
-    RULGNN_TRY(check_step_ptrs(a->params, a->workspace, a->x, a->pred, a->grads, a->y, a->dpred, shape->batch, bwd));
+    RULGNN_TRY(check_step_ptrs(a, shape->batch, bwd));
     return bwd && !a->training ? RULGNN_EINVAL : RULGNN_OK;                // (the same code as a batch without d pred or targets)
 }
 
 int rulgnn_stagnn_forward_f32(const rulgnn_stagnn_shape* shape, const rulgnn_stagnn_args* args, void* stream) {
-    const int rc = check_stagnn(shape, args, false);
-    if (rc != RULGNN_OK) return rc;
-    return stagnn_run(shape, args, 1, static_cast<hipStream_t>(stream));
+    return step_forward<Stagnn>(shape, args, stream);
 }
-
 int rulgnn_stagnn_backward_f32(const rulgnn_stagnn_shape* shape, const rulgnn_stagnn_args* args, void* stream) {
-    const int rc = check_stagnn(shape, args, true);
-    if (rc != RULGNN_OK) return rc;
-    return stagnn_run(shape, args, 2, static_cast<hipStream_t>(stream));
+    return step_backward<Stagnn>(shape, args, stream);
 }
-
 int rulgnn_stagnn_fwdbwd_f32(const rulgnn_stagnn_shape* shape, const rulgnn_stagnn_args* args, const rulgnn_adam_args* opt, void* stream) {
-    RULGNN_TRY(check_stagnn(shape, args, true));
-    auto run = [&](hipStream_t st) { return stagnn_run(shape, args, 3, st); };
-    return fused_step_tail(args->dpred, !args->y && shape->batch > 0, opt, args->params, run, args->grads, 0, stagnn_param_count(shape), stream);
+    return step_fwdbwd<Stagnn>(shape, args, opt, stream);
 }
 
 // ---- plain GEMM -------------------------------------------------------------------------------------------------------------------
@@ -1022,40 +907,24 @@ int rulgnn_sgemm_splitk_f32(const float* A, int64_t sAm, int64_t sAk, const floa
     return sgemm_splitk_colsum(A, sAm, sAk, B, sBn, sBk, C, ldc, M, N, K, colsum, ones, part, st);
 }
 
-// ---- RGCNU ----------------------------------------------------------------------------------------------------------------------
-int64_t rulgnn_rgcnu_param_count(const rulgnn_rgcnu_shape* shape) { return rgcnu_param_count(shape); }
-size_t rulgnn_rgcnu_workspace_bytes(const rulgnn_rgcnu_shape* shape) { return rgcnu_workspace_bytes(shape); }
+// ---- RGCNU ------------------------------------------------------------------------------------------
+int64_t rulgnn_rgcnu_param_count(const rulgnn_rgcnu_shape* shape) { return Rgcnu::param_count(shape); }
+size_t rulgnn_rgcnu_workspace_bytes(const rulgnn_rgcnu_shape* shape) { return Rgcnu::workspace_bytes(shape); }
 
-static int check_rgcnu(const rulgnn_rgcnu_shape* shape, const rulgnn_rgcnu_args* a, bool fwd, bool bwd) {
-    if (!shape || !a) return RULGNN_EINVAL;
-    if (rgcnu_param_count(shape) < 0) return rgcnu_workspace_bytes(shape) == 0 && shape->batch >= 0 && shape->num_nodes >= 1 &&
-                                                     shape->time_length >= 1 && shape->hidden_dim >= 1 && shape->encoder_hidden_dim >= 1 &&
-                                                     shape->kernel_size >= 1
-                                                 ? RULGNN_EUNSUPPORTED
-                                                 : RULGNN_EINVAL;
+int Rgcnu::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
+    RULGNN_TRY(shape_status(shape));
     if (!(a->dropout_p >= 0.f && a->dropout_p < 1.f)) return RULGNN_EINVAL;
-    (void)fwd;
-    return check_step_ptrs(a->params, a->workspace, a->x, a->pred, a->grads, a->y, a->dpred, shape->batch, bwd);
+    return check_step_ptrs(a, shape->batch, bwd);
 }
 
 int rulgnn_rgcnu_forward_f32(const rulgnn_rgcnu_shape* shape, const rulgnn_rgcnu_args* args, void* stream) {
-    const int rc = check_rgcnu(shape, args, true, false);
-    if (rc != RULGNN_OK) return rc;
-    return rgcnu_run(shape, args, 1, static_cast<hipStream_t>(stream));
+    return step_forward<Rgcnu>(shape, args, stream);
 }
-
 int rulgnn_rgcnu_backward_f32(const rulgnn_rgcnu_shape* shape, const rulgnn_rgcnu_args* args, void* stream) {
-    const int rc = check_rgcnu(shape, args, false, true);
-    if (rc != RULGNN_OK) return rc;
-    return rgcnu_run(shape, args, 2, static_cast<hipStream_t>(stream));
+    return step_backward<Rgcnu>(shape, args, stream);
 }
-
 int rulgnn_rgcnu_fwdbwd_f32(const rulgnn_rgcnu_shape* shape, const rulgnn_rgcnu_args* args, const rulgnn_adam_args* opt, void* stream) {
-    RULGNN_TRY(check_rgcnu(shape, args, true, true));
-    // the second head (fc2, the last E*L + 1 entries) has no gradient in the reference (`grad is None`): torch's Adam leaves it untouched
-    const int64_t live = rgcnu_param_count(shape) - ((int64_t)shape->encoder_hidden_dim * shape->time_length + 1);
-    auto run = [&](hipStream_t st) { return rgcnu_run(shape, args, 3, st); };
-    return fused_step_tail(args->dpred, !args->y && shape->batch > 0, opt, args->params, run, args->grads, 0, live, stream);
+    return step_fwdbwd<Rgcnu>(shape, args, opt, stream);
 }
 
 static int check_gru_fwd(const rulgnn_gru_shape* shape, const rulgnn_gru_args* a) {
@@ -1094,114 +963,79 @@ int rulgnn_gru_persistent_backward_f32(const rulgnn_gru_shape* shape, const rulg
     return gru_persistent_backward(shape, args, static_cast<hipStream_t>(stream));
 }
 
-// ---- GRU_CM ---------------------------------------------------------------------------------------------------------------------
-int64_t rulgnn_grucm_param_count(const rulgnn_grucm_shape* shape) { return grucm_param_count(shape); }
-size_t rulgnn_grucm_workspace_bytes(const rulgnn_grucm_shape* shape) { return grucm_workspace_bytes(shape); }
+// ---- GRU_CM ------------------------------------------------------------------------------------------
+int64_t rulgnn_grucm_param_count(const rulgnn_grucm_shape* shape) { return Grucm::param_count(shape); }
+size_t rulgnn_grucm_workspace_bytes(const rulgnn_grucm_shape* shape) { return Grucm::workspace_bytes(shape); }
 
-static int check_grucm(const rulgnn_grucm_shape* shape, const rulgnn_grucm_args* a, bool bwd) {
-    if (!shape || !a) return RULGNN_EINVAL;
-    if (grucm_param_count(shape) < 0 || grucm_workspace_bytes(shape) == 0)
-        return shape->batch >= 0 && shape->num_nodes >= 2 && shape->time_length >= 1 && shape->gru_hidden_dim >= 1 ? RULGNN_EUNSUPPORTED
-                                                                                                                 : RULGNN_EINVAL;
+int Grucm::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
+    RULGNN_TRY(shape_status(shape));
     if (a->global_batch < shape->batch || a->sample_offset < 0) return RULGNN_EINVAL;
     for (int site = 0; site < 3; ++site)
         if (!(a->dropout_p[site] >= 0.f && a->dropout_p[site] < 1.f)) return RULGNN_EINVAL;
     if (a->gru_path != RULGNN_GRUCM_GRU_AUTO && a->gru_path != RULGNN_GRUCM_GRU_STEP_LOOP && a->gru_path != RULGNN_GRUCM_GRU_PERSISTENT)
         return RULGNN_EINVAL;
-    RULGNN_TRY(check_fwd_ptrs(a->params, a->workspace, a->x, a->pred, shape->batch));
+    RULGNN_TRY(check_fwd_ptrs(a, shape->batch));
     for (const void* p : {(const void*)a->y, (const void*)a->dpred, (const void*)a->loss})
         if (!opt_aligned(p)) return RULGNN_EALIGN;
-    return bwd ? check_bwd_ptrs(a->grads, a->y, a->dpred, shape->batch) : RULGNN_OK;
+    return bwd ? check_bwd_ptrs(a, shape->batch) : RULGNN_OK;
 }
 
 int rulgnn_grucm_forward_f32(const rulgnn_grucm_shape* shape, const rulgnn_grucm_args* args, void* stream) {
-    const int rc = check_grucm(shape, args, false);
-    if (rc != RULGNN_OK) return rc;
-    return grucm_run(shape, args, 1, static_cast<hipStream_t>(stream));
+    return step_forward<Grucm>(shape, args, stream);
 }
-
 int rulgnn_grucm_backward_f32(const rulgnn_grucm_shape* shape, const rulgnn_grucm_args* args, void* stream) {
-    const int rc = check_grucm(shape, args, true);
-    if (rc != RULGNN_OK) return rc;
-    return grucm_run(shape, args, 2, static_cast<hipStream_t>(stream));
+    return step_backward<Grucm>(shape, args, stream);
 }
-
 int rulgnn_grucm_fwdbwd_f32(const rulgnn_grucm_shape* shape, const rulgnn_grucm_args* args, const rulgnn_adam_args* opt, void* stream) {
-    RULGNN_TRY(check_grucm(shape, args, true));
-    auto run = [&](hipStream_t st) { return grucm_run(shape, args, 3, st); };
-    return fused_step_tail(args->dpred, !args->y && shape->batch > 0, opt, args->params, run, args->grads, 0, grucm_param_count(shape), stream);
+    return step_fwdbwd<Grucm>(shape, args, opt, stream);
 }
 
-int64_t rulgnn_hiercorrpool_param_count(const rulgnn_hiercorrpool_shape* shape) { return hiercorrpool_param_count(shape); }
-int64_t rulgnn_hiercorrpool_bn_state_count(const rulgnn_hiercorrpool_shape* shape) { return hiercorrpool_bn_state_count(shape); }
-size_t rulgnn_hiercorrpool_workspace_bytes(const rulgnn_hiercorrpool_shape* shape) { return hiercorrpool_workspace_bytes(shape); }
-int64_t rulgnn_hiercorrpool_tap_offset(const rulgnn_hiercorrpool_shape* shape, int32_t which) { return hiercorrpool_tap_offset(shape, which); }
+// ---- HierCorrPool ------------------------------------------------------------------------------------------
+int64_t rulgnn_hiercorrpool_param_count(const rulgnn_hiercorrpool_shape* shape) { return Hiercorrpool::param_count(shape); }
+int64_t rulgnn_hiercorrpool_bn_state_count(const rulgnn_hiercorrpool_shape* shape) { return Hiercorrpool::bn_state_count(shape); }
+size_t rulgnn_hiercorrpool_workspace_bytes(const rulgnn_hiercorrpool_shape* shape) { return Hiercorrpool::workspace_bytes(shape); }
+int64_t rulgnn_hiercorrpool_tap_offset(const rulgnn_hiercorrpool_shape* shape, int32_t which) { return Hiercorrpool::tap_offset(shape, which); }
 
-static int check_hiercorrpool(const rulgnn_hiercorrpool_shape* shape, const rulgnn_hiercorrpool_args* a, bool bwd) {
-    if (!shape || !a) return RULGNN_EINVAL;
-    if (hiercorrpool_param_count(shape) < 0)          // (a negative extent is invalid, anything else outside the limits unsupported)
-        return shape->batch >= 0 && shape->patch_size >= 0 && shape->num_patch >= 0 && shape->hidden_dim >= 0 && shape->embedding_dim >= 0 &&
-                       shape->num_nodes >= 0 && shape->encoder_conv_kernel >= 0 && shape->num_nodes_out >= 0
-                   ? RULGNN_EUNSUPPORTED
-                   : RULGNN_EINVAL;
+int Hiercorrpool::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
+    RULGNN_TRY(shape_status(shape));
     if (a->global_batch < shape->batch || a->sample_offset < 0) return RULGNN_EINVAL;
     if (!(a->dropout_p >= 0.f && a->dropout_p < 1.f)) return RULGNN_EINVAL;
     RULGNN_TRY(check_ptrs({a->params, a->workspace, a->bn_state}));
-    RULGNN_TRY(check_step_ptrs(a->params, a->workspace, a->x, a->pred, a->grads, a->y, a->dpred, shape->batch, bwd));
+    RULGNN_TRY(check_step_ptrs(a, shape->batch, bwd));
     return bwd && !a->training ? RULGNN_EINVAL : RULGNN_OK;
 }
 
 int rulgnn_hiercorrpool_forward_f32(const rulgnn_hiercorrpool_shape* shape, const rulgnn_hiercorrpool_args* args, void* stream) {
-    const int rc = check_hiercorrpool(shape, args, false);
-    if (rc != RULGNN_OK) return rc;
-    return hiercorrpool_run(shape, args, 1, static_cast<hipStream_t>(stream));
+    return step_forward<Hiercorrpool>(shape, args, stream);
 }
-
 int rulgnn_hiercorrpool_backward_f32(const rulgnn_hiercorrpool_shape* shape, const rulgnn_hiercorrpool_args* args, void* stream) {
-    const int rc = check_hiercorrpool(shape, args, true);
-    if (rc != RULGNN_OK) return rc;
-    return hiercorrpool_run(shape, args, 2, static_cast<hipStream_t>(stream));
+    return step_backward<Hiercorrpool>(shape, args, stream);
+}
+int rulgnn_hiercorrpool_fwdbwd_f32(const rulgnn_hiercorrpool_shape* shape, const rulgnn_hiercorrpool_args* args, const rulgnn_adam_args* opt, void* stream) {
+    return step_fwdbwd<Hiercorrpool>(shape, args, opt, stream);
 }
 
-int rulgnn_hiercorrpool_fwdbwd_f32(const rulgnn_hiercorrpool_shape* shape, const rulgnn_hiercorrpool_args* args, const rulgnn_adam_args* opt,
-                                   void* stream) {
-    RULGNN_TRY(check_hiercorrpool(shape, args, true));
-    auto run = [&](hipStream_t st) { return hiercorrpool_run(shape, args, 3, st); };
-    return fused_step_tail(args->dpred, !args->y && shape->batch > 0, opt, args->params, run, args->grads, 0, hiercorrpool_param_count(shape), stream);
-}
+// ---- LOGO ------------------------------------------------------------------------------------------
+int64_t rulgnn_logo_param_count(const rulgnn_logo_shape* shape) { return Logo::param_count(shape); }
+size_t rulgnn_logo_workspace_bytes(const rulgnn_logo_shape* shape) { return Logo::workspace_bytes(shape); }
+int64_t rulgnn_logo_tap_offset(const rulgnn_logo_shape* shape, int32_t which) { return Logo::tap_offset(shape, which); }
 
-int64_t rulgnn_logo_param_count(const rulgnn_logo_shape* shape) { return logo_param_count(shape); }
-size_t rulgnn_logo_workspace_bytes(const rulgnn_logo_shape* shape) { return logo_workspace_bytes(shape); }
-int64_t rulgnn_logo_tap_offset(const rulgnn_logo_shape* shape, int32_t which) { return logo_tap_offset(shape, which); }
-
-static int check_logo(const rulgnn_logo_shape* shape, const rulgnn_logo_args* a, bool bwd) {
-    if (!shape || !a) return RULGNN_EINVAL;
-    if (logo_workspace_bytes(shape) == 0)          // (a negative extent is invalid, anything else outside the limits unsupported)
-        return shape->batch >= 0 && shape->patch_size >= 0 && shape->num_patch >= 0 && shape->num_nodes >= 0 && shape->hidden_dim >= 0
-                   ? RULGNN_EUNSUPPORTED
-                   : RULGNN_EINVAL;
+int Logo::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
+    RULGNN_TRY(shape_status(shape));
     if (a->global_batch < shape->batch) return RULGNN_EINVAL;
     if (!(a->dropout_p >= 0.f && a->dropout_p < 1.f)) return RULGNN_EINVAL;
     if (!opt_aligned(a->loss) || !opt_aligned(a->loss_gl)) return RULGNN_EALIGN;
-    return check_step_ptrs(a->params, a->workspace, a->x, a->pred, a->grads, a->y, a->dpred, shape->batch, bwd);
+    return check_step_ptrs(a, shape->batch, bwd);
 }
 
 int rulgnn_logo_forward_f32(const rulgnn_logo_shape* shape, const rulgnn_logo_args* args, void* stream) {
-    const int rc = check_logo(shape, args, false);
-    if (rc != RULGNN_OK) return rc;
-    return logo_run(shape, args, 1, static_cast<hipStream_t>(stream));
+    return step_forward<Logo>(shape, args, stream);
 }
-
 int rulgnn_logo_backward_f32(const rulgnn_logo_shape* shape, const rulgnn_logo_args* args, void* stream) {
-    const int rc = check_logo(shape, args, true);
-    if (rc != RULGNN_OK) return rc;
-    return logo_run(shape, args, 2, static_cast<hipStream_t>(stream));
+    return step_backward<Logo>(shape, args, stream);
 }
-
 int rulgnn_logo_fwdbwd_f32(const rulgnn_logo_shape* shape, const rulgnn_logo_args* args, const rulgnn_adam_args* opt, void* stream) {
-    RULGNN_TRY(check_logo(shape, args, true));
-    auto run = [&](hipStream_t st) { return logo_run(shape, args, 3, st); };
-    return fused_step_tail(args->dpred, !args->y && shape->batch > 0, opt, args->params, run, args->grads, 0, logo_param_count(shape), stream);
+    return step_fwdbwd<Logo>(shape, args, opt, stream);
 }
 
 size_t rulgnn_rul_metrics_workspace_bytes(int64_t n) { return rul_metrics_workspace_bytes(n); }

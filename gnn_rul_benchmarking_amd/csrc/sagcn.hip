@@ -627,17 +627,23 @@ inline unsigned sg_grid(int64_t n) {
 
 }  // namespace
 
-int64_t sagcn_param_count(const rulgnn_sagcn_shape* s) {
+// RULGNN_OK, or the code every entry returns for a refused shape: unsupported for anything sg_geometry refuses, a negative batch included.
+int Sagcn::shape_status(const Shape* s) {
+    SgGeom g;
+    return sg_geometry(s, &g) == RULGNN_OK ? RULGNN_OK : RULGNN_EUNSUPPORTED;
+}
+
+int64_t Sagcn::param_count(const Shape* s) {
     SgGeom g;
     return sg_geometry(s, &g) == RULGNN_OK ? g.pcount : -1;
 }
 
-size_t sagcn_workspace_bytes(const rulgnn_sagcn_shape* s) {
+size_t Sagcn::workspace_bytes(const Shape* s) {
     SgGeom g;
     return sg_geometry(s, &g) == RULGNN_OK ? (size_t)g.total * sizeof(float) : 0;
 }
 
-int64_t sagcn_tap_offset(const rulgnn_sagcn_shape* s, int which) {
+int64_t Sagcn::tap_offset(const Shape* s, int which) {
     SgGeom g;
     if (sg_geometry(s, &g) != RULGNN_OK) return -1;
     switch (which) {
@@ -664,13 +670,8 @@ int sagcn_features(int64_t B, int P, int n, const float* x, float* raw, float* f
     return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
 }
 
-#define SG_LAUNCH_OK()                                           \
-    do {                                                         \
-        if (hipGetLastError() != hipSuccess) return RULGNN_EHIP; \
-    } while (0)
-
 // mode bit 0: forward, bit 1: backward (after a forward with the same args / workspace)
-int sagcn_run(const rulgnn_sagcn_shape* s, const rulgnn_sagcn_args* a, int mode, hipStream_t st) {
+int Sagcn::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
     SgGeom g;
     RULGNN_TRY(sg_geometry(s, &g));
     if (a->workspace_bytes < (size_t)g.total * sizeof(float)) return RULGNN_EWORKSPACE;
@@ -701,7 +702,7 @@ int sagcn_run(const rulgnn_sagcn_shape* s, const rulgnn_sagcn_args* a, int mode,
         } else
         hipLaunchKernelGGL(sg_graph_kernel, dim3((unsigned)(g.B < 4096 ? g.B : 4096)), dim3(GB), lds2, st, g, (const float*)(ws + g.w_raw),
                            ws + g.w_feat, ws + g.w_ax);
-        SG_LAUNCH_OK();
+        RULGNN_LAUNCH_OK();
         // gcn1: [R, 40] x W1^T
         RULGNN_TRY(sgemm(ws + g.w_ax, SG_F, 1, prm + g.o_w1, SG_F, 1, h1, H, R, H, SG_F, false, st));
         hipLaunchKernelGGL(sg_bias_cols_kernel, dim3(sg_grid(RH)), dim3(GB), 0, st, h1, prm + g.o_b1, (int64_t)R, H, 1);
@@ -713,7 +714,7 @@ int sagcn_run(const rulgnn_sagcn_shape* s, const rulgnn_sagcn_args* a, int mode,
             RULGNN_TRY(sgemm(u[i], H, 1, prm + g.o_wl[i], H, 1, hh[i + 1], H, R, H, H, false, st));
             hipLaunchKernelGGL(sg_bias_cols_kernel, dim3(sg_grid(RH)), dim3(GB), 0, st, hh[i + 1], prm + g.o_bl[i], (int64_t)R, H, 1);
         }
-        SG_LAUNCH_OK();
+        RULGNN_LAUNCH_OK();
         // attention: S [Ah, B*H] = tanh(Wt [Ah, P] x h3 + bt[a]) ; logits [P, B*H] = Ws [P, Ah] x S (+ bs[p] in the head kernel)
         RULGNN_TRY(sgemm(prm + g.o_wt, P, 1, hh[2], 1, BH, S, BH, Ah, BH, P, false, st));
         hipLaunchKernelGGL(sg_bias_rows_kernel, dim3(sg_grid((int64_t)Ah * BH)), dim3(GB), 0, st, S, prm + g.o_bt, Ah, (int64_t)BH, 2);
@@ -726,7 +727,7 @@ int sagcn_run(const rulgnn_sagcn_shape* s, const rulgnn_sagcn_args* a, int mode,
                                inv_gb);
         }
         if (a->y && a->loss) (void)block_sum((const float*)(ws + g.w_sq), g.B, a->loss, st);
-        SG_LAUNCH_OK();
+        RULGNN_LAUNCH_OK();
     }
     if (mode & 2) {
         if (!a->grads) return RULGNN_EINVAL;
@@ -742,7 +743,7 @@ int sagcn_run(const rulgnn_sagcn_shape* s, const rulgnn_sagcn_args* a, int mode,
                            gr + g.o_wfc);
         RULGNN_TRY(sgemm_splitk(dpred, 0, 1, one, 0, 0, gr + g.o_bfc, 1, 1, 1, (int)g.B, false, split, st));
         hipLaunchKernelGGL(sg_attn_head_bwd_kernel, dim3(sg_grid(BH)), dim3(GB), 0, st, g, (const float*)attn, (const float*)hh[2], prm, dpred, dA, dB);
-        SG_LAUNCH_OK();
+        RULGNN_LAUNCH_OK();
         RULGNN_TRY(sgemm_splitk(dB, BH, 1, S, BH, 1, gr + g.o_ws, Ah, P, Ah, BH, false, split, st));
         hipLaunchKernelGGL(sg_rowsum_kernel, dim3(P, SG_ROW_SLICES), dim3(GB), 0, st, (const float*)dB, (int64_t)BH, ws + g.w_rowpart);
         hipLaunchKernelGGL(sg_rowsum_finish_kernel, dim3((P + GB - 1) / GB), dim3(GB), 0, st, (const float*)(ws + g.w_rowpart), P, gr + g.o_bs);
@@ -754,7 +755,7 @@ int sagcn_run(const rulgnn_sagcn_shape* s, const rulgnn_sagcn_args* a, int mode,
         hipLaunchKernelGGL(sg_rowsum_finish_kernel, dim3((Ah + GB - 1) / GB), dim3(GB), 0, st, (const float*)(ws + g.w_rowpart), Ah, gr + g.o_bt);
         // d h3 += Wt^T x d(tanh input)
         RULGNN_TRY(sgemm(prm + g.o_wt, 1, P, ds, 1, BH, dA, BH, P, BH, Ah, true, st));
-        SG_LAUNCH_OK();
+        RULGNN_LAUNCH_OK();
         float* d = dA;
         float* other = dB;
         for (int i = 1; i >= 0; --i) {
@@ -768,12 +769,12 @@ int sagcn_run(const rulgnn_sagcn_shape* s, const rulgnn_sagcn_args* a, int mode,
             hipLaunchKernelGGL(sg_rowsum_finish_kernel, dim3((P + GB - 1) / GB), dim3(GB), 0, st, (const float*)(ws + g.w_rowpart), P, gr + g.o_bp[i]);
             // d h_in [P, B*H] = Wp^T x d U
             RULGNN_TRY(sgemm(prm + g.o_wp[i], 1, P, other, 1, BH, d, BH, P, BH, P, false, st));
-            SG_LAUNCH_OK();
+            RULGNN_LAUNCH_OK();
         }
         hipLaunchKernelGGL(sg_relu_bwd_kernel, dim3(sg_grid(RH)), dim3(GB), 0, st, d, (const float*)h1, RH);
         RULGNN_TRY(sgemm_splitk(d, 1, H, ws + g.w_ax, 1, SG_F, gr + g.o_w1, SG_F, H, SG_F, R, false, split, st));
         RULGNN_TRY(sgemm_splitk(one, 0, 0, d, 1, H, gr + g.o_b1, H, 1, H, R, false, split, st));
-        SG_LAUNCH_OK();
+        RULGNN_LAUNCH_OK();
     }
     return RULGNN_OK;
 }

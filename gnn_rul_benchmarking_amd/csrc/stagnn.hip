@@ -1479,22 +1479,28 @@ inline int tg_head_groups(const TgGeom& g, bool bwd) {
 
 }  // namespace
 
-int64_t stagnn_param_count(const rulgnn_stagnn_shape* s) {
+// RULGNN_OK, or the code every entry returns for a refused shape: unsupported for anything tg_geometry refuses, a negative batch included.
+int Stagnn::shape_status(const Shape* s) {
+    TgGeom g;
+    return tg_geometry(s, &g) == RULGNN_OK ? RULGNN_OK : RULGNN_EUNSUPPORTED;
+}
+
+int64_t Stagnn::param_count(const Shape* s) {
     TgGeom g;
     return tg_geometry(s, &g) == RULGNN_OK ? g.pcount : -1;
 }
 
-int64_t stagnn_bn_state_count(const rulgnn_stagnn_shape* s) {
+int64_t Stagnn::bn_state_count(const Shape* s) {
     TgGeom g;
     return tg_geometry(s, &g) == RULGNN_OK ? g.bn_total : -1;
 }
 
-size_t stagnn_workspace_bytes(const rulgnn_stagnn_shape* s) {
+size_t Stagnn::workspace_bytes(const Shape* s) {
     TgGeom g;
     return tg_geometry(s, &g) == RULGNN_OK ? (size_t)g.total * sizeof(float) : 0;
 }
 
-int64_t stagnn_tap_offset(const rulgnn_stagnn_shape* s, int which) {
+int64_t Stagnn::tap_offset(const Shape* s, int which) {
     TgGeom g;
     if (tg_geometry(s, &g) != RULGNN_OK) return -1;
     switch (which) {
@@ -1508,13 +1514,8 @@ int64_t stagnn_tap_offset(const rulgnn_stagnn_shape* s, int which) {
     }
 }
 
-#define TG_LAUNCH_OK()                                           \
-    do {                                                         \
-        if (hipGetLastError() != hipSuccess) return RULGNN_EHIP; \
-    } while (0)
-
 // mode bit 0: forward, bit 1: backward (after a TRAINING forward with the same args / workspace)
-int stagnn_run(const rulgnn_stagnn_shape* s, const rulgnn_stagnn_args* a, int mode, hipStream_t st) {
+int Stagnn::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
     TgGeom g;
     RULGNN_TRY(tg_geometry(s, &g));
     if (a->workspace_bytes < (size_t)g.total * sizeof(float)) return RULGNN_EWORKSPACE;
@@ -1533,7 +1534,7 @@ int stagnn_run(const rulgnn_stagnn_shape* s, const rulgnn_stagnn_args* a, int mo
         const size_t lg = tg_lds_graph_fwd(g, G);
         RULGNN_TRY(allow_dynamic_lds(tg_graph_fwd_kernel, lg));
         hipLaunchKernelGGL(tg_graph_fwd_kernel, grid, dim3(TB * G), lg, st, g, G, a->x, prm, ws);
-        TG_LAUNCH_OK();
+        RULGNN_LAUNCH_OK();
         for (int l = 0; l < 2; ++l) {
             const int Ci = g.Ci[l], Co = g.Co[l];
             const size_t l1 = sizeof(float) * ((size_t)Ci * TP + (size_t)Co * TP + 2 * (size_t)Co * Ci);
@@ -1554,11 +1555,11 @@ int stagnn_run(const rulgnn_stagnn_shape* s, const rulgnn_stagnn_args* a, int mo
             } else
             hipLaunchKernelGGL(tg_mid_fwd_kernel, grid, blk, l2, st, g, l, stage_in[l], prm, (const float*)a->bn_state, ws, training);
             hipLaunchKernelGGL(tg_end_fwd_kernel, grid, blk, l3, st, g, l, prm, (const float*)a->bn_state, ws, training, a->y, a->pred, inv_gb);
-            TG_LAUNCH_OK();
+            RULGNN_LAUNCH_OK();
         }
         if (training && a->update_running_stats) hipLaunchKernelGGL(tg_running_kernel, dim3(4), dim3(TB), 0, st, g, (const float*)ws, a->bn_state);
         if (a->y && a->loss) (void)block_sum((const float*)(ws + g.w_sq), g.B, a->loss, st);
-        TG_LAUNCH_OK();
+        RULGNN_LAUNCH_OK();
     }
     if (mode & 2) {
         if (!a->grads) return RULGNN_EINVAL;
@@ -1586,13 +1587,13 @@ int stagnn_run(const rulgnn_stagnn_shape* s, const rulgnn_stagnn_args* a, int mo
                 hipLaunchKernelGGL(tg_conv1_bwd_mx_kernel, grid, blk, l1m, st, g, l, stage_in[l], prm, (const float*)a->bn_state, ws, ws + g.w_dxin[l]);
             } else
             hipLaunchKernelGGL(tg_conv1_bwd_kernel, grid, blk, l1, st, g, l, stage_in[l], prm, (const float*)a->bn_state, ws, ws + g.w_dxin[l]);
-            TG_LAUNCH_OK();
+            RULGNN_LAUNCH_OK();
         }
         const int G = tg_head_groups(g, true);
         const size_t lg = tg_lds_graph_bwd(g, G);
         RULGNN_TRY(allow_dynamic_lds(tg_graph_bwd_kernel, lg));
         hipLaunchKernelGGL(tg_graph_bwd_kernel, grid, dim3(TB * G), lg, st, g, G, prm, ws);
-        TG_LAUNCH_OK();
+        RULGNN_LAUNCH_OK();
         RULGNN_TRY(rows_sum(ws + g.w_gpart, g.nblk, g.pcount, g.pcount, a->grads, st));
     }
     return RULGNN_OK;

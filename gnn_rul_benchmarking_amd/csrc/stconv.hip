@@ -5,7 +5,7 @@
 // Reference: models/ST_Conv/Model.py (pcc_graph_construction :10-28, MPNN_mk :30-55, CNNLayer :58-71, TemporalConvNet :81-155,
 // ST_Conv_model :173-222) and algorithms/algorithms.py:195-220.  The reference's forward uses the "_1" modules for both
 // branches (Model.py:196-206): the two branches are equal, so one branch is computed and its gradient carries both uses; the
-// BatchNorm running statistics are updated twice per training forward (stconv_bn_running_update applies the momentum twice).
+// BatchNorm running statistics are updated twice per training forward (Stconv::bn_running_update applies the momentum twice).
 //
 // The TCN is the block shared with ASTGCNN (tcn_nodes.hpp); the theta projection and the weight gradients with a long
 // reduction are MFMA GEMMs (sgemm_mfma.hpp); the rest is one workgroup per sample with the [nodes x time] tile in LDS.
@@ -403,12 +403,12 @@ void sc_ws_layout(const ScGeom& g, ScWs* w) {
 
 }  // namespace
 
-int64_t stconv_param_count(const rulgnn_stconv_shape* s) {
+int64_t Stconv::param_count(const Shape* s) {
     ScGeom g;
     return sc_geometry(s, &g) == RULGNN_OK ? g.nparam : -1;
 }
 
-size_t stconv_workspace_bytes(const rulgnn_stconv_shape* s) {
+size_t Stconv::workspace_bytes(const Shape* s) {
     ScGeom g;
     if (sc_geometry(s, &g) != RULGNN_OK) return 0;
     ScWs w;
@@ -417,7 +417,7 @@ size_t stconv_workspace_bytes(const rulgnn_stconv_shape* s) {
 }
 
 // mode bit 0: forward (args->training: batch / running statistics), bit 1: backward.  The args struct is ASTGCNN's.
-int stconv_run(const rulgnn_stconv_shape* s, const rulgnn_astgcnn_args* a, int mode, hipStream_t st) {
+int Stconv::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
     ScGeom g;
     RULGNN_TRY(sc_geometry(s, &g));
     ScWs w;
@@ -490,7 +490,7 @@ int stconv_run(const rulgnn_stconv_shape* s, const rulgnn_astgcnn_args* a, int m
     return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
 }
 
-int stconv_bn_running_update(const rulgnn_stconv_shape* s, float* bn_stats, const float* bn_batch, int64_t count, float momentum,
+int Stconv::bn_running_update(const Shape* s, float* bn_stats, const float* bn_batch, int64_t count, float momentum,
                              int from_moments, hipStream_t st) {
     ScGeom g;
     RULGNN_TRY(sc_geometry(s, &g));

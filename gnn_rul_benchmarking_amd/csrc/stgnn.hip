@@ -276,13 +276,21 @@ inline unsigned gn_blocks(int64_t n) {
 
 }  // namespace
 
-int64_t stgnn_param_count(const rulgnn_stgnn_shape* s) {
+// RULGNN_OK, or the code the step entries return for a refused shape: invalid for a negative batch, unsupported for anything else
+// gn_geometry refuses -- its other invalid extents (top_k > num_nodes, a dimension below 1) included.
+int Stgnn::shape_status(const Shape* s) {
+    GnGeom g;
+    if (gn_geometry(s, &g) == RULGNN_OK) return RULGNN_OK;
+    return s->batch < 0 ? RULGNN_EINVAL : RULGNN_EUNSUPPORTED;
+}
+
+int64_t Stgnn::param_count(const Shape* s) {
     GnGeom g;
     if (gn_geometry(s, &g) != RULGNN_OK) return -1;
     return gn_offsets(g).total;
 }
 
-size_t stgnn_step_workspace_bytes(const rulgnn_stgnn_shape* s) {
+size_t Stgnn::workspace_bytes(const Shape* s) {
     GnGeom g;
     if (gn_geometry(s, &g) != RULGNN_OK) return 0;
     GnWs w;
@@ -292,7 +300,7 @@ size_t stgnn_step_workspace_bytes(const rulgnn_stgnn_shape* s) {
 
 // mode bit 0: forward (pred; with y also d pred and the loss terms), bit 1: backward (gradients; d pred from args->dpred or
 // from the forward of this call)
-int stgnn_run(const rulgnn_stgnn_shape* s, const rulgnn_stmsgcn_args* a, int mode, hipStream_t st) {
+int Stgnn::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
     GnGeom g;
     RULGNN_TRY(gn_geometry(s, &g));
     GnWs w;

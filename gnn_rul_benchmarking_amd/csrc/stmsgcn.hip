@@ -1647,12 +1647,12 @@ static void dispatch_gru(const MsgGeom& g, const MsgWs& w, const Workspace& ws, 
 
 }  // namespace
 
-int64_t stmsgcn_param_count(const rulgnn_stmsgcn_shape* s) {
+int64_t Stmsgcn::param_count(const Shape* s) {
     MsgGeom g;
     return msg_geometry(s, &g) == RULGNN_OK ? g.nparam : -1;
 }
 
-size_t stmsgcn_workspace_bytes(const rulgnn_stmsgcn_shape* s) {
+size_t Stmsgcn::workspace_bytes(const Shape* s) {
     MsgGeom g;
     if (msg_geometry(s, &g) != RULGNN_OK) return 0;
     MsgWs w;
@@ -1669,7 +1669,7 @@ int stmsgcn_features(const rulgnn_stmsgcn_shape* s, const float* x, const float*
 }
 
 // mode bit 0: forward, bit 1: backward
-int stmsgcn_run(const rulgnn_stmsgcn_shape* s, const rulgnn_stmsgcn_args* a, int mode, hipStream_t st) {
+int Stmsgcn::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
     MsgGeom g;
     RULGNN_TRY(msg_geometry(s, &g));
     MsgWs w;

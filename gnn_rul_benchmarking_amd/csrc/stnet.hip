@@ -297,23 +297,24 @@ inline unsigned sn_grid(int64_t n) {
 
 }  // namespace
 
-int64_t stnet_param_count(const rulgnn_stnet_shape* s) {
+// RULGNN_OK, or the code every entry returns for a refused shape: unsupported for anything sn_geometry refuses, a negative batch included.
+int Stnet::shape_status(const Shape* s) {
+    SnGeom g;
+    return sn_geometry(s, &g) == RULGNN_OK ? RULGNN_OK : RULGNN_EUNSUPPORTED;
+}
+
+int64_t Stnet::param_count(const Shape* s) {
     SnGeom g;
     return sn_geometry(s, &g) == RULGNN_OK ? g.pcount : -1;
 }
 
-size_t stnet_workspace_bytes(const rulgnn_stnet_shape* s) {
+size_t Stnet::workspace_bytes(const Shape* s) {
     SnGeom g;
     return sn_geometry(s, &g) == RULGNN_OK ? (size_t)g.total * sizeof(float) : 0;
 }
 
-#define SN_LAUNCH_OK()                                        \
-    do {                                                      \
-        if (hipGetLastError() != hipSuccess) return RULGNN_EHIP; \
-    } while (0)
-
 // mode bit 0: forward, bit 1: backward (after a forward with the same args / workspace)
-int stnet_run(const rulgnn_stnet_shape* s, const rulgnn_stnet_args* a, int mode, hipStream_t st) {
+int Stnet::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
     SnGeom g;
     RULGNN_TRY(sn_geometry(s, &g));
     if (a->workspace_bytes < (size_t)g.total * sizeof(float)) return RULGNN_EWORKSPACE;
@@ -364,11 +365,11 @@ int stnet_run(const rulgnn_stnet_shape* s, const rulgnn_stnet_args* a, int mode,
         if (lds > 48 * 1024) return RULGNN_EUNSUPPORTED;
         RULGNN_TRY(fill_f32(ws + g.w_one + 3, 1, 0.0f, st));
         hipLaunchKernelGGL(sn_stft_kernel, dim3(ggrid), dim3(SB), lds, st, g, a->x, prm, ws);
-        SN_LAUNCH_OK();
+        RULGNN_LAUNCH_OK();
         const float* cur = ws + g.w_mag;
         for (int i = 0; i < nc; ++i) {
             hipLaunchKernelGGL(sn_terms_kernel, dim3(ggrid), dim3(SB), 0, st, g, g.C[i], cur, mask, ws + g.w_terms[i]);
-            SN_LAUNCH_OK();
+            RULGNN_LAUNCH_OK();
             RULGNN_TRY(sgemm(ws + g.w_terms[i], 3 * g.C[i], 1, fop[i], 1, g.C[i + 1], ws + g.w_out[i], g.C[i + 1], R, g.C[i + 1], 3 * g.C[i],
                         false, st));
             cur = ws + g.w_out[i];
@@ -386,12 +387,12 @@ int stnet_run(const rulgnn_stnet_shape* s, const rulgnn_stnet_args* a, int mode,
                                (int64_t)BT, dout[i], i < 3 ? 1 : 0);
             h = ws + g.w_dec[i];
         }
-        SN_LAUNCH_OK();
+        RULGNN_LAUNCH_OK();
         // reconstruction error (and, when a backward follows, its gradients w.r.t. both of its arguments)
         hipLaunchKernelGGL(sn_recon_kernel, dim3(g.rblocks), dim3(SB), 0, st, (const float*)cur, (const float*)(ws + g.w_dec[3]), (int64_t)BT * D,
                            rscale, ws + g.w_dD1, ws + g.w_dD2, ws + g.w_rsq);
         (void)block_sum((const float*)(ws + g.w_rsq), (int64_t)g.rblocks, ws + g.w_one + 1, st);
-        SN_LAUNCH_OK();
+        RULGNN_LAUNCH_OK();
         RULGNN_TRY(bilstm_forward(&ls, &la, st, 1));
         hipLaunchKernelGGL(sn_head_kernel, dim3((unsigned)(g.B < 1024 ? g.B : 1024)), dim3(SB), 0, st, g, (const float*)(ws + g.w_hseq), prm, a->y,
                            a->pred, ws, inv_gb);
@@ -401,7 +402,7 @@ int stnet_run(const rulgnn_stnet_shape* s, const rulgnn_stnet_args* a, int mode,
             (void)block_sum((const float*)(ws + g.w_sq), g.B, ws + g.w_one + 2, st);
             hipLaunchKernelGGL(sn_loss_kernel, dim3(1), dim3(1), 0, st, (const float*)(ws + g.w_one + 1), (const float*)(ws + g.w_one + 2), a->loss);
         }
-        SN_LAUNCH_OK();
+        RULGNN_LAUNCH_OK();
     }
     if (mode & 2) {
         if (!a->grads) return RULGNN_EINVAL;
@@ -414,7 +415,7 @@ int stnet_run(const rulgnn_stnet_shape* s, const rulgnn_stnet_args* a, int mode,
         RULGNN_TRY(sgemm_splitk(dpred, 0, 1, ws + g.w_hseq, 1, E * g.T, gr + g.o_lw, E * g.T, 1, E * g.T, (int)g.B, false, split, st));
         RULGNN_TRY(sgemm_splitk(dpred, 0, 1, one, 0, 0, gr + g.o_lb, 1, 1, 1, (int)g.B, false, split, st));
         hipLaunchKernelGGL(sn_head_bwd_kernel, dim3(sn_grid(g.B * E * g.T)), dim3(SB), 0, st, g, dpred, prm, ws + g.w_dhs);
-        SN_LAUNCH_OK();
+        RULGNN_LAUNCH_OK();
         la.dout = ws + g.w_dhs;
         la.dx = ws + g.w_dH;
         la.dw_ih[0] = gr + g.o_wih; la.dw_hh[0] = gr + g.o_whh; la.db_ih[0] = gr + g.o_bih; la.db_hh[0] = gr + g.o_bhh;
@@ -438,7 +439,7 @@ int stnet_run(const rulgnn_stnet_shape* s, const rulgnn_stnet_args* a, int mode,
         }
         // d H = decoder path + LSTM path
         hipLaunchKernelGGL(sn_add_kernel, dim3(sn_grid((int64_t)BT * A)), dim3(SB), 0, st, d, (const float*)(ws + g.w_dH), (int64_t)BT * A);
-        SN_LAUNCH_OK();
+        RULGNN_LAUNCH_OK();
         const float* yo = ws + g.w_out[nc - 1];
         for (int i = 3; i >= 0; --i) {
             const float* hin = i > 0 ? ws + g.w_enc[i - 1] : yo;
@@ -452,7 +453,7 @@ int stnet_run(const rulgnn_stnet_shape* s, const rulgnn_stnet_args* a, int mode,
         }
         // d Y_o = encoder path + the reconstruction term's own gradient
         hipLaunchKernelGGL(sn_add_kernel, dim3(sn_grid((int64_t)BT * D)), dim3(SB), 0, st, d, (const float*)(ws + g.w_dD2), (int64_t)BT * D);
-        SN_LAUNCH_OK();
+        RULGNN_LAUNCH_OK();
         const float* dcur = d;                        // [R, C_last]
         float* dc[2] = {ws + g.w_dc1, ws + g.w_dc2};
         for (int i = nc - 1; i >= 0; --i) {
@@ -462,7 +463,7 @@ int stnet_run(const rulgnn_stnet_shape* s, const rulgnn_stnet_args* a, int mode,
             RULGNN_TRY(sgemm(dcur, Co, 1, fop[i], Co, 1, ws + g.w_dterms, 3 * Ci, R, 3 * Ci, Co, false, st));
             float* dn = dc[i & 1];
             hipLaunchKernelGGL(sn_terms_bwd_kernel, dim3(ggrid), dim3(SB), 0, st, g, Ci, (const float*)(ws + g.w_dterms), mask, dn);
-            SN_LAUNCH_OK();
+            RULGNN_LAUNCH_OK();
             dcur = dn;
         }
     }

@@ -107,6 +107,32 @@ FAMILIES = {
         "odd_9x21": (_plain(L.GrucmShape, 9, 21, 64), (6,)),
         # gru_hidden_dim 64 has the persistent GRU, any other width the step loop only
         "hidden32": (_plain(L.GrucmShape, 14, 50, 32), ()), "hidden65": (_plain(L.GrucmShape, 14, 50, 65), ()), "hidden8_9x21": (_plain(L.GrucmShape, 9, 21, 8), ())}),
+    # hidden widths as the fixtures'; num_heads 1 (the default) and 4, num_patch at the limit of 256 and beyond it
+    "agcntf": (("param_count", "workspace_bytes"), {
+        "phm_40x64": (_plain(L.AgcntfShape, 40, 64, 100, 100, 1), (4,)), "small_5x7_heads2": (_plain(L.AgcntfShape, 5, 7, 6, 7, 2), (6,)),
+        "xjtu_like_20x256": (_plain(L.AgcntfShape, 20, 256, 100, 100, 1), (3,)), "curve_12x16": (_plain(L.AgcntfShape, 12, 16, 24, 20, 1), (8,)),
+        "row_xjtu_c1": (_plain(L.AgcntfShape, 128, 256, 100, 100, 1), ()), "row_xjtu_c3": (_plain(L.AgcntfShape, 256, 128, 100, 100, 1), ()),
+        "heads4_12x16": (_plain(L.AgcntfShape, 12, 16, 24, 20, 4), ()), "heads5_12x16": (_plain(L.AgcntfShape, 12, 16, 24, 20, 5), ()),
+        "patches257": (_plain(L.AgcntfShape, 257, 128, 100, 100, 1), ())}),
+    # (patch_size, num_patch, hidden_dim, embedding_dim, num_nodes, encoder_conv_kernel, num_nodes_out)
+    "hiercorrpool": (("param_count", "bn_state_count", "workspace_bytes"), {
+        "small_7x3_n5": (_plain(L.HiercorrpoolShape, 3, 7, 2, 2, 5, 12, 3), (6, 8)), "fd001geom": (_plain(L.HiercorrpoolShape, 25, 2, 1, 1, 14, 8, 6), ()),
+        "fd004geom": (_plain(L.HiercorrpoolShape, 10, 5, 1, 1, 14, 12, 6), ()), "ncmapssgeom": (_plain(L.HiercorrpoolShape, 1, 50, 1, 1, 20, 32, 6), (3,)),
+        "row_fd001": (_plain(L.HiercorrpoolShape, 25, 2, 10, 10, 14, 8, 6), ()), "row_fd002": (_plain(L.HiercorrpoolShape, 10, 5, 10, 10, 14, 12, 6), ()),
+        "row_fd003": (_plain(L.HiercorrpoolShape, 5, 10, 10, 10, 14, 12, 6), ()), "row_ncmapss": (_plain(L.HiercorrpoolShape, 1, 50, 10, 10, 20, 32, 6), ()),
+        # encoder_conv_kernel * embedding_dim at the limit of 512 (L' = 8, 4 h = 64) and beyond it; L' * 4 h != K * e
+        "ke512": (_plain(L.HiercorrpoolShape, 1, 50, 16, 16, 14, 32, 6), ()), "ke513": (_plain(L.HiercorrpoolShape, 1, 50, 16, 19, 14, 27, 6), ()),
+        "flat_view_mismatch": (_plain(L.HiercorrpoolShape, 3, 7, 2, 2, 5, 11, 3), ())}),
+    # (patch_size, num_patch, num_nodes, hidden_dim)
+    "logo": (("param_count", "workspace_bytes"), {
+        "small_3x2x2_h1": (_plain(L.LogoShape, 2, 2, 3, 1), (8,)), "fd001geom": (_plain(L.LogoShape, 10, 5, 14, 2), (5,)),
+        "fd002geom": (_plain(L.LogoShape, 2, 25, 14, 2), ()), "ncmapssgeom": (_plain(L.LogoShape, 5, 10, 20, 2), (3,)),
+        "row_fd001": (_plain(L.LogoShape, 10, 5, 14, 8), ()), "row_fd002": (_plain(L.LogoShape, 2, 25, 14, 6), ()),
+        "row_fd003_h32": (_plain(L.LogoShape, 10, 5, 14, 32), ()), "row_fd004": (_plain(L.LogoShape, 10, 5, 14, 10), ()),
+        "row_ncmapss": (_plain(L.LogoShape, 5, 10, 20, 10), (50,)),
+        # 6 * hidden_dim on either side of the limit of 128 (126 and 132), num_nodes at the limit of 32 and beyond it
+        "h21": (_plain(L.LogoShape, 2, 2, 3, 21), ()), "h22": (_plain(L.LogoShape, 2, 2, 3, 22), ()),
+        "nodes32": (_plain(L.LogoShape, 2, 2, 32, 1), ()), "nodes33": (_plain(L.LogoShape, 2, 2, 33, 1), ())}),
     "hagcn": (("graph_param_count", "workspace_bytes"), {
         "n14_e60_h64": (_plain(L.HagcnShape, 14, 60, 64), (6, 5, 7, 24)), "n20_e60_h64": (_plain(L.HagcnShape, 20, 60, 64), (3,)),
         "n12_e8_h16": (_plain(L.HagcnShape, 12, 8, 16), (4,))}),
@@ -129,7 +155,10 @@ def _sizes(lib):
                 shp = make(b)                    # (one value per query, in the family's order above)
                 out[f"{fam}/{name}/b{b}"] = [int(getattr(lib, f"rulgnn_{fam}_{q}")(C.byref(shp))) for q in queries]
     for fam, name, make in (("sagcn", "phm_c2like_9x20", FAMILIES["sagcn"][1]["phm_c2like_9x20"][0]),
-                            ("stagnn", "small_5x12", FAMILIES["stagnn"][1]["small_5x12"][0])):
+                            ("stagnn", "small_5x12", FAMILIES["stagnn"][1]["small_5x12"][0]),
+                            ("agcntf", "small_5x7_heads2", FAMILIES["agcntf"][1]["small_5x7_heads2"][0]),
+                            ("hiercorrpool", "small_7x3_n5", FAMILIES["hiercorrpool"][1]["small_7x3_n5"][0]),
+                            ("logo", "small_3x2x2_h1", FAMILIES["logo"][1]["small_3x2x2_h1"][0])):
         out[f"{fam}/{name}/tap_offsets_from_minus1"] = [int(getattr(lib, f"rulgnn_{fam}_tap_offset")(C.byref(make(4)), w)) for w in range(-1, 12)]
     for N, P in STGCN_NP:
         for layers in (1, 2, 3):
@@ -180,7 +209,17 @@ _STEP_FAMILIES = {
     "stagnn": (L.StagnnArgs, _plain(L.StagnnShape, 5, 12, 9, 4, 2, 0.001), _plain(L.StagnnShape, 5, 12, 4, 4, 2, 0.001), {"training": 1}),
     "rgcnu": (L.RgcnuArgs, _plain(L.RgcnuShape, 5, 12, 6, 8, 3, 0.7), _plain(L.RgcnuShape, 5, 12, 6, 8, 4, 0.7), {"training": 1, "dropout_p": 0.2}),
     "grucm": (L.GrucmArgs, _plain(L.GrucmShape, 9, 21, 64), _plain(L.GrucmShape, 33, 21, 64), {"training": 1}),
+    # (the BatchNorm families refuse batch < 1, so their empty-batch set answers differently: recorded as the parent answers it)
+    "astgcnn": (L.AstgcnnArgs, _plain(L.AstgcnnShape, 5, 12, 8, 3), _plain(L.AstgcnnShape, 5, 12, 8, 4), {"training": 1, "bn_moment_weight": 0.0}),
+    "stconv": (L.AstgcnnArgs, _plain(L.StconvShape, 6, 11, 6), _plain(L.StconvShape, 6, 11, 5), {"training": 1, "bn_moment_weight": 0.0}),
+    "fcstgnn": (L.FcstgnnArgs, _plain(L.FcstgnnShape, *_FC_ROWS["fd003like_6p"]), _plain(L.FcstgnnShape, 1, 6, 3, 17, 6, 2, 24, 25, 14, 8),
+                {"training": 1, "bn_moment_weight": 0.0, "dropout_p": 0.2}),
+    "agcntf": (L.AgcntfArgs, _plain(L.AgcntfShape, 5, 7, 6, 7, 2), _plain(L.AgcntfShape, 5, 7, 6, 7, 5), {}),
+    "hiercorrpool": (L.HiercorrpoolArgs, _plain(L.HiercorrpoolShape, 3, 7, 2, 2, 5, 12, 3), _plain(L.HiercorrpoolShape, 3, 7, 2, 2, 33, 12, 3),
+                     {"training": 1, "dropout_p": 0.2}),
+    "logo": (L.LogoArgs, _plain(L.LogoShape, 2, 2, 3, 1), _plain(L.LogoShape, 2, 2, 33, 1), {"training": 1, "dropout_p": 0.2, "theta": 0.001, "gamma": 0.5}),
 }
+_BN_FAMILIES = ("astgcnn", "fcstgnn", "stconv")
 _OPTIONAL = ("dpred", "recon_weight", "step_state", "aux_stream")
 
 
@@ -270,6 +309,90 @@ def _family_codes(lib, fam, out):
     if fam == "rgcnu":
         a, _ = args(dropout_p=1.0, params=None)
         out["rgcnu/fwdbwd/dropout_p1_and_params_null"] = int(lib.rulgnn_rgcnu_fwdbwd_f32(C.byref(good(B)), C.byref(a), None, None))
+
+    def more(entry, key, over, **opt_over):
+        """One more set on rulgnn_<fam>_<entry>_f32; `opt_over` (fwdbwd only) builds an optimizer block on the set's own parameters."""
+        a, _ = args(**over)
+        fn = getattr(lib, f"rulgnn_{fam}_{entry}_f32")
+        opt = C.byref(_adam(a.params, **opt_over)) if opt_over else None
+        out[f"{fam}/{entry}/{key}"] = int(fn(C.byref(good(B)), C.byref(a), opt, None) if entry == "fwdbwd" else fn(C.byref(good(B)), C.byref(a), None))
+
+    if fam == "logo":
+        for key, over in (("loss_gl_plus1", dict(loss_gl="misalign")), ("global_batch_short", dict(global_batch=1)), ("dropout_p1", dict(dropout_p=1.0)),
+                          ("dropout_p1_and_params_null", dict(dropout_p=1.0, params=None)), ("loss_gl_plus1_and_grads_null", dict(loss_gl="misalign", grads=None)),
+                          ("global_batch_short_and_loss_plus1", dict(global_batch=1, loss="misalign"))):
+            more("fwdbwd", key, over)
+    if fam == "hiercorrpool":
+        for entry in ("backward", "fwdbwd"):
+            more(entry, "eval_mode", dict(training=0))
+        for key, over in (("sample_offset_negative", dict(sample_offset=-1)), ("global_batch_short", dict(global_batch=1)), ("dropout_p1", dict(dropout_p=1.0)),
+                          ("sample_offset_negative_and_bn_state_null", dict(sample_offset=-1, bn_state=None)),
+                          ("dropout_p1_and_params_plus1", dict(dropout_p=1.0, params="misalign")),
+                          ("bn_state_plus1_and_x_null", dict(bn_state="misalign", x=None))):
+            more("fwdbwd", key, over)
+    if fam in _BN_FAMILIES:
+        for entry in ("forward", "backward", "fwdbwd"):
+            more(entry, "bn_moment_weight_negative", dict(bn_moment_weight=-1.0))
+            more(entry, "bn_moment_weight_negative_and_params_null", dict(bn_moment_weight=-1.0, params=None))
+            more(entry, "global_batch_short", dict(global_batch=1))
+        more("forward", "eval_mode_bn_stats_null", dict(training=0, bn_stats=None))
+        more("forward", "eval_mode_bn_stats_plus1", dict(training=0, bn_stats="misalign"))
+        more("forward", "eval_mode_bn_stats_null_and_y_plus1", dict(training=0, bn_stats=None, y="misalign"))
+        more("fwdbwd", "opt_bn_stats_set_and_bn_batch_null", dict(bn_batch=None), bn_stats=BASE + 196608)
+        more("fwdbwd", "opt_bn_stats_plus1", {}, bn_stats=BASE + 196609)
+        more("fwdbwd", "opt_bn_stats_plus1_and_exp_avg_null", {}, bn_stats=BASE + 196609, exp_avg=None)
+        more("fwdbwd", "opt_bn_stats_plus1_and_dpred_set", dict(dpred=BASE + 512 * 64), bn_stats=BASE + 196609)
+        if fam == "fcstgnn":
+            for key, over in (("sample_offset_negative", dict(sample_offset=-1)), ("dropout_p1", dict(dropout_p=1.0)),
+                              ("sample_offset_negative_and_x_null", dict(sample_offset=-1, x=None))):
+                more("fwdbwd", key, over)
+        _bn_running_update_codes(lib, fam, good(B), out)
+        if fam != "stconv":
+            _syncbn_codes(lib, fam, good(B), args, out)
+
+
+def _syncbn_codes(lib, fam, shp, args, out):
+    """rulgnn_<fam>_fwdbwd_syncbn_f32.  The callback raises if it is ever called: every set returns before the first launch, and the
+    first all-reduce sits behind one."""
+    fn = getattr(lib, f"rulgnn_{fam}_fwdbwd_syncbn_f32")
+    called = []
+
+    def hook(_user, _buf, _count, _stream):
+        called.append(1)
+        raise AssertionError("the all-reduce callback of a refused call ran")
+    cb, null_cb = L.ALLREDUCE_F64_FN(hook), C.cast(None, L.ALLREDUCE_F64_FN)
+    a0, _ = args()
+    for key, shape, a, scale, f in (("null_shape", None, C.byref(a0), 1.0, cb), ("null_args", C.byref(shp), None, 1.0, cb),
+                                    ("short_workspace", C.byref(shp), C.byref(a0), 1.0, cb), ("null_callback", C.byref(shp), C.byref(a0), 1.0, null_cb),
+                                    ("scale_nan", C.byref(shp), C.byref(a0), float("nan"), cb), ("scale_inf", C.byref(shp), C.byref(a0), float("inf"), cb),
+                                    ("scale_negative", C.byref(shp), C.byref(a0), -0.5, cb), ("scale_above_one", C.byref(shp), C.byref(a0), 1.5, cb),
+                                    ("scale_zero_short_workspace", C.byref(shp), C.byref(a0), 0.0, cb),
+                                    ("scale_nan_and_null_callback", C.byref(shp), C.byref(a0), float("nan"), null_cb)):
+        out[f"{fam}/fwdbwd_syncbn/{key}"] = int(fn(shape, a, scale, f, None, None))
+    for key, over, scale, f in (("dpred_set", dict(dpred=BASE + 512 * 64), 1.0, cb), ("dpred_set_and_null_callback", dict(dpred=BASE + 512 * 64), 1.0, null_cb),
+                                ("scale_nan_and_params_null", dict(params=None), float("nan"), cb), ("eval_mode_and_null_callback", dict(training=0), 1.0, null_cb),
+                                ("bn_moment_weight_positive", dict(bn_moment_weight=0.5), 1.0, cb), ("global_batch_short", dict(global_batch=1), 1.0, cb)):
+        out[f"{fam}/fwdbwd_syncbn/{key}"] = int(fn(C.byref(shp), C.byref(args(**over)[0]), scale, f, None, None))
+    assert not called, (fam, "the all-reduce callback ran")
+
+
+def _bn_running_update_codes(lib, fam, shp, out):
+    """rulgnn_<fam>_bn_running_update_f32: ASTGCNN's and ST_Conv's take the element count, FC_STGNN's has it in its shape."""
+    fn = getattr(lib, f"rulgnn_{fam}_bn_running_update_f32")
+    counted = fam != "fcstgnn"
+    stats, batch = BASE + 256, BASE + 512
+
+    def call(key, shape, s, b, count=100):
+        out[f"{fam}/bn_running_update/{key}"] = int(fn(shape, s, b, count, 0.1, 0, None) if counted else fn(shape, s, b, 0.1, 0, None))
+
+    call("null_shape", None, stats, batch)
+    for key, s, b in (("bn_stats_null", None, batch), ("bn_stats_plus1", stats + 1, batch), ("bn_batch_null", stats, None), ("bn_batch_plus1", stats, batch + 1),
+                      ("bn_stats_plus1_and_bn_batch_null", stats + 1, None), ("bn_stats_null_and_bn_batch_plus1", None, batch + 1)):
+        call(key, C.byref(shp), s, b)
+    if counted:
+        call("count0", C.byref(shp), stats, batch, 0)
+        call("count0_and_bn_stats_plus1", C.byref(shp), stats + 1, batch, 0)
+        call("count_negative_and_null_shape", None, stats, batch, -1)
 
 
 def _gru_codes(lib, out):

@@ -49,7 +49,7 @@ def _compare(want, got, group):
 
 def test_golden_names_its_parent_commit(golden):
     assert len(golden["parent_commit"]) == 40 and int(golden["parent_commit"], 16) >= 0
-    assert len(golden["sizes"]) > 1000 and len(golden["codes"]) > 900
+    assert len(golden["sizes"]) > 1200 and len(golden["codes"]) > 1650
 
 
 @pytest.mark.parametrize("group", _groups("sizes"))
