@@ -48,6 +48,9 @@
 // leave one tile late, right behind the s_waitcnt vmcnt(0) that also counts stores (stgcn_forward_mx.hip, round 3).  The records are
 // stored write-through (whole 16-byte pieces out of a staging tile), so a phase ends with no dirty lines in L2 for the next launch to
 // wait behind, and a record's last reader in the step loads it non-temporally (MXT_RECORD_POLICY, MXT_LAST_READER_NT).
+// A full-tile record is written into its staging tile where its values are produced (branch-free: padding lanes write to a dump area)
+// and the tile is the pending storage; the next tile issues the 16-byte LDS reads in front of its wait and the stores back to back
+// behind it (round 24; MXT_RECORD_STAGING in stgcn_train_mx_ops.hpp: one switch per piece, profiles/r24_record_stores.md).
 #include <algorithm>
 #include <cstdlib>
 #include <type_traits>
@@ -94,7 +97,7 @@ __device__ __forceinline__ void mxp_dump() {
 // partials]; then one region per wavefront (the wavefronts only meet in the prologue and the epilogue).
 struct MxtLds {
     int bnc, red, pairbuf, waves;                                       // the workgroup's part; `waves`: the wavefronts' regions
-    int zero, scr, sh, wg, X, A, SB, DX, XP, HS, H, wave_floats;        // within a region
+    int zero, scr, dump, sh, wg, X, A, SB, DX, XP, HS, H, wave_floats;  // within a region
     int total;
 };
 __host__ __device__ constexpr MxtLds mxt_lds(int L, int kind, int idx, int nfix, int N) {
@@ -107,6 +110,7 @@ __host__ __device__ constexpr MxtLds mxt_lds(int L, int kind, int idx, int nfix,
     l.waves = l.pairbuf + 2 * MXT_WAVES * (2 * F + 2);
     l.zero = 0;
     l.scr = l.zero + MXT_ZERO_FLOATS;
+    l.dump = l.scr;                                          // [MXT_DUMP_FLOATS]: where the padding lanes' staging writes go (TILE_OUT; TOP has none)
     l.sh = l.scr + MXT_SCRATCH_FLOATS;
     l.wg = l.sh + MXT_SHIFT_FLOATS;                          // G: the transposing image of the weight gradient's operands
     l.X = l.wg + (kind == PH_G ? MXT_WG_FLOATS : 0);         // X_LIN, or H_LY (H_IN)
@@ -114,8 +118,8 @@ __host__ __device__ constexpr MxtLds mxt_lds(int L, int kind, int idx, int nfix,
     l.SB = l.A + (t.H_TOP ? XF : t.AF);                      // G_{2l}
     l.DX = l.SB + (t.NEED_SB ? XF : 0);                      // gradient in (full tile or TOP's two rows)
     l.XP = l.DX + (t.GRAD_IN ? XF : 0);                      // G_{2l}, l >= 1: the gated x-hat of BatchNorm 2l-1
-    l.HS = l.XP + (t.BWD_PREV ? XF : 0);                     // the staging tile (TILE_OUT)
-    l.H = l.HS + (t.TILE_OUT ? XF : 0);                      // H_TILE: H_{l-1} (F_{2l}) / H_l (G_{2l})
+    l.HS = l.XP + (t.BWD_PREV ? XF : 0);                     // the staging tiles (TILE_OUT): one, or one per record (MxtTraits::NSTG)
+    l.H = l.HS + t.NSTG * XF;                                // H_TILE: H_{l-1} (F_{2l}) / H_l (G_{2l})
     l.wave_floats = l.H + (t.H_TILE ? XF : 0);
     l.total = l.waves + MXT_WAVES * l.wave_floats;
     return l;
@@ -330,16 +334,58 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
     // A full-tile record leaves through LDS: the tile is assembled in the wavefront's staging words and stored as 16-byte pieces of the
     // contiguous [10][4 N] record -- three dwordx4 stores of whole cache lines instead of twelve dword stores of 4 N-byte row pieces.
     // All four samples go out: beyond the batch a record is never used (every reader overwrites the samples >= ns of what it loads).
-    auto st_tile = [&](float* dst, const float (&v)[4][3]) {
-        float* const stg = smem + off_HS;
+    // The three pieces of that path have a switch each (MXT_RECORD_STAGING, stgcn_train_mx_ops.hpp).
+    // Staging writes.  `swr[r]`: where register row r of sample 0 goes in staging tile 0 -- the lane's word of the tile, or (branch-free
+    // form) for a padding lane its word of the dump area; sample s is s N words on (an immediate offset at fixed N), staging tile k
+    // another k XF for the lanes inside the tile (the dump area lies in front of the tiles).
+    static_assert(!T.TILE_OUT || (KIND != PH_TOP && LC.dump >= LC.scr && LC.dump + MXT_DUMP_FLOATS <= LC.sh),
+                  "the dump area lies inside the wavefront's region, in words no tile-writing phase uses");
+    int swr[3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) swr[r] = xoff[r] >= 0 ? off_HS + xoff[r] : LC.dump + lane;
+    auto stg_put = [&](int k, int s, int r, float v) {
+        if constexpr (MXT_STAGE_BRANCHFREE) {
+            const int w = k == 0 ? swr[r] : (swr[r] >= off_HS ? swr[r] + k * XF : swr[r]);
+            smem[w + s * N] = v;
+        } else {
+            if (xoff[r] >= 0) smem[off_HS + k * XF + xoff[r] + s * N] = v;
+        }
+    };
+    auto stg_put_tile = [&](int k, const float (&v)[4][3]) {
 #pragma unroll
         for (int s = 0; s < 4; ++s)
 #pragma unroll
-            for (int r = 0; r < 3; ++r)
-                if (xoff[r] >= 0) stg[xoff[r] + s * N] = v[s][r];
-        __builtin_amdgcn_wave_barrier();
-        const int nq = XF / 4;
+            for (int r = 0; r < 3; ++r) stg_put(k, s, r, v[s][r]);
+    };
+    // Staging tile k -> its record, 16-byte pieces.  Rolled: one LDS round trip per piece (the store's asm is a memory barrier for the
+    // compiler).  Read-ahead form: stg_read issues every read (MXT_MAX_PIECES per lane; at fixed N the count is known: three at N = 14, the
+    // last on twelve lanes), stg_store the stores back to back; the caller puts the tile's wait between them.
+    struct StgPieces { float4 q[MXT_MAX_PIECES]; };
+    const int nq = XF / 4;
+    auto stg_read = [&](int k, StgPieces& p) {
+        const float4* const stg = reinterpret_cast<const float4*>(smem + off_HS + k * XF);
+#pragma unroll
+        for (int j = 0; j < MXT_MAX_PIECES; ++j) {
+            const int i = lane + 64 * j;
+            p.q[j] = stg[i < nq ? i : 0];
+        }
+    };
+    auto stg_store = [&](float* dst, const StgPieces& p) {
+#pragma unroll
+        for (int j = 0; j < MXT_MAX_PIECES; ++j) {
+            const int i = lane + 64 * j;
+            if (i < nq) st_rec16<MXT_RECORD_POLICY>(dst + 4 * i, p.q[j]);
+        }
+    };
+    auto stg_drain_rolled = [&](int k, float* dst) {
+        const float* const stg = smem + off_HS + k * XF;
         for (int i = lane; i < nq; i += 64) st_rec16<MXT_RECORD_POLICY>(dst + 4 * i, reinterpret_cast<const float4*>(stg)[i]);
+    };
+    // (not staged where produced: registers -> the one staging tile -> record, at the top of the next tile)
+    auto st_tile = [&](float* dst, const float (&v)[4][3]) {
+        stg_put_tile(0, v);
+        __builtin_amdgcn_wave_barrier();
+        stg_drain_rolled(0, dst);
         __builtin_amdgcn_wave_barrier();
     };
     const int sh_rd1 = col >= 1 ? lane - 1 : 64, sh_rd2 = col >= 2 ? lane - 2 : 64;     // forward taps: column t - d
@@ -486,13 +532,62 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
     bool pend = false;
     int64_t pend_tile = 0;
     int pend_ns = 0;
-    float pend_v[4][3], pend_q[4][3], pend_h[4][3];
+    float pend_v[4][3], pend_q[4][3], pend_h[4][3];     // (staged where produced: unused, the staging tiles hold the records)
     float pend_top0 = 0.f, pend_top1 = 0.f, pend_pred = 0.f;
     uint32_t pend_m = 0u;                       // dropout mask bits of the tile (F_{2l}, TOP: written)
 #pragma unroll
     for (int s = 0; s < 4; ++s)
 #pragma unroll
         for (int r = 0; r < 3; ++r) pend_v[s][r] = pend_q[s][r] = pend_h[s][r] = 0.f;
+    // The full-tile records of this phase, in the order they leave; REC k lives in pend_v / pend_q / pend_h or in staging tile k.
+    // (F_{2l}: X_l, Q_l, H_l; F_1: H_0; G_{2l+1}: d(x0 + H); G_{2l}: d X_l)
+    constexpr int NREC = WITH_PREV ? 3 : (T.TILE_OUT ? 1 : 0);
+    constexpr int REC_H = WITH_PREV ? 2 : 0;    // H_OUT: which record H_l is
+    auto rec_dst = [&](int k) -> float* {
+        if constexpr (WITH_PREV) return (k == 0 ? a.xrec[LY] : k == 1 ? a.qrec[LY] : a.hrec[LY]) + pend_tile * XF;
+        else if constexpr (H_OUT) return a.hrec[LY] + pend_tile * XF;
+        else if constexpr (KIND == PH_G && BLK == 1) return a.sb + pend_tile * XF;
+        else return a.dx + pend_tile * XF;
+    };
+    // a value of record k as it is produced (k: 0 -> pend_v, 1 -> pend_q, 2 -> pend_h where the registers are the pending storage)
+    auto rec_put = [&](int k, int s, int r, float v) {
+        if constexpr (MXT_STAGE_EARLY) stg_put(k, s, r, v);
+        else (k == 0 ? pend_v : k == 1 ? pend_q : pend_h)[s][r] = v;
+    };
+    // the pending records' way out.  Staged where produced: `rec_read` in front of the tile's wait (read-ahead) or nothing, `rec_store`
+    // behind it; the epilogue runs both.
+    // (`pieces`: a local of the tile body -- declared outside the loop the twelve registers per record are carried around the back edge)
+    // (G_{2l}, l >= 1, sits at 256 registers: with the pieces held across the wait it spills more than its parent, so it keeps the
+    // rolled drain behind the wait; so does the generic-N single launch, one register allocation for eight bodies)
+    constexpr bool READ_AHEAD = MXT_STAGE_READ_AHEAD && !BWD_PREV && !(PERSIST && NFIX == 0);
+    using RecPieces = StgPieces[NREC > 0 ? NREC : 1];
+    auto rec_read = [&](RecPieces& pieces) {
+        if constexpr (READ_AHEAD) {
+            asm volatile("" ::: "memory");
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int k = 0; k < NREC; ++k) stg_read(k, pieces[k]);
+        }
+    };
+    auto rec_store = [&](const RecPieces& pieces) {
+        if constexpr (READ_AHEAD) {
+#pragma unroll
+            for (int k = 0; k < NREC; ++k) stg_store(rec_dst(k), pieces[k]);
+        } else if constexpr (MXT_STAGE_EARLY) {
+            __builtin_amdgcn_wave_barrier();
+#pragma unroll
+            for (int k = 0; k < NREC; ++k) stg_drain_rolled(k, rec_dst(k));
+            __builtin_amdgcn_wave_barrier();
+        } else {
+            if constexpr (WITH_PREV) {
+                st_tile(rec_dst(0), pend_v);
+                st_tile(rec_dst(1), pend_q);
+                st_tile(rec_dst(2), pend_h);
+            } else if constexpr (NREC == 1) {
+                st_tile(rec_dst(0), pend_v);
+            }
+        }
+    };
 
     MXP_MARKI(5);                                                                  // constants ready
     for (; tile < a.ntiles; tile += tstride) {
@@ -504,19 +599,18 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
         constexpr bool FULL = decltype(FULL_)::value;
         const int ns = FULL ? 4 : ns_tile;
         const int64_t nt = tile + tstride;
+        // (read-ahead: the pending records' LDS reads go first -- their latency sits under the wait the tile pays anyway)
+        RecPieces pieces;
+        if constexpr (NREC > 0) { if (pend) rec_read(pieces); }
         asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_wave_barrier();
         if (!pend) MXP_MARKI(13);                                                  // the first tile in hand
         // ---- what the previous tile leaves: stored HERE, behind the wait that also counts stores ------------------------------------
         if (pend) {
+            if constexpr (NREC > 0) rec_store(pieces);
             if constexpr (WITH_PREV) {
-                st_tile(a.xrec[LY] + pend_tile * XF, pend_v);
-                st_tile(a.qrec[LY] + pend_tile * XF, pend_q);
                 if (use_drop) st_rec4<MXT_RECORD_POLICY>(a.mrec[LY - 1] + pend_tile * 64 + lane, pend_m);
             }
-            if constexpr (H_OUT) st_tile(a.hrec[LY] + pend_tile * XF, pend_h);
-            if constexpr (KIND == PH_G && BLK == 1) st_tile(a.sb + pend_tile * XF, pend_v);
-            if constexpr (BWD_PREV) st_tile(a.dx + pend_tile * XF, pend_v);
             if constexpr (KIND == PH_TOP) {
                 if (g < pend_ns && col_ok && a.do_backward) {
                     float* p = a.dtop + pend_tile * (8 * N) + g * N + col;
@@ -578,12 +672,13 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
         if constexpr (KIND == PH_F) {
             // ===== forward statistics phases ==============================================================================================
             if constexpr (WITH_PREV) {
-                if constexpr (H_PREV) layer_full(X, adjB, kp, dkey[LY - 1], sbase, nullptr, nullptr, &pend_q, &pend_m, &HT);
-                else layer_full(X, adjB, kp, dkey[LY - 1], sbase, nullptr, nullptr, &pend_q, &pend_m);
+                float Qn[4][3];
+                if constexpr (H_PREV) layer_full(X, adjB, kp, dkey[LY - 1], sbase, nullptr, nullptr, &Qn, &pend_m, &HT);
+                else layer_full(X, adjB, kp, dkey[LY - 1], sbase, nullptr, nullptr, &Qn, &pend_m);
 #pragma unroll
                 for (int s = 0; s < 4; ++s)
 #pragma unroll
-                    for (int r = 0; r < 3; ++r) pend_v[s][r] = X[s][r];
+                    for (int r = 0; r < 3; ++r) { rec_put(0, s, r, X[s][r]); rec_put(1, s, r, Qn[s][r]); }
             }
             f32x4 z[4];
             float H[4][3];
@@ -605,7 +700,7 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
 #pragma unroll
                 for (int s = 0; s < 4; ++s)
 #pragma unroll
-                    for (int r = 0; r < 3; ++r) pend_h[s][r] = H[s][r];
+                    for (int r = 0; r < 3; ++r) rec_put(REC_H, s, r, H[s][r]);
             }
             if constexpr (BLK == 0) {
                 stage_conv(H, 0.f, kc.w[0], sh_rd1, sh_rd1_lo, z, pk, ps);          // raw z1
@@ -920,7 +1015,7 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
                         for (int r = 0; r < 3; ++r) {
                             float gq = dI[e][r] + gsum[e][r];
                             gq = (V[e][r] > 0.f && HS + e < ns) ? gq * colm : 0.f;
-                            pend_v[HS + e][r] = gq;
+                            rec_put(0, HS + e, r, gq);
                             const float dy = y1[e][r] > 0.f ? gq : 0.f;
                             s_a[r] += dy;
                             s_b[r] = fmaf(dy, xh0[e][r], s_b[r]);
@@ -980,7 +1075,7 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
 #pragma unroll
                             for (int r = 0; r < 3; ++r) {
                                 const float dX = (HS + e < ns) ? (dXl[e][r] + gin[HS + e][r]) * colm : 0.f;
-                                pend_v[HS + e][r] = dX;
+                                rec_put(0, HS + e, r, dX);
                                 const bool open = Q[HS + e][r] < INFINITY;
                                 const float dy = open ? dX * a.drop_scale : 0.f;
                                 s_a[r] += dy;
@@ -1003,14 +1098,10 @@ __device__ __forceinline__ void mxt_phase_body(const MxTrainK& a, float* smem_al
     MXP_MARKI(6);                                                                  // tile loop done
     // ---- the last tile's outputs ---------------------------------------------------------------------------------------------------------
     if (pend) {
+        if constexpr (NREC > 0) { RecPieces pieces; rec_read(pieces); rec_store(pieces); }
         if constexpr (WITH_PREV) {
-            st_tile(a.xrec[LY] + pend_tile * XF, pend_v);
-            st_tile(a.qrec[LY] + pend_tile * XF, pend_q);
             if (use_drop) st_rec4<MXT_RECORD_POLICY>(a.mrec[LY - 1] + pend_tile * 64 + lane, pend_m);
         }
-        if constexpr (H_OUT) st_tile(a.hrec[LY] + pend_tile * XF, pend_h);
-        if constexpr (KIND == PH_G && BLK == 1) st_tile(a.sb + pend_tile * XF, pend_v);
-        if constexpr (BWD_PREV) st_tile(a.dx + pend_tile * XF, pend_v);
         if constexpr (KIND == PH_TOP) {
             if (g < pend_ns && col_ok && a.do_backward) {
                 float* p = a.dtop + pend_tile * (8 * N) + g * N + col;
@@ -1223,12 +1314,15 @@ constexpr bool mxt_bytes_are(int L, int N, std::initializer_list<int> want) {
     mxt_each_phase(L, [&](int kind, int idx) { ok = ok && 4 * mxt_lds(L, kind, idx, mxt_nfix(N), N).total == *w++; });
     return ok;
 }
+// (F_{2l}, l >= 1, staged where produced: two more staging tiles per wavefront, 2 x 4 x 160 N bytes)
+constexpr int mxt_f_even_extra(int N) { return MXT_STAGE_EARLY ? 2 * MXT_WAVES * 160 * N : 0; }
+static_assert(mxt_f_even_extra(14) == 17920 || !MXT_STAGE_EARLY);
 static_assert(mxt_bytes_are(1, 14, {30320, 33840, 42096, 47536}));
-static_assert(mxt_bytes_are(2, 14, {30880, 34400, 34400, 21920, 42656, 48096, 78496, 48096}));
-static_assert(mxt_bytes_are(3, 14, {31440, 34960, 34960, 22480, 34960, 22480, 43216, 48656, 79056, 48656, 79056, 48656}));
-static_assert(mxt_bytes_are(2, 15, {32160, 35680, 35680, 22560, 43936, 50016, 72736, 50016}));
-static_assert(mxt_bytes_are(3, 15, {32720, 36240, 36240, 23120, 36240, 23120, 44496, 50576, 73296, 50576, 73296, 50576}));
-static_assert(mxt_bytes_are(2, 2, {15520, 19040, 19040, 14240, 27296, 25056, 31136, 25056}));
+static_assert(mxt_bytes_are(2, 14, {30880, 34400, 34400 + mxt_f_even_extra(14), 21920, 42656, 48096, 78496, 48096}));
+static_assert(mxt_bytes_are(3, 14, {31440, 34960, 34960 + mxt_f_even_extra(14), 22480, 34960 + mxt_f_even_extra(14), 22480, 43216, 48656, 79056, 48656, 79056, 48656}));
+static_assert(mxt_bytes_are(2, 15, {32160, 35680, 35680 + mxt_f_even_extra(15), 22560, 43936, 50016, 72736, 50016}));
+static_assert(mxt_bytes_are(3, 15, {32720, 36240, 36240 + mxt_f_even_extra(15), 23120, 36240 + mxt_f_even_extra(15), 23120, 44496, 50576, 73296, 50576, 73296, 50576}));
+static_assert(mxt_bytes_are(2, 2, {15520, 19040, 19040 + mxt_f_even_extra(2), 14240, 27296, 25056, 31136, 25056}));
 
 template <int L, int KIND, int IDX, int NFIX>
 static int mxt_launch(const MxTrainK& k, hipStream_t stream, int max_grid, int* grid_out) {

@@ -64,10 +64,35 @@ constexpr bool mxt_h0_record(int L) { return MXT_H0_READ_G1 || MXT_H0_READ_G0 ||
 // and the generic ones keep the rebuild.  G_0 has three of those tiles and fits at every N.  (`nfix`: the kernel's NFIX.)
 constexpr bool mxt_g_even_reads_h(int ly, int nfix) { return ly == 0 ? MXT_H0_READ_G0 : (MXT_H_READ_G_EVEN && nfix == 14); }
 
+// How a full-tile record (X_l, Q_l, H_l, d(x0 + H), d X_l) gets from the D-layout registers into its staging tile and out of it
+// (narrow chain; profiles/r24_record_stores.md).  One switch per piece, built cumulatively (-DMXT_RECORD_STAGING=<bits>,
+// tools/build_variants.py):
+//   bit 0  staged where produced: a phase writes the values into the staging tile when they exist (end of the tile body; each half of a
+//          G tile its two samples) and the tile is the pending storage -- no loop-carried copy in registers.  F_{2l}, l >= 1, gets one
+//          staging tile per record (three).
+//   bit 1  branch-free staging writes: per register row one LDS address, the lane's word of the tile or, for a padding lane, a word of
+//          the dump area (MxtLds::dump) -- no exec-mask region per write.
+//   bit 2  (needs bit 0) the 16-byte LDS reads of the pending records are issued IN FRONT of the tile's s_waitcnt vmcnt(0), the
+//          write-through stores back to back behind it, with a compile-time piece count.
+// Measured cumulatively at batch 65 536, ms per step, three alternated runs each: parent 0.3011-0.3024, bit 0 alone 0.3014-0.3028 (no
+// gain by itself), bits 0-1 0.2991-0.2994, all three 0.2952-0.2959.  ALL ON.  Bit 2 is not applied to G_{2l}, l >= 1, and to the
+// generic-N single launch (scratch above the parent's: mxt_phase_body); the opt-in single launch at batch 100 loses 5 us with them.
+#ifndef MXT_RECORD_STAGING
+#define MXT_RECORD_STAGING 7
+#endif
+constexpr bool MXT_STAGE_EARLY = (MXT_RECORD_STAGING & 1) != 0;
+constexpr bool MXT_STAGE_BRANCHFREE = (MXT_RECORD_STAGING & 2) != 0;
+constexpr bool MXT_STAGE_READ_AHEAD = (MXT_RECORD_STAGING & 4) != 0;
+static_assert(!MXT_STAGE_READ_AHEAD || MXT_STAGE_EARLY, "the reads can go in front of the wait only where the staging tile is the pending storage");
+// the dump area: a padding lane writes word `lane` + s N, s < 4 -- the head's exchange words, which only TOP uses and TOP writes no tile
+constexpr int MXT_DUMP_FLOATS = 64 + 3 * 15;
+static_assert(MXT_DUMP_FLOATS <= MXT_SCRATCH_FLOATS, "the dump area of the staging writes lies inside the scratch words");
+constexpr int MXT_MAX_PIECES = 3;        // 16-byte pieces of a [10][4 N] tile per lane: 10 N <= 150 of them on 64 lanes
+
 // What phase (L, kind, idx) of a training chain is, once, for the bodies' `if constexpr`, the LDS layouts and the launchers.  (`nfix`: the
 // kernel's NFIX; the wide chain, which has no H records, passes 0.)
 struct MxtTraits {
-    int LY, BLK, LIN, AF, NTH;
+    int LY, BLK, LIN, AF, NTH, NSTG;
     bool WITH_PREV, BWD_PREV, GRAD_IN, GRAD_TOP, NEED_SB, H_OUT, H_IN, H_TOP, H_PREV, H_GE, H_TILE, TILE_OUT, LATE;
 };
 __host__ __device__ constexpr MxtTraits mxt_traits(int L, int kind, int idx, int nfix) {
@@ -89,9 +114,11 @@ __host__ __device__ constexpr MxtTraits mxt_traits(int L, int kind, int idx, int
     t.H_PREV = t.WITH_PREV && MXT_H_READ_F_EVEN;                   // F_{2l}: the pass over layer l-1 starts from H_{l-1}
     t.H_GE = kind == PH_G && t.BLK == 0 && mxt_g_even_reads_h(t.LY, nfix);    // G_{2l}: H_l beside X_l and the adjacency
     t.H_TILE = t.H_PREV || t.H_GE;                                 // ... in a tile of its own
-    // every full-tile record a phase writes (F_{2l}: X_l, Q_l, H_l; G_{2l+1}: d(x0 + H); G_{2l}, l >= 1: d X_l) leaves through ONE
-    // staging tile per wavefront, one record after the other
+    // every full-tile record a phase writes (F_{2l}: X_l, Q_l, H_l; G_{2l+1}: d(x0 + H); G_{2l}, l >= 1: d X_l) leaves through a staging
+    // tile per wavefront: one per record where the tile is the pending storage (MXT_STAGE_EARLY), else one for all, one record after
+    // the other
     t.TILE_OUT = t.WITH_PREV || t.H_OUT || (kind == PH_G && t.BLK == 1) || t.BWD_PREV;
+    t.NSTG = !t.TILE_OUT ? 0 : (MXT_STAGE_EARLY && t.WITH_PREV ? 3 : 1);
     t.AF = t.H_IN ? 0 : 220;                                   // floats of the narrow chain's adjacency tile
     // wide chain.  G_{2l} carries the most state (the theta-gradient tiles): its records are read from LDS where they are used instead of
     // being held in registers across the sample, the next sample's records are requested once the region is free, and d X_l is stored

@@ -55,3 +55,11 @@ for k, reg in enumerate(regions):
     tot.update(c)
     print(k, 'VALU', sum(c[x] for x in VALU), dict(sorted(c.items())))
 print('total VALU', sum(tot[x] for x in VALU), dict(sorted(tot.items())))
+# the kernel's resources (the compiler's comment block behind s_endpgm) and the branches inside the tile loop
+res = {}
+for ln in s[a:]:
+    m = re.match(r'\s*; (NumVgprs|NumAgprs|ScratchSize|Occupancy): (\d+)', ln)
+    if m and m.group(1) not in res: res[m.group(1)] = int(m.group(2))
+    if len(res) == 4: break
+print('resources', res, 'branches in loop', sum(1 for t in loop if re.match(r'\s*s_c?branch', t)),
+      'branches in kernel', sum(1 for t in body if re.match(r'\s*s_c?branch', t)))
