@@ -153,6 +153,18 @@ class LogoArgs(C.Structure):
                 ("dropout_p", C.c_float), ("seed", C.c_uint64), ("step", C.c_uint64), ("training", C.c_int32)]
 
 
+class DvgtformerShape(C.Structure):
+    _fields_ = [("batch", C.c_int64), ("num_nodes", C.c_int32), ("time_length", C.c_int32), ("num_heads", C.c_int32),
+                ("num_blocks", C.c_int32), ("d_model", C.c_int32 * 2), ("d_ff", C.c_int32 * 2), ("lambda_param", C.c_float)]
+
+
+class DvgtformerArgs(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("dpred", C.c_void_p), ("params", C.c_void_p), ("grads", C.c_void_p),
+                ("pred", C.c_void_p), ("loss", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("global_batch", C.c_int64), ("sample_offset", C.c_int64), ("dropout_p", C.c_float), ("seed", C.c_uint64),
+                ("step", C.c_uint64), ("training", C.c_int32)]
+
+
 class StagnnShape(C.Structure):
     _fields_ = [("batch", C.c_int64), ("num_nodes", C.c_int32), ("time_length", C.c_int32), ("hidden_dim", C.c_int32),
                 ("output_dim", C.c_int32), ("num_heads", C.c_int32), ("threshold", C.c_float)]
@@ -253,6 +265,7 @@ _SIGNATURES = {
     **_step_family("grucm", GrucmShape, GrucmArgs),
     **_step_family("hiercorrpool", HiercorrpoolShape, HiercorrpoolArgs, tap_offset=True, bn_state_count=True),
     **_step_family("logo", LogoShape, LogoArgs, tap_offset=True),
+    **_step_family("dvgtformer", DvgtformerShape, DvgtformerArgs, tap_offset=True),
     "rulgnn_sgemm_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                    C.c_int32, C.c_int32, C.c_void_p]),
     "rulgnn_sgemm_mode": (C.c_int, [C.c_int32]),
@@ -358,7 +371,7 @@ _SIGNATURES = {
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
 # index -> ctypes mirror, in the order of the RULGNN_STRUCT_* constants of include/rulgnn.h (rulgnn_struct_size)
-STRUCTS = (StgcnShape, StgcnTrainArgs, AdamArgs, StmsgcnShape, StmsgcnArgs, AstgcnnShape, AstgcnnArgs, FcstgnnShape, FcstgnnArgs, RgcnuShape, RgcnuArgs, StnetShape, StnetArgs, SagcnShape, SagcnArgs, StagnnShape, StagnnArgs, HagcnShape, HagcnArgs, BilstmShape, BilstmArgs, StconvShape, StgnnShape, GruShape, GruArgs, GrucmShape, GrucmArgs, AgcntfShape, AgcntfArgs, HiercorrpoolShape, HiercorrpoolArgs, LogoShape, LogoArgs)
+STRUCTS = (StgcnShape, StgcnTrainArgs, AdamArgs, StmsgcnShape, StmsgcnArgs, AstgcnnShape, AstgcnnArgs, FcstgnnShape, FcstgnnArgs, RgcnuShape, RgcnuArgs, StnetShape, StnetArgs, SagcnShape, SagcnArgs, StagnnShape, StagnnArgs, HagcnShape, HagcnArgs, BilstmShape, BilstmArgs, StconvShape, StgnnShape, GruShape, GruArgs, GrucmShape, GrucmArgs, AgcntfShape, AgcntfArgs, HiercorrpoolShape, HiercorrpoolArgs, LogoShape, LogoArgs, DvgtformerShape, DvgtformerArgs)
 
 _lib = None
 

@@ -3,7 +3,7 @@ algorithms/algorithms.py:29-48 does it (lookup by name in this module's globals,
 ``NotImplementedError("Algorithm not found: ...")`` otherwise).
 
 The ST_GCN (reference algorithms/algorithms.py:465-490), STMSGCN (:546-571), ASTGCNN (:139-163), FC_STGNN (:51-76), HAGCN (:222-248),
-ST_Conv (:195-220), GRU_CM (:355-380), AGCN_TF (:574-599), HierCorrPool (:79-104) and LOGO (:107-136) wrappers are implemented:
+ST_Conv (:195-220), GRU_CM (:355-380), AGCN_TF (:574-599), HierCorrPool (:79-104), LOGO (:107-136) and DVGTformer (:326-351) wrappers are implemented:
 the hot paths this package accelerates.  The classes keep the reference contract -- constructor
 ``(configs, hparams, device)``, attributes ``model`` / ``optimizer`` / ``hparams`` / ``mse``,
 ``update(X, y, epoch) -> {'loss': float}`` -- so the reference's trainer can drive it unchanged."""
@@ -30,6 +30,7 @@ from .sagcn import SAGCN_model
 from .agcntf import AGCN_TF_model
 from .hiercorrpool import HierCorrPool_model
 from .logo import LOGO_model
+from .dvgtformer import DVGTformer_model
 from .stagnn import STAGNN_model
 
 
@@ -339,4 +340,13 @@ class GRU_CM(_FusedAlgorithm):
     needs_train_mode = "dropout"
 
 
-_NOT_ALGORITHMS = {"Algorithm", "GRU_CM_model", "FusedAdam", "RGCNU_model", "STNet_model", "SAGCN_model", "AGCN_TF_model", "HierCorrPool_model", "LOGO_model", "STAGNN_model", "ST_GCN_model", "STMSGCN_model", "ASTGCNN_model", "FC_STGNN_RUL", "HAGCN_model", "ST_Conv_model", "STGNN_model", "get_algorithm_class", "torch", "nn", "annotations", "math", "_lib", "deferred_weight_gradients"}
+class DVGTformer(_FusedAlgorithm):
+    """DVGTformer training wrapper (reference algorithms.py:326-351; the fused encoder kernels of csrc/dvgtformer.hip, the head on the
+    shared SGEMM): MSE only, Adam with weight decay, no scheduler.  No BatchNorm and no recurrence: samples are independent and data
+    parallelism is the plain ``[gradient | loss]`` bucket."""
+    model_class = DVGTformer_model
+    supports_graphs = False
+    needs_train_mode = "dropout"
+
+
+_NOT_ALGORITHMS = {"Algorithm", "DVGTformer_model", "GRU_CM_model", "FusedAdam", "RGCNU_model", "STNet_model", "SAGCN_model", "AGCN_TF_model", "HierCorrPool_model", "LOGO_model", "STAGNN_model", "ST_GCN_model", "STMSGCN_model", "ASTGCNN_model", "FC_STGNN_RUL", "HAGCN_model", "ST_Conv_model", "STGNN_model", "get_algorithm_class", "torch", "nn", "annotations", "math", "_lib", "deferred_weight_gradients"}

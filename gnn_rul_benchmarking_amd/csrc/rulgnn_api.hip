@@ -332,6 +332,8 @@ size_t rulgnn_struct_size(int32_t which) {
     case RULGNN_STRUCT_HIERCORRPOOL_ARGS: return sizeof(rulgnn_hiercorrpool_args);
     case RULGNN_STRUCT_LOGO_SHAPE: return sizeof(rulgnn_logo_shape);
     case RULGNN_STRUCT_LOGO_ARGS: return sizeof(rulgnn_logo_args);
+    case RULGNN_STRUCT_DVGTFORMER_SHAPE: return sizeof(rulgnn_dvgtformer_shape);
+    case RULGNN_STRUCT_DVGTFORMER_ARGS: return sizeof(rulgnn_dvgtformer_args);
     default: return 0;
     }
 }
@@ -1036,6 +1038,31 @@ int rulgnn_logo_backward_f32(const rulgnn_logo_shape* shape, const rulgnn_logo_a
 }
 int rulgnn_logo_fwdbwd_f32(const rulgnn_logo_shape* shape, const rulgnn_logo_args* args, const rulgnn_adam_args* opt, void* stream) {
     return step_fwdbwd<Logo>(shape, args, opt, stream);
+}
+
+// ---- DVGTformer ------------------------------------------------------------------------------------------
+int64_t rulgnn_dvgtformer_param_count(const rulgnn_dvgtformer_shape* shape) { return Dvgtformer::param_count(shape); }
+size_t rulgnn_dvgtformer_workspace_bytes(const rulgnn_dvgtformer_shape* shape) { return Dvgtformer::workspace_bytes(shape); }
+int64_t rulgnn_dvgtformer_tap_offset(const rulgnn_dvgtformer_shape* shape, int32_t which) { return Dvgtformer::tap_offset(shape, which); }
+
+int Dvgtformer::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
+    RULGNN_TRY(shape_status(shape));
+    if (a->global_batch < shape->batch || a->sample_offset < 0) return RULGNN_EINVAL;
+    if (!(a->dropout_p >= 0.f && a->dropout_p < 1.f)) return RULGNN_EINVAL;
+    for (const void* p : {(const void*)a->y, (const void*)a->dpred, (const void*)a->loss})
+        if (!opt_aligned(p)) return RULGNN_EALIGN;
+    return check_step_ptrs(a, shape->batch, bwd);
+}
+
+int rulgnn_dvgtformer_forward_f32(const rulgnn_dvgtformer_shape* shape, const rulgnn_dvgtformer_args* args, void* stream) {
+    return step_forward<Dvgtformer>(shape, args, stream);
+}
+int rulgnn_dvgtformer_backward_f32(const rulgnn_dvgtformer_shape* shape, const rulgnn_dvgtformer_args* args, void* stream) {
+    return step_backward<Dvgtformer>(shape, args, stream);
+}
+int rulgnn_dvgtformer_fwdbwd_f32(const rulgnn_dvgtformer_shape* shape, const rulgnn_dvgtformer_args* args, const rulgnn_adam_args* opt,
+                                 void* stream) {
+    return step_fwdbwd<Dvgtformer>(shape, args, opt, stream);
 }
 
 size_t rulgnn_rul_metrics_workspace_bytes(int64_t n) { return rul_metrics_workspace_bytes(n); }

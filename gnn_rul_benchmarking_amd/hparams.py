@@ -1,7 +1,7 @@
 """Hyper-parameter tables, looked up by dataset name then dataset id, like the reference's
 configs/hparams.py:3-7 (``get_hparams_class(name)(dataset_id)`` -> object with ``train_params`` and
 ``alg_hparams`` dicts keyed by ``--GNN_method``; unknown dataset -> NotImplementedError, unknown id ->
-ValueError).  Only the ST_GCN, STMSGCN, ASTGCNN, FC_STGNN, HAGCN, ST_Conv, STGNN, RGCNU, GRU_CM, STNet, SAGCN, AGCN_TF, STAGNN, HierCorrPool and LOGO rows are restated (the methods this package
+ValueError).  Only the ST_GCN, STMSGCN, ASTGCNN, FC_STGNN, HAGCN, ST_Conv, STGNN, RGCNU, GRU_CM, STNet, SAGCN, AGCN_TF, STAGNN, HierCorrPool, LOGO and DVGTformer rows are restated (the methods this package
 implements).
 
 PHM2012 / XJTU_SY rows are the reference's (configs/hparams.py:223,238,... and :334,349,...; STMSGCN
@@ -102,6 +102,10 @@ class _Table:
             self.train_params['LOGO'] = {'num_epochs': 81, 'batch_size': 100 if dataset_id is not None else 50,
                                          'weight_decay': 1e-4 if dataset_id is not None else 0, 'learning_rate': 1e-3, 'theta': theta}
             self.alg_hparams['LOGO'] = {'patch_size': ps, 'num_patch': npatch, 'num_nodes': self._astgcnn_nodes, 'hidden_dim': hidden}
+            # configs/hparams.py:25,44 / 63,84 / 103,124 / 143,164 (C-MAPSS FD001-4) and :189,208 (N-CMAPSS): one row everywhere
+            self.train_params['DVGTformer'] = dict(_ASTGCNN_TRAIN)
+            self.alg_hparams['DVGTformer'] = {'num_nodes': self._astgcnn_nodes, 'time_length': 50, 'd_model': [144, 248], 'num_heads': 4,
+                                              'lambda_param': 0.5, 'd_ff': [72, 124], 'dropout': 0.1, 'num_blocks': 3}
         if dataset_id in self._stnet_rows:
             self.train_params['STNet'] = {'num_epochs': 81, 'batch_size': 100, 'weight_decay': 1e-2, 'learning_rate': 1e-2}
             num_patch, patch_size, num_nodes, nperseg, input_dim = self._stnet_rows[dataset_id]

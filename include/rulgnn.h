@@ -338,6 +338,8 @@ size_t rulgnn_stgcn_train_args_size(void);
 #define RULGNN_STRUCT_HIERCORRPOOL_ARGS 30
 #define RULGNN_STRUCT_LOGO_SHAPE 31
 #define RULGNN_STRUCT_LOGO_ARGS 32
+#define RULGNN_STRUCT_DVGTFORMER_SHAPE 33
+#define RULGNN_STRUCT_DVGTFORMER_ARGS 34
 size_t rulgnn_struct_size(int32_t which);
 
 /* Profiling aid: the training step is a chain of 4*num_layers+1 phase kernels:
@@ -1342,6 +1344,75 @@ int rulgnn_logo_forward_f32(const rulgnn_logo_shape *shape, const rulgnn_logo_ar
 int rulgnn_logo_backward_f32(const rulgnn_logo_shape *shape, const rulgnn_logo_args *args, void *stream);
 /* LOGO.update body (algorithms.py:125-136); with `opt` also Adam on the flat parameter buffer. */
 int rulgnn_logo_fwdbwd_f32(const rulgnn_logo_shape *shape, const rulgnn_logo_args *args, const rulgnn_adam_args *opt, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * DVGTformer path (reference models/DVGTformer/Model.py, algorithms/algorithms.py:326-351; wired to C-MAPSS FD001-4 and N-CMAPSS,
+ * configs/hparams.py:25,44,63,84,103,124,143,164,189,208).
+ *
+ * N = num_nodes, L = time_length, H = num_heads, (dt, ds) = d_model, (ft, fs) = d_ff, lam = lambda_param.
+ * x [batch, N, L] -> linear_t over L, transpose, linear_x over N, append the row t_v and the column x_v -> X [L+1][N+1];
+ * A_temp = Pearson correlation of the rows of X, A_spat = of its columns, both BEFORE the positional encoding is added (a constant row
+ * gives 0 / 0 = NaN, as the reference; no epsilon); X += PE (a constant: for i = 0, 2, .. < N columns i, i+1 = sin, cos of
+ * pos / 10000^(2 i / (N+1))).  num_blocks x (temporal half on tokens L+1 / features N+1 with A_temp, spatial half on the transposed
+ * sample with A_spat); a half: per head P = softmax((1-lam) softmax(Q K^T / sqrt(d)) + lam softmax(relu(A))), head = P V,
+ * O = concat W_O^T + b, R = LayerNorm1(O) + X, D = dropout(R) (temporal halves only, training != 0), out = LayerNorm2(FF(D)) + D with
+ * FF = Linear - erf GELU - Linear, LayerNorm eps 1e-5.  Flatten -> Linear(100) - GELU - Linear(1).
+ *
+ * Flat parameter buffer in the reference's named_parameters() order (6 + num_blocks (12 H + 20) + 4 tensors; 214 at 3 blocks, 4 heads):
+ *   t_v[N] | x_v[L+1] | linear_t.{weight[L][L], bias[L]} | linear_x.{weight[N][N], bias[N]} | the temporal halves, then the spatial
+ *   halves, each H x linears_Q.{weight[d][F], bias[d]}, H x linears_K, H x linears_V, W_O.{weight[F][H d], bias[F]}, layer_norm1.{weight,
+ *   bias}[F], layer_norm2.{weight, bias}[F], feed_forward.0.{weight[ff][F], bias[ff]}, feed_forward.2.{weight[F][ff], bias[F]} with
+ *   F = N+1 (temporal) / L+1 (spatial) | output_layer.0.{weight[100][(L+1)(N+1)], bias[100]} | output_layer.2.{weight[100], bias[1]}
+ * The gradient of every linears_K bias is zero in exact arithmetic and is written as an exact zero.
+ * Dropout: the counter hash of the other families, key = dropout_layer_key(seed, step, block); element [b][l][n] of a temporal half is
+ * dropped where lowbias32(counter ^ key) < round(p 2^32), counter = ((sample_offset + b) (L+1) + l) (N+1) + n mod 2^32.
+ * Limits: 2 <= N <= RULGNN_DVGT_MAX_NODES, 1 <= L <= RULGNN_DVGT_MAX_TIME, H <= RULGNN_DVGT_MAX_HEADS, num_blocks <=
+ * RULGNN_DVGT_MAX_BLOCKS, d_model <= RULGNN_DVGT_MAX_D_MODEL, d_ff <= RULGNN_DVGT_MAX_D_FF: at these maxima a sample's backward state
+ * is 146 KB of the compute unit's 160 KB of LDS (csrc/dvgtformer_device.hpp: DvLds).  RULGNN_EUNSUPPORTED beyond, before any launch:
+ * the workspace query returns 0.  Deterministic: no floating-point atomics, fixed-order reductions.
+ */
+#define RULGNN_DVGT_MAX_NODES 24
+#define RULGNN_DVGT_MAX_TIME 56
+#define RULGNN_DVGT_MAX_HEADS 8
+#define RULGNN_DVGT_MAX_BLOCKS 8
+#define RULGNN_DVGT_MAX_D_MODEL 1024
+#define RULGNN_DVGT_MAX_D_FF 128
+
+typedef struct rulgnn_dvgtformer_shape {
+    int64_t batch;
+    int32_t num_nodes, time_length, num_heads, num_blocks;
+    int32_t d_model[2], d_ff[2];   /* temporal, spatial */
+    float lambda_param;
+} rulgnn_dvgtformer_shape;
+
+typedef struct rulgnn_dvgtformer_args {
+    const float *x;           /* [batch, num_nodes, time_length] */
+    const float *y;           /* [batch] targets, or NULL */
+    const float *dpred;       /* [batch] d loss / d pred (autograd backward); NULL = MSE against y */
+    const float *params;
+    float *grads;             /* same layout as params */
+    float *pred;              /* [batch] */
+    float *loss;              /* [1] sum over the batch of (pred - y)^2 / global_batch; may be NULL */
+    void *workspace;
+    size_t workspace_bytes;
+    int64_t global_batch;
+    int64_t sample_offset;    /* index of this call's first sample in the global batch (dropout counters) */
+    float dropout_p;          /* applied when training != 0 (0.1 in the reference) */
+    uint64_t seed, step;      /* dropout stream: mask = f(seed, step, block, element counter); a backward takes its forward's values */
+    int32_t training;
+} rulgnn_dvgtformer_args;
+
+int64_t rulgnn_dvgtformer_param_count(const rulgnn_dvgtformer_shape *shape);       /* < 0: invalid / unsupported */
+size_t rulgnn_dvgtformer_workspace_bytes(const rulgnn_dvgtformer_shape *shape);    /* 0: invalid / unsupported */
+/* workspace taps for the parity tests, float offsets: 0 X behind the input stage and the positional encoding [batch][L+1][N+1], 1 the
+ * encoder output (same shape); -1 otherwise */
+int64_t rulgnn_dvgtformer_tap_offset(const rulgnn_dvgtformer_shape *shape, int32_t which);
+int rulgnn_dvgtformer_forward_f32(const rulgnn_dvgtformer_shape *shape, const rulgnn_dvgtformer_args *args, void *stream);
+/* loss.backward() after a forward with the same args / workspace. */
+int rulgnn_dvgtformer_backward_f32(const rulgnn_dvgtformer_shape *shape, const rulgnn_dvgtformer_args *args, void *stream);
+/* DVGTformer.update body (algorithms.py:341-351); with `opt` also Adam on the flat parameter buffer. */
+int rulgnn_dvgtformer_fwdbwd_f32(const rulgnn_dvgtformer_shape *shape, const rulgnn_dvgtformer_args *args, const rulgnn_adam_args *opt,
+                                 void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * RUL test metrics on the device.
