@@ -165,6 +165,19 @@ class DvgtformerArgs(C.Structure):
                 ("step", C.c_uint64), ("training", C.c_int32)]
 
 
+class GdagdlShape(C.Structure):
+    _fields_ = [("batch", C.c_int64), ("num_patch", C.c_int32), ("patch_size", C.c_int32), ("num_nodes", C.c_int32), ("nperseg", C.c_int32),
+                ("input_dim", C.c_int32), ("num_gat", C.c_int32), ("gat_layer_dim", C.c_int32 * 4), ("lstm_hidden_dim", C.c_int32),
+                ("autoencoder_hidden_dim", C.c_int32), ("autoencoder_out_dim", C.c_int32)]
+
+
+class GdagdlArgs(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("dpred", C.c_void_p), ("params", C.c_void_p), ("grads", C.c_void_p),
+                ("pred", C.c_void_p), ("recon", C.c_void_p), ("loss", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_size_t), ("global_batch", C.c_int64), ("recon_weight", C.c_void_p), ("sample_offset", C.c_int64),
+                ("dropout_p", C.c_float), ("seed", C.c_uint64), ("step", C.c_uint64), ("training", C.c_int32)]
+
+
 class StagnnShape(C.Structure):
     _fields_ = [("batch", C.c_int64), ("num_nodes", C.c_int32), ("time_length", C.c_int32), ("hidden_dim", C.c_int32),
                 ("output_dim", C.c_int32), ("num_heads", C.c_int32), ("threshold", C.c_float)]
@@ -266,6 +279,7 @@ _SIGNATURES = {
     **_step_family("hiercorrpool", HiercorrpoolShape, HiercorrpoolArgs, tap_offset=True, bn_state_count=True),
     **_step_family("logo", LogoShape, LogoArgs, tap_offset=True),
     **_step_family("dvgtformer", DvgtformerShape, DvgtformerArgs, tap_offset=True),
+    **_step_family("gdagdl", GdagdlShape, GdagdlArgs, tap_offset=True),
     "rulgnn_sgemm_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                    C.c_int32, C.c_int32, C.c_void_p]),
     "rulgnn_sgemm_mode": (C.c_int, [C.c_int32]),
@@ -371,7 +385,7 @@ _SIGNATURES = {
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
 # index -> ctypes mirror, in the order of the RULGNN_STRUCT_* constants of include/rulgnn.h (rulgnn_struct_size)
-STRUCTS = (StgcnShape, StgcnTrainArgs, AdamArgs, StmsgcnShape, StmsgcnArgs, AstgcnnShape, AstgcnnArgs, FcstgnnShape, FcstgnnArgs, RgcnuShape, RgcnuArgs, StnetShape, StnetArgs, SagcnShape, SagcnArgs, StagnnShape, StagnnArgs, HagcnShape, HagcnArgs, BilstmShape, BilstmArgs, StconvShape, StgnnShape, GruShape, GruArgs, GrucmShape, GrucmArgs, AgcntfShape, AgcntfArgs, HiercorrpoolShape, HiercorrpoolArgs, LogoShape, LogoArgs, DvgtformerShape, DvgtformerArgs)
+STRUCTS = (StgcnShape, StgcnTrainArgs, AdamArgs, StmsgcnShape, StmsgcnArgs, AstgcnnShape, AstgcnnArgs, FcstgnnShape, FcstgnnArgs, RgcnuShape, RgcnuArgs, StnetShape, StnetArgs, SagcnShape, SagcnArgs, StagnnShape, StagnnArgs, HagcnShape, HagcnArgs, BilstmShape, BilstmArgs, StconvShape, StgnnShape, GruShape, GruArgs, GrucmShape, GrucmArgs, AgcntfShape, AgcntfArgs, HiercorrpoolShape, HiercorrpoolArgs, LogoShape, LogoArgs, DvgtformerShape, DvgtformerArgs, GdagdlShape, GdagdlArgs)
 
 _lib = None
 

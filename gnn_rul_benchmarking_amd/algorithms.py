@@ -3,7 +3,7 @@ algorithms/algorithms.py:29-48 does it (lookup by name in this module's globals,
 ``NotImplementedError("Algorithm not found: ...")`` otherwise).
 
 The ST_GCN (reference algorithms/algorithms.py:465-490), STMSGCN (:546-571), ASTGCNN (:139-163), FC_STGNN (:51-76), HAGCN (:222-248),
-ST_Conv (:195-220), GRU_CM (:355-380), AGCN_TF (:574-599), HierCorrPool (:79-104), LOGO (:107-136) and DVGTformer (:326-351) wrappers are implemented:
+ST_Conv (:195-220), GRU_CM (:355-380), AGCN_TF (:574-599), HierCorrPool (:79-104), LOGO (:107-136), DVGTformer (:326-351) and GDAGDL (:519-544) wrappers are implemented:
 the hot paths this package accelerates.  The classes keep the reference contract -- constructor
 ``(configs, hparams, device)``, attributes ``model`` / ``optimizer`` / ``hparams`` / ``mse``,
 ``update(X, y, epoch) -> {'loss': float}`` -- so the reference's trainer can drive it unchanged."""
@@ -31,6 +31,7 @@ from .agcntf import AGCN_TF_model
 from .hiercorrpool import HierCorrPool_model
 from .logo import LOGO_model
 from .dvgtformer import DVGTformer_model
+from .gdagdl import GDAGDL_model
 from .stagnn import STAGNN_model
 
 
@@ -349,4 +350,18 @@ class DVGTformer(_FusedAlgorithm):
     needs_train_mode = "dropout"
 
 
-_NOT_ALGORITHMS = {"Algorithm", "DVGTformer_model", "GRU_CM_model", "FusedAdam", "RGCNU_model", "STNet_model", "SAGCN_model", "AGCN_TF_model", "HierCorrPool_model", "LOGO_model", "STAGNN_model", "ST_GCN_model", "STMSGCN_model", "ASTGCNN_model", "FC_STGNN_RUL", "HAGCN_model", "ST_Conv_model", "STGNN_model", "get_algorithm_class", "torch", "nn", "annotations", "math", "_lib", "deferred_weight_gradients"}
+class GDAGDL(_FusedAlgorithm):
+    """GDAGDL training wrapper (reference algorithms.py:519-544; the front end and the fused graph-attention kernels of csrc/gdagdl.hip,
+    the one-direction LSTM of csrc/bilstm.hip, matrix-core GEMMs): MSE + the auto-encoder's reconstruction loss, Adam with weight decay
+    -- which never touches ``node_importance_linear`` (no gradient in the reference).  No BatchNorm and no recurrence along the batch:
+    samples are independent; in data parallel the reconstruction term is averaged over the GLOBAL batch's elements."""
+    model_class = GDAGDL_model
+    supports_graphs = False
+    needs_train_mode = "dropout"
+
+    def _reference_loss(self, X, y):
+        predicted_RUL, reconstruction_losss = self.model(X, train=True)       # algorithms.py:536-539
+        return self.mse(predicted_RUL, y) + reconstruction_losss
+
+
+_NOT_ALGORITHMS = {"Algorithm", "GDAGDL_model", "DVGTformer_model","GRU_CM_model", "FusedAdam", "RGCNU_model", "STNet_model", "SAGCN_model", "AGCN_TF_model", "HierCorrPool_model", "LOGO_model", "STAGNN_model", "ST_GCN_model", "STMSGCN_model", "ASTGCNN_model", "FC_STGNN_RUL", "HAGCN_model", "ST_Conv_model", "STGNN_model", "get_algorithm_class", "torch", "nn", "annotations", "math", "_lib", "deferred_weight_gradients"}

@@ -19,12 +19,12 @@ namespace rulgnn {
 //   run(s, a, mode, stream)                 mode bit 0: forward, bit 1: backward; checks the workspace size before its first launch
 //   check_args(s, a, fwd, bwd)              what the entries refuse before run(): shape_status, then the args' own fields (defined in
 //                                           rulgnn_api.hip on its pointer checks; s and a are not null)
-//   adam_first, adam_frozen_tail(s)         the fused step's Adam updates the flat floats [adam_first, param_count - adam_frozen_tail)
+//   adam_first(s), adam_frozen_tail(s)      the fused step's Adam updates the flat floats [adam_first, param_count - adam_frozen_tail)
 template <typename S, typename A>
 struct StepFamily {
     using Shape = S;
     using Args = A;
-    static constexpr int64_t adam_first = 0;
+    static int64_t adam_first(const S*) { return 0; }
     static int64_t adam_frozen_tail(const S*) { return 0; }
 };
 
@@ -97,7 +97,7 @@ struct Stgnn : StepFamily<rulgnn_stgnn_shape, rulgnn_stmsgcn_args> {
 };
 struct Stnet : StepFamily<rulgnn_stnet_shape, rulgnn_stnet_args> {
     // cnn.{weight, bias} (the first 3 entries) have no gradient in the reference (`grad is None`): torch's Adam leaves them untouched
-    static constexpr int64_t adam_first = 3;
+    static int64_t adam_first(const Shape*) { return 3; }
     static int shape_status(const Shape* s);
     static int64_t param_count(const Shape* s);
     static size_t workspace_bytes(const Shape* s);
@@ -165,6 +165,16 @@ struct Logo : StepFamily<rulgnn_logo_shape, rulgnn_logo_args> {
     static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
 };
 struct Dvgtformer : StepFamily<rulgnn_dvgtformer_shape, rulgnn_dvgtformer_args> {
+    static int shape_status(const Shape* s);
+    static int64_t param_count(const Shape* s);
+    static size_t workspace_bytes(const Shape* s);
+    static int64_t tap_offset(const Shape* s, int which);
+    static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
+    static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
+};
+struct Gdagdl : StepFamily<rulgnn_gdagdl_shape, rulgnn_gdagdl_args> {
+    // node_importance_linear.{weight, bias} (the first f + 1 entries) have no gradient in the reference: torch's Adam leaves them untouched
+    static int64_t adam_first(const Shape* s);
     static int shape_status(const Shape* s);
     static int64_t param_count(const Shape* s);
     static size_t workspace_bytes(const Shape* s);

@@ -115,7 +115,8 @@ static int step_fwdbwd(const typename F::Shape* shape, const typename F::Args* a
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int rc = F::run(shape, args, 3, st);
     if (rc != RULGNN_OK || !opt) return rc;
-    return adam_tail(opt, args->grads, F::adam_first, F::param_count(shape) - F::adam_first - F::adam_frozen_tail(shape), st);
+    const int64_t first = F::adam_first(shape);
+    return adam_tail(opt, args->grads, first, F::param_count(shape) - first - F::adam_frozen_tail(shape), st);
 }
 }  // extern "C++"
 
@@ -334,6 +335,8 @@ size_t rulgnn_struct_size(int32_t which) {
     case RULGNN_STRUCT_LOGO_ARGS: return sizeof(rulgnn_logo_args);
     case RULGNN_STRUCT_DVGTFORMER_SHAPE: return sizeof(rulgnn_dvgtformer_shape);
     case RULGNN_STRUCT_DVGTFORMER_ARGS: return sizeof(rulgnn_dvgtformer_args);
+    case RULGNN_STRUCT_GDAGDL_SHAPE: return sizeof(rulgnn_gdagdl_shape);
+    case RULGNN_STRUCT_GDAGDL_ARGS: return sizeof(rulgnn_gdagdl_args);
     default: return 0;
     }
 }
@@ -1063,6 +1066,34 @@ int rulgnn_dvgtformer_backward_f32(const rulgnn_dvgtformer_shape* shape, const r
 int rulgnn_dvgtformer_fwdbwd_f32(const rulgnn_dvgtformer_shape* shape, const rulgnn_dvgtformer_args* args, const rulgnn_adam_args* opt,
                                  void* stream) {
     return step_fwdbwd<Dvgtformer>(shape, args, opt, stream);
+}
+
+// ---- GDAGDL ----------------------------------------------------------------------------------------------
+int64_t rulgnn_gdagdl_param_count(const rulgnn_gdagdl_shape* shape) { return Gdagdl::param_count(shape); }
+size_t rulgnn_gdagdl_workspace_bytes(const rulgnn_gdagdl_shape* shape) { return Gdagdl::workspace_bytes(shape); }
+int64_t rulgnn_gdagdl_tap_offset(const rulgnn_gdagdl_shape* shape, int32_t which) { return Gdagdl::tap_offset(shape, which); }
+
+int Gdagdl::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
+    RULGNN_TRY(shape_status(shape));
+    if (a->global_batch < shape->batch || a->sample_offset < 0) return RULGNN_EINVAL;
+    if (!(a->dropout_p >= 0.f && a->dropout_p < 1.f)) return RULGNN_EINVAL;
+    // the dropout counter of the global batch's last attention entry must fit 32 bits
+    const double entries = (double)shape->num_patch * shape->num_nodes * shape->num_nodes;
+    if (((double)a->sample_offset + (double)shape->batch) * entries > 4294967296.0 || (double)a->global_batch * entries > 4294967296.0)
+        return RULGNN_EUNSUPPORTED;
+    for (const void* p : {(const void*)a->y, (const void*)a->dpred, (const void*)a->loss, (const void*)a->recon, (const void*)a->recon_weight})
+        if (!opt_aligned(p)) return RULGNN_EALIGN;
+    return check_step_ptrs(a, shape->batch, bwd);
+}
+
+int rulgnn_gdagdl_forward_f32(const rulgnn_gdagdl_shape* shape, const rulgnn_gdagdl_args* args, void* stream) {
+    return step_forward<Gdagdl>(shape, args, stream);
+}
+int rulgnn_gdagdl_backward_f32(const rulgnn_gdagdl_shape* shape, const rulgnn_gdagdl_args* args, void* stream) {
+    return step_backward<Gdagdl>(shape, args, stream);
+}
+int rulgnn_gdagdl_fwdbwd_f32(const rulgnn_gdagdl_shape* shape, const rulgnn_gdagdl_args* args, const rulgnn_adam_args* opt, void* stream) {
+    return step_fwdbwd<Gdagdl>(shape, args, opt, stream);
 }
 
 size_t rulgnn_rul_metrics_workspace_bytes(int64_t n) { return rul_metrics_workspace_bytes(n); }

@@ -17,12 +17,12 @@
 
 #include "sgemm_mfma.hpp"
 #include "families_host.hpp"
+#include "stnet_device.hpp"        // SB, the STFT magnitude, the back end's small kernels (shared with gdagdl.hip)
 
 namespace rulgnn {
 
 namespace {
 
-constexpr int SB = 256;
 constexpr int SN_MAX_CHEB = 4, SN_MAXSEG = 64, SN_MAXFR = 64, SN_MAXNODE = 33;
 constexpr float SN_THRESHOLD = 0.7f;            // Model.py:106
 
@@ -120,37 +120,15 @@ int sn_geometry(const rulgnn_stnet_shape* s, SnGeom* g) {
 // ---- STFT magnitude, node weights, mask: one workgroup per (sample, patch) --------------------------------------------------------
 __global__ __launch_bounds__(SB) void sn_stft_kernel(SnGeom g, const float* __restrict__ x, const float* __restrict__ prm, float* __restrict__ ws) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
-    const int P = g.P, ns = g.nseg, half = ns / 2, N = g.N, f = g.f, tid = threadIdx.x;
-    float* xp = sm;                       // [P + ns] reflect-padded patch
-    float* cs = xp + P + ns;              // [ns] cos(2 pi j / ns)
-    float* sn = cs + ns;                  // [ns] sin
-    float* win = sn + ns;                 // [ns] periodic Hann
-    float* mg = win + ns;                 // [N][f]
-    for (int j = tid; j < ns; j += SB) {
-        const float a = 6.283185307179586f * (float)j / (float)ns;
-        cs[j] = cosf(a);
-        sn[j] = sinf(a);
-        win[j] = 0.5f - 0.5f * cosf(a);
-    }
+    const int P = g.P, ns = g.nseg, N = g.N, f = g.f, tid = threadIdx.x;
+    const StftLds l = stft_carve(sm, P, ns);
+    float* mg = l.end;                    // [N][f]
+    stft_tables(l, ns, tid);
     for (int64_t gi = blockIdx.x; gi < g.G; gi += gridDim.x) {
-        const float* px = x + gi * P;
-        for (int i = tid; i < P + ns; i += SB) {
-            int q = i - half;                                   // reflect without repeating the edge sample (torch 'reflect')
-            if (q < 0) q = -q;
-            if (q >= P) q = 2 * (P - 1) - q;
-            xp[i] = px[q];
-        }
+        stft_load_patch(l, x + gi * P, P, ns, tid);
         __syncthreads();
         for (int i = tid; i < N * f; i += SB) {
-            const int k = i / f, t = i % f;
-            float re = 0.f, im = 0.f;
-            for (int m = 0; m < ns; ++m) {
-                const float v = xp[t * ns + m] * win[m];
-                const int j = (k * m) % ns;
-                re = fmaf(v, cs[j], re);
-                im = fmaf(-v, sn[j], im);
-            }
-            const float a = sqrtf(re * re + im * im);
+            const float a = stft_magnitude(l, ns, i / f, i % f);
             mg[i] = a;
             ws[g.w_mag + gi * N * f + i] = a;
         }
@@ -207,93 +185,7 @@ __global__ __launch_bounds__(SB) void sn_terms_bwd_kernel(SnGeom g, int C, const
     }
 }
 
-__global__ void sn_bias_act_kernel(float* __restrict__ z, const float* __restrict__ bias, int64_t rows, int C, int relu) {
-    const int64_t n = rows * C;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        const float v = z[i] + bias[i % C];
-        z[i] = relu ? fmaxf(v, 0.f) : v;
-    }
-}
-
-__global__ void sn_relu_bwd_kernel(float* __restrict__ d, const float* __restrict__ h, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        d[i] = h[i] > 0.f ? d[i] : 0.f;
-}
-
-// a *= w[0], b *= w[0]: the reconstruction term's gradients under a weight other than 1 (autograd path)
-__global__ void sn_scale2_kernel(float* __restrict__ a, float* __restrict__ b, int64_t n, const float* __restrict__ w) {
-    const float s = w[0];
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        a[i] *= s;
-        b[i] *= s;
-    }
-}
-__global__ void sn_add_kernel(float* __restrict__ a, const float* __restrict__ b, int64_t n) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) a[i] += b[i];
-}
-
-// reconstruction error: partial sums of (Yo - Yp)^2 (one per workgroup, fixed assignment), d Yp = -2 s (Yo - Yp), d Yo = +2 s (Yo - Yp)
-__global__ __launch_bounds__(SB) void sn_recon_kernel(const float* __restrict__ yo, const float* __restrict__ yp, int64_t n, float scale,
-                                                      float* __restrict__ dyp, float* __restrict__ dyo, float* __restrict__ part) {
-    __shared__ float red[SB];
-    float a = 0.f;
-    for (int64_t i = (int64_t)blockIdx.x * SB + threadIdx.x; i < n; i += (int64_t)gridDim.x * SB) {
-        const float d = yo[i] - yp[i];
-        a = fmaf(d, d, a);
-        if (dyp) { dyp[i] = -2.f * scale * d; dyo[i] = 2.f * scale * d; }
-    }
-    red[threadIdx.x] = a;
-    __syncthreads();
-    for (int m = SB / 2; m > 0; m >>= 1) {
-        if ((int)threadIdx.x < m) red[threadIdx.x] += red[threadIdx.x + m];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) part[blockIdx.x] = red[0] * scale;
-}
-
-// head: pred = hseq_flat . w + b; squared error and d loss / d pred
-__global__ __launch_bounds__(SB) void sn_head_kernel(SnGeom g, const float* __restrict__ hseq, const float* __restrict__ prm, const float* __restrict__ y,
-                                                     float* __restrict__ pred, float* __restrict__ ws, float inv_gb) {
-    __shared__ float red[SB];
-    const int n = g.E * g.T;
-    for (int64_t b = blockIdx.x; b < g.B; b += gridDim.x) {
-        float a = 0.f;
-        for (int i = threadIdx.x; i < n; i += SB) a = fmaf(hseq[b * n + i], prm[g.o_lw + i], a);
-        red[threadIdx.x] = a;
-        __syncthreads();
-        for (int m = SB / 2; m > 0; m >>= 1) {
-            if ((int)threadIdx.x < m) red[threadIdx.x] += red[threadIdx.x + m];
-            __syncthreads();
-        }
-        if (threadIdx.x == 0) {
-            const float pr = red[0] + prm[g.o_lb];
-            pred[b] = pr;
-            if (y) {
-                const float d = pr - y[b];
-                ws[g.w_sq + b] = d * d * inv_gb;
-                ws[g.w_dpred + b] = 2.f * d * inv_gb;
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// d hseq[b][i] = dpred[b] w[i]
-__global__ void sn_head_bwd_kernel(SnGeom g, const float* __restrict__ dpred, const float* __restrict__ prm, float* __restrict__ dhs) {
-    const int n = g.E * g.T;
-    const int64_t tot = g.B * n;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < tot; i += (int64_t)gridDim.x * blockDim.x)
-        dhs[i] = dpred[i / n] * prm[g.o_lw + i % n];
-}
-
-__global__ void sn_loss_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ loss) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) loss[0] = a[0] + b[0];
-}
-
-inline unsigned sn_grid(int64_t n) {
-    int64_t b = (n + SB - 1) / SB;
-    return (unsigned)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
-}
+// (bias + activation, ReLU backward, add, the reconstruction error and its gradients, the head: stnet_device.hpp)
 
 }  // namespace
 
@@ -361,7 +253,7 @@ int Stnet::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
         }
     }
     if (mode & 1) {
-        const size_t lds = sizeof(float) * ((size_t)g.P + g.nseg + 3 * (size_t)g.nseg + (size_t)g.N * g.f);
+        const size_t lds = sizeof(float) * (stft_lds_floats(g.P, g.nseg) + (size_t)g.N * g.f);
         if (lds > 48 * 1024) return RULGNN_EUNSUPPORTED;
         RULGNN_TRY(fill_f32(ws + g.w_one + 3, 1, 0.0f, st));
         hipLaunchKernelGGL(sn_stft_kernel, dim3(ggrid), dim3(SB), lds, st, g, a->x, prm, ws);
@@ -394,7 +286,7 @@ int Stnet::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
         (void)block_sum((const float*)(ws + g.w_rsq), (int64_t)g.rblocks, ws + g.w_one + 1, st);
         RULGNN_LAUNCH_OK();
         RULGNN_TRY(bilstm_forward(&ls, &la, st, 1));
-        hipLaunchKernelGGL(sn_head_kernel, dim3((unsigned)(g.B < 1024 ? g.B : 1024)), dim3(SB), 0, st, g, (const float*)(ws + g.w_hseq), prm, a->y,
+        hipLaunchKernelGGL(sn_head_kernel<SnGeom>, dim3((unsigned)(g.B < 1024 ? g.B : 1024)), dim3(SB), 0, st, g, (const float*)(ws + g.w_hseq), prm, a->y,
                            a->pred, ws, inv_gb);
         if (a->recon) hipLaunchKernelGGL(sn_loss_kernel, dim3(1), dim3(1), 0, st, (const float*)(ws + g.w_one + 1), (const float*)(ws + g.w_one + 3),
                                          a->recon);          // w_one + 3 holds 0
@@ -414,7 +306,7 @@ int Stnet::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
         // head
         RULGNN_TRY(sgemm_splitk(dpred, 0, 1, ws + g.w_hseq, 1, E * g.T, gr + g.o_lw, E * g.T, 1, E * g.T, (int)g.B, false, split, st));
         RULGNN_TRY(sgemm_splitk(dpred, 0, 1, one, 0, 0, gr + g.o_lb, 1, 1, 1, (int)g.B, false, split, st));
-        hipLaunchKernelGGL(sn_head_bwd_kernel, dim3(sn_grid(g.B * E * g.T)), dim3(SB), 0, st, g, dpred, prm, ws + g.w_dhs);
+        hipLaunchKernelGGL(sn_head_bwd_kernel<SnGeom>, dim3(sn_grid(g.B * E * g.T)), dim3(SB), 0, st, g, dpred, prm, ws + g.w_dhs);
         RULGNN_LAUNCH_OK();
         la.dout = ws + g.w_dhs;
         la.dx = ws + g.w_dH;

@@ -340,6 +340,8 @@ size_t rulgnn_stgcn_train_args_size(void);
 #define RULGNN_STRUCT_LOGO_ARGS 32
 #define RULGNN_STRUCT_DVGTFORMER_SHAPE 33
 #define RULGNN_STRUCT_DVGTFORMER_ARGS 34
+#define RULGNN_STRUCT_GDAGDL_SHAPE 35
+#define RULGNN_STRUCT_GDAGDL_ARGS 36
 size_t rulgnn_struct_size(int32_t which);
 
 /* Profiling aid: the training step is a chain of 4*num_layers+1 phase kernels:
@@ -1413,6 +1415,78 @@ int rulgnn_dvgtformer_backward_f32(const rulgnn_dvgtformer_shape *shape, const r
 /* DVGTformer.update body (algorithms.py:341-351); with `opt` also Adam on the flat parameter buffer. */
 int rulgnn_dvgtformer_fwdbwd_f32(const rulgnn_dvgtformer_shape *shape, const rulgnn_dvgtformer_args *args, const rulgnn_adam_args *opt,
                                  void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * GDAGDL path (reference models/GDAGDL/Model.py, algorithms/algorithms.py:519-544; wired to the bearing datasets PHM2012 and XJTU_SY).
+ *
+ * T = num_patch, P = patch_size, N = num_nodes = nperseg/2 + 1, f = input_dim = 1 + P/nperseg, C_0 = f, C_l = gat_layer_dim[l-1].
+ * x [batch, T * P] -> per (sample, patch) graph: mag [N][f] = |STFT| as STNet's (n_fft = hop = win = nperseg, periodic Hann,
+ * reflect-centred) -> c = mag - mean_f(mag), pcc = (c reshape(c, [f][N])) / (|c_i| |c_j|) (the reference reshapes the second operand
+ * where a Pearson matrix would transpose it, Model.py:51: kept; no epsilon: an all-zero patch gives NaN) ->
+ * ni = pcc (mag w_ni + b_ni) [N] -> m_i = (ni_i > 0) (false for NaN), adjacency M = m m^T -> num_gat layers
+ *   Z = h W^T + b, u_ij = a1 . Z_i + a2 . Z_j + b_att, Pm = softmax_j(leakyrelu(u, 0.1)), Q = Pm o D o M, h = ELU(Q Z)
+ * (D: dropout keep mask / (1 - p), training != 0 only; the mask is applied behind the softmax: rows do not sum to one and a row with
+ * m_i = 0 is exactly 0) -> Y_o [batch, T, N C_L] -> encoder Linear/ReLU x3 + Linear (N C_L -> A -> A/2 -> A/4 -> O), decoder its mirror,
+ * reconstruction = mean((Y_o - decoder(H))^2) -> LSTM(O -> lstm_hidden) over the T patches -> Linear(lstm_hidden * T -> 1).
+ * GDAGDL.update: loss = MSE(pred, y) + reconstruction.  The mask passes no gradient: node_importance_linear.{weight, bias} have grad
+ * None in the reference (their entries of `grads` are written as zeros, and the optimizer must leave them alone).
+ *
+ * Flat parameter buffer: the two gradless tensors FIRST, then the reference's named_parameters() order:
+ *   node_importance_linear.{weight[f], bias[1]} | gat_layers.l.{linear.weight[C_l+1][C_l], linear.bias[C_l+1], attention.weight[2 C_l+1]
+ *   (a1 then a2), attention.bias[1]} ... | encoder.{0,2,4,6}.{weight[out][in], bias} | decoder.{0,2,4,6}.{weight, bias} |
+ *   lstm.{weight_ih_l0[4E][O], weight_hh_l0[4E][E], bias_ih_l0[4E], bias_hh_l0[4E]} | linear.{weight[E * T], bias[1]}
+ * Dropout: the counter hash of the other families, key = dropout_layer_key(seed, step, layer); Pm_ij of graph (b, t) is dropped where
+ * lowbias32(counter ^ key) < round(p 2^32), counter = (((sample_offset + b) T + t) N + i) N + j; a call whose counters would pass
+ * 2^32 is refused (RULGNN_EUNSUPPORTED).
+ * Limits (RULGNN_EUNSUPPORTED beyond, before any launch; the workspace query returns 0): even nperseg <= RULGNN_GDAGDL_MAX_NPERSEG
+ * dividing patch_size, f <= RULGNN_GDAGDL_MAX_FRAMES, 1 .. RULGNN_GDAGDL_MAX_LAYERS GAT layers of width <= RULGNN_GDAGDL_MAX_WIDTH,
+ * lstm_hidden <= RULGNN_GDAGDL_MAX_LSTM_HIDDEN, autoencoder_hidden / autoencoder_out <= RULGNN_GDAGDL_MAX_AE_WIDTH.  At the maxima
+ * (N = 33, width 512) one graph's backward state is 150 KB of a compute unit's 160 KB of LDS (csrc/gdagdl.hip: gd_att_lds_floats).
+ * num_nodes / input_dim must equal the STFT's shape.  Deterministic: no floating-point atomics, fixed-order reductions.
+ */
+#define RULGNN_GDAGDL_MAX_NPERSEG 64
+#define RULGNN_GDAGDL_MAX_FRAMES 64
+#define RULGNN_GDAGDL_MAX_LAYERS 4
+#define RULGNN_GDAGDL_MAX_WIDTH 512
+#define RULGNN_GDAGDL_MAX_LSTM_HIDDEN 128
+#define RULGNN_GDAGDL_MAX_AE_WIDTH 1024
+
+typedef struct rulgnn_gdagdl_shape {
+    int64_t batch;
+    int32_t num_patch, patch_size, num_nodes, nperseg, input_dim;
+    int32_t num_gat, gat_layer_dim[4];
+    int32_t lstm_hidden_dim, autoencoder_hidden_dim, autoencoder_out_dim;
+} rulgnn_gdagdl_shape;
+
+typedef struct rulgnn_gdagdl_args {
+    const float *x;           /* [batch, num_patch * patch_size] */
+    const float *y;           /* [batch] targets, or NULL */
+    const float *dpred;       /* [batch] d loss / d pred (autograd backward); NULL = MSE against y */
+    const float *params;
+    float *grads;
+    float *pred;              /* [batch] */
+    float *recon;             /* [1] reconstruction MSE, averaged over the GLOBAL batch's elements (this shard's share); may be NULL */
+    float *loss;              /* [1] this shard's share of MSE(pred, y) + reconstruction; may be NULL */
+    void *workspace;
+    size_t workspace_bytes;
+    int64_t global_batch;
+    const float *recon_weight; /* backward only: [1] device scalar d loss / d reconstruction; NULL = 1, the reference's loss */
+    int64_t sample_offset;    /* index of this call's first sample in the global batch (dropout counters) */
+    float dropout_p;          /* applied when training != 0 (0.5 in the reference, hard-coded there) */
+    uint64_t seed, step;      /* dropout stream: mask = f(seed, step, layer, element counter); a backward takes its forward's values */
+    int32_t training;
+} rulgnn_gdagdl_args;
+
+int64_t rulgnn_gdagdl_param_count(const rulgnn_gdagdl_shape *shape);         /* < 0: invalid / unsupported */
+size_t rulgnn_gdagdl_workspace_bytes(const rulgnn_gdagdl_shape *shape);      /* 0: invalid / unsupported */
+/* workspace taps for the parity tests, float offsets: 0 mag [batch][T][N][f], 1 ni [batch][T][N], 2 mask (same), 3 Y_o
+ * [batch][T][N C_L], 4 H = the encoder output [batch][T][O]; -1 otherwise */
+int64_t rulgnn_gdagdl_tap_offset(const rulgnn_gdagdl_shape *shape, int32_t which);
+int rulgnn_gdagdl_forward_f32(const rulgnn_gdagdl_shape *shape, const rulgnn_gdagdl_args *args, void *stream);
+/* loss.backward() after a forward with the same args / workspace. */
+int rulgnn_gdagdl_backward_f32(const rulgnn_gdagdl_shape *shape, const rulgnn_gdagdl_args *args, void *stream);
+/* GDAGDL.update body (algorithms.py:535-544); with `opt` also Adam on the flat parameter buffer behind the two gradless tensors. */
+int rulgnn_gdagdl_fwdbwd_f32(const rulgnn_gdagdl_shape *shape, const rulgnn_gdagdl_args *args, const rulgnn_adam_args *opt, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * RUL test metrics on the device.
