@@ -3,7 +3,7 @@ algorithms/algorithms.py:29-48 does it (lookup by name in this module's globals,
 ``NotImplementedError("Algorithm not found: ...")`` otherwise).
 
 The ST_GCN (reference algorithms/algorithms.py:465-490), STMSGCN (:546-571), ASTGCNN (:139-163), FC_STGNN (:51-76), HAGCN (:222-248),
-ST_Conv (:195-220), GRU_CM (:355-380), AGCN_TF (:574-599), HierCorrPool (:79-104), LOGO (:107-136), DVGTformer (:326-351) and GDAGDL (:519-544) wrappers are implemented:
+ST_Conv (:195-220), GRU_CM (:355-380), AGCN_TF (:574-599), HierCorrPool (:79-104), LOGO (:107-136), DVGTformer (:326-351), GDAGDL (:519-544) and GAT_LSTM (:492-517) wrappers are implemented:
 the hot paths this package accelerates.  The classes keep the reference contract -- constructor
 ``(configs, hparams, device)``, attributes ``model`` / ``optimizer`` / ``hparams`` / ``mse``,
 ``update(X, y, epoch) -> {'loss': float}`` -- so the reference's trainer can drive it unchanged."""
@@ -32,6 +32,7 @@ from .hiercorrpool import HierCorrPool_model
 from .logo import LOGO_model
 from .dvgtformer import DVGTformer_model
 from .gdagdl import GDAGDL_model
+from .gatlstm import GAT_LSTM_model
 from .stagnn import STAGNN_model
 
 
@@ -364,4 +365,13 @@ class GDAGDL(_FusedAlgorithm):
         return self.mse(predicted_RUL, y) + reconstruction_losss
 
 
-_NOT_ALGORITHMS = {"Algorithm", "GDAGDL_model", "DVGTformer_model","GRU_CM_model", "FusedAdam", "RGCNU_model", "STNet_model", "SAGCN_model", "AGCN_TF_model", "HierCorrPool_model", "LOGO_model", "STAGNN_model", "ST_GCN_model", "STMSGCN_model", "ASTGCNN_model", "FC_STGNN_RUL", "HAGCN_model", "ST_Conv_model", "STGNN_model", "get_algorithm_class", "torch", "nn", "annotations", "math", "_lib", "deferred_weight_gradients"}
+class GAT_LSTM(_FusedAlgorithm):
+    """GAT_LSTM training wrapper (reference algorithms.py:492-517; the patch statistics and the banded graph-attention kernels of
+    csrc/gatlstm.hip, the one-direction LSTMs of csrc/bilstm.hip, matrix-core GEMMs): MSE only, Adam with weight decay.  No BatchNorm and
+    no recurrence along the batch: samples are independent and data parallelism is the plain ``[gradient | loss]`` bucket."""
+    model_class = GAT_LSTM_model
+    supports_graphs = False
+    needs_train_mode = "dropout"
+
+
+_NOT_ALGORITHMS = {"Algorithm", "GAT_LSTM_model", "GDAGDL_model", "DVGTformer_model","GRU_CM_model", "FusedAdam", "RGCNU_model", "STNet_model", "SAGCN_model", "AGCN_TF_model", "HierCorrPool_model", "LOGO_model", "STAGNN_model", "ST_GCN_model", "STMSGCN_model", "ASTGCNN_model", "FC_STGNN_RUL", "HAGCN_model", "ST_Conv_model", "STGNN_model", "get_algorithm_class", "torch", "nn", "annotations", "math", "_lib", "deferred_weight_gradients"}

@@ -182,6 +182,14 @@ struct Gdagdl : StepFamily<rulgnn_gdagdl_shape, rulgnn_gdagdl_args> {
     static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
     static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
 };
+struct Gatlstm : StepFamily<rulgnn_gatlstm_shape, rulgnn_gatlstm_args> {
+    static int shape_status(const Shape* s);
+    static int64_t param_count(const Shape* s);
+    static size_t workspace_bytes(const Shape* s);
+    static int64_t tap_offset(const Shape* s, int which);
+    static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
+    static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
+};
 
 int64_t hagcn_graph_param_count(const rulgnn_hagcn_shape* s);
 size_t hagcn_workspace_bytes(const rulgnn_hagcn_shape* s);

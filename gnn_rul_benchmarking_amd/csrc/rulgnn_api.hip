@@ -337,6 +337,8 @@ size_t rulgnn_struct_size(int32_t which) {
     case RULGNN_STRUCT_DVGTFORMER_ARGS: return sizeof(rulgnn_dvgtformer_args);
     case RULGNN_STRUCT_GDAGDL_SHAPE: return sizeof(rulgnn_gdagdl_shape);
     case RULGNN_STRUCT_GDAGDL_ARGS: return sizeof(rulgnn_gdagdl_args);
+    case RULGNN_STRUCT_GATLSTM_SHAPE: return sizeof(rulgnn_gatlstm_shape);
+    case RULGNN_STRUCT_GATLSTM_ARGS: return sizeof(rulgnn_gatlstm_args);
     default: return 0;
     }
 }
@@ -1094,6 +1096,34 @@ int rulgnn_gdagdl_backward_f32(const rulgnn_gdagdl_shape* shape, const rulgnn_gd
 }
 int rulgnn_gdagdl_fwdbwd_f32(const rulgnn_gdagdl_shape* shape, const rulgnn_gdagdl_args* args, const rulgnn_adam_args* opt, void* stream) {
     return step_fwdbwd<Gdagdl>(shape, args, opt, stream);
+}
+
+// ---- GAT_LSTM --------------------------------------------------------------------------------------------
+int64_t rulgnn_gatlstm_param_count(const rulgnn_gatlstm_shape* shape) { return Gatlstm::param_count(shape); }
+size_t rulgnn_gatlstm_workspace_bytes(const rulgnn_gatlstm_shape* shape) { return Gatlstm::workspace_bytes(shape); }
+int64_t rulgnn_gatlstm_tap_offset(const rulgnn_gatlstm_shape* shape, int32_t which) { return Gatlstm::tap_offset(shape, which); }
+
+int Gatlstm::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
+    RULGNN_TRY(shape_status(shape));
+    if (a->global_batch < shape->batch || a->sample_offset < 0) return RULGNN_EINVAL;
+    if (!(a->dropout_p >= 0.f && a->dropout_p < 1.f)) return RULGNN_EINVAL;
+    // the dropout counter of the global batch's last band entry must fit 32 bits
+    const double entries = 3.0 * (double)shape->num_patch;
+    if (((double)a->sample_offset + (double)shape->batch) * entries > 4294967296.0 || (double)a->global_batch * entries > 4294967296.0)
+        return RULGNN_EUNSUPPORTED;
+    for (const void* p : {(const void*)a->y, (const void*)a->dpred, (const void*)a->loss})
+        if (!opt_aligned(p)) return RULGNN_EALIGN;
+    return check_step_ptrs(a, shape->batch, bwd);
+}
+
+int rulgnn_gatlstm_forward_f32(const rulgnn_gatlstm_shape* shape, const rulgnn_gatlstm_args* args, void* stream) {
+    return step_forward<Gatlstm>(shape, args, stream);
+}
+int rulgnn_gatlstm_backward_f32(const rulgnn_gatlstm_shape* shape, const rulgnn_gatlstm_args* args, void* stream) {
+    return step_backward<Gatlstm>(shape, args, stream);
+}
+int rulgnn_gatlstm_fwdbwd_f32(const rulgnn_gatlstm_shape* shape, const rulgnn_gatlstm_args* args, const rulgnn_adam_args* opt, void* stream) {
+    return step_fwdbwd<Gatlstm>(shape, args, opt, stream);
 }
 
 size_t rulgnn_rul_metrics_workspace_bytes(int64_t n) { return rul_metrics_workspace_bytes(n); }

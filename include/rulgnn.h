@@ -342,6 +342,9 @@ size_t rulgnn_stgcn_train_args_size(void);
 #define RULGNN_STRUCT_DVGTFORMER_ARGS 34
 #define RULGNN_STRUCT_GDAGDL_SHAPE 35
 #define RULGNN_STRUCT_GDAGDL_ARGS 36
+/* (index 37 is unassigned and answers 0) */
+#define RULGNN_STRUCT_GATLSTM_SHAPE 38
+#define RULGNN_STRUCT_GATLSTM_ARGS 39
 size_t rulgnn_struct_size(int32_t which);
 
 /* Profiling aid: the training step is a chain of 4*num_layers+1 phase kernels:
@@ -1487,6 +1490,75 @@ int rulgnn_gdagdl_forward_f32(const rulgnn_gdagdl_shape *shape, const rulgnn_gda
 int rulgnn_gdagdl_backward_f32(const rulgnn_gdagdl_shape *shape, const rulgnn_gdagdl_args *args, void *stream);
 /* GDAGDL.update body (algorithms.py:535-544); with `opt` also Adam on the flat parameter buffer behind the two gradless tensors. */
 int rulgnn_gdagdl_fwdbwd_f32(const rulgnn_gdagdl_shape *shape, const rulgnn_gdagdl_args *args, const rulgnn_adam_args *opt, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * GAT_LSTM path (reference models/GAT_LSTM/Model.py, algorithms/algorithms.py:492-517; wired to the bearing datasets PHM2012 and XJTU_SY).
+ *
+ * T = num_patch, P = patch_size, C_0 = 11, C_l = hidden_dim[l-1], E_0 = C_L, E_k = lstm_hidden_dim[k-1].
+ * x [batch, T * P] -> 11 statistics per patch (Model.py:8-72, in the reference's order: mean, unbiased std, (mean sqrt|x|)^2, rms,
+ * (max - min) / 2, skewness, kurtosis, crest, clearance, shape and impulse factor; central moments from a second pass over the patch,
+ * no epsilon: a constant patch gives NaN in skewness and kurtosis, an all-zero patch also in the four factors) -> one graph per sample,
+ * T nodes, adjacency adj_ij = [|i - j| <= 1] -> num_gat layers
+ *   Z = h W^T + b, u_ij = a1 . Z_i + a2 . Z_j + c, p = softmax_j(leakyrelu(u, 0.1)) over ALL j, q = p o D o adj, h = leakyrelu(q Z, 0.01)
+ * (D: dropout keep mask / (1 - p_drop), training != 0 only; the band is applied behind the softmax: rows do not sum to one; a NaN node
+ * makes every row of its own sample NaN) -> num_lstm stacked one-layer unidirectional LSTMs over the T nodes (h0 = c0 = 0) ->
+ * Linear(E_last * T -> 1).  GAT_LSTM.update: loss = MSE(pred, y).
+ *
+ * Flat parameter buffer = the reference's named_parameters() order:
+ *   gat_layers.l.{linear.weight[C_l+1][C_l], linear.bias[C_l+1], attention.weight[2 C_l+1] (a1 then a2), attention.bias[1]} ... |
+ *   lstm_layers.k.{weight_ih_l0[4 E_k+1][E_k], weight_hh_l0[4 E_k+1][E_k+1], bias_ih_l0[4 E_k+1], bias_hh_l0[4 E_k+1]} ... | fc.{weight[E_last * T], bias[1]}
+ * Dropout: the counter hash of the other families, key = dropout_layer_key(seed, step, layer); only the band is drawn: p_ij of sample b
+ * is dropped where lowbias32(counter ^ key) < round(p_drop 2^32), counter = ((sample_offset + b) T + i) 3 + (j - i + 1); a call whose
+ * counters would pass 2^32 is refused (RULGNN_EUNSUPPORTED).
+ * Limits (RULGNN_EUNSUPPORTED beyond, before any launch; the workspace query returns 0): num_patch <= RULGNN_GATLSTM_MAX_NUM_PATCH,
+ * 4 <= patch_size <= RULGNN_GATLSTM_MAX_PATCH_SIZE (the reference itself divides by zero for patch_size <= 3), 1 ..
+ * RULGNN_GATLSTM_MAX_LAYERS GAT layers of width <= RULGNN_GATLSTM_MAX_WIDTH, 1 .. RULGNN_GATLSTM_MAX_LSTM_LAYERS LSTM layers of hidden
+ * width <= RULGNN_GATLSTM_MAX_LSTM_HIDDEN.  The leakyrelu slope of the logits is 0.1 (the reference's default, which every row uses).
+ * Deterministic: no floating-point atomics, fixed-order reductions.
+ */
+#define RULGNN_GATLSTM_MAX_NUM_PATCH 128
+#define RULGNN_GATLSTM_MIN_PATCH_SIZE 4
+#define RULGNN_GATLSTM_MAX_PATCH_SIZE 2048
+#define RULGNN_GATLSTM_MAX_LAYERS 4
+#define RULGNN_GATLSTM_MAX_WIDTH 512
+#define RULGNN_GATLSTM_MAX_LSTM_LAYERS 3
+#define RULGNN_GATLSTM_MAX_LSTM_HIDDEN 128
+#define RULGNN_GATLSTM_TAP_LSTM (1 + RULGNN_GATLSTM_MAX_LAYERS)      /* rulgnn_gatlstm_tap_offset: behind the GAT layers' taps */
+
+typedef struct rulgnn_gatlstm_shape {
+    int64_t batch;
+    int32_t num_patch, patch_size;
+    int32_t num_gat, hidden_dim[4];
+    int32_t num_lstm, lstm_hidden_dim[3];
+} rulgnn_gatlstm_shape;
+
+typedef struct rulgnn_gatlstm_args {
+    const float *x;           /* [batch, num_patch * patch_size] */
+    const float *y;           /* [batch] targets, or NULL */
+    const float *dpred;       /* [batch] d loss / d pred (autograd backward); NULL = MSE against y */
+    const float *params;
+    float *grads;
+    float *pred;              /* [batch] */
+    float *loss;              /* [1] this shard's share of MSE(pred, y) over the global batch; may be NULL */
+    void *workspace;
+    size_t workspace_bytes;
+    int64_t global_batch;
+    int64_t sample_offset;    /* index of this call's first sample in the global batch (dropout counters) */
+    float dropout_p;          /* applied when training != 0 */
+    uint64_t seed, step;      /* dropout stream: mask = f(seed, step, layer, element counter); a backward takes its forward's values */
+    int32_t training;
+} rulgnn_gatlstm_args;
+
+int64_t rulgnn_gatlstm_param_count(const rulgnn_gatlstm_shape *shape);        /* < 0: invalid / unsupported */
+size_t rulgnn_gatlstm_workspace_bytes(const rulgnn_gatlstm_shape *shape);     /* 0: invalid / unsupported */
+/* workspace taps for the parity tests, float offsets: 0 the features [batch][T][11], 1 + l the output of GAT layer l [batch][T][C_l+1],
+ * RULGNN_GATLSTM_TAP_LSTM the last LSTM layer's output [batch][T][E_last]; -1 otherwise */
+int64_t rulgnn_gatlstm_tap_offset(const rulgnn_gatlstm_shape *shape, int32_t which);
+int rulgnn_gatlstm_forward_f32(const rulgnn_gatlstm_shape *shape, const rulgnn_gatlstm_args *args, void *stream);
+/* loss.backward() after a forward with the same args / workspace. */
+int rulgnn_gatlstm_backward_f32(const rulgnn_gatlstm_shape *shape, const rulgnn_gatlstm_args *args, void *stream);
+/* GAT_LSTM.update body (algorithms.py:508-517); with `opt` also Adam on the flat parameter buffer. */
+int rulgnn_gatlstm_fwdbwd_f32(const rulgnn_gatlstm_shape *shape, const rulgnn_gatlstm_args *args, const rulgnn_adam_args *opt, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * RUL test metrics on the device.

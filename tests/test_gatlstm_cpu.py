@@ -1,0 +1,265 @@
+"""GAT_LSTM without a GPU: the registry, the module's surface (22 names in order, a seed gives the reference's initial weights, strict
+load), the hparams rows, the C-ABI's size queries, the coverage gate at every limit and the workspace's growth per sample."""
+import ctypes as C
+import glob
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from gnn_rul_benchmarking_amd import _lib
+
+from conftest import GOLDEN
+
+import gatlstm_oracle as O
+from test_gatlstm_oracle_golden import CURVE, FULL, NAN, SMALL, load_case
+
+BASE = dict(hidden_dim=[300, 200, 100], lstm_hidden_dim=[30, 20], dropout=0.2)
+ROWS = {"PHM2012/Condition_1": (40, 64), "PHM2012/Condition_2": (80, 32), "PHM2012/Condition_3": (40, 64),
+        "XJTU_SY/Condition_1": (32, 1024), "XJTU_SY/Condition_2": (64, 512), "XJTU_SY/Condition_3": (32, 1024)}
+TINY = dict(num_patch=1, patch_size=4, hidden_dim=[1], lstm_hidden_dim=[1], dropout=0.1)
+COUNTS = {40: 105904, 80: 106704, 32: 105744, 64: 106384}
+RULGNN_EUNSUPPORTED = -2                # include/rulgnn.h
+
+
+def row_cfg(key):
+    T, P = ROWS[key]
+    return dict(BASE, num_patch=T, patch_size=P)
+
+
+def shape_of(batch, cfg):
+    s = _lib.GatlstmShape()
+    s.batch, s.num_patch, s.patch_size = batch, cfg["num_patch"], cfg["patch_size"]
+    s.num_gat, s.num_lstm = len(cfg["hidden_dim"]), len(cfg["lstm_hidden_dim"])
+    for i, c in enumerate(cfg["hidden_dim"][:4]):
+        s.hidden_dim[i] = c
+    for i, e in enumerate(cfg["lstm_hidden_dim"][:3]):
+        s.lstm_hidden_dim[i] = e
+    return s
+
+
+def test_registry_serves_the_algorithm_and_refuses_the_model():
+    from gnn_rul_benchmarking_amd import algorithms as A
+    assert A.get_algorithm_class("GAT_LSTM") is A.GAT_LSTM
+    with pytest.raises(NotImplementedError, match="Algorithm not found: GAT_LSTM_model"):
+        A.get_algorithm_class("GAT_LSTM_model")
+    assert A.GAT_LSTM.needs_train_mode == "dropout" and A.GAT_LSTM.supports_graphs is False
+
+
+@pytest.mark.parametrize("key", list(ROWS))
+def test_algorithm_construction_from_the_rows(key):
+    from gnn_rul_benchmarking_amd import algorithms as A
+    from gnn_rul_benchmarking_amd.gatlstm import GAT_LSTM_model
+    from gnn_rul_benchmarking_amd.hparams import get_hparams_class
+    from gnn_rul_benchmarking_amd.optim import FusedAdam
+    ds, did = key.split("/")
+    cfg = row_cfg(key)
+    h = get_hparams_class(ds)(did)
+    assert h.alg_hparams["GAT_LSTM"] == cfg
+    algo = A.get_algorithm_class("GAT_LSTM")(h.alg_hparams["GAT_LSTM"], h.train_params["GAT_LSTM"], "cpu")
+    assert isinstance(algo.model, GAT_LSTM_model) and isinstance(algo.optimizer, FusedAdam)
+    assert algo.hparams == h.train_params["GAT_LSTM"] and algo.model.c_family == "gatlstm" and algo.model.dropout_p == 0.2
+    assert algo.model.dropout_by_sample_offset is True and algo.model.eval_sample_independent is True and algo.model.bucket_tail == 1
+    count = COUNTS[cfg["num_patch"]]
+    lib = _lib.load()
+    assert sum(p.numel() for p in algo.model.parameters()) == lib.rulgnn_gatlstm_param_count(C.byref(shape_of(100, cfg))) == count
+    assert O.param_count(cfg) == count and algo.model.num_live == count
+    assert lib.rulgnn_gatlstm_workspace_bytes(C.byref(shape_of(100, cfg))) > 0
+    algo.eval()
+    with pytest.raises(RuntimeError, match="needs algorithm.train"):
+        algo.update(torch.zeros(2, cfg["num_patch"] * cfg["patch_size"]), torch.zeros(2, 1))
+
+
+@pytest.mark.parametrize("name", SMALL + FULL + [NAN])
+def test_a_seed_gives_the_reference_keys_and_initial_values(name):
+    """The names, their order, strict load and -- under the fixture's seed plus the maker's recorded perturbation -- the reference's
+    values: bit for bit where the fixture stores them, by the fp64 checksum of all of them where it stores the seed alone."""
+    from gnn_rul_benchmarking_amd.gatlstm import GAT_LSTM_model
+    z = load_case(name)[0]
+    cfg = json.loads(str(z["cfg_json"]))
+    seed = int(z["seed"])
+    torch.manual_seed(seed)
+    m = GAT_LSTM_model(**cfg)
+    sd = m.state_dict()
+    names = O.param_names(cfg)
+    assert list(sd.keys()) == [n for n, _ in m.named_parameters()] == list(m._layout) == names
+    assert len(names) == 4 * len(cfg["hidden_dim"]) + 4 * len(cfg["lstm_hidden_dim"]) + 2 and (name not in FULL or len(names) == 22)
+    assert {k: tuple(v.shape) for k, v in sd.items()} == O.param_shapes(cfg) and not list(m.named_buffers())
+    assert np.array_equal(m.flat_params.numpy(), np.concatenate([sd[k].numpy().ravel() for k in names]))
+    assert m.bucket.numel() == m.num_live + 1
+    g = torch.Generator().manual_seed(seed + 1000)
+    moved = {k: v.clone().add_(torch.empty_like(v).uniform_(-0.1, 0.1, generator=g)) for k, v in sd.items()}
+    flat = np.concatenate([moved[k].numpy().astype(np.float64).ravel() for k in names])
+    assert np.allclose([flat.sum(), (flat * flat).sum()], z["checksum"], rtol=1e-12, atol=0)
+    if name in SMALL:
+        for k in names:
+            assert np.array_equal(moved[k].numpy(), z["sd:" + k]), k
+        other = GAT_LSTM_model(**cfg)
+        full = {k: torch.from_numpy(z["sd:" + k]) for k in names}
+        other.load_state_dict(full, strict=True)
+        assert np.array_equal(other.state_dict()["fc.weight"].numpy(), z["sd:fc.weight"])
+        with pytest.raises(RuntimeError):
+            other.load_state_dict({k: full[k] for k in names[1:]}, strict=True)              # a missing key
+        with pytest.raises(RuntimeError):
+            other.load_state_dict(dict(full, **{"fc.extra": torch.zeros(1)}), strict=True)   # an extra key
+    else:
+        assert m.num_live == O.param_count(cfg)
+
+
+def test_hparams_rows_equal_the_reference():
+    from gnn_rul_benchmarking_amd.hparams import get_hparams_class
+    z = np.load(os.path.join(GOLDEN, "gatlstm_hparams_rows.npz"))
+    rows = json.loads(str(z["rows_json"]))
+    assert sorted(rows) == sorted(ROWS)
+    for key, ref in rows.items():
+        ds, did = key.split("/")
+        h = get_hparams_class(ds)(did)
+        assert h.train_params["GAT_LSTM"] == ref["train_params"] and h.alg_hparams["GAT_LSTM"] == ref["alg_hparams"] == row_cfg(key), key
+        assert h.train_params["GAT_LSTM"] == {'num_epochs': 81, 'batch_size': 100, 'weight_decay': 1e-4, 'learning_rate': 1e-4}
+    assert sorted(json.loads(str(z["absent_json"]))) == ["CMAPSS/FD001", "CMAPSS/FD002", "CMAPSS/FD003", "CMAPSS/FD004", "NCMAPSS/None"]
+    for h in [get_hparams_class("CMAPSS")(d) for d in ("FD001", "FD002", "FD003", "FD004")] + [get_hparams_class("NCMAPSS")(None)]:
+        assert "GAT_LSTM" not in h.alg_hparams and "GAT_LSTM" not in h.train_params
+
+
+LIMIT_NAMES = (("MAX_NUM_PATCH", "max_num_patch"), ("MIN_PATCH_SIZE", "min_patch_size"), ("MAX_PATCH_SIZE", "max_patch_size"),
+               ("MAX_LAYERS", "max_layers"), ("MAX_WIDTH", "max_width"), ("MAX_LSTM_LAYERS", "max_lstm_layers"),
+               ("MAX_LSTM_HIDDEN", "max_lstm_hidden"))
+
+
+def test_limits_are_stated_once_and_admit_the_six_rows():
+    from gnn_rul_benchmarking_amd.gatlstm import LIMITS
+    lib = _lib.load()
+    header = open(os.path.join(os.path.dirname(__file__), "..", "include", "rulgnn.h")).read()
+    assert len(LIMITS) == len(LIMIT_NAMES)
+    for name, key in LIMIT_NAMES:
+        assert f"#define RULGNN_GATLSTM_{name} {LIMITS[key]}\n" in header
+    assert header.count("#define RULGNN_GATLSTM_M") == len(LIMIT_NAMES)
+    for key in ROWS:
+        for B in (1, 100, 1024):
+            assert lib.rulgnn_gatlstm_workspace_bytes(C.byref(shape_of(B, row_cfg(key)))) > 0
+            assert lib.rulgnn_gatlstm_param_count(C.byref(shape_of(B, row_cfg(key)))) == O.param_count(row_cfg(key))
+
+
+def test_coverage_gate_every_limit_plus_one():
+    from gnn_rul_benchmarking_amd.gatlstm import LIMITS, within_limits
+    lib = _lib.load()
+
+    def query(cfg, B=3):
+        s = shape_of(B, cfg)
+        pc, ws = lib.rulgnn_gatlstm_param_count(C.byref(s)), lib.rulgnn_gatlstm_workspace_bytes(C.byref(s))
+        assert (pc < 0) == (ws == 0) and (lib.rulgnn_gatlstm_tap_offset(C.byref(s), 1) < 0) == (ws == 0)
+        assert within_limits(cfg["num_patch"], cfg["patch_size"], cfg["hidden_dim"], cfg["lstm_hidden_dim"]) == (ws > 0)
+        if ws == 0:                                    # refused by the entries too, before any launch (no device is needed to be told so)
+            a = _lib.GatlstmArgs()
+            rcs = {lib.rulgnn_gatlstm_forward_f32(C.byref(s), C.byref(a), None), lib.rulgnn_gatlstm_backward_f32(C.byref(s), C.byref(a), None),
+                   lib.rulgnn_gatlstm_fwdbwd_f32(C.byref(s), C.byref(a), None, None)}
+            assert rcs == {RULGNN_EUNSUPPORTED}
+        return ws > 0
+
+    assert query(TINY)                                                      # every lower limit at once (num_patch = 1: the band is the diagonal)
+    assert query(dict(TINY, num_patch=2))
+    assert not query(dict(TINY, hidden_dim=[])) and not query(dict(TINY, lstm_hidden_dim=[])) and not query(dict(TINY, hidden_dim=[0]))
+    assert not query(dict(TINY, lstm_hidden_dim=[0])) and not query(dict(TINY, num_patch=0))
+    W, E = LIMITS["max_width"], LIMITS["max_lstm_hidden"]
+    top = dict(num_patch=LIMITS["max_num_patch"], patch_size=LIMITS["max_patch_size"], hidden_dim=[W] * LIMITS["max_layers"],
+               lstm_hidden_dim=[E] * LIMITS["max_lstm_layers"], dropout=0.1)
+    assert query(top)                                                       # every upper limit at once
+    for base in (top, TINY):
+        assert not query(dict(base, num_patch=LIMITS["max_num_patch"] + 1))
+        assert not query(dict(base, patch_size=LIMITS["min_patch_size"] - 1)) and not query(dict(base, patch_size=LIMITS["max_patch_size"] + 1))
+        assert not query(dict(base, hidden_dim=[1] * (LIMITS["max_layers"] + 1)))
+        assert not query(dict(base, hidden_dim=[W + 1])) and not query(dict(base, hidden_dim=[1, W + 1]))
+        assert not query(dict(base, lstm_hidden_dim=[E + 1])) and not query(dict(base, lstm_hidden_dim=[1, E + 1]))
+        assert not query(dict(base, lstm_hidden_dim=[1] * (LIMITS["max_lstm_layers"] + 1)))
+    assert all(query(row_cfg(k)) for k in ROWS)
+    ws = lambda b: lib.rulgnn_gatlstm_workspace_bytes(C.byref(shape_of(b, row_cfg("PHM2012/Condition_2"))))      # noqa: E731
+    assert ws(0) > 0 and ws(1024) > ws(100) > ws(1) >= ws(0) and ws(-1) == 0
+
+
+def test_dropout_counters_that_do_not_fit_are_refused():
+    """(sample_offset + batch) 3 T and global_batch 3 T must fit 32 bits: refused by all three entries before any launch."""
+    lib = _lib.load()
+    cfg = row_cfg("PHM2012/Condition_2")
+    s = shape_of(2, cfg)
+    a = _lib.GatlstmArgs()
+    a.global_batch, a.sample_offset = 2, (1 << 32) // (3 * 80)
+    rcs = {lib.rulgnn_gatlstm_forward_f32(C.byref(s), C.byref(a), None), lib.rulgnn_gatlstm_backward_f32(C.byref(s), C.byref(a), None),
+           lib.rulgnn_gatlstm_fwdbwd_f32(C.byref(s), C.byref(a), None, None)}
+    assert rcs == {RULGNN_EUNSUPPORTED}
+    a.sample_offset, a.global_batch = 0, (1 << 32) // (3 * 80) + 1
+    assert lib.rulgnn_gatlstm_forward_f32(C.byref(s), C.byref(a), None) == RULGNN_EUNSUPPORTED
+
+
+@pytest.mark.parametrize("key", ["PHM2012/Condition_1", "PHM2012/Condition_2", "XJTU_SY/Condition_1"])
+def test_workspace_grows_by_the_stated_tensors_and_nothing_pair_shaped(key):
+    """Per sample: feat + sum_l (Z_l + h_l) + the LSTM outputs, d Z and two d h buffers of the widest layer, two floats of the head and the
+    LSTMs' own tapes -- and nothing T^2-shaped: the upper bound below is computed from the shapes and has no T^2 term, while the
+    reference's first pair tensor alone is T^2 2 C_1 floats per sample."""
+    lib = _lib.load()
+    cfg = row_cfg(key)
+    T, Cs, Es = cfg["num_patch"], cfg["hidden_dim"], cfg["lstm_hidden_dim"]
+    per = (lib.rulgnn_gatlstm_workspace_bytes(C.byref(shape_of(2048, cfg))) - lib.rulgnn_gatlstm_workspace_bytes(C.byref(shape_of(1024, cfg)))) / 4 / 1024
+    graph = T * (11 + 2 * sum(Cs) + sum(Es)) + 3 * T * max(Cs + Es) + 2
+    ins = [Cs[-1]] + Es[:-1]
+    lstm = sum(T * (3 * 2 * 4 * e + 4 * 2 * e) for e in Es)                     # bilstm.hip: gi, gates, dgates [2][4 E]; c, tanh c, h, h_prev [2][E]
+    # (the slack: the split-K scratch of the weight-gradient GEMMs, the model's and the LSTMs', also grows with the rows)
+    assert graph + lstm <= per <= 1.05 * (graph + lstm)
+    assert per < T * T * 2 * Cs[0] and ins
+    s = shape_of(7, cfg)
+    offs = [lib.rulgnn_gatlstm_tap_offset(C.byref(s), i) for i in range(7)]
+    assert offs[0] == 0 and offs[4] == -1 and offs[6] == -1 and all(o >= 0 for o in offs[:4] + offs[5:6]) and len(set(offs[:4] + offs[5:6])) == 5
+    assert offs[1] - offs[0] >= 7 * T * 11 + 7 * T * Cs[0]                       # feat, then Z_0, then h_0
+
+
+def test_out_of_limit_model_constructs_and_is_refused_before_the_library_is_touched(monkeypatch):
+    from gnn_rul_benchmarking_amd.gatlstm import GAT_LSTM_model
+    m = GAT_LSTM_model(**dict(TINY, hidden_dim=[513]))
+    monkeypatch.setattr(GAT_LSTM_model, "_require_device", lambda self, x: None)       # the limits answer before any device call
+    monkeypatch.setattr(_lib, "load", lambda: (_ for _ in ()).throw(AssertionError("library touched")))
+    with pytest.raises(RuntimeError, match="do not cover this configuration"):
+        m(torch.zeros(2, 4))
+    with pytest.raises(RuntimeError, match="do not cover this configuration"):
+        m.fused_mse_step(torch.zeros(2, 4), torch.zeros(2))
+    assert not m._bufs
+    for bad in (dict(TINY, patch_size=3), dict(TINY, hidden_dim=[1] * 5), dict(TINY, lstm_hidden_dim=[1] * 4), dict(TINY, alpha=0.2)):
+        other = GAT_LSTM_model(**bad)                                                  # patch_size <= 3 raises in the reference; here it constructs
+        with pytest.raises(RuntimeError, match="do not cover this configuration"):
+            other(torch.zeros(2, bad["num_patch"] * bad["patch_size"]))
+
+
+def test_cpu_input_raises():
+    from gnn_rul_benchmarking_amd.gatlstm import GAT_LSTM_model
+    m = GAT_LSTM_model(**TINY)
+    with pytest.raises(RuntimeError, match="HIP path only"):
+        m(torch.zeros(2, 4))
+    with pytest.raises(RuntimeError, match="HIP path only"):
+        m.fused_mse_step(torch.zeros(2, 4), torch.zeros(2))
+
+
+def test_fixtures_hold_no_grad_key_and_stay_small():
+    """tests/test_grad_gate_cpu.py globs every fixture for ``grad:`` keys: this family's gradients are ``refgrad:`` and ``grad64:``."""
+    files = sorted(glob.glob(os.path.join(GOLDEN, "gatlstm_*.npz")))
+    assert len(files) == 18                                    # 9 fixtures; the three full-width ones in four files each
+    for f in files:
+        assert not [k for k in np.load(f).files if k.startswith("grad:")], f
+        assert os.path.getsize(f) < 1 << 20
+    for name in SMALL + FULL:
+        z, cfg, _ = load_case(name)
+        assert sorted(k[4:] for k in z.files if k.startswith("tap:")) == sorted(["feat", "lstm"] + [f"h{l}" for l in range(len(cfg["hidden_dim"]))])
+        for prefix in ("refgrad:", "grad64:"):
+            assert sorted(k[len(prefix):] for k in z.files if k.startswith(prefix)) == sorted(O.param_names(cfg))
+    for name in SMALL + FULL + [NAN]:
+        assert {"x", "y", "pred", "pred32", "pred_eval", "loss", "seed", "checksum", "tap:feat", "tap:lstm"} <= set(load_case(name)[0].files)
+    assert {"xs", "ys", "losses", "eval_pred_end", "lr", "wd"} <= set(np.load(os.path.join(GOLDEN, CURVE + ".npz")).files)
+
+
+def test_struct_sizes_are_checked_at_load():
+    lib = _lib.load()
+    assert _lib.STRUCTS_AT == {38: _lib.GatlstmShape, 39: _lib.GatlstmArgs} and len(_lib.STRUCTS) == 37
+    header = open(os.path.join(os.path.dirname(__file__), "..", "include", "rulgnn.h")).read()
+    assert "#define RULGNN_STRUCT_GATLSTM_SHAPE 38\n" in header and "#define RULGNN_STRUCT_GATLSTM_ARGS 39\n" in header
+    assert lib.rulgnn_struct_size(38) == C.sizeof(_lib.GatlstmShape) == 56
+    assert lib.rulgnn_struct_size(39) == C.sizeof(_lib.GatlstmArgs) == 120
+    assert lib.rulgnn_struct_size(37) == 0 and lib.rulgnn_struct_size(40) == 0

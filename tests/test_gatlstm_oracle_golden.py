@@ -1,0 +1,236 @@
+"""The fp64 GAT_LSTM oracle (tests/gatlstm_oracle.py) against what the reference itself produced on the CPU in fp64
+(tests/golden/make_golden_gatlstm.py): forward, taps and loss at 1e-9 relative, the hand-written backward against the reference's fp64
+autograd at 1e-9 of each tensor's largest element, the torch restatement against both, the reference's fp32 gradients within their own
+noise, the NaN case, the training curve and the dropout masks."""
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import GOLDEN
+
+import gatlstm_oracle as O
+
+SMALL = ["gatlstm_small_t3_p4_bs4", "gatlstm_small_t5_p8_bs3"]
+FULL = ["gatlstm_geom_40x64_bs2", "gatlstm_geom_80x32_bs2", "gatlstm_geom_32x1024_bs2"]
+NAN = "gatlstm_nan_t5_p8_bs3"
+CURVE = "gatlstm_train_curve_t5_p8_bs8"
+TOL64 = 1e-9              # fp64 against fp64
+RESTATE_TOL = 1e-6        # the torch restatement (fp32 included) against the fixtures
+
+_cache = {}
+
+
+def seeded_weights(cfg, seed):
+    """The maker's weights: the constructor's under the seed (the package's module draws in the reference's order), moved by the
+    recorded perturbation."""
+    from gnn_rul_benchmarking_amd.gatlstm import GAT_LSTM_model
+    torch.manual_seed(seed)
+    sd = GAT_LSTM_model(**cfg).state_dict()
+    g = torch.Generator().manual_seed(seed + 1000)
+    return {k: (v.clone() + torch.empty_like(v).uniform_(-0.1, 0.1, generator=g)).numpy() for k, v in sd.items()}
+
+
+class Case:
+    """A fixture read from ``<name>.npz`` and, where the maker split it, ``<name>_taps / _grad64 / _refgrad.npz``: one mapping."""
+
+    def __init__(self, name):
+        self._d = {}
+        for suffix in ("", "_taps", "_grad64", "_refgrad"):
+            path = os.path.join(GOLDEN, name + suffix + ".npz")
+            if os.path.exists(path):
+                z = np.load(path)
+                self._d.update({k: z[k] for k in z.files})
+        self.files = list(self._d)
+
+    def __getitem__(self, k):
+        return self._d[k]
+
+
+def load_case(name):
+    """(fixture, cfg, weights name -> fp32 array); cached and never modified."""
+    if name not in _cache:
+        z = Case(name)
+        cfg = json.loads(str(z["cfg_json"]))
+        if "sd:fc.bias" in z.files:
+            P = {k: z["sd:" + k] for k in O.param_names(cfg)}
+        else:
+            P = seeded_weights(cfg, int(z["seed"]))
+        flat = np.concatenate([P[k].astype(np.float64).ravel() for k in O.param_names(cfg)])
+        assert np.allclose([flat.sum(), (flat * flat).sum()], z["checksum"], rtol=1e-12, atol=0)
+        _cache[name] = (z, cfg, P)
+    return _cache[name]
+
+
+def oracle_run(name):
+    """The fp64 oracle's forward + backward of a fixture (train mode, dropout off), computed once."""
+    key = ("run", name)
+    if key not in _cache:
+        z, cfg, P = load_case(name)
+        _cache[key] = O.forward_backward(P, z["x"], z["y"], cfg)
+    return _cache[key]
+
+
+def rel(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
+
+
+def rel_finite(a, b):
+    """``rel`` over the entries where ``b`` is finite; NaN must sit in the same places."""
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64).reshape(np.asarray(a).shape)
+    assert np.array_equal(np.isnan(a), np.isnan(b))
+    ok = ~np.isnan(b)
+    return rel(a[ok], b[ok]) if ok.any() else 0.0
+
+
+@pytest.mark.parametrize("name", SMALL + FULL)
+def test_forward_taps_and_loss(name):
+    z, cfg, P = load_case(name)
+    o = oracle_run(name)
+    assert rel(o["pred"], z["pred"]) < TOL64 and rel(o["pred"], z["pred_eval"]) < TOL64        # dropout off: train == eval
+    assert abs(o["loss"] - float(z["loss"])) < TOL64 * float(z["loss"])
+    taps = [k[4:] for k in z.files if k.startswith("tap:")]
+    assert sorted(taps) == sorted(["feat", "lstm"] + [f"h{l}" for l in range(len(cfg["hidden_dim"]))])
+    for k in taps:
+        assert rel(o[k], z["tap:" + k]) < TOL64, k
+    assert rel(z["pred32"], z["pred"]) < 1e-5                  # the reference's own fp32 run
+    if name in SMALL:          # perturbed weights: the input matters (the full widths saturate the LSTMs: there the taps carry the comparison)
+        assert np.abs(z["pred"] - z["pred"].mean()).max() > 1e-3 * np.abs(z["pred"]).max()
+    assert rel(z["tap:lstm"][0], z["tap:lstm"][1]) > 1e-3         # ten times the forward gate of the GPU tests
+
+
+def test_the_kurtosis_column_dwarfs_the_others():
+    for name, least in zip(FULL, (100.0, 40.0, 2000.0)):
+        f = load_case(name)[0]["tap:feat"]
+        assert np.abs(f[..., 6]).max() > least and np.abs(np.delete(f, 6, -1)).max() < 50.0, name
+
+
+@pytest.mark.parametrize("name", SMALL + FULL)
+def test_backward_against_the_reference_autograd(name):
+    """Every fp64 gradient of the reference (all of them, on every fixture) at 1e-9 of the tensor's largest element; the restatement
+    in fp64 likewise; the reference's fp32 gradients within the restatement's own fp32 noise."""
+    z, cfg, P = load_case(name)
+    g64 = oracle_run(name)["grads"]
+    assert list(g64) and sorted(g64) == sorted(O.param_names(cfg)) and len(g64) == 4 * len(cfg["hidden_dim"]) + 4 * len(cfg["lstm_hidden_dim"]) + 2
+    held = [k[7:] for k in z.files if k.startswith("grad64:")]
+    assert sorted(held) == sorted(g64) == sorted(k[8:] for k in z.files if k.startswith("refgrad:"))
+    gmax = max(float(np.abs(v).max()) for v in g64.values())
+    for k in held:
+        assert g64[k].shape == z["grad64:" + k].shape
+        assert float(np.abs(z["grad64:" + k] - g64[k]).max()) <= TOL64 * max(float(np.abs(g64[k]).max()), 1e-6 * gmax), k
+    _, l64, t64 = O.torch_grads(P, z["x"], z["y"], cfg, torch.float64)
+    _, l32, t32 = O.torch_grads(P, z["x"], z["y"], cfg, torch.float32)
+    assert abs(l64 - float(z["loss"])) < TOL64 * float(z["loss"]) and abs(l32 - float(z["loss"])) < RESTATE_TOL * float(z["loss"])
+    for k in g64:
+        assert float(np.abs(t64[k] - g64[k]).max()) <= TOL64 * max(float(np.abs(g64[k]).max()), 1e-6 * gmax), k
+
+    def noise_of(k):
+        return max(float(np.abs(t32[k].astype(np.float64) - g64[k]).max()), 2.0 ** -23 * float(np.abs(g64[k]).max()))
+    for k in [k[8:] for k in z.files if k.startswith("refgrad:")]:
+        noise = max(noise_of(k), noise_of(O.noise_partner(k)) if O.noise_partner(k) else 0.0)
+        assert float(np.abs(z["refgrad:" + k].astype(np.float64) - g64[k]).max()) <= 16 * noise, k
+
+
+@pytest.mark.parametrize("name", SMALL + FULL)
+@pytest.mark.parametrize("dtype", [torch.float64, torch.float32])
+def test_torch_restatement_forward(name, dtype):
+    z, cfg, P = load_case(name)
+    Pt = {k: torch.tensor(v, dtype=dtype) for k, v in P.items()}
+    pred, taps = O.torch_forward(Pt, torch.tensor(z["x"], dtype=dtype), cfg)
+    assert rel(pred.numpy(), z["pred"]) < (TOL64 if dtype == torch.float64 else RESTATE_TOL)
+    if dtype == torch.float64:                                 # every tap at the fp64 bar
+        for k in [k[4:] for k in z.files if k.startswith("tap:")]:
+            assert rel(taps[k].numpy(), z["tap:" + k]) < TOL64, k
+    else:
+        # An extra beyond the restatement's 1e-6 check of the prediction: the features and the LSTM output of the fp32 run at 1e-5, some
+        # hundred fp32 ulps (the kurtosis column is a quotient of fp32 sums of fourth powers, the LSTM output sits behind up to 80
+        # recurrent steps).  The GAT layers' outputs of an fp32 run that rounds the logits s_i + t_j to fp32 are up to 7e-4 from fp64
+        # at the full widths (h1 at 32 x 1024): no bar is put on them here.
+        for k in ("feat", "lstm"):
+            assert rel(taps[k].numpy(), z["tap:" + k]) < 1e-5, k
+
+
+def test_nan_case_poisons_its_own_samples_only():
+    z, cfg, P = load_case(NAN)
+    o = oracle_run(NAN)
+    nan = np.isnan(z["pred_eval"]).reshape(-1)
+    assert nan.tolist() == [True, False, True] and np.isnan(z["pred32"]).reshape(-1).tolist() == nan.tolist()
+    assert np.isnan(o["pred"]).reshape(-1).tolist() == nan.tolist()
+    assert abs(float(o["pred"][1, 0]) - float(z["pred_eval"][1, 0])) < TOL64 * abs(float(z["pred_eval"][1, 0]))
+    f = z["tap:feat"]
+    assert np.array_equal(np.isnan(o["feat"]), np.isnan(f)) and np.isnan(f).sum() == 8
+    assert np.isnan(f[0, 1, [5, 6]]).all() and np.isnan(f[2, -1, 5:]).all()
+    assert rel_finite(o["feat"], f) < TOL64
+    for k in ("h0", "h1", "lstm"):                             # every row of a poisoned sample, no row of the clean one
+        assert np.isnan(z["tap:" + k][[0, 2]]).all() and not np.isnan(z["tap:" + k][1]).any(), k
+        assert rel_finite(o[k], z["tap:" + k]) < TOL64, k
+    pred, taps = O.torch_forward({k: torch.tensor(v) for k, v in P.items()}, torch.tensor(z["x"]), cfg)
+    assert np.isnan(pred.numpy()).reshape(-1).tolist() == nan.tolist()
+
+
+def test_oracle_curve_follows_the_reference_curve():
+    """Twenty steps of fp64 oracle gradients + fp64 torch Adam against the reference's fp32 run: losses at 1e-4, the checkpointed weights
+    at 1e-4 of each tensor's largest element (lr 1e-4 over twenty steps moves a weight by at most 2e-3)."""
+    z = np.load(os.path.join(GOLDEN, CURVE + ".npz"))
+    cfg = json.loads(str(z["cfg_json"]))
+    names = O.param_names(cfg)
+    P = {k: torch.tensor(z["sd0:" + k], dtype=torch.float64) for k in names}
+    opt = torch.optim.Adam(list(P.values()), lr=float(z["lr"]), weight_decay=float(z["wd"]))
+    for s in range(len(z["losses"])):
+        o = O.forward_backward({k: v.numpy() for k, v in P.items()}, z["xs"][s], z["ys"][s], cfg)
+        assert abs(o["loss"] - z["losses"][s]) < 1e-4 * z["losses"][s], s
+        for k in names:
+            P[k].grad = torch.tensor(o["grads"][k])
+        opt.step()
+        if f"sd{s + 1}:fc.bias" in z.files:
+            for k in names:
+                assert rel(P[k].numpy(), z[f"sd{s + 1}:" + k]) < 1e-4, (s, k)
+    assert sorted(int(k[2:k.index(":")]) for k in z.files if k.startswith("sd") and k.endswith(":fc.bias")) == [0, 1, 10, 20]
+
+
+def test_torch_restatement_with_keep_masks_equals_the_oracle():
+    z, cfg, P = load_case(SMALL[1])
+    keep = O.keep_masks(z["x"].shape[0], cfg, seed=5, step=3, p=0.5)
+    o = O.forward_backward(P, z["x"], z["y"], cfg, keep=keep, dropout_p=0.5)
+    pred, loss, g = O.torch_grads(P, z["x"], z["y"], cfg, torch.float64, keep=keep, dropout_p=0.5)
+    assert rel(pred, o["pred"]) < 1e-12 and abs(loss - o["loss"]) < 1e-12
+    gmax = max(float(np.abs(v).max()) for v in g.values())
+    for k in g:
+        assert float(np.abs(g[k] - o["grads"][k]).max()) < TOL64 * max(float(np.abs(g[k]).max()), 1e-6 * gmax), k
+    assert rel(o["pred"], oracle_run(SMALL[1])["pred"]) > 1e-3          # the masks do change the function
+
+
+def test_shards_sum_to_the_batch_in_the_oracle():
+    z, cfg, P = load_case(SMALL[0])
+    full = oracle_run(SMALL[0])
+    a = O.forward_backward(P, z["x"][:1], z["y"][:1], cfg, global_batch=4)
+    b = O.forward_backward(P, z["x"][1:], z["y"][1:], cfg, global_batch=4)
+    assert abs(a["loss"] + b["loss"] - full["loss"]) < 1e-12
+    gmax = max(float(np.abs(v).max()) for v in full["grads"].values())
+    for k in full["grads"]:
+        assert float(np.abs(a["grads"][k] + b["grads"][k] - full["grads"][k]).max()) < 1e-10 * gmax, k
+
+
+def test_keep_masks_share_offsets_and_steps():
+    cfg = load_case(FULL[1])[1]
+    masks = O.keep_masks(6, cfg, seed=11, step=1, p=0.2)
+    assert len(masks) == len(cfg["hidden_dim"])
+    for mk in masks:
+        assert mk.shape == (6, cfg["num_patch"], 3) and mk.size >= 1000 and 0.75 <= mk.mean() <= 0.85
+    assert not np.array_equal(masks[0], masks[1])
+    assert not np.array_equal(masks[0], O.keep_masks(6, cfg, seed=11, step=2, p=0.2)[0])
+    tail = O.keep_masks(5, cfg, seed=11, step=1, p=0.2, sample_offset=1)
+    assert np.array_equal(tail[0], masks[0][1:])               # masks follow the global sample index
+    D = O.dense_keep(masks[0])
+    assert D.shape == (6, 80, 80) and np.array_equal(D[:, 3, 2:5], masks[0][:, 3]) and (D * (1 - O.band(80)) == 1 - O.band(80)).all()
+
+
+def test_names_shapes_and_counts():
+    for name, count in zip(FULL, (105904, 106704, 105744)):
+        cfg = load_case(name)[1]
+        names = O.param_names(cfg)
+        assert len(names) == 22 and names[12] == "lstm_layers.0.weight_ih_l0" and names[-2:] == ["fc.weight", "fc.bias"]
+        assert O.param_count(cfg) == count
