@@ -5,10 +5,15 @@ and input: what tests/test_grad_gate_cpu.py, tests/test_grad_elementwise_gpu.py 
 the fp64 gradients ``g64`` and the reference's fp32 autograd ``ref32`` under the reference's parameter names, both in the fixture's
 layout.  ``ref32[k] is None`` where the fixture records that the reference produced no gradient (``hasgrad:k`` false).
 ``maxnorm_failures`` restates each family's existing whole-tensor rule (the ``check_grads`` of its GPU test file) so that the CPU test
-can show what that rule lets through.  Nothing here needs a GPU or the extension."""
+can show what that rule lets through.  Nothing here needs a GPU or the extension.
+
+``Case.x`` is the batch: the fixture's ``x``, or, for the ``*_wrap_*`` fixtures of tests/golden/make_golden_wrap.py (batches of
+thousands, ``Case.wrap``), the array rebuilt from the fixture's seed and checked against its checksum (tests/golden_io.py).
+``Case.pred64`` / ``Case.loss64`` are the oracle's own prediction and loss of the step, ``Case.oracle_seconds`` what the oracle took."""
 import functools
 import glob
 import os
+import time
 
 import numpy as np
 
@@ -58,6 +63,8 @@ def rtol_of(family):
 class Case:
     def __init__(self, family, name, z, g64, extra=None):
         self.family, self.name, self.z, self.rtol = family, name, z, rtol_of(family)
+        self.x = z["x"]                       # the stored array, or the one rebuilt from the fixture's seed (tests/golden/synth.py::Fixture)
+        self.wrap = "x_seed" in z.files       # a batch that wraps every clamped grid (tests/golden/make_golden_wrap.py)
         self.ref32, self.g64 = {}, {}
         for k, v in g64.items():
             key = "grad_nodes" if k == "grad_nodes" else "grad:" + k
@@ -71,6 +78,8 @@ class Case:
         self.zero = GG.zero_in_exact_arithmetic(self.g64, self.ref32)
         self.live = [k for k in self.g64 if k not in self.zero]
         self.extra = extra or {}
+        self.pred64 = np.asarray(self.extra["pred"], np.float64).reshape(-1) if "pred" in self.extra else None       # the oracle's own step
+        self.loss64 = float(self.extra["loss"]) if "loss" in self.extra else None
         for v in list(self.g64.values()) + [v for v in self.ref32.values() if v is not None]:
             v.setflags(write=False)
 
@@ -93,97 +102,97 @@ def _stgcn(name):
     z, sd = load_case(name)
     N, P, L, K = stgcn_dims(name, z)
     fc = O.forward(sd, z["x"].astype(np.float64), N, P, L, train=True, dropout=0.0)
-    _, dpred = O.mse_loss_and_grad(fc.pred, z["y"].astype(np.float64))
+    loss, dpred = O.mse_loss_and_grad(fc.pred, z["y"].astype(np.float64))
     g = O.backward(sd, fc, dpred)
-    return z, {k: g[k] for k in O.live_param_names(L, K)}, {"sd": sd, "dims": (N, P, L, K)}
+    return z, {k: g[k] for k in O.live_param_names(L, K)}, {"sd": sd, "dims": (N, P, L, K), "pred": fc.pred, "loss": loss}
 
 
 def _fcstgnn(name):
     from oracle import fcstgnn_oracle as O
     from test_fcstgnn_oracle_golden import load_case
     z, cfg, p = load_case(name)
-    _, g, _ = O.loss_and_grads(p, z["x"].astype(np.float64), z["y"].astype(np.float64), cfg)
-    return z, {k: g[k] for k in O.param_names(cfg)}, {"cfg": cfg, "p": p}
+    loss, g, fw = O.loss_and_grads(p, z["x"].astype(np.float64), z["y"].astype(np.float64), cfg)
+    return z, {k: g[k] for k in O.param_names(cfg)}, {"pred": fw.pred, "loss": loss, "cfg": cfg, "p": p}
 
 
 def _astgcnn(name):
     from oracle import astgcnn_oracle as O
     from test_astgcnn_oracle_golden import load_case
     z, p = load_case(name)
-    _, g, _ = O.loss_and_grads(p, z["x"].astype(np.float64), z["y"].astype(np.float64))
-    return z, {k: g[k] for k in O.live_param_names()}, {"p": p}
+    loss, g, fw = O.loss_and_grads(p, z["x"].astype(np.float64), z["y"].astype(np.float64))
+    return z, {k: g[k] for k in O.live_param_names()}, {"pred": fw.pred, "loss": loss, "p": p}
 
 
 def _stconv(name):
     from oracle import stconv_oracle as O
     from test_stconv_oracle_golden import load_case
     z, p = load_case(name)
-    _, g, _ = O.loss_and_grads(p, z["x"].astype(np.float64), z["y"].astype(np.float64))
-    return z, {k: g[k] for k in O.live_param_names()}, {"p": p}
+    loss, g, fw = O.loss_and_grads(p, z["x"].astype(np.float64), z["y"].astype(np.float64))
+    return z, {k: g[k] for k in O.live_param_names()}, {"pred": fw.pred, "loss": loss, "p": p}
 
 
 def _stmsgcn(name):
     from oracle import stmsgcn_oracle as O
     from test_stmsgcn_oracle_golden import load_case
     z, cfg, p = load_case(name)
-    _, g, _ = O.loss_and_grads(p, z["x"].astype(np.float64), z["y"].astype(np.float64), cfg)
-    return z, {k: g[k] for k in O.param_names(cfg)}, {"cfg": cfg, "p": p}
+    loss, g, fw = O.loss_and_grads(p, z["x"].astype(np.float64), z["y"].astype(np.float64), cfg)
+    return z, {k: g[k] for k in O.param_names(cfg)}, {"pred": fw.pred, "loss": loss, "cfg": cfg, "p": p}
 
 
 def _rgcnu(name):
     from oracle import rgcnu_oracle as O
     from test_rgcnu_oracle_golden import load_case
     z, cfg, p = load_case(name)
-    _, g, _ = O.loss_and_grads(p, z["x"].astype(np.float64), z["y"].astype(np.float64), cfg["alpha"])
-    return z, {k: g[k] for k in O.param_names()}, {"cfg": cfg, "p": p}
+    loss, g, fw = O.loss_and_grads(p, z["x"].astype(np.float64), z["y"].astype(np.float64), cfg["alpha"])
+    return z, {k: g[k] for k in O.param_names()}, {"pred": fw.pred, "loss": loss, "cfg": cfg, "p": p}
 
 
 def _stagnn(name):
     from oracle import stagnn_oracle as O
     from test_stagnn_oracle_golden import load_case
     z, cfg, p = load_case(name)
-    _, g, _ = O.loss_and_grads(p, z["x"].astype(np.float64), z["y"].astype(np.float64), cfg["num_heads"], cfg["threshold"])
-    return z, {k: g[k] for k in O.live_param_names(cfg["num_heads"])}, {"cfg": cfg, "p": p}
+    loss, g, fw = O.loss_and_grads(p, z["x"].astype(np.float64), z["y"].astype(np.float64), cfg["num_heads"], cfg["threshold"])
+    return z, {k: g[k] for k in O.live_param_names(cfg["num_heads"])}, {"pred": fw.pred, "loss": loss, "cfg": cfg, "p": p}
 
 
 def _stgnn(name):
     from oracle import stgnn_oracle as O
     from test_stgnn_oracle_golden import load
     z, cfg, p = load(os.path.join(GOLDEN, name + ".npz"))
-    _, g, _, _ = O.forward_backward(z["x"].astype(np.float64), z["y"].astype(np.float64), p, cfg["num_patch"], cfg["patch_size"], cfg["top_k"])
-    return z, {k: g[k] for k in O.param_names()}, {"cfg": cfg, "p": p}
+    loss, g, out, _ = O.forward_backward(z["x"].astype(np.float64), z["y"].astype(np.float64), p, cfg["num_patch"], cfg["patch_size"], cfg["top_k"])
+    return z, {k: g[k] for k in O.param_names()}, {"pred": out, "loss": loss, "cfg": cfg, "p": p}
 
 
 def _stnet(name):
     from oracle import stnet_oracle as O
     from test_stnet_oracle_golden import load_case
     z, cfg, p = load_case(name)
-    _, g, _ = O.loss_and_grads(p, z["x"].astype(np.float64), z["y"].astype(np.float64), cfg["num_patch"], cfg["patch_size"], cfg["nperseg"])
-    return z, {k: g[k] for k in O.param_names(len(cfg["Cheb_layers"]))}, {"cfg": cfg, "p": p}
+    loss, g, fw = O.loss_and_grads(p, z["x"].astype(np.float64), z["y"].astype(np.float64), cfg["num_patch"], cfg["patch_size"], cfg["nperseg"])
+    return z, {k: g[k] for k in O.param_names(len(cfg["Cheb_layers"]))}, {"pred": fw.pred, "loss": loss, "cfg": cfg, "p": p}
 
 
 def _sagcn(name):
     from oracle import sagcn_oracle as O
     from test_sagcn_oracle_golden import load_case
     z, cfg, p = load_case(name)
-    _, g, _ = O.loss_and_grads(p, z["x"].astype(np.float64), z["y"].astype(np.float64), cfg["num_patch"], cfg["patch_size"])
-    return z, {k: g[k] for k in O.param_names()}, {"cfg": cfg, "p": p}
+    loss, g, fw = O.loss_and_grads(p, z["x"].astype(np.float64), z["y"].astype(np.float64), cfg["num_patch"], cfg["patch_size"])
+    return z, {k: g[k] for k in O.param_names()}, {"pred": fw.pred, "loss": loss, "cfg": cfg, "p": p}
 
 
 def _agcntf(name):
     import agcntf_oracle as O
     from test_agcntf_oracle_golden import load_case
     z, cfg, p = load_case(name)
-    _, g, _ = O.loss_and_grads(p, z["x"].astype(np.float64), z["y"].astype(np.float64), cfg["num_patch"], cfg["patch_size"])
-    return z, {k: g[k] for k in O.param_names(cfg.get("num_heads", 1))}, {"cfg": cfg, "p": p}
+    loss, g, fw = O.loss_and_grads(p, z["x"].astype(np.float64), z["y"].astype(np.float64), cfg["num_patch"], cfg["patch_size"])
+    return z, {k: g[k] for k in O.param_names(cfg.get("num_heads", 1))}, {"pred": fw.pred, "loss": loss, "cfg": cfg, "p": p}
 
 
 def _grucm(name):
     import grucm_oracle as O
     from test_grucm_oracle_golden import load
     z, cfg, p = load(os.path.join(GOLDEN, name + ".npz"))
-    _, g, _, _ = O.forward_backward(z["x"].astype(np.float64), z["y"].astype(np.float64), p)
-    return z, {k: g[k] for k in O.param_names()}, {"cfg": cfg, "p": p}
+    loss, g, out, _ = O.forward_backward(z["x"].astype(np.float64), z["y"].astype(np.float64), p)
+    return z, {k: g[k] for k in O.param_names()}, {"pred": out, "loss": loss, "cfg": cfg, "p": p}
 
 
 def _hagcn(name):
@@ -220,8 +229,11 @@ _ORACLES = {"ST_GCN": _stgcn, "FC_STGNN": _fcstgnn, "ASTGCNN": _astgcnn, "HAGCN"
 
 @functools.lru_cache(maxsize=None)
 def case(family, name):
+    t0 = time.perf_counter()
     z, g64, extra = _ORACLES[family](name)
-    return Case(family, name, z, g64, extra)
+    c = Case(family, name, z, g64, extra)
+    c.oracle_seconds = time.perf_counter() - t0
+    return c
 
 
 # ---- each family's existing whole-tensor rule, restated -------------------------------------------------------------------------

@@ -9,13 +9,14 @@ import pytest
 
 import agcntf_oracle as O
 from test_sagcn_oracle_golden import rel
+from golden_io import load_npz
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 CASES = ["agcntf_phm_40x64_bs4", "agcntf_small_5x7_bs6", "agcntf_xjtu_like_20x256_bs3"]
 
 
 def load_case(name):
-    z = np.load(os.path.join(GOLD, name + ".npz"))
+    z = load_npz(os.path.join(GOLD, name + ".npz"))
     cfg = {k[4:]: int(z[k]) for k in z.files if k.startswith("cfg:")}
     p = {k[3:]: z[k].astype(np.float64) for k in z.files if k.startswith("sd:")}
     return z, cfg, p

@@ -9,13 +9,14 @@ import pytest
 import torch
 
 import grucm_oracle as O
+from golden_io import load_npz
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 CASES = sorted(p for p in glob.glob(os.path.join(GOLD, "grucm_*x*_bs*.npz")) if "curve" not in p)
 
 
 def load(path):
-    z = np.load(path)
+    z = load_npz(path)
     cfg = {k[4:]: int(z[k]) for k in z.files if k.startswith("cfg:")}
     p = {k[3:]: z[k].astype(np.float64) for k in z.files if k.startswith("sd:")}
     return z, cfg, p

@@ -11,14 +11,15 @@ import pytest
 from oracle import stgcn_oracle as O
 
 from conftest import GOLDEN
+from golden_io import load_npz
 
 FB_CASES = sorted(os.path.basename(p)[:-4] for p in glob.glob(os.path.join(GOLDEN, "stgcn_*x*_bs*.npz"))
-                  if "train_curve" not in p and "layers" not in p and "order" not in p)
+                  if "train_curve" not in p and "layers" not in p and "order" not in p and "_wrap_" not in p)     # (no taps: tests/grad_cases.py)
 ORDER_CASES = ["stgcn_order2_14x30_bs19", "stgcn_order3_14x30_bs10", "stgcn_order2_40x64_bs5", "stgcn_order3_9x21_layers3_bs7"]
 
 
 def load_case(name):
-    z = np.load(os.path.join(GOLDEN, name + ".npz"))
+    z = load_npz(os.path.join(GOLDEN, name + ".npz"))
     sd = {k[3:]: z[k] for k in z.files if k.startswith("sd:")}
     return z, sd
 

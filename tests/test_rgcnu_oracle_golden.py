@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from oracle import rgcnu_oracle as O
+from golden_io import load_npz
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 CASES = ["rgcnu_cmapss_14x50_bs7", "rgcnu_ncmapss_20x50_bs5", "rgcnu_small_5x12_bs9"]
@@ -18,7 +19,7 @@ def rel(a, b):
 
 
 def load_case(name):
-    z = np.load(os.path.join(GOLD, name + ".npz"))
+    z = load_npz(os.path.join(GOLD, name + ".npz"))
     cfg = {k[4:]: (float(z[k]) if k == "cfg:alpha" else int(z[k])) for k in z.files if k.startswith("cfg:")}
     p = {k[3:]: z[k].astype(np.float64) for k in z.files if k.startswith("sd:")}
     return z, cfg, p

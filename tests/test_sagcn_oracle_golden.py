@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from oracle import sagcn_oracle as O
+from golden_io import load_npz
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 CASES = ["sagcn_phm_c1like_12x16_bs5", "sagcn_phm_c2like_9x20_bs4", "sagcn_xjtu_like_4x1024_bs3", "sagcn_small_3x7_bs6"]
@@ -20,7 +21,7 @@ def rel(a, b):
 
 
 def load_case(name):
-    z = np.load(os.path.join(GOLD, name + ".npz"))
+    z = load_npz(os.path.join(GOLD, name + ".npz"))
     cfg = {k[4:]: int(z[k]) for k in z.files if k.startswith("cfg:")}
     p = {k[3:]: z[k].astype(np.float64) for k in z.files if k.startswith("sd:")}
     return z, cfg, p

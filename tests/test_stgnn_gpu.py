@@ -12,6 +12,8 @@ from gnn_rul_benchmarking_amd.algorithms import get_algorithm_class
 from gnn_rul_benchmarking_amd.stgnn import STGNN_model
 from oracle import stgnn_oracle as O
 
+from golden_io import load_npz
+
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 CASES = sorted(p for p in glob.glob(os.path.join(GOLD, "stgnn_*.npz")) if "init" not in p and "curve" not in p and "trainer" not in p)
@@ -26,15 +28,17 @@ def model_from(z, cfg):
 
 @pytest.mark.parametrize("path", CASES, ids=[os.path.basename(p)[:-4] for p in CASES])
 def test_forward_and_gradients_match_the_reference(path):
-    z = np.load(path)
+    z = load_npz(path)
     cfg = {k[4:]: int(z[k]) for k in z.files if k.startswith("cfg:")}
     m = model_from(z, cfg)
-    x, y = torch.from_numpy(z["x"]).to(DEV), torch.from_numpy(z["y"]).to(DEV)
+    x, y = torch.tensor(z["x"], device=DEV), torch.from_numpy(z["y"]).to(DEV)
     m.train()
     pred = m(x, return_adjacency=True)
     adj = m.last_adjacency.reshape(-1, cfg["num_nodes"], cfg["num_nodes"]).cpu().numpy()
-    assert ((adj != 0) == (z["adj"] != 0)).all()                     # same top-k selection
-    assert np.allclose(adj, z["adj"], rtol=1e-4, atol=1e-7)
+    assert "adj" in z.files or "x_seed" in z.files                   # only a fixture whose input comes from a seed holds no taps
+    if "adj" in z.files:
+        assert ((adj != 0) == (z["adj"] != 0)).all()                 # same top-k selection
+        assert np.allclose(adj, z["adj"], rtol=1e-4, atol=1e-7)
     assert np.allclose(pred.detach().cpu().numpy(), z["pred"], rtol=1e-4, atol=1e-5)
     loss = torch.nn.functional.mse_loss(pred, y)
     loss.backward()

@@ -8,13 +8,14 @@ import numpy as np
 import pytest
 
 from oracle import stgnn_oracle as O
+from golden_io import load_npz
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 CASES = sorted(p for p in glob.glob(os.path.join(GOLD, "stgnn_*.npz")) if "init" not in p and "curve" not in p and "trainer" not in p)
 
 
 def load(path):
-    z = np.load(path)
+    z = load_npz(path)
     cfg = {k[4:]: int(z[k]) for k in z.files if k.startswith("cfg:")}
     p = {k[3:]: z[k].astype(np.float64) for k in z.files if k.startswith("sd:")}
     return z, cfg, p
@@ -26,10 +27,13 @@ def test_oracle_matches_reference_forward_and_gradients(path):
     x, y = z["x"].astype(np.float64), z["y"].astype(np.float64)
     loss, grads, out, c = O.forward_backward(x, y, p, cfg["num_patch"], cfg["patch_size"], cfg["top_k"])
     bs, N, H, L = x.shape[0], cfg["num_nodes"], cfg["hidden_dim"], cfg["num_patch"]
-    assert np.allclose(c["adj"], z["adj"], rtol=1e-4, atol=1e-7)
-    assert (c["adj"] != 0).sum(-1).max() <= cfg["top_k"] and ((c["adj"] != 0) == (z["adj"] != 0)).all()
-    assert np.allclose(c["cheb"], z["cheb"], rtol=1e-4, atol=1e-5)
-    assert np.allclose(c["hs"], z["gru_out"], rtol=1e-4, atol=1e-6)
+    assert (c["adj"] != 0).sum(-1).max() <= cfg["top_k"]
+    assert "adj" in z.files or "x_seed" in z.files          # only a fixture whose input comes from a seed (thousands of samples) holds no taps
+    if "adj" in z.files:
+        assert np.allclose(c["adj"], z["adj"], rtol=1e-4, atol=1e-7)
+        assert ((c["adj"] != 0) == (z["adj"] != 0)).all()
+        assert np.allclose(c["cheb"], z["cheb"], rtol=1e-4, atol=1e-5)
+        assert np.allclose(c["hs"], z["gru_out"], rtol=1e-4, atol=1e-6)
     assert np.allclose(out, z["pred"], rtol=1e-4, atol=1e-6)
     assert np.allclose(out, z["eval_pred"], rtol=1e-4, atol=1e-6)           # no dropout, no BatchNorm: eval == train
     assert abs(loss - float(z["loss"])) <= 1e-5 * abs(float(z["loss"]))

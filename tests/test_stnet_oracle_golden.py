@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from oracle import stnet_oracle as O
+from golden_io import load_npz
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 CASES = ["stnet_phm_c1like_6x128_bs5", "stnet_phm_c3like_7x32_bs4", "stnet_small_3x24_bs6"]
@@ -18,7 +19,7 @@ def rel(a, b):
 
 
 def load_case(name):
-    z = np.load(os.path.join(GOLD, name + ".npz"))
+    z = load_npz(os.path.join(GOLD, name + ".npz"))
     cfg = {k[4:]: (z[k].tolist() if z[k].ndim else int(z[k])) for k in z.files if k.startswith("cfg:")}
     p = {k[3:]: z[k].astype(np.float64) for k in z.files if k.startswith("sd:")}
     return z, cfg, p
