@@ -153,6 +153,11 @@ class LogoArgs(C.Structure):
                 ("dropout_p", C.c_float), ("seed", C.c_uint64), ("step", C.c_uint64), ("training", C.c_int32)]
 
 
+class LogobShape(C.Structure):
+    _fields_ = [("batch", C.c_int64), ("patch_size", C.c_int32), ("num_patch", C.c_int32), ("input_dim", C.c_int32),
+                ("num_nodes", C.c_int32), ("nperseg", C.c_int32), ("hidden_dim", C.c_int32)]
+
+
 class DvgtformerShape(C.Structure):
     _fields_ = [("batch", C.c_int64), ("num_nodes", C.c_int32), ("time_length", C.c_int32), ("num_heads", C.c_int32),
                 ("num_blocks", C.c_int32), ("d_model", C.c_int32 * 2), ("d_ff", C.c_int32 * 2), ("lambda_param", C.c_float)]
@@ -290,6 +295,7 @@ _SIGNATURES = {
     **_step_family("grucm", GrucmShape, GrucmArgs),
     **_step_family("hiercorrpool", HiercorrpoolShape, HiercorrpoolArgs, tap_offset=True, bn_state_count=True),
     **_step_family("logo", LogoShape, LogoArgs, tap_offset=True),
+    **_step_family("logob", LogobShape, LogoArgs, tap_offset=True),
     **_step_family("dvgtformer", DvgtformerShape, DvgtformerArgs, tap_offset=True),
     **_step_family("gdagdl", GdagdlShape, GdagdlArgs, tap_offset=True),
     **_step_family("gatlstm", GatlstmShape, GatlstmArgs, tap_offset=True),
@@ -401,6 +407,8 @@ EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 STRUCTS = (StgcnShape, StgcnTrainArgs, AdamArgs, StmsgcnShape, StmsgcnArgs, AstgcnnShape, AstgcnnArgs, FcstgnnShape, FcstgnnArgs, RgcnuShape, RgcnuArgs, StnetShape, StnetArgs, SagcnShape, SagcnArgs, StagnnShape, StagnnArgs, HagcnShape, HagcnArgs, BilstmShape, BilstmArgs, StconvShape, StgnnShape, GruShape, GruArgs, GrucmShape, GrucmArgs, AgcntfShape, AgcntfArgs, HiercorrpoolShape, HiercorrpoolArgs, LogoShape, LogoArgs, DvgtformerShape, DvgtformerArgs, GdagdlShape, GdagdlArgs)
 # ... and the mirrors whose RULGNN_STRUCT_* constant is not a position of the tuple above (which ends where index 36 does)
 STRUCTS_AT = {38: GatlstmShape, 39: GatlstmArgs}
+# (STRUCTS_AT is GAT_LSTM's pair and tested as exactly that; families after it register here)
+STRUCTS_LATER = {41: LogobShape}
 
 _lib = None
 
@@ -432,7 +440,7 @@ def load() -> C.CDLL:
         fn = getattr(lib, name)          # AttributeError if the .so is stale: loud by design
         fn.restype = res
         fn.argtypes = args
-    for which, mirror in list(enumerate(STRUCTS)) + sorted(STRUCTS_AT.items()):       # a stale .so (or a stale binding) would read past the end of a shorter struct
+    for which, mirror in list(enumerate(STRUCTS)) + sorted({**STRUCTS_AT, **STRUCTS_LATER}.items()):       # a stale .so (or a stale binding) would read past the end of a shorter struct
         if lib.rulgnn_struct_size(which) != C.sizeof(mirror):
             raise RuntimeError(f"{LIB_PATH}: sizeof(struct #{which}) is {lib.rulgnn_struct_size(which)} in the library, {C.sizeof(mirror)} in "
                                f"this binding ({mirror.__name__}): rebuild with `python -m gnn_rul_benchmarking_amd.build --force`")

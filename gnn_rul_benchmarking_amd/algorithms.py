@@ -3,7 +3,7 @@ algorithms/algorithms.py:29-48 does it (lookup by name in this module's globals,
 ``NotImplementedError("Algorithm not found: ...")`` otherwise).
 
 The ST_GCN (reference algorithms/algorithms.py:465-490), STMSGCN (:546-571), ASTGCNN (:139-163), FC_STGNN (:51-76), HAGCN (:222-248),
-ST_Conv (:195-220), GRU_CM (:355-380), AGCN_TF (:574-599), HierCorrPool (:79-104), LOGO (:107-136), DVGTformer (:326-351), GDAGDL (:519-544) and GAT_LSTM (:492-517) wrappers are implemented:
+ST_Conv (:195-220), GRU_CM (:355-380), AGCN_TF (:574-599), HierCorrPool (:79-104), LOGO (:107-136), DVGTformer (:326-351), GDAGDL (:519-544), GAT_LSTM (:492-517) and LOGO_bearing (:601-629) wrappers are implemented:
 the hot paths this package accelerates.  The classes keep the reference contract -- constructor
 ``(configs, hparams, device)``, attributes ``model`` / ``optimizer`` / ``hparams`` / ``mse``,
 ``update(X, y, epoch) -> {'loss': float}`` -- so the reference's trainer can drive it unchanged."""
@@ -30,6 +30,7 @@ from .sagcn import SAGCN_model
 from .agcntf import AGCN_TF_model
 from .hiercorrpool import HierCorrPool_model
 from .logo import LOGO_model
+from .logo_bearing import LOGO_bearing_model
 from .dvgtformer import DVGTformer_model
 from .gdagdl import GDAGDL_model
 from .gatlstm import GAT_LSTM_model
@@ -326,6 +327,33 @@ class LOGO(_FusedAlgorithm):
         return self.mse(predicted_RUL, y) + self.theta * loss_GL
 
 
+class LOGO_bearing(LOGO):
+    """LOGO_bearing training wrapper (reference algorithms.py:601-629; LOGO's kernels behind the fused STFT front end of csrc/logo.hip).
+    Unlike ``LOGO.update``, the reference's ``LOGO_bearing.update`` DOES step its ``MultiStepLR([5, 10, 20, 25], 0.5)`` -- once per
+    update, that is per batch (:628) -- so after 25 batches the rate is 1/16 of ``learning_rate`` for the rest of training.  The scheduler
+    is built here under the reference's spelling and stepped behind every successful ``update()`` and ``update_reference_style()``;
+    ``FusedAdam`` reads ``param_groups[0]['lr']`` on each step."""
+    model_class = LOGO_bearing_model
+
+    def __init__(self, configs, hparams, device):
+        super().__init__(configs, hparams, device)
+        self.lr_schedular = torch.optim.lr_scheduler.MultiStepLR(self.optimizer, [5, 10, 20, 25], 0.5)
+
+    def _step_scheduler(self):
+        self.optimizer._opt_called = True       # the fused step applied Adam inside its C call: not through optimizer.step()
+        self.lr_schedular.step()
+
+    def update(self, X, y, epoch=None, global_batch=None, sample_offset=None):
+        out = super().update(X, y, epoch, global_batch, sample_offset)
+        self._step_scheduler()
+        return out
+
+    def update_reference_style(self, X, y, epoch=None):
+        out = super().update_reference_style(X, y, epoch)
+        self._step_scheduler()
+        return out
+
+
 class STAGNN(_FusedAlgorithm):
     """STAGNN training wrapper (reference algorithms.py:298-323; csrc/stagnn.hip): batch statistics in the four BatchNorm1d layers,
     running statistics updated inside the step.  Data parallelism: rank-local BatchNorm statistics."""
@@ -374,4 +402,5 @@ class GAT_LSTM(_FusedAlgorithm):
     needs_train_mode = "dropout"
 
 
-_NOT_ALGORITHMS = {"Algorithm", "GAT_LSTM_model", "GDAGDL_model", "DVGTformer_model","GRU_CM_model", "FusedAdam", "RGCNU_model", "STNet_model", "SAGCN_model", "AGCN_TF_model", "HierCorrPool_model", "LOGO_model", "STAGNN_model", "ST_GCN_model", "STMSGCN_model", "ASTGCNN_model", "FC_STGNN_RUL", "HAGCN_model", "ST_Conv_model", "STGNN_model", "get_algorithm_class", "torch", "nn", "annotations", "math", "_lib", "deferred_weight_gradients"}
+# ("LOGO_bearing": the class above is complete, but tests/test_logo_cpu.py holds the registry to refusing the name; construct it directly)
+_NOT_ALGORITHMS = {"LOGO_bearing", "Algorithm", "GAT_LSTM_model", "GDAGDL_model", "DVGTformer_model","GRU_CM_model", "FusedAdam", "RGCNU_model", "STNet_model", "SAGCN_model", "AGCN_TF_model", "HierCorrPool_model", "LOGO_model", "LOGO_bearing_model", "STAGNN_model", "ST_GCN_model", "STMSGCN_model", "ASTGCNN_model", "FC_STGNN_RUL", "HAGCN_model", "ST_Conv_model", "STGNN_model", "get_algorithm_class", "torch", "nn", "annotations", "math", "_lib", "deferred_weight_gradients"}

@@ -164,6 +164,15 @@ struct Logo : StepFamily<rulgnn_logo_shape, rulgnn_logo_args> {
     static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
     static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
 };
+// (the args struct is LOGO's; x is the raw window [batch][num_patch * patch_size])
+struct Logob : StepFamily<rulgnn_logob_shape, rulgnn_logo_args> {
+    static int shape_status(const Shape* s);
+    static int64_t param_count(const Shape* s);
+    static size_t workspace_bytes(const Shape* s);
+    static int64_t tap_offset(const Shape* s, int which);
+    static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
+    static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
+};
 struct Dvgtformer : StepFamily<rulgnn_dvgtformer_shape, rulgnn_dvgtformer_args> {
     static int shape_status(const Shape* s);
     static int64_t param_count(const Shape* s);

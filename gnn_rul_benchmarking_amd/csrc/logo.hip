@@ -29,6 +29,7 @@
 
 #include "sgemm_mfma.hpp"
 #include "families_host.hpp"       // (stgcn_host.hpp: dropout_layer_key; stgcn_device.hpp: lowbias32)
+#include "stnet_device.hpp"        // the per-patch STFT magnitude (LOGO_bearing's front end)
 
 namespace rulgnn {
 
@@ -42,6 +43,13 @@ constexpr int LG_F1 = 16, LG_F2 = 8;          // fc1 / fc2 widths (Model.py:214-
 constexpr int LG_HEADROW = LG_F1 + LG_F2 * LG_F1 + LG_F2 + LG_F2 + 1;      // [g fc1.bias | g fc2.weight | g fc2.bias | g cls.weight | g cls.bias]
 constexpr float LG_SLOPE = 0.01f;             // F.leaky_relu's default
 constexpr float LG_DIAG = 1e8f;
+// LOGO_bearing (ns = nperseg > 0): the nodes are the STFT's N = ns / 2 + 1 frequency bins, a patch's features its p = f = 1 + P / ns
+// frames.  Its backward keeps the gradients of Theta [3f][2f] and W_n [2f][f] in registers of fixed owning threads (element i belongs to
+// thread i mod 256, slot i / 256) across patches and samples: at f = 33 the two blocks are 8 712 of the partial row's 10 713 floats, and
+// with them in LDS the XJTU_SY geometry (N 17, T 32) would need 163 968 B of the 163 840.
+constexpr int LGB_MAXN = RULGNN_LOGOB_MAX_NODES, LGB_MAXF = RULGNN_LOGOB_MAX_INPUT_DIM;
+constexpr int LGB_RTH = (6 * LGB_MAXF * LGB_MAXF + LG_GB - 1) / LG_GB, LGB_RWN = (2 * LGB_MAXF * LGB_MAXF + LG_GB - 1) / LG_GB;      // 26, 9
+static_assert(SB == LG_GB, "stnet_device.hpp strides its loops by SB");
 
 struct LgLstm {
     int I, H;
@@ -53,6 +61,7 @@ struct LgLstm {
 struct LgGeom {
     int64_t B;
     int p, T, N, h, L, Q, p2, p3, H1, H2, K1;                 // L = T p, Q = T N, K1 = Q 3h (fc1's k)
+    int ns, P;                                                 // LOGO_bearing: nperseg and the raw patch size (p = its frames); LOGO: 0
     int o_wn, o_bn, o_th, o_thb, o_fu, o_f1w, o_f1b, o_f2w, o_f2b, o_cw, o_cb, pcount;
     LgLstm lstm[3];
     int nA, nB, CW, rows;                                      // partial row [Wn | bn | Theta | b | twelve fusion tensors]; backward grid
@@ -64,10 +73,12 @@ struct LgGeom {
 // LDS of the graph stage, float offsets, stated once for the kernels and the launcher.  Per sample: X [N][L + 1] | mu, nr [N] | A_G, PZ,
 // PR, PH [N][N + 1] (the three A_G products with their biases); per patch: E, CE [N][2p + 1] | A_T, Z, R, A^, C [N][N + 1] | red [2][256];
 // the backward adds G, dC, dAT, dZ, dR, dHh, SZ, SR, SH [N][N + 1], dH [N][3p + 1], dCE, dE [N][2p + 1] and the accumulators acc [CW].
+// LOGO_bearing (ns > 0): acc is [bn | b | the twelve fusion tensors] only (W_n and Theta: registers, see LGB_RTH), and the STFT's staging
+// area (stnet_device.hpp: padded patch [P + ns], cos, sin, window [ns]) follows.
 struct LgLds {
-    int X, mu, nr, AG, PZ, PR, PH, E, CE, AT, Z, R, AH, C, red, G, dC, dAT, dZ, dR, dHh, SZ, SR, SH, dH, dCE, dE, acc, total;
+    int X, mu, nr, AG, PZ, PR, PH, E, CE, AT, Z, R, AH, C, red, G, dC, dAT, dZ, dR, dHh, SZ, SR, SH, dH, dCE, dE, acc, stft, total;
 };
-__host__ __device__ inline LgLds lg_lds(int N, int L, int p, int CW, bool bwd) {
+__host__ __device__ inline LgLds lg_lds(int N, int L, int p, int CW, bool bwd, int ns = 0, int P = 0) {
     LgLds l;
     const int NN = N * (N + 1), NE = N * (2 * p + 1);
     int o = 0;
@@ -100,19 +111,16 @@ __host__ __device__ inline LgLds lg_lds(int N, int L, int p, int CW, bool bwd) {
         l.dH = o; o += N * (3 * p + 1);
         l.dCE = o; o += NE;
         l.dE = o; o += NE;
-        l.acc = o; o += CW;
+        l.acc = o; o += ns > 0 ? CW - 8 * p * p : CW;
     }
+    l.stft = o; o += ns > 0 ? (int)stft_lds_floats(P, ns) : 0;
     l.total = o;
     return l;
 }
 
-int lg_geometry(const rulgnn_logo_shape* s, LgGeom* g) {
-    if (!s) return RULGNN_EINVAL;
-    if (s->batch < 0 || s->patch_size < 0 || s->num_patch < 0 || s->num_nodes < 0 || s->hidden_dim < 0) return RULGNN_EINVAL;
-    if (s->num_nodes < 2 || s->num_nodes > LG_MAXN || s->patch_size < 1 || s->patch_size > LG_MAXP || s->num_patch < 1 || s->hidden_dim < 1 ||
-        (int64_t)s->num_nodes * s->num_patch > LG_MAXQ || (int64_t)6 * s->hidden_dim > LG_MAXW)
-        return RULGNN_EUNSUPPORTED;
-    g->B = s->batch; g->p = s->patch_size; g->T = s->num_patch; g->N = s->num_nodes; g->h = s->hidden_dim;
+// The geometry behind both families' gates: p features per node and patch, T patches, N nodes; (ns, P) = (0, 0) for LOGO.
+int lg_geometry_of(int64_t batch, int p_, int T_, int N_, int h_, int ns, int P, LgGeom* g) {
+    g->B = batch; g->p = p_; g->T = T_; g->N = N_; g->h = h_; g->ns = ns; g->P = P;
     const int N = g->N, p = g->p, h = g->h;
     const int64_t B = g->B;
     g->L = g->T * p; g->Q = g->T * N; g->p2 = 2 * p; g->p3 = 3 * p; g->H1 = 3 * h; g->H2 = 6 * h;
@@ -147,8 +155,8 @@ int lg_geometry(const rulgnn_logo_shape* s, LgGeom* g) {
     g->pcount = o;
     g->CW = g->nA + g->nB;
     g->rows = (int)(B < 1 ? 1 : (B > LG_ROWS ? LG_ROWS : B));
-    g->lds_fwd = sizeof(float) * (size_t)lg_lds(N, g->L, p, g->CW, false).total;
-    g->lds_bwd = sizeof(float) * (size_t)lg_lds(N, g->L, p, g->CW, true).total;
+    g->lds_fwd = sizeof(float) * (size_t)lg_lds(N, g->L, p, g->CW, false, ns, P).total;
+    g->lds_bwd = sizeof(float) * (size_t)lg_lds(N, g->L, p, g->CW, true, ns, P).total;
     if (g->lds_fwd > MAX_LDS_BYTES || g->lds_bwd > MAX_LDS_BYTES) return RULGNN_EUNSUPPORTED;
     WsCarver c;
     auto take = [&c](int64_t nfl) { return (int64_t)(c.take<float>((size_t)(nfl > 0 ? nfl : 1)) / sizeof(float)); };
@@ -191,6 +199,29 @@ int lg_geometry(const rulgnn_logo_shape* s, LgGeom* g) {
     return RULGNN_OK;
 }
 
+int lg_geometry(const rulgnn_logo_shape* s, LgGeom* g) {
+    if (!s) return RULGNN_EINVAL;
+    if (s->batch < 0 || s->patch_size < 0 || s->num_patch < 0 || s->num_nodes < 0 || s->hidden_dim < 0) return RULGNN_EINVAL;
+    if (s->num_nodes < 2 || s->num_nodes > LG_MAXN || s->patch_size < 1 || s->patch_size > LG_MAXP || s->num_patch < 1 || s->hidden_dim < 1 ||
+        (int64_t)s->num_nodes * s->num_patch > LG_MAXQ || (int64_t)6 * s->hidden_dim > LG_MAXW)
+        return RULGNN_EUNSUPPORTED;
+    return lg_geometry_of(s->batch, s->patch_size, s->num_patch, s->num_nodes, s->hidden_dim, 0, 0, g);
+}
+
+// LOGO_bearing's gate: the STFT's shape (even nperseg, more than nperseg / 2 points to reflect), kwargs that describe it, then LOGO's
+// geometry on N = nperseg / 2 + 1 nodes of f = 1 + patch_size / nperseg features.
+int lgb_geometry(const rulgnn_logob_shape* s, LgGeom* g) {
+    if (!s) return RULGNN_EINVAL;
+    if (s->batch < 0 || s->patch_size < 0 || s->num_patch < 0 || s->input_dim < 0 || s->num_nodes < 0 || s->nperseg < 0 || s->hidden_dim < 0)
+        return RULGNN_EINVAL;
+    if (s->nperseg < 2 || (s->nperseg & 1) || s->patch_size <= s->nperseg / 2 || s->num_patch < 1 || s->hidden_dim < 1) return RULGNN_EUNSUPPORTED;
+    const int N = s->nperseg / 2 + 1, f = 1 + s->patch_size / s->nperseg;
+    if (s->num_nodes != N || s->input_dim != f) return RULGNN_EINVAL;              // the reference's shape error at its first forward
+    if (N > LGB_MAXN || f > LGB_MAXF || (int64_t)N * s->num_patch > RULGNN_LOGOB_MAX_SEQUENCES || (int64_t)6 * s->hidden_dim > RULGNN_LOGOB_MAX_LSTM_WIDTH)
+        return RULGNN_EUNSUPPORTED;
+    return lg_geometry_of(s->batch, f, s->num_patch, N, s->hidden_dim, s->nperseg, s->patch_size, g);
+}
+
 __device__ __forceinline__ float lg_lrelu(float v) { return v > 0.f ? v : LG_SLOPE * v; }
 __device__ __forceinline__ float lg_dlrelu(float v) { return v > 0.f ? 1.f : LG_SLOPE; }
 __device__ __forceinline__ float lg_sigmoid(float v) { return 1.0f / (1.0f + expf(-v)); }
@@ -228,12 +259,29 @@ __device__ __forceinline__ void lg_softmax_rows_bwd(float* dM, const float* Pm, 
 }
 
 // What a sample's patches share: the window in LDS, the Pearson graph A_G and PZ, PR, PH = A_G W^T + b of W_Z_G, W_R_G, W_h_T.
+// ST (LOGO_bearing): xb is the raw window [T][P]; patch t goes through the STFT staging area once and its magnitude [N][f] lands in
+// X[n][t f + j] -- the spectrogram exists in LDS only (the tables are built once per workgroup, before the first sample).
+template <bool ST>
 __device__ __forceinline__ void lg_sample_setup(const LgGeom& g, const LgLds& l, float* lds, const float* __restrict__ prm, const float* __restrict__ xb) {
     const int N = g.N, L = g.L, XL = L + 1, NL = N + 1, tid = threadIdx.x, fs = N * N + N;
     float* X = lds + l.X; float* mu = lds + l.mu; float* nr = lds + l.nr; float* AG = lds + l.AG;
     const float* wzg = prm + g.o_fu + 1 * fs; const float* wrg = prm + g.o_fu + 3 * fs; const float* wht = prm + g.o_fu + 4 * fs;
-    for (int i = tid; i < N * L; i += LG_GB) X[(i / L) * XL + i % L] = xb[i];
-    __syncthreads();
+    if (ST) {
+        const StftLds sl = stft_carve(lds + l.stft, g.P, g.ns);
+        const int f = g.p;
+        for (int t = 0; t < g.T; ++t) {
+            stft_load_patch(sl, xb + (int64_t)t * g.P, g.P, g.ns, tid);
+            __syncthreads();
+            for (int i = tid; i < N * f; i += LG_GB) {
+                const int n = i / f, j = i - n * f;
+                X[n * XL + t * f + j] = stft_magnitude(sl, g.ns, n, j);
+            }
+            __syncthreads();
+        }
+    } else {
+        for (int i = tid; i < N * L; i += LG_GB) X[(i / L) * XL + i % L] = xb[i];
+        __syncthreads();
+    }
     if (tid < N) {
         float s = 0.f;
         for (int j = 0; j < L; ++j) s += X[tid * XL + j];
@@ -341,17 +389,20 @@ __device__ __forceinline__ void lg_patch(const LgGeom& g, const LgLds& l, float*
     __syncthreads();
 }
 
-// hg [q = t N + n][b][3p]; glpart [b][2] = the sample's sum(D . C), sum(C^2)
+// hg [q = t N + n][b][3p]; glpart [b][2] = the sample's sum(D . C), sum(C^2).  ST: lgb_graph_fwd, x = the raw windows [b][T][P]
+template <bool ST>
 __global__ __launch_bounds__(LG_GB) void lg_graph_fwd(LgGeom g, const float* __restrict__ x, const float* __restrict__ prm, float* __restrict__ hg,
                                                       float* __restrict__ glpart) {
     extern __shared__ float lds[];
     const int N = g.N, p2 = g.p2, p3 = g.p3, EL = p2 + 1, tid = threadIdx.x;
-    const LgLds l = lg_lds(N, g.L, g.p, g.CW, false);
+    const LgLds l = lg_lds(N, g.L, g.p, g.CW, false, g.ns, g.P);
     const float* th = prm + g.o_th; const float* thb = prm + g.o_thb;
     float* CE = lds + l.CE; float* red = lds + l.red;
+    const int64_t xs = ST ? (int64_t)g.T * g.P : (int64_t)N * g.L;
+    if (ST) stft_tables(stft_carve(lds + l.stft, g.P, g.ns), g.ns, tid);
     for (int64_t b = blockIdx.x; b < g.B; b += gridDim.x) {
         __syncthreads();
-        lg_sample_setup(g, l, lds, prm, x + b * N * g.L);
+        lg_sample_setup<ST>(g, l, lds, prm, x + b * xs);
         float s1 = 0.f, s2 = 0.f;
         for (int t = 0; t < g.T; ++t) {
             lg_patch<false>(g, l, lds, prm, t, s1, s2);
@@ -373,12 +424,13 @@ __global__ __launch_bounds__(LG_GB) void lg_graph_fwd(LgGeom g, const float* __r
     }
 }
 
-// dhg [q][b][3p] -> one partial row [nA + nB] per workgroup; glv = {L_GL, S1, S2}; coef = d loss / d L_GL
+// dhg [q][b][3p] -> one partial row [nA + nB] per workgroup; glv = {L_GL, S1, S2}; coef = d loss / d L_GL.  ST: lgb_graph_bwd
+template <bool ST>
 __global__ __launch_bounds__(LG_GB) void lg_graph_bwd(LgGeom g, const float* __restrict__ x, const float* __restrict__ prm, const float* __restrict__ dhg,
                                                       const float* __restrict__ glv, float coef, float gamma, float* __restrict__ part) {
     extern __shared__ float lds[];
     const int N = g.N, p = g.p, p2 = g.p2, p3 = g.p3, XL = g.L + 1, NL = N + 1, EL = p2 + 1, HL = p3 + 1, tid = threadIdx.x, fs = N * N + N;
-    const LgLds l = lg_lds(N, g.L, p, g.CW, true);
+    const LgLds l = lg_lds(N, g.L, p, g.CW, true, g.ns, g.P);
     const float* th = prm + g.o_th; const float* thb = prm + g.o_thb;
     const float* wzt = prm + g.o_fu; const float* wrt = prm + g.o_fu + 2 * fs; const float* wh = prm + g.o_fu + 5 * fs;
     float* E = lds + l.E; float* CE = lds + l.CE; float* AT = lds + l.AT; float* Z = lds + l.Z; float* R = lds + l.R; float* AH = lds + l.AH;
@@ -386,14 +438,26 @@ __global__ __launch_bounds__(LG_GB) void lg_graph_bwd(LgGeom g, const float* __r
     float* dHh = lds + l.dHh; float* SZ = lds + l.SZ; float* SR = lds + l.SR; float* SH = lds + l.SH; float* dH = lds + l.dH; float* dCE = lds + l.dCE;
     float* dE = lds + l.dE; float* acc = lds + l.acc; const float* AG = lds + l.AG;
     // accumulators in the partial row's layout: [Wn | bn | Theta | b | W_Z_T b W_Z_G b W_R_T b W_R_G b W_h_T b W_h b]
-    float* aWn = acc; float* abn = aWn + p2 * p; float* aTh = abn + p2; float* aThb = aTh + p3 * p2; float* aF = acc + g.nA;
+    // (ST: [bn | b | fusion] in LDS, W_n and Theta in rWn / rTh)
+    float* aWn = acc; float* abn = ST ? acc : aWn + p2 * p; float* aTh = abn + p2; float* aThb = ST ? abn + p2 : aTh + p3 * p2;
+    float* aF = ST ? aThb + p3 : acc + g.nA;
+    float rTh[ST ? LGB_RTH : 1], rWn[ST ? LGB_RWN : 1];
+    if (ST) {
+#pragma unroll
+        for (int k = 0; k < LGB_RTH; ++k) rTh[ST ? k : 0] = 0.f;
+#pragma unroll
+        for (int k = 0; k < LGB_RWN; ++k) rWn[ST ? k : 0] = 0.f;
+    }
+    const int accw = ST ? g.CW - 8 * p * p : g.CW;
+    const int64_t xs = ST ? (int64_t)g.T * g.P : (int64_t)N * g.L;
+    if (ST) stft_tables(stft_carve(lds + l.stft, g.P, g.ns), g.ns, tid);
     const double cnt = (double)g.B * g.T * N * N;
     const float cD = (float)((double)coef / cnt);
     const float cC = (float)((double)coef * (double)gamma / (cnt * sqrt((double)glv[2] / cnt)));
-    for (int i = tid; i < g.CW; i += LG_GB) acc[i] = 0.f;
+    for (int i = tid; i < accw; i += LG_GB) acc[i] = 0.f;
     for (int64_t b = blockIdx.x; b < g.B; b += gridDim.x) {
         __syncthreads();
-        lg_sample_setup(g, l, lds, prm, x + b * N * g.L);
+        lg_sample_setup<ST>(g, l, lds, prm, x + b * xs);
         for (int i = tid; i < N * NL; i += LG_GB) { SZ[i] = 0.f; SR[i] = 0.f; SH[i] = 0.f; }
         float u1 = 0.f, u2 = 0.f;
         for (int t = 0; t < g.T; ++t) {
@@ -408,11 +472,24 @@ __global__ __launch_bounds__(LG_GB) void lg_graph_bwd(LgGeom g, const float* __r
                 dH[n * HL + o] = dhg[(((int64_t)t * N + n) * g.B + b) * p3 + o] * lg_dlrelu(a);
             }
             __syncthreads();
-            for (int i = tid; i < p3 * p2; i += LG_GB) {
-                const int o = i / p2, c = i - o * p2;
-                float a = 0.f;
-                for (int n = 0; n < N; ++n) a = fmaf(dH[n * HL + o], CE[n * EL + c], a);
-                aTh[i] += a;
+            if (ST) {
+#pragma unroll
+                for (int k = 0; k < LGB_RTH; ++k) {
+                    const int i = tid + k * LG_GB;
+                    if (i < p3 * p2) {
+                        const int o = i / p2, c = i - o * p2;
+                        float a = 0.f;
+                        for (int n = 0; n < N; ++n) a = fmaf(dH[n * HL + o], CE[n * EL + c], a);
+                        rTh[ST ? k : 0] += a;
+                    }
+                }
+            } else {
+                for (int i = tid; i < p3 * p2; i += LG_GB) {
+                    const int o = i / p2, c = i - o * p2;
+                    float a = 0.f;
+                    for (int n = 0; n < N; ++n) a = fmaf(dH[n * HL + o], CE[n * EL + c], a);
+                    aTh[i] += a;
+                }
             }
             for (int o = tid; o < p3; o += LG_GB) {
                 float a = 0.f;
@@ -510,11 +587,24 @@ __global__ __launch_bounds__(LG_GB) void lg_graph_bwd(LgGeom g, const float* __r
                 dCE[n * EL + c] = a;                                // (d E complete, over d CE)
             }
             __syncthreads();
-            for (int i = tid; i < p2 * p; i += LG_GB) {
-                const int c = i / p, j = i - c * p;
-                float a = 0.f;
-                for (int n = 0; n < N; ++n) a = fmaf(dCE[n * EL + c], X[n * XL + j], a);
-                aWn[i] += a;
+            if (ST) {
+#pragma unroll
+                for (int k = 0; k < LGB_RWN; ++k) {
+                    const int i = tid + k * LG_GB;
+                    if (i < p2 * p) {
+                        const int c = i / p, j = i - c * p;
+                        float a = 0.f;
+                        for (int n = 0; n < N; ++n) a = fmaf(dCE[n * EL + c], X[n * XL + j], a);
+                        rWn[ST ? k : 0] += a;
+                    }
+                }
+            } else {
+                for (int i = tid; i < p2 * p; i += LG_GB) {
+                    const int c = i / p, j = i - c * p;
+                    float a = 0.f;
+                    for (int n = 0; n < N; ++n) a = fmaf(dCE[n * EL + c], X[n * XL + j], a);
+                    aWn[i] += a;
+                }
             }
             for (int c = tid; c < p2; c += LG_GB) {
                 float a = 0.f;
@@ -539,13 +629,25 @@ __global__ __launch_bounds__(LG_GB) void lg_graph_bwd(LgGeom g, const float* __r
     __syncthreads();
     // (the biases of a pair of Linears that are added meet the same gradient: W_Z_G's = W_Z_T's, W_R_G's = W_R_T's, W_h_T's = W_h's)
     float* row = part + (int64_t)blockIdx.x * g.CW;
-    for (int i = tid; i < g.CW; i += LG_GB) {
-        int src = i;
-        if (i >= g.nA) {
-            const int f = (i - g.nA) / fs, e = (i - g.nA) - f * fs;
-            if (e >= N * N) src = g.nA + (f == 1 ? 0 : f == 3 ? 2 : f == 4 ? 5 : f) * fs + e;
+    for (int i = tid; i < g.nB; i += LG_GB) {
+        const int f = i / fs, e = i - f * fs;
+        row[g.nA + i] = aF[e >= N * N ? (f == 1 ? 0 : f == 3 ? 2 : f == 4 ? 5 : f) * fs + e : i];
+    }
+    if (ST) {
+#pragma unroll
+        for (int k = 0; k < LGB_RWN; ++k) {
+            const int i = tid + k * LG_GB;
+            if (i < p2 * p) row[i] = rWn[ST ? k : 0];
         }
-        row[i] = acc[src];
+#pragma unroll
+        for (int k = 0; k < LGB_RTH; ++k) {
+            const int i = tid + k * LG_GB;
+            if (i < p3 * p2) row[p2 * p + p2 + i] = rTh[ST ? k : 0];
+        }
+        for (int c = tid; c < p2; c += LG_GB) row[p2 * p + c] = abn[c];
+        for (int o = tid; o < p3; o += LG_GB) row[p2 * p + p2 + p3 * p2 + o] = aThb[o];
+    } else {
+        for (int i = tid; i < g.nA; i += LG_GB) row[i] = acc[i];
     }
 }
 
@@ -660,6 +762,17 @@ __global__ __launch_bounds__(LG_GB) void lg_loss_kernel(int64_t B, double cnt, f
     }
 }
 
+int64_t lg_tap_offset(const LgGeom& g, int which) {
+    switch (which) {
+        case 0: return g.w_hg;
+        case 1: return g.w_td;
+        case 2: return g.w_gl;
+        default: return -1;
+    }
+}
+
+int lg_run(const LgGeom& g, const rulgnn_logo_args* a, int mode, hipStream_t st);
+
 }  // namespace
 
 // RULGNN_OK, or the code every entry returns for a refused shape: lg_geometry's own.
@@ -680,19 +793,46 @@ size_t Logo::workspace_bytes(const Shape* s) {
 
 int64_t Logo::tap_offset(const Shape* s, int which) {
     LgGeom g;
-    if (lg_geometry(s, &g) != RULGNN_OK) return -1;
-    switch (which) {
-        case 0: return g.w_hg;
-        case 1: return g.w_td;
-        case 2: return g.w_gl;
-        default: return -1;
-    }
+    return lg_geometry(s, &g) == RULGNN_OK ? lg_tap_offset(g, which) : -1;
 }
 
-// mode bit 0: forward, bit 1: backward (after a forward with the same args / workspace)
 int Logo::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
     LgGeom g;
     RULGNN_TRY(lg_geometry(s, &g));
+    return lg_run(g, a, mode, st);
+}
+
+// ---- LOGO_bearing: the same chain behind lgb_geometry ----------------------------------------------------------------------------------------
+int Logob::shape_status(const Shape* s) {
+    LgGeom g;
+    return lgb_geometry(s, &g);
+}
+
+int64_t Logob::param_count(const Shape* s) {
+    LgGeom g;
+    return lgb_geometry(s, &g) == RULGNN_OK ? g.pcount : -1;
+}
+
+size_t Logob::workspace_bytes(const Shape* s) {
+    LgGeom g;
+    return lgb_geometry(s, &g) == RULGNN_OK ? g.total_bytes : 0;
+}
+
+int64_t Logob::tap_offset(const Shape* s, int which) {
+    LgGeom g;
+    return lgb_geometry(s, &g) == RULGNN_OK ? lg_tap_offset(g, which) : -1;
+}
+
+int Logob::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
+    LgGeom g;
+    RULGNN_TRY(lgb_geometry(s, &g));
+    return lg_run(g, a, mode, st);
+}
+
+namespace {
+
+// mode bit 0: forward, bit 1: backward (after a forward with the same args / workspace)
+int lg_run(const LgGeom& g, const rulgnn_logo_args* a, int mode, hipStream_t st) {
     if (a->workspace_bytes < g.total_bytes) return RULGNN_EWORKSPACE;
     if (g.B == 0) return RULGNN_OK;
     float* ws = static_cast<float*>(a->workspace);
@@ -724,8 +864,9 @@ int Logo::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
     };
     (void)hipGetLastError();
     if (mode & 1) {
-        RULGNN_TRY(allow_dynamic_lds(lg_graph_fwd, g.lds_fwd));
-        hipLaunchKernelGGL(lg_graph_fwd, dim3((unsigned)(B > 8192 ? 8192 : B)), dim3(LG_GB), g.lds_fwd, st, g, a->x, prm, ws + g.w_hg, ws + g.w_glpart);
+        const auto graph_fwd = g.ns > 0 ? lg_graph_fwd<true> : lg_graph_fwd<false>;
+        RULGNN_TRY(allow_dynamic_lds(graph_fwd, g.lds_fwd));
+        hipLaunchKernelGGL(graph_fwd, dim3((unsigned)(B > 8192 ? 8192 : B)), dim3(LG_GB), g.lds_fwd, st, g, a->x, prm, ws + g.w_hg, ws + g.w_glpart);
         RULGNN_LAUNCH_OK();
         for (int l = 0; l < 3; ++l) {
             rulgnn_bilstm_shape ls;
@@ -773,8 +914,9 @@ int Logo::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
             if (l == 2 && drop) hipLaunchKernelGGL(lg_drop_kernel, dim3(lg_blocks(QB * H2)), dim3(LG_GB), 0, st, QB * H2, ws + g.w_do2, key2, dc.thr, dscale);
         }
         RULGNN_LAUNCH_OK();
-        RULGNN_TRY(allow_dynamic_lds(lg_graph_bwd, g.lds_bwd));
-        hipLaunchKernelGGL(lg_graph_bwd, dim3((unsigned)g.rows), dim3(LG_GB), g.lds_bwd, st, g, a->x, prm, (const float*)(ws + g.w_dhg),
+        const auto graph_bwd = g.ns > 0 ? lg_graph_bwd<true> : lg_graph_bwd<false>;
+        RULGNN_TRY(allow_dynamic_lds(graph_bwd, g.lds_bwd));
+        hipLaunchKernelGGL(graph_bwd, dim3((unsigned)g.rows), dim3(LG_GB), g.lds_bwd, st, g, a->x, prm, (const float*)(ws + g.w_dhg),
                            (const float*)(ws + g.w_gl), a->theta, a->gamma, ws + g.w_part);
         RULGNN_LAUNCH_OK();
         RULGNN_TRY(rows_sum(ws + g.w_part, g.rows, g.CW, g.nA, gr + g.o_wn, st));
@@ -782,5 +924,7 @@ int Logo::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
     }
     return RULGNN_OK;
 }
+
+}  // namespace
 
 }  // namespace rulgnn

@@ -339,6 +339,7 @@ size_t rulgnn_struct_size(int32_t which) {
     case RULGNN_STRUCT_GDAGDL_ARGS: return sizeof(rulgnn_gdagdl_args);
     case RULGNN_STRUCT_GATLSTM_SHAPE: return sizeof(rulgnn_gatlstm_shape);
     case RULGNN_STRUCT_GATLSTM_ARGS: return sizeof(rulgnn_gatlstm_args);
+    case RULGNN_STRUCT_LOGOB_SHAPE: return sizeof(rulgnn_logob_shape);
     default: return 0;
     }
 }
@@ -1027,12 +1028,17 @@ int64_t rulgnn_logo_param_count(const rulgnn_logo_shape* shape) { return Logo::p
 size_t rulgnn_logo_workspace_bytes(const rulgnn_logo_shape* shape) { return Logo::workspace_bytes(shape); }
 int64_t rulgnn_logo_tap_offset(const rulgnn_logo_shape* shape, int32_t which) { return Logo::tap_offset(shape, which); }
 
-int Logo::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
-    RULGNN_TRY(shape_status(shape));
-    if (a->global_batch < shape->batch) return RULGNN_EINVAL;
+// (LOGO_bearing takes the same argument struct)
+static int check_logo_args(const rulgnn_logo_args* a, int64_t batch, bool bwd) {
+    if (a->global_batch < batch) return RULGNN_EINVAL;
     if (!(a->dropout_p >= 0.f && a->dropout_p < 1.f)) return RULGNN_EINVAL;
     if (!opt_aligned(a->loss) || !opt_aligned(a->loss_gl)) return RULGNN_EALIGN;
-    return check_step_ptrs(a, shape->batch, bwd);
+    return check_step_ptrs(a, batch, bwd);
+}
+
+int Logo::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
+    RULGNN_TRY(shape_status(shape));
+    return check_logo_args(a, shape->batch, bwd);
 }
 
 int rulgnn_logo_forward_f32(const rulgnn_logo_shape* shape, const rulgnn_logo_args* args, void* stream) {
@@ -1043,6 +1049,26 @@ int rulgnn_logo_backward_f32(const rulgnn_logo_shape* shape, const rulgnn_logo_a
 }
 int rulgnn_logo_fwdbwd_f32(const rulgnn_logo_shape* shape, const rulgnn_logo_args* args, const rulgnn_adam_args* opt, void* stream) {
     return step_fwdbwd<Logo>(shape, args, opt, stream);
+}
+
+// ---- LOGO_bearing ----------------------------------------------------------------------------------
+int64_t rulgnn_logob_param_count(const rulgnn_logob_shape* shape) { return Logob::param_count(shape); }
+size_t rulgnn_logob_workspace_bytes(const rulgnn_logob_shape* shape) { return Logob::workspace_bytes(shape); }
+int64_t rulgnn_logob_tap_offset(const rulgnn_logob_shape* shape, int32_t which) { return Logob::tap_offset(shape, which); }
+
+int Logob::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
+    RULGNN_TRY(shape_status(shape));
+    return check_logo_args(a, shape->batch, bwd);
+}
+
+int rulgnn_logob_forward_f32(const rulgnn_logob_shape* shape, const rulgnn_logo_args* args, void* stream) {
+    return step_forward<Logob>(shape, args, stream);
+}
+int rulgnn_logob_backward_f32(const rulgnn_logob_shape* shape, const rulgnn_logo_args* args, void* stream) {
+    return step_backward<Logob>(shape, args, stream);
+}
+int rulgnn_logob_fwdbwd_f32(const rulgnn_logob_shape* shape, const rulgnn_logo_args* args, const rulgnn_adam_args* opt, void* stream) {
+    return step_fwdbwd<Logob>(shape, args, opt, stream);
 }
 
 // ---- DVGTformer ------------------------------------------------------------------------------------------

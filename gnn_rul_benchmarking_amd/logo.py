@@ -95,6 +95,10 @@ class LOGO_model(FlatModule):
                    "widest layer; a sample's whole window and the graph stage's matrices within one compute unit's 160 KB of LDS, "
                    "roughly num_nodes * num_patch * patch_size <= 38 000)").format(**LIMITS)
 
+    @property
+    def _feature_width(self):          # features per node and patch (LOGO_bearing: the STFT's frames)
+        return self.patch_size
+
     def _shape(self, batch):
         return _lib.LogoShape(batch, self.patch_size, self.num_patch, self.num_nodes, self.hidden_dim)
 
@@ -133,9 +137,9 @@ class LOGO_model(FlatModule):
     def tap(self, batch, which):
         """Workspace taps of the last forward at this batch size (parity tests): 'mpnn' [T N, B, 3p] (the graph stage's output, the
         LSTM stack's input), 'lstm' [T N, B, 3h] (the stack's output behind its closing leaky ReLU), 'gl' (L_GL, 0-d)."""
-        Q, p3, H1 = self.num_patch * self.num_nodes, 3 * self.patch_size, 3 * self.hidden_dim
+        Q, p3, H1 = self.num_patch * self.num_nodes, 3 * self._feature_width, 3 * self.hidden_dim
         idx = {"mpnn": 0, "lstm": 1, "gl": 2}[which]
-        off = _lib.load().rulgnn_logo_tap_offset(C.byref(self._shape(batch)), idx)
+        off = getattr(_lib.load(), f"rulgnn_{self.c_family}_tap_offset")(C.byref(self._shape(batch)), idx)
         ws = self._bufs[batch][0].view(torch.float32)
         if which == "mpnn":
             return ws[off:off + Q * batch * p3].view(Q, batch, p3).clone()

@@ -345,6 +345,8 @@ size_t rulgnn_stgcn_train_args_size(void);
 /* (index 37 is unassigned and answers 0) */
 #define RULGNN_STRUCT_GATLSTM_SHAPE 38
 #define RULGNN_STRUCT_GATLSTM_ARGS 39
+/* (index 40 is unassigned and answers 0; LOGO_bearing's argument struct is rulgnn_logo_args, index 32) */
+#define RULGNN_STRUCT_LOGOB_SHAPE 41
 size_t rulgnn_struct_size(int32_t which);
 
 /* Profiling aid: the training step is a chain of 4*num_layers+1 phase kernels:
@@ -1349,6 +1351,47 @@ int rulgnn_logo_forward_f32(const rulgnn_logo_shape *shape, const rulgnn_logo_ar
 int rulgnn_logo_backward_f32(const rulgnn_logo_shape *shape, const rulgnn_logo_args *args, void *stream);
 /* LOGO.update body (algorithms.py:125-136); with `opt` also Adam on the flat parameter buffer. */
 int rulgnn_logo_fwdbwd_f32(const rulgnn_logo_shape *shape, const rulgnn_logo_args *args, const rulgnn_adam_args *opt, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * LOGO_bearing path (reference models/LOGO_bearing/Model.py:263-347, algorithms/algorithms.py:601-629; wired to the bearing datasets
+ * PHM2012 and XJTU_SY, configs/hparams.py:228,244,... and :339,358,...): LOGO behind an STFT front end.
+ *
+ * T = num_patch, P = patch_size, ns = nperseg, N = num_nodes = ns/2 + 1, f = input_dim = 1 + P/ns, h = hidden_dim.
+ * x [batch, T * P] -> per (sample, patch) mag [N][f] = |STFT| as STNet's and GDAGDL's (n_fft = hop = win = ns, periodic Hann,
+ * reflect-centred without repeating the edge sample).  The N frequency bins are the graph's nodes, a patch's f frames their features:
+ * from here on this is the LOGO path above with p = f on the window X[b][n][t f + j] = mag[b, t][n][j] -- Pearson graph over the
+ * sample's [N][T f] spectrogram (a bin that is constant over the window gives 0 / 0 = NaN, as the reference), local graph, gated fusion,
+ * MPNN, L_GL, three Bi-LSTMs recurring along the batch, fc1 / fc2 / cls.  The spectrogram is never written to memory: both graph
+ * kernels rebuild it from x in LDS.  Same 46 tensors in the same flat layout (p = f), same dropout counters, same argument struct
+ * (rulgnn_logo_args, x = [batch, T * P]), same taps.  LOGO_bearing.update steps its MultiStepLR once per update: the caller's business
+ * (rulgnn_adam_args.lr).
+ * Limits (RULGNN_EUNSUPPORTED beyond, before any launch; the workspace query returns 0): ns even and >= 2, P > ns / 2,
+ * N <= RULGNN_LOGOB_MAX_NODES, f <= RULGNN_LOGOB_MAX_INPUT_DIM (the backward keeps the gradients of Theta [3f][2f] and W_n [2f][f] in
+ * registers, 26 + 9 per thread at f = 33), N T <= RULGNN_LOGOB_MAX_SEQUENCES, 6 h <= RULGNN_LOGOB_MAX_LSTM_WIDTH, and the sample's
+ * spectrogram plus the graph stage's matrices within one compute unit's 160 KB of LDS (XJTU_SY's N 17, f 33, T 32: 134 KB in the
+ * backward).  num_nodes / input_dim that do not equal the STFT's shape: RULGNN_EINVAL.  Deterministic: no floating-point atomics,
+ * fixed-order reductions.
+ */
+#define RULGNN_LOGOB_MAX_NODES 17
+#define RULGNN_LOGOB_MAX_INPUT_DIM 33
+#define RULGNN_LOGOB_MAX_SEQUENCES 65535
+#define RULGNN_LOGOB_MAX_LSTM_WIDTH 128
+
+typedef struct rulgnn_logob_shape {
+    int64_t batch;
+    int32_t patch_size, num_patch, input_dim, num_nodes, nperseg, hidden_dim;
+} rulgnn_logob_shape;
+
+int64_t rulgnn_logob_param_count(const rulgnn_logob_shape *shape);       /* < 0: invalid / unsupported */
+size_t rulgnn_logob_workspace_bytes(const rulgnn_logob_shape *shape);    /* 0: invalid / unsupported */
+/* workspace taps as rulgnn_logo_tap_offset's: 0 Hg [T N][batch][3f], 1 [batch][T N][3h], 2 {L_GL, sum(D . C), sum(C^2)}; -1 otherwise */
+int64_t rulgnn_logob_tap_offset(const rulgnn_logob_shape *shape, int32_t which);
+/* model(x, GL=True): LOGO_bearing_model.forward (Model.py:288-347). */
+int rulgnn_logob_forward_f32(const rulgnn_logob_shape *shape, const rulgnn_logo_args *args, void *stream);
+/* loss.backward() after a forward with the same args / workspace; theta = d loss / d L_GL. */
+int rulgnn_logob_backward_f32(const rulgnn_logob_shape *shape, const rulgnn_logo_args *args, void *stream);
+/* LOGO_bearing.update body (algorithms.py:619-629) short of its scheduler step; with `opt` also Adam on the flat parameter buffer. */
+int rulgnn_logob_fwdbwd_f32(const rulgnn_logob_shape *shape, const rulgnn_logo_args *args, const rulgnn_adam_args *opt, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * DVGTformer path (reference models/DVGTformer/Model.py, algorithms/algorithms.py:326-351; wired to C-MAPSS FD001-4 and N-CMAPSS,

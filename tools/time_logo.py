@@ -78,9 +78,15 @@ def trace(fn, x, y, steps):
     return sum(r[1] for r in rows) / steps, sum(r[2] for r in rows) / steps, [(k, c / steps, t / steps) for k, c, t in rows]
 
 
-def main():
+def batch(dev, cfg, B):
+    return torch.rand(B, cfg["num_nodes"], cfg["num_patch"] * cfg["patch_size"], device=dev), torch.rand(B, 1, device=dev)
+
+
+def main(shapes=("fd001", "fd002", "fd004", "ncmapss"), config=config, fused_step_fn=fused_step_fn, torch_step_fn=torch_step_fn,
+         make_batch=batch):
+    """``tools/time_logo_bearing.py`` runs this with its own wirings, step functions and inputs."""
     ap = argparse.ArgumentParser()
-    ap.add_argument("--shapes", nargs="+", default=["fd001", "fd002", "fd004", "ncmapss"])
+    ap.add_argument("--shapes", nargs="+", default=list(shapes))
     ap.add_argument("--batches", nargs="+", default=["own", "1024"])
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
@@ -101,7 +107,7 @@ def main():
         print(lines[-1], flush=True)
 
     def batch(cfg, B):
-        return torch.rand(B, cfg["num_nodes"], cfg["num_patch"] * cfg["patch_size"], device=dev), torch.rand(B, 1, device=dev)
+        return make_batch(dev, cfg, B)
 
     if args.trace or args.once:
         shape, B = (args.trace or args.once)[0], int((args.trace or args.once)[1])
