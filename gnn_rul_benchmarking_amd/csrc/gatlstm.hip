@@ -16,7 +16,7 @@
 // per graph, a wavefront per node strip; s, t, m, D in LDS); backward per layer one kernel (gl_att_bwd_kernel: recomputes s, t, m, D
 // from the saved Z, takes the sign of y from the saved h, writes dZ and one partial row [da1 | da2 | dc] per wavefront, summed in a
 // fixed order by rows_sum) and the GEMMs dW = dZ^T h, db = sum dZ, dh = dZ W.  The LSTMs are bilstm.hip's persistent kernels (one
-// direction), the head and the loss stnet_device.hpp's.  Between launches only feat, Z_l, h_l, dZ, dh, the LSTM tensors and the partial
+// direction), the head and the loss seq_backend.hip's.  Between launches only feat, Z_l, h_l, dZ, dh, the LSTM tensors and the partial
 // rows exist.  No floating-point atomics; the partial-row count is fixed by the launch geometry, so two runs give the same bits.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -24,7 +24,7 @@
 #include "sgemm_mfma.hpp"
 #include "families_host.hpp"       // (stgcn_host.hpp: dropout_layer_key)
 #include "stgcn_device.hpp"        // lowbias32
-#include "stnet_device.hpp"        // SB, the head's small kernels
+#include "seq_backend.hpp"         // the LSTM stack and the head (shared with stnet.hip and gdagdl.hip)
 
 namespace rulgnn {
 
@@ -42,17 +42,15 @@ static_assert(RULGNN_GATLSTM_MAX_NUM_PATCH <= GL_BLOCK / 2, "the backward sums d
 
 struct GlGeom {
     int64_t B, R;                                // samples = graphs, node rows = B * T
-    int T, P, nl, nk, E;                         // E: the last LSTM's width (the head's)
+    int T, P, nl;
     int C[GL_MAXL + 1];                          // channel widths: 11, hidden_dim...
-    int H[GL_MAXK + 1];                          // LSTM widths: C[nl], lstm_hidden_dim...
-    // flat parameter offsets
-    int o_w[GL_MAXL], o_b[GL_MAXL], o_aw[GL_MAXL], o_ab[GL_MAXL], o_wih[GL_MAXK], o_whh[GL_MAXK], o_bih[GL_MAXK], o_bhh[GL_MAXK], o_lw, o_lb,
-        pcount;
+    int o_w[GL_MAXL], o_b[GL_MAXL], o_aw[GL_MAXL], o_ab[GL_MAXL], pcount;      // flat parameter offsets of the GAT layers; the back end's are the plan's
+    LstmHeadPlan lh;                             // LSTM widths C[nl], lstm_hidden_dim... over the T nodes, Linear(E_K * T, 1)
     // workspace offsets (floats)
     int64_t w_wal[GL_MAXL];                      // 16-byte aligned copies of the projection weights (see Gatlstm::run)
-    int64_t w_feat, w_z[GL_MAXL], w_h[GL_MAXL], w_hseq[GL_MAXK], w_lstm[GL_MAXK], w_dpred, w_sq, w_dz, w_d1, w_d2, w_one, w_part, w_split,
-        total;
+    int64_t w_feat, w_z[GL_MAXL], w_h[GL_MAXL], w_dz, w_d1, w_d2, w_part, w_split, total;
 };
+static_assert(GL_MAXK <= SEQ_MAX_LSTM, "the plan holds every LSTM layer");
 
 // ---- LDS layout of the attention kernels, stated once for kernel and launcher (floats) ------------------------------------------------
 // forward: s, t, m (max_j t_j, the same in every entry), D [N] each; backward: the same, then g [N][3] (d_ij dy_i . Z_j on the band), q [N][3] (p_ij d_ij), r, ds, dt [N] each.
@@ -64,7 +62,9 @@ int gl_geometry(const rulgnn_gatlstm_shape* s, GlGeom* g) {
     if (s->num_patch > RULGNN_GATLSTM_MAX_NUM_PATCH || s->patch_size < RULGNN_GATLSTM_MIN_PATCH_SIZE ||
         s->patch_size > RULGNN_GATLSTM_MAX_PATCH_SIZE || s->num_gat > GL_MAXL || s->num_lstm > GL_MAXK)
         return RULGNN_EUNSUPPORTED;
-    g->B = s->batch; g->T = s->num_patch; g->P = s->patch_size; g->nl = s->num_gat; g->nk = s->num_lstm;
+    g->B = s->batch; g->T = s->num_patch; g->P = s->patch_size; g->nl = s->num_gat;
+    LstmHeadPlan& lh = g->lh;
+    lh.B = g->B; lh.T = g->T; lh.nk = s->num_lstm;
     g->C[0] = GL_F;
     int wmax = GL_F;
     for (int i = 0; i < g->nl; ++i) {
@@ -73,55 +73,34 @@ int gl_geometry(const rulgnn_gatlstm_shape* s, GlGeom* g) {
         g->C[i + 1] = s->hidden_dim[i];
         if (g->C[i + 1] > wmax) wmax = g->C[i + 1];
     }
-    g->H[0] = g->C[g->nl];
-    for (int k = 0; k < g->nk; ++k) {
+    lh.H[0] = g->C[g->nl];
+    for (int k = 0; k < lh.nk; ++k) {
         if (s->lstm_hidden_dim[k] < 1) return RULGNN_EINVAL;
         if (s->lstm_hidden_dim[k] > RULGNN_GATLSTM_MAX_LSTM_HIDDEN) return RULGNN_EUNSUPPORTED;
-        g->H[k + 1] = s->lstm_hidden_dim[k];
-        if (g->H[k + 1] > wmax) wmax = g->H[k + 1];
+        lh.H[k + 1] = s->lstm_hidden_dim[k];
+        if (lh.H[k + 1] > wmax) wmax = lh.H[k + 1];
     }
-    g->E = g->H[g->nk];
     g->R = g->B * g->T;
     if (g->R * (int64_t)wmax > 0x7fffffff) return RULGNN_EUNSUPPORTED;      // the GEMMs take int extents
     int o = 0;
+    int64_t w = 0;
+    SplitKScratch sp(1024);
     auto tk = [&](int n) { const int r = o; o += n; return r; };
+    auto wk = [&](int64_t n) { const int64_t r = w; w += (n + 63) & ~(int64_t)63; return r; };
     for (int i = 0; i < g->nl; ++i) {
         g->o_w[i] = tk(g->C[i + 1] * g->C[i]); g->o_b[i] = tk(g->C[i + 1]);
         g->o_aw[i] = tk(2 * g->C[i + 1]); g->o_ab[i] = tk(1);
     }
-    for (int k = 0; k < g->nk; ++k) {
-        const int I = g->H[k], E = g->H[k + 1];
-        g->o_wih[k] = tk(4 * E * I); g->o_whh[k] = tk(4 * E * E); g->o_bih[k] = tk(4 * E); g->o_bhh[k] = tk(4 * E);
-    }
-    g->o_lw = tk(g->E * g->T); g->o_lb = tk(1);
-    g->pcount = o;
-    int64_t w = 0;
-    auto wk = [&](int64_t n) { const int64_t r = w; w += (n + 63) & ~(int64_t)63; return r; };
     const int64_t R = g->R;
     g->w_feat = wk(R * GL_F);
     for (int i = 0; i < g->nl; ++i) { g->w_z[i] = wk(R * g->C[i + 1]); g->w_h[i] = wk(R * g->C[i + 1]); }
-    for (int k = 0; k < g->nk; ++k) g->w_hseq[k] = wk(R * g->H[k + 1]);
-    g->w_dpred = wk(g->B); g->w_sq = wk(g->B);
+    RULGNN_TRY(lstm_head_layout(&lh, &o, &w, &sp));
+    g->pcount = o;
     g->w_dz = wk(R * wmax); g->w_d1 = wk(R * wmax); g->w_d2 = wk(R * wmax);
-    g->w_one = wk(64);
     g->w_part = wk((int64_t)GL_ATT_MAXGRID * GL_WAVES * (2 * wmax + 1));
     for (int i = 0; i < g->nl; ++i) g->w_wal[i] = wk((int64_t)g->C[i] * g->C[i + 1]);
-    int64_t sp = 1024;
-    auto need = [&](int M, int Nn, int64_t K) {
-        if (K > 0x7fffffff) return;
-        const int64_t v = (int64_t)sgemm_splitk_need_floats(M, Nn, (int)K);
-        if (v > sp) sp = v;
-    };
-    for (int i = 0; i < g->nl; ++i) { need(g->C[i + 1], g->C[i], R); need(1, g->C[i + 1], R); }
-    need(1, g->E * g->T, g->B);
-    need(1, 1, g->B);
-    g->w_split = wk(sp);
-    for (int k = 0; k < g->nk; ++k) {
-        rulgnn_bilstm_shape ls{g->T, (int32_t)(g->B > 0 ? g->B : 1), g->H[k], g->H[k + 1]};
-        const size_t lb = bilstm_workspace_bytes(&ls);
-        if (lb == 0) return RULGNN_EUNSUPPORTED;
-        g->w_lstm[k] = wk((int64_t)(lb / sizeof(float)) + 64);
-    }
+    for (int i = 0; i < g->nl; ++i) { sp.need(g->C[i + 1], g->C[i], R); sp.need(1, g->C[i + 1], R); }
+    g->w_split = wk((int64_t)sp.floats());
     g->total = w;
     return RULGNN_OK;
 }
@@ -433,7 +412,7 @@ int64_t Gatlstm::tap_offset(const Shape* s, int which) {
     if (gl_geometry(s, &g) != RULGNN_OK) return -1;
     if (which == 0) return g.w_feat;
     if (which >= 1 && which <= g.nl) return g.w_h[which - 1];
-    if (which == RULGNN_GATLSTM_TAP_LSTM) return g.w_hseq[g.nk - 1];
+    if (which == RULGNN_GATLSTM_TAP_LSTM) return g.lh.w_hseq[g.lh.nk - 1];
     return -1;
 }
 
@@ -447,31 +426,16 @@ int Gatlstm::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
     const float* prm = a->params;
     const int64_t gb = a->global_batch > 0 ? a->global_batch : g.B;
     const float inv_gb = 1.0f / (float)gb;
-    const int nl = g.nl, nk = g.nk, R = (int)g.R;
+    const int nl = g.nl, R = (int)g.R;
     float* split = ws + g.w_split;
+    const float* hgat = ws + g.w_h[nl - 1];       // the last GAT layer's output: the LSTM stack's input
     (void)hipGetLastError();
-    // LSTM layer k: bilstm.hip's persistent kernels with one direction, {seq_len = T, num_seq = B}
-    auto lstm = [&](int k, rulgnn_bilstm_shape* ls, rulgnn_bilstm_args* la) {
-        *ls = rulgnn_bilstm_shape{g.T, (int32_t)g.B, g.H[k], g.H[k + 1]};
-        *la = rulgnn_bilstm_args{};
-        la->x = k > 0 ? ws + g.w_hseq[k - 1] : ws + g.w_h[nl - 1];
-        la->w_ih[0] = la->w_ih[1] = prm + g.o_wih[k]; la->w_hh[0] = la->w_hh[1] = prm + g.o_whh[k];
-        la->b_ih[0] = la->b_ih[1] = prm + g.o_bih[k]; la->b_hh[0] = la->b_hh[1] = prm + g.o_bhh[k];
-        la->out = ws + g.w_hseq[k];
-        la->workspace = ws + g.w_lstm[k];
-        la->workspace_bytes = bilstm_workspace_bytes(ls);
-    };
-    // The projection weights as GEMM operands: the flat buffer puts them behind odd-sized tensors, off a 16-byte boundary, and the
-    // large-tile GEMM falls back to the 64 x 64 fp32 tiles for a misaligned operand: a misaligned weight is copied into the workspace
-    // once per call (gdagdl.hip does the same).
+    // The projection weights as GEMM operands: the flat buffer puts them behind odd-sized tensors, off a 16-byte boundary
+    // (seq_backend.hpp: aligned_operand).
     const float* wop[GL_MAXL];
     for (int i = 0; i < nl; ++i) {
-        wop[i] = prm + g.o_w[i];
-        if (reinterpret_cast<uintptr_t>(wop[i]) & 15) {
-            if (hipMemcpyAsync(ws + g.w_wal[i], wop[i], sizeof(float) * g.C[i] * g.C[i + 1], hipMemcpyDeviceToDevice, st) != hipSuccess)
-                return RULGNN_EHIP;
-            wop[i] = ws + g.w_wal[i];
-        }
+        wop[i] = aligned_operand(prm + g.o_w[i], (size_t)g.C[i] * g.C[i + 1], ws + g.w_wal[i], st);
+        if (!wop[i]) return RULGNN_EHIP;
     }
     GlAtt q{};
     q.G = g.B; q.g0 = a->sample_offset; q.N = g.T;
@@ -495,43 +459,18 @@ int Gatlstm::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
             RULGNN_TRY(launch_checked(gl_att_fwd_kernel, dim3(L.grid), dim3(GL_BLOCK), L.lds, st, q));
             cur = ws + g.w_h[i];
         }
-        for (int k = 0; k < nk; ++k) {
-            rulgnn_bilstm_shape ls;
-            rulgnn_bilstm_args la;
-            lstm(k, &ls, &la);
-            RULGNN_TRY(bilstm_forward(&ls, &la, st, 1));
-        }
-        hipLaunchKernelGGL(sn_head_kernel<GlGeom>, dim3((unsigned)(g.B < 1024 ? g.B : 1024)), dim3(SB), 0, st, g,
-                           (const float*)(ws + g.w_hseq[nk - 1]), prm, a->y, a->pred, ws, inv_gb);
-        RULGNN_LAUNCH_OK();
-        if (a->y && a->loss) RULGNN_TRY(block_sum((const float*)(ws + g.w_sq), g.B, a->loss, st));
+        RULGNN_TRY(lstm_head_forward(g.lh, hgat, prm, ws, a->y, a->pred, inv_gb, st));
+        if (a->y && a->loss) RULGNN_TRY(block_sum((const float*)(ws + g.lh.w_sq), g.B, a->loss, st));
     }
     if (mode & 2) {
         if (!a->grads) return RULGNN_EINVAL;
         float* gr = a->grads;
-        const float* dpred = a->dpred ? a->dpred : ws + g.w_dpred;
-        float* one = ws + g.w_one;
+        const float* dpred = a->dpred ? a->dpred : ws + g.lh.w_dpred;
+        float* one = ws + g.lh.w_one;
         RULGNN_TRY(fill_f32(one, 1, 1.0f, st));
-        // head
-        const int ET = g.E * g.T;
-        RULGNN_TRY(sgemm_splitk(dpred, 0, 1, ws + g.w_hseq[nk - 1], 1, ET, gr + g.o_lw, ET, 1, ET, (int)g.B, false, split, st));
-        RULGNN_TRY(sgemm_splitk(dpred, 0, 1, one, 0, 0, gr + g.o_lb, 1, 1, 1, (int)g.B, false, split, st));
-        float* dbuf[2] = {ws + g.w_d1, ws + g.w_d2};      // the data gradient walks down through two buffers
-        int cur = 0;
-        hipLaunchKernelGGL(sn_head_bwd_kernel<GlGeom>, dim3(sn_grid(g.B * ET)), dim3(SB), 0, st, g, dpred, prm, dbuf[cur]);
-        RULGNN_LAUNCH_OK();
-        // LSTM stack: layer k's dx is layer k - 1's dout, layer 0's is d h of the last GAT layer
-        for (int k = nk - 1; k >= 0; --k) {
-            rulgnn_bilstm_shape ls;
-            rulgnn_bilstm_args la;
-            lstm(k, &ls, &la);
-            la.dout = dbuf[cur];
-            la.dx = dbuf[cur ^ 1];
-            la.dw_ih[0] = la.dw_ih[1] = gr + g.o_wih[k]; la.dw_hh[0] = la.dw_hh[1] = gr + g.o_whh[k];
-            la.db_ih[0] = la.db_ih[1] = gr + g.o_bih[k]; la.db_hh[0] = la.db_hh[1] = gr + g.o_bhh[k];
-            RULGNN_TRY(bilstm_backward(&ls, &la, st, 1));
-            cur ^= 1;
-        }
+        float* const dbuf[2] = {ws + g.w_d1, ws + g.w_d2};      // the data gradient walks down through two buffers
+        RULGNN_TRY(lstm_head_backward(g.lh, hgat, prm, ws, dpred, gr, dbuf, split, st));
+        int cur = g.lh.nk & 1;                       // d h of the last GAT layer
         GlLaunch L;
         RULGNN_TRY(gl_att_launch(gl_att_bwd_kernel, g, true, &L));
         for (int i = nl - 1; i >= 0; --i) {
@@ -543,11 +482,9 @@ int Gatlstm::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
             // attention.weight [2 Co] and attention.bias [1] are adjacent in the flat layout: one fixed-order sum of the partial rows
             RULGNN_TRY(rows_sum(ws + g.w_part, L.grid * GL_WAVES, 2 * Co + 1, 2 * Co + 1, gr + g.o_aw[i], st));
             const float* hin = i > 0 ? ws + g.w_h[i - 1] : ws + g.w_feat;
-            const float* dz = ws + g.w_dz;
-            RULGNN_TRY(sgemm_splitk(dz, 1, Co, hin, 1, Ci, gr + g.o_w[i], Ci, Co, Ci, R, false, split, st));
-            RULGNN_TRY(sgemm_splitk(one, 0, 0, dz, 1, Co, gr + g.o_b[i], Co, 1, Co, R, false, split, st));
-            if (i == 0) break;                        // the features have no parameters upstream
-            RULGNN_TRY(sgemm(dz, Co, 1, wop[i], 1, Ci, dbuf[cur ^ 1], Ci, R, Ci, Co, false, st));
+            // (the features have no parameters upstream)
+            RULGNN_TRY(dense_backward(ws + g.w_dz, hin, wop[i], one, gr + g.o_w[i], gr + g.o_b[i], i > 0 ? DENSE_PLAIN : DENSE_NO_DATA, dbuf[cur ^ 1], R,
+                                      Co, Ci, split, st));
             cur ^= 1;
         }
     }

@@ -2,7 +2,7 @@
 // Reference path replaced: GDAGDL_model.forward -- models/GDAGDL/Model.py:66-170 (GraphAttentionLayer :6-39, pcc_graph_construction
 // :42-63) -- and GDAGDL.update, algorithms/algorithms.py:519-544 (loss = MSE(pred, y) + the auto-encoder's reconstruction MSE).
 //
-//   x [bs, T * P] -> per (sample, patch) graph: mag = |STFT| (stnet_device.hpp) = N frequency nodes x f frames -> the reference's
+//   x [bs, T * P] -> per (sample, patch) graph: mag = |STFT| (stft_device.hpp) = N frequency nodes x f frames -> the reference's
 //   "Pearson" matrix of the nodes over the frames: c = mag - mean_f(mag), pcc = (c reshape(c, [f, N])) / (|c_i| |c_j|) -- the second
 //   operand is the tile reshaped, not transposed (Model.py:51), a quirk kept because the mask, and with it every prediction, follows
 //   from it; no epsilon: an all-zero patch gives 0 / 0 = NaN -> ni = pcc (mag w_ni + b_ni) -> m = (ni > 0), adjacency
@@ -24,7 +24,8 @@
 #include "sgemm_mfma.hpp"
 #include "families_host.hpp"       // (stgcn_host.hpp: dropout_layer_key)
 #include "stgcn_device.hpp"        // lowbias32
-#include "stnet_device.hpp"        // SB, the STFT magnitude, the back end's small kernels (shared with stnet.hip)
+#include "stft_device.hpp"         // SB, the STFT magnitude
+#include "seq_backend.hpp"         // the auto-encoder, the LSTM and the head (shared with stnet.hip and gatlstm.hip)
 
 namespace rulgnn {
 
@@ -40,15 +41,13 @@ struct GdGeom {
     int T, P, nseg, N, f, nl, A, O, E;
     int C[GD_MAXL + 1];                         // channel widths: f, gat_layer_dim...
     int D;                                      // N * C[last]: auto-encoder width
-    int ein[4], eout[4], din[4], dout[4];       // encoder / decoder Linear widths
-    // flat parameter offsets (the two gradless tensors first)
-    int o_niw, o_nib, o_w[GD_MAXL], o_b[GD_MAXL], o_aw[GD_MAXL], o_ab[GD_MAXL], o_enc_w[4], o_enc_b[4], o_dec_w[4], o_dec_b[4], o_wih,
-        o_whh, o_bih, o_bhh, o_lw, o_lb, pcount;
+    // flat parameter offsets of the front end and the GAT layers (the two gradless tensors first); the back end's are the plans'
+    int o_niw, o_nib, o_w[GD_MAXL], o_b[GD_MAXL], o_aw[GD_MAXL], o_ab[GD_MAXL], pcount;
+    AutoEncoderPlan ae;                         // D -> A -> A/2 -> A/4 -> O and back
+    LstmHeadPlan lh;                            // one LSTM O -> E over the T patches, Linear(E * T, 1)
     // workspace offsets (floats)
     int64_t w_wal[GD_MAXL];                     // 16-byte aligned copies of the projection weights (see Gdagdl::run)
-    int64_t w_mag, w_ni, w_mask, w_z[GD_MAXL], w_h[GD_MAXL], w_enc[4], w_dec[4], w_hseq, w_dpred, w_sq, w_rsq, w_dD1, w_dD2, w_dA1, w_dA2,
-        w_dz, w_dh, w_dhs, w_dH, w_one, w_part, w_split, w_lstm, total;
-    int rblocks;                                // workgroups of the reconstruction-error kernel (= partial sums)
+    int64_t w_mag, w_ni, w_mask, w_z[GD_MAXL], w_h[GD_MAXL], w_dz, w_dh, w_dhs, w_part, w_split, total;
 };
 
 // ---- LDS layouts, stated once for kernel and launcher (floats) -------------------------------------------------------------------
@@ -99,55 +98,32 @@ int gd_geometry(const rulgnn_gdagdl_shape* s, GdGeom* g) {
     g->D = g->N * g->C[g->nl];
     if (g->R * (int64_t)(cmax > g->f ? cmax : g->f) > 0x7fffffff) return RULGNN_EUNSUPPORTED;      // the GEMMs take int extents
     const int A = g->A, D = g->D, O = g->O;
-    const int ein[4] = {D, A, A / 2, A / 4}, eout[4] = {A, A / 2, A / 4, O}, din[4] = {O, A / 4, A / 2, A}, dout[4] = {A / 4, A / 2, A, D};
-    for (int i = 0; i < 4; ++i) { g->ein[i] = ein[i]; g->eout[i] = eout[i]; g->din[i] = din[i]; g->dout[i] = dout[i]; }
     int o = 0;
+    int64_t w = 0;
+    SplitKScratch sp(1024);
     auto tk = [&](int n) { const int r = o; o += n; return r; };
+    auto wk = [&](int64_t n) { const int64_t r = w; w += (n + 63) & ~(int64_t)63; return r; };
     g->o_niw = tk(g->f); g->o_nib = tk(1);
     for (int i = 0; i < g->nl; ++i) {
         g->o_w[i] = tk(g->C[i + 1] * g->C[i]); g->o_b[i] = tk(g->C[i + 1]);
         g->o_aw[i] = tk(2 * g->C[i + 1]); g->o_ab[i] = tk(1);
     }
-    for (int i = 0; i < 4; ++i) { g->o_enc_w[i] = tk(eout[i] * ein[i]); g->o_enc_b[i] = tk(eout[i]); }
-    for (int i = 0; i < 4; ++i) { g->o_dec_w[i] = tk(dout[i] * din[i]); g->o_dec_b[i] = tk(dout[i]); }
-    g->o_wih = tk(4 * g->E * O); g->o_whh = tk(4 * g->E * g->E); g->o_bih = tk(4 * g->E); g->o_bhh = tk(4 * g->E);
-    g->o_lw = tk(g->E * g->T); g->o_lb = tk(1);
-    g->pcount = o;
-    int64_t w = 0;
-    auto wk = [&](int64_t n) { const int64_t r = w; w += (n + 63) & ~(int64_t)63; return r; };
     const int64_t R = g->R, BT = g->BT;
     g->w_mag = wk(R * g->f); g->w_ni = wk(R); g->w_mask = wk(R);
     for (int i = 0; i < g->nl; ++i) { g->w_z[i] = wk(R * g->C[i + 1]); g->w_h[i] = wk(R * g->C[i + 1]); }
-    int amax = A > O ? A : O;
-    for (int i = 0; i < 4; ++i) g->w_enc[i] = wk(BT * eout[i]);
-    for (int i = 0; i < 4; ++i) g->w_dec[i] = wk(BT * dout[i]);
-    g->w_hseq = wk(BT * g->E);
-    g->w_dpred = wk(g->B); g->w_sq = wk(g->B);
-    g->rblocks = 1024;
-    g->w_rsq = wk(g->rblocks);
-    g->w_dD1 = wk(BT * D); g->w_dD2 = wk(BT * D);
-    g->w_dA1 = wk(BT * amax); g->w_dA2 = wk(BT * amax);
+    const int ein[4] = {D, A, A / 2, A / 4}, eout[4] = {A, A / 2, A / 4, O}, din[4] = {O, A / 4, A / 2, A}, dout[4] = {A / 4, A / 2, A, D};
+    g->ae.BT = BT;
+    for (int i = 0; i < 4; ++i) { g->ae.ein[i] = ein[i]; g->ae.eout[i] = eout[i]; g->ae.din[i] = din[i]; g->ae.dout[i] = dout[i]; }
+    autoencoder_layout(&g->ae, &o, &w, &sp);
+    g->lh.B = g->B; g->lh.T = g->T; g->lh.nk = 1; g->lh.H[0] = O; g->lh.H[1] = g->E;
+    RULGNN_TRY(lstm_head_layout(&g->lh, &o, &w, &sp));
+    g->pcount = o;
     g->w_dz = wk(R * cmax); g->w_dh = wk(R * cmax);
-    g->w_dhs = wk(BT * g->E); g->w_dH = wk(BT * O);
-    g->w_one = wk(64);
+    g->w_dhs = wk(BT * g->E);
     g->w_part = wk((int64_t)GD_ATT_MAXGRID * GD_MAXWAVES * (2 * cmax + 1));
     for (int i = 0; i < g->nl; ++i) g->w_wal[i] = wk((int64_t)g->C[i] * g->C[i + 1]);
-    int64_t sp = 1024;
-    auto need = [&](int M, int Nn, int64_t K) {
-        if (K > 0x7fffffff) return;
-        const int64_t v = (int64_t)sgemm_splitk_need_floats(M, Nn, (int)K);
-        if (v > sp) sp = v;
-    };
-    for (int i = 0; i < g->nl; ++i) { need(g->C[i + 1], g->C[i], R); need(1, g->C[i + 1], R); }
-    for (int i = 0; i < 4; ++i) { need(eout[i], ein[i], BT); need(1, eout[i], BT); need(dout[i], din[i], BT); need(1, dout[i], BT); }
-    need(1, g->E * g->T, g->B);
-    need(1, 1, g->B);
-    for (int i = 0; i < 4; ++i) { need((int)BT, eout[i], ein[i]); need((int)BT, din[i], dout[i]); }      // activations over a long reduction: gemm_rows
-    g->w_split = wk(sp);
-    rulgnn_bilstm_shape ls{g->T, (int32_t)(g->B > 0 ? g->B : 1), O, g->E};
-    const size_t lb = bilstm_workspace_bytes(&ls);
-    if (lb == 0) return RULGNN_EUNSUPPORTED;
-    g->w_lstm = wk((int64_t)(lb / sizeof(float)) + 64);
+    for (int i = 0; i < g->nl; ++i) { sp.need(g->C[i + 1], g->C[i], R); sp.need(1, g->C[i + 1], R); }
+    g->w_split = wk((int64_t)sp.floats());
     g->total = w;
     return RULGNN_OK;
 }
@@ -446,7 +422,7 @@ int64_t Gdagdl::tap_offset(const Shape* s, int which) {
     case 1: return g.w_ni;
     case 2: return g.w_mask;
     case 3: return g.w_h[g.nl - 1];
-    case 4: return g.w_enc[3];
+    case 4: return g.ae.w_enc[3];
     default: return -1;
     }
 }
@@ -461,38 +437,20 @@ int Gdagdl::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
     const float* prm = a->params;
     const int64_t gb = a->global_batch > 0 ? a->global_batch : g.B;
     const float inv_gb = 1.0f / (float)gb;
-    const int D = g.D, E = g.E, O = g.O, nl = g.nl;
-    const int R = (int)g.R, BT = (int)g.BT;
-    const int *ein = g.ein, *eout = g.eout, *din = g.din, *dout = g.dout;
-    const float rscale = 1.0f / ((float)gb * (float)g.T * (float)D);          // 1 / elements of the global batch's Y_o
+    const int nl = g.nl, R = (int)g.R;
+    const float rscale = 1.0f / ((float)gb * (float)g.T * (float)g.D);          // 1 / elements of the global batch's Y_o
     float* split = ws + g.w_split;
-    rulgnn_bilstm_shape ls{g.T, (int32_t)g.B, O, E};
-    rulgnn_bilstm_args la{};
-    la.x = ws + g.w_enc[3];
-    la.w_ih[0] = prm + g.o_wih; la.w_hh[0] = prm + g.o_whh; la.b_ih[0] = prm + g.o_bih; la.b_hh[0] = prm + g.o_bhh;
-    la.w_ih[1] = la.w_ih[0]; la.w_hh[1] = la.w_hh[0]; la.b_ih[1] = la.b_ih[0]; la.b_hh[1] = la.b_hh[0];
-    la.out = ws + g.w_hseq;
-    la.workspace = ws + g.w_lstm;
-    la.workspace_bytes = bilstm_workspace_bytes(&ls);
+    float* one = ws + g.lh.w_one;                 // [0] = 1 (backward), [1] the reconstruction term, [2] the MSE, [3] = 0
+    const float* yo = ws + g.w_h[nl - 1];         // Y_o as [BT, D] rows
+    const float* henc = ws + g.ae.w_enc[3];       // the encoder's output: the LSTM's input
     const unsigned ggrid = (unsigned)(g.G < 4096 ? g.G : 4096);
     (void)hipGetLastError();
-    // a short product over a long reduction: split over k (stnet.hip: gemm_rows)
-    auto gemm_rows = [&](const float* Am, int64_t sAm, int64_t sAk, const float* Bm, int64_t sBn, int64_t sBk, float* Cm, int64_t ldc, int M, int N,
-                         int K) -> int {
-        if (K >= 512 && (int64_t)((M + 63) / 64) * ((N + 63) / 64) < 128) return sgemm_splitk(Am, sAm, sAk, Bm, sBn, sBk, Cm, ldc, M, N, K, false, split, st);
-        return sgemm(Am, sAm, sAk, Bm, sBn, sBk, Cm, ldc, M, N, K, false, st);
-    };
     // The projection weights as GEMM operands: the flat buffer puts them behind f + 1 floats and odd-sized tensors, off a 16-byte
-    // boundary, and the large-tile GEMM falls back to the 64 x 64 fp32 tiles for a misaligned operand (stnet.hip measured 25 %): a
-    // misaligned weight is copied into the workspace once per call.
+    // boundary (seq_backend.hpp: aligned_operand).
     const float* wop[GD_MAXL];
     for (int i = 0; i < nl; ++i) {
-        wop[i] = prm + g.o_w[i];
-        if (reinterpret_cast<uintptr_t>(wop[i]) & 15) {
-            if (hipMemcpyAsync(ws + g.w_wal[i], wop[i], sizeof(float) * g.C[i] * g.C[i + 1], hipMemcpyDeviceToDevice, st) != hipSuccess)
-                return RULGNN_EHIP;
-            wop[i] = ws + g.w_wal[i];
-        }
+        wop[i] = aligned_operand(prm + g.o_w[i], (size_t)g.C[i] * g.C[i + 1], ws + g.w_wal[i], st);
+        if (!wop[i]) return RULGNN_EHIP;
     }
     GdAtt q{};
     q.G = g.G; q.g0 = a->sample_offset * (int64_t)g.T; q.N = g.N; q.mask = ws + g.w_mask;
@@ -501,7 +459,7 @@ int Gdagdl::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
     if (mode & 1) {
         const size_t lds = sizeof(float) * gd_front_lds_floats(g.P, g.nseg, g.N, g.f);
         if (lds > DEFAULT_LDS_BYTES) return RULGNN_EUNSUPPORTED;
-        RULGNN_TRY(fill_f32(ws + g.w_one + 3, 1, 0.0f, st));
+        RULGNN_TRY(fill_f32(one + 3, 1, 0.0f, st));
         hipLaunchKernelGGL(gd_front_kernel, dim3(ggrid), dim3(SB), lds, st, g, a->x, prm, ws);
         RULGNN_LAUNCH_OK();
         const float* cur = ws + g.w_mag;
@@ -516,87 +474,24 @@ int Gdagdl::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
             RULGNN_LAUNCH_OK();
             cur = ws + g.w_h[i];
         }
-        const float* h = cur;                         // Y_o as [BT, D] rows
-        for (int i = 0; i < 4; ++i) {
-            RULGNN_TRY(gemm_rows(h, ein[i], 1, prm + g.o_enc_w[i], ein[i], 1, ws + g.w_enc[i], eout[i], BT, eout[i], ein[i]));
-            hipLaunchKernelGGL(sn_bias_act_kernel, dim3(sn_grid((int64_t)BT * eout[i])), dim3(SB), 0, st, ws + g.w_enc[i], prm + g.o_enc_b[i],
-                               (int64_t)BT, eout[i], i < 3 ? 1 : 0);
-            h = ws + g.w_enc[i];
-        }
-        for (int i = 0; i < 4; ++i) {
-            RULGNN_TRY(sgemm(h, din[i], 1, prm + g.o_dec_w[i], din[i], 1, ws + g.w_dec[i], dout[i], BT, dout[i], din[i], false, st));
-            hipLaunchKernelGGL(sn_bias_act_kernel, dim3(sn_grid((int64_t)BT * dout[i])), dim3(SB), 0, st, ws + g.w_dec[i], prm + g.o_dec_b[i],
-                               (int64_t)BT, dout[i], i < 3 ? 1 : 0);
-            h = ws + g.w_dec[i];
-        }
-        RULGNN_LAUNCH_OK();
-        // reconstruction error (and, when a backward follows, its gradients w.r.t. both of its arguments)
-        hipLaunchKernelGGL(sn_recon_kernel, dim3(g.rblocks), dim3(SB), 0, st, (const float*)cur, (const float*)(ws + g.w_dec[3]), (int64_t)BT * D,
-                           rscale, ws + g.w_dD1, ws + g.w_dD2, ws + g.w_rsq);
-        (void)block_sum((const float*)(ws + g.w_rsq), (int64_t)g.rblocks, ws + g.w_one + 1, st);
-        RULGNN_LAUNCH_OK();
-        RULGNN_TRY(bilstm_forward(&ls, &la, st, 1));
-        hipLaunchKernelGGL(sn_head_kernel<GdGeom>, dim3((unsigned)(g.B < 1024 ? g.B : 1024)), dim3(SB), 0, st, g, (const float*)(ws + g.w_hseq), prm,
-                           a->y, a->pred, ws, inv_gb);
-        if (a->recon) hipLaunchKernelGGL(sn_loss_kernel, dim3(1), dim3(1), 0, st, (const float*)(ws + g.w_one + 1), (const float*)(ws + g.w_one + 3),
-                                         a->recon);          // w_one + 3 holds 0
+        RULGNN_TRY(autoencoder_forward(g.ae, yo, prm, ws, rscale, one + 1, split, st));
+        RULGNN_TRY(lstm_head_forward(g.lh, henc, prm, ws, a->y, a->pred, inv_gb, st));
+        if (a->recon) RULGNN_TRY(sum_pair(one + 1, one + 3, a->recon, st));
         if (a->y && a->loss) {
-            (void)block_sum((const float*)(ws + g.w_sq), g.B, ws + g.w_one + 2, st);
-            hipLaunchKernelGGL(sn_loss_kernel, dim3(1), dim3(1), 0, st, (const float*)(ws + g.w_one + 1), (const float*)(ws + g.w_one + 2), a->loss);
+            RULGNN_TRY(block_sum((const float*)(ws + g.lh.w_sq), g.B, one + 2, st));
+            RULGNN_TRY(sum_pair(one + 1, one + 2, a->loss, st));
         }
-        RULGNN_LAUNCH_OK();
     }
     if (mode & 2) {
         if (!a->grads) return RULGNN_EINVAL;
         float* gr = a->grads;
-        const float* dpred = a->dpred ? a->dpred : ws + g.w_dpred;
-        float* one = ws + g.w_one;
+        const float* dpred = a->dpred ? a->dpred : ws + g.lh.w_dpred;
         RULGNN_TRY(fill_f32(one, 1, 1.0f, st));
         RULGNN_TRY(fill_f32(gr + g.o_niw, g.f + 1, 0.0f, st));          // the mask has no gradient
-        // head
-        RULGNN_TRY(sgemm_splitk(dpred, 0, 1, ws + g.w_hseq, 1, E * g.T, gr + g.o_lw, E * g.T, 1, E * g.T, (int)g.B, false, split, st));
-        RULGNN_TRY(sgemm_splitk(dpred, 0, 1, one, 0, 0, gr + g.o_lb, 1, 1, 1, (int)g.B, false, split, st));
-        hipLaunchKernelGGL(sn_head_bwd_kernel<GdGeom>, dim3(sn_grid(g.B * E * g.T)), dim3(SB), 0, st, g, dpred, prm, ws + g.w_dhs);
-        RULGNN_LAUNCH_OK();
-        la.dout = ws + g.w_dhs;
-        la.dx = ws + g.w_dH;
-        la.dw_ih[0] = gr + g.o_wih; la.dw_hh[0] = gr + g.o_whh; la.db_ih[0] = gr + g.o_bih; la.db_hh[0] = gr + g.o_bhh;
-        la.dw_ih[1] = la.dw_ih[0]; la.dw_hh[1] = la.dw_hh[0]; la.db_ih[1] = la.db_ih[0]; la.db_hh[1] = la.db_hh[0];
-        RULGNN_TRY(bilstm_backward(&ls, &la, st, 1));
-        // decoder, from d Yp = w_dD1 (the reconstruction scale of a data-parallel shard is the global one: recon is in the loss with weight 1)
-        if (a->recon_weight)
-            hipLaunchKernelGGL(sn_scale2_kernel, dim3(sn_grid((int64_t)BT * D)), dim3(SB), 0, st, ws + g.w_dD1, ws + g.w_dD2, (int64_t)BT * D,
-                               a->recon_weight);
-        float* d = ws + g.w_dD1;
-        float* dA[2] = {ws + g.w_dA1, ws + g.w_dA2};
-        for (int i = 3; i >= 0; --i) {
-            const float* hin = i > 0 ? ws + g.w_dec[i - 1] : ws + g.w_enc[3];
-            if (i < 3) hipLaunchKernelGGL(sn_relu_bwd_kernel, dim3(sn_grid((int64_t)BT * dout[i])), dim3(SB), 0, st, d, (const float*)(ws + g.w_dec[i]),
-                                          (int64_t)BT * dout[i]);
-            RULGNN_TRY(sgemm_splitk(d, 1, dout[i], hin, 1, din[i], gr + g.o_dec_w[i], din[i], dout[i], din[i], BT, false, split, st));
-            RULGNN_TRY(sgemm_splitk(one, 0, 0, d, 1, dout[i], gr + g.o_dec_b[i], dout[i], 1, dout[i], BT, false, split, st));
-            float* dn = dA[i & 1];
-            RULGNN_TRY(gemm_rows(d, dout[i], 1, prm + g.o_dec_w[i], 1, din[i], dn, din[i], BT, din[i], dout[i]));
-            d = dn;
-        }
-        // d H = decoder path + LSTM path
-        hipLaunchKernelGGL(sn_add_kernel, dim3(sn_grid((int64_t)BT * O)), dim3(SB), 0, st, d, (const float*)(ws + g.w_dH), (int64_t)BT * O);
-        RULGNN_LAUNCH_OK();
-        const float* yo = ws + g.w_h[nl - 1];
-        for (int i = 3; i >= 0; --i) {
-            const float* hin = i > 0 ? ws + g.w_enc[i - 1] : yo;
-            if (i < 3) hipLaunchKernelGGL(sn_relu_bwd_kernel, dim3(sn_grid((int64_t)BT * eout[i])), dim3(SB), 0, st, d, (const float*)(ws + g.w_enc[i]),
-                                          (int64_t)BT * eout[i]);
-            RULGNN_TRY(sgemm_splitk(d, 1, eout[i], hin, 1, ein[i], gr + g.o_enc_w[i], ein[i], eout[i], ein[i], BT, false, split, st));
-            RULGNN_TRY(sgemm_splitk(one, 0, 0, d, 1, eout[i], gr + g.o_enc_b[i], eout[i], 1, eout[i], BT, false, split, st));
-            float* dn = i > 0 ? (d == dA[0] ? dA[1] : dA[0]) : ws + g.w_dD1;          // the last one is [BT, D]: d Y_o through the encoder
-            RULGNN_TRY(sgemm(d, eout[i], 1, prm + g.o_enc_w[i], 1, ein[i], dn, ein[i], BT, ein[i], eout[i], false, st));
-            d = dn;
-        }
-        // d Y_o = encoder path + the reconstruction term's own gradient
-        hipLaunchKernelGGL(sn_add_kernel, dim3(sn_grid((int64_t)BT * D)), dim3(SB), 0, st, d, (const float*)(ws + g.w_dD2), (int64_t)BT * D);
-        RULGNN_LAUNCH_OK();
-        const float* dcur = d;                        // d h_last [R, C_last]
+        float* const dseq[2] = {ws + g.w_dhs, ws + g.ae.w_dH};
+        RULGNN_TRY(lstm_head_backward(g.lh, henc, prm, ws, dpred, gr, dseq, split, st));
+        RULGNN_TRY(autoencoder_backward(g.ae, yo, prm, ws, gr, one, a->recon_weight, split, st));
+        const float* dcur = ws + g.ae.w_dD1;          // d Y_o = d h_last [R, C_last]
         for (int i = nl - 1; i >= 0; --i) {
             const int Ci = g.C[i], Co = g.C[i + 1];
             GdLaunch L;
@@ -609,11 +504,9 @@ int Gdagdl::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
             // attention.weight [2 Co] and attention.bias [1] are adjacent in the flat layout: one fixed-order sum of the partial rows
             RULGNN_TRY(rows_sum(ws + g.w_part, L.grid * L.waves, 2 * Co + 1, 2 * Co + 1, gr + g.o_aw[i], st));
             const float* hin = i > 0 ? ws + g.w_h[i - 1] : ws + g.w_mag;
-            const float* dz = ws + g.w_dz;
-            RULGNN_TRY(sgemm_splitk(dz, 1, Co, hin, 1, Ci, gr + g.o_w[i], Ci, Co, Ci, R, false, split, st));
-            RULGNN_TRY(sgemm_splitk(one, 0, 0, dz, 1, Co, gr + g.o_b[i], Co, 1, Co, R, false, split, st));
-            if (i == 0) break;                        // the magnitude carries no gradient
-            RULGNN_TRY(sgemm(dz, Co, 1, wop[i], 1, Ci, ws + g.w_dh, Ci, R, Ci, Co, false, st));      // (d h of layer i is consumed: one buffer serves every layer)
+            // (d h of layer i is consumed: one buffer serves every layer; the magnitude carries no gradient)
+            RULGNN_TRY(dense_backward(ws + g.w_dz, hin, wop[i], one, gr + g.o_w[i], gr + g.o_b[i], i > 0 ? DENSE_PLAIN : DENSE_NO_DATA, ws + g.w_dh, R, Co,
+                                      Ci, split, st));
             dcur = ws + g.w_dh;
         }
     }

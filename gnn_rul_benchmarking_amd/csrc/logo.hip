@@ -29,7 +29,7 @@
 
 #include "sgemm_mfma.hpp"
 #include "families_host.hpp"       // (stgcn_host.hpp: dropout_layer_key; stgcn_device.hpp: lowbias32)
-#include "stnet_device.hpp"        // the per-patch STFT magnitude (LOGO_bearing's front end)
+#include "stft_device.hpp"        // the per-patch STFT magnitude (LOGO_bearing's front end)
 
 namespace rulgnn {
 
@@ -49,7 +49,7 @@ constexpr float LG_DIAG = 1e8f;
 // with them in LDS the XJTU_SY geometry (N 17, T 32) would need 163 968 B of the 163 840.
 constexpr int LGB_MAXN = RULGNN_LOGOB_MAX_NODES, LGB_MAXF = RULGNN_LOGOB_MAX_INPUT_DIM;
 constexpr int LGB_RTH = (6 * LGB_MAXF * LGB_MAXF + LG_GB - 1) / LG_GB, LGB_RWN = (2 * LGB_MAXF * LGB_MAXF + LG_GB - 1) / LG_GB;      // 26, 9
-static_assert(SB == LG_GB, "stnet_device.hpp strides its loops by SB");
+static_assert(SB == LG_GB, "stft_device.hpp strides its loops by SB");
 
 struct LgLstm {
     int I, H;
@@ -74,7 +74,7 @@ struct LgGeom {
 // PR, PH [N][N + 1] (the three A_G products with their biases); per patch: E, CE [N][2p + 1] | A_T, Z, R, A^, C [N][N + 1] | red [2][256];
 // the backward adds G, dC, dAT, dZ, dR, dHh, SZ, SR, SH [N][N + 1], dH [N][3p + 1], dCE, dE [N][2p + 1] and the accumulators acc [CW].
 // LOGO_bearing (ns > 0): acc is [bn | b | the twelve fusion tensors] only (W_n and Theta: registers, see LGB_RTH), and the STFT's staging
-// area (stnet_device.hpp: padded patch [P + ns], cos, sin, window [ns]) follows.
+// area (stft_device.hpp: padded patch [P + ns], cos, sin, window [ns]) follows.
 struct LgLds {
     int X, mu, nr, AG, PZ, PR, PH, E, CE, AT, Z, R, AH, C, red, G, dC, dAT, dZ, dR, dHh, SZ, SR, SH, dH, dCE, dE, acc, stft, total;
 };

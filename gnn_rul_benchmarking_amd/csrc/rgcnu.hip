@@ -19,6 +19,7 @@
 #include "sgemm_mfma.hpp"
 #include "stgcn_device.hpp"
 #include "families_host.hpp"
+#include "seq_backend.hpp"         // lstm_uni_args
 
 namespace rulgnn {
 
@@ -1102,14 +1103,11 @@ int Rgcnu::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
     const float scale = drop.scale;
     const uint32_t key = dropout_layer_key(a->seed, a->step, 0);
     const float inv_gb = 1.0f / (float)(a->global_batch > 0 ? a->global_batch : g.B);
-    rulgnn_bilstm_shape ls{g.L, (int32_t)g.B, g.N, g.E};
-    rulgnn_bilstm_args la{};
-    la.x = ws + g.w_sp;
-    la.w_ih[0] = prm + g.o_wih; la.w_hh[0] = prm + g.o_whh; la.b_ih[0] = prm + g.o_bih; la.b_hh[0] = prm + g.o_bhh;
-    la.w_ih[1] = la.w_ih[0]; la.w_hh[1] = la.w_hh[0]; la.b_ih[1] = la.b_ih[0]; la.b_hh[1] = la.b_hh[0];      // unused (ndir = 1)
-    la.out = ws + g.w_hseq;
-    la.workspace = ws + g.w_lstm;
-    la.workspace_bytes = bilstm_workspace_bytes(&ls);
+    rulgnn_bilstm_shape ls;
+    rulgnn_bilstm_args la;
+    const int o_lstm[4] = {g.o_wih, g.o_whh, g.o_bih, g.o_bhh};
+    lstm_uni_args(&ls, &la, g.L, g.B, g.N, g.E, ws + g.w_sp, ws + g.w_hseq, ws + g.w_lstm, prm, o_lstm, a->grads, ws + g.w_dM, ws + g.w_dsp);
+    // (the backward's pointers ride along from here: bilstm_forward reads none of them, and a null `grads` leaves the gradient slots null)
     // the matrix-core SCL kernels give a graph to a wavefront: half the workgroups (and partial rows), twice the graphs in flight
     const bool scl_mx = g.N <= 32 && g.H == RG_MXH;
     const int scl_nt = g.N <= 16 ? 1 : 2;
@@ -1149,10 +1147,6 @@ int Rgcnu::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
         else
         hipLaunchKernelGGL(rg_fusion_bwd_kernel, dim3(blocks), dim3(RB), lds, st, g, a->x, a->dpred, prm, ws);
         if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
-        la.dout = ws + g.w_dM;
-        la.dx = ws + g.w_dsp;
-        la.dw_ih[0] = a->grads + g.o_wih; la.dw_hh[0] = a->grads + g.o_whh; la.db_ih[0] = a->grads + g.o_bih; la.db_hh[0] = a->grads + g.o_bhh;
-        la.dw_ih[1] = la.dw_ih[0]; la.dw_hh[1] = la.dw_hh[0]; la.db_ih[1] = la.db_ih[0]; la.db_hh[1] = la.db_hh[0];
         RULGNN_TRY(bilstm_backward(&ls, &la, st, 1));
         RULGNN_TRY(allow_dynamic_lds(rg_scl_bwd_kernel, lds_sclb));
         if (scl_mx) {

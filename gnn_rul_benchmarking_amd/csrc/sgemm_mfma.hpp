@@ -130,6 +130,18 @@ static inline size_t sgemm_splitk_need_floats(int M, int N, int K) {
     const int lb = sgemm_longk_blocks(M, N, K);
     return (size_t)(lb > 0 ? lb : sgemm_splitk_slices(M, N, K)) * M * N;
 }
+// The `partial` region of a caller that launches several split-K products: need(M, N, K) for every product it may launch, floats() is
+// the largest of them (at least `floor`).  A K beyond int is skipped: the geometry that registers it refuses such a shape elsewhere.
+struct SplitKScratch {
+    size_t v;
+    explicit SplitKScratch(size_t floor) : v(floor) {}
+    void need(int M, int N, int64_t K) {
+        if (K > 0x7fffffff) return;
+        const size_t n = sgemm_splitk_need_floats(M, N, (int)K);
+        if (n > v) v = n;
+    }
+    size_t floats() const { return v; }
+};
 // ... and for every output of at most M x Nmax values (the two paths do not grow monotonically with the output size)
 static inline size_t sgemm_splitk_bound_floats(int M, int Nmax, int K) {
     size_t v = sgemm_splitk_need_floats(M, Nmax, K);

@@ -391,13 +391,9 @@ void sc_ws_layout(const ScGeom& g, ScWs* w) {
     w->gp1 = c.take<float>(w->rows * nW);
     w->gp2 = c.take<float>(w->rows * nW);
     w->gp3 = c.take<float>(w->rows * (nW + g.N));
-    size_t mx = 1;
-    auto need = [&](int M, int Nn, int64_t K) {
-        const size_t v = sgemm_splitk_need_floats(M, Nn, (int)K);
-        if (v > mx) mx = v;
-    };
-    need(g.T, g.T, g.B * g.N); need(1, g.T, g.B * g.N); need(1, g.NT, g.B); need(1, 1, g.B);
-    w->split = c.take<float>(mx);
+    SplitKScratch sp(1);
+    sp.need(g.T, g.T, g.B * g.N); sp.need(1, g.T, g.B * g.N); sp.need(1, g.NT, g.B); sp.need(1, 1, g.B);
+    w->split = c.take<float>(sp.floats());
     w->total = c.total();
 }
 

@@ -17,7 +17,8 @@
 
 #include "sgemm_mfma.hpp"
 #include "families_host.hpp"
-#include "stnet_device.hpp"        // SB, the STFT magnitude, the back end's small kernels (shared with gdagdl.hip)
+#include "stft_device.hpp"         // SB, the STFT magnitude
+#include "seq_backend.hpp"         // the auto-encoder, the LSTM and the head (shared with gdagdl.hip and gatlstm.hip)
 
 namespace rulgnn {
 
@@ -31,13 +32,12 @@ struct SnGeom {
     int T, P, nseg, N, f, ncheb, A, E;
     int C[SN_MAX_CHEB + 1];                     // channel widths: f, Cheb_layers...
     int D;                                      // N * C[last]: auto-encoder width
-    // flat parameter offsets
-    int o_cw, o_cb, o_f[SN_MAX_CHEB], o_enc_w[4], o_enc_b[4], o_dec_w[4], o_dec_b[4], o_wih, o_whh, o_bih, o_bhh, o_lw, o_lb, pcount;
+    int o_cw, o_cb, o_f[SN_MAX_CHEB], pcount;   // flat parameter offsets of the front end; the back end's are the plans'
+    AutoEncoderPlan ae;                         // D -> A -> A -> A -> A and back
+    LstmHeadPlan lh;                            // one LSTM A -> E over the T patches, Linear(E * T, 1)
     // workspace offsets (floats)
     int64_t w_fal[SN_MAX_CHEB];          // 16-byte aligned copies of the ChebNet filters (their flat-buffer offsets are odd: the big-tile GEMM needs aligned operands)
-    int64_t w_mag, w_mask, w_terms[SN_MAX_CHEB], w_out[SN_MAX_CHEB], w_enc[4], w_dec[4], w_hseq, w_dpred, w_sq, w_rsq, w_dD1, w_dD2,
-        w_dA1, w_dA2, w_dterms, w_dc1, w_dc2, w_dhs, w_dH, w_one, w_split, w_lstm, total;
-    int rblocks;                                // workgroups of the reconstruction-error kernel (= partial sums)
+    int64_t w_mag, w_mask, w_terms[SN_MAX_CHEB], w_out[SN_MAX_CHEB], w_dterms, w_dc1, w_dc2, w_dhs, w_split, total;
 };
 
 int sn_geometry(const rulgnn_stnet_shape* s, SnGeom* g) {
@@ -64,18 +64,12 @@ int sn_geometry(const rulgnn_stnet_shape* s, SnGeom* g) {
     g->D = g->N * g->C[g->ncheb];
     if (g->R * 3 * 4096 > ((int64_t)1 << 40)) return RULGNN_EUNSUPPORTED;
     int o = 0;
+    int64_t w = 0;
+    SplitKScratch sp(1024);
     auto tk = [&](int n) { const int r = o; o += n; return r; };
+    auto wk = [&](int64_t n) { const int64_t r = w; w += (n + 63) & ~(int64_t)63; return r; };
     g->o_cw = tk(2); g->o_cb = tk(1);
     for (int i = 0; i < g->ncheb; ++i) g->o_f[i] = tk(3 * g->C[i] * g->C[i + 1]);
-    const int A = g->A, D = g->D;
-    const int ein[4] = {D, A, A, A}, eout[4] = {A, A, A, A}, din[4] = {A, A, A, A}, dout[4] = {A, A, A, D};
-    for (int i = 0; i < 4; ++i) { g->o_enc_w[i] = tk(eout[i] * ein[i]); g->o_enc_b[i] = tk(eout[i]); }
-    for (int i = 0; i < 4; ++i) { g->o_dec_w[i] = tk(dout[i] * din[i]); g->o_dec_b[i] = tk(dout[i]); }
-    g->o_wih = tk(4 * g->E * A); g->o_whh = tk(4 * g->E * g->E); g->o_bih = tk(4 * g->E); g->o_bhh = tk(4 * g->E);
-    g->o_lw = tk(g->E * g->T); g->o_lb = tk(1);
-    g->pcount = o;
-    int64_t w = 0;
-    auto wk = [&](int64_t n) { const int64_t r = w; w += (n + 63) & ~(int64_t)63; return r; };
     const int64_t R = g->R, BT = g->BT;
     g->w_mag = wk(R * g->f); g->w_mask = wk(R);
     int cmax = 0;
@@ -85,34 +79,18 @@ int sn_geometry(const rulgnn_stnet_shape* s, SnGeom* g) {
         if (g->C[i] > cmax) cmax = g->C[i];
         if (g->C[i + 1] > cmax) cmax = g->C[i + 1];
     }
-    for (int i = 0; i < 4; ++i) g->w_enc[i] = wk(BT * A);
-    for (int i = 0; i < 3; ++i) g->w_dec[i] = wk(BT * A);
-    g->w_dec[3] = wk(BT * D);
-    g->w_hseq = wk(BT * g->E);
-    g->w_dpred = wk(g->B); g->w_sq = wk(g->B);
-    g->rblocks = 1024;
-    g->w_rsq = wk(g->rblocks);
-    g->w_dD1 = wk(BT * D); g->w_dD2 = wk(BT * D);
-    g->w_dA1 = wk(BT * A); g->w_dA2 = wk(BT * A);
+    const int A = g->A, D = g->D;
+    g->ae.BT = BT;
+    for (int i = 0; i < 4; ++i) { g->ae.ein[i] = i ? A : D; g->ae.eout[i] = A; g->ae.din[i] = A; g->ae.dout[i] = i < 3 ? A : D; }
+    autoencoder_layout(&g->ae, &o, &w, &sp);
+    g->lh.B = g->B; g->lh.T = g->T; g->lh.nk = 1; g->lh.H[0] = A; g->lh.H[1] = g->E;
+    RULGNN_TRY(lstm_head_layout(&g->lh, &o, &w, &sp));
+    g->pcount = o;
     g->w_dterms = wk(R * 3 * cmax); g->w_dc1 = wk(R * cmax); g->w_dc2 = wk(R * cmax);
-    g->w_dhs = wk(BT * g->E); g->w_dH = wk(BT * A);
-    g->w_one = wk(64);
+    g->w_dhs = wk(BT * g->E);
     for (int i = 0; i < g->ncheb; ++i) g->w_fal[i] = wk((int64_t)3 * g->C[i] * g->C[i + 1]);
-    int64_t sp = 1024;
-    auto need = [&](int M, int Nn, int64_t K) {
-        if (K > 0x7fffffff) return;
-        const int64_t v = (int64_t)sgemm_splitk_need_floats(M, Nn, (int)K);
-        if (v > sp) sp = v;
-    };
-    for (int i = 0; i < g->ncheb; ++i) need(3 * g->C[i], g->C[i + 1], R);
-    for (int i = 0; i < 4; ++i) { need(eout[i], ein[i], BT); need(1, eout[i], BT); need(dout[i], din[i], BT); need(1, dout[i], BT); }
-    need(1, g->E * g->T, g->B);
-    for (int i = 0; i < 4; ++i) { need((int)BT, eout[i], ein[i]); need((int)BT, din[i], dout[i]); }      // activations over a long reduction: sn_gemm_rows
-    g->w_split = wk(sp);
-    rulgnn_bilstm_shape ls{g->T, (int32_t)(g->B > 0 ? g->B : 1), A, g->E};
-    const size_t lb = bilstm_workspace_bytes(&ls);
-    if (lb == 0) return RULGNN_EUNSUPPORTED;
-    g->w_lstm = wk((int64_t)(lb / sizeof(float)) + 64);
+    for (int i = 0; i < g->ncheb; ++i) sp.need(3 * g->C[i], g->C[i + 1], R);
+    g->w_split = wk((int64_t)sp.floats());
     g->total = w;
     return RULGNN_OK;
 }
@@ -185,8 +163,6 @@ __global__ __launch_bounds__(SB) void sn_terms_bwd_kernel(SnGeom g, int C, const
     }
 }
 
-// (bias + activation, ReLU backward, add, the reconstruction error and its gradients, the head: stnet_device.hpp)
-
 }  // namespace
 
 // RULGNN_OK, or the code every entry returns for a refused shape: unsupported for anything sn_geometry refuses, a negative batch included.
@@ -215,47 +191,27 @@ int Stnet::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
     const float* prm = a->params;
     const int64_t gb = a->global_batch > 0 ? a->global_batch : g.B;
     const float inv_gb = 1.0f / (float)gb;
-    const int A = g.A, D = g.D, E = g.E, nc = g.ncheb;
-    const int R = (int)g.R, BT = (int)g.BT;
-    const int ein[4] = {D, A, A, A}, eout[4] = {A, A, A, A}, din[4] = {A, A, A, A}, dout[4] = {A, A, A, D};
-    const float rscale = 1.0f / ((float)gb * (float)g.T * (float)D);          // 1 / elements of the global batch's Y_o
+    const int nc = g.ncheb, R = (int)g.R;
+    const float rscale = 1.0f / ((float)gb * (float)g.T * (float)g.D);          // 1 / elements of the global batch's Y_o
     const float* mask = ws + g.w_mask;
     float* split = ws + g.w_split;
-    rulgnn_bilstm_shape ls{g.T, (int32_t)g.B, A, E};
-    rulgnn_bilstm_args la{};
-    la.x = ws + g.w_enc[3];
-    la.w_ih[0] = prm + g.o_wih; la.w_hh[0] = prm + g.o_whh; la.b_ih[0] = prm + g.o_bih; la.b_hh[0] = prm + g.o_bhh;
-    la.w_ih[1] = la.w_ih[0]; la.w_hh[1] = la.w_hh[0]; la.b_ih[1] = la.b_ih[0]; la.b_hh[1] = la.b_hh[0];
-    la.out = ws + g.w_hseq;
-    la.workspace = ws + g.w_lstm;
-    la.workspace_bytes = bilstm_workspace_bytes(&ls);
+    float* one = ws + g.lh.w_one;                 // [0] = 1 (backward), [1] the reconstruction term, [2] the MSE, [3] = 0
+    const float* yo = ws + g.w_out[nc - 1];       // Y_o as [BT, D] rows
+    const float* henc = ws + g.ae.w_enc[3];       // the encoder's output: the LSTM's input
     const unsigned ggrid = (unsigned)(g.G < 4096 ? g.G : 4096);
     (void)hipGetLastError();
-    // [BT x K] x [K x 50] with K = 900: 32 output tiles, each walking all of K alone (45 us); split over k it is a 6-us product and a
-    // 6-us fixed-order sum (the scratch need of these shapes is registered in sn_geometry)
-    auto gemm_rows = [&](const float* Am, int64_t sAm, int64_t sAk, const float* Bm, int64_t sBn, int64_t sBk, float* Cm, int64_t ldc, int M, int N,
-                         int K) -> int {
-        if (K >= 512 && (int64_t)((M + 63) / 64) * ((N + 63) / 64) < 128) return sgemm_splitk(Am, sAm, sAk, Bm, sBn, sBk, Cm, ldc, M, N, K, false, split, st);
-        return sgemm(Am, sAm, sAk, Bm, sBn, sBk, Cm, ldc, M, N, K, false, st);
-    };
-    // The filters as GEMM operands: the flat parameter buffer puts them behind three scalars, 12 bytes off a 16-byte boundary, and the
-    // large-tile GEMM (sgemm.hip: 16-byte vector loads) falls back to the 64 x 64 fp32 tiles for a misaligned operand -- 123 instead of
-    // 98 us for the [18 000 x 900] x [900 x 200] product, 98 instead of 80 us for its transpose.  A misaligned filter is copied into the
-    // workspace once per call (1 MB at the reference's widths, ~3 us a copy).
+    // The filters as GEMM operands: the flat parameter buffer puts them behind three scalars, 12 bytes off a 16-byte boundary
+    // (seq_backend.hpp: aligned_operand; 1 MB at the reference's widths, ~3 us a copy).
     const float* fop[SN_MAX_CHEB];
     for (int i = 0; i < nc; ++i) {
-        fop[i] = prm + g.o_f[i];
         const bool used_big = i > 0 || (mode & 1);                  // layer 0's transpose product is never formed (the input carries no gradient)
-        if ((reinterpret_cast<uintptr_t>(fop[i]) & 15) && used_big) {
-            if (hipMemcpyAsync(ws + g.w_fal[i], fop[i], sizeof(float) * 3 * g.C[i] * g.C[i + 1], hipMemcpyDeviceToDevice, st) != hipSuccess)
-                return RULGNN_EHIP;
-            fop[i] = ws + g.w_fal[i];
-        }
+        fop[i] = used_big ? aligned_operand(prm + g.o_f[i], (size_t)3 * g.C[i] * g.C[i + 1], ws + g.w_fal[i], st) : prm + g.o_f[i];
+        if (!fop[i]) return RULGNN_EHIP;
     }
     if (mode & 1) {
         const size_t lds = sizeof(float) * (stft_lds_floats(g.P, g.nseg) + (size_t)g.N * g.f);
         if (lds > 48 * 1024) return RULGNN_EUNSUPPORTED;
-        RULGNN_TRY(fill_f32(ws + g.w_one + 3, 1, 0.0f, st));
+        RULGNN_TRY(fill_f32(one + 3, 1, 0.0f, st));
         hipLaunchKernelGGL(sn_stft_kernel, dim3(ggrid), dim3(SB), lds, st, g, a->x, prm, ws);
         RULGNN_LAUNCH_OK();
         const float* cur = ws + g.w_mag;
@@ -266,87 +222,24 @@ int Stnet::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
                         false, st));
             cur = ws + g.w_out[i];
         }
-        const float* h = cur;                         // Y_o as [BT, D] rows
-        for (int i = 0; i < 4; ++i) {
-            RULGNN_TRY(gemm_rows(h, ein[i], 1, prm + g.o_enc_w[i], ein[i], 1, ws + g.w_enc[i], eout[i], BT, eout[i], ein[i]));
-            hipLaunchKernelGGL(sn_bias_act_kernel, dim3(sn_grid((int64_t)BT * eout[i])), dim3(SB), 0, st, ws + g.w_enc[i], prm + g.o_enc_b[i],
-                               (int64_t)BT, eout[i], i < 3 ? 1 : 0);
-            h = ws + g.w_enc[i];
-        }
-        for (int i = 0; i < 4; ++i) {
-            RULGNN_TRY(sgemm(h, din[i], 1, prm + g.o_dec_w[i], din[i], 1, ws + g.w_dec[i], dout[i], BT, dout[i], din[i], false, st));
-            hipLaunchKernelGGL(sn_bias_act_kernel, dim3(sn_grid((int64_t)BT * dout[i])), dim3(SB), 0, st, ws + g.w_dec[i], prm + g.o_dec_b[i],
-                               (int64_t)BT, dout[i], i < 3 ? 1 : 0);
-            h = ws + g.w_dec[i];
-        }
-        RULGNN_LAUNCH_OK();
-        // reconstruction error (and, when a backward follows, its gradients w.r.t. both of its arguments)
-        hipLaunchKernelGGL(sn_recon_kernel, dim3(g.rblocks), dim3(SB), 0, st, (const float*)cur, (const float*)(ws + g.w_dec[3]), (int64_t)BT * D,
-                           rscale, ws + g.w_dD1, ws + g.w_dD2, ws + g.w_rsq);
-        (void)block_sum((const float*)(ws + g.w_rsq), (int64_t)g.rblocks, ws + g.w_one + 1, st);
-        RULGNN_LAUNCH_OK();
-        RULGNN_TRY(bilstm_forward(&ls, &la, st, 1));
-        hipLaunchKernelGGL(sn_head_kernel<SnGeom>, dim3((unsigned)(g.B < 1024 ? g.B : 1024)), dim3(SB), 0, st, g, (const float*)(ws + g.w_hseq), prm, a->y,
-                           a->pred, ws, inv_gb);
-        if (a->recon) hipLaunchKernelGGL(sn_loss_kernel, dim3(1), dim3(1), 0, st, (const float*)(ws + g.w_one + 1), (const float*)(ws + g.w_one + 3),
-                                         a->recon);          // w_one + 3 holds 0
+        RULGNN_TRY(autoencoder_forward(g.ae, yo, prm, ws, rscale, one + 1, split, st));
+        RULGNN_TRY(lstm_head_forward(g.lh, henc, prm, ws, a->y, a->pred, inv_gb, st));
+        if (a->recon) RULGNN_TRY(sum_pair(one + 1, one + 3, a->recon, st));
         if (a->y && a->loss) {
-            (void)block_sum((const float*)(ws + g.w_sq), g.B, ws + g.w_one + 2, st);
-            hipLaunchKernelGGL(sn_loss_kernel, dim3(1), dim3(1), 0, st, (const float*)(ws + g.w_one + 1), (const float*)(ws + g.w_one + 2), a->loss);
+            RULGNN_TRY(block_sum((const float*)(ws + g.lh.w_sq), g.B, one + 2, st));
+            RULGNN_TRY(sum_pair(one + 1, one + 2, a->loss, st));
         }
-        RULGNN_LAUNCH_OK();
     }
     if (mode & 2) {
         if (!a->grads) return RULGNN_EINVAL;
         float* gr = a->grads;
-        const float* dpred = a->dpred ? a->dpred : ws + g.w_dpred;
-        float* one = ws + g.w_one;
+        const float* dpred = a->dpred ? a->dpred : ws + g.lh.w_dpred;
         RULGNN_TRY(fill_f32(one, 1, 1.0f, st));
         RULGNN_TRY(fill_f32(gr + g.o_cw, 3, 0.0f, st));          // the 1x1 convolution has no gradient
-        // head
-        RULGNN_TRY(sgemm_splitk(dpred, 0, 1, ws + g.w_hseq, 1, E * g.T, gr + g.o_lw, E * g.T, 1, E * g.T, (int)g.B, false, split, st));
-        RULGNN_TRY(sgemm_splitk(dpred, 0, 1, one, 0, 0, gr + g.o_lb, 1, 1, 1, (int)g.B, false, split, st));
-        hipLaunchKernelGGL(sn_head_bwd_kernel<SnGeom>, dim3(sn_grid(g.B * E * g.T)), dim3(SB), 0, st, g, dpred, prm, ws + g.w_dhs);
-        RULGNN_LAUNCH_OK();
-        la.dout = ws + g.w_dhs;
-        la.dx = ws + g.w_dH;
-        la.dw_ih[0] = gr + g.o_wih; la.dw_hh[0] = gr + g.o_whh; la.db_ih[0] = gr + g.o_bih; la.db_hh[0] = gr + g.o_bhh;
-        la.dw_ih[1] = la.dw_ih[0]; la.dw_hh[1] = la.dw_hh[0]; la.db_ih[1] = la.db_ih[0]; la.db_hh[1] = la.db_hh[0];
-        RULGNN_TRY(bilstm_backward(&ls, &la, st, 1));
-        // decoder, from d Yp = w_dD1 (the reconstruction scale of a data-parallel shard is the global one: recon is in the loss with weight 1)
-        if (a->recon_weight)
-            hipLaunchKernelGGL(sn_scale2_kernel, dim3(sn_grid((int64_t)BT * D)), dim3(SB), 0, st, ws + g.w_dD1, ws + g.w_dD2, (int64_t)BT * D,
-                               a->recon_weight);
-        float* d = ws + g.w_dD1;
-        float* dA[2] = {ws + g.w_dA1, ws + g.w_dA2};
-        for (int i = 3; i >= 0; --i) {
-            const float* hin = i > 0 ? ws + g.w_dec[i - 1] : ws + g.w_enc[3];
-            if (i < 3) hipLaunchKernelGGL(sn_relu_bwd_kernel, dim3(sn_grid((int64_t)BT * dout[i])), dim3(SB), 0, st, d, (const float*)(ws + g.w_dec[i]),
-                                          (int64_t)BT * dout[i]);
-            RULGNN_TRY(sgemm_splitk(d, 1, dout[i], hin, 1, din[i], gr + g.o_dec_w[i], din[i], dout[i], din[i], BT, false, split, st));
-            RULGNN_TRY(sgemm_splitk(one, 0, 0, d, 1, dout[i], gr + g.o_dec_b[i], dout[i], 1, dout[i], BT, false, split, st));
-            float* dn = dA[i & 1];
-            RULGNN_TRY(gemm_rows(d, dout[i], 1, prm + g.o_dec_w[i], 1, din[i], dn, din[i], BT, din[i], dout[i]));
-            d = dn;
-        }
-        // d H = decoder path + LSTM path
-        hipLaunchKernelGGL(sn_add_kernel, dim3(sn_grid((int64_t)BT * A)), dim3(SB), 0, st, d, (const float*)(ws + g.w_dH), (int64_t)BT * A);
-        RULGNN_LAUNCH_OK();
-        const float* yo = ws + g.w_out[nc - 1];
-        for (int i = 3; i >= 0; --i) {
-            const float* hin = i > 0 ? ws + g.w_enc[i - 1] : yo;
-            if (i < 3) hipLaunchKernelGGL(sn_relu_bwd_kernel, dim3(sn_grid((int64_t)BT * eout[i])), dim3(SB), 0, st, d, (const float*)(ws + g.w_enc[i]),
-                                          (int64_t)BT * eout[i]);
-            RULGNN_TRY(sgemm_splitk(d, 1, eout[i], hin, 1, ein[i], gr + g.o_enc_w[i], ein[i], eout[i], ein[i], BT, false, split, st));
-            RULGNN_TRY(sgemm_splitk(one, 0, 0, d, 1, eout[i], gr + g.o_enc_b[i], eout[i], 1, eout[i], BT, false, split, st));
-            float* dn = i > 0 ? (d == dA[0] ? dA[1] : dA[0]) : ws + g.w_dD1;          // the last one is [BT, D]: d Y_o through the encoder
-            RULGNN_TRY(sgemm(d, eout[i], 1, prm + g.o_enc_w[i], 1, ein[i], dn, ein[i], BT, ein[i], eout[i], false, st));
-            d = dn;
-        }
-        // d Y_o = encoder path + the reconstruction term's own gradient
-        hipLaunchKernelGGL(sn_add_kernel, dim3(sn_grid((int64_t)BT * D)), dim3(SB), 0, st, d, (const float*)(ws + g.w_dD2), (int64_t)BT * D);
-        RULGNN_LAUNCH_OK();
-        const float* dcur = d;                        // [R, C_last]
+        float* const dseq[2] = {ws + g.w_dhs, ws + g.ae.w_dH};
+        RULGNN_TRY(lstm_head_backward(g.lh, henc, prm, ws, dpred, gr, dseq, split, st));
+        RULGNN_TRY(autoencoder_backward(g.ae, yo, prm, ws, gr, one, a->recon_weight, split, st));
+        const float* dcur = ws + g.ae.w_dD1;          // d Y_o: [R, C_last]
         float* dc[2] = {ws + g.w_dc1, ws + g.w_dc2};
         for (int i = nc - 1; i >= 0; --i) {
             const int Ci = g.C[i], Co = g.C[i + 1];

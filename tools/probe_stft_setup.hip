@@ -1,12 +1,12 @@
 // Probe for profiles/r28_logo_bearing.md: the STFT magnitude at LOGO_bearing's two geometries (batch 100 and 1024) as (a) a separate pass,
 // one workgroup per (sample, patch), magnitude to HBM, and (b) the setup of lg_graph_fwd<true> / lg_graph_bwd<true> alone, one workgroup per
-// sample walking its T patches into the LDS window.  Both on stnet_device.hpp's functions; one JSON line per case.
+// sample walking its T patches into the LDS window.  Both on stft_device.hpp's functions; one JSON line per case.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/probe_stft_setup.hip -o tools/probe_stft_setup.bin && tools/probe_stft_setup.bin
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
-#include "../gnn_rul_benchmarking_amd/csrc/stnet_device.hpp"
+#include "../gnn_rul_benchmarking_amd/csrc/stft_device.hpp"
 using namespace rulgnn;
 #define CK(e) do { hipError_t r_ = (e); if (r_ != hipSuccess) { printf("HIP error %s at line %d\n", hipGetErrorString(r_), __LINE__); return 1; } } while (0)
 
