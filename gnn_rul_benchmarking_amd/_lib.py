@@ -153,6 +153,12 @@ class LogoArgs(C.Structure):
                 ("dropout_p", C.c_float), ("seed", C.c_uint64), ("step", C.c_uint64), ("training", C.c_int32)]
 
 
+class HcpbShape(C.Structure):
+    _fields_ = [("batch", C.c_int64), ("patch_size", C.c_int32), ("num_patch", C.c_int32), ("input_dim", C.c_int32),
+                ("hidden_dim", C.c_int32), ("embedding_dim", C.c_int32), ("num_nodes", C.c_int32), ("nperseg", C.c_int32),
+                ("encoder_conv_kernel", C.c_int32), ("num_nodes_out", C.c_int32)]
+
+
 class LogobShape(C.Structure):
     _fields_ = [("batch", C.c_int64), ("patch_size", C.c_int32), ("num_patch", C.c_int32), ("input_dim", C.c_int32),
                 ("num_nodes", C.c_int32), ("nperseg", C.c_int32), ("hidden_dim", C.c_int32)]
@@ -294,6 +300,7 @@ _SIGNATURES = {
     **_step_family("rgcnu", RgcnuShape, RgcnuArgs),
     **_step_family("grucm", GrucmShape, GrucmArgs),
     **_step_family("hiercorrpool", HiercorrpoolShape, HiercorrpoolArgs, tap_offset=True, bn_state_count=True),
+    **_step_family("hcpb", HcpbShape, HiercorrpoolArgs, tap_offset=True, bn_state_count=True),
     **_step_family("logo", LogoShape, LogoArgs, tap_offset=True),
     **_step_family("logob", LogobShape, LogoArgs, tap_offset=True),
     **_step_family("dvgtformer", DvgtformerShape, DvgtformerArgs, tap_offset=True),
@@ -409,6 +416,8 @@ STRUCTS = (StgcnShape, StgcnTrainArgs, AdamArgs, StmsgcnShape, StmsgcnArgs, Astg
 STRUCTS_AT = {38: GatlstmShape, 39: GatlstmArgs}
 # (STRUCTS_AT is GAT_LSTM's pair and tested as exactly that; families after it register here)
 STRUCTS_LATER = {41: LogobShape}
+# (STRUCTS_LATER is tested as exactly that too; 42 is unassigned)
+STRUCTS_HCPB = {43: HcpbShape}
 
 _lib = None
 
@@ -440,7 +449,7 @@ def load() -> C.CDLL:
         fn = getattr(lib, name)          # AttributeError if the .so is stale: loud by design
         fn.restype = res
         fn.argtypes = args
-    for which, mirror in list(enumerate(STRUCTS)) + sorted({**STRUCTS_AT, **STRUCTS_LATER}.items()):       # a stale .so (or a stale binding) would read past the end of a shorter struct
+    for which, mirror in list(enumerate(STRUCTS)) + sorted({**STRUCTS_AT, **STRUCTS_LATER, **STRUCTS_HCPB}.items()):       # a stale .so (or a stale binding) would read past the end of a shorter struct
         if lib.rulgnn_struct_size(which) != C.sizeof(mirror):
             raise RuntimeError(f"{LIB_PATH}: sizeof(struct #{which}) is {lib.rulgnn_struct_size(which)} in the library, {C.sizeof(mirror)} in "
                                f"this binding ({mirror.__name__}): rebuild with `python -m gnn_rul_benchmarking_amd.build --force`")

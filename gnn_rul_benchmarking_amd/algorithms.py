@@ -3,7 +3,7 @@ algorithms/algorithms.py:29-48 does it (lookup by name in this module's globals,
 ``NotImplementedError("Algorithm not found: ...")`` otherwise).
 
 The ST_GCN (reference algorithms/algorithms.py:465-490), STMSGCN (:546-571), ASTGCNN (:139-163), FC_STGNN (:51-76), HAGCN (:222-248),
-ST_Conv (:195-220), GRU_CM (:355-380), AGCN_TF (:574-599), HierCorrPool (:79-104), LOGO (:107-136), DVGTformer (:326-351), GDAGDL (:519-544), GAT_LSTM (:492-517) and LOGO_bearing (:601-629) wrappers are implemented:
+ST_Conv (:195-220), GRU_CM (:355-380), AGCN_TF (:574-599), HierCorrPool (:79-104), LOGO (:107-136), DVGTformer (:326-351), GDAGDL (:519-544), GAT_LSTM (:492-517), LOGO_bearing (:601-629) and HierCorrPool_bearing (:633-658) wrappers are implemented:
 the hot paths this package accelerates.  The classes keep the reference contract -- constructor
 ``(configs, hparams, device)``, attributes ``model`` / ``optimizer`` / ``hparams`` / ``mse``,
 ``update(X, y, epoch) -> {'loss': float}`` -- so the reference's trainer can drive it unchanged."""
@@ -31,6 +31,7 @@ from .agcntf import AGCN_TF_model
 from .hiercorrpool import HierCorrPool_model
 from .logo import LOGO_model
 from .logo_bearing import LOGO_bearing_model
+from .hiercorrpool_bearing import HierCorrPool_bearing_model
 from .dvgtformer import DVGTformer_model
 from .gdagdl import GDAGDL_model
 from .gatlstm import GAT_LSTM_model
@@ -301,6 +302,12 @@ class HierCorrPool(_FusedAlgorithm):
                            "single-process): run independent replicas")
 
 
+class HierCorrPool_bearing(HierCorrPool):
+    """HierCorrPool_bearing training wrapper (reference algorithms.py:633-658; HierCorrPool's kernels behind the STFT packing kernel of
+    csrc/hiercorrpool.hip): plain MSE + Adam, no scheduler, as HierCorrPool.  Data parallelism is refused as there."""
+    model_class = HierCorrPool_bearing_model
+
+
 class LOGO(_FusedAlgorithm):
     """LOGO training wrapper (reference algorithms.py:107-136; graph stage of csrc/logo.hip, the three Bi-LSTM layers of csrc/bilstm.hip):
     ``loss = MSE + theta * L_GL`` with ``theta = hparams['theta']``; the returned ``'loss'`` is that sum.  The reference constructs a
@@ -403,4 +410,6 @@ class GAT_LSTM(_FusedAlgorithm):
 
 
 # ("LOGO_bearing": the class above is complete, but tests/test_logo_cpu.py holds the registry to refusing the name; construct it directly)
-_NOT_ALGORITHMS = {"LOGO_bearing", "Algorithm", "GAT_LSTM_model", "GDAGDL_model", "DVGTformer_model","GRU_CM_model", "FusedAdam", "RGCNU_model", "STNet_model", "SAGCN_model", "AGCN_TF_model", "HierCorrPool_model", "LOGO_model", "LOGO_bearing_model", "STAGNN_model", "ST_GCN_model", "STMSGCN_model", "ASTGCNN_model", "FC_STGNN_RUL", "HAGCN_model", "ST_Conv_model", "STGNN_model", "get_algorithm_class", "torch", "nn", "annotations", "math", "_lib", "deferred_weight_gradients"}
+# ("HierCorrPool_bearing": likewise complete; tests/test_hiercorrpool_cpu.py and tests/test_logo_bearing_cpu.py hold the registry to
+# refusing the name; construct it directly)
+_NOT_ALGORITHMS = {"HierCorrPool_bearing", "HierCorrPool_bearing_model", "LOGO_bearing", "Algorithm", "GAT_LSTM_model", "GDAGDL_model", "DVGTformer_model","GRU_CM_model", "FusedAdam", "RGCNU_model", "STNet_model", "SAGCN_model", "AGCN_TF_model", "HierCorrPool_model", "LOGO_model", "LOGO_bearing_model", "STAGNN_model", "ST_GCN_model", "STMSGCN_model", "ASTGCNN_model", "FC_STGNN_RUL", "HAGCN_model", "ST_Conv_model", "STGNN_model", "get_algorithm_class", "torch", "nn", "annotations", "math", "_lib", "deferred_weight_gradients"}

@@ -156,6 +156,16 @@ struct Hiercorrpool : StepFamily<rulgnn_hiercorrpool_shape, rulgnn_hiercorrpool_
     static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
     static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
 };
+// (the args struct is HierCorrPool's; x is the raw window [batch][num_patch * patch_size])
+struct Hcpb : StepFamily<rulgnn_hcpb_shape, rulgnn_hiercorrpool_args> {
+    static int shape_status(const Shape* s);
+    static int64_t param_count(const Shape* s);
+    static int64_t bn_state_count(const Shape* s);
+    static size_t workspace_bytes(const Shape* s);
+    static int64_t tap_offset(const Shape* s, int which);
+    static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
+    static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
+};
 struct Logo : StepFamily<rulgnn_logo_shape, rulgnn_logo_args> {
     static int shape_status(const Shape* s);
     static int64_t param_count(const Shape* s);

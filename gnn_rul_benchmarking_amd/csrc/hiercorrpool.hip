@@ -19,12 +19,19 @@
 //
 // Graph stage: one workgroup per sample, everything between X and A' X' in LDS (hcp_graph_fwd / hcp_graph_bwd below); products with a
 // d-long k run on v_mfma_f32_16x16x4_f32 (hc_mm).  No floating-point atomics anywhere: two runs give the same bits.
+//
+// HierCorrPool_bearing (models/HierCorrPool_bearing/Model.py:6-67; HierCorrPool_bearing.update, algorithms/algorithms.py:633-658) is the
+// same chain behind an STFT front end: x is the raw window [bs, P p], the nodes are the N = nperseg / 2 + 1
+// frequency bins of a patch's spectrogram and a node's features its f = 1 + p / nperseg frames, so block 1 reads C0 = N f channels.
+// hcpb_stft_input_kernel below takes hc_pack_input_kernel's place and nothing else changes: one geometry function (hc_geometry with a
+// front-end description, HcFront) and one host chain (hc_run) serve both families.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "bn_cells.hpp"
 #include "sgemm_mfma.hpp"
 #include "families_host.hpp"       // (stgcn_host.hpp: dropout_layer_key; stgcn_device.hpp: lowbias32)
+#include "stft_device.hpp"         // the per-patch STFT magnitude (HierCorrPool_bearing's front end)
 
 namespace rulgnn {
 
@@ -33,6 +40,7 @@ namespace {
 constexpr int HC_GB = 256, HC_WAVES = HC_GB / 64;
 constexpr int HC_TAPS = 8, HC_PAD = 4;
 constexpr int HC_MAXN = 32, HC_MAXM = 16, HC_MAXD = 512, HC_MAXP = 64, HC_MAXC3 = 1024;
+constexpr int HCPB_GRID = 2048;               // workgroups of the STFT packing kernel: eight of 256 threads on each of 256 compute units
 constexpr int HC_SLICES = 64;                 // row slices of a BatchNorm reduction (fixed: it fixes the summation order)
 constexpr float HC_SLOPE = 0.01f;             // F.leaky_relu's default
 constexpr float HC_EPS = 1e-5f, HC_MOMENTUM = 0.1f;
@@ -45,9 +53,18 @@ struct HcBlock {
     int64_t w_in, w_z, w_dz, w_din, w_wp, w_wt, w_dwp, w_coef, w_bcoef, w_part;
 };
 
+// What stands in front of block 1, and the limits that go with it.  HierCorrPool: the window [N][P p] itself, w = p values per node and
+// step.  HierCorrPool_bearing: |STFT| of the raw window [P p] at nperseg ns, w = f frames per frequency bin and patch.
+struct HcFront {
+    int ns;                                   // nperseg; 0: no STFT
+    int w, C0;                                // per-node width (p or f), block 1's channels N w
+    int max_nodes, max_patch, max_patch_size, max_d;
+};
+
 struct HcGeom {
     int64_t B;
     int p, P, h, e, N, K, M, d, d3, e3, Lq;   // Lq = L'
+    int ns, w;                                // the front end: nperseg (0: none) and the per-node width, C0 = N w = blk[0].Cin
     HcBlock blk[3];
     int o_tw, o_tb, o_wd, o_bd, o_wm, o_bm, o_f0w, o_f0b, o_f1w, o_f1b, pcount, bncount;
     int CW;                                   // floats of one sample's [d Wd | d bd | d Wm] contribution
@@ -88,23 +105,23 @@ __host__ __device__ inline HcGraphLds hc_graph_lds(int N, int M, int d, bool bwd
     return l;
 }
 
-int hc_geometry(const rulgnn_hiercorrpool_shape* s, HcGeom* g) {
-    if (!s) return RULGNN_EINVAL;
+int hc_geometry(const rulgnn_hiercorrpool_shape* s, const HcFront& fe, HcGeom* g) {
     if (s->batch < 0 || s->patch_size < 0 || s->num_patch < 0 || s->hidden_dim < 0 || s->embedding_dim < 0 || s->num_nodes < 0 ||
         s->encoder_conv_kernel < 0 || s->num_nodes_out < 0)
         return RULGNN_EINVAL;
-    if (s->num_nodes < 2 || s->num_nodes > HC_MAXN || s->num_nodes_out < 1 || s->num_nodes_out > HC_MAXM || s->num_patch < 2 ||
-        s->num_patch > HC_MAXP || s->patch_size < 1 || s->patch_size > HC_MAXP || s->hidden_dim < 1 || s->embedding_dim < 1 ||
+    if (s->num_nodes < 2 || s->num_nodes > fe.max_nodes || s->num_nodes_out < 1 || s->num_nodes_out > HC_MAXM || s->num_patch < 2 ||
+        s->num_patch > fe.max_patch || s->patch_size < 1 || s->patch_size > fe.max_patch_size || s->hidden_dim < 1 || s->embedding_dim < 1 ||
         s->encoder_conv_kernel < 1)
         return RULGNN_EUNSUPPORTED;
+    g->ns = fe.ns; g->w = fe.w;
     g->B = s->batch; g->p = s->patch_size; g->P = s->num_patch; g->h = s->hidden_dim; g->e = s->embedding_dim; g->N = s->num_nodes;
     g->K = s->encoder_conv_kernel; g->M = s->num_nodes_out;
     const int64_t d64 = (int64_t)g->K * g->e, c364 = (int64_t)4 * g->h * g->N;
-    if (d64 > HC_MAXD || c364 > HC_MAXC3) return RULGNN_EUNSUPPORTED;
+    if (d64 > fe.max_d || c364 > HC_MAXC3) return RULGNN_EUNSUPPORTED;
     g->d = (int)d64; g->d3 = 3 * g->d; g->e3 = 3 * g->e;
     const int N = g->N, M = g->M, d = g->d;
     const int64_t B = g->B;
-    int C = N * g->p, L = g->P, o = 0, obn = 0;
+    int C = fe.C0, L = g->P, o = 0, obn = 0;
     for (int l = 0; l < 3; ++l) {
         HcBlock& k = g->blk[l];
         k.Cin = C; k.Cout = (g->h * N) << l; k.Lin = L; k.Lc = L + 1; k.Lp = k.Lc / 2 + 1;
@@ -180,6 +197,30 @@ int hc_geometry(const rulgnn_hiercorrpool_shape* s, HcGeom* g) {
     return RULGNN_OK;
 }
 
+// HierCorrPool's gate: the packed window in front, the limits of include/rulgnn.h's HierCorrPool section
+int hc_geometry(const rulgnn_hiercorrpool_shape* s, HcGeom* g) {
+    if (!s) return RULGNN_EINVAL;
+    const HcFront fe{0, s->patch_size, s->num_nodes * s->patch_size, HC_MAXN, HC_MAXP, HC_MAXP, HC_MAXD};
+    return hc_geometry(s, fe, g);
+}
+
+// HierCorrPool_bearing's gate: the STFT's shape (even nperseg, more than nperseg / 2 points to reflect), kwargs that describe it, then the
+// shared geometry under RULGNN_HCPB_MAX_*
+int hcpb_geometry(const rulgnn_hcpb_shape* s, HcGeom* g) {
+    if (!s) return RULGNN_EINVAL;
+    if (s->input_dim < 0 || s->nperseg < 0 || s->patch_size < 0 || s->num_nodes < 0) return RULGNN_EINVAL;
+    const int ns = s->nperseg;
+    if (ns < 2 || (ns & 1) || ns > RULGNN_HCPB_MAX_NPERSEG || s->patch_size <= ns / 2) return RULGNN_EUNSUPPORTED;
+    if (s->num_nodes != ns / 2 + 1 || s->input_dim != 1 + s->patch_size / ns || s->input_dim > RULGNN_HCPB_MAX_INPUT_DIM)
+        return RULGNN_EUNSUPPORTED;
+    const rulgnn_hiercorrpool_shape core{s->batch, s->patch_size, s->num_patch, s->hidden_dim, s->embedding_dim, s->num_nodes,
+                                         s->encoder_conv_kernel, s->num_nodes_out};
+    // (patch_size < (max_input_dim + 1) nperseg follows from input_dim's limit: the staged patch stays under 5 KB of LDS)
+    const HcFront fe{ns, s->input_dim, s->num_nodes * s->input_dim, RULGNN_HCPB_MAX_NODES, RULGNN_HCPB_MAX_NUM_PATCH,
+                     (RULGNN_HCPB_MAX_INPUT_DIM + 1) * RULGNN_HCPB_MAX_NPERSEG, RULGNN_HCPB_MAX_D};
+    return hc_geometry(&core, fe, g);
+}
+
 __device__ __forceinline__ float hc_lrelu(float v) { return v > 0.f ? v : HC_SLOPE * v; }
 __device__ __forceinline__ float hc_dlrelu(float v) { return v > 0.f ? 1.f : HC_SLOPE; }
 
@@ -243,6 +284,43 @@ __global__ void hc_pack_input_kernel(int64_t B, int N, int P, int p, const float
         float v = 0.f;
         if (t >= 0 && t < P) { const int n = c / p, j = c - n * p; v = x[(b * N + n) * (int64_t)(P * p) + t * p + j]; }
         in[i] = v;
+    }
+}
+
+// HierCorrPool_bearing's block-1 input, written directly in the layout the convolutions read: in [b][P + 8][C0 = N f],
+// in[b][4 + t][n f + j] = |STFT(patch t of sample b)|[bin n][frame j] (torch.stft with n_fft = hop = win = ns, periodic Hann,
+// reflect-centred: stft_device.hpp's arithmetic), zero rows around.  THE SPECTROGRAM EXISTS IN NO OTHER LAYOUT AND IN NO OTHER BUFFER:
+// this kernel reads the raw window x [b][P p] and its only output is `in`, which the block-1 products read as it stands.
+// Work mapping.  The kernel moves 4 (P p + (P + 8) C0) bytes per sample and does ns multiply-adds per output (at most 32): it is bound by
+// its stores, so the mapping is chosen for them.  An item is one ROW of the output, (sample, r) with r over the P + 8 rows of a sample: a
+// pad row is C0 zeros, any other row is one (sample, patch) -- its reflect-padded patch (p + ns floats; with the tables p + 4 ns, 2.5 KB
+// at the widest reference row) is staged in LDS once, the workgroup's threads take the row's N f outputs (at most 289 at the reference's
+// rows: one or two passes of 256), and consecutive threads store consecutive floats, so every row is written contiguously and exactly
+// once.  Workgroups walk the items in a grid-stride loop and build the twiddle and window tables once each, not once per patch.  With
+// the pad rows as items of the same loop the kernel writes every float of `in`: nothing depends on what the workspace held.  No atomics,
+// one writer per element: two runs give the same bits.  The STFT is not differentiated (the input has no gradient).
+__global__ __launch_bounds__(SB) void hcpb_stft_input_kernel(int64_t B, int N, int f, int P, int p, int ns, const float* __restrict__ x,
+                                                             float* __restrict__ in) {
+    extern __shared__ float hcpb_sm[];
+    const StftLds l = stft_carve(hcpb_sm, p, ns);
+    const int tid = threadIdx.x, C0 = N * f, rows = P + 2 * HC_PAD;
+    stft_tables(l, ns, tid);
+    const int64_t items = B * rows;
+    for (int64_t it = blockIdx.x; it < items; it += gridDim.x) {
+        const int64_t b = it / rows;
+        const int t = (int)(it - b * rows) - HC_PAD;
+        float* row = in + it * C0;
+        if (t < 0 || t >= P) {                             // (the same for every thread of the workgroup)
+            for (int c = tid; c < C0; c += SB) row[c] = 0.f;
+            continue;
+        }
+        __syncthreads();                                   // the tables are written; the previous patch has been read
+        stft_load_patch(l, x + (b * P + t) * (int64_t)p, p, ns, tid);
+        __syncthreads();
+        for (int c = tid; c < C0; c += SB) {
+            const int n = c / f;
+            row[c] = stft_magnitude(l, ns, n, c - n * f);
+        }
     }
 }
 
@@ -691,45 +769,9 @@ HcEpi hc_epi(const HcGeom& g, int l, float* ws, const rulgnn_hiercorrpool_args* 
     return q;
 }
 
-}  // namespace
-
-// RULGNN_OK, or the code every entry returns for a refused shape: hc_geometry's own.
-int Hiercorrpool::shape_status(const Shape* s) {
-    HcGeom g;
-    return hc_geometry(s, &g);
-}
-
-int64_t Hiercorrpool::param_count(const Shape* s) {
-    HcGeom g;
-    return hc_geometry(s, &g) == RULGNN_OK ? g.pcount : -1;
-}
-
-int64_t Hiercorrpool::bn_state_count(const Shape* s) {
-    HcGeom g;
-    return hc_geometry(s, &g) == RULGNN_OK ? g.bncount : -1;
-}
-
-size_t Hiercorrpool::workspace_bytes(const Shape* s) {
-    HcGeom g;
-    return hc_geometry(s, &g) == RULGNN_OK ? g.total_bytes : 0;
-}
-
-int64_t Hiercorrpool::tap_offset(const Shape* s, int which) {
-    HcGeom g;
-    if (hc_geometry(s, &g) != RULGNN_OK) return -1;
-    switch (which) {
-        case 0: return g.w_enc;
-        case 1: return g.w_xp;
-        case 2: return g.w_ap;
-        case 3: return g.w_H;
-        default: return -1;
-    }
-}
-
+// The chain of both families; the front end (g.ns) decides the first launch and nothing else.
 // mode bit 0: forward, bit 1: backward (after a forward with the same args / workspace)
-int Hiercorrpool::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
-    HcGeom g;
-    RULGNN_TRY(hc_geometry(s, &g));
+int hc_run(const HcGeom& g, const rulgnn_hiercorrpool_args* a, int mode, hipStream_t st) {
     if (a->workspace_bytes < g.total_bytes) return RULGNN_EWORKSPACE;
     if (g.B == 0) return RULGNN_OK;
     float* ws = static_cast<float*>(a->workspace);
@@ -741,7 +783,11 @@ int Hiercorrpool::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
     const float* dpred = a->dpred ? a->dpred : ws + g.w_dpred;
     (void)hipGetLastError();
     if (mode & 1) {
-        hipLaunchKernelGGL(hc_pack_input_kernel, dim3(hc_blocks(g.blk[0].R * g.blk[0].Cin)), dim3(HC_GB), 0, st, B, N, g.P, g.p, a->x, ws + g.blk[0].w_in);
+        if (g.ns)
+            hipLaunchKernelGGL(hcpb_stft_input_kernel, dim3(hc_grid(g.blk[0].R, HCPB_GRID)), dim3(SB), sizeof(float) * stft_lds_floats(g.p, g.ns), st,
+                               B, N, g.w, g.P, g.p, g.ns, a->x, ws + g.blk[0].w_in);
+        else
+            hipLaunchKernelGGL(hc_pack_input_kernel, dim3(hc_blocks(g.blk[0].R * g.blk[0].Cin)), dim3(HC_GB), 0, st, B, N, g.P, g.p, a->x, ws + g.blk[0].w_in);
         HcPack pk{};
         for (int l = 0; l < 3; ++l) {
             const HcBlock& k = g.blk[l];
@@ -832,6 +878,85 @@ int Hiercorrpool::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
         RULGNN_LAUNCH_OK();
     }
     return RULGNN_OK;
+}
+
+// workspace taps of both families, float offsets (4, 5: the block-1 input and block 1's convolution output, which follows it)
+int64_t hc_tap(const HcGeom& g, int which, bool bearing) {
+    switch (which) {
+        case 0: return g.w_enc;
+        case 1: return g.w_xp;
+        case 2: return g.w_ap;
+        case 3: return g.w_H;
+        case 4: return bearing ? g.blk[0].w_in : -1;
+        case 5: return bearing ? g.blk[0].w_z : -1;
+        default: return -1;
+    }
+}
+
+}  // namespace
+
+// RULGNN_OK, or the code every entry returns for a refused shape: hc_geometry's own.
+int Hiercorrpool::shape_status(const Shape* s) {
+    HcGeom g;
+    return hc_geometry(s, &g);
+}
+
+int64_t Hiercorrpool::param_count(const Shape* s) {
+    HcGeom g;
+    return hc_geometry(s, &g) == RULGNN_OK ? g.pcount : -1;
+}
+
+int64_t Hiercorrpool::bn_state_count(const Shape* s) {
+    HcGeom g;
+    return hc_geometry(s, &g) == RULGNN_OK ? g.bncount : -1;
+}
+
+size_t Hiercorrpool::workspace_bytes(const Shape* s) {
+    HcGeom g;
+    return hc_geometry(s, &g) == RULGNN_OK ? g.total_bytes : 0;
+}
+
+int64_t Hiercorrpool::tap_offset(const Shape* s, int which) {
+    HcGeom g;
+    return hc_geometry(s, &g) == RULGNN_OK ? hc_tap(g, which, false) : -1;
+}
+
+int Hiercorrpool::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
+    HcGeom g;
+    RULGNN_TRY(hc_geometry(s, &g));
+    return hc_run(g, a, mode, st);
+}
+
+// ---- HierCorrPool_bearing: the same chain behind hcpb_geometry -----------------------------------------------------------------------------
+int Hcpb::shape_status(const Shape* s) {
+    HcGeom g;
+    return hcpb_geometry(s, &g);
+}
+
+int64_t Hcpb::param_count(const Shape* s) {
+    HcGeom g;
+    return hcpb_geometry(s, &g) == RULGNN_OK ? g.pcount : -1;
+}
+
+int64_t Hcpb::bn_state_count(const Shape* s) {
+    HcGeom g;
+    return hcpb_geometry(s, &g) == RULGNN_OK ? g.bncount : -1;
+}
+
+size_t Hcpb::workspace_bytes(const Shape* s) {
+    HcGeom g;
+    return hcpb_geometry(s, &g) == RULGNN_OK ? g.total_bytes : 0;
+}
+
+int64_t Hcpb::tap_offset(const Shape* s, int which) {
+    HcGeom g;
+    return hcpb_geometry(s, &g) == RULGNN_OK ? hc_tap(g, which, true) : -1;
+}
+
+int Hcpb::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
+    HcGeom g;
+    RULGNN_TRY(hcpb_geometry(s, &g));
+    return hc_run(g, a, mode, st);
 }
 
 }  // namespace rulgnn

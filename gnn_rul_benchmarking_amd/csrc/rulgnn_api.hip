@@ -340,6 +340,7 @@ size_t rulgnn_struct_size(int32_t which) {
     case RULGNN_STRUCT_GATLSTM_SHAPE: return sizeof(rulgnn_gatlstm_shape);
     case RULGNN_STRUCT_GATLSTM_ARGS: return sizeof(rulgnn_gatlstm_args);
     case RULGNN_STRUCT_LOGOB_SHAPE: return sizeof(rulgnn_logob_shape);
+    case RULGNN_STRUCT_HCPB_SHAPE: return sizeof(rulgnn_hcpb_shape);
     default: return 0;
     }
 }
@@ -1004,13 +1005,18 @@ int64_t rulgnn_hiercorrpool_bn_state_count(const rulgnn_hiercorrpool_shape* shap
 size_t rulgnn_hiercorrpool_workspace_bytes(const rulgnn_hiercorrpool_shape* shape) { return Hiercorrpool::workspace_bytes(shape); }
 int64_t rulgnn_hiercorrpool_tap_offset(const rulgnn_hiercorrpool_shape* shape, int32_t which) { return Hiercorrpool::tap_offset(shape, which); }
 
-int Hiercorrpool::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
-    RULGNN_TRY(shape_status(shape));
-    if (a->global_batch < shape->batch || a->sample_offset < 0) return RULGNN_EINVAL;
+// (HierCorrPool_bearing takes the same argument struct)
+static int check_hiercorrpool_args(const rulgnn_hiercorrpool_args* a, int64_t batch, bool bwd) {
+    if (a->global_batch < batch || a->sample_offset < 0) return RULGNN_EINVAL;
     if (!(a->dropout_p >= 0.f && a->dropout_p < 1.f)) return RULGNN_EINVAL;
     RULGNN_TRY(check_ptrs({a->params, a->workspace, a->bn_state}));
-    RULGNN_TRY(check_step_ptrs(a, shape->batch, bwd));
+    RULGNN_TRY(check_step_ptrs(a, batch, bwd));
     return bwd && !a->training ? RULGNN_EINVAL : RULGNN_OK;
+}
+
+int Hiercorrpool::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
+    RULGNN_TRY(shape_status(shape));
+    return check_hiercorrpool_args(a, shape->batch, bwd);
 }
 
 int rulgnn_hiercorrpool_forward_f32(const rulgnn_hiercorrpool_shape* shape, const rulgnn_hiercorrpool_args* args, void* stream) {
@@ -1021,6 +1027,27 @@ int rulgnn_hiercorrpool_backward_f32(const rulgnn_hiercorrpool_shape* shape, con
 }
 int rulgnn_hiercorrpool_fwdbwd_f32(const rulgnn_hiercorrpool_shape* shape, const rulgnn_hiercorrpool_args* args, const rulgnn_adam_args* opt, void* stream) {
     return step_fwdbwd<Hiercorrpool>(shape, args, opt, stream);
+}
+
+// ---- HierCorrPool_bearing --------------------------------------------------------------------------
+int64_t rulgnn_hcpb_param_count(const rulgnn_hcpb_shape* shape) { return Hcpb::param_count(shape); }
+int64_t rulgnn_hcpb_bn_state_count(const rulgnn_hcpb_shape* shape) { return Hcpb::bn_state_count(shape); }
+size_t rulgnn_hcpb_workspace_bytes(const rulgnn_hcpb_shape* shape) { return Hcpb::workspace_bytes(shape); }
+int64_t rulgnn_hcpb_tap_offset(const rulgnn_hcpb_shape* shape, int32_t which) { return Hcpb::tap_offset(shape, which); }
+
+int Hcpb::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
+    RULGNN_TRY(shape_status(shape));
+    return check_hiercorrpool_args(a, shape->batch, bwd);
+}
+
+int rulgnn_hcpb_forward_f32(const rulgnn_hcpb_shape* shape, const rulgnn_hiercorrpool_args* args, void* stream) {
+    return step_forward<Hcpb>(shape, args, stream);
+}
+int rulgnn_hcpb_backward_f32(const rulgnn_hcpb_shape* shape, const rulgnn_hiercorrpool_args* args, void* stream) {
+    return step_backward<Hcpb>(shape, args, stream);
+}
+int rulgnn_hcpb_fwdbwd_f32(const rulgnn_hcpb_shape* shape, const rulgnn_hiercorrpool_args* args, const rulgnn_adam_args* opt, void* stream) {
+    return step_fwdbwd<Hcpb>(shape, args, opt, stream);
 }
 
 // ---- LOGO ------------------------------------------------------------------------------------------

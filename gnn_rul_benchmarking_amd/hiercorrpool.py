@@ -145,7 +145,10 @@ class HierCorrPool_model(FlatModule):
         M, d = self.num_nodes_out, self.feature_dim
         idx, shape = {"encoder": (0, (self.encoder_out_length, 4 * self.hidden_dim * self.num_nodes)), "pooled_x": (1, (M, d)),
                       "pooled_adj": (2, (M, M)), "H": (3, (M, 3 * d))}[which]
-        off = _lib.load().rulgnn_hiercorrpool_tap_offset(C.byref(self._shape(batch)), idx)
+        return self._tap(batch, idx, shape)
+
+    def _tap(self, batch, idx, shape):
+        off = getattr(_lib.load(), f"rulgnn_{self.c_family}_tap_offset")(C.byref(self._shape(batch)), idx)
         ws = self._bufs[batch][0].view(torch.float32)
         return ws[off:off + batch * shape[0] * shape[1]].view(batch, *shape).clone()
 

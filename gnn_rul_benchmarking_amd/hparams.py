@@ -1,7 +1,7 @@
 """Hyper-parameter tables, looked up by dataset name then dataset id, like the reference's
 configs/hparams.py:3-7 (``get_hparams_class(name)(dataset_id)`` -> object with ``train_params`` and
 ``alg_hparams`` dicts keyed by ``--GNN_method``; unknown dataset -> NotImplementedError, unknown id ->
-ValueError).  Only the ST_GCN, STMSGCN, ASTGCNN, FC_STGNN, HAGCN, ST_Conv, STGNN, RGCNU, GRU_CM, STNet, SAGCN, AGCN_TF, STAGNN, HierCorrPool, LOGO, DVGTformer, GDAGDL, GAT_LSTM and LOGO_bearing rows are restated (the methods this package
+ValueError).  Only the ST_GCN, STMSGCN, ASTGCNN, FC_STGNN, HAGCN, ST_Conv, STGNN, RGCNU, GRU_CM, STNet, SAGCN, AGCN_TF, STAGNN, HierCorrPool, LOGO, DVGTformer, GDAGDL, GAT_LSTM, LOGO_bearing and HierCorrPool_bearing rows are restated (the methods this package
 implements).
 
 PHM2012 / XJTU_SY rows are the reference's (configs/hparams.py:223,238,... and :334,349,...; STMSGCN
@@ -58,6 +58,7 @@ class _Table:
     _gdagdl_rows: dict = {}           # ... and GDAGDL (configs/hparams.py:225,240,255,272,291 and the XJTU_SY class)
     _gatlstm_rows: dict = {}          # ... and GAT_LSTM (configs/hparams.py:224,239,254,270,290,306 and :335,350,370,385,404,419)
     _logob_rows: dict = {}            # ... and LOGO_bearing (configs/hparams.py:228,244,258,278,294,314 and :339,358,374,393,408,427)
+    _hcpb_rows: dict = {}             # ... and HierCorrPool_bearing (configs/hparams.py:230,245,260,280,296,316 and :341,360,376,395,410,429)
     _sagcn_rows: dict = {}            # ... and SAGCN (configs/hparams.py:221,235,266,302 and :332,346,381,415)
     _agcntf_rows: dict = {}           # ... and AGCN_TF (configs/hparams.py:227,243,257,277,293,313 and :338,357,373,392,407,426)
     _astgcnn_nodes = None             # ... and ASTGCNN to the aero-engine datasets only (configs/hparams.py:38,202)
@@ -132,6 +133,12 @@ class _Table:
             patch_size, num_patch, input_dim, num_nodes, nperseg = self._logob_rows[dataset_id]
             self.alg_hparams['LOGO_bearing'] = {'patch_size': patch_size, 'num_patch': num_patch, 'input_dim': input_dim,
                                                 'num_nodes': num_nodes, 'nperseg': nperseg, 'hidden_dim': 10}
+        if dataset_id in self._hcpb_rows:
+            self.train_params['HierCorrPool_bearing'] = {'num_epochs': 81, 'batch_size': 100, 'weight_decay': 1e-4, 'learning_rate': 1e-3}
+            patch_size, num_patch, input_dim, num_nodes, nperseg, conv_kernel = self._hcpb_rows[dataset_id]
+            self.alg_hparams['HierCorrPool_bearing'] = {'patch_size': patch_size, 'num_patch': num_patch, 'input_dim': input_dim,
+                                                        'hidden_dim': 10, 'embedding_dim': 10, 'num_nodes': num_nodes, 'nperseg': nperseg,
+                                                        'encoder_conv_kernel': conv_kernel, 'num_nodes_out': 6}
         if dataset_id in self._sagcn_rows:
             self.train_params['SAGCN'] = {'num_epochs': 81, 'batch_size': 100, 'weight_decay': 1e-4, 'learning_rate': 1e-4}
             num_patch, patch_size, gcn_hidden, attention_hidden = self._sagcn_rows[dataset_id]
@@ -178,6 +185,7 @@ class PHM2012(_Table):
     _gdagdl_rows = {'Condition_1': (128, 20, 3, 4, 6), 'Condition_2': (128, 20, 3, 4, 6), 'Condition_3': (80, 32, 5, 8, 5)}
     _gatlstm_rows = {'Condition_1': (40, 64), 'Condition_2': (80, 32), 'Condition_3': (40, 64)}
     _logob_rows = {c: (64, 40, 9, 5, 8) for c in ('Condition_1', 'Condition_2', 'Condition_3')}
+    _hcpb_rows = {'Condition_1': (32, 80, 5, 5, 8, 48), 'Condition_2': (128, 20, 9, 9, 16, 20), 'Condition_3': (64, 40, 9, 5, 8, 28)}
     _sagcn_rows = {'Condition_1': (160, 16, 100, 100), 'Condition_2': (128, 20, 1000, 200), 'Condition_3': (128, 20, 1000, 200)}
     _agcntf_rows = {'Condition_1': (40, 64, 100, 100), 'Condition_2': (40, 64, 100, 100), 'Condition_3': (40, 64, 100, 100)}
 
@@ -193,6 +201,7 @@ class XJTU_SY(_Table):
     _gdagdl_rows = {c: (32, 1024, 17, 32, 33) for c in ('Condition_1', 'Condition_2', 'Condition_3')}
     _gatlstm_rows = {'Condition_1': (32, 1024), 'Condition_2': (64, 512), 'Condition_3': (32, 1024)}
     _logob_rows = {c: (1024, 32, 33, 17, 32) for c in ('Condition_1', 'Condition_2', 'Condition_3')}
+    _hcpb_rows = {'Condition_1': (512, 64, 17, 17, 32, 40), 'Condition_2': (256, 128, 17, 9, 16, 72), 'Condition_3': (256, 128, 17, 9, 16, 72)}
     _sagcn_rows = {'Condition_1': (32, 1024, 1000, 100), 'Condition_2': (32, 1024, 1000, 200), 'Condition_3': (32, 1024, 1000, 200)}
     _agcntf_rows = {'Condition_1': (128, 256, 100, 100), 'Condition_2': (128, 256, 100, 100), 'Condition_3': (256, 128, 100, 100)}
 

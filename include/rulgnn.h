@@ -347,6 +347,8 @@ size_t rulgnn_stgcn_train_args_size(void);
 #define RULGNN_STRUCT_GATLSTM_ARGS 39
 /* (index 40 is unassigned and answers 0; LOGO_bearing's argument struct is rulgnn_logo_args, index 32) */
 #define RULGNN_STRUCT_LOGOB_SHAPE 41
+/* (index 42 is unassigned and answers 0; HierCorrPool_bearing's argument struct is rulgnn_hiercorrpool_args, index 30) */
+#define RULGNN_STRUCT_HCPB_SHAPE 43
 size_t rulgnn_struct_size(int32_t which);
 
 /* Profiling aid: the training step is a chain of 4*num_layers+1 phase kernels:
@@ -1392,6 +1394,47 @@ int rulgnn_logob_forward_f32(const rulgnn_logob_shape *shape, const rulgnn_logo_
 int rulgnn_logob_backward_f32(const rulgnn_logob_shape *shape, const rulgnn_logo_args *args, void *stream);
 /* LOGO_bearing.update body (algorithms.py:619-629) short of its scheduler step; with `opt` also Adam on the flat parameter buffer. */
 int rulgnn_logob_fwdbwd_f32(const rulgnn_logob_shape *shape, const rulgnn_logo_args *args, const rulgnn_adam_args *opt, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * HierCorrPool_bearing path (reference models/HierCorrPool_bearing/Model.py:6-67, algorithms/algorithms.py:633-658; wired to the
+ * bearing datasets PHM2012 and XJTU_SY, configs/hparams.py): HierCorrPool behind an STFT front end.
+ *
+ * P = num_patch, p = patch_size, ns = nperseg, N = num_nodes = ns/2 + 1, f = input_dim = 1 + p/ns.
+ * x [batch, P * p] -> per (sample, patch) mag [N][f] = |STFT| as STNet's, GDAGDL's and LOGO_bearing's (n_fft = hop = win = ns, periodic
+ * Hann, reflect-centred without repeating the edge sample) -> encoder input [batch, C0 = N f, P], in[b][n f + j][t] = mag[b, t][n][j].
+ * From block 1 on this is the HierCorrPool path above with C0 = N f: same 19 tensors in the same flat layout (conv_block1.0.weight is
+ * [h N][N f][8]), same bn_state, same dropout counters, same argument struct (rulgnn_hiercorrpool_args, x = [batch, P * p]).  The
+ * STFT is not differentiated.  The spectrogram is written once, by one kernel, in the channel-last time-padded layout block 1's
+ * products read; it exists in no other layout or buffer.  HierCorrPool_bearing.update: plain MSE.
+ * Limits (RULGNN_EUNSUPPORTED beyond, before any launch; the workspace query returns 0): ns even, 2 <= ns <= RULGNN_HCPB_MAX_NPERSEG,
+ * p > ns / 2, num_nodes == ns/2 + 1 (<= RULGNN_HCPB_MAX_NODES), input_dim == 1 + p/ns <= RULGNN_HCPB_MAX_INPUT_DIM,
+ * 2 <= P <= RULGNN_HCPB_MAX_NUM_PATCH, 1 <= num_nodes_out <= 16, d = K e <= RULGNN_HCPB_MAX_D, 4 h N <= 1024, L' 4 h == K e, every
+ * padded activation under 2^31 elements, and the graph stage within one compute unit's 160 KB of LDS (N 17, M 16, d 720: 113 212 B in the
+ * backward).  Deterministic: no floating-point atomics, fixed-order reductions.
+ */
+#define RULGNN_HCPB_MAX_NPERSEG 32
+#define RULGNN_HCPB_MAX_NODES 17
+#define RULGNN_HCPB_MAX_INPUT_DIM 33
+#define RULGNN_HCPB_MAX_NUM_PATCH 128
+#define RULGNN_HCPB_MAX_D 720
+
+typedef struct rulgnn_hcpb_shape {
+    int64_t batch;
+    int32_t patch_size, num_patch, input_dim, hidden_dim, embedding_dim, num_nodes, nperseg, encoder_conv_kernel, num_nodes_out;
+} rulgnn_hcpb_shape;
+
+int64_t rulgnn_hcpb_param_count(const rulgnn_hcpb_shape *shape);       /* < 0: invalid / unsupported */
+int64_t rulgnn_hcpb_bn_state_count(const rulgnn_hcpb_shape *shape);    /* < 0: invalid / unsupported */
+size_t rulgnn_hcpb_workspace_bytes(const rulgnn_hcpb_shape *shape);    /* 0: invalid / unsupported */
+/* workspace taps 0-3 as rulgnn_hiercorrpool_tap_offset's; 4 the block-1 input [batch][P + 8][C0] (the spectrogram between four zero
+ * rows on each side), 5 block 1's convolution output, which follows it; -1 otherwise */
+int64_t rulgnn_hcpb_tap_offset(const rulgnn_hcpb_shape *shape, int32_t which);
+/* model(x): HierCorrPool_bearing_model.forward (Model.py:25-67). */
+int rulgnn_hcpb_forward_f32(const rulgnn_hcpb_shape *shape, const rulgnn_hiercorrpool_args *args, void *stream);
+/* loss.backward() after a TRAINING forward with the same args / workspace (RULGNN_EINVAL when args->training == 0). */
+int rulgnn_hcpb_backward_f32(const rulgnn_hcpb_shape *shape, const rulgnn_hiercorrpool_args *args, void *stream);
+/* HierCorrPool_bearing.update body (algorithms.py:649-658); with `opt` also Adam on the flat parameter buffer. */
+int rulgnn_hcpb_fwdbwd_f32(const rulgnn_hcpb_shape *shape, const rulgnn_hiercorrpool_args *args, const rulgnn_adam_args *opt, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * DVGTformer path (reference models/DVGTformer/Model.py, algorithms/algorithms.py:326-351; wired to C-MAPSS FD001-4 and N-CMAPSS,

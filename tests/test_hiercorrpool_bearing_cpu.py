@@ -1,0 +1,278 @@
+"""HierCorrPool_bearing without a GPU: the registry and the algorithm class, the six hparams rows, the seed, parameter counts, the C-ABI's
+struct table, the coverage gate at every limit, the workspace layout in front of block 1 and the CPU-input refusal."""
+import ctypes as C
+import glob
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from gnn_rul_benchmarking_amd import _lib
+from gnn_rul_benchmarking_amd.hiercorrpool_bearing import LIMITS, HierCorrPool_bearing_model
+
+from conftest import GOLDEN
+
+import hiercorrpool_bearing_oracle as O
+from test_hiercorrpool_bearing_oracle_golden import CURVE, FORWARD_ONLY, SMALL, load_case
+
+FIELDS = O.KEYS
+RULGNN_EINVAL, RULGNN_EUNSUPPORTED = -1, -2                # include/rulgnn.h
+LDS_BUDGET = 160 * 1024                                    # csrc/launch.hpp MAX_LDS_BYTES
+DATASETS = [(ds, f"Condition_{i}") for ds in ("PHM2012", "XJTU_SY") for i in (1, 2, 3)]
+
+
+def make_cfg(p=8, P=2, ns=4, h=1, e=1, K=8, M=1, **over):
+    return dict(dict(patch_size=p, num_patch=P, input_dim=1 + p // ns if ns > 0 else 0, hidden_dim=h, embedding_dim=e, num_nodes=ns // 2 + 1,
+                     nperseg=ns, encoder_conv_kernel=K, num_nodes_out=M), **over)
+
+
+# the reference's rows (configs/hparams.py), restated from the issue's table
+ROWS = {"PHM2012/Condition_1": make_cfg(32, 80, 8, 10, 10, 48, 6), "PHM2012/Condition_2": make_cfg(128, 20, 16, 10, 10, 20, 6),
+        "PHM2012/Condition_3": make_cfg(64, 40, 8, 10, 10, 28, 6), "XJTU_SY/Condition_1": make_cfg(512, 64, 32, 10, 10, 40, 6),
+        "XJTU_SY/Condition_2": make_cfg(256, 128, 16, 10, 10, 72, 6), "XJTU_SY/Condition_3": make_cfg(256, 128, 16, 10, 10, 72, 6)}
+
+
+def shape_of(batch, cfg):
+    return _lib.HcpbShape(batch, *[cfg[k] for k in FIELDS])
+
+
+def want_param_count(cfg):
+    N, f, h, e, K, M = (cfg[k] for k in ("num_nodes", "input_dim", "hidden_dim", "embedding_dim", "encoder_conv_kernel", "num_nodes_out"))
+    d, C0, C1 = K * e, N * f, h * N
+    return 8 * (C1 * C0 + 2 * C1 * C1 + 8 * C1 * C1) + 2 * 7 * C1 + 3 * d * d + 3 * d + M * d + M + M * (N + M) + M + 3 * e * 3 * d * M + 3 * e + 3 * e + 1
+
+
+def test_registry_refuses_the_name_and_the_class_constructs_from_every_row():
+    from gnn_rul_benchmarking_amd import algorithms as A
+    from gnn_rul_benchmarking_amd.hparams import get_hparams_class
+    from gnn_rul_benchmarking_amd.hiercorrpool import HierCorrPool_model
+    from gnn_rul_benchmarking_amd.optim import FusedAdam
+    assert issubclass(A.HierCorrPool_bearing, A.HierCorrPool) and A.HierCorrPool_bearing.model_class is HierCorrPool_bearing_model
+    assert issubclass(HierCorrPool_bearing_model, HierCorrPool_model)
+    for name in ("HierCorrPool_bearing", "HierCorrPool_bearing_model"):
+        with pytest.raises(NotImplementedError, match="Algorithm not found: " + name):
+            A.get_algorithm_class(name)
+    assert A.get_algorithm_class("HierCorrPool") is A.HierCorrPool
+    assert A.HierCorrPool_bearing.supports_graphs is False and "BatchNorm" in A.HierCorrPool_bearing.needs_train_mode
+    for ds, did in DATASETS:
+        h = get_hparams_class(ds)(did)
+        algo = A.HierCorrPool_bearing(h.alg_hparams["HierCorrPool_bearing"], h.train_params["HierCorrPool_bearing"], "cpu")
+        assert isinstance(algo.model, HierCorrPool_bearing_model) and isinstance(algo.optimizer, FusedAdam)
+        assert algo.model.c_family == "hcpb" and algo.model.dropout_p == 0.35 and not hasattr(algo, "lr_schedular")
+        assert algo.model.num_live == want_param_count(ROWS[f"{ds}/{did}"])
+        with pytest.raises(RuntimeError, match="data parallelism for HierCorrPool is not built yet"):
+            algo.attach_data_parallel(object())
+
+
+def test_hparams_rows_equal_the_reference():
+    from gnn_rul_benchmarking_amd.hparams import get_hparams_class
+    rows = json.loads(str(np.load(os.path.join(GOLDEN, "hcpb_hparams_rows.npz"))["rows_json"]))
+    assert sorted(rows) == sorted(ROWS)
+    for key, ref in rows.items():
+        ds, did = key.split("/")
+        h = get_hparams_class(ds)(did)
+        assert h.train_params["HierCorrPool_bearing"] == ref["train_params"] and h.alg_hparams["HierCorrPool_bearing"] == ref["alg_hparams"], key
+        assert h.alg_hparams["HierCorrPool_bearing"] == ROWS[key] and list(h.alg_hparams["HierCorrPool_bearing"]) == FIELDS
+        assert h.train_params["HierCorrPool_bearing"] == {"num_epochs": 81, "batch_size": 100, "weight_decay": 1e-4, "learning_rate": 1e-3}
+    for ds, did in (("CMAPSS", "FD001"), ("NCMAPSS", None)):
+        h = get_hparams_class(ds)(did)
+        assert "HierCorrPool_bearing" not in h.alg_hparams and "HierCorrPool_bearing" not in h.train_params
+
+
+@pytest.mark.parametrize("name", SMALL + FORWARD_ONLY + [CURVE])
+def test_a_seed_gives_the_reference_keys_and_initial_values(name):
+    """The 28 keys, their order, strict load and -- under the fixture's seed, minus the maker's recorded perturbation of the parameters --
+    the reference's initial values bit for bit."""
+    z, cfg, stored = load_case(name, "sd0:" if name == CURVE else "sd:")
+    seed = int(z["seed"])
+    torch.manual_seed(seed)
+    m = HierCorrPool_bearing_model(**cfg)
+    sd = m.state_dict()
+    assert list(sd.keys()) == list(stored) == O.state_keys() and len(sd) == 28
+    names = [n for n, _ in m.named_parameters()]
+    assert names == O.param_names() and len(names) == 19
+    assert tuple(sd[O.ENC.format(1) + "0.weight"].shape) == (cfg["hidden_dim"] * cfg["num_nodes"], cfg["input_dim"] * cfg["num_nodes"], 8)
+    assert np.array_equal(m.flat_params.numpy(), np.concatenate([sd[k].numpy().ravel() for k in names]))
+    g = torch.Generator().manual_seed(seed + 1000)                  # the maker's p.add_(uniform(-0.1, 0.1)) over named_parameters()
+    want = {k: sd[k].clone() for k in sd}
+    for k in names:
+        want[k].add_(torch.empty_like(want[k]).uniform_(-0.1, 0.1, generator=g))
+    for k, v in want.items():
+        assert v.shape == stored[k].shape and np.array_equal(v.numpy(), stored[k]), k
+    other = HierCorrPool_bearing_model(**cfg)
+    other.load_state_dict({k: torch.from_numpy(np.asarray(stored[k])) for k in sd}, strict=True)
+    with pytest.raises(RuntimeError):
+        other.load_state_dict({k: torch.from_numpy(np.asarray(stored[k])) for k in list(sd)[1:]}, strict=True)
+
+
+@pytest.mark.parametrize("key", sorted(ROWS))
+def test_param_counts_and_every_reference_row_is_accepted(key):
+    cfg = ROWS[key]
+    lib = _lib.load()
+    m = HierCorrPool_bearing_model(**cfg)
+    count = sum(p.numel() for p in m.parameters())
+    assert count == want_param_count(cfg) == m.num_live
+    C1 = cfg["hidden_dim"] * cfg["num_nodes"]
+    for B in (1, 100, 1024):                                         # the batches the limits must admit
+        s = shape_of(B, cfg)
+        assert lib.rulgnn_hcpb_param_count(C.byref(s)) == count and lib.rulgnn_hcpb_workspace_bytes(C.byref(s)) > 0
+        assert lib.rulgnn_hcpb_bn_state_count(C.byref(s)) == 2 * 7 * C1
+
+
+def test_construction_names_both_numbers_when_the_reshape_cannot_exist():
+    with pytest.raises(ValueError, match=r"480 in all.*encoder_conv_kernel \* embedding_dim = 490"):
+        HierCorrPool_bearing_model(**dict(ROWS["PHM2012/Condition_1"], encoder_conv_kernel=49))
+    bad = shape_of(4, dict(ROWS["PHM2012/Condition_1"], encoder_conv_kernel=49))
+    lib = _lib.load()
+    assert lib.rulgnn_hcpb_param_count(C.byref(bad)) < 0 and lib.rulgnn_hcpb_workspace_bytes(C.byref(bad)) == 0
+
+
+def test_struct_table_and_limits_header():
+    lib = _lib.load()
+    assert _lib.STRUCTS_HCPB == {43: _lib.HcpbShape} and len(_lib.STRUCTS) == 37
+    assert _lib.STRUCTS_AT == {38: _lib.GatlstmShape, 39: _lib.GatlstmArgs} and _lib.STRUCTS_LATER == {41: _lib.LogobShape}
+    header = open(os.path.join(os.path.dirname(__file__), "..", "include", "rulgnn.h")).read()
+    assert "#define RULGNN_STRUCT_HCPB_SHAPE 43\n" in header and "index 42 is unassigned and answers 0" in header
+    assert lib.rulgnn_struct_size(43) == C.sizeof(_lib.HcpbShape) == 48
+    assert lib.rulgnn_struct_size(42) == 0 and lib.rulgnn_struct_size(44) == 0
+    assert [n for n, _ in _lib.HcpbShape._fields_] == ["batch"] + FIELDS
+    # the argument struct is HierCorrPool's
+    assert HierCorrPool_bearing_model.Args is _lib.HiercorrpoolArgs
+    assert lib.rulgnn_hcpb_fwdbwd_f32.argtypes[1]._type_ is _lib.HiercorrpoolArgs
+    assert lib.rulgnn_struct_size(_lib.STRUCTS.index(_lib.HiercorrpoolArgs)) == C.sizeof(_lib.HiercorrpoolArgs)
+    assert LIMITS == {"max_nperseg": 32, "max_nodes": 17, "max_input_dim": 33, "max_num_patch": 128, "max_d": 720, "max_nodes_out": 16,
+                      "max_c3": 1024}
+    for name, key in (("NPERSEG", "max_nperseg"), ("NODES", "max_nodes"), ("INPUT_DIM", "max_input_dim"), ("NUM_PATCH", "max_num_patch"),
+                      ("D", "max_d")):
+        assert f"#define RULGNN_HCPB_MAX_{name} {LIMITS[key]}\n" in header
+    m = HierCorrPool_bearing_model(**make_cfg())
+    assert "do not cover this configuration" in m.not_covered and "encoder_conv_kernel * embedding_dim <= 720" in m.not_covered
+    # HierCorrPool's own message and limits are untouched
+    from gnn_rul_benchmarking_amd.hiercorrpool import HierCorrPool_model
+    assert "2 <= num_patch <= 64" in HierCorrPool_model.not_covered and "embedding_dim <= 512" in HierCorrPool_model.not_covered
+
+
+def graph_lds_floats(N, M, d, bwd):
+    """csrc/hiercorrpool.hip hc_graph_lds, restated."""
+    LD, NL, ML = d + 1, N + 1, M + 1
+    o = N * LD + max(N, M) * LD + N * NL + 2 * N * ML + M * NL + M * ML
+    if bwd:
+        o += 2 * N * NL + 5 * N * ML + M * ML + 16
+    return o
+
+
+def test_coverage_gate_every_limit_plus_and_minus_one():
+    lib = _lib.load()
+
+    def query(cfg, B=3, code=RULGNN_EUNSUPPORTED):
+        s = shape_of(B, cfg)
+        pc, ws = lib.rulgnn_hcpb_param_count(C.byref(s)), lib.rulgnn_hcpb_workspace_bytes(C.byref(s))
+        assert (pc == -1) == (ws == 0) and (pc < 0) == (ws == 0) and (lib.rulgnn_hcpb_bn_state_count(C.byref(s)) < 0) == (ws == 0)
+        assert all((lib.rulgnn_hcpb_tap_offset(C.byref(s), i) < 0) == (ws == 0) for i in range(6))
+        if ws == 0:                    # refused by the entries too, before any launch (no device is needed to be told so)
+            a = _lib.HiercorrpoolArgs()
+            rcs = {lib.rulgnn_hcpb_forward_f32(C.byref(s), C.byref(a), None), lib.rulgnn_hcpb_backward_f32(C.byref(s), C.byref(a), None),
+                   lib.rulgnn_hcpb_fwdbwd_f32(C.byref(s), C.byref(a), None, None)}
+            assert rcs == {code}, (cfg, rcs)
+        return ws > 0
+
+    cfg = make_cfg
+    assert query(cfg(p=2, P=2, ns=2))                                        # every lower limit at once: nperseg 2, N 2, p 2, P 2, M 1
+    # nperseg: even, 2 .. 32
+    assert query(cfg(p=64, ns=32)) and not query(cfg(p=64, ns=34))
+    assert not query(cfg(ns=0)) and not query(cfg(ns=3, num_nodes=2, input_dim=3)) and not query(cfg(ns=5)) and not query(cfg(p=64, ns=33))
+    assert not query(cfg(ns=-2), code=RULGNN_EINVAL)
+    # patch_size > nperseg / 2
+    assert not query(cfg(p=1, ns=2)) and query(cfg(p=3, ns=4)) and not query(cfg(p=2, ns=4))
+    assert query(cfg(p=17, ns=32)) and not query(cfg(p=16, ns=32))
+    # (num_nodes, input_dim) is the STFT's shape
+    for bad in (dict(num_nodes=4), dict(num_nodes=2), dict(input_dim=2), dict(input_dim=4), dict(num_nodes=2, input_dim=4)):
+        assert not query(cfg(p=8, ns=4, **bad))
+    # input_dim <= 33
+    assert query(cfg(p=65, ns=2)) and not query(cfg(p=66, ns=2))
+    assert query(cfg(p=1055, ns=32)) and not query(cfg(p=1056, ns=32))
+    # 2 <= num_patch <= 128
+    assert not query(cfg(P=1)) and not query(cfg(P=0)) and not query(cfg(P=-1), code=RULGNN_EINVAL)
+    assert query(cfg(P=65, K=40)) and query(cfg(P=128, K=72)) and not query(cfg(P=129, K=72))       # L'(128) = L'(129) = 18
+    # 1 <= num_nodes_out <= 16
+    assert not query(cfg(M=0)) and query(cfg(M=16)) and not query(cfg(M=17))
+    # d = K e <= 720
+    assert query(cfg(h=90, e=90, K=8, ns=2, p=2)) and not query(cfg(h=91, e=91, K=8, ns=2, p=2))    # d = 720 / 728
+    # (724 = 4 * 181 is no L' 4 h with L' >= 2 and 8 | L' 4 h at P = 2: it is refused as d before the reshape is looked at)
+    assert query(cfg(P=128, K=72, h=10, e=10, ns=2, p=2)) and not query(cfg(P=128, K=724, h=181, e=1, ns=2, p=2))       # d = 720 / 724
+    # 4 h N <= 1024
+    assert query(cfg(p=32, ns=32, h=15, e=15)) and not query(cfg(p=32, ns=32, h=16, e=16))          # C3 = 1020 / 1088
+    # L' 4 h == K e
+    assert not query(cfg(K=9)) and not query(cfg(h=0, e=0)) and not query(cfg(K=0))
+    # the LDS check never binds under these limits: the largest graph stage the gate admits
+    assert 4 * graph_lds_floats(17, 16, 720, True) == 113212 <= LDS_BUDGET
+    assert query(cfg(p=32, ns=32, P=80, h=15, e=10, K=72, M=16))             # N 17, d 720, C3 1020, M 16
+    ws = lambda b: lib.rulgnn_hcpb_workspace_bytes(C.byref(shape_of(b, ROWS["PHM2012/Condition_3"])))      # noqa: E731
+    assert ws(0) > 0 and ws(1024) > ws(100) > ws(1) >= ws(0) and ws(-1) == 0
+    # the 32-bit row check: a padded activation of 2^31 elements is refused, one below is not
+    big = ROWS["XJTU_SY/Condition_2"]                                        # block 1 binds: B (P + 8) + 7 rows of C0 = 153 channels
+    b_max = max(b for b in range(103000, 103400) if (b * 136 + 7) * 153 < 1 << 31)
+    assert b_max < 103399
+    assert query(big, B=b_max) and not query(big, B=b_max + 1)
+
+
+def test_kwargs_that_do_not_describe_the_stft_construct_and_are_refused_at_the_first_forward():
+    """The reference constructs such a model and fails with a shape error inside its first forward."""
+    for bad in (dict(num_nodes=4), dict(input_dim=2), dict(num_nodes=2, input_dim=4)):
+        cfg = make_cfg(p=8, P=2, ns=4, **bad)
+        m = HierCorrPool_bearing_model(**cfg)
+        assert len(m.state_dict()) == 28
+        m._require_device = lambda x: None                              # (the shape check sits behind the device check)
+        with pytest.raises(RuntimeError, match=rf"\(3, 3\).*\({cfg['num_nodes']}, {cfg['input_dim']}\)"):
+            m._check_input(torch.zeros(2, 16))
+    m = HierCorrPool_bearing_model(**make_cfg(p=8, P=2, ns=4))
+    m._require_device = lambda x: None
+    for x in (torch.zeros(2, 16), torch.zeros(2, 2, 8), torch.zeros(2, 1, 16), torch.zeros(2, 4, 2, 2)):
+        assert m._check_input(x).shape == (2, 16)
+    with pytest.raises(RuntimeError, match="numel / batch == 16"):
+        m._check_input(torch.zeros(2, 17))
+
+
+def test_workspace_holds_the_block1_input_and_no_other_spectrogram():
+    """The workspace starts with the block-1 input [B][P + 8][C0] -- the spectrogram in the layout the convolutions read -- and block 1's
+    convolution output follows it directly: nothing else of spectrogram size ([B][P][N][f], or its transpose) lies between x and the
+    first product.  Regions are carved in order on 256-byte boundaries, and the taps are their float offsets."""
+    lib = _lib.load()
+    al = lambda floats: (floats + 63) // 64 * 64      # noqa: E731
+    for cfg in list(ROWS.values()) + [make_cfg(8, 7, 4, 2, 2, 12, 3)]:
+        P, N, f, h = (cfg[k] for k in ("num_patch", "num_nodes", "input_dim", "hidden_dim"))
+        C0 = N * f
+        for B in (1, 3, 100, 1024):
+            s = shape_of(B, cfg)
+            inp, z1, enc = (lib.rulgnn_hcpb_tap_offset(C.byref(s), i) for i in (4, 5, 0))
+            assert lib.rulgnn_hcpb_tap_offset(C.byref(s), 6) == -1
+            assert inp == 0 and z1 - inp == al(B * (P + 8) * C0)          # the input, then block 1's z: no gap a spectrogram would fit in
+            assert z1 - inp - B * (P + 8) * C0 < 64
+            assert enc > z1 + B * (P + 8) * h * N
+    # HierCorrPool itself has no such taps
+    hs = _lib.HiercorrpoolShape(3, 3, 7, 2, 2, 5, 12, 3)
+    assert lib.rulgnn_hiercorrpool_tap_offset(C.byref(hs), 4) == -1 and lib.rulgnn_hiercorrpool_tap_offset(C.byref(hs), 5) == -1
+
+
+def test_cpu_input_raises():
+    m = HierCorrPool_bearing_model(**make_cfg(8, 7, 4, 2, 2, 12, 3))
+    for x in (torch.zeros(2, 56), torch.zeros(2, 7, 8), torch.zeros(2, 1, 56)):
+        with pytest.raises(RuntimeError, match="HIP path only"):
+            m(x)
+    with pytest.raises(RuntimeError, match="HIP path only"):
+        m.fused_mse_step(torch.zeros(2, 56), torch.zeros(2))
+
+
+def test_fixtures_hold_no_grad_key_and_stay_under_the_size_limit():
+    """tests/test_grad_gate_cpu.py globs every fixture for ``grad:`` keys: this family's reference gradients are ``refgrad:``."""
+    files = sorted(glob.glob(os.path.join(GOLDEN, "hcpb_*.npz")))
+    assert len(files) == 6 and len(glob.glob(os.path.join(GOLDEN, "hiercorrpool_*.npz"))) == 7
+    for f in files:
+        assert not [k for k in np.load(f).files if k.startswith("grad:")], f
+        assert os.path.getsize(f) < 1 << 20, f
+    for name in SMALL + FORWARD_ONLY:
+        z = load_case(name)[0]
+        assert sorted(k[8:] for k in z if k.startswith("refgrad:")) == (sorted(O.param_names()) if name in SMALL else [])
+        assert {"x", "y", "pred", "pred_eval", "loss", "spec", "seed", "encoder", "pooled_x", "pooled_adj", "H"} <= set(z)

@@ -77,9 +77,14 @@ def trace(fn, x, y, steps):
     return sum(r[1] for r in rows) / steps, sum(r[2] for r in rows) / steps, [(k, c / steps, t / steps) for k, c, t in rows]
 
 
-def main():
+def batch(dev, cfg, B):
+    return torch.rand(B, cfg["num_nodes"], cfg["num_patch"] * cfg["patch_size"], device=dev), torch.rand(B, 1, device=dev)
+
+
+def main(shapes=("fd001", "fd004", "ncmapss"), config=config, fused_step_fn=fused_step_fn, torch_step_fn=torch_step_fn, make_batch=batch):
+    """``tools/time_hiercorrpool_bearing.py`` runs this with its own wirings, step functions and inputs."""
     ap = argparse.ArgumentParser()
-    ap.add_argument("--shapes", nargs="+", default=["fd001", "fd004", "ncmapss"])
+    ap.add_argument("--shapes", nargs="+", default=list(shapes))
     ap.add_argument("--batches", type=int, nargs="+", default=[100, 1024])
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=10)
@@ -99,7 +104,7 @@ def main():
         print(lines[-1], flush=True)
 
     def batch(cfg, B):
-        return torch.rand(B, cfg["num_nodes"], cfg["num_patch"] * cfg["patch_size"], device=dev), torch.rand(B, 1, device=dev)
+        return make_batch(dev, cfg, B)
 
     if args.trace:
         cfg, B = config(args.trace[0]), int(args.trace[1])
