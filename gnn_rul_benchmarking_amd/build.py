@@ -39,7 +39,7 @@ def needs_build() -> bool:
 
 
 OBJ_DIR = os.path.join(PKG_DIR, "..", "build", "obj")
-COMPILE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-c"]
+COMPILE_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Werror=unused-result", "-c"]
 # per-source additions.  stgcn_forward_mx.hip: the SLP vectoriser pairs scalar fp32 adds into v_pk_add_f32 and pays for it in
 # v_mov register shuffles (same FLOP rate on gfx950): measured 80 -> 73 us at batch 65536.
 EXTRA_FLAGS = {"stgcn_forward_mx.hip": ["-fno-slp-vectorize"], "stgcn_train_mx.hip": ["-fno-slp-vectorize"], "stgcn_train_mxw.hip": ["-fno-slp-vectorize"]}

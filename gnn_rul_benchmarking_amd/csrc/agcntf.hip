@@ -656,35 +656,31 @@ int Agcntf::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
                    ws + g.w_dpUs, ws + g.w_dGt, ws + g.w_dct, ws + g.w_dGs, ws + g.w_dcs, ws + g.w_XT};
     AtAttnBufs aq{ws + g.w_Q, ws + g.w_K, ws + g.w_V, ws + g.w_O, ws + g.w_lse, ws + g.w_rowdot, ws + g.w_part,
                   a->dpred ? a->dpred : ws + g.w_dpred, ws + g.w_dQ, ws + g.w_dK, ws + g.w_dV};
-    (void)hipGetLastError();
     if (mode & 1) {
         RULGNN_TRY(sagcn_features(g.B, g.P, g.n, a->x, ws + g.w_raw, ws + g.w_feat, st));
         RULGNN_TRY(allow_dynamic_lds(at_graph_kernel<false>, g.lds_graph_fwd));
-        hipLaunchKernelGGL(at_graph_kernel<false>, dim3(at_grid(g.B, 8192)), dim3(AT_GB), g.lds_graph_fwd, st, g, prm, gq);
-        RULGNN_LAUNCH_OK();
+        RULGNN_TRY(launch_checked(at_graph_kernel<false>, dim3(at_grid(g.B, 8192)), dim3(AT_GB), g.lds_graph_fwd, st, g, prm, gq));
         for (int h = 0; h < g.heads; ++h)
             for (int t = 0; t < 3; ++t)
                 RULGNN_TRY(sgemm(ws + g.w_H, Hg, 1, prm + g.o_head + h * g.head_stride + t * (Hg * Hg + Hg), Hg, 1, ws + qkv[t] + h * Hg, HD, BN, Hg,
                                  Hg, false, st));
         RULGNN_TRY(allow_dynamic_lds(at_attn_fwd_kernel, g.lds_attn_fwd));
-        hipLaunchKernelGGL(at_attn_fwd_kernel, dim3(at_grid(g.B * g.heads * g.nqt, 1 << 16)), dim3(AT_GB), g.lds_attn_fwd, st, g, prm, aq);
-        hipLaunchKernelGGL(at_head_finish_kernel, dim3(at_grid((g.B + AT_GB - 1) / AT_GB, 4096)), dim3(AT_GB), 0, st, g, (const float*)(ws + g.w_part),
-                           prm, a->y, a->pred, ws + g.w_sq, ws + g.w_dpred, 1.0f / (float)gb);
-        RULGNN_LAUNCH_OK();
+        RULGNN_TRY(launch_checked(at_attn_fwd_kernel, dim3(at_grid(g.B * g.heads * g.nqt, 1 << 16)), dim3(AT_GB), g.lds_attn_fwd, st, g, prm, aq));
+        RULGNN_TRY(launch_checked(at_head_finish_kernel, dim3(at_grid((g.B + AT_GB - 1) / AT_GB, 4096)), dim3(AT_GB), 0, st, g, (const float*)(ws + g.w_part),
+                                  prm, a->y, a->pred, ws + g.w_sq, ws + g.w_dpred, 1.0f / (float)gb));
         if (a->y && a->loss) RULGNN_TRY(block_sum((const float*)(ws + g.w_sq), g.B, a->loss, st));
     }
     if (mode & 2) {
         if (!a->grads) return RULGNN_EINVAL;
         float* gr = a->grads;
         RULGNN_TRY(fill_f32(ws + g.w_one, 1, 1.0f, st));
-        hipLaunchKernelGGL(at_fc_grad_kernel, dim3(at_grid(((int64_t)g.N * HD + AT_GB) / AT_GB, 8192)), dim3(AT_GB), 0, st, g, (const float*)(ws + g.w_O),
-                           aq.dpred, gr + g.o_wfc, gr + g.o_bfc);
+        RULGNN_TRY(launch_checked(at_fc_grad_kernel, dim3(at_grid(((int64_t)g.N * HD + AT_GB) / AT_GB, 8192)), dim3(AT_GB), 0, st, g, (const float*)(ws + g.w_O),
+                                  aq.dpred, gr + g.o_wfc, gr + g.o_bfc));
         RULGNN_TRY(allow_dynamic_lds(at_attn_bwd_kernel<false>, g.lds_attn_bwd));
         RULGNN_TRY(allow_dynamic_lds(at_attn_bwd_kernel<true>, g.lds_attn_bwd));
         const unsigned grid = at_grid(g.B * g.heads * g.nbt, 1 << 16);
-        hipLaunchKernelGGL(at_attn_bwd_kernel<false>, dim3(grid), dim3(AT_GB), g.lds_attn_bwd, st, g, prm, aq);
-        hipLaunchKernelGGL(at_attn_bwd_kernel<true>, dim3(grid), dim3(AT_GB), g.lds_attn_bwd, st, g, prm, aq);
-        RULGNN_LAUNCH_OK();
+        RULGNN_TRY(launch_checked(at_attn_bwd_kernel<false>, dim3(grid), dim3(AT_GB), g.lds_attn_bwd, st, g, prm, aq));
+        RULGNN_TRY(launch_checked(at_attn_bwd_kernel<true>, dim3(grid), dim3(AT_GB), g.lds_attn_bwd, st, g, prm, aq));
         // dH [B N, Hg] = sum over heads of dQ Wq + dK Wk + dV Wv
         const int64_t dq[3] = {g.w_dQ, g.w_dK, g.w_dV};
         for (int h = 0; h < g.heads; ++h)
@@ -692,8 +688,7 @@ int Agcntf::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
                 RULGNN_TRY(sgemm(ws + dq[t] + h * Hg, HD, 1, prm + g.o_head + h * g.head_stride + t * (Hg * Hg + Hg), 1, Hg, ws + g.w_dH, Hg, BN, Hg,
                                  Hg, h + t > 0, st));
         RULGNN_TRY(allow_dynamic_lds(at_graph_kernel<true>, g.lds_graph_bwd));
-        hipLaunchKernelGGL(at_graph_kernel<true>, dim3(at_grid(g.B, 8192)), dim3(AT_GB), g.lds_graph_bwd, st, g, prm, gq);
-        RULGNN_LAUNCH_OK();
+        RULGNN_TRY(launch_checked(at_graph_kernel<true>, dim3(at_grid(g.B, 8192)), dim3(AT_GB), g.lds_graph_bwd, st, g, prm, gq));
         SplitKJob jobs[12 + 6 * AT_MAXHEADS];
         const int nj = at_pgrad_jobs(g, ws, gr, jobs);
         for (int j0 = 0; j0 < nj; j0 += 10)

@@ -797,7 +797,6 @@ static int astgcnn_run_t(const rulgnn_astgcnn_shape* s, const rulgnn_astgcnn_arg
     const int N = g.N, T = g.T, E = g.E, O = g.O, KE = g.KE;
     const int M = (int)(g.B * N);
     const float inv_gb = 1.0f / (float)(a->global_batch > 0 ? a->global_batch : g.B);
-    (void)hipGetLastError();
     // reduction pair `blk` (forward or backward) is complete behind the launch just enqueued: 2 MAXN contiguous doubles of every replica
     constexpr int PAIR = 2 * MAXN, FWD0 = offsetof(Cells, fwd) / sizeof(double), BWD0 = offsetof(Cells, bwd) / sizeof(double);
     static_assert(FWD0 == 0 && BWD0 == 2 * PAIR && sizeof(Cells) == sizeof(double) * 4 * PAIR, "Cells: fwd[2] then bwd[2] pairs of doubles");
@@ -808,25 +807,25 @@ static int astgcnn_run_t(const rulgnn_astgcnn_shape* s, const rulgnn_astgcnn_arg
     // aux_stream.hpp) they run beside the TCN backward, forked behind the graph-backward kernel's own completion signal.
     AuxFork fk(st, (mode & 2) ? a->aux_stream : nullptr);
     if (mode & 1) {
-        hipLaunchKernelGGL(ast_prepare_kernel, dim3(1), dim3(1024), 0, st, cells, F(w.one));
+        RULGNN_TRY(launch_checked(ast_prepare_kernel, dim3(1), dim3(1024), 0, st, cells, F(w.one)));
         const int rows = resident_rows((tcn_conv_kernel<1, AstGeom, SN, SE, TTB>), TTB, 0, g.B, 1 << 20);
-        hipLaunchKernelGGL((tcn_conv_kernel<1, AstGeom, SN, SE, TTB>), dim3(rows), dim3(TTB), 0, st, g, a->x, prm, a->bn_stats, training, (const float*)nullptr,
-                           F(w.z1), (float*)nullptr, cells);
+        RULGNN_TRY(launch_checked((tcn_conv_kernel<1, AstGeom, SN, SE, TTB>), dim3(rows), dim3(TTB), 0, st, g, a->x, prm, a->bn_stats, training, (const float*)nullptr,
+                                  F(w.z1), (float*)nullptr, cells));
         RULGNN_TRY(sync_pair(0, 0));
-        hipLaunchKernelGGL((tcn_conv_kernel<2, AstGeom, SN, SE, TTB>), dim3(rows), dim3(TTB), 0, st, g, a->x, prm, a->bn_stats, training, (const float*)F(w.z1),
-                           F(w.z2), F(w.out0), cells);
+        RULGNN_TRY(launch_checked((tcn_conv_kernel<2, AstGeom, SN, SE, TTB>), dim3(rows), dim3(TTB), 0, st, g, a->x, prm, a->bn_stats, training, (const float*)F(w.z1),
+                                  F(w.z2), F(w.out0), cells));
         RULGNN_TRY(sync_pair(0, 1));
         // gate, P projection, graph, Chebyshev terms, node sums, the filter product and the head: one launch (ast_front_kernel)
-        hipLaunchKernelGGL((ast_front_kernel<SN, SE, SO>), dim3(resident_rows((ast_front_kernel<SN, SE, SO>), AB, 0, g.B, 1 << 20)), dim3(AB), 0, st, g, a->x, prm, a->bn_stats, training,
-                           (const Cells*)cells, (const float*)F(w.z2), (const float*)F(w.out0), F(w.zpre), F(w.out1), F(w.tcat), F(w.px), F(w.adj),
-                           F(w.dist), F(w.scat), F(w.pooled), a->y, a->pred, F(w.dpred), F(w.sqerr), F(w.dmat), inv_gb);
+        RULGNN_TRY(launch_checked((ast_front_kernel<SN, SE, SO>), dim3(resident_rows((ast_front_kernel<SN, SE, SO>), AB, 0, g.B, 1 << 20)), dim3(AB), 0, st, g, a->x, prm, a->bn_stats, training,
+                                  (const Cells*)cells, (const float*)F(w.z2), (const float*)F(w.out0), F(w.zpre), F(w.out1), F(w.tcat), F(w.px), F(w.adj),
+                                  F(w.dist), F(w.scat), F(w.pooled), a->y, a->pred, F(w.dpred), F(w.sqerr), F(w.dmat), inv_gb));
         if (training && a->bn_batch && !(mode & 2))            // (with a backward in the same call: beside its chain, below)
-            hipLaunchKernelGGL(ast_bn_batch_kernel, dim3(1), dim3(64), 0, st, g, (const Cells*)cells, a->bn_batch, a->bn_moment_weight);
+            RULGNN_TRY(launch_checked(ast_bn_batch_kernel, dim3(1), dim3(64), 0, st, g, (const Cells*)cells, a->bn_batch, a->bn_moment_weight));
     }
     if (mode & 2) {
         if (a->dpred)          // external d loss / d pred (autograd): D = dpred fc.weight / N
-            hipLaunchKernelGGL(ast_head_kernel, dim3((unsigned)((g.B + 3) / 4 > 2048 ? 2048 : (g.B + 3) / 4)), dim3(AB), 0, st, g, prm,
-                               F(w.pooled), (const float*)nullptr, a->dpred, a->pred, F(w.dpred), F(w.sqerr), F(w.dmat), inv_gb, 1);
+            RULGNN_TRY(launch_checked(ast_head_kernel, dim3((unsigned)((g.B + 3) / 4 > 2048 ? 2048 : (g.B + 3) / 4)), dim3(AB), 0, st, g, prm,
+                                      F(w.pooled), (const float*)nullptr, a->dpred, a->pred, F(w.dpred), F(w.sqerr), F(w.dmat), inv_gb, 1));
         float* gr = a->grads;
         float* split = F(w.split);
         hipStream_t wst = fk.side();
@@ -838,9 +837,9 @@ static int astgcnn_run_t(const rulgnn_astgcnn_shape* s, const rulgnn_astgcnn_arg
         // DT = D Fcat^T, the graph backward, dG = dG_cheb + dPX P and the gate backward (BatchNorm-2 sums): one launch
         const int bwd_rows = resident_rows((ast_graph_bwd_kernel<SN, SE, SO>), AB, 0, g.B, AST_BWD_ROWS);
         hipEvent_t bwd_done = fk.stop_event();                       // (the fork point: behind this kernel)
-        RULGNN_LAUNCH_EV(bwd_done, (ast_graph_bwd_kernel<SN, SE, SO>), dim3(bwd_rows), dim3(AB), 0, st, g, prm,
-                         (const float*)F(w.px), (const float*)F(w.tcat), (const float*)F(w.adj), (const float*)F(w.dist), (const float*)F(w.dmat),
-                         F(w.dpx), cells, (const float*)F(w.z2), (const float*)F(w.out1), F(w.zpre), F(w.ds1), F(w.dy2), F(w.thb));
+        RULGNN_TRY(launch_checked_ev(bwd_done, (ast_graph_bwd_kernel<SN, SE, SO>), dim3(bwd_rows), dim3(AB), 0, st, g, prm,
+                                     (const float*)F(w.px), (const float*)F(w.tcat), (const float*)F(w.adj), (const float*)F(w.dist), (const float*)F(w.dmat),
+                                     F(w.dpx), cells, (const float*)F(w.z2), (const float*)F(w.out1), F(w.zpre), F(w.ds1), F(w.dy2), F(w.thb)));
         // The five parameter-gradient products -- d fc.weight[o] = sum_b dpred[b] pooled[b][o], d fc.bias = sum_b dpred[b],
         // d filters = Scat^T D, d P = dPX^T G, d theta.weight = dZpre^T x -- as ONE split-K launch + ONE reduction (sgemm_splitk_batch).
         // As nine launches (5-8 us each, at their latency floor) they needed a side stream from the front kernel on -- two forks and a join,
@@ -859,11 +858,11 @@ static int astgcnn_run_t(const rulgnn_astgcnn_shape* s, const rulgnn_astgcnn_arg
         }
         const int rows = resident_rows((tcn_conv_bwd_kernel<2, AstGeom, SN, SE, TTB>), TTB, 0, g.B, w.rows);
         RULGNN_TRY(sync_pair(1, 1));
-        hipLaunchKernelGGL((tcn_conv_bwd_kernel<2, AstGeom, SN, SE, TTB>), dim3(rows), dim3(TTB), 0, st, g, prm, cells, (const float*)F(w.z2), (const float*)F(w.dy2),
-                           (const float*)F(w.out0), (const float*)F(w.ds1), (const float*)F(w.z1), F(w.dy1), F(w.gp2));
+        RULGNN_TRY(launch_checked((tcn_conv_bwd_kernel<2, AstGeom, SN, SE, TTB>), dim3(rows), dim3(TTB), 0, st, g, prm, cells, (const float*)F(w.z2), (const float*)F(w.dy2),
+                                  (const float*)F(w.out0), (const float*)F(w.ds1), (const float*)F(w.z1), F(w.dy1), F(w.gp2)));
         RULGNN_TRY(sync_pair(1, 0));
-        hipLaunchKernelGGL((tcn_conv_bwd_kernel<1, AstGeom, SN, SE, TTB>), dim3(rows), dim3(TTB), 0, st, g, prm, cells, (const float*)F(w.z1), (const float*)F(w.dy1),
-                           a->x, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, F(w.gp1));
+        RULGNN_TRY(launch_checked((tcn_conv_bwd_kernel<1, AstGeom, SN, SE, TTB>), dim3(rows), dim3(TTB), 0, st, g, prm, cells, (const float*)F(w.z1), (const float*)F(w.dy1),
+                                  a->x, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, F(w.gp1)));
         AstFin fin;
         fin.cells = cells; fin.grads = gr; fin.bn_scale = sync ? sync->bn_param_grad_scale : 1.0f;
         fin.bn_batch = ((mode & 1) && training) ? a->bn_batch : (float*)nullptr;
@@ -887,8 +886,7 @@ static int astgcnn_run_t(const rulgnn_astgcnn_shape* s, const rulgnn_astgcnn_arg
                 ad.gbase = gr;
                 adam->gbase = gr;
             }
-            hipLaunchKernelGGL(ast_tail_kernel, dim3(rb.first[rb.n] + 2 * nb01 + nb2 + 1), dim3(1024), 0, st, g, fin, jb, nb01, nb01, nb2, rb, ad);
-            return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+            return launch_checked(ast_tail_kernel, dim3(rb.first[rb.n] + 2 * nb01 + nb2 + 1), dim3(1024), 0, st, g, fin, jb, nb01, nb01, nb2, rb, ad);
         }
         // both convolutions' partial weight rows in one launch (the second used to sit between the two backward kernels)
         // ... and the gate's bias gradient (the graph backward's partial rows; theta.bias and gate.bias share it)
@@ -896,10 +894,10 @@ static int astgcnn_run_t(const rulgnn_astgcnn_shape* s, const rulgnn_astgcnn_arg
                          bwd_rows, (int64_t)E, E, st));
         // (the finalize kernel reads the cells and the squared errors only -- nothing the side stream writes: it runs in front of the join,
         // beside the side stream's last product, instead of behind the wake-up of a stream that sat waiting)
-        hipLaunchKernelGGL(ast_finalize_kernel, dim3(1), dim3(AB), 0, st, g, fin);
+        RULGNN_TRY(launch_checked(ast_finalize_kernel, dim3(1), dim3(AB), 0, st, g, fin));
         RULGNN_TRY(fk.join());
     }
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return RULGNN_OK;
 }
 
 int Astgcnn::run(const Shape* s, const Args* a, int mode, hipStream_t st, const SyncHook* sync, float* bn_running_out,
@@ -916,9 +914,7 @@ int Astgcnn::bn_running_update(const Shape* s, float* bn_stats, const float* bn_
                               int from_moments, hipStream_t st) {
     AstGeom g;
     RULGNN_TRY(ast_geometry(s, &g));
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(ast_bn_running_kernel, dim3(1), dim3(64), 0, st, bn_stats, bn_batch, g.N, (double)count, momentum, from_moments);
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return launch_checked(ast_bn_running_kernel, dim3(1), dim3(64), 0, st, bn_stats, bn_batch, g.N, (double)count, momentum, from_moments);
 }
 
 }  // namespace rulgnn

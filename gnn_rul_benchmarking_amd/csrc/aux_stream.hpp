@@ -12,6 +12,7 @@
 #include <hip/hip_ext.h>
 
 #include "../../include/rulgnn.h"
+#include "launch.hpp"
 
 namespace rulgnn {
 
@@ -53,7 +54,7 @@ struct AuxFork {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         if (active() && (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone)) capturing = true;
     }
-    // The fork point is "behind THIS kernel": stop_event() before the launch, the launch through RULGNN_LAUNCH_EV with it, fork_after()
+    // The fork point is "behind THIS kernel": stop_event() before the launch, the launch through launch_checked_ev with it, fork_after()
     // behind it.  Without a side stream, or inside a capture, stop_event() is null and the three reduce to a plain launch + fork().
     hipEvent_t stop_event() { return (active() && !capturing && rc == RULGNN_OK) ? aux_pooled_stop_event() : nullptr; }
     void fork_after(hipEvent_t ev) {
@@ -88,11 +89,13 @@ struct AuxFork {
     }
 };
 
-// launch on `stream` with `ev` (may be null) signalled by the kernel's completion
-#define RULGNN_LAUNCH_EV(ev, kernel, grid, block, lds, stream, ...)                                                     \
-    do {                                                                                                                \
-        if (ev) hipExtLaunchKernelGGL(kernel, grid, block, lds, stream, nullptr, ev, 0, __VA_ARGS__);                   \
-        else hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);                                         \
-    } while (0)
+// launch_checked on `stream` with `ev` (may be null) signalled by the kernel's completion
+template <typename... P, typename... A>
+[[nodiscard]] inline int launch_checked_ev(hipEvent_t ev, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, const A&... args) {
+    if (!ev) return launch_checked(kernel, grid, block, lds, stream, args...);
+    (void)hipGetLastError();
+    hipExtLaunchKernelGGL(kernel, grid, block, lds, stream, nullptr, ev, 0, args...);
+    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+}
 
 }  // namespace rulgnn

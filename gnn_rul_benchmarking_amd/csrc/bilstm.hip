@@ -363,7 +363,6 @@ int bilstm_forward(const rulgnn_bilstm_shape* s, const rulgnn_bilstm_args* a, hi
     RULGNN_TRY(lstm_geometry(s, &g));
     if (a->workspace_bytes < (size_t)g.total * sizeof(float)) return RULGNN_EWORKSPACE;
     float* ws = static_cast<float*>(a->workspace);
-    (void)hipGetLastError();
     const int R = (int)g.rows;
     // input projections of both directions: gi[dir] = x W_ih[dir]^T   ([rows, I] x [I, 4H])
     if (ndir != 1 && ndir != 2) return RULGNN_EINVAL;
@@ -372,17 +371,16 @@ int bilstm_forward(const rulgnn_bilstm_shape* s, const rulgnn_bilstm_args* a, hi
     const int threads = (g.H4 + 63) & ~63;
     const int d1 = ndir == 2 ? 1 : 0;                 // the one-direction launch never selects direction 1
     auto fwd = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(ndir * g.Bq), dim3(threads), 0, st, g, (const float*)(ws + g.o_gi), a->w_hh[0], a->w_hh[d1], a->b_ih[0],
-                           a->b_hh[0], a->b_ih[d1], a->b_hh[d1], ws + g.o_gates, ws + g.o_c, ws + g.o_h, ws + g.o_hprev, ws + g.o_tc);
+        return launch_checked(kernel, dim3(ndir * g.Bq), dim3(threads), 0, st, g, (const float*)(ws + g.o_gi), a->w_hh[0], a->w_hh[d1], a->b_ih[0],
+                              a->b_hh[0], a->b_ih[d1], a->b_hh[d1], ws + g.o_gates, ws + g.o_c, ws + g.o_h, ws + g.o_hprev, ws + g.o_tc);
     };
     // (the mask-free form serves every width: lanes beyond it repeat unit H - 1; HAGCN's widths also skip the products beyond them)
-    if (g.H == 60) fwd(lstm_forward_kernel<64, true, 60>);
-    else if (g.H <= 64) fwd(lstm_forward_kernel<64, true>);
-    else if (g.H == 120) fwd(lstm_forward_kernel<128, true, 120>);
-    else fwd(lstm_forward_kernel<128, true>);
-    if (ndir == 2) hipLaunchKernelGGL(lstm_sum_kernel, dim3(1024), dim3(256), 0, st, g, (const float*)(ws + g.o_h), a->out);
-    else hipLaunchKernelGGL(lstm_copy_kernel, dim3((unsigned)((g.rows * g.H + 255) / 256)), dim3(256), 0, st, (const float*)(ws + g.o_h), a->out, (int)(g.rows * g.H));
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    if (g.H == 60) RULGNN_TRY(fwd(lstm_forward_kernel<64, true, 60>));
+    else if (g.H <= 64) RULGNN_TRY(fwd(lstm_forward_kernel<64, true>));
+    else if (g.H == 120) RULGNN_TRY(fwd(lstm_forward_kernel<128, true, 120>));
+    else RULGNN_TRY(fwd(lstm_forward_kernel<128, true>));
+    if (ndir == 2) return launch_checked(lstm_sum_kernel, dim3(1024), dim3(256), 0, st, g, (const float*)(ws + g.o_h), a->out);
+    return launch_checked(lstm_copy_kernel, dim3((unsigned)((g.rows * g.H + 255) / 256)), dim3(256), 0, st, (const float*)(ws + g.o_h), a->out, (int)(g.rows * g.H));
 }
 
 int bilstm_backward(const rulgnn_bilstm_shape* s, const rulgnn_bilstm_args* a, hipStream_t st, int ndir) {
@@ -390,19 +388,18 @@ int bilstm_backward(const rulgnn_bilstm_shape* s, const rulgnn_bilstm_args* a, h
     RULGNN_TRY(lstm_geometry(s, &g));
     if (a->workspace_bytes < (size_t)g.total * sizeof(float)) return RULGNN_EWORKSPACE;
     float* ws = static_cast<float*>(a->workspace);
-    (void)hipGetLastError();
     const int R = (int)g.rows, H = g.H, H4 = g.H4, I = g.I;
     const int threads = (H4 + 63) & ~63;
     if (ndir != 1 && ndir != 2) return RULGNN_EINVAL;
     const int d1 = ndir == 2 ? 1 : 0;
     auto bwd = [&](auto kernel) {
-        hipLaunchKernelGGL(kernel, dim3(ndir * g.Bq), dim3(threads), 0, st, g, a->w_hh[0], a->w_hh[d1], (const float*)(ws + g.o_gates),
-                           (const float*)(ws + g.o_c), (const float*)(ws + g.o_tc), a->dout, ws + g.o_dgates);
+        return launch_checked(kernel, dim3(ndir * g.Bq), dim3(threads), 0, st, g, a->w_hh[0], a->w_hh[d1], (const float*)(ws + g.o_gates),
+                              (const float*)(ws + g.o_c), (const float*)(ws + g.o_tc), a->dout, ws + g.o_dgates);
     };
-    if (H == 60) bwd(lstm_backward_kernel<64, true, 60>);
-    else if (H <= 64) bwd(lstm_backward_kernel<64, true>);
-    else if (H == 120) bwd(lstm_backward_kernel<128, true, 120>);
-    else bwd(lstm_backward_kernel<128, true>);
+    if (H == 60) RULGNN_TRY(bwd(lstm_backward_kernel<64, true, 60>));
+    else if (H <= 64) RULGNN_TRY(bwd(lstm_backward_kernel<64, true>));
+    else if (H == 120) RULGNN_TRY(bwd(lstm_backward_kernel<128, true, 120>));
+    else RULGNN_TRY(bwd(lstm_backward_kernel<128, true>));
     float* one = ws + g.o_one;
     float* split = ws + g.o_split;
     RULGNN_TRY(fill_f32(one, 1, 1.f, st));
@@ -434,7 +431,7 @@ int bilstm_backward(const rulgnn_bilstm_shape* s, const rulgnn_bilstm_args* a, h
     else
         for (int j = 0; j < nj; ++j)
             if (hipMemsetAsync(jobs[j].C, 0, sizeof(float) * (size_t)jobs[j].M * jobs[j].N, wst) != hipSuccess) return RULGNN_EHIP;
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return RULGNN_OK;
 }
 
 }  // namespace rulgnn

@@ -31,10 +31,10 @@ struct StepFamily {
 struct Stmsgcn : StepFamily<rulgnn_stmsgcn_shape, rulgnn_stmsgcn_args> {
     static int64_t param_count(const Shape* s);
     static size_t workspace_bytes(const Shape* s);
-    static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
-    static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
+    [[nodiscard]] static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
+    [[nodiscard]] static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
 };
-int stmsgcn_features(const rulgnn_stmsgcn_shape* s, const float* x, const float* prm, float* features, hipStream_t stream);
+[[nodiscard]] int stmsgcn_features(const rulgnn_stmsgcn_shape* s, const float* x, const float* prm, float* features, hipStream_t stream);
 
 // The BatchNorm families (ASTGCNN, FC_STGNN, ST_Conv) share their argument check and fused step (rulgnn_api.hip: check_bn_args,
 // bn_step_fwdbwd).  On top of a step family's members:
@@ -50,12 +50,12 @@ struct Astgcnn : StepFamily<rulgnn_astgcnn_shape, rulgnn_astgcnn_args> {
     static constexpr bool run_takes_optimizer = true;
     static int64_t param_count(const Shape* s);
     static size_t workspace_bytes(const Shape* s);
-    static int run(const Shape* s, const Args* a, int mode, hipStream_t st, const SyncHook* sync = nullptr, float* bn_running_out = nullptr,
+    [[nodiscard]] static int run(const Shape* s, const Args* a, int mode, hipStream_t st, const SyncHook* sync = nullptr, float* bn_running_out = nullptr,
                    float bn_momentum = 0.f, AdamFuse* adam = nullptr);
-    static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
-    static int bn_running_update(const Shape* s, float* bn_stats, const float* bn_batch, int64_t count, float momentum, int from_moments,
+    [[nodiscard]] static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
+    [[nodiscard]] static int bn_running_update(const Shape* s, float* bn_stats, const float* bn_batch, int64_t count, float momentum, int from_moments,
                                  hipStream_t st);
-    static int step_bn_update(const Shape* s, float* bn_stats, const float* bn_batch, float momentum, int from_moments, hipStream_t st) {
+    [[nodiscard]] static int step_bn_update(const Shape* s, float* bn_stats, const float* bn_batch, float momentum, int from_moments, hipStream_t st) {
         return bn_running_update(s, bn_stats, bn_batch, s->batch * (int64_t)s->time_length, momentum, from_moments, st);
     }
 };
@@ -65,11 +65,11 @@ struct Fcstgnn : StepFamily<rulgnn_fcstgnn_shape, rulgnn_fcstgnn_args> {
     static int64_t param_count(const Shape* s);
     static int64_t bn_count(const Shape* s);
     static size_t workspace_bytes(const Shape* s);
-    static int run(const Shape* s, const Args* a, int mode, hipStream_t st, const SyncHook* sync = nullptr, float* bn_running_out = nullptr,
+    [[nodiscard]] static int run(const Shape* s, const Args* a, int mode, hipStream_t st, const SyncHook* sync = nullptr, float* bn_running_out = nullptr,
                    float bn_momentum = 0.f, const AdamFuse* adam = nullptr);
-    static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
-    static int bn_running_update(const Shape* s, float* bn_stats, const float* bn_batch, float momentum, int from_moments, hipStream_t st);
-    static int step_bn_update(const Shape* s, float* bn_stats, const float* bn_batch, float momentum, int from_moments, hipStream_t st) {
+    [[nodiscard]] static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
+    [[nodiscard]] static int bn_running_update(const Shape* s, float* bn_stats, const float* bn_batch, float momentum, int from_moments, hipStream_t st);
+    [[nodiscard]] static int step_bn_update(const Shape* s, float* bn_stats, const float* bn_batch, float momentum, int from_moments, hipStream_t st) {
         return bn_running_update(s, bn_stats, bn_batch, momentum, from_moments, st);          // (the element counts are the shape's)
     }
 };
@@ -78,177 +78,177 @@ struct Stconv : StepFamily<rulgnn_stconv_shape, rulgnn_astgcnn_args> {
     static constexpr bool run_takes_optimizer = false;
     static int64_t param_count(const Shape* s);
     static size_t workspace_bytes(const Shape* s);
-    static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
-    static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
-    static int bn_running_update(const Shape* s, float* bn_stats, const float* bn_batch, int64_t count, float momentum, int from_moments,
+    [[nodiscard]] static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
+    [[nodiscard]] static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
+    [[nodiscard]] static int bn_running_update(const Shape* s, float* bn_stats, const float* bn_batch, int64_t count, float momentum, int from_moments,
                                  hipStream_t st);
-    static int step_bn_update(const Shape* s, float* bn_stats, const float* bn_batch, float momentum, int from_moments, hipStream_t st) {
+    [[nodiscard]] static int step_bn_update(const Shape* s, float* bn_stats, const float* bn_batch, float momentum, int from_moments, hipStream_t st) {
         return bn_running_update(s, bn_stats, bn_batch, s->batch * (int64_t)s->time_length, momentum, from_moments, st);
     }
 };
 
 // (the args struct is STMSGCN's; workspace_bytes is the step's -- stgnn_workspace_bytes below is that of the terms / cheb entries)
 struct Stgnn : StepFamily<rulgnn_stgnn_shape, rulgnn_stmsgcn_args> {
-    static int shape_status(const Shape* s);
+    [[nodiscard]] static int shape_status(const Shape* s);
     static int64_t param_count(const Shape* s);
     static size_t workspace_bytes(const Shape* s);
-    static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
-    static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
+    [[nodiscard]] static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
+    [[nodiscard]] static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
 };
 struct Stnet : StepFamily<rulgnn_stnet_shape, rulgnn_stnet_args> {
     // cnn.{weight, bias} (the first 3 entries) have no gradient in the reference (`grad is None`): torch's Adam leaves them untouched
     static int64_t adam_first(const Shape*) { return 3; }
-    static int shape_status(const Shape* s);
+    [[nodiscard]] static int shape_status(const Shape* s);
     static int64_t param_count(const Shape* s);
     static size_t workspace_bytes(const Shape* s);
-    static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
-    static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
+    [[nodiscard]] static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
+    [[nodiscard]] static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
 };
 struct Sagcn : StepFamily<rulgnn_sagcn_shape, rulgnn_sagcn_args> {
-    static int shape_status(const Shape* s);
+    [[nodiscard]] static int shape_status(const Shape* s);
     static int64_t param_count(const Shape* s);
     static size_t workspace_bytes(const Shape* s);
     static int64_t tap_offset(const Shape* s, int which);
-    static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
-    static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
+    [[nodiscard]] static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
+    [[nodiscard]] static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
 };
 // SAGCN's parameter-free front end alone: x [B][P * n] -> raw [B * P][20] (scratch) -> features [B][P][40] (unit Frobenius norm)
-int sagcn_features(int64_t B, int P, int n, const float* x, float* raw, float* feat, hipStream_t st);
+[[nodiscard]] int sagcn_features(int64_t B, int P, int n, const float* x, float* raw, float* feat, hipStream_t st);
 struct Agcntf : StepFamily<rulgnn_agcntf_shape, rulgnn_agcntf_args> {
-    static int shape_status(const Shape* s);
+    [[nodiscard]] static int shape_status(const Shape* s);
     static int64_t param_count(const Shape* s);
     static size_t workspace_bytes(const Shape* s);
     static int64_t tap_offset(const Shape* s, int which);
-    static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
-    static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
+    [[nodiscard]] static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
+    [[nodiscard]] static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
 };
 struct Stagnn : StepFamily<rulgnn_stagnn_shape, rulgnn_stagnn_args> {
-    static int shape_status(const Shape* s);
+    [[nodiscard]] static int shape_status(const Shape* s);
     static int64_t param_count(const Shape* s);
     static int64_t bn_state_count(const Shape* s);
     static size_t workspace_bytes(const Shape* s);
     static int64_t tap_offset(const Shape* s, int which);
-    static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
-    static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
+    [[nodiscard]] static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
+    [[nodiscard]] static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
 };
 struct Rgcnu : StepFamily<rulgnn_rgcnu_shape, rulgnn_rgcnu_args> {
     // the second head (fc2, the last E*L + 1 entries) has no gradient in the reference (`grad is None`): torch's Adam leaves it untouched
     static int64_t adam_frozen_tail(const Shape* s) { return (int64_t)s->encoder_hidden_dim * s->time_length + 1; }
-    static int shape_status(const Shape* s);
+    [[nodiscard]] static int shape_status(const Shape* s);
     static int64_t param_count(const Shape* s);
     static size_t workspace_bytes(const Shape* s);
-    static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
-    static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
+    [[nodiscard]] static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
+    [[nodiscard]] static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
 };
 struct Grucm : StepFamily<rulgnn_grucm_shape, rulgnn_grucm_args> {
-    static int shape_status(const Shape* s);
+    [[nodiscard]] static int shape_status(const Shape* s);
     static int64_t param_count(const Shape* s);
     static size_t workspace_bytes(const Shape* s);
-    static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
-    static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
+    [[nodiscard]] static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
+    [[nodiscard]] static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
 };
 struct Hiercorrpool : StepFamily<rulgnn_hiercorrpool_shape, rulgnn_hiercorrpool_args> {
-    static int shape_status(const Shape* s);
+    [[nodiscard]] static int shape_status(const Shape* s);
     static int64_t param_count(const Shape* s);
     static int64_t bn_state_count(const Shape* s);
     static size_t workspace_bytes(const Shape* s);
     static int64_t tap_offset(const Shape* s, int which);
-    static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
-    static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
+    [[nodiscard]] static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
+    [[nodiscard]] static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
 };
 // (the args struct is HierCorrPool's; x is the raw window [batch][num_patch * patch_size])
 struct Hcpb : StepFamily<rulgnn_hcpb_shape, rulgnn_hiercorrpool_args> {
-    static int shape_status(const Shape* s);
+    [[nodiscard]] static int shape_status(const Shape* s);
     static int64_t param_count(const Shape* s);
     static int64_t bn_state_count(const Shape* s);
     static size_t workspace_bytes(const Shape* s);
     static int64_t tap_offset(const Shape* s, int which);
-    static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
-    static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
+    [[nodiscard]] static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
+    [[nodiscard]] static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
 };
 struct Logo : StepFamily<rulgnn_logo_shape, rulgnn_logo_args> {
-    static int shape_status(const Shape* s);
+    [[nodiscard]] static int shape_status(const Shape* s);
     static int64_t param_count(const Shape* s);
     static size_t workspace_bytes(const Shape* s);
     static int64_t tap_offset(const Shape* s, int which);
-    static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
-    static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
+    [[nodiscard]] static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
+    [[nodiscard]] static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
 };
 // (the args struct is LOGO's; x is the raw window [batch][num_patch * patch_size])
 struct Logob : StepFamily<rulgnn_logob_shape, rulgnn_logo_args> {
-    static int shape_status(const Shape* s);
+    [[nodiscard]] static int shape_status(const Shape* s);
     static int64_t param_count(const Shape* s);
     static size_t workspace_bytes(const Shape* s);
     static int64_t tap_offset(const Shape* s, int which);
-    static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
-    static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
+    [[nodiscard]] static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
+    [[nodiscard]] static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
 };
 struct Dvgtformer : StepFamily<rulgnn_dvgtformer_shape, rulgnn_dvgtformer_args> {
-    static int shape_status(const Shape* s);
+    [[nodiscard]] static int shape_status(const Shape* s);
     static int64_t param_count(const Shape* s);
     static size_t workspace_bytes(const Shape* s);
     static int64_t tap_offset(const Shape* s, int which);
-    static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
-    static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
+    [[nodiscard]] static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
+    [[nodiscard]] static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
 };
 struct Gdagdl : StepFamily<rulgnn_gdagdl_shape, rulgnn_gdagdl_args> {
     // node_importance_linear.{weight, bias} (the first f + 1 entries) have no gradient in the reference: torch's Adam leaves them untouched
     static int64_t adam_first(const Shape* s);
-    static int shape_status(const Shape* s);
+    [[nodiscard]] static int shape_status(const Shape* s);
     static int64_t param_count(const Shape* s);
     static size_t workspace_bytes(const Shape* s);
     static int64_t tap_offset(const Shape* s, int which);
-    static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
-    static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
+    [[nodiscard]] static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
+    [[nodiscard]] static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
 };
 struct Gatlstm : StepFamily<rulgnn_gatlstm_shape, rulgnn_gatlstm_args> {
-    static int shape_status(const Shape* s);
+    [[nodiscard]] static int shape_status(const Shape* s);
     static int64_t param_count(const Shape* s);
     static size_t workspace_bytes(const Shape* s);
     static int64_t tap_offset(const Shape* s, int which);
-    static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
-    static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
+    [[nodiscard]] static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
+    [[nodiscard]] static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
 };
 
 int64_t hagcn_graph_param_count(const rulgnn_hagcn_shape* s);
 size_t hagcn_workspace_bytes(const rulgnn_hagcn_shape* s);
-int hagcn_graph_forward(const rulgnn_hagcn_shape* s, const rulgnn_hagcn_args* a, hipStream_t stream);
-int hagcn_graph_backward(const rulgnn_hagcn_shape* s, const rulgnn_hagcn_args* a, hipStream_t stream);
+[[nodiscard]] int hagcn_graph_forward(const rulgnn_hagcn_shape* s, const rulgnn_hagcn_args* a, hipStream_t stream);
+[[nodiscard]] int hagcn_graph_backward(const rulgnn_hagcn_shape* s, const rulgnn_hagcn_args* a, hipStream_t stream);
 size_t bilstm_workspace_bytes(const rulgnn_bilstm_shape* s);
-int bilstm_forward(const rulgnn_bilstm_shape* s, const rulgnn_bilstm_args* a, hipStream_t stream, int ndir = 2);
-int bilstm_backward(const rulgnn_bilstm_shape* s, const rulgnn_bilstm_args* a, hipStream_t stream, int ndir = 2);
-int adam_step(float* p, const float* g, float* m, float* v, int64_t n, int64_t step, float lr, float beta1, float beta2,
+[[nodiscard]] int bilstm_forward(const rulgnn_bilstm_shape* s, const rulgnn_bilstm_args* a, hipStream_t stream, int ndir = 2);
+[[nodiscard]] int bilstm_backward(const rulgnn_bilstm_shape* s, const rulgnn_bilstm_args* a, hipStream_t stream, int ndir = 2);
+[[nodiscard]] int adam_step(float* p, const float* g, float* m, float* v, int64_t n, int64_t step, float lr, float beta1, float beta2,
               float eps, float wd, float gscale, hipStream_t stream, void* step_state = nullptr, const float* guard = nullptr);
 // Synchronised BatchNorm, the one step behind every launch that completes a reduction pair (bn_cells.hpp): the CELL_REP replicas of the
 // `n` <= 128 contiguous doubles at cells + off (the replicas `replica_stride` doubles apart) are collapsed into replica 0, then
 // h->fn runs on cells + off.  RULGNN_OK at once when `h` is null; RULGNN_EHIP / RULGNN_ECALLBACK.
-int sync_cells(const SyncHook* h, double* cells, int off, int n, int replica_stride, hipStream_t st);
+[[nodiscard]] int sync_cells(const SyncHook* h, double* cells, int off, int n, int replica_stride, hipStream_t st);
 // p[0 .. n) = v
-int fill_f32(float* p, int64_t n, float v, hipStream_t st);
-int step_state_set(void* state, uint64_t dropout_step, int64_t adam_step, hipStream_t stream);
-int step_prepare_dropout(void* state, uint64_t seed, int num_layers, hipStream_t stream);   // ++dropout_step, keys
-int step_prepare_adam(void* state, float lr, float beta1, float beta2, hipStream_t stream); // ++adam_step, bias corrections
-int bn_running_update(float* bn, const float* batch, int num_layers, int64_t count, float momentum, int from_moments,
+[[nodiscard]] int fill_f32(float* p, int64_t n, float v, hipStream_t st);
+[[nodiscard]] int step_state_set(void* state, uint64_t dropout_step, int64_t adam_step, hipStream_t stream);
+[[nodiscard]] int step_prepare_dropout(void* state, uint64_t seed, int num_layers, hipStream_t stream);   // ++dropout_step, keys
+[[nodiscard]] int step_prepare_adam(void* state, float lr, float beta1, float beta2, hipStream_t stream); // ++adam_step, bias corrections
+[[nodiscard]] int bn_running_update(float* bn, const float* batch, int num_layers, int64_t count, float momentum, int from_moments,
                       hipStream_t stream, const float* guard = nullptr);
 // adam_step + bn_running_update in one launch (what follows a data-parallel bucket all-reduce); `guard` may be null
-int adam_bn_step(float* p, const float* g, float* m, float* v, int64_t n, int64_t step, float lr, float beta1, float beta2, float eps,
+[[nodiscard]] int adam_bn_step(float* p, const float* g, float* m, float* v, int64_t n, int64_t step, float lr, float beta1, float beta2, float eps,
                  float wd, float gscale, float* bn, const float* batch, int num_layers, int64_t count, float momentum, int from_moments,
                  const float* guard, hipStream_t stream);
 
 size_t stgnn_workspace_bytes(const rulgnn_stgnn_shape* s);
-int stgnn_terms(const rulgnn_stgnn_shape* s, const float* x, float* terms, float* adj, hipStream_t st);
-int stgnn_cheb_forward(const rulgnn_stgnn_shape* s, const float* terms, const float* filters, float* out, hipStream_t st);
-int stgnn_cheb_backward(const rulgnn_stgnn_shape* s, const float* terms, const float* dout, float* dfilters, void* workspace,
+[[nodiscard]] int stgnn_terms(const rulgnn_stgnn_shape* s, const float* x, float* terms, float* adj, hipStream_t st);
+[[nodiscard]] int stgnn_cheb_forward(const rulgnn_stgnn_shape* s, const float* terms, const float* filters, float* out, hipStream_t st);
+[[nodiscard]] int stgnn_cheb_backward(const rulgnn_stgnn_shape* s, const float* terms, const float* dout, float* dfilters, void* workspace,
                         size_t workspace_bytes, hipStream_t st);
 size_t gru_workspace_bytes(const rulgnn_gru_shape* s);
-int gru_forward(const rulgnn_gru_shape* s, const rulgnn_gru_args* a, hipStream_t st);
-int gru_backward(const rulgnn_gru_shape* s, const rulgnn_gru_args* a, hipStream_t st);
+[[nodiscard]] int gru_forward(const rulgnn_gru_shape* s, const rulgnn_gru_args* a, hipStream_t st);
+[[nodiscard]] int gru_backward(const rulgnn_gru_shape* s, const rulgnn_gru_args* a, hipStream_t st);
 // the same layer as one launch over all steps (gru_seq.hip); 0 / RULGNN_EUNSUPPORTED outside hidden_dim == 64, input_dim <= 64, seq_len <= 1024
 size_t gru_persistent_workspace_bytes(const rulgnn_gru_shape* s);
-int gru_persistent_forward(const rulgnn_gru_shape* s, const rulgnn_gru_args* a, hipStream_t st);
-int gru_persistent_backward(const rulgnn_gru_shape* s, const rulgnn_gru_args* a, hipStream_t st);
+[[nodiscard]] int gru_persistent_forward(const rulgnn_gru_shape* s, const rulgnn_gru_args* a, hipStream_t st);
+[[nodiscard]] int gru_persistent_backward(const rulgnn_gru_shape* s, const rulgnn_gru_args* a, hipStream_t st);
 size_t rul_metrics_workspace_bytes(int64_t n);
-int rul_metrics(const float* pred, const float* real, int64_t n, float max_rul, double* out, void* workspace, size_t workspace_bytes,
+[[nodiscard]] int rul_metrics(const float* pred, const float* real, int64_t n, float max_rul, double* out, void* workspace, size_t workspace_bytes,
                 hipStream_t st, int raw = 0);
 
 }  // namespace rulgnn

@@ -1997,12 +1997,12 @@ int Fcstgnn::run(const Shape* s, const Args* a, int mode, hipStream_t st, const 
     const bool mlp_fused = g.D2 == 2 * g.HD && (g.D2 == 16 || g.D2 == 32 || g.D2 == 64);
     auto mlp_tail = [&](int tail_mode, const float* y, const float* dpred_in) {
         auto go = [&](auto kernel) {
-            hipLaunchKernelGGL(kernel, dim3((unsigned)((g.B + 63) / 64)), dim3(64), 0, st, g, prm, P_(w.h1), P_(w.h2), P_(w.h3), y, dpred_in, a->pred,
-                               P_(w.dpred), P_(w.sqerr), P_(w.dh3), P_(w.dh2), P_(w.dh1), inv_gb, tail_mode);
+            return launch_checked(kernel, dim3((unsigned)((g.B + 63) / 64)), dim3(64), 0, st, g, prm, P_(w.h1), P_(w.h2), P_(w.h3), y, dpred_in, a->pred,
+                                  P_(w.dpred), P_(w.sqerr), P_(w.dh3), P_(w.dh2), P_(w.dh1), inv_gb, tail_mode);
         };
-        if (g.D2 == 16) go(fc_mlp_tail_kernel<16>);
-        else if (g.D2 == 32) go(fc_mlp_tail_kernel<32>);
-        else go(fc_mlp_tail_kernel<64>);
+        if (g.D2 == 16) return go(fc_mlp_tail_kernel<16>);
+        if (g.D2 == 32) return go(fc_mlp_tail_kernel<32>);
+        return go(fc_mlp_tail_kernel<64>);
     };
     // positional-encoding dropout (train mode only)
     const float p = training ? a->dropout_p : 0.f;
@@ -2012,7 +2012,6 @@ int Fcstgnn::run(const Shape* s, const Args* a, int mode, hipStream_t st, const 
     const uint32_t key = dropout_layer_key(a->seed, a->step, 0);
     const uint32_t* key_dev = a->step_state ? static_cast<const StepState*>(a->step_state)->drop_key : nullptr;
     const int64_t row_off = a->sample_offset * g.NP * g.N;
-    (void)hipGetLastError();
     // reduction pair `id` (forward or backward) is complete behind the launch just enqueued: 2 MAXC contiguous doubles of every replica
     constexpr int PAIR = 2 * MAXC, FWD0 = offsetof(Cells, fwd) / sizeof(double), BWD0 = offsetof(Cells, bwd) / sizeof(double);
     static_assert(FWD0 == 0 && BWD0 == NBN * PAIR && CELLS_STRIDE == 2 * NBN * PAIR, "Cells: fwd[NBN] then bwd[NBN] pairs of doubles");
@@ -2026,28 +2025,28 @@ int Fcstgnn::run(const Shape* s, const Args* a, int mode, hipStream_t st, const 
         // (the reference's C-MAPSS wiring has its own instantiations: shapes as compile-time constants)
         const bool fd004_conv = g.K == 2 && g.L1 == 3 && g.L2 == 4 && g.H1 == 8 && g.CO == 6;
         const bool fd004_in = fd004_conv && g.N == 14 && g.NP == 25 && g.PS == 2 && g.TL == 50;
-        if (fd004_in) hipLaunchKernelGGL(fc_conv1_kernel<true>, dim3(grid_for(g.M * g.H1 * g.L1)), dim3(FB), 0, st, g, a->x, prm, P_(w.z1), cells, training);
-        else hipLaunchKernelGGL(fc_conv1_kernel<false>, dim3(grid_for(g.M * g.H1 * g.L1)), dim3(FB), 0, st, g, a->x, prm, P_(w.z1), cells, training);
+        if (fd004_in) RULGNN_TRY(launch_checked(fc_conv1_kernel<true>, dim3(grid_for(g.M * g.H1 * g.L1)), dim3(FB), 0, st, g, a->x, prm, P_(w.z1), cells, training));
+        else RULGNN_TRY(launch_checked(fc_conv1_kernel<false>, dim3(grid_for(g.M * g.H1 * g.L1)), dim3(FB), 0, st, g, a->x, prm, P_(w.z1), cells, training));
         RULGNN_TRY(sync_pair(0, 0));
         if (fd004_conv)
-            hipLaunchKernelGGL((fc_conv2_kernel<2, 3, 4, 8, 6>), dim3(grid_for(g.M * CL)), dim3(FB), 0, st, g, prm, run, (const float*)P_(w.z1), P_(w.z2),
-                               cells, training);
+            RULGNN_TRY(launch_checked((fc_conv2_kernel<2, 3, 4, 8, 6>), dim3(grid_for(g.M * CL)), dim3(FB), 0, st, g, prm, run, (const float*)P_(w.z1), P_(w.z2),
+                                      cells, training));
         else
-            hipLaunchKernelGGL((fc_conv2_kernel<0, 0, 0, 0, 0>), dim3(grid_for(g.M * CL)), dim3(FB), 0, st, g, prm, run, (const float*)P_(w.z1), P_(w.z2),
-                               cells, training);
+            RULGNN_TRY(launch_checked((fc_conv2_kernel<0, 0, 0, 0, 0>), dim3(grid_for(g.M * CL)), dim3(FB), 0, st, g, prm, run, (const float*)P_(w.z1), P_(w.z2),
+                                      cells, training));
         RULGNN_TRY(sync_pair(0, 1));
         if (proj_fused) {
-            hipLaunchKernelGGL(fc_proj3_kernel, dim3(grid_for(g.M * CL)), dim3(FB), proj_lds, st, g, prm, run, cells, training,
-                               (const float*)P_(w.z2), P_(w.a2), P_(w.z3));
+            RULGNN_TRY(launch_checked(fc_proj3_kernel, dim3(grid_for(g.M * CL)), dim3(FB), proj_lds, st, g, prm, run, cells, training,
+                                      (const float*)P_(w.z2), P_(w.a2), P_(w.z3)));
         } else {
-            hipLaunchKernelGGL(fc_act2_kernel, dim3(grid_for(g.M * CL)), dim3(FB), 0, st, g, prm, run, (const Cells*)cells, training,
-                               (const float*)P_(w.z2), P_(w.a2));
+            RULGNN_TRY(launch_checked(fc_act2_kernel, dim3(grid_for(g.M * CL)), dim3(FB), 0, st, g, prm, run, (const Cells*)cells, training,
+                                      (const float*)P_(w.z2), P_(w.a2)));
             RULGNN_TRY(sgemm(P_(w.a2), CL, 1, prm + g.o_W3, CL, 1, P_(w.z3), D2, Mi, D2, CL, false, st, bf));
-            hipLaunchKernelGGL(fc_bias_stats_kernel, dim3(grid_for(g.M * D2)), dim3(FB), 0, st, P_(w.z3), prm + g.o_b3, g.M, D2, cells, 2, training);
+            RULGNN_TRY(launch_checked(fc_bias_stats_kernel, dim3(grid_for(g.M * D2)), dim3(FB), 0, st, P_(w.z3), prm + g.o_b3, g.M, D2, cells, 2, training));
         }
         RULGNN_TRY(sync_pair(0, 2));
-        hipLaunchKernelGGL(fc_pe_kernel, dim3(grid_for(g.M * D2)), dim3(FB), 0, st, g, prm, run, cells, training, (const float*)P_(w.z3),
-                           P_(w.F), thr, dscale, key, key_dev, row_off);
+        RULGNN_TRY(launch_checked(fc_pe_kernel, dim3(grid_for(g.M * D2)), dim3(FB), 0, st, g, prm, run, cells, training, (const float*)P_(w.z3),
+                                  P_(w.F), thr, dscale, key, key_dev, row_off));
         RULGNN_TRY(sync_pair(0, 3));
         RULGNN_TRY(sync_pair(0, 5));
         const int64_t Gmax = g.G[0] > g.G[1] ? g.G[0] : g.G[1];
@@ -2060,13 +2059,13 @@ int Fcstgnn::run(const Shape* s, const Args* a, int mode, hipStream_t st, const 
                 // graphs -- 2304 workgroups, 4.5 rounds -- every wavefront paid the prologue (BatchNorm table, weights, a barrier) for ONE graph:
                 // FD004 batch 256 0.352 -> 0.336 ms with both graph kernels capped; 128: 0.373, 192: 0.343, 384: 0.343, 512: 0.340)
                 constexpr unsigned capf = 256u;
-                hipLaunchKernelGGL(kernel, dim3(wgs < capf ? wgs : capf, 2), dim3(64 * FC_MX_WAVES), 0, st, g, prm, run, cells, training,
-                                   (const float*)P_(w.F), Ptr2{{P_(w.Mm[0]), P_(w.Mm[1])}}, Ptr2{{P_(w.P[0]), P_(w.P[1])}},
-                                   Ptr2{{P_(w.AX[0]), P_(w.AX[1])}}, Ptr2{{P_(w.z5[0]), P_(w.z5[1])}});
+                return launch_checked(kernel, dim3(wgs < capf ? wgs : capf, 2), dim3(64 * FC_MX_WAVES), 0, st, g, prm, run, cells, training,
+                                      (const float*)P_(w.F), Ptr2{{P_(w.Mm[0]), P_(w.Mm[1])}}, Ptr2{{P_(w.P[0]), P_(w.P[1])}},
+                                      Ptr2{{P_(w.AX[0]), P_(w.AX[1])}}, Ptr2{{P_(w.z5[0]), P_(w.z5[1])}});
             };
             // (compute_dtype = bf16: the four products of a window graph on bf16 matrix instructions, fc_prod)
-            if (D2 == 16) { if (bf) go(fc_block_mx_kernel<16, true>); else go(fc_block_mx_kernel<16, false>); }
-            else { if (bf) go(fc_block_mx_kernel<32, true>); else go(fc_block_mx_kernel<32, false>); }
+            if (D2 == 16) { if (bf) RULGNN_TRY(go(fc_block_mx_kernel<16, true>)); else RULGNN_TRY(go(fc_block_mx_kernel<16, false>)); }
+            else { if (bf) RULGNN_TRY(go(fc_block_mx_kernel<32, true>)); else RULGNN_TRY(go(fc_block_mx_kernel<32, false>)); }
             RULGNN_TRY(sync_pair(0, 4));
             RULGNN_TRY(sync_pair(0, 6));
         }
@@ -2077,39 +2076,39 @@ int Fcstgnn::run(const Shape* s, const Args* a, int mode, hipStream_t st, const 
                 RULGNN_TRY(sgemm(P_(w.F), D2, 1, prm + g.o_map[b], D2, 1, P_(w.Mm[b]), D2, Mi, D2, D2, false, st, bf));
                 if (graph_mx) {
                     auto go = [&](auto kernel) {
-                        hipLaunchKernelGGL(kernel, dim3(wgs < 4096 ? wgs : 4096), dim3(64 * FC_MX_WAVES), 0, st, g, b, prm, run, (const Cells*)cells, training,
-                                           (const float*)P_(w.F), (const float*)P_(w.Mm[b]), P_(w.P[b]), P_(w.AX[b]));
+                        return launch_checked(kernel, dim3(wgs < 4096 ? wgs : 4096), dim3(64 * FC_MX_WAVES), 0, st, g, b, prm, run, (const Cells*)cells, training,
+                                              (const float*)P_(w.F), (const float*)P_(w.Mm[b]), P_(w.P[b]), P_(w.AX[b]));
                     };
-                    if (D2 == 16) go(fc_graph_mx_kernel<16>);
-                    else go(fc_graph_mx_kernel<32>);
+                    if (D2 == 16) RULGNN_TRY(go(fc_graph_mx_kernel<16>));
+                    else RULGNN_TRY(go(fc_graph_mx_kernel<32>));
                 } else {
-                    hipLaunchKernelGGL(fc_graph_kernel, dim3((unsigned)(g.G[b] < 8192 ? g.G[b] : 8192)), dim3(FC_GRAPH_FWD_THREADS),
-                                       sizeof(float) * (2 * g.Q * (g.D2 + 1) + g.Q * (g.Q + 1)), st, g, b, prm, run, (const Cells*)cells, training,
-                                       (const float*)P_(w.F), (const float*)P_(w.Mm[b]), P_(w.P[b]), P_(w.AX[b]));
+                    RULGNN_TRY(launch_checked(fc_graph_kernel, dim3((unsigned)(g.G[b] < 8192 ? g.G[b] : 8192)), dim3(FC_GRAPH_FWD_THREADS),
+                                              sizeof(float) * (2 * g.Q * (g.D2 + 1) + g.Q * (g.Q + 1)), st, g, b, prm, run, (const Cells*)cells, training,
+                                              (const float*)P_(w.F), (const float*)P_(w.Mm[b]), P_(w.P[b]), P_(w.AX[b])));
                 }
                 RULGNN_TRY(sgemm(P_(w.AX[b]), D2, 1, prm + g.o_th[b], D2, 1, P_(w.z5[b]), HD, GQ, HD, D2, false, st, bf));
-                hipLaunchKernelGGL(fc_bias_stats_kernel, dim3(grid_for((int64_t)GQ * HD)), dim3(FB), 0, st, P_(w.z5[b]), prm + g.o_thb[b],
-                                   (int64_t)GQ, HD, cells, 4 + 2 * b, training);
+                RULGNN_TRY(launch_checked(fc_bias_stats_kernel, dim3(grid_for((int64_t)GQ * HD)), dim3(FB), 0, st, P_(w.z5[b]), prm + g.o_thb[b],
+                                          (int64_t)GQ, HD, cells, 4 + 2 * b, training));
             }
             RULGNN_TRY(sync_pair(0, 4 + 2 * b));
         }
-        hipLaunchKernelGGL(fc_pool_kernel, dim3(grid_for(Gmax * g.N * HD), 2), dim3(FB), 0, st, g, prm, run, (const Cells*)cells, training,
-                           CPtr2{{P_(w.z5[0]), P_(w.z5[1])}}, P_(w.feat));
+        RULGNN_TRY(launch_checked(fc_pool_kernel, dim3(grid_for(Gmax * g.N * HD), 2), dim3(FB), 0, st, g, prm, run, (const Cells*)cells, training,
+                                  CPtr2{{P_(w.z5[0]), P_(w.z5[1])}}, P_(w.feat)));
         // K = FIN (4032 at FD004) against a [batch x 16] output: split the reduction, or four workgroups walk it alone (250 us)
         RULGNN_TRY(sgemm_splitk(P_(w.feat), FIN, 1, prm + g.o_f1w, FIN, 1, P_(w.h1), D2, Bi, D2, FIN, false, P_(w.split), st));
         if (mlp_fused) {
-            mlp_tail(1, a->y, nullptr);
+            RULGNN_TRY(mlp_tail(1, a->y, nullptr));
         } else {
-            hipLaunchKernelGGL(fc_bias_relu_kernel, dim3(grid_for(g.B * D2)), dim3(FB), 0, st, P_(w.h1), prm + g.o_f1b, g.B, D2);
+            RULGNN_TRY(launch_checked(fc_bias_relu_kernel, dim3(grid_for(g.B * D2)), dim3(FB), 0, st, P_(w.h1), prm + g.o_f1b, g.B, D2));
             RULGNN_TRY(sgemm(P_(w.h1), D2, 1, prm + g.o_f2w, D2, 1, P_(w.h2), D2, Bi, D2, D2, false, st, bf));
-            hipLaunchKernelGGL(fc_bias_relu_kernel, dim3(grid_for(g.B * D2)), dim3(FB), 0, st, P_(w.h2), prm + g.o_f2b, g.B, D2);
+            RULGNN_TRY(launch_checked(fc_bias_relu_kernel, dim3(grid_for(g.B * D2)), dim3(FB), 0, st, P_(w.h2), prm + g.o_f2b, g.B, D2));
             RULGNN_TRY(sgemm(P_(w.h2), D2, 1, prm + g.o_f3w, D2, 1, P_(w.h3), HD, Bi, HD, D2, false, st, bf));
-            hipLaunchKernelGGL(fc_bias_relu_kernel, dim3(grid_for(g.B * HD)), dim3(FB), 0, st, P_(w.h3), prm + g.o_f3b, g.B, HD);
-            hipLaunchKernelGGL(fc_head_kernel, dim3((unsigned)((g.B + FB - 1) / FB)), dim3(FB), 0, st, g, prm, (const float*)P_(w.h3), a->y,
-                               (const float*)nullptr, a->pred, P_(w.dpred), P_(w.sqerr), P_(w.dh3), inv_gb, 0);
+            RULGNN_TRY(launch_checked(fc_bias_relu_kernel, dim3(grid_for(g.B * HD)), dim3(FB), 0, st, P_(w.h3), prm + g.o_f3b, g.B, HD));
+            RULGNN_TRY(launch_checked(fc_head_kernel, dim3((unsigned)((g.B + FB - 1) / FB)), dim3(FB), 0, st, g, prm, (const float*)P_(w.h3), a->y,
+                                      (const float*)nullptr, a->pred, P_(w.dpred), P_(w.sqerr), P_(w.dh3), inv_gb, 0));
         }
         if (training && a->bn_batch && !(mode & 2))            // (with a backward in the same call: beside its chain, below)
-            hipLaunchKernelGGL(fc_bn_batch_kernel, dim3(1), dim3(64), 0, st, g, (const Cells*)cells, a->bn_batch, a->bn_moment_weight);
+            RULGNN_TRY(launch_checked(fc_bn_batch_kernel, dim3(1), dim3(64), 0, st, g, (const Cells*)cells, a->bn_batch, a->bn_moment_weight));
     }
     if (mode & 2) {
         float* gr = a->grads;
@@ -2126,19 +2125,19 @@ int Fcstgnn::run(const Shape* s, const Args* a, int mode, hipStream_t st, const 
         // ... and so do the other launches nothing on the chain waits for: the constant for the column sums, the batch moments for the
         // bucket, the loss sum
         // (one fork for everything that is ready when the backward starts: with an incoming gradient the MLP's d h first)
-        if (mlp_fused && a->dpred) mlp_tail(2, nullptr, a->dpred);
+        if (mlp_fused && a->dpred) RULGNN_TRY(mlp_tail(2, nullptr, a->dpred));
         fork();
         // (the host enqueues in program order: the MAIN stream's next kernel goes out before the dozen side-stream launches behind this fork
         // -- with the side launches first the main queue sat empty for ~30 us while the host enqueued them; same at every fork below)
         if (mlp_fused) RULGNN_TRY(sgemm(P_(w.dh1), D2, 1, prm + g.o_f1w, 1, FIN, P_(w.dfeat), FIN, Bi, FIN, D2, false, st, bf));
         if ((mode & 1) && training && a->bn_batch)
-            hipLaunchKernelGGL(fc_side_head_kernel, dim3(1), dim3(64), 0, wst, g, (const Cells*)cells, one, a->bn_batch, a->bn_moment_weight,
-                               (bn_running_out && a->bn_moment_weight == 0.f) ? bn_running_out : (float*)nullptr, bn_momentum);
+            RULGNN_TRY(launch_checked(fc_side_head_kernel, dim3(1), dim3(64), 0, wst, g, (const Cells*)cells, one, a->bn_batch, a->bn_moment_weight,
+                                      (bn_running_out && a->bn_moment_weight == 0.f) ? bn_running_out : (float*)nullptr, bn_momentum));
         else
             RULGNN_TRY(fill_f32(one, 1, 1.f, wst));
         // (batches of the reference protocol's size: every MLP parameter gradient and the loss sum in one launch, fc_mlp_wgrad_kernel)
         const bool mlp_wgrad_fused = mlp_fused && g.B <= FC_MLPW_MAXB && D2 <= 64;
-        if (!a->dpred && a->loss && !mlp_wgrad_fused) (void)block_sum((const float*)P_(w.sqerr), (int64_t)g.B, a->loss, wst);
+        if (!a->dpred && a->loss && !mlp_wgrad_fused) RULGNN_TRY(block_sum((const float*)P_(w.sqerr), (int64_t)g.B, a->loss, wst));
         auto colsum = [&](const float* src, int64_t rows, int C, float* dst) {      // dst[c] = sum_r src[r][c]
             if (cols_sum_small_ok(rows, C)) return cols_sum_small(src, (int)rows, C, dst, wst);
             return sgemm_splitk(one, 0, 0, src, 1, C, dst, C, 1, C, (int)rows, false, split, wst);
@@ -2156,7 +2155,7 @@ int Fcstgnn::run(const Shape* s, const Args* a, int mode, hipStream_t st, const 
             RULGNN_TRY(sgemm_splitk(P_(w.dh1), 1, D2, P_(w.feat), 1, FIN, gr + g.o_f1w, FIN, D2, FIN, Bi, false, split, wst));
             k.B = Bi; k.D2 = D2; k.HD = HD; k.FIN = FIN; k.nfw = 0;
             const int small = D2 * D2 + HD * D2 + HD + D2 + D2 + HD + 2;
-            hipLaunchKernelGGL(fc_mlp_wgrad_kernel, dim3((unsigned)(k.nfw + (small + 255) / 256)), dim3(256), 0, wst, k);
+            RULGNN_TRY(launch_checked(fc_mlp_wgrad_kernel, dim3((unsigned)(k.nfw + (small + 255) / 256)), dim3(256), 0, wst, k));
         } else if (mlp_fused) {
             // d h3, d h2, d h1 are there (formed with the loss in the forward's fused MLP kernel, or here from the incoming gradient):
             // one fork, every parameter gradient of the MLP on the side
@@ -2171,19 +2170,19 @@ int Fcstgnn::run(const Shape* s, const Args* a, int mode, hipStream_t st, const 
         } else {
         fork();
         if (a->dpred)
-            hipLaunchKernelGGL(fc_head_kernel, dim3((unsigned)((g.B + FB - 1) / FB)), dim3(FB), 0, st, g, prm, (const float*)P_(w.h3),
-                               (const float*)nullptr, a->dpred, a->pred, P_(w.dpred), P_(w.sqerr), P_(w.dh3), inv_gb, 1);
+            RULGNN_TRY(launch_checked(fc_head_kernel, dim3((unsigned)((g.B + FB - 1) / FB)), dim3(FB), 0, st, g, prm, (const float*)P_(w.h3),
+                                      (const float*)nullptr, a->dpred, a->pred, P_(w.dpred), P_(w.sqerr), P_(w.dh3), inv_gb, 1));
         RULGNN_TRY(sgemm_splitk(P_(w.dpred), 0, 1, P_(w.h3), 1, HD, gr + g.o_f4w, HD, 1, HD, Bi, false, split, wst));
         RULGNN_TRY(sgemm_splitk(P_(w.dpred), 0, 1, one, 0, 0, gr + g.o_f4b, 1, 1, 1, Bi, false, split, wst));
         RULGNN_TRY(sgemm_splitk(P_(w.dh3), 1, HD, P_(w.h2), 1, D2, gr + g.o_f3w, D2, HD, D2, Bi, false, split, wst));
         RULGNN_TRY(colsum(P_(w.dh3), g.B, HD, gr + g.o_f3b));
         RULGNN_TRY(sgemm(P_(w.dh3), HD, 1, prm + g.o_f3w, 1, D2, P_(w.dh2), D2, Bi, D2, HD, false, st, bf));
-        hipLaunchKernelGGL(fc_relu_mask_kernel, dim3(grid_for(g.B * D2)), dim3(FB), 0, st, P_(w.dh2), (const float*)P_(w.h2), g.B * D2);
+        RULGNN_TRY(launch_checked(fc_relu_mask_kernel, dim3(grid_for(g.B * D2)), dim3(FB), 0, st, P_(w.dh2), (const float*)P_(w.h2), g.B * D2));
         fork();
         RULGNN_TRY(sgemm_splitk(P_(w.dh2), 1, D2, P_(w.h1), 1, D2, gr + g.o_f2w, D2, D2, D2, Bi, false, split, wst));
         RULGNN_TRY(colsum(P_(w.dh2), g.B, D2, gr + g.o_f2b));
         RULGNN_TRY(sgemm(P_(w.dh2), D2, 1, prm + g.o_f2w, 1, D2, P_(w.dh1), D2, Bi, D2, D2, false, st, bf));
-        hipLaunchKernelGGL(fc_relu_mask_kernel, dim3(grid_for(g.B * D2)), dim3(FB), 0, st, P_(w.dh1), (const float*)P_(w.h1), g.B * D2);
+        RULGNN_TRY(launch_checked(fc_relu_mask_kernel, dim3(grid_for(g.B * D2)), dim3(FB), 0, st, P_(w.dh1), (const float*)P_(w.h1), g.B * D2));
         fork();
         RULGNN_TRY(sgemm_splitk(P_(w.dh1), 1, D2, P_(w.feat), 1, FIN, gr + g.o_f1w, FIN, D2, FIN, Bi, false, split, wst));
         RULGNN_TRY(colsum(P_(w.dh1), g.B, D2, gr + g.o_f1b));
@@ -2196,12 +2195,12 @@ int Fcstgnn::run(const Shape* s, const Args* a, int mode, hipStream_t st, const 
             const int64_t GQ0 = g.G[0] * g.Q, GQ1 = g.G[1] * g.Q;
             const CPtr2 z5p{{P_(w.z5[0]), P_(w.z5[1])}};
             const Ptr2 dz5p{{P_(w.dz5[0]), P_(w.dz5[1])}};
-            hipLaunchKernelGGL(fc_pool_bwd_kernel, dim3(grid_for(Gmax * g.Q * HD), 2), dim3(FB), 0, st, g, prm, cells, z5p,
-                               (const float*)P_(w.dfeat), dz5p);
+            RULGNN_TRY(launch_checked(fc_pool_bwd_kernel, dim3(grid_for(Gmax * g.Q * HD), 2), dim3(FB), 0, st, g, prm, cells, z5p,
+                                      (const float*)P_(w.dfeat), dz5p));
             RULGNN_TRY(sync_pair(1, 4));
             RULGNN_TRY(sync_pair(1, 6));
-            hipLaunchKernelGGL(fc_bn_rows_bwd_kernel, dim3(grid_for(Gmax * g.Q * HD), 2), dim3(FB), 0, st, g, 4, prm, (const Cells*)cells, z5p, dz5p,
-                               GQ0, GQ1);
+            RULGNN_TRY(launch_checked(fc_bn_rows_bwd_kernel, dim3(grid_for(Gmax * g.Q * HD), 2), dim3(FB), 0, st, g, 4, prm, (const Cells*)cells, z5p, dz5p,
+                                      GQ0, GQ1));
             const bool bwd_fused = graph_mx && D2 == 2 * HD;          // d AX = d z5 W_theta inside the graph kernel
             if (!bwd_fused)
                 for (int b = 0; b < 2; ++b)
@@ -2211,57 +2210,57 @@ int Fcstgnn::run(const Shape* s, const Args* a, int mode, hipStream_t st, const 
                 const unsigned wgs = (unsigned)((Gmax + FC_MX_WAVES - 1) / FC_MX_WAVES);
                 auto go = [&](auto kernel) {
                     constexpr unsigned capb = 256u;                      // (as the forward block kernel: one workgroup per CU and window block)
-                    hipLaunchKernelGGL(kernel, dim3(wgs < capb ? wgs : capb, 2), dim3(64 * FC_MX_WAVES), 0, st, g, prm, (const Cells*)cells,
-                                       (const float*)P_(w.F), CPtr2{{P_(w.Mm[0]), P_(w.Mm[1])}}, CPtr2{{P_(w.P[0]), P_(w.P[1])}},
-                                       CPtr2{{P_(w.dz5[0]), P_(w.dz5[1])}}, Ptr2{{P_(w.dAX[0]), P_(w.dAX[1])}},
-                                       Ptr2{{P_(w.dMb[0]), P_(w.dMb[1])}});
+                    return launch_checked(kernel, dim3(wgs < capb ? wgs : capb, 2), dim3(64 * FC_MX_WAVES), 0, st, g, prm, (const Cells*)cells,
+                                          (const float*)P_(w.F), CPtr2{{P_(w.Mm[0]), P_(w.Mm[1])}}, CPtr2{{P_(w.P[0]), P_(w.P[1])}},
+                                          CPtr2{{P_(w.dz5[0]), P_(w.dz5[1])}}, Ptr2{{P_(w.dAX[0]), P_(w.dAX[1])}},
+                                          Ptr2{{P_(w.dMb[0]), P_(w.dMb[1])}});
                 };
                 if (bwd_fused) {
-                    if (D2 == 16) { if (bf) go(fc_graph_bwd_mx_kernel<16, true, true>); else go(fc_graph_bwd_mx_kernel<16, true, false>); }
-                    else { if (bf) go(fc_graph_bwd_mx_kernel<32, true, true>); else go(fc_graph_bwd_mx_kernel<32, true, false>); }
+                    if (D2 == 16) { if (bf) RULGNN_TRY(go(fc_graph_bwd_mx_kernel<16, true, true>)); else RULGNN_TRY(go(fc_graph_bwd_mx_kernel<16, true, false>)); }
+                    else { if (bf) RULGNN_TRY(go(fc_graph_bwd_mx_kernel<32, true, true>)); else RULGNN_TRY(go(fc_graph_bwd_mx_kernel<32, true, false>)); }
                 } else {
-                    if (D2 == 16) { if (bf) go(fc_graph_bwd_mx_kernel<16, false, true>); else go(fc_graph_bwd_mx_kernel<16, false, false>); }
-                    else { if (bf) go(fc_graph_bwd_mx_kernel<32, false, true>); else go(fc_graph_bwd_mx_kernel<32, false, false>); }
+                    if (D2 == 16) { if (bf) RULGNN_TRY(go(fc_graph_bwd_mx_kernel<16, false, true>)); else RULGNN_TRY(go(fc_graph_bwd_mx_kernel<16, false, false>)); }
+                    else { if (bf) RULGNN_TRY(go(fc_graph_bwd_mx_kernel<32, false, true>)); else RULGNN_TRY(go(fc_graph_bwd_mx_kernel<32, false, false>)); }
                 }
             } else {
             for (int b = 0; b < 2; ++b) {
                 const size_t lds_b = sizeof(float) * (3 * g.Q * (g.D2 + 1) + 3 * g.Q * (g.Q + 1));
                 if (const int rcl = allow_dynamic_lds(fc_graph_bwd_kernel, lds_b); rcl != RULGNN_OK) return rcl;
-            hipLaunchKernelGGL(fc_graph_bwd_kernel, dim3((unsigned)(g.G[b] < 8192 ? g.G[b] : 8192)), dim3(FC_GRAPH_BWD_THREADS), sizeof(float) * (3 * g.Q * (g.D2 + 1) + 3 * g.Q * (g.Q + 1)), st, g, b, prm,
-                               (const Cells*)cells, (const float*)P_(w.F), (const float*)P_(w.Mm[b]), (const float*)P_(w.P[b]),
-                               P_(w.dAX[b]), P_(w.dMb[b]));
+            RULGNN_TRY(launch_checked(fc_graph_bwd_kernel, dim3((unsigned)(g.G[b] < 8192 ? g.G[b] : 8192)), dim3(FC_GRAPH_BWD_THREADS), sizeof(float) * (3 * g.Q * (g.D2 + 1) + 3 * g.Q * (g.Q + 1)), st, g, b, prm,
+                                      (const Cells*)cells, (const float*)P_(w.F), (const float*)P_(w.Mm[b]), (const float*)P_(w.P[b]),
+                                      P_(w.dAX[b]), P_(w.dMb[b])));
             }
             }
-            hipLaunchKernelGGL(fc_graph_gather_kernel, dim3(grid_for(g.M * D2), 2), dim3(FB), 0, st, g, CPtr2{{P_(w.dAX[0]), P_(w.dAX[1])}},
-                               CPtr2{{P_(w.dMb[0]), P_(w.dMb[1])}}, Ptr2{{P_(w.gX[0]), P_(w.gX[1])}}, Ptr2{{P_(w.gM[0]), P_(w.gM[1])}});
+            RULGNN_TRY(launch_checked(fc_graph_gather_kernel, dim3(grid_for(g.M * D2), 2), dim3(FB), 0, st, g, CPtr2{{P_(w.dAX[0]), P_(w.dAX[1])}},
+                                      CPtr2{{P_(w.dMb[0]), P_(w.dMb[1])}}, Ptr2{{P_(w.gX[0]), P_(w.gX[1])}}, Ptr2{{P_(w.gM[0]), P_(w.gM[1])}}));
             // (weight gradient and the bias gradient over the same rows: one split-K pass with the bias sums as an extra column.  The five
             // such products of the backward -- theta and mapping of both window blocks, the projection -- are collected and go out as ONE
             // pair of launches behind the last of their inputs (sgemm_splitk_colsum_batch): they were ten launches, the tail of the side stream)
             for (int b = 0; b < 2; ++b)
                 wjobs[nwj++] = SplitKColsumJob{P_(w.dz5[b]), 1, HD, P_(w.AX[b]), 1, D2, gr + g.o_th[b], D2, HD, D2, (int)(g.G[b] * g.Q), gr + g.o_thb[b]};
         }
-        hipLaunchKernelGGL(fc_feat_stats_kernel, dim3(grid_for(g.M * D2)), dim3(FB), 0, st, g, prm, cells, (const float*)P_(w.F),
-                           (const float*)P_(w.gX[0]), (const float*)P_(w.gX[1]));
+        RULGNN_TRY(launch_checked(fc_feat_stats_kernel, dim3(grid_for(g.M * D2)), dim3(FB), 0, st, g, prm, cells, (const float*)P_(w.F),
+                                  (const float*)P_(w.gX[0]), (const float*)P_(w.gX[1])));
         RULGNN_TRY(sync_pair(1, 3));
         RULGNN_TRY(sync_pair(1, 5));
         // window BatchNorms' backward + both d M W_map products + positional encoding / dropout backward: one launch
-        hipLaunchKernelGGL(fc_feat_pe_bwd_kernel, dim3(grid_for(g.M * D2)), dim3(FB), 0, st, g, prm, cells, (const float*)P_(w.F),
-                           (const float*)P_(w.gX[0]), (const float*)P_(w.gX[1]), (const float*)P_(w.gM[0]), (const float*)P_(w.gM[1]),
-                           (const float*)P_(w.z3), P_(w.dF), thr, dscale, key, key_dev, row_off);
+        RULGNN_TRY(launch_checked(fc_feat_pe_bwd_kernel, dim3(grid_for(g.M * D2)), dim3(FB), 0, st, g, prm, cells, (const float*)P_(w.F),
+                                  (const float*)P_(w.gX[0]), (const float*)P_(w.gX[1]), (const float*)P_(w.gM[0]), (const float*)P_(w.gM[1]),
+                                  (const float*)P_(w.z3), P_(w.dF), thr, dscale, key, key_dev, row_off));
         for (int b = 0; b < 2; ++b)
             wjobs[nwj++] = SplitKColsumJob{P_(w.gM[b]), 1, D2, P_(w.F), 1, D2, gr + g.o_map[b], D2, D2, D2, Mi, gr + g.o_bmap[b]};
         RULGNN_TRY(sync_pair(1, 2));
-        hipLaunchKernelGGL(fc_bn_rows_bwd_kernel, dim3(grid_for(g.M * D2)), dim3(FB), 0, st, g, 2, prm, (const Cells*)cells,
-                           CPtr2{{P_(w.z3), nullptr}}, Ptr2{{P_(w.dF), nullptr}}, g.M, (int64_t)0);
+        RULGNN_TRY(launch_checked(fc_bn_rows_bwd_kernel, dim3(grid_for(g.M * D2)), dim3(FB), 0, st, g, 2, prm, (const Cells*)cells,
+                                  CPtr2{{P_(w.z3), nullptr}}, Ptr2{{P_(w.dF), nullptr}}, g.M, (int64_t)0));
         fork();
         // ---- encoder convolutions ----
         if (proj_fused) {
-            hipLaunchKernelGGL(fc_proj3_bwd_kernel, dim3(grid_for(g.M * CL)), dim3(FB), proj_lds, st, g, prm, cells, (const float*)P_(w.z2),
-                               (const float*)P_(w.a2), (const float*)P_(w.dF), P_(w.da2));
+            RULGNN_TRY(launch_checked(fc_proj3_bwd_kernel, dim3(grid_for(g.M * CL)), dim3(FB), proj_lds, st, g, prm, cells, (const float*)P_(w.z2),
+                                      (const float*)P_(w.a2), (const float*)P_(w.dF), P_(w.da2)));
         } else {
             RULGNN_TRY(sgemm(P_(w.dF), D2, 1, prm + g.o_W3, 1, CL, P_(w.da2), CL, Mi, CL, D2, false, st, bf));
-            hipLaunchKernelGGL(fc_act2_bwd_kernel, dim3(grid_for(g.M * CL)), dim3(FB), 0, st, g, prm, cells, (const float*)P_(w.z2),
-                               (const float*)P_(w.a2), P_(w.da2));
+            RULGNN_TRY(launch_checked(fc_act2_bwd_kernel, dim3(grid_for(g.M * CL)), dim3(FB), 0, st, g, prm, cells, (const float*)P_(w.z2),
+                                      (const float*)P_(w.a2), P_(w.da2)));
         }
         wjobs[nwj++] = SplitKColsumJob{P_(w.dF), 1, D2, P_(w.a2), 1, CL, gr + g.o_W3, CL, D2, CL, Mi, gr + g.o_b3};
         RULGNN_TRY(sgemm_splitk_colsum_batch(wjobs, nwj, one, split, w.split_floats, wst));
@@ -2271,19 +2270,19 @@ int Fcstgnn::run(const Shape* s, const Args* a, int mode, hipStream_t st, const 
         const int rows = (int)(g.M < w.rows ? g.M : w.rows);
         const bool fd004_conv = g.K == 2 && g.L1 == 3 && g.L2 == 4 && g.H1 == 8 && g.CO == 6;     // the reference's C-MAPSS wiring: constants
         if (g.K == 2 && g.L1 == 3 && g.L2 == 4 && g.H1 == 8 && g.CO == 6)
-            hipLaunchKernelGGL((fc_conv2_dx_kernel<2, 3, 4, 8, 6>), dim3(grid_for(g.M * g.H1 * g.L1)), dim3(FB), 0, st, g, prm, cells,
-                               (const float*)P_(w.z1), (const float*)P_(w.da2), P_(w.dy1), (const float*)P_(w.z2));
+            RULGNN_TRY(launch_checked((fc_conv2_dx_kernel<2, 3, 4, 8, 6>), dim3(grid_for(g.M * g.H1 * g.L1)), dim3(FB), 0, st, g, prm, cells,
+                                      (const float*)P_(w.z1), (const float*)P_(w.da2), P_(w.dy1), (const float*)P_(w.z2)));
         else
-            hipLaunchKernelGGL((fc_conv2_dx_kernel<0, 0, 0, 0, 0>), dim3(grid_for(g.M * g.H1 * g.L1)), dim3(FB), 0, st, g, prm, cells,
-                               (const float*)P_(w.z1), (const float*)P_(w.da2), P_(w.dy1), (const float*)P_(w.z2));
+            RULGNN_TRY(launch_checked((fc_conv2_dx_kernel<0, 0, 0, 0, 0>), dim3(grid_for(g.M * g.H1 * g.L1)), dim3(FB), 0, st, g, prm, cells,
+                                      (const float*)P_(w.z1), (const float*)P_(w.da2), P_(w.dy1), (const float*)P_(w.z2)));
         RULGNN_TRY(sync_pair(1, 0));
         // both convolutions' weight gradients (the second one's needs d z2 only, but the side stream is the longer one by then)
         if (fd004_conv)
-            hipLaunchKernelGGL((fc_conv_wgrad_both_kernel<2, 3, 4, 8, 6>), dim3(rows, 2), dim3(FB), 0, st, g, a->x, prm, (const Cells*)cells,
-                               (const float*)P_(w.z1), (const float*)P_(w.z2), (const float*)P_(w.dy1), (const float*)P_(w.da2), P_(w.gp1), P_(w.gp2));
+            RULGNN_TRY(launch_checked((fc_conv_wgrad_both_kernel<2, 3, 4, 8, 6>), dim3(rows, 2), dim3(FB), 0, st, g, a->x, prm, (const Cells*)cells,
+                                      (const float*)P_(w.z1), (const float*)P_(w.z2), (const float*)P_(w.dy1), (const float*)P_(w.da2), P_(w.gp1), P_(w.gp2)));
         else
-            hipLaunchKernelGGL((fc_conv_wgrad_both_kernel<>), dim3(rows, 2), dim3(FB), 0, st, g, a->x, prm, (const Cells*)cells,
-                               (const float*)P_(w.z1), (const float*)P_(w.z2), (const float*)P_(w.dy1), (const float*)P_(w.da2), P_(w.gp1), P_(w.gp2));
+            RULGNN_TRY(launch_checked((fc_conv_wgrad_both_kernel<>), dim3(rows, 2), dim3(FB), 0, st, g, a->x, prm, (const Cells*)cells,
+                                      (const float*)P_(w.z1), (const float*)P_(w.z2), (const float*)P_(w.dy1), (const float*)P_(w.da2), P_(w.gp1), P_(w.gp2)));
         int nbn = 0;
         for (int i = 0; i < NBN; ++i) nbn += g.bn_ch[i];
         // (reads the convolutions' partial rows and the cells only: in front of the join, beside whatever the side stream still runs --
@@ -2293,21 +2292,19 @@ int Fcstgnn::run(const Shape* s, const Args* a, int mode, hipStream_t st, const 
         AdamFuse none{};
         none.p = nullptr;
         if (with_adam) RULGNN_TRY(fk.join());
-        hipLaunchKernelGGL(fc_finalize_kernel, dim3(nfin + (with_adam ? (g.nparam + FB - 1) / FB : 0)), dim3(FB), 0, st, g,
-                           (const float*)P_(w.gp1), (const float*)P_(w.gp2), rows, (const Cells*)cells, gr, sync ? sync->bn_param_grad_scale : 1.0f,
-                           with_adam ? *fuse : none, nfin);
+        RULGNN_TRY(launch_checked(fc_finalize_kernel, dim3(nfin + (with_adam ? (g.nparam + FB - 1) / FB : 0)), dim3(FB), 0, st, g,
+                                  (const float*)P_(w.gp1), (const float*)P_(w.gp2), rows, (const Cells*)cells, gr, sync ? sync->bn_param_grad_scale : 1.0f,
+                                  with_adam ? *fuse : none, nfin));
         RULGNN_TRY(fk.join());                                    // the gradient GEMMs are done when the call's work has drained
     }
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return RULGNN_OK;
 }
 
 int Fcstgnn::bn_running_update(const Shape* s, float* bn_stats, const float* bn_batch, float momentum, int from_moments,
                               hipStream_t st) {
     FcGeom g;
     RULGNN_TRY(fc_geometry(s, &g));
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(fc_bn_running_kernel, dim3(1), dim3(64), 0, st, g, bn_stats, bn_batch, momentum, from_moments);
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return launch_checked(fc_bn_running_kernel, dim3(1), dim3(64), 0, st, g, bn_stats, bn_batch, momentum, from_moments);
 }
 
 }  // namespace rulgnn

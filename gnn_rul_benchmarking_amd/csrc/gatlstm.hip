@@ -429,7 +429,6 @@ int Gatlstm::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
     const int nl = g.nl, R = (int)g.R;
     float* split = ws + g.w_split;
     const float* hgat = ws + g.w_h[nl - 1];       // the last GAT layer's output: the LSTM stack's input
-    (void)hipGetLastError();
     // The projection weights as GEMM operands: the flat buffer puts them behind odd-sized tensors, off a 16-byte boundary
     // (seq_backend.hpp: aligned_operand).
     const float* wop[GL_MAXL];

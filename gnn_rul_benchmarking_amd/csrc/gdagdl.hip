@@ -444,7 +444,6 @@ int Gdagdl::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
     const float* yo = ws + g.w_h[nl - 1];         // Y_o as [BT, D] rows
     const float* henc = ws + g.ae.w_enc[3];       // the encoder's output: the LSTM's input
     const unsigned ggrid = (unsigned)(g.G < 4096 ? g.G : 4096);
-    (void)hipGetLastError();
     // The projection weights as GEMM operands: the flat buffer puts them behind f + 1 floats and odd-sized tensors, off a 16-byte
     // boundary (seq_backend.hpp: aligned_operand).
     const float* wop[GD_MAXL];
@@ -460,8 +459,7 @@ int Gdagdl::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
         const size_t lds = sizeof(float) * gd_front_lds_floats(g.P, g.nseg, g.N, g.f);
         if (lds > DEFAULT_LDS_BYTES) return RULGNN_EUNSUPPORTED;
         RULGNN_TRY(fill_f32(one + 3, 1, 0.0f, st));
-        hipLaunchKernelGGL(gd_front_kernel, dim3(ggrid), dim3(SB), lds, st, g, a->x, prm, ws);
-        RULGNN_LAUNCH_OK();
+        RULGNN_TRY(launch_checked(gd_front_kernel, dim3(ggrid), dim3(SB), lds, st, g, a->x, prm, ws));
         const float* cur = ws + g.w_mag;
         for (int i = 0; i < nl; ++i) {
             const int Ci = g.C[i], Co = g.C[i + 1];
@@ -470,8 +468,7 @@ int Gdagdl::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
             RULGNN_TRY(gd_att_launch(gd_att_fwd_kernel, g, Co, false, &L));
             q.C = Co; q.waves = L.waves; q.z = ws + g.w_z[i]; q.bias = prm + g.o_b[i]; q.att = prm + g.o_aw[i]; q.h = ws + g.w_h[i];
             q.key = dropout_layer_key(a->seed, a->step, i);
-            hipLaunchKernelGGL(gd_att_fwd_kernel, dim3(L.grid), dim3(GD_WAVE * L.waves), L.lds, st, q);
-            RULGNN_LAUNCH_OK();
+            RULGNN_TRY(launch_checked(gd_att_fwd_kernel, dim3(L.grid), dim3(GD_WAVE * L.waves), L.lds, st, q));
             cur = ws + g.w_h[i];
         }
         RULGNN_TRY(autoencoder_forward(g.ae, yo, prm, ws, rscale, one + 1, split, st));
@@ -499,8 +496,7 @@ int Gdagdl::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
             q.C = Co; q.waves = L.waves; q.z = ws + g.w_z[i]; q.bias = prm + g.o_b[i]; q.att = prm + g.o_aw[i]; q.h = ws + g.w_h[i];
             q.dh = dcur; q.dz = ws + g.w_dz; q.part = ws + g.w_part;
             q.key = dropout_layer_key(a->seed, a->step, i);
-            hipLaunchKernelGGL(gd_att_bwd_kernel, dim3(L.grid), dim3(GD_WAVE * L.waves), L.lds, st, q);
-            RULGNN_LAUNCH_OK();
+            RULGNN_TRY(launch_checked(gd_att_bwd_kernel, dim3(L.grid), dim3(GD_WAVE * L.waves), L.lds, st, q));
             // attention.weight [2 Co] and attention.bias [1] are adjacent in the flat layout: one fixed-order sum of the partial rows
             RULGNN_TRY(rows_sum(ws + g.w_part, L.grid * L.waves, 2 * Co + 1, 2 * Co + 1, gr + g.o_aw[i], st));
             const float* hin = i > 0 ? ws + g.w_h[i - 1] : ws + g.w_mag;

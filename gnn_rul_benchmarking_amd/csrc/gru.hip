@@ -146,18 +146,17 @@ int gru_forward(const rulgnn_gru_shape* s, const rulgnn_gru_args* a, hipStream_t
     // gi[row][q] = sum_i x[row][i] W_ih[q][i]
     RULGNN_TRY(sgemm(a->x, g.I, 1, a->w_ih, g.I, 1, Fp(w.gi), g.H3, (int)g.R, g.H3, g.I, false, st));
     if (hipMemsetAsync(Fp(w.gh), 0, (size_t)g.R * g.H3 * sizeof(float), st) != hipSuccess) return RULGNN_EHIP;
-    (void)hipGetLastError();
     for (int t = 0; t < g.L; ++t) {
         if (t > 0) {
             // gh[s][q] = sum_j h_{t-1}[s][j] W_hh[q][j]; h_{t-1} = out[s, t-1, :] (row stride L*H)
             RULGNN_TRY(sgemm(a->out + (int64_t)(t - 1) * g.H, (int64_t)g.L * g.H, 1, a->w_hh, g.H, 1, Fp(w.ghstep), g.H3, (int)g.S, g.H3, g.H,
                          false, st));
-            hipLaunchKernelGGL(gru_rows_copy_kernel, dim3(blocks(g.S * g.H3)), dim3(256), 0, st, g, t, (const float*)Fp(w.ghstep), Fp(w.gh), 1);
+            RULGNN_TRY(launch_checked(gru_rows_copy_kernel, dim3(blocks(g.S * g.H3)), dim3(256), 0, st, g, t, (const float*)Fp(w.ghstep), Fp(w.gh), 1));
         }
-        hipLaunchKernelGGL(gru_gate_kernel, dim3(blocks(g.S * g.H)), dim3(256), 0, st, g, t, (const float*)Fp(w.gi), (const float*)Fp(w.ghstep),
-                           a->b_ih, a->b_hh, a->out, Fp(w.hprev));
+        RULGNN_TRY(launch_checked(gru_gate_kernel, dim3(blocks(g.S * g.H)), dim3(256), 0, st, g, t, (const float*)Fp(w.gi), (const float*)Fp(w.ghstep),
+                                  a->b_ih, a->b_hh, a->out, Fp(w.hprev)));
     }
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return RULGNN_OK;
 }
 
 int gru_backward(const rulgnn_gru_shape* s, const rulgnn_gru_args* a, hipStream_t st) {
@@ -174,13 +173,12 @@ int gru_backward(const rulgnn_gru_shape* s, const rulgnn_gru_args* a, hipStream_
     }
     const Workspace ws(a->workspace);
     auto Fp = [&](size_t off) { return ws.at<float>(off); };
-    (void)hipGetLastError();
     for (int t = g.L - 1; t >= 0; --t) {
-        hipLaunchKernelGGL(gru_gate_bwd_kernel, dim3(blocks(g.S * g.H)), dim3(256), 0, st, g, t, (const float*)Fp(w.gi), (const float*)Fp(w.gh),
-                           a->b_ih, a->b_hh, (const float*)Fp(w.hprev), a->dout, Fp(w.dh), Fp(w.dgi), Fp(w.dgh), t == g.L - 1 ? 1 : 0);
+        RULGNN_TRY(launch_checked(gru_gate_bwd_kernel, dim3(blocks(g.S * g.H)), dim3(256), 0, st, g, t, (const float*)Fp(w.gi), (const float*)Fp(w.gh),
+                                  a->b_ih, a->b_hh, (const float*)Fp(w.hprev), a->dout, Fp(w.dh), Fp(w.dgi), Fp(w.dgh), t == g.L - 1 ? 1 : 0));
         if (t > 0) {
             // dh[s][j] += sum_q dgh_t[s][q] W_hh[q][j]
-            hipLaunchKernelGGL(gru_rows_copy_kernel, dim3(blocks(g.S * g.H3)), dim3(256), 0, st, g, t, (const float*)Fp(w.dgh), Fp(w.dgstep), 0);
+            RULGNN_TRY(launch_checked(gru_rows_copy_kernel, dim3(blocks(g.S * g.H3)), dim3(256), 0, st, g, t, (const float*)Fp(w.dgh), Fp(w.dgstep), 0));
             RULGNN_TRY(sgemm(Fp(w.dgstep), g.H3, 1, a->w_hh, 1, g.H, Fp(w.dh), g.H, (int)g.S, g.H, g.H3, true, st));
         }
     }

@@ -248,10 +248,8 @@ int gru_persistent_forward(const rulgnn_gru_shape* s, const rulgnn_gru_args* a, 
     auto Fp = [&](size_t off) { return ws.at<float>(off); };
     // gi[row][q] = sum_i x[row][i] W_ih[q][i]
     RULGNN_TRY(sgemm(a->x, g.I, 1, a->w_ih, g.I, 1, Fp(w.gi), GS_H3, (int)g.R, GS_H3, g.I, false, st));
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(gru_seq_fwd_kernel, dim3(gs_tiles(g)), dim3(GS_BLOCK), 0, st, g, (const float*)Fp(w.gi), a->w_hh, a->b_ih, a->b_hh,
-                       a->out, Fp(w.gh), Fp(w.hprev));
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return launch_checked(gru_seq_fwd_kernel, dim3(gs_tiles(g)), dim3(GS_BLOCK), 0, st, g, (const float*)Fp(w.gi), a->w_hh, a->b_ih, a->b_hh,
+                          a->out, Fp(w.gh), Fp(w.hprev));
 }
 
 int gru_persistent_backward(const rulgnn_gru_shape* s, const rulgnn_gru_args* a, hipStream_t st) {
@@ -268,9 +266,8 @@ int gru_persistent_backward(const rulgnn_gru_shape* s, const rulgnn_gru_args* a,
     }
     const Workspace ws(a->workspace);
     auto Fp = [&](size_t off) { return ws.at<float>(off); };
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(gru_seq_bwd_kernel, dim3(gs_tiles(g)), dim3(GS_BLOCK), 0, st, g, (const float*)Fp(w.gi), (const float*)Fp(w.gh),
-                       (const float*)Fp(w.hprev), a->w_hh, a->b_ih, a->b_hh, a->dout, Fp(w.dgi), Fp(w.dgh));
+    RULGNN_TRY(launch_checked(gru_seq_bwd_kernel, dim3(gs_tiles(g)), dim3(GS_BLOCK), 0, st, g, (const float*)Fp(w.gi), (const float*)Fp(w.gh),
+                              (const float*)Fp(w.hprev), a->w_hh, a->b_ih, a->b_hh, a->dout, Fp(w.dgi), Fp(w.dgh)));
     RULGNN_TRY(fill_f32(Fp(w.one), g.R, 1.0f, st));
     // dW_ih[q][i] = sum_row dgi[row][q] x[row][i];  dW_hh[q][j] = sum_row dgh[row][q] hprev[row][j];  biases: column sums
     SplitKJob jobs[4];

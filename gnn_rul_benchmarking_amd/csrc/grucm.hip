@@ -438,19 +438,19 @@ void gc_ws(const GcGeom& g, GcWs* w) {
 }
 
 template <int HC, int BLK>
-void gc_launch_graph(const GcGeom& g, const GcDrop& d, const GcWs& w, bool bwd, const float* x, const float* prm, float* pooled,
-                     const float* dpooled, float* part, hipStream_t st) {
-    if (!bwd) hipLaunchKernelGGL((grucm_graph_fwd_kernel<HC, GC_FB>), dim3(w.fblocks), dim3(GC_FB), 0, st, g, d, x, prm, pooled);
-    else hipLaunchKernelGGL((grucm_graph_bwd_kernel<HC, BLK>), dim3(w.gblocks), dim3(BLK), 0, st, g, d, x, prm, dpooled, part);
+int gc_launch_graph(const GcGeom& g, const GcDrop& d, const GcWs& w, bool bwd, const float* x, const float* prm, float* pooled,
+                    const float* dpooled, float* part, hipStream_t st) {
+    if (!bwd) return launch_checked((grucm_graph_fwd_kernel<HC, GC_FB>), dim3(w.fblocks), dim3(GC_FB), 0, st, g, d, x, prm, pooled);
+    return launch_checked((grucm_graph_bwd_kernel<HC, BLK>), dim3(w.gblocks), dim3(BLK), 0, st, g, d, x, prm, dpooled, part);
 }
 
-void gc_graph(const GcGeom& g, const GcDrop& d, const GcWs& w, bool bwd, const float* x, const float* prm, float* pooled, const float* dpooled,
-              float* part, hipStream_t st) {
+int gc_graph(const GcGeom& g, const GcDrop& d, const GcWs& w, bool bwd, const float* x, const float* prm, float* pooled, const float* dpooled,
+             float* part, hipStream_t st) {
     switch (g.HC) {
-    case 4: gc_launch_graph<4, 256>(g, d, w, bwd, x, prm, pooled, dpooled, part, st); break;
-    case 7: gc_launch_graph<7, 128>(g, d, w, bwd, x, prm, pooled, dpooled, part, st); break;
-    case 10: gc_launch_graph<10, 128>(g, d, w, bwd, x, prm, pooled, dpooled, part, st); break;
-    default: gc_launch_graph<16, 64>(g, d, w, bwd, x, prm, pooled, dpooled, part, st); break;
+    case 4: return gc_launch_graph<4, 256>(g, d, w, bwd, x, prm, pooled, dpooled, part, st);
+    case 7: return gc_launch_graph<7, 128>(g, d, w, bwd, x, prm, pooled, dpooled, part, st);
+    case 10: return gc_launch_graph<10, 128>(g, d, w, bwd, x, prm, pooled, dpooled, part, st);
+    default: return gc_launch_graph<16, 64>(g, d, w, bwd, x, prm, pooled, dpooled, part, st);
     }
 }
 
@@ -514,29 +514,24 @@ int Grucm::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
     ga.w_ih = prm + o.wih; ga.w_hh = prm + o.whh; ga.b_ih = prm + o.bih; ga.b_hh = prm + o.bhh;
     ga.workspace = ws.at<void>(w.gru); ga.workspace_bytes = w.gru_bytes;
     ga.x = Fp(w.pooled);
-    (void)hipGetLastError();
     if (mode & 1) {
-        gc_graph(g, d, w, false, a->x, prm, Fp(w.pooled), nullptr, nullptr, st);
-        if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
+        RULGNN_TRY(gc_graph(g, d, w, false, a->x, prm, Fp(w.pooled), nullptr, nullptr, st));
         ga.out = Fp(w.hs);
         RULGNN_TRY(persistent ? gru_persistent_forward(&gs, &ga, st) : gru_forward(&gs, &ga, st));
         const float inv_gb = 1.0f / (float)(a->global_batch > 0 ? a->global_batch : g.B);
-        hipLaunchKernelGGL(grucm_head_kernel, dim3((unsigned)g.B), dim3(GC_HB), 0, st, g, d, (const float*)Fp(w.hs), prm + o.wout, prm + o.bout,
-                           a->y, a->pred, Fp(w.dpred), Fp(w.sqerr), inv_gb);
-        if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
+        RULGNN_TRY(launch_checked(grucm_head_kernel, dim3((unsigned)g.B), dim3(GC_HB), 0, st, g, d, (const float*)Fp(w.hs), prm + o.wout, prm + o.bout,
+                                  a->y, a->pred, Fp(w.dpred), Fp(w.sqerr), inv_gb));
     }
     if (mode & 2) {
         const float* dpred = a->dpred ? a->dpred : Fp(w.dpred);
         float* gr = a->grads;
-        hipLaunchKernelGGL(grucm_head_bwd_kernel, dim3((unsigned)((Q + 1 + GC_HB - 1) / GC_HB), (unsigned)w.hslices), dim3(GC_HB), 0, st, g, d,
-                           (const float*)Fp(w.hs), prm + o.wout, dpred, Fp(w.dhs), w.hslices == 1 ? gr + o.wout : Fp(w.hpart));
-        if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
+        RULGNN_TRY(launch_checked(grucm_head_bwd_kernel, dim3((unsigned)((Q + 1 + GC_HB - 1) / GC_HB), (unsigned)w.hslices), dim3(GC_HB), 0, st, g, d,
+                                  (const float*)Fp(w.hs), prm + o.wout, dpred, Fp(w.dhs), w.hslices == 1 ? gr + o.wout : Fp(w.hpart)));
         if (w.hslices > 1) RULGNN_TRY(rows_sum(Fp(w.hpart), w.hslices, Q + 1, Q + 1, gr + o.wout, st));
         ga.dout = Fp(w.dhs); ga.dx = Fp(w.dpooled);
         ga.dw_ih = gr + o.wih; ga.dw_hh = gr + o.whh; ga.db_ih = gr + o.bih; ga.db_hh = gr + o.bhh;
         RULGNN_TRY(persistent ? gru_persistent_backward(&gs, &ga, st) : gru_backward(&gs, &ga, st));
-        gc_graph(g, d, w, true, a->x, prm, nullptr, Fp(w.dpooled), Fp(w.gpart), st);
-        if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
+        RULGNN_TRY(gc_graph(g, d, w, true, a->x, prm, nullptr, Fp(w.dpooled), Fp(w.gpart), st));
         RULGNN_TRY(rows_sum(Fp(w.gpart), w.gblocks, o.graph, o.graph, gr, st));
         if (!a->dpred && a->loss) RULGNN_TRY(block_sum((const float*)Fp(w.sqerr), g.B, a->loss, st));
     }

@@ -526,12 +526,10 @@ int hagcn_graph_forward(const rulgnn_hagcn_shape* s, const rulgnn_hagcn_args* a,
     RULGNN_TRY(hg_geometry(s, &g));
     if (a->workspace_bytes < (size_t)g.total_floats * sizeof(float)) return RULGNN_EWORKSPACE;
     float* ws = static_cast<float*>(a->workspace);
-    (void)hipGetLastError();
     RULGNN_TRY(allow_dynamic_lds(hg_forward_kernel, HG_FWD_LDS));
-    hipLaunchKernelGGL(hg_forward_kernel, dim3(resident_rows(hg_forward_kernel, HB, HG_FWD_LDS, g.G, g.G)), dim3(HB), HG_FWD_LDS, st, g, a->nodes,
-                       a->params, ws, a->feats, a->topk, a->forced_topk);
-    hipLaunchKernelGGL(hg_kl_kernel, dim3(1), dim3(1024), 0, st, (const float*)(ws + g.t_kl), g.G * NLV, 1.0f / (float)g.G, a->kl);
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    RULGNN_TRY(launch_checked(hg_forward_kernel, dim3(resident_rows(hg_forward_kernel, HB, HG_FWD_LDS, g.G, g.G)), dim3(HB), HG_FWD_LDS, st, g, a->nodes,
+                              a->params, ws, a->feats, a->topk, a->forced_topk));
+    return launch_checked(hg_kl_kernel, dim3(1), dim3(1024), 0, st, (const float*)(ws + g.t_kl), g.G * NLV, 1.0f / (float)g.G, a->kl);
 }
 
 int hagcn_graph_backward(const rulgnn_hagcn_shape* s, const rulgnn_hagcn_args* a, hipStream_t st) {
@@ -539,10 +537,9 @@ int hagcn_graph_backward(const rulgnn_hagcn_shape* s, const rulgnn_hagcn_args* a
     RULGNN_TRY(hg_geometry(s, &g));
     if (a->workspace_bytes < (size_t)g.total_floats * sizeof(float)) return RULGNN_EWORKSPACE;
     float* ws = static_cast<float*>(a->workspace);
-    (void)hipGetLastError();
     RULGNN_TRY(allow_dynamic_lds(hg_backward_kernel, HG_BWD_LDS));
-    hipLaunchKernelGGL(hg_backward_kernel, dim3(resident_rows(hg_backward_kernel, HB, HG_BWD_LDS, g.G, g.G)), dim3(HB), HG_BWD_LDS, st, g, a->params, ws,
-                       a->dfeats, a->dkl, a->dnodes);
+    RULGNN_TRY(launch_checked(hg_backward_kernel, dim3(resident_rows(hg_backward_kernel, HB, HG_BWD_LDS, g.G, g.G)), dim3(HB), HG_BWD_LDS, st, g, a->params, ws,
+                              a->dfeats, a->dkl, a->dnodes));
     float* one = ws + g.t_one;
     float* split = ws + g.t_split;
     RULGNN_TRY(fill_f32(one, 1, 1.f, st));
@@ -555,7 +552,7 @@ int hagcn_graph_backward(const rulgnn_hagcn_shape* s, const rulgnn_hagcn_args* a
     } else if (hipMemsetAsync(a->grads, 0, sizeof(float) * (size_t)g.nparam, st) != hipSuccess) {      // (no graphs: every sum is empty)
         return RULGNN_EHIP;
     }
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return RULGNN_OK;
 }
 
 }  // namespace rulgnn

@@ -781,20 +781,18 @@ int hc_run(const HcGeom& g, const rulgnn_hiercorrpool_args* a, int mode, hipStre
     const int N = g.N, M = g.M, d = g.d, d3 = g.d3, e3 = g.e3, BM = (int)(B * M);
     HcGraphBufs gq{ws + g.w_enc, ws + g.w_xp, ws + g.w_ap, ws + g.w_axp, ws + g.w_dq, ws + g.w_dxp, ws + g.w_denc, ws + g.w_contrib};
     const float* dpred = a->dpred ? a->dpred : ws + g.w_dpred;
-    (void)hipGetLastError();
     if (mode & 1) {
         if (g.ns)
-            hipLaunchKernelGGL(hcpb_stft_input_kernel, dim3(hc_grid(g.blk[0].R, HCPB_GRID)), dim3(SB), sizeof(float) * stft_lds_floats(g.p, g.ns), st,
-                               B, N, g.w, g.P, g.p, g.ns, a->x, ws + g.blk[0].w_in);
+            RULGNN_TRY(launch_checked(hcpb_stft_input_kernel, dim3(hc_grid(g.blk[0].R, HCPB_GRID)), dim3(SB), sizeof(float) * stft_lds_floats(g.p, g.ns), st,
+                                      B, N, g.w, g.P, g.p, g.ns, a->x, ws + g.blk[0].w_in));
         else
-            hipLaunchKernelGGL(hc_pack_input_kernel, dim3(hc_blocks(g.blk[0].R * g.blk[0].Cin)), dim3(HC_GB), 0, st, B, N, g.P, g.p, a->x, ws + g.blk[0].w_in);
+            RULGNN_TRY(launch_checked(hc_pack_input_kernel, dim3(hc_blocks(g.blk[0].R * g.blk[0].Cin)), dim3(HC_GB), 0, st, B, N, g.P, g.p, a->x, ws + g.blk[0].w_in));
         HcPack pk{};
         for (int l = 0; l < 3; ++l) {
             const HcBlock& k = g.blk[l];
             pk.W[l] = prm + k.o_w; pk.Wp[l] = ws + k.w_wp; pk.Wt[l] = l > 0 ? ws + k.w_wt : nullptr; pk.Cin[l] = k.Cin; pk.Cout[l] = k.Cout;
         }
-        hipLaunchKernelGGL(hc_pack_weights_kernel<false>, dim3(hc_blocks((int64_t)g.blk[2].Cout * g.blk[2].Cin * HC_TAPS, 4096)), dim3(HC_GB), 0, st, pk);
-        RULGNN_LAUNCH_OK();
+        RULGNN_TRY(launch_checked(hc_pack_weights_kernel<false>, dim3(hc_blocks((int64_t)g.blk[2].Cout * g.blk[2].Cin * HC_TAPS, 4096)), dim3(HC_GB), 0, st, pk));
         for (int l = 0; l < 3; ++l) {
             const HcBlock& k = g.blk[l];
             // z [R - 7][Cout] = (overlapping-row view of the padded input) [R - 7][8 Cin] . Wp^T
@@ -804,40 +802,34 @@ int hc_run(const HcGeom& g, const rulgnn_hiercorrpool_args* a, int mode, hipStre
             const HcEpi q = hc_epi(g, l, ws, a);
             double* part = reinterpret_cast<double*>(ws + k.w_part);
             const int slices = (int)hc_grid((B * k.Lc + 31) / 32, HC_SLICES);
-            if (a->training) hipLaunchKernelGGL(hc_stats_kernel<false>, dim3((k.Cout + 63) / 64, slices), dim3(HC_GB), 0, st, q, part);
-            hipLaunchKernelGGL(hc_stats_finish_kernel<false>, dim3((k.Cout + 63) / 64), dim3(64), 0, st, k.Cout, slices, (double)(B * k.Lc),
-                               (const double*)part, prm + k.o_g, prm + k.o_b, ws + k.w_coef, ws + k.w_bcoef, a->bn_state + k.o_bn,
-                               a->training ? 1 : 0, (a->training && a->update_running_stats) ? 1 : 0, (float*)nullptr, (float*)nullptr);
-            hipLaunchKernelGGL(hc_epilogue_fwd_kernel, dim3(hc_blocks(B * q.orow * k.Cout)), dim3(HC_GB), 0, st, q);
-            RULGNN_LAUNCH_OK();
+            if (a->training) RULGNN_TRY(launch_checked(hc_stats_kernel<false>, dim3((k.Cout + 63) / 64, slices), dim3(HC_GB), 0, st, q, part));
+            RULGNN_TRY(launch_checked(hc_stats_finish_kernel<false>, dim3((k.Cout + 63) / 64), dim3(64), 0, st, k.Cout, slices, (double)(B * k.Lc),
+                                      (const double*)part, prm + k.o_g, prm + k.o_b, ws + k.w_coef, ws + k.w_bcoef, a->bn_state + k.o_bn,
+                                      a->training ? 1 : 0, (a->training && a->update_running_stats) ? 1 : 0, (float*)nullptr, (float*)nullptr));
+            RULGNN_TRY(launch_checked(hc_epilogue_fwd_kernel, dim3(hc_blocks(B * q.orow * k.Cout)), dim3(HC_GB), 0, st, q));
         }
         RULGNN_TRY(allow_dynamic_lds(hcp_graph_fwd, g.lds_fwd));
-        hipLaunchKernelGGL(hcp_graph_fwd, dim3(hc_grid(B, 8192)), dim3(HC_GB), g.lds_fwd, st, g, prm, gq);
-        RULGNN_LAUNCH_OK();
+        RULGNN_TRY(launch_checked(hcp_graph_fwd, dim3(hc_grid(B, 8192)), dim3(HC_GB), g.lds_fwd, st, g, prm, gq));
         // H = leaky((A' X') Wt^T + bt); pre0 = H.flat fc_0^T
         RULGNN_TRY(sgemm(ws + g.w_axp, d, 1, prm + g.o_tw, d, 1, ws + g.w_H, d3, BM, d3, d, false, st));
-        hipLaunchKernelGGL(hc_bias_leaky_kernel<false>, dim3(hc_blocks((int64_t)BM * d3)), dim3(HC_GB), 0, st, (int64_t)BM, d3, ws + g.w_H, prm + g.o_tb,
-                           (const float*)nullptr);
-        RULGNN_LAUNCH_OK();
+        RULGNN_TRY(launch_checked(hc_bias_leaky_kernel<false>, dim3(hc_blocks((int64_t)BM * d3)), dim3(HC_GB), 0, st, (int64_t)BM, d3, ws + g.w_H, prm + g.o_tb,
+                                  (const float*)nullptr));
         RULGNN_TRY(sgemm_splitk(ws + g.w_H, (int64_t)M * d3, 1, prm + g.o_f0w, (int64_t)M * d3, 1, ws + g.w_pre0, e3, (int)B, e3, M * d3, false,
                                 ws + g.w_split, st));
-        hipLaunchKernelGGL(hc_head_kernel, dim3(hc_blocks(B, 4096)), dim3(HC_GB), 0, st, g, prm, ws + g.w_pre0, ws + g.w_pre1, a->y, a->pred, ws + g.w_sq,
-                           ws + g.w_dpred, 1.0f / (float)gb);
-        RULGNN_LAUNCH_OK();
+        RULGNN_TRY(launch_checked(hc_head_kernel, dim3(hc_blocks(B, 4096)), dim3(HC_GB), 0, st, g, prm, ws + g.w_pre0, ws + g.w_pre1, a->y, a->pred, ws + g.w_sq,
+                                  ws + g.w_dpred, 1.0f / (float)gb));
         if (a->y && a->loss) RULGNN_TRY(block_sum((const float*)(ws + g.w_sq), B, a->loss, st));
     }
     if (mode & 2) {
         if (!a->grads) return RULGNN_EINVAL;
         float* gr = a->grads;
-        hipLaunchKernelGGL(hc_head_bwd_kernel, dim3(hc_blocks(B, 4096)), dim3(HC_GB), 0, st, g, prm, (const float*)(ws + g.w_pre0), (const float*)(ws + g.w_pre1),
-                           dpred, ws + g.w_prod, ws + g.w_dpre0, gr);
-        RULGNN_LAUNCH_OK();
+        RULGNN_TRY(launch_checked(hc_head_bwd_kernel, dim3(hc_blocks(B, 4096)), dim3(HC_GB), 0, st, g, prm, (const float*)(ws + g.w_pre0), (const float*)(ws + g.w_pre1),
+                                  dpred, ws + g.w_prod, ws + g.w_dpre0, gr));
         // g fc_0.weight [3e][3dM] = dpre0^T H.flat (k = the batch, one fixed-order product); dH = dpre0 fc_0
         RULGNN_TRY(sgemm(ws + g.w_dpre0, 1, e3, ws + g.w_H, 1, (int64_t)M * d3, gr + g.o_f0w, (int64_t)M * d3, e3, M * d3, (int)B, false, st));
         RULGNN_TRY(sgemm(ws + g.w_dpre0, e3, 1, prm + g.o_f0w, 1, (int64_t)M * d3, ws + g.w_dH, (int64_t)M * d3, (int)B, M * d3, e3, false, st));
-        hipLaunchKernelGGL(hc_bias_leaky_kernel<true>, dim3(hc_blocks((int64_t)BM * d3)), dim3(HC_GB), 0, st, (int64_t)BM, d3, ws + g.w_dH,
-                           (const float*)nullptr, (const float*)(ws + g.w_H));
-        RULGNN_LAUNCH_OK();
+        RULGNN_TRY(launch_checked(hc_bias_leaky_kernel<true>, dim3(hc_blocks((int64_t)BM * d3)), dim3(HC_GB), 0, st, (int64_t)BM, d3, ws + g.w_dH,
+                                  (const float*)nullptr, (const float*)(ws + g.w_H)));
         {   // [g fc_1.weight | g fc_1.bias], g fc_0.bias and g theta.bias: three fixed-order column sums in one launch
             const float* const part[3] = {ws + g.w_prod, ws + g.w_dpre0, ws + g.w_dH};
             float* const out[3] = {gr + g.o_f1w, gr + g.o_f0b, gr + g.o_tb};
@@ -849,8 +841,7 @@ int hc_run(const HcGeom& g, const rulgnn_hiercorrpool_args* a, int mode, hipStre
         RULGNN_TRY(sgemm_splitk(ws + g.w_dH, 1, d3, ws + g.w_axp, 1, d, gr + g.o_tw, d, d3, d, BM, false, ws + g.w_split, st));
         RULGNN_TRY(sgemm(ws + g.w_dH, d3, 1, prm + g.o_tw, 1, d, ws + g.w_dq, d, BM, d, d3, false, st));
         RULGNN_TRY(allow_dynamic_lds(hcp_graph_bwd, g.lds_bwd));
-        hipLaunchKernelGGL(hcp_graph_bwd, dim3(hc_grid(B, 8192)), dim3(HC_GB), g.lds_bwd, st, g, prm, gq);
-        RULGNN_LAUNCH_OK();
+        RULGNN_TRY(launch_checked(hcp_graph_bwd, dim3(hc_grid(B, 8192)), dim3(HC_GB), g.lds_bwd, st, g, prm, gq));
         // [g Wd | g bd | g Wm] = the samples' contributions in order (contiguous in the parameter layout)
         RULGNN_TRY(rows_sum(ws + g.w_contrib, (int)B, g.CW, g.CW, gr + g.o_wd, st));
         HcPack up{};
@@ -859,11 +850,10 @@ int hc_run(const HcGeom& g, const rulgnn_hiercorrpool_args* a, int mode, hipStre
             const HcEpi q = hc_epi(g, l, ws, a);
             double* part = reinterpret_cast<double*>(ws + k.w_part);
             const int slices = (int)hc_grid((B * k.Lc + 31) / 32, HC_SLICES);
-            hipLaunchKernelGGL(hc_stats_kernel<true>, dim3((k.Cout + 63) / 64, slices), dim3(HC_GB), 0, st, q, part);
-            hipLaunchKernelGGL(hc_stats_finish_kernel<true>, dim3((k.Cout + 63) / 64), dim3(64), 0, st, k.Cout, slices, (double)(B * k.Lc),
-                               (const double*)part, prm + k.o_g, prm + k.o_b, ws + k.w_coef, ws + k.w_bcoef, (float*)nullptr, 1, 0, gr + k.o_g, gr + k.o_b);
-            hipLaunchKernelGGL(hc_dz_kernel, dim3(hc_blocks((k.R + 7) * k.Cout)), dim3(HC_GB), 0, st, q, prm + k.o_g);
-            RULGNN_LAUNCH_OK();
+            RULGNN_TRY(launch_checked(hc_stats_kernel<true>, dim3((k.Cout + 63) / 64, slices), dim3(HC_GB), 0, st, q, part));
+            RULGNN_TRY(launch_checked(hc_stats_finish_kernel<true>, dim3((k.Cout + 63) / 64), dim3(64), 0, st, k.Cout, slices, (double)(B * k.Lc),
+                                      (const double*)part, prm + k.o_g, prm + k.o_b, ws + k.w_coef, ws + k.w_bcoef, (float*)nullptr, 1, 0, gr + k.o_g, gr + k.o_b));
+            RULGNN_TRY(launch_checked(hc_dz_kernel, dim3(hc_blocks((k.R + 7) * k.Cout)), dim3(HC_GB), 0, st, q, prm + k.o_g));
             const float* dz = ws + k.w_dz + (int64_t)7 * k.Cout;           // row r of z's numbering
             // d Wp [Cout][8 Cin] = dz^T . view, k = the R - 7 rows in fixed slices
             RULGNN_TRY(sgemm_splitk(dz, 1, k.Cout, ws + k.w_in, 1, k.Cin, ws + k.w_dwp, (int64_t)HC_TAPS * k.Cin, k.Cout, HC_TAPS * k.Cin, (int)(k.R - 7),
@@ -874,8 +864,7 @@ int hc_run(const HcGeom& g, const rulgnn_hiercorrpool_args* a, int mode, hipStre
                                         HC_TAPS * k.Cout, false, ws + g.w_split, st));
             up.W[l] = ws + k.w_dwp; up.Wp[l] = gr + k.o_w; up.Wt[l] = nullptr; up.Cin[l] = k.Cin; up.Cout[l] = k.Cout;
         }
-        hipLaunchKernelGGL(hc_pack_weights_kernel<true>, dim3(hc_blocks((int64_t)g.blk[2].Cout * g.blk[2].Cin * HC_TAPS, 4096)), dim3(HC_GB), 0, st, up);
-        RULGNN_LAUNCH_OK();
+        RULGNN_TRY(launch_checked(hc_pack_weights_kernel<true>, dim3(hc_blocks((int64_t)g.blk[2].Cout * g.blk[2].Cin * HC_TAPS, 4096)), dim3(HC_GB), 0, st, up));
     }
     return RULGNN_OK;
 }

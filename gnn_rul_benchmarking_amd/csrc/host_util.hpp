@@ -1,4 +1,4 @@
-// Host-side plumbing the family drivers share, next to launch.hpp: the return-on-error and launch-check macros, the workspace carver
+// Host-side plumbing the family drivers share, next to launch.hpp: the return-on-error macro, the workspace carver
 // and its typed read-back, the dropout constants and the "resident rows" clamp.  Host only: nothing here is compiled for the device.
 #pragma once
 #include <stddef.h>
@@ -12,12 +12,6 @@
     do {                                   \
         const int rc_ = (__VA_ARGS__);     \
         if (rc_ != RULGNN_OK) return rc_;  \
-    } while (0)
-
-// Behind a kernel launch: leave the enclosing function with RULGNN_EHIP if the runtime refused it.
-#define RULGNN_LAUNCH_OK()                                       \
-    do {                                                         \
-        if (hipGetLastError() != hipSuccess) return RULGNN_EHIP; \
     } while (0)
 
 namespace rulgnn {

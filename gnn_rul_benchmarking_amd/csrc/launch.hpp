@@ -15,20 +15,23 @@ constexpr size_t DEFAULT_LDS_BYTES = 48 * 1024;     // what a kernel may request
 // runtime refuses the raise.  The attribute belongs to one kernel on one device, so the raise is asked of the runtime on every call for
 // the kernel and the current device: any memo would have to be keyed by (kernel address, device), never by the kernel's type -- kernels
 // that differ only in template arguments share their pointer type -- and never process-wide.
-inline int allow_dynamic_lds(const void* kernel, size_t bytes, size_t cap = MAX_LDS_BYTES) {
+[[nodiscard]] inline int allow_dynamic_lds(const void* kernel, size_t bytes, size_t cap = MAX_LDS_BYTES) {
     if (bytes > cap) return RULGNN_EUNSUPPORTED;
     if (bytes > DEFAULT_LDS_BYTES && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess)
         return RULGNN_EHIP;
     return RULGNN_OK;
 }
 template <typename... A>
-inline int allow_dynamic_lds(void (*kernel)(A...), size_t bytes, size_t cap = MAX_LDS_BYTES) {
+[[nodiscard]] inline int allow_dynamic_lds(void (*kernel)(A...), size_t bytes, size_t cap = MAX_LDS_BYTES) {
     return allow_dynamic_lds(reinterpret_cast<const void*>(kernel), bytes, cap);
 }
 
-// Launch tail: drop any stale error of the caller's earlier HIP calls, launch, report this launch's own error.
+// The one way to launch a kernel (with launch_checked_ev, aux_stream.hpp): drop any stale error of the caller's earlier HIP calls, launch,
+// report this launch's own error.  Every launch's status is checked (RULGNN_TRY) or returned; [[nodiscard]] and -Werror=unused-result hold
+// the callers to it, tests/test_launch_sites_cpu.py keeps raw launches out of the other files.  The arguments convert to the kernel's
+// parameter types at the launch; a kernel's default arguments do not exist behind the pointer and have to be passed.
 template <typename... P, typename... A>
-inline int launch_checked(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, const A&... args) {
+[[nodiscard]] inline int launch_checked(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t stream, const A&... args) {
     (void)hipGetLastError();
     hipLaunchKernelGGL(kernel, grid, block, lds, stream, args...);
     return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;

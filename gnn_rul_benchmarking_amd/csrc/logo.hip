@@ -862,44 +862,38 @@ int lg_run(const LgGeom& g, const rulgnn_logo_args* a, int mode, hipStream_t st)
         la->workspace = ws + k.w_ws;
         la->workspace_bytes = k.ws_bytes;
     };
-    (void)hipGetLastError();
     if (mode & 1) {
         const auto graph_fwd = g.ns > 0 ? lg_graph_fwd<true> : lg_graph_fwd<false>;
         RULGNN_TRY(allow_dynamic_lds(graph_fwd, g.lds_fwd));
-        hipLaunchKernelGGL(graph_fwd, dim3((unsigned)(B > 8192 ? 8192 : B)), dim3(LG_GB), g.lds_fwd, st, g, a->x, prm, ws + g.w_hg, ws + g.w_glpart);
-        RULGNN_LAUNCH_OK();
+        RULGNN_TRY(launch_checked(graph_fwd, dim3((unsigned)(B > 8192 ? 8192 : B)), dim3(LG_GB), g.lds_fwd, st, g, a->x, prm, ws + g.w_hg, ws + g.w_glpart));
         for (int l = 0; l < 3; ++l) {
             rulgnn_bilstm_shape ls;
             rulgnn_bilstm_args la;
             lstm_args(l, &ls, &la);
             RULGNN_TRY(bilstm_forward(&ls, &la, st, 2));
-            if (l == 1 && drop) hipLaunchKernelGGL(lg_drop_kernel, dim3(lg_blocks(QB * H2)), dim3(LG_GB), 0, st, QB * H2, ws + g.w_o2, key2, dc.thr, dscale);
+            if (l == 1 && drop) RULGNN_TRY(launch_checked(lg_drop_kernel, dim3(lg_blocks(QB * H2)), dim3(LG_GB), 0, st, QB * H2, ws + g.w_o2, key2, dc.thr, dscale));
         }
-        hipLaunchKernelGGL(lg_close_kernel<false>, dim3(lg_blocks(QB * H1)), dim3(LG_GB), 0, st, B, Q, H1, (const float*)(ws + g.w_o3), (const float*)nullptr,
-                           ws + g.w_td, key3, dc.thr, dscale);
-        RULGNN_LAUNCH_OK();
+        RULGNN_TRY(launch_checked(lg_close_kernel<false>, dim3(lg_blocks(QB * H1)), dim3(LG_GB), 0, st, B, Q, H1, (const float*)(ws + g.w_o3), (const float*)nullptr,
+                                  ws + g.w_td, key3, dc.thr, dscale));
         // pre1 [B][16] = td [B][Q 3h] fc1^T: a few tiles over k = Q 3h, in fixed slices
         RULGNN_TRY(sgemm_splitk(ws + g.w_td, K1, 1, prm + g.o_f1w, K1, 1, ws + g.w_pre1, LG_F1, (int)B, LG_F1, K1, false, ws + g.w_split, st));
-        hipLaunchKernelGGL(lg_head_kernel, dim3(lg_blocks(B, 4096)), dim3(LG_GB), 0, st, g, prm, ws + g.w_pre1, ws + g.w_a2, a->y, a->pred, ws + g.w_sq,
-                           ws + g.w_dpred, 1.0f / (float)gb);
-        hipLaunchKernelGGL(lg_loss_kernel, dim3(1), dim3(LG_GB), 0, st, B, cnt, a->theta, a->gamma, (const float*)(ws + g.w_glpart),
-                           a->y ? (const float*)(ws + g.w_sq) : (const float*)nullptr, ws + g.w_gl, a->loss_gl, a->loss);
-        RULGNN_LAUNCH_OK();
+        RULGNN_TRY(launch_checked(lg_head_kernel, dim3(lg_blocks(B, 4096)), dim3(LG_GB), 0, st, g, prm, ws + g.w_pre1, ws + g.w_a2, a->y, a->pred, ws + g.w_sq,
+                                  ws + g.w_dpred, 1.0f / (float)gb));
+        RULGNN_TRY(launch_checked(lg_loss_kernel, dim3(1), dim3(LG_GB), 0, st, B, cnt, a->theta, a->gamma, (const float*)(ws + g.w_glpart),
+                                  a->y ? (const float*)(ws + g.w_sq) : (const float*)nullptr, ws + g.w_gl, a->loss_gl, a->loss));
     }
     if (mode & 2) {
         if (!a->grads) return RULGNN_EINVAL;
         float* gr = a->grads;
-        hipLaunchKernelGGL(lg_head_bwd_kernel, dim3(lg_blocks(B, 4096)), dim3(LG_GB), 0, st, g, prm, (const float*)(ws + g.w_pre1), (const float*)(ws + g.w_a2),
-                           dpred, ws + g.w_prod, ws + g.w_dpre1);
-        RULGNN_LAUNCH_OK();
+        RULGNN_TRY(launch_checked(lg_head_bwd_kernel, dim3(lg_blocks(B, 4096)), dim3(LG_GB), 0, st, g, prm, (const float*)(ws + g.w_pre1), (const float*)(ws + g.w_a2),
+                                  dpred, ws + g.w_prod, ws + g.w_dpre1));
         // [g fc1.bias .. g cls.bias] = the samples' rows in order (contiguous in the parameter layout)
         RULGNN_TRY(rows_sum(ws + g.w_prod, (int)B, LG_HEADROW, LG_HEADROW, gr + g.o_f1b, st));
         // g fc1.weight [16][Q 3h] = dpre1^T td (k = the batch, one fixed-order product); dtd = dpre1 fc1
         RULGNN_TRY(sgemm(ws + g.w_dpre1, 1, LG_F1, ws + g.w_td, 1, K1, gr + g.o_f1w, K1, LG_F1, K1, (int)B, false, st));
         RULGNN_TRY(sgemm(ws + g.w_dpre1, LG_F1, 1, prm + g.o_f1w, 1, K1, ws + g.w_dtd, K1, (int)B, K1, LG_F1, false, st));
-        hipLaunchKernelGGL(lg_close_kernel<true>, dim3(lg_blocks(QB * H1)), dim3(LG_GB), 0, st, B, Q, H1, (const float*)(ws + g.w_dtd),
-                           (const float*)(ws + g.w_td), ws + g.w_do3, key3, dc.thr, dscale);
-        RULGNN_LAUNCH_OK();
+        RULGNN_TRY(launch_checked(lg_close_kernel<true>, dim3(lg_blocks(QB * H1)), dim3(LG_GB), 0, st, B, Q, H1, (const float*)(ws + g.w_dtd),
+                                  (const float*)(ws + g.w_td), ws + g.w_do3, key3, dc.thr, dscale));
         for (int l = 2; l >= 0; --l) {
             const LgLstm& k = g.lstm[l];
             rulgnn_bilstm_shape ls;
@@ -911,14 +905,12 @@ int lg_run(const LgGeom& g, const rulgnn_logo_args* a, int mode, hipStream_t st)
                 la.dw_ih[d] = gr + k.o_wih[d]; la.dw_hh[d] = gr + k.o_whh[d]; la.db_ih[d] = gr + k.o_bih[d]; la.db_hh[d] = gr + k.o_bhh[d];
             }
             RULGNN_TRY(bilstm_backward(&ls, &la, st, 2));
-            if (l == 2 && drop) hipLaunchKernelGGL(lg_drop_kernel, dim3(lg_blocks(QB * H2)), dim3(LG_GB), 0, st, QB * H2, ws + g.w_do2, key2, dc.thr, dscale);
+            if (l == 2 && drop) RULGNN_TRY(launch_checked(lg_drop_kernel, dim3(lg_blocks(QB * H2)), dim3(LG_GB), 0, st, QB * H2, ws + g.w_do2, key2, dc.thr, dscale));
         }
-        RULGNN_LAUNCH_OK();
         const auto graph_bwd = g.ns > 0 ? lg_graph_bwd<true> : lg_graph_bwd<false>;
         RULGNN_TRY(allow_dynamic_lds(graph_bwd, g.lds_bwd));
-        hipLaunchKernelGGL(graph_bwd, dim3((unsigned)g.rows), dim3(LG_GB), g.lds_bwd, st, g, a->x, prm, (const float*)(ws + g.w_dhg),
-                           (const float*)(ws + g.w_gl), a->theta, a->gamma, ws + g.w_part);
-        RULGNN_LAUNCH_OK();
+        RULGNN_TRY(launch_checked(graph_bwd, dim3((unsigned)g.rows), dim3(LG_GB), g.lds_bwd, st, g, a->x, prm, (const float*)(ws + g.w_dhg),
+                                  (const float*)(ws + g.w_gl), a->theta, a->gamma, ws + g.w_part));
         RULGNN_TRY(rows_sum(ws + g.w_part, g.rows, g.CW, g.nA, gr + g.o_wn, st));
         RULGNN_TRY(rows_sum(ws + g.w_part + g.nA, g.rows, g.CW, g.nB, gr + g.o_fu, st));
     }

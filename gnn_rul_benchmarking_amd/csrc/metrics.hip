@@ -67,10 +67,8 @@ int rul_metrics(const float* pred, const float* real, int64_t n, float max_rul, 
     if (!workspace || workspace_bytes < rul_metrics_workspace_bytes(n)) return RULGNN_EWORKSPACE;
     const int nb = metric_blocks(n);
     double* partial = static_cast<double*>(workspace);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(rul_metrics_partial_kernel, dim3(nb), dim3(MB), 0, st, pred, real, n, (double)max_rul, partial);
-    hipLaunchKernelGGL(rul_metrics_final_kernel, dim3(1), dim3(64), 0, st, (const double*)partial, nb, n, (double)max_rul, out, raw);
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    RULGNN_TRY(launch_checked(rul_metrics_partial_kernel, dim3(nb), dim3(MB), 0, st, pred, real, n, (double)max_rul, partial));
+    return launch_checked(rul_metrics_final_kernel, dim3(1), dim3(64), 0, st, (const double*)partial, nb, n, (double)max_rul, out, raw);
 }
 
 }  // namespace rulgnn

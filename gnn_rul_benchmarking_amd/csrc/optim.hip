@@ -141,8 +141,7 @@ __global__ __launch_bounds__(128) void cells_collapse_kernel(double* __restrict_
 int sync_cells(const SyncHook* h, double* cells, int off, int n, int replica_stride, hipStream_t st) {
     if (!h) return RULGNN_OK;
     if (n < 1 || n > 128) return RULGNN_EINVAL;
-    hipLaunchKernelGGL(cells_collapse_kernel, dim3(1), dim3(n <= 64 ? 64 : 128), 0, st, cells, off, n, replica_stride);
-    if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
+    RULGNN_TRY(launch_checked(cells_collapse_kernel, dim3(1), dim3(n <= 64 ? 64 : 128), 0, st, cells, off, n, replica_stride));
     return h->fn(h->user, cells + off, n, st) == 0 ? RULGNN_OK : RULGNN_ECALLBACK;
 }
 
@@ -154,27 +153,21 @@ int fill_f32(float* p, int64_t n, float v, hipStream_t st) {
     if (n > 0) {
         const int block = n < 256 ? 64 : 256;
         const int64_t grid = (n + block - 1) / block;
-        hipLaunchKernelGGL(fill_f32_kernel, dim3((unsigned)(grid > 1024 ? 1024 : grid)), dim3(block), 0, st, p, n, v);
+        RULGNN_TRY(launch_checked(fill_f32_kernel, dim3((unsigned)(grid > 1024 ? 1024 : grid)), dim3(block), 0, st, p, n, v));
     }
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return RULGNN_OK;
 }
 
 int step_state_set(void* state, uint64_t dropout_step, int64_t adam_step, hipStream_t stream) {
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(step_state_set_kernel, dim3(1), dim3(1), 0, stream, static_cast<StepState*>(state), dropout_step, adam_step);
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return launch_checked(step_state_set_kernel, dim3(1), dim3(1), 0, stream, static_cast<StepState*>(state), dropout_step, adam_step);
 }
 
 int step_prepare_dropout(void* state, uint64_t seed, int num_layers, hipStream_t stream) {
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(step_prepare_dropout_kernel, dim3(1), dim3(1), 0, stream, static_cast<StepState*>(state), seed, num_layers);
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return launch_checked(step_prepare_dropout_kernel, dim3(1), dim3(1), 0, stream, static_cast<StepState*>(state), seed, num_layers);
 }
 
 int step_prepare_adam(void* state, float lr, float beta1, float beta2, hipStream_t stream) {
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(step_prepare_adam_kernel, dim3(1), dim3(1), 0, stream, static_cast<StepState*>(state), lr, beta1, beta2);
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return launch_checked(step_prepare_adam_kernel, dim3(1), dim3(1), 0, stream, static_cast<StepState*>(state), lr, beta1, beta2);
 }
 
 int adam_step(float* p, const float* g, float* m, float* v, int64_t n, int64_t step, float lr, float beta1, float beta2,
@@ -189,11 +182,9 @@ int adam_step(float* p, const float* g, float* m, float* v, int64_t n, int64_t s
     const int block = 256;
     int64_t grid = (n + block - 1) / block;
     if (grid > 1024) grid = 1024;
-    (void)hipGetLastError();   // drop any stale error of the caller's earlier HIP calls
-    hipLaunchKernelGGL(adam_step_kernel, dim3((unsigned)grid), dim3(block), 0, stream, p, g, m, v, n,
-                       (float)((double)lr / bc1), (float)(1.0 / sqrt(bc2)), beta1, beta2, eps, wd, gscale,
-                       static_cast<const StepState*>(step_state), guard);
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return launch_checked(adam_step_kernel, dim3((unsigned)grid), dim3(block), 0, stream, p, g, m, v, n,
+                          (float)((double)lr / bc1), (float)(1.0 / sqrt(bc2)), beta1, beta2, eps, wd, gscale,
+                          static_cast<const StepState*>(step_state), guard);
 }
 
 int bn_running_update(float* bn, const float* batch, int num_layers, int64_t count, float momentum, int from_moments,
@@ -201,10 +192,8 @@ int bn_running_update(float* bn, const float* batch, int num_layers, int64_t cou
     const int n_bn = num_layers * 2;
     const float unbias = count > 1 ? (float)((double)count / (double)(count - 1)) : 1.f;
     const int total = n_bn * 2 * F;
-    (void)hipGetLastError();   // drop any stale error of the caller's earlier HIP calls
-    hipLaunchKernelGGL(bn_running_update_kernel, dim3((total + 255) / 256), dim3(256), 0, stream, bn, batch, n_bn,
-                       momentum, unbias, from_moments, guard);
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return launch_checked(bn_running_update_kernel, dim3((total + 255) / 256), dim3(256), 0, stream, bn, batch, n_bn,
+                          momentum, unbias, from_moments, guard);
 }
 
 // the constants adam_step passes to its kernel, for a step kernel that applies the update itself (adam_device.hpp: AdamFuse)
@@ -228,11 +217,9 @@ int adam_bn_step(float* p, const float* g, float* m, float* v, int64_t n, int64_
     int64_t grid = (n + block - 1) / block;
     if (grid > 1024) grid = 1024;
     if (grid < 1) grid = 1;
-    (void)hipGetLastError();   // drop any stale error of the caller's earlier HIP calls
-    hipLaunchKernelGGL(adam_bn_step_kernel, dim3((unsigned)grid + 1), dim3(block), 0, stream, p, g, m, v, n, (float)((double)lr / bc1),
-                       (float)(1.0 / sqrt(bc2)), beta1, beta2, eps, wd, gscale, bn, batch, num_layers * 2, momentum, unbias,
-                       from_moments, guard);
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return launch_checked(adam_bn_step_kernel, dim3((unsigned)grid + 1), dim3(block), 0, stream, p, g, m, v, n, (float)((double)lr / bc1),
+                          (float)(1.0 / sqrt(bc2)), beta1, beta2, eps, wd, gscale, bn, batch, num_layers * 2, momentum, unbias,
+                          from_moments, guard);
 }
 
 }  // namespace rulgnn

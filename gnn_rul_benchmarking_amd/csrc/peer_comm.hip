@@ -26,6 +26,7 @@
 #include <new>
 
 #include "../../include/rulgnn.h"
+#include "host_util.hpp"
 
 namespace rulgnn {
 namespace {
@@ -143,10 +144,8 @@ int rulgnn_peer_allreduce_f64(void* comm, double* device_buf, int32_t count, voi
     if (!c || !device_buf || count < 0 || count > PEER_MAX_COUNT) return RULGNN_EINVAL;
     if (count == 0) return RULGNN_OK;
     ++c->seq;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(peer_allreduce_kernel, dim3(1), dim3(PEER_MAX_COUNT), 0, static_cast<hipStream_t>(stream), device_buf, (int)count, c->peers,
-                       c->rank, c->world, c->seq, c->timeout_ticks);
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return launch_checked(peer_allreduce_kernel, dim3(1), dim3(PEER_MAX_COUNT), 0, static_cast<hipStream_t>(stream), device_buf, (int)count, c->peers,
+                          c->rank, c->world, c->seq, c->timeout_ticks);
 }
 int64_t rulgnn_peer_comm_collectives(void* comm) { return comm ? (int64_t)static_cast<PeerComm*>(comm)->seq : -1; }
 // 0: every collective completed so far found its peers; otherwise the number of the (last) collective that timed out.  Synchronises

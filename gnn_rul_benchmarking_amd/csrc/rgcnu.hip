@@ -1114,53 +1114,46 @@ int Rgcnu::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
     const int blocks = g.blocks, gblocks = scl_mx ? (g.gblocks + 1) / 2 : g.gblocks;
     const size_t lds_scl = sizeof(float) * ((size_t)g.N * g.N + 2 * g.N + 3 * (size_t)g.N * g.H + (size_t)g.H * (g.H + 1));
     const size_t lds_sclb = sizeof(float) * ((size_t)g.N * g.N + 4 * g.N + 5 * (size_t)g.N * g.H + (size_t)g.H * (g.H + 1));
-    (void)hipGetLastError();
     if (mode & 1) {
-        hipLaunchKernelGGL(rg_adj_kernel, dim3(blocks), dim3(RB), 0, st, g, a->x, prm, ws);
+        RULGNN_TRY(launch_checked(rg_adj_kernel, dim3(blocks), dim3(RB), 0, st, g, a->x, prm, ws));
         if (scl_mx) {
             const size_t lm = rg_scl_mx_lds(scl_nt, false);
             auto go = [&](auto kernel) -> int {
                 RULGNN_TRY(allow_dynamic_lds(kernel, lm));
-                hipLaunchKernelGGL(kernel, dim3((unsigned)gblocks), dim3(64 * RG_MXW), lm, st, g, a->x, prm, ws, key, thr, scale, a->sample_offset);
-                return RULGNN_OK;
+                return launch_checked(kernel, dim3((unsigned)gblocks), dim3(64 * RG_MXW), lm, st, g, a->x, prm, ws, key, thr, scale, a->sample_offset);
             };
             RULGNN_TRY(scl_nt == 1 ? go(rg_scl_mx_kernel<1>) : go(rg_scl_mx_kernel<2>));
         } else
-        hipLaunchKernelGGL(rg_scl_kernel, dim3((unsigned)gblocks), dim3(RB), lds_scl, st, g, a->x, prm, ws, key, thr, scale, a->sample_offset);
-        if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
+        RULGNN_TRY(launch_checked(rg_scl_kernel, dim3((unsigned)gblocks), dim3(RB), lds_scl, st, g, a->x, prm, ws, key, thr, scale, a->sample_offset));
         RULGNN_TRY(bilstm_forward(&ls, &la, st, 1));
         const size_t lds = rg_fusion_lds(g, false);
         RULGNN_TRY(allow_dynamic_lds(rg_fusion_kernel, lds));
         if (rg_fusion_mx_ok(g))
-            hipLaunchKernelGGL(rg_fusion_mx_kernel, dim3(blocks), dim3(RB), 0, st, g, a->x, a->y, prm, ws, a->pred, a->std_pred, inv_gb);
+            RULGNN_TRY(launch_checked(rg_fusion_mx_kernel, dim3(blocks), dim3(RB), 0, st, g, a->x, a->y, prm, ws, a->pred, a->std_pred, inv_gb));
         else
-        hipLaunchKernelGGL(rg_fusion_kernel, dim3(blocks), dim3(RB), lds, st, g, a->x, a->y, prm, ws, a->pred, a->std_pred, inv_gb);
-        if (a->y && a->loss) (void)block_sum((const float*)(ws + g.w_sq), g.B, a->loss, st);
-        if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
+        RULGNN_TRY(launch_checked(rg_fusion_kernel, dim3(blocks), dim3(RB), lds, st, g, a->x, a->y, prm, ws, a->pred, a->std_pred, inv_gb));
+        if (a->y && a->loss) RULGNN_TRY(block_sum((const float*)(ws + g.w_sq), g.B, a->loss, st));
     }
     if (mode & 2) {
         if (!a->grads) return RULGNN_EINVAL;
         const size_t lds = rg_fusion_lds(g, true);
         RULGNN_TRY(allow_dynamic_lds(rg_fusion_bwd_kernel, lds));
         if (rg_fusion_mx_ok(g))
-            hipLaunchKernelGGL(rg_fusion_bwd_mx_kernel, dim3(blocks), dim3(RB), 0, st, g, a->x, a->dpred, prm, ws);
+            RULGNN_TRY(launch_checked(rg_fusion_bwd_mx_kernel, dim3(blocks), dim3(RB), 0, st, g, a->x, a->dpred, prm, ws));
         else
-        hipLaunchKernelGGL(rg_fusion_bwd_kernel, dim3(blocks), dim3(RB), lds, st, g, a->x, a->dpred, prm, ws);
-        if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
+        RULGNN_TRY(launch_checked(rg_fusion_bwd_kernel, dim3(blocks), dim3(RB), lds, st, g, a->x, a->dpred, prm, ws));
         RULGNN_TRY(bilstm_backward(&ls, &la, st, 1));
         RULGNN_TRY(allow_dynamic_lds(rg_scl_bwd_kernel, lds_sclb));
         if (scl_mx) {
             const size_t lm = rg_scl_mx_lds(scl_nt, true);
             auto go = [&](auto kernel) -> int {
                 RULGNN_TRY(allow_dynamic_lds(kernel, lm));
-                hipLaunchKernelGGL(kernel, dim3((unsigned)gblocks), dim3(64 * RG_MXW), lm, st, g, a->x, prm, ws, key, thr, scale, a->sample_offset);
-                return RULGNN_OK;
+                return launch_checked(kernel, dim3((unsigned)gblocks), dim3(64 * RG_MXW), lm, st, g, a->x, prm, ws, key, thr, scale, a->sample_offset);
             };
             RULGNN_TRY(scl_nt == 1 ? go(rg_scl_bwd_mx_kernel<1>) : go(rg_scl_bwd_mx_kernel<2>));
         } else
-        hipLaunchKernelGGL(rg_scl_bwd_kernel, dim3((unsigned)gblocks), dim3(RB), lds_sclb, st, g, a->x, prm, ws, key, thr, scale, a->sample_offset);
-        hipLaunchKernelGGL(rg_adj_bwd_kernel, dim3(blocks), dim3(RB), 0, st, g, a->x, prm, ws);
-        if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
+        RULGNN_TRY(launch_checked(rg_scl_bwd_kernel, dim3((unsigned)gblocks), dim3(RB), lds_sclb, st, g, a->x, prm, ws, key, thr, scale, a->sample_offset));
+        RULGNN_TRY(launch_checked(rg_adj_bwd_kernel, dim3(blocks), dim3(RB), 0, st, g, a->x, prm, ws));
         {   // the three groups' partial rows in one launch
             const float* const part[3] = {ws + g.w_partA, ws + g.w_partS, ws + g.w_partF};
             float* const out[3] = {a->grads, a->grads + g.o_g1w, a->grads + g.o_c1w};
@@ -1169,8 +1162,7 @@ int Rgcnu::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
             RULGNN_TRY(rows_sum_three(part, out, rows, ld, n, st));
         }
         const int nz = g.E * g.L + 1;                                    // the `std` head is not in the loss (algorithms.py:287-290)
-        hipLaunchKernelGGL(rg_zero_kernel, dim3((nz + 255) / 256), dim3(256), 0, st, a->grads + g.o_f2w, nz);
-        if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
+        RULGNN_TRY(launch_checked(rg_zero_kernel, dim3((nz + 255) / 256), dim3(256), 0, st, a->grads + g.o_f2w, nz));
     }
     return RULGNN_OK;
 }

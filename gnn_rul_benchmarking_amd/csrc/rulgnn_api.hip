@@ -910,9 +910,7 @@ int rulgnn_sgemm_splitk_f32(const float* A, int64_t sAm, int64_t sAk, const floa
     float* part = static_cast<float*>(workspace);
     if (!colsum) return sgemm_splitk(A, sAm, sAk, B, sBn, sBk, C, ldc, M, N, K, false, part, st);
     float* ones = part + splitk_part_floats(M, N, K);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(splitk_ones_kernel, dim3(64), dim3(256), 0, st, ones, K);
-    if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
+    RULGNN_TRY(launch_checked(splitk_ones_kernel, dim3(64), dim3(256), 0, st, ones, K));
     return sgemm_splitk_colsum(A, sAm, sAk, B, sBn, sBk, C, ldc, M, N, K, colsum, ones, part, st);
 }
 

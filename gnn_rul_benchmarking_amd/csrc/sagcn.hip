@@ -610,14 +610,13 @@ __global__ void sg_fcw_kernel(SgGeom g, const float* __restrict__ attn, const fl
 }
 
 // the 20 statistics of every patch: g.R, g.n, g.nh are read
-inline void sg_launch_patch_features(const SgGeom& g, const float* x, float* raw, hipStream_t st) {
+inline int sg_launch_patch_features(const SgGeom& g, const float* x, float* raw, hipStream_t st) {
     if (g.n <= 64) {
         const size_t lw = sizeof(float) * ((size_t)3 * g.n + g.nh + 7 * 64);
-        hipLaunchKernelGGL(sg_patch_features_kernel<64>, dim3((unsigned)(g.R < 65536 ? g.R : 65536)), dim3(64), lw, st, g, x, raw);
-    } else {
-        const size_t lds1 = sizeof(float) * ((size_t)3 * g.n + g.nh + 7 * GB);
-        hipLaunchKernelGGL(sg_patch_features_kernel<GB>, dim3((unsigned)(g.R < 16384 ? g.R : 16384)), dim3(GB), lds1, st, g, x, raw);
+        return launch_checked(sg_patch_features_kernel<64>, dim3((unsigned)(g.R < 65536 ? g.R : 65536)), dim3(64), lw, st, g, x, raw);
     }
+    const size_t lds1 = sizeof(float) * ((size_t)3 * g.n + g.nh + 7 * GB);
+    return launch_checked(sg_patch_features_kernel<GB>, dim3((unsigned)(g.R < 16384 ? g.R : 16384)), dim3(GB), lds1, st, g, x, raw);
 }
 
 inline unsigned sg_grid(int64_t n) {
@@ -663,11 +662,9 @@ int sagcn_features(int64_t B, int P, int n, const float* x, float* raw, float* f
     if (B == 0) return RULGNN_OK;
     SgGeom g{};
     g.B = B; g.P = P; g.n = n; g.nh = n / 2 + 1; g.R = B * P;
-    (void)hipGetLastError();
-    sg_launch_patch_features(g, x, raw, st);
-    hipLaunchKernelGGL(sg_features_kernel, dim3((unsigned)(B < 4096 ? B : 4096)), dim3(GB), sizeof(float) * ((size_t)P * (SG_F + 1) + GB), st, B, P,
-                       (const float*)raw, feat);
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    RULGNN_TRY(sg_launch_patch_features(g, x, raw, st));
+    return launch_checked(sg_features_kernel, dim3((unsigned)(B < 4096 ? B : 4096)), dim3(GB), sizeof(float) * ((size_t)P * (SG_F + 1) + GB), st, B, P,
+                          (const float*)raw, feat);
 }
 
 // mode bit 0: forward, bit 1: backward (after a forward with the same args / workspace)
@@ -688,46 +685,42 @@ int Sagcn::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
     float* hh[3] = {h1, ws + g.w_h[0], ws + g.w_h[1]};                 // h1, h2, h3
     float* S = ws + g.w_s;
     float* attn = ws + g.w_attn;
-    (void)hipGetLastError();
     if (mode & 1) {
         const size_t lds1 = sizeof(float) * ((size_t)3 * g.n + g.nh + 7 * GB);
         const size_t lds2 = sizeof(float) * ((size_t)P * (SG_F + 1) + 2 * P + GB);
         if (lds1 > 64 * 1024 || lds2 > 64 * 1024) return RULGNN_EUNSUPPORTED;
-        sg_launch_patch_features(g, a->x, ws + g.w_raw, st);
+        RULGNN_TRY(sg_launch_patch_features(g, a->x, ws + g.w_raw, st));
         if (P % 16 == 0 && P <= 128) {
             const size_t lm = sg_graph_mx_lds(P);
             RULGNN_TRY(allow_dynamic_lds(sg_graph_mx_kernel, lm));
-            hipLaunchKernelGGL(sg_graph_mx_kernel, dim3((unsigned)(g.B < 4096 ? g.B : 4096)), dim3(GB), lm, st, g, (const float*)(ws + g.w_raw),
-                           ws + g.w_feat, ws + g.w_ax);
+            RULGNN_TRY(launch_checked(sg_graph_mx_kernel, dim3((unsigned)(g.B < 4096 ? g.B : 4096)), dim3(GB), lm, st, g, (const float*)(ws + g.w_raw),
+                                  ws + g.w_feat, ws + g.w_ax));
         } else
-        hipLaunchKernelGGL(sg_graph_kernel, dim3((unsigned)(g.B < 4096 ? g.B : 4096)), dim3(GB), lds2, st, g, (const float*)(ws + g.w_raw),
-                           ws + g.w_feat, ws + g.w_ax);
-        RULGNN_LAUNCH_OK();
+        RULGNN_TRY(launch_checked(sg_graph_kernel, dim3((unsigned)(g.B < 4096 ? g.B : 4096)), dim3(GB), lds2, st, g, (const float*)(ws + g.w_raw),
+                                  ws + g.w_feat, ws + g.w_ax));
         // gcn1: [R, 40] x W1^T
         RULGNN_TRY(sgemm(ws + g.w_ax, SG_F, 1, prm + g.o_w1, SG_F, 1, h1, H, R, H, SG_F, false, st));
-        hipLaunchKernelGGL(sg_bias_cols_kernel, dim3(sg_grid(RH)), dim3(GB), 0, st, h1, prm + g.o_b1, (int64_t)R, H, 1);
+        RULGNN_TRY(launch_checked(sg_bias_cols_kernel, dim3(sg_grid(RH)), dim3(GB), 0, st, h1, prm + g.o_b1, (int64_t)R, H, 1));
         for (int i = 0; i < 2; ++i) {
             // node axis: U [P, B*H] = Wp [P, P] x h [P, B*H] + bp[p]
             RULGNN_TRY(sgemm(prm + g.o_wp[i], P, 1, hh[i], 1, BH, u[i], BH, P, BH, P, false, st));
-            hipLaunchKernelGGL(sg_bias_rows_kernel, dim3(sg_grid(RH)), dim3(GB), 0, st, u[i], prm + g.o_bp[i], P, (int64_t)BH, 0);
+            RULGNN_TRY(launch_checked(sg_bias_rows_kernel, dim3(sg_grid(RH)), dim3(GB), 0, st, u[i], prm + g.o_bp[i], P, (int64_t)BH, 0));
             // feature axis: [R, H] x Wl^T + bl, ReLU
             RULGNN_TRY(sgemm(u[i], H, 1, prm + g.o_wl[i], H, 1, hh[i + 1], H, R, H, H, false, st));
-            hipLaunchKernelGGL(sg_bias_cols_kernel, dim3(sg_grid(RH)), dim3(GB), 0, st, hh[i + 1], prm + g.o_bl[i], (int64_t)R, H, 1);
+            RULGNN_TRY(launch_checked(sg_bias_cols_kernel, dim3(sg_grid(RH)), dim3(GB), 0, st, hh[i + 1], prm + g.o_bl[i], (int64_t)R, H, 1));
         }
-        RULGNN_LAUNCH_OK();
         // attention: S [Ah, B*H] = tanh(Wt [Ah, P] x h3 + bt[a]) ; logits [P, B*H] = Ws [P, Ah] x S (+ bs[p] in the head kernel)
         RULGNN_TRY(sgemm(prm + g.o_wt, P, 1, hh[2], 1, BH, S, BH, Ah, BH, P, false, st));
-        hipLaunchKernelGGL(sg_bias_rows_kernel, dim3(sg_grid((int64_t)Ah * BH)), dim3(GB), 0, st, S, prm + g.o_bt, Ah, (int64_t)BH, 2);
+        RULGNN_TRY(launch_checked(sg_bias_rows_kernel, dim3(sg_grid((int64_t)Ah * BH)), dim3(GB), 0, st, S, prm + g.o_bt, Ah, (int64_t)BH, 2));
         RULGNN_TRY(sgemm(prm + g.o_ws, Ah, 1, S, 1, BH, attn, BH, P, BH, Ah, false, st));
         {
             const int64_t waves = g.B * ((H + 63) / 64);
-            hipLaunchKernelGGL(sg_attn_head_kernel, dim3((unsigned)(waves < 65536 ? waves : 65536)), dim3(64), 0, st, g, attn, (const float*)hh[2], prm,
-                               ws + g.w_headpart);
-            hipLaunchKernelGGL(sg_head_finish_kernel, dim3(sg_grid(g.B)), dim3(GB), 0, st, g, (const float*)(ws + g.w_headpart), prm, a->y, a->pred, ws,
-                               inv_gb);
+            RULGNN_TRY(launch_checked(sg_attn_head_kernel, dim3((unsigned)(waves < 65536 ? waves : 65536)), dim3(64), 0, st, g, attn, (const float*)hh[2], prm,
+                                      ws + g.w_headpart));
+            RULGNN_TRY(launch_checked(sg_head_finish_kernel, dim3(sg_grid(g.B)), dim3(GB), 0, st, g, (const float*)(ws + g.w_headpart), prm, a->y, a->pred, ws,
+                                      inv_gb));
         }
-        if (a->y && a->loss) (void)block_sum((const float*)(ws + g.w_sq), g.B, a->loss, st);
-        RULGNN_LAUNCH_OK();
+        if (a->y && a->loss) RULGNN_TRY(block_sum((const float*)(ws + g.w_sq), g.B, a->loss, st));
     }
     if (mode & 2) {
         if (!a->grads) return RULGNN_EINVAL;
@@ -739,42 +732,38 @@ int Sagcn::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
         float* ds = ws + g.w_ds;
         RULGNN_TRY(fill_f32(one, 1, 1.0f, st));
         // head + softmax: dA = d h3 (direct path), dB = d logits
-        hipLaunchKernelGGL(sg_fcw_kernel, dim3(sg_grid((int64_t)P * H)), dim3(GB), 0, st, g, (const float*)attn, (const float*)hh[2], dpred,
-                           gr + g.o_wfc);
+        RULGNN_TRY(launch_checked(sg_fcw_kernel, dim3(sg_grid((int64_t)P * H)), dim3(GB), 0, st, g, (const float*)attn, (const float*)hh[2], dpred,
+                                  gr + g.o_wfc));
         RULGNN_TRY(sgemm_splitk(dpred, 0, 1, one, 0, 0, gr + g.o_bfc, 1, 1, 1, (int)g.B, false, split, st));
-        hipLaunchKernelGGL(sg_attn_head_bwd_kernel, dim3(sg_grid(BH)), dim3(GB), 0, st, g, (const float*)attn, (const float*)hh[2], prm, dpred, dA, dB);
-        RULGNN_LAUNCH_OK();
+        RULGNN_TRY(launch_checked(sg_attn_head_bwd_kernel, dim3(sg_grid(BH)), dim3(GB), 0, st, g, (const float*)attn, (const float*)hh[2], prm, dpred, dA, dB));
         RULGNN_TRY(sgemm_splitk(dB, BH, 1, S, BH, 1, gr + g.o_ws, Ah, P, Ah, BH, false, split, st));
-        hipLaunchKernelGGL(sg_rowsum_kernel, dim3(P, SG_ROW_SLICES), dim3(GB), 0, st, (const float*)dB, (int64_t)BH, ws + g.w_rowpart);
-        hipLaunchKernelGGL(sg_rowsum_finish_kernel, dim3((P + GB - 1) / GB), dim3(GB), 0, st, (const float*)(ws + g.w_rowpart), P, gr + g.o_bs);
+        RULGNN_TRY(launch_checked(sg_rowsum_kernel, dim3(P, SG_ROW_SLICES), dim3(GB), 0, st, (const float*)dB, (int64_t)BH, ws + g.w_rowpart));
+        RULGNN_TRY(launch_checked(sg_rowsum_finish_kernel, dim3((P + GB - 1) / GB), dim3(GB), 0, st, (const float*)(ws + g.w_rowpart), P, gr + g.o_bs));
         // d S [Ah, B*H] = Ws^T x d logits ; through tanh
         RULGNN_TRY(sgemm(prm + g.o_ws, 1, Ah, dB, 1, BH, ds, BH, Ah, BH, P, false, st));
-        hipLaunchKernelGGL(sg_tanh_bwd_kernel, dim3(sg_grid((int64_t)Ah * BH)), dim3(GB), 0, st, ds, (const float*)S, (int64_t)Ah * BH);
+        RULGNN_TRY(launch_checked(sg_tanh_bwd_kernel, dim3(sg_grid((int64_t)Ah * BH)), dim3(GB), 0, st, ds, (const float*)S, (int64_t)Ah * BH));
         RULGNN_TRY(sgemm_splitk(ds, BH, 1, hh[2], BH, 1, gr + g.o_wt, P, Ah, P, BH, false, split, st));
-        hipLaunchKernelGGL(sg_rowsum_kernel, dim3(Ah, SG_ROW_SLICES), dim3(GB), 0, st, (const float*)ds, (int64_t)BH, ws + g.w_rowpart);
-        hipLaunchKernelGGL(sg_rowsum_finish_kernel, dim3((Ah + GB - 1) / GB), dim3(GB), 0, st, (const float*)(ws + g.w_rowpart), Ah, gr + g.o_bt);
+        RULGNN_TRY(launch_checked(sg_rowsum_kernel, dim3(Ah, SG_ROW_SLICES), dim3(GB), 0, st, (const float*)ds, (int64_t)BH, ws + g.w_rowpart));
+        RULGNN_TRY(launch_checked(sg_rowsum_finish_kernel, dim3((Ah + GB - 1) / GB), dim3(GB), 0, st, (const float*)(ws + g.w_rowpart), Ah, gr + g.o_bt));
         // d h3 += Wt^T x d(tanh input)
         RULGNN_TRY(sgemm(prm + g.o_wt, 1, P, ds, 1, BH, dA, BH, P, BH, Ah, true, st));
-        RULGNN_LAUNCH_OK();
         float* d = dA;
         float* other = dB;
         for (int i = 1; i >= 0; --i) {
-            hipLaunchKernelGGL(sg_relu_bwd_kernel, dim3(sg_grid(RH)), dim3(GB), 0, st, d, (const float*)hh[i + 1], RH);
+            RULGNN_TRY(launch_checked(sg_relu_bwd_kernel, dim3(sg_grid(RH)), dim3(GB), 0, st, d, (const float*)hh[i + 1], RH));
             RULGNN_TRY(sgemm_splitk(d, 1, H, u[i], 1, H, gr + g.o_wl[i], H, H, H, R, false, split, st));
             RULGNN_TRY(sgemm_splitk(one, 0, 0, d, 1, H, gr + g.o_bl[i], H, 1, H, R, false, split, st));
             // d U [R, H] = d V [R, H] x Wl
             RULGNN_TRY(sgemm(d, H, 1, prm + g.o_wl[i], 1, H, other, H, R, H, H, false, st));
             RULGNN_TRY(sgemm_splitk(other, BH, 1, hh[i], BH, 1, gr + g.o_wp[i], P, P, P, BH, false, split, st));
-            hipLaunchKernelGGL(sg_rowsum_kernel, dim3(P, SG_ROW_SLICES), dim3(GB), 0, st, (const float*)other, (int64_t)BH, ws + g.w_rowpart);
-            hipLaunchKernelGGL(sg_rowsum_finish_kernel, dim3((P + GB - 1) / GB), dim3(GB), 0, st, (const float*)(ws + g.w_rowpart), P, gr + g.o_bp[i]);
+            RULGNN_TRY(launch_checked(sg_rowsum_kernel, dim3(P, SG_ROW_SLICES), dim3(GB), 0, st, (const float*)other, (int64_t)BH, ws + g.w_rowpart));
+            RULGNN_TRY(launch_checked(sg_rowsum_finish_kernel, dim3((P + GB - 1) / GB), dim3(GB), 0, st, (const float*)(ws + g.w_rowpart), P, gr + g.o_bp[i]));
             // d h_in [P, B*H] = Wp^T x d U
             RULGNN_TRY(sgemm(prm + g.o_wp[i], 1, P, other, 1, BH, d, BH, P, BH, P, false, st));
-            RULGNN_LAUNCH_OK();
         }
-        hipLaunchKernelGGL(sg_relu_bwd_kernel, dim3(sg_grid(RH)), dim3(GB), 0, st, d, (const float*)h1, RH);
+        RULGNN_TRY(launch_checked(sg_relu_bwd_kernel, dim3(sg_grid(RH)), dim3(GB), 0, st, d, (const float*)h1, RH));
         RULGNN_TRY(sgemm_splitk(d, 1, H, ws + g.w_ax, 1, SG_F, gr + g.o_w1, SG_F, H, SG_F, R, false, split, st));
         RULGNN_TRY(sgemm_splitk(one, 0, 0, d, 1, H, gr + g.o_b1, H, 1, H, R, false, split, st));
-        RULGNN_LAUNCH_OK();
     }
     return RULGNN_OK;
 }

@@ -13,7 +13,7 @@ constexpr int SEQ_MAX_LSTM = 3;
 // C = A B^T (strides as sgemm): a short product over a long reduction (K >= 512, fewer than 128 output tiles: [BT x 900] x [900 x 50]
 // is 32 tiles walking all of K alone, 45 us) is split over k (6 us + a 6-us fixed-order sum), anything else is the plain SGEMM.  The two
 // paths sum in different orders: which products come here is part of a family's bits.
-int gemm_rows(const float* A, int64_t sAm, int64_t sAk, const float* B, int64_t sBn, int64_t sBk, float* C, int64_t ldc, int M, int N, int K,
+[[nodiscard]] int gemm_rows(const float* A, int64_t sAm, int64_t sAk, const float* B, int64_t sBn, int64_t sBk, float* C, int64_t ldc, int M, int N, int K,
               float* split, hipStream_t st);
 // `p`, or its copy at `slot` (enqueued on `st`; nullptr when that fails) when p is off a 16-byte boundary: the large-tile GEMM (16-byte
 // vector loads) falls back to the 64 x 64 fp32 tiles for a misaligned operand -- 123 instead of 98 us for STNet's [18 000 x 900] x
@@ -22,9 +22,9 @@ const float* aligned_operand(const float* p, size_t count, float* slot, hipStrea
 // Backward of y = h W^T + b over `rows` rows, d = dy: gw = d^T h and gb = sum_rows d (split-K, gb against `one`), then dn = d W by the
 // GEMM the caller names (the choice changes the summation order).
 enum DenseData { DENSE_NO_DATA, DENSE_PLAIN, DENSE_ROWS };          // no data gradient / sgemm / gemm_rows
-int dense_backward(const float* d, const float* h, const float* W, const float* one, float* gw, float* gb, DenseData data, float* dn, int rows,
+[[nodiscard]] int dense_backward(const float* d, const float* h, const float* W, const float* one, float* gw, float* gb, DenseData data, float* dn, int rows,
                    int out, int in, float* split, hipStream_t st);
-int sum_pair(const float* a, const float* b, float* out, hipStream_t st);          // out[0] = a[0] + b[0]
+[[nodiscard]] int sum_pair(const float* a, const float* b, float* out, hipStream_t st);          // out[0] = a[0] + b[0]
 // One direction of bilstm.hip over T steps of B sequences, I -> E wide, parameters at flat offsets o = {w_ih, w_hh, b_ih, b_hh} of `prm`
 // (and of `grads`; null with dout and dx for a forward alone).  Slot [1] mirrors [0] (unused).
 void lstm_uni_args(rulgnn_bilstm_shape* ls, rulgnn_bilstm_args* la, int T, int64_t B, int I, int E, const float* x, float* out, float* lstm_ws,
@@ -37,11 +37,11 @@ struct LstmHeadPlan {
     int64_t w_hseq[SEQ_MAX_LSTM], w_lstm[SEQ_MAX_LSTM], w_dpred, w_sq, w_one;      // workspace (floats); w_one: 64 floats, [0] = 1 in a backward
 };
 // B, T, nk, H are set: takes parameters and workspace regions, registers the head's split-K products; EUNSUPPORTED where bilstm.hip refuses
-int lstm_head_layout(LstmHeadPlan* p, int* o, int64_t* w, SplitKScratch* sp);
+[[nodiscard]] int lstm_head_layout(LstmHeadPlan* p, int* o, int64_t* w, SplitKScratch* sp);
 // x [B * T][H[0]] -> the layers -> pred [B]; with y, the squared-error terms / global batch in w_sq and d loss / d pred in w_dpred
-int lstm_head_forward(const LstmHeadPlan& p, const float* x, const float* prm, float* ws, const float* y, float* pred, float inv_gb, hipStream_t st);
+[[nodiscard]] int lstm_head_forward(const LstmHeadPlan& p, const float* x, const float* prm, float* ws, const float* y, float* pred, float inv_gb, hipStream_t st);
 // linear.{weight, bias} gradients, d hseq into dbuf[0], then down the layers from one buffer into the other: d x is left in dbuf[nk & 1]
-int lstm_head_backward(const LstmHeadPlan& p, const float* x, const float* prm, float* ws, const float* dpred, float* grads, float* const dbuf[2],
+[[nodiscard]] int lstm_head_backward(const LstmHeadPlan& p, const float* x, const float* prm, float* ws, const float* dpred, float* grads, float* const dbuf[2],
                        float* split, hipStream_t st);
 
 struct AutoEncoderPlan {
@@ -55,10 +55,10 @@ struct AutoEncoderPlan {
 void autoencoder_layout(AutoEncoderPlan* p, int* o, int64_t* w, SplitKScratch* sp);
 // yo [BT][D] -> encoder (output w_enc[3]: the LSTM's input) -> decoder; recon_sum[0] = mean over the GLOBAL batch of (yo - yp)^2 (rscale =
 // 1 / its element count), the term's gradients w.r.t. yp and yo in w_dD1 / w_dD2
-int autoencoder_forward(const AutoEncoderPlan& p, const float* yo, const float* prm, float* ws, float rscale, float* recon_sum, float* split,
+[[nodiscard]] int autoencoder_forward(const AutoEncoderPlan& p, const float* yo, const float* prm, float* ws, float rscale, float* recon_sum, float* split,
                         hipStream_t st);
 // w_dH holds the LSTM path's d (encoder output); recon_weight (device, may be null) scales the reconstruction gradients.  d yo: w_dD1.
-int autoencoder_backward(const AutoEncoderPlan& p, const float* yo, const float* prm, float* ws, float* grads, const float* one,
+[[nodiscard]] int autoencoder_backward(const AutoEncoderPlan& p, const float* yo, const float* prm, float* ws, float* grads, const float* one,
                          const float* recon_weight, float* split, hipStream_t st);
 
 }  // namespace rulgnn

@@ -1,6 +1,6 @@
 // SGEMM on the gfx950 matrix cores, shared by every family (interface: sgemm_mfma.hpp).  ONE translation unit: the kernels used
 // to live in the header and were instantiated in every unit that included it (most of the library size and build time).
-#include "launch.hpp"
+#include "host_util.hpp"
 #include "sgemm_mfma.hpp"
 #include "reduce_device.hpp"
 
@@ -944,9 +944,7 @@ static __global__ __launch_bounds__(256) void absmax_partials_kernel(const float
 }
 int absmax_partials(const float* x, int64_t n, float* part, int nparts, hipStream_t st) {
     if (nparts <= 0) return RULGNN_EINVAL;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(absmax_partials_kernel, dim3(nparts), dim3(256), 0, st, x, n, part);
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return launch_checked(absmax_partials_kernel, dim3(nparts), dim3(256), 0, st, x, n, part);
 }
 
 // 256x256 tiles when both output dimensions fill them and there are enough of them for one per CU
@@ -979,12 +977,11 @@ static inline int sgemm_with_kfast(bool ak, bool bk, F&& f) {
 }
 
 // the matrix-core GEMM of a (possibly split-K) problem: the 128x128 kernel where it pays, the 64x64 one otherwise.  RULGNN_EHIP when
-// the runtime refuses a kernel its LDS; the caller reads the launch's own error afterwards.
+// the runtime refuses a kernel its LDS or the launch.
 static inline int sgemm_launch_tiles(const GemmArgs& g, int slices, hipStream_t st) {
     auto go = [&](auto kernel, int tile, int threads, size_t lds) -> int {
         if (const int rc = allow_dynamic_lds(kernel, lds); rc != RULGNN_OK) return rc;
-        hipLaunchKernelGGL(kernel, dim3((g.N + tile - 1) / tile, (g.M + tile - 1) / tile, slices), dim3(threads), lds, st, g);
-        return RULGNN_OK;
+        return launch_checked(kernel, dim3((g.N + tile - 1) / tile, (g.M + tile - 1) / tile, slices), dim3(threads), lds, st, g);
     };
     if (sgemm_big_ok(g, slices)) {
         const int mode = sgemm_big_mode();                           // (1: bf16 x 3, f16 x 2 where the caller passes scales; 2: bf16 x 3 only)
@@ -999,8 +996,7 @@ static inline int sgemm_launch_tiles(const GemmArgs& g, int slices, hipStream_t 
                        : go(sgemm_bf16x3_kernel<AK, BK>, 128, T128, lds_bytes<SplitBf16x3::PLANES, 128>());
         });
     }
-    hipLaunchKernelGGL(sgemm_mfma_kernel, dim3((g.N + 63) / 64, (g.M + 63) / 64, slices), dim3(256), 0, st, g);
-    return RULGNN_OK;
+    return launch_checked(sgemm_mfma_kernel, dim3((g.N + 63) / 64, (g.M + 63) / 64, slices), dim3(256), 0, st, g);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1127,9 +1123,7 @@ static int sgemm_rows_bf16_launch(const GemmArgs& g, hipStream_t st) {
     const int64_t tiles = ((int64_t)g.M + 15) / 16;
     int64_t blocks = (tiles + 3) / 4;
     if (blocks > 4096) blocks = 4096;                   // 16 waves per CU worth of persistent workgroups
-    (void)hipGetLastError();
-    hipLaunchKernelGGL((sgemm_rows_bf16_kernel<NT, KS>), dim3((unsigned)blocks), dim3(256), 0, st, g);
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return launch_checked((sgemm_rows_bf16_kernel<NT, KS>), dim3((unsigned)blocks), dim3(256), 0, st, g);
 }
 
 static int sgemm_rows_bf16(const GemmArgs& g, hipStream_t st) {
@@ -1158,16 +1152,12 @@ int sgemm(const float* A, int64_t sAm, int64_t sAk, const float* B, int64_t sBn,
         const int NT = N <= 8 ? 8 : (N <= 16 ? 16 : 32);
         const size_t lds = (size_t)(K > 0 ? K : 1) * NT * sizeof(float);
         const dim3 grid((unsigned)((M + 255) / 256));
-        (void)hipGetLastError();
-        if (NT == 8) hipLaunchKernelGGL(sgemm_skinny_kernel<8>, grid, dim3(256), lds, st, g);
-        else if (NT == 16) hipLaunchKernelGGL(sgemm_skinny_kernel<16>, grid, dim3(256), lds, st, g);
-        else hipLaunchKernelGGL(sgemm_skinny_kernel<32>, grid, dim3(256), lds, st, g);
-        return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+        if (NT == 8) return launch_checked(sgemm_skinny_kernel<8>, grid, dim3(256), lds, st, g);
+        if (NT == 16) return launch_checked(sgemm_skinny_kernel<16>, grid, dim3(256), lds, st, g);
+        return launch_checked(sgemm_skinny_kernel<32>, grid, dim3(256), lds, st, g);
     }
     GemmArgs g{A, sAm, sAk, B, sBn, sBk, C, ldc, M, N, K, accumulate ? 1 : 0, K > 0 ? (K + 15) & ~15 : 16, amax_a, amax_b, amax_na, amax_nb};
-    (void)hipGetLastError();
-    if (const int rc = sgemm_launch_tiles(g, 1, st); rc != RULGNN_OK) return rc;
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return sgemm_launch_tiles(g, 1, st);
 }
 
 // Split-K for reductions over a long K (weight gradients: K = batch * nodes) with few output tiles: `slices` partial
@@ -1231,11 +1221,10 @@ int sgemm_splitk_batch_products(const SplitKJob* jobs, int n, float* partial, si
         off += (size_t)used * q.M * q.N;
     }
     gb.first[n] = wg; rb.first[n] = rwg;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(sgemm_mfma_batch_kernel, dim3(wg), dim3(256), 0, st, gb);
+    RULGNN_TRY(launch_checked(sgemm_mfma_batch_kernel, dim3(wg), dim3(256), 0, st, gb));
     if (reduce_out) *reduce_out = rb;          // (the caller runs the slice sums inside a launch of its own: reduce_slices_batch_body)
-    else hipLaunchKernelGGL(sgemm_reduce_slices_batch_kernel, dim3(rwg), dim3(1024), 0, st, rb);
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    else RULGNN_TRY(launch_checked(sgemm_reduce_slices_batch_kernel, dim3(rwg), dim3(1024), 0, st, rb));
+    return RULGNN_OK;
 }
 
 // ... for large contiguous outputs (M N a multiple of 4, ldc == N: the [N x N] weight gradients of the tiled ST_GCN path, 4 MB per slice):
@@ -1263,13 +1252,12 @@ static __global__ __launch_bounds__(256) void sgemm_reduce_slices4_kernel(const 
 }
 static inline int sgemm_reduce_slices(const float* partial, float* C, int64_t ldc, int M, int N, int slices, bool accumulate, hipStream_t st) {
     const int64_t MN = (int64_t)M * N;
-    (void)hipGetLastError();
     if (MN >= 65536 && MN % 4 == 0 && (ldc == N || M == 1) && ((reinterpret_cast<uintptr_t>(partial) | reinterpret_cast<uintptr_t>(C)) & 15) == 0)
-        hipLaunchKernelGGL(sgemm_reduce_slices4_kernel, dim3((unsigned)((MN / 4 + 255) / 256)), dim3(256), 0, st,
-                           reinterpret_cast<const float4*>(partial), reinterpret_cast<float4*>(C), MN / 4, slices, accumulate ? 1 : 0);
+        RULGNN_TRY(launch_checked(sgemm_reduce_slices4_kernel, dim3((unsigned)((MN / 4 + 255) / 256)), dim3(256), 0, st,
+                                  reinterpret_cast<const float4*>(partial), reinterpret_cast<float4*>(C), MN / 4, slices, accumulate ? 1 : 0));
     else
-        hipLaunchKernelGGL(sgemm_reduce_slices_kernel, dim3((M * N + 63) / 64), dim3(1024), 0, st, partial, C, ldc, M, N, slices, accumulate ? 1 : 0);
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+        RULGNN_TRY(launch_checked(sgemm_reduce_slices_kernel, dim3((M * N + 63) / 64), dim3(1024), 0, st, partial, C, ldc, M, N, slices, accumulate ? 1 : 0));
+    return RULGNN_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1431,10 +1419,10 @@ static __global__ __launch_bounds__(256) void sgemm_longk_mfma_batch_kernel(Long
     sgemm_longk_mfma_body<MT, NT>(b.g[j], b.kper[j], ones, b.nwaves[j]);
 }
 static bool sgemm_longk_mfma_ok(const GemmArgs& g) { return g.sAm == 1 && g.sBn == 1 && g.M <= 32 && g.N <= 64; }
-static void sgemm_longk_mfma_launch(const GemmArgs& g, int kper, int ones, int nwaves, hipStream_t st) {
+static int sgemm_longk_mfma_launch(const GemmArgs& g, int kper, int ones, int nwaves, hipStream_t st) {
     const int MT = (g.M + 15) / 16, NT = (g.N + 15) / 16;
     const dim3 grid((nwaves + 3) / 4), block(256);
-#define RULGNN_LK(mt, nt) hipLaunchKernelGGL((sgemm_longk_mfma_kernel<mt, nt>), grid, block, 0, st, g, kper, ones, nwaves)
+#define RULGNN_LK(mt, nt) return launch_checked((sgemm_longk_mfma_kernel<mt, nt>), grid, block, 0, st, g, kper, ones, nwaves)
     if (MT == 1) { if (NT == 1) RULGNN_LK(1, 1); else if (NT == 2) RULGNN_LK(1, 2); else if (NT == 3) RULGNN_LK(1, 3); else RULGNN_LK(1, 4); }
     else { if (NT == 1) RULGNN_LK(2, 1); else if (NT == 2) RULGNN_LK(2, 2); else if (NT == 3) RULGNN_LK(2, 3); else RULGNN_LK(2, 4); }
 #undef RULGNN_LK
@@ -1557,16 +1545,12 @@ int sgemm_splitk(const float* A, int64_t sAm, int64_t sAk, const float* B, int64
         int kper = (K + ks - 1) / ks;
         kper = (kper + 31) & ~31;
         ks = (K + kper - 1) / kper;
-        (void)hipGetLastError();
-        hipLaunchKernelGGL(sgemm_vecmat_kernel, dim3((N + 63) / 64, ks), dim3(256), 0, st, A, sAk, B, sBk, ks > 1 ? partial : C, N, K, kper);
-        if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
+        RULGNN_TRY(launch_checked(sgemm_vecmat_kernel, dim3((N + 63) / 64, ks), dim3(256), 0, st, A, sAk, B, sBk, ks > 1 ? partial : C, N, K, kper));
         return ks > 1 ? rows_sum(partial, ks, N, N, C, st) : RULGNN_OK;
     }
     if (sgemm_tiny_ok(M, N, K)) {
         GemmArgs g{A, sAm, sAk, B, sBn, sBk, C, ldc, M, N, K, 0, K};
-        (void)hipGetLastError();
-        hipLaunchKernelGGL(sgemm_tiny_kernel, dim3(1), dim3(1024), 0, st, g, accumulate ? 1 : 0);
-        return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+        return launch_checked(sgemm_tiny_kernel, dim3(1), dim3(1024), 0, st, g, accumulate ? 1 : 0);
     }
     if (sgemm_longk_blocks(M, N, K) > 0) {
         int nblk = sgemm_longk_blocks(M, N, K);
@@ -1574,13 +1558,11 @@ int sgemm_splitk(const float* A, int64_t sAm, int64_t sAk, const float* B, int64
         kper = (kper + SKT_ROWS - 1) / SKT_ROWS * SKT_ROWS;
         nblk = (K + kper - 1) / kper;
         GemmArgs g{A, sAm, sAk, B, sBn, sBk, partial, N, M, N, K, 0, kper};
-        (void)hipGetLastError();
-        if (sgemm_longk_mfma_ok(g)) sgemm_longk_mfma_launch(g, kper, 0, nblk, st);
+        if (sgemm_longk_mfma_ok(g)) RULGNN_TRY(sgemm_longk_mfma_launch(g, kper, 0, nblk, st));
         else
-        hipLaunchKernelGGL(sgemm_longk_kernel, dim3(nblk), dim3(256), ((size_t)SKT_ROWS * (M + N) + 256) * sizeof(float), st, g, kper, 0);
-        hipLaunchKernelGGL(sgemm_longk_reduce_kernel, dim3((M * N + 3) / 4), dim3(256), 0, st, (const float*)partial, C, ldc, M, N, nblk,
-                           accumulate ? 1 : 0, (float*)nullptr);
-        return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+        RULGNN_TRY(launch_checked(sgemm_longk_kernel, dim3(nblk), dim3(256), ((size_t)SKT_ROWS * (M + N) + 256) * sizeof(float), st, g, kper, 0));
+        return launch_checked(sgemm_longk_reduce_kernel, dim3((M * N + 3) / 4), dim3(256), 0, st, (const float*)partial, C, ldc, M, N, nblk,
+                              accumulate ? 1 : 0, (float*)nullptr);
     }
     const int slices = sgemm_splitk_slices(M, N, K);
     if (slices <= 1) return sgemm(A, sAm, sAk, B, sBn, sBk, C, ldc, M, N, K, accumulate, st, 0, amax_a, amax_na, amax_b, amax_nb, plane_ws, plane_ws_bytes);
@@ -1598,9 +1580,7 @@ int sgemm_splitk(const float* A, int64_t sAm, int64_t sAk, const float* B, int64
     kchunk = (kchunk + 15) & ~15;
     const int used = (K + kchunk - 1) / kchunk;
     GemmArgs g{A, sAm, sAk, B, sBn, sBk, partial, N, M, N, K, 0, kchunk, amax_a, amax_b, amax_na, amax_nb};
-    (void)hipGetLastError();
     if (const int rc = sgemm_launch_tiles(g, used, st); rc != RULGNN_OK) return rc;
-    if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
     return sgemm_reduce_slices(partial, C, ldc, M, N, used, accumulate, st);
 }
 
@@ -1616,13 +1596,11 @@ int sgemm_splitk_colsum(const float* A, int64_t sAm, int64_t sAk, const float* B
         kper = (kper + SKT_ROWS - 1) / SKT_ROWS * SKT_ROWS;
         nblk = (K + kper - 1) / kper;
         GemmArgs g{A, sAm, sAk, B, sBn, sBk, partial, NE, M, NE, K, 0, kper};
-        (void)hipGetLastError();
-        if (sgemm_longk_mfma_ok(g)) sgemm_longk_mfma_launch(g, kper, 1, nblk, st);
+        if (sgemm_longk_mfma_ok(g)) RULGNN_TRY(sgemm_longk_mfma_launch(g, kper, 1, nblk, st));
         else
-        hipLaunchKernelGGL(sgemm_longk_kernel, dim3(nblk), dim3(256), ((size_t)SKT_ROWS * (M + NE) + 256) * sizeof(float), st, g, kper, 1);
-        hipLaunchKernelGGL(sgemm_longk_reduce_kernel, dim3((M * NE + 3) / 4), dim3(256), 0, st, (const float*)partial, C, ldc, M, NE, nblk, 0,
-                           colsum);
-        return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+        RULGNN_TRY(launch_checked(sgemm_longk_kernel, dim3(nblk), dim3(256), ((size_t)SKT_ROWS * (M + NE) + 256) * sizeof(float), st, g, kper, 1));
+        return launch_checked(sgemm_longk_reduce_kernel, dim3((M * NE + 3) / 4), dim3(256), 0, st, (const float*)partial, C, ldc, M, NE, nblk, 0,
+                              colsum);
     }
     const int rc = sgemm_splitk(A, sAm, sAk, B, sBn, sBk, C, ldc, M, N, K, false, partial, st);
     if (rc != RULGNN_OK) return rc;
@@ -1706,14 +1684,12 @@ int sgemm_splitk_colsum_batch(const SplitKColsumJob* jobs, int n, const float* o
         maxw = nblk > maxw ? nblk : maxw;
         maxo = q.M * NE > maxo ? q.M * NE : maxo;
     }
-    (void)hipGetLastError();
     const dim3 grid((maxw + 3) / 4, n), block(256);
-#define RULGNN_LKB(mt, nt) hipLaunchKernelGGL((sgemm_longk_mfma_batch_kernel<mt, nt>), grid, block, 0, st, lb, 1)
+#define RULGNN_LKB(mt, nt) RULGNN_TRY(launch_checked((sgemm_longk_mfma_batch_kernel<mt, nt>), grid, block, 0, st, lb, 1))
     if (MT0 == 1) { if (NT0 == 1) RULGNN_LKB(1, 1); else if (NT0 == 2) RULGNN_LKB(1, 2); else if (NT0 == 3) RULGNN_LKB(1, 3); else RULGNN_LKB(1, 4); }
     else { if (NT0 == 1) RULGNN_LKB(2, 1); else if (NT0 == 2) RULGNN_LKB(2, 2); else if (NT0 == 3) RULGNN_LKB(2, 3); else RULGNN_LKB(2, 4); }
 #undef RULGNN_LKB
-    hipLaunchKernelGGL(sgemm_longk_reduce_batch_kernel, dim3((maxo + 3) / 4, n), dim3(256), 0, st, rb);
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return launch_checked(sgemm_longk_reduce_batch_kernel, dim3((maxo + 3) / 4, n), dim3(256), 0, st, rb);
 }
 
 // out[e] = sum_r part[r][e] over `rows` per-workgroup partial rows of n values (row stride ld): 32 columns x 32 row slices per
@@ -1764,9 +1740,7 @@ int rows_sum3(const float* partA, float* outA, const float* partB, float* outB, 
     jb.part[1] = partB; jb.out[1] = outB; jb.rows[1] = rows; jb.n[1] = n; jb.ld[1] = ld;
     jb.part[2] = partC; jb.out[2] = outC; jb.out2[2] = outC2; jb.rows[2] = rowsC; jb.n[2] = nC; jb.ld[2] = ldC;
     const int nmax = n > nC ? n : nC;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(rows_sum_multi_kernel, dim3((nmax + 31) / 32, partC && nC > 0 ? 3 : 2), dim3(1024), 0, st, jb);
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return launch_checked(rows_sum_multi_kernel, dim3((nmax + 31) / 32, partC && nC > 0 ? 3 : 2), dim3(1024), 0, st, jb);
 }
 int rows_sum_three(const float* const part[3], float* const out[3], const int rows[3], const int64_t ld[3], const int n[3], hipStream_t st) {
     RowsSumJobs jb{};
@@ -1776,15 +1750,11 @@ int rows_sum_three(const float* const part[3], float* const out[3], const int ro
         nmax = jb.n[j] > nmax ? jb.n[j] : nmax;
     }
     if (nmax <= 0) return RULGNN_OK;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(rows_sum_multi_kernel, dim3((nmax + 31) / 32, 3), dim3(1024), 0, st, jb);
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return launch_checked(rows_sum_multi_kernel, dim3((nmax + 31) / 32, 3), dim3(1024), 0, st, jb);
 }
 int rows_sum(const float* part, int rows, int64_t ld, int n, float* out, hipStream_t st) {
     if (n <= 0) return RULGNN_OK;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(rows_sum_kernel, dim3((n + 31) / 32), dim3(1024), 0, st, part, rows, ld, n, out);
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return launch_checked(rows_sum_kernel, dim3((n + 31) / 32), dim3(1024), 0, st, part, rows, ld, n, out);
 }
 
 // dst[c] = sum over the rows of src[r][c] for a SHORT matrix (bias gradients over batch-sized row counts): one workgroup, a thread per
@@ -1805,9 +1775,7 @@ static __global__ __launch_bounds__(1024) void cols_sum_small_kernel(const float
 }
 int cols_sum_small(const float* src, int rows, int C, float* dst, hipStream_t st) {
     if (C == 1) return block_sum(src, rows, dst, st);              // (one column: a tree, not one thread adding 1024 stripes)
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(cols_sum_small_kernel, dim3(1), dim3(1024), 0, st, src, rows, C, dst);
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return launch_checked(cols_sum_small_kernel, dim3(1), dim3(1024), 0, st, src, rows, C, dst);
 }
 
 // out[0] = sum(v[0..n)) with one workgroup: strided partial sums, then a fixed-order tree (deterministic).
@@ -1826,9 +1794,7 @@ static __global__ __launch_bounds__(1024) void block_sum_kernel(const float* __r
 
 
 int block_sum(const float* v, int64_t n, float* out, hipStream_t st) {
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(block_sum_kernel, dim3(1), dim3(1024), 0, st, v, n, out);
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return launch_checked(block_sum_kernel, dim3(1), dim3(1024), 0, st, v, n, out);
 }
 
 }  // namespace rulgnn

@@ -15,7 +15,7 @@ int& sgemm_big_mode();
 
 // C[m][n] (+)= sum_k A(m,k) * B(n,k) with element strides (sAm, sAk), (sBn, sBk); picks the tile / tall-and-skinny / big-tile kernel.
 // `bf16` != 0: operands rounded to bf16 on the matrix cores where the shape qualifies, fp32 paths otherwise.
-int sgemm(const float* A, int64_t sAm, int64_t sAk, const float* B, int64_t sBn, int64_t sBk, float* C, int64_t ldc,
+[[nodiscard]] int sgemm(const float* A, int64_t sAm, int64_t sAk, const float* B, int64_t sBn, int64_t sBk, float* C, int64_t ldc,
           int M, int N, int K, bool accumulate, hipStream_t st, int bf16 = 0, const float* amax_a = nullptr, int amax_na = 0,
           const float* amax_b = nullptr, int amax_nb = 0, void* plane_ws = nullptr, size_t plane_ws_bytes = 0);
 // (plane_ws: optional scratch of sgemm_planes_ws_bytes(M, N, K) bytes.  With it -- and with the maxima -- products whose shape
@@ -24,7 +24,7 @@ int sgemm(const float* A, int64_t sAm, int64_t sAk, const float* B, int64_t sBn,
 size_t sgemm_planes_ws_bytes(int M, int N, int K);
 int sgemm_planes_slices(int M, int N, int K, bool want_split);       // 0: this shape does not run on the pre-split kernel
 bool sgemm_planes_ok(const float* A, int64_t sAm, int64_t sAk, const float* B, int64_t sBn, int64_t sBk, int M, int N, int K, int slices);
-int sgemm_planes(const float* A, int64_t sAm, int64_t sAk, const float* B, int64_t sBn, int64_t sBk, float* C, int64_t ldc, int M, int N, int K,
+[[nodiscard]] int sgemm_planes(const float* A, int64_t sAm, int64_t sAk, const float* B, int64_t sBn, int64_t sBk, float* C, int64_t ldc, int M, int N, int K,
                  bool accumulate, int slices, const float* amax_a, int amax_na, const float* amax_b, int amax_nb, void* ws, size_t ws_bytes,
                  hipStream_t st, bool a_presplit = false);
 // operand A split by the kernel that PRODUCES it (no split pass, no fp32 copy): where it writes inside `ws` -- f16 planes [M][K], k
@@ -35,17 +35,17 @@ void sgemm_planes_a_slots(void* ws, int M, int K, void** hi, void** lo, float** 
 // split (three matrix instructions per product instead of six; csrc/sgemm.hip: sgemm_f16x2v_kernel).)
 
 // nparts partial maxima of |x| over the finite elements of x[0..n) (one per workgroup): an operand's scale row for the arguments above
-int absmax_partials(const float* x, int64_t n, float* part, int nparts, hipStream_t st);
+[[nodiscard]] int absmax_partials(const float* x, int64_t n, float* part, int nparts, hipStream_t st);
 
 // The same product as a deterministic split-K reduction (weight gradients: K = all rows of the batch); `partial` is caller-provided
 // scratch of sgemm_splitk_need_floats(M, N, K) floats.
-int sgemm_splitk(const float* A, int64_t sAm, int64_t sAk, const float* B, int64_t sBn, int64_t sBk, float* C, int64_t ldc,
+[[nodiscard]] int sgemm_splitk(const float* A, int64_t sAm, int64_t sAk, const float* B, int64_t sBn, int64_t sBk, float* C, int64_t ldc,
                  int M, int N, int K, bool accumulate, float* partial, hipStream_t st, const float* amax_a = nullptr, int amax_na = 0,
                  const float* amax_b = nullptr, int amax_nb = 0, void* plane_ws = nullptr, size_t plane_ws_bytes = 0);
 
 // ... and colsum[m] = sum_k A(m, k) from the same pass (weight gradient + the bias gradient over the same rows); `ones`: K ones for
 // the shapes that take two calls; `partial`: sgemm_splitk_need_floats(M, N + 1, K) floats
-int sgemm_splitk_colsum(const float* A, int64_t sAm, int64_t sAk, const float* B, int64_t sBn, int64_t sBk, float* C, int64_t ldc,
+[[nodiscard]] int sgemm_splitk_colsum(const float* A, int64_t sAm, int64_t sAk, const float* B, int64_t sBn, int64_t sBk, float* C, int64_t ldc,
                         int M, int N, int K, float* colsum, const float* ones, float* partial, hipStream_t st);
 
 // ... for several (A, B) pairs at once (the same results; two launches for all of them where every pair is a long-k product of one tile
@@ -58,7 +58,7 @@ struct SplitKColsumJob {
     float* colsum;
 };
 size_t sgemm_splitk_colsum_batch_floats(const SplitKColsumJob* jobs, int n);
-int sgemm_splitk_colsum_batch(const SplitKColsumJob* jobs, int n, const float* ones, float* partial, size_t partial_floats, hipStream_t st);
+[[nodiscard]] int sgemm_splitk_colsum_batch(const SplitKColsumJob* jobs, int n, const float* ones, float* partial, size_t partial_floats, hipStream_t st);
 
 // Up to ten products C_j = A_j B_j^T (element strides as in sgemm) as one split-K launch of the 64 x 64 tile kernel + one reduction launch:
 // the parameter gradients of a small model, each of which is a 5-8 us launch pair at its latency floor.  Deterministic (fixed slices,
@@ -70,25 +70,25 @@ struct SplitKJob {
     int M, N, K;
 };
 size_t sgemm_splitk_batch_floats(const SplitKJob* jobs, int n);
-int sgemm_splitk_batch(const SplitKJob* jobs, int n, float* partial, size_t partial_floats, hipStream_t st);
+[[nodiscard]] int sgemm_splitk_batch(const SplitKJob* jobs, int n, float* partial, size_t partial_floats, hipStream_t st);
 // ... the product launch alone; *reduce (reduce_device.hpp: ReduceBatch, reduce->first[n] workgroups of 1024 threads) describes the slice sums
 // for a kernel of the caller that runs reduce_slices_batch_body beside its own last reductions
 struct ReduceBatch;
-int sgemm_splitk_batch_products(const SplitKJob* jobs, int n, float* partial, size_t partial_floats, hipStream_t st, ReduceBatch* reduce);
+[[nodiscard]] int sgemm_splitk_batch_products(const SplitKJob* jobs, int n, float* partial, size_t partial_floats, hipStream_t st, ReduceBatch* reduce);
 
 // out[e] = sum_r part[r * ld + e] over `rows` partial rows (fixed order); out[0] = sum(v[0..n)) with one workgroup (fixed order)
-int rows_sum(const float* part, int rows, int64_t ld, int n, float* out, hipStream_t st);
-int rows_sum2(const float* partA, float* outA, const float* partB, float* outB, int rows, int64_t ld, int n, hipStream_t st);
+[[nodiscard]] int rows_sum(const float* part, int rows, int64_t ld, int n, float* out, hipStream_t st);
+[[nodiscard]] int rows_sum2(const float* partA, float* outA, const float* partB, float* outB, int rows, int64_t ld, int n, hipStream_t st);
 // ... plus a third sum of another shape whose result is written twice (outC and, if given, outC2)
-int rows_sum3(const float* partA, float* outA, const float* partB, float* outB, int rows, int64_t ld, int n, const float* partC, float* outC,
+[[nodiscard]] int rows_sum3(const float* partA, float* outA, const float* partB, float* outB, int rows, int64_t ld, int n, const float* partC, float* outC,
               float* outC2, int rowsC, int64_t ldC, int nC, hipStream_t st);
 // three sums of different shapes in one launch
-int rows_sum_three(const float* const part[3], float* const out[3], const int rows[3], const int64_t ld[3], const int n[3], hipStream_t st);
+[[nodiscard]] int rows_sum_three(const float* const part[3], float* const out[3], const int rows[3], const int64_t ld[3], const int n[3], hipStream_t st);
 // dst[c] = sum_r src[r][c] of a short row-major matrix with ONE workgroup.  A thread walks rows * C / 1024 elements alone: beyond
 // ~64 of them the split-K pair wins again (10 240 rows x 50 columns: > 100 us)
 inline bool cols_sum_small_ok(int64_t rows, int C) { return C >= 1 && C <= 64 && rows * C <= 65536; }
-int cols_sum_small(const float* src, int rows, int C, float* dst, hipStream_t st);
-int block_sum(const float* v, int64_t n, float* out, hipStream_t st);
+[[nodiscard]] int cols_sum_small(const float* src, int rows, int C, float* dst, hipStream_t st);
+[[nodiscard]] int block_sum(const float* v, int64_t n, float* out, hipStream_t st);
 
 // ---- scratch sizing (host) ----------------------------------------------------------------------------------------------------
 constexpr int SKT_ROWS = 128;

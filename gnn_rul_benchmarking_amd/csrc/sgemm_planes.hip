@@ -18,7 +18,7 @@
 //      that the four column tiles of a row panel run on one XCD (they share the panel's A planes in that XCD's L2).
 //
 // Shapes: M a multiple of 160 or 128, N of 256, every k slice of 32; anything else stays on sgemm_f16x2v_kernel (sgemm.hip).
-#include "launch.hpp"
+#include "host_util.hpp"
 #include "sgemm_mfma.hpp"
 
 namespace rulgnn {
@@ -325,13 +325,11 @@ static int pl_split_operand(const float* src, int64_t s_row, int64_t s_k, int ro
     if (s_k == 1 && s_row % 4 == 0 && K % 8 == 0) {
         const int64_t oct = (int64_t)rows * (K / 8);
         const int blocks = (int)((oct + 255) / 256 < 4096 ? (oct + 255) / 256 : 4096);
-        hipLaunchKernelGGL(split_planes_direct_kernel, dim3(blocks), dim3(256), 0, st, a);
-        return RULGNN_OK;
+        return launch_checked(split_planes_direct_kernel, dim3(blocks), dim3(256), 0, st, a);
     }
     if (s_row == 1 && s_k % 4 == 0 && rows % 64 == 0 && K % 64 == 0) {
         const int tiles = (rows / 64) * (K / 64);
-        hipLaunchKernelGGL(split_planes_transposed_kernel, dim3(tiles < 4096 ? tiles : 4096), dim3(256), 0, st, a);
-        return RULGNN_OK;
+        return launch_checked(split_planes_transposed_kernel, dim3(tiles < 4096 ? tiles : 4096), dim3(256), 0, st, a);
     }
     return RULGNN_EUNSUPPORTED;
 }
@@ -366,7 +364,6 @@ int sgemm_planes(const float* A, int64_t sAm, int64_t sAk, const float* B, int64
     _Float16* Alo = Ahi + (size_t)M * K;
     _Float16* Bhi = Alo + (size_t)M * K;
     _Float16* Blo = Bhi + (size_t)N * K;
-    (void)hipGetLastError();
     int rc = a_presplit ? RULGNN_OK : pl_split_operand(A, sAm, sAk, M, K, amax_a, amax_na, Ahi, Alo, scales, st);
     if (rc != RULGNN_OK) return rc;
     rc = pl_split_operand(B, sBn, sBk, N, K, amax_b, amax_nb, Bhi, Blo, scales + 64, st);
@@ -376,8 +373,7 @@ int sgemm_planes(const float* A, int64_t sAm, int64_t sAk, const float* B, int64
     const int grid = g.tiles_m * g.tiles_n * slices;
     auto go = [&](auto kernel, size_t lds) -> int {
         if (const int allowed = allow_dynamic_lds(kernel, lds); allowed != RULGNN_OK) return allowed;
-        hipLaunchKernelGGL(kernel, dim3(grid), dim3(512), lds, st, g);
-        return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+        return launch_checked(kernel, dim3(grid), dim3(512), lds, st, g);
     };
     if (mb == 5) return go(sgemm_planes_kernel<5>, (size_t)3 * (2 * 160 * 64 + 2 * 256 * 64));
     return go(sgemm_planes_kernel<4>, (size_t)3 * (2 * 128 * 64 + 2 * 256 * 64));

@@ -1528,13 +1528,11 @@ int Stagnn::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
     const int T = g.T, TP = g.T | 1, Hd = g.heads;
     const dim3 grid((unsigned)g.nblk), blk(TB);
     const float* stage_in[2] = {ws + g.w_G, ws + g.w_e[0]};
-    (void)hipGetLastError();
     if (mode & 1) {
         const int G = tg_head_groups(g, false);
         const size_t lg = tg_lds_graph_fwd(g, G);
         RULGNN_TRY(allow_dynamic_lds(tg_graph_fwd_kernel, lg));
-        hipLaunchKernelGGL(tg_graph_fwd_kernel, grid, dim3(TB * G), lg, st, g, G, a->x, prm, ws);
-        RULGNN_LAUNCH_OK();
+        RULGNN_TRY(launch_checked(tg_graph_fwd_kernel, grid, dim3(TB * G), lg, st, g, G, a->x, prm, ws));
         for (int l = 0; l < 2; ++l) {
             const int Ci = g.Ci[l], Co = g.Co[l];
             const size_t l1 = sizeof(float) * ((size_t)Ci * TP + (size_t)Co * TP + 2 * (size_t)Co * Ci);
@@ -1546,20 +1544,18 @@ int Stagnn::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
             if (tg_conv1_mx_ok(g, l)) {
                 const size_t l1m = tg_conv1_fwd_mx_lds(g, l);
                 RULGNN_TRY(allow_dynamic_lds(tg_conv1_fwd_mx_kernel, l1m));
-                hipLaunchKernelGGL(tg_conv1_fwd_mx_kernel, grid, blk, l1m, st, g, l, stage_in[l], prm, ws);
+                RULGNN_TRY(launch_checked(tg_conv1_fwd_mx_kernel, grid, blk, l1m, st, g, l, stage_in[l], prm, ws));
             } else
-            hipLaunchKernelGGL(tg_conv1_fwd_kernel, grid, blk, l1, st, g, l, stage_in[l], prm, ws);
+            RULGNN_TRY(launch_checked(tg_conv1_fwd_kernel, grid, blk, l1, st, g, l, stage_in[l], prm, ws));
             if (tg_mid_mx_ok(g, l)) {
                 RULGNN_TRY(allow_dynamic_lds(tg_mid_fwd_mx_kernel, TM_FWD_LDS));
-                hipLaunchKernelGGL(tg_mid_fwd_mx_kernel, grid, blk, TM_FWD_LDS, st, g, l, stage_in[l], prm, (const float*)a->bn_state, ws, training);
+                RULGNN_TRY(launch_checked(tg_mid_fwd_mx_kernel, grid, blk, TM_FWD_LDS, st, g, l, stage_in[l], prm, (const float*)a->bn_state, ws, training));
             } else
-            hipLaunchKernelGGL(tg_mid_fwd_kernel, grid, blk, l2, st, g, l, stage_in[l], prm, (const float*)a->bn_state, ws, training);
-            hipLaunchKernelGGL(tg_end_fwd_kernel, grid, blk, l3, st, g, l, prm, (const float*)a->bn_state, ws, training, a->y, a->pred, inv_gb);
-            RULGNN_LAUNCH_OK();
+            RULGNN_TRY(launch_checked(tg_mid_fwd_kernel, grid, blk, l2, st, g, l, stage_in[l], prm, (const float*)a->bn_state, ws, training));
+            RULGNN_TRY(launch_checked(tg_end_fwd_kernel, grid, blk, l3, st, g, l, prm, (const float*)a->bn_state, ws, training, a->y, a->pred, inv_gb));
         }
-        if (training && a->update_running_stats) hipLaunchKernelGGL(tg_running_kernel, dim3(4), dim3(TB), 0, st, g, (const float*)ws, a->bn_state);
-        if (a->y && a->loss) (void)block_sum((const float*)(ws + g.w_sq), g.B, a->loss, st);
-        RULGNN_LAUNCH_OK();
+        if (training && a->update_running_stats) RULGNN_TRY(launch_checked(tg_running_kernel, dim3(4), dim3(TB), 0, st, g, (const float*)ws, a->bn_state));
+        if (a->y && a->loss) RULGNN_TRY(block_sum((const float*)(ws + g.w_sq), g.B, a->loss, st));
     }
     if (mode & 2) {
         if (!a->grads) return RULGNN_EINVAL;
@@ -1575,25 +1571,23 @@ int Stagnn::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
             RULGNN_TRY(allow_dynamic_lds(tg_end_bwd_kernel, l3));
             RULGNN_TRY(allow_dynamic_lds(tg_conv1_bwd_kernel, l1));
             // (the gradient w.r.t. a stage's input is written over w_dxin[l], which the next kernel down the chain reads)
-            hipLaunchKernelGGL(tg_end_bwd_kernel, grid, blk, l3, st, g, l, prm, (const float*)a->bn_state, ws, dpred, (const float*)(ws + g.w_dxin[1]));
+            RULGNN_TRY(launch_checked(tg_end_bwd_kernel, grid, blk, l3, st, g, l, prm, (const float*)a->bn_state, ws, dpred, (const float*)(ws + g.w_dxin[1])));
             if (tg_mid_mx_ok(g, l)) {
                 RULGNN_TRY(allow_dynamic_lds(tg_mid_bwd_mx_kernel, TM_BWD_LDS));
-                hipLaunchKernelGGL(tg_mid_bwd_mx_kernel, grid, blk, TM_BWD_LDS, st, g, l, stage_in[l], prm, (const float*)a->bn_state, ws);
+                RULGNN_TRY(launch_checked(tg_mid_bwd_mx_kernel, grid, blk, TM_BWD_LDS, st, g, l, stage_in[l], prm, (const float*)a->bn_state, ws));
             } else
-            hipLaunchKernelGGL(tg_mid_bwd_kernel, grid, blk, l2, st, g, l, stage_in[l], prm, (const float*)a->bn_state, ws);
+            RULGNN_TRY(launch_checked(tg_mid_bwd_kernel, grid, blk, l2, st, g, l, stage_in[l], prm, (const float*)a->bn_state, ws));
             if (tg_conv1_mx_ok(g, l)) {
                 const size_t l1m = tg_conv1_bwd_mx_lds(g, l);
                 RULGNN_TRY(allow_dynamic_lds(tg_conv1_bwd_mx_kernel, l1m));
-                hipLaunchKernelGGL(tg_conv1_bwd_mx_kernel, grid, blk, l1m, st, g, l, stage_in[l], prm, (const float*)a->bn_state, ws, ws + g.w_dxin[l]);
+                RULGNN_TRY(launch_checked(tg_conv1_bwd_mx_kernel, grid, blk, l1m, st, g, l, stage_in[l], prm, (const float*)a->bn_state, ws, ws + g.w_dxin[l]));
             } else
-            hipLaunchKernelGGL(tg_conv1_bwd_kernel, grid, blk, l1, st, g, l, stage_in[l], prm, (const float*)a->bn_state, ws, ws + g.w_dxin[l]);
-            RULGNN_LAUNCH_OK();
+            RULGNN_TRY(launch_checked(tg_conv1_bwd_kernel, grid, blk, l1, st, g, l, stage_in[l], prm, (const float*)a->bn_state, ws, ws + g.w_dxin[l]));
         }
         const int G = tg_head_groups(g, true);
         const size_t lg = tg_lds_graph_bwd(g, G);
         RULGNN_TRY(allow_dynamic_lds(tg_graph_bwd_kernel, lg));
-        hipLaunchKernelGGL(tg_graph_bwd_kernel, grid, dim3(TB * G), lg, st, g, G, prm, ws);
-        RULGNN_LAUNCH_OK();
+        RULGNN_TRY(launch_checked(tg_graph_bwd_kernel, grid, dim3(TB * G), lg, st, g, G, prm, ws));
         RULGNN_TRY(rows_sum(ws + g.w_gpart, g.nblk, g.pcount, g.pcount, a->grads, st));
     }
     return RULGNN_OK;

@@ -427,23 +427,22 @@ int Stconv::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
     const int training = a->training ? 1 : 0;
     const int N = g.N, T = g.T, M = (int)(g.B * N);
     const float inv_gb = 1.0f / (float)(a->global_batch > 0 ? a->global_batch : g.B);
-    (void)hipGetLastError();
     const int rows = resident_rows(sc_cnn_bwd_kernel, AB, 0, g.B, w.rows);
     if (mode & 1) {
         if (hipMemsetAsync(cells, 0, w.one - w.cells, st) != hipSuccess) return RULGNN_EHIP;     // both cell blocks
-        hipLaunchKernelGGL(sc_graph_kernel, dim3(rows), dim3(AB), 0, st, g, a->x, F(w.ax));
+        RULGNN_TRY(launch_checked(sc_graph_kernel, dim3(rows), dim3(AB), 0, st, g, a->x, F(w.ax)));
         RULGNN_TRY(sgemm(F(w.ax), T, 1, prm + g.o_gw, T, 1, F(w.gpre), T, M, T, T, false, st));
-        hipLaunchKernelGGL(sc_cnn_kernel, dim3(rows), dim3(AB), 0, st, g, prm, F(w.gpre), F(w.zc), c3, training);
-        hipLaunchKernelGGL((tcn_conv_kernel<1, ScGeom>), dim3(rows), dim3(AB), 0, st, g, a->x, prm, a->bn_stats, training,
-                           (const float*)nullptr, F(w.z1), (float*)nullptr, cells);
-        hipLaunchKernelGGL((tcn_conv_kernel<2, ScGeom>), dim3(rows), dim3(AB), 0, st, g, a->x, prm, a->bn_stats, training,
-                           (const float*)F(w.z1), F(w.z2), F(w.out0), cells);
-        hipLaunchKernelGGL(sc_head_kernel<0>, dim3(rows), dim3(AB), 0, st, g, a->x, prm, a->bn_stats, training, cells, c3,
-                           (const float*)F(w.zc), (const float*)F(w.z2), (const float*)F(w.out0), a->y, F(w.res), a->pred, F(w.dpred),
-                           F(w.sqerr), (float*)nullptr, (float*)nullptr, (float*)nullptr, inv_gb);
+        RULGNN_TRY(launch_checked(sc_cnn_kernel, dim3(rows), dim3(AB), 0, st, g, prm, F(w.gpre), F(w.zc), c3, training));
+        RULGNN_TRY(launch_checked((tcn_conv_kernel<1, ScGeom>), dim3(rows), dim3(AB), 0, st, g, a->x, prm, a->bn_stats, training,
+                                  (const float*)nullptr, F(w.z1), (float*)nullptr, cells));
+        RULGNN_TRY(launch_checked((tcn_conv_kernel<2, ScGeom>), dim3(rows), dim3(AB), 0, st, g, a->x, prm, a->bn_stats, training,
+                                  (const float*)F(w.z1), F(w.z2), F(w.out0), cells));
+        RULGNN_TRY(launch_checked(sc_head_kernel<0>, dim3(rows), dim3(AB), 0, st, g, a->x, prm, a->bn_stats, training, cells, c3,
+                                  (const float*)F(w.zc), (const float*)F(w.z2), (const float*)F(w.out0), a->y, F(w.res), a->pred, F(w.dpred),
+                                  F(w.sqerr), (float*)nullptr, (float*)nullptr, (float*)nullptr, inv_gb));
         if (training && a->bn_batch)
-            hipLaunchKernelGGL(sc_bn_batch_kernel, dim3(1), dim3(128), 0, st, g, (const Cells*)cells, (const Cells3*)c3, a->bn_batch,
-                               a->bn_moment_weight);
+            RULGNN_TRY(launch_checked(sc_bn_batch_kernel, dim3(1), dim3(128), 0, st, g, (const Cells*)cells, (const Cells3*)c3, a->bn_batch,
+                                      a->bn_moment_weight));
     }
     if (mode & 2) {
         float* gr = a->grads;
@@ -455,16 +454,16 @@ int Stconv::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
         // fc: d weight = dpred^T res ; d bias = sum dpred
         RULGNN_TRY(sgemm_splitk(F(w.dpred), 0, 1, F(w.res), 1, g.NT, gr + g.o_fcw, g.NT, 1, g.NT, (int)g.B, false, split, st));
         RULGNN_TRY(sgemm_splitk(F(w.dpred), 0, 1, one, 0, 0, gr + g.o_fcb, 1, 1, 1, (int)g.B, false, split, st));
-        hipLaunchKernelGGL(sc_head_kernel<1>, dim3(rows), dim3(AB), 0, st, g, a->x, prm, a->bn_stats, 1, cells, c3, (const float*)F(w.zc),
-                           (const float*)F(w.z2), (const float*)F(w.out0), (const float*)nullptr, (float*)nullptr, (float*)nullptr,
-                           F(w.dpred), (float*)nullptr, F(w.ds1), F(w.dy2), F(w.dyc), inv_gb);
-        hipLaunchKernelGGL((tcn_conv_bwd_kernel<2, ScGeom>), dim3(rows), dim3(AB), 0, st, g, prm, cells, (const float*)F(w.z2),
-                           (const float*)F(w.dy2), (const float*)F(w.out0), (const float*)F(w.ds1), (const float*)F(w.z1), F(w.dy1),
-                           F(w.gp2));
-        hipLaunchKernelGGL((tcn_conv_bwd_kernel<1, ScGeom>), dim3(rows), dim3(AB), 0, st, g, prm, cells, (const float*)F(w.z1),
-                           (const float*)F(w.dy1), a->x, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, F(w.gp1));
-        hipLaunchKernelGGL(sc_cnn_bwd_kernel, dim3(rows), dim3(AB), 0, st, g, prm, (const Cells3*)c3, (const float*)F(w.zc),
-                           (const float*)F(w.dyc), F(w.gpre), F(w.gp3));
+        RULGNN_TRY(launch_checked(sc_head_kernel<1>, dim3(rows), dim3(AB), 0, st, g, a->x, prm, a->bn_stats, 1, cells, c3, (const float*)F(w.zc),
+                                  (const float*)F(w.z2), (const float*)F(w.out0), (const float*)nullptr, (float*)nullptr, (float*)nullptr,
+                                  F(w.dpred), (float*)nullptr, F(w.ds1), F(w.dy2), F(w.dyc), inv_gb));
+        RULGNN_TRY(launch_checked((tcn_conv_bwd_kernel<2, ScGeom>), dim3(rows), dim3(AB), 0, st, g, prm, cells, (const float*)F(w.z2),
+                                  (const float*)F(w.dy2), (const float*)F(w.out0), (const float*)F(w.ds1), (const float*)F(w.z1), F(w.dy1),
+                                  F(w.gp2)));
+        RULGNN_TRY(launch_checked((tcn_conv_bwd_kernel<1, ScGeom>), dim3(rows), dim3(AB), 0, st, g, prm, cells, (const float*)F(w.z1),
+                                  (const float*)F(w.dy1), a->x, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, F(w.gp1)));
+        RULGNN_TRY(launch_checked(sc_cnn_bwd_kernel, dim3(rows), dim3(AB), 0, st, g, prm, (const Cells3*)c3, (const float*)F(w.zc),
+                                  (const float*)F(w.dyc), F(w.gpre), F(w.gp3)));
         // theta of the MPNN: d weight = dgpre^T (A X) ; d bias = column sums
         RULGNN_TRY(sgemm_splitk(F(w.gpre), 1, T, F(w.ax), 1, T, gr + g.o_gw, T, T, T, M, false, split, st));
         RULGNN_TRY(sgemm_splitk(one, 0, 0, F(w.gpre), 1, T, gr + g.o_gb, T, 1, T, M, false, split, st));
@@ -479,20 +478,18 @@ int Stconv::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
                 RULGNN_TRY(rows_sum(F(w.gp3) + nW, rows, nW + N, N, gr + g.o_cb, st));
             }
         }
-        hipLaunchKernelGGL(sc_finalize_kernel, dim3((N + 4 + AB - 1) / AB), dim3(AB), 0, st, g, (const Cells*)cells, (const Cells3*)c3, gr);
+        RULGNN_TRY(launch_checked(sc_finalize_kernel, dim3((N + 4 + AB - 1) / AB), dim3(AB), 0, st, g, (const Cells*)cells, (const Cells3*)c3, gr));
         if (!a->dpred && a->loss)
-            (void)block_sum((const float*)F(w.sqerr), (int64_t)g.B, a->loss, st);
+            RULGNN_TRY(block_sum((const float*)F(w.sqerr), (int64_t)g.B, a->loss, st));
     }
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return RULGNN_OK;
 }
 
 int Stconv::bn_running_update(const Shape* s, float* bn_stats, const float* bn_batch, int64_t count, float momentum,
                              int from_moments, hipStream_t st) {
     ScGeom g;
     RULGNN_TRY(sc_geometry(s, &g));
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(sc_bn_running_kernel, dim3(1), dim3(128), 0, st, bn_stats, bn_batch, g.N, (double)count, momentum, from_moments);
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return launch_checked(sc_bn_running_kernel, dim3(1), dim3(128), 0, st, bn_stats, bn_batch, g.N, (double)count, momentum, from_moments);
 }
 
 }  // namespace rulgnn

@@ -20,7 +20,7 @@ struct TileGeom {
     int64_t ntiles;     // wavefront tiles = ceil(batch / SPW)
 };
 
-inline int validate_shape(const rulgnn_stgcn_shape* s) {
+[[nodiscard]] inline int validate_shape(const rulgnn_stgcn_shape* s) {
     if (!s) return RULGNN_EINVAL;
     if (s->batch < 0 || s->num_patch < 2 || s->patch_size < 2 || s->num_layers < 1) return RULGNN_EINVAL;
     if (s->mpnn_k < 1) return RULGNN_EINVAL;
@@ -32,7 +32,7 @@ inline int validate_shape(const rulgnn_stgcn_shape* s) {
     return RULGNN_OK;
 }
 
-inline int tile_geometry(const rulgnn_stgcn_shape* s, TileGeom* g) {
+[[nodiscard]] inline int tile_geometry(const rulgnn_stgcn_shape* s, TileGeom* g) {
     const int rc = validate_shape(s);
     if (rc != RULGNN_OK) return rc;
     const int N = s->num_patch, P = s->patch_size;
@@ -93,22 +93,22 @@ inline int persistent_grid(K kernel, int64_t ntiles, size_t lds_bytes, int overs
 
 // Eval-forward path selection (include/rulgnn.h: RULGNN_EVAL_*): AUTO = matrix-core kernel when the shape qualifies.
 enum { STGCN_EVAL_AUTO = RULGNN_EVAL_AUTO, STGCN_EVAL_EXACT = RULGNN_EVAL_EXACT, STGCN_EVAL_MX = RULGNN_EVAL_MX };
-int stgcn_forward_eval(const rulgnn_stgcn_shape* s, const float* x, const float* prm, const float* bn, float* out,
+[[nodiscard]] int stgcn_forward_eval(const rulgnn_stgcn_shape* s, const float* x, const float* prm, const float* bn, float* out,
                        hipStream_t stream, int path = STGCN_EVAL_AUTO);
 // Matrix-core kernel (stgcn_forward_mx.hip); RULGNN_EUNSUPPORTED when the shape does not qualify (nothing launched).
 // `taps`: optional debug buffer, MX_TAP_FLOATS floats (raw register dumps of the first tile, see the kernel).
-int stgcn_forward_eval_mx(const rulgnn_stgcn_shape* s, const float* x, const float* prm, const float* bn, float* out,
+[[nodiscard]] int stgcn_forward_eval_mx(const rulgnn_stgcn_shape* s, const float* x, const float* prm, const float* bn, float* out,
                           hipStream_t stream, float* taps = nullptr);
 int stgcn_forward_mx_tap_floats();
 // The matrix-core eval forward for 16 <= num_patch <= 47 (stgcn_forward_mx.hip) and the scanning launch that follows it: every
 // non-finite prediction is recomputed by the exact row-mapped routine (stgcn_forward.hip).
-int stgcn_forward_eval_mxw(const rulgnn_stgcn_shape* s, const float* x, const float* prm, const float* bn, float* out, hipStream_t stream);
-int stgcn_forward_fixup(const rulgnn_stgcn_shape* s, const float* x, const float* prm, const float* bn, float* out, hipStream_t stream);
+[[nodiscard]] int stgcn_forward_eval_mxw(const rulgnn_stgcn_shape* s, const float* x, const float* prm, const float* bn, float* out, hipStream_t stream);
+[[nodiscard]] int stgcn_forward_fixup(const rulgnn_stgcn_shape* s, const float* x, const float* prm, const float* bn, float* out, hipStream_t stream);
 // Training phase F_0 on the matrix cores (stgcn_forward_mx.hip); RULGNN_EUNSUPPORTED when the shape is outside its rules
-int stgcn_train_f0_mx(const rulgnn_stgcn_shape* s, const float* x, const float* prm, float* cacheX, float* cacheA, float* H0, float* Z1,
+[[nodiscard]] int stgcn_train_f0_mx(const rulgnn_stgcn_shape* s, const float* x, const float* prm, float* cacheX, float* cacheA, float* H0, float* Z1,
                       double* cells_bn0, int cell_stride_doubles, int replicas, hipStream_t stream);
 size_t stgcn_tiled_forward_workspace_bytes(const rulgnn_stgcn_shape* s);
-int stgcn_tiled_forward_eval(const rulgnn_stgcn_shape* s, const float* x, const float* prm, const float* bn, float* pred,
+[[nodiscard]] int stgcn_tiled_forward_eval(const rulgnn_stgcn_shape* s, const float* x, const float* prm, const float* bn, float* pred,
                              void* workspace, size_t workspace_bytes, hipStream_t stream);
 size_t stgcn_tiled_train_workspace_bytes(const rulgnn_stgcn_shape* s);
 // optional "these gradients are final" callback of the tiled training step (include/rulgnn.h: rulgnn_grad_ready_fn)
@@ -117,7 +117,7 @@ struct GradReadyHook {
     void* user;
 };
 // (`sync` != nullptr, synchronised BatchNorm -- SyncHook, bn_cells.hpp: whole steps only, mode 2; the reduction pairs are 2 F doubles)
-int stgcn_tiled_train(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args* a, int mode, hipStream_t stream,
+[[nodiscard]] int stgcn_tiled_train(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args* a, int mode, hipStream_t stream,
                       const GradReadyHook* ready = nullptr, const SyncHook* sync = nullptr);
 size_t stgcn_train_workspace_bytes(const rulgnn_stgcn_shape* s);
 // The LDS bytes a launch form of the fused row-mapped kernels requests at this shape (and MPNN order): the exact eval kernel, the scan
@@ -128,14 +128,14 @@ size_t stgcn_train_workspace_bytes(const rulgnn_stgcn_shape* s);
 size_t stgcn_forward_exact_lds_bytes(const rulgnn_stgcn_shape* s);
 size_t stgcn_forward_fixup_lds_bytes(const rulgnn_stgcn_shape* s);
 size_t stgcn_train_chain_lds_bytes(const rulgnn_stgcn_shape* s);
-int stgcn_train_forward(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args* a, hipStream_t stream);
-int stgcn_train_backward(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args* a, hipStream_t stream);
-int stgcn_train_fwdbwd(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args* a, hipStream_t stream);
-int stgcn_train_step(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args* a, const rulgnn_adam_args* opt,
+[[nodiscard]] int stgcn_train_forward(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args* a, hipStream_t stream);
+[[nodiscard]] int stgcn_train_backward(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args* a, hipStream_t stream);
+[[nodiscard]] int stgcn_train_fwdbwd(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args* a, hipStream_t stream);
+[[nodiscard]] int stgcn_train_step(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args* a, const rulgnn_adam_args* opt,
                      hipStream_t stream, int path = RULGNN_STEP_AUTO);     // opt == nullptr: forward + backward only
-int stgcn_train_phase(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args* a, int phase, hipStream_t stream,
+[[nodiscard]] int stgcn_train_phase(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args* a, int phase, hipStream_t stream,
                       int path = RULGNN_STEP_AUTO);
-int stgcn_train_fwdbwd_syncbn(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args* a, const SyncHook* hook, hipStream_t stream,
+[[nodiscard]] int stgcn_train_fwdbwd_syncbn(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args* a, const SyncHook* hook, hipStream_t stream,
                               int path = RULGNN_STEP_CHAIN);
 int stgcn_train_mx_kind(const rulgnn_stgcn_shape* s, const float* x);        // 0 fp32 phases, 1 matrix-core chain, 2 wide matrix-core chain
 int64_t stgcn_train_guard_counter_offset(const rulgnn_stgcn_shape* s);

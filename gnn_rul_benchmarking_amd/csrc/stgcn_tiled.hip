@@ -472,12 +472,7 @@ size_t stgcn_tiled_forward_workspace_bytes(const rulgnn_stgcn_shape* s) {
 }
 
 // (persistent kernels: at most T_PGRID workgroups)
-#define T_LAUNCH_P(kern, n, ...)                                                                            \
-    do {                                                                                                    \
-        (void)hipGetLastError();                                                                            \
-        hipLaunchKernelGGL(kern, dim3((unsigned)t_pgrid(n)), dim3(256), 0, stream, __VA_ARGS__);            \
-        if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;                                            \
-    } while (0)
+#define T_LAUNCH_P(kern, n, ...) RULGNN_TRY(launch_checked(kern, dim3((unsigned)t_pgrid(n)), dim3(256), 0, stream, __VA_ARGS__))
 // patch statistics: the LDS-staged form for the wirings' patch sizes (x 16-byte aligned), the per-thread walk otherwise
 #define T_STATS(xp, X0p)                                                                                    \
     do {                                                                                                    \
@@ -485,12 +480,7 @@ size_t stgcn_tiled_forward_workspace_bytes(const rulgnn_stgcn_shape* s) {
         else if (a.P == 16 && (reinterpret_cast<uintptr_t>(xp) & 15) == 0) T_LAUNCH(t_stats_lds_kernel<16>, BN_, xp, X0p, a); \
         else T_LAUNCH(t_stats_kernel, BN_, xp, X0p, a);                                                     \
     } while (0)
-#define T_LAUNCH(kern, n, ...)                                                                              \
-    do {                                                                                                    \
-        (void)hipGetLastError();                                                                            \
-        hipLaunchKernelGGL(kern, dim3((unsigned)(((n) + 255) / 256)), dim3(256), 0, stream, __VA_ARGS__);   \
-        if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;                                            \
-    } while (0)
+#define T_LAUNCH(kern, n, ...) RULGNN_TRY(launch_checked(kern, dim3((unsigned)(((n) + 255) / 256)), dim3(256), 0, stream, __VA_ARGS__))
 
 int stgcn_tiled_forward_eval(const rulgnn_stgcn_shape* s, const float* x, const float* prm, const float* bn, float* pred,
                              void* workspace, size_t workspace_bytes, hipStream_t stream) {
@@ -519,10 +509,8 @@ int stgcn_tiled_forward_eval(const rulgnn_stgcn_shape* s, const float* x, const 
 
     T_LAUNCH(t_bnfold_kernel, L * 2 * F, prm, bn, bnf, N, L);
     if (scaled) {
-        (void)hipGetLastError();
-        hipLaunchKernelGGL(t_absmax_kernel, dim3(n_th, L), dim3(256), 0, stream, prm, (int64_t)LS, (int64_t)off_theta_w(N), (int64_t)N * N,
-                           amax + T_AMAX_MAX, (double*)nullptr, 0);
-        if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
+        RULGNN_TRY(launch_checked(t_absmax_kernel, dim3(n_th, L), dim3(256), 0, stream, prm, (int64_t)LS, (int64_t)off_theta_w(N), (int64_t)N * N,
+                                  amax + T_AMAX_MAX, (double*)nullptr, 0));
     }
     // theta(A.X) on pre-split operands with the A planes written by the aggregation itself (t_aggregate_planes_kernel: no split pass, no
     // fp32 A.X; XJTU-SY batch 1024: 2 x (22 + 17) us of aggregation + split pass become 2 x ~25): needs max |X_l| from the launch in front
@@ -530,10 +518,8 @@ int stgcn_tiled_forward_eval(const rulgnn_stgcn_shape* s, const float* x, const 
                               sgemm_planes_slices((int)(B * F), N, N, false) == 1 &&
                               sgemm_planes_ok(AX, N, 1, prm + off_theta_w(N), N, 1, (int)(B * F), N, N, 1);
     T_STATS(x, Xa);
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(t_gram_kernel, dim3((unsigned)B), dim3(256), 0, stream, Xa, A, a, (float*)nullptr, (float*)nullptr,
-                       fused_planes ? amaxX : (float*)nullptr);
-    if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
+    RULGNN_TRY(launch_checked(t_gram_kernel, dim3((unsigned)B), dim3(256), 0, stream, Xa, A, a, (float*)nullptr, (float*)nullptr,
+                              fused_planes ? amaxX : (float*)nullptr));
     float* Xin = Xa;
     float* Xout = Xb;
     for (int l = 0; l < L; ++l) {
@@ -553,7 +539,7 @@ int stgcn_tiled_forward_eval(const rulgnn_stgcn_shape* s, const float* x, const 
             float* tmp = Xin; Xin = Xout; Xout = tmp;
             continue;
         }
-        T_LAUNCH(t_aggregate_kernel, BN_, A, Xin, (const float*)nullptr, AX, a, scaled ? amax : (float*)nullptr);
+        T_LAUNCH(t_aggregate_kernel, BN_, A, Xin, (const float*)nullptr, AX, a, scaled ? amax : (float*)nullptr, (const float*)nullptr, (const float*)nullptr);
         if (few_rows)
             rc = sgemm_splitk(AX, N, 1, pl + off_theta_w(N), N, 1, Hpre, N, (int)(B * F), N, N, false, split, stream, scaled ? amax : (float*)nullptr,
                               n_pos, scaled ? amax + (size_t)(1 + l) * T_AMAX_MAX : (float*)nullptr, n_th);
@@ -566,9 +552,7 @@ int stgcn_tiled_forward_eval(const rulgnn_stgcn_shape* s, const float* x, const 
     }
     int rc = sgemm_splitk(pooled, N, 1, prm + off_fc1_w(N, L), N, 1, y1pre, N, (int)B, N, N, false, split, stream);          // fc1
     if (rc != RULGNN_OK) return rc;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(t_head_kernel, dim3((unsigned)B), dim3(256), 0, stream, y1pre, prm, pred, a);
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return launch_checked(t_head_kernel, dim3((unsigned)B), dim3(256), 0, stream, y1pre, prm, pred, a);
 }
 
 
@@ -1394,25 +1378,21 @@ int stgcn_tiled_train(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args
         }
         if (!scaled && hipMemsetAsync(cells, 0, w.cells_bytes, stream) != hipSuccess) return RULGNN_EHIP;
         if (scaled) {
-            (void)hipGetLastError();
             // (theta of every layer and, as "layer L" of the same stride, fc1.weight)
             static_assert(off_theta_w(1) == 0 && off_fc1_w(7, 3) == 3 * layer_stride(7), "fc1.weight sits where a layer-L theta would");
-            hipLaunchKernelGGL(t_absmax_kernel, dim3(n_th, L + 1), dim3(256), 0, stream, prm, (int64_t)LS, (int64_t)off_theta_w(N), (int64_t)N * N, am_th(0),
-                               cells, (int)(w.cells_bytes / sizeof(double)));
-            if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
+            RULGNN_TRY(launch_checked(t_absmax_kernel, dim3(n_th, L + 1), dim3(256), 0, stream, prm, (int64_t)LS, (int64_t)off_theta_w(N), (int64_t)N * N, am_th(0),
+                                      cells, (int)(w.cells_bytes / sizeof(double))));
         }
         T_STATS(ar->x, TP(w.off_X, 0));
-        (void)hipGetLastError();
         // (+ the first layer's aggregation and its operand-scale row, one entry per sample, where the batch fits a row)
         const bool agg0 = scaled && B <= T_AMAX_MAX;
-        hipLaunchKernelGGL(t_gram_kernel, dim3((unsigned)B), dim3(256), 0, stream, TP(w.off_X, 0), A, a, agg0 ? TP(w.off_AX, 0) : (float*)nullptr,
-                           agg0 ? am_ax(0) : (float*)nullptr);
-        if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
+        RULGNN_TRY(launch_checked(t_gram_kernel, dim3((unsigned)B), dim3(256), 0, stream, TP(w.off_X, 0), A, a, agg0 ? TP(w.off_AX, 0) : (float*)nullptr,
+                                  agg0 ? am_ax(0) : (float*)nullptr, (float*)nullptr));
         for (int l = 0; l < L; ++l) {
             const float* pl = prm + l * LS;
             t.drop_key = dropout_layer_key(ar->seed, ar->step, l);
             t.key_dev = sstate ? &sstate->drop_key[l] : nullptr;
-            if (l == 0 && !agg0) T_LAUNCH(t_aggregate_kernel, BN_, A, TP(w.off_X, l), (const float*)nullptr, TP(w.off_AX, l), a, am_ax(0));
+            if (l == 0 && !agg0) T_LAUNCH(t_aggregate_kernel, BN_, A, TP(w.off_X, l), (const float*)nullptr, TP(w.off_AX, l), a, am_ax(0), (const float*)nullptr, (const float*)nullptr);
             float* const Hpl = TP(w.off_H, l);             // the layer's slot keeps the product's output: H = leaky(Hpre + bias) is re-derived by its readers
             if (few_rows)
                 rc = sgemm_splitk(TP(w.off_AX, l), N, 1, pl + off_theta_w(N), N, 1, Hpl, N, (int)(B * F), N, N, false, split, stream, am_ax(l),
@@ -1438,10 +1418,8 @@ int stgcn_tiled_train(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args
         if (hipMemsetAsync(t.cells_bwd, 0, sizeof(double) * T_REP * tc_sb(L), stream) != hipSuccess) return RULGNN_EHIP;
     }
     // head (also recomputed by a backward-only call: cheap, gives dpred for the incoming gradient)
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(t_head_train_kernel, dim3((unsigned)B), dim3(256), 0, stream, y1pre, prm, gy, has_dpred, y1, ar->pred, dpredb,
-                       dy1, t, one, am_dy1);
-    if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
+    RULGNN_TRY(launch_checked(t_head_train_kernel, dim3((unsigned)B), dim3(256), 0, stream, y1pre, prm, gy, has_dpred, y1, ar->pred, dpredb,
+                              dy1, t, one, am_dy1));
 
     if (mode != 0) {
         float* g = ar->grads;
@@ -1516,7 +1494,7 @@ int stgcn_tiled_train(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args
                 // (A^T dAX + dXn, A symmetric.  Folded into the tail kernel of the layer below it cost more there -- 100 adjacency loads and
                 // 100 FMAs per position inside the persistent loop: +22 us -- than this launch takes)
                 if (l == L - 1) T_LAUNCH(t_aggregate_kernel, BN_, A, dAX, (const float*)nullptr, dX, a, (float*)nullptr, (const float*)dpool, (const float*)TP(w.off_X, L));
-                else T_LAUNCH(t_aggregate_kernel, BN_, A, dAX, dX, dX, a, (float*)nullptr);
+                else T_LAUNCH(t_aggregate_kernel, BN_, A, dAX, dX, dX, a, (float*)nullptr, (const float*)nullptr, (const float*)nullptr);
             }
         }
     }
@@ -1531,9 +1509,7 @@ int stgcn_tiled_train(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_args
     f.cell_grad_scale = sync ? sync->bn_param_grad_scale : 1.0f;
     f.write_loss = (has_dpred == 0) && ar->loss && mode != 0;
     f.write_grads = mode != 0;          // forward only: just the batch statistics for the running-stat update
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(t_finalize_kernel, dim3(2 * L * TFIN_SUB), dim3(1024), 0, stream, f);
-    if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
+    RULGNN_TRY(launch_checked(t_finalize_kernel, dim3(2 * L * TFIN_SUB), dim3(1024), 0, stream, f));
     // (the finalize kernel reads the chain's partial rows and cells only: it runs beside the side stream's last products; the parameter
     // gradients are final in `stream` order from here)
     return fk.join();

@@ -1598,7 +1598,6 @@ static int run_train_rw(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_ar
     void* adam_state = fused_adam ? opt->step_state : nullptr;
     if (adam_state && a->step_state && adam_state != a->step_state) return RULGNN_EINVAL;
     StepState* st = static_cast<StepState*>(a->step_state ? a->step_state : adam_state);
-    (void)hipGetLastError();
     // RULGNN_TRAIN_WS_CLEAN: the caller vouches that the previous matrix-core step on this workspace was the last thing to touch it -- its
     // finalize kernel left the cells zero, F_0's workgroup 0 writes the head-of-step scalars (and checks the clean token)
     const bool skip_prepare = use_mx && (a->flags & RULGNN_TRAIN_WS_CLEAN) != 0 && !a->step_state && !adam_state && s->batch > 0;
@@ -1612,19 +1611,17 @@ static int run_train_rw(const rulgnn_stgcn_shape* s, const rulgnn_stgcn_train_ar
     if (skip_prepare) {
     } else if (mode == TM_FORWARD || mode == TM_FWDBWD) {
         // a new forward: all cells, fresh dropout keys (a backward-only call below reuses the keys of its forward)
-        hipLaunchKernelGGL(stgcn_prepare_kernel, dim3(1), dim3(1024), 0, stream, k.cells, 0, cell_stride(L), cell_stride(L), sc,
-                           a->step_state ? st : nullptr, a->seed, a->step, L, 1, fused_adam ? 1 : 0, fused_adam ? opt->step : 0,
-                           fused_adam ? opt->lr : 0.f, fused_adam ? opt->beta1 : 0.f, fused_adam ? opt->beta2 : 0.f, bn_count);
-        if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
+        RULGNN_TRY(launch_checked(stgcn_prepare_kernel, dim3(1), dim3(1024), 0, stream, k.cells, 0, cell_stride(L), cell_stride(L), sc,
+                                  a->step_state ? st : nullptr, a->seed, a->step, L, 1, fused_adam ? 1 : 0, fused_adam ? opt->step : 0,
+                                  fused_adam ? opt->lr : 0.f, fused_adam ? opt->beta1 : 0.f, fused_adam ? opt->beta2 : 0.f, bn_count));
         if (!use_mx) {
             RULGNN_TRY(PhaseChain<RW, L, 2 * L - 1>::forward_stats(k, a->x, a->params, lds, w.max_grid, stream, hook));
         }
     } else {
         // backward after a separate forward: forward cells are valid, clear the backward ones + loss
-        hipLaunchKernelGGL(stgcn_prepare_kernel, dim3(1), dim3(1024), 0, stream, k.cells, cell_bwd(L), cell_stride(L) - cell_bwd(L),
-                           cell_stride(L), sc, (StepState*)nullptr,
-                           a->seed, a->step, L, 0, 0, (int64_t)0, 0.f, 0.f, 0.f, bn_count);
-        if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
+        RULGNN_TRY(launch_checked(stgcn_prepare_kernel, dim3(1), dim3(1024), 0, stream, k.cells, cell_bwd(L), cell_stride(L) - cell_bwd(L),
+                                  cell_stride(L), sc, (StepState*)nullptr,
+                                  a->seed, a->step, L, 0, 0, (int64_t)0, 0.f, 0.f, 0.f, bn_count));
     }
     int grid_top = 0;
     int grids[16] = {0};

@@ -142,9 +142,7 @@ int stgnn_terms(const rulgnn_stgnn_shape* s, const float* x, float* terms, float
     if (g.G == 0) return RULGNN_OK;
     const size_t lds = terms_lds_bytes(g);
     if (lds > 64 * 1024) return RULGNN_EUNSUPPORTED;
-    (void)hipGetLastError();
-    hipLaunchKernelGGL(stgnn_terms_kernel, dim3((unsigned)g.G), dim3(GB), lds, st, g, x, terms, adj);
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return launch_checked(stgnn_terms_kernel, dim3((unsigned)g.G), dim3(GB), lds, st, g, x, terms, adj);
 }
 
 int stgnn_cheb_forward(const rulgnn_stgnn_shape* s, const float* terms, const float* filters, float* out, hipStream_t st) {
@@ -324,17 +322,15 @@ int Stgnn::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
     float* seq = g.L == 1 ? Fp(w.cheb) : Fp(w.seq);          // one patch: the permutation is the identity
     float* dseq = Fp(w.dseq);
     float* dcheb = g.L == 1 ? dseq : Fp(w.dcheb);
-    (void)hipGetLastError();
     if (mode & 1) {
         RULGNN_TRY(stgnn_terms(s, a->x, Fp(w.terms), nullptr, st));
         RULGNN_TRY(stgnn_cheb_forward(s, Fp(w.terms), prm + o.filters, Fp(w.cheb), st));
-        if (g.L > 1) hipLaunchKernelGGL(stgnn_permute_kernel, dim3(gn_blocks(R * g.H)), dim3(GB), 0, st, g, (const float*)Fp(w.cheb), seq, 1);
+        if (g.L > 1) RULGNN_TRY(launch_checked(stgnn_permute_kernel, dim3(gn_blocks(R * g.H)), dim3(GB), 0, st, g, (const float*)Fp(w.cheb), seq, 1));
         ga.x = seq; ga.out = Fp(w.hs);
         RULGNN_TRY(gru_forward(&gs, &ga, st));
         const float inv_gb = 1.0f / (float)(a->global_batch > 0 ? a->global_batch : g.B);
-        hipLaunchKernelGGL(stgnn_head_kernel, dim3((unsigned)g.B), dim3(GB), 0, st, g, (const float*)Fp(w.hs), prm + o.fcw, prm + o.fcb, a->y,
-                           a->pred, Fp(w.dpred), Fp(w.sqerr), inv_gb);
-        if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
+        RULGNN_TRY(launch_checked(stgnn_head_kernel, dim3((unsigned)g.B), dim3(GB), 0, st, g, (const float*)Fp(w.hs), prm + o.fcw, prm + o.fcb, a->y,
+                                  a->pred, Fp(w.dpred), Fp(w.sqerr), inv_gb));
     }
     if (mode & 2) {
         const float* dpred = a->dpred ? a->dpred : Fp(w.dpred);
@@ -344,15 +340,14 @@ int Stgnn::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
         // fc: d w[q] = sum_b dpred[b] flat[b][q], d b = sum_b dpred[b], d flat = dpred (x) w
         RULGNN_TRY(sgemm_splitk(dpred, 0, 1, Fp(w.hs), 1, Q, gr + o.fcw, Q, 1, Q, (int)g.B, false, split, st));
         RULGNN_TRY(sgemm_splitk(dpred, 0, 1, Fp(w.one), 0, 0, gr + o.fcb, 1, 1, 1, (int)g.B, false, split, st));
-        hipLaunchKernelGGL(stgnn_dflat_kernel, dim3(gn_blocks(g.B * Q)), dim3(GB), 0, st, g, dpred, prm + o.fcw, Fp(w.dhs));
+        RULGNN_TRY(launch_checked(stgnn_dflat_kernel, dim3(gn_blocks(g.B * Q)), dim3(GB), 0, st, g, dpred, prm + o.fcw, Fp(w.dhs)));
         ga.x = seq; ga.dout = Fp(w.dhs); ga.dx = dseq;
         ga.dw_ih = gr + o.wih; ga.dw_hh = gr + o.whh; ga.db_ih = gr + o.bih; ga.db_hh = gr + o.bhh;
         RULGNN_TRY(gru_backward(&gs, &ga, st));
-        if (g.L > 1) hipLaunchKernelGGL(stgnn_permute_kernel, dim3(gn_blocks(R * g.H)), dim3(GB), 0, st, g, (const float*)dseq, dcheb, 0);
+        if (g.L > 1) RULGNN_TRY(launch_checked(stgnn_permute_kernel, dim3(gn_blocks(R * g.H)), dim3(GB), 0, st, g, (const float*)dseq, dcheb, 0));
         RULGNN_TRY(stgnn_cheb_backward(s, Fp(w.terms), dcheb, gr + o.filters, split, sgemm_splitk_partial_floats(g.KF, g.H) * sizeof(float), st));
         if (!a->dpred && a->loss)
-            (void)block_sum((const float*)Fp(w.sqerr), (int64_t)g.B, a->loss, st);
-        if (hipGetLastError() != hipSuccess) return RULGNN_EHIP;
+            RULGNN_TRY(block_sum((const float*)Fp(w.sqerr), (int64_t)g.B, a->loss, st));
     }
     return RULGNN_OK;
 }

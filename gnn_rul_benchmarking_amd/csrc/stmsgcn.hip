@@ -1598,8 +1598,7 @@ static int launch_features_tw(const MsgGeom& g, const float* x, const float* prm
     const size_t lds = features_lds_bytes(g);
     RULGNN_TRY(allow_dynamic_lds(msg_features_kernel<TW>, lds));
     const int grid = resident_rows(msg_features_kernel<TW>, MB, lds, g.G, 1 << 20);
-    hipLaunchKernelGGL(msg_features_kernel<TW>, dim3(grid), dim3(MB), lds, st, g, x, prm, cat, gi);
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return launch_checked(msg_features_kernel<TW>, dim3(grid), dim3(MB), lds, st, g, x, prm, cat, gi);
 }
 static int launch_features(const MsgGeom& g, const float* x, const float* prm, float* cat, float* gi, hipStream_t st) {
     size_t lds = 0;
@@ -1608,8 +1607,7 @@ static int launch_features(const MsgGeom& g, const float* x, const float* prm, f
             RULGNN_TRY(allow_dynamic_lds(kern, lds));
             const int64_t need = (g.G + MXW - 1) / MXW;
             const int grid = resident_rows(kern, 64 * MXW, lds, need, need);
-            hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * MXW), lds, st, g, x, prm, cat, gi);
-            return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+            return launch_checked(kern, dim3((unsigned)grid), dim3(64 * MXW), lds, st, g, x, prm, cat, gi);
         };
         return MsgXJ::matches(g) ? go(&msg_features_mx_kernel<true>) : go(&msg_features_mx_kernel<false>);   // (the XJTU-SY layer shapes as constants)
     }
@@ -1622,27 +1620,26 @@ static int launch_gcn_backward(const MsgGeom& g, int rows_max, const float* cat,
     const size_t lds = gcn_backward_lds_bytes(g);
     RULGNN_TRY(allow_dynamic_lds(msg_gcn_backward_kernel<TW>, lds));
     const int rows = resident_rows(msg_gcn_backward_kernel<TW>, MB, lds, g.G, rows_max);
-    hipLaunchKernelGGL(msg_gcn_backward_kernel<TW>, dim3(rows), dim3(MB), lds, st, g, cat, dcat, prm, gpart);
+    RULGNN_TRY(launch_checked(msg_gcn_backward_kernel<TW>, dim3(rows), dim3(MB), lds, st, g, cat, dcat, prm, gpart));
     *rows_out = rows;
     return RULGNN_OK;
 }
 
 template <int HG>
-static void launch_gru(const MsgGeom& g, const MsgWs& w, const Workspace& ws, const float* prm, bool backward, hipStream_t st) {
+static int launch_gru(const MsgGeom& g, const MsgWs& w, const Workspace& ws, const float* prm, bool backward, hipStream_t st) {
     const int grid = w.rows_gru;
     if (!backward)
-        hipLaunchKernelGGL(msg_gru_forward_kernel<HG>, dim3(grid), dim3(MB), 0, st, g, ws.at<float>(w.gi), prm,
-                           ws.at<float>(w.hseq));
-    else
-        hipLaunchKernelGGL(msg_gru_backward_kernel<HG>, dim3(grid), dim3(MB), 0, st, g, ws.at<float>(w.gi),
-                           ws.at<float>(w.hseq), prm, ws.at<float>(w.dpred), ws.at<float>(w.dgi),
-                           ws.at<float>(w.gpart_gru));
+        return launch_checked(msg_gru_forward_kernel<HG>, dim3(grid), dim3(MB), 0, st, g, ws.at<float>(w.gi), prm,
+                              ws.at<float>(w.hseq));
+    return launch_checked(msg_gru_backward_kernel<HG>, dim3(grid), dim3(MB), 0, st, g, ws.at<float>(w.gi),
+                          ws.at<float>(w.hseq), prm, ws.at<float>(w.dpred), ws.at<float>(w.dgi),
+                          ws.at<float>(w.gpart_gru));
 }
 
-static void dispatch_gru(const MsgGeom& g, const MsgWs& w, const Workspace& ws, const float* prm, bool backward, hipStream_t st) {
-    if (w.HG == 4) launch_gru<4>(g, w, ws, prm, backward, st);
-    else if (w.HG == 8) launch_gru<8>(g, w, ws, prm, backward, st);
-    else launch_gru<16>(g, w, ws, prm, backward, st);
+static int dispatch_gru(const MsgGeom& g, const MsgWs& w, const Workspace& ws, const float* prm, bool backward, hipStream_t st) {
+    if (w.HG == 4) return launch_gru<4>(g, w, ws, prm, backward, st);
+    if (w.HG == 8) return launch_gru<8>(g, w, ws, prm, backward, st);
+    return launch_gru<16>(g, w, ws, prm, backward, st);
 }
 
 }  // namespace
@@ -1664,7 +1661,6 @@ int stmsgcn_features(const rulgnn_stmsgcn_shape* s, const float* x, const float*
     MsgGeom g;
     RULGNN_TRY(msg_geometry(s, &g));
     if (g.B == 0) return RULGNN_OK;
-    (void)hipGetLastError();
     return launch_features(g, x, prm, features, nullptr, st);
 }
 
@@ -1676,21 +1672,20 @@ int Stmsgcn::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
     msg_ws_layout(g, &w);
     if (a->workspace_bytes < w.total) return RULGNN_EWORKSPACE;
     const Workspace ws(a->workspace);
-    (void)hipGetLastError();
     const float inv_gb = 1.0f / (float)(a->global_batch > 0 ? a->global_batch : g.B);
     if (mode & 1) {
         RULGNN_TRY(launch_features(g, a->x, a->params, ws.at<float>(w.cat), ws.at<float>(w.gi), st));
-        dispatch_gru(g, w, ws, a->params, false, st);
+        RULGNN_TRY(dispatch_gru(g, w, ws, a->params, false, st));
         {
             // enough workgroups to fill the chip: a sample's (patch, unit) pairs in up to HEAD_MAX_PARTS slices
             int parts = 1;
             while (parts < HEAD_MAX_PARTS && g.B * parts < 1024 && g.NP * g.H / (2 * parts) >= MB) parts *= 2;
-            hipLaunchKernelGGL(msg_head_kernel, dim3((unsigned)(g.B * parts)), dim3(MB), 0, st, g, ws.at<float>(w.hseq), a->params,
-                               a->y, a->pred, ws.at<float>(w.pooled), ws.at<float>(w.dpred), ws.at<float>(w.sqerr), inv_gb, parts,
-                               ws.at<float>(w.hpart));
+            RULGNN_TRY(launch_checked(msg_head_kernel, dim3((unsigned)(g.B * parts)), dim3(MB), 0, st, g, ws.at<float>(w.hseq), a->params,
+                                      a->y, a->pred, ws.at<float>(w.pooled), ws.at<float>(w.dpred), ws.at<float>(w.sqerr), inv_gb, parts,
+                                      ws.at<float>(w.hpart)));
             if (parts > 1)
-                hipLaunchKernelGGL(msg_head_finish_kernel, dim3((unsigned)((g.B + 255) / 256)), dim3(256), 0, st, g, a->params,
-                                   ws.at<float>(w.hpart), parts, a->y, a->pred, ws.at<float>(w.dpred), ws.at<float>(w.sqerr), inv_gb);
+                RULGNN_TRY(launch_checked(msg_head_finish_kernel, dim3((unsigned)((g.B + 255) / 256)), dim3(256), 0, st, g, a->params,
+                                          ws.at<float>(w.hpart), parts, a->y, a->pred, ws.at<float>(w.dpred), ws.at<float>(w.sqerr), inv_gb));
         }
     }
     if (mode & 2) {
@@ -1698,7 +1693,7 @@ int Stmsgcn::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
             if (hipMemcpyAsync(ws.at<float>(w.dpred), a->dpred, sizeof(float) * g.B, hipMemcpyDeviceToDevice, st) != hipSuccess)
                 return RULGNN_EHIP;
         }
-        dispatch_gru(g, w, ws, a->params, true, st);
+        RULGNN_TRY(dispatch_gru(g, w, ws, a->params, true, st));
         // GRU input projection backward over all (graph, node) rows: d cat = d gi W_ih, d W_ih = d gi^T cat, d b_ih = column sums of d gi
         int rows_gi = 0;
         {
@@ -1708,8 +1703,8 @@ int Stmsgcn::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
                 int64_t parts = (R + 4 * GI_ROWS - 1) / (4 * GI_ROWS);
                 if (parts > GI_MAX_PARTS) parts = GI_MAX_PARTS;
                 rows_gi = (int)parts;
-                hipLaunchKernelGGL(msg_gi_backward_kernel<24>, dim3((unsigned)parts), dim3(GIB), 0, st, g.C, dgi, ws.at<float>(w.cat),
-                                   a->params + g.off_wih, ws.at<float>(w.dcat), ws.at<float>(w.gpart_gi), R);
+                RULGNN_TRY(launch_checked(msg_gi_backward_kernel<24>, dim3((unsigned)parts), dim3(GIB), 0, st, g.C, dgi, ws.at<float>(w.cat),
+                                          a->params + g.off_wih, ws.at<float>(w.dcat), ws.at<float>(w.gpart_gi), R));
             } else {
                 const float* wih = a->params + g.off_wih;
                 float* one = ws.at<float>(w.one);
@@ -1727,13 +1722,10 @@ int Stmsgcn::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
             auto launch_mx = [&](auto kern) -> int {
                 RULGNN_TRY(allow_dynamic_lds(kern, lds_mx));
                 rows = resident_rows(kern, 64 * MXW, lds_mx, (g.G + MXW - 1) / MXW, w.rows_gcn_max);
-                hipLaunchKernelGGL(kern, dim3((unsigned)rows), dim3(64 * MXW), lds_mx, st, g, ws.at<float>(w.cat),
-                                   ws.at<float>(w.dcat), a->params, ws.at<float>(w.gpart_gcn));
-                return RULGNN_OK;
+                return launch_checked(kern, dim3((unsigned)rows), dim3(64 * MXW), lds_mx, st, g, ws.at<float>(w.cat),
+                                      ws.at<float>(w.dcat), a->params, ws.at<float>(w.gpart_gcn));
             };
-            const int rl = MsgXJ::matches(g) ? launch_mx(&msg_gcn_backward_mx_kernel<true>) : launch_mx(&msg_gcn_backward_mx_kernel<false>);
-            if (rl != RULGNN_OK) return rl;
-            rcb = hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+            rcb = MsgXJ::matches(g) ? launch_mx(&msg_gcn_backward_mx_kernel<true>) : launch_mx(&msg_gcn_backward_mx_kernel<false>);
         } else
         rcb = g.n >= 12 ? launch_gcn_backward<4>(g, w.rows_gcn_max, ws.at<float>(w.cat), ws.at<float>(w.dcat), a->params,
                                                            ws.at<float>(w.gpart_gcn), st, &rows)
@@ -1741,13 +1733,13 @@ int Stmsgcn::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
                                                            ws.at<float>(w.gpart_gcn), st, &rows);
         if (rcb != RULGNN_OK) return rcb;
         const bool mse = a->dpred == nullptr;
-        hipLaunchKernelGGL(msg_finalize_kernel, dim3((g.nparam + 3) / 4), dim3(MB), 0, st, g,
-                           ws.at<float>(w.gpart_gcn), rows, ws.at<float>(w.gpart_gru), w.rows_gru,
-                           ws.at<float>(w.gpart_gi), rows_gi, ws.at<float>(w.dpred), ws.at<float>(w.pooled), a->grads);
+        RULGNN_TRY(launch_checked(msg_finalize_kernel, dim3((g.nparam + 3) / 4), dim3(MB), 0, st, g,
+                                  ws.at<float>(w.gpart_gcn), rows, ws.at<float>(w.gpart_gru), w.rows_gru,
+                                  ws.at<float>(w.gpart_gi), rows_gi, ws.at<float>(w.dpred), ws.at<float>(w.pooled), a->grads));
         if (mse && a->loss)
-            (void)block_sum(ws.at<float>(w.sqerr), (int64_t)g.B, a->loss, st);
+            RULGNN_TRY(block_sum(ws.at<float>(w.sqerr), (int64_t)g.B, a->loss, st));
     }
-    return hipGetLastError() == hipSuccess ? RULGNN_OK : RULGNN_EHIP;
+    return RULGNN_OK;
 }
 
 }  // namespace rulgnn

@@ -199,7 +199,6 @@ int Stnet::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
     const float* yo = ws + g.w_out[nc - 1];       // Y_o as [BT, D] rows
     const float* henc = ws + g.ae.w_enc[3];       // the encoder's output: the LSTM's input
     const unsigned ggrid = (unsigned)(g.G < 4096 ? g.G : 4096);
-    (void)hipGetLastError();
     // The filters as GEMM operands: the flat parameter buffer puts them behind three scalars, 12 bytes off a 16-byte boundary
     // (seq_backend.hpp: aligned_operand; 1 MB at the reference's widths, ~3 us a copy).
     const float* fop[SN_MAX_CHEB];
@@ -212,12 +211,10 @@ int Stnet::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
         const size_t lds = sizeof(float) * (stft_lds_floats(g.P, g.nseg) + (size_t)g.N * g.f);
         if (lds > 48 * 1024) return RULGNN_EUNSUPPORTED;
         RULGNN_TRY(fill_f32(one + 3, 1, 0.0f, st));
-        hipLaunchKernelGGL(sn_stft_kernel, dim3(ggrid), dim3(SB), lds, st, g, a->x, prm, ws);
-        RULGNN_LAUNCH_OK();
+        RULGNN_TRY(launch_checked(sn_stft_kernel, dim3(ggrid), dim3(SB), lds, st, g, a->x, prm, ws));
         const float* cur = ws + g.w_mag;
         for (int i = 0; i < nc; ++i) {
-            hipLaunchKernelGGL(sn_terms_kernel, dim3(ggrid), dim3(SB), 0, st, g, g.C[i], cur, mask, ws + g.w_terms[i]);
-            RULGNN_LAUNCH_OK();
+            RULGNN_TRY(launch_checked(sn_terms_kernel, dim3(ggrid), dim3(SB), 0, st, g, g.C[i], cur, mask, ws + g.w_terms[i]));
             RULGNN_TRY(sgemm(ws + g.w_terms[i], 3 * g.C[i], 1, fop[i], 1, g.C[i + 1], ws + g.w_out[i], g.C[i + 1], R, g.C[i + 1], 3 * g.C[i],
                         false, st));
             cur = ws + g.w_out[i];
@@ -247,8 +244,7 @@ int Stnet::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
             if (i == 0) break;                        // the input carries no gradient
             RULGNN_TRY(sgemm(dcur, Co, 1, fop[i], Co, 1, ws + g.w_dterms, 3 * Ci, R, 3 * Ci, Co, false, st));
             float* dn = dc[i & 1];
-            hipLaunchKernelGGL(sn_terms_bwd_kernel, dim3(ggrid), dim3(SB), 0, st, g, Ci, (const float*)(ws + g.w_dterms), mask, dn);
-            RULGNN_LAUNCH_OK();
+            RULGNN_TRY(launch_checked(sn_terms_bwd_kernel, dim3(ggrid), dim3(SB), 0, st, g, Ci, (const float*)(ws + g.w_dterms), mask, dn));
             dcur = dn;
         }
     }
