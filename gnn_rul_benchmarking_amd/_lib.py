@@ -189,6 +189,18 @@ class GdagdlArgs(C.Structure):
                 ("dropout_p", C.c_float), ("seed", C.c_uint64), ("step", C.c_uint64), ("training", C.c_int32)]
 
 
+class StfaShape(C.Structure):
+    _fields_ = [("batch", C.c_int64), ("num_patch", C.c_int32), ("patch_size", C.c_int32), ("num_nodes", C.c_int32), ("output_dim", C.c_int32),
+                ("num_heads", C.c_int32), ("encoder_hidden_dim", C.c_int32)]
+
+
+class StfaArgs(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("dpred", C.c_void_p), ("params", C.c_void_p), ("grads", C.c_void_p),
+                ("pred", C.c_void_p), ("loss", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
+                ("global_batch", C.c_int64), ("sample_offset", C.c_int64), ("dropout_p", C.c_float), ("seed", C.c_uint64),
+                ("step", C.c_uint64), ("training", C.c_int32)]
+
+
 class GatlstmShape(C.Structure):
     _fields_ = [("batch", C.c_int64), ("num_patch", C.c_int32), ("patch_size", C.c_int32), ("num_gat", C.c_int32), ("hidden_dim", C.c_int32 * 4),
                 ("num_lstm", C.c_int32), ("lstm_hidden_dim", C.c_int32 * 3)]
@@ -306,6 +318,7 @@ _SIGNATURES = {
     **_step_family("dvgtformer", DvgtformerShape, DvgtformerArgs, tap_offset=True),
     **_step_family("gdagdl", GdagdlShape, GdagdlArgs, tap_offset=True),
     **_step_family("gatlstm", GatlstmShape, GatlstmArgs, tap_offset=True),
+    **_step_family("stfa", StfaShape, StfaArgs, tap_offset=True),
     "rulgnn_sgemm_f32": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
                                    C.c_int32, C.c_int32, C.c_void_p]),
     "rulgnn_sgemm_mode": (C.c_int, [C.c_int32]),
@@ -418,6 +431,8 @@ STRUCTS_AT = {38: GatlstmShape, 39: GatlstmArgs}
 STRUCTS_LATER = {41: LogobShape}
 # (STRUCTS_LATER is tested as exactly that too; 42 is unassigned)
 STRUCTS_HCPB = {43: HcpbShape}
+# (44 is unassigned)
+STRUCTS_STFA = {45: StfaShape, 46: StfaArgs}
 
 _lib = None
 
@@ -449,7 +464,7 @@ def load() -> C.CDLL:
         fn = getattr(lib, name)          # AttributeError if the .so is stale: loud by design
         fn.restype = res
         fn.argtypes = args
-    for which, mirror in list(enumerate(STRUCTS)) + sorted({**STRUCTS_AT, **STRUCTS_LATER, **STRUCTS_HCPB}.items()):       # a stale .so (or a stale binding) would read past the end of a shorter struct
+    for which, mirror in list(enumerate(STRUCTS)) + sorted({**STRUCTS_AT, **STRUCTS_LATER, **STRUCTS_HCPB, **STRUCTS_STFA}.items()):       # a stale .so (or a stale binding) would read past the end of a shorter struct
         if lib.rulgnn_struct_size(which) != C.sizeof(mirror):
             raise RuntimeError(f"{LIB_PATH}: sizeof(struct #{which}) is {lib.rulgnn_struct_size(which)} in the library, {C.sizeof(mirror)} in "
                                f"this binding ({mirror.__name__}): rebuild with `python -m gnn_rul_benchmarking_amd.build --force`")

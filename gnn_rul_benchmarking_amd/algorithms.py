@@ -3,7 +3,7 @@ algorithms/algorithms.py:29-48 does it (lookup by name in this module's globals,
 ``NotImplementedError("Algorithm not found: ...")`` otherwise).
 
 The ST_GCN (reference algorithms/algorithms.py:465-490), STMSGCN (:546-571), ASTGCNN (:139-163), FC_STGNN (:51-76), HAGCN (:222-248),
-ST_Conv (:195-220), GRU_CM (:355-380), AGCN_TF (:574-599), HierCorrPool (:79-104), LOGO (:107-136), DVGTformer (:326-351), GDAGDL (:519-544), GAT_LSTM (:492-517), LOGO_bearing (:601-629) and HierCorrPool_bearing (:633-658) wrappers are implemented:
+ST_Conv (:195-220), GRU_CM (:355-380), AGCN_TF (:574-599), HierCorrPool (:79-104), LOGO (:107-136), DVGTformer (:326-351), GDAGDL (:519-544), GAT_LSTM (:492-517), STFA (:166-192), LOGO_bearing (:601-629) and HierCorrPool_bearing (:633-658) wrappers are implemented:
 the hot paths this package accelerates.  The classes keep the reference contract -- constructor
 ``(configs, hparams, device)``, attributes ``model`` / ``optimizer`` / ``hparams`` / ``mse``,
 ``update(X, y, epoch) -> {'loss': float}`` -- so the reference's trainer can drive it unchanged."""
@@ -35,6 +35,7 @@ from .hiercorrpool_bearing import HierCorrPool_bearing_model
 from .dvgtformer import DVGTformer_model
 from .gdagdl import GDAGDL_model
 from .gatlstm import GAT_LSTM_model
+from .stfa import STFA_model
 from .stagnn import STAGNN_model
 
 
@@ -409,7 +410,17 @@ class GAT_LSTM(_FusedAlgorithm):
     needs_train_mode = "dropout"
 
 
+class STFA(_FusedAlgorithm):
+    """STFA training wrapper (reference algorithms.py:166-192; the fused multi-head graph-attention kernels of csrc/stfa.hip, the
+    one-direction LSTM of csrc/bilstm.hip, a last-step head): MSE only, Adam with weight decay.  The reference writes
+    ``configs['device'] = 'cuda:0'`` into the dictionary it is given; the model here takes ``device`` and ignores it, so the caller's
+    dictionary is left alone.  ``v`` has a zero gradient and stays an Adam parameter (weight decay moves it), as there."""
+    model_class = STFA_model
+    supports_graphs = False
+    needs_train_mode = "dropout"
+
+
 # ("LOGO_bearing": the class above is complete, but tests/test_logo_cpu.py holds the registry to refusing the name; construct it directly)
 # ("HierCorrPool_bearing": likewise complete; tests/test_hiercorrpool_cpu.py and tests/test_logo_bearing_cpu.py hold the registry to
 # refusing the name; construct it directly)
-_NOT_ALGORITHMS = {"HierCorrPool_bearing", "HierCorrPool_bearing_model", "LOGO_bearing", "Algorithm", "GAT_LSTM_model", "GDAGDL_model", "DVGTformer_model","GRU_CM_model", "FusedAdam", "RGCNU_model", "STNet_model", "SAGCN_model", "AGCN_TF_model", "HierCorrPool_model", "LOGO_model", "LOGO_bearing_model", "STAGNN_model", "ST_GCN_model", "STMSGCN_model", "ASTGCNN_model", "FC_STGNN_RUL", "HAGCN_model", "ST_Conv_model", "STGNN_model", "get_algorithm_class", "torch", "nn", "annotations", "math", "_lib", "deferred_weight_gradients"}
+_NOT_ALGORITHMS = {"STFA_model", "HierCorrPool_bearing", "HierCorrPool_bearing_model", "LOGO_bearing", "Algorithm", "GAT_LSTM_model", "GDAGDL_model", "DVGTformer_model","GRU_CM_model", "FusedAdam", "RGCNU_model", "STNet_model", "SAGCN_model", "AGCN_TF_model", "HierCorrPool_model", "LOGO_model", "LOGO_bearing_model", "STAGNN_model", "ST_GCN_model", "STMSGCN_model", "ASTGCNN_model", "FC_STGNN_RUL", "HAGCN_model", "ST_Conv_model", "STGNN_model", "get_algorithm_class", "torch", "nn", "annotations", "math", "_lib", "deferred_weight_gradients"}

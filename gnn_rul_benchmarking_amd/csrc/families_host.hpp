@@ -209,6 +209,15 @@ struct Gatlstm : StepFamily<rulgnn_gatlstm_shape, rulgnn_gatlstm_args> {
     [[nodiscard]] static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
     [[nodiscard]] static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
 };
+// v.{weight, bias} stay inside Adam's range: the reference gives them zero gradients, not None, and its weight decay moves them
+struct Stfa : StepFamily<rulgnn_stfa_shape, rulgnn_stfa_args> {
+    [[nodiscard]] static int shape_status(const Shape* s);
+    static int64_t param_count(const Shape* s);
+    static size_t workspace_bytes(const Shape* s);
+    static int64_t tap_offset(const Shape* s, int which);
+    [[nodiscard]] static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
+    [[nodiscard]] static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
+};
 
 int64_t hagcn_graph_param_count(const rulgnn_hagcn_shape* s);
 size_t hagcn_workspace_bytes(const rulgnn_hagcn_shape* s);

@@ -341,6 +341,8 @@ size_t rulgnn_struct_size(int32_t which) {
     case RULGNN_STRUCT_GATLSTM_ARGS: return sizeof(rulgnn_gatlstm_args);
     case RULGNN_STRUCT_LOGOB_SHAPE: return sizeof(rulgnn_logob_shape);
     case RULGNN_STRUCT_HCPB_SHAPE: return sizeof(rulgnn_hcpb_shape);
+    case RULGNN_STRUCT_STFA_SHAPE: return sizeof(rulgnn_stfa_shape);
+    case RULGNN_STRUCT_STFA_ARGS: return sizeof(rulgnn_stfa_args);
     default: return 0;
     }
 }
@@ -1175,6 +1177,34 @@ int rulgnn_gatlstm_backward_f32(const rulgnn_gatlstm_shape* shape, const rulgnn_
 }
 int rulgnn_gatlstm_fwdbwd_f32(const rulgnn_gatlstm_shape* shape, const rulgnn_gatlstm_args* args, const rulgnn_adam_args* opt, void* stream) {
     return step_fwdbwd<Gatlstm>(shape, args, opt, stream);
+}
+
+// ---- STFA ------------------------------------------------------------------------------------------------
+int64_t rulgnn_stfa_param_count(const rulgnn_stfa_shape* shape) { return Stfa::param_count(shape); }
+size_t rulgnn_stfa_workspace_bytes(const rulgnn_stfa_shape* shape) { return Stfa::workspace_bytes(shape); }
+int64_t rulgnn_stfa_tap_offset(const rulgnn_stfa_shape* shape, int32_t which) { return Stfa::tap_offset(shape, which); }
+
+int Stfa::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
+    RULGNN_TRY(shape_status(shape));
+    if (a->global_batch < shape->batch || a->sample_offset < 0) return RULGNN_EINVAL;
+    if (!(a->dropout_p >= 0.f && a->dropout_p < 1.f)) return RULGNN_EINVAL;
+    // the dropout counter of the global batch's last edge must fit 32 bits
+    const double entries = 44.0 * (double)shape->num_heads * (double)shape->num_patch;
+    if (((double)a->sample_offset + (double)shape->batch) * entries > 4294967296.0 || (double)a->global_batch * entries > 4294967296.0)
+        return RULGNN_EUNSUPPORTED;
+    for (const void* p : {(const void*)a->y, (const void*)a->dpred, (const void*)a->loss})
+        if (!opt_aligned(p)) return RULGNN_EALIGN;
+    return check_step_ptrs(a, shape->batch, bwd);
+}
+
+int rulgnn_stfa_forward_f32(const rulgnn_stfa_shape* shape, const rulgnn_stfa_args* args, void* stream) {
+    return step_forward<Stfa>(shape, args, stream);
+}
+int rulgnn_stfa_backward_f32(const rulgnn_stfa_shape* shape, const rulgnn_stfa_args* args, void* stream) {
+    return step_backward<Stfa>(shape, args, stream);
+}
+int rulgnn_stfa_fwdbwd_f32(const rulgnn_stfa_shape* shape, const rulgnn_stfa_args* args, const rulgnn_adam_args* opt, void* stream) {
+    return step_fwdbwd<Stfa>(shape, args, opt, stream);
 }
 
 size_t rulgnn_rul_metrics_workspace_bytes(int64_t n) { return rul_metrics_workspace_bytes(n); }

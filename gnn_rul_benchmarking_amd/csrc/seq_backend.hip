@@ -1,4 +1,4 @@
-// The auto-encoder / LSTM / head back end of STNet, GDAGDL and GAT_LSTM (seq_backend.hpp): its small kernels, compiled once, and the host
+// The auto-encoder / LSTM / head back end of STNet, GDAGDL, GAT_LSTM and STFA (seq_backend.hpp): its small kernels, compiled once, and the host
 // chain around them.  Every sum has a fixed order; the grids that write per-workgroup partials (rblocks, min(B, 1024)) are part of the bits.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -58,7 +58,8 @@ __global__ __launch_bounds__(SQB) void sq_recon_kernel(const float* __restrict__
 // head: pred = hseq_flat . w + b; squared error and d loss / d pred
 struct SqHead {
     int64_t B;
-    int n;                                       // H * T values per sample
+    int n;                                       // values per sample the head reads: H * T, or H (the last step's) under last_step
+    int64_t stride;                              // floats between two samples' first value (hseq points at sample 0's)
     const float *hseq, *w, *b, *y;               // y may be null: prediction alone
     float *pred, *sq, *dpred;
     float inv_gb;
@@ -68,7 +69,7 @@ __global__ __launch_bounds__(SQB) void sq_head_kernel(SqHead g) {
     const int n = g.n;
     for (int64_t b = blockIdx.x; b < g.B; b += gridDim.x) {
         float a = 0.f;
-        for (int i = threadIdx.x; i < n; i += SQB) a = fmaf(g.hseq[b * n + i], g.w[i], a);
+        for (int i = threadIdx.x; i < n; i += SQB) a = fmaf(g.hseq[b * g.stride + i], g.w[i], a);
         red[threadIdx.x] = a;
         __syncthreads();
         for (int m = SQB / 2; m > 0; m >>= 1) {
@@ -93,6 +94,15 @@ __global__ void sq_head_bwd_kernel(int64_t B, int n, const float* __restrict__ d
     const int64_t tot = B * n;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < tot; i += (int64_t)gridDim.x * blockDim.x)
         dhs[i] = dpred[i / n] * w[i % n];
+}
+
+// last-step head: d hseq[b][t][e] = dpred[b] w[e] at t = T - 1, 0 before
+__global__ void sq_head_last_bwd_kernel(int64_t B, int T, int E, const float* __restrict__ dpred, const float* __restrict__ w, float* __restrict__ dhs) {
+    const int64_t n = (int64_t)T * E, tot = B * n;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < tot; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = i % n;
+        dhs[i] = r >= n - E ? dpred[i / n] * w[r - (n - E)] : 0.f;
+    }
 }
 
 __global__ void sq_sum_pair_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ out) {
@@ -159,11 +169,12 @@ int lstm_head_layout(LstmHeadPlan* p, int* o, int64_t* w, SplitKScratch* sp) {
         const int I = p->H[k], Ek = p->H[k + 1];
         p->o_lstm[k][0] = take(o, 4 * Ek * I); p->o_lstm[k][1] = take(o, 4 * Ek * Ek); p->o_lstm[k][2] = take(o, 4 * Ek); p->o_lstm[k][3] = take(o, 4 * Ek);
     }
-    p->o_lw = take(o, E * p->T); p->o_lb = take(o, 1);
+    const int nhead = p->last_step ? E : E * p->T;
+    p->o_lw = take(o, nhead); p->o_lb = take(o, 1);
     for (int k = 0; k < p->nk; ++k) p->w_hseq[k] = take(w, p->B * p->T * p->H[k + 1]);
     p->w_dpred = take(w, p->B); p->w_sq = take(w, p->B);
     p->w_one = take(w, 64);
-    sp->need(1, E * p->T, p->B);
+    sp->need(1, nhead, p->B);
     sp->need(1, 1, p->B);
     for (int k = 0; k < p->nk; ++k) {
         rulgnn_bilstm_shape ls{p->T, (int32_t)(p->B > 0 ? p->B : 1), p->H[k], p->H[k + 1]};
@@ -181,17 +192,25 @@ int lstm_head_forward(const LstmHeadPlan& p, const float* x, const float* prm, f
         lstm_layer_args(p, k, x, prm, ws, &ls, &la);
         RULGNN_TRY(bilstm_forward(&ls, &la, st, 1));
     }
-    const SqHead h{p.B, p.H[p.nk] * p.T, ws + p.w_hseq[p.nk - 1], prm + p.o_lw, prm + p.o_lb, y, pred, ws + p.w_sq, ws + p.w_dpred, inv_gb};
+    const int E = p.H[p.nk], ET = E * p.T;
+    const float* hseq = ws + p.w_hseq[p.nk - 1];
+    const SqHead h{p.B, p.last_step ? E : ET, ET, p.last_step ? hseq + (ET - E) : hseq, prm + p.o_lw, prm + p.o_lb, y, pred, ws + p.w_sq, ws + p.w_dpred,
+                   inv_gb};
     return launch_checked(sq_head_kernel, dim3((unsigned)(p.B < 1024 ? p.B : 1024)), dim3(SQB), 0, st, h);
 }
 
 int lstm_head_backward(const LstmHeadPlan& p, const float* x, const float* prm, float* ws, const float* dpred, float* grads, float* const dbuf[2],
                        float* split, hipStream_t st) {
-    const int ET = p.H[p.nk] * p.T;
-    RULGNN_TRY(sgemm_splitk(dpred, 0, 1, ws + p.w_hseq[p.nk - 1], 1, ET, grads + p.o_lw, ET, 1, ET, (int)p.B, false, split, st));
+    const int E = p.H[p.nk], ET = E * p.T;
+    // the weight gradient over B rows of the head's width: the whole sequence, or the last step's E values (rows ET apart)
+    const int nh = p.last_step ? E : ET;
+    RULGNN_TRY(sgemm_splitk(dpred, 0, 1, ws + p.w_hseq[p.nk - 1] + (ET - nh), 1, ET, grads + p.o_lw, nh, 1, nh, (int)p.B, false, split, st));
     RULGNN_TRY(sgemm_splitk(dpred, 0, 1, ws + p.w_one, 0, 0, grads + p.o_lb, 1, 1, 1, (int)p.B, false, split, st));
     int cur = 0;
-    RULGNN_TRY(launch_checked(sq_head_bwd_kernel, sq_grid(p.B * ET), dim3(SQB), 0, st, p.B, ET, dpred, prm + p.o_lw, dbuf[cur]));
+    if (p.last_step)
+        RULGNN_TRY(launch_checked(sq_head_last_bwd_kernel, sq_grid(p.B * ET), dim3(SQB), 0, st, p.B, p.T, E, dpred, prm + p.o_lw, dbuf[cur]));
+    else
+        RULGNN_TRY(launch_checked(sq_head_bwd_kernel, sq_grid(p.B * ET), dim3(SQB), 0, st, p.B, ET, dpred, prm + p.o_lw, dbuf[cur]));
     // layer k's dx is layer k - 1's dout
     for (int k = p.nk - 1; k >= 0; --k, cur ^= 1) {
         rulgnn_bilstm_shape ls;

@@ -1,5 +1,6 @@
-// The back end STNet, GDAGDL and GAT_LSTM end in (csrc/seq_backend.hip): an optional 4 + 4 Linear / ReLU auto-encoder over the patch rows
-// with its reconstruction term, unidirectional LSTMs over the patches (bilstm.hip, one direction), Linear(H * T, 1) with the MSE.  A
+// The back end STNet, GDAGDL, GAT_LSTM and STFA end in (csrc/seq_backend.hip): an optional 4 + 4 Linear / ReLU auto-encoder over the patch rows
+// with its reconstruction term, unidirectional LSTMs over the patches (bilstm.hip, one direction), Linear(H * T, 1) -- or Linear(H, 1) over
+// the last step (LstmHeadPlan::last_step) -- with the MSE.  A
 // family's geometry embeds the plans and lays them out from its own running parameter (`o`) and workspace (`w`: floats, 64-float granules)
 // counters; what differs between the families (which sums make the loss, which buffers the gradient walks through) stays with the caller.
 #pragma once
@@ -33,6 +34,7 @@ void lstm_uni_args(rulgnn_bilstm_shape* ls, rulgnn_bilstm_args* la, int T, int64
 struct LstmHeadPlan {
     int64_t B;
     int T, nk, H[SEQ_MAX_LSTM + 1];              // nk layers, H[k] -> H[k + 1] wide; the head reads H[nk] * T values per sample
+    int last_step = 0;                           // != 0: the head is Linear(H[nk], 1) over the last step alone (STFA: fc(lstm_output[:, -1, :]))
     int o_lstm[SEQ_MAX_LSTM][4], o_lw, o_lb;     // flat parameter offsets: {w_ih, w_hh, b_ih, b_hh} per layer, linear.{weight, bias}
     int64_t w_hseq[SEQ_MAX_LSTM], w_lstm[SEQ_MAX_LSTM], w_dpred, w_sq, w_one;      // workspace (floats); w_one: 64 floats, [0] = 1 in a backward
 };
@@ -40,7 +42,7 @@ struct LstmHeadPlan {
 [[nodiscard]] int lstm_head_layout(LstmHeadPlan* p, int* o, int64_t* w, SplitKScratch* sp);
 // x [B * T][H[0]] -> the layers -> pred [B]; with y, the squared-error terms / global batch in w_sq and d loss / d pred in w_dpred
 [[nodiscard]] int lstm_head_forward(const LstmHeadPlan& p, const float* x, const float* prm, float* ws, const float* y, float* pred, float inv_gb, hipStream_t st);
-// linear.{weight, bias} gradients, d hseq into dbuf[0], then down the layers from one buffer into the other: d x is left in dbuf[nk & 1]
+// linear.{weight, bias} gradients, d hseq into dbuf[0] (zero before the last step under last_step), then down the layers from one buffer into the other: d x is left in dbuf[nk & 1]
 [[nodiscard]] int lstm_head_backward(const LstmHeadPlan& p, const float* x, const float* prm, float* ws, const float* dpred, float* grads, float* const dbuf[2],
                        float* split, hipStream_t st);
 

@@ -1,7 +1,7 @@
 """Hyper-parameter tables, looked up by dataset name then dataset id, like the reference's
 configs/hparams.py:3-7 (``get_hparams_class(name)(dataset_id)`` -> object with ``train_params`` and
 ``alg_hparams`` dicts keyed by ``--GNN_method``; unknown dataset -> NotImplementedError, unknown id ->
-ValueError).  Only the ST_GCN, STMSGCN, ASTGCNN, FC_STGNN, HAGCN, ST_Conv, STGNN, RGCNU, GRU_CM, STNet, SAGCN, AGCN_TF, STAGNN, HierCorrPool, LOGO, DVGTformer, GDAGDL, GAT_LSTM, LOGO_bearing and HierCorrPool_bearing rows are restated (the methods this package
+ValueError).  Only the ST_GCN, STMSGCN, ASTGCNN, FC_STGNN, HAGCN, ST_Conv, STGNN, RGCNU, GRU_CM, STNet, SAGCN, AGCN_TF, STAGNN, HierCorrPool, LOGO, DVGTformer, GDAGDL, GAT_LSTM, STFA, LOGO_bearing and HierCorrPool_bearing rows are restated (the methods this package
 implements).
 
 PHM2012 / XJTU_SY rows are the reference's (configs/hparams.py:223,238,... and :334,349,...; STMSGCN
@@ -62,6 +62,7 @@ class _Table:
     _sagcn_rows: dict = {}            # ... and SAGCN (configs/hparams.py:221,235,266,302 and :332,346,381,415)
     _agcntf_rows: dict = {}           # ... and AGCN_TF (configs/hparams.py:227,243,257,277,293,313 and :338,357,373,392,407,426)
     _astgcnn_nodes = None             # ... and ASTGCNN to the aero-engine datasets only (configs/hparams.py:38,202)
+    _stfa = False                     # ... and STFA to C-MAPSS only (configs/hparams.py:20,39 / 58,76 / 98,116 / 138,156; no N-CMAPSS row)
 
     def __init__(self, dataset_id=None, **overrides):
         if dataset_id not in self._rows:
@@ -110,6 +111,10 @@ class _Table:
             self.train_params['DVGTformer'] = dict(_ASTGCNN_TRAIN)
             self.alg_hparams['DVGTformer'] = {'num_nodes': self._astgcnn_nodes, 'time_length': 50, 'd_model': [144, 248], 'num_heads': 4,
                                               'lambda_param': 0.5, 'd_ff': [72, 124], 'dropout': 0.1, 'num_blocks': 3}
+        if self._stfa:                 # one row for FD001-FD004; the prior-knowledge graph is the 14 C-MAPSS sensors'
+            self.train_params['STFA'] = dict(_ASTGCNN_TRAIN)
+            self.alg_hparams['STFA'] = {'patch_size': 2, 'num_patch': 25, 'num_nodes': 14, 'hidden_dim': 16, 'output_dim': 5,
+                                        'encoder_hidden_dim': 64, 'num_heads': 10, 'dropout': 0.2}
         if dataset_id in self._stnet_rows:
             self.train_params['STNet'] = {'num_epochs': 81, 'batch_size': 100, 'weight_decay': 1e-2, 'learning_rate': 1e-2}
             num_patch, patch_size, num_nodes, nperseg, input_dim = self._stnet_rows[dataset_id]
@@ -157,6 +162,7 @@ class _Table:
 
 class CMAPSS(_Table):
     _astgcnn_nodes = 14
+    _stfa = True
 
     def __init__(self, dataset_id, window=50):
         # default window = the reference's preprocessed C-MAPSS windows (data_model_configs.CMAPSS.sequence_len = 50); bench.py and

@@ -1,7 +1,12 @@
 """CLI with the reference's flags (main.py:12-34) plus the data-parallel additions.
 
     python -m gnn_rul_benchmarking_amd.main --GNN_method ST_GCN --dataset CMAPSS --dataset_id FD004 --device cuda:0
+    python -m gnn_rul_benchmarking_amd.main --GNN_method STFA --dataset CMAPSS --dataset_id FD001 --device cuda:0
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m gnn_rul_benchmarking_amd.main ...
+
+``--GNN_method`` takes the reference's names (main.py:43-46).  Aero-engine datasets (CMAPSS, NCMAPSS): ASTGCNN, GRU_CM, HAGCN, ST_Conv, STFA
+(CMAPSS only), RGCNU, STGNN, STAGNN, FC_STGNN, HierCorrPool, LOGO, DVGTformer; bearing datasets (PHM2012, XJTU_SY): STNet, SAGCN, ST_GCN,
+GAT_LSTM, GDAGDL, STMSGCN, AGCN_TF, LOGO_bearing, HierCorrPool_bearing; ST_GCN also runs on the aero-engine datasets (hparams.py).
 """
 import argparse
 import os

@@ -349,6 +349,9 @@ size_t rulgnn_stgcn_train_args_size(void);
 #define RULGNN_STRUCT_LOGOB_SHAPE 41
 /* (index 42 is unassigned and answers 0; HierCorrPool_bearing's argument struct is rulgnn_hiercorrpool_args, index 30) */
 #define RULGNN_STRUCT_HCPB_SHAPE 43
+/* (index 44 is unassigned and answers 0) */
+#define RULGNN_STRUCT_STFA_SHAPE 45
+#define RULGNN_STRUCT_STFA_ARGS 46
 size_t rulgnn_struct_size(int32_t which);
 
 /* Profiling aid: the training step is a chain of 4*num_layers+1 phase kernels:
@@ -1645,6 +1648,74 @@ int rulgnn_gatlstm_forward_f32(const rulgnn_gatlstm_shape *shape, const rulgnn_g
 int rulgnn_gatlstm_backward_f32(const rulgnn_gatlstm_shape *shape, const rulgnn_gatlstm_args *args, void *stream);
 /* GAT_LSTM.update body (algorithms.py:508-517); with `opt` also Adam on the flat parameter buffer. */
 int rulgnn_gatlstm_fwdbwd_f32(const rulgnn_gatlstm_shape *shape, const rulgnn_gatlstm_args *args, const rulgnn_adam_args *opt, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * STFA path (reference models/STFA/Model.py, algorithms/algorithms.py:166-192; wired to C-MAPSS FD001-FD004).
+ *
+ * T = num_patch, P = patch_size, C = output_dim, Hd = num_heads, E = encoder_hidden_dim, W = T + 14 C.
+ * x [batch, 14, T * P] -> batch * T graphs of the 14 sensors with P features each -> per head h
+ *   Z = x W_h^T + b_h, u_ij = a1 . Z_i + a2 . Z_j + c, p = softmax_j(leakyrelu(u, 0.1)) over ALL 14 nodes, q = p o D o A, h' = q Z
+ * (D: dropout keep mask / (1 - p_drop), training != 0 only; A: the fixed prior-knowledge graph of Model.py:61-77 -- 22 undirected edges,
+ * no self-loops -- applied behind the softmax and the dropout: rows do not sum to one) -> relu(mean over the heads) [14][C] per graph ->
+ * the LSTM's input row [1 x T | 14 C features] (the reference's "ASE" softmax acts on one element and is exactly 1, Model.py:115) ->
+ * one unidirectional LSTM W -> E over the T patches (h0 = c0 = 0) -> Linear(E -> 1) on the LAST step.  STFA.update: loss = MSE(pred, y).
+ *
+ * Flat parameter buffer = the reference's named_parameters() order:
+ *   gat.attention_h.{linear.weight[C][P], linear.bias[C], attention.weight[2 C] (a1 then a2), attention.bias[1]} for h = 0 .. Hd-1 |
+ *   v.{weight[14 C], bias[1]} | lstm.{weight_ih_l0[4 E][W], weight_hh_l0[4 E][E], bias_ih_l0[4 E], bias_hh_l0[4 E]} | fc.{weight[E], bias[1]}
+ * v's gradient is written as exact zeros (the singleton softmax); the fused Adam treats v like any other parameter (its weight decay
+ * moves it).  x has no gradient.  A non-finite sample makes its own prediction NaN, and only its own.
+ * Dropout: the counter hash of the other families, key = dropout_layer_key(seed, step, 0); only the 44 directed edges are drawn: q_ij of
+ * head h of patch t of sample b is dropped where lowbias32(counter ^ key) < round(p_drop 2^32), counter =
+ * (((sample_offset + b) T + t) Hd + h) 44 + e, e the edge's index in row-major order of A; a call whose counters would pass 2^32 is
+ * refused (RULGNN_EUNSUPPORTED).
+ * Limits (before any launch; the workspace query returns 0): RULGNN_EINVAL for an extent below 1 or a negative batch,
+ * RULGNN_EUNSUPPORTED for num_nodes != RULGNN_STFA_NUM_NODES, num_patch > RULGNN_STFA_MAX_NUM_PATCH, patch_size >
+ * RULGNN_STFA_MAX_PATCH_SIZE, output_dim > RULGNN_STFA_MAX_OUTPUT_DIM, num_heads > RULGNN_STFA_MAX_HEADS, encoder_hidden_dim >
+ * RULGNN_STFA_MAX_LSTM_HIDDEN.  Deterministic: no floating-point atomics, fixed-order reductions.
+ */
+#define RULGNN_STFA_NUM_NODES 14
+#define RULGNN_STFA_MAX_NUM_PATCH 128
+#define RULGNN_STFA_MAX_PATCH_SIZE 64
+#define RULGNN_STFA_MAX_OUTPUT_DIM 16
+#define RULGNN_STFA_MAX_HEADS 16
+#define RULGNN_STFA_MAX_LSTM_HIDDEN 128
+#define RULGNN_STFA_TAP_ROWS 0
+#define RULGNN_STFA_TAP_LSTM 1
+
+typedef struct rulgnn_stfa_shape {
+    int64_t batch;
+    int32_t num_patch, patch_size, num_nodes;
+    int32_t output_dim, num_heads, encoder_hidden_dim;
+} rulgnn_stfa_shape;
+
+typedef struct rulgnn_stfa_args {
+    const float *x;           /* [batch, 14, num_patch * patch_size] */
+    const float *y;           /* [batch] targets, or NULL */
+    const float *dpred;       /* [batch] d loss / d pred (autograd backward); NULL = MSE against y */
+    const float *params;
+    float *grads;
+    float *pred;              /* [batch] */
+    float *loss;              /* [1] this shard's share of MSE(pred, y) over the global batch; may be NULL */
+    void *workspace;
+    size_t workspace_bytes;
+    int64_t global_batch;
+    int64_t sample_offset;    /* index of this call's first sample in the global batch (dropout counters) */
+    float dropout_p;          /* applied when training != 0 */
+    uint64_t seed, step;      /* dropout stream: mask = f(seed, step, element counter); a backward takes its forward's values */
+    int32_t training;
+} rulgnn_stfa_args;
+
+int64_t rulgnn_stfa_param_count(const rulgnn_stfa_shape *shape);        /* < 0: invalid / unsupported */
+size_t rulgnn_stfa_workspace_bytes(const rulgnn_stfa_shape *shape);     /* 0: invalid / unsupported */
+/* workspace taps for the parity tests, float offsets: RULGNN_STFA_TAP_ROWS the LSTM's input rows [batch][T][W] (T ones, then the stage
+ * output [14][C]: the `gat` tap is their last 14 C columns), RULGNN_STFA_TAP_LSTM the LSTM's output [batch][T][E]; -1 otherwise */
+int64_t rulgnn_stfa_tap_offset(const rulgnn_stfa_shape *shape, int32_t which);
+int rulgnn_stfa_forward_f32(const rulgnn_stfa_shape *shape, const rulgnn_stfa_args *args, void *stream);
+/* loss.backward() after a forward with the same args / workspace. */
+int rulgnn_stfa_backward_f32(const rulgnn_stfa_shape *shape, const rulgnn_stfa_args *args, void *stream);
+/* STFA.update body (algorithms.py:183-192); with `opt` also Adam on the whole flat parameter buffer. */
+int rulgnn_stfa_fwdbwd_f32(const rulgnn_stfa_shape *shape, const rulgnn_stfa_args *args, const rulgnn_adam_args *opt, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * RUL test metrics on the device.

@@ -1,0 +1,287 @@
+"""STFA without a GPU: the registry, the hparams rows, the module's surface (48 names in order, a seed gives the reference's initial
+weights), the parameter count, the C-ABI's struct sizes and status codes, the coverage gate at every limit, the checks that answer before
+any launch, and the inputs that raise."""
+import ctypes as C
+import glob
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from gnn_rul_benchmarking_amd import _lib
+
+from conftest import GOLDEN
+
+import stfa_oracle as O
+from test_stfa_oracle_golden import CURVE, FULL, NAN, SMALL, load_case
+
+ROW = dict(patch_size=2, num_patch=25, num_nodes=14, hidden_dim=16, output_dim=5, encoder_hidden_dim=64, num_heads=10, dropout=0.2)
+TINY = dict(ROW, patch_size=1, num_patch=1, output_dim=1, encoder_hidden_dim=1, num_heads=1)
+RULGNN_EINVAL, RULGNN_EUNSUPPORTED, RULGNN_EWORKSPACE = -1, -2, -3                # include/rulgnn.h
+
+
+def shape_of(batch, cfg):
+    s = _lib.StfaShape()
+    s.batch, s.num_patch, s.patch_size, s.num_nodes = batch, cfg["num_patch"], cfg["patch_size"], cfg["num_nodes"]
+    s.output_dim, s.num_heads, s.encoder_hidden_dim = cfg["output_dim"], cfg["num_heads"], cfg["encoder_hidden_dim"]
+    return s
+
+
+def entry_codes(lib, s, a=None):
+    a = a if a is not None else _lib.StfaArgs()
+    return {lib.rulgnn_stfa_forward_f32(C.byref(s), C.byref(a), None), lib.rulgnn_stfa_backward_f32(C.byref(s), C.byref(a), None),
+            lib.rulgnn_stfa_fwdbwd_f32(C.byref(s), C.byref(a), None, None)}
+
+
+def test_registry_serves_the_algorithm_and_refuses_the_model():
+    from gnn_rul_benchmarking_amd import algorithms as A
+    assert A.get_algorithm_class("STFA") is A.STFA
+    with pytest.raises(NotImplementedError, match="Algorithm not found: STFA_model"):
+        A.get_algorithm_class("STFA_model")
+    assert A.STFA.needs_train_mode == "dropout" and A.STFA.supports_graphs is False
+
+
+def test_hparams_rows_equal_the_reference():
+    from gnn_rul_benchmarking_amd.hparams import get_hparams_class
+    z = np.load(os.path.join(GOLDEN, "stfa_hparams_rows.npz"))
+    rows = json.loads(str(z["rows_json"]))
+    assert sorted(rows) == ["CMAPSS/FD001", "CMAPSS/FD002", "CMAPSS/FD003", "CMAPSS/FD004"]
+    for key, ref in rows.items():
+        ds, did = key.split("/")
+        h = get_hparams_class(ds)(did)
+        assert h.train_params["STFA"] == ref["train_params"] == {'num_epochs': 81, 'batch_size': 100, 'weight_decay': 1e-4, 'learning_rate': 1e-3}
+        assert h.alg_hparams["STFA"] == ref["alg_hparams"] == ROW, key
+    assert sorted(json.loads(str(z["absent_json"]))) == sorted(["NCMAPSS/None"] + [f"{d}/Condition_{i}" for d in ("PHM2012", "XJTU_SY") for i in (1, 2, 3)])
+    others = [get_hparams_class("NCMAPSS")(None)] + [get_hparams_class(d)(f"Condition_{i}") for d in ("PHM2012", "XJTU_SY") for i in (1, 2, 3)]
+    for h in others:
+        assert "STFA" not in h.alg_hparams and "STFA" not in h.train_params
+
+
+def test_algorithm_construction_from_the_row_leaves_the_configs_alone():
+    from gnn_rul_benchmarking_amd import algorithms as A
+    from gnn_rul_benchmarking_amd.hparams import get_hparams_class
+    from gnn_rul_benchmarking_amd.optim import FusedAdam
+    from gnn_rul_benchmarking_amd.stfa import STFA_model
+    h = get_hparams_class("CMAPSS")("FD003")
+    cfg = h.alg_hparams["STFA"]
+    algo = A.get_algorithm_class("STFA")(cfg, h.train_params["STFA"], "cpu")
+    assert cfg == ROW and "device" not in cfg                     # the reference writes 'cuda:0' into it
+    assert isinstance(algo.model, STFA_model) and isinstance(algo.optimizer, FusedAdam) and algo.model.c_family == "stfa"
+    assert algo.model.dropout_p == 0.2 and algo.model.dropout_by_sample_offset is True and algo.model.eval_sample_independent is True
+    assert algo.model.bucket_tail == 1 and algo.model.gradless_params == 0
+    algo.eval()
+    with pytest.raises(RuntimeError, match="needs algorithm.train"):
+        algo.update(torch.zeros(2, 14, 50), torch.zeros(2, 1))
+
+
+def test_param_count_is_41612():
+    from gnn_rul_benchmarking_amd.stfa import STFA_model
+    lib = _lib.load()
+    m = STFA_model(**ROW)
+    assert sum(p.numel() for p in m.parameters()) == m.num_live == O.param_count(ROW) == 41612
+    for B in (1, 100, 1024):
+        assert lib.rulgnn_stfa_param_count(C.byref(shape_of(B, ROW))) == 41612 and lib.rulgnn_stfa_workspace_bytes(C.byref(shape_of(B, ROW))) > 0
+    assert m.bucket.numel() == 41613 and not list(m.named_buffers())
+
+
+@pytest.mark.parametrize("name", SMALL + FULL + [NAN])
+def test_a_seed_gives_the_reference_keys_and_initial_values(name):
+    """48 names (at ten heads) in the reference's order, strict load and -- under the fixture's seed plus the maker's recorded
+    perturbation -- the reference's values: bit for bit where the fixture stores them, by the fp64 checksum where it stores the seed."""
+    from gnn_rul_benchmarking_amd.stfa import STFA_model
+    z, cfg, _ = load_case(name)
+    seed = int(z["seed"])
+    torch.manual_seed(seed)
+    m = STFA_model(**cfg)
+    sd = m.state_dict()
+    names = O.param_names(cfg)
+    assert list(sd.keys()) == [n for n, _ in m.named_parameters()] == list(m._layout) == names
+    assert len(names) == 4 * cfg["num_heads"] + 8 and (name not in FULL or len(names) == 48)
+    if name in FULL:
+        assert names[:4] == ["gat.attention_0.linear.weight", "gat.attention_0.linear.bias", "gat.attention_0.attention.weight",
+                             "gat.attention_0.attention.bias"]
+        assert names[36:] == ["gat.attention_9.linear.weight", "gat.attention_9.linear.bias", "gat.attention_9.attention.weight",
+                              "gat.attention_9.attention.bias", "v.weight", "v.bias", "lstm.weight_ih_l0", "lstm.weight_hh_l0", "lstm.bias_ih_l0",
+                              "lstm.bias_hh_l0", "fc.weight", "fc.bias"]
+    assert {k: tuple(v.shape) for k, v in sd.items()} == O.param_shapes(cfg)
+    assert np.array_equal(m.flat_params.numpy(), np.concatenate([sd[k].numpy().ravel() for k in names]))
+    g = torch.Generator().manual_seed(seed + 1000)
+    moved = {k: v.clone().add_(torch.empty_like(v).uniform_(-0.1, 0.1, generator=g)) for k, v in sd.items()}
+    flat = np.concatenate([moved[k].numpy().astype(np.float64).ravel() for k in names])
+    assert np.allclose([flat.sum(), (flat * flat).sum()], z["checksum"], rtol=1e-12, atol=0)
+    if name in SMALL:
+        for k in names:
+            assert np.array_equal(moved[k].numpy(), z["sd:" + k]), k
+        other = STFA_model(**cfg)
+        full = {k: torch.from_numpy(z["sd:" + k]) for k in names}
+        other.load_state_dict(full, strict=True)
+        assert np.array_equal(other.state_dict()["v.weight"].numpy(), z["sd:v.weight"])
+        with pytest.raises(RuntimeError):
+            other.load_state_dict({k: full[k] for k in names[1:]}, strict=True)              # a missing key
+
+
+def test_device_argument_is_accepted_and_ignored():
+    from gnn_rul_benchmarking_amd.stfa import STFA_model
+    torch.manual_seed(3)
+    a = STFA_model(**ROW)
+    torch.manual_seed(3)
+    b = STFA_model(device="cuda:0", **ROW)                        # the reference's algorithm passes this on a machine without one, too
+    torch.manual_seed(3)
+    c = STFA_model(2, 25, 14, 16, 5, 64, None, 10, 0.2)           # the reference's positional order
+    assert torch.equal(a.flat_params, b.flat_params) and torch.equal(a.flat_params, c.flat_params)
+    assert b.flat_params.device.type == "cpu" and not hasattr(b, "adj") and c.hidden_dim == 16
+
+
+def test_struct_sizes_are_checked_at_load():
+    lib = _lib.load()
+    assert _lib.STRUCTS_STFA == {45: _lib.StfaShape, 46: _lib.StfaArgs} and len(_lib.STRUCTS) == 37
+    header = open(os.path.join(os.path.dirname(__file__), "..", "include", "rulgnn.h")).read()
+    assert "#define RULGNN_STRUCT_STFA_SHAPE 45\n" in header and "#define RULGNN_STRUCT_STFA_ARGS 46\n" in header
+    assert "#define RULGNN_EINVAL       -1 " in header and "#define RULGNN_EUNSUPPORTED -2 " in header      # the codes this file names
+    assert "#define RULGNN_EWORKSPACE   -3 " in header
+    assert lib.rulgnn_struct_size(45) == C.sizeof(_lib.StfaShape) == 32
+    assert lib.rulgnn_struct_size(46) == C.sizeof(_lib.StfaArgs) == C.sizeof(_lib.GatlstmArgs) == 120
+    assert lib.rulgnn_struct_size(44) == 0 and lib.rulgnn_struct_size(47) == 0
+    assert [n for n, _ in _lib.StfaArgs._fields_] == [n for n, _ in _lib.GatlstmArgs._fields_]
+    for n in ("param_count", "workspace_bytes", "tap_offset", "forward_f32", "backward_f32", "fwdbwd_f32"):
+        assert f"rulgnn_stfa_{n}" in _lib.EXPORTED_SYMBOLS and f"rulgnn_stfa_{n}(" in header
+
+
+LIMIT_NAMES = (("NUM_NODES", "num_nodes"), ("MAX_NUM_PATCH", "max_num_patch"), ("MAX_PATCH_SIZE", "max_patch_size"),
+               ("MAX_OUTPUT_DIM", "max_output_dim"), ("MAX_HEADS", "max_heads"), ("MAX_LSTM_HIDDEN", "max_lstm_hidden"))
+CFG_OF_LIMIT = {"max_num_patch": "num_patch", "max_patch_size": "patch_size", "max_output_dim": "output_dim", "max_heads": "num_heads",
+                "max_lstm_hidden": "encoder_hidden_dim"}
+
+
+def test_limits_are_stated_once_and_admit_what_the_issue_asks():
+    from gnn_rul_benchmarking_amd.stfa import LIMITS
+    header = open(os.path.join(os.path.dirname(__file__), "..", "include", "rulgnn.h")).read()
+    assert len(LIMITS) == len(LIMIT_NAMES)
+    for name, key in LIMIT_NAMES:
+        assert f"#define RULGNN_STFA_{name} {LIMITS[key]}\n" in header
+    assert LIMITS["num_nodes"] == 14 and LIMITS["max_patch_size"] >= 64 and LIMITS["max_output_dim"] >= 16 and LIMITS["max_heads"] >= 16
+    assert LIMITS["max_num_patch"] >= 128 and LIMITS["max_lstm_hidden"] >= 128
+
+
+def test_shape_status_codes_and_every_limit_plus_one():
+    from gnn_rul_benchmarking_amd.stfa import LIMITS, within_limits
+    lib = _lib.load()
+
+    def query(cfg, B=3, code=RULGNN_EUNSUPPORTED):
+        s = shape_of(B, cfg)
+        pc, ws = lib.rulgnn_stfa_param_count(C.byref(s)), lib.rulgnn_stfa_workspace_bytes(C.byref(s))
+        assert (pc < 0) == (ws == 0) and all((lib.rulgnn_stfa_tap_offset(C.byref(s), i) < 0) == (ws == 0) for i in (0, 1))
+        assert lib.rulgnn_stfa_tap_offset(C.byref(s), 2) == -1
+        assert within_limits(cfg["num_nodes"], cfg["num_patch"], cfg["patch_size"], cfg["output_dim"], cfg["num_heads"],
+                             cfg["encoder_hidden_dim"]) == (ws > 0 or B < 0)
+        if ws == 0:                    # refused by the entries too, before any launch (no device is needed to be told so)
+            assert entry_codes(lib, s) == {code}, (cfg, code)
+        return ws > 0
+
+    top = dict(ROW, **{cfg_key: LIMITS[lim] for lim, cfg_key in CFG_OF_LIMIT.items()})
+    assert query(TINY) and query(ROW) and query(top)              # every lower limit at once, the reference row, every upper limit at once
+    for base in (TINY, ROW, top):
+        for lim, cfg_key in CFG_OF_LIMIT.items():
+            assert not query(dict(base, **{cfg_key: LIMITS[lim] + 1}))                     # beyond a limit: unsupported
+            assert not query(dict(base, **{cfg_key: 0}), code=RULGNN_EINVAL)               # no extent at all: invalid
+        assert not query(dict(base, num_nodes=13)) and not query(dict(base, num_nodes=15)) and not query(dict(base, num_nodes=20))
+        assert not query(dict(base, num_nodes=0), code=RULGNN_EINVAL)
+        assert not query(base, B=-1, code=RULGNN_EINVAL)
+    ws = lambda b: lib.rulgnn_stfa_workspace_bytes(C.byref(shape_of(b, ROW)))      # noqa: E731
+    assert ws(0) > 0 and ws(1024) > ws(100) > ws(1) >= ws(0)
+    assert lib.rulgnn_stfa_param_count(None) == -1 and lib.rulgnn_stfa_workspace_bytes(None) == 0
+    # per sample: the LSTM's input rows and output, two gradient buffers of the wider of the two, two floats of the head and the LSTM's own
+    # tapes (bilstm.hip: gi, gates, dgates [2][4 E]; c, tanh c, h, h_prev [2][E]) -- and nothing [Hd][14][14]-shaped: the stage keeps no
+    # activation but its output (the slack: the split-K scratch of the weight-gradient GEMMs also grows with the rows)
+    per = (ws(2048) - ws(1024)) / 4 / 1024
+    T, W, E = 25, 95, 64
+    graph = T * W + T * E + 2 * T * max(W, E) + 2
+    lstm = T * (3 * 2 * 4 * E + 4 * 2 * E)
+    assert graph + lstm <= per <= 1.05 * (graph + lstm), (per, graph, lstm)
+
+
+def test_bad_arguments_are_rejected_before_any_launch():
+    """No device is touched: every pointer below is null or host memory, and the codes come back all the same."""
+    lib = _lib.load()
+    s = shape_of(2, ROW)
+    a = _lib.StfaArgs()
+    a.global_batch = 1                                            # smaller than the batch
+    assert entry_codes(lib, s, a) == {RULGNN_EINVAL}
+    a.global_batch, a.sample_offset = 2, -1
+    assert entry_codes(lib, s, a) == {RULGNN_EINVAL}
+    a.sample_offset = 0
+    for p in (-0.1, 1.0, float("nan")):
+        a.dropout_p = p
+        assert entry_codes(lib, s, a) == {RULGNN_EINVAL}, p
+    a.dropout_p = 0.2
+    # dropout counters that do not fit 32 bits: (sample_offset + batch) T Hd 44 and global_batch T Hd 44
+    a.sample_offset = (1 << 32) // (44 * 10 * 25)
+    assert entry_codes(lib, s, a) == {RULGNN_EUNSUPPORTED}
+    a.sample_offset, a.global_batch = 0, (1 << 32) // (44 * 10 * 25) + 1
+    assert entry_codes(lib, s, a) == {RULGNN_EUNSUPPORTED}
+    a.global_batch = 2
+    assert entry_codes(lib, s, a) == {RULGNN_EINVAL}              # null pointers
+    # Bad Adam arguments: what the fused entry's Adam check refuses (step < 1 without a device step state, a parameter pointer other
+    # than the step's, a null moment buffer), it refuses with RULGNN_EINVAL behind the argument check and before run().  The control: the
+    # same call with a valid Adam block passes that check and is stopped by run()'s first statement, the workspace size
+    # (workspace_bytes = 0: RULGNN_EWORKSPACE), which stands before every launch -- so the host buffers below can reach no kernel, on a
+    # machine with a GPU either.  (lr, betas and eps are not validated by the library, for no family: torch.optim.Adam's own checks are
+    # the constructor's, optim.FusedAdam's here.)
+    buf, other = (C.c_float * 64)(), (C.c_float * 64)()
+    ok = _lib.StfaArgs()
+    for f in ("x", "y", "params", "grads", "pred", "loss", "workspace"):
+        setattr(ok, f, C.addressof(buf))
+    ok.global_batch, ok.dropout_p, ok.workspace_bytes = 2, 0.2, 0
+
+    def fused(**change):
+        kw = dict(params=C.addressof(buf), exp_avg=C.addressof(buf), exp_avg_sq=C.addressof(buf), step=1, lr=1e-3, beta1=0.9, beta2=0.999,
+                  eps=1e-8)
+        kw.update(change)
+        opt = _lib.AdamArgs()
+        for k, v in kw.items():
+            setattr(opt, k, v)
+        return lib.rulgnn_stfa_fwdbwd_f32(C.byref(s), C.byref(ok), C.byref(opt), None)
+
+    assert RULGNN_EWORKSPACE not in (RULGNN_EINVAL, 0)
+    assert fused() == RULGNN_EWORKSPACE                            # the control: a valid block gets past the Adam check
+    assert lib.rulgnn_stfa_fwdbwd_f32(C.byref(s), C.byref(ok), None, None) == RULGNN_EWORKSPACE
+    for bad in (dict(step=0), dict(step=-3), dict(params=C.addressof(other)), dict(params=None), dict(exp_avg=None), dict(exp_avg_sq=None)):
+        assert fused(**bad) == RULGNN_EINVAL, bad
+
+
+def test_out_of_limit_model_constructs_and_is_refused_before_the_library_is_touched(monkeypatch):
+    from gnn_rul_benchmarking_amd.stfa import LIMITS, STFA_model
+    bads = [dict(TINY, **{cfg_key: LIMITS[lim] + 1}) for lim, cfg_key in CFG_OF_LIMIT.items()] + [dict(TINY, num_nodes=13)]
+    models = [STFA_model(**bad) for bad in bads]                  # constructs
+    monkeypatch.setattr(STFA_model, "_require_device", lambda self, x: None)       # the limits answer before any device call
+    monkeypatch.setattr(_lib, "load", lambda: (_ for _ in ()).throw(AssertionError("library touched")))
+    for m, bad in zip(models, bads):
+        x = torch.zeros(2, bad["num_nodes"], bad["num_patch"] * bad["patch_size"])
+        with pytest.raises(RuntimeError, match="do not cover this configuration"):
+            m(x)
+        with pytest.raises(RuntimeError, match="do not cover this configuration"):
+            m.fused_mse_step(x, torch.zeros(2))
+        assert not m._bufs and not m._grad_flat.any()
+
+
+def test_cpu_input_raises():
+    from gnn_rul_benchmarking_amd.stfa import STFA_model
+    m = STFA_model(**TINY)
+    with pytest.raises(RuntimeError, match="HIP path only"):
+        m(torch.zeros(2, 14, 1))
+    with pytest.raises(RuntimeError, match="HIP path only"):
+        m.fused_mse_step(torch.zeros(2, 14, 1), torch.zeros(2))
+
+
+def test_fixtures_hold_no_grad_key_and_stay_small():
+    files = sorted(glob.glob(os.path.join(GOLDEN, "stfa_*.npz")))
+    assert len(files) == 7
+    for f in files:
+        assert not [k for k in np.load(f).files if k.startswith("grad:")], f
+        assert os.path.getsize(f) < 1 << 20
+    for name in SMALL + FULL + [NAN]:
+        assert {"x", "y", "pred", "pred32", "pred_eval", "loss", "seed", "checksum", "tap:gat", "tap:rows", "tap:lstm", "kink_margin"} <= set(load_case(name)[0])
+    assert "sd:fc.bias" not in load_case(FULL[0])[0]              # the full-width case holds the seed and the checksum
+    assert {"xs", "ys", "losses", "eval_pred_end", "lr", "wd"} <= set(np.load(os.path.join(GOLDEN, CURVE + ".npz")).files)

@@ -1,0 +1,203 @@
+"""The fp64 STFA oracle (tests/stfa_oracle.py) against what the reference itself produced on the CPU in fp64
+(tests/golden/make_golden_stfa.py): forward, taps and loss at 1e-9 relative, the hand-written backward against the reference's fp64
+autograd at 1e-9 of each tensor's largest element, the torch restatement against both, the zero gradients of ``v``, the equal
+ones-columns of the LSTM's input weights, the kink margin, the NaN case, the curve and the dropout masks."""
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import GOLDEN
+
+import stfa_oracle as O
+
+SMALL = ["stfa_small_t2_p3_bs3", "stfa_small_t3_p5_bs4"]
+FULL = ["stfa_row_t25_p2_bs2"]
+NAN = "stfa_nan_t3_p5_bs3"
+CURVE = "stfa_train_curve_t3_p5_bs8"
+TOL64 = 1e-9              # fp64 against fp64
+RESTATE_TOL = 1e-5        # the torch restatement in fp32 against the fixtures' fp64 values (the maker's bar for the reference's own fp32 run)
+
+_cache = {}
+
+
+def seeded_weights(cfg, seed):
+    """The maker's weights: the constructor's under the seed (the package's module draws in the reference's order), moved by the
+    recorded perturbation."""
+    from gnn_rul_benchmarking_amd.stfa import STFA_model
+    torch.manual_seed(seed)
+    sd = STFA_model(**cfg).state_dict()
+    g = torch.Generator().manual_seed(seed + 1000)
+    return {k: (v.clone() + torch.empty_like(v).uniform_(-0.1, 0.1, generator=g)).numpy() for k, v in sd.items()}
+
+
+def load_case(name):
+    """(fixture, cfg, weights name -> fp32 array); cached and never modified."""
+    if name not in _cache:
+        z = np.load(os.path.join(GOLDEN, name + ".npz"))
+        z = {k: z[k] for k in z.files}
+        cfg = json.loads(str(z["cfg_json"]))
+        P = seeded_weights(cfg, int(z["seed"]))        # the package's module under the fixture's seed: the reference's initial weights
+        if "sd:fc.bias" in z:                          # ... bit for bit where the fixture stores them, by the checksum below otherwise
+            assert list(P) == O.param_names(cfg) and all(np.array_equal(P[k], z["sd:" + k]) for k in P)
+        flat = np.concatenate([P[k].astype(np.float64).ravel() for k in O.param_names(cfg)])
+        assert np.allclose([flat.sum(), (flat * flat).sum()], z["checksum"], rtol=1e-12, atol=0)
+        _cache[name] = (z, cfg, P)
+    return _cache[name]
+
+
+def oracle_run(name):
+    """The fp64 oracle's forward + backward of a fixture (train mode, dropout off), computed once."""
+    key = ("run", name)
+    if key not in _cache:
+        z, cfg, P = load_case(name)
+        _cache[key] = O.forward_backward(P, z["x"], z["y"], cfg)
+    return _cache[key]
+
+
+def rel(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
+
+
+def rel_finite(a, b):
+    """``rel`` over the entries where ``b`` is finite; NaN must sit in the same places."""
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64).reshape(np.asarray(a).shape)
+    assert np.array_equal(np.isnan(a), np.isnan(b))
+    ok = ~np.isnan(b)
+    return rel(a[ok], b[ok]) if ok.any() else 0.0
+
+
+@pytest.mark.parametrize("name", SMALL + FULL)
+def test_forward_taps_and_loss(name):
+    z, cfg, P = load_case(name)
+    o = oracle_run(name)
+    assert rel(o["pred"], z["pred"]) < TOL64 and rel(o["pred"], z["pred_eval"]) < TOL64        # dropout off: train == eval
+    assert abs(o["loss"] - float(z["loss"])) < TOL64 * float(z["loss"])
+    assert sorted(k[4:] for k in z if k.startswith("tap:")) == ["gat", "lstm", "rows"]
+    for k in ("gat", "rows", "lstm"):
+        assert o[k].shape == z["tap:" + k].shape and rel(o[k], z["tap:" + k]) < TOL64, k
+    T = cfg["num_patch"]
+    assert z["tap:rows"].shape[-1] == T + 14 * cfg["output_dim"]
+    assert (z["tap:rows"][..., :T] == 1.0).all()                 # the singleton softmax: exactly one
+    assert np.array_equal(z["tap:rows"][..., T:], z["tap:gat"])
+    assert rel(z["pred32"], z["pred"]) < 1e-5                    # the reference's own fp32 run
+    assert float(z["kink_margin"]) > 1.0 and float(z["gat_matters"]) > 100 * 1e-4
+
+
+@pytest.mark.parametrize("name", SMALL + FULL)
+def test_kink_margin_holds_in_the_oracle_run(name):
+    """Every leakyrelu and ReLU argument of the fp64 run is farther from zero than 16 fp32 ulps of its tensor's largest magnitude."""
+    o = oracle_run(name)
+    Hd = load_case(name)[1]["num_heads"]
+    assert sorted(o["kinks"]) == sorted(["relu"] + [f"leakyrelu{h}" for h in range(Hd)])
+    for k, v in o["kinks"].items():
+        assert np.abs(v).min() > 16 * 2.0 ** -23 * np.abs(v).max(), k
+    assert abs(O.kink_margin(o) - float(load_case(name)[0]["kink_margin"])) < 1e-6 * O.kink_margin(o)
+
+
+@pytest.mark.parametrize("name", SMALL + FULL)
+def test_backward_against_the_reference_autograd(name):
+    """All 48 fp64 gradients of the reference at 1e-9 of the tensor's largest element; the restatement in fp64 likewise; the reference's
+    fp32 gradients within 1e-4 of the model's largest."""
+    z, cfg, P = load_case(name)
+    g64 = oracle_run(name)["grads"]
+    names = O.param_names(cfg)
+    assert list(g64) == names and len(names) == 4 * cfg["num_heads"] + 8 and (name not in FULL or len(names) == 48)
+    assert sorted(k[7:] for k in z if k.startswith("grad64:")) == sorted(names) == sorted(k[8:] for k in z if k.startswith("refgrad:"))
+    assert not [k for k in z if k.startswith("grad:")]            # tests/test_grad_gate_cpu.py globs every fixture for ``grad:`` keys
+    gmax = max(float(np.abs(v).max()) for v in g64.values())
+    restated = O.torch_grads(P, z["x"], z["y"], cfg, torch.float64)
+    assert rel(restated[0], z["pred"]) < TOL64 and abs(restated[1] - float(z["loss"])) < TOL64 * float(z["loss"])
+    for k in names:
+        ref = z["grad64:" + k]
+        assert g64[k].shape == ref.shape == O.param_shapes(cfg)[k], k
+        if k.startswith("v."):
+            continue
+        scale = max(float(np.abs(ref).max()), 1e-12 * gmax)
+        assert np.abs(g64[k] - ref).max() < TOL64 * scale, (k, np.abs(g64[k] - ref).max(), scale)
+        assert np.abs(restated[2][k] - ref).max() < TOL64 * scale, k
+        assert np.abs(z["refgrad:" + k] - ref).max() < 1e-4 * gmax, k
+    for k in ("gat.attention_0.linear.weight", "gat.attention_0.attention.weight", "fc.weight"):
+        assert np.abs(z["grad64:" + k]).max() > 0, k
+
+
+@pytest.mark.parametrize("name", SMALL + FULL)
+def test_v_gradients_are_exactly_zero_and_the_ones_columns_are_equal(name):
+    z, cfg, P = load_case(name)
+    g64 = oracle_run(name)["grads"]
+    for k in ("v.weight", "v.bias"):
+        for g in (z["grad64:" + k], z["refgrad:" + k], g64[k]):
+            assert g.shape == O.param_shapes(cfg)[k] and not g.any(), k          # zeros, not None: a tensor is stored
+    T = cfg["num_patch"]
+    for g, tol in ((z["grad64:lstm.weight_ih_l0"], 1e-12), (g64["lstm.weight_ih_l0"], 1e-12), (z["refgrad:lstm.weight_ih_l0"], 1e-5)):
+        ones = g[:, :T]
+        assert np.abs(ones - ones[:, :1]).max() <= tol * np.abs(g).max()          # T equal input columns: T equal gradient columns
+        assert np.abs(ones).max() > 0
+    # ... and they equal the bias gradient (a constant-one input)
+    assert rel(g64["lstm.weight_ih_l0"][:, 0], g64["lstm.bias_ih_l0"]) < 1e-12
+
+
+@pytest.mark.parametrize("name", SMALL)
+def test_restatement_in_fp32(name):
+    z, cfg, P = load_case(name)
+    pred, loss, g = O.torch_grads(P, z["x"], z["y"], cfg, torch.float32)
+    assert rel(pred, z["pred"]) < RESTATE_TOL and abs(loss - float(z["loss"])) < 1e-5 * float(z["loss"])
+    assert not g["v.weight"].any() and not g["v.bias"].any()
+
+
+def test_nan_case():
+    z, cfg, P = load_case(NAN)
+    assert np.isnan(z["x"]).sum() == 1 and np.isnan(z["x"][1]).sum() == 1
+    o = O.forward_backward(P, z["x"], None, cfg)
+    want = z["pred_eval"].reshape(-1)
+    assert np.isnan(want).tolist() == [False, True, False] and np.isnan(o["pred"].reshape(-1)).tolist() == [False, True, False]
+    assert rel_finite(o["pred"].reshape(-1), want) < TOL64
+    for k in ("gat", "rows", "lstm"):                             # the clean samples' taps
+        assert rel(o[k][[0, 2]], z["tap:" + k][[0, 2]]) < TOL64, k
+    # the reference poisons the sample's whole LSTM output through the singleton softmax (a NaN "one" in every row); the graph stage alone
+    # is poisoned in the patch that holds the NaN, and there in every node (the softmax runs over all 14)
+    assert np.isnan(z["tap:lstm"][1]).all() and np.isnan(z["tap:gat"][1, 1]).all() and not np.isnan(z["tap:gat"][1, [0, 2]]).any()
+    assert np.isnan(o["gat"][1, 1]).all() and not np.isnan(o["gat"][1, [0, 2]]).any() and np.isnan(o["lstm"][1, 1:]).all()
+
+
+def test_training_curve_fixture():
+    z = np.load(os.path.join(GOLDEN, CURVE + ".npz"))
+    cfg = json.loads(str(z["cfg_json"]))
+    assert cfg["dropout"] == 0.0 and "device" not in cfg and len(z["losses"]) == 20 and z["xs"].shape[:2] == (20, 8)
+    sd0 = {k[4:]: z[k] for k in z.files if k.startswith("sd0:")}
+    from gnn_rul_benchmarking_amd.stfa import STFA_model
+    shapes = {k: tuple(v.shape) for k, v in STFA_model(**cfg).state_dict().items()}
+    assert list(sd0) == O.param_names(cfg) == list(shapes) and {k: v.shape for k, v in sd0.items()} == shapes
+    o = O.forward_backward(sd0, z["xs"][0], z["ys"][0], cfg, want_grads=False)
+    assert abs(o["loss"] - z["losses"][0]) < 1e-5 * z["losses"][0]
+    # the kink margin holds, as a condition, at every state the fixture stores with the batch that meets it
+    for i, s in enumerate((0, 1, 10)):
+        sd_s = {k: z[f"sd{s}:" + k] for k in sd0}
+        margin = O.kink_margin(O.forward_backward(sd_s, z["xs"][s], None, cfg))
+        assert margin > 1.0 and abs(margin - z["kink_margin"][i]) < 1e-6 * margin, (s, margin)
+    # Adam's weight decay moves v although its gradient is zero: by about lr per step towards zero
+    lr = float(z["lr"])
+    for k in ("v.weight", "v.bias"):
+        d1 = z["sd1:" + k].astype(np.float64) - sd0[k]
+        # (the first step is lr g / (|g| + eps) with g = wd w: short of lr by eps / (wd |w|), under 10 % for |w| > 1e-3)
+        big = np.abs(sd0[k]) > 1e-3
+        assert big.any() and np.allclose(d1[big], -lr * np.sign(sd0[k][big]), rtol=0.1, atol=0), k
+        assert np.abs(z["sd20:" + k].astype(np.float64) - sd0[k]).max() > 10 * lr
+
+
+def test_keep_masks_draw_only_the_edges():
+    cfg = load_case(SMALL[1])[1]
+    A = O.adjacency()
+    assert A.sum() == 44 and not np.diag(A).any() and np.array_equal(A, A.T) and A.sum(1).min() == 1 and A.sum(1).max() == 6
+    k = O.keep_masks(4, cfg, 1234, 1, 0.5)
+    assert k.shape == (4, cfg["num_patch"], cfg["num_heads"], 14, 14) and (k[..., A == 0] == 1).all()
+    share = 1 - k[..., A > 0].mean()
+    assert abs(share - 0.5) < 0.05
+    assert not np.array_equal(k, O.keep_masks(4, cfg, 1234, 2, 0.5)) and np.array_equal(k, O.keep_masks(4, cfg, 1234, 1, 0.5))
+    assert np.array_equal(k[1:], O.keep_masks(3, cfg, 1234, 1, 0.5, sample_offset=1))           # keyed by the global sample index
+    o0, o1 = O.forward_backward(load_case(SMALL[1])[2], load_case(SMALL[1])[0]["x"], None, cfg), \
+        O.forward_backward(load_case(SMALL[1])[2], load_case(SMALL[1])[0]["x"], None, cfg, keep=k, dropout_p=0.5)
+    assert rel(o1["gat"], o0["gat"]) > 1e-2
