@@ -18,18 +18,27 @@ TRAIN_WS_CLEAN = 1                                        # include/rulgnn.h RUL
 NUM_STATS = 10
 
 
+# ---- the argument structs of the step entries share their field lists (include/rulgnn.h spells them out struct by struct) -----------
+_TRAINING = ("training", C.c_int32)
+# dropout drawn from the counter hash by sample index in the global batch: where the shard starts, the rate, the stream, train / eval
+_DROPOUT = [("sample_offset", C.c_int64), ("dropout_p", C.c_float), ("seed", C.c_uint64), ("step", C.c_uint64), _TRAINING]
+
+
+def _step_fields(before_loss=(), after_loss=(), tail=()):
+    """``x y dpred params grads pred [before_loss...] loss [after_loss...] workspace`` (pointers), ``workspace_bytes``, ``global_batch``, then
+    the family's ``tail``."""
+    ptrs = ("x", "y", "dpred", "params", "grads", "pred", *before_loss, "loss", *after_loss, "workspace")
+    return [(name, C.c_void_p) for name in ptrs] + [("workspace_bytes", C.c_size_t), ("global_batch", C.c_int64)] + list(tail)
+
+
 class StgcnShape(C.Structure):
     _fields_ = [("batch", C.c_int64), ("num_patch", C.c_int32), ("patch_size", C.c_int32),
                 ("num_layers", C.c_int32), ("mpnn_k", C.c_int32)]
 
 
 class StgcnTrainArgs(C.Structure):
-    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("dpred", C.c_void_p), ("params", C.c_void_p),
-                ("grads", C.c_void_p), ("pred", C.c_void_p), ("loss", C.c_void_p), ("bn_batch", C.c_void_p),
-                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
-                ("global_batch", C.c_int64), ("sample_offset", C.c_int64),
-                ("dropout_p", C.c_float), ("seed", C.c_uint64), ("step", C.c_uint64),
-                ("bn_moment_weight", C.c_float), ("step_state", C.c_void_p), ("flags", C.c_uint32), ("aux_stream", C.c_void_p)]
+    _fields_ = _step_fields(after_loss=("bn_batch",), tail=_DROPOUT[:4] + [("bn_moment_weight", C.c_float), ("step_state", C.c_void_p), ("flags", C.c_uint32),
+                                                                         ("aux_stream", C.c_void_p)])
 
 
 class AdamArgs(C.Structure):
@@ -49,9 +58,7 @@ class StmsgcnShape(C.Structure):
 
 
 class StmsgcnArgs(C.Structure):
-    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("dpred", C.c_void_p), ("params", C.c_void_p),
-                ("grads", C.c_void_p), ("pred", C.c_void_p), ("loss", C.c_void_p), ("workspace", C.c_void_p),
-                ("workspace_bytes", C.c_size_t), ("global_batch", C.c_int64)]
+    _fields_ = _step_fields()
 
 
 class AstgcnnShape(C.Structure):
@@ -60,10 +67,7 @@ class AstgcnnShape(C.Structure):
 
 
 class AstgcnnArgs(C.Structure):
-    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("dpred", C.c_void_p), ("params", C.c_void_p), ("grads", C.c_void_p),
-                ("pred", C.c_void_p), ("loss", C.c_void_p), ("bn_stats", C.c_void_p), ("bn_batch", C.c_void_p),
-                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("global_batch", C.c_int64),
-                ("bn_moment_weight", C.c_float), ("training", C.c_int32), ("aux_stream", C.c_void_p)]
+    _fields_ = _step_fields(after_loss=("bn_stats", "bn_batch"), tail=[("bn_moment_weight", C.c_float), _TRAINING, ("aux_stream", C.c_void_p)])
 
 
 class StconvShape(C.Structure):
@@ -90,12 +94,8 @@ class FcstgnnShape(C.Structure):
 
 
 class FcstgnnArgs(C.Structure):
-    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("dpred", C.c_void_p), ("params", C.c_void_p), ("grads", C.c_void_p),
-                ("pred", C.c_void_p), ("loss", C.c_void_p), ("bn_stats", C.c_void_p), ("bn_batch", C.c_void_p),
-                ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t), ("global_batch", C.c_int64),
-                ("sample_offset", C.c_int64), ("bn_moment_weight", C.c_float), ("dropout_p", C.c_float),
-                ("seed", C.c_uint64), ("step", C.c_uint64), ("training", C.c_int32), ("step_state", C.c_void_p),
-                ("compute_dtype", C.c_int32), ("aux_stream", C.c_void_p)]
+    _fields_ = _step_fields(after_loss=("bn_stats", "bn_batch"), tail=[_DROPOUT[0], ("bn_moment_weight", C.c_float)] + _DROPOUT[1:] + [
+        ("step_state", C.c_void_p), ("compute_dtype", C.c_int32), ("aux_stream", C.c_void_p)])
 
 
 class StnetShape(C.Structure):
@@ -105,9 +105,7 @@ class StnetShape(C.Structure):
 
 
 class StnetArgs(C.Structure):
-    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("dpred", C.c_void_p), ("params", C.c_void_p), ("grads", C.c_void_p),
-                ("pred", C.c_void_p), ("recon", C.c_void_p), ("loss", C.c_void_p), ("workspace", C.c_void_p),
-                ("workspace_bytes", C.c_size_t), ("global_batch", C.c_int64), ("recon_weight", C.c_void_p)]
+    _fields_ = _step_fields(before_loss=("recon",), tail=[("recon_weight", C.c_void_p)])
 
 
 class SagcnShape(C.Structure):
@@ -116,9 +114,7 @@ class SagcnShape(C.Structure):
 
 
 class SagcnArgs(C.Structure):
-    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("dpred", C.c_void_p), ("params", C.c_void_p), ("grads", C.c_void_p),
-                ("pred", C.c_void_p), ("loss", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
-                ("global_batch", C.c_int64)]
+    _fields_ = _step_fields()
 
 
 class AgcntfShape(C.Structure):
@@ -136,10 +132,7 @@ class HiercorrpoolShape(C.Structure):
 
 
 class HiercorrpoolArgs(C.Structure):
-    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("dpred", C.c_void_p), ("params", C.c_void_p), ("grads", C.c_void_p),
-                ("pred", C.c_void_p), ("loss", C.c_void_p), ("bn_state", C.c_void_p), ("workspace", C.c_void_p),
-                ("workspace_bytes", C.c_size_t), ("global_batch", C.c_int64), ("sample_offset", C.c_int64), ("dropout_p", C.c_float),
-                ("seed", C.c_uint64), ("step", C.c_uint64), ("training", C.c_int32), ("update_running_stats", C.c_int32)]
+    _fields_ = _step_fields(after_loss=("bn_state",), tail=_DROPOUT + [("update_running_stats", C.c_int32)])
 
 
 class LogoShape(C.Structure):
@@ -147,10 +140,7 @@ class LogoShape(C.Structure):
 
 
 class LogoArgs(C.Structure):
-    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("dpred", C.c_void_p), ("params", C.c_void_p), ("grads", C.c_void_p),
-                ("pred", C.c_void_p), ("loss", C.c_void_p), ("loss_gl", C.c_void_p), ("workspace", C.c_void_p),
-                ("workspace_bytes", C.c_size_t), ("global_batch", C.c_int64), ("theta", C.c_float), ("gamma", C.c_float),
-                ("dropout_p", C.c_float), ("seed", C.c_uint64), ("step", C.c_uint64), ("training", C.c_int32)]
+    _fields_ = _step_fields(after_loss=("loss_gl",), tail=[("theta", C.c_float), ("gamma", C.c_float)] + _DROPOUT[1:])       # (no sample_offset)
 
 
 class HcpbShape(C.Structure):
@@ -170,10 +160,7 @@ class DvgtformerShape(C.Structure):
 
 
 class DvgtformerArgs(C.Structure):
-    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("dpred", C.c_void_p), ("params", C.c_void_p), ("grads", C.c_void_p),
-                ("pred", C.c_void_p), ("loss", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
-                ("global_batch", C.c_int64), ("sample_offset", C.c_int64), ("dropout_p", C.c_float), ("seed", C.c_uint64),
-                ("step", C.c_uint64), ("training", C.c_int32)]
+    _fields_ = _step_fields(tail=_DROPOUT)
 
 
 class GdagdlShape(C.Structure):
@@ -183,10 +170,7 @@ class GdagdlShape(C.Structure):
 
 
 class GdagdlArgs(C.Structure):
-    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("dpred", C.c_void_p), ("params", C.c_void_p), ("grads", C.c_void_p),
-                ("pred", C.c_void_p), ("recon", C.c_void_p), ("loss", C.c_void_p), ("workspace", C.c_void_p),
-                ("workspace_bytes", C.c_size_t), ("global_batch", C.c_int64), ("recon_weight", C.c_void_p), ("sample_offset", C.c_int64),
-                ("dropout_p", C.c_float), ("seed", C.c_uint64), ("step", C.c_uint64), ("training", C.c_int32)]
+    _fields_ = _step_fields(before_loss=("recon",), tail=[("recon_weight", C.c_void_p)] + _DROPOUT)
 
 
 class StfaShape(C.Structure):
@@ -195,10 +179,7 @@ class StfaShape(C.Structure):
 
 
 class StfaArgs(C.Structure):
-    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("dpred", C.c_void_p), ("params", C.c_void_p), ("grads", C.c_void_p),
-                ("pred", C.c_void_p), ("loss", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
-                ("global_batch", C.c_int64), ("sample_offset", C.c_int64), ("dropout_p", C.c_float), ("seed", C.c_uint64),
-                ("step", C.c_uint64), ("training", C.c_int32)]
+    _fields_ = _step_fields(tail=_DROPOUT)
 
 
 class GatlstmShape(C.Structure):
@@ -207,10 +188,7 @@ class GatlstmShape(C.Structure):
 
 
 class GatlstmArgs(C.Structure):
-    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("dpred", C.c_void_p), ("params", C.c_void_p), ("grads", C.c_void_p),
-                ("pred", C.c_void_p), ("loss", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
-                ("global_batch", C.c_int64), ("sample_offset", C.c_int64), ("dropout_p", C.c_float), ("seed", C.c_uint64),
-                ("step", C.c_uint64), ("training", C.c_int32)]
+    _fields_ = _step_fields(tail=_DROPOUT)
 
 
 class StagnnShape(C.Structure):
@@ -219,9 +197,7 @@ class StagnnShape(C.Structure):
 
 
 class StagnnArgs(C.Structure):
-    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("dpred", C.c_void_p), ("params", C.c_void_p), ("grads", C.c_void_p),
-                ("pred", C.c_void_p), ("loss", C.c_void_p), ("bn_state", C.c_void_p), ("workspace", C.c_void_p),
-                ("workspace_bytes", C.c_size_t), ("global_batch", C.c_int64), ("training", C.c_int32), ("update_running_stats", C.c_int32)]
+    _fields_ = _step_fields(after_loss=("bn_state",), tail=[_TRAINING, ("update_running_stats", C.c_int32)])
 
 
 class RgcnuShape(C.Structure):
@@ -230,10 +206,7 @@ class RgcnuShape(C.Structure):
 
 
 class RgcnuArgs(C.Structure):
-    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("dpred", C.c_void_p), ("params", C.c_void_p), ("grads", C.c_void_p),
-                ("pred", C.c_void_p), ("std_pred", C.c_void_p), ("loss", C.c_void_p), ("workspace", C.c_void_p),
-                ("workspace_bytes", C.c_size_t), ("global_batch", C.c_int64), ("sample_offset", C.c_int64), ("dropout_p", C.c_float),
-                ("seed", C.c_uint64), ("step", C.c_uint64), ("training", C.c_int32)]
+    _fields_ = _step_fields(before_loss=("std_pred",), tail=_DROPOUT)
 
 
 class GrucmShape(C.Structure):
@@ -241,10 +214,7 @@ class GrucmShape(C.Structure):
 
 
 class GrucmArgs(C.Structure):
-    _fields_ = [("x", C.c_void_p), ("y", C.c_void_p), ("dpred", C.c_void_p), ("params", C.c_void_p), ("grads", C.c_void_p),
-                ("pred", C.c_void_p), ("loss", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t),
-                ("global_batch", C.c_int64), ("sample_offset", C.c_int64), ("dropout_p", C.c_float * 3), ("seed", C.c_uint64),
-                ("step", C.c_uint64), ("training", C.c_int32), ("gru_path", C.c_int32)]
+    _fields_ = _step_fields(tail=[_DROPOUT[0], ("dropout_p", C.c_float * 3)] + _DROPOUT[2:] + [("gru_path", C.c_int32)])      # (a rate per dropout site)
 
 
 GRUCM_GRU_AUTO, GRUCM_GRU_STEP_LOOP, GRUCM_GRU_PERSISTENT = 0, 1, 2      # include/rulgnn.h RULGNN_GRUCM_GRU_*
@@ -423,16 +393,16 @@ _SIGNATURES = {
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
-# index -> ctypes mirror, in the order of the RULGNN_STRUCT_* constants of include/rulgnn.h (rulgnn_struct_size)
-STRUCTS = (StgcnShape, StgcnTrainArgs, AdamArgs, StmsgcnShape, StmsgcnArgs, AstgcnnShape, AstgcnnArgs, FcstgnnShape, FcstgnnArgs, RgcnuShape, RgcnuArgs, StnetShape, StnetArgs, SagcnShape, SagcnArgs, StagnnShape, StagnnArgs, HagcnShape, HagcnArgs, BilstmShape, BilstmArgs, StconvShape, StgnnShape, GruShape, GruArgs, GrucmShape, GrucmArgs, AgcntfShape, AgcntfArgs, HiercorrpoolShape, HiercorrpoolArgs, LogoShape, LogoArgs, DvgtformerShape, DvgtformerArgs, GdagdlShape, GdagdlArgs)
-# ... and the mirrors whose RULGNN_STRUCT_* constant is not a position of the tuple above (which ends where index 36 does)
-STRUCTS_AT = {38: GatlstmShape, 39: GatlstmArgs}
-# (STRUCTS_AT is GAT_LSTM's pair and tested as exactly that; families after it register here)
-STRUCTS_LATER = {41: LogobShape}
-# (STRUCTS_LATER is tested as exactly that too; 42 is unassigned)
-STRUCTS_HCPB = {43: HcpbShape}
-# (44 is unassigned)
-STRUCTS_STFA = {45: StfaShape, 46: StfaArgs}
+# RULGNN_STRUCT_* index of include/rulgnn.h (rulgnn_struct_size) -> ctypes mirror.  A new struct takes the next free index; the gaps
+# (37, 40, 42, 44) stay unassigned.
+STRUCTS = {
+    0: StgcnShape, 1: StgcnTrainArgs, 2: AdamArgs, 3: StmsgcnShape, 4: StmsgcnArgs, 5: AstgcnnShape, 6: AstgcnnArgs, 7: FcstgnnShape,
+    8: FcstgnnArgs, 9: RgcnuShape, 10: RgcnuArgs, 11: StnetShape, 12: StnetArgs, 13: SagcnShape, 14: SagcnArgs, 15: StagnnShape,
+    16: StagnnArgs, 17: HagcnShape, 18: HagcnArgs, 19: BilstmShape, 20: BilstmArgs, 21: StconvShape, 22: StgnnShape, 23: GruShape,
+    24: GruArgs, 25: GrucmShape, 26: GrucmArgs, 27: AgcntfShape, 28: AgcntfArgs, 29: HiercorrpoolShape, 30: HiercorrpoolArgs,
+    31: LogoShape, 32: LogoArgs, 33: DvgtformerShape, 34: DvgtformerArgs, 35: GdagdlShape, 36: GdagdlArgs, 38: GatlstmShape,
+    39: GatlstmArgs, 41: LogobShape, 43: HcpbShape, 45: StfaShape, 46: StfaArgs,
+}
 
 _lib = None
 
@@ -464,7 +434,7 @@ def load() -> C.CDLL:
         fn = getattr(lib, name)          # AttributeError if the .so is stale: loud by design
         fn.restype = res
         fn.argtypes = args
-    for which, mirror in list(enumerate(STRUCTS)) + sorted({**STRUCTS_AT, **STRUCTS_LATER, **STRUCTS_HCPB, **STRUCTS_STFA}.items()):       # a stale .so (or a stale binding) would read past the end of a shorter struct
+    for which, mirror in STRUCTS.items():       # a stale .so (or a stale binding) would read past the end of a shorter struct
         if lib.rulgnn_struct_size(which) != C.sizeof(mirror):
             raise RuntimeError(f"{LIB_PATH}: sizeof(struct #{which}) is {lib.rulgnn_struct_size(which)} in the library, {C.sizeof(mirror)} in "
                                f"this binding ({mirror.__name__}): rebuild with `python -m gnn_rul_benchmarking_amd.build --force`")

@@ -18,9 +18,6 @@ beyond that the reference's own CPU and GPU sorts disagree with each other on th
 """
 from __future__ import annotations
 
-import ctypes as C
-
-import torch
 import torch.nn as nn
 
 from . import _lib
@@ -82,13 +79,9 @@ class AGCN_TF_model(FlatModule):
     def tap(self, batch, which):
         """Workspace taps of the last forward at this batch size (parity tests): 'features' [B, P, 40], 'H' [B, N, Hg] (the 40 spatial
         rows first, as the reference concatenates), 'attention_out' [B, N, heads * Hg]; N = num_patch + 40."""
-        idx = {"features": 0, "H": 1, "attention_out": 2}[which]
-        shp = self._shape(batch)
-        off = _lib.load().rulgnn_agcntf_tap_offset(C.byref(shp), idx)
-        ws = self._bufs[batch][0].view(torch.float32)
-        rows, width = ((self.num_patch, 40), (self.num_patch + 40, self.hidden_gnn_dim),
-                       (self.num_patch + 40, self.num_heads * self.hidden_gnn_dim))[idx]
-        return ws[off:off + batch * rows * width].view(batch, rows, width).clone()
+        idx, shape = {"features": (0, (self.num_patch, 40)), "H": (1, (self.num_patch + 40, self.hidden_gnn_dim)),
+                      "attention_out": (2, (self.num_patch + 40, self.num_heads * self.hidden_gnn_dim))}[which]
+        return self._tap(batch, idx, (batch, *shape))
 
     # ---- nn.Module surface -----------------------------------------------------------------------------
     def forward(self, x):

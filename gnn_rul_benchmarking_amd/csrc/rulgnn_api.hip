@@ -120,6 +120,21 @@ static int step_fwdbwd(const typename F::Shape* shape, const typename F::Args* a
 }
 }  // extern "C++"
 
+// The extern "C" entries of step family F under the prefix rulgnn_<name>_ (include/rulgnn.h declares each): the two queries and the
+// three step calls, the fused one on the template `fwdbwd` (the BatchNorm families have their own below); _TAPS adds tap_offset.
+#define STEP_FAMILY_ENTRIES_ON(name, F, fwdbwd)                                                                                             \
+    int64_t rulgnn_##name##_param_count(const F::Shape* shape) { return F::param_count(shape); }                                            \
+    size_t rulgnn_##name##_workspace_bytes(const F::Shape* shape) { return F::workspace_bytes(shape); }                                     \
+    int rulgnn_##name##_forward_f32(const F::Shape* shape, const F::Args* args, void* stream) { return step_forward<F>(shape, args, stream); } \
+    int rulgnn_##name##_backward_f32(const F::Shape* shape, const F::Args* args, void* stream) { return step_backward<F>(shape, args, stream); } \
+    int rulgnn_##name##_fwdbwd_f32(const F::Shape* shape, const F::Args* args, const rulgnn_adam_args* opt, void* stream) {                 \
+        return fwdbwd<F>(shape, args, opt, stream);                                                                                         \
+    }
+#define STEP_FAMILY_ENTRIES(name, F) STEP_FAMILY_ENTRIES_ON(name, F, step_fwdbwd)
+#define STEP_FAMILY_ENTRIES_TAPS(name, F) \
+    STEP_FAMILY_ENTRIES(name, F)          \
+    int64_t rulgnn_##name##_tap_offset(const F::Shape* shape, int32_t which) { return F::tap_offset(shape, which); }
+
 // Path selection.  The fused row-mapped kernels cover num_patch <= 64 as long as one wavefront's input tile fits its LDS staging area,
 // every launch form a call may reach fits the 160 KB of LDS a workgroup can have (stgcn_host.hpp: the *_lds_bytes functions the
 // launchers size their launches with) and, for training, num_layers <= 3 / <= 2; everything else valid goes to the tiled path, which has
@@ -459,9 +474,6 @@ int rulgnn_bn_running_update_f32(float* bn_stats, const float* bn_batch, int32_t
 
 
 // ---- STMSGCN ------------------------------------------------------------------------------------------
-int64_t rulgnn_stmsgcn_param_count(const rulgnn_stmsgcn_shape* shape) { return Stmsgcn::param_count(shape); }
-size_t rulgnn_stmsgcn_workspace_bytes(const rulgnn_stmsgcn_shape* shape) { return Stmsgcn::workspace_bytes(shape); }
-
 int rulgnn_stmsgcn_features_f32(const rulgnn_stmsgcn_shape* shape, const float* x, const float* params, float* features,
                                 void* stream) {
     if (!shape) return RULGNN_EINVAL;
@@ -482,15 +494,7 @@ int Stmsgcn::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
     return check_ptrs({a->y, a->loss});
 }
 
-int rulgnn_stmsgcn_forward_f32(const rulgnn_stmsgcn_shape* shape, const rulgnn_stmsgcn_args* args, void* stream) {
-    return step_forward<Stmsgcn>(shape, args, stream);
-}
-int rulgnn_stmsgcn_backward_f32(const rulgnn_stmsgcn_shape* shape, const rulgnn_stmsgcn_args* args, void* stream) {
-    return step_backward<Stmsgcn>(shape, args, stream);
-}
-int rulgnn_stmsgcn_fwdbwd_f32(const rulgnn_stmsgcn_shape* shape, const rulgnn_stmsgcn_args* args, const rulgnn_adam_args* opt, void* stream) {
-    return step_fwdbwd<Stmsgcn>(shape, args, opt, stream);
-}
+STEP_FAMILY_ENTRIES(stmsgcn, Stmsgcn)
 
 // ---- the BatchNorm families: ASTGCNN, FC_STGNN, ST_Conv ---------------------------------------------------------------------------------
 // Their shared argument check (the args structs have these fields under the same names).  The shape is judged by run(), behind it.
@@ -560,21 +564,9 @@ static int check_bn_update(const void* shape, const float* bn_stats, const float
 }
 
 // ---- ASTGCNN ------------------------------------------------------------------------------------------
-int64_t rulgnn_astgcnn_param_count(const rulgnn_astgcnn_shape* shape) { return Astgcnn::param_count(shape); }
-size_t rulgnn_astgcnn_workspace_bytes(const rulgnn_astgcnn_shape* shape) { return Astgcnn::workspace_bytes(shape); }
-
 int Astgcnn::check_args(const Shape* shape, const Args* a, bool fwd, bool bwd) { return check_bn_args(shape->batch, a, fwd, bwd); }
 
-int rulgnn_astgcnn_forward_f32(const rulgnn_astgcnn_shape* shape, const rulgnn_astgcnn_args* args, void* stream) {
-    return step_forward<Astgcnn>(shape, args, stream);
-}
-int rulgnn_astgcnn_backward_f32(const rulgnn_astgcnn_shape* shape, const rulgnn_astgcnn_args* args, void* stream) {
-    return step_backward<Astgcnn>(shape, args, stream);
-}
-int rulgnn_astgcnn_fwdbwd_f32(const rulgnn_astgcnn_shape* shape, const rulgnn_astgcnn_args* args, const rulgnn_adam_args* opt,
-                              void* stream) {
-    return bn_step_fwdbwd<Astgcnn>(shape, args, opt, stream);
-}
+STEP_FAMILY_ENTRIES_ON(astgcnn, Astgcnn, bn_step_fwdbwd)
 int rulgnn_astgcnn_fwdbwd_syncbn_f32(const rulgnn_astgcnn_shape* shape, const rulgnn_astgcnn_args* args, float bn_param_grad_scale,
                                      rulgnn_allreduce_f64_fn allreduce, void* user, void* stream) {
     return bn_step_syncbn<Astgcnn>(shape, args, bn_param_grad_scale, allreduce, user, stream);
@@ -586,25 +578,14 @@ int rulgnn_astgcnn_bn_running_update_f32(const rulgnn_astgcnn_shape* shape, floa
 }
 
 // ---- FC_STGNN -----------------------------------------------------------------------------------------
-int64_t rulgnn_fcstgnn_param_count(const rulgnn_fcstgnn_shape* shape) { return Fcstgnn::param_count(shape); }
 int64_t rulgnn_fcstgnn_bn_count(const rulgnn_fcstgnn_shape* shape) { return Fcstgnn::bn_count(shape); }
-size_t rulgnn_fcstgnn_workspace_bytes(const rulgnn_fcstgnn_shape* shape) { return Fcstgnn::workspace_bytes(shape); }
 
 int Fcstgnn::check_args(const Shape* shape, const Args* a, bool fwd, bool bwd) {
     if (a->sample_offset < 0 || !(a->dropout_p >= 0.f && a->dropout_p < 1.f)) return RULGNN_EINVAL;
     return check_bn_args(shape->batch, a, fwd, bwd);
 }
 
-int rulgnn_fcstgnn_forward_f32(const rulgnn_fcstgnn_shape* shape, const rulgnn_fcstgnn_args* args, void* stream) {
-    return step_forward<Fcstgnn>(shape, args, stream);
-}
-int rulgnn_fcstgnn_backward_f32(const rulgnn_fcstgnn_shape* shape, const rulgnn_fcstgnn_args* args, void* stream) {
-    return step_backward<Fcstgnn>(shape, args, stream);
-}
-int rulgnn_fcstgnn_fwdbwd_f32(const rulgnn_fcstgnn_shape* shape, const rulgnn_fcstgnn_args* args, const rulgnn_adam_args* opt,
-                              void* stream) {
-    return bn_step_fwdbwd<Fcstgnn>(shape, args, opt, stream);
-}
+STEP_FAMILY_ENTRIES_ON(fcstgnn, Fcstgnn, bn_step_fwdbwd)
 int rulgnn_fcstgnn_fwdbwd_syncbn_f32(const rulgnn_fcstgnn_shape* shape, const rulgnn_fcstgnn_args* args, float bn_param_grad_scale,
                                      rulgnn_allreduce_f64_fn allreduce, void* user, void* stream) {
     return bn_step_syncbn<Fcstgnn>(shape, args, bn_param_grad_scale, allreduce, user, stream);
@@ -616,21 +597,9 @@ int rulgnn_fcstgnn_bn_running_update_f32(const rulgnn_fcstgnn_shape* shape, floa
 }
 
 // ---- ST_Conv ------------------------------------------------------------------------------------------
-int64_t rulgnn_stconv_param_count(const rulgnn_stconv_shape* shape) { return Stconv::param_count(shape); }
-size_t rulgnn_stconv_workspace_bytes(const rulgnn_stconv_shape* shape) { return Stconv::workspace_bytes(shape); }
-
 int Stconv::check_args(const Shape* shape, const Args* a, bool fwd, bool bwd) { return check_bn_args(shape->batch, a, fwd, bwd); }
 
-int rulgnn_stconv_forward_f32(const rulgnn_stconv_shape* shape, const rulgnn_astgcnn_args* args, void* stream) {
-    return step_forward<Stconv>(shape, args, stream);
-}
-int rulgnn_stconv_backward_f32(const rulgnn_stconv_shape* shape, const rulgnn_astgcnn_args* args, void* stream) {
-    return step_backward<Stconv>(shape, args, stream);
-}
-int rulgnn_stconv_fwdbwd_f32(const rulgnn_stconv_shape* shape, const rulgnn_astgcnn_args* args, const rulgnn_adam_args* opt,
-                             void* stream) {
-    return bn_step_fwdbwd<Stconv>(shape, args, opt, stream);
-}
+STEP_FAMILY_ENTRIES_ON(stconv, Stconv, bn_step_fwdbwd)
 int rulgnn_stconv_bn_running_update_f32(const rulgnn_stconv_shape* shape, float* bn_stats, const float* bn_batch, int64_t count,
                                         float momentum, int32_t from_moments, void* stream) {
     RULGNN_TRY(check_bn_update(shape, bn_stats, bn_batch, count));
@@ -755,63 +724,28 @@ int rulgnn_stgnn_fwdbwd_f32(const rulgnn_stgnn_shape* shape, const rulgnn_stmsgc
 }
 
 // ---- STNet ------------------------------------------------------------------------------------------
-int64_t rulgnn_stnet_param_count(const rulgnn_stnet_shape* shape) { return Stnet::param_count(shape); }
-size_t rulgnn_stnet_workspace_bytes(const rulgnn_stnet_shape* shape) { return Stnet::workspace_bytes(shape); }
-
 int Stnet::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
     RULGNN_TRY(shape_status(shape));
     return check_step_ptrs(a, shape->batch, bwd);
 }
 
-int rulgnn_stnet_forward_f32(const rulgnn_stnet_shape* shape, const rulgnn_stnet_args* args, void* stream) {
-    return step_forward<Stnet>(shape, args, stream);
-}
-int rulgnn_stnet_backward_f32(const rulgnn_stnet_shape* shape, const rulgnn_stnet_args* args, void* stream) {
-    return step_backward<Stnet>(shape, args, stream);
-}
-int rulgnn_stnet_fwdbwd_f32(const rulgnn_stnet_shape* shape, const rulgnn_stnet_args* args, const rulgnn_adam_args* opt, void* stream) {
-    return step_fwdbwd<Stnet>(shape, args, opt, stream);
-}
+STEP_FAMILY_ENTRIES(stnet, Stnet)
 
 // ---- SAGCN ------------------------------------------------------------------------------------------
-int64_t rulgnn_sagcn_param_count(const rulgnn_sagcn_shape* shape) { return Sagcn::param_count(shape); }
-size_t rulgnn_sagcn_workspace_bytes(const rulgnn_sagcn_shape* shape) { return Sagcn::workspace_bytes(shape); }
-int64_t rulgnn_sagcn_tap_offset(const rulgnn_sagcn_shape* shape, int32_t which) { return Sagcn::tap_offset(shape, which); }
-
 int Sagcn::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
     RULGNN_TRY(shape_status(shape));
     return check_step_ptrs(a, shape->batch, bwd);
 }
 
-int rulgnn_sagcn_forward_f32(const rulgnn_sagcn_shape* shape, const rulgnn_sagcn_args* args, void* stream) {
-    return step_forward<Sagcn>(shape, args, stream);
-}
-int rulgnn_sagcn_backward_f32(const rulgnn_sagcn_shape* shape, const rulgnn_sagcn_args* args, void* stream) {
-    return step_backward<Sagcn>(shape, args, stream);
-}
-int rulgnn_sagcn_fwdbwd_f32(const rulgnn_sagcn_shape* shape, const rulgnn_sagcn_args* args, const rulgnn_adam_args* opt, void* stream) {
-    return step_fwdbwd<Sagcn>(shape, args, opt, stream);
-}
+STEP_FAMILY_ENTRIES_TAPS(sagcn, Sagcn)
 
 // ---- AGCN_TF ------------------------------------------------------------------------------------------
-int64_t rulgnn_agcntf_param_count(const rulgnn_agcntf_shape* shape) { return Agcntf::param_count(shape); }
-size_t rulgnn_agcntf_workspace_bytes(const rulgnn_agcntf_shape* shape) { return Agcntf::workspace_bytes(shape); }
-int64_t rulgnn_agcntf_tap_offset(const rulgnn_agcntf_shape* shape, int32_t which) { return Agcntf::tap_offset(shape, which); }
-
 int Agcntf::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
     RULGNN_TRY(shape_status(shape));
     return check_step_ptrs(a, shape->batch, bwd);
 }
 
-int rulgnn_agcntf_forward_f32(const rulgnn_agcntf_shape* shape, const rulgnn_agcntf_args* args, void* stream) {
-    return step_forward<Agcntf>(shape, args, stream);
-}
-int rulgnn_agcntf_backward_f32(const rulgnn_agcntf_shape* shape, const rulgnn_agcntf_args* args, void* stream) {
-    return step_backward<Agcntf>(shape, args, stream);
-}
-int rulgnn_agcntf_fwdbwd_f32(const rulgnn_agcntf_shape* shape, const rulgnn_agcntf_args* args, const rulgnn_adam_args* opt, void* stream) {
-    return step_fwdbwd<Agcntf>(shape, args, opt, stream);
-}
+STEP_FAMILY_ENTRIES_TAPS(agcntf, Agcntf)
 
 int rulgnn_sgemm_mode(int32_t mode) {
     const int prev = sgemm_big_mode();
@@ -820,10 +754,7 @@ int rulgnn_sgemm_mode(int32_t mode) {
 }
 
 // ---- STAGNN ------------------------------------------------------------------------------------------
-int64_t rulgnn_stagnn_param_count(const rulgnn_stagnn_shape* shape) { return Stagnn::param_count(shape); }
 int64_t rulgnn_stagnn_bn_state_count(const rulgnn_stagnn_shape* shape) { return Stagnn::bn_state_count(shape); }
-size_t rulgnn_stagnn_workspace_bytes(const rulgnn_stagnn_shape* shape) { return Stagnn::workspace_bytes(shape); }
-int64_t rulgnn_stagnn_tap_offset(const rulgnn_stagnn_shape* shape, int32_t which) { return Stagnn::tap_offset(shape, which); }
 
 int Stagnn::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
     RULGNN_TRY(shape_status(shape));
@@ -832,15 +763,7 @@ int Stagnn::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
     return bwd && !a->training ? RULGNN_EINVAL : RULGNN_OK;                // (the same code as a batch without d pred or targets)
 }
 
-int rulgnn_stagnn_forward_f32(const rulgnn_stagnn_shape* shape, const rulgnn_stagnn_args* args, void* stream) {
-    return step_forward<Stagnn>(shape, args, stream);
-}
-int rulgnn_stagnn_backward_f32(const rulgnn_stagnn_shape* shape, const rulgnn_stagnn_args* args, void* stream) {
-    return step_backward<Stagnn>(shape, args, stream);
-}
-int rulgnn_stagnn_fwdbwd_f32(const rulgnn_stagnn_shape* shape, const rulgnn_stagnn_args* args, const rulgnn_adam_args* opt, void* stream) {
-    return step_fwdbwd<Stagnn>(shape, args, opt, stream);
-}
+STEP_FAMILY_ENTRIES_TAPS(stagnn, Stagnn)
 
 // ---- plain GEMM -------------------------------------------------------------------------------------------------------------------
 int rulgnn_sgemm_f32(const float* A, int64_t sAm, int64_t sAk, const float* B, int64_t sBn, int64_t sBk, float* C, int64_t ldc, int32_t M,
@@ -917,24 +840,13 @@ int rulgnn_sgemm_splitk_f32(const float* A, int64_t sAm, int64_t sAk, const floa
 }
 
 // ---- RGCNU ------------------------------------------------------------------------------------------
-int64_t rulgnn_rgcnu_param_count(const rulgnn_rgcnu_shape* shape) { return Rgcnu::param_count(shape); }
-size_t rulgnn_rgcnu_workspace_bytes(const rulgnn_rgcnu_shape* shape) { return Rgcnu::workspace_bytes(shape); }
-
 int Rgcnu::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
     RULGNN_TRY(shape_status(shape));
     if (!(a->dropout_p >= 0.f && a->dropout_p < 1.f)) return RULGNN_EINVAL;
     return check_step_ptrs(a, shape->batch, bwd);
 }
 
-int rulgnn_rgcnu_forward_f32(const rulgnn_rgcnu_shape* shape, const rulgnn_rgcnu_args* args, void* stream) {
-    return step_forward<Rgcnu>(shape, args, stream);
-}
-int rulgnn_rgcnu_backward_f32(const rulgnn_rgcnu_shape* shape, const rulgnn_rgcnu_args* args, void* stream) {
-    return step_backward<Rgcnu>(shape, args, stream);
-}
-int rulgnn_rgcnu_fwdbwd_f32(const rulgnn_rgcnu_shape* shape, const rulgnn_rgcnu_args* args, const rulgnn_adam_args* opt, void* stream) {
-    return step_fwdbwd<Rgcnu>(shape, args, opt, stream);
-}
+STEP_FAMILY_ENTRIES(rgcnu, Rgcnu)
 
 static int check_gru_fwd(const rulgnn_gru_shape* shape, const rulgnn_gru_args* a) {
     if (!shape || !a) return RULGNN_EINVAL;
@@ -973,9 +885,6 @@ int rulgnn_gru_persistent_backward_f32(const rulgnn_gru_shape* shape, const rulg
 }
 
 // ---- GRU_CM ------------------------------------------------------------------------------------------
-int64_t rulgnn_grucm_param_count(const rulgnn_grucm_shape* shape) { return Grucm::param_count(shape); }
-size_t rulgnn_grucm_workspace_bytes(const rulgnn_grucm_shape* shape) { return Grucm::workspace_bytes(shape); }
-
 int Grucm::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
     RULGNN_TRY(shape_status(shape));
     if (a->global_batch < shape->batch || a->sample_offset < 0) return RULGNN_EINVAL;
@@ -989,21 +898,10 @@ int Grucm::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
     return bwd ? check_bwd_ptrs(a, shape->batch) : RULGNN_OK;
 }
 
-int rulgnn_grucm_forward_f32(const rulgnn_grucm_shape* shape, const rulgnn_grucm_args* args, void* stream) {
-    return step_forward<Grucm>(shape, args, stream);
-}
-int rulgnn_grucm_backward_f32(const rulgnn_grucm_shape* shape, const rulgnn_grucm_args* args, void* stream) {
-    return step_backward<Grucm>(shape, args, stream);
-}
-int rulgnn_grucm_fwdbwd_f32(const rulgnn_grucm_shape* shape, const rulgnn_grucm_args* args, const rulgnn_adam_args* opt, void* stream) {
-    return step_fwdbwd<Grucm>(shape, args, opt, stream);
-}
+STEP_FAMILY_ENTRIES(grucm, Grucm)
 
 // ---- HierCorrPool ------------------------------------------------------------------------------------------
-int64_t rulgnn_hiercorrpool_param_count(const rulgnn_hiercorrpool_shape* shape) { return Hiercorrpool::param_count(shape); }
 int64_t rulgnn_hiercorrpool_bn_state_count(const rulgnn_hiercorrpool_shape* shape) { return Hiercorrpool::bn_state_count(shape); }
-size_t rulgnn_hiercorrpool_workspace_bytes(const rulgnn_hiercorrpool_shape* shape) { return Hiercorrpool::workspace_bytes(shape); }
-int64_t rulgnn_hiercorrpool_tap_offset(const rulgnn_hiercorrpool_shape* shape, int32_t which) { return Hiercorrpool::tap_offset(shape, which); }
 
 // (HierCorrPool_bearing takes the same argument struct)
 static int check_hiercorrpool_args(const rulgnn_hiercorrpool_args* a, int64_t batch, bool bwd) {
@@ -1019,42 +917,19 @@ int Hiercorrpool::check_args(const Shape* shape, const Args* a, bool, bool bwd) 
     return check_hiercorrpool_args(a, shape->batch, bwd);
 }
 
-int rulgnn_hiercorrpool_forward_f32(const rulgnn_hiercorrpool_shape* shape, const rulgnn_hiercorrpool_args* args, void* stream) {
-    return step_forward<Hiercorrpool>(shape, args, stream);
-}
-int rulgnn_hiercorrpool_backward_f32(const rulgnn_hiercorrpool_shape* shape, const rulgnn_hiercorrpool_args* args, void* stream) {
-    return step_backward<Hiercorrpool>(shape, args, stream);
-}
-int rulgnn_hiercorrpool_fwdbwd_f32(const rulgnn_hiercorrpool_shape* shape, const rulgnn_hiercorrpool_args* args, const rulgnn_adam_args* opt, void* stream) {
-    return step_fwdbwd<Hiercorrpool>(shape, args, opt, stream);
-}
+STEP_FAMILY_ENTRIES_TAPS(hiercorrpool, Hiercorrpool)
 
 // ---- HierCorrPool_bearing --------------------------------------------------------------------------
-int64_t rulgnn_hcpb_param_count(const rulgnn_hcpb_shape* shape) { return Hcpb::param_count(shape); }
 int64_t rulgnn_hcpb_bn_state_count(const rulgnn_hcpb_shape* shape) { return Hcpb::bn_state_count(shape); }
-size_t rulgnn_hcpb_workspace_bytes(const rulgnn_hcpb_shape* shape) { return Hcpb::workspace_bytes(shape); }
-int64_t rulgnn_hcpb_tap_offset(const rulgnn_hcpb_shape* shape, int32_t which) { return Hcpb::tap_offset(shape, which); }
 
 int Hcpb::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
     RULGNN_TRY(shape_status(shape));
     return check_hiercorrpool_args(a, shape->batch, bwd);
 }
 
-int rulgnn_hcpb_forward_f32(const rulgnn_hcpb_shape* shape, const rulgnn_hiercorrpool_args* args, void* stream) {
-    return step_forward<Hcpb>(shape, args, stream);
-}
-int rulgnn_hcpb_backward_f32(const rulgnn_hcpb_shape* shape, const rulgnn_hiercorrpool_args* args, void* stream) {
-    return step_backward<Hcpb>(shape, args, stream);
-}
-int rulgnn_hcpb_fwdbwd_f32(const rulgnn_hcpb_shape* shape, const rulgnn_hiercorrpool_args* args, const rulgnn_adam_args* opt, void* stream) {
-    return step_fwdbwd<Hcpb>(shape, args, opt, stream);
-}
+STEP_FAMILY_ENTRIES_TAPS(hcpb, Hcpb)
 
 // ---- LOGO ------------------------------------------------------------------------------------------
-int64_t rulgnn_logo_param_count(const rulgnn_logo_shape* shape) { return Logo::param_count(shape); }
-size_t rulgnn_logo_workspace_bytes(const rulgnn_logo_shape* shape) { return Logo::workspace_bytes(shape); }
-int64_t rulgnn_logo_tap_offset(const rulgnn_logo_shape* shape, int32_t which) { return Logo::tap_offset(shape, which); }
-
 // (LOGO_bearing takes the same argument struct)
 static int check_logo_args(const rulgnn_logo_args* a, int64_t batch, bool bwd) {
     if (a->global_batch < batch) return RULGNN_EINVAL;
@@ -1068,144 +943,63 @@ int Logo::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
     return check_logo_args(a, shape->batch, bwd);
 }
 
-int rulgnn_logo_forward_f32(const rulgnn_logo_shape* shape, const rulgnn_logo_args* args, void* stream) {
-    return step_forward<Logo>(shape, args, stream);
-}
-int rulgnn_logo_backward_f32(const rulgnn_logo_shape* shape, const rulgnn_logo_args* args, void* stream) {
-    return step_backward<Logo>(shape, args, stream);
-}
-int rulgnn_logo_fwdbwd_f32(const rulgnn_logo_shape* shape, const rulgnn_logo_args* args, const rulgnn_adam_args* opt, void* stream) {
-    return step_fwdbwd<Logo>(shape, args, opt, stream);
-}
+STEP_FAMILY_ENTRIES_TAPS(logo, Logo)
 
 // ---- LOGO_bearing ----------------------------------------------------------------------------------
-int64_t rulgnn_logob_param_count(const rulgnn_logob_shape* shape) { return Logob::param_count(shape); }
-size_t rulgnn_logob_workspace_bytes(const rulgnn_logob_shape* shape) { return Logob::workspace_bytes(shape); }
-int64_t rulgnn_logob_tap_offset(const rulgnn_logob_shape* shape, int32_t which) { return Logob::tap_offset(shape, which); }
-
 int Logob::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
     RULGNN_TRY(shape_status(shape));
     return check_logo_args(a, shape->batch, bwd);
 }
 
-int rulgnn_logob_forward_f32(const rulgnn_logob_shape* shape, const rulgnn_logo_args* args, void* stream) {
-    return step_forward<Logob>(shape, args, stream);
-}
-int rulgnn_logob_backward_f32(const rulgnn_logob_shape* shape, const rulgnn_logo_args* args, void* stream) {
-    return step_backward<Logob>(shape, args, stream);
-}
-int rulgnn_logob_fwdbwd_f32(const rulgnn_logob_shape* shape, const rulgnn_logo_args* args, const rulgnn_adam_args* opt, void* stream) {
-    return step_fwdbwd<Logob>(shape, args, opt, stream);
-}
+STEP_FAMILY_ENTRIES_TAPS(logob, Logob)
 
-// ---- DVGTformer ------------------------------------------------------------------------------------------
-int64_t rulgnn_dvgtformer_param_count(const rulgnn_dvgtformer_shape* shape) { return Dvgtformer::param_count(shape); }
-size_t rulgnn_dvgtformer_workspace_bytes(const rulgnn_dvgtformer_shape* shape) { return Dvgtformer::workspace_bytes(shape); }
-int64_t rulgnn_dvgtformer_tap_offset(const rulgnn_dvgtformer_shape* shape, int32_t which) { return Dvgtformer::tap_offset(shape, which); }
+// ---- DVGTformer, GDAGDL, GAT_LSTM, STFA: dropout drawn by sample index in the global batch ---------------------------------------------
+// What their entries refuse behind shape_status, in this order: a global batch below the batch or a negative sample offset, a rate
+// outside [0, 1) (EINVAL); a global batch whose last dropout counter passes 32 bits at `draws_per_sample` draws (EUNSUPPORTED; 0 draws:
+// the family's counter has no such bound); a misaligned optional pointer -- y, dpred, loss and the family's `more`; then the step's
+// pointers.
+extern "C++" {
+template <typename A>
+static int check_dropout_step_args(const A* a, int64_t batch, bool bwd, double draws_per_sample, std::initializer_list<const void*> more = {}) {
+    if (a->global_batch < batch || a->sample_offset < 0) return RULGNN_EINVAL;
+    if (!(a->dropout_p >= 0.f && a->dropout_p < 1.f)) return RULGNN_EINVAL;
+    if (((double)a->sample_offset + (double)batch) * draws_per_sample > 4294967296.0 || (double)a->global_batch * draws_per_sample > 4294967296.0)
+        return RULGNN_EUNSUPPORTED;
+    for (const void* p : {(const void*)a->y, (const void*)a->dpred, (const void*)a->loss})
+        if (!opt_aligned(p)) return RULGNN_EALIGN;
+    for (const void* p : more)
+        if (!opt_aligned(p)) return RULGNN_EALIGN;
+    return check_step_ptrs(a, batch, bwd);
+}
+}  // extern "C++"
 
+// (one mask per temporal block: no counter bound)
 int Dvgtformer::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
     RULGNN_TRY(shape_status(shape));
-    if (a->global_batch < shape->batch || a->sample_offset < 0) return RULGNN_EINVAL;
-    if (!(a->dropout_p >= 0.f && a->dropout_p < 1.f)) return RULGNN_EINVAL;
-    for (const void* p : {(const void*)a->y, (const void*)a->dpred, (const void*)a->loss})
-        if (!opt_aligned(p)) return RULGNN_EALIGN;
-    return check_step_ptrs(a, shape->batch, bwd);
+    return check_dropout_step_args(a, shape->batch, bwd, 0.0);
 }
+STEP_FAMILY_ENTRIES_TAPS(dvgtformer, Dvgtformer)
 
-int rulgnn_dvgtformer_forward_f32(const rulgnn_dvgtformer_shape* shape, const rulgnn_dvgtformer_args* args, void* stream) {
-    return step_forward<Dvgtformer>(shape, args, stream);
-}
-int rulgnn_dvgtformer_backward_f32(const rulgnn_dvgtformer_shape* shape, const rulgnn_dvgtformer_args* args, void* stream) {
-    return step_backward<Dvgtformer>(shape, args, stream);
-}
-int rulgnn_dvgtformer_fwdbwd_f32(const rulgnn_dvgtformer_shape* shape, const rulgnn_dvgtformer_args* args, const rulgnn_adam_args* opt,
-                                 void* stream) {
-    return step_fwdbwd<Dvgtformer>(shape, args, opt, stream);
-}
-
-// ---- GDAGDL ----------------------------------------------------------------------------------------------
-int64_t rulgnn_gdagdl_param_count(const rulgnn_gdagdl_shape* shape) { return Gdagdl::param_count(shape); }
-size_t rulgnn_gdagdl_workspace_bytes(const rulgnn_gdagdl_shape* shape) { return Gdagdl::workspace_bytes(shape); }
-int64_t rulgnn_gdagdl_tap_offset(const rulgnn_gdagdl_shape* shape, int32_t which) { return Gdagdl::tap_offset(shape, which); }
-
+// (a draw per attention entry)
 int Gdagdl::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
     RULGNN_TRY(shape_status(shape));
-    if (a->global_batch < shape->batch || a->sample_offset < 0) return RULGNN_EINVAL;
-    if (!(a->dropout_p >= 0.f && a->dropout_p < 1.f)) return RULGNN_EINVAL;
-    // the dropout counter of the global batch's last attention entry must fit 32 bits
-    const double entries = (double)shape->num_patch * shape->num_nodes * shape->num_nodes;
-    if (((double)a->sample_offset + (double)shape->batch) * entries > 4294967296.0 || (double)a->global_batch * entries > 4294967296.0)
-        return RULGNN_EUNSUPPORTED;
-    for (const void* p : {(const void*)a->y, (const void*)a->dpred, (const void*)a->loss, (const void*)a->recon, (const void*)a->recon_weight})
-        if (!opt_aligned(p)) return RULGNN_EALIGN;
-    return check_step_ptrs(a, shape->batch, bwd);
+    return check_dropout_step_args(a, shape->batch, bwd, (double)shape->num_patch * shape->num_nodes * shape->num_nodes, {a->recon, a->recon_weight});
 }
+STEP_FAMILY_ENTRIES_TAPS(gdagdl, Gdagdl)
 
-int rulgnn_gdagdl_forward_f32(const rulgnn_gdagdl_shape* shape, const rulgnn_gdagdl_args* args, void* stream) {
-    return step_forward<Gdagdl>(shape, args, stream);
-}
-int rulgnn_gdagdl_backward_f32(const rulgnn_gdagdl_shape* shape, const rulgnn_gdagdl_args* args, void* stream) {
-    return step_backward<Gdagdl>(shape, args, stream);
-}
-int rulgnn_gdagdl_fwdbwd_f32(const rulgnn_gdagdl_shape* shape, const rulgnn_gdagdl_args* args, const rulgnn_adam_args* opt, void* stream) {
-    return step_fwdbwd<Gdagdl>(shape, args, opt, stream);
-}
-
-// ---- GAT_LSTM --------------------------------------------------------------------------------------------
-int64_t rulgnn_gatlstm_param_count(const rulgnn_gatlstm_shape* shape) { return Gatlstm::param_count(shape); }
-size_t rulgnn_gatlstm_workspace_bytes(const rulgnn_gatlstm_shape* shape) { return Gatlstm::workspace_bytes(shape); }
-int64_t rulgnn_gatlstm_tap_offset(const rulgnn_gatlstm_shape* shape, int32_t which) { return Gatlstm::tap_offset(shape, which); }
-
+// (a draw per band entry)
 int Gatlstm::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
     RULGNN_TRY(shape_status(shape));
-    if (a->global_batch < shape->batch || a->sample_offset < 0) return RULGNN_EINVAL;
-    if (!(a->dropout_p >= 0.f && a->dropout_p < 1.f)) return RULGNN_EINVAL;
-    // the dropout counter of the global batch's last band entry must fit 32 bits
-    const double entries = 3.0 * (double)shape->num_patch;
-    if (((double)a->sample_offset + (double)shape->batch) * entries > 4294967296.0 || (double)a->global_batch * entries > 4294967296.0)
-        return RULGNN_EUNSUPPORTED;
-    for (const void* p : {(const void*)a->y, (const void*)a->dpred, (const void*)a->loss})
-        if (!opt_aligned(p)) return RULGNN_EALIGN;
-    return check_step_ptrs(a, shape->batch, bwd);
+    return check_dropout_step_args(a, shape->batch, bwd, 3.0 * (double)shape->num_patch);
 }
+STEP_FAMILY_ENTRIES_TAPS(gatlstm, Gatlstm)
 
-int rulgnn_gatlstm_forward_f32(const rulgnn_gatlstm_shape* shape, const rulgnn_gatlstm_args* args, void* stream) {
-    return step_forward<Gatlstm>(shape, args, stream);
-}
-int rulgnn_gatlstm_backward_f32(const rulgnn_gatlstm_shape* shape, const rulgnn_gatlstm_args* args, void* stream) {
-    return step_backward<Gatlstm>(shape, args, stream);
-}
-int rulgnn_gatlstm_fwdbwd_f32(const rulgnn_gatlstm_shape* shape, const rulgnn_gatlstm_args* args, const rulgnn_adam_args* opt, void* stream) {
-    return step_fwdbwd<Gatlstm>(shape, args, opt, stream);
-}
-
-// ---- STFA ------------------------------------------------------------------------------------------------
-int64_t rulgnn_stfa_param_count(const rulgnn_stfa_shape* shape) { return Stfa::param_count(shape); }
-size_t rulgnn_stfa_workspace_bytes(const rulgnn_stfa_shape* shape) { return Stfa::workspace_bytes(shape); }
-int64_t rulgnn_stfa_tap_offset(const rulgnn_stfa_shape* shape, int32_t which) { return Stfa::tap_offset(shape, which); }
-
+// (a draw per directed edge, head and patch)
 int Stfa::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
     RULGNN_TRY(shape_status(shape));
-    if (a->global_batch < shape->batch || a->sample_offset < 0) return RULGNN_EINVAL;
-    if (!(a->dropout_p >= 0.f && a->dropout_p < 1.f)) return RULGNN_EINVAL;
-    // the dropout counter of the global batch's last edge must fit 32 bits
-    const double entries = 44.0 * (double)shape->num_heads * (double)shape->num_patch;
-    if (((double)a->sample_offset + (double)shape->batch) * entries > 4294967296.0 || (double)a->global_batch * entries > 4294967296.0)
-        return RULGNN_EUNSUPPORTED;
-    for (const void* p : {(const void*)a->y, (const void*)a->dpred, (const void*)a->loss})
-        if (!opt_aligned(p)) return RULGNN_EALIGN;
-    return check_step_ptrs(a, shape->batch, bwd);
+    return check_dropout_step_args(a, shape->batch, bwd, 44.0 * (double)shape->num_heads * (double)shape->num_patch);
 }
-
-int rulgnn_stfa_forward_f32(const rulgnn_stfa_shape* shape, const rulgnn_stfa_args* args, void* stream) {
-    return step_forward<Stfa>(shape, args, stream);
-}
-int rulgnn_stfa_backward_f32(const rulgnn_stfa_shape* shape, const rulgnn_stfa_args* args, void* stream) {
-    return step_backward<Stfa>(shape, args, stream);
-}
-int rulgnn_stfa_fwdbwd_f32(const rulgnn_stfa_shape* shape, const rulgnn_stfa_args* args, const rulgnn_adam_args* opt, void* stream) {
-    return step_fwdbwd<Stfa>(shape, args, opt, stream);
-}
+STEP_FAMILY_ENTRIES_TAPS(stfa, Stfa)
 
 size_t rulgnn_rul_metrics_workspace_bytes(int64_t n) { return rul_metrics_workspace_bytes(n); }
 

@@ -26,7 +26,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .flat import FlatModule
+from .flat import DropoutStepModule
 
 # include/rulgnn.h RULGNN_DVGT_MAX_*
 LIMITS = {"max_nodes": 24, "max_time": 56, "max_heads": 8, "max_blocks": 8, "max_d_model": 1024, "max_d_ff": 128}
@@ -53,10 +53,7 @@ class _HalfBlock(nn.Module):
         setattr(self, "dropout1" if view == "temp" else "dropout2", nn.Dropout(dropout))
 
 
-class DVGTformer_model(FlatModule):
-    dropout_by_sample_offset = True          # dp.py: pass the shard's first global sample index to fused_mse_step
-    eval_sample_independent = True           # no BatchNorm, no recurrence: a test set may be re-batched per shard
-
+class DVGTformer_model(DropoutStepModule):
     def __init__(self, num_nodes, time_length, d_model, num_heads, lambda_param, d_ff, dropout, num_blocks):
         super().__init__()
         self.num_nodes, self.time_length, self.num_heads, self.num_blocks = int(num_nodes), int(time_length), int(num_heads), int(num_blocks)
@@ -73,11 +70,9 @@ class DVGTformer_model(FlatModule):
         self.svgtformer_blocks = nn.ModuleList([_HalfBlock(L + 1, self.d_model[1], self.num_heads, self.d_ff[1], dropout, "spat")
                                                 for _ in range(self.num_blocks)])
         self.output_layer = nn.Sequential(nn.Linear((L + 1) * (N + 1), 100), nn.GELU(), nn.Linear(100, 1))
-        self._seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
-        self._step = 0
         self._init_flat()
 
-    workspace_slots = 3
+    workspace_slots = 3          # (an empty batch gives an empty prediction: ``empty_batch`` stays None)
 
     # ---- C-ABI calls -----------------------------------------------------------------------------------
     c_family, Args = "dvgtformer", _lib.DvgtformerArgs
@@ -98,37 +93,7 @@ class DVGTformer_model(FlatModule):
             raise RuntimeError(self.not_covered)             # before the library is touched: nothing allocated, nothing launched
         return x.contiguous().float()
 
-    def _args(self, shp, x, training, step, y=None, dpred=None, global_batch=None, sample_offset=0):
-        """``training`` and ``step`` of a backward must be the forward's: it redraws the forward's dropout masks from them."""
-        a = super()._args(shp, x, y, dpred, global_batch)
-        a.sample_offset = int(sample_offset)
-        a.dropout_p = float(self.dropout_p)
-        a.seed, a.step = self._seed, int(step)
-        a.training = 1 if training else 0
-        return a
-
     def tap(self, batch, which):
         """Workspace taps of the last forward at this batch size (parity tests), both [batch, L+1, N+1]: 'x0' (X behind the input stage
         and the positional encoding), 'enc' (the encoder output, the head's input)."""
-        idx = {"x0": 0, "enc": 1}[which]
-        off = _lib.load().rulgnn_dvgtformer_tap_offset(C.byref(self._shape(batch)), idx)
-        ws = self._bufs[batch][0].view(torch.float32)
-        n = batch * (self.time_length + 1) * (self.num_nodes + 1)
-        return ws[off:off + n].view(batch, self.time_length + 1, self.num_nodes + 1).clone()
-
-    def fused_mse_step(self, x, y, optimizer=None, global_batch=None, sample_offset=0):
-        """forward (train mode) + MSE + backward (+ Adam when ``optimizer`` is a FusedAdam over this model) in one C call; fills
-        ``self.bucket`` = [grad | loss]; returns (pred [B], loss 0-d tensor) on the device, no host sync."""
-        x, yv = self._step_inputs(x, y)
-        self._step += 1
-        return self._fused_step(x, yv, optimizer, global_batch, True, self._step, sample_offset=sample_offset)
-
-    # ---- nn.Module surface -----------------------------------------------------------------------------
-    def forward(self, X):
-        """Dropout follows ``self.training``; through autograd when grad mode is on."""
-        x = self._check_input(X)
-        if x.size(0) == 0:
-            return torch.empty(0, 1, dtype=torch.float32, device=x.device)
-        if self.training:
-            self._step += 1
-        return self._predict(x, self.training, self._step, autograd=self._needs_grad())[0]
+        return self._tap(batch, {"x0": 0, "enc": 1}[which], (batch, self.time_length + 1, self.num_nodes + 1))

@@ -15,10 +15,12 @@ hipGraphs and the optimizer state point into the buffers).
 
 A family describes its C entries as data (``c_family``, ``Args``, ``not_covered``...) and keeps what is its own: ``_shape``, the shape
 check of ``_check_input``, the family fields of ``_args``, its BatchNorm running-statistics entry and the ``forward`` the reference
-pins."""
+pins.  ``DropoutStepModule`` (at the end) is the base of the families that draw dropout by sample index in the global batch: it holds
+their step counter, the dropout fields of ``_args``, ``fused_mse_step`` and the train / eval ``forward``."""
 from __future__ import annotations
 
 import ctypes as C
+import math
 from collections import OrderedDict
 
 import torch
@@ -360,6 +362,13 @@ class FlatModule(nn.Module):
         self._after_train_forward(x.size(0))
         return pred
 
+    def _tap(self, batch, index, shape):
+        """Tap ``index`` of the family's ``rulgnn_<c_family>_tap_offset`` in the workspace of the last forward at this batch size, as a new
+        tensor of ``shape`` (the layout the kernels wrote: ``shape`` says where the batch sits)."""
+        off = getattr(_lib.load(), f"rulgnn_{self.c_family}_tap_offset")(C.byref(self._shape(batch)), index)
+        ws = self._bufs[batch][0].view(torch.float32)
+        return ws[off:off + math.prod(shape)].view(shape).clone()
+
     def _needs_grad(self):
         return torch.is_grad_enabled() and any(p.requires_grad for p in self._named())
 
@@ -369,3 +378,51 @@ class FlatModule(nn.Module):
         if autograd:
             return _FlatFunction.apply(self, x, state, *self._named())
         return tuple(o.clone() for o in self._run_forward(x, *state))
+
+
+class DropoutStepModule(FlatModule):
+    """A family without a BatchNorm path of FlatModule's whose dropout masks come from the package's counter hash, keyed by
+    ``(seed, step, sample index in the global batch)``: the step counter, the five dropout fields of ``Args`` (``sample_offset``,
+    ``dropout_p``, ``seed``, ``step``, ``training``), the fused step and the train / eval ``forward``.  ``state`` of a call is
+    ``(training, step)``.  The family supplies ``dropout_p`` (what the struct's field takes: an attribute, or a property over the
+    modules that hold the rates) and ``empty_batch``."""
+    dropout_by_sample_offset = True          # dp.py: pass the shard's first global sample index to fused_mse_step
+    eval_sample_independent = True           # no BatchNorm, no recurrence along the batch: a test set may be re-batched per shard
+    empty_batch = None                       # RuntimeError text of a forward on an empty batch; None: it gives an empty prediction
+
+    def _init_flat(self, layout=None, count=None):
+        self._seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
+        self._step = 0
+        super()._init_flat(layout, count)
+
+    def _args(self, shp, x, training, step, y=None, dpred=None, global_batch=None, sample_offset=0):
+        """``training`` and ``step`` of a backward must be the forward's: it redraws the forward's dropout masks from them."""
+        a = super()._args(shp, x, y, dpred, global_batch)
+        a.sample_offset = int(sample_offset)
+        a.dropout_p = self.dropout_p
+        a.seed, a.step = self._seed, int(step)
+        a.training = 1 if training else 0
+        return a
+
+    def fused_mse_step(self, x, y, optimizer=None, global_batch=None, sample_offset=0, **fields):
+        """forward (train mode) + MSE + backward (+ Adam when ``optimizer`` is a FusedAdam over this model) in one C call; fills
+        ``self.bucket`` = [grad | loss]; returns (pred [B], loss 0-d tensor) on the device, no host sync.  ``fields`` go to the family's
+        ``_args``."""
+        x, yv = self._step_inputs(x, y)
+        vars(self)["_step"] = step = self._step + 1          # (past nn.Module.__setattr__, as in FlatModule._args)
+        return self._fused_step(x, yv, optimizer, global_batch, True, step, sample_offset=sample_offset, **fields)
+
+    def _forward_outputs(self, x):
+        """Every output of one forward; dropout follows ``self.training`` (a training forward advances the step), through autograd when
+        grad mode is on."""
+        x = self._check_input(x)
+        if x.size(0) == 0:
+            if self.empty_batch is None:
+                return (torch.empty(0, 1, dtype=torch.float32, device=x.device),)
+            raise RuntimeError(self.empty_batch)
+        if self.training:
+            self._step += 1
+        return self._predict(x, self.training, self._step, autograd=self._needs_grad())
+
+    def forward(self, x):
+        return self._forward_outputs(x)[0]

@@ -19,13 +19,10 @@ limits constructs and is refused at its first forward, before any launch.
 """
 from __future__ import annotations
 
-import ctypes as C
-
-import torch
 import torch.nn as nn
 
 from . import _lib
-from .flat import FlatModule
+from .flat import DropoutStepModule
 
 # include/rulgnn.h RULGNN_GATLSTM_*
 LIMITS = {"max_num_patch": 128, "min_patch_size": 4, "max_patch_size": 2048, "max_layers": 4, "max_width": 512, "max_lstm_layers": 3,
@@ -49,10 +46,7 @@ class GraphAttentionLayer(nn.Module):
         self.attention = nn.Linear(2 * out_features, 1)
 
 
-class GAT_LSTM_model(FlatModule):
-    dropout_by_sample_offset = True          # dp.py: pass the shard's first global sample index to fused_mse_step
-    eval_sample_independent = True           # no BatchNorm, no recurrence along the batch: a test set may be re-batched per shard
-
+class GAT_LSTM_model(DropoutStepModule):
     def __init__(self, num_patch, patch_size, hidden_dim, lstm_hidden_dim, dropout=0.1, alpha=0.1):
         super().__init__()
         self.num_patch, self.patch_size = int(num_patch), int(patch_size)
@@ -65,11 +59,10 @@ class GAT_LSTM_model(FlatModule):
         self.gat_layers = nn.ModuleList([GraphAttentionLayer(dims[i], dims[i + 1], dropout, alpha) for i in range(len(dims) - 1)])
         self.lstm_layers = nn.ModuleList([nn.LSTM(ldims[i], ldims[i + 1], num_layers=1, batch_first=True) for i in range(len(ldims) - 1)])
         self.fc = nn.Linear(ldims[-1] * self.num_patch, 1)
-        self._seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
-        self._step = 0
         self._init_flat()
 
     workspace_slots = 3
+    empty_batch = "GAT_LSTM_model: empty batch"
 
     # ---- C-ABI calls -----------------------------------------------------------------------------------
     c_family, Args = "gatlstm", _lib.GatlstmArgs
@@ -96,44 +89,10 @@ class GAT_LSTM_model(FlatModule):
             raise RuntimeError(self.not_covered)             # before the library is touched: nothing allocated, nothing launched
         return x.reshape(bs, self.num_patch * self.patch_size).contiguous().float()
 
-    def _args(self, shp, x, training, step, y=None, dpred=None, global_batch=None, sample_offset=0):
-        """``training`` and ``step`` of a backward must be the forward's: it redraws the forward's dropout masks from them."""
-        a = super()._args(shp, x, y, dpred, global_batch)
-        a.sample_offset = int(sample_offset)
-        a.dropout_p = float(self.dropout_p)
-        a.seed, a.step = self._seed, int(step)
-        a.training = 1 if training else 0
-        return a
-
     def tap(self, batch, which):
         """Workspace taps of the last forward at this batch size (parity tests): 'feat' [batch, T, 11], 'h{l}' (the output of GAT layer l)
         [batch, T, hidden_dim[l]], 'lstm' (the last LSTM layer's output) [batch, T, lstm_hidden_dim[-1]]."""
-        T = self.num_patch
-        if which == "feat":
-            idx, shape = 0, (batch, T, NUM_FEATURES)
-        elif which == "lstm":
-            idx, shape = 1 + LIMITS["max_layers"], (batch, T, self.lstm_hidden_dim[-1])       # RULGNN_GATLSTM_TAP_LSTM
-        else:
-            layer = int(which[1:])
-            idx, shape = 1 + layer, (batch, T, self.hidden_dim[layer])
-        off = _lib.load().rulgnn_gatlstm_tap_offset(C.byref(self._shape(batch)), idx)
-        ws = self._bufs[batch][0].view(torch.float32)
-        n = shape[0] * shape[1] * shape[2]
-        return ws[off:off + n].view(shape).clone()
-
-    def fused_mse_step(self, x, y, optimizer=None, global_batch=None, sample_offset=0):
-        """forward (train mode) + MSE + backward (+ Adam when ``optimizer`` is a FusedAdam over this model) in one C call; fills
-        ``self.bucket`` = [grad | loss]; returns (pred [B], loss 0-d tensor) on the device, no host sync."""
-        x, yv = self._step_inputs(x, y)
-        self._step += 1
-        return self._fused_step(x, yv, optimizer, global_batch, True, self._step, sample_offset=sample_offset)
-
-    # ---- nn.Module surface -----------------------------------------------------------------------------
-    def forward(self, x):
-        """Dropout follows ``self.training``; through autograd when grad mode is on."""
-        x2 = self._check_input(x)
-        if x2.size(0) == 0:
-            raise RuntimeError("GAT_LSTM_model: empty batch")
-        if self.training:
-            self._step += 1
-        return self._predict(x2, self.training, self._step, autograd=self._needs_grad())[0]
+        taps = {"feat": (0, NUM_FEATURES), "lstm": (1 + LIMITS["max_layers"], self.lstm_hidden_dim[-1]),       # RULGNN_GATLSTM_TAP_LSTM
+                **{f"h{l}": (1 + l, c) for l, c in enumerate(self.hidden_dim)}}
+        idx, width = taps[which]
+        return self._tap(batch, idx, (batch, self.num_patch, width))

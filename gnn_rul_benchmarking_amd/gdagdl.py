@@ -19,13 +19,10 @@ limits constructs and is refused at its first forward, before any launch.
 """
 from __future__ import annotations
 
-import ctypes as C
-
-import torch
 import torch.nn as nn
 
 from . import _lib
-from .flat import FlatModule
+from .flat import DropoutStepModule
 
 # include/rulgnn.h RULGNN_GDAGDL_MAX_*
 LIMITS = {"max_nperseg": 64, "max_frames": 64, "max_layers": 4, "max_width": 512, "max_lstm_hidden": 128, "max_ae_width": 1024}
@@ -49,10 +46,7 @@ class GraphAttentionLayer(nn.Module):
         self.attention = nn.Linear(2 * out_features, 1)
 
 
-class GDAGDL_model(FlatModule):
-    dropout_by_sample_offset = True          # dp.py: pass the shard's first global sample index to fused_mse_step
-    eval_sample_independent = True           # no BatchNorm, no recurrence along the batch: a test set may be re-batched per shard
-
+class GDAGDL_model(DropoutStepModule):
     def __init__(self, num_patch, patch_size, num_nodes, nperseg, input_dim, gat_layer_dim, lstm_hidden_dim, autoencoder_hidden_dim,
                  autoencoder_out_dim):
         super().__init__()
@@ -73,8 +67,6 @@ class GDAGDL_model(FlatModule):
                                      nn.Linear(A, D))
         self.lstm = nn.LSTM(input_size=O, hidden_size=self.lstm_hidden_dim, batch_first=True)
         self.linear = nn.Linear(self.lstm_hidden_dim * self.num_patch, 1)
-        self._seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
-        self._step = 0
         # flat layout: the two tensors without a gradient first (include/rulgnn.h), then the reference's order
         gradless = ["node_importance_linear.weight", "node_importance_linear.bias"]
         self.flat_order = gradless + [n for n, _ in self.named_parameters() if n not in gradless]
@@ -86,6 +78,7 @@ class GDAGDL_model(FlatModule):
     workspace_slots = 3
     # the reconstruction gradients are scaled in place by the backward: one backward per forward
     consumes_tape = True
+    empty_batch = "GDAGDL_model: empty batch"
 
     @property
     def bucket(self):
@@ -120,14 +113,9 @@ class GDAGDL_model(FlatModule):
         return x.reshape(bs, self.num_patch * self.patch_size).contiguous().float()
 
     def _args(self, shp, x, training, step, y=None, dpred=None, global_batch=None, sample_offset=0, recon_weight=None):
-        """``training`` and ``step`` of a backward must be the forward's: it redraws the forward's dropout masks from them."""
-        a = super()._args(shp, x, y, dpred, global_batch)
+        a = super()._args(shp, x, training, step, y, dpred, global_batch, sample_offset)
         a.recon = self._grad_flat.data_ptr() + 4 * (self._count + 1)
         a.recon_weight = recon_weight.data_ptr() if recon_weight is not None else None
-        a.sample_offset = int(sample_offset)
-        a.dropout_p = float(self.dropout_p)
-        a.seed, a.step = self._seed, int(step)
-        a.training = 1 if training else 0
         return a
 
     def _run_forward(self, x, *state):
@@ -146,28 +134,10 @@ class GDAGDL_model(FlatModule):
         T, N = self.num_patch, self.num_nodes
         idx, shape = {"mag": (0, (batch, T, N, self.input_dim)), "ni": (1, (batch, T, N)), "mask": (2, (batch, T, N)),
                       "yo": (3, (batch, T, N * self.gat_layer_dim[-1])), "H": (4, (batch, T, self.autoencoder_out_dim))}[which]
-        off = _lib.load().rulgnn_gdagdl_tap_offset(C.byref(self._shape(batch)), idx)
-        ws = self._bufs[batch][0].view(torch.float32)
-        n = 1
-        for v in shape:
-            n *= v
-        return ws[off:off + n].view(shape).clone()
-
-    def fused_mse_step(self, x, y, optimizer=None, global_batch=None, sample_offset=0):
-        """forward (train mode) + MSE + reconstruction + backward (+ Adam when ``optimizer`` is a FusedAdam over this model) in one C
-        call; fills ``self.bucket`` = [grad | loss]; returns (pred [B], loss 0-d tensor) on the device, no host sync."""
-        x, yv = self._step_inputs(x, y)
-        self._step += 1
-        return self._fused_step(x, yv, optimizer, global_batch, True, self._step, sample_offset=sample_offset)
+        return self._tap(batch, idx, shape)
 
     # ---- nn.Module surface -----------------------------------------------------------------------------
     def forward(self, x, train=False):
-        """Dropout follows ``self.training``; through autograd when grad mode is on.  ``train`` only selects the return value, as in the
-        reference."""
-        x2 = self._check_input(x)
-        if x2.size(0) == 0:
-            raise RuntimeError("GDAGDL_model: empty batch")
-        if self.training:
-            self._step += 1
-        pred, recon = self._predict(x2, self.training, self._step, autograd=self._needs_grad())
+        """``train`` only selects the return value, as in the reference."""
+        pred, recon = self._forward_outputs(x)
         return (pred, recon) if train else pred

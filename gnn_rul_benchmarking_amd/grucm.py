@@ -12,11 +12,10 @@ path: a non-CUDA input raises.
 """
 from __future__ import annotations
 
-import torch
 import torch.nn as nn
 
 from . import _lib
-from .flat import FlatModule
+from .flat import DropoutStepModule
 
 
 # ---- parameter holders: created in the reference's order so that a seed gives the reference's initial weights; never called ----
@@ -47,9 +46,7 @@ def param_layout(num_nodes, time_length, gru_hidden_dim):
     return layout, off
 
 
-class GRU_CM_model(FlatModule):
-    dropout_by_sample_offset = True          # dp.py: pass the shard's first global sample index to fused_mse_step
-
+class GRU_CM_model(DropoutStepModule):
     def __init__(self, time_length, num_nodes, gru_hidden_dim=128):
         super().__init__()
         self.time_length, self.num_nodes, self.gru_hidden_dim = int(time_length), int(num_nodes), int(gru_hidden_dim)
@@ -62,8 +59,6 @@ class GRU_CM_model(FlatModule):
         self.gru = nn.GRU(hidden_dim, self.gru_hidden_dim, batch_first=True)
         self.dropout3 = nn.Dropout(0.2)
         self.output_linear = nn.Linear(self.gru_hidden_dim * self.time_length, 1)
-        self._seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
-        self._step = 0
         self.gru_path = _lib.GRUCM_GRU_AUTO  # debugging / measurement: _lib.GRUCM_GRU_STEP_LOOP runs the recurrence on csrc/gru.hip
         if [n for n, _ in self.named_parameters()] != PARAM_ORDER:
             raise RuntimeError("parameter order differs from the flat layout of include/rulgnn.h")
@@ -71,6 +66,9 @@ class GRU_CM_model(FlatModule):
 
     flat_order = PARAM_ORDER
     workspace_slots = 4
+    # like the reference: reshape(0, -1) is ambiguous (Model.py:77)
+    empty_batch = ("cannot reshape tensor of 0 elements into shape [0, -1] because the unspecified dimension size -1 can be any value and is "
+                   "ambiguous")
 
     # ---- C-ABI calls -----------------------------------------------------------------------------------
     c_family, Args = "grucm", _lib.GrucmArgs
@@ -86,30 +84,12 @@ class GRU_CM_model(FlatModule):
         self._require_device(x)
         return x.contiguous().float()
 
+    @property
+    def dropout_p(self):           # read at every call: a rate per dropout site, held by the three nn.Dropout
+        mods = self._modules           # (nn.Module.__getattr__ costs half a microsecond a name)
+        return mods["dropout1"].p, mods["dropout2"].p, mods["dropout3"].p
+
     def _args(self, shp, x, training, step, y=None, dpred=None, global_batch=None, sample_offset=0):
-        """``training`` and ``step`` of a backward must be the forward's: it redraws the forward's dropout masks from them."""
-        a = super()._args(shp, x, y, dpred, global_batch)
-        a.sample_offset = int(sample_offset)
-        a.dropout_p[0], a.dropout_p[1], a.dropout_p[2] = float(self.dropout1.p), float(self.dropout2.p), float(self.dropout3.p)
-        a.seed, a.step = self._seed, int(step)
-        a.training = 1 if training else 0
+        a = super()._args(shp, x, training, step, y, dpred, global_batch, sample_offset)
         a.gru_path = int(self.gru_path)
         return a
-
-    def fused_mse_step(self, x, y, optimizer=None, global_batch=None, sample_offset=0):
-        """forward (train mode) + MSE + backward (+ Adam when ``optimizer`` is a FusedAdam over this model) in one C call; fills
-        ``self.bucket`` = [grad | loss]; returns (pred [B], loss 0-d tensor) on the device, no host sync."""
-        x, yv = self._step_inputs(x, y)
-        self._step += 1
-        return self._fused_step(x, yv, optimizer, global_batch, True, self._step, sample_offset=sample_offset)
-
-    # ---- nn.Module surface -----------------------------------------------------------------------------
-    def forward(self, x):
-        """Dropout follows ``self.training``; through autograd when grad mode is on."""
-        x = self._check_input(x)
-        if x.size(0) == 0:              # like the reference: reshape(0, -1) is ambiguous (Model.py:77)
-            raise RuntimeError("cannot reshape tensor of 0 elements into shape [0, -1] because the unspecified dimension size -1 can be "
-                               "any value and is ambiguous")
-        if self.training:
-            self._step += 1
-        return self._predict(x, self.training, self._step, autograd=self._needs_grad())[0]

@@ -17,13 +17,11 @@ output length); here such a configuration raises at construction and names both 
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 import torch.nn as nn
 
 from . import _lib
-from .flat import FlatModule
+from .flat import DropoutStepModule
 
 
 def encoder_lengths(num_patch):
@@ -70,7 +68,9 @@ class Graph_Classification_block(nn.Module):
 _BN_LAYERS = ("Time_Preprocessing.conv_block1.1", "Time_Preprocessing.conv_block2.1", "Time_Preprocessing.conv_block3.1")
 
 
-class HierCorrPool_model(FlatModule):
+class HierCorrPool_model(DropoutStepModule):
+    dropout_by_sample_offset = False         # data parallelism is refused (algorithms.py): dp.py has no sample offset to pass
+
     def __init__(self, patch_size, num_patch, input_dim, hidden_dim, embedding_dim, num_nodes, encoder_conv_kernel, num_nodes_out):
         super().__init__()
         self.patch_size, self.num_patch, self.input_dim = int(patch_size), int(num_patch), input_dim
@@ -89,8 +89,6 @@ class HierCorrPool_model(FlatModule):
         self.fc_0 = nn.Linear(K * M * e * 3, e * 3)
         self.fc_1 = nn.Linear(e * 3, 1)
         self.dropout_p = 0.35
-        self._seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
-        self._step = 0
         self._bn_channels = (h * N, 2 * h * N, 4 * h * N)
         self._bn = self._nbt = None
         self._track_batchnorm_counters()
@@ -129,13 +127,8 @@ class HierCorrPool_model(FlatModule):
         return x.contiguous().float()
 
     def _args(self, shp, x, training, step, y=None, dpred=None, global_batch=None, sample_offset=0, update_running_stats=True):
-        """``training`` and ``step`` of a backward must be the forward's: it redraws the forward's dropout mask from them."""
-        a = super()._args(shp, x, y, dpred, global_batch)
+        a = super()._args(shp, x, training, step, y, dpred, global_batch, sample_offset)
         a.bn_state = self._bn.data_ptr()
-        a.sample_offset = int(sample_offset)
-        a.dropout_p = float(self.dropout_p)
-        a.seed, a.step = self._seed, int(step)
-        a.training = 1 if training else 0
         a.update_running_stats = 1 if (training and update_running_stats and dpred is None) else 0      # (never in a backward)
         return a
 
@@ -145,20 +138,12 @@ class HierCorrPool_model(FlatModule):
         M, d = self.num_nodes_out, self.feature_dim
         idx, shape = {"encoder": (0, (self.encoder_out_length, 4 * self.hidden_dim * self.num_nodes)), "pooled_x": (1, (M, d)),
                       "pooled_adj": (2, (M, M)), "H": (3, (M, 3 * d))}[which]
-        return self._tap(batch, idx, shape)
-
-    def _tap(self, batch, idx, shape):
-        off = getattr(_lib.load(), f"rulgnn_{self.c_family}_tap_offset")(C.byref(self._shape(batch)), idx)
-        ws = self._bufs[batch][0].view(torch.float32)
-        return ws[off:off + batch * shape[0] * shape[1]].view(batch, *shape).clone()
+        return self._tap(batch, idx, (batch, *shape))
 
     def fused_mse_step(self, x, y, optimizer=None, global_batch=None, update_running_stats=True, sample_offset=0):
         """train-mode forward + MSE + backward (+ Adam when ``optimizer`` is a FusedAdam over this model) in one C call; fills
         ``self.bucket`` = [grad | loss]; returns (pred [B], loss 0-d tensor) on the device, no host sync."""
-        x, yv = self._step_inputs(x, y)
-        self._step += 1
-        out = self._fused_step(x, yv, optimizer, global_batch, True, self._step, sample_offset=sample_offset,
-                               update_running_stats=update_running_stats)
+        out = super().fused_mse_step(x, y, optimizer, global_batch, sample_offset, update_running_stats=update_running_stats)
         if update_running_stats:
             self._nbt_pending += 1
         return out

@@ -19,7 +19,6 @@ Coverage (stated once: ``LIMITS``, mirrored by include/rulgnn.h ``RULGNN_HCPB_MA
 """
 from __future__ import annotations
 
-import torch
 import torch.nn as nn
 
 from . import _lib
@@ -52,8 +51,6 @@ class HierCorrPool_bearing_model(HierCorrPool_model):
         self.fc_0 = nn.Linear(K * M * e * 3, e * 3)
         self.fc_1 = nn.Linear(e * 3, 1)
         self.dropout_p = 0.35
-        self._seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
-        self._step = 0
         self._bn_channels = (h * N, 2 * h * N, 4 * h * N)
         self._bn = self._nbt = None
         self._track_batchnorm_counters()
@@ -87,4 +84,4 @@ class HierCorrPool_bearing_model(HierCorrPool_model):
         spectrogram (channel ``n * input_dim + j`` = bin n, frame j) between four zero rows on each side."""
         if which != "stft":
             return super().tap(batch, which)
-        return self._tap(batch, 4, (self.num_patch + 8, self.num_nodes * self.input_dim))
+        return self._tap(batch, 4, (batch, self.num_patch + 8, self.num_nodes * self.input_dim))

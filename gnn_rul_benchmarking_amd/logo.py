@@ -19,7 +19,6 @@ Coverage (stated once: ``LIMITS``, mirrored by include/rulgnn.h): the reference'
 """
 from __future__ import annotations
 
-import ctypes as C
 from collections import OrderedDict
 
 import torch
@@ -138,14 +137,8 @@ class LOGO_model(FlatModule):
         """Workspace taps of the last forward at this batch size (parity tests): 'mpnn' [T N, B, 3p] (the graph stage's output, the
         LSTM stack's input), 'lstm' [T N, B, 3h] (the stack's output behind its closing leaky ReLU), 'gl' (L_GL, 0-d)."""
         Q, p3, H1 = self.num_patch * self.num_nodes, 3 * self._feature_width, 3 * self.hidden_dim
-        idx = {"mpnn": 0, "lstm": 1, "gl": 2}[which]
-        off = getattr(_lib.load(), f"rulgnn_{self.c_family}_tap_offset")(C.byref(self._shape(batch)), idx)
-        ws = self._bufs[batch][0].view(torch.float32)
-        if which == "mpnn":
-            return ws[off:off + Q * batch * p3].view(Q, batch, p3).clone()
-        if which == "lstm":          # kept as [B][T N][3h], the layout fc1 reads
-            return ws[off:off + batch * Q * H1].view(batch, Q, H1).permute(1, 0, 2).contiguous()
-        return ws[off].clone()
+        out = self._tap(batch, *{"mpnn": (0, (Q, batch, p3)), "lstm": (1, (batch, Q, H1)), "gl": (2, ())}[which])
+        return out.permute(1, 0, 2).contiguous() if which == "lstm" else out          # kept as [B][T N][3h], the layout fc1 reads
 
     def fused_mse_step(self, x, y, optimizer=None, global_batch=None, theta=0.0, gamma=1.0):
         """train-mode forward + MSE + ``theta`` * L_GL + backward (+ Adam when ``optimizer`` is a FusedAdam over this model) in one C

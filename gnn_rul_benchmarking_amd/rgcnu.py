@@ -13,11 +13,10 @@ cannot be reproduced by any other implementation).  There is no CPU path: a non-
 """
 from __future__ import annotations
 
-import torch
 import torch.nn as nn
 
 from . import _lib
-from .flat import FlatModule
+from .flat import DropoutStepModule
 
 SCL_DROPOUT = 0.5          # models/RGCNU/Model.py:31
 
@@ -69,8 +68,7 @@ PARAM_ORDER = ["adj.trainable_theta1.weight", "adj.trainable_theta1.bias", "adj.
                "fusion.fc1.weight", "fusion.fc1.bias", "fusion.fc2.weight", "fusion.fc2.bias"]
 
 
-class RGCNU_model(FlatModule):
-    dropout_by_sample_offset = True          # dp.py: pass the shard's first global sample index to fused_mse_step
+class RGCNU_model(DropoutStepModule):
     # graph (b, l) meets the adjacency of sample (b * T + l) % bs: the eval forward depends on WHICH samples share a batch, so a test
     # set must be walked in the reference's batches on every rank, never re-batched per shard (trainer.py / dataloader.data_generator)
     eval_sample_independent = False
@@ -84,8 +82,6 @@ class RGCNU_model(FlatModule):
         self.scl = SCL(self.hidden_dim)
         self.tdl = TDL(self.num_nodes, self.encoder_hidden_dim)
         self.fusion = FusionModule(self.num_nodes, self.encoder_hidden_dim, self.kernel_size, self.time_length)
-        self._seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
-        self._step = 0
         if [n for n, _ in self.named_parameters()] != PARAM_ORDER:
             raise RuntimeError("parameter order differs from the flat layout of include/rulgnn.h")
         self._init_flat()
@@ -96,6 +92,7 @@ class RGCNU_model(FlatModule):
     workspace_slots = 4
     output_buffers = 2         # prediction, std head
     consumes_tape = True       # the backward reworks the gate tape in place: one backward per forward
+    empty_batch = "RGCNU_model: empty batch"
 
     # ---- C-ABI calls -----------------------------------------------------------------------------------
     c_family, Args = "rgcnu", _lib.RgcnuArgs
@@ -111,31 +108,18 @@ class RGCNU_model(FlatModule):
         self._require_device(x)
         return x.contiguous().float()
 
-    def _args(self, shp, x, training, step, y=None, dpred=None, global_batch=None, sample_offset=0):
-        """``training`` and ``step`` of a backward must be the forward's: the dropout mask of rg_scl_bwd is applied only then."""
-        a = super()._args(shp, x, y, dpred, global_batch)
-        a.std_pred = self._out_bufs[1].data_ptr()
-        a.sample_offset = int(sample_offset)
-        a.dropout_p = float(self.scl.dropout.p)
-        a.seed, a.step = self._seed, int(step)
-        a.training = 1 if training else 0
-        return a
+    @property
+    def dropout_p(self):           # read at every call: SCL's nn.Dropout holds the rate
+        return float(self.scl.dropout.p)
 
-    def fused_mse_step(self, x, y, optimizer=None, global_batch=None, sample_offset=0):
-        """forward (train mode) + MSE of the first head + backward (+ Adam when ``optimizer`` is a FusedAdam over this model) in one C
-        call; fills ``self.bucket`` = [grad | loss]; returns (pred [B], loss 0-d tensor) on the device, no host sync."""
-        x, yv = self._step_inputs(x, y)
-        self._step += 1
-        return self._fused_step(x, yv, optimizer, global_batch, True, self._step, sample_offset=sample_offset)
+    def _args(self, shp, x, training, step, y=None, dpred=None, global_batch=None, sample_offset=0):
+        a = super()._args(shp, x, training, step, y, dpred, global_batch, sample_offset)
+        a.std_pred = self._out_bufs[1].data_ptr()
+        return a
 
     # ---- nn.Module surface -----------------------------------------------------------------------------
     def forward(self, X, train=False):
         """``train`` selects the return value like the reference (Model.py:115-118); dropout follows ``self.training``."""
-        x = self._check_input(X)
-        if x.size(0) == 0:
-            raise RuntimeError("RGCNU_model: empty batch")
-        if self.training:
-            self._step += 1
         # the second head is returned detached: its only consumer in the reference is a commented-out loss (algorithms.py:288)
-        pred, std = self._predict(x, self.training, self._step, autograd=self._needs_grad())
+        pred, std = self._forward_outputs(X)
         return (pred, std.detach()) if train else pred

@@ -15,9 +15,6 @@ Condition_1 row) -- beyond that the reference's own CPU and GPU sorts disagree w
 """
 from __future__ import annotations
 
-import ctypes as C
-
-import torch
 import torch.nn as nn
 
 from . import _lib
@@ -75,15 +72,11 @@ class SAGCN_model(FlatModule):
     def tap(self, batch, which):
         """Workspace taps of the last forward at this batch size (parity tests): 'features' [B, P, 40], 'aggregated' (A_hat X), 'h3',
         'attention' -- the last three returned sample-major [B, P, .] (they are stored node-major)."""
-        idx = {"features": 0, "aggregated": 1, "h3": 2, "attention": 3}[which]
-        shp = self._shape(batch)
-        off = _lib.load().rulgnn_sagcn_tap_offset(C.byref(shp), idx)
-        ws = self._bufs[batch][0].view(torch.float32)
         P = self.num_patch
-        if idx == 0:
-            return ws[off:off + batch * P * 40].view(batch, P, 40).clone()
-        w = 40 if idx == 1 else self.gcn_hidden_dim
-        return ws[off:off + batch * P * w].view(P, batch, w).permute(1, 0, 2).contiguous()
+        if which == "features":
+            return self._tap(batch, 0, (batch, P, 40))
+        idx, width = {"aggregated": (1, 40), "h3": (2, self.gcn_hidden_dim), "attention": (3, self.gcn_hidden_dim)}[which]
+        return self._tap(batch, idx, (P, batch, width)).permute(1, 0, 2).contiguous()
 
     # ---- nn.Module surface -----------------------------------------------------------------------------
     def forward(self, x):

@@ -12,8 +12,6 @@ Data parallelism shards the batch with rank-local BatchNorm statistics (what tor
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 import torch.nn as nn
 from torch.nn.utils import weight_norm
@@ -164,9 +162,7 @@ class STAGNN_model(FlatModule):
         idx, shape = {"adjacency": (0, (self.num_nodes, self.num_nodes)), "graph": (1, (self.num_nodes, self.hidden_dim)),
                       "tcn1": (2, (self.hidden_dim, self.hidden_dim)), "encoder1": (3, (self.hidden_dim, self.hidden_dim)),
                       "tcn2": (4, (self.output_dim, self.hidden_dim)), "encoder2": (5, (self.output_dim, self.hidden_dim))}[which]
-        off = _lib.load().rulgnn_stagnn_tap_offset(C.byref(self._shape(batch)), idx)
-        ws = self._bufs[batch][0].view(torch.float32)
-        return ws[off:off + batch * shape[0] * shape[1]].view(batch, *shape).clone()
+        return self._tap(batch, idx, (batch, *shape))
 
     def fused_mse_step(self, x, y, optimizer=None, global_batch=None, update_running_stats=True):
         """train-mode forward + MSE + backward (+ Adam when ``optimizer`` is a FusedAdam over this model) in one C call; fills

@@ -28,13 +28,10 @@ constructs and is refused at its first forward, before any launch or allocation.
 """
 from __future__ import annotations
 
-import ctypes as C
-
-import torch
 import torch.nn as nn
 
 from . import _lib
-from .flat import FlatModule
+from .flat import DropoutStepModule
 
 # include/rulgnn.h RULGNN_STFA_*
 LIMITS = {"num_nodes": 14, "max_num_patch": 128, "max_patch_size": 64, "max_output_dim": 16, "max_heads": 16, "max_lstm_hidden": 128}
@@ -67,10 +64,7 @@ class GAT(nn.Module):
             self.add_module('attention_{}'.format(i), GraphAttentionLayer(nfeat, nout, dropout=dropout))
 
 
-class STFA_model(FlatModule):
-    dropout_by_sample_offset = True          # dp.py: pass the shard's first global sample index to fused_mse_step
-    eval_sample_independent = True           # no BatchNorm, no recurrence along the batch: a test set may be re-batched per shard
-
+class STFA_model(DropoutStepModule):
     def __init__(self, patch_size, num_patch, num_nodes, hidden_dim, output_dim, encoder_hidden_dim, device=None, num_heads=1, dropout=0.0):
         super().__init__()
         self.patch_size, self.num_patch, self.num_nodes = int(patch_size), int(num_patch), int(num_nodes)
@@ -81,11 +75,10 @@ class STFA_model(FlatModule):
         self.v = nn.Linear(self.output_dim * self.num_nodes, 1)
         self.lstm = nn.LSTM(self.output_dim * self.num_nodes + self.num_patch, self.encoder_hidden_dim, batch_first=True)
         self.fc = nn.Linear(self.encoder_hidden_dim, 1)
-        self._seed = int(torch.initial_seed()) & 0xFFFFFFFFFFFFFFFF
-        self._step = 0
         self._init_flat()
 
     workspace_slots = 3
+    empty_batch = "STFA_model: empty batch"
 
     # ---- C-ABI calls -----------------------------------------------------------------------------------
     c_family, Args = "stfa", _lib.StfaArgs
@@ -108,40 +101,10 @@ class STFA_model(FlatModule):
             raise RuntimeError(self.not_covered)             # before the library is touched: nothing allocated, nothing launched
         return x.reshape(bs, self.num_nodes * self.num_patch * self.patch_size).contiguous().float()
 
-    def _args(self, shp, x, training, step, y=None, dpred=None, global_batch=None, sample_offset=0):
-        """``training`` and ``step`` of a backward must be the forward's: it redraws the forward's dropout masks from them."""
-        a = super()._args(shp, x, y, dpred, global_batch)
-        a.sample_offset = int(sample_offset)
-        a.dropout_p = float(self.dropout_p)
-        a.seed, a.step = self._seed, int(step)
-        a.training = 1 if training else 0
-        return a
-
     def tap(self, batch, which):
         """Workspace taps of the last forward at this batch size (parity tests): 'gat' (the stage output, relu of the heads' mean)
         [batch, T, 14 * output_dim], 'rows' (the LSTM's input: T ones, then 'gat') [batch, T, T + 14 * output_dim], 'lstm' (the LSTM's
         output) [batch, T, encoder_hidden_dim]."""
-        T, F = self.num_patch, self.num_nodes * self.output_dim
-        idx, shape = (TAP_LSTM, (batch, T, self.encoder_hidden_dim)) if which == "lstm" else (TAP_ROWS, (batch, T, T + F))
-        off = _lib.load().rulgnn_stfa_tap_offset(C.byref(self._shape(batch)), idx)
-        ws = self._bufs[batch][0].view(torch.float32)
-        n = shape[0] * shape[1] * shape[2]
-        out = ws[off:off + n].view(shape)
-        return (out[:, :, T:] if which == "gat" else out).clone()
-
-    def fused_mse_step(self, x, y, optimizer=None, global_batch=None, sample_offset=0):
-        """forward (train mode) + MSE + backward (+ Adam when ``optimizer`` is a FusedAdam over this model) in one C call; fills
-        ``self.bucket`` = [grad | loss]; returns (pred [B], loss 0-d tensor) on the device, no host sync."""
-        x, yv = self._step_inputs(x, y)
-        self._step += 1
-        return self._fused_step(x, yv, optimizer, global_batch, True, self._step, sample_offset=sample_offset)
-
-    # ---- nn.Module surface -----------------------------------------------------------------------------
-    def forward(self, x):
-        """Dropout follows ``self.training``; through autograd when grad mode is on."""
-        x2 = self._check_input(x)
-        if x2.size(0) == 0:
-            raise RuntimeError("STFA_model: empty batch")
-        if self.training:
-            self._step += 1
-        return self._predict(x2, self.training, self._step, autograd=self._needs_grad())[0]
+        T, rows = self.num_patch, (TAP_ROWS, (batch, self.num_patch, self.num_patch + self.num_nodes * self.output_dim))
+        out = self._tap(batch, *{"gat": rows, "rows": rows, "lstm": (TAP_LSTM, (batch, T, self.encoder_hidden_dim))}[which])
+        return out[:, :, T:].clone() if which == "gat" else out

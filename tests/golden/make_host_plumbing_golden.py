@@ -60,6 +60,50 @@ def _plain(cls, *fields):
     return lambda batch: cls(batch, *fields)
 
 
+def _dvgt(nodes, time, d_model, heads, d_ff, blocks, lam=0.5):
+    return lambda batch: L.DvgtformerShape(batch, nodes, time, heads, blocks, (C.c_int32 * 2)(*d_model), (C.c_int32 * 2)(*d_ff), lam)
+
+
+def _gdagdl(num_patch, patch_size, nperseg, gat, lstm, ae, ae_out, nodes=None, input_dim=None, num_gat=None):
+    """num_nodes and input_dim as the STFT gives them unless stated."""
+    def make(batch):
+        s = L.GdagdlShape()
+        s.batch, s.num_patch, s.patch_size, s.nperseg = batch, num_patch, patch_size, nperseg
+        s.num_nodes = nperseg // 2 + 1 if nodes is None else nodes
+        s.input_dim = 1 + patch_size // nperseg if input_dim is None else input_dim
+        s.num_gat = len(gat) if num_gat is None else num_gat
+        for i, c in enumerate(gat[:4]):
+            s.gat_layer_dim[i] = c
+        s.lstm_hidden_dim, s.autoencoder_hidden_dim, s.autoencoder_out_dim = lstm, ae, ae_out
+        return s
+    return make
+
+
+def _gatlstm(num_patch, patch_size, hidden, lstm, num_gat=None, num_lstm=None):
+    def make(batch):
+        s = L.GatlstmShape()
+        s.batch, s.num_patch, s.patch_size = batch, num_patch, patch_size
+        s.num_gat, s.num_lstm = len(hidden) if num_gat is None else num_gat, len(lstm) if num_lstm is None else num_lstm
+        for i, c in enumerate(hidden[:4]):
+            s.hidden_dim[i] = c
+        for i, e in enumerate(lstm[:3]):
+            s.lstm_hidden_dim[i] = e
+        return s
+    return make
+
+
+def _logob(patch_size, num_patch, nperseg, hidden):
+    return _plain(L.LogobShape, patch_size, num_patch, 1 + patch_size // nperseg, nperseg // 2 + 1, nperseg, hidden)
+
+
+def _hcpb(patch_size, num_patch, nperseg, hidden, embedding, conv_kernel, nodes_out):
+    return _plain(L.HcpbShape, patch_size, num_patch, 1 + patch_size // nperseg, hidden, embedding, nperseg // 2 + 1, nperseg, conv_kernel, nodes_out)
+
+
+_GD_SMALL, _GD_ROW = ([5, 4, 3], 3, 8, 4), ([300, 150, 50], 20, 256, 50)         # (gat_layer_dim, lstm, autoencoder hidden, out)
+_GL_SMALL, _GL_ROW = ([5, 4, 3], [3, 2]), ([300, 200, 100], [30, 20])             # (hidden_dim, lstm_hidden_dim)
+_DV_SMALL, _DV_ROW = ([3, 5], 1, [2, 3], 1), ([144, 248], 4, [72, 124], 3)          # (d_model, num_heads, d_ff, num_blocks)
+
 _FC_ROWS = {"fd001": (25, 2, 27, 8, 32, 2, 8, 6, 14, 2), "fd002": (1, 50, 3, 8, 12, 2, 8, 10, 14, 74), "fd003": (1, 50, 3, 8, 6, 2, 24, 25, 14, 74),
             "fd004": (2, 25, 4, 8, 6, 2, 8, 10, 14, 36), "ncmapss": (2, 25, 4, 8, 32, 2, 8, 6, 20, 36), "fd003like_6p": (1, 6, 3, 8, 6, 2, 24, 25, 14, 8)}
 
@@ -133,6 +177,83 @@ FAMILIES = {
         # 6 * hidden_dim on either side of the limit of 128 (126 and 132), num_nodes at the limit of 32 and beyond it
         "h21": (_plain(L.LogoShape, 2, 2, 3, 21), ()), "h22": (_plain(L.LogoShape, 2, 2, 3, 22), ()),
         "nodes32": (_plain(L.LogoShape, 2, 2, 32, 1), ()), "nodes33": (_plain(L.LogoShape, 2, 2, 33, 1), ())}),
+    # RULGNN_DVGT_MAX_*: each limit and one past it, on the small fixture; num_nodes below its minimum of 2; lambda_param outside [0, 1]
+    "dvgtformer": (("param_count", "workspace_bytes"), {
+        "small_3x4_h1_b1": (_dvgt(3, 4, *_DV_SMALL), (3,)), "small_5x7_h2_b2": (_dvgt(5, 7, [6, 10], 2, [4, 6], 2), (4, 8)),
+        "row_fd": (_dvgt(14, 50, *_DV_ROW), (3,)), "row_ncmapss": (_dvgt(20, 50, *_DV_ROW), (3,)),
+        "nodes24": (_dvgt(24, 4, *_DV_SMALL), ()), "nodes25": (_dvgt(25, 4, *_DV_SMALL), ()), "nodes1": (_dvgt(1, 4, *_DV_SMALL), ()),
+        "time56": (_dvgt(3, 56, *_DV_SMALL), ()), "time57": (_dvgt(3, 57, *_DV_SMALL), ()),
+        "heads8": (_dvgt(3, 4, [3, 5], 8, [2, 3], 1), ()), "heads9": (_dvgt(3, 4, [3, 5], 9, [2, 3], 1), ()),
+        "blocks8": (_dvgt(3, 4, [3, 5], 1, [2, 3], 8), ()), "blocks9": (_dvgt(3, 4, [3, 5], 1, [2, 3], 9), ()),
+        "d_model1024": (_dvgt(3, 4, [1024, 1024], 1, [2, 3], 1), ()), "d_model1025_temp": (_dvgt(3, 4, [1025, 5], 1, [2, 3], 1), ()),
+        "d_model1025_spat": (_dvgt(3, 4, [3, 1025], 1, [2, 3], 1), ()),
+        "d_ff128": (_dvgt(3, 4, [3, 5], 1, [128, 128], 1), ()), "d_ff129_temp": (_dvgt(3, 4, [3, 5], 1, [129, 3], 1), ()),
+        "d_ff129_spat": (_dvgt(3, 4, [3, 5], 1, [2, 129], 1), ()),
+        "lambda0": (_dvgt(3, 4, *_DV_SMALL, lam=0.0), ()), "lambda1": (_dvgt(3, 4, *_DV_SMALL, lam=1.0), ()), "lambda1_5": (_dvgt(3, 4, *_DV_SMALL, lam=1.5), ()),
+        "nodes24_time56_row_widths": (_dvgt(24, 56, *_DV_ROW), ())}),
+    # RULGNN_GDAGDL_MAX_*: (num_patch, patch_size, nperseg, gat_layer_dim, lstm, autoencoder hidden, out)
+    "gdagdl": (("param_count", "workspace_bytes"), {
+        "small_n3_t3": (_gdagdl(3, 8, 4, *_GD_SMALL), (4,)), "small_n5_t2": (_gdagdl(2, 32, 8, [7, 6, 5], 3, 8, 4), (3, 8)),
+        "row_phm_c1": (_gdagdl(128, 20, 4, *_GD_ROW), (2,)), "row_phm_c3": (_gdagdl(80, 32, 8, *_GD_ROW), (2,)), "row_xjtu": (_gdagdl(32, 1024, 32, *_GD_ROW), (2,)),
+        "nperseg64": (_gdagdl(3, 64, 64, *_GD_SMALL), ()), "nperseg66": (_gdagdl(3, 66, 66, *_GD_SMALL), ()), "nperseg5": (_gdagdl(3, 10, 5, *_GD_SMALL), ()),
+        "patch_not_a_multiple": (_gdagdl(3, 10, 4, *_GD_SMALL), ()), "patch_half_nperseg": (_gdagdl(3, 2, 4, *_GD_SMALL), ()),
+        "frames64": (_gdagdl(3, 126, 2, *_GD_SMALL), ()), "frames65": (_gdagdl(3, 128, 2, *_GD_SMALL), ()),
+        "nodes_not_the_stfts": (_gdagdl(3, 8, 4, *_GD_SMALL, nodes=4), ()), "input_dim_not_the_stfts": (_gdagdl(3, 8, 4, *_GD_SMALL, input_dim=4), ()),
+        "layers4": (_gdagdl(3, 8, 4, [5, 4, 3, 2], 3, 8, 4), ()), "layers5": (_gdagdl(3, 8, 4, [5, 4, 3, 2], 3, 8, 4, num_gat=5), ()),
+        "layers0": (_gdagdl(3, 8, 4, [], 3, 8, 4), ()),
+        "width512": (_gdagdl(3, 8, 4, [512, 512], 3, 8, 4), ()), "width513": (_gdagdl(3, 8, 4, [5, 513], 3, 8, 4), ()),
+        "lstm128": (_gdagdl(3, 8, 4, [5, 4, 3], 128, 8, 4), ()), "lstm129": (_gdagdl(3, 8, 4, [5, 4, 3], 129, 8, 4), ()),
+        "ae1024": (_gdagdl(3, 8, 4, [5, 4, 3], 3, 1024, 1024), ()), "ae_hidden1025": (_gdagdl(3, 8, 4, [5, 4, 3], 3, 1025, 4), ()),
+        "ae_out1025": (_gdagdl(3, 8, 4, [5, 4, 3], 3, 8, 1025), ()), "ae_hidden3": (_gdagdl(3, 8, 4, [5, 4, 3], 3, 3, 4), ())}),
+    # RULGNN_GATLSTM_*: (num_patch, patch_size, hidden_dim, lstm_hidden_dim)
+    "gatlstm": (("param_count", "workspace_bytes"), {
+        "small_t3_p4": (_gatlstm(3, 4, *_GL_SMALL), (4,)), "small_t5_p8": (_gatlstm(5, 8, [7, 3], [4]), (3, 8)),
+        "row_40x64": (_gatlstm(40, 64, *_GL_ROW), (2,)), "row_80x32": (_gatlstm(80, 32, *_GL_ROW), (2,)), "row_32x1024": (_gatlstm(32, 1024, *_GL_ROW), (2,)),
+        "row_64x512": (_gatlstm(64, 512, *_GL_ROW), ()),
+        "patches128": (_gatlstm(128, 4, *_GL_SMALL), ()), "patches129": (_gatlstm(129, 4, *_GL_SMALL), ()),
+        "patch_size3": (_gatlstm(3, 3, *_GL_SMALL), ()), "patch_size2048": (_gatlstm(3, 2048, *_GL_SMALL), ()), "patch_size2049": (_gatlstm(3, 2049, *_GL_SMALL), ()),
+        "layers4": (_gatlstm(3, 4, [5, 4, 3, 2], [3, 2]), ()), "layers5": (_gatlstm(3, 4, [5, 4, 3, 2], [3, 2], num_gat=5), ()), "layers0": (_gatlstm(3, 4, [], [3, 2]), ()),
+        "width512": (_gatlstm(3, 4, [512, 512], [3, 2]), ()), "width513": (_gatlstm(3, 4, [5, 513], [3, 2]), ()),
+        "lstm_layers3": (_gatlstm(3, 4, [5, 4, 3], [3, 2, 2]), ()), "lstm_layers4": (_gatlstm(3, 4, [5, 4, 3], [3, 2, 2], num_lstm=4), ()),
+        "lstm_layers0": (_gatlstm(3, 4, [5, 4, 3], []), ()),
+        "lstm128": (_gatlstm(3, 4, [5, 4, 3], [128, 128]), ()), "lstm129": (_gatlstm(3, 4, [5, 4, 3], [3, 129]), ())}),
+    # RULGNN_LOGOB_MAX_*: (patch_size, num_patch, nperseg, hidden_dim); num_nodes and input_dim are the STFT's
+    "logob": (("param_count", "workspace_bytes"), {
+        "tiny_ns4_p8_t2_h1": (_logob(8, 2, 4, 1), (3,)), "ns2_p6_t3_h1": (_logob(6, 3, 2, 1), (2,)), "ragged_ns4_p10_t3_h2": (_logob(10, 3, 4, 2), (2,)),
+        "onepatch_ns4_p8_t1_h1": (_logob(8, 1, 4, 1), (2,)), "row_phm2012": (_logob(64, 40, 8, 10), (2,)), "row_xjtu": (_logob(1024, 32, 32, 10), (2,)),
+        "nodes17": (_logob(32, 2, 32, 1), ()), "nodes18": (_logob(34, 2, 34, 1), ()), "nperseg3": (_logob(8, 2, 3, 1), ()),
+        "patch_half_nperseg": (_logob(2, 2, 4, 1), ()),
+        "input_dim33": (_logob(64, 2, 2, 1), ()), "input_dim34": (_logob(66, 2, 2, 1), ()),
+        "sequences65535": (_logob(8, 21845, 4, 1), ()), "sequences65538": (_logob(8, 21846, 4, 1), ()),
+        "h21": (_logob(8, 2, 4, 21), ()), "h22": (_logob(8, 2, 4, 22), ()),
+        "nodes_not_the_stfts": (_plain(L.LogobShape, 8, 2, 3, 4, 4, 1), ())}),
+    # RULGNN_HCPB_MAX_* and HierCorrPool's num_nodes_out and 4 * hidden_dim * num_nodes: (patch_size, num_patch, nperseg, hidden_dim,
+    # embedding_dim, encoder_conv_kernel, num_nodes_out)
+    "hcpb": (("param_count", "bn_state_count", "workspace_bytes"), {
+        "small_ns4_p8_t7": (_hcpb(8, 7, 4, 2, 2, 12, 3), (6, 8)), "ragged_ns4_p10_t3": (_hcpb(10, 3, 4, 2, 2, 12, 2), (3,)),
+        "ns2_p6_t3": (_hcpb(6, 3, 2, 1, 1, 12, 2), (3,)), "p65_ns4": (_hcpb(4, 65, 4, 1, 1, 40, 4), (2,)),
+        "row_phm_c1": (_hcpb(32, 80, 8, 10, 10, 48, 6), ()), "row_phm_c2": (_hcpb(128, 20, 16, 10, 10, 20, 6), ()), "row_phm_c3": (_hcpb(64, 40, 8, 10, 10, 28, 6), ()),
+        "row_xjtu_c1": (_hcpb(512, 64, 32, 10, 10, 40, 6), ()), "row_xjtu_c2": (_hcpb(256, 128, 16, 10, 10, 72, 6), ()),
+        "nperseg32": (_hcpb(32, 7, 32, 2, 2, 12, 3), ()), "nperseg34": (_hcpb(34, 7, 34, 2, 2, 12, 3), ()), "nperseg3": (_hcpb(8, 7, 3, 2, 2, 12, 3), ()),
+        "patch_half_nperseg": (_hcpb(2, 7, 4, 2, 2, 12, 3), ()),
+        "input_dim33": (_hcpb(64, 7, 2, 2, 2, 12, 3), ()), "input_dim34": (_hcpb(66, 7, 2, 2, 2, 12, 3), ()),
+        "patches128": (_hcpb(4, 128, 4, 1, 1, 72, 4), ()), "patches129": (_hcpb(4, 129, 4, 1, 1, 72, 4), ()), "patches1": (_hcpb(8, 1, 4, 2, 2, 8, 3), ()),
+        "d720": (_hcpb(8, 7, 4, 60, 60, 12, 3), ()), "d732": (_hcpb(8, 7, 4, 61, 61, 12, 3), ()),
+        "nodes_out16": (_hcpb(8, 7, 4, 2, 2, 12, 16), ()), "nodes_out17": (_hcpb(8, 7, 4, 2, 2, 12, 17), ()),
+        "c3_1024": (_hcpb(32, 2, 30, 16, 16, 8, 3), ()), "c3_1088": (_hcpb(32, 2, 32, 16, 16, 8, 3), ()),
+        "flat_view_mismatch": (_hcpb(8, 7, 4, 2, 2, 11, 3), ()),
+        "nodes_not_the_stfts": (_plain(L.HcpbShape, 8, 7, 3, 2, 2, 4, 4, 12, 3), ())}),
+    # RULGNN_STFA_*: (num_patch, patch_size, num_nodes, output_dim, num_heads, encoder_hidden_dim)
+    "stfa": (("param_count", "workspace_bytes"), {
+        "small_t2_p3": (_plain(L.StfaShape, 2, 3, 14, 2, 2, 3), (3,)), "small_t3_p5": (_plain(L.StfaShape, 3, 5, 14, 3, 3, 5), (4, 8)),
+        "row_t25_p2": (_plain(L.StfaShape, 25, 2, 14, 5, 10, 64), (2,)),
+        "nodes13": (_plain(L.StfaShape, 2, 3, 13, 2, 2, 3), ()), "nodes15": (_plain(L.StfaShape, 2, 3, 15, 2, 2, 3), ()),
+        "patches128": (_plain(L.StfaShape, 128, 3, 14, 2, 2, 3), ()), "patches129": (_plain(L.StfaShape, 129, 3, 14, 2, 2, 3), ()),
+        "patch_size64": (_plain(L.StfaShape, 2, 64, 14, 2, 2, 3), ()), "patch_size65": (_plain(L.StfaShape, 2, 65, 14, 2, 2, 3), ()),
+        "output_dim16": (_plain(L.StfaShape, 2, 3, 14, 16, 2, 3), ()), "output_dim17": (_plain(L.StfaShape, 2, 3, 14, 17, 2, 3), ()),
+        "heads16": (_plain(L.StfaShape, 2, 3, 14, 2, 16, 3), ()), "heads17": (_plain(L.StfaShape, 2, 3, 14, 2, 17, 3), ()), "heads0": (_plain(L.StfaShape, 2, 3, 14, 2, 0, 3), ()),
+        "lstm128": (_plain(L.StfaShape, 2, 3, 14, 2, 2, 128), ()), "lstm129": (_plain(L.StfaShape, 2, 3, 14, 2, 2, 129), ()),
+        "every_limit": (_plain(L.StfaShape, 128, 64, 14, 16, 16, 128), ())}),
     "hagcn": (("graph_param_count", "workspace_bytes"), {
         "n14_e60_h64": (_plain(L.HagcnShape, 14, 60, 64), (6, 5, 7, 24)), "n20_e60_h64": (_plain(L.HagcnShape, 20, 60, 64), (3,)),
         "n12_e8_h16": (_plain(L.HagcnShape, 12, 8, 16), (4,))}),
@@ -158,7 +279,13 @@ def _sizes(lib):
                             ("stagnn", "small_5x12", FAMILIES["stagnn"][1]["small_5x12"][0]),
                             ("agcntf", "small_5x7_heads2", FAMILIES["agcntf"][1]["small_5x7_heads2"][0]),
                             ("hiercorrpool", "small_7x3_n5", FAMILIES["hiercorrpool"][1]["small_7x3_n5"][0]),
-                            ("logo", "small_3x2x2_h1", FAMILIES["logo"][1]["small_3x2x2_h1"][0])):
+                            ("logo", "small_3x2x2_h1", FAMILIES["logo"][1]["small_3x2x2_h1"][0]),
+                            ("dvgtformer", "small_3x4_h1_b1", FAMILIES["dvgtformer"][1]["small_3x4_h1_b1"][0]),
+                            ("gdagdl", "small_n5_t2", FAMILIES["gdagdl"][1]["small_n5_t2"][0]),
+                            ("gatlstm", "small_t3_p4", FAMILIES["gatlstm"][1]["small_t3_p4"][0]),
+                            ("logob", "tiny_ns4_p8_t2_h1", FAMILIES["logob"][1]["tiny_ns4_p8_t2_h1"][0]),
+                            ("hcpb", "small_ns4_p8_t7", FAMILIES["hcpb"][1]["small_ns4_p8_t7"][0]),
+                            ("stfa", "small_t2_p3", FAMILIES["stfa"][1]["small_t2_p3"][0])):
         out[f"{fam}/{name}/tap_offsets_from_minus1"] = [int(getattr(lib, f"rulgnn_{fam}_tap_offset")(C.byref(make(4)), w)) for w in range(-1, 12)]
     for N, P in STGCN_NP:
         for layers in (1, 2, 3):
@@ -218,8 +345,18 @@ _STEP_FAMILIES = {
     "hiercorrpool": (L.HiercorrpoolArgs, _plain(L.HiercorrpoolShape, 3, 7, 2, 2, 5, 12, 3), _plain(L.HiercorrpoolShape, 3, 7, 2, 2, 33, 12, 3),
                      {"training": 1, "dropout_p": 0.2}),
     "logo": (L.LogoArgs, _plain(L.LogoShape, 2, 2, 3, 1), _plain(L.LogoShape, 2, 2, 33, 1), {"training": 1, "dropout_p": 0.2, "theta": 0.001, "gamma": 0.5}),
+    "logob": (L.LogoArgs, _logob(8, 2, 4, 1), _logob(8, 2, 4, 22), {"training": 1, "dropout_p": 0.2, "theta": 0.001, "gamma": 0.5}),
+    "hcpb": (L.HiercorrpoolArgs, _hcpb(8, 7, 4, 2, 2, 12, 3), _hcpb(8, 7, 4, 2, 2, 12, 17), {"training": 1, "dropout_p": 0.2}),
+    "dvgtformer": (L.DvgtformerArgs, _dvgt(3, 4, *_DV_SMALL), _dvgt(25, 4, *_DV_SMALL), {"training": 1, "dropout_p": 0.1}),
+    "gdagdl": (L.GdagdlArgs, _gdagdl(3, 8, 4, *_GD_SMALL), _gdagdl(3, 8, 4, [5, 4, 3], 129, 8, 4), {"training": 1, "dropout_p": 0.5}),
+    "gatlstm": (L.GatlstmArgs, _gatlstm(3, 4, *_GL_SMALL), _gatlstm(3, 3, *_GL_SMALL), {"training": 1, "dropout_p": 0.2}),
+    "stfa": (L.StfaArgs, _plain(L.StfaShape, 2, 3, 14, 2, 2, 3), _plain(L.StfaShape, 2, 3, 15, 2, 2, 3), {"training": 1, "dropout_p": 0.2}),
 }
 _BN_FAMILIES = ("astgcnn", "fcstgnn", "stconv")
+# The families whose dropout is drawn by sample index in the global batch, with the pointers their entries treat as optional on top of
+# y / dpred / loss.  GDAGDL, GAT_LSTM and STFA refuse a global batch whose last dropout counter passes 32 bits; the sets that ask for
+# one run on the others too, where they pin that there is no such bound.
+_SAMPLE_DROPOUT = {"rgcnu": (), "hiercorrpool": (), "hcpb": (), "dvgtformer": (), "gdagdl": ("recon", "recon_weight"), "gatlstm": (), "stfa": ()}
 _OPTIONAL = ("dpred", "recon_weight", "step_state", "aux_stream")
 
 
@@ -310,19 +447,65 @@ def _family_codes(lib, fam, out):
         a, _ = args(dropout_p=1.0, params=None)
         out["rgcnu/fwdbwd/dropout_p1_and_params_null"] = int(lib.rulgnn_rgcnu_fwdbwd_f32(C.byref(good(B)), C.byref(a), None, None))
 
-    def more(entry, key, over, **opt_over):
+    def more(entry, key, over, shape=good, **opt_over):
         """One more set on rulgnn_<fam>_<entry>_f32; `opt_over` (fwdbwd only) builds an optimizer block on the set's own parameters."""
         a, _ = args(**over)
         fn = getattr(lib, f"rulgnn_{fam}_{entry}_f32")
         opt = C.byref(_adam(a.params, **opt_over)) if opt_over else None
-        out[f"{fam}/{entry}/{key}"] = int(fn(C.byref(good(B)), C.byref(a), opt, None) if entry == "fwdbwd" else fn(C.byref(good(B)), C.byref(a), None))
+        out[f"{fam}/{entry}/{key}"] = int(fn(C.byref(shape(B)), C.byref(a), opt, None) if entry == "fwdbwd" else fn(C.byref(shape(B)), C.byref(a), None))
 
-    if fam == "logo":
+    if fam in _SAMPLE_DROPOUT:
+        for entry in ("forward", "backward", "fwdbwd"):
+            for key, over in (("sample_offset_negative", dict(sample_offset=-1)), ("global_batch_short", dict(global_batch=1)), ("dropout_p1", dict(dropout_p=1.0)),
+                              ("dropout_p_negative", dict(dropout_p=-0.5)), ("dropout_p_nan", dict(dropout_p=float("nan"))),
+                              # ... each with a second fault behind it, and with one ahead of it
+                              ("sample_offset_negative_and_params_null", dict(sample_offset=-1, params=None)),
+                              ("sample_offset_negative_and_y_plus1", dict(sample_offset=-1, y="misalign")),
+                              ("global_batch_short_and_loss_plus1", dict(global_batch=1, loss="misalign")),
+                              ("global_batch_short_and_workspace_null", dict(global_batch=1, workspace=None)),
+                              ("dropout_p1_and_dpred_plus1", dict(dropout_p=1.0, dpred=BASE + 512 * 64 + 1)),
+                              ("dropout_p1_and_x_null", dict(dropout_p=1.0, x=None)),
+                              ("dropout_p1_and_sample_offset_negative", dict(dropout_p=1.0, sample_offset=-1)),
+                              # the 32-bit dropout counter, from either side, alone and between two other faults
+                              ("global_batch_2p31", dict(global_batch=1 << 31)), ("sample_offset_2p31", dict(sample_offset=1 << 31, global_batch=(1 << 31) + B)),
+                              ("global_batch_2p31_and_dropout_p1", dict(global_batch=1 << 31, dropout_p=1.0)),
+                              ("global_batch_2p31_and_y_plus1", dict(global_batch=1 << 31, y="misalign")),
+                              ("global_batch_2p31_and_params_null", dict(global_batch=1 << 31, params=None)),
+                              ("sample_offset_2p31_and_loss_plus1", dict(sample_offset=1 << 31, global_batch=(1 << 31) + B, loss="misalign")),
+                              # the optional pointers against the required ones
+                              ("y_plus1_and_params_null", dict(y="misalign", params=None)), ("loss_plus1_and_x_null", dict(loss="misalign", x=None)),
+                              ("dpred_plus1_and_grads_null", dict(dpred=BASE + 512 * 64 + 1, grads=None)),
+                              ("loss_plus1_and_workspace_plus1", dict(loss="misalign", workspace="misalign"))):
+                more(entry, key, over)
+            more(entry, "unsupported_shape_and_sample_offset_negative", dict(sample_offset=-1), shape=bad)
+            more(entry, "unsupported_shape_and_global_batch_2p31", dict(global_batch=1 << 31), shape=bad)
+            for name in _SAMPLE_DROPOUT[fam]:
+                for key, over in ((f"{name}_plus1", {name: "misalign"}), (f"{name}_plus1_and_params_null", {name: "misalign", "params": None}),
+                                  (f"{name}_plus1_and_grads_null", {name: "misalign", "grads": None}),
+                                  (f"{name}_plus1_and_global_batch_short", {name: "misalign", "global_batch": 1}),
+                                  (f"{name}_plus1_and_global_batch_2p31", {name: "misalign", "global_batch": 1 << 31}),
+                                  (f"{name}_plus1_and_y_plus1", {name: "misalign", "y": "misalign"})):
+                    more(entry, key, over)
+    if fam == "hcpb":
+        for entry in ("forward", "backward", "fwdbwd"):
+            for key, over in (("bn_state_null_and_x_plus1", dict(bn_state=None, x="misalign")), ("bn_state_plus1_and_dropout_p1", dict(bn_state="misalign", dropout_p=1.0)),
+                              ("bn_state_null_and_params_plus1", dict(bn_state=None, params="misalign")),
+                              ("bn_state_plus1_and_grads_null", dict(bn_state="misalign", grads=None)),
+                              ("bn_state_null_and_eval_mode", dict(bn_state=None, training=0))):
+                more(entry, key, over)
+    if fam == "logob":
+        for entry in ("forward", "backward", "fwdbwd"):
+            for key, over in (("loss_gl_plus1_and_params_null", dict(loss_gl="misalign", params=None)),
+                              ("loss_gl_plus1_and_dropout_p1", dict(loss_gl="misalign", dropout_p=1.0)),
+                              ("loss_gl_plus1_and_loss_plus1", dict(loss_gl="misalign", loss="misalign")),
+                              ("loss_gl_null", dict(loss_gl=None)), ("loss_gl_null_and_grads_null", dict(loss_gl=None, grads=None))):
+                more(entry, key, over)
+    if fam in ("logo", "logob"):
         for key, over in (("loss_gl_plus1", dict(loss_gl="misalign")), ("global_batch_short", dict(global_batch=1)), ("dropout_p1", dict(dropout_p=1.0)),
                           ("dropout_p1_and_params_null", dict(dropout_p=1.0, params=None)), ("loss_gl_plus1_and_grads_null", dict(loss_gl="misalign", grads=None)),
                           ("global_batch_short_and_loss_plus1", dict(global_batch=1, loss="misalign"))):
             more("fwdbwd", key, over)
-    if fam == "hiercorrpool":
+    if fam in ("hiercorrpool", "hcpb"):
         for entry in ("backward", "fwdbwd"):
             more(entry, "eval_mode", dict(training=0))
         for key, over in (("sample_offset_negative", dict(sample_offset=-1)), ("global_batch_short", dict(global_batch=1)), ("dropout_p1", dict(dropout_p=1.0)),

@@ -27,6 +27,59 @@ def test_every_declared_symbol_is_exported_and_bound():
         assert hasattr(raw, name), name
 
 
+def _struct_defines():
+    """{index: define suffix} of the ``#define RULGNN_STRUCT_<X> <n>`` lines of include/rulgnn.h."""
+    hdr = open(os.path.join(ROOT, "include", "rulgnn.h")).read()
+    found = re.findall(r"^#define RULGNN_STRUCT_(\w+) (\d+)\s*$", hdr, re.M)
+    table = {int(n): suffix for suffix, n in found}
+    assert len(table) == len(found), "two RULGNN_STRUCT_* constants share an index"
+    return table
+
+
+def test_struct_table_is_the_headers():
+    assert set(_struct_defines()) == set(_lib.STRUCTS)
+
+
+def test_struct_size_answers_the_mirror_and_zero_elsewhere():
+    lib = _lib.load()
+    for which in range(-2, max(_lib.STRUCTS) + 8):
+        mirror = _lib.STRUCTS.get(which)
+        assert lib.rulgnn_struct_size(which) == (C.sizeof(mirror) if mirror is not None else 0), which
+
+
+def _c_compiler():
+    """The system C compiler; without one, the host compiler hipcc drives (the library cannot have been built without it)."""
+    import shutil
+    if shutil.which("cc"):
+        return shutil.which("cc")
+    clang = os.path.join(os.path.dirname(os.path.realpath(build._hipcc())), "..", "lib", "llvm", "bin", "clang")
+    assert os.access(clang, os.X_OK), "no C compiler: neither cc nor hipcc's clang"
+    return clang
+
+
+def test_every_mirror_field_sits_where_the_header_puts_it(tmp_path):
+    """sizeof and offsetof of every field of every mirror, as a C99 compiler reads include/rulgnn.h, against ctypes.  The C struct of
+    ``RULGNN_STRUCT_<X>`` is ``rulgnn_<x>``."""
+    import subprocess
+    lines, want = ['#include <stdio.h>', '#include <stddef.h>', '#include "rulgnn.h"', 'int main(void) {'], []
+    for which, suffix in sorted(_struct_defines().items()):
+        mirror, cname = _lib.STRUCTS[which], "rulgnn_" + suffix.lower()
+        lines.append(f'    printf("{which} sizeof %zu\\n", sizeof({cname}));')
+        want.append(f"{which} sizeof {C.sizeof(mirror)}")
+        for field, _ in mirror._fields_:
+            lines.append(f'    printf("{which} {field} %zu\\n", offsetof({cname}, {field}));')
+            want.append(f"{which} {field} {getattr(mirror, field).offset}")
+    lines += ['    return 0;', '}']
+    src, exe = tmp_path / "offsets.c", tmp_path / "offsets"
+    src.write_text("\n".join(lines) + "\n")
+    cc = subprocess.run([_c_compiler(), "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)], capture_output=True, text=True)
+    assert cc.returncode == 0, cc.stderr
+    got = subprocess.run([str(exe)], capture_output=True, text=True, timeout=60)
+    assert got.returncode == 0, got.stderr
+    assert len(want) > 480
+    assert got.stdout.splitlines() == want
+
+
 def test_param_count_and_layout_agree_with_library():
     lib = _lib.load()
     for N, L in [(14, 2), (40, 2), (16, 3), (2, 1)]:

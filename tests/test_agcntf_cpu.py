@@ -73,9 +73,9 @@ def test_registry_serves_the_algorithm_and_refuses_the_model():
 
 def test_struct_sizes_are_checked_at_load():
     lib = _lib.load()
-    assert _lib.AgcntfShape in _lib.STRUCTS and _lib.AgcntfArgs in _lib.STRUCTS
-    assert lib.rulgnn_struct_size(_lib.STRUCTS.index(_lib.AgcntfShape)) == C.sizeof(_lib.AgcntfShape) == 32
-    assert lib.rulgnn_struct_size(_lib.STRUCTS.index(_lib.AgcntfArgs)) == C.sizeof(_lib.AgcntfArgs) == C.sizeof(_lib.SagcnArgs)
+    assert _lib.STRUCTS[27] is _lib.AgcntfShape and _lib.STRUCTS[28] is _lib.AgcntfArgs
+    assert lib.rulgnn_struct_size(27) == C.sizeof(_lib.AgcntfShape) == 32
+    assert lib.rulgnn_struct_size(28) == C.sizeof(_lib.AgcntfArgs) == C.sizeof(_lib.SagcnArgs)
 
 
 @pytest.mark.parametrize("P,n,Ha,Hg,heads", [(40, 64, 100, 100, 1), (128, 256, 100, 100, 1), (256, 128, 100, 100, 1), (5, 7, 6, 7, 2),

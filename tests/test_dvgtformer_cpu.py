@@ -213,7 +213,6 @@ def test_fixtures_hold_no_grad_key_and_stay_small():
 
 def test_struct_sizes_are_checked_at_load():
     lib = _lib.load()
-    assert _lib.DvgtformerShape in _lib.STRUCTS and _lib.DvgtformerArgs in _lib.STRUCTS
-    assert lib.rulgnn_struct_size(_lib.STRUCTS.index(_lib.DvgtformerShape)) == C.sizeof(_lib.DvgtformerShape) == 48
-    assert lib.rulgnn_struct_size(_lib.STRUCTS.index(_lib.DvgtformerArgs)) == C.sizeof(_lib.DvgtformerArgs)
-    assert lib.rulgnn_struct_size(len(_lib.STRUCTS)) == 0
+    assert _lib.STRUCTS[33] is _lib.DvgtformerShape and _lib.STRUCTS[34] is _lib.DvgtformerArgs
+    assert lib.rulgnn_struct_size(33) == C.sizeof(_lib.DvgtformerShape) == 48
+    assert lib.rulgnn_struct_size(34) == C.sizeof(_lib.DvgtformerArgs)

@@ -125,9 +125,9 @@ def test_new_fixtures_hold_no_grad_key():
 
 def test_struct_sizes_are_checked_at_load():
     lib = _lib.load()
-    assert _lib.HiercorrpoolShape in _lib.STRUCTS and _lib.HiercorrpoolArgs in _lib.STRUCTS
-    assert lib.rulgnn_struct_size(_lib.STRUCTS.index(_lib.HiercorrpoolShape)) == C.sizeof(_lib.HiercorrpoolShape) == 40
-    assert lib.rulgnn_struct_size(_lib.STRUCTS.index(_lib.HiercorrpoolArgs)) == C.sizeof(_lib.HiercorrpoolArgs)
+    assert _lib.STRUCTS[29] is _lib.HiercorrpoolShape and _lib.STRUCTS[30] is _lib.HiercorrpoolArgs
+    assert lib.rulgnn_struct_size(29) == C.sizeof(_lib.HiercorrpoolShape) == 40
+    assert lib.rulgnn_struct_size(30) == C.sizeof(_lib.HiercorrpoolArgs)
 
 
 @pytest.mark.parametrize("cfg,millions", [(FD001, 2.0), (FD004, 1.8), (NCMAPSS, 3.7)])

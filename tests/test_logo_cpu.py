@@ -156,10 +156,9 @@ def test_new_fixtures_hold_no_grad_key():
 
 def test_struct_sizes_are_checked_at_load():
     lib = _lib.load()
-    assert _lib.LogoShape in _lib.STRUCTS and _lib.LogoArgs in _lib.STRUCTS
-    assert lib.rulgnn_struct_size(_lib.STRUCTS.index(_lib.LogoShape)) == C.sizeof(_lib.LogoShape) == 24
-    assert lib.rulgnn_struct_size(_lib.STRUCTS.index(_lib.LogoArgs)) == C.sizeof(_lib.LogoArgs)
-    assert lib.rulgnn_struct_size(len(_lib.STRUCTS)) == 0
+    assert _lib.STRUCTS[31] is _lib.LogoShape and _lib.STRUCTS[32] is _lib.LogoArgs
+    assert lib.rulgnn_struct_size(31) == C.sizeof(_lib.LogoShape) == 24
+    assert lib.rulgnn_struct_size(32) == C.sizeof(_lib.LogoArgs)
 
 
 def lds_floats(N, L, p, bwd):
