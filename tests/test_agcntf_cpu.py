@@ -1,6 +1,5 @@
 """AGCN_TF without a GPU: the module's surface, the registry, the hparams rows, the C-ABI's size queries and coverage gate."""
 import ctypes as C
-import json
 import os
 
 import numpy as np
@@ -12,6 +11,7 @@ from gnn_rul_benchmarking_amd import _lib
 from conftest import GOLDEN
 
 import agcntf_oracle as O
+import family_kit as K
 
 LIMITS = "num_patch patch_size hidden_adj_dim hidden_gnn_dim num_heads".split()
 
@@ -45,15 +45,8 @@ def test_cpu_input_raises_and_the_tie_rule_is_documented():
 
 
 def test_hparams_rows_equal_the_reference():
-    from gnn_rul_benchmarking_amd.hparams import get_hparams_class
-    rows = json.loads(str(np.load(os.path.join(GOLDEN, "agcntf_hparams_rows.npz"))["rows_json"]))
-    assert sorted(rows) == [f"{ds}/Condition_{i}" for ds in ("PHM2012", "XJTU_SY") for i in (1, 2, 3)]
-    for key, ref in rows.items():
-        ds, did = key.split("/")
-        h = get_hparams_class(ds)(did)
-        assert h.train_params["AGCN_TF"] == ref["train_params"] and h.alg_hparams["AGCN_TF"] == ref["alg_hparams"], key
-    for h in (get_hparams_class("CMAPSS")("FD001"), get_hparams_class("NCMAPSS")(None)):
-        assert "AGCN_TF" not in h.alg_hparams and "AGCN_TF" not in h.train_params
+    K.hparams_rows_check("AGCN_TF", "agcntf_hparams_rows.npz", [f"{ds}/Condition_{i}" for ds in ("PHM2012", "XJTU_SY") for i in (1, 2, 3)],
+                         ["CMAPSS/FD001", "NCMAPSS/None"])
 
 
 def test_registry_serves_the_algorithm_and_refuses_the_model():
@@ -61,10 +54,7 @@ def test_registry_serves_the_algorithm_and_refuses_the_model():
     from gnn_rul_benchmarking_amd.agcntf import AGCN_TF_model
     from gnn_rul_benchmarking_amd.hparams import get_hparams_class
     from gnn_rul_benchmarking_amd.optim import FusedAdam
-    assert A.get_algorithm_class("AGCN_TF") is A.AGCN_TF
-    with pytest.raises(NotImplementedError, match="Algorithm not found: AGCN_TF_model"):
-        A.get_algorithm_class("AGCN_TF_model")
-    assert A.AGCN_TF.needs_train_mode is None and A.AGCN_TF.supports_graphs is False
+    K.registry_check("AGCN_TF", needs_train_mode=None)
     h = get_hparams_class("PHM2012")("Condition_1")
     algo = A.get_algorithm_class("AGCN_TF")(h.alg_hparams["AGCN_TF"], h.train_params["AGCN_TF"], "cpu")
     assert isinstance(algo.model, AGCN_TF_model) and isinstance(algo.optimizer, FusedAdam)

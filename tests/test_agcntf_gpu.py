@@ -4,8 +4,6 @@ Gates, relative to each tensor's largest entry: 1e-4 on features, taps, predicti
 reference fixtures and the fp64 oracle alike (the fp32 reference against its own fp64 run stays within 3.3e-6 / 4.7e-5 over shapes from
 5 x 7 to 256 x 128, so the reference alone passes them with 10x room).  Each head's W_k.bias gradient is analytically zero (the rows of a
 softmax gradient sum to zero): it is compared as max|g| <= 5e-4 max|grad W_q.bias| of the same head."""
-import argparse
-import ctypes as C
 import os
 
 import numpy as np
@@ -13,6 +11,8 @@ import pytest
 import torch
 
 import agcntf_oracle as O
+import family_kit as K
+from family_kit import grads_of
 from test_agcntf_oracle_golden import CASES, load_case
 from test_sagcn_gpu import rank_margin, signal
 from test_sagcn_oracle_golden import rel
@@ -28,11 +28,6 @@ def build_model(cfg, p):
     m = AGCN_TF_model(**cfg)
     m.load_state_dict({k: torch.from_numpy(np.asarray(v, np.float32)) for k, v in p.items()})
     return m.to(DEV)
-
-
-def grads_of(m):
-    flat = m._grad_flat[:m.num_live].detach().cpu().numpy().astype(np.float64)
-    return {name: flat[off:off + int(np.prod(shape))].reshape(shape) for name, (off, shape) in m._layout.items()}
 
 
 def check_grads(got, want, heads):
@@ -245,40 +240,15 @@ def test_trainer_matches_reference_harness_run_on_phm2012(tmp_path, monkeypatch)
     100 / 100, batch 100, lr 1e-4, wd 1e-4): the reference's own harness, run on the CPU with the argsort pinned to the stable order by
     tests/golden/make_golden_agcntf.py::case_trainer_phm2012, vs this package's harness on the GPU."""
     import io
-    import sys
     import pandas as pd
-    sys.path.insert(0, GOLD)
-    from synth import synthetic_phm2012
-    from gnn_rul_benchmarking_amd import trainer as T
     z = np.load(os.path.join(GOLD, "agcntf_trainer_phm2012_c1_reference_run.npz"))
     assert bool(z["argsort_pinned_stable"])
-    (xtr, ytr), (xte, yte) = synthetic_phm2012(int(z["seed"]), int(z["n_train"]), int(z["n_test"]))
-    assert abs(xtr.astype(np.float64).sum() - float(z["x_train_checksum"])) < 1e-6
-    d = tmp_path / "data" / "PHM2012" / "Condition_1"
-    d.mkdir(parents=True)
-    torch.save({"samples": xtr, "labels": ytr, "max_ruls": 1.0}, d / "train.pt")
-    torch.save({"samples": xte, "labels": yte, "max_ruls": 1.0}, d / "test.pt")
-    monkeypatch.chdir(tmp_path)
-    args = argparse.Namespace(save_dir=str(tmp_path / "logs"), experiment_description="exp", run_description="r",
-                              GNN_method="AGCN_TF", data_path=str(tmp_path / "data"), dataset="PHM2012",
-                              dataset_id="Condition_1", bearing_id="Testing_bearing_1", num_runs=1, device="cuda:0")
-    tr = T.GNN_RUL_trainer(args)
-    tr.train_configs["num_epochs"] = int(z["epochs"])
-    assert tr.model_configs == dict(num_patch=40, patch_size=64, hidden_adj_dim=100, hidden_gnn_dim=100)
-    assert tr.train_configs == {'num_epochs': 3, 'batch_size': 100, 'weight_decay': 1e-4, 'learning_rate': 1e-4}
-    per_epoch = []
-    orig = tr.calc_results_per_run
 
-    def spy(run_id):
-        per_epoch.append(T._calc_metrics(tr.pred_labels, tr.true_labels, tr.max_ruls))
-        return orig(run_id)
-    tr.calc_results_per_run = spy
-    tr.train()
-    got, ref = np.asarray(per_epoch, np.float64), z["per_epoch"]
-    print("AGCN_TF harness per-epoch got/ref:\n", got, "\n", ref)
-    assert got.shape == ref.shape == (3, 4)
-    assert np.max(np.abs(got[:, 3] - ref[:, 3])) < 1e-4
-    assert np.max(np.abs(got[:, 2:] - ref[:, 2:]) / np.abs(ref[:, 2:])) < 1e-4
+    def row(tr):
+        assert tr.model_configs == dict(num_patch=40, patch_size=64, hidden_adj_dim=100, hidden_gnn_dim=100)
+        assert tr.train_configs == {'num_epochs': 3, 'batch_size': 100, 'weight_decay': 1e-4, 'learning_rate': 1e-4}
+    _, per_epoch = K.harness_run(tmp_path, monkeypatch, "AGCN_TF", "PHM2012", "Condition_1", z, configure=row)
+    K.assert_harness("AGCN_TF", per_epoch, None, z, dict(rmse_abs=1e-4, rmse_scale=1.0, rel=1e-4, rel_from=2))
     csv = pd.read_csv(tmp_path / "logs" / "exp" / "r" / "AGCN_TF_run_0" / "results.csv")
     ref_csv = pd.read_csv(io.StringIO(str(z["csv_text"])))
     assert list(csv.columns) == list(ref_csv.columns) and len(csv) == len(ref_csv)

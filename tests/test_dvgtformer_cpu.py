@@ -14,6 +14,7 @@ from gnn_rul_benchmarking_amd import _lib
 from conftest import GOLDEN
 
 import dvgtformer_oracle as O
+import family_kit as K
 from test_dvgtformer_oracle_golden import FULL, SMALL, load_case
 
 FD = dict(num_nodes=14, time_length=50, d_model=[144, 248], num_heads=4, lambda_param=0.5, d_ff=[72, 124], dropout=0.1, num_blocks=3)
@@ -28,11 +29,7 @@ def shape_of(batch, cfg):
 
 
 def test_registry_serves_the_algorithm_and_refuses_the_model():
-    from gnn_rul_benchmarking_amd import algorithms as A
-    assert A.get_algorithm_class("DVGTformer") is A.DVGTformer
-    with pytest.raises(NotImplementedError, match="Algorithm not found: DVGTformer_model"):
-        A.get_algorithm_class("DVGTformer_model")
-    assert A.DVGTformer.needs_train_mode == "dropout" and A.DVGTformer.supports_graphs is False
+    K.registry_check("DVGTformer")
 
 
 def test_algorithm_construction():
@@ -85,14 +82,8 @@ def test_a_seed_gives_the_reference_keys_and_initial_values(name):
 
 def test_hparams_rows_equal_the_reference():
     from gnn_rul_benchmarking_amd.hparams import get_hparams_class
-    rows = json.loads(str(np.load(os.path.join(GOLDEN, "dvgtformer_hparams_rows.npz"))["rows_json"]))
-    assert sorted(rows) == ["CMAPSS/FD001", "CMAPSS/FD002", "CMAPSS/FD003", "CMAPSS/FD004", "NCMAPSS/None"]
-    for key, ref in rows.items():
-        ds, did = key.split("/")
-        h = get_hparams_class(ds)(None if did == "None" else did)
-        assert h.train_params["DVGTformer"] == ref["train_params"] and h.alg_hparams["DVGTformer"] == ref["alg_hparams"], key
-    h = get_hparams_class("PHM2012")("Condition_1")
-    assert "DVGTformer" not in h.alg_hparams and "DVGTformer" not in h.train_params
+    K.hparams_rows_check("DVGTformer", "dvgtformer_hparams_rows.npz", ["CMAPSS/FD001", "CMAPSS/FD002", "CMAPSS/FD003", "CMAPSS/FD004", "NCMAPSS/None"],
+                         ["PHM2012/Condition_1"])
     assert get_hparams_class("CMAPSS")("FD003").alg_hparams["DVGTformer"] == FD
     assert get_hparams_class("NCMAPSS")(None).alg_hparams["DVGTformer"] == NCMAPSS
 
@@ -189,10 +180,7 @@ def test_out_of_limit_model_constructs_and_is_refused_before_the_library_is_touc
 def test_cpu_input_raises():
     from gnn_rul_benchmarking_amd.dvgtformer import DVGTformer_model
     m = DVGTformer_model(**TINY)
-    with pytest.raises(RuntimeError, match="HIP path only"):
-        m(torch.zeros(2, 2, 1))
-    with pytest.raises(RuntimeError, match="HIP path only"):
-        m.fused_mse_step(torch.zeros(2, 2, 1), torch.zeros(2))
+    K.cpu_input_raises(m, torch.zeros(2, 2, 1))
     with pytest.raises(RuntimeError, match="expects"):
         m(torch.zeros(2, 3, 1))
 

@@ -9,7 +9,6 @@ noise term is the REFERENCE's fp32 gradient against the fp64 oracle (the fixture
 of the torch restatement on the CPU), never the kernels' output.  The tensors whose gradient is zero in exact arithmetic are detected
 (grad_gate.zero_in_exact_arithmetic), not listed: at lambda = 0.5 they must be exactly the linears_K biases, which the kernels write as
 exact zeros.  Every test prints its worst gate ratio ("DVGT-GATE ...")."""
-import argparse
 import functools
 import os
 
@@ -17,14 +16,13 @@ import numpy as np
 import pytest
 import torch
 
-import adam_reference as R
+import family_kit as K
 import grad_gate as GG
 import dvgtformer_oracle as O
-from test_dvgtformer_oracle_golden import CURVE, FULL, SMALL, load_case, oracle_of, rel, seeded_state
+from family_kit import DEV, GOLD, dev, grads_of, rel_same_shape as rel
+from test_dvgtformer_oracle_golden import CURVE, FULL, SMALL, load_case, oracle_of, seeded_state
 
 pytestmark = pytest.mark.gpu
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
-DEV = "cuda:0"
 TOL, RTOL = 1e-4, 5e-4 / 2 ** 7
 FD = dict(num_nodes=14, time_length=50, d_model=[144, 248], num_heads=4, lambda_param=0.5, d_ff=[72, 124], dropout=0.1, num_blocks=3)
 
@@ -35,15 +33,7 @@ def make_cfg(N, L, H=2, nb=1, lam=0.5, d=(6, 10), ff=(4, 6)):
 
 def build_model(cfg, sd, dropout=0.0):
     from gnn_rul_benchmarking_amd.dvgtformer import DVGTformer_model
-    m = DVGTformer_model(**cfg)
-    m.load_state_dict({k: torch.from_numpy(np.asarray(v, np.float32)) for k, v in sd.items()}, strict=True)
-    m.dropout_p = dropout
-    return m.to(DEV)
-
-
-def grads_of(m, bucket=None):
-    flat = (m._grad_flat if bucket is None else bucket)[:m.num_live].detach().cpu().numpy().astype(np.float64)
-    return {name: flat[off:off + int(np.prod(shape))].reshape(shape) for name, (off, shape) in m._layout.items()}
+    return K.build_model(DVGTformer_model, cfg, sd, dropout)
 
 
 def k_weight_of(name):
@@ -51,25 +41,19 @@ def k_weight_of(name):
     return name.replace("linears_Q_", "linears_K_").rsplit(".", 1)[0] + ".weight" if "linears_" in name else None
 
 
+def k_weight_bound(name, g64, ref32):
+    """Not exact zeros: at most the reference's own residue, or fp32 ulps of the head's K-weight gradient."""
+    kw = k_weight_of(name)
+    return 16 * max(np.abs(ref32[name]).max(), 2.0 ** -23 * (np.abs(g64[kw]).max() if kw else 0.0))
+
+
+K_WEIGHT_RULE = K.ZeroRule(GG.zero_in_exact_arithmetic, k_weight_bound, lambda zero: f"; zero in exact arithmetic: {len(zero)} tensors")
+
+
 def check_grads(what, got, g64, ref32, cfg):
     """Every tensor through the element-wise gate; returns the names detected as zero in exact arithmetic."""
-    zero = GG.zero_in_exact_arithmetic(g64, ref32)
-    worst = (0.0, None)
-    for k in O.param_names(cfg):
-        assert got[k].shape == g64[k].shape, k
-        if k in zero:
-            if got[k].any():                        # not exact zeros: at most the reference's own residue
-                kw = k_weight_of(k)
-                bound = 16 * max(np.abs(ref32[k]).max(), 2.0 ** -23 * (np.abs(g64[kw]).max() if kw else 0.0))
-                assert np.abs(got[k]).max() <= bound, (k, np.abs(got[k]).max(), bound)
-            continue
-        ratio, where = GG.gate(got[k], g64[k], RTOL, GG.floor_for(ref32[k], g64[k]))
-        if ratio > 0.25:
-            print(f"  grad {k}: gate {ratio:.3f} at {where}  rel {rel(got[k], g64[k]):.2e}  max|g| {np.abs(g64[k]).max():.2e}")
-        worst = max(worst, (ratio, k))
-    print(f"DVGT-GATE {what}: worst gradient gate ratio {worst[0]:.3f} ({worst[1]}); zero in exact arithmetic: {len(zero)} tensors")
-    assert worst[0] <= 1.0, worst
-    return zero
+    assert list(g64) == O.param_names(cfg)
+    return K.check_grads(what, "DVGT", got, g64, ref32, RTOL, K_WEIGHT_RULE)
 
 
 def k_biases(cfg):
@@ -77,17 +61,8 @@ def k_biases(cfg):
 
 
 def check_forward(what, m, bs, pred, loss, want, want_loss):
-    errs = {"x0": rel(m.tap(bs, "x0").cpu().numpy(), want["x0"]), "enc": rel(m.tap(bs, "enc").cpu().numpy(), want["enc"]),
-            "pred": rel(pred.detach().cpu().numpy().reshape(-1), np.asarray(want["pred"]).reshape(-1))}
-    if loss is not None:
-        errs["loss"] = abs(float(loss) - want_loss) / abs(want_loss)
-    print(f"DVGT-GATE {what}: forward " + " ".join(f"{k}={v:.2e}" for k, v in errs.items()))
-    for k, v in errs.items():
-        assert v < TOL, (k, v)
-
-
-def dev(a):
-    return torch.from_numpy(np.asarray(a, np.float32)).to(DEV)
+    errs = {**K.tap_errs(m, bs, want, ("x0", "enc"), rel), **K.pred_err(pred, want, rel), **K.loss_err(loss, want_loss)}
+    K.check_forward(what, "DVGT", errs, TOL)
 
 
 @functools.lru_cache(maxsize=None)
@@ -272,109 +247,30 @@ def test_two_runs_give_the_same_bits(cfg_bs):
 
 # ---- 7. the optimizer, the curve, the trainer ------------------------------------------------------------------------------------------
 def test_fused_step_applies_adam_to_every_element_exactly_once():
-    """The twin-model procedure of tests/test_fused_adam_families_gpu.py (bounds from tests/adam_reference.py), dropout on."""
-    from gnn_rul_benchmarking_amd.optim import FusedAdam
-    from test_fused_adam_families_gpu import LR, SEED, STEP0, WD, _bits, _np
+    """The twin-model procedure (family_kit.adam_twin_check), dropout on."""
     z, cfg, sd = load_case(SMALL[1])
-    x, y = dev(z["x"]), dev(z["y"])
-
-    def ready():
-        m = build_model(cfg, sd, dropout=0.1).train()
-        m._seed = SEED
-        return m
-    a = ready()
-    p0 = _np(a.flat_params)
-    _, loss_a = a.fused_mse_step(x, y)
-    g_a, loss_a = _np(a.bucket[:a.num_live]), float(loss_a)
-    assert np.isfinite(g_a).all() and np.array_equal(_bits(_np(a.flat_params)), _bits(p0))
-    b = ready()
-    opt = FusedAdam(b, lr=LR, weight_decay=WD)
-    m0, v0 = R.moments_like(g_a, np.random.default_rng(12))
-    s = opt.state_dict()
-    s.update(step=STEP0, exp_avg=torch.from_numpy(m0).to(DEV), exp_avg_sq=torch.from_numpy(v0).to(DEV))
-    opt.load_state_dict(s)
-    worst = dict(p=0.0, m=0.0, v=0.0)
-    for k in (STEP0 + 1, STEP0 + 2, STEP0 + 3):
-        before = tuple(_np(t) for t in (b.flat_params, opt._exp_avg, opt._exp_avg_sq))
-        _, loss_b = b.fused_mse_step(x, y, opt)
-        g = _np(b.bucket[:b.num_live])
-        after = tuple(_np(t) for t in (b.flat_params, opt._exp_avg, opt._exp_avg_sq))
-        if k == STEP0 + 1:
-            assert np.array_equal(_bits(g), _bits(g_a)) and float(loss_b) == loss_a
-        r = R.check(after, before[0], g, before[1], before[2], k, WD, 1.0, what=f"DVGTformer, step {k}")
-        worst = {q: max(worst[q], r[q]) for q in worst}
-    assert opt._steps == STEP0 + 3
-    print("ADAM-RATIO family DVGTformer: " + " ".join(f"{q}={worst[q]:.3f}" for q in "pmv"))
+    K.adam_twin_check(lambda: build_model(cfg, sd, dropout=0.1).train(), dev(z["x"]), dev(z["y"]), "DVGTformer")
 
 
 def test_training_curve_matches_reference_algorithm():
     """Twenty update() steps against the reference's own.  Tolerances: the project's curve tolerances for a BatchNorm-free family
     (GRU_CM, tests/test_grucm_gpu.py: the first three losses 1e-4, every loss 2e-3, the eval prediction at the end 5e-3)."""
-    from gnn_rul_benchmarking_amd.algorithms import get_algorithm_class
     z, cfg, sd0 = load_case(CURVE, "sd0:")
-    algo = get_algorithm_class("DVGTformer")(cfg, {"learning_rate": float(z["lr"]), "weight_decay": float(z["wd"])}, DEV)
-    algo.model.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd0.items()})
-    algo.model.dropout_p = 0.0
-    algo.to(DEV).train()
-    xs, ys = torch.from_numpy(z["xs"]).to(DEV), torch.from_numpy(z["ys"]).to(DEV)
-    losses = np.asarray([algo.update(xs[s], ys[s], 1)["loss"] for s in range(xs.size(0))])
-    ref = z["losses"]
-    print("DVGT-GATE curve: worst loss ratio", np.abs(losses / ref - 1).max())
-    assert len(ref) == 20 and np.max(np.abs(losses[:3] - ref[:3]) / ref[:3]) < 1e-4
-    assert np.max(np.abs(losses - ref) / ref) < 2e-3
-    algo.eval()
-    with torch.no_grad():
-        assert rel(algo.model(xs[0]).cpu().numpy(), z["eval_pred_end"]) < 5e-3
+    K.curve_check("DVGTformer", "DVGT", cfg, z, sd0, dict(steps=20, first3=1e-4, every=2e-3, eval=5e-3), dropout_off=True)
 
 
 def test_trainer_matches_reference_harness_run_on_cmapss(tmp_path, monkeypatch):
     """--GNN_method DVGTformer on C-MAPSS FD001 as the reference wires it: the reference's own harness, run on the CPU by
     tests/golden/make_golden_dvgtformer.py::case_trainer_cmapss with dropout switched off on the constructed model, vs this package's
     harness on the GPU with the same switch.  Bars: those of the other families' harness tests (tests/test_trainer_gpu.py)."""
-    import sys
-    sys.path.insert(0, GOLD)
-    from synth import synthetic_cmapss
-    from gnn_rul_benchmarking_amd import trainer as T
     z = np.load(os.path.join(GOLD, "dvgtformer_trainer_fd001_reference_run.npz"))
-    (xtr, ytr), (xte, yte) = synthetic_cmapss(int(z["seed"]), int(z["n_train"]), int(z["n_test"]))
-    assert abs(xtr.astype(np.float64).sum() - float(z["x_train_checksum"])) < 1e-6
-    d = tmp_path / "data" / "CMAPSS" / "FD001"
-    os.makedirs(d)
-    torch.save({"samples": xtr, "labels": ytr, "max_ruls": 125}, d / "train.pt")
-    torch.save({"samples": xte, "labels": yte, "max_ruls": 125}, d / "test.pt")
-    monkeypatch.chdir(tmp_path)
-    base = T.get_algorithm_class("DVGTformer")
 
-    class NoDropout(base):
-        def __init__(self, *a, **k):
-            super().__init__(*a, **k)
-            self.model.dropout_p = 0.0
-    monkeypatch.setattr(T, "get_algorithm_class", lambda n: NoDropout)
-    args = argparse.Namespace(save_dir=str(tmp_path / "logs"), experiment_description="exp", run_description="r",
-                              GNN_method="DVGTformer", data_path=str(tmp_path / "data"), dataset="CMAPSS",
-                              dataset_id="FD001", bearing_id=None, num_runs=1, device=DEV)
-    tr = T.GNN_RUL_trainer(args)
-    tr.train_configs["num_epochs"] = int(z["epochs"])
-    assert tr.train_configs["batch_size"] == int(z["batch_size"]) and tr.train_configs["learning_rate"] == float(z["lr"])
-    assert tr.model_configs == FD
-    per_epoch = []
-    orig = tr.calc_results_per_run
-
-    def spy(run_id):
-        per_epoch.append(T._calc_metrics(tr.pred_labels, tr.true_labels, tr.max_ruls))
-        return orig(run_id)
-    tr.calc_results_per_run = spy
-    tr.train()
-    got, ref = np.asarray(per_epoch, np.float64), z["per_epoch"]
-    print("DVGT harness per-epoch got/ref:\n", got, "\n", ref)
-    assert got.shape == ref.shape == (int(z["epochs"]), 4)
-    assert np.max(np.abs(got[:, 2:] - ref[:, 2:]) / np.abs(ref[:, 2:])) < 1e-3      # MAE, RMSE (in RUL cycles), relative
-    assert np.max(np.abs(got[:, 3] - ref[:, 3]) / 125.0) < 1e-3                      # RMSE on the normalised scale, absolute
-    sd = tr.algorithm.state_dict()
-    for k in z.files:
-        if k.startswith("final:"):
-            a, b = sd["model." + k[6:]].cpu().numpy().astype(np.float64), z[k].astype(np.float64)
-            assert np.max(np.abs(a - b)) / max(np.max(np.abs(b)), 1e-30) < 3e-3, k
+    def row(tr):
+        assert tr.train_configs["batch_size"] == int(z["batch_size"]) and tr.train_configs["learning_rate"] == float(z["lr"])
+        assert tr.model_configs == FD
+    tr, per_epoch = K.harness_run(tmp_path, monkeypatch, "DVGTformer", "CMAPSS", "FD001", z, no_dropout=K.model_dropout_off, configure=row)
+    K.assert_harness("DVGT", per_epoch, K.state_of(tr), z,        # MAE, RMSE (in RUL cycles), relative; RMSE on the normalised scale, absolute
+                     dict(rmse_abs=1e-3, rmse_scale=125.0, rel=1e-3, rel_from=2, final=3e-3, final_prefix="model."))
 
 
 # ---- 8. coverage -----------------------------------------------------------------------------------------------------------------------
@@ -382,10 +278,4 @@ def test_trainer_matches_reference_harness_run_on_cmapss(tmp_path, monkeypatch):
                                  make_cfg(2, 1, d=(1, 1025))], ids=["N25", "L57", "H9", "nb9", "ff129", "d1025"])
 def test_just_outside_each_limit_is_not_covered_and_launches_nothing(cfg):
     from gnn_rul_benchmarking_amd.dvgtformer import DVGTformer_model
-    m = DVGTformer_model(**cfg).to(DEV)
-    x = torch.rand(2, cfg["num_nodes"], cfg["time_length"], device=DEV)
-    with pytest.raises(RuntimeError, match="do not cover this configuration"):
-        m(x)
-    with pytest.raises(RuntimeError, match="do not cover this configuration"):
-        m.fused_mse_step(x, torch.zeros(2, device=DEV))
-    assert not m._bufs and not m.bucket.any()                  # no workspace was made, nothing was written
+    K.refused_outside_limits(DVGTformer_model(**cfg), torch.rand(2, cfg["num_nodes"], cfg["time_length"], device=DEV))

@@ -13,8 +13,9 @@ import pytest
 import adam_reference as AR
 import grad_gate as GG
 import dvgtformer_oracle as O
+import family_kit as K
+from family_kit import GOLD, rel_same_shape as rel
 
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
 SMALL = ["dvgtformer_small_3x4_h1_b1_bs3", "dvgtformer_small_5x7_h2_b2_bs4"]
 FULL = ["dvgtformer_fdgeom_bs3", "dvgtformer_ncmapssgeom_bs3"]
 CURVE = "dvgtformer_train_curve_5x7_bs8"
@@ -22,21 +23,9 @@ RTOL = 5e-4          # the family's starting gradient gate (AGCN_TF's, tests/tes
 TAPS = ("x0", "enc", "a_temp", "a_spat")
 
 
-def rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    assert a.shape == b.shape, (a.shape, b.shape)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
-
-
-def seeded_state(cfg, seed, model_class=None):
-    """The constructor's state dict under ``seed``, moved away from init as the fixtures' maker does.  ``model_class``: the package's
-    module (the tests that rebuild a full-geometry fixture's weights); default: nn.Linear / LayerNorm holders in the same order."""
-    import torch
+def seeded_state(cfg, seed):
     from gnn_rul_benchmarking_amd.dvgtformer import DVGTformer_model
-    torch.manual_seed(seed)
-    m = (model_class or DVGTformer_model)(**cfg)
-    g = torch.Generator().manual_seed(seed + 1000)
-    return {k: (v + torch.empty_like(v).uniform_(-0.1, 0.1, generator=g)).numpy().copy() for k, v in m.state_dict().items()}
+    return K.seeded_state(DVGTformer_model, cfg, seed)
 
 
 @functools.lru_cache(maxsize=None)

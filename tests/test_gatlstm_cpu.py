@@ -13,6 +13,7 @@ from gnn_rul_benchmarking_amd import _lib
 
 from conftest import GOLDEN
 
+import family_kit as K
 import gatlstm_oracle as O
 from test_gatlstm_oracle_golden import CURVE, FULL, NAN, SMALL, load_case
 
@@ -41,11 +42,7 @@ def shape_of(batch, cfg):
 
 
 def test_registry_serves_the_algorithm_and_refuses_the_model():
-    from gnn_rul_benchmarking_amd import algorithms as A
-    assert A.get_algorithm_class("GAT_LSTM") is A.GAT_LSTM
-    with pytest.raises(NotImplementedError, match="Algorithm not found: GAT_LSTM_model"):
-        A.get_algorithm_class("GAT_LSTM_model")
-    assert A.GAT_LSTM.needs_train_mode == "dropout" and A.GAT_LSTM.supports_graphs is False
+    K.registry_check("GAT_LSTM")
 
 
 @pytest.mark.parametrize("key", list(ROWS))
@@ -109,18 +106,9 @@ def test_a_seed_gives_the_reference_keys_and_initial_values(name):
 
 
 def test_hparams_rows_equal_the_reference():
-    from gnn_rul_benchmarking_amd.hparams import get_hparams_class
-    z = np.load(os.path.join(GOLDEN, "gatlstm_hparams_rows.npz"))
-    rows = json.loads(str(z["rows_json"]))
-    assert sorted(rows) == sorted(ROWS)
-    for key, ref in rows.items():
-        ds, did = key.split("/")
-        h = get_hparams_class(ds)(did)
-        assert h.train_params["GAT_LSTM"] == ref["train_params"] and h.alg_hparams["GAT_LSTM"] == ref["alg_hparams"] == row_cfg(key), key
-        assert h.train_params["GAT_LSTM"] == {'num_epochs': 81, 'batch_size': 100, 'weight_decay': 1e-4, 'learning_rate': 1e-4}
-    assert sorted(json.loads(str(z["absent_json"]))) == ["CMAPSS/FD001", "CMAPSS/FD002", "CMAPSS/FD003", "CMAPSS/FD004", "NCMAPSS/None"]
-    for h in [get_hparams_class("CMAPSS")(d) for d in ("FD001", "FD002", "FD003", "FD004")] + [get_hparams_class("NCMAPSS")(None)]:
-        assert "GAT_LSTM" not in h.alg_hparams and "GAT_LSTM" not in h.train_params
+    train = {'num_epochs': 81, 'batch_size': 100, 'weight_decay': 1e-4, 'learning_rate': 1e-4}
+    absent = ["CMAPSS/FD001", "CMAPSS/FD002", "CMAPSS/FD003", "CMAPSS/FD004", "NCMAPSS/None"]
+    K.hparams_rows_check("GAT_LSTM", "gatlstm_hparams_rows.npz", {key: (train, row_cfg(key)) for key in ROWS}, absent, absent_is_all=True)
 
 
 LIMIT_NAMES = (("MAX_NUM_PATCH", "max_num_patch"), ("MIN_PATCH_SIZE", "min_patch_size"), ("MAX_PATCH_SIZE", "max_patch_size"),
@@ -231,11 +219,7 @@ def test_out_of_limit_model_constructs_and_is_refused_before_the_library_is_touc
 
 def test_cpu_input_raises():
     from gnn_rul_benchmarking_amd.gatlstm import GAT_LSTM_model
-    m = GAT_LSTM_model(**TINY)
-    with pytest.raises(RuntimeError, match="HIP path only"):
-        m(torch.zeros(2, 4))
-    with pytest.raises(RuntimeError, match="HIP path only"):
-        m.fused_mse_step(torch.zeros(2, 4), torch.zeros(2))
+    K.cpu_input_raises(GAT_LSTM_model(**TINY), torch.zeros(2, 4))
 
 
 def test_fixtures_hold_no_grad_key_and_stay_small():

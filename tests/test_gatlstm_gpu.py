@@ -21,14 +21,12 @@ import numpy as np
 import pytest
 import torch
 
-import adam_reference as R
-import grad_gate as GG
+import family_kit as K
 import gatlstm_oracle as O
-from test_gatlstm_oracle_golden import CURVE, FULL, NAN, SMALL, load_case, oracle_run, rel, rel_finite, seeded_weights
+from family_kit import DEV, GOLD, dev, grads_of, rel, rel_finite
+from test_gatlstm_oracle_golden import CURVE, FULL, NAN, SMALL, load_case, oracle_run, seeded_weights
 
 pytestmark = pytest.mark.gpu
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
-DEV = "cuda:0"
 TOL, RTOL = 1e-4, 5e-4 / 2 ** 9
 LADDER = [5e-4 / 2 ** k for k in range(13)]
 
@@ -42,57 +40,19 @@ TINY = make_cfg(3, 4, [5, 4, 3])
 
 def build_model(cfg, sd, dropout=0.0):
     from gnn_rul_benchmarking_amd.gatlstm import GAT_LSTM_model
-    m = GAT_LSTM_model(**cfg)
-    m.load_state_dict({k: torch.from_numpy(np.asarray(v, np.float32)) for k, v in sd.items()}, strict=True)
-    m.dropout_p = dropout
-    return m.to(DEV)
-
-
-def grads_of(m, bucket=None):
-    flat = (m._grad_flat if bucket is None else bucket)[:m.num_live].detach().cpu().numpy().astype(np.float64)
-    return {name: flat[off:off + int(np.prod(shape))].reshape(shape) for name, (off, shape) in m._layout.items()}
-
-
-def dev(a):
-    return torch.from_numpy(np.asarray(a, np.float32)).to(DEV)
+    return K.build_model(GAT_LSTM_model, cfg, sd, dropout)
 
 
 def check_grads(what, got, g64, ref32):
-    """Every tensor through the element-wise gate.  Returns the names detected as zero in exact arithmetic."""
-    zero = GG.zero_in_exact_arithmetic(g64, ref32)
-    gmax = max(float(np.abs(v).max()) for v in g64.values())
-    ladder = np.zeros(len(LADDER))
-    worst = (0.0, None)
-    for k in g64:
-        assert got[k].shape == g64[k].shape, k
-        if k in zero:               # rounding residue of a sum that cancels: at most the reference's own, or fp32 ulps of the model's largest gradient
-            bound = 16 * max(float(np.abs(ref32[k]).max()) if ref32.get(k) is not None else 0.0, 2.0 ** -23 * gmax)
-            assert np.abs(got[k]).max() <= bound, (k, np.abs(got[k]).max(), bound)
-            continue
-        floor = GG.floor_for(ref32[k], g64[k])
-        if O.noise_partner(k):          # a one-element tensor shares its layer's attention.weight noise (gatlstm_oracle.noise_partner)
-            floor = max(floor, GG.floor_for(ref32[O.noise_partner(k)], g64[O.noise_partner(k)]))
-        ladder = np.maximum(ladder, [GG.gate(got[k], g64[k], r, floor)[0] for r in LADDER])
-        ratio, where = GG.gate(got[k], g64[k], RTOL, floor)
-        if ratio > 0.25:
-            print(f"  grad {k}: gate {ratio:.3f} at {where}  rel {rel(got[k], g64[k]):.2e}  max|g| {np.abs(g64[k]).max():.2e}")
-        worst = max(worst, (ratio, k))
-    print(f"GATLSTM-GATE {what}: worst gradient gate ratio {worst[0]:.3f} ({worst[1]}); zero in exact arithmetic: {zero}")
-    print(f"GATLSTM-LADDER {what}: " + " ".join(f"{v:.3f}" for v in ladder))
-    assert worst[0] <= 1.0, worst
-    return zero
+    """Every tensor through the element-wise gate.  Returns the names detected as zero in exact arithmetic (family_kit.residue_bound)."""
+    return K.check_grads(what, "GATLSTM", got, g64, ref32, RTOL, K.RESIDUE, noise_partner=O.noise_partner, ladder=LADDER)
 
 
 def check_forward(what, m, bs, pred, loss, want, want_loss):
-    errs = {"pred": rel_finite(pred.detach().cpu().numpy().reshape(-1), np.asarray(want["pred"]).reshape(-1))}
-    for k in ["feat", "lstm"] + [f"h{l}" for l in range(len(m.hidden_dim))]:
-        if k in want:
-            errs[k] = rel_finite(m.tap(bs, k).cpu().numpy(), want[k])          # NaN exactly where the expected one is
-    if loss is not None and np.isfinite(want_loss):
-        errs["loss"] = abs(float(loss) - want_loss) / abs(want_loss)
-    print(f"GATLSTM-GATE {what}: forward " + " ".join(f"{k}={v:.2e}" for k, v in errs.items()))
-    for k, v in errs.items():
-        assert v < TOL, (k, v)
+    taps = [k for k in ["feat", "lstm"] + [f"h{l}" for l in range(len(m.hidden_dim))] if k in want]
+    errs = {**K.pred_err(pred, want, rel_finite), **K.tap_errs(m, bs, want, taps, rel_finite, same_shape=False),      # NaN exactly where the expected one is
+            **(K.loss_err(loss, want_loss) if np.isfinite(want_loss) else {})}
+    K.check_forward(what, "GATLSTM", errs, TOL)
 
 
 def fixture_grads(name):
@@ -257,115 +217,40 @@ def test_two_runs_give_the_same_bits(case):
 
 # ---- 6. the optimizer, the curve, the harness -------------------------------------------------------------------------------------------
 def test_fused_step_applies_adam_to_every_element_once():
-    """The twin-model procedure of tests/test_fused_adam_families_gpu.py (bounds from tests/adam_reference.py), dropout and weight decay
-    on: every element of the flat buffer within the bounds."""
-    from gnn_rul_benchmarking_amd.optim import FusedAdam
-    from test_fused_adam_families_gpu import LR, SEED, STEP0, WD, _bits, _np
+    """The twin-model procedure (family_kit.adam_twin_check), dropout and weight decay on: every element of the flat buffer within the
+    bounds."""
     z, cfg, sd = load_case(SMALL[1])
-    x, y = dev(z["x"]), dev(z["y"])
-    assert WD > 0
-
-    def ready():
-        m = build_model(cfg, sd, dropout=0.2).train()
-        m._seed = SEED
-        return m
-    a = ready()
-    p0 = _np(a.flat_params)
-    _, loss_a = a.fused_mse_step(x, y)
-    g_a, loss_a = _np(a.bucket[:a.num_live]), float(loss_a)
-    assert np.isfinite(g_a).all() and np.array_equal(_bits(_np(a.flat_params)), _bits(p0))
-    b = ready()
-    opt = FusedAdam(b, lr=LR, weight_decay=WD)
-    m0, v0 = R.moments_like(g_a, np.random.default_rng(12))
-    s = opt.state_dict()
-    s.update(step=STEP0, exp_avg=torch.from_numpy(m0).to(DEV), exp_avg_sq=torch.from_numpy(v0).to(DEV))
-    opt.load_state_dict(s)
-    worst = dict(p=0.0, m=0.0, v=0.0)
-    for k in (STEP0 + 1, STEP0 + 2, STEP0 + 3):
-        before = tuple(_np(t) for t in (b.flat_params, opt._exp_avg, opt._exp_avg_sq))
-        _, loss_b = b.fused_mse_step(x, y, opt)
-        g = _np(b.bucket[:b.num_live])
-        after = tuple(_np(t) for t in (b.flat_params, opt._exp_avg, opt._exp_avg_sq))
-        if k == STEP0 + 1:
-            assert np.array_equal(_bits(g), _bits(g_a)) and float(loss_b) == loss_a
-        r = R.check(after, before[0], g, before[1], before[2], k, WD, 1.0, what=f"GAT_LSTM, step {k}")
-        worst = {q: max(worst[q], r[q]) for q in worst}
-    assert opt._steps == STEP0 + 3
-    print("ADAM-RATIO family GAT_LSTM: " + " ".join(f"{q}={worst[q]:.3f}" for q in "pmv"))
+    K.adam_twin_check(lambda: build_model(cfg, sd, dropout=0.2).train(), dev(z["x"]), dev(z["y"]), "GAT_LSTM")
 
 
 def test_training_curve_matches_reference_algorithm():
     """Twenty update() steps against the reference's own.  Tolerances: GRU_CM's curve tolerances (tests/test_grucm_gpu.py: the first
     three losses 1e-4, every loss 2e-3, the eval prediction at the end 5e-3)."""
-    from gnn_rul_benchmarking_amd.algorithms import get_algorithm_class
     z = np.load(os.path.join(GOLD, CURVE + ".npz"))
     cfg = json.loads(str(z["cfg_json"]))
-    algo = get_algorithm_class("GAT_LSTM")(cfg, {"learning_rate": float(z["lr"]), "weight_decay": float(z["wd"])}, DEV)
-    algo.model.load_state_dict({k[4:]: torch.from_numpy(z[k]) for k in z.files if k.startswith("sd0:")}, strict=True)
-    assert algo.model.dropout_p == 0.0
-    algo.to(DEV).train()
-    xs, ys = torch.from_numpy(z["xs"]).to(DEV), torch.from_numpy(z["ys"]).to(DEV)
-    losses = np.asarray([algo.update(xs[s], ys[s], 1)["loss"] for s in range(xs.size(0))])
-    ref = z["losses"]
-    print("GATLSTM-GATE curve: worst loss ratio", np.abs(losses / ref - 1).max())
-    assert len(ref) == 20 and np.max(np.abs(losses[:3] - ref[:3]) / ref[:3]) < 1e-4
-    assert np.max(np.abs(losses - ref) / ref) < 2e-3
-    sd = algo.model.state_dict()
-    for k in O.param_names(cfg):
-        assert rel(sd[k].cpu().numpy(), z["sd20:" + k]) < 2e-3, k
-    algo.eval()
-    with torch.no_grad():
-        assert rel(algo.model(xs[0]).cpu().numpy(), z["eval_pred_end"]) < 5e-3
+    sd0 = {k[4:]: z[k] for k in z.files if k.startswith("sd0:")}
+    _, sd = K.curve_check("GAT_LSTM", "GATLSTM", cfg, z, sd0, dict(steps=20, first3=1e-4, every=2e-3, params=2e-3, eval=5e-3), dropout_off=False)
+    assert list(sd) == O.param_names(cfg)
 
 
 def test_trainer_matches_reference_harness_run_on_phm2012(tmp_path, monkeypatch):
     """--GNN_method GAT_LSTM on PHM2012 Condition_1 as the reference wires it: the reference's own harness, run on the CPU by
     tests/golden/make_golden_gatlstm.py::case_trainer_phm2012 with the row's dropout set to 0, vs this package's harness on the GPU with
     the same switch.  Bars: those of tests/test_trainer_gpu.py's harness tests."""
-    import argparse
-    import sys
     import pandas as pd
-    sys.path.insert(0, GOLD)
-    from synth import synthetic_phm2012
-    from gnn_rul_benchmarking_amd import trainer as T
     z = np.load(os.path.join(GOLD, "gatlstm_trainer_phm2012_c1_reference_run.npz"))
-    (xtr, ytr), (xte, yte) = synthetic_phm2012(int(z["seed"]), int(z["n_train"]), int(z["n_test"]))
-    assert abs(xtr.astype(np.float64).sum() - float(z["x_train_checksum"])) < 1e-6
-    d = tmp_path / "data" / "PHM2012" / "Condition_1"
-    os.makedirs(d)
-    torch.save({"samples": xtr, "labels": ytr, "max_ruls": 1.0}, d / "train.pt")
-    torch.save({"samples": xte, "labels": yte, "max_ruls": 1.0}, d / "test.pt")
-    monkeypatch.chdir(tmp_path)
-    args = argparse.Namespace(save_dir=str(tmp_path / "logs"), experiment_description="exp", run_description="r",
-                              GNN_method="GAT_LSTM", data_path=str(tmp_path / "data"), dataset="PHM2012",
-                              dataset_id="Condition_1", bearing_id="Testing_bearing_1", num_runs=1, device=DEV)
-    tr = T.GNN_RUL_trainer(args)
-    tr.train_configs["num_epochs"] = int(z["epochs"])
-    assert tr.train_configs["batch_size"] == int(z["batch_size"]) and tr.train_configs["learning_rate"] == float(z["lr"])
-    assert tr.model_configs == dict(load_case(FULL[0])[1], dropout=0.2)
-    tr.model_configs["dropout"] = 0.0
-    per_epoch = []
-    orig = tr.calc_results_per_run
 
-    def spy(run_id):
-        per_epoch.append(T._calc_metrics(tr.pred_labels, tr.true_labels, tr.max_ruls))
-        return orig(run_id)
-    tr.calc_results_per_run = spy
-    tr.train()
-    got, ref = np.asarray(per_epoch, np.float64), z["per_epoch"]
-    print("GATLSTM harness per-epoch got/ref:\n", got, "\n", ref)
-    assert got.shape == ref.shape == (int(z["epochs"]), 4)
-    assert np.max(np.abs(got[:, 3] - ref[:, 3])) < 1e-3                              # RMSE, absolute (north star)
-    assert np.max(np.abs(got[:, 2:] - ref[:, 2:]) / np.abs(ref[:, 2:])) < 1e-3      # MAE, RMSE relative
+    def row(tr):
+        assert tr.train_configs["batch_size"] == int(z["batch_size"]) and tr.train_configs["learning_rate"] == float(z["lr"])
+        assert tr.model_configs == dict(load_case(FULL[0])[1], dropout=0.2)
+        tr.model_configs["dropout"] = 0.0
+    tr, per_epoch = K.harness_run(tmp_path, monkeypatch, "GAT_LSTM", "PHM2012", "Condition_1", z, configure=row)
+    K.assert_harness("GATLSTM", per_epoch, K.state_of(tr), z,     # RMSE, absolute (north star); MAE, RMSE relative
+                     dict(rmse_abs=1e-3, rmse_scale=1.0, rel=1e-3, rel_from=2, final=2e-3, final_prefix="model."))
     csv = pd.read_csv(tmp_path / "logs" / "exp" / "r" / "GAT_LSTM_run_0" / "results.csv")
     ref_csv = pd.read_csv(io.StringIO(str(z["csv_text"])))
     assert list(csv.columns) == list(ref_csv.columns) and len(csv) == len(ref_csv)
     assert np.allclose(csv.iloc[1:].to_numpy()[:, 2:], ref_csv.iloc[1:].to_numpy()[:, 2:], rtol=2e-3)
-    sd = tr.algorithm.state_dict()
-    for k in z.files:
-        if k.startswith("final:"):
-            a, b = sd["model." + k[6:]].cpu().numpy().astype(np.float64), z[k].astype(np.float64)
-            assert np.max(np.abs(a - b)) / max(np.max(np.abs(b)), 1e-30) < 2e-3, k
 
 
 # ---- 7. NaN ----------------------------------------------------------------------------------------------------------------------------
@@ -390,10 +275,4 @@ def test_nan_fixture_poisons_exactly_its_own_samples():
                          ids=["num_patch129", "patch_size3", "patch_size2049", "width513", "five-layers", "lstm129", "four-lstm-layers"])
 def test_just_outside_each_limit_is_not_covered_and_launches_nothing(cfg):
     from gnn_rul_benchmarking_amd.gatlstm import GAT_LSTM_model
-    m = GAT_LSTM_model(**cfg).to(DEV)
-    x = torch.rand(2, cfg["num_patch"] * cfg["patch_size"], device=DEV)
-    with pytest.raises(RuntimeError, match="do not cover this configuration"):
-        m(x)
-    with pytest.raises(RuntimeError, match="do not cover this configuration"):
-        m.fused_mse_step(x, torch.zeros(2, device=DEV))
-    assert not m._bufs and not m._grad_flat.any()                  # no workspace was made, nothing was written
+    K.refused_outside_limits(GAT_LSTM_model(**cfg), torch.rand(2, cfg["num_patch"] * cfg["patch_size"], device=DEV))

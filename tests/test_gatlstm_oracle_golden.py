@@ -12,6 +12,7 @@ import torch
 from conftest import GOLDEN
 
 import gatlstm_oracle as O
+from family_kit import rel, rel_finite, seeded_state
 
 SMALL = ["gatlstm_small_t3_p4_bs4", "gatlstm_small_t5_p8_bs3"]
 FULL = ["gatlstm_geom_40x64_bs2", "gatlstm_geom_80x32_bs2", "gatlstm_geom_32x1024_bs2"]
@@ -27,10 +28,7 @@ def seeded_weights(cfg, seed):
     """The maker's weights: the constructor's under the seed (the package's module draws in the reference's order), moved by the
     recorded perturbation."""
     from gnn_rul_benchmarking_amd.gatlstm import GAT_LSTM_model
-    torch.manual_seed(seed)
-    sd = GAT_LSTM_model(**cfg).state_dict()
-    g = torch.Generator().manual_seed(seed + 1000)
-    return {k: (v.clone() + torch.empty_like(v).uniform_(-0.1, 0.1, generator=g)).numpy() for k, v in sd.items()}
+    return seeded_state(GAT_LSTM_model, cfg, seed)
 
 
 class Case:
@@ -71,19 +69,6 @@ def oracle_run(name):
         z, cfg, P = load_case(name)
         _cache[key] = O.forward_backward(P, z["x"], z["y"], cfg)
     return _cache[key]
-
-
-def rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
-
-
-def rel_finite(a, b):
-    """``rel`` over the entries where ``b`` is finite; NaN must sit in the same places."""
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64).reshape(np.asarray(a).shape)
-    assert np.array_equal(np.isnan(a), np.isnan(b))
-    ok = ~np.isnan(b)
-    return rel(a[ok], b[ok]) if ok.any() else 0.0
 
 
 @pytest.mark.parametrize("name", SMALL + FULL)

@@ -21,14 +21,12 @@ import numpy as np
 import pytest
 import torch
 
-import adam_reference as R
-import grad_gate as GG
+import family_kit as K
 import gdagdl_oracle as O
-from test_gdagdl_oracle_golden import CURVE, FULL, SMALL, load_case, oracle_run, rel, seeded_weights
+from family_kit import DEV, GOLD, dev, grads_of, rel
+from test_gdagdl_oracle_golden import CURVE, FULL, SMALL, load_case, oracle_run, seeded_weights
 
 pytestmark = pytest.mark.gpu
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
-DEV = "cuda:0"
 TOL, RTOL = 1e-4, 5e-4 / 2 ** 10
 LADDER = [5e-4 / 2 ** k for k in range(13)]
 
@@ -43,67 +41,26 @@ TINY = make_cfg(4, 3, 3, [5, 4, 3])
 
 def build_model(cfg, sd, dropout=0.0):
     from gnn_rul_benchmarking_amd.gdagdl import GDAGDL_model
-    m = GDAGDL_model(**cfg)
-    m.load_state_dict({k: torch.from_numpy(np.asarray(v, np.float32)) for k, v in sd.items()}, strict=True)
-    m.dropout_p = dropout
-    return m.to(DEV)
-
-
-def grads_of(m, bucket=None):
-    flat = (m._grad_flat if bucket is None else bucket)[:m.num_live].detach().cpu().numpy().astype(np.float64)
-    return {name: flat[off:off + int(np.prod(shape))].reshape(shape) for name, (off, shape) in m._layout.items()}
-
-
-def dev(a):
-    return torch.from_numpy(np.asarray(a, np.float32)).to(DEV)
+    return K.build_model(GDAGDL_model, cfg, sd, dropout)
 
 
 def check_grads(what, got, g64, ref32, cfg):
     """Every live tensor through the element-wise gate; the two gradless tensors' entries must be exact zeros.  Returns the names
-    detected as zero in exact arithmetic."""
-    for k in O.GRADLESS:
-        assert not got[k].any(), k
-    zero = GG.zero_in_exact_arithmetic(g64, ref32)
-    gmax = max(float(np.abs(v).max()) for v in g64.values())
-    ladder = np.zeros(len(LADDER))
-    worst = (0.0, None)
-    for k in g64:
-        assert got[k].shape == g64[k].shape, k
-        if k in zero:               # rounding residue of a sum that cancels: at most the reference's own, or fp32 ulps of the model's largest gradient
-            bound = 16 * max(float(np.abs(ref32[k]).max()), 2.0 ** -23 * gmax)
-            assert np.abs(got[k]).max() <= bound, (k, np.abs(got[k]).max(), bound)
-            continue
-        floor = GG.floor_for(ref32[k], g64[k])
-        if O.noise_partner(k):          # a one-element tensor shares its layer's attention.weight noise (gdagdl_oracle.noise_partner)
-            floor = max(floor, GG.floor_for(ref32[O.noise_partner(k)], g64[O.noise_partner(k)]))
-        ladder = np.maximum(ladder, [GG.gate(got[k], g64[k], r, floor)[0] for r in LADDER])
-        ratio, where = GG.gate(got[k], g64[k], RTOL, floor)
-        if ratio > 0.25:
-            print(f"  grad {k}: gate {ratio:.3f} at {where}  rel {rel(got[k], g64[k]):.2e}  max|g| {np.abs(g64[k]).max():.2e}")
-        worst = max(worst, (ratio, k))
-    print(f"GDAGDL-GATE {what}: worst gradient gate ratio {worst[0]:.3f} ({worst[1]}); zero in exact arithmetic: {zero}")
-    print(f"GDAGDL-LADDER {what}: " + " ".join(f"{v:.3f}" for v in ladder))
-    assert worst[0] <= 1.0, worst
-    return zero
+    detected as zero in exact arithmetic (held to family_kit.residue_bound)."""
+    return K.check_grads(what, "GDAGDL", got, g64, ref32, RTOL, K.RESIDUE, exact_zero=O.GRADLESS, noise_partner=O.noise_partner, ladder=LADDER)
 
 
 def check_forward(what, m, bs, pred, loss, want, want_loss, want_recon=None):
-    errs = {"pred": rel(pred.detach().cpu().numpy().reshape(-1), np.asarray(want["pred"]).reshape(-1))}
-    for k in ("mag", "yo", "H"):
-        if k in want:
-            errs[k] = rel(m.tap(bs, k).cpu().numpy(), np.asarray(want[k]).reshape(m.tap(bs, k).shape))
+    errs = {**K.pred_err(pred, want), **K.tap_errs(m, bs, want, [k for k in ("mag", "yo", "H") if k in want], same_shape=False)}
     ni, wni = m.tap(bs, "ni").cpu().numpy(), np.asarray(want["ni"])
     assert np.array_equal(np.isnan(ni), np.isnan(wni)), what                       # NaN exactly where the reference's is
     assert np.array_equal(m.tap(bs, "mask").cpu().numpy(), np.asarray(want["mask"], np.float32)), what      # element for element
     if not np.isnan(ni).all():
         errs["ni"] = rel(ni[~np.isnan(ni)], wni[~np.isnan(wni)])
-    if loss is not None:
-        errs["loss"] = abs(float(loss) - want_loss) / abs(want_loss)
+    errs.update(K.loss_err(loss, want_loss))
     if want_recon is not None:
         errs["recon"] = abs(float(m._grad_flat[m.num_live + 1]) - want_recon) / abs(want_recon)
-    print(f"GDAGDL-GATE {what}: forward " + " ".join(f"{k}={v:.2e}" for k, v in errs.items()))
-    for k, v in errs.items():
-        assert v < TOL, (k, v)
+    K.check_forward(what, "GDAGDL", errs, TOL)
 
 
 @functools.lru_cache(maxsize=None)
@@ -282,72 +239,25 @@ def test_two_runs_give_the_same_bits(case):
 
 # ---- 6. the optimizer, the curve ---------------------------------------------------------------------------------------------------------
 def test_fused_step_applies_adam_to_every_live_element_once_and_never_to_the_gradless():
-    """The twin-model procedure of tests/test_fused_adam_families_gpu.py (bounds from tests/adam_reference.py), dropout and weight decay
-    on: the optimized range [f + 1, count) within the bounds, the two gradless tensors' parameters and moments bit-identical and their
-    bucket entries exact zeros."""
-    from gnn_rul_benchmarking_amd.optim import FusedAdam
-    from test_fused_adam_families_gpu import LR, SEED, STEP0, WD, _bits, _np
+    """The twin-model procedure (family_kit.adam_twin_check), dropout and weight decay on: the optimized range [f + 1, count) within the
+    bounds, the two gradless tensors' parameters and moments bit-identical and their bucket entries exact zeros."""
+    from test_fused_adam_families_gpu import _bits, _np
     z, cfg, sd = load_case(SMALL[1])
-    x, y = dev(z["x"]), dev(z["y"])
     f1 = cfg["input_dim"] + 1
-    assert WD > 0
-
-    def ready():
-        m = build_model(cfg, sd, dropout=0.5).train()
-        m._seed = SEED
-        return m
-    a = ready()
-    p0 = _np(a.flat_params)
-    _, loss_a = a.fused_mse_step(x, y)
-    g_a, loss_a = _np(a.bucket[:a.num_live]), float(loss_a)
-    assert np.isfinite(g_a).all() and np.array_equal(_bits(_np(a.flat_params)), _bits(p0)) and not g_a[:f1].any()
-    b = ready()
+    b = K.adam_twin_check(lambda: build_model(cfg, sd, dropout=0.5).train(), dev(z["x"]), dev(z["y"]), "GDAGDL", first=f1)
     assert b.optimized_range == (f1, b.num_live)
-    opt = FusedAdam(b, lr=LR, weight_decay=WD)
-    m0, v0 = R.moments_like(g_a, np.random.default_rng(12))
-    s = opt.state_dict()
-    s.update(step=STEP0, exp_avg=torch.from_numpy(m0).to(DEV), exp_avg_sq=torch.from_numpy(v0).to(DEV))
-    opt.load_state_dict(s)
-    worst = dict(p=0.0, m=0.0, v=0.0)
-    for k in (STEP0 + 1, STEP0 + 2, STEP0 + 3):
-        before = tuple(_np(t) for t in (b.flat_params, opt._exp_avg, opt._exp_avg_sq))
-        _, loss_b = b.fused_mse_step(x, y, opt)
-        g = _np(b.bucket[:b.num_live])
-        after = tuple(_np(t) for t in (b.flat_params, opt._exp_avg, opt._exp_avg_sq))
-        if k == STEP0 + 1:
-            assert np.array_equal(_bits(g), _bits(g_a)) and float(loss_b) == loss_a
-        assert not g[:f1].any()
-        for got, was in zip(after, before):
-            assert np.array_equal(_bits(got[:f1]), _bits(was[:f1]))               # no update, no weight decay, no moment
-        r = R.check(tuple(t[f1:] for t in after), before[0][f1:], g[f1:], before[1][f1:], before[2][f1:], k, WD, 1.0, what=f"GDAGDL, step {k}")
-        worst = {q: max(worst[q], r[q]) for q in worst}
-    assert opt._steps == STEP0 + 3
     assert np.array_equal(_bits(_np(b.node_importance_linear.weight)), _bits(sd["node_importance_linear.weight"]))
     assert np.array_equal(_bits(_np(b.node_importance_linear.bias)), _bits(sd["node_importance_linear.bias"]))
-    print("ADAM-RATIO family GDAGDL: " + " ".join(f"{q}={worst[q]:.3f}" for q in "pmv"))
 
 
 def test_training_curve_matches_reference_algorithm():
     """Twenty update() steps against the reference's own.  Tolerances: GRU_CM's curve tolerances (tests/test_grucm_gpu.py: the first
     three losses 1e-4, every loss 2e-3, the eval prediction at the end 5e-3)."""
-    from gnn_rul_benchmarking_amd.algorithms import get_algorithm_class
     z = np.load(os.path.join(GOLD, CURVE + ".npz"))
     cfg = load_case(SMALL[1])[1]
     assert cfg == __import__("json").loads(str(z["cfg_json"]))
-    algo = get_algorithm_class("GDAGDL")(cfg, {"learning_rate": float(z["lr"]), "weight_decay": float(z["wd"])}, DEV)
-    algo.model.load_state_dict({k[4:]: torch.from_numpy(z[k]) for k in z.files if k.startswith("sd0:")}, strict=True)
-    algo.model.dropout_p = 0.0
-    algo.to(DEV).train()
-    xs, ys = torch.from_numpy(z["xs"]).to(DEV), torch.from_numpy(z["ys"]).to(DEV)
-    losses = np.asarray([algo.update(xs[s], ys[s], 1)["loss"] for s in range(xs.size(0))])
-    ref = z["losses"]
-    print("GDAGDL-GATE curve: worst loss ratio", np.abs(losses / ref - 1).max())
-    assert len(ref) == 20 and np.max(np.abs(losses[:3] - ref[:3]) / ref[:3]) < 1e-4
-    assert np.max(np.abs(losses - ref) / ref) < 2e-3
-    algo.eval()
-    with torch.no_grad():
-        assert rel(algo.model(xs[0]).cpu().numpy(), z["eval_pred_end"]) < 5e-3
-    sd = algo.model.state_dict()
+    sd0 = {k[4:]: z[k] for k in z.files if k.startswith("sd0:")}
+    _, sd = K.curve_check("GDAGDL", "GDAGDL", cfg, z, sd0, dict(steps=20, first3=1e-4, every=2e-3, eval=5e-3), dropout_off=True)
     for k in O.GRADLESS:
         assert torch.equal(sd[k].cpu(), torch.from_numpy(z["sd0:" + k])), k           # untouched by Adam and its weight decay
 
@@ -356,51 +266,14 @@ def test_trainer_matches_reference_harness_run_on_phm2012(tmp_path, monkeypatch)
     """--GNN_method GDAGDL on PHM2012 Condition_1 as the reference wires it: the reference's own harness, run on the CPU by
     tests/golden/make_golden_gdagdl.py::case_trainer_phm2012 with the attention dropout switched off on the constructed model, vs this
     package's harness on the GPU with the same switch.  Bars: those of tests/test_trainer_gpu.py's harness tests."""
-    import argparse
-    import sys
-    sys.path.insert(0, GOLD)
-    from synth import synthetic_phm2012
-    from gnn_rul_benchmarking_amd import trainer as T
     z = np.load(os.path.join(GOLD, "gdagdl_trainer_phm2012_c1_reference_run.npz"))
-    (xtr, ytr), (xte, yte) = synthetic_phm2012(int(z["seed"]), int(z["n_train"]), int(z["n_test"]))
-    assert abs(xtr.astype(np.float64).sum() - float(z["x_train_checksum"])) < 1e-6
-    d = tmp_path / "data" / "PHM2012" / "Condition_1"
-    os.makedirs(d)
-    torch.save({"samples": xtr, "labels": ytr, "max_ruls": 1.0}, d / "train.pt")
-    torch.save({"samples": xte, "labels": yte, "max_ruls": 1.0}, d / "test.pt")
-    monkeypatch.chdir(tmp_path)
-    base = T.get_algorithm_class("GDAGDL")
 
-    class NoDropout(base):
-        def __init__(self, *a, **k):
-            super().__init__(*a, **k)
-            self.model.dropout_p = 0.0
-    monkeypatch.setattr(T, "get_algorithm_class", lambda n: NoDropout)
-    args = argparse.Namespace(save_dir=str(tmp_path / "logs"), experiment_description="exp", run_description="r",
-                              GNN_method="GDAGDL", data_path=str(tmp_path / "data"), dataset="PHM2012",
-                              dataset_id="Condition_1", bearing_id="Testing_bearing_1", num_runs=1, device=DEV)
-    tr = T.GNN_RUL_trainer(args)
-    tr.train_configs["num_epochs"] = int(z["epochs"])
-    assert tr.train_configs["batch_size"] == int(z["batch_size"]) and tr.train_configs["learning_rate"] == float(z["lr"])
-    assert tr.model_configs == load_case(FULL[0])[1]
-    per_epoch = []
-    orig = tr.calc_results_per_run
-
-    def spy(run_id):
-        per_epoch.append(T._calc_metrics(tr.pred_labels, tr.true_labels, tr.max_ruls))
-        return orig(run_id)
-    tr.calc_results_per_run = spy
-    tr.train()
-    got, ref = np.asarray(per_epoch, np.float64), z["per_epoch"]
-    print("GDAGDL harness per-epoch got/ref:\n", got, "\n", ref)
-    assert got.shape == ref.shape == (int(z["epochs"]), 4)
-    assert np.max(np.abs(got[:, 3] - ref[:, 3])) < 1e-3                              # RMSE, absolute (north star)
-    assert np.max(np.abs(got[:, 2:] - ref[:, 2:]) / np.abs(ref[:, 2:])) < 1e-3      # MAE, RMSE relative
-    sd = tr.algorithm.state_dict()
-    for k in z.files:
-        if k.startswith("final:"):
-            a, b = sd["model." + k[6:]].cpu().numpy().astype(np.float64), z[k].astype(np.float64)
-            assert np.max(np.abs(a - b)) / max(np.max(np.abs(b)), 1e-30) < 2e-3, k
+    def row(tr):
+        assert tr.train_configs["batch_size"] == int(z["batch_size"]) and tr.train_configs["learning_rate"] == float(z["lr"])
+        assert tr.model_configs == load_case(FULL[0])[1]
+    tr, per_epoch = K.harness_run(tmp_path, monkeypatch, "GDAGDL", "PHM2012", "Condition_1", z, no_dropout=K.model_dropout_off, configure=row)
+    K.assert_harness("GDAGDL", per_epoch, K.state_of(tr), z,      # RMSE, absolute (north star); MAE, RMSE relative
+                     dict(rmse_abs=1e-3, rmse_scale=1.0, rel=1e-3, rel_from=2, final=2e-3, final_prefix="model."))
 
 
 # ---- 7. coverage -----------------------------------------------------------------------------------------------------------------------
@@ -409,10 +282,4 @@ def test_trainer_matches_reference_harness_run_on_phm2012(tmp_path, monkeypatch)
                          ids=["nperseg66", "f65", "five-layers", "width513", "lstm129", "A1025", "O1025"])
 def test_just_outside_each_limit_is_not_covered_and_launches_nothing(cfg):
     from gnn_rul_benchmarking_amd.gdagdl import GDAGDL_model
-    m = GDAGDL_model(**cfg).to(DEV)
-    x = torch.rand(2, cfg["num_patch"] * cfg["patch_size"], device=DEV)
-    with pytest.raises(RuntimeError, match="do not cover this configuration"):
-        m(x)
-    with pytest.raises(RuntimeError, match="do not cover this configuration"):
-        m.fused_mse_step(x, torch.zeros(2, device=DEV))
-    assert not m._bufs and not m._grad_flat.any()                  # no workspace was made, nothing was written
+    K.refused_outside_limits(GDAGDL_model(**cfg), torch.rand(2, cfg["num_patch"] * cfg["patch_size"], device=DEV))

@@ -11,6 +11,7 @@ import torch
 from conftest import GOLDEN
 
 import gdagdl_oracle as O
+from family_kit import rel, seeded_state
 
 SMALL = ["gdagdl_small_n3_t3_bs4", "gdagdl_small_n5_t2_bs3"]
 FULL = ["gdagdl_phmc1geom_bs2", "gdagdl_phmc3geom_bs2", "gdagdl_xjtugeom_bs2"]
@@ -24,10 +25,7 @@ def seeded_weights(cfg, seed):
     """The maker's weights: the constructor's under the seed (the package's module draws in the reference's order), moved by the
     recorded perturbation."""
     from gnn_rul_benchmarking_amd.gdagdl import GDAGDL_model
-    torch.manual_seed(seed)
-    sd = GDAGDL_model(**cfg).state_dict()
-    g = torch.Generator().manual_seed(seed + 1000)
-    return {k: (v.clone() + torch.empty_like(v).uniform_(-0.1, 0.1, generator=g)).numpy() for k, v in sd.items()}
+    return seeded_state(GDAGDL_model, cfg, seed)
 
 
 def load_case(name):
@@ -52,11 +50,6 @@ def oracle_run(name):
         z, cfg, P = load_case(name)
         _cache[key] = O.forward_backward(P, z["x"], z["y"], cfg)
     return _cache[key]
-
-
-def rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
 
 
 @pytest.mark.parametrize("name", SMALL + FULL)

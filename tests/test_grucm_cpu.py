@@ -1,7 +1,6 @@
 """CPU-side checks of the GRU_CM family: registry, module attributes, parameter layout, hparams rows (against the reference's, recorded
 by tests/golden/make_golden_grucm.py) and the host-only parts of its C entries (no kernels are launched here)."""
 import ctypes as C
-import json
 import os
 
 import numpy as np
@@ -12,6 +11,7 @@ from gnn_rul_benchmarking_amd import _lib
 
 from conftest import GOLDEN
 
+import family_kit
 import grucm_oracle as O
 
 
@@ -23,11 +23,7 @@ def _algo(ds="CMAPSS", did="FD004"):
 
 
 def test_registry_serves_the_algorithm_and_refuses_the_model():
-    from gnn_rul_benchmarking_amd import algorithms as A
-    assert A.get_algorithm_class("GRU_CM") is A.GRU_CM
-    with pytest.raises(NotImplementedError, match="Algorithm not found: GRU_CM_model"):
-        A.get_algorithm_class("GRU_CM_model")
-    assert A.GRU_CM.needs_train_mode == "dropout" and A.GRU_CM.supports_graphs is False
+    family_kit.registry_check("GRU_CM")
 
 
 def test_algorithm_attributes_and_state_dict_keys():
@@ -67,13 +63,7 @@ def test_param_layout_counts():
 
 
 def test_hparams_rows_equal_the_reference():
-    from gnn_rul_benchmarking_amd.hparams import get_hparams_class
-    rows = json.loads(str(np.load(os.path.join(GOLDEN, "grucm_hparams_rows.npz"))["rows_json"]))
-    assert sorted(rows) == ["CMAPSS/FD001", "CMAPSS/FD002", "CMAPSS/FD003", "CMAPSS/FD004", "NCMAPSS/None"]
-    for key, ref in rows.items():
-        ds, did = key.split("/")
-        h = get_hparams_class(ds)(None if did == "None" else did)
-        assert h.train_params["GRU_CM"] == ref["train_params"] and h.alg_hparams["GRU_CM"] == ref["alg_hparams"], key
+    family_kit.hparams_rows_check("GRU_CM", "grucm_hparams_rows.npz", ["CMAPSS/FD001", "CMAPSS/FD002", "CMAPSS/FD003", "CMAPSS/FD004", "NCMAPSS/None"], [])
 
 
 def test_workspace_queries_decide_the_supported_range():

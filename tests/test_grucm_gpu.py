@@ -4,7 +4,6 @@ semantics, and the module / algorithm / trainer surface.
 
 Tolerances (each relative to the largest entry of the tensor, gpu_util.rel_err): 1e-4 on predictions and loss, 5e-4 on gradients against
 the fp32 reference, 2e-4 against the fp64 oracle."""
-import argparse
 import ctypes as C
 import glob
 import os
@@ -15,6 +14,7 @@ import torch
 
 from gnn_rul_benchmarking_amd import _lib
 
+import family_kit
 import gpu_util as G
 import grucm_oracle as O
 from conftest import GOLDEN
@@ -318,27 +318,12 @@ def test_trainer_drives_grucm_on_cmapss(tmp_path, monkeypatch):
     import sys
     sys.path.insert(0, GOLDEN)
     from synth import synthetic_cmapss
-    from gnn_rul_benchmarking_amd import trainer as T
     (xtr, ytr), (xte, yte) = synthetic_cmapss(4, 250, 80)
-    d = tmp_path / "data" / "CMAPSS" / "FD004"
-    os.makedirs(d)
-    torch.save({"samples": xtr, "labels": ytr, "max_ruls": 125}, d / "train.pt")
-    torch.save({"samples": xte, "labels": yte, "max_ruls": 125}, d / "test.pt")
-    monkeypatch.chdir(tmp_path)
-    args = argparse.Namespace(save_dir=str(tmp_path / "logs"), experiment_description="exp", run_description="r",
-                              GNN_method="GRU_CM", data_path=str(tmp_path / "data"), dataset="CMAPSS",
-                              dataset_id="FD004", bearing_id="Testing_bearing_1", num_runs=1, device="cuda:0")
-    tr = T.GNN_RUL_trainer(args)
-    tr.train_configs["num_epochs"] = 1
-    assert tr.model_configs == dict(num_nodes=14, time_length=50, gru_hidden_dim=64)
-    per_epoch = []
-    orig = tr.calc_results_per_run
+    data = ({"samples": xtr, "labels": ytr, "max_ruls": 125}, {"samples": xte, "labels": yte, "max_ruls": 125})
 
-    def spy(run_id):
-        per_epoch.append(T._calc_metrics(tr.pred_labels, tr.true_labels, tr.max_ruls))
-        return orig(run_id)
-    tr.calc_results_per_run = spy
-    tr.train()
+    def row(tr):
+        assert tr.model_configs == dict(num_nodes=14, time_length=50, gru_hidden_dim=64)
+    _, per_epoch = family_kit.harness_run(tmp_path, monkeypatch, "GRU_CM", "CMAPSS", "FD004", {"epochs": 1}, data=data, configure=row)
     got = np.asarray(per_epoch, np.float64)
     print("GRU_CM harness metrics:", got)
     assert got.shape == (1, 4) and np.isfinite(got).all()

@@ -2,7 +2,6 @@
 struct table, the coverage gate at every limit, the workspace layout in front of block 1 and the CPU-input refusal."""
 import ctypes as C
 import glob
-import json
 import os
 
 import numpy as np
@@ -14,6 +13,7 @@ from gnn_rul_benchmarking_amd.hiercorrpool_bearing import LIMITS, HierCorrPool_b
 
 from conftest import GOLDEN
 
+import family_kit as K
 import hiercorrpool_bearing_oracle as O
 from test_hiercorrpool_bearing_oracle_golden import CURVE, FORWARD_ONLY, SMALL, load_case
 
@@ -68,17 +68,10 @@ def test_registry_refuses_the_name_and_the_class_constructs_from_every_row():
 
 def test_hparams_rows_equal_the_reference():
     from gnn_rul_benchmarking_amd.hparams import get_hparams_class
-    rows = json.loads(str(np.load(os.path.join(GOLDEN, "hcpb_hparams_rows.npz"))["rows_json"]))
-    assert sorted(rows) == sorted(ROWS)
-    for key, ref in rows.items():
-        ds, did = key.split("/")
-        h = get_hparams_class(ds)(did)
-        assert h.train_params["HierCorrPool_bearing"] == ref["train_params"] and h.alg_hparams["HierCorrPool_bearing"] == ref["alg_hparams"], key
-        assert h.alg_hparams["HierCorrPool_bearing"] == ROWS[key] and list(h.alg_hparams["HierCorrPool_bearing"]) == FIELDS
-        assert h.train_params["HierCorrPool_bearing"] == {"num_epochs": 81, "batch_size": 100, "weight_decay": 1e-4, "learning_rate": 1e-3}
-    for ds, did in (("CMAPSS", "FD001"), ("NCMAPSS", None)):
-        h = get_hparams_class(ds)(did)
-        assert "HierCorrPool_bearing" not in h.alg_hparams and "HierCorrPool_bearing" not in h.train_params
+    train = {"num_epochs": 81, "batch_size": 100, "weight_decay": 1e-4, "learning_rate": 1e-3}
+    K.hparams_rows_check("HierCorrPool_bearing", "hcpb_hparams_rows.npz", {key: (train, ROWS[key]) for key in ROWS}, ["CMAPSS/FD001", "NCMAPSS/None"])
+    for key in ROWS:
+        assert list(get_hparams_class(key.split("/")[0])(key.split("/")[1]).alg_hparams["HierCorrPool_bearing"]) == FIELDS
 
 
 @pytest.mark.parametrize("name", SMALL + FORWARD_ONLY + [CURVE])
@@ -256,11 +249,10 @@ def test_workspace_holds_the_block1_input_and_no_other_spectrogram():
 
 def test_cpu_input_raises():
     m = HierCorrPool_bearing_model(**make_cfg(8, 7, 4, 2, 2, 12, 3))
-    for x in (torch.zeros(2, 56), torch.zeros(2, 7, 8), torch.zeros(2, 1, 56)):
+    K.cpu_input_raises(m, torch.zeros(2, 56))
+    for x in (torch.zeros(2, 7, 8), torch.zeros(2, 1, 56)):
         with pytest.raises(RuntimeError, match="HIP path only"):
             m(x)
-    with pytest.raises(RuntimeError, match="HIP path only"):
-        m.fused_mse_step(torch.zeros(2, 56), torch.zeros(2))
 
 
 def test_fixtures_hold_no_grad_key_and_stay_under_the_size_limit():

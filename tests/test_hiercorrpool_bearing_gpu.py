@@ -17,14 +17,14 @@ import numpy as np
 import pytest
 import torch
 
-import adam_reference as R
+import family_kit as K
 import hiercorrpool_bearing_oracle as O
+from family_kit import DEV, grads_of, rel_same_shape as rel
 from test_hiercorrpool_bearing_cpu import ROWS, make_cfg
-from test_hiercorrpool_bearing_oracle_golden import CURVE, FORWARD_ONLY, SMALL, TAPS, load_case, rel
-from test_hiercorrpool_gpu import check_forward, check_grads, grads_of, keep_mask
+from test_hiercorrpool_bearing_oracle_golden import CURVE, FORWARD_ONLY, SMALL, TAPS, load_case
+from test_hiercorrpool_gpu import check_forward, check_grads, keep_mask
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 TOL, RTOL = 1e-4, 5e-4
 KEYS = O.KEYS
 STFT_GRID = 2048           # csrc/hiercorrpool.hip HCPB_GRID: the packing kernel's workgroups, one output row (sample, padded step) at a time
@@ -32,11 +32,7 @@ STFT_GRID = 2048           # csrc/hiercorrpool.hip HCPB_GRID: the packing kernel
 
 def build_model(cfg, sd, dropout=0.0):
     from gnn_rul_benchmarking_amd.hiercorrpool_bearing import HierCorrPool_bearing_model
-    m = HierCorrPool_bearing_model(**{k: cfg[k] for k in KEYS})
-    m.load_state_dict({k: torch.from_numpy(np.asarray(v, np.float32) if np.asarray(v).dtype.kind == "f" else np.asarray(v)) for k, v in sd.items()},
-                      strict=True)
-    m.dropout_p = dropout
-    return m.to(DEV)
+    return K.build_model(HierCorrPool_bearing_model, cfg, sd, dropout, KEYS)
 
 
 def seeded_state(cfg, seed):
@@ -151,15 +147,9 @@ def test_just_outside_each_limit_is_not_covered_and_launches_nothing(cfg):
     if cfg["encoder_conv_kernel"] == 724:      # (no L' 4 h equals 724: the constructor's reshape check is not what is under test)
         m = HierCorrPool_bearing_model(**dict(cfg, hidden_dim=10, embedding_dim=10, encoder_conv_kernel=72))
         m.encoder_conv_kernel, m.embedding_dim = 724, 1
-        m = m.to(DEV)
     else:
-        m = HierCorrPool_bearing_model(**cfg).to(DEV)
-    x = torch.zeros(2, cfg["num_patch"] * cfg["patch_size"], device=DEV)
-    with pytest.raises(RuntimeError, match="do not cover this configuration"):
-        m(x)
-    with pytest.raises(RuntimeError, match="do not cover this configuration"):
-        m.fused_mse_step(x, torch.zeros(2, device=DEV))
-    assert not m._bufs and not m.bucket.any()                  # no workspace was made, nothing was written
+        m = HierCorrPool_bearing_model(**cfg)
+    K.refused_outside_limits(m, torch.zeros(2, cfg["num_patch"] * cfg["patch_size"], device=DEV))
 
 
 # ---- 3e. dropout -----------------------------------------------------------------------------------------------------------------------
@@ -268,36 +258,8 @@ def test_training_curve_matches_reference_algorithm():
 
 # ---- 3h. the optimizer inside the fused step -------------------------------------------------------------------------------------------
 def test_fused_step_applies_adam_to_every_element_exactly_once():
-    """The twin-model procedure of tests/test_fused_adam_families_gpu.py (steps 7-9, bounds from tests/adam_reference.py), dropout on."""
-    from gnn_rul_benchmarking_amd.optim import FusedAdam
-    from test_fused_adam_families_gpu import LR, SEED, STEP0, WD, _bits, _np
+    """The twin-model procedure (family_kit.adam_twin_check: steps 7-9), dropout on."""
     z, cfg, sd = load_case(SMALL[0])
-    x, y = torch.from_numpy(z["x"]).to(DEV), torch.from_numpy(z["y"]).to(DEV)
-
-    def ready():
-        m = build_model(cfg, sd, dropout=0.35).train()
-        m._seed = SEED
-        return m
-    a = ready()
-    p0 = _np(a.flat_params)
-    _, loss_a = a.fused_mse_step(x, y)
-    g_a, loss_a = _np(a.bucket[:a.num_live]), float(loss_a)
-    assert np.isfinite(g_a).all() and np.array_equal(_bits(_np(a.flat_params)), _bits(p0))
-    b = ready()
-    opt = FusedAdam(b, lr=LR, weight_decay=WD)
-    m0, v0 = R.moments_like(g_a, np.random.default_rng(12))
-    s = opt.state_dict()
-    s.update(step=STEP0, exp_avg=torch.from_numpy(m0).to(DEV), exp_avg_sq=torch.from_numpy(v0).to(DEV))
-    opt.load_state_dict(s)
-    worst = dict(p=0.0, m=0.0, v=0.0)
-    for k in (STEP0 + 1, STEP0 + 2, STEP0 + 3):
-        before = tuple(_np(t) for t in (b.flat_params, opt._exp_avg, opt._exp_avg_sq))
-        _, loss_b = b.fused_mse_step(x, y, opt)
-        g = _np(b.bucket[:b.num_live])
-        after = tuple(_np(t) for t in (b.flat_params, opt._exp_avg, opt._exp_avg_sq))
-        if k == STEP0 + 1:
-            assert np.array_equal(_bits(g), _bits(g_a)) and float(loss_b) == loss_a
-        r = R.check(after, before[0], g, before[1], before[2], k, WD, 1.0, what=f"HierCorrPool_bearing, step {k}")
-        worst = {q: max(worst[q], r[q]) for q in worst}
-    assert opt._steps == STEP0 + 3 and int(b.state_dict()[O.ENC.format(3) + "1.num_batches_tracked"]) == 3
-    print("ADAM-RATIO family HierCorrPool_bearing: " + " ".join(f"{q}={worst[q]:.3f}" for q in "pmv"))
+    b = K.adam_twin_check(lambda: build_model(cfg, sd, dropout=0.35).train(), torch.from_numpy(z["x"]).to(DEV), torch.from_numpy(z["y"]).to(DEV),
+                          "HierCorrPool_bearing")
+    assert int(b.state_dict()[O.ENC.format(3) + "1.num_batches_tracked"]) == 3

@@ -4,34 +4,19 @@ spectrogram ``torch.stft`` returned inside the forward, the encoder output, X', 
 BatchNorm buffers at 1e-6 relative to the tensor's largest value (tests/test_hiercorrpool_oracle_golden.py's bar; the maker keeps a seed
 only when the reference's own fp32 outputs lie within it of its own fp64 run), every parameter gradient element by element
 (tests/grad_gate.py), and the reference's own twelve-step training curve against the torch restatement's ``torch_step`` in fp64."""
-import os
-
 import numpy as np
 import pytest
 
 import grad_gate as GG
 import hiercorrpool_bearing_oracle as O
+from family_kit import load_case, rel_same_shape as rel
 
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
 SMALL = ["hcpb_small_ns4_p8_t7_bs6", "hcpb_ragged_ns4_p10_t3_bs3", "hcpb_p65_ns4_bs2"]
 FORWARD_ONLY = ["hcpb_ns2_p6_t3_bs3"]          # N = 2: several gradients are zero in exact arithmetic, the fixture holds none
 CURVE = "hcpb_train_curve_ns4_p8_t7_bs8"
 TAPS = ("encoder", "pooled_x", "pooled_adj", "H")
 BAR = 1e-6
 RTOL = 5e-4          # the family's gradient gate (tests/test_hiercorrpool_bearing_gpu.py); the oracle stays far inside
-
-
-def rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    assert a.shape == b.shape, (a.shape, b.shape)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
-
-
-def load_case(name, prefix="sd:"):
-    z = np.load(os.path.join(GOLD, name + ".npz"))
-    cfg = {k[4:]: int(z[k]) for k in z.files if k.startswith("cfg:")}
-    sd = {k[len(prefix):]: z[k] for k in z.files if k.startswith(prefix)}
-    return z, cfg, sd
 
 
 @pytest.mark.parametrize("name", SMALL + FORWARD_ONLY)

@@ -2,7 +2,6 @@
 workspace layout (no N x N or N x d graph intermediate per sample beyond X itself)."""
 import ctypes as C
 import glob
-import json
 import os
 
 import numpy as np
@@ -13,6 +12,7 @@ from gnn_rul_benchmarking_amd import _lib
 
 from conftest import GOLDEN
 
+import family_kit as K
 import hiercorrpool_oracle as O
 
 FIELDS = "patch_size num_patch hidden_dim embedding_dim num_nodes encoder_conv_kernel num_nodes_out".split()
@@ -28,12 +28,9 @@ def shape_of(batch, cfg):
 
 def test_registry_serves_the_algorithm_and_refuses_the_model():
     from gnn_rul_benchmarking_amd import algorithms as A
-    assert A.get_algorithm_class("HierCorrPool") is A.HierCorrPool
-    with pytest.raises(NotImplementedError, match="Algorithm not found: HierCorrPool_model"):
-        A.get_algorithm_class("HierCorrPool_model")
+    K.registry_check("HierCorrPool", needs_train_mode="BatchNorm batch statistics, dropout")
     with pytest.raises(NotImplementedError, match="Algorithm not found: HierCorrPool_bearing"):
         A.get_algorithm_class("HierCorrPool_bearing")
-    assert A.HierCorrPool.needs_train_mode == "BatchNorm batch statistics, dropout" and A.HierCorrPool.supports_graphs is False
 
 
 def test_algorithm_construction_and_data_parallel_refusal():
@@ -78,14 +75,8 @@ def test_a_seed_gives_the_reference_state_dict(name):
 
 def test_hparams_rows_equal_the_reference():
     from gnn_rul_benchmarking_amd.hparams import get_hparams_class
-    rows = json.loads(str(np.load(os.path.join(GOLDEN, "hiercorrpool_hparams_rows.npz"))["rows_json"]))
-    assert sorted(rows) == ["CMAPSS/FD001", "CMAPSS/FD002", "CMAPSS/FD003", "CMAPSS/FD004", "NCMAPSS/None"]
-    for key, ref in rows.items():
-        ds, did = key.split("/")
-        h = get_hparams_class(ds)(None if did == "None" else did)
-        assert h.train_params["HierCorrPool"] == ref["train_params"] and h.alg_hparams["HierCorrPool"] == ref["alg_hparams"], key
-    h = get_hparams_class("PHM2012")("Condition_1")
-    assert "HierCorrPool" not in h.alg_hparams and "HierCorrPool" not in h.train_params
+    K.hparams_rows_check("HierCorrPool", "hiercorrpool_hparams_rows.npz", ["CMAPSS/FD001", "CMAPSS/FD002", "CMAPSS/FD003", "CMAPSS/FD004", "NCMAPSS/None"],
+                         ["PHM2012/Condition_1"])
     assert get_hparams_class("CMAPSS")("FD001").alg_hparams["HierCorrPool"] == dict(FD001, input_dim=10)
     assert get_hparams_class("CMAPSS")("FD004").alg_hparams["HierCorrPool"] == dict(FD004, input_dim=10)
     assert get_hparams_class("NCMAPSS")(None).alg_hparams["HierCorrPool"] == dict(NCMAPSS, input_dim=10)
@@ -104,11 +95,7 @@ def test_construction_names_both_numbers_when_the_reshape_cannot_exist():
 
 def test_cpu_input_raises():
     from gnn_rul_benchmarking_amd.hiercorrpool import HierCorrPool_model
-    m = HierCorrPool_model(3, 7, 10, 2, 2, 5, 12, 3)
-    with pytest.raises(RuntimeError, match="HIP path only"):
-        m(torch.zeros(2, 5, 21))
-    with pytest.raises(RuntimeError, match="HIP path only"):
-        m.fused_mse_step(torch.zeros(2, 5, 21), torch.zeros(2))
+    K.cpu_input_raises(HierCorrPool_model(3, 7, 10, 2, 2, 5, 12, 3), torch.zeros(2, 5, 21))
 
 
 def test_new_fixtures_hold_no_grad_key():

@@ -2,32 +2,17 @@
 written by tests/golden/make_golden_hiercorrpool.py running the reference on the CPU, dropout 0): the encoder output, X', A', H, the
 prediction, the loss, the BatchNorm buffers after the forward, every parameter gradient element by element (tests/grad_gate.py), and
 the reference's own twelve-step training curve with the oracle's gradients and fp64 Adam (tests/adam_reference.py)."""
-import os
-
 import numpy as np
 import pytest
 
 import adam_reference as AR
 import grad_gate as GG
 import hiercorrpool_oracle as O
+from family_kit import load_case, rel_same_shape as rel
 
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
 CASES = ["hiercorrpool_small_7x3_n5_bs6", "hiercorrpool_fd001geom_bs4", "hiercorrpool_fd004geom_bs4", "hiercorrpool_ncmapssgeom_bs3"]
 CURVE = "hiercorrpool_train_curve_7x3_n5_bs8"
 RTOL = 5e-4          # the family's gradient gate (tests/test_hiercorrpool_gpu.py); the oracle stays far inside
-
-
-def rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    assert a.shape == b.shape, (a.shape, b.shape)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
-
-
-def load_case(name, prefix="sd:"):
-    z = np.load(os.path.join(GOLD, name + ".npz"))
-    cfg = {k[4:]: int(z[k]) for k in z.files if k.startswith("cfg:")}
-    sd = {k[len(prefix):]: z[k] for k in z.files if k.startswith(prefix)}
-    return z, cfg, sd
 
 
 @pytest.mark.parametrize("name", CASES)

@@ -2,7 +2,6 @@
 C-ABI's size queries, the coverage gate at every limit, the consistency refusals and the backward's LDS plan."""
 import ctypes as C
 import glob
-import json
 import os
 
 import numpy as np
@@ -13,6 +12,7 @@ from gnn_rul_benchmarking_amd import _lib
 
 from conftest import GOLDEN
 
+import family_kit as K
 import logo_bearing_oracle as O
 from test_logo_bearing_oracle_golden import CURVE, FULL, SMALL, load_case
 
@@ -67,18 +67,13 @@ def test_registry_algorithm_scheduler_and_data_parallel_refusal():
 
 def test_hparams_rows_equal_the_reference():
     from gnn_rul_benchmarking_amd import algorithms as A
-    from gnn_rul_benchmarking_amd.hparams import get_hparams_class
-    rows = json.loads(str(np.load(os.path.join(GOLDEN, "logob_hparams_rows.npz"))["rows_json"]))
-    assert sorted(rows) == [f"{ds}/Condition_{i}" for ds in ("PHM2012", "XJTU_SY") for i in (1, 2, 3)]
+    train = {"num_epochs": 81, "batch_size": 100, "weight_decay": 1e-4, "learning_rate": 1e-3, "theta": 0.001}
+    keys = [f"{ds}/Condition_{i}" for ds in ("PHM2012", "XJTU_SY") for i in (1, 2, 3)]
+    rows = K.hparams_rows_check("LOGO_bearing", "logob_hparams_rows.npz", {k: (train, PHM if k.startswith("PHM2012") else XJTU) for k in keys},
+                                ["CMAPSS/FD001"])
     for key, ref in rows.items():
-        ds, did = key.split("/")
-        h = get_hparams_class(ds)(did)
-        assert h.train_params["LOGO_bearing"] == ref["train_params"] and h.alg_hparams["LOGO_bearing"] == ref["alg_hparams"], key
-        assert h.alg_hparams["LOGO_bearing"] == (PHM if ds == "PHM2012" else XJTU)
-        assert h.train_params["LOGO_bearing"] == {"num_epochs": 81, "batch_size": 100, "weight_decay": 1e-4, "learning_rate": 1e-3, "theta": 0.001}
-        algo = A.LOGO_bearing(h.alg_hparams["LOGO_bearing"], h.train_params["LOGO_bearing"], "cpu")
-        assert algo.model.num_live == (177434 if ds == "PHM2012" else 369674)
-    assert "LOGO_bearing" not in get_hparams_class("CMAPSS")("FD001").alg_hparams
+        algo = A.LOGO_bearing(ref["alg_hparams"], ref["train_params"], "cpu")
+        assert algo.model.num_live == (177434 if key.startswith("PHM2012") else 369674)
 
 
 @pytest.mark.parametrize("cfg,count", [(PHM, 177434), (XJTU, 369674)], ids=["PHM2012", "XJTU_SY"])
@@ -219,13 +214,12 @@ def test_kwargs_that_do_not_describe_the_stft_construct_and_are_refused():
 def test_cpu_input_raises():
     from gnn_rul_benchmarking_amd.logo_bearing import LOGO_bearing_model
     m = LOGO_bearing_model(**cfg_of(P=8, T=2, ns=4))
-    for x in (torch.zeros(2, 16), torch.zeros(2, 2, 8), torch.zeros(2, 1, 16)):
+    K.cpu_input_raises(m, torch.zeros(2, 16))
+    for x in (torch.zeros(2, 2, 8), torch.zeros(2, 1, 16)):
         with pytest.raises(RuntimeError, match="HIP path only"):
             m(x)
     with pytest.raises(RuntimeError, match="HIP path only"):
         m(torch.zeros(2, 16), GL=True)
-    with pytest.raises(RuntimeError, match="HIP path only"):
-        m.fused_mse_step(torch.zeros(2, 16), torch.zeros(2))
 
 
 def test_fixtures_hold_no_grad_key_and_stay_under_the_size_limit():

@@ -17,12 +17,14 @@ import numpy as np
 import pytest
 import torch
 
+import family_kit as K
 import grad_gate as GG
 import logo_bearing_oracle as O
-from test_logo_bearing_oracle_golden import CASES, CURVE, SMALL, fixture_oracle, fusion_is_constant, load_case, rel, seeded_state
+from family_kit import DEV, grads_of, rel_same_shape as rel
+from test_logo_bearing_oracle_golden import CASES, CURVE, SMALL, fixture_oracle, fusion_is_constant, load_case, seeded_state
+from test_logo_gpu import check_forward as logo_check_forward
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 TOL, RTOL = 1e-4, 5e-4
 KEYS = O.KEYS
 TINY = dict(patch_size=8, num_patch=2, input_dim=3, num_nodes=3, nperseg=4, hidden_dim=1)
@@ -30,15 +32,7 @@ TINY = dict(patch_size=8, num_patch=2, input_dim=3, num_nodes=3, nperseg=4, hidd
 
 def build_model(cfg, sd, dropout=0.0):
     from gnn_rul_benchmarking_amd.logo_bearing import LOGO_bearing_model
-    m = LOGO_bearing_model(**{k: cfg[k] for k in KEYS})
-    m.load_state_dict({k: torch.from_numpy(np.asarray(v, np.float32)) for k, v in sd.items()}, strict=True)
-    m.dropout_p = dropout
-    return m.to(DEV)
-
-
-def grads_of(m):
-    flat = m._grad_flat[:m.num_live].detach().cpu().numpy().astype(np.float64)
-    return {name: flat[off:off + int(np.prod(shape))].reshape(shape) for name, (off, shape) in m._layout.items()}
+    return K.build_model(LOGO_bearing_model, cfg, sd, dropout, KEYS)
 
 
 def check_grads(what, cfg, got, g64, ref32):
@@ -60,14 +54,7 @@ def check_grads(what, cfg, got, g64, ref32):
 
 
 def check_forward(what, m, bs, pred, loss, want, want_loss):
-    errs = {"mpnn": rel(m.tap(bs, "mpnn").cpu().numpy(), want["mpnn"]), "lstm": rel(m.tap(bs, "lstm").cpu().numpy(), want["lstm"]),
-            "gl": abs(float(m.tap(bs, "gl")) - want["gl"]) / abs(want["gl"]),
-            "pred": rel(pred.detach().cpu().numpy().reshape(-1, 1), np.asarray(want["pred"]).reshape(-1, 1))}
-    if loss is not None:
-        errs["loss"] = abs(float(loss) - want_loss) / abs(want_loss)
-    print(f"LOGOB-GATE {what}: forward " + " ".join(f"{k}={v:.2e}" for k, v in errs.items()))
-    for k, v in errs.items():
-        assert v < TOL, (k, v)
+    logo_check_forward(what, m, bs, pred, loss, want, want_loss, tag="LOGOB")
 
 
 # ---- 1. the reference's fixtures: the tiny shapes and both reference geometries at full width -----------------------------------------
@@ -210,13 +197,7 @@ def _cfg(P, T, ns, h, **over):
                                  _cfg(2, 1, 4, 1)], ids=["N18", "f35", "6h132", "lds", "odd-nperseg", "short-patch"])
 def test_just_outside_each_limit_is_not_covered_and_launches_nothing(cfg):
     from gnn_rul_benchmarking_amd.logo_bearing import LOGO_bearing_model
-    m = LOGO_bearing_model(**cfg).to(DEV)
-    x = torch.randn(2, cfg["num_patch"] * cfg["patch_size"], device=DEV)
-    with pytest.raises(RuntimeError, match="do not cover this configuration"):
-        m(x)
-    with pytest.raises(RuntimeError, match="do not cover this configuration"):
-        m.fused_mse_step(x, torch.zeros(2, device=DEV), theta=0.01)
-    assert not m._bufs and not m.bucket.any()                  # no workspace was made, nothing was written
+    K.refused_outside_limits(LOGO_bearing_model(**cfg), torch.randn(2, cfg["num_patch"] * cfg["patch_size"], device=DEV), theta=0.01)
 
 
 def test_kwargs_that_do_not_describe_the_stft_fail_at_the_first_forward_naming_both():

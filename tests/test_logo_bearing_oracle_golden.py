@@ -13,10 +13,11 @@ import pytest
 
 import adam_reference as AR
 import grad_gate as GG
+import family_kit as K
 import logo_bearing_oracle as O
-from test_logo_oracle_golden import RTOL, rel
+from family_kit import GOLD, rel_same_shape as rel
+from test_logo_oracle_golden import RTOL
 
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
 SMALL = ["logob_tiny_ns4_p8_t2_h1_bs3", "logob_ns2_p6_t3_h1_bs2", "logob_ragged_ns4_p10_t3_h2_bs2", "logob_onepatch_ns4_p8_t1_h1_bs2"]
 FULL = ["logob_phm2012_full_bs2", "logob_xjtu_full_bs2"]
 CASES = SMALL + FULL
@@ -24,13 +25,8 @@ CURVE = "logob_train_curve_ns4_p8_t2_h1_bs4"
 
 
 def seeded_state(cfg, seed):
-    """The constructor's state dict under ``seed``, moved away from init as the fixtures' maker does (numpy)."""
-    import torch
     from gnn_rul_benchmarking_amd.logo_bearing import LOGO_bearing_model
-    torch.manual_seed(seed)
-    g = torch.Generator().manual_seed(seed + 1000)
-    return {k: (v + torch.empty_like(v).uniform_(-0.1, 0.1, generator=g)).numpy().copy()
-            for k, v in LOGO_bearing_model(**{k: cfg[k] for k in O.KEYS}).state_dict().items()}
+    return K.seeded_state(LOGO_bearing_model, cfg, seed, O.KEYS)
 
 
 @functools.lru_cache(maxsize=None)

@@ -2,7 +2,6 @@
 queries, the coverage gate at every limit and the workspace layout (no [B T, N, N] tensor)."""
 import ctypes as C
 import glob
-import json
 import os
 
 import numpy as np
@@ -13,6 +12,7 @@ from gnn_rul_benchmarking_amd import _lib
 
 from conftest import GOLDEN
 
+import family_kit as K
 import logo_oracle as O
 
 FIELDS = O.KEYS
@@ -31,12 +31,9 @@ def shape_of(batch, cfg):
 
 def test_registry_serves_the_algorithm_and_refuses_the_model():
     from gnn_rul_benchmarking_amd import algorithms as A
-    assert A.get_algorithm_class("LOGO") is A.LOGO
-    with pytest.raises(NotImplementedError, match="Algorithm not found: LOGO_model"):
-        A.get_algorithm_class("LOGO_model")
+    K.registry_check("LOGO")
     with pytest.raises(NotImplementedError, match="Algorithm not found: LOGO_bearing"):
         A.get_algorithm_class("LOGO_bearing")
-    assert A.LOGO.needs_train_mode == "dropout" and A.LOGO.supports_graphs is False
 
 
 def test_algorithm_construction_theta_and_data_parallel_refusal():
@@ -84,17 +81,11 @@ def test_a_seed_gives_the_reference_keys_and_initial_values(name):
 
 def test_hparams_rows_equal_the_reference():
     from gnn_rul_benchmarking_amd.hparams import get_hparams_class
-    rows = json.loads(str(np.load(os.path.join(GOLDEN, "logo_hparams_rows.npz"))["rows_json"]))
-    assert sorted(rows) == ["CMAPSS/FD001", "CMAPSS/FD002", "CMAPSS/FD003", "CMAPSS/FD004", "NCMAPSS/None"]
-    for key, ref in rows.items():
-        ds, did = key.split("/")
-        h = get_hparams_class(ds)(None if did == "None" else did)
-        assert h.train_params["LOGO"] == ref["train_params"] and h.alg_hparams["LOGO"] == ref["alg_hparams"], key
+    rows = K.hparams_rows_check("LOGO", "logo_hparams_rows.npz", ["CMAPSS/FD001", "CMAPSS/FD002", "CMAPSS/FD003", "CMAPSS/FD004", "NCMAPSS/None"],
+                                ["PHM2012/Condition_1"])
     assert [rows[k]["train_params"]["theta"] for k in sorted(rows)] == [0.001, 0.01, 0.01, 0.001, 0.001]
     n = get_hparams_class("NCMAPSS")(None).train_params["LOGO"]
     assert n["batch_size"] == 50 and n["weight_decay"] == 0
-    h = get_hparams_class("PHM2012")("Condition_1")
-    assert "LOGO" not in h.alg_hparams and "LOGO" not in h.train_params
     for did, cfg in (("FD001", FD001), ("FD002", FD002), ("FD003", FD003), ("FD004", FD004)):
         assert get_hparams_class("CMAPSS")(did).alg_hparams["LOGO"] == cfg
     assert get_hparams_class("NCMAPSS")(None).alg_hparams["LOGO"] == NCMAPSS
@@ -133,12 +124,9 @@ def test_fd003_constructs_and_is_refused_with_the_workspace_query_at_zero():
 def test_cpu_input_raises():
     from gnn_rul_benchmarking_amd.logo import LOGO_model
     m = LOGO_model(2, 2, 3, 1)
-    with pytest.raises(RuntimeError, match="HIP path only"):
-        m(torch.zeros(2, 3, 4))
+    K.cpu_input_raises(m, torch.zeros(2, 3, 4))
     with pytest.raises(RuntimeError, match="HIP path only"):
         m(torch.zeros(2, 3, 4), GL=True)
-    with pytest.raises(RuntimeError, match="HIP path only"):
-        m.fused_mse_step(torch.zeros(2, 3, 4), torch.zeros(2))
 
 
 def test_new_fixtures_hold_no_grad_key():

@@ -6,7 +6,6 @@ Gradients: element by element through tests/grad_gate.py at rtol 5e-4 and margin
 0.14 at most -- so the tighter 5e-4 is the gate, the rule this family was given.)  The floor's noise term is the REFERENCE's fp32
 gradient against the fp64 oracle (the fixture's ``refgrad:`` entries; without a fixture an fp32 run of the torch restatement on the
 CPU), never the kernels' output.  Every test prints its worst gate ratio ("LOGO-GATE ...")."""
-import argparse
 import functools
 import os
 
@@ -14,14 +13,12 @@ import numpy as np
 import pytest
 import torch
 
-import adam_reference as R
-import grad_gate as GG
+import family_kit as K
 import logo_oracle as O
-from test_logo_oracle_golden import CASES, CURVE, load_case, rel
+from family_kit import DEV, GOLD, grads_of, rel_same_shape as rel
+from test_logo_oracle_golden import CASES, CURVE, load_case
 
 pytestmark = pytest.mark.gpu
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
-DEV = "cuda:0"
 TOL, RTOL = 1e-4, 5e-4
 KEYS = O.KEYS
 FD001 = dict(patch_size=10, num_patch=5, num_nodes=14, hidden_dim=8)
@@ -34,48 +31,25 @@ def make_cfg(p, T, N, h):
 
 def build_model(cfg, sd, dropout=0.0):
     from gnn_rul_benchmarking_amd.logo import LOGO_model
-    m = LOGO_model(**{k: cfg[k] for k in KEYS})
-    m.load_state_dict({k: torch.from_numpy(np.asarray(v, np.float32)) for k, v in sd.items()}, strict=True)
-    m.dropout_p = dropout
-    return m.to(DEV)
+    return K.build_model(LOGO_model, cfg, sd, dropout, KEYS)
 
 
 def seeded_state(cfg, seed):
-    """The constructor's state dict under ``seed``, moved away from init as the fixtures' maker does (numpy)."""
     from gnn_rul_benchmarking_amd.logo import LOGO_model
-    torch.manual_seed(seed)
-    g = torch.Generator().manual_seed(seed + 1000)
-    return {k: (v + torch.empty_like(v).uniform_(-0.1, 0.1, generator=g)).numpy().copy()
-            for k, v in LOGO_model(**{k: cfg[k] for k in KEYS}).state_dict().items()}
-
-
-def grads_of(m):
-    flat = m._grad_flat[:m.num_live].detach().cpu().numpy().astype(np.float64)
-    return {name: flat[off:off + int(np.prod(shape))].reshape(shape) for name, (off, shape) in m._layout.items()}
+    return K.seeded_state(LOGO_model, cfg, seed, KEYS)
 
 
 def check_grads(what, got, g64, ref32):
-    worst = (0.0, None)
-    for k in O.param_names():
-        if not g64[k].any():              # exactly zero in the oracle (bs = 1: a one-step recurrence has h_prev = 0, so g weight_hh = 0)
-            assert got[k].shape == g64[k].shape and not got[k].any() and not np.asarray(ref32[k]).any(), f"{k} must be exactly zero"
-            continue
-        ratio, where = GG.gate(got[k], g64[k], RTOL, GG.floor_for(ref32[k], g64[k]))
-        print(f"  grad {k}: gate {ratio:.3f} at {where}  rel {rel(got[k], g64[k]):.2e}  max|g| {np.abs(g64[k]).max():.2e}")
-        worst = max(worst, (ratio, k))
-    print(f"LOGO-GATE {what}: worst gradient gate ratio {worst[0]:.3f} ({worst[1]})")
-    assert worst[0] <= 1.0, worst
+    """Every tensor's ratio is printed.  A tensor that is exactly zero in the oracle (bs = 1: a one-step recurrence has h_prev = 0, so
+    g weight_hh = 0) must be exactly zero in the reference and in the kernels (family_kit.EXACT_ZERO)."""
+    assert list(g64) == O.param_names()
+    K.check_grads(what, "LOGO", got, g64, ref32, RTOL, K.EXACT_ZERO, verbose=True)
 
 
-def check_forward(what, m, bs, pred, loss, want, want_loss):
-    errs = {"mpnn": rel(m.tap(bs, "mpnn").cpu().numpy(), want["mpnn"]), "lstm": rel(m.tap(bs, "lstm").cpu().numpy(), want["lstm"]),
-            "gl": abs(float(m.tap(bs, "gl")) - want["gl"]) / abs(want["gl"]),
-            "pred": rel(pred.detach().cpu().numpy().reshape(-1, 1), np.asarray(want["pred"]).reshape(-1, 1))}
-    if loss is not None:
-        errs["loss"] = abs(float(loss) - want_loss) / abs(want_loss)
-    print(f"LOGO-GATE {what}: forward " + " ".join(f"{k}={v:.2e}" for k, v in errs.items()))
-    for k, v in errs.items():
-        assert v < TOL, (k, v)
+def check_forward(what, m, bs, pred, loss, want, want_loss, tag="LOGO"):
+    errs = {**K.tap_errs(m, bs, want, ("mpnn", "lstm"), rel), "gl": abs(float(m.tap(bs, "gl")) - want["gl"]) / abs(want["gl"]),
+            **K.pred_err(pred, want, rel), **K.loss_err(loss, want_loss)}
+    K.check_forward(what, tag, errs, TOL)
 
 
 @functools.lru_cache(maxsize=None)
@@ -256,63 +230,17 @@ def test_constant_sensor_makes_every_prediction_of_the_batch_nan_and_the_call_re
 def test_training_curve_matches_reference_algorithm():
     """Twelve update() steps against the reference's own.  Tolerances: the project's curve tolerances for a BatchNorm-free family
     (GRU_CM, tests/test_grucm_gpu.py:253-261: the first three losses 1e-4, every loss 2e-3, end state and eval prediction 5e-3)."""
-    from gnn_rul_benchmarking_amd.algorithms import get_algorithm_class
     z, cfg, sd0 = load_case(CURVE, "sd0:")
-    algo = get_algorithm_class("LOGO")({k: cfg[k] for k in KEYS}, {"learning_rate": float(z["lr"]), "weight_decay": float(z["wd"]),
-                                                                      "theta": float(z["theta"])}, DEV)
-    algo.model.load_state_dict({k: torch.from_numpy(np.asarray(v)) for k, v in sd0.items()})
-    algo.model.dropout_p = 0.0
-    algo.to(DEV).train()
-    xs, ys = torch.from_numpy(z["xs"]).to(DEV), torch.from_numpy(z["ys"]).to(DEV)
-    assert xs.size(0) == 12
-    losses = np.asarray([algo.update(xs[s], ys[s], 1)["loss"] for s in range(12)])
-    ref = z["losses"]
-    print("LOGO-GATE curve: worst loss ratio", np.abs(losses / ref - 1).max())
-    assert np.max(np.abs(losses[:3] - ref[:3]) / ref[:3]) < 1e-4
-    assert np.max(np.abs(losses - ref) / ref) < 2e-3
-    sd = algo.model.state_dict()
+    _, sd = K.curve_check("LOGO", "LOGO", {k: cfg[k] for k in KEYS}, z, sd0, dict(steps=12, first3=1e-4, every=2e-3, params=5e-3, eval=5e-3),
+                          dropout_off=True)
     assert list(sd) == O.state_keys()
-    for k in sd:
-        assert rel(sd[k].cpu().numpy(), z["sd_end:" + k]) < 5e-3, k
-    algo.eval()
-    with torch.no_grad():
-        assert rel(algo.model(xs[0]).cpu().numpy(), z["eval_pred_end"]) < 5e-3
 
 
 # ---- 7. the optimizer inside the fused step -----------------------------------------------------------------------------------------
 def test_fused_step_applies_adam_to_every_element_exactly_once():
-    """The twin-model procedure of tests/test_fused_adam_families_gpu.py (steps 7-9, bounds from tests/adam_reference.py), dropout on."""
-    from gnn_rul_benchmarking_amd.optim import FusedAdam
-    from test_fused_adam_families_gpu import LR, SEED, STEP0, WD, _bits, _np
+    """The twin-model procedure (family_kit.adam_twin_check: steps 7-9), dropout on."""
     cfg, sd, x, y, theta = _case(CASES[0])
-
-    def ready():
-        m = build_model(cfg, sd, dropout=0.2).train()
-        m._seed = SEED
-        return m
-    a = ready()
-    p0 = _np(a.flat_params)
-    _, loss_a = a.fused_mse_step(x, y, theta=theta)
-    g_a, loss_a = _np(a.bucket[:a.num_live]), float(loss_a)
-    assert np.isfinite(g_a).all() and np.array_equal(_bits(_np(a.flat_params)), _bits(p0))
-    b = ready()
-    opt = FusedAdam(b, lr=LR, weight_decay=WD)
-    m0, v0 = R.moments_like(g_a, np.random.default_rng(12))
-    s = opt.state_dict()
-    s.update(step=STEP0, exp_avg=torch.from_numpy(m0).to(DEV), exp_avg_sq=torch.from_numpy(v0).to(DEV))
-    opt.load_state_dict(s)
-    worst = dict(p=0.0, m=0.0, v=0.0)
-    for k in (STEP0 + 1, STEP0 + 2, STEP0 + 3):
-        before = tuple(_np(t) for t in (b.flat_params, opt._exp_avg, opt._exp_avg_sq))
-        _, loss_b = b.fused_mse_step(x, y, opt, theta=theta)
-        g = _np(b.bucket[:b.num_live])
-        after = tuple(_np(t) for t in (b.flat_params, opt._exp_avg, opt._exp_avg_sq))
-        if k == STEP0 + 1:
-            assert np.array_equal(_bits(g), _bits(g_a)) and float(loss_b) == loss_a
-        r = R.check(after, before[0], g, before[1], before[2], k, WD, 1.0, what=f"LOGO, step {k}")
-        worst = {q: max(worst[q], r[q]) for q in worst}
-    assert opt._steps == STEP0 + 3
-    print("ADAM-RATIO family LOGO: " + " ".join(f"{q}={worst[q]:.3f}" for q in "pmv"))
+    K.adam_twin_check(lambda: build_model(cfg, sd, dropout=0.2).train(), x, y, "LOGO", theta=theta)
 
 
 # ---- 8. coverage ---------------------------------------------------------------------------------------------------------------------
@@ -320,13 +248,7 @@ def test_fused_step_applies_adam_to_every_element_exactly_once():
                                  make_cfg(10, 5, 14, 32)], ids=["N33", "p17", "6h132", "lds", "FD003"])
 def test_just_outside_each_limit_is_not_covered_and_launches_nothing(cfg):
     from gnn_rul_benchmarking_amd.logo import LOGO_model
-    m = LOGO_model(**cfg).to(DEV)
-    x = torch.rand(2, cfg["num_nodes"], cfg["num_patch"] * cfg["patch_size"], device=DEV)
-    with pytest.raises(RuntimeError, match="do not cover this configuration"):
-        m(x)
-    with pytest.raises(RuntimeError, match="do not cover this configuration"):
-        m.fused_mse_step(x, torch.zeros(2, device=DEV), theta=0.01)
-    assert not m._bufs and not m.bucket.any()                  # no workspace was made, nothing was written
+    K.refused_outside_limits(LOGO_model(**cfg), torch.rand(2, cfg["num_nodes"], cfg["num_patch"] * cfg["patch_size"], device=DEV), theta=0.01)
 
 
 @pytest.mark.parametrize("cfg", [make_cfg(16, 2, 32, 1), make_cfg(3, 2, 5, 21), make_cfg(16, 13, 32, 1)], ids=["N32-p16", "6h126", "N32-p16-T13-lds"])
@@ -343,48 +265,13 @@ def test_trainer_matches_reference_harness_run_on_cmapss(tmp_path, monkeypatch):
     """--GNN_method LOGO on C-MAPSS FD001 as the reference wires it (configs/hparams.py:18,37; shuffling DataLoader): the reference's
     own harness, run on the CPU by tests/golden/make_golden_logo.py::case_trainer_cmapss with the two dropouts switched off on the
     constructed model, vs this package's harness on the GPU with the same switch.  Bars: those of the other families' harness tests
-    (tests/test_trainer_gpu.py:279-285)."""
-    import sys
-    sys.path.insert(0, GOLD)
-    from synth import synthetic_cmapss
-    from gnn_rul_benchmarking_amd import trainer as T
+    (tests/test_trainer_gpu.py)."""
     z = np.load(os.path.join(GOLD, "logo_trainer_fd001_reference_run.npz"))
-    (xtr, ytr), (xte, yte) = synthetic_cmapss(int(z["seed"]), int(z["n_train"]), int(z["n_test"]))
-    assert abs(xtr.astype(np.float64).sum() - float(z["x_train_checksum"])) < 1e-6
-    d = tmp_path / "data" / "CMAPSS" / "FD001"
-    os.makedirs(d)
-    torch.save({"samples": xtr, "labels": ytr, "max_ruls": 125}, d / "train.pt")
-    torch.save({"samples": xte, "labels": yte, "max_ruls": 125}, d / "test.pt")
-    monkeypatch.chdir(tmp_path)
-    base = T.get_algorithm_class("LOGO")
+    assert int(z["epochs"]) == 3
 
-    class NoDropout(base):
-        def __init__(self, *a, **k):
-            super().__init__(*a, **k)
-            self.model.dropout_p = 0.0
-    monkeypatch.setattr(T, "get_algorithm_class", lambda n: NoDropout)
-    args = argparse.Namespace(save_dir=str(tmp_path / "logs"), experiment_description="exp", run_description="r",
-                              GNN_method="LOGO", data_path=str(tmp_path / "data"), dataset="CMAPSS",
-                              dataset_id="FD001", bearing_id=None, num_runs=1, device=DEV)
-    tr = T.GNN_RUL_trainer(args)
-    tr.train_configs["num_epochs"] = int(z["epochs"])
-    assert tr.train_configs["batch_size"] == int(z["batch_size"]) and tr.train_configs["learning_rate"] == float(z["lr"])
-    assert tr.train_configs["theta"] == float(z["theta"]) and tr.model_configs == FD001
-    per_epoch = []
-    orig = tr.calc_results_per_run
-
-    def spy(run_id):
-        per_epoch.append(T._calc_metrics(tr.pred_labels, tr.true_labels, tr.max_ruls))
-        return orig(run_id)
-    tr.calc_results_per_run = spy
-    tr.train()
-    got, ref = np.asarray(per_epoch, np.float64), z["per_epoch"]
-    print("LOGO harness per-epoch got/ref:\n", got, "\n", ref)
-    assert got.shape == ref.shape == (3, 4)
-    assert np.max(np.abs(got[:, 2:] - ref[:, 2:]) / np.abs(ref[:, 2:])) < 1e-3      # MAE, RMSE (in RUL cycles), relative
-    assert np.max(np.abs(got[:, 3] - ref[:, 3]) / 125.0) < 1e-3                      # RMSE on the normalised scale, absolute
-    sd = tr.algorithm.state_dict()
-    for k in z.files:
-        if k.startswith("final:"):
-            a, b = sd[k[6:]].cpu().numpy().astype(np.float64), z[k].astype(np.float64)
-            assert np.max(np.abs(a - b)) / max(np.max(np.abs(b)), 1e-30) < 3e-3, k
+    def row(tr):
+        assert tr.train_configs["batch_size"] == int(z["batch_size"]) and tr.train_configs["learning_rate"] == float(z["lr"])
+        assert tr.train_configs["theta"] == float(z["theta"]) and tr.model_configs == FD001
+    tr, per_epoch = K.harness_run(tmp_path, monkeypatch, "LOGO", "CMAPSS", "FD001", z, no_dropout=K.model_dropout_off, configure=row)
+    K.assert_harness("LOGO", per_epoch, K.state_of(tr), z,        # MAE, RMSE (in RUL cycles), relative; RMSE on the normalised scale, absolute
+                     dict(rmse_abs=1e-3, rmse_scale=125.0, rel=1e-3, rel_from=2, final=3e-3, final_prefix=""))

@@ -3,32 +3,17 @@ tests/golden/make_golden_logo.py running the reference on the CPU, dropouts 0): 
 the prediction in train and eval mode, L_GL, the loss, every parameter gradient element by element (tests/grad_gate.py), a
 finite-difference check of the hand-written backward including the theta * L_GL term, the torch restatement, and the reference's own
 twelve-step training curve with the oracle's gradients and fp64 Adam (tests/adam_reference.py)."""
-import os
-
 import numpy as np
 import pytest
 
 import adam_reference as AR
 import grad_gate as GG
 import logo_oracle as O
+from family_kit import load_case, rel_same_shape as rel
 
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
 CASES = ["logo_small_3x2x2_h1_bs4", "logo_fd001geom_bs5", "logo_fd002geom_bs4", "logo_ncmapssgeom_bs3"]
 CURVE = "logo_train_curve_3x2x2_h1_bs8"
 RTOL = 5e-4          # the family's gradient gate (tests/test_logo_gpu.py); the oracle stays far inside
-
-
-def rel(a, b):
-    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
-    assert a.shape == b.shape, (a.shape, b.shape)
-    return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
-
-
-def load_case(name, prefix="sd:"):
-    z = np.load(os.path.join(GOLD, name + ".npz"))
-    cfg = {k[4:]: int(z[k]) for k in z.files if k.startswith("cfg:")}
-    sd = {k[len(prefix):]: z[k] for k in z.files if k.startswith(prefix)}
-    return z, cfg, sd
 
 
 @pytest.mark.parametrize("name", CASES)

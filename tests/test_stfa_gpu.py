@@ -23,17 +23,16 @@ import numpy as np
 import pytest
 import torch
 
-import adam_reference as R
-import grad_gate as GG
+import family_kit as K
 import stfa_oracle as O
-from test_stfa_oracle_golden import CURVE, FULL, NAN, SMALL, load_case, oracle_run, rel, rel_finite, seeded_weights
+from family_kit import DEV, GOLD, dev, grads_of, rel, rel_finite
+from test_stfa_oracle_golden import CURVE, FULL, NAN, SMALL, load_case, oracle_run, seeded_weights
 
 pytestmark = pytest.mark.gpu
-GOLD = os.path.join(os.path.dirname(__file__), "golden")
-DEV = "cuda:0"
 TOL, RTOL = 1e-4, 5e-4 / 2 ** 12
 LADDER = [5e-4 / 2 ** k for k in range(13)]
 ROW = dict(patch_size=2, num_patch=25, num_nodes=14, hidden_dim=16, output_dim=5, encoder_hidden_dim=64, num_heads=10, dropout=0.2)
+V = ("v.weight", "v.bias")
 
 
 def make_cfg(T=2, P=3, C=2, Hd=2, E=3, dropout=0.2, nodes=14):
@@ -43,64 +42,23 @@ def make_cfg(T=2, P=3, C=2, Hd=2, E=3, dropout=0.2, nodes=14):
 
 def build_model(cfg, sd, dropout=0.0):
     from gnn_rul_benchmarking_amd.stfa import STFA_model
-    m = STFA_model(**cfg)
-    m.load_state_dict({k: torch.from_numpy(np.asarray(v, np.float32)) for k, v in sd.items()}, strict=True)
-    m.dropout_p = dropout
-    return m.to(DEV)
-
-
-def grads_of(m, bucket=None):
-    flat = (m._grad_flat if bucket is None else bucket)[:m.num_live].detach().cpu().numpy().astype(np.float64)
-    return {name: flat[off:off + int(np.prod(shape))].reshape(shape) for name, (off, shape) in m._layout.items()}
-
-
-def dev(a):
-    return torch.from_numpy(np.asarray(a, np.float32)).to(DEV)
+    return K.build_model(STFA_model, cfg, sd, dropout)
 
 
 def check_grads(what, got, g64, ref32):
-    """Every tensor through the element-wise gate; v's two exactly zero.  Other tensors whose gradient is zero in exact arithmetic (the
-    recurrent weights at T = 1) are detected (grad_gate.zero_in_exact_arithmetic), not listed, and held to the rule GDAGDL and GAT_LSTM
-    use: at most 16 times the reference's own residue, or fp32 ulps of the model's largest gradient."""
-    zero = GG.zero_in_exact_arithmetic(g64, ref32)
-    gmax = max(float(np.abs(v).max()) for v in g64.values())
-    ladder = np.zeros(len(LADDER))
-    worst = (0.0, None)
+    """Every tensor through the element-wise gate; v's two exactly zero, in the reference's fp64 and fp32 runs and in the kernels.  Other
+    tensors whose gradient is zero in exact arithmetic (the recurrent weights at T = 1) are detected, not listed, and held to the rule
+    GDAGDL and GAT_LSTM use (family_kit.residue_bound)."""
     assert list(got) == list(g64)
-    for k in g64:
-        assert got[k].shape == g64[k].shape, k
-        if k in ("v.weight", "v.bias"):
-            assert not g64[k].any() and not np.asarray(ref32[k]).any() and not got[k].any(), k      # exactly zero, everywhere
-            continue
-        if k in zero:
-            bound = 16 * max(float(np.abs(ref32[k]).max()), 2.0 ** -23 * gmax)
-            assert np.abs(got[k]).max() <= bound, (k, np.abs(got[k]).max(), bound)
-            continue
-        floor = GG.floor_for(ref32[k], g64[k])
-        if O.noise_partner(k):          # a one-element tensor shares its head's attention.weight noise (stfa_oracle.noise_partner)
-            floor = max(floor, GG.floor_for(ref32[O.noise_partner(k)], g64[O.noise_partner(k)]))
-        ladder = np.maximum(ladder, [GG.gate(got[k], g64[k], r, floor)[0] for r in LADDER])
-        ratio, where = GG.gate(got[k], g64[k], RTOL, floor)
-        if ratio > 0.25:
-            print(f"  grad {k}: gate {ratio:.3f} at {where}  rel {rel(got[k], g64[k]):.2e}  max|g| {np.abs(g64[k]).max():.2e}")
-        worst = max(worst, (ratio, k))
-    print(f"STFA-GATE {what}: worst gradient gate ratio {worst[0]:.3f} ({worst[1]}); zero in exact arithmetic: {zero}")
-    print(f"STFA-LADDER {what}: " + " ".join(f"{v:.3f}" for v in ladder))
-    assert worst[0] <= 1.0, worst
+    for k in V:
+        assert not g64[k].any() and not np.asarray(ref32[k]).any(), k
+    K.check_grads(what, "STFA", got, g64, ref32, RTOL, K.RESIDUE, exact_zero=V, noise_partner=O.noise_partner, ladder=LADDER)
 
 
 def check_forward(what, m, bs, pred, loss, want, want_loss):
-    errs = {"pred": rel_finite(pred.detach().cpu().numpy().reshape(-1), np.asarray(want["pred"]).reshape(-1))}
-    for k in ("gat", "rows", "lstm"):
-        if k in want:
-            got = m.tap(bs, k).cpu().numpy()
-            assert got.shape == np.asarray(want[k]).shape, k
-            errs[k] = rel_finite(got, want[k])
-    if loss is not None and np.isfinite(want_loss):
-        errs["loss"] = abs(float(loss) - want_loss) / abs(want_loss)
-    print(f"STFA-GATE {what}: forward " + " ".join(f"{k}={v:.2e}" for k, v in errs.items()))
-    for k, v in errs.items():
-        assert v < TOL, (k, v)
+    errs = {**K.pred_err(pred, want, rel_finite), **K.tap_errs(m, bs, want, [k for k in ("gat", "rows", "lstm") if k in want], rel_finite),
+            **(K.loss_err(loss, want_loss) if np.isfinite(want_loss) else {})}
+    K.check_forward(what, "STFA", errs, TOL)
 
 
 def fixture_grads(name):
@@ -284,120 +242,53 @@ def test_two_runs_give_the_same_bits(case):
 
 # ---- 6. the optimizer, the curve, the harness -------------------------------------------------------------------------------------------
 def test_fused_step_applies_adam_to_every_element_once():
-    """The twin-model procedure of tests/test_fused_adam_families_gpu.py (bounds from tests/adam_reference.py), dropout and weight decay
-    on: every element of the flat buffer within the bounds -- v's included, which move although their gradient is zero."""
-    from gnn_rul_benchmarking_amd.optim import FusedAdam
-    from test_fused_adam_families_gpu import LR, SEED, STEP0, WD, _bits, _np
+    """The twin-model procedure (family_kit.adam_twin_check), dropout and weight decay on: every element of the flat buffer within the
+    bounds -- v's included, which move although their gradient is zero."""
+    from test_fused_adam_families_gpu import LR
     z, cfg, sd = load_case(SMALL[1])
-    x, y = dev(z["x"]), dev(z["y"])
-    assert WD > 0
+    vsl = []
 
-    def ready():
-        m = build_model(cfg, sd, dropout=0.2).train()
-        m._seed = SEED
-        return m
-    a = ready()
-    p0 = _np(a.flat_params)
-    _, loss_a = a.fused_mse_step(x, y)
-    g_a, loss_a = _np(a.bucket[:a.num_live]), float(loss_a)
-    assert np.isfinite(g_a).all() and np.array_equal(_bits(_np(a.flat_params)), _bits(p0))
-    b = ready()
-    opt = FusedAdam(b, lr=LR, weight_decay=WD)
-    m0, v0 = R.moments_like(g_a, np.random.default_rng(12))
-    voff, vshape = b._layout["v.weight"]
-    vsl = slice(voff, voff + int(np.prod(vshape)) + 1)            # v.weight and v.bias are adjacent
-    m0[vsl], v0[vsl] = 0.0, 0.0                                   # a zero gradient from the first step on: zero moments
-    s = opt.state_dict()
-    s.update(step=STEP0, exp_avg=torch.from_numpy(m0).to(DEV), exp_avg_sq=torch.from_numpy(v0).to(DEV))
-    opt.load_state_dict(s)
-    worst = dict(p=0.0, m=0.0, v=0.0)
-    for k in (STEP0 + 1, STEP0 + 2, STEP0 + 3):
-        before = tuple(_np(t) for t in (b.flat_params, opt._exp_avg, opt._exp_avg_sq))
-        _, loss_b = b.fused_mse_step(x, y, opt)
-        g = _np(b.bucket[:b.num_live])
-        after = tuple(_np(t) for t in (b.flat_params, opt._exp_avg, opt._exp_avg_sq))
-        if k == STEP0 + 1:
-            assert np.array_equal(_bits(g), _bits(g_a)) and float(loss_b) == loss_a
-        assert not g[vsl].any()
-        r = R.check(after, before[0], g, before[1], before[2], k, WD, 1.0, what=f"STFA, step {k}")
-        worst = {q: max(worst[q], r[q]) for q in worst}
-        moved = after[0][vsl] - before[0][vsl]
-        big = np.abs(before[0][vsl]) > 1e-3
-        assert big.any() and (np.sign(moved[big]) == -np.sign(before[0][vsl][big])).all()      # towards zero, by the weight decay alone
+    def zero_moments_of_v(m0, v0, model):
+        voff, vshape = model._layout["v.weight"]
+        vsl.append(slice(voff, voff + int(np.prod(vshape)) + 1))    # v.weight and v.bias are adjacent
+        m0[vsl[0]], v0[vsl[0]] = 0.0, 0.0                           # a zero gradient from the first step on: zero moments
+
+    def v_moves_by_the_weight_decay_alone(before, after, g):
+        assert not g[vsl[0]].any()
+        moved = after[0][vsl[0]] - before[0][vsl[0]]
+        big = np.abs(before[0][vsl[0]]) > 1e-3
+        assert big.any() and (np.sign(moved[big]) == -np.sign(before[0][vsl[0]][big])).all()      # towards zero
         assert (np.abs(moved[big]) > 0.1 * LR).all() and (np.abs(moved[big]) < 10 * LR).all()
-    assert opt._steps == STEP0 + 3
-    print("ADAM-RATIO family STFA: " + " ".join(f"{q}={worst[q]:.3f}" for q in "pmv"))
+    K.adam_twin_check(lambda: build_model(cfg, sd, dropout=0.2).train(), dev(z["x"]), dev(z["y"]), "STFA",
+                      prepare_moments=zero_moments_of_v, after_step=v_moves_by_the_weight_decay_alone)
 
 
 def test_training_curve_matches_reference_algorithm():
     """Twenty update() steps against the reference's own.  Tolerances: GRU_CM's curve tolerances (tests/test_grucm_gpu.py: the first
     three losses 1e-4, every loss 2e-3, the parameters at the end 2e-3, the eval prediction at the end 5e-3).  v is included and moved."""
-    from gnn_rul_benchmarking_amd.algorithms import get_algorithm_class
     z = np.load(os.path.join(GOLD, CURVE + ".npz"))
     cfg = json.loads(str(z["cfg_json"]))
-    algo = get_algorithm_class("STFA")(cfg, {"learning_rate": float(z["lr"]), "weight_decay": float(z["wd"])}, DEV)
-    algo.model.load_state_dict({k[4:]: torch.from_numpy(z[k]) for k in z.files if k.startswith("sd0:")}, strict=True)
-    assert algo.model.dropout_p == 0.0 and "device" not in cfg
-    algo.to(DEV).train()
-    xs, ys = torch.from_numpy(z["xs"]).to(DEV), torch.from_numpy(z["ys"]).to(DEV)
-    losses = np.asarray([algo.update(xs[s], ys[s], 1)["loss"] for s in range(xs.size(0))])
-    ref = z["losses"]
-    print("STFA-GATE curve: worst loss ratio", np.abs(losses / ref - 1).max())
-    assert len(ref) == 20 and np.max(np.abs(losses[:3] - ref[:3]) / ref[:3]) < 1e-4
-    assert np.max(np.abs(losses - ref) / ref) < 2e-3
-    sd = algo.model.state_dict()
-    for k in O.param_names(cfg):
-        assert rel(sd[k].cpu().numpy(), z["sd20:" + k]) < 2e-3, k
-    for k in ("v.weight", "v.bias"):
+    assert "device" not in cfg
+    sd0 = {k[4:]: z[k] for k in z.files if k.startswith("sd0:")}
+    _, sd = K.curve_check("STFA", "STFA", cfg, z, sd0, dict(steps=20, first3=1e-4, every=2e-3, params=2e-3, eval=5e-3), dropout_off=False)
+    assert list(sd) == O.param_names(cfg)
+    for k in V:
         assert np.abs(sd[k].cpu().numpy() - z["sd0:" + k]).max() > 10 * float(z["lr"]), k      # it moved
-    algo.eval()
-    with torch.no_grad():
-        assert rel(algo.model(xs[0]).cpu().numpy(), z["eval_pred_end"]) < 5e-3
 
 
 def test_trainer_matches_reference_harness_run_on_cmapss(tmp_path, monkeypatch):
     """--GNN_method STFA on C-MAPSS FD001 as the reference wires it: the reference's own harness, run on the CPU by
     tests/golden/make_golden_stfa.py::case_trainer_cmapss with the row's dropout set to 0, vs this package's harness on the GPU with the
     same switch.  Bars: those of tests/test_trainer_gpu.py's C-MAPSS harness tests."""
-    import argparse
-    import sys
-    sys.path.insert(0, GOLD)
-    from synth import synthetic_cmapss
-    from gnn_rul_benchmarking_amd import trainer as T
     z = np.load(os.path.join(GOLD, "stfa_trainer_fd001_reference_run.npz"))
-    (xtr, ytr), (xte, yte) = synthetic_cmapss(int(z["seed"]), int(z["n_train"]), int(z["n_test"]))
-    assert abs(xtr.astype(np.float64).sum() - float(z["x_train_checksum"])) < 1e-6
-    d = tmp_path / "data" / "CMAPSS" / "FD001"
-    os.makedirs(d)
-    torch.save({"samples": xtr, "labels": ytr, "max_ruls": 125}, d / "train.pt")
-    torch.save({"samples": xte, "labels": yte, "max_ruls": 125}, d / "test.pt")
-    monkeypatch.chdir(tmp_path)
-    args = argparse.Namespace(save_dir=str(tmp_path / "logs"), experiment_description="exp", run_description="r",
-                              GNN_method="STFA", data_path=str(tmp_path / "data"), dataset="CMAPSS",
-                              dataset_id="FD001", bearing_id=None, num_runs=1, device=DEV)
-    tr = T.GNN_RUL_trainer(args)
-    tr.train_configs["num_epochs"] = int(z["epochs"])
-    assert tr.train_configs["batch_size"] == int(z["batch_size"]) and tr.train_configs["learning_rate"] == float(z["lr"])
-    assert tr.model_configs == ROW
-    tr.model_configs["dropout"] = 0.0
-    per_epoch = []
-    orig = tr.calc_results_per_run
 
-    def spy(run_id):
-        per_epoch.append(T._calc_metrics(tr.pred_labels, tr.true_labels, tr.max_ruls))
-        return orig(run_id)
-    tr.calc_results_per_run = spy
-    tr.train()
-    got, ref = np.asarray(per_epoch, np.float64), z["per_epoch"]
-    print("STFA harness per-epoch got/ref:\n", got, "\n", ref)
-    assert got.shape == ref.shape == (int(z["epochs"]), 4)
-    assert np.max(np.abs(got[:, 2:] - ref[:, 2:]) / np.abs(ref[:, 2:])) < 1e-3      # MAE, RMSE (in RUL cycles), relative
-    assert np.max(np.abs(got[:, 3] - ref[:, 3]) / 125.0) < 1e-3                      # RMSE on the normalised scale, absolute
-    sd = tr.algorithm.state_dict()
-    for k in z.files:
-        if k.startswith("final:"):
-            a, b = sd["model." + k[6:]].cpu().numpy().astype(np.float64), z[k].astype(np.float64)
-            assert np.max(np.abs(a - b)) / max(np.max(np.abs(b)), 1e-30) < 2e-3, k
+    def row(tr):
+        assert tr.train_configs["batch_size"] == int(z["batch_size"]) and tr.train_configs["learning_rate"] == float(z["lr"])
+        assert tr.model_configs == ROW
+        tr.model_configs["dropout"] = 0.0
+    tr, per_epoch = K.harness_run(tmp_path, monkeypatch, "STFA", "CMAPSS", "FD001", z, configure=row)
+    K.assert_harness("STFA", per_epoch, K.state_of(tr), z,        # MAE, RMSE (in RUL cycles), relative; RMSE on the normalised scale, absolute
+                     dict(rmse_abs=1e-3, rmse_scale=125.0, rel=1e-3, rel_from=2, final=2e-3, final_prefix="model."))
 
 
 # ---- 7. NaN ----------------------------------------------------------------------------------------------------------------------------
@@ -422,10 +313,4 @@ def test_nan_fixture_poisons_exactly_its_own_sample():
                          ids=["num_patch129", "patch_size65", "output_dim17", "heads17", "lstm129", "nodes13", "nodes15"])
 def test_just_outside_each_limit_is_not_covered_and_launches_nothing(cfg):
     from gnn_rul_benchmarking_amd.stfa import STFA_model
-    m = STFA_model(**cfg).to(DEV)
-    x = torch.rand(2, cfg["num_nodes"], cfg["num_patch"] * cfg["patch_size"], device=DEV)
-    with pytest.raises(RuntimeError, match="do not cover this configuration"):
-        m(x)
-    with pytest.raises(RuntimeError, match="do not cover this configuration"):
-        m.fused_mse_step(x, torch.zeros(2, device=DEV))
-    assert not m._bufs and not m._grad_flat.any()                  # no workspace was made, nothing was written
+    K.refused_outside_limits(STFA_model(**cfg), torch.rand(2, cfg["num_nodes"], cfg["num_patch"] * cfg["patch_size"], device=DEV))

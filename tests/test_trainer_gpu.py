@@ -1,12 +1,15 @@
 """-m gpu: end-to-end harness run on a synthetic C-MAPSS-shaped dataset written in the reference's
 on-disk format ({'samples','labels','max_ruls'} in train.pt / test.pt)."""
 import argparse
+import io
 import os
 
 import numpy as np
 import pandas as pd
 import pytest
 import torch
+
+import family_kit as K
 
 pytestmark = pytest.mark.gpu
 
@@ -85,102 +88,58 @@ def test_unknown_method_and_dataset_errors(tmp_path):
         GNN_RUL_trainer(argparse.Namespace(GNN_method="ST_GCN", **dict(base, dataset="NOPE")))
 
 
+# ---- the reference's own harness runs (fixtures made on the CPU by tests/golden/make_golden*.py) against this package's on the GPU ----------
+# family_kit.harness_run writes the synthetic data set, builds the arguments, spies on calc_results_per_run and trains;
+# family_kit.assert_harness holds the comparisons.  The bars and each row's own checks stay here.
+CMAPSS = dict(rmse_abs=1e-3, rmse_scale=125.0, rel=1e-3, rel_from=2, final_prefix="")      # MAE, RMSE (in RUL cycles) relative; RMSE on the normalised scale
+PHM2012 = dict(rmse_abs=1e-3, rmse_scale=1.0, rel=1e-3, rel_from=2, final_prefix="")       # RMSE absolute (north star); MAE, RMSE relative
+
+
+def gold(name):
+    return np.load(os.path.join(K.GOLD, name + ".npz"))
+
+
+def same_csv_rows(tmp_path, method, z, rtol=None, cols=slice(None)):
+    """results.csv has the reference's columns and rows (first row inf, then one row per RMSE improvement)."""
+    csv = pd.read_csv(tmp_path / "logs" / "exp" / "r" / f"{method}_run_0" / "results.csv")
+    ref_csv = pd.read_csv(io.StringIO(str(z["csv_text"])))
+    assert list(csv.columns) == list(ref_csv.columns) and len(csv) == len(ref_csv)
+    if rtol is not None:
+        assert np.allclose(csv.iloc[1:].to_numpy()[:, cols], ref_csv.iloc[1:].to_numpy()[:, cols], rtol=rtol)
+
+
+def batch_and_rate(tr, z):
+    assert tr.train_configs["batch_size"] == int(z["batch_size"]) and tr.train_configs["learning_rate"] == float(z["lr"])
+
+
 def test_trainer_matches_reference_harness_run_on_phm2012(tmp_path, monkeypatch):
     """End-to-end RMSE parity: the reference's own harness (trainer.GNN_RUL_trainer, run on CPU by
     tests/golden/make_golden.py::case_trainer_phm2012) vs this package's harness on the GPU, same synthetic
     PHM2012 Condition_1 dataset, same seed (=> same initial weights), same batches (shuffle off), dropout off.
     BASELINE.json asks for RMSE within 1e-3 of the reference."""
-    import sys
-    from conftest import GOLDEN
-    sys.path.insert(0, GOLDEN)
-    from synth import synthetic_phm2012
-    from gnn_rul_benchmarking_amd import trainer as T
-    z = np.load(os.path.join(GOLDEN, "trainer_phm2012_c1_reference_run.npz"))
-    (xtr, ytr), (xte, yte) = synthetic_phm2012(int(z["seed"]), int(z["n_train"]), int(z["n_test"]))
-    assert abs(xtr.astype(np.float64).sum() - float(z["x_train_checksum"])) < 1e-6
-    d = tmp_path / "data" / "PHM2012" / "Condition_1"
-    os.makedirs(d)
-    torch.save({"samples": xtr, "labels": ytr, "max_ruls": 1.0}, d / "train.pt")
-    torch.save({"samples": xte, "labels": yte, "max_ruls": 1.0}, d / "test.pt")
-    monkeypatch.chdir(tmp_path)
-    args = argparse.Namespace(save_dir=str(tmp_path / "logs"), experiment_description="exp", run_description="r",
-                              GNN_method="ST_GCN", data_path=str(tmp_path / "data"), dataset="PHM2012",
-                              dataset_id="Condition_1", bearing_id="Testing_bearing_1", num_runs=1, device="cuda:0")
-    tr = T.GNN_RUL_trainer(args)
-    tr.train_configs["num_epochs"] = int(z["epochs"])
-    tr.model_configs["dropout"] = 1e-12
-    assert tr.train_configs["batch_size"] == int(z["batch_size"]) and tr.train_configs["learning_rate"] == float(z["lr"])
-    per_epoch = []
-    orig = tr.calc_results_per_run
+    z = gold("trainer_phm2012_c1_reference_run")
 
-    def spy(run_id):
-        per_epoch.append(T._calc_metrics(tr.pred_labels, tr.true_labels, tr.max_ruls))
-        return orig(run_id)
-    tr.calc_results_per_run = spy
-    tr.train()
-    got, ref = np.asarray(per_epoch, np.float64), z["per_epoch"]
-    assert got.shape == ref.shape == (3, 4)
-    assert np.max(np.abs(got[:, 3] - ref[:, 3])) < 1e-3                  # RMSE, absolute (north star)
-    assert np.max(np.abs(got - ref) / np.abs(ref)) < 2e-4                # Score_v1, Score_v2, MAE, RMSE, relative
-    sd = tr.algorithm.state_dict()
-    for k in z.files:
-        if k.startswith("final:"):
-            a, b = sd[k[6:]].cpu().numpy().astype(np.float64), z[k].astype(np.float64)
-            assert np.max(np.abs(a - b)) / np.max(np.abs(b)) < 2e-4, k
-    # the results CSV has the same rows (first row inf, then one row per RMSE improvement)
-    csv = pd.read_csv(tmp_path / "logs" / "exp" / "r" / "ST_GCN_run_0" / "results.csv")
-    import io
-    ref_csv = pd.read_csv(io.StringIO(str(z["csv_text"])))
-    assert list(csv.columns) == list(ref_csv.columns) and len(csv) == len(ref_csv)
-    assert np.allclose(csv.iloc[1:].to_numpy(), ref_csv.iloc[1:].to_numpy(), rtol=2e-4)
+    def row(tr):
+        tr.model_configs["dropout"] = 1e-12
+        batch_and_rate(tr, z)
+    tr, per_epoch = K.harness_run(tmp_path, monkeypatch, "ST_GCN", "PHM2012", "Condition_1", z, configure=row)
+    # RMSE, absolute (north star); Score_v1, Score_v2, MAE, RMSE, relative
+    K.assert_harness(None, per_epoch, K.state_of(tr), z, dict(PHM2012, rel=2e-4, rel_from=0, final=2e-4))
+    same_csv_rows(tmp_path, "ST_GCN", z, rtol=2e-4)
 
 
 def test_stmsgcn_trainer_matches_reference_harness_run_on_phm2012(tmp_path, monkeypatch):
     """Same as above for --GNN_method STMSGCN (reference hparams: lr 1e-2, wd 0, batch 100, 160 patches of 16 points):
     the reference's own harness, run on CPU by tests/golden/make_golden_stmsgcn.py::case_trainer_phm2012, vs this
     package's harness on the GPU."""
-    import sys
-    from conftest import GOLDEN
-    sys.path.insert(0, GOLDEN)
-    from synth import synthetic_phm2012
-    from gnn_rul_benchmarking_amd import trainer as T
-    z = np.load(os.path.join(GOLDEN, "stmsgcn_trainer_phm2012_c1_reference_run.npz"))
-    (xtr, ytr), (xte, yte) = synthetic_phm2012(int(z["seed"]), int(z["n_train"]), int(z["n_test"]))
-    assert abs(xtr.astype(np.float64).sum() - float(z["x_train_checksum"])) < 1e-6
-    d = tmp_path / "data" / "PHM2012" / "Condition_1"
-    os.makedirs(d)
-    torch.save({"samples": xtr, "labels": ytr, "max_ruls": 1.0}, d / "train.pt")
-    torch.save({"samples": xte, "labels": yte, "max_ruls": 1.0}, d / "test.pt")
-    monkeypatch.chdir(tmp_path)
-    args = argparse.Namespace(save_dir=str(tmp_path / "logs"), experiment_description="exp", run_description="r",
-                              GNN_method="STMSGCN", data_path=str(tmp_path / "data"), dataset="PHM2012",
-                              dataset_id="Condition_1", bearing_id="Testing_bearing_1", num_runs=1, device="cuda:0")
-    tr = T.GNN_RUL_trainer(args)
-    tr.train_configs["num_epochs"] = int(z["epochs"])
-    assert tr.train_configs["batch_size"] == int(z["batch_size"]) and tr.train_configs["learning_rate"] == float(z["lr"])
-    assert tr.model_configs["num_patch"] == 160 and tr.model_configs["interval"] == 6
-    per_epoch = []
-    orig = tr.calc_results_per_run
+    z = gold("stmsgcn_trainer_phm2012_c1_reference_run")
 
-    def spy(run_id):
-        per_epoch.append(T._calc_metrics(tr.pred_labels, tr.true_labels, tr.max_ruls))
-        return orig(run_id)
-    tr.calc_results_per_run = spy
-    tr.train()
-    got, ref = np.asarray(per_epoch, np.float64), z["per_epoch"]
-    print("STMSGCN harness per-epoch got/ref:\n", got, "\n", ref)
-    assert got.shape == ref.shape == (3, 4)
-    assert np.max(np.abs(got[:, 3] - ref[:, 3])) < 1e-3                  # RMSE, absolute (north star)
-    assert np.max(np.abs(got[:, 2:] - ref[:, 2:]) / np.abs(ref[:, 2:])) < 1e-3      # MAE, RMSE relative
-    sd = tr.algorithm.state_dict()
-    for k in z.files:
-        if k.startswith("final:"):
-            a, b = sd[k[6:]].cpu().numpy().astype(np.float64), z[k].astype(np.float64)
-            assert np.max(np.abs(a - b)) / np.max(np.abs(b)) < 2e-3, k
-    csv = pd.read_csv(tmp_path / "logs" / "exp" / "r" / "STMSGCN_run_0" / "results.csv")
-    import io
-    ref_csv = pd.read_csv(io.StringIO(str(z["csv_text"])))
-    assert list(csv.columns) == list(ref_csv.columns) and len(csv) == len(ref_csv)
+    def row(tr):
+        batch_and_rate(tr, z)
+        assert tr.model_configs["num_patch"] == 160 and tr.model_configs["interval"] == 6
+    tr, per_epoch = K.harness_run(tmp_path, monkeypatch, "STMSGCN", "PHM2012", "Condition_1", z, configure=row)
+    K.assert_harness("STMSGCN", per_epoch, K.state_of(tr), z, dict(PHM2012, final=2e-3))
+    same_csv_rows(tmp_path, "STMSGCN", z)
 
 
 def test_astgcnn_trainer_matches_reference_harness_run_on_cmapss(tmp_path, monkeypatch):
@@ -188,49 +147,15 @@ def test_astgcnn_trainer_matches_reference_harness_run_on_cmapss(tmp_path, monke
     data_model_configs.py:13): the reference's own harness, run on CPU by
     tests/golden/make_golden_astgcnn.py::case_trainer_cmapss, vs this package's harness on the GPU.  Equal results need
     the same initial weights AND the same shuffled batches, i.e. the same global-RNG consumption as torch's DataLoader."""
-    import sys
-    from conftest import GOLDEN
-    sys.path.insert(0, GOLDEN)
-    from synth import synthetic_cmapss
-    from gnn_rul_benchmarking_amd import trainer as T
-    z = np.load(os.path.join(GOLDEN, "astgcnn_trainer_cmapss_fd001_reference_run.npz"))
-    (xtr, ytr), (xte, yte) = synthetic_cmapss(int(z["seed"]), int(z["n_train"]), int(z["n_test"]))
-    assert abs(xtr.astype(np.float64).sum() - float(z["x_train_checksum"])) < 1e-6
-    d = tmp_path / "data" / "CMAPSS" / "FD001"
-    os.makedirs(d)
-    torch.save({"samples": xtr, "labels": ytr, "max_ruls": 125}, d / "train.pt")
-    torch.save({"samples": xte, "labels": yte, "max_ruls": 125}, d / "test.pt")
-    monkeypatch.chdir(tmp_path)
-    args = argparse.Namespace(save_dir=str(tmp_path / "logs"), experiment_description="exp", run_description="r",
-                              GNN_method="ASTGCNN", data_path=str(tmp_path / "data"), dataset="CMAPSS",
-                              dataset_id="FD001", bearing_id="Testing_bearing_1", num_runs=1, device="cuda:0")
-    tr = T.GNN_RUL_trainer(args)
-    tr.train_configs["num_epochs"] = int(z["epochs"])
-    assert tr.dataset_configs.shuffle is True
-    assert tr.train_configs["batch_size"] == int(z["batch_size"]) and tr.train_configs["learning_rate"] == float(z["lr"])
-    assert tr.model_configs == dict(num_nodes=14, time_length=50, encoder_out_dim=50, output_dim=64, K=3)
-    per_epoch = []
-    orig = tr.calc_results_per_run
+    z = gold("astgcnn_trainer_cmapss_fd001_reference_run")
 
-    def spy(run_id):
-        per_epoch.append(T._calc_metrics(tr.pred_labels, tr.true_labels, tr.max_ruls))
-        return orig(run_id)
-    tr.calc_results_per_run = spy
-    tr.train()
-    got, ref = np.asarray(per_epoch, np.float64), z["per_epoch"]
-    print("ASTGCNN harness per-epoch got/ref:\n", got, "\n", ref)
-    assert got.shape == ref.shape == (3, 4)
-    assert np.max(np.abs(got[:, 2:] - ref[:, 2:]) / np.abs(ref[:, 2:])) < 1e-3      # MAE, RMSE (in RUL cycles), relative
-    assert np.max(np.abs(got[:, 3] - ref[:, 3]) / 125.0) < 1e-3                      # RMSE on the normalised scale, absolute
-    sd = tr.algorithm.state_dict()
-    for k in z.files:
-        if k.startswith("final:"):
-            a, b = sd[k[6:]].cpu().numpy().astype(np.float64), z[k].astype(np.float64)
-            assert np.max(np.abs(a - b)) / max(np.max(np.abs(b)), 1e-30) < 2e-3, k
-    csv = pd.read_csv(tmp_path / "logs" / "exp" / "r" / "ASTGCNN_run_0" / "results.csv")
-    import io
-    ref_csv = pd.read_csv(io.StringIO(str(z["csv_text"])))
-    assert list(csv.columns) == list(ref_csv.columns) and len(csv) == len(ref_csv)
+    def row(tr):
+        assert tr.dataset_configs.shuffle is True
+        batch_and_rate(tr, z)
+        assert tr.model_configs == dict(num_nodes=14, time_length=50, encoder_out_dim=50, output_dim=64, K=3)
+    tr, per_epoch = K.harness_run(tmp_path, monkeypatch, "ASTGCNN", "CMAPSS", "FD001", z, configure=row)
+    K.assert_harness("ASTGCNN", per_epoch, K.state_of(tr), z, dict(CMAPSS, final=2e-3))
+    same_csv_rows(tmp_path, "ASTGCNN", z)
 
 
 def test_fcstgnn_trainer_matches_reference_harness_run_on_cmapss(tmp_path, monkeypatch):
@@ -238,51 +163,13 @@ def test_fcstgnn_trainer_matches_reference_harness_run_on_cmapss(tmp_path, monke
     the reference's own harness, run on CPU by tests/golden/make_golden_fcstgnn.py::case_trainer_cmapss with the
     positional-encoding dropout switched off on the constructed model, vs this package's harness on the GPU with the same
     switch."""
-    import sys
-    from conftest import GOLDEN
-    sys.path.insert(0, GOLDEN)
-    from synth import synthetic_cmapss
-    from gnn_rul_benchmarking_amd import trainer as T
-    z = np.load(os.path.join(GOLDEN, "fcstgnn_trainer_cmapss_fd004_reference_run.npz"))
-    (xtr, ytr), (xte, yte) = synthetic_cmapss(int(z["seed"]), int(z["n_train"]), int(z["n_test"]))
-    assert abs(xtr.astype(np.float64).sum() - float(z["x_train_checksum"])) < 1e-6
-    d = tmp_path / "data" / "CMAPSS" / "FD004"
-    os.makedirs(d)
-    torch.save({"samples": xtr, "labels": ytr, "max_ruls": 125}, d / "train.pt")
-    torch.save({"samples": xte, "labels": yte, "max_ruls": 125}, d / "test.pt")
-    monkeypatch.chdir(tmp_path)
-    base = T.get_algorithm_class("FC_STGNN")
+    z = gold("fcstgnn_trainer_cmapss_fd004_reference_run")
 
-    class NoDropout(base):
-        def __init__(self, *a, **k):
-            super().__init__(*a, **k)
-            self.model.dropout_p = 0.0
-    monkeypatch.setattr(T, "get_algorithm_class", lambda n: NoDropout)
-    args = argparse.Namespace(save_dir=str(tmp_path / "logs"), experiment_description="exp", run_description="r",
-                              GNN_method="FC_STGNN", data_path=str(tmp_path / "data"), dataset="CMAPSS",
-                              dataset_id="FD004", bearing_id="Testing_bearing_1", num_runs=1, device="cuda:0")
-    tr = T.GNN_RUL_trainer(args)
-    tr.train_configs["num_epochs"] = int(z["epochs"])
-    assert tr.train_configs["batch_size"] == int(z["batch_size"]) and tr.train_configs["learning_rate"] == float(z["lr"])
-    assert tr.model_configs["num_patch"] == 25 and tr.model_configs["num_windows"] == 36
-    per_epoch = []
-    orig = tr.calc_results_per_run
-
-    def spy(run_id):
-        per_epoch.append(T._calc_metrics(tr.pred_labels, tr.true_labels, tr.max_ruls))
-        return orig(run_id)
-    tr.calc_results_per_run = spy
-    tr.train()
-    got, ref = np.asarray(per_epoch, np.float64), z["per_epoch"]
-    print("FC_STGNN harness per-epoch got/ref:\n", got, "\n", ref)
-    assert got.shape == ref.shape == (3, 4)
-    assert np.max(np.abs(got[:, 2:] - ref[:, 2:]) / np.abs(ref[:, 2:])) < 1e-3      # MAE, RMSE (in RUL cycles), relative
-    assert np.max(np.abs(got[:, 3] - ref[:, 3]) / 125.0) < 1e-3                      # RMSE on the normalised scale, absolute
-    sd = tr.algorithm.state_dict()
-    for k in z.files:
-        if k.startswith("final:"):
-            a, b = sd[k[6:]].cpu().numpy().astype(np.float64), z[k].astype(np.float64)
-            assert np.max(np.abs(a - b)) / max(np.max(np.abs(b)), 1e-30) < 3e-3, k
+    def row(tr):
+        batch_and_rate(tr, z)
+        assert tr.model_configs["num_patch"] == 25 and tr.model_configs["num_windows"] == 36
+    tr, per_epoch = K.harness_run(tmp_path, monkeypatch, "FC_STGNN", "CMAPSS", "FD004", z, no_dropout=K.model_dropout_off, configure=row)
+    K.assert_harness("FC_STGNN", per_epoch, K.state_of(tr), z, dict(CMAPSS, final=3e-3))
 
 
 def test_hagcn_trainer_runs_the_reference_protocol_on_cmapss(tmp_path, monkeypatch):
@@ -292,41 +179,15 @@ def test_hagcn_trainer_runs_the_reference_protocol_on_cmapss(tmp_path, monkeypat
     nodes from the first step on, and Adam amplifies that: perturbing the inputs of THIS package's run by 1e-7 moves its epoch-2
     test RMSE from 44.7 to 67.8 cycles (measured).  Single-step parity is covered in test_hagcn_gpu.py; here the
     harness must run the reference's protocol end to end and land in the same regime after the first epoch."""
-    import sys
-    from conftest import GOLDEN
-    sys.path.insert(0, GOLDEN)
-    from synth import synthetic_cmapss
-    from gnn_rul_benchmarking_amd import trainer as T
-    z = np.load(os.path.join(GOLDEN, "hagcn_trainer_cmapss_fd004_reference_run.npz"))
-    (xtr, ytr), (xte, yte) = synthetic_cmapss(int(z["seed"]), int(z["n_train"]), int(z["n_test"]))
-    assert abs(xtr.astype(np.float64).sum() - float(z["x_train_checksum"])) < 1e-6
-    d = tmp_path / "data" / "CMAPSS" / "FD004"
-    os.makedirs(d)
-    torch.save({"samples": xtr, "labels": ytr, "max_ruls": 125}, d / "train.pt")
-    torch.save({"samples": xte, "labels": yte, "max_ruls": 125}, d / "test.pt")
-    monkeypatch.chdir(tmp_path)
-    base = T.get_algorithm_class("HAGCN")
+    z = gold("hagcn_trainer_cmapss_fd004_reference_run")
 
-    class NoDropout(base):
-        def __init__(self, *a, **k):
-            super().__init__(*a, **k)
-            for dr in (self.model.TD.drop1, self.model.TD.drop2, self.model.TD.drop3):
-                dr.p = 0.0
-    monkeypatch.setattr(T, "get_algorithm_class", lambda n: NoDropout)
-    args = argparse.Namespace(save_dir=str(tmp_path / "logs"), experiment_description="exp", run_description="r",
-                              GNN_method="HAGCN", data_path=str(tmp_path / "data"), dataset="CMAPSS",
-                              dataset_id="FD004", bearing_id="Testing_bearing_1", num_runs=1, device="cuda:0")
-    tr = T.GNN_RUL_trainer(args)
-    tr.train_configs["num_epochs"] = int(z["epochs"])
-    assert tr.train_configs["alpha"] == 100 and tr.model_configs["patch_size"] == 50
-    per_epoch = []
-    orig = tr.calc_results_per_run
+    def lstm_stack_dropout_off(algo):
+        for dr in (algo.model.TD.drop1, algo.model.TD.drop2, algo.model.TD.drop3):
+            dr.p = 0.0
 
-    def spy(run_id):
-        per_epoch.append(T._calc_metrics(tr.pred_labels, tr.true_labels, tr.max_ruls))
-        return orig(run_id)
-    tr.calc_results_per_run = spy
-    tr.train()
+    def row(tr):
+        assert tr.train_configs["alpha"] == 100 and tr.model_configs["patch_size"] == 50
+    _, per_epoch = K.harness_run(tmp_path, monkeypatch, "HAGCN", "CMAPSS", "FD004", z, no_dropout=lstm_stack_dropout_off, configure=row)
     got, ref = np.asarray(per_epoch, np.float64), z["per_epoch"]
     print("HAGCN harness per-epoch got/ref:\n", got, "\n", ref)
     assert got.shape == ref.shape == (3, 4)
@@ -340,93 +201,29 @@ def test_hagcn_trainer_runs_the_reference_protocol_on_cmapss(tmp_path, monkeypat
 def test_stconv_trainer_matches_reference_harness_run_on_cmapss(tmp_path, monkeypatch):
     """--GNN_method ST_Conv on C-MAPSS FD002 as the reference wires it (configs/hparams.py:59,78; shuffling DataLoader): the
     reference's own harness, run on CPU by tests/golden/make_golden_stconv.py::case_trainer_cmapss, vs this package's on the GPU."""
-    import sys
-    from conftest import GOLDEN
-    sys.path.insert(0, GOLDEN)
-    from synth import synthetic_cmapss
-    from gnn_rul_benchmarking_amd import trainer as T
-    z = np.load(os.path.join(GOLDEN, "stconv_trainer_cmapss_fd002_reference_run.npz"))
-    (xtr, ytr), (xte, yte) = synthetic_cmapss(int(z["seed"]), int(z["n_train"]), int(z["n_test"]))
-    assert abs(xtr.astype(np.float64).sum() - float(z["x_train_checksum"])) < 1e-6
-    d = tmp_path / "data" / "CMAPSS" / "FD002"
-    os.makedirs(d)
-    torch.save({"samples": xtr, "labels": ytr, "max_ruls": 125}, d / "train.pt")
-    torch.save({"samples": xte, "labels": yte, "max_ruls": 125}, d / "test.pt")
-    monkeypatch.chdir(tmp_path)
-    args = argparse.Namespace(save_dir=str(tmp_path / "logs"), experiment_description="exp", run_description="r",
-                              GNN_method="ST_Conv", data_path=str(tmp_path / "data"), dataset="CMAPSS",
-                              dataset_id="FD002", bearing_id="Testing_bearing_1", num_runs=1, device="cuda:0")
-    tr = T.GNN_RUL_trainer(args)
-    tr.train_configs["num_epochs"] = int(z["epochs"])
-    assert tr.model_configs == dict(num_nodes=14, time_length=50, kernel_size=6)
-    per_epoch = []
-    orig = tr.calc_results_per_run
+    z = gold("stconv_trainer_cmapss_fd002_reference_run")
 
-    def spy(run_id):
-        per_epoch.append(T._calc_metrics(tr.pred_labels, tr.true_labels, tr.max_ruls))
-        return orig(run_id)
-    tr.calc_results_per_run = spy
-    tr.train()
-    got, ref = np.asarray(per_epoch, np.float64), z["per_epoch"]
-    print("ST_Conv harness per-epoch got/ref:\n", got, "\n", ref)
-    assert got.shape == ref.shape == (3, 4)
-    assert np.max(np.abs(got[:, 2:] - ref[:, 2:]) / np.abs(ref[:, 2:])) < 1e-3
-    assert np.max(np.abs(got[:, 3] - ref[:, 3]) / 125.0) < 1e-3
-    sd = tr.algorithm.state_dict()
-    for k in z.files:
-        if k.startswith("final:"):
-            a, b = sd[k[6:]].cpu().numpy().astype(np.float64), z[k].astype(np.float64)
-            assert np.max(np.abs(a - b)) / max(np.max(np.abs(b)), 1e-30) < 2e-3, k
+    def row(tr):
+        assert tr.model_configs == dict(num_nodes=14, time_length=50, kernel_size=6)
+    tr, per_epoch = K.harness_run(tmp_path, monkeypatch, "ST_Conv", "CMAPSS", "FD002", z, configure=row)
+    K.assert_harness("ST_Conv", per_epoch, K.state_of(tr), z, dict(CMAPSS, final=2e-3))
 
 
 def test_stgnn_trainer_matches_reference_harness_run_on_cmapss(tmp_path, monkeypatch):
     """--GNN_method STGNN on C-MAPSS FD003 as the reference wires it (configs/hparams.py:105,128; shuffling DataLoader): the
     reference's own harness, run on CPU by tests/golden/make_golden_stgnn.py::case_trainer_cmapss, vs this package's harness
     on the GPU (HIP graph function + HIP GRU through autograd, torch.optim.Adam like the reference)."""
-    import sys
-    from conftest import GOLDEN
-    sys.path.insert(0, GOLDEN)
-    from synth import synthetic_cmapss
-    from gnn_rul_benchmarking_amd import trainer as T
-    z = np.load(os.path.join(GOLDEN, "stgnn_trainer_cmapss_fd003_reference_run.npz"))
-    (xtr, ytr), (xte, yte) = synthetic_cmapss(int(z["seed"]), int(z["n_train"]), int(z["n_test"]))
-    assert abs(xtr.astype(np.float64).sum() - float(z["x_train_checksum"])) < 1e-6
-    d = tmp_path / "data" / "CMAPSS" / "FD003"
-    os.makedirs(d)
-    torch.save({"samples": xtr, "labels": ytr, "max_ruls": 125}, d / "train.pt")
-    torch.save({"samples": xte, "labels": yte, "max_ruls": 125}, d / "test.pt")
-    monkeypatch.chdir(tmp_path)
-    args = argparse.Namespace(save_dir=str(tmp_path / "logs"), experiment_description="exp", run_description="r",
-                              GNN_method="STGNN", data_path=str(tmp_path / "data"), dataset="CMAPSS",
-                              dataset_id="FD003", bearing_id="Testing_bearing_1", num_runs=1, device="cuda:0")
-    tr = T.GNN_RUL_trainer(args)
-    tr.train_configs["num_epochs"] = int(z["epochs"])
-    assert tr.train_configs["batch_size"] == int(z["batch_size"]) and tr.train_configs["learning_rate"] == float(z["lr"])
-    assert tr.model_configs == dict(patch_size=50, num_patch=1, num_nodes=14, hidden_dim=64, K=3, top_k=10)
-    per_epoch = []
-    orig = tr.calc_results_per_run
+    z = gold("stgnn_trainer_cmapss_fd003_reference_run")
 
-    def spy(run_id):
-        per_epoch.append(T._calc_metrics(tr.pred_labels, tr.true_labels, tr.max_ruls))
-        return orig(run_id)
-    tr.calc_results_per_run = spy
-    tr.train()
-    got, ref = np.asarray(per_epoch, np.float64), z["per_epoch"]
-    print("STGNN harness per-epoch got/ref:\n", got, "\n", ref)
-    assert got.shape == ref.shape == (3, 4)
-    assert np.max(np.abs(got[:, 2:] - ref[:, 2:]) / np.abs(ref[:, 2:])) < 2e-3      # MAE, RMSE (in RUL cycles), relative
-    sd = tr.algorithm.state_dict()
-    for k in z.files:
-        if k.startswith("final:"):
-            a, b = sd[k[6:]].cpu().numpy().astype(np.float64), z[k].astype(np.float64)
-            assert np.max(np.abs(a - b)) / max(np.max(np.abs(b)), 1e-30) < 3e-3, k
-    a = sd["model.chebnet.filters"].cpu().numpy().astype(np.float64).mean(axis=1)
+    def row(tr):
+        batch_and_rate(tr, z)
+        assert tr.model_configs == dict(patch_size=50, num_patch=1, num_nodes=14, hidden_dim=64, K=3, top_k=10)
+    tr, per_epoch = K.harness_run(tmp_path, monkeypatch, "STGNN", "CMAPSS", "FD003", z, configure=row)
+    sd = K.state_of(tr)
+    K.assert_harness("STGNN", per_epoch, sd, z, dict(rel=2e-3, rel_from=2, final=3e-3, final_prefix=""))      # MAE, RMSE (in RUL cycles), relative
+    a = sd["model.chebnet.filters"].astype(np.float64).mean(axis=1)
     assert np.max(np.abs(a - z["final_mean:model.chebnet.filters"])) / np.max(np.abs(z["final_mean:model.chebnet.filters"])) < 3e-3
-    csv = pd.read_csv(tmp_path / "logs" / "exp" / "r" / "STGNN_run_0" / "results.csv")
-    import io
-    ref_csv = pd.read_csv(io.StringIO(str(z["csv_text"])))
-    assert list(csv.columns) == list(ref_csv.columns) and len(csv) == len(ref_csv)
-    assert np.allclose(csv.iloc[1:].to_numpy()[:, 2:], ref_csv.iloc[1:].to_numpy()[:, 2:], rtol=2e-3)
+    same_csv_rows(tmp_path, "STGNN", z, rtol=2e-3, cols=slice(2, None))
 
 
 def test_trainer_dict_of_test_sets_matches_reference_harness_run(tmp_path, monkeypatch):
@@ -434,47 +231,25 @@ def test_trainer_dict_of_test_sets_matches_reference_harness_run(tmp_path, monke
     test set per bearing ({'samples': {key: ...}, 'labels': {key: ...}}), max_ruls is a dict with the same keys, every key gets its
     own best-RMSE bookkeeping and its own "<int(key)>_results.csv/.pt".  Fixture: the reference's own harness on the same synthetic
     data (tests/golden/make_golden.py::case_trainer_phm2012_dict)."""
-    import io
-    import sys
-    from conftest import GOLDEN
-    sys.path.insert(0, GOLDEN)
-    from synth import synthetic_phm2012
-    from gnn_rul_benchmarking_amd import trainer as T
-    z = np.load(os.path.join(GOLDEN, "trainer_phm2012_c1_dict_reference_run.npz"))
+    z = gold("trainer_phm2012_c1_dict_reference_run")
     n_tests = [int(v) for v in z["n_tests"]]
-    (xtr, ytr), (xte, yte) = synthetic_phm2012(int(z["seed"]), int(z["n_train"]), sum(n_tests))
-    assert abs(xtr.astype(np.float64).sum() - float(z["x_train_checksum"])) < 1e-6
+    (xtr, ytr), (xte, yte) = K.synthetic_data(z, "PHM2012", n_test=sum(n_tests))
     keys = [float(k) for k in z["keys"]]
     max_ruls = {k: float(m) for k, m in zip(keys, z["max_ruls"])}
     cut = n_tests[0]
-    d = tmp_path / "data" / "PHM2012" / "Condition_1"
-    os.makedirs(d)
-    torch.save({"samples": xtr, "labels": ytr, "max_ruls": max_ruls}, d / "train.pt")
-    torch.save({"samples": {keys[0]: xte[:cut], keys[1]: xte[cut:]}, "labels": {keys[0]: yte[:cut], keys[1]: yte[cut:]},
-                "max_ruls": max_ruls}, d / "test.pt")
-    monkeypatch.chdir(tmp_path)
-    args = argparse.Namespace(save_dir=str(tmp_path / "logs"), experiment_description="exp", run_description="r",
-                              GNN_method="ST_GCN", data_path=str(tmp_path / "data"), dataset="PHM2012",
-                              dataset_id="Condition_1", bearing_id="Testing_bearing_1", num_runs=1, device="cuda:0")
-    tr = T.GNN_RUL_trainer(args)
-    tr.train_configs["num_epochs"] = int(z["epochs"])
-    tr.model_configs["dropout"] = 1e-12
-    per_epoch = {k: [] for k in keys}
-    orig = tr.calc_results_per_run
+    data = ({"samples": xtr, "labels": ytr, "max_ruls": max_ruls},
+            {"samples": {keys[0]: xte[:cut], keys[1]: xte[cut:]}, "labels": {keys[0]: yte[:cut], keys[1]: yte[cut:]}, "max_ruls": max_ruls})
 
-    def spy(run_id):
-        assert isinstance(tr.pred_labels, dict) and list(tr.pred_labels) == keys
-        for k in keys:
-            per_epoch[k].append(T._calc_metrics(tr.pred_labels[k], tr.true_labels[k], tr.max_ruls[k]))
-        return orig(run_id)
-    tr.calc_results_per_run = spy
-    tr.train()
+    def row(tr):
+        tr.model_configs["dropout"] = 1e-12
+    _, per_epoch = K.harness_run(tmp_path, monkeypatch, "ST_GCN", "PHM2012", "Condition_1", z, data=data, configure=row)
+    assert all(isinstance(e, dict) and list(e) == keys for e in per_epoch)
     run_dir = tmp_path / "logs" / "exp" / "r" / "ST_GCN_run_0"
     files = sorted(f for f in os.listdir(run_dir) if f.endswith(("results.csv", "results.pt")))
     assert "|".join(files) == str(z["files"])                       # 3_results.csv, 3_results.pt, 4_results.csv, 4_results.pt
     for k in keys:
         ik = int(k)
-        got, ref = np.asarray(per_epoch[k], np.float64), z[f"per_epoch:{ik}"]
+        got, ref = np.asarray([e[k] for e in per_epoch], np.float64), z[f"per_epoch:{ik}"]
         assert got.shape == ref.shape
         assert np.max(np.abs(got[:, 3] - ref[:, 3])) < 1e-3 * max_ruls[k]      # RMSE in cycles: 1e-3 of the normalised scale
         assert np.max(np.abs(got - ref) / np.abs(ref)) < 5e-4
@@ -491,134 +266,45 @@ def test_rgcnu_trainer_matches_reference_harness_run_on_cmapss(tmp_path, monkeyp
     reference's own harness, run on CPU by tests/golden/make_golden_rgcnu.py::case_trainer_cmapss (SCL's dropout switched off on both
     sides: torch's Bernoulli stream cannot be reproduced), vs this package's harness on the GPU.  The ragged last batch (250 % 100 =
     50 samples) exercises the adjacency-tiling quirk at a second batch size."""
-    import io
-    import sys
-    from conftest import GOLDEN
-    sys.path.insert(0, GOLDEN)
-    from synth import synthetic_cmapss
-    from gnn_rul_benchmarking_amd import trainer as T
     from gnn_rul_benchmarking_amd import rgcnu as R
-    z = np.load(os.path.join(GOLDEN, "rgcnu_trainer_cmapss_fd001_reference_run.npz"))
-    (xtr, ytr), (xte, yte) = synthetic_cmapss(int(z["seed"]), int(z["n_train"]), int(z["n_test"]))
-    assert abs(xtr.astype(np.float64).sum() - float(z["x_train_checksum"])) < 1e-6
-    d = tmp_path / "data" / "CMAPSS" / "FD001"
-    os.makedirs(d)
-    torch.save({"samples": xtr, "labels": ytr, "max_ruls": 125}, d / "train.pt")
-    torch.save({"samples": xte, "labels": yte, "max_ruls": 125}, d / "test.pt")
-    monkeypatch.chdir(tmp_path)
+    z = gold("rgcnu_trainer_cmapss_fd001_reference_run")
     monkeypatch.setattr(R, "SCL_DROPOUT", 0.0)
-    args = argparse.Namespace(save_dir=str(tmp_path / "logs"), experiment_description="exp", run_description="r",
-                              GNN_method="RGCNU", data_path=str(tmp_path / "data"), dataset="CMAPSS",
-                              dataset_id="FD001", bearing_id="Testing_bearing_1", num_runs=1, device="cuda:0")
-    tr = T.GNN_RUL_trainer(args)
-    tr.train_configs["num_epochs"] = int(z["epochs"])
-    assert tr.model_configs == dict(num_nodes=14, time_length=50, hidden_dim=32, encoder_hidden_dim=32, kernel_size=3, alpha=1)
-    assert tr.train_configs["batch_size"] == 100 and tr.train_configs["learning_rate"] == 1e-3
-    per_epoch = []
-    orig = tr.calc_results_per_run
 
-    def spy(run_id):
-        per_epoch.append(T._calc_metrics(tr.pred_labels, tr.true_labels, tr.max_ruls))
-        return orig(run_id)
-    tr.calc_results_per_run = spy
-    tr.train()
-    got, ref = np.asarray(per_epoch, np.float64), z["per_epoch"]
-    print("RGCNU harness per-epoch got/ref:\n", got, "\n", ref)
-    assert got.shape == ref.shape == (3, 4)
-    assert np.max(np.abs(got[:, 2:] - ref[:, 2:]) / np.abs(ref[:, 2:])) < 2e-3      # MAE, RMSE (in RUL cycles), relative
-    assert np.max(np.abs(got[:, 3] - ref[:, 3])) / 125.0 < 1e-3                     # RMSE within 1e-3 on the normalised scale
-    csv = pd.read_csv(tmp_path / "logs" / "exp" / "r" / "RGCNU_run_0" / "results.csv")
-    ref_csv = pd.read_csv(io.StringIO(str(z["csv_text"])))
-    assert list(csv.columns) == list(ref_csv.columns) and len(csv) == len(ref_csv)
-    assert np.allclose(csv.iloc[1:].to_numpy()[:, 2:], ref_csv.iloc[1:].to_numpy()[:, 2:], rtol=2e-3)
+    def row(tr):
+        assert tr.model_configs == dict(num_nodes=14, time_length=50, hidden_dim=32, encoder_hidden_dim=32, kernel_size=3, alpha=1)
+        assert tr.train_configs["batch_size"] == 100 and tr.train_configs["learning_rate"] == 1e-3
+    _, per_epoch = K.harness_run(tmp_path, monkeypatch, "RGCNU", "CMAPSS", "FD001", z, configure=row)
+    K.assert_harness("RGCNU", per_epoch, None, z, dict(CMAPSS, rel=2e-3))         # MAE, RMSE relative 2e-3; RMSE within 1e-3 on the normalised scale
+    same_csv_rows(tmp_path, "RGCNU", z, rtol=2e-3, cols=slice(2, None))
 
 
 def test_stnet_trainer_matches_reference_harness_run_on_phm2012(tmp_path, monkeypatch):
     """--GNN_method STNet on PHM2012 Condition_1 as the reference wires it (configs/hparams.py:222,236: 20 patches of 128 points, STFT
     9 x 9, ChebNets [300, 200, 100], batch 100, lr 1e-2, wd 1e-2): the reference's own harness, run on CPU by
     tests/golden/make_golden_stnet.py::case_trainer_phm2012, vs this package's harness on the GPU (measured agreement: RMSE to 6e-7)."""
-    import io
-    import sys
-    from conftest import GOLDEN
-    sys.path.insert(0, GOLDEN)
-    from synth import synthetic_phm2012
-    from gnn_rul_benchmarking_amd import trainer as T
-    z = np.load(os.path.join(GOLDEN, "stnet_trainer_phm2012_c1_reference_run.npz"))
-    (xtr, ytr), (xte, yte) = synthetic_phm2012(int(z["seed"]), int(z["n_train"]), int(z["n_test"]))
-    assert abs(xtr.astype(np.float64).sum() - float(z["x_train_checksum"])) < 1e-6
-    d = tmp_path / "data" / "PHM2012" / "Condition_1"
-    os.makedirs(d)
-    torch.save({"samples": xtr, "labels": ytr, "max_ruls": 1.0}, d / "train.pt")
-    torch.save({"samples": xte, "labels": yte, "max_ruls": 1.0}, d / "test.pt")
-    monkeypatch.chdir(tmp_path)
-    args = argparse.Namespace(save_dir=str(tmp_path / "logs"), experiment_description="exp", run_description="r",
-                              GNN_method="STNet", data_path=str(tmp_path / "data"), dataset="PHM2012",
-                              dataset_id="Condition_1", bearing_id="Testing_bearing_1", num_runs=1, device="cuda:0")
-    tr = T.GNN_RUL_trainer(args)
-    tr.train_configs["num_epochs"] = int(z["epochs"])
-    assert tr.model_configs == dict(num_patch=20, patch_size=128, num_nodes=9, nperseg=16, input_dim=9, Cheb_layers=[300, 200, 100],
-                                    lstm_hidden_dim=10, autoencoder_hidden_dim=50)
-    assert tr.train_configs == {'num_epochs': 3, 'batch_size': 100, 'weight_decay': 1e-2, 'learning_rate': 1e-2}
-    per_epoch = []
-    orig = tr.calc_results_per_run
+    z = gold("stnet_trainer_phm2012_c1_reference_run")
 
-    def spy(run_id):
-        per_epoch.append(T._calc_metrics(tr.pred_labels, tr.true_labels, tr.max_ruls))
-        return orig(run_id)
-    tr.calc_results_per_run = spy
-    tr.train()
-    got, ref = np.asarray(per_epoch, np.float64), z["per_epoch"]
-    print("STNet harness per-epoch got/ref:\n", got, "\n", ref)
-    assert got.shape == ref.shape == (3, 4)
-    assert np.max(np.abs(got[:, 3] - ref[:, 3])) < 1e-4                  # RMSE on the normalised scale (north star: 1e-3)
-    assert np.max(np.abs(got[:, 2:] - ref[:, 2:]) / np.abs(ref[:, 2:])) < 1e-4
-    csv = pd.read_csv(tmp_path / "logs" / "exp" / "r" / "STNet_run_0" / "results.csv")
-    ref_csv = pd.read_csv(io.StringIO(str(z["csv_text"])))
-    assert list(csv.columns) == list(ref_csv.columns) and len(csv) == len(ref_csv)
+    def row(tr):
+        assert tr.model_configs == dict(num_patch=20, patch_size=128, num_nodes=9, nperseg=16, input_dim=9, Cheb_layers=[300, 200, 100],
+                                        lstm_hidden_dim=10, autoencoder_hidden_dim=50)
+        assert tr.train_configs == {'num_epochs': 3, 'batch_size': 100, 'weight_decay': 1e-2, 'learning_rate': 1e-2}
+    _, per_epoch = K.harness_run(tmp_path, monkeypatch, "STNet", "PHM2012", "Condition_1", z, configure=row)
+    K.assert_harness("STNet", per_epoch, None, z, dict(PHM2012, rmse_abs=1e-4, rel=1e-4))      # RMSE on the normalised scale (north star: 1e-3)
+    same_csv_rows(tmp_path, "STNet", z)
 
 
 def test_sagcn_trainer_matches_reference_harness_run_on_phm2012(tmp_path, monkeypatch):
     """--GNN_method SAGCN on PHM2012 Condition_1 as the reference wires it (configs/hparams.py:221,235: 160 patches of 16 points,
     hidden 100 / 100, batch 100, lr 1e-4, wd 1e-4 -- patches of 16 points: the reference's unstable argsort agrees with the stable order): the reference's own harness, run on CPU by
     tests/golden/make_golden_sagcn.py::case_trainer_phm2012, vs this package's harness on the GPU ."""
-    import io
-    import sys
-    from conftest import GOLDEN
-    sys.path.insert(0, GOLDEN)
-    from synth import synthetic_phm2012
-    from gnn_rul_benchmarking_amd import trainer as T
-    z = np.load(os.path.join(GOLDEN, "sagcn_trainer_phm2012_c1_reference_run.npz"))
-    (xtr, ytr), (xte, yte) = synthetic_phm2012(int(z["seed"]), int(z["n_train"]), int(z["n_test"]))
-    assert abs(xtr.astype(np.float64).sum() - float(z["x_train_checksum"])) < 1e-6
-    d = tmp_path / "data" / "PHM2012" / "Condition_1"
-    os.makedirs(d)
-    torch.save({"samples": xtr, "labels": ytr, "max_ruls": 1.0}, d / "train.pt")
-    torch.save({"samples": xte, "labels": yte, "max_ruls": 1.0}, d / "test.pt")
-    monkeypatch.chdir(tmp_path)
-    args = argparse.Namespace(save_dir=str(tmp_path / "logs"), experiment_description="exp", run_description="r",
-                              GNN_method="SAGCN", data_path=str(tmp_path / "data"), dataset="PHM2012",
-                              dataset_id="Condition_1", bearing_id="Testing_bearing_1", num_runs=1, device="cuda:0")
-    tr = T.GNN_RUL_trainer(args)
-    tr.train_configs["num_epochs"] = int(z["epochs"])
-    assert tr.model_configs == dict(num_patch=160, patch_size=16, gcn_hidden_dim=100, attention_hidden_dim=100)
-    assert tr.train_configs == {'num_epochs': 3, 'batch_size': 100, 'weight_decay': 1e-4, 'learning_rate': 1e-4}
-    per_epoch = []
-    orig = tr.calc_results_per_run
+    z = gold("sagcn_trainer_phm2012_c1_reference_run")
 
-    def spy(run_id):
-        per_epoch.append(T._calc_metrics(tr.pred_labels, tr.true_labels, tr.max_ruls))
-        return orig(run_id)
-    tr.calc_results_per_run = spy
-    tr.train()
-    got, ref = np.asarray(per_epoch, np.float64), z["per_epoch"]
-    print("SAGCN harness per-epoch got/ref:\n", got, "\n", ref)
-    assert got.shape == ref.shape == (3, 4)
-    assert np.max(np.abs(got[:, 3] - ref[:, 3])) < 1e-4                  # RMSE on the normalised scale (north star: 1e-3)
-    assert np.max(np.abs(got[:, 2:] - ref[:, 2:]) / np.abs(ref[:, 2:])) < 1e-4
-    csv = pd.read_csv(tmp_path / "logs" / "exp" / "r" / "SAGCN_run_0" / "results.csv")
-    ref_csv = pd.read_csv(io.StringIO(str(z["csv_text"])))
-    assert list(csv.columns) == list(ref_csv.columns) and len(csv) == len(ref_csv)
-
+    def row(tr):
+        assert tr.model_configs == dict(num_patch=160, patch_size=16, gcn_hidden_dim=100, attention_hidden_dim=100)
+        assert tr.train_configs == {'num_epochs': 3, 'batch_size': 100, 'weight_decay': 1e-4, 'learning_rate': 1e-4}
+    _, per_epoch = K.harness_run(tmp_path, monkeypatch, "SAGCN", "PHM2012", "Condition_1", z, configure=row)
+    K.assert_harness("SAGCN", per_epoch, None, z, dict(PHM2012, rmse_abs=1e-4, rel=1e-4))      # RMSE on the normalised scale (north star: 1e-3)
+    same_csv_rows(tmp_path, "SAGCN", z)
 
 
 def test_stagnn_trainer_matches_reference_harness_run_on_cmapss(tmp_path, monkeypatch):
@@ -626,41 +312,14 @@ def test_stagnn_trainer_matches_reference_harness_run_on_cmapss(tmp_path, monkey
     100, lr 1e-3, wd 1e-4, shuffling DataLoader): the reference's own harness, run on CPU by
     tests/golden/make_golden_stagnn.py::case_trainer_cmapss, vs this package's harness on the GPU -- train-mode BatchNorm statistics in
     the steps, running statistics in the per-epoch test passes, a ragged last batch (300 % 100 == 0 here; the test set's 80 is)."""
-    import io
-    import sys
-    from conftest import GOLDEN
-    sys.path.insert(0, GOLDEN)
-    from synth import synthetic_cmapss
-    from gnn_rul_benchmarking_amd import trainer as T
-    z = np.load(os.path.join(GOLDEN, "stagnn_trainer_cmapss_fd002_reference_run.npz"))
-    fd = str(z["fd"])
-    (xtr, ytr), (xte, yte) = synthetic_cmapss(int(z["seed"]), int(z["n_train"]), int(z["n_test"]))
-    assert abs(xtr.astype(np.float64).sum() - float(z["x_train_checksum"])) < 1e-6
-    d = tmp_path / "data" / "CMAPSS" / fd
-    os.makedirs(d)
-    torch.save({"samples": torch.from_numpy(xtr), "labels": torch.from_numpy(ytr), "max_ruls": 125.0}, d / "train.pt")
-    torch.save({"samples": torch.from_numpy(xte), "labels": torch.from_numpy(yte), "max_ruls": 125.0}, d / "test.pt")
-    monkeypatch.chdir(tmp_path)
-    args = argparse.Namespace(save_dir=str(tmp_path / "logs"), experiment_description="exp", run_description="r",
-                              GNN_method="STAGNN", data_path=str(tmp_path / "data"), dataset="CMAPSS",
-                              dataset_id=fd, bearing_id=None, num_runs=1, device="cuda:0")
-    tr = T.GNN_RUL_trainer(args)
-    tr.train_configs["num_epochs"] = int(z["epochs"])
-    assert tr.model_configs == dict(num_nodes=14, time_length=50, hidden_dim=16, output_dim=10, num_heads=3, threshold=0)
-    assert tr.train_configs == {'num_epochs': 3, 'batch_size': 100, 'weight_decay': 1e-4, 'learning_rate': 1e-3}
-    per_epoch = []
-    orig = tr.calc_results_per_run
+    z = gold("stagnn_trainer_cmapss_fd002_reference_run")
+    (xtr, ytr), (xte, yte) = K.synthetic_data(z, "CMAPSS")
+    data = ({"samples": torch.from_numpy(xtr), "labels": torch.from_numpy(ytr), "max_ruls": 125.0},         # tensors on disk, as the fixture's maker wrote them
+            {"samples": torch.from_numpy(xte), "labels": torch.from_numpy(yte), "max_ruls": 125.0})
 
-    def spy(run_id):
-        per_epoch.append(T._calc_metrics(tr.pred_labels, tr.true_labels, tr.max_ruls))
-        return orig(run_id)
-    tr.calc_results_per_run = spy
-    tr.train()
-    got, ref = np.asarray(per_epoch, np.float64), z["per_epoch"]
-    print("STAGNN harness per-epoch got/ref:\n", got, "\n", ref)
-    assert got.shape == ref.shape == (3, 4)
-    assert np.max(np.abs(got[:, 3] - ref[:, 3]) / 125.0) < 1e-3          # RMSE on the normalised scale (north star: 1e-3)
-    assert np.max(np.abs(got[:, 2:] - ref[:, 2:]) / np.abs(ref[:, 2:])) < 2e-3
-    csv = pd.read_csv(tmp_path / "logs" / "exp" / "r" / "STAGNN_run_0" / "results.csv")
-    ref_csv = pd.read_csv(io.StringIO(str(z["csv_text"])))
-    assert list(csv.columns) == list(ref_csv.columns) and len(csv) == len(ref_csv)
+    def row(tr):
+        assert tr.model_configs == dict(num_nodes=14, time_length=50, hidden_dim=16, output_dim=10, num_heads=3, threshold=0)
+        assert tr.train_configs == {'num_epochs': 3, 'batch_size': 100, 'weight_decay': 1e-4, 'learning_rate': 1e-3}
+    _, per_epoch = K.harness_run(tmp_path, monkeypatch, "STAGNN", "CMAPSS", str(z["fd"]), z, data=data, configure=row)
+    K.assert_harness("STAGNN", per_epoch, None, z, dict(CMAPSS, rel=2e-3))        # RMSE on the normalised scale (north star: 1e-3)
+    same_csv_rows(tmp_path, "STAGNN", z)
