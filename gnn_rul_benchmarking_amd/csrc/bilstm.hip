@@ -21,6 +21,10 @@ namespace rulgnn {
 
 namespace {
 
+// Most layers of one shape a grouped call runs side by side (bilstm_forward_group / bilstm_backward_group): the groups' pointers travel
+// by value in the kernel arguments -- 8 x 7 pointers are 448 bytes.
+constexpr int LSTM_MAX_GROUPS = 8;
+
 struct LstmGeom {
     int64_t T;                  // time steps (batch_size * num_node)
     int Bq, I, H, H4;           // sequences, input width, hidden width
@@ -148,8 +152,9 @@ __device__ __forceinline__ float quad_perm(float v) {
 // instruction count: FULL (H == HMAX, HAGCN's layers) has no lane masks, every lane of a quad stores (its gate and one of c, h,
 // h entering, tanh c -- the last saves the BPTT an exp and a reciprocal per step), ring slots and LDS halves are immediates.
 // ---------------------------------------------------------------------------------------------------
-template <int HMAX, bool FULL, int KLIVE = HMAX>
-__global__ __launch_bounds__(4 * HMAX) void lstm_forward_kernel(LstmGeom g, const float* __restrict__ gi, const float* __restrict__ w_hh0,
+// The body is shared by the single-layer kernel and the grouped one (below): they differ only in where the pointers come from.
+template <int HMAX, bool FULL, int KLIVE>
+__device__ __forceinline__ void lstm_forward_body(const LstmGeom& g, const float* __restrict__ gi, const float* __restrict__ w_hh0,
                                     const float* __restrict__ w_hh1, const float* __restrict__ b_ih0, const float* __restrict__ b_hh0,
                                     const float* __restrict__ b_ih1, const float* __restrict__ b_hh1, float* __restrict__ gates,
                                     float* __restrict__ cseq, float* __restrict__ hseq, float* __restrict__ hprev, float* __restrict__ tseq) {
@@ -226,8 +231,48 @@ __global__ __launch_bounds__(4 * HMAX) void lstm_forward_kernel(LstmGeom g, cons
     }
 }
 
+template <int HMAX, bool FULL, int KLIVE = HMAX>
+__global__ __launch_bounds__(4 * HMAX) void lstm_forward_kernel(LstmGeom g, const float* __restrict__ gi, const float* __restrict__ w_hh0,
+                                    const float* __restrict__ w_hh1, const float* __restrict__ b_ih0, const float* __restrict__ b_hh0,
+                                    const float* __restrict__ b_ih1, const float* __restrict__ b_hh1, float* __restrict__ gates,
+                                    float* __restrict__ cseq, float* __restrict__ hseq, float* __restrict__ hprev, float* __restrict__ tseq) {
+    lstm_forward_body<HMAX, FULL, KLIVE>(g, gi, w_hh0, w_hh1, b_ih0, b_hh0, b_ih1, b_hh1, gates, cseq, hseq, hprev, tseq);
+}
+
+// Grouped form: workgroup = (group, direction, sequence), grid (2 * num_seq, groups).  The groups are independent layers of ONE shape
+// (the same layer of several training runs): each has its own weights and its own workspace, laid out by lstm_geometry like a single
+// layer's.  The table travels by value in the kernel arguments and blockIdx.y is wavefront-uniform: a group's pointers are scalar loads
+// from the argument segment.  Workgroups never wait for one another, so any number of them may be queued behind the resident ones.
+struct LstmGroupFwd {
+    const float *w_hh[2], *b_ih[2], *b_hh[2];
+    float* ws;
+};
+struct LstmGroupFwdTable {
+    LstmGroupFwd grp[LSTM_MAX_GROUPS];
+};
+template <int HMAX, bool FULL, int KLIVE = HMAX>
+__global__ __launch_bounds__(4 * HMAX) void lstm_forward_group_kernel(LstmGeom g, LstmGroupFwdTable tab) {
+    const LstmGroupFwd& e = tab.grp[blockIdx.y];
+    float* ws = e.ws;
+    lstm_forward_body<HMAX, FULL, KLIVE>(g, ws + g.o_gi, e.w_hh[0], e.w_hh[1], e.b_ih[0], e.b_hh[0], e.b_ih[1], e.b_hh[1], ws + g.o_gates,
+                                         ws + g.o_c, ws + g.o_h, ws + g.o_hprev, ws + g.o_tc);
+}
+
 // out[q][t][:] = h_fwd + h_bwd   (Model.py:59-61)
 __global__ void lstm_sum_kernel(LstmGeom g, const float* __restrict__ hseq, float* __restrict__ out) {
+    const int64_t n = g.rows * g.H;
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x)
+        out[e] = hseq[e] + hseq[n + e];
+}
+
+// the same for every group (blockIdx.y)
+struct LstmGroupSumTable {
+    const float* hseq[LSTM_MAX_GROUPS];
+    float* out[LSTM_MAX_GROUPS];
+};
+__global__ void lstm_sum_group_kernel(LstmGeom g, LstmGroupSumTable tab) {
+    const float* __restrict__ hseq = tab.hseq[blockIdx.y];
+    float* __restrict__ out = tab.out[blockIdx.y];
     const int64_t n = g.rows * g.H;
     for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n; e += (int64_t)gridDim.x * blockDim.x)
         out[e] = hseq[e] + hseq[n + e];
@@ -244,8 +289,8 @@ __global__ void lstm_sum_kernel(LstmGeom g, const float* __restrict__ hseq, floa
 //   k_c = o (1 - tc^2);   k_p = A (E (m - E) + b) with (A, E, m, b) = (g, i, 1, 0), (c entering, f, 1, 0), (i, g, 0, 1), (tc, o, 1, 0):
 // the same three instructions in every row, A and E read through per-lane LDS offsets.
 // ---------------------------------------------------------------------------------------------------
-template <int HMAX, bool FULL, int KLIVE = HMAX>
-__global__ __launch_bounds__(4 * HMAX) void lstm_backward_kernel(LstmGeom g, const float* __restrict__ w_hh0, const float* __restrict__ w_hh1,
+template <int HMAX, bool FULL, int KLIVE>
+__device__ __forceinline__ void lstm_backward_body(const LstmGeom& g, const float* __restrict__ w_hh0, const float* __restrict__ w_hh1,
                                      const float* __restrict__ gates, const float* __restrict__ cseq, const float* __restrict__ tseq,
                                      const float* __restrict__ dout, float* __restrict__ dgates) {
     constexpr int ROW = 4 * HMAX;                                              // floats per ring row
@@ -342,6 +387,28 @@ __global__ __launch_bounds__(4 * HMAX) void lstm_backward_kernel(LstmGeom g, con
     }
 }
 
+template <int HMAX, bool FULL, int KLIVE = HMAX>
+__global__ __launch_bounds__(4 * HMAX) void lstm_backward_kernel(LstmGeom g, const float* __restrict__ w_hh0, const float* __restrict__ w_hh1,
+                                     const float* __restrict__ gates, const float* __restrict__ cseq, const float* __restrict__ tseq,
+                                     const float* __restrict__ dout, float* __restrict__ dgates) {
+    lstm_backward_body<HMAX, FULL, KLIVE>(g, w_hh0, w_hh1, gates, cseq, tseq, dout, dgates);
+}
+
+// grouped form (see lstm_forward_group_kernel): workgroup = (group, direction, sequence)
+struct LstmGroupBwd {
+    const float *w_hh[2], *dout;
+    float* ws;
+};
+struct LstmGroupBwdTable {
+    LstmGroupBwd grp[LSTM_MAX_GROUPS];
+};
+template <int HMAX, bool FULL, int KLIVE = HMAX>
+__global__ __launch_bounds__(4 * HMAX) void lstm_backward_group_kernel(LstmGeom g, LstmGroupBwdTable tab) {
+    const LstmGroupBwd& e = tab.grp[blockIdx.y];
+    float* ws = e.ws;
+    lstm_backward_body<HMAX, FULL, KLIVE>(g, e.w_hh[0], e.w_hh[1], ws + g.o_gates, ws + g.o_c, ws + g.o_tc, e.dout, ws + g.o_dgates);
+}
+
 // db_ih = db_hh: copy
 __global__ void lstm_copy_kernel(const float* __restrict__ a, float* __restrict__ b, int n) {
     const int e = blockIdx.x * blockDim.x + threadIdx.x;
@@ -383,41 +450,38 @@ int bilstm_forward(const rulgnn_bilstm_shape* s, const rulgnn_bilstm_args* a, hi
     return launch_checked(lstm_copy_kernel, dim3((unsigned)((g.rows * g.H + 255) / 256)), dim3(256), 0, st, (const float*)(ws + g.o_h), a->out, (int)(g.rows * g.H));
 }
 
-int bilstm_backward(const rulgnn_bilstm_shape* s, const rulgnn_bilstm_args* a, hipStream_t st, int ndir) {
-    LstmGeom g;
-    RULGNN_TRY(lstm_geometry(s, &g));
-    if (a->workspace_bytes < (size_t)g.total * sizeof(float)) return RULGNN_EWORKSPACE;
+namespace {
+
+// what follows a layer's BPTT on `st`: the ones vector of the bias sums, then the data gradient -- the layer below waits for nothing
+// else.  dx (+)= dG W_ih
+int lstm_data_gradient(const LstmGeom& g, const rulgnn_bilstm_args* a, int ndir, hipStream_t st) {
     float* ws = static_cast<float*>(a->workspace);
-    const int R = (int)g.rows, H = g.H, H4 = g.H4, I = g.I;
-    const int threads = (H4 + 63) & ~63;
-    if (ndir != 1 && ndir != 2) return RULGNN_EINVAL;
-    const int d1 = ndir == 2 ? 1 : 0;
-    auto bwd = [&](auto kernel) {
-        return launch_checked(kernel, dim3(ndir * g.Bq), dim3(threads), 0, st, g, a->w_hh[0], a->w_hh[d1], (const float*)(ws + g.o_gates),
-                              (const float*)(ws + g.o_c), (const float*)(ws + g.o_tc), a->dout, ws + g.o_dgates);
-    };
-    if (H == 60) RULGNN_TRY(bwd(lstm_backward_kernel<64, true, 60>));
-    else if (H <= 64) RULGNN_TRY(bwd(lstm_backward_kernel<64, true>));
-    else if (H == 120) RULGNN_TRY(bwd(lstm_backward_kernel<128, true, 120>));
-    else RULGNN_TRY(bwd(lstm_backward_kernel<128, true>));
-    float* one = ws + g.o_one;
-    float* split = ws + g.o_split;
-    RULGNN_TRY(fill_f32(one, 1, 1.f, st));
-    // The data gradient first: the layer below waits for nothing else.  dx (+)= dG W_ih
+    RULGNN_TRY(fill_f32(ws + g.o_one, 1, 1.f, st));
     if (a->dx)
         for (int d = 0; d < ndir; ++d)
-            RULGNN_TRY(sgemm(ws + g.o_dgates + (int64_t)d * g.rows * H4, H4, 1, a->w_ih[d], 1, I, a->dx, I, R, I, H4, d == 1, st));
-    // The parameter gradients feed nothing in this call: on the caller's second stream (args->aux_stream) they run beside what the caller
-    // enqueues on `st` next -- in a stack of layers the BPTT of the layer below, a persistent recurrence on 2 * num_seq of the CUs.
-    // NOT joined here: the caller joins before it reads them (include/rulgnn.h).
-    hipStream_t wst = st;
-    if (a->aux_stream) {
-        wst = static_cast<hipStream_t>(a->aux_stream);
+            RULGNN_TRY(sgemm(ws + g.o_dgates + (int64_t)d * g.rows * g.H4, g.H4, 1, a->w_ih[d], 1, g.I, a->dx, g.I, (int)g.rows, g.I, g.H4, d == 1, st));
+    return RULGNN_OK;
+}
+
+// The parameter gradients feed nothing in the call: on the caller's second stream (args->aux_stream) they run beside what the caller
+// enqueues on `st` next -- in a stack of layers the BPTT of the layer below, a persistent recurrence on 2 * num_seq of the CUs.
+// NOT joined: the caller joins before it reads them (include/rulgnn.h).  `*wst` becomes the stream that carries them.
+int lstm_fork_weight_stream(void* aux_stream, hipStream_t st, hipStream_t* wst) {
+    *wst = st;
+    if (aux_stream) {
+        *wst = static_cast<hipStream_t>(aux_stream);
         hipEvent_t ev = aux_pooled_event();
-        if (!ev || hipEventRecord(ev, st) != hipSuccess || hipStreamWaitEvent(wst, ev, 0) != hipSuccess) return RULGNN_EHIP;
+        if (!ev || hipEventRecord(ev, st) != hipSuccess || hipStreamWaitEvent(*wst, ev, 0) != hipSuccess) return RULGNN_EHIP;
     }
-    // dW_ih = dG^T x ; dW_hh = dG^T h_prev ; db_ih = db_hh = column sums of dG -- of both directions: ONE split-K launch + ONE reduction
-    // (they were seven launches per direction, 5-8 us each; behind the first layer's BPTT nothing is left to hide them under)
+    return RULGNN_OK;
+}
+
+// dW_ih = dG^T x ; dW_hh = dG^T h_prev ; db_ih = db_hh = column sums of dG -- of both directions: ONE split-K launch + ONE reduction
+// (they were seven launches per direction, 5-8 us each; behind the first layer's BPTT nothing is left to hide them under)
+int lstm_weight_gradients(const LstmGeom& g, const rulgnn_bilstm_args* a, int ndir, hipStream_t wst) {
+    float* ws = static_cast<float*>(a->workspace);
+    const float* one = ws + g.o_one;
+    const int R = (int)g.rows, H = g.H, H4 = g.H4, I = g.I;
     SplitKJob jobs[8];
     int nj = 0;
     for (int d = 0; d < ndir; ++d) {
@@ -427,10 +491,100 @@ int bilstm_backward(const rulgnn_bilstm_shape* s, const rulgnn_bilstm_args* a, h
         jobs[nj++] = SplitKJob{one, 0, 0, dg, 1, H4, a->db_ih[d], H4, 1, H4, R};
         jobs[nj++] = SplitKJob{one, 0, 0, dg, 1, H4, a->db_hh[d], H4, 1, H4, R};
     }
-    if (R > 0) RULGNN_TRY(sgemm_splitk_batch(jobs, nj, split, (size_t)g.o_split_floats, wst));
+    if (R > 0) RULGNN_TRY(sgemm_splitk_batch(jobs, nj, ws + g.o_split, (size_t)g.o_split_floats, wst));
     else
         for (int j = 0; j < nj; ++j)
             if (hipMemsetAsync(jobs[j].C, 0, sizeof(float) * (size_t)jobs[j].M * jobs[j].N, wst) != hipSuccess) return RULGNN_EHIP;
+    return RULGNN_OK;
+}
+
+}  // namespace
+
+int bilstm_backward(const rulgnn_bilstm_shape* s, const rulgnn_bilstm_args* a, hipStream_t st, int ndir) {
+    LstmGeom g;
+    RULGNN_TRY(lstm_geometry(s, &g));
+    if (a->workspace_bytes < (size_t)g.total * sizeof(float)) return RULGNN_EWORKSPACE;
+    float* ws = static_cast<float*>(a->workspace);
+    const int threads = (g.H4 + 63) & ~63;
+    if (ndir != 1 && ndir != 2) return RULGNN_EINVAL;
+    const int d1 = ndir == 2 ? 1 : 0;
+    auto bwd = [&](auto kernel) {
+        return launch_checked(kernel, dim3(ndir * g.Bq), dim3(threads), 0, st, g, a->w_hh[0], a->w_hh[d1], (const float*)(ws + g.o_gates),
+                              (const float*)(ws + g.o_c), (const float*)(ws + g.o_tc), a->dout, ws + g.o_dgates);
+    };
+    if (g.H == 60) RULGNN_TRY(bwd(lstm_backward_kernel<64, true, 60>));
+    else if (g.H <= 64) RULGNN_TRY(bwd(lstm_backward_kernel<64, true>));
+    else if (g.H == 120) RULGNN_TRY(bwd(lstm_backward_kernel<128, true, 120>));
+    else RULGNN_TRY(bwd(lstm_backward_kernel<128, true>));
+    RULGNN_TRY(lstm_data_gradient(g, a, ndir, st));
+    hipStream_t wst;
+    RULGNN_TRY(lstm_fork_weight_stream(a->aux_stream, st, &wst));
+    return lstm_weight_gradients(g, a, ndir, wst);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// Grouped calls: `n` layers of one shape -- the same layer of n independent training runs -- advance through their recurrences side
+// by side in ONE launch, workgroup = (group, direction, sequence).  Everything else is what the single call does, group by group and
+// with the same arguments, so a group's results are the single call's bit for bit: the projections and dx on the shared SGEMM, the
+// eight parameter-gradient products as one split-K batch per group in that group's own scratch (a job's slice count depends on its
+// own M, N, K only).  Every group is checked before the first launch.
+// ---------------------------------------------------------------------------------------------------
+int bilstm_max_groups() { return LSTM_MAX_GROUPS; }
+
+namespace {
+
+int lstm_group_geometry(const rulgnn_bilstm_shape* s, const rulgnn_bilstm_args* grp, int n, LstmGeom* g) {
+    if (!grp || n < 1) return RULGNN_EINVAL;
+    if (n > LSTM_MAX_GROUPS) return RULGNN_EUNSUPPORTED;
+    RULGNN_TRY(lstm_geometry(s, g));
+    for (int i = 0; i < n; ++i) {
+        if (!grp[i].workspace) return RULGNN_EINVAL;
+        if (grp[i].workspace_bytes < (size_t)g->total * sizeof(float)) return RULGNN_EWORKSPACE;
+    }
+    return RULGNN_OK;
+}
+
+}  // namespace
+
+int bilstm_forward_group(const rulgnn_bilstm_shape* s, const rulgnn_bilstm_args* grp, int n, hipStream_t st) {
+    LstmGeom g;
+    RULGNN_TRY(lstm_group_geometry(s, grp, n, &g));
+    LstmGroupFwdTable tab{};
+    LstmGroupSumTable sums{};
+    for (int i = 0; i < n; ++i) {
+        const rulgnn_bilstm_args* a = &grp[i];
+        float* ws = static_cast<float*>(a->workspace);
+        for (int d = 0; d < 2; ++d)
+            RULGNN_TRY(sgemm(a->x, g.I, 1, a->w_ih[d], g.I, 1, ws + g.o_gi + (int64_t)d * g.rows * g.H4, g.H4, (int)g.rows, g.H4, g.I, false, st));
+        tab.grp[i] = LstmGroupFwd{{a->w_hh[0], a->w_hh[1]}, {a->b_ih[0], a->b_ih[1]}, {a->b_hh[0], a->b_hh[1]}, ws};
+        sums.hseq[i] = ws + g.o_h;
+        sums.out[i] = a->out;
+    }
+    const dim3 grid(2 * g.Bq, n), block((g.H4 + 63) & ~63);
+    if (g.H == 60) RULGNN_TRY(launch_checked(lstm_forward_group_kernel<64, true, 60>, grid, block, 0, st, g, tab));
+    else if (g.H <= 64) RULGNN_TRY(launch_checked(lstm_forward_group_kernel<64, true>, grid, block, 0, st, g, tab));
+    else if (g.H == 120) RULGNN_TRY(launch_checked(lstm_forward_group_kernel<128, true, 120>, grid, block, 0, st, g, tab));
+    else RULGNN_TRY(launch_checked(lstm_forward_group_kernel<128, true>, grid, block, 0, st, g, tab));
+    return launch_checked(lstm_sum_group_kernel, dim3(1024, n), dim3(256), 0, st, g, sums);
+}
+
+int bilstm_backward_group(const rulgnn_bilstm_shape* s, const rulgnn_bilstm_args* grp, int n, hipStream_t st) {
+    LstmGeom g;
+    RULGNN_TRY(lstm_group_geometry(s, grp, n, &g));
+    for (int i = 1; i < n; ++i)
+        if (grp[i].aux_stream != grp[0].aux_stream) return RULGNN_EINVAL;       // one side stream carries every group's parameter gradients
+    LstmGroupBwdTable tab{};
+    for (int i = 0; i < n; ++i)
+        tab.grp[i] = LstmGroupBwd{{grp[i].w_hh[0], grp[i].w_hh[1]}, grp[i].dout, static_cast<float*>(grp[i].workspace)};
+    const dim3 grid(2 * g.Bq, n), block((g.H4 + 63) & ~63);
+    if (g.H == 60) RULGNN_TRY(launch_checked(lstm_backward_group_kernel<64, true, 60>, grid, block, 0, st, g, tab));
+    else if (g.H <= 64) RULGNN_TRY(launch_checked(lstm_backward_group_kernel<64, true>, grid, block, 0, st, g, tab));
+    else if (g.H == 120) RULGNN_TRY(launch_checked(lstm_backward_group_kernel<128, true, 120>, grid, block, 0, st, g, tab));
+    else RULGNN_TRY(launch_checked(lstm_backward_group_kernel<128, true>, grid, block, 0, st, g, tab));
+    for (int i = 0; i < n; ++i) RULGNN_TRY(lstm_data_gradient(g, &grp[i], 2, st));
+    hipStream_t wst;
+    RULGNN_TRY(lstm_fork_weight_stream(grp[0].aux_stream, st, &wst));
+    for (int i = 0; i < n; ++i) RULGNN_TRY(lstm_weight_gradients(g, &grp[i], 2, wst));
     return RULGNN_OK;
 }
 

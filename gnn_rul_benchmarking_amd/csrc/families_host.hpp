@@ -226,6 +226,10 @@ size_t hagcn_workspace_bytes(const rulgnn_hagcn_shape* s);
 size_t bilstm_workspace_bytes(const rulgnn_bilstm_shape* s);
 [[nodiscard]] int bilstm_forward(const rulgnn_bilstm_shape* s, const rulgnn_bilstm_args* a, hipStream_t stream, int ndir = 2);
 [[nodiscard]] int bilstm_backward(const rulgnn_bilstm_shape* s, const rulgnn_bilstm_args* a, hipStream_t stream, int ndir = 2);
+// `n` bidirectional layers of one shape (1 <= n <= bilstm_max_groups()), their recurrences in one launch: groups[i] is layer i's arguments
+int bilstm_max_groups();
+[[nodiscard]] int bilstm_forward_group(const rulgnn_bilstm_shape* s, const rulgnn_bilstm_args* groups, int n, hipStream_t stream);
+[[nodiscard]] int bilstm_backward_group(const rulgnn_bilstm_shape* s, const rulgnn_bilstm_args* groups, int n, hipStream_t stream);
 [[nodiscard]] int adam_step(float* p, const float* g, float* m, float* v, int64_t n, int64_t step, float lr, float beta1, float beta2,
               float eps, float wd, float gscale, hipStream_t stream, void* step_state = nullptr, const float* guard = nullptr);
 // Synchronised BatchNorm, the one step behind every launch that completes a reduction pair (bn_cells.hpp): the CELL_REP replicas of the

@@ -664,6 +664,35 @@ int rulgnn_bilstm_backward_f32(const rulgnn_bilstm_shape* shape, const rulgnn_bi
     return bilstm_backward(shape, a, static_cast<hipStream_t>(stream));
 }
 
+// grouped forms: the group count first, then every group's pointers like the single entries', all before the first launch
+int32_t rulgnn_bilstm_max_groups(void) { return bilstm_max_groups(); }
+
+static int check_bilstm_group_count(const rulgnn_bilstm_shape* shape, const rulgnn_bilstm_args* groups, int32_t num_groups) {
+    if (!shape || !groups || num_groups < 1) return RULGNN_EINVAL;
+    return num_groups > bilstm_max_groups() ? RULGNN_EUNSUPPORTED : RULGNN_OK;
+}
+
+int rulgnn_bilstm_forward_group_f32(const rulgnn_bilstm_shape* shape, const rulgnn_bilstm_args* groups, int32_t num_groups, void* stream) {
+    RULGNN_TRY(check_bilstm_group_count(shape, groups, num_groups));
+    for (int32_t i = 0; i < num_groups; ++i) {
+        const rulgnn_bilstm_args* a = &groups[i];
+        RULGNN_TRY(check_ptrs({a->x, a->w_ih[0], a->w_ih[1], a->w_hh[0], a->w_hh[1], a->b_ih[0], a->b_ih[1], a->b_hh[0], a->b_hh[1], a->out,
+                               a->workspace}));
+    }
+    return bilstm_forward_group(shape, groups, num_groups, static_cast<hipStream_t>(stream));
+}
+
+int rulgnn_bilstm_backward_group_f32(const rulgnn_bilstm_shape* shape, const rulgnn_bilstm_args* groups, int32_t num_groups, void* stream) {
+    RULGNN_TRY(check_bilstm_group_count(shape, groups, num_groups));
+    for (int32_t i = 0; i < num_groups; ++i) {
+        const rulgnn_bilstm_args* a = &groups[i];
+        RULGNN_TRY(check_ptrs({a->x, a->w_ih[0], a->w_ih[1], a->w_hh[0], a->w_hh[1], a->dout, a->dw_ih[0], a->dw_ih[1], a->dw_hh[0],
+                               a->dw_hh[1], a->db_ih[0], a->db_ih[1], a->db_hh[0], a->db_hh[1], a->workspace}));
+        if (!opt_aligned(a->dx)) return RULGNN_EALIGN;
+    }
+    return bilstm_backward_group(shape, groups, num_groups, static_cast<hipStream_t>(stream));
+}
+
 
 size_t rulgnn_stgnn_workspace_bytes(const rulgnn_stgnn_shape* shape) { return stgnn_workspace_bytes(shape); }
 

@@ -152,6 +152,92 @@ def bilstm_sum(lstm: nn.LSTM, x):
                             lstm.weight_hh_l0_reverse, lstm.bias_ih_l0_reverse, lstm.bias_hh_l0_reverse)
 
 
+_LSTM_LEAVES = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0", "weight_ih_l0_reverse", "weight_hh_l0_reverse",
+                "bias_ih_l0_reverse", "bias_hh_l0_reverse")
+
+
+class _BiLstmSumGroup(torch.autograd.Function):
+    """``_BiLstmSum`` for several independent layers of one shape at once -- the same layer of several training runs (runs.py): the
+    groups' recurrences advance side by side in one launch (``rulgnn_bilstm_forward_group_f32`` / ``..._backward_group_f32``), on
+    CUs a single layer's 2 * num_patch workgroups leave idle.  Inputs: per group ``x`` and the eight parameters, flattened; outputs:
+    one ``out`` per group, each bit-equal to ``_BiLstmSum`` on that group's tensors."""
+
+    @staticmethod
+    def forward(ctx, *flat):
+        G = len(flat) // 9
+        xs = [flat[9 * g].contiguous().float() for g in range(G)]
+        if not all(x.is_cuda for x in xs):
+            raise RuntimeError("the bidirectional LSTM layers run on the HIP kernels only: tensors must be on a CUDA (ROCm) device")
+        Bq, T, I = xs[0].shape
+        H = flat[2].shape[1]
+        for g in range(G):
+            if tuple(xs[g].shape) != (Bq, T, I) or tuple(flat[9 * g + 2].shape) != (4 * H, H) or xs[g].device != xs[0].device:
+                raise RuntimeError("bilstm_sum_group: every group must have the same shape and device")
+        shp = _lib.BilstmShape(T, Bq, I, H)
+        nbytes = _lib.load().rulgnn_bilstm_workspace_bytes(C.byref(shp))
+        if nbytes == 0:
+            raise RuntimeError("bidirectional LSTM kernels do not cover this configuration (hidden <= 128, <= 64 sequences)")
+        wss = [torch.empty(nbytes, dtype=torch.uint8, device=xs[0].device) for _ in range(G)]
+        outs = [torch.empty(Bq, T, H, dtype=torch.float32, device=xs[0].device) for _ in range(G)]
+        args = (_lib.BilstmArgs * G)()
+        for g, a in enumerate(args):
+            a.x, a.out = xs[g].data_ptr(), outs[g].data_ptr()
+            for d in range(2):
+                wi, wh, bi, bh = flat[9 * g + 1 + 4 * d:9 * g + 5 + 4 * d]
+                a.w_ih[d], a.w_hh[d], a.b_ih[d], a.b_hh[d] = wi.data_ptr(), wh.data_ptr(), bi.data_ptr(), bh.data_ptr()
+            a.workspace, a.workspace_bytes = wss[g].data_ptr(), wss[g].numel()
+        _lib.check(_lib.load().rulgnn_bilstm_forward_group_f32(C.byref(shp), args, G, _stream()), "rulgnn_bilstm_forward_group_f32")
+        saved = []
+        for g in range(G):
+            saved += [xs[g], *flat[9 * g + 1:9 * g + 9]]
+        ctx.save_for_backward(*saved)
+        ctx.wss, ctx.shp = wss, (T, Bq, I, H)
+        return tuple(outs)
+
+    @staticmethod
+    def backward(ctx, *douts):
+        flat = ctx.saved_tensors
+        G = len(flat) // 9
+        T, Bq, I, H = ctx.shp
+        shp = _lib.BilstmShape(T, Bq, I, H)
+        douts = [d.contiguous().float() for d in douts]
+        grads = [[torch.empty_like(t) for t in flat[9 * g + 1:9 * g + 9]] for g in range(G)]
+        dxs = [torch.empty_like(flat[9 * g]) if ctx.needs_input_grad[9 * g] else None for g in range(G)]
+        side = _DEFERRED[0]
+        # the deferral rule of _BiLstmSum, over the leaves of ALL groups: one side stream carries every group's parameter gradients
+        leaves = [t for g in range(G) for t in flat[9 * g + 1:9 * g + 9]]
+        if side is not None and (side.device != flat[0].device or not _accumulate_grad_steals(leaves)):
+            side = None
+        args = (_lib.BilstmArgs * G)()
+        for g, a in enumerate(args):
+            a.x, a.dout, a.dx = flat[9 * g].data_ptr(), douts[g].data_ptr(), dxs[g].data_ptr() if dxs[g] is not None else None
+            for d in range(2):
+                a.w_ih[d], a.w_hh[d] = flat[9 * g + 1 + 4 * d].data_ptr(), flat[9 * g + 2 + 4 * d].data_ptr()
+                a.dw_ih[d], a.dw_hh[d], a.db_ih[d], a.db_hh[d] = (t.data_ptr() for t in grads[g][4 * d:4 * d + 4])
+            a.workspace, a.workspace_bytes = ctx.wss[g].data_ptr(), ctx.wss[g].numel()
+            if side is not None:
+                a.aux_stream = side.cuda_stream
+                for t in (ctx.wss[g], flat[9 * g], *grads[g]):          # the side stream reads / writes them after this function has returned
+                    t.record_stream(side)
+        _lib.check(_lib.load().rulgnn_bilstm_backward_group_f32(C.byref(shp), args, G, _stream()), "rulgnn_bilstm_backward_group_f32")
+        out = []
+        for g in range(G):
+            out += [dxs[g], *grads[g]]
+        return tuple(out)
+
+
+def bilstm_sum_group(lstms, xs):
+    """``bilstm_sum`` of ``lstms[g]`` on ``xs[g]`` for every g, the recurrences of all groups in one launch; a tuple of outputs.  The
+    layers must have one shape and there may be at most ``rulgnn_bilstm_max_groups()`` of them."""
+    lstms, xs = list(lstms), list(xs)
+    if not lstms or len(lstms) != len(xs):
+        raise ValueError("bilstm_sum_group: one input per layer, at least one layer")
+    flat = []
+    for lstm, x in zip(lstms, xs):
+        flat += [x, *(getattr(lstm, leaf) for leaf in _LSTM_LEAVES)]
+    return _BiLstmSumGroup.apply(*flat)
+
+
 class Bi_LSTM_Standard(nn.Module):
     """The reference's LSTM stack (Model.py:26-73); the nn.LSTM modules hold the parameters, csrc/bilstm.hip runs them."""
 

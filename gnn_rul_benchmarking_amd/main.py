@@ -3,6 +3,7 @@
     python -m gnn_rul_benchmarking_amd.main --GNN_method ST_GCN --dataset CMAPSS --dataset_id FD004 --device cuda:0
     python -m gnn_rul_benchmarking_amd.main --GNN_method STFA --dataset CMAPSS --dataset_id FD001 --device cuda:0
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 -m gnn_rul_benchmarking_amd.main ...
+    python -m gnn_rul_benchmarking_amd.main --GNN_method HAGCN --dataset_id FD004 --num_runs 5 --concurrent_runs 5      # the five seeds stepped together (runs.py)
 
 ``--GNN_method`` takes the reference's names (main.py:43-46).  Aero-engine datasets (CMAPSS, NCMAPSS): ASTGCNN, GRU_CM, HAGCN, ST_Conv, STFA
 (CMAPSS only), RGCNU, STGNN, STAGNN, FC_STGNN, HierCorrPool, LOGO, DVGTformer; bearing datasets (PHM2012, XJTU_SY): STNet, SAGCN, ST_GCN,
@@ -27,6 +28,8 @@ def build_parser():
     # additions
     p.add_argument('--window', default=None, type=int, help='C-MAPSS window length (= ST_GCN patch_size); data decides')
     p.add_argument('--num_epochs', default=None, type=int, help='override the table value (81)')
+    p.add_argument('--concurrent_runs', default=1, type=int,
+                   help='step this many of the --num_runs runs together on the device (HAGCN only, single process, at most 8); 1: one after the other')
     return p
 
 

@@ -64,6 +64,17 @@ class GNN_RUL_trainer(object):
             self.train_configs = dict(self.train_configs, num_epochs=int(self.num_epochs_override))
         self.default_hparams = {**self.model_configs, **self.train_configs}
 
+        # --concurrent_runs N > 1: the runs are stepped N at a time on this one device (runs.py) -- refused here, before any data is loaded,
+        # for a method without a runs class and under a process group
+        self.concurrent_runs = int(getattr(args, "concurrent_runs", 1) or 1)
+        if self.concurrent_runs < 1:
+            raise ValueError("--concurrent_runs must be at least 1")
+        if self.concurrent_runs > 1:
+            from .runs import get_runs_class
+            get_runs_class(self.GNN_method)
+            if torch.distributed.is_available() and torch.distributed.is_initialized():
+                raise RuntimeError("--concurrent_runs steps several runs in ONE process: it does not combine with a process group")
+
     def get_configs(self, dataset_id):
         dataset_class = get_dataset_class(self.dataset)
         hparams_class = get_hparams_class(self.dataset)
@@ -82,6 +93,8 @@ class GNN_RUL_trainer(object):
             os.makedirs(self.exp_log_dir, exist_ok=True)
         if self.dp is not None:
             torch.distributed.barrier()
+        if self.concurrent_runs > 1:
+            return self._train_concurrently()
 
         for run_id in range(self.num_runs):
             fix_randomness(run_id)
@@ -122,6 +135,62 @@ class GNN_RUL_trainer(object):
 
             self.algorithm = algorithm
             if self.rank == 0:
+                save_checkpoint(self.home_path, self.algorithm, self.dataset_configs, self.log_dir, self.default_hparams)
+
+    def _train_concurrently(self):
+        """``--concurrent_runs N``: the loop above for N run ids at a time, stepped together by the method's runs class (runs.py).  Every
+        run keeps what the sequential loop gives it -- its seed, its loaders, its logger, its best rows, its directory and files -- and
+        whatever draws random numbers for run r (building it, its samplers, its dropouts, its test passes) runs under run r's own
+        generator states, so a run computes what it would compute alone."""
+        from .runs import get_runs_class
+        runs_class = get_runs_class(self.GNN_method)
+        num_epochs = self.train_configs["num_epochs"]
+        for first in range(0, self.num_runs, self.concurrent_runs):
+            run_ids = list(range(first, min(first + self.concurrent_runs, self.num_runs)))
+            group = runs_class(self.model_configs, self.train_configs, self.device, run_ids)
+            shard_test = getattr(getattr(type(group.runs[0]), "model_class", None), "eval_sample_independent", True)
+            per_run = []
+            for r, run_id in enumerate(run_ids):
+                with group.active(r):
+                    logger, log_dir = starting_logs(self.dataset, self.GNN_method, self.exp_log_dir, self.dataset_id, self.bearing_id, run_id,
+                                                    to_stdout=True)
+                    train_dl, test_dl, max_ruls = data_generator(self.data_path, self.dataset_configs, self.train_configs, self.device,
+                                                                 self.rank, self.world_size, shard_test_sets=shard_test)
+                if isinstance(test_dl, dict):
+                    best = {key: [[np.inf], [np.inf], [np.inf], [np.inf]] for key in test_dl.keys()}
+                else:
+                    best = [[np.inf], [np.inf], [np.inf], [np.inf]]
+                per_run.append(dict(logger=logger, log_dir=log_dir, train_dl=train_dl, test_dl=test_dl, max_ruls=max_ruls, best=best,
+                                    meters=collections.defaultdict(lambda: AverageMeter())))
+
+            for epoch in range(1, num_epochs + 1):
+                group.train()
+                batches = [iter(p["train_dl"]) for p in per_run]           # (a loader draws at its first batch, not here)
+                while True:
+                    step = []
+                    for r, it in enumerate(batches):
+                        with group.active(r):
+                            step.append(next(it, None))
+                    if any(b is None for b in step):
+                        assert all(b is None for b in step), "the runs' loaders walk the same data set in the same batch size"
+                        break
+                    losses = group.update([b[0].float().to(self.device) for b in step], [b[1].float().to(self.device) for b in step], epoch)
+                    for p, b, run_losses in zip(per_run, step, losses):
+                        for key, val in run_losses.items():
+                            p["meters"][key].update(val, b[2])
+                for r, (run_id, p) in enumerate(zip(run_ids, per_run)):
+                    self.logger, self.log_dir = p["logger"], p["log_dir"]
+                    self.train_dl, self.test_dl, self.max_ruls, self.best_result = p["train_dl"], p["test_dl"], p["max_ruls"], p["best"]
+                    self.logger.debug(f'[Epoch : {epoch}/{num_epochs}]')
+                    for key, val in p["meters"].items():
+                        self.logger.debug(f'{key}\t: {float(val.avg):2.4f}')
+                    with group.active(r):
+                        self.test_prediction(group.runs[r])
+                    self.calc_results_per_run(run_id)
+                    self.logger.debug('-------------------------------------')
+
+            for r, p in enumerate(per_run):
+                self.algorithm, self.log_dir = group.runs[r], p["log_dir"]
                 save_checkpoint(self.home_path, self.algorithm, self.dataset_configs, self.log_dir, self.default_hparams)
 
     # ---------------------------------------------------------------------------------------------

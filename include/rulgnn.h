@@ -1055,6 +1055,19 @@ size_t rulgnn_bilstm_workspace_bytes(const rulgnn_bilstm_shape *shape);     /* 0
 int rulgnn_bilstm_forward_f32(const rulgnn_bilstm_shape *shape, const rulgnn_bilstm_args *args, void *stream);
 int rulgnn_bilstm_backward_f32(const rulgnn_bilstm_shape *shape, const rulgnn_bilstm_args *args, void *stream);
 
+/* Grouped forms: `num_groups` independent layers of ONE shape -- the same layer of several training runs -- whose recurrences advance
+ * side by side in one launch, workgroup = (group, direction, sequence): a single layer's recurrence occupies 2 * num_seq of the 256
+ * CUs for thousands of dependent steps, and the other groups' recurrences run on CUs that would idle.  `groups` is a HOST array of
+ * the struct above, one element per group: its own x, weights, out / dout / dx, gradients and workspace (each at least
+ * rulgnn_bilstm_workspace_bytes(shape); a group's tape is what the single call would have written).  A group's results are the
+ * single call's on the same arguments, bit for bit.  1 <= num_groups <= rulgnn_bilstm_max_groups() (8): RULGNN_EINVAL below,
+ * RULGNN_EUNSUPPORTED above; a group whose workspace is too small: RULGNN_EWORKSPACE.  Every group is checked before the first
+ * launch.  `aux_stream` keeps its contract and must be the same in every group: all groups' parameter gradients are produced there
+ * and the call does not join. */
+int32_t rulgnn_bilstm_max_groups(void);
+int rulgnn_bilstm_forward_group_f32(const rulgnn_bilstm_shape *shape, const rulgnn_bilstm_args *groups, int32_t num_groups, void *stream);
+int rulgnn_bilstm_backward_group_f32(const rulgnn_bilstm_shape *shape, const rulgnn_bilstm_args *groups, int32_t num_groups, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * ST_Conv path (reference models/ST_Conv/Model.py, algorithms/algorithms.py:195-220): the
  * reference's natively C-MAPSS / N-CMAPSS wired spatio-temporal convolution (configs/hparams.py:40,203).
