@@ -393,6 +393,11 @@ _SIGNATURES = {
     "rulgnn_bilstm_forward_group_f32": (C.c_int, [C.POINTER(BilstmShape), C.POINTER(BilstmArgs), C.c_int32, C.c_void_p]),      # a host array
     "rulgnn_bilstm_backward_group_f32": (C.c_int, [C.POINTER(BilstmShape), C.POINTER(BilstmArgs), C.c_int32, C.c_void_p]),     # of BilstmArgs
     "rulgnn_stmsgcn_features_f32": (C.c_int, [C.POINTER(StmsgcnShape), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    # grouped fused steps: host arrays of the family's Args and (or NULL) of AdamArgs, one element per run
+    "rulgnn_step_max_groups": (C.c_int32, []),
+    "rulgnn_dvgtformer_fwdbwd_group_f32": (C.c_int, [C.POINTER(DvgtformerShape), C.POINTER(DvgtformerArgs), C.POINTER(AdamArgs), C.c_int32,
+                                                     C.c_void_p]),
+    "rulgnn_logo_fwdbwd_group_f32": (C.c_int, [C.POINTER(LogoShape), C.POINTER(LogoArgs), C.POINTER(AdamArgs), C.c_int32, C.c_void_p]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -24,6 +24,7 @@ namespace {
 // Most layers of one shape a grouped call runs side by side (bilstm_forward_group / bilstm_backward_group): the groups' pointers travel
 // by value in the kernel arguments -- 8 x 7 pointers are 448 bytes.
 constexpr int LSTM_MAX_GROUPS = 8;
+static_assert(STEP_MAX_GROUPS <= LSTM_MAX_GROUPS, "a grouped fused step (families_host.hpp) hands all its runs' layers to one grouped Bi-LSTM call");
 
 struct LstmGeom {
     int64_t T;                  // time steps (batch_size * num_node)

@@ -90,6 +90,55 @@ __global__ __launch_bounds__(DV_BLK) void dv_encoder_bwd_kernel(DvGeom g, DvOff 
     }
 }
 
+// ---- grouped forms: several runs of one shape, grid (x, runs) ---------------------------------------------------------------------------
+// Run blockIdx.y's pointers and dropout keys come from a table that travels by value in the kernel arguments (blockIdx.y is
+// wavefront-uniform: scalar loads from the argument segment, as in lstm_forward_group_kernel); the bodies are the single kernels'.
+struct DvGroup {
+    const float *x, *prm;           // the run's batch and parameters
+    float *fw, *hin;                // its folded operands; its half-block inputs and encoder output
+    const float* denc;
+    float *part, *red, *grads;      // its partial rows, their sum, its gradient
+    DvDrop drop;                    // keys of the run's own seed and step
+};
+struct DvGroupTable {
+    DvGroup grp[STEP_MAX_GROUPS];
+};
+
+__global__ __launch_bounds__(256) void dv_fold_group_kernel(DvGeom g, DvOff o, DvGroupTable tab) {
+    const DvGroup& r = tab.grp[blockIdx.y];
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e < o.fw_total + g.E) r.fw[e] = dv_fold_elem(g, o, r.prm, e);
+}
+
+__global__ __launch_bounds__(256) void dv_unfold_group_kernel(DvGeom g, DvOff o, DvGroupTable tab) {
+    const DvGroup& r = tab.grp[blockIdx.y];
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e < o.hw1) r.grads[e] = dv_unfold_elem(g, o, r.prm, r.red, e);
+}
+
+__global__ __launch_bounds__(DV_BLK) void dv_encoder_fwd_group_kernel(DvGeom g, DvOff o, DvLds l, DvGroupTable tab) {
+    extern __shared__ float dv_smem[];
+    const DvGroup& r = tab.grp[blockIdx.y];
+    const DvCtx c{(int)threadIdx.x, DV_BLK, dv_smem};
+    const int64_t slot = g.B * (int64_t)g.E;
+    for (int64_t b = blockIdx.x; b < g.B; b += gridDim.x)
+        dv_sample_fwd(c, g, o, l, r.drop, b, r.x + b * g.N * g.L, r.prm, r.fw, r.hin + b * g.E, slot);
+}
+
+// (grid x = DvWs::rows, as the single kernel's: a run's partial rows hold the single call's sums)
+__global__ __launch_bounds__(DV_BLK) void dv_encoder_bwd_group_kernel(DvGeom g, DvOff o, DvLds l, DvGroupTable tab) {
+    extern __shared__ float dv_smem[];
+    const DvGroup& r = tab.grp[blockIdx.y];
+    const DvCtx c{(int)threadIdx.x, DV_BLK, dv_smem};
+    const int64_t slot = g.B * (int64_t)g.E;
+    float* row = r.part + (int64_t)blockIdx.x * o.row_total;
+    bool first = true;
+    for (int64_t b = blockIdx.x; b < g.B; b += gridDim.x) {
+        dv_sample_bwd(c, g, o, l, r.drop, b, r.x + b * g.N * g.L, r.prm, r.fw, r.hin + b * g.E, slot, r.denc + b * g.E, row, first);
+        first = false;
+    }
+}
+
 // ---- head: Linear(E, 100) (on the shared SGEMM) - GELU - Linear(100, 1) --------------------------------------------------------------
 constexpr int DV_HID = 100;
 
@@ -196,6 +245,66 @@ int64_t Dvgtformer::tap_offset(const Shape* s, int which) {
     return (int64_t)(w.hin / sizeof(float)) + (which == 1 ? (int64_t)(2 * g.nb * B * g.E) : 0);
 }
 
+namespace {
+
+// One run's view of a call: its workspace blocks and dropout keys.  The per-run stages below are what run() and run_group() enqueue
+// around the fold, the encoder kernels and the unfold, which the one launches per run and the other once for all runs.
+struct DvRun {
+    const rulgnn_dvgtformer_args* a;
+    float *fw, *hin, *enc, *h1, *dh, *denc, *dpred, *sqerr, *part, *red;
+    DvDrop drop;
+};
+
+DvRun dv_run_of(const DvGeom& g, const DvWs& w, const rulgnn_dvgtformer_args* a) {
+    DvRun r{};
+    r.a = a;
+    const DropoutConst dc = dropout_const(a->training ? a->dropout_p : 0.f);
+    r.drop.thr = dc.thr;
+    r.drop.scale = dc.scale;
+    for (int b = 0; b < g.nb; ++b) r.drop.key[b] = dropout_layer_key(a->seed, a->step, b);
+    r.drop.sample_offset = (uint32_t)a->sample_offset;
+    const Workspace ws(a->workspace);
+    r.fw = ws.at<float>(w.fw); r.hin = ws.at<float>(w.hin); r.h1 = ws.at<float>(w.h1); r.dh = ws.at<float>(w.dh);
+    r.denc = ws.at<float>(w.denc); r.dpred = ws.at<float>(w.dpred); r.sqerr = ws.at<float>(w.sqerr); r.part = ws.at<float>(w.part);
+    r.red = ws.at<float>(w.red);
+    r.enc = r.hin + (size_t)2 * g.nb * g.B * g.E;
+    return r;
+}
+
+// behind the encoder forward: the head's first layer on the shared SGEMM, then pred (with y also d pred and the loss terms)
+int dv_head_fwd(const DvGeom& g, const DvOff& o, const DvRun& r, hipStream_t st) {
+    const rulgnn_dvgtformer_args* a = r.a;
+    const float* prm = a->params;
+    const int B = (int)g.B, E = g.E;
+    RULGNN_TRY(sgemm(r.enc, E, 1, prm + o.hw1, E, 1, r.h1, DV_HID, B, DV_HID, E, false, st));
+    const float inv_gb = 1.0f / (float)(a->global_batch > 0 ? a->global_batch : g.B);
+    return launch_checked(dv_head_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, g.B, (const float*)r.h1, prm + o.hb1, prm + o.hw2,
+                          prm + o.hb2, a->y, a->pred, r.dpred, r.sqerr, inv_gb);
+}
+
+// in front of the encoder backward: the head's gradients and d enc
+int dv_head_bwd(const DvGeom& g, const DvOff& o, const DvRun& r, hipStream_t st) {
+    const rulgnn_dvgtformer_args* a = r.a;
+    const float* prm = a->params;
+    const int B = (int)g.B, E = g.E;
+    const float* dpred = a->dpred ? a->dpred : r.dpred;
+    float* gr = a->grads;
+    RULGNN_TRY(launch_checked(dv_head_dh_kernel, dim3((unsigned)(((int64_t)B * DV_HID + 255) / 256)), dim3(256), 0, st, g.B, (const float*)r.h1,
+                              prm + o.hb1, prm + o.hw2, dpred, r.dh));
+    RULGNN_TRY(launch_checked(dv_head_small_kernel, dim3(1), dim3(128), 0, st, g.B, (const float*)r.h1, prm + o.hb1, dpred, (const float*)r.dh,
+                              gr + o.hb1, gr + o.hw2, gr + o.hb2));
+    // dW1 [100][E] = dh^T enc, d enc [B][E] = dh W1
+    RULGNN_TRY(sgemm(r.dh, 1, DV_HID, r.enc, 1, E, gr + o.hw1, E, DV_HID, E, B, false, st));
+    return sgemm(r.dh, DV_HID, 1, prm + o.hw1, 1, E, r.denc, E, B, E, DV_HID, false, st);
+}
+
+int dv_loss_sum(const DvGeom& g, const DvRun& r, hipStream_t st) {
+    if (r.a->dpred || !r.a->loss) return RULGNN_OK;
+    return block_sum((const float*)r.sqerr, g.B, r.a->loss, st);
+}
+
+}  // namespace
+
 // mode bit 0: forward (pred; with y also d pred and the loss terms), bit 1: backward (gradients; d pred from args->dpred or from the
 // forward of this call)
 int Dvgtformer::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
@@ -210,50 +319,79 @@ int Dvgtformer::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
         if ((mode & 2) && a->loss && hipMemsetAsync(a->loss, 0, sizeof(float), st) != hipSuccess) return RULGNN_EHIP;
         return RULGNN_OK;
     }
-    DvDrop drop{};
-    const DropoutConst dc = dropout_const(a->training ? a->dropout_p : 0.f);
-    drop.thr = dc.thr;
-    drop.scale = dc.scale;
-    for (int b = 0; b < g.nb; ++b) drop.key[b] = dropout_layer_key(a->seed, a->step, b);
-    drop.sample_offset = (uint32_t)a->sample_offset;
-    const Workspace ws(a->workspace);
-    auto Fp = [&](size_t off) { return ws.at<float>(off); };
+    const DvRun r = dv_run_of(g, w, a);
     const float* prm = a->params;
-    const int B = (int)g.B, E = g.E;
-    float* enc = Fp(w.hin) + (size_t)2 * g.nb * B * E;
+    const int E = g.E;
     // the folded operands follow the parameters of THIS call (an optimizer step lies between two calls)
-    RULGNN_TRY(launch_checked(dv_fold_kernel, dim3((unsigned)((o.fw_total + E + 255) / 256)), dim3(256), 0, st, g, o, prm, Fp(w.fw)));
+    RULGNN_TRY(launch_checked(dv_fold_kernel, dim3((unsigned)((o.fw_total + E + 255) / 256)), dim3(256), 0, st, g, o, prm, r.fw));
     if (mode & 1) {
         const DvLds l = dv_lds(g, false);
         const size_t lds = sizeof(float) * (size_t)l.total;
         RULGNN_TRY(allow_dynamic_lds(dv_encoder_fwd_kernel, lds));
         const int grid = resident_rows(dv_encoder_fwd_kernel, DV_BLK, lds, g.B, 4096);
-        RULGNN_TRY(launch_checked(dv_encoder_fwd_kernel, dim3((unsigned)grid), dim3(DV_BLK), lds, st, g, o, l, drop, a->x, prm,
-                                  (const float*)Fp(w.fw), Fp(w.hin)));
-        RULGNN_TRY(sgemm(enc, E, 1, prm + o.hw1, E, 1, Fp(w.h1), DV_HID, B, DV_HID, E, false, st));
-        const float inv_gb = 1.0f / (float)(a->global_batch > 0 ? a->global_batch : g.B);
-        RULGNN_TRY(launch_checked(dv_head_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, g.B, (const float*)Fp(w.h1), prm + o.hb1,
-                                  prm + o.hw2, prm + o.hb2, a->y, a->pred, Fp(w.dpred), Fp(w.sqerr), inv_gb));
+        RULGNN_TRY(launch_checked(dv_encoder_fwd_kernel, dim3((unsigned)grid), dim3(DV_BLK), lds, st, g, o, l, r.drop, a->x, prm, (const float*)r.fw,
+                                  r.hin));
+        RULGNN_TRY(dv_head_fwd(g, o, r, st));
     }
     if (mode & 2) {
-        const float* dpred = a->dpred ? a->dpred : Fp(w.dpred);
-        float* gr = a->grads;
-        RULGNN_TRY(launch_checked(dv_head_dh_kernel, dim3((unsigned)(((int64_t)B * DV_HID + 255) / 256)), dim3(256), 0, st, g.B,
-                                  (const float*)Fp(w.h1), prm + o.hb1, prm + o.hw2, dpred, Fp(w.dh)));
-        RULGNN_TRY(launch_checked(dv_head_small_kernel, dim3(1), dim3(128), 0, st, g.B, (const float*)Fp(w.h1), prm + o.hb1, dpred,
-                                  (const float*)Fp(w.dh), gr + o.hb1, gr + o.hw2, gr + o.hb2));
-        // dW1 [100][E] = dh^T enc, d enc [B][E] = dh W1
-        RULGNN_TRY(sgemm(Fp(w.dh), 1, DV_HID, enc, 1, E, gr + o.hw1, E, DV_HID, E, B, false, st));
-        RULGNN_TRY(sgemm(Fp(w.dh), DV_HID, 1, prm + o.hw1, 1, E, Fp(w.denc), E, B, E, DV_HID, false, st));
+        RULGNN_TRY(dv_head_bwd(g, o, r, st));
         const DvLds l = dv_lds(g, true);
         const size_t lds = sizeof(float) * (size_t)l.total;
         RULGNN_TRY(allow_dynamic_lds(dv_encoder_bwd_kernel, lds));
-        RULGNN_TRY(launch_checked(dv_encoder_bwd_kernel, dim3((unsigned)w.rows), dim3(DV_BLK), lds, st, g, o, l, drop, a->x, prm,
-                                  (const float*)Fp(w.fw), (const float*)Fp(w.hin), (const float*)Fp(w.denc), Fp(w.part)));
-        RULGNN_TRY(rows_sum(Fp(w.part), w.rows, o.row_total, o.row_total, Fp(w.red), st));
-        RULGNN_TRY(launch_checked(dv_unfold_kernel, dim3((unsigned)((o.hw1 + 255) / 256)), dim3(256), 0, st, g, o, prm, (const float*)Fp(w.red), gr));
-        if (!a->dpred && a->loss) RULGNN_TRY(block_sum((const float*)Fp(w.sqerr), g.B, a->loss, st));
+        RULGNN_TRY(launch_checked(dv_encoder_bwd_kernel, dim3((unsigned)w.rows), dim3(DV_BLK), lds, st, g, o, l, r.drop, a->x, prm, (const float*)r.fw,
+                                  (const float*)r.hin, (const float*)r.denc, r.part));
+        RULGNN_TRY(rows_sum(r.part, w.rows, o.row_total, o.row_total, r.red, st));
+        RULGNN_TRY(launch_checked(dv_unfold_kernel, dim3((unsigned)((o.hw1 + 255) / 256)), dim3(256), 0, st, g, o, prm, (const float*)r.red, a->grads));
+        RULGNN_TRY(dv_loss_sum(g, r, st));
     }
+    return RULGNN_OK;
+}
+
+// The fused step (mode 3) of `n` runs of one shape: the fold, the encoder forward, the encoder backward and the unfold are one launch
+// each for all runs, grid (x, n); the head, the row sum and the loss sum follow per run in run order, with run()'s arguments.  The
+// forward's grid x is sized for the whole group (its samples are independent); the backward's stays DvWs::rows, which fixes each run's
+// summation order.  The entry has checked every group.
+int Dvgtformer::run_group(const Shape* s, const Args* groups, int n, hipStream_t st) {
+    DvGeom g;
+    RULGNN_TRY(dv_geometry(s, &g));
+    if (n < 1 || n > STEP_MAX_GROUPS) return RULGNN_EINVAL;
+    const DvOff o = dv_offsets(g);
+    DvWs w;
+    dv_ws(g, o, &w);
+    for (int i = 0; i < n; ++i)
+        if (!groups[i].workspace || groups[i].workspace_bytes < w.total) return RULGNN_EWORKSPACE;
+    if (g.B == 0) {
+        for (int i = 0; i < n; ++i) RULGNN_TRY(run(s, &groups[i], 3, st));
+        return RULGNN_OK;
+    }
+    DvRun runs[STEP_MAX_GROUPS];
+    DvGroupTable tab{};
+    for (int i = 0; i < n; ++i) {
+        const DvRun& r = runs[i] = dv_run_of(g, w, &groups[i]);
+        tab.grp[i] = DvGroup{groups[i].x, groups[i].params, r.fw, r.hin, r.denc, r.part, r.red, groups[i].grads, r.drop};
+    }
+    const unsigned ny = (unsigned)n;
+    RULGNN_TRY(launch_checked(dv_fold_group_kernel, dim3((unsigned)((o.fw_total + g.E + 255) / 256), ny), dim3(256), 0, st, g, o, tab));
+    {
+        const DvLds l = dv_lds(g, false);
+        const size_t lds = sizeof(float) * (size_t)l.total;
+        RULGNN_TRY(allow_dynamic_lds(dv_encoder_fwd_group_kernel, lds));
+        const int resident = resident_rows(dv_encoder_fwd_group_kernel, DV_BLK, lds, g.B * n, (int64_t)4096 * n);
+        RULGNN_TRY(launch_checked(dv_encoder_fwd_group_kernel, dim3((unsigned)((resident + n - 1) / n), ny), dim3(DV_BLK), lds, st, g, o, l, tab));
+    }
+    for (int i = 0; i < n; ++i) {
+        RULGNN_TRY(dv_head_fwd(g, o, runs[i], st));
+        RULGNN_TRY(dv_head_bwd(g, o, runs[i], st));
+    }
+    {
+        const DvLds l = dv_lds(g, true);
+        const size_t lds = sizeof(float) * (size_t)l.total;
+        RULGNN_TRY(allow_dynamic_lds(dv_encoder_bwd_group_kernel, lds));
+        RULGNN_TRY(launch_checked(dv_encoder_bwd_group_kernel, dim3((unsigned)w.rows, ny), dim3(DV_BLK), lds, st, g, o, l, tab));
+    }
+    for (int i = 0; i < n; ++i) RULGNN_TRY(rows_sum(runs[i].part, w.rows, o.row_total, o.row_total, runs[i].red, st));
+    RULGNN_TRY(launch_checked(dv_unfold_group_kernel, dim3((unsigned)((o.hw1 + 255) / 256), ny), dim3(256), 0, st, g, o, tab));
+    for (int i = 0; i < n; ++i) RULGNN_TRY(dv_loss_sum(g, runs[i], st));
     return RULGNN_OK;
 }
 

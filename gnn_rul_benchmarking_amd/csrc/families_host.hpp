@@ -20,6 +20,11 @@ namespace rulgnn {
 //   check_args(s, a, fwd, bwd)              what the entries refuse before run(): shape_status, then the args' own fields (defined in
 //                                           rulgnn_api.hip on its pointer checks; s and a are not null)
 //   adam_first(s), adam_frozen_tail(s)      the fused step's Adam updates the flat floats [adam_first, param_count - adam_frozen_tail)
+//   run_group(s, groups, n, stream)        (the families with a rulgnn_<family>_fwdbwd_group_f32 entry) mode 3 of `n` runs of one shape in one
+//                                           call, groups[i] run i's arguments: what run() enqueues for each, its dominant kernels as
+//                                           grouped launches (grid y = the run); the entry has checked every group, workspaces included
+// Most runs a grouped fused step advances (rulgnn_step_max_groups): their pointer tables travel by value in the kernel arguments.
+constexpr int STEP_MAX_GROUPS = 8;
 template <typename S, typename A>
 struct StepFamily {
     using Shape = S;
@@ -172,6 +177,7 @@ struct Logo : StepFamily<rulgnn_logo_shape, rulgnn_logo_args> {
     static size_t workspace_bytes(const Shape* s);
     static int64_t tap_offset(const Shape* s, int which);
     [[nodiscard]] static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
+    [[nodiscard]] static int run_group(const Shape* s, const Args* groups, int n, hipStream_t st);
     [[nodiscard]] static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
 };
 // (the args struct is LOGO's; x is the raw window [batch][num_patch * patch_size])
@@ -189,6 +195,7 @@ struct Dvgtformer : StepFamily<rulgnn_dvgtformer_shape, rulgnn_dvgtformer_args> 
     static size_t workspace_bytes(const Shape* s);
     static int64_t tap_offset(const Shape* s, int which);
     [[nodiscard]] static int run(const Shape* s, const Args* a, int mode, hipStream_t st);
+    [[nodiscard]] static int run_group(const Shape* s, const Args* groups, int n, hipStream_t st);
     [[nodiscard]] static int check_args(const Shape* s, const Args* a, bool fwd, bool bwd);
 };
 struct Gdagdl : StepFamily<rulgnn_gdagdl_shape, rulgnn_gdagdl_args> {

@@ -390,9 +390,10 @@ __device__ __forceinline__ void lg_patch(const LgGeom& g, const LgLds& l, float*
 }
 
 // hg [q = t N + n][b][3p]; glpart [b][2] = the sample's sum(D . C), sum(C^2).  ST: lgb_graph_fwd, x = the raw windows [b][T][P]
+// (the body of the single kernel and of the grouped one below: they differ only in where the pointers come from)
 template <bool ST>
-__global__ __launch_bounds__(LG_GB) void lg_graph_fwd(LgGeom g, const float* __restrict__ x, const float* __restrict__ prm, float* __restrict__ hg,
-                                                      float* __restrict__ glpart) {
+__device__ __forceinline__ void lg_graph_fwd_body(LgGeom g, const float* __restrict__ x, const float* __restrict__ prm, float* __restrict__ hg,
+                                                  float* __restrict__ glpart) {
     extern __shared__ float lds[];
     const int N = g.N, p2 = g.p2, p3 = g.p3, EL = p2 + 1, tid = threadIdx.x;
     const LgLds l = lg_lds(N, g.L, g.p, g.CW, false, g.ns, g.P);
@@ -424,10 +425,36 @@ __global__ __launch_bounds__(LG_GB) void lg_graph_fwd(LgGeom g, const float* __r
     }
 }
 
+template <bool ST>
+__global__ __launch_bounds__(LG_GB) void lg_graph_fwd(LgGeom g, const float* __restrict__ x, const float* __restrict__ prm, float* __restrict__ hg,
+                                                      float* __restrict__ glpart) {
+    lg_graph_fwd_body<ST>(g, x, prm, hg, glpart);
+}
+
+// Grouped forms of the two graph kernels: several runs of one shape, grid (x, runs).  Run blockIdx.y's pointers and loss weights come from
+// a table that travels by value in the kernel arguments (blockIdx.y is wavefront-uniform: scalar loads from the argument segment, as in
+// lstm_forward_group_kernel).  LOGO only: the LOGO_bearing (ST) bodies are not instantiated in grouped form.
+struct LgGroup {
+    const float *x, *prm;            // the run's batch and parameters
+    float *hg, *glpart;              // forward: its graph-stage output and per-sample loss sums
+    const float *dhg, *glv;          // backward: d Hg and {L_GL, S1, S2}
+    float* part;                     // its partial rows
+    float coef, gamma;               // d loss / d L_GL (the run's theta) and gamma
+};
+struct LgGroupTable {
+    LgGroup grp[STEP_MAX_GROUPS];
+};
+
+__global__ __launch_bounds__(LG_GB) void lg_graph_fwd_group(LgGeom g, LgGroupTable tab) {
+    const LgGroup& r = tab.grp[blockIdx.y];
+    lg_graph_fwd_body<false>(g, r.x, r.prm, r.hg, r.glpart);
+}
+
 // dhg [q][b][3p] -> one partial row [nA + nB] per workgroup; glv = {L_GL, S1, S2}; coef = d loss / d L_GL.  ST: lgb_graph_bwd
 template <bool ST>
-__global__ __launch_bounds__(LG_GB) void lg_graph_bwd(LgGeom g, const float* __restrict__ x, const float* __restrict__ prm, const float* __restrict__ dhg,
-                                                      const float* __restrict__ glv, float coef, float gamma, float* __restrict__ part) {
+__device__ __forceinline__ void lg_graph_bwd_body(LgGeom g, const float* __restrict__ x, const float* __restrict__ prm,
+                                                  const float* __restrict__ dhg, const float* __restrict__ glv, float coef, float gamma,
+                                                  float* __restrict__ part) {
     extern __shared__ float lds[];
     const int N = g.N, p = g.p, p2 = g.p2, p3 = g.p3, XL = g.L + 1, NL = N + 1, EL = p2 + 1, HL = p3 + 1, tid = threadIdx.x, fs = N * N + N;
     const LgLds l = lg_lds(N, g.L, p, g.CW, true, g.ns, g.P);
@@ -651,6 +678,18 @@ __global__ __launch_bounds__(LG_GB) void lg_graph_bwd(LgGeom g, const float* __r
     }
 }
 
+template <bool ST>
+__global__ __launch_bounds__(LG_GB) void lg_graph_bwd(LgGeom g, const float* __restrict__ x, const float* __restrict__ prm, const float* __restrict__ dhg,
+                                                      const float* __restrict__ glv, float coef, float gamma, float* __restrict__ part) {
+    lg_graph_bwd_body<ST>(g, x, prm, dhg, glv, coef, gamma, part);
+}
+
+// (grid x = LgGeom::rows, as the single kernel's: a run's partial rows hold the single call's sums)
+__global__ __launch_bounds__(LG_GB) void lg_graph_bwd_group(LgGeom g, LgGroupTable tab) {
+    const LgGroup& r = tab.grp[blockIdx.y];
+    lg_graph_bwd_body<false>(g, r.x, r.prm, r.dhg, r.glv, r.coef, r.gamma, r.part);
+}
+
 // ---- inter-layer passes -------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float lg_keep(uint32_t ctr, uint32_t key, uint32_t thr, float scale) {
     return scale == 0.f ? 1.f : (lowbias32(ctr ^ key) >= thr ? scale : 0.f);
@@ -831,92 +870,199 @@ int Logob::run(const Shape* s, const Args* a, int mode, hipStream_t st) {
 
 namespace {
 
-// mode bit 0: forward, bit 1: backward (after a forward with the same args / workspace)
-int lg_run(const LgGeom& g, const rulgnn_logo_args* a, int mode, hipStream_t st) {
-    if (a->workspace_bytes < g.total_bytes) return RULGNN_EWORKSPACE;
-    if (g.B == 0) return RULGNN_OK;
-    float* ws = static_cast<float*>(a->workspace);
-    const float* prm = a->params;
-    const int64_t B = g.B, gb = a->global_batch > 0 ? a->global_batch : B;
-    const int Q = g.Q, H1 = g.H1, H2 = g.H2, K1 = g.K1;
-    const int64_t QB = (int64_t)Q * B;
-    const bool drop = a->training && a->dropout_p > 0.f;
-    const DropoutConst dc = dropout_const(drop ? a->dropout_p : 0.f);
-    const float dscale = drop ? dc.scale : 0.f;
-    const uint32_t key2 = dropout_layer_key(a->seed, a->step, 0), key3 = dropout_layer_key(a->seed, a->step, 1);
-    const double cnt = (double)B * g.T * g.N * g.N;
-    const float* dpred = a->dpred ? a->dpred : ws + g.w_dpred;
+// One run's view of a call: its workspace, parameters and dropout constants.  The per-run stages below are what lg_run and lg_run_group
+// enqueue around the graph kernels and the recurrences, which the one launches per run and the other once for all runs.
+struct LgRun {
+    const rulgnn_logo_args* a;
+    float* ws;
+    const float* prm;
+    bool drop;
+    uint32_t thr, key2, key3;
+    float dscale;
+};
+
+LgRun lg_run_of(const rulgnn_logo_args* a) {
+    LgRun r{};
+    r.a = a;
+    r.ws = static_cast<float*>(a->workspace);
+    r.prm = a->params;
+    r.drop = a->training && a->dropout_p > 0.f;
+    const DropoutConst dc = dropout_const(r.drop ? a->dropout_p : 0.f);
+    r.thr = dc.thr;
+    r.dscale = r.drop ? dc.scale : 0.f;
+    r.key2 = dropout_layer_key(a->seed, a->step, 0);
+    r.key3 = dropout_layer_key(a->seed, a->step, 1);
+    return r;
+}
+
+// layer l of the run's temporal stack; bwd: with d out, d x and the gradients
+void lg_lstm_args(const LgGeom& g, const LgRun& r, int l, bool bwd, rulgnn_bilstm_shape* ls, rulgnn_bilstm_args* la) {
+    float* ws = r.ws;
     float* const lin[3] = {ws + g.w_hg, ws + g.w_o1, ws + g.w_o2};
     float* const lout[3] = {ws + g.w_o1, ws + g.w_o2, ws + g.w_o3};
     float* const ldout[3] = {ws + g.w_do1, ws + g.w_do2, ws + g.w_do3};
     float* const ldx[3] = {ws + g.w_dhg, ws + g.w_do1, ws + g.w_do2};
-    auto lstm_args = [&](int l, rulgnn_bilstm_shape* ls, rulgnn_bilstm_args* la) {
-        const LgLstm& k = g.lstm[l];
-        *ls = rulgnn_bilstm_shape{B, Q, k.I, k.H};
-        *la = rulgnn_bilstm_args{};
-        la->x = lin[l];
-        la->out = lout[l];
+    const LgLstm& k = g.lstm[l];
+    *ls = rulgnn_bilstm_shape{g.B, g.Q, k.I, k.H};
+    *la = rulgnn_bilstm_args{};
+    la->x = lin[l];
+    la->out = lout[l];
+    for (int d = 0; d < 2; ++d) {
+        la->w_ih[d] = r.prm + k.o_wih[d]; la->w_hh[d] = r.prm + k.o_whh[d]; la->b_ih[d] = r.prm + k.o_bih[d]; la->b_hh[d] = r.prm + k.o_bhh[d];
+    }
+    la->workspace = ws + k.w_ws;
+    la->workspace_bytes = k.ws_bytes;
+    if (bwd) {
+        float* gr = r.a->grads;
+        la->dout = ldout[l];
+        la->dx = ldx[l];
         for (int d = 0; d < 2; ++d) {
-            la->w_ih[d] = prm + k.o_wih[d]; la->w_hh[d] = prm + k.o_whh[d]; la->b_ih[d] = prm + k.o_bih[d]; la->b_hh[d] = prm + k.o_bhh[d];
+            la->dw_ih[d] = gr + k.o_wih[d]; la->dw_hh[d] = gr + k.o_whh[d]; la->db_ih[d] = gr + k.o_bih[d]; la->db_hh[d] = gr + k.o_bhh[d];
         }
-        la->workspace = ws + k.w_ws;
-        la->workspace_bytes = k.ws_bytes;
-    };
+    }
+}
+
+// dropout behind bi_lstm2: o2 in the forward, with the same key d o2 in the backward
+int lg_mid_drop(const LgGeom& g, const LgRun& r, float* v, hipStream_t st) {
+    if (!r.drop) return RULGNN_OK;
+    const int64_t n = (int64_t)g.Q * g.B * g.H2;
+    return launch_checked(lg_drop_kernel, dim3(lg_blocks(n)), dim3(LG_GB), 0, st, n, v, r.key2, r.thr, r.dscale);
+}
+
+// behind the temporal stack: closing pass, fc1, head and loss
+int lg_head_fwd(const LgGeom& g, const LgRun& r, hipStream_t st) {
+    const rulgnn_logo_args* a = r.a;
+    float* ws = r.ws;
+    const float* prm = r.prm;
+    const int64_t B = g.B, gb = a->global_batch > 0 ? a->global_batch : B, QB = (int64_t)g.Q * B;
+    const int Q = g.Q, H1 = g.H1, K1 = g.K1;
+    const double cnt = (double)B * g.T * g.N * g.N;
+    RULGNN_TRY(launch_checked(lg_close_kernel<false>, dim3(lg_blocks(QB * H1)), dim3(LG_GB), 0, st, B, Q, H1, (const float*)(ws + g.w_o3), (const float*)nullptr,
+                              ws + g.w_td, r.key3, r.thr, r.dscale));
+    // pre1 [B][16] = td [B][Q 3h] fc1^T: a few tiles over k = Q 3h, in fixed slices
+    RULGNN_TRY(sgemm_splitk(ws + g.w_td, K1, 1, prm + g.o_f1w, K1, 1, ws + g.w_pre1, LG_F1, (int)B, LG_F1, K1, false, ws + g.w_split, st));
+    RULGNN_TRY(launch_checked(lg_head_kernel, dim3(lg_blocks(B, 4096)), dim3(LG_GB), 0, st, g, prm, ws + g.w_pre1, ws + g.w_a2, a->y, a->pred, ws + g.w_sq,
+                              ws + g.w_dpred, 1.0f / (float)gb));
+    return launch_checked(lg_loss_kernel, dim3(1), dim3(LG_GB), 0, st, B, cnt, a->theta, a->gamma, (const float*)(ws + g.w_glpart),
+                          a->y ? (const float*)(ws + g.w_sq) : (const float*)nullptr, ws + g.w_gl, a->loss_gl, a->loss);
+}
+
+// in front of the temporal stack's backward: the head's gradients, d td and the closing pass's backward
+int lg_head_bwd(const LgGeom& g, const LgRun& r, hipStream_t st) {
+    const rulgnn_logo_args* a = r.a;
+    float* ws = r.ws;
+    const float* prm = r.prm;
+    const int64_t B = g.B, QB = (int64_t)g.Q * B;
+    const int Q = g.Q, H1 = g.H1, K1 = g.K1;
+    const float* dpred = a->dpred ? a->dpred : ws + g.w_dpred;
+    float* gr = a->grads;
+    RULGNN_TRY(launch_checked(lg_head_bwd_kernel, dim3(lg_blocks(B, 4096)), dim3(LG_GB), 0, st, g, prm, (const float*)(ws + g.w_pre1), (const float*)(ws + g.w_a2),
+                              dpred, ws + g.w_prod, ws + g.w_dpre1));
+    // [g fc1.bias .. g cls.bias] = the samples' rows in order (contiguous in the parameter layout)
+    RULGNN_TRY(rows_sum(ws + g.w_prod, (int)B, LG_HEADROW, LG_HEADROW, gr + g.o_f1b, st));
+    // g fc1.weight [16][Q 3h] = dpre1^T td (k = the batch, one fixed-order product); dtd = dpre1 fc1
+    RULGNN_TRY(sgemm(ws + g.w_dpre1, 1, LG_F1, ws + g.w_td, 1, K1, gr + g.o_f1w, K1, LG_F1, K1, (int)B, false, st));
+    RULGNN_TRY(sgemm(ws + g.w_dpre1, LG_F1, 1, prm + g.o_f1w, 1, K1, ws + g.w_dtd, K1, (int)B, K1, LG_F1, false, st));
+    return launch_checked(lg_close_kernel<true>, dim3(lg_blocks(QB * H1)), dim3(LG_GB), 0, st, B, Q, H1, (const float*)(ws + g.w_dtd),
+                          (const float*)(ws + g.w_td), ws + g.w_do3, r.key3, r.thr, r.dscale);
+}
+
+// behind the graph backward: the partial rows' two blocks, added in a fixed order
+int lg_graph_sums(const LgGeom& g, const LgRun& r, hipStream_t st) {
+    float* gr = r.a->grads;
+    RULGNN_TRY(rows_sum(r.ws + g.w_part, g.rows, g.CW, g.nA, gr + g.o_wn, st));
+    return rows_sum(r.ws + g.w_part + g.nA, g.rows, g.CW, g.nB, gr + g.o_fu, st);
+}
+
+// mode bit 0: forward, bit 1: backward (after a forward with the same args / workspace)
+int lg_run(const LgGeom& g, const rulgnn_logo_args* a, int mode, hipStream_t st) {
+    if (a->workspace_bytes < g.total_bytes) return RULGNN_EWORKSPACE;
+    if (g.B == 0) return RULGNN_OK;
+    const LgRun r = lg_run_of(a);
+    float* ws = r.ws;
+    const int64_t B = g.B;
     if (mode & 1) {
         const auto graph_fwd = g.ns > 0 ? lg_graph_fwd<true> : lg_graph_fwd<false>;
         RULGNN_TRY(allow_dynamic_lds(graph_fwd, g.lds_fwd));
-        RULGNN_TRY(launch_checked(graph_fwd, dim3((unsigned)(B > 8192 ? 8192 : B)), dim3(LG_GB), g.lds_fwd, st, g, a->x, prm, ws + g.w_hg, ws + g.w_glpart));
+        RULGNN_TRY(launch_checked(graph_fwd, dim3((unsigned)(B > 8192 ? 8192 : B)), dim3(LG_GB), g.lds_fwd, st, g, a->x, r.prm, ws + g.w_hg, ws + g.w_glpart));
         for (int l = 0; l < 3; ++l) {
             rulgnn_bilstm_shape ls;
             rulgnn_bilstm_args la;
-            lstm_args(l, &ls, &la);
+            lg_lstm_args(g, r, l, false, &ls, &la);
             RULGNN_TRY(bilstm_forward(&ls, &la, st, 2));
-            if (l == 1 && drop) RULGNN_TRY(launch_checked(lg_drop_kernel, dim3(lg_blocks(QB * H2)), dim3(LG_GB), 0, st, QB * H2, ws + g.w_o2, key2, dc.thr, dscale));
+            if (l == 1) RULGNN_TRY(lg_mid_drop(g, r, ws + g.w_o2, st));
         }
-        RULGNN_TRY(launch_checked(lg_close_kernel<false>, dim3(lg_blocks(QB * H1)), dim3(LG_GB), 0, st, B, Q, H1, (const float*)(ws + g.w_o3), (const float*)nullptr,
-                                  ws + g.w_td, key3, dc.thr, dscale));
-        // pre1 [B][16] = td [B][Q 3h] fc1^T: a few tiles over k = Q 3h, in fixed slices
-        RULGNN_TRY(sgemm_splitk(ws + g.w_td, K1, 1, prm + g.o_f1w, K1, 1, ws + g.w_pre1, LG_F1, (int)B, LG_F1, K1, false, ws + g.w_split, st));
-        RULGNN_TRY(launch_checked(lg_head_kernel, dim3(lg_blocks(B, 4096)), dim3(LG_GB), 0, st, g, prm, ws + g.w_pre1, ws + g.w_a2, a->y, a->pred, ws + g.w_sq,
-                                  ws + g.w_dpred, 1.0f / (float)gb));
-        RULGNN_TRY(launch_checked(lg_loss_kernel, dim3(1), dim3(LG_GB), 0, st, B, cnt, a->theta, a->gamma, (const float*)(ws + g.w_glpart),
-                                  a->y ? (const float*)(ws + g.w_sq) : (const float*)nullptr, ws + g.w_gl, a->loss_gl, a->loss));
+        RULGNN_TRY(lg_head_fwd(g, r, st));
     }
     if (mode & 2) {
         if (!a->grads) return RULGNN_EINVAL;
-        float* gr = a->grads;
-        RULGNN_TRY(launch_checked(lg_head_bwd_kernel, dim3(lg_blocks(B, 4096)), dim3(LG_GB), 0, st, g, prm, (const float*)(ws + g.w_pre1), (const float*)(ws + g.w_a2),
-                                  dpred, ws + g.w_prod, ws + g.w_dpre1));
-        // [g fc1.bias .. g cls.bias] = the samples' rows in order (contiguous in the parameter layout)
-        RULGNN_TRY(rows_sum(ws + g.w_prod, (int)B, LG_HEADROW, LG_HEADROW, gr + g.o_f1b, st));
-        // g fc1.weight [16][Q 3h] = dpre1^T td (k = the batch, one fixed-order product); dtd = dpre1 fc1
-        RULGNN_TRY(sgemm(ws + g.w_dpre1, 1, LG_F1, ws + g.w_td, 1, K1, gr + g.o_f1w, K1, LG_F1, K1, (int)B, false, st));
-        RULGNN_TRY(sgemm(ws + g.w_dpre1, LG_F1, 1, prm + g.o_f1w, 1, K1, ws + g.w_dtd, K1, (int)B, K1, LG_F1, false, st));
-        RULGNN_TRY(launch_checked(lg_close_kernel<true>, dim3(lg_blocks(QB * H1)), dim3(LG_GB), 0, st, B, Q, H1, (const float*)(ws + g.w_dtd),
-                                  (const float*)(ws + g.w_td), ws + g.w_do3, key3, dc.thr, dscale));
+        RULGNN_TRY(lg_head_bwd(g, r, st));
         for (int l = 2; l >= 0; --l) {
-            const LgLstm& k = g.lstm[l];
             rulgnn_bilstm_shape ls;
             rulgnn_bilstm_args la;
-            lstm_args(l, &ls, &la);
-            la.dout = ldout[l];
-            la.dx = ldx[l];
-            for (int d = 0; d < 2; ++d) {
-                la.dw_ih[d] = gr + k.o_wih[d]; la.dw_hh[d] = gr + k.o_whh[d]; la.db_ih[d] = gr + k.o_bih[d]; la.db_hh[d] = gr + k.o_bhh[d];
-            }
+            lg_lstm_args(g, r, l, true, &ls, &la);
             RULGNN_TRY(bilstm_backward(&ls, &la, st, 2));
-            if (l == 2 && drop) RULGNN_TRY(launch_checked(lg_drop_kernel, dim3(lg_blocks(QB * H2)), dim3(LG_GB), 0, st, QB * H2, ws + g.w_do2, key2, dc.thr, dscale));
+            if (l == 2) RULGNN_TRY(lg_mid_drop(g, r, ws + g.w_do2, st));
         }
         const auto graph_bwd = g.ns > 0 ? lg_graph_bwd<true> : lg_graph_bwd<false>;
         RULGNN_TRY(allow_dynamic_lds(graph_bwd, g.lds_bwd));
-        RULGNN_TRY(launch_checked(graph_bwd, dim3((unsigned)g.rows), dim3(LG_GB), g.lds_bwd, st, g, a->x, prm, (const float*)(ws + g.w_dhg),
+        RULGNN_TRY(launch_checked(graph_bwd, dim3((unsigned)g.rows), dim3(LG_GB), g.lds_bwd, st, g, a->x, r.prm, (const float*)(ws + g.w_dhg),
                                   (const float*)(ws + g.w_gl), a->theta, a->gamma, ws + g.w_part));
-        RULGNN_TRY(rows_sum(ws + g.w_part, g.rows, g.CW, g.nA, gr + g.o_wn, st));
-        RULGNN_TRY(rows_sum(ws + g.w_part + g.nA, g.rows, g.CW, g.nB, gr + g.o_fu, st));
+        RULGNN_TRY(lg_graph_sums(g, r, st));
     }
     return RULGNN_OK;
 }
 
+// The fused step (mode 3) of `n` runs of one LOGO shape: the graph forward, each layer's recurrences (bilstm_forward_group /
+// bilstm_backward_group) and the graph backward are one grouped launch each for all runs; the dropout passes, the head and the sums
+// follow per run in run order, with lg_run's arguments.  The graph backward's grid x stays LgGeom::rows, which fixes each run's
+// summation order.  The entry has checked every group.
+int lg_run_group(const LgGeom& g, const rulgnn_logo_args* groups, int n, hipStream_t st) {
+    if (n < 1 || n > STEP_MAX_GROUPS || g.ns > 0) return RULGNN_EINVAL;
+    for (int i = 0; i < n; ++i) {
+        if (groups[i].workspace_bytes < g.total_bytes) return RULGNN_EWORKSPACE;
+        if (!groups[i].grads) return RULGNN_EINVAL;
+    }
+    if (g.B == 0) return RULGNN_OK;
+    LgRun runs[STEP_MAX_GROUPS];
+    LgGroupTable tab{};
+    for (int i = 0; i < n; ++i) {
+        const LgRun& r = runs[i] = lg_run_of(&groups[i]);
+        float* ws = r.ws;
+        tab.grp[i] = LgGroup{groups[i].x, r.prm, ws + g.w_hg, ws + g.w_glpart, ws + g.w_dhg, ws + g.w_gl, ws + g.w_part, groups[i].theta, groups[i].gamma};
+    }
+    const int64_t B = g.B;
+    const unsigned ny = (unsigned)n;
+    rulgnn_bilstm_shape ls;
+    rulgnn_bilstm_args la[STEP_MAX_GROUPS];
+    RULGNN_TRY(allow_dynamic_lds(lg_graph_fwd_group, g.lds_fwd));
+    RULGNN_TRY(launch_checked(lg_graph_fwd_group, dim3((unsigned)(B > 8192 ? 8192 : B), ny), dim3(LG_GB), g.lds_fwd, st, g, tab));
+    for (int l = 0; l < 3; ++l) {
+        for (int i = 0; i < n; ++i) lg_lstm_args(g, runs[i], l, false, &ls, &la[i]);
+        RULGNN_TRY(bilstm_forward_group(&ls, la, n, st));
+        if (l == 1)
+            for (int i = 0; i < n; ++i) RULGNN_TRY(lg_mid_drop(g, runs[i], runs[i].ws + g.w_o2, st));
+    }
+    for (int i = 0; i < n; ++i) RULGNN_TRY(lg_head_fwd(g, runs[i], st));
+    for (int i = 0; i < n; ++i) RULGNN_TRY(lg_head_bwd(g, runs[i], st));
+    for (int l = 2; l >= 0; --l) {
+        for (int i = 0; i < n; ++i) lg_lstm_args(g, runs[i], l, true, &ls, &la[i]);
+        RULGNN_TRY(bilstm_backward_group(&ls, la, n, st));
+        if (l == 2)
+            for (int i = 0; i < n; ++i) RULGNN_TRY(lg_mid_drop(g, runs[i], runs[i].ws + g.w_do2, st));
+    }
+    RULGNN_TRY(allow_dynamic_lds(lg_graph_bwd_group, g.lds_bwd));
+    RULGNN_TRY(launch_checked(lg_graph_bwd_group, dim3((unsigned)g.rows, ny), dim3(LG_GB), g.lds_bwd, st, g, tab));
+    for (int i = 0; i < n; ++i) RULGNN_TRY(lg_graph_sums(g, runs[i], st));
+    return RULGNN_OK;
+}
+
 }  // namespace
+
+int Logo::run_group(const Shape* s, const Args* groups, int n, hipStream_t st) {
+    LgGeom g;
+    RULGNN_TRY(lg_geometry(s, &g));
+    return lg_run_group(g, groups, n, st);
+}
 
 }  // namespace rulgnn

@@ -118,6 +118,30 @@ static int step_fwdbwd(const typename F::Shape* shape, const typename F::Args* a
     const int64_t first = F::adam_first(shape);
     return adam_tail(opt, args->grads, first, F::param_count(shape) - first - F::adam_frozen_tail(shape), st);
 }
+// The fused call of `n` runs of one shape (rulgnn_<family>_fwdbwd_group_f32): groups[i] is run i's args, opts null or one block per run.
+// Every group passes what step_fwdbwd checks and the workspace size run() would check, and no two groups may write the same buffers,
+// all before F::run_group's first launch; Adam follows run by run.
+template <typename F>
+static int step_fwdbwd_group(const typename F::Shape* shape, const typename F::Args* groups, const rulgnn_adam_args* opts, int32_t n,
+                             void* stream) {
+    if (!shape || !groups || n < 1) return RULGNN_EINVAL;
+    if (n > STEP_MAX_GROUPS) return RULGNN_EUNSUPPORTED;
+    for (int32_t i = 0; i < n; ++i) {
+        const typename F::Args* a = &groups[i];
+        RULGNN_TRY(step_check<F>(shape, a, true, true));
+        if (a->dpred || (!a->y && shape->batch > 0)) return RULGNN_EINVAL;
+        if (a->workspace_bytes < F::workspace_bytes(shape)) return RULGNN_EWORKSPACE;
+        if (opts) RULGNN_TRY(check_adam(&opts[i], a->params));
+        for (int32_t j = 0; j < i; ++j)
+            if (groups[j].workspace == a->workspace || groups[j].grads == a->grads || groups[j].params == a->params) return RULGNN_EINVAL;
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    RULGNN_TRY(F::run_group(shape, groups, n, st));
+    if (!opts) return RULGNN_OK;
+    const int64_t first = F::adam_first(shape), count = F::param_count(shape) - first - F::adam_frozen_tail(shape);
+    for (int32_t i = 0; i < n; ++i) RULGNN_TRY(adam_tail(&opts[i], groups[i].grads, first, count, st));
+    return RULGNN_OK;
+}
 }  // extern "C++"
 
 // The extern "C" entries of step family F under the prefix rulgnn_<name>_ (include/rulgnn.h declares each): the two queries and the
@@ -134,6 +158,13 @@ static int step_fwdbwd(const typename F::Shape* shape, const typename F::Args* a
 #define STEP_FAMILY_ENTRIES_TAPS(name, F) \
     STEP_FAMILY_ENTRIES(name, F)          \
     int64_t rulgnn_##name##_tap_offset(const F::Shape* shape, int32_t which) { return F::tap_offset(shape, which); }
+// The grouped fused step of a family whose description has run_group.
+#define STEP_FAMILY_GROUP_ENTRY(name, F)                                                                                                    \
+    int rulgnn_##name##_fwdbwd_group_f32(const F::Shape* shape, const F::Args* groups, const rulgnn_adam_args* opts, int32_t num_groups,    \
+                                         void* stream) {                                                                                    \
+        return step_fwdbwd_group<F>(shape, groups, opts, num_groups, stream);                                                               \
+    }
+int32_t rulgnn_step_max_groups(void) { return STEP_MAX_GROUPS; }
 
 // Path selection.  The fused row-mapped kernels cover num_patch <= 64 as long as one wavefront's input tile fits its LDS staging area,
 // every launch form a call may reach fits the 160 KB of LDS a workgroup can have (stgcn_host.hpp: the *_lds_bytes functions the
@@ -973,6 +1004,7 @@ int Logo::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
 }
 
 STEP_FAMILY_ENTRIES_TAPS(logo, Logo)
+STEP_FAMILY_GROUP_ENTRY(logo, Logo)
 
 // ---- LOGO_bearing ----------------------------------------------------------------------------------
 int Logob::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
@@ -1008,6 +1040,7 @@ int Dvgtformer::check_args(const Shape* shape, const Args* a, bool, bool bwd) {
     return check_dropout_step_args(a, shape->batch, bwd, 0.0);
 }
 STEP_FAMILY_ENTRIES_TAPS(dvgtformer, Dvgtformer)
+STEP_FAMILY_GROUP_ENTRY(dvgtformer, Dvgtformer)
 
 // (a draw per attention entry)
 int Gdagdl::check_args(const Shape* shape, const Args* a, bool, bool bwd) {

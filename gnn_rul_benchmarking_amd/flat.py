@@ -228,18 +228,23 @@ class FlatModule(nn.Module):
             self._bufs[key] = ent
         return ent
 
-    def _adam_args(self, optimizer, bn=None):
-        """``byref(rulgnn_adam_args)`` for a fused step with ``optimizer`` (optim.FusedAdam over this model), advancing its
-        step count; None when the call should only produce gradients."""
+    def _adam_block(self, optimizer, bn=None):
+        """The ``rulgnn_adam_args`` of a fused step with ``optimizer`` (optim.FusedAdam over this model), advancing its step count;
+        None when the call should only produce gradients."""
         if optimizer is None:
             return None
         m, v = optimizer._state_buffers()
         optimizer._steps += 1
         g = optimizer.param_groups[0]
-        return C.byref(_lib.AdamArgs(self._flat.data_ptr(), m.data_ptr(), v.data_ptr(), bn.data_ptr() if bn is not None else None,
-                                     optimizer._steps, float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
-                                     float(g["weight_decay"]), 0.1,
-                                     self._step_state.data_ptr() if self._step_state is not None else None))
+        return _lib.AdamArgs(self._flat.data_ptr(), m.data_ptr(), v.data_ptr(), bn.data_ptr() if bn is not None else None,
+                             optimizer._steps, float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]),
+                             float(g["weight_decay"]), 0.1,
+                             self._step_state.data_ptr() if self._step_state is not None else None)
+
+    def _adam_args(self, optimizer, bn=None):
+        """``byref`` of ``_adam_block``'s struct, or None."""
+        block = self._adam_block(optimizer, bn=bn)
+        return None if block is None else C.byref(block)
 
     def _require_device(self, x):
         """The input guard of every family: the model runs on its HIP kernels, on the device of its parameters."""
@@ -301,11 +306,18 @@ class FlatModule(nn.Module):
 
     def _fused_step(self, x, yv, optimizer, global_batch, *state, bn=None, **fields):
         """One ``fwdbwd`` call (forward + MSE + backward, + Adam with ``optimizer``) on checked inputs (``_step_inputs``)."""
+        shp, a, opt = self._fused_step_args(x, yv, optimizer, global_batch, *state, bn=bn, **fields)
+        self._call("fwdbwd", shp, a, None if opt is None else C.byref(opt))
+        return self._pred_buf, self._grad_flat[self._count]
+
+    def _fused_step_args(self, x, yv, optimizer, global_batch, *state, bn=None, **fields):
+        """What one ``fwdbwd`` call takes, everything short of the call itself: ``(shape, args, rulgnn_adam_args or None)``.  The
+        tape is marked, the batch's workspace entry becomes current and the optimizer's step count advances, as in ``_fused_step``
+        (runs.py hands several models' triples to one grouped call)."""
         shp = self._shape(x.size(0))
         self._tape.mark(x.size(0))
         a = self._args(shp, x, *state, y=yv, global_batch=global_batch, **fields)
-        self._call("fwdbwd", shp, a, self._adam_args(optimizer, bn=bn))
-        return self._pred_buf, self._grad_flat[self._count]
+        return shp, a, self._adam_block(optimizer, bn=bn)
 
     def fused_mse_step(self, x, y, optimizer=None, global_batch=None):
         """forward + MSE + backward (+ Adam when ``optimizer`` is a FusedAdam over this model) in one C call; fills ``self.bucket`` =
@@ -411,6 +423,13 @@ class DropoutStepModule(FlatModule):
         x, yv = self._step_inputs(x, y)
         vars(self)["_step"] = step = self._step + 1          # (past nn.Module.__setattr__, as in FlatModule._args)
         return self._fused_step(x, yv, optimizer, global_batch, True, step, sample_offset=sample_offset, **fields)
+
+    def fused_mse_step_args(self, x, y, optimizer=None, **fields):
+        """What ``fused_mse_step(x, y, optimizer, **fields)`` would hand to its C call, short of calling: ``(shape, args,
+        rulgnn_adam_args or None, the checked tensors the structs point to)``; the step counters advance as there."""
+        x, yv = self._step_inputs(x, y)
+        vars(self)["_step"] = step = self._step + 1
+        return self._fused_step_args(x, yv, optimizer, None, True, step, **fields) + ((x, yv),)
 
     def _forward_outputs(self, x):
         """Every output of one forward; dropout follows ``self.training`` (a training forward advances the step), through autograd when

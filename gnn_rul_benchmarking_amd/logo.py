@@ -147,6 +147,13 @@ class LOGO_model(FlatModule):
         self._step += 1
         return self._fused_step(x, yv, optimizer, global_batch, True, self._step, theta, gamma)
 
+    def fused_mse_step_args(self, x, y, optimizer=None, theta=0.0, gamma=1.0):
+        """What ``fused_mse_step`` would hand to its C call, short of calling: ``(shape, args, rulgnn_adam_args or None, the checked
+        tensors the structs point to)``; the step counters advance as there (runs.LOGO_runs: several runs in one grouped call)."""
+        x, yv = self._step_inputs(x, y)
+        self._step += 1
+        return self._fused_step_args(x, yv, optimizer, None, True, self._step, theta, gamma) + ((x, yv),)
+
     # ---- nn.Module surface -----------------------------------------------------------------------------
     def forward(self, X, GL=False, gamma=1):
         x = self._check_input(X)

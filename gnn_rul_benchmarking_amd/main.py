@@ -29,7 +29,8 @@ def build_parser():
     p.add_argument('--window', default=None, type=int, help='C-MAPSS window length (= ST_GCN patch_size); data decides')
     p.add_argument('--num_epochs', default=None, type=int, help='override the table value (81)')
     p.add_argument('--concurrent_runs', default=1, type=int,
-                   help='step this many of the --num_runs runs together on the device (HAGCN only, single process, at most 8); 1: one after the other')
+                   help='step this many of the --num_runs runs together on the device (HAGCN, DVGTformer and LOGO; single process, at most 8); '
+                        '1: one after the other')
     return p
 
 

@@ -1370,6 +1370,21 @@ int rulgnn_logo_backward_f32(const rulgnn_logo_shape *shape, const rulgnn_logo_a
 /* LOGO.update body (algorithms.py:125-136); with `opt` also Adam on the flat parameter buffer. */
 int rulgnn_logo_fwdbwd_f32(const rulgnn_logo_shape *shape, const rulgnn_logo_args *args, const rulgnn_adam_args *opt, void *stream);
 
+/* Grouped fused steps: `num_groups` independent training runs of ONE shape (so of one batch size) advance through one call; the kernels
+ * that dominate the step carry the run index in blockIdx.y, so the runs' workgroups share the device by construction of the grid.
+ * `groups` is a HOST array of the family's argument struct, groups[i] being run i's ordinary arguments (its own x, y, parameters,
+ * gradients, outputs, workspace of at least rulgnn_<family>_workspace_bytes(shape), seed and step); `opts` is NULL (gradients only) or a
+ * HOST array of one Adam block per group.  A run's results are the single rulgnn_<family>_fwdbwd_f32 call's on the same arguments, bit
+ * for bit: the per-sample arithmetic, the partial-row count and every reduction order are the single call's; workspace layout, queries
+ * and tap offsets are unchanged.  Every group is checked before the first launch: null structs or num_groups < 1 RULGNN_EINVAL,
+ * num_groups > rulgnn_step_max_groups() (8) RULGNN_EUNSUPPORTED, for every group whatever the single entry refuses with its code
+ * (a workspace one byte short: RULGNN_EWORKSPACE), two groups sharing a workspace, grads or params pointer RULGNN_EINVAL. */
+int32_t rulgnn_step_max_groups(void);
+/* LOGO: the graph stage forward and backward and the six recurrences of the three Bi-LSTM layers are grouped launches; the dropout
+ * passes, the head, the loss and Adam run per group, in group order, on the same stream. */
+int rulgnn_logo_fwdbwd_group_f32(const rulgnn_logo_shape *shape, const rulgnn_logo_args *groups, const rulgnn_adam_args *opts,
+                                 int32_t num_groups, void *stream);
+
 /* ------------------------------------------------------------------------------------------------
  * LOGO_bearing path (reference models/LOGO_bearing/Model.py:263-347, algorithms/algorithms.py:601-629; wired to the bearing datasets
  * PHM2012 and XJTU_SY, configs/hparams.py:228,244,... and :339,358,...): LOGO behind an STFT front end.
@@ -1520,6 +1535,11 @@ int rulgnn_dvgtformer_backward_f32(const rulgnn_dvgtformer_shape *shape, const r
 /* DVGTformer.update body (algorithms.py:341-351); with `opt` also Adam on the flat parameter buffer. */
 int rulgnn_dvgtformer_fwdbwd_f32(const rulgnn_dvgtformer_shape *shape, const rulgnn_dvgtformer_args *args, const rulgnn_adam_args *opt,
                                  void *stream);
+/* The grouped fused step (contract: rulgnn_step_max_groups above): fold, encoder forward, encoder backward and unfold are grouped
+ * launches, grid (x, num_groups); the head (three SGEMMs and its small kernels), the row and loss sums and Adam run per group, in
+ * group order, on the same stream. */
+int rulgnn_dvgtformer_fwdbwd_group_f32(const rulgnn_dvgtformer_shape *shape, const rulgnn_dvgtformer_args *groups,
+                                       const rulgnn_adam_args *opts, int32_t num_groups, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * GDAGDL path (reference models/GDAGDL/Model.py, algorithms/algorithms.py:519-544; wired to the bearing datasets PHM2012 and XJTU_SY).
