@@ -38,6 +38,15 @@ extern "C" {
 #define RULGNN_EALIGN       -5   /* pointer not 4-byte aligned */
 #define RULGNN_ECALLBACK    -6   /* a caller-supplied callback (rulgnn_allreduce_f64_fn) returned non-zero */
 
+/* Workspaces.  A workspace need not be initialised and need not be preserved between calls.  The only state a call may rely on is what
+ * the forward of the same arguments left for its backward.  (Whatever a call reads it has written itself: a workspace that last held
+ * another batch size's layout, NaN or another model's activations gives the same result as a zeroed one.)
+ * ST_GCN's training workspace has two documented exceptions, both in the step scratch behind its BatchNorm cells:
+ *   - the zero-cells fast path: a step flagged RULGNN_TRAIN_WS_CLEAN (below) relies on the cleared reduction cells and the clean
+ *     token the matrix-core step before it left; without the token it ends like a step the range guard rejected, never on stale sums;
+ *   - the sticky guard counter (rulgnn_stgcn_train_guard_counter_offset): only ever added to by the kernels, zeroed by the caller when
+ *     it allocates the workspace. */
+
 #define RULGNN_NUM_STATS 10      /* statistics per patch == graph nodes == TCN channels */
 
 typedef struct rulgnn_stgcn_shape {

@@ -2,7 +2,9 @@
 AGCN_TF and GRU_CM, an older lineage, take grads_of, the harness run and the CPU checks): the leaf helpers, the element-wise gradient gate loop, the forward gate, the twin-model
 Adam procedure, the training curve, the reference-harness run and the coverage refusals, each stated once.  A plain module: no
 fixtures, no plugins.  Every tolerance, rtol, ladder and seed is the calling family's and is passed in: nothing here has a default for
-one.  tests/test_family_kit_cpu.py plants faults into the numpy parts (check_grads, check_forward, assert_harness, adam_step_check)."""
+one.  tests/test_family_kit_cpu.py plants faults into the numpy parts (check_grads, check_forward, assert_harness, adam_step_check).
+Section 9, the stale-workspace check, serves every FlatModule family (tests/test_stale_workspace_gpu.py; its faults:
+tests/test_stale_workspace_cpu.py)."""
 import argparse
 import json
 import os
@@ -410,3 +412,173 @@ def hparams_rows_check(method, npz, present, absent, absent_is_all=False):
         h = row(key)
         assert method not in h.alg_hparams and method not in h.train_params, key
     return rows
+
+
+# ---- 9. a call on a stale workspace ------------------------------------------------------------------------------------------------------------
+# A workspace need not be initialised and need not be preserved between calls (include/rulgnn.h).  ``stale_run`` makes one fresh model and
+# one fresh optimizer, primes the workspaces, puts one of STALE_FILLS into the workspace of the batch immediately before every call and
+# returns everything the call produced; ``stale_compare`` holds a fill's run to the "zero" run.  Nothing here imports the package: the
+# model only has to look like a FlatModule (tests/test_stale_workspace_cpu.py plants faults into a numpy one).
+STALE_FILLS = ("zero", "nan", "other-batch", "same-batch")
+STALE_CALLS = ("step", "eval", "autograd")
+STALE_B_BIG = 37
+QUIET_NAN = 0x7FC00000
+
+
+class StaleCase(NamedTuple):
+    """One family for the stale-workspace check.  ``ready()``: a fresh model from the family's state dict, in train mode, dropout at the
+    family's own rate, a fixed ``_seed``;  ``make_opt(model)``: a fresh optimizer over it;  ``draw(B, seed)``: (x, y) of batch ``B`` on the
+    model's device, the same for the same arguments;  ``other_state(model)``: another state dict for the same model;  ``step_kw``: what
+    the family's ``fused_mse_step`` takes beyond (x, y, optimizer);  ``bar``: None for equal bit patterns, else the largest |difference|
+    relative to the tensor's largest magnitude."""
+    ready: Callable
+    make_opt: Callable
+    draw: Callable
+    other_state: Callable
+    step_kw: dict
+    bar: object
+
+
+def _host(t):
+    return t.detach().cpu().numpy().copy()
+
+
+def _words(ws):
+    return ws.view(torch.int32)
+
+
+def _state_of(m, opt):
+    """Everything a call may move, as host arrays: parameters, moments, the state dict's buffers, the batch statistics, the counters."""
+    out = {"flat_params": _host(m.flat_params)}
+    sd = opt.state_dict()
+    out["exp_avg"], out["exp_avg_sq"], out["adam_steps"] = _host(sd["exp_avg"]), _host(sd["exp_avg_sq"]), np.asarray(int(sd["step"]))
+    for k, v in m.state_dict().items():
+        out["sd:" + k] = _host(v)
+    if getattr(m, "_bn_batch", None) is not None:
+        out["_bn_batch"] = _host(m._bn_batch)
+    out["_step"] = np.asarray(int(getattr(m, "_step", 0)))
+    return out
+
+
+def _same_state(a, b):
+    return a.keys() == b.keys() and all(a[k].shape == b[k].shape and a[k].tobytes() == b[k].tobytes() for k in a)
+
+
+def _load(m, sd):
+    m.state_dict()                               # (brings pending BatchNorm counters up to date before they are overwritten)
+    m.load_state_dict({k: v.clone() for k, v in sd.items()}, strict=True)
+
+
+def _stale_fill(m, B, fill, source):
+    """Put ``fill`` into the workspace of batch ``B`` and return how many of its fp32 words are non-zero behind it."""
+    ws = m._bufs[B][0]
+    assert ws.numel() % 256 == 0, "workspace sizes are 256-byte multiples: no partial word"
+    w = _words(ws)
+    if fill == "zero":
+        ws.zero_()
+    elif fill == "nan":
+        w.fill_(QUIET_NAN)
+        probe = w[[0, w.numel() // 2, w.numel() - 1]].tolist()
+        assert probe == [QUIET_NAN] * 3, probe
+    elif fill == "other-batch":
+        n = min(ws.numel(), source.numel())
+        ws[:n].copy_(source[:n])
+        at = [0, n // 8, n // 4 - 1]
+        assert w[at].tolist() == _words(source[:n])[at].tolist()
+    else:
+        assert fill == "same-batch" and source is None               # what the step before left: no explicit fill
+    return int(torch.count_nonzero(w))
+
+
+def stale_run(case, B, fill, call):
+    """One fresh model and optimizer of ``case`` through ``call`` at batch ``B`` with ``fill`` in the workspace before every launch of it.
+    Returns {name: host array} of everything the call produced, "filled:<i>" among it: the non-zero words of the workspace before call i."""
+    assert fill in STALE_FILLS and call in STALE_CALLS
+    m = case.ready()
+    opt = case.make_opt(m)
+    x, y = case.draw(B, B)
+    m._pin_bufs = True                                                  # nothing is evicted: the workspace filled is the one the call uses
+    before = _state_of(m, opt)
+    m.eval()
+    with torch.no_grad():
+        for b in (B, STALE_B_BIG) if fill == "other-batch" else (B,):   # the workspace of a batch size exists only after a call at it
+            m(case.draw(b, 1000 + b)[0])
+    m.train()
+    assert _same_state(before, _state_of(m, opt)), "priming moved the model or the optimizer"
+    source = None
+    if fill in ("other-batch", "same-batch"):                           # a training step on other data under another state dict
+        b = STALE_B_BIG if fill == "other-batch" else B
+        home, step = {k: v.clone() for k, v in m.state_dict().items()}, getattr(m, "_step", None)
+        _load(m, case.other_state(m))
+        xo, yo = case.draw(b, 2000 + b)
+        m.fused_mse_step(xo, yo, **case.step_kw)
+        _load(m, home)
+        if step is not None:
+            m._step = step
+        if getattr(m, "_bn_batch", None) is not None:
+            m._bn_batch.copy_(torch.from_numpy(before["_bn_batch"]))
+        m.bucket.zero_()
+        assert _same_state(before, _state_of(m, opt)), "the step that made the stale workspace left its mark outside it"
+        if fill == "other-batch":
+            source = m._bufs[b][0].clone()
+    out = {}
+
+    def collect(tag, **more):
+        for k, v in more.items():
+            out[f"{tag}:{k}"] = _host(v)
+        for k, v in _state_of(m, opt).items():
+            out[f"{tag}:{k}"] = v
+
+    if call == "step":
+        for i in (1, 2):                                                # the second starts from what the first left and from moved parameters
+            out[f"filled:{i}"] = np.asarray(_stale_fill(m, B, fill, source))
+            pred, loss = m.fused_mse_step(x, y, opt, **case.step_kw)
+            collect(f"step{i}", pred=pred, loss=loss, bucket=m.bucket[:m.num_live + 1])
+    elif call == "eval":
+        m.eval()
+        out["filled:1"] = np.asarray(_stale_fill(m, B, fill, source))
+        with torch.no_grad():
+            pred = m(x)
+        collect("eval", pred=pred)
+    else:
+        out["filled:1"] = np.asarray(_stale_fill(m, B, fill, source))   # before the forward only: the backward is entitled to its tape
+        pred = m(x)
+        loss = torch.nn.functional.mse_loss(pred, y.reshape(-1, 1))
+        loss.backward()
+        grads = [p.grad.reshape(-1) for p in m._named() if p.grad is not None]
+        collect("autograd", pred=pred, loss=loss, grad=torch.cat(grads), bucket=m.bucket[:m.num_live])
+    return out
+
+
+def stale_baseline_ok(base, call):
+    """The "zero" run can be trusted: its workspace held zeros, everything it produced is finite and its gradient is not all zero."""
+    for k, v in base.items():
+        if k.startswith("filled:"):
+            assert int(v) == 0, k
+        elif v.dtype.kind == "f":
+            assert np.isfinite(v).all(), k
+    if call != "eval":
+        for k in [k for k in base if k.endswith(":bucket") or k.endswith(":grad")]:
+            assert base[k].any(), f"{k} is all zero"
+
+
+def stale_compare(base, got, fill, bar):
+    """``got`` (the run under ``fill``) against ``base`` (the "zero" run), tensor by tensor: equal bit patterns where ``bar`` is None, else
+    finite and within ``bar`` of the tensor's largest magnitude (integer tensors always equal).  The fill must have taken."""
+    assert fill != "zero" and base.keys() == got.keys(), sorted(set(base) ^ set(got))
+    for k, want in base.items():
+        have = got[k]
+        if k.startswith("filled:"):
+            assert int(have) > 0, f"{k}: the {fill} fill left the workspace as the baseline's"
+            continue
+        assert have.shape == want.shape and have.dtype == want.dtype, k
+        if bar is None or want.dtype.kind != "f":
+            if have.tobytes() != want.tobytes():
+                a, b = have.astype(np.float64).reshape(-1), want.astype(np.float64).reshape(-1)
+                bad = np.flatnonzero(~((a == b) | (np.isnan(a) & np.isnan(b))))
+                raise AssertionError(f"{k} under the {fill} fill: {bad.size} of {a.size} elements differ from the zero fill's, first at "
+                                     f"{bad[:8].tolist()}: {a[bad[:4]].tolist()} against {b[bad[:4]].tolist()}")
+        else:
+            assert np.isfinite(have).all(), f"{k} under the {fill} fill is not finite"
+            err = rel_same_shape(have, want)
+            assert err <= bar, f"{k} under the {fill} fill: {err:.3e} of the tensor's largest magnitude, the bar is {bar:.1e}"
